@@ -17,9 +17,12 @@ Contract: `python bench.py --gpus N --steps K --warmup W`.  One rank per GPU.  U
 WORLD_SIZE in the environment) this process is one rank; without one and N > 1 it starts the N rank processes itself (fresh
 interpreters, before anything here touches a GPU) and waits for them.  W untimed steps, exactly K timed steps between
 barrier + synchronize, MAX over ranks; rank 0 prints ONE JSON line - the LAST line of stdout, compact (< 4 KB, scalars only:
-metric / value / config / roofline / stage_ms / cpu_baseline, and at N = 1 the metric's 2-D half - BASELINE configs[1], 10 steps run
-after the 3-D measurement - as value_2d / ms_per_step_2d / roofline_2d_frac / cpu_baseline_2d).  `--extra` additionally runs the secondary workloads and writes them,
-with the CPU legs' run lists, to gpurun_out/bench_extra.json; they are never part of the line.
+metric / value / unit / ms_per_step / dtype / config).  A plain run does nothing else; `--dump-outputs DIR` writes the samples of the
+last timed step to DIR/samples.npy (float32; inputs are seeded, so two builds can be compared output for output).
+`--full` adds what the headline does not need: roofline / stage_ms (one profiled step), cpu_baseline, and at N = 1 the metric's 2-D
+half - BASELINE configs[1], 10 steps run after the 3-D measurement - as value_2d / ms_per_step_2d / roofline_2d_frac / cpu_baseline_2d;
+their detail goes to --extra-out.  `--extra` additionally runs the secondary workloads and writes them, with the CPU legs' run lists,
+to --extra-out; they are never part of the line.
 """
 import argparse
 import json
@@ -64,7 +67,11 @@ def parse():
                    help="CPU oracle timed beside the GPU number (rank 0, N = 1): full = the SURVEY 8(d) protocol, median of 3 runs of the bounded sample + "
                         "an end-to-end reduced-grid chain as a check of the extrapolation (about 75 s of CPU work; the default) + the CPU legs of every "
                         "--extra workload, sample = ONE run of the bounded sample (about 15 s), none = skip")
-    p.add_argument("--no-2d", action="store_true", help="skip the second leg of the default run (BASELINE configs[1], the metric's 2-D half: "
+    p.add_argument("--full", action="store_true", help="besides the headline also measure the roofline and stage shares of the timed workload "
+                   "(one profiled step), the CPU baseline (--cpu-baseline) and, at N = 1, the 3-D workload's 2-D half (unless --no-2d); off by default")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps write the samples of the last timed step to DIR/samples.npy (float32, all ranks' pairs)")
+    p.add_argument("--no-2d", action="store_true", help="skip the second leg of a --full run (BASELINE configs[1], the metric's 2-D half: "
                    "10 steps after the 3-D measurement, reported as value_2d / ms_per_step_2d / roofline_2d_frac / cpu_baseline_2d)")
     p.add_argument("--no-cpu-baseline", action="store_true", help="same as --cpu-baseline none")
     p.add_argument("--extra", action="store_true", help="after the headline measurement also run the secondary workloads (the other BASELINE configs, the "
@@ -251,6 +258,21 @@ def timed_loop(wl, steps, warmup, dist):
     pool.shutdown()
     timed = [draw_s[k] for k in range(warmup, total) if k in draw_s]
     return secs, out, (sum(timed) / len(timed) if timed else 0.0)
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(path, arrays):
+    """`--dump-outputs`: what the timed path handed its caller in the last timed step, as <path>/<name>.npy in float32.  An array larger
+    than the byte budget keeps a fixed, seeded sample of its leading (pair) index, in order."""
+    os.makedirs(path, exist_ok=True)
+    for name, t in arrays.items():
+        x = t.detach().float().cpu().numpy()
+        n_max = max(1, DUMP_LIMIT_BYTES // len(arrays) // max(1, x[:1].nbytes))
+        if x.shape[0] > n_max:
+            x = x[np.sort(np.random.default_rng(0).choice(x.shape[0], n_max, replace=False))]
+        np.save(os.path.join(path, name + ".npy"), x)
 
 
 # ---------------------------------------------------------------------------------------------------------------- roofline
@@ -744,7 +766,7 @@ def main():
     wl = Workload(a.workload, pairs, dev, rank, world, a.contraction)
 
     engine.prof_enable(False)
-    secs, _, draw_secs = timed_loop(wl, a.steps, a.warmup, dist)
+    secs, out, draw_secs = timed_loop(wl, a.steps, a.warmup, dist)
     if dist is not None:
         tmax = torch.tensor([secs], device=dev if a.backend == "nccl" else "cpu")
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
@@ -752,13 +774,15 @@ def main():
     if rank != 0:
         dist.destroy_process_group()
         return
-    roof, shares = stage_profile(wl, secs / a.steps, a.contraction)
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs, {"samples": out})
+    roof, shares = stage_profile(wl, secs / a.steps, a.contraction) if a.full else (None, None)
     meas = {"samples": wl.B * pairs * world * a.steps, "secs": secs, "world": world, "steps": a.steps, "warmup": a.warmup, "contraction": a.contraction,
             "workload": a.workload, "pairs": pairs, "B": wl.B, "S": wl.S, "rows": wl.rows, "n_obj": wl.n_obj, "draw_secs": draw_secs,
             "gloo": world > 1 and a.backend == "gloo", "unet_form": "%s%s" % ((lambda f: (f[0], " batched" if f[1] else ""))(wl.net.effective_form(wl.B * pairs, wl.L)))}
     cpu, detail = None, {}
     second = None
-    if world == 1 and a.workload == "3d" and not a.no_2d and not a.force_group:
+    if a.full and world == 1 and a.workload == "3d" and not a.no_2d and not a.force_group:
         # the metric's 2-D half (BASELINE configs[1]) in the same line: 10 timed steps after 2 warm-up steps, its trunk's roofline fraction
         # from HIP events, and (below, with the CPU legs) the oracle on a bounded sample of it
         w2 = Workload("2d", DEFAULT_PAIRS["2d"], dev, rank, world, a.contraction)
@@ -774,7 +798,7 @@ def main():
         hv2 = host_view(w2)
         del w2
         torch.cuda.empty_cache()
-    if world == 1 and a.cpu_baseline != "none":
+    if a.full and world == 1 and a.cpu_baseline != "none":
         cpu, detail["cpu_baseline"] = cpu_baseline(host_view(wl), full=a.cpu_baseline == "full")
         if second is not None:
             c2, detail["cpu_baseline_2d"] = cpu_baseline(hv2, full=False, median=a.cpu_baseline == "full")

@@ -251,7 +251,7 @@ def test_bench_spawns_ranks_itself(dev):
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "0", "--pairs", "2", "--backend", "gloo",
-                        "--no-cpu-baseline", "--no-extra"], capture_output=True, text=True, env=env, timeout=600)
+                        "--full", "--no-cpu-baseline", "--no-extra"], capture_output=True, text=True, env=env, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     out = r.stdout.strip().splitlines()
     # only rank 0 writes stdout: ONE JSON line, and it is the last line (gloo itself may print a connection note before it)
@@ -270,6 +270,27 @@ def test_bench_spawns_ranks_itself(dev):
     if torch.cuda.device_count() < 2:
         r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "0"], capture_output=True, text=True, env=env, timeout=120)
         assert r.returncode != 0 and "GPU" in r.stderr
+
+
+def test_bench_plain_run_dumps_its_outputs(dev, tmp_path):
+    """A plain `bench.py --gpus 1 --steps K --warmup W` reports the headline alone (no roofline, CPU baseline or 2-D leg) with exactly K timed
+    steps; `--dump-outputs` writes the last timed step's samples, and two runs with the same arguments write the same samples."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
+    got = []
+    for run in ("a", "b"):
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--pairs", "2",
+                            "--dump-outputs", str(tmp_path / run)], capture_output=True, text=True, env=env, timeout=600)
+        assert r.returncode == 0, r.stderr[-2000:]
+        line = json.loads(r.stdout.strip().splitlines()[-1])
+        assert line["steps"] == 2 and line["ms_per_step"] > 0 and line["value"] > 0 and line["higher_is_better"] is True
+        assert not {"roofline", "stage_ms", "cpu_baseline", "value_2d"} & set(line), sorted(line)
+        got.append(np.load(tmp_path / run / "samples.npy"))
+    assert got[0].dtype == np.float32 and got[0].shape == (2, 32, 42, 1) and np.isfinite(got[0]).all()
+    assert np.array_equal(got[0], got[1])
 
 
 def test_sharded_cli_matches_single_process(dev, tmp_path):

@@ -93,7 +93,7 @@ def test_bench_rank_body_on_rccl_world_size_1():
     env = dict(os.environ, MASTER_ADDR="127.0.0.1", MASTER_PORT="29533", RANK="0", LOCAL_RANK="0", WORLD_SIZE="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     vals = {}
     for tag, extra in (("plain", []), ("rccl", ["--force-group"])):
-        r = subprocess.run([sys.executable, "bench.py", "--gpus", "1", "--steps", "10", "--warmup", "2", "--no-cpu-baseline", "--no-extra", "--no-2d"] + extra, cwd=root, env=env,
+        r = subprocess.run([sys.executable, "bench.py", "--gpus", "1", "--steps", "10", "--warmup", "2", "--full", "--no-cpu-baseline", "--no-extra", "--no-2d"] + extra, cwd=root, env=env,
                            capture_output=True, text=True, timeout=900)
         assert r.returncode == 0, r.stderr[-3000:]
         last = r.stdout.strip().splitlines()[-1]                      # what a tail-capturing driver keeps

@@ -309,6 +309,29 @@ def test_bench_headline_is_compact_and_parses():
             assert len(json.dumps(bench.headline(dict(m, workload=w, contraction=c), roof, stages, cpu))) < 4096
 
 
+def test_bench_dump_outputs_and_plain_defaults(tmp_path, monkeypatch):
+    """`--dump-outputs`: float32 .npy files of what the timed path returned; beyond the byte budget a fixed, seeded sample of the pairs (in
+    order, the same on every run).  A plain command line is lean: --full (roofline, CPU baseline, 2-D leg) is off unless asked for."""
+    import sys
+    import bench
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "3", "--warmup", "1"])
+    a = bench.parse()
+    assert not a.full and a.dump_outputs is None and a.steps == 3
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", str(tmp_path)])
+    assert bench.parse().full and bench.parse().dump_outputs == str(tmp_path)
+    x = torch.arange(10 * 4 * 3, dtype=torch.float64).reshape(10, 4, 3, 1)
+    bench.dump_outputs(str(tmp_path / "all"), {"samples": x})
+    got = np.load(tmp_path / "all" / "samples.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, x.float().numpy())
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 4 * 4 * 3 * 4)              # room for four pairs
+    for d in ("s1", "s2"):
+        bench.dump_outputs(str(tmp_path / d), {"samples": x})
+    s1, s2 = np.load(tmp_path / "s1" / "samples.npy"), np.load(tmp_path / "s2" / "samples.npy")
+    assert s1.shape == (4, 4, 3, 1) and np.array_equal(s1, s2)
+    idx = s1[:, 0, 0, 0].astype(int) // 12
+    assert list(idx) == sorted(set(idx)) and np.array_equal(s1, x.float().numpy()[idx])
+
+
 def test_shipped_library_is_built_from_this_tree():
     """Build provenance: dgdm_amd/csrc/libdgdm_hip.so is git-ignored and travels to the GPU box with the snapshot; its side file records the
     content hashes of every source / header / flag set it was compiled from, and rebuilds are decided by those hashes (not by mtimes).  The
