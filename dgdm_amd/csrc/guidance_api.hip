@@ -8,7 +8,6 @@
 #include <cstring>
 #include <unordered_map>
 #include <atomic>
-#include <chrono>
 #include <thread>
 
 using namespace dgdm;
@@ -23,14 +22,6 @@ std::vector<float> linspace_f32(float start, float end, int steps) {
     const int half = steps / 2;
     for (int i = 0; i < steps; ++i) v[i] = i < half ? start + step * (float)i : end - step * (float)(steps - i - 1);
     return v;
-}
-
-// experiment hook (DGDM_HOST_TIMING): host wall-clock stamps of the calls' phases on stderr
-static inline void host_stamp(const char *tag) {
-    static const bool on = getenv("DGDM_HOST_TIMING") != nullptr;
-    if (!on) return;
-    static const auto t0 = std::chrono::steady_clock::now();
-    fprintf(stderr, "host %9.3f ms  %s\n", std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(), tag);
 }
 
 struct ObjectTables {       // 3-D, per object
@@ -68,12 +59,7 @@ struct DgdmGuidance {
     std::vector<std::unique_ptr<ObjectTables>> tables;   // 3-D
     bool bf16 = false;                           // contractions of the trunk on bf16 MFMA (dgdm_guidance_set_contraction_dtype)
     bool f32_mfma = false;                       // float32 mode on the k-ordered float32 MFMA chain (trunk.hip) instead of the f16x3 form (trunk_f16l.hip)
-#ifndef DGDM_NBUILD
-#define DGDM_NBUILD 3
-#endif
-    static constexpr int NBUILD = 16;            // most objects whose tables can be built concurrently (own stream + 0.5 GB of temporaries each)
-    // how many are: DGDM_NBUILD at compile time, the environment variable of that name at run time (experiments: bench.py --extra records them)
-    int nbuild = []() { const char *e = getenv("DGDM_NBUILD"); const int v = e ? atoi(e) : DGDM_NBUILD; return v < 1 ? 1 : (v > 16 ? 16 : v); }();
+    static constexpr int NBUILD = 3;             // most objects whose tables are built concurrently (own stream + 0.5 GB of temporaries each)
     DevBuf pool_crowded, pool_clist, pool_off, pool_pairs, pool_rank, pool_F1, pool_U;   // [n_objects] x the light build stages' outputs (built by one launch per stage)
     DevBuf pool_xyz, pool_fps1, pool_fps2, pool_flags, pool_ncr;   // [n_objects] x per-object FPS tables (ObjectTables point into these), crowded-centre counts
     DevBuf tmpY[NBUILD], tmpL2[NBUILD], vlist;      // 3-D table-build temporaries of the heavy stages (per build stream)
@@ -335,7 +321,6 @@ extern "C" int dgdm_guidance_set_objects(DgdmGuidance *g, const float *objects_d
     DGDM_REQUIRE(n_objects <= std::max(1, g->cfg.max_objects), DGDM_EINVAL, "%d objects > max_objects %d", n_objects, g->cfg.max_objects);
     hipStream_t s = (hipStream_t)stream;
     int rc;
-    host_stamp("set_objects: enter");
     prof_begin(s, DGDM_STAGE_TABLES);
     if (g->m->kind == 2) {
         // (a grow-only member, not a local: a local's hipFree - and the synchronize that had to precede it - stalled the host behind
@@ -353,7 +338,7 @@ extern "C" int dgdm_guidance_set_objects(DgdmGuidance *g, const float *objects_d
         }
         // objects are independent: build them round-robin on a few side streams so the latency-bound stages (FPS: 512
         // dependent iterations on 128 workgroups) of one object overlap the bandwidth/MFMA-bound stages of the others
-        const int nb = std::min<int>(g->nbuild, n_objects);
+        const int nb = std::min<int>(DgdmGuidance::NBUILD, n_objects);
         if (!g->bstart) DGDM_HIP_CHECK(hipEventCreateWithFlags(&g->bstart, hipEventDisableTiming));
         if (!g->ldone) DGDM_HIP_CHECK(hipEventCreateWithFlags(&g->ldone, hipEventDisableTiming));
         for (int i = 0; i < nb; ++i) {
@@ -439,7 +424,6 @@ extern "C" int dgdm_guidance_set_objects(DgdmGuidance *g, const float *objects_d
     }
     g->n_objects = n_objects;
     g->grads_since_set = 0;
-    host_stamp("set_objects: return");
     return DGDM_OK;
 }
 
@@ -544,8 +528,6 @@ int DgdmGuidance::upload_starts(const int64_t *starts_host, int n_chains, int64_
             for (int64_t i = 0; i < rt; ++i) { const int r = tmp[i]; o[cnt[d[2 * r]]++] = r | (d[2 * r + 1] << 22); }      // row id | s2 << 22
         }
     };
-    static const bool host_timing = getenv("DGDM_HOST_TIMING") != nullptr;      // experiment hook: the host's conversion + sort time per call
-    const auto ht0 = std::chrono::steady_clock::now();
     const int hw = (int)std::max(2u, std::thread::hardware_concurrency());
     const int nthreads = (int)std::min<int64_t>(std::min(16, hw / 2), std::max<int64_t>(1, std::min<int64_t>(n_chains, (int64_t)n_chains * rt / 65536)));
     if (nthreads <= 1) {
@@ -555,9 +537,6 @@ int DgdmGuidance::upload_starts(const int64_t *starts_host, int n_chains, int64_
         for (int t = 0; t < nthreads; ++t) pool.emplace_back(work, (int)((int64_t)n_chains * t / nthreads), (int)((int64_t)n_chains * (t + 1) / nthreads));
         for (auto &th : pool) th.join();
     }
-    if (host_timing)
-        fprintf(stderr, "upload_starts: %d chains x %lld rows, %d threads, need_order %d: host %.2f ms\n", n_chains, (long long)rt, nthreads, (int)need_order,
-                std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - ht0).count());
     DGDM_REQUIRE(!bad.load(), DGDM_EINVAL, "FPS start out of range (sa1 must be in [0, %d), sa2 in [0, 512))", N);
     if (!cstream) {
         DGDM_HIP_CHECK(hipStreamCreateWithFlags(&cstream, hipStreamNonBlocking));
@@ -674,11 +653,8 @@ int DgdmGuidance::embed(const int *oidx, int n_chains, const int64_t *starts_hos
         tab = bf16 ? tables[oidx[i]]->has_x16 : tables[oidx[i]]->has_x;
     }
     const int64_t rt = R * n_calls;
-    host_stamp("embed: enter");
     if ((rc = upload_starts(starts_host, n_chains, R, s, !tab, n_calls, call_stride))) return rc;     // host work: overlaps a table build still in flight
-    host_stamp("embed: starts converted, sorted, copy queued");
     if ((rc = finish_objects())) return rc;
-    host_stamp("embed: tables finished");
     TrunkParams scratch{};
     if (tab && (rc = use_xtab(oidx, n_chains, rt, bf16, &scratch, &tab, s))) return rc;
     e->used16 = false;
@@ -739,11 +715,6 @@ static int guidance_grad(DgdmGuidance *g, int kind, const float *x_dev, int time
     if (kind != 3) p.xstride = g->R;
     if (g->bf16) {
         g->m->fill_trunk_bf16(&p);       // only the two weight streams differ
-#ifdef DGDM_TRUNK_CLOCKS
-        static long long *dclk = nullptr;
-        if (!dclk) (void)hipMalloc(&dclk, (size_t)1 << 26);
-        p.clk = dclk;
-#endif
         if ((rc = trunk_bf16_launch(kind, p, s))) return rc;
     } else if (g->f32_mfma) {
         if ((rc = trunk_launch(kind, false, false, p, s))) return rc;
@@ -752,19 +723,6 @@ static int guidance_grad(DgdmGuidance *g, int kind, const float *x_dev, int time
         g->m->fill_trunk_f16(&p, &sc);   // only the two weight streams differ (+ their scale exponents)
         if ((rc = trunk_f16l_launch(kind, p, sc, s))) return rc;
     }
-#ifdef DGDM_TRUNK_CLOCKS
-    if (g->bf16) {      // mean cycles per phase over all waves (experiment build)
-        const size_t nw = (size_t)(p.ntiles + 1) / 2;
-        std::vector<long long> h(nw * 8);
-        (void)hipStreamSynchronize(s);
-        (void)hipMemcpy(h.data(), p.clk, nw * 64, hipMemcpyDeviceToHost);
-        double ph[6] = {0, 0, 0, 0, 0, 0};
-        for (size_t w = 0; w < nw; ++w)
-            for (int i = 0; i < 6; ++i) ph[i] += (double)(h[w * 8 + i + 1] - h[w * 8 + i]);
-        fprintf(stderr, "PHASES(mean cycles, %zu waves) first %.0f fwdmid %.0f wout+obj %.0f woutT %.0f bwdmid %.0f final %.0f\n", nw, ph[0] / nw, ph[1] / nw, ph[2] / nw,
-                ph[3] / nw, ph[4] / nw, ph[5] / nw);
-    }
-#endif
     prof_begin(s, DGDM_STAGE_GUIDE_MISC);
     rc = dyn_post64(g->m->W1, g->partial.as<float>(), g->tiles_per_b, g->m->blob64.at(g->m->off64.w1c_w), g->m->blob64.at(g->m->off64.g2_w),
                     g->m->blob64.at(g->m->off64.g0_w), g->V.as<double>(), grad_dev, n_chains * g->B, g->m->L, s);
@@ -860,7 +818,6 @@ extern "C" int dgdm_guided_chains_run(DgdmUnet1d *unet, DgdmGuidance *g, const f
         }
     }
     DGDM_HIP_CHECK(hipGetLastError());
-    host_stamp("chains_run: all steps queued");
     return DGDM_OK;
 }
 

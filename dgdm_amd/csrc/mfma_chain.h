@@ -56,9 +56,7 @@ __device__ __forceinline__ float4 feat4(const float *__restrict__ row, int o, in
 
 // Depth of the software prefetch ring on the weight stream: one float4 per lane feeds 4 MFMAs
 // (256 cycles), so DEPTH entries cover DEPTH*256 cycles of L2 latency with one wave per SIMD.
-#ifndef DGDM_CHAIN_DEPTH
-#define DGDM_CHAIN_DEPTH 12      // A/B on MI355X: 8 -> 12 is +6 % on the 3-D trunk, 0 on the 2-D one; 16 = 12
-#endif
+constexpr int CHAIN_DEPTH = 12;      // A/B on MI355X: 8 -> 12 is +6 % on the 3-D trunk, 0 on the 2-D one; 16 = 12
 
 // Weight images are read through a buffer descriptor (wave-uniform base in SGPRs, per-lane byte
 // offset lane*16 in ONE VGPR, entry offset as scalar/immediate): no 64-bit per-load address math in
@@ -85,10 +83,10 @@ __device__ __forceinline__ float4 wload(wrsrc_t rs, int voff, int soff) {
 }
 
 // Streams `TOTAL` consecutive float4-per-lane weight entries (1 KiB apart) starting at byte offset
-// `base_off` of the image and feeds them to `body(i, a)` in order, keeping DGDM_CHAIN_DEPTH loads in flight.
+// `base_off` of the image and feeds them to `body(i, a)` in order, keeping CHAIN_DEPTH loads in flight.
 template <int TOTAL, class Body>
 __device__ __forceinline__ void stream_weights(wrsrc_t rs, int voff, int base_off, Body &&body) {
-    constexpr int D = DGDM_CHAIN_DEPTH < TOTAL ? DGDM_CHAIN_DEPTH : TOTAL;
+    constexpr int D = CHAIN_DEPTH < TOTAL ? CHAIN_DEPTH : TOTAL;
     float4 ring[D];
 #pragma unroll
     for (int i = 0; i < D; ++i) ring[i] = wload(rs, voff, base_off + i * 1024);

@@ -35,7 +35,7 @@ struct DynOff {   // offsets (floats) into the blob
     size_t fwd_floats, bwd_floats;
     size_t wout, bout;
     size_t te0_wt, te0_b, te2_wt, te2_b, oe0_wt, oe0_b, oe2_wt, oe2_b, tfreq;
-    size_t sa1_w0t, sa1_b0, sa1_w1, sa1_b1, sa2_wf_t, sa2_b0, sa2_vx, sa2_w1_img, sa2_b1, sa3_w_img, sa3_wx, sa3_b;
+    size_t sa1_w0t, sa1_b0, sa1_w1, sa1_b1, sa2_wf_t, sa2_b0, sa2_vx, sa2_w1_img, sa2_b1, sa3_wx, sa3_b;
 };
 struct DynOff64 {   // offsets (doubles) into blob64: the unrounded folds of the stages that run in float64 (smallnet.h, pointnet64)
     size_t g0_wt, g0_b, g0_w, g2_wt, g2_b, g2_w;

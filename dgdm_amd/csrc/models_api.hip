@@ -553,7 +553,6 @@ extern "C" int dgdm_dynamics_create(DgdmDynamics **out, int kind, const DgdmTens
         o.sa2_wf_t = bl.add(transpose(cols(b0.w, 128, 131, 3, 128).data(), 128, 128)); o.sa2_b0 = bl.add(b0.b);
         o.sa2_vx = bl.add(transpose(cols(b0.w, 128, 131, 0, 3).data(), 128, 3));
         o.sa2_w1_img = bl.add(pack_chain(b1.w.data(), 256, 128)); o.sa2_b1 = bl.add(b1.b);
-        o.sa3_w_img = bl.add(pack_chain(cols(c0.w, 256, 259, 3, 256).data(), 256, 256));
         sa3_img16 = pack_chain_bf16(cols(c0.w, 256, 259, 3, 256).data(), 256, 256);
         o.sa3_wx = bl.add(transpose(cols(c0.w, 256, 259, 0, 3).data(), 256, 3)); o.sa3_b = bl.add(c0.b);
     }
@@ -720,7 +719,6 @@ PnWeights DgdmDynamics::pn() const {
     w.sa1_w0t = blob.at(off.sa1_w0t); w.sa1_b0 = blob.at(off.sa1_b0); w.sa1_w1 = blob.at(off.sa1_w1); w.sa1_b1 = blob.at(off.sa1_b1);
     w.sa2_wf_t = blob.at(off.sa2_wf_t); w.sa2_b0 = blob.at(off.sa2_b0); w.sa2_vx = blob.at(off.sa2_vx);
     w.sa2_w1_img = blob.at4(off.sa2_w1_img); w.sa2_b1 = blob.at(off.sa2_b1);
-    w.sa3_w_img = blob.at4(off.sa3_w_img);
     w.sa3_w_img16 = reinterpret_cast<const float4 *>(static_cast<const char *>(w16.p) + sa3_16_offset);
     w.sa3_wx = blob.at(off.sa3_wx); w.sa3_b = blob.at(off.sa3_b);
     return w;

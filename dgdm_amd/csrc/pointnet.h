@@ -15,8 +15,7 @@ struct PnWeights {
     const float *sa2_vx;          // [3][128]   sa2.mlp_convs.0[:, 0:3] (kn)
     const float4 *sa2_w1_img;     // chain image of sa2.mlp_convs.1 [256 x 128]
     const float *sa2_b1;          // [256]
-    const float4 *sa3_w_img;      // chain image of sa3.mlp_convs.0[:, 3:] [256 x 256]
-    const float4 *sa3_w_img16;    // the same as a pack_chain_bf16 image (bf16 mode, z16_kernel)
+    const float4 *sa3_w_img16;    // pack_chain_bf16 image of sa3.mlp_convs.0[:, 3:] [256 x 256] (bf16 mode, z16_kernel)
     const float *sa3_wx;          // [3][256]   sa3.mlp_convs.0[:, 0:3] (kn)
     const float *sa3_b;           // [256]
 };
@@ -107,9 +106,6 @@ int pn_l2(const float *xyz, int N, const PnWeights &w, const int *fps1, const in
 // bf16 mode T6: bf16 contraction from L2_16 rows; writes the float32 rows and their bf16 copy
 int pn_z16(const float *xyz, int N, int nv, const PnWeights &w, const uint32_t *L2_16, float *Z, uint32_t *Z16, const int *clist, const int *ncr,
            hipStream_t s);
-// Z16 (optional): the same rows again in bf16 operand order
-int pn_z(const float *xyz, int N, int nv, const PnWeights &w, const float *L2, float *Z, uint32_t *Z16, const int *clist, const int *ncr,
-         hipStream_t s);
 // ---- float64 table build (pointnet64.hip): same inputs, same float32 outputs (each rounded ONCE from a float64 accumulation)
 // F1_64 [N][128] doubles (sa1 features); U is then linear64(F1_64) -> U64 [N][128] doubles
 int pn_sa1_64(const float *xyz, int N, float r1sq, const PnWeights64 &w, double *F1_64, hipStream_t s, int nobj = 1);

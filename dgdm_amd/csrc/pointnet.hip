@@ -472,16 +472,8 @@ __device__ __forceinline__ void l2c_centre(int c, int N, const int *__restrict__
     // blockIdx.y: this workgroup's share of the variants (an object has ~40 crowded centres: one workgroup per centre leaves five CUs
     // of six idle, and the reduction is bound by the LDS bandwidth of the CU it runs on; staging the block of Y once per share is cheap)
     const int vlo = 1 + (int)(((int64_t)(nv - 1) * blockIdx.y) / gridDim.y), vhi = 1 + (int)(((int64_t)(nv - 1) * (blockIdx.y + 1)) / gridDim.y);
-#ifdef DGDM_L2C_CLOCKS
-    long long tk[8]; int nk = 0;
-#define L2C_STAMP() do { if (nk < 8) tk[nk++] = __builtin_readcyclecounter(); } while (0)
-#else
-#define L2C_STAMP() do {} while (0)
-#endif
-    L2C_STAMP();
     for (int i = threadIdx.x; i < N; i += L2C_THREADS) rks[i] = rank[(size_t)c * N + i];
     __syncthreads();
-    L2C_STAMP();
     if (K > 255) {
         // a ball with more points than a byte can index (never on the shipped 512-point clouds): gather from global memory as
         // l2_kernel does, W / 64 dwords per lane
@@ -544,12 +536,10 @@ __device__ __forceinline__ void l2c_centre(int c, int N, const int *__restrict__
     const uint32_t *Yc = Y + (size_t)off[c] * W;
     for (int f0 = 0; f0 < W; f0 += 4 * lpr) {
         __syncthreads();                                          // selections written / previous chunk consumed
-        L2C_STAMP();
         const int pieces = K * lpr;
         for (int i = threadIdx.x; i < pieces; i += L2C_THREADS)
             *reinterpret_cast<uint4 *>(ych + (size_t)i * 4) = *reinterpret_cast<const uint4 *>(Yc + (size_t)(i / lpr) * W + f0 + (i % lpr) * 4);
         __syncthreads();
-        L2C_STAMP();
         for (int v = vlo + wave; v < vhi; v += nwave) {
             uint32_t *dst = L2 + ((size_t)v * N + c) * W + f0;
             const unsigned char *sv = sel + (size_t)v * 64;
@@ -562,15 +552,6 @@ __device__ __forceinline__ void l2c_centre(int c, int N, const int *__restrict__
             }
         }
     }
-#ifdef DGDM_L2C_CLOCKS
-    __syncthreads();
-    L2C_STAMP();
-    if (threadIdx.x == 0 && blockIdx.x == 3 && blockIdx.y == 0) {
-        printf("l2c c %d K %d lpr %d share %d..%d:", c, K, lpr, vlo, vhi);
-        for (int i = 1; i < nk; ++i) printf(" %lld", tk[i] - tk[i - 1]);
-        printf("\n");
-    }
-#endif
 }
 
 // Grid (centres' stride, variant shares): a workgroup takes the crowded centres blockIdx.x, blockIdx.x + gridDim.x, ... and of each the
@@ -584,9 +565,6 @@ __global__ __launch_bounds__(L2C_THREADS, 1) void l2c_kernel(int N, const int *_
                                                              const short *__restrict__ rank) {
     __shared__ int selw[L2C_THREADS / 64][64];
     const int n = *ncr;
-#ifdef DGDM_L2C_CLOCKS
-    if (threadIdx.x == 0 && blockIdx.x == 0 && blockIdx.y == 0) printf("l2c ncr %d pairs %d\n", n, off[N]);
-#endif
     for (int ci = blockIdx.x; ci < n; ci += gridDim.x) {
         l2c_centre<BF16>(clist[ci], N, fps1, nv, Y, L2, off, rank, selw);
         __syncthreads();                                          // the LDS areas are reused by the next centre
@@ -596,69 +574,10 @@ __global__ __launch_bounds__(L2C_THREADS, 1) void l2c_kernel(int N, const int *_
 // ------------------------------------------------------------------------------------------------ T6
 // Z[row][256] = ReLU(W3'[:,3:] L2[row] + W3'[:,0:3] xyz_c + b3'),  row = slot*N + c   (sa3, pointnet2.py:19)
 // mode 0: slot 0, all N centres.  mode 1: slots 1..nv-1, crowded centres only (work item k -> slot 1 + k / ncr, centre clist[k % ncr]).
-__global__ __launch_bounds__(256, 1) void z_kernel(const float *__restrict__ xyz, int N, int nv, const float *__restrict__ L2,
-                                                   const float4 *__restrict__ Wimg, const float *__restrict__ w3x /*[3][256]*/,
-                                                   const float *__restrict__ bias, float *__restrict__ Z, uint32_t *__restrict__ Z16,
-                                                   int mode, const int *__restrict__ clist, const int *__restrict__ ncr) {
-    const int lane = threadIdx.x & 63, n = lane & 31, h4 = (lane >> 5) * 4;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int64_t tile = (int64_t)blockIdx.x * 4 + wave;
-    const int ncrv = mode ? *ncr : N;
-    const int64_t items = mode ? (int64_t)(nv - 1) * ncrv : N;
-    if (tile * 32 >= items) return;
-    const int64_t item = min(tile * 32 + n, items - 1);
-    const int c = mode ? clist[item % ncrv] : (int)item;
-    const int64_t row = mode ? (1 + item / ncrv) * N + c : c;
-    const int64_t rows = items;
-    const float x = xyz[3 * c], y = xyz[3 * c + 1], z = xyz[3 * c + 2];
-    f32x16 in[8], out[8];
-    const float *lrow = L2 + (size_t)row * 256;
-#pragma unroll
-    for (int o = 0; o < 8; ++o) {
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const float4 v = feat4(lrow, o, q, h4);
-            in[o][4 * q + 0] = v.x; in[o][4 * q + 1] = v.y; in[o][4 * q + 2] = v.z; in[o][4 * q + 3] = v.w;
-            const float4 b = feat4(bias, o, q, h4);
-            const float4 a0 = feat4(w3x, o, q, h4), a1 = feat4(w3x + 256, o, q, h4), a2 = feat4(w3x + 512, o, q, h4);
-            out[o][4 * q + 0] = fmaf(a2.x, z, fmaf(a1.x, y, fmaf(a0.x, x, b.x)));
-            out[o][4 * q + 1] = fmaf(a2.y, z, fmaf(a1.y, y, fmaf(a0.y, x, b.y)));
-            out[o][4 * q + 2] = fmaf(a2.z, z, fmaf(a1.z, y, fmaf(a0.z, x, b.z)));
-            out[o][4 * q + 3] = fmaf(a2.w, z, fmaf(a1.w, y, fmaf(a0.w, x, b.w)));
-        }
-    }
-    chain_layer<8, 8, CHAIN_KEEP>(Wimg, nullptr, in, out, lane);
-    if (tile * 32 + n < rows) {
-        float *dst = Z + (size_t)row * 256;   // rows of one tile are distinct (item -> row is injective)
-#pragma unroll
-        for (int o = 0; o < 8; ++o) {
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                float4 v;
-                v.x = fmaxf(out[o][4 * q + 0], 0.f); v.y = fmaxf(out[o][4 * q + 1], 0.f);
-                v.z = fmaxf(out[o][4 * q + 2], 0.f); v.w = fmaxf(out[o][4 * q + 3], 0.f);
-                *reinterpret_cast<float4 *>(dst + 32 * o + 8 * q + h4) = v;
-            }
-        }
-        if (Z16) {
-            // the same row in bf16 operand order for the bf16 trunk (mfma_chain.h): the lane's 8 dwords of block o are contiguous
-            uint4 *d16 = reinterpret_cast<uint4 *>(Z16 + (size_t)row * 128) + (h4 >> 1);
-#pragma unroll
-            for (int o = 0; o < 8; ++o) {
-                uint32_t pk[8];
-#pragma unroll
-                for (int d = 0; d < 8; ++d) pk[d] = pack_bf16(fmaxf(out[o][2 * d], 0.f), fmaxf(out[o][2 * d + 1], 0.f));
-                d16[4 * o] = make_uint4(pk[0], pk[1], pk[2], pk[3]);
-                d16[4 * o + 1] = make_uint4(pk[4], pk[5], pk[6], pk[7]);
-            }
-        }
-    }
-}
-
-// T6 in bf16 mode: the sa3 contraction on v_mfma_f32_32x32x16_bf16.  One wave = two 32-row tiles (each weight entry feeds two
+// bf16 mode: the sa3 contraction on v_mfma_f32_32x32x16_bf16.  One wave = two 32-row tiles (each weight entry feeds two
 // MFMAs).  L2_16 rows are already the B operand (operand order); W3'[:, 3:] comes as a pack_chain_bf16 image through the
 // buffer-load ring; the coordinate part W3'[:, 0:3] xyz_c + b3' is the float32 accumulator start.  Writes the float32 rows
-// (orientation sweep, M0) and their bf16 operand-order copy (xobj gathers).  Items as in z_kernel.
+// (orientation sweep, M0) and their bf16 operand-order copy (xobj gathers).
 typedef __bf16 zbf16x8 __attribute__((ext_vector_type(8)));
 __global__ __launch_bounds__(256, 1) void z16_kernel(const float *__restrict__ xyz, int N, int nv, const uint32_t *__restrict__ L2_16,
                                                      const float4 *__restrict__ Wimg16, const float *__restrict__ w3x /*[3][256]*/,
@@ -1518,8 +1437,7 @@ int pn_l2c(int N, const int *fps1, int nv, const float *Y, float *L2, const int 
     }
     // 64 x 4 = 256 workgroups, one per CU (150 KB of LDS each): ONE round whatever the number of crowded centres is (0 .. N: a few
     // objects of a batch have every centre crowded and carry most of the build's work), and 160 busy CUs at the typical 40
-    static const int split = []() { const char *e = getenv("DGDM_L2C_SPLIT"); const int v = e ? atoi(e) : 4; return v < 1 ? 1 : (v > 32 ? 32 : v); }();
-    static const int gx = []() { const char *e = getenv("DGDM_L2C_GRID"); const int v = e ? atoi(e) : 64; return v < 1 ? 1 : v; }();
+    constexpr int split = 4, gx = 64;
     const dim3 grid(std::min(N, gx), std::min(split, std::max(nv - 1, 1)));
     if (bf16) hipLaunchKernelGGL(l2c_kernel<true>, grid, dim3(L2C_THREADS), lds, s, N, fps1, nv, reinterpret_cast<const uint32_t *>(Y),
                                  reinterpret_cast<uint32_t *>(L2), clist, ncr, off, rank);
@@ -1544,18 +1462,6 @@ int pn_l2(const float *xyz, int N, const PnWeights &w, const int *fps1, const in
     } else {
         hipLaunchKernelGGL(l2_kernel<false>, g0, dim3(256), 0, s, xyz, N, w.r2sq, fps1, vlist, nv, Y, L2, 0, clist, ncr, off, rank);
         if (nv > 1) hipLaunchKernelGGL(l2_kernel<false>, g1, dim3(256), 0, s, xyz, N, w.r2sq, fps1, vlist, nv, Y, L2, 1, clist, ncr, off, rank);
-    }
-    DGDM_HIP_CHECK(hipGetLastError());
-    return DGDM_OK;
-}
-
-int pn_z(const float *xyz, int N, int nv, const PnWeights &w, const float *L2, float *Z, uint32_t *Z16, const int *clist, const int *ncr,
-         hipStream_t s) {
-    const int64_t t0 = (N + 31) / 32;
-    hipLaunchKernelGGL(z_kernel, dim3((unsigned)((t0 + 3) / 4)), dim3(256), 0, s, xyz, N, nv, L2, w.sa3_w_img, w.sa3_wx, w.sa3_b, Z, Z16, 0, clist, ncr);
-    if (nv > 1) {      // sized for the worst case (every centre crowded); surplus workgroups leave at once
-        const int64_t t1 = ((int64_t)(nv - 1) * N + 31) / 32;
-        hipLaunchKernelGGL(z_kernel, dim3((unsigned)((t1 + 3) / 4)), dim3(256), 0, s, xyz, N, nv, L2, w.sa3_w_img, w.sa3_wx, w.sa3_b, Z, Z16, 1, clist, ncr);
     }
     DGDM_HIP_CHECK(hipGetLastError());
     return DGDM_OK;

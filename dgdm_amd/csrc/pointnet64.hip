@@ -86,9 +86,6 @@ __global__ __launch_bounds__(256) void sa1_64_kernel(const float *xyz_all, int N
         const float *xyz = xyz_all + (size_t)ob * 3 * N;
         double *F1 = F1_all + (size_t)ob * N * 128;
         const int p0 = 2 * pp, p1 = min(2 * pp + 1, N - 1);
-#ifdef DGDM_SA1_CLOCKS
-        const long long tk0 = __builtin_readcyclecounter();
-#endif
 #pragma unroll
         for (int c = 0; c < 2; ++c) {                        // float32 distances (index decision), one centre after the other
             const int pc = c ? p1 : p0;
@@ -104,9 +101,6 @@ __global__ __launch_bounds__(256) void sa1_64_kernel(const float *xyz_all, int N
 #pragma unroll
         for (int c = 0; c < 64; ++c) h[c] = fmax(fma(w0t[128 + c], dz, fma(w0t[64 + c], dy, fma(w0t[c], dx, b0[c]))), 0.0);
         double res[4] = {0.0, 0.0, 0.0, 0.0};
-#ifdef DGDM_SA1_CLOCKS
-        const long long tk1 = __builtin_readcyclecounter();
-#endif
 #pragma nounroll
         for (int f = 0; f < 128; ++f) {
             const double *wf = sa1_w + f * 64;               // wave-uniform: broadcast reads
@@ -119,10 +113,6 @@ __global__ __launch_bounds__(256) void sa1_64_kernel(const float *xyz_all, int N
             acc = fmax(acc, 0.0);                            // ReLU outputs are >= 0 and the group is never empty
             if (sl == (f & 31)) res[f >> 5] = acc;
         }
-#ifdef DGDM_SA1_CLOCKS
-        const long long tk2 = __builtin_readcyclecounter();
-        if (threadIdx.x == 0 && blockIdx.x == 100 && task < 4 * gridDim.x * 2) printf("sa1 task %d: ball + layer 0 %lld cycles, layer 1 %lld\n", task, tk1 - tk0, tk2 - tk1);
-#endif
         if (half == 0 || 2 * pp + 1 < N) {
 #pragma unroll
             for (int j = 0; j < 4; ++j) F1[(size_t)p * 128 + 32 * j + sl] = res[j];
@@ -189,7 +179,7 @@ __global__ __launch_bounds__(256, 2) void pair64_kernel(const float *__restrict_
 }
 
 // ------------------------------------------------------------------------------------------------ T6
-// Z[row][256] = float32( ReLU(W3'[:,3:] L2[row] + W3'[:,0:3] xyz_c + b3') ),  rows as pointnet.hip z_kernel's two modes in ONE launch:
+// Z[row][256] = float32( ReLU(W3'[:,3:] L2[row] + W3'[:,0:3] xyz_c + b3') ),  row = slot * N + c, all rows in ONE launch:
 // items 0 .. N-1 are slot 0's rows (every centre), item N + j is (variant 1 + j / ncr, crowded centre clist[j % ncr]).  The item count
 // is device data: a bounded grid whose waves stride over the 16-row tiles (a worst-case grid is 4096 workgroups of which ~330 find work).
 // (Round 5, tried: two tiles per wave against one pass over the weight image - half the L2 traffic per FLOP, one wave per SIMD with

@@ -14,7 +14,6 @@ int linear(const float *X, int ldx, const float *WT, const float *bias, const fl
 int tile_table(const float *T, int rows, int W, float *out, hipStream_t s);
 int pose_embed(const float *ori, const float *pos, float *out /*[rows][27]*/, int rows, hipStream_t s);
 int time_embed(const float *t_dev /*or null*/, float t_scalar, const float *freqs, float *out, int rows, int half, hipStream_t s);
-int gather_add(const float *a, const int *idx, const float *b, float *out, int groups, int N, hipStream_t s);
 int dyn_post(int W1, const float *partial, int tiles_per_b, const float *w1c, const float *g2w, const float *g0w, const float *V,
              float *grad, int rows, int L, hipStream_t s);
 

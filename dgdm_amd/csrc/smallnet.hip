@@ -152,24 +152,6 @@ int time_embed(const float *t_dev, float t_scalar, const float *freqs, float *ou
     return DGDM_OK;
 }
 
-// out[g][n] = (a ? a[idx ? idx[g] : g][n] : 0) + (b ? b[n] : 0)
-__global__ void gather_add_kernel(const float *__restrict__ a, const int *__restrict__ idx, const float *__restrict__ b,
-                                  float *__restrict__ out, int groups, int N) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= groups * N) return;
-    const int g = i / N, n = i - g * N;
-    float v = b ? b[n] : 0.f;
-    if (a) v += a[(size_t)(idx ? idx[g] : g) * N + n];
-    out[i] = v;
-}
-
-int gather_add(const float *a, const int *idx, const float *b, float *out, int groups, int N, hipStream_t s) {
-    if (groups <= 0) return DGDM_OK;
-    hipLaunchKernelGGL(gather_add_kernel, dim3((groups * N + 255) / 256), dim3(256), 0, s, a, idx, b, out, groups, N);
-    DGDM_HIP_CHECK(hipGetLastError());
-    return DGDM_OK;
-}
-
 // ------------------------------------------------------------------------------------------------
 // Backward tail of cond_fn for one finger of one chain (what autograd does after the trunk,
 // generator/diffusion.py:498,504): fold the tile partials over cells, then go back through

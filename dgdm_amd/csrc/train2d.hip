@@ -34,10 +34,7 @@
 namespace dgdm {
 namespace {
 
-#ifndef DGDM_TRAIN_RC
-#define DGDM_TRAIN_RC 16
-#endif
-constexpr int TI = 128, TJ = 256, RC = DGDM_TRAIN_RC, PU = RC / 8, QU = RC / 4, W = 256;      // RC = contraction depth of one LDS chunk
+constexpr int TI = 128, TJ = 256, RC = 16, PU = RC / 8, QU = RC / 4, W = 256;      // RC = contraction depth of one LDS chunk
 enum { EPI_FWD = 0, EPI_BWD = 1, EPI_WGRAD = 2 };
 enum { MASK_NONE = 0, MASK_RELU = 1, MASK_SILU = 2, MASK_RELU_BN = 3 };
 

@@ -244,10 +244,7 @@ typedef float f32x4v_t __attribute__((ext_vector_type(4)));
 typedef __attribute__((address_space(3))) f32x4v_t lds_f32x4_t;      // keeps ds_read / ds_write (a generic pointer would turn into flat accesses)
 constexpr int FRONT_CHUNKS = 64;                                      // 2 passes x 32 chunks of 16 entries
 
-#ifndef DGDM_FRONT_DEPTH
-#define DGDM_FRONT_DEPTH 1
-#endif
-constexpr int FSD = DGDM_FRONT_DEPTH;      // chunks a quarter-chunk load is given to arrive beyond the first (measured: 2-4 are no faster, and spill)
+constexpr int FSD = 1;      // chunks a quarter-chunk load is given to arrive beyond the first (measured: 2-4 are no faster, and spill)
 
 struct FrontStage {
     float4 q[FSD][4];              // this wave's quarter of chunks cc + 2 .. cc + 1 + FSD, in flight from L2; chunk k sits in slot (k - 2) % FSD
@@ -277,17 +274,11 @@ __device__ __forceinline__ void front_chunk_end() {
 }
 
 // The A operands of the front come out of LDS through an 8-entry register ring in CONSUMPTION order (LDS latency is ~100 cycles: eight
-// steps of cover are plenty, and the other half of the usual 16-entry ring pays for the second accumulator below).  Consumption order
+// steps of cover are plenty, and the other half of the usual 16-entry ring pays for the layer-1 accumulators below).  Consumption order
 // within a chunk: a layer-1 chunk (one output block, 16 K-steps) as stored; a layer-2 chunk (8 output blocks x 2 K-steps, stored block-
 // major) K-step-major, so that consecutive MFMAs never hit the same accumulator - a dependent v_mfma_f32_32x32x16_bf16 issues only every
 // ~68 cycles, which is what this phase was really bound by (1 560 cycles per 16-MFMA chunk with the weights already in LDS).
 // Chunk sequence of a pass: z(0), z(1), l2(0), z(2), l2(1), ..., z(15), l2(14), l2(15).
-#ifdef DGDM_FRONT_STAMPS
-__device__ long long g_front_stamps[16];
-#define FSTAMP(i) do { if (T == 0 && KB == 5 && blockIdx.x == gridDim.x / 2 && tid == 0) g_front_stamps[i] = clock64(); } while (0)
-#else
-#define FSTAMP(i) do { } while (0)
-#endif
 
 constexpr bool front_is_l2(int cc) { return (cc % 32) == 31 || ((cc % 32) >= 2 && (cc % 32) % 2 == 0); }
 constexpr int front_entry(int cc, int j) { return front_is_l2(cc) ? 2 * (j % 8) + j / 8 : j; }
@@ -351,59 +342,37 @@ __device__ __forceinline__ void front3d(const wrsrc_t rs, const int voff, float4
             }
         }
     }
-    // a layer-1 block accumulates on TWO accumulators (even / odd K-steps): the MFMAs of one accumulator are dependent
-    f32x16 zA[2], zB[2];
+    // layer-1 block KB accumulates on zA[KB & 1] while the epilogue of block KB - 1 reads the other; one accumulator per block (a second one
+    // for the odd K-steps needs registers the phase does not have: it spilled)
+    f32x16 zA[2];
     u32x4_t zin[2];
     uint32_t mk = 0;
-    f32x16 zero;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) zero[r] = 0.f;
     static_for<0, 17>([&](auto kc) {
         constexpr int KB = decltype(kc)::value;          // z(KB) for KB < 16, then l2(KB - 1) for KB >= 1
         if constexpr (KB < 16) {
             f32x16 init;
             table_sum(raw[KB & 1], init);
             constexpr int CZ = 32 * T + (KB == 0 ? 0 : 2 * KB - 1);          // chunk number of z(KB) in the two-pass sequence
-            FSTAMP(0);
             front_chunk_begin<CZ>(rs, voff, wave, wb, st);
-            FSTAMP(1);
             static_for<0, 16>([&](auto ic) {
                 constexpr int I = decltype(ic)::value;
                 const float4 a = front_take<CZ, I>(fr, wb);
                 if constexpr (KB > 0 && I == 0) mk = 0u;
                 if constexpr (KB > 0 && I < 8) {          // epilogue of z(KB-1): one pair per step
                     constexpr int Q = (KB - 1) & 1;
-#ifdef DGDM_FRONT_TWO_ACC
-                    zin[I / 4][I % 4] = fwd_pair<I + 8 * T>(zA[Q][2 * I] + zB[Q][2 * I], zA[Q][2 * I + 1] + zB[Q][2 * I + 1], mk);
-#else
                     zin[I / 4][I % 4] = fwd_pair<I + 8 * T>(zA[Q][2 * I], zA[Q][2 * I + 1], mk);
-#endif
                 }
-#ifdef DGDM_FRONT_TWO_ACC
-                if constexpr (I == 0) zA[KB & 1] = mfma_bf16(a, xin[0][0], init);
-                else if constexpr (I == 1) zB[KB & 1] = mfma_bf16(a, xin[0][1], zero);
-                else if constexpr (I % 2 == 0) zA[KB & 1] = mfma_bf16(a, xin[I / 2][0], zA[KB & 1]);
-                else zB[KB & 1] = mfma_bf16(a, xin[I / 2][1], zB[KB & 1]);
-#else
                 if constexpr (I == 0) zA[KB & 1] = mfma_bf16(a, xin[0][0], init);
                 else zA[KB & 1] = mfma_bf16(a, xin[I / 2][I % 2], zA[KB & 1]);
-#endif
                 if constexpr (I == 8 && KB < 15) table_load(tr, KB + 1, h4, raw[(KB + 1) & 1]);     // next block's table part
                 STEP_FENCE();
-                if constexpr (I == 7) FSTAMP(2);
             });
-            FSTAMP(3);
             front_chunk_end();
-            FSTAMP(4);
         } else {
             mk = 0u;
             static_for<0, 8>([&](auto ic) {
                 constexpr int I = decltype(ic)::value;
-#ifdef DGDM_FRONT_TWO_ACC
-                zin[I / 4][I % 4] = fwd_pair<I + 8 * T>(zA[1][2 * I] + zB[1][2 * I], zA[1][2 * I + 1] + zB[1][2 * I + 1], mk);
-#else
                 zin[I / 4][I % 4] = fwd_pair<I + 8 * T>(zA[1][2 * I], zA[1][2 * I + 1], mk);
-#endif
             });
         }
         if constexpr (KB >= 1) {
@@ -413,7 +382,6 @@ __device__ __forceinline__ void front3d(const wrsrc_t rs, const int voff, float4
             else (void)__hip_atomic_fetch_or(&smask[KP][tid], mk, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);   // ds_or_b32, no read-back
             constexpr int CL = 32 * T + (KP == 15 ? 31 : 2 * KP + 2);        // chunk number of l2(KP)
             front_chunk_begin<CL>(rs, voff, wave, wb, st);
-            FSTAMP(5);
             static_for<0, 16>([&](auto jc) {
                 constexpr int J = decltype(jc)::value;
                 constexpr int OP = J % 8, S = J / 8;       // K-step-major: eight different accumulators in a row
@@ -421,9 +389,7 @@ __device__ __forceinline__ void front3d(const wrsrc_t rs, const int voff, float4
                 acc2[OP] = mfma_bf16(a, zin[S], acc2[OP]);
                 STEP_FENCE();
             });
-            FSTAMP(6);
             front_chunk_end();
-            FSTAMP(7);
         }
     });
     if (T == 1) ring_fill(rs, voff, 512 * 1024, ring);       // the stack's first 16 entries, in flight during the epilogue below
@@ -468,14 +434,6 @@ __global__ __launch_bounds__(256, 1) void trunk_bf16_kernel(const TrunkParams p)
     const TileRows tr0 = tile_rows(p, tile0, n, lane, W1);
     const TileRows tr1 = tile_rows(p, has1 ? tile0 + 1 : tile0, n, lane, W1);
 
-#ifdef DGDM_TRUNK_CLOCKS
-    long long tstamp[8];
-    int nts = 0;
-#define STAMP() tstamp[nts++] = __builtin_readcyclecounter()
-#else
-#define STAMP()
-#endif
-    STAMP();
     Act16 X, Y;
     Pipe pipe;
     pipe.mk = 0;
@@ -536,7 +494,6 @@ __global__ __launch_bounds__(256, 1) void trunk_bf16_kernel(const TrunkParams p)
         if (!active) return;
     }
     int pend_slot = (KIND == 3) ? 16 + 7 : 7;
-    STAMP();
 
     // ---- 256 -> 256 layers, two per iteration (X -> Y -> X)
     int l = 0;
@@ -553,7 +510,6 @@ __global__ __launch_bounds__(256, 1) void trunk_bf16_kernel(const TrunkParams p)
         pend_slot = S_MID + 8 * l + 7;
     }
     Act16 &H = (KIND == 2) ? Y : X;                        // a_8, block 7 pending
-    STAMP();
 
     // ---- output layer 256 -> 3 (padded to one 32-row block): 16 entries; finishes the pending block on the way
     f32x16 lo[2];
@@ -605,12 +561,10 @@ __global__ __launch_bounds__(256, 1) void trunk_bf16_kernel(const TrunkParams p)
             GB.v[t][0][1] = u32x4_t{0u, 0u, 0u, 0u};
         }
     }
-    STAMP();
     // ---- transposed output layer: 8 blocks x 2 K-steps; masks of a_8
     layer16<false, false, 2>(rsB, voff, woff, ring, nullptr, nullptr, GB, GA, pipe, smask, 0, S_MID + 8 * (p.n_mid - 1), tid, h4);
     woff += 16 * 1024;
 
-    STAMP();
     // ---- backward through the mid layers, two per iteration (GA -> GB -> GA); layer j masks with the output of layer j-1
     for (int j = p.n_mid - 1; j >= ((KIND == 2) ? 2 : 1); j -= 2) {
         layer16<false, true, 16>(rsB, voff, woff, ring, nullptr, nullptr, GA, GB, pipe, smask, 0, S_MID + 8 * (j - 1), tid, h4);
@@ -619,7 +573,6 @@ __global__ __launch_bounds__(256, 1) void trunk_bf16_kernel(const TrunkParams p)
         woff += 128 * 1024;
     }
 
-    STAMP();
     // ---- last layer back (2-D: W2'^T, 8 blocks; 3-D: W2'^T onto the 512-wide layer 1, 16 blocks): float32 epilogue,
     //      mask of a_1, fold of the tile's 32 cells, one partial vector per tile
     const bool same_b = has1 && tr0.chain == tr1.chain && tr0.b == tr1.b;
@@ -685,11 +638,6 @@ __global__ __launch_bounds__(256, 1) void trunk_bf16_kernel(const TrunkParams p)
             if (has1) fold(g[1], dst1);
         }
     });
-    STAMP();
-#ifdef DGDM_TRUNK_CLOCKS
-    if (p.clk && lane == 0)
-        for (int i = 0; i < 7; ++i) p.clk[(size_t)(blockIdx.x * 4 + wave) * 8 + i] = tstamp[i];
-#endif
 }
 
 int trunk_bf16_launch(int kind, const TrunkParams &p, hipStream_t s) {
@@ -703,15 +651,6 @@ int trunk_bf16_launch(int kind, const TrunkParams &p, hipStream_t s) {
     if (kind == 2) hipLaunchKernelGGL((trunk_bf16_kernel<2>), dim3(grid), dim3(256), 0, s, p);
     else hipLaunchKernelGGL((trunk_bf16_kernel<3>), dim3(grid), dim3(256), 0, s, p);
     DGDM_HIP_CHECK(hipGetLastError());
-#ifdef DGDM_FRONT_STAMPS
-    if (kind == 3) {
-        long long st[16];
-        hipStreamSynchronize(s);
-        hipMemcpyFromSymbol(st, HIP_SYMBOL(g_front_stamps), sizeof(st));
-        fprintf(stderr, "front stamps (z(5) chunk: begin-staging %lld, steps 0-7 %lld, steps 8-15 %lld, barrier %lld | l2(4) chunk: staging %lld, 16 steps %lld, barrier %lld)\n",
-                st[1] - st[0], st[2] - st[1], st[3] - st[2], st[4] - st[3], st[5] - st[4], st[6] - st[5], st[7] - st[6]);
-    }
-#endif
     prof_end(s, DGDM_STAGE_TRUNK, rows * per_row);
     return DGDM_OK;
 }

@@ -53,13 +53,6 @@
 #include "trunk.h"
 
 namespace dgdm {
-#ifdef DGDM_F16_STAMPS
-// experiment hook: cycle stamps of one wave at the phase boundaries (printed by trunk_f16l_launch)
-__device__ long long g_f16l_stamps[48];
-#define HSTAMP(i) do { if (blockIdx.x == gridDim.x / 2 && threadIdx.x == 0) g_f16l_stamps[i] = clock64(); } while (0)
-#else
-#define HSTAMP(i) do { } while (0)
-#endif
 namespace f16l {
 
 typedef _Float16 hf16x8_t __attribute__((ext_vector_type(8)));
@@ -109,20 +102,11 @@ struct Act2 {
 };
 
 // The shared weight stream (see the file header).
-// Chunk = CH stream entries (1 KiB each): 16 (one K-step of all four output-block pairs) in four slots.  -DDGDM_F16_CHUNK=32 (round 5
-// experiment): a whole 32-feature input block (both K-steps) per chunk in THREE slots (96 KiB) - half the barriers and counted waits per
-// MFMA (one per 1 536 cycles of issue); c + 3 goes into c's slot once every wave has passed the barrier behind its last reads of c.
-// Bit-identical results, and 1.5 % SLOWER on the same box (3-D launch 6.92 -> 7.03 ms, three alternating runs each): the barrier count
-// is not what holds the stack at 0.6 of its MFMA rate.
-#ifndef DGDM_F16_CHUNK
-#define DGDM_F16_CHUNK 16
-#endif
-#ifndef DGDM_F16_SLOTS
-#define DGDM_F16_SLOTS 4
-#endif
-// LDS slots of the stream and chunks requested ahead of the one being consumed (AHEAD = NBUF - 2 with 16 KiB chunks: the slot a request
-// lands in is the one the PREVIOUS chunk left, proven free by the barrier; 32 KiB chunks keep their three slots and two chunks ahead)
-constexpr int CH = DGDM_F16_CHUNK, NBUF = CH == 16 ? DGDM_F16_SLOTS : 3, AHEAD = CH == 16 ? NBUF - 2 : 2;
+// Chunk = CH stream entries (1 KiB each): 16 (one K-step of all four output-block pairs) in four slots.  Whole 32 KiB input blocks per
+// chunk in three slots (round 5: half the barriers) gave bit-identical results 1.5 % slower; that variant is in git history.
+// LDS slots of the stream and chunks requested ahead of the one being consumed (AHEAD = NBUF - 2: the slot a request lands in is the one
+// the PREVIOUS chunk left, proven free by the barrier)
+constexpr int CH = 16, NBUF = 4, AHEAD = NBUF - 2;
 constexpr int CQ = CH / 4 /* entries a wave fetches per chunk */, CG = CH / 4 /* groups of four entries per chunk */;
 static_assert(NBUF >= 3 && NBUF <= 6 && CQ * AHEAD <= 48, "stream slots: 3 .. 6 (LDS), at most 48 DMA loads in flight per wave (vmcnt)");
 typedef __attribute__((address_space(3))) v4f32 lds_f4_t;      // (a plain vector type: HIP's float4 class has no address-space-qualified copy)
@@ -135,9 +119,6 @@ struct LStream {
     int voff, wave, lane;
     int base;                // byte offset of the stream's chunk 0
     int cur, slot;           // chunk whose entries read() addresses (relative to base), and its slot
-#ifdef DGDM_F16_STAMPS
-    long long stall_vm = 0, stall_bar = 0;
-#endif
     // This wave's quarter of chunk c, straight into LDS.  Inline assembly on purpose: behind an LDS-DMA load hipcc can see, it orders EVERY
     // LDS read after ALL such loads in flight (s_waitcnt vmcnt(0) in front of each ds_read_b128 - it cannot tell the four slots apart),
     // which serialises the stream with its own prefetch; the first version of this kernel was 20 % slower than the per-wave ring for that.
@@ -165,17 +146,8 @@ struct LStream {
     // chunk cur + 1 becomes readable, chunk cur + AHEAD + 1 is requested; cur moves on
     __device__ __forceinline__ void advance() {
         // (lgkmcnt(0): this wave's LDS reads of the chunk it leaves have returned - with three slots the chunk requested below lands in that slot)
-#ifdef DGDM_F16_STAMPS
-        const long long t0 = clock64();
-        asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" : : "n"(CQ * (AHEAD - 1)) : "memory");
-        const long long t1 = clock64();
-        __builtin_amdgcn_s_barrier();
-        const long long t2 = clock64();
-        stall_vm += t1 - t0; stall_bar += t2 - t1;
-#else
         asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" : : "n"(CQ * (AHEAD - 1)) : "memory");
         __builtin_amdgcn_s_barrier();
-#endif
         issue(cur + AHEAD + 1);
         ++cur;
         slot = slot == NBUF - 1 ? 0 : slot + 1;
@@ -224,7 +196,6 @@ __device__ __forceinline__ void stream_layer(LStream &ls, v4f32 (&wn)[4], const 
         }
     }
     hu32x4_t P[2][2][2];                           // [block parity][piece][K-step]
-    HSTAMP(FWD ? 23 : 26);
     uint32_t mk = FWD ? 0u : smask[slot_in][tid];
     auto item = [&](const f32x16 &y, const int blk, const int d, const bool far) __attribute__((always_inline)) {
         // scale first (one packed multiply; exact, f is a power of two), then ReLU / mask: the same values as the other way round
@@ -253,7 +224,6 @@ __device__ __forceinline__ void stream_layer(LStream &ls, v4f32 (&wn)[4], const 
     };
 #pragma unroll
     for (int d = 0; d < 8; ++d) item(Yp[0], 0, d, false);        // block 0's pieces feed the first MFMAs
-    HSTAMP(FWD ? 24 : 27);
 #pragma unroll
     for (int b = 0; b < 8; ++b) {
 #pragma unroll
@@ -278,7 +248,6 @@ __device__ __forceinline__ void stream_layer(LStream &ls, v4f32 (&wn)[4], const 
             }
         }
     }
-    HSTAMP(FWD ? 25 : 28);
 }
 
 // one 32-feature output block from a 256-feature input on two alternating accumulators (16 K-steps x [h l]): z = za + zb
@@ -359,7 +328,7 @@ __global__ __launch_bounds__(256, 1) void trunk_f16l_kernel(const TrunkParams p,
     const int tid = threadIdx.x;
     const int lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    __shared__ __attribute__((aligned(16))) v4f32 wbuf[NBUF * CH * 64];      // the shared weight stream: 3 slots of 32 KiB (4 of 16 KiB with -DDGDM_F16_CHUNK=16)
+    __shared__ __attribute__((aligned(16))) v4f32 wbuf[NBUF * CH * 64];      // the shared weight stream: 4 slots of 16 KiB
     // the stack's biases and the output layer's three rows, copied once: read from global memory where they are used, every one of these
     // 32-load bursts is a full memory round trip behind the stream's prefetches (3.5 k cycles per layer prologue, 15 k for the output phase)
     __shared__ __attribute__((aligned(16))) v4f32 small[(8 * 256 + 768) / 4];
@@ -383,7 +352,6 @@ __global__ __launch_bounds__(256, 1) void trunk_f16l_kernel(const TrunkParams p,
     uint32_t m[4];
     int slot = 0;
     int E = 0;                                                // Y = true values x 2^E for this lane's row
-    HSTAMP(0);
     const wrsrc_t rsF = weight_rsrc(p.Wfwd, p.fwd_bytes);
     LStream ls;
     ls.buf = (lds_f4_t *)wbuf; ls.voff = voff; ls.wave = wave; ls.lane = lane;
@@ -421,10 +389,8 @@ __global__ __launch_bounds__(256, 1) void trunk_f16l_kernel(const TrunkParams p,
         // largest entry); layer 2's input arrives block by block and takes its row scale from a bound (below)
 #pragma unroll
         for (int j = 0; j < 4; ++j) wn[j] = ls.read(j);
-        HSTAMP(36);
         Act2 X;
         const int kx = split_rows(Y, X);
-        HSTAMP(37);
         const float un1 = pow2f(-(kx + sc.ew_l1));            // layer-1 accumulators -> true values
         // The f16 scale of layer 2's input rows, from a bound on layer 1's output that is known now (the file header says why a bound
         // does): |z_j| <= max |A[finger]| + max |P[cell]| + ||W1o_j||_1 max |x|, and max |x| < 2^(13 - kx) by the choice of kx.
@@ -469,15 +435,12 @@ __global__ __launch_bounds__(256, 1) void trunk_f16l_kernel(const TrunkParams p,
             }
         };
         table_terms_request(0);
-        HSTAMP(38);
         for (int blk = 0; blk < 16; blk += 2) {
             uint32_t bits2 = 0;
 #pragma unroll
             for (int e = 0; e < 2; ++e) {
                 const int kb = blk + e;
-                if (kb == 8) HSTAMP(32);
                 f32x16 z = block_out(ls, wn, X, zero, zero, [](int) __attribute__((always_inline)) {});      // leaves wn = entries 0 .. 3 of layer 2's pass
-                if (kb == 8) HSTAMP(33);
                 table_terms();
                 table_terms_request((kb + 1) & 15);
 #pragma unroll
@@ -495,7 +458,6 @@ __global__ __launch_bounds__(256, 1) void trunk_f16l_kernel(const TrunkParams p,
                     split2(lo * f2, hi * f2, a, bb);
                     ah[d / 4][d % 4] = a; al[d / 4][d % 4] = bb;
                 }
-                if (kb == 8) HSTAMP(34);
                 // layer 2: 32 entries = two chunks, eight groups of [A.h A.l B.h B.l]; the group's operands are read one group ahead (wn holds
                 // the first group on entry, the next pass' entries 0 .. 3 - layer 1's next block, or the stack's first group - on return)
 #pragma unroll
@@ -510,7 +472,6 @@ __global__ __launch_bounds__(256, 1) void trunk_f16l_kernel(const TrunkParams p,
                     F16_STEP(Y[2 * pp], Y[2 * pp + 1], w, ah[sx], al[sx]);
                     __builtin_amdgcn_sched_barrier(0);
                 }
-                if (kb == 8) HSTAMP(35);
             }
             smask[blk / 2][tid] = bits2;
         }
@@ -522,12 +483,10 @@ __global__ __launch_bounds__(256, 1) void trunk_f16l_kernel(const TrunkParams p,
     }
     constexpr int BASE = (KIND == 3) ? 8 : 0;
     f32x16 Z[8];
-    HSTAMP(1);
     for (int l = 0; l < p.n_mid; ++l) {
         stream_layer<true, true>(ls, wn, sbias + 64 * l, Y, Z, smask, BASE + 4 * l, tid, h4, E, sc.ew_mid[l]);
 #pragma unroll
         for (int o = 0; o < 8; ++o) Y[o] = Z[o];
-        HSTAMP(2 + l);
     }
     slot = BASE + 4 * p.n_mid;
     relu_mask<8>(Y, m);
@@ -579,12 +538,10 @@ __global__ __launch_bounds__(256, 1) void trunk_f16l_kernel(const TrunkParams p,
     for (int j = 0; j < 4; ++j) wn[j] = ls.read(j);
 
     // ---- backward through the 256 -> 256 layers
-    HSTAMP(10);
     for (int l = p.n_mid - 1; l >= 0; --l) {
         stream_layer<false, false>(ls, wn, nullptr, Y, Z, smask, BASE + 4 + 4 * l, tid, h4, E, sc.ew_mid[l]);
 #pragma unroll
         for (int o = 0; o < 8; ++o) Y[o] = Z[o];
-        HSTAMP(11 + (p.n_mid - 1 - l));
     }
 #pragma unroll
     for (int i = 0; i < 4; ++i) m[i] = smask[BASE + i][tid];
@@ -605,7 +562,6 @@ __global__ __launch_bounds__(256, 1) void trunk_f16l_kernel(const TrunkParams p,
         }
     } else {
         // 3-D: one more layer back (256 -> 512), block by block, straight into the fold
-        HSTAMP(40);
         Act2 X;
         const int kt = split_rows(Y, X);
         const float un = pow2f(-(E + kt + sc.ew_l2));
@@ -625,22 +581,15 @@ __global__ __launch_bounds__(256, 1) void trunk_f16l_kernel(const TrunkParams p,
                 if (n == ROWS_SUM_LANE && live) *reinterpret_cast<float4 *>(dst + 32 * kb + 8 * (rr / 4) + h4) = acc;
             }
         };
-        HSTAMP(41);
         for (int kb = 1; kb < 16; ++kb) {
-            if (kb == 8) HSTAMP(42);
             const uint32_t bits = smask[(kb - 1) / 2][tid] >> (16 * ((kb - 1) & 1));
             const f32x16 gn = block_out(ls, wn, X, zero, zero, [&](const int ks) __attribute__((always_inline)) { fold_one(ks, kb - 1, bits); });
             g = gn;
-            if (kb == 8) HSTAMP(43);
         }
         const uint32_t bits = smask[7][tid] >> 16;
 #pragma unroll
         for (int rr = 0; rr < 16; ++rr) fold_one(rr, 15, bits);
     }
-    HSTAMP(20);
-#ifdef DGDM_F16_STAMPS
-    if (blockIdx.x == gridDim.x / 2 && tid == 0) { g_f16l_stamps[21] = ls.stall_vm; g_f16l_stamps[22] = ls.stall_bar; }
-#endif
 }
 
 int trunk_f16l_launch(int kind, const TrunkParams &p, const TrunkF16Scales &sc, hipStream_t s) {
@@ -655,18 +604,6 @@ int trunk_f16l_launch(int kind, const TrunkParams &p, const TrunkF16Scales &sc, 
     else hipLaunchKernelGGL((trunk_f16l_kernel<3>), dim3(grid), dim3(256), 0, s, p, sc);
     DGDM_HIP_CHECK(hipGetLastError());
     prof_end(s, DGDM_STAGE_TRUNK, rows * per_row);
-#ifdef DGDM_F16_STAMPS
-    {
-        long long st[48];
-        hipStreamSynchronize(s);
-        hipMemcpyFromSymbol(st, HIP_SYMBOL(g_f16l_stamps), sizeof(st));
-        fprintf(stderr, "f16l stamps kind %d:", kind);
-        long long prev = st[0];
-        for (int i = 1; i <= 20; ++i) if (st[i]) { fprintf(stderr, " [%d]%lld", i, st[i] - prev); prev = st[i]; }
-        fprintf(stderr, " total %lld; advance(): counted wait %lld, barrier %lld; last fwd layer: prologue %lld first items %lld loop %lld; bwd: %lld %lld %lld; front block 8: layer-1 block %lld, epilogue %lld, layer-2 pass %lld; before the front loop: stream start + embedding row %lld, its split %lld, bias + first table terms %lld; tail: split + first block %lld, block 8 with the fold of block 7 %lld\n", st[20] - st[0], st[21], st[22],
-                st[23] - st[1 + p.n_mid - 1], st[24] - st[23], st[25] - st[24], st[26] - st[10 + p.n_mid - 1], st[27] - st[26], st[28] - st[27], st[33] - st[32], st[34] - st[33], st[35] - st[34], st[36] - st[0], st[37] - st[36], st[38] - st[37], st[41] - st[40], st[43] - st[42]);
-    }
-#endif
     return DGDM_OK;
 }
 

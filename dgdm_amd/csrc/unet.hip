@@ -21,15 +21,10 @@
 namespace dgdm {
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
-#ifndef UNET_THREADS
-#define UNET_THREADS 512
-#endif
-#ifndef DGDM_UNET_SLAB_GROUPS
-#define DGDM_UNET_SLAB_GROUPS 2
-#endif
+constexpr int UNET_THREADS = 512;
 // f16x3 convolutions: channel groups of 32 split per slab pass (conv_mfma_f16x3; every width is a multiple of 64).  Measured per 1024
 // samples at L = 42: 1.52 ms with one group per pass, 1.43 with two (half the barriers).
-constexpr int UNET_SLAB_GROUPS = DGDM_UNET_SLAB_GROUPS;
+constexpr int UNET_SLAB_GROUPS = 2;
 constexpr int UNET_ROW_PAD = 8;      // LDS activation rows are C + 8 floats: see the header comment (bank mapping of the B-operand reads)
 // Activations live in LDS.  The device functions below are real calls (not inlined into the kernel), so a plain `float *`
 // parameter would be a generic pointer: every access a flat_load/flat_store with 64-bit address arithmetic on the VALU
@@ -41,22 +36,6 @@ typedef __attribute__((address_space(3))) f32x4 lds_f4;
 // also counts on lgkmcnt, so every wait for an LDS operand would wait for the weight prefetch as well.
 typedef const __attribute__((address_space(1))) f32x4 glb_f4;
 
-// Experiment build only (DGDM_EXTRA_FLAGS=-DDGDM_UNET_CLOCKS): thread 0 of every workgroup stamps the shader clock at every phase
-// boundary; dgdm_debug_unet_clocks copies the stamps out (scripts/unet_phases.py prints the mean time per phase).
-#ifdef DGDM_UNET_CLOCKS
-__device__ long long unet_clk[1024 * 64];
-#define UCLK()                                                                                              \
-    do {                                                                                                    \
-        if (threadIdx.x == 0 && blockIdx.x < 1024 && clk_i < 64) unet_clk[blockIdx.x * 64 + clk_i] = (long long)__builtin_readcyclecounter(); \
-        ++clk_i;                                                                                            \
-    } while (0)
-#define UCLK_ARG , int &clk_i
-#define UCLK_PASS , clk_i
-#else
-#define UCLK() do {} while (0)
-#define UCLK_ARG
-#define UCLK_PASS
-#endif
 
 __device__ __forceinline__ f32x4 mfma16(float a, float b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
 
@@ -591,7 +570,7 @@ struct Bufs { lds_f *A, *B, *C, *D, *film, *cond, *tmp, *xin, *scr; int bf16, sl
 // ConditionalResidualBlock1D.forward (diffusion_utils.py:101-120): x(in, cin channels) -> out; t1 scratch.
 // `out` may be a wider buffer (row stride CPout >= cout + 4): the concat buffer of the up path.
 __device__ void res_block(const UnetRes &w, const lds_f *in, lds_f *t1, lds_f *out, int CPout, int L, int cond_dim, int groups, const Bufs s,
-                          const lds_f *film UCLK_ARG) {
+                          const lds_f *film) {
     const int CPi = w.cin + UNET_ROW_PAD, CPo = w.cout + UNET_ROW_PAD;
     // the block's FiLM vector (cond_encoder: Mish -> Linear(cond_dim, 2 cout)) was computed with the other seven before the first block
     if (w.cin == 1) {   // first block: single input channel held in s.xin[pos + 2]; conv k5 and the 1x1 residual on the VALU
@@ -607,17 +586,13 @@ __device__ void res_block(const UnetRes &w, const lds_f *in, lds_f *t1, lds_f *o
     }
     zero_halo(t1, CPo, w.cout, L);
     __syncthreads();
-    UCLK();
     gn_mish_film(t1, CPo, w.cout, L, groups, w.g0_w, w.g0_b, film);
     __syncthreads();
-    UCLK();
     conv<0>(conv_args(w.c1_w, w.c1_b, w.cout, w.cout, 5, 2, 1, s.bf16, w.c1_e, s.scr, s.slab_groups), t1, CPo, out, CPout, L);
     zero_halo(out, CPout, w.cout, L);
     __syncthreads();
-    UCLK();
     gn_mish_film(out, CPout, w.cout, L, groups, w.g1_w, w.g1_b, nullptr);
     __syncthreads();
-    UCLK();
     if (w.cin == 1) {
         for (int i = threadIdx.x; i < L * w.cout; i += blockDim.x) {
             const int l = i / w.cout, co = i - l * w.cout;
@@ -632,7 +607,6 @@ __device__ void res_block(const UnetRes &w, const lds_f *in, lds_f *t1, lds_f *o
         }
     }
     __syncthreads();
-    UCLK();
 }
 
 // `pp` points at the UnetParams in device memory: passing the struct by value and handing references to its members to the
@@ -657,10 +631,6 @@ __global__ __launch_bounds__(UNET_THREADS) void unet_kernel(const UnetParams *__
     s.bf16 = p.bf16;
     s.slab_groups = slab_groups;
     const int G = p.groups;
-#ifdef DGDM_UNET_CLOCKS
-    int clk_i = 0;
-#endif
-    UCLK();
 
     // ---- diffusion_step_encoder: SinusoidalPosEmb -> Linear -> Mish -> Linear   (diffusion_utils.py:25-37,149-154)
     {
@@ -695,27 +665,24 @@ __global__ __launch_bounds__(UNET_THREADS) void unet_kernel(const UnetParams *__
         }
     }
     __syncthreads();
-    UCLK();      // step encoder + FiLM vectors done
 
     const int CP0 = p.d0 + UNET_ROW_PAD, CP1 = p.d1 + UNET_ROW_PAD, CPcat = 2 * p.d1 + UNET_ROW_PAD;
-    res_block(p.res[0], nullptr, s.B, s.C, CP0, L, p.dsed, G, s, s.film + 0 * 2 * p.cmax UCLK_PASS);     // down0.0   1 -> d0
-    res_block(p.res[1], s.C, s.B, s.D, CP0, L, p.dsed, G, s, s.film + 1 * 2 * p.cmax UCLK_PASS);         // down0.1   d0 -> d0   (its skip is never consumed, :264-278)
+    res_block(p.res[0], nullptr, s.B, s.C, CP0, L, p.dsed, G, s, s.film + 0 * 2 * p.cmax);     // down0.0   1 -> d0
+    res_block(p.res[1], s.C, s.B, s.D, CP0, L, p.dsed, G, s, s.film + 1 * 2 * p.cmax);         // down0.1   d0 -> d0   (its skip is never consumed, :264-278)
     conv<0>(conv_args(p.down_w, p.down_b, p.d0, p.d0, 3, 1, 2, p.bf16, p.down_e, s.scr, s.slab_groups), s.D, CP0, s.B, CP0, L2);       // Downsample1d (:42)
     zero_halo(s.B, CP0, p.d0, L2);
     __syncthreads();
-    UCLK();      // downsample conv
-    res_block(p.res[2], s.B, s.C, s.D, CP1, L2, p.dsed, G, s, s.film + 2 * 2 * p.cmax UCLK_PASS);        // down1.0   d0 -> d1
-    res_block(p.res[3], s.D, s.B, s.C, CP1, L2, p.dsed, G, s, s.film + 3 * 2 * p.cmax UCLK_PASS);        // down1.1   -> skip, stays in C until the concat
-    res_block(p.res[4], s.C, s.B, s.D, CP1, L2, p.dsed, G, s, s.film + 4 * 2 * p.cmax UCLK_PASS);        // mid0
-    res_block(p.res[5], s.D, s.B, s.A, CPcat, L2, p.dsed, G, s, s.film + 5 * 2 * p.cmax UCLK_PASS);      // mid1 -> channels [0, d1) of the concat buffer
+    res_block(p.res[2], s.B, s.C, s.D, CP1, L2, p.dsed, G, s, s.film + 2 * 2 * p.cmax);        // down1.0   d0 -> d1
+    res_block(p.res[3], s.D, s.B, s.C, CP1, L2, p.dsed, G, s, s.film + 3 * 2 * p.cmax);        // down1.1   -> skip, stays in C until the concat
+    res_block(p.res[4], s.C, s.B, s.D, CP1, L2, p.dsed, G, s, s.film + 4 * 2 * p.cmax);        // mid0
+    res_block(p.res[5], s.D, s.B, s.A, CPcat, L2, p.dsed, G, s, s.film + 5 * 2 * p.cmax);      // mid1 -> channels [0, d1) of the concat buffer
     for (int i = t; i < (L2 + 4) * p.d1; i += blockDim.x) {           // torch.cat((x, h.pop()), dim=1) (:275): skip -> channels [d1, 2 d1)
         const int r = i / p.d1, c = i - r * p.d1;
         s.A[r * CPcat + p.d1 + c] = s.C[r * CP1 + c];
     }
     __syncthreads();
-    UCLK();      // concat copy
-    res_block(p.res[6], s.A, s.B, s.D, CP0, L2, p.dsed, G, s, s.film + 6 * 2 * p.cmax UCLK_PASS);        // up0.0   2*d1 -> d0
-    res_block(p.res[7], s.D, s.B, s.C, CP0, L2, p.dsed, G, s, s.film + 7 * 2 * p.cmax UCLK_PASS);        // up0.1
+    res_block(p.res[6], s.A, s.B, s.D, CP0, L2, p.dsed, G, s, s.film + 6 * 2 * p.cmax);        // up0.0   2*d1 -> d0
+    res_block(p.res[7], s.D, s.B, s.C, CP0, L2, p.dsed, G, s, s.film + 7 * 2 * p.cmax);        // up0.1
     {   // Upsample1d: ConvTranspose1d(d0, d0, 4, 2, 1) (:51): out[2 li] = W1 in[li] + W3 in[li-1];  out[2 li + 1] = W2 in[li] + W0 in[li+1]
         ConvArgs e = conv_args(p.up_w_even, p.up_b, p.d0, p.d0, 2, 0, 1, p.bf16, p.up_e_even, s.scr, s.slab_groups);
         e.ioff0 = 0; e.iostep = -1; e.ostride = 2; e.ooff = 0;
@@ -725,20 +692,16 @@ __global__ __launch_bounds__(UNET_THREADS) void unet_kernel(const UnetParams *__
         conv<0>(o, s.C, CP0, s.A, CP0, L2);
         zero_halo(s.A, CP0, p.d0, L);                                 // 2*L2 == L (checked by the launcher)
         __syncthreads();
-        UCLK();  // upsample convs
     }
     conv<0>(conv_args(p.fin_w, p.fin_b, p.d0, p.d0, 5, 2, 1, p.bf16, p.fin_e, s.scr, s.slab_groups), s.A, CP0, s.B, CP0, L);          // final_conv.0
     __syncthreads();
-    UCLK();      // final conv
     gn_mish_film(s.B, CP0, p.d0, L, G, p.fin_gw, p.fin_gb, nullptr);
     __syncthreads();
-    UCLK();      // final GroupNorm
     for (int l = t; l < L; l += blockDim.x) {                         // final_conv.1: Conv1d(d0, 1, 1)
         float acc = 0.f;
         for (int c = 0; c < p.d0; ++c) acc = fmaf(p.out_w[c], s.B[(l + 2) * CP0 + c], acc);
         eps[(size_t)b * L + l] = acc + p.out_b[0];
     }
-    UCLK();          // output conv
 }
 
 // ================================================================================================ batched form (f16x3, large batches)
@@ -753,14 +716,6 @@ __global__ __launch_bounds__(UNET_THREADS) void unet_kernel(const UnetParams *__
 // chunked accumulation, the same per-(sample, convolution input) power-of-two scale - its max now comes from the producing launch's
 // epilogue -, gn_group as it is): the two forms return the same bits (tests/test_gpu_parity.py::test_unet_batched_equals_per_sample).
 constexpr int UB_THREADS = 512;
-#ifdef DGDM_UB_CLOCKS
-// experiment build: workgroup 0's thread 0 stamps the shader clock at phase boundaries of the launch numbered DGDM_UB_CLOCKS (printed by the launcher)
-__device__ long long g_ub_clk[64];
-__device__ int g_ub_clk_n;
-#define UBCLK(A_) do { if ((A_).clk_on && blockIdx.x == 0 && threadIdx.x == 0) { const int i_ = g_ub_clk_n; if (i_ < 64) { g_ub_clk[i_] = (long long)__builtin_readcyclecounter(); g_ub_clk_n = i_ + 1; } } } while (0)
-#else
-#define UBCLK(A_) do { } while (0)
-#endif
 typedef const __attribute__((address_space(1))) float glb_f;
 typedef __attribute__((address_space(3))) int lds_i;
 typedef __attribute__((address_space(3))) uint32_t lds_u;
@@ -790,7 +745,6 @@ struct UbArgs {
     float *out; int out_ld;                     // [B][Lout + 4][out_ld] (channel offset applied)
     float *amax_out;                            // [B]
     const float *fin_w, *fin_b; float *eps;     // final 1x1 convolution -> eps [B][Lout] instead of `out`
-    int clk_on;                                 // experiment build (DGDM_UB_CLOCKS): this launch stamps its phases
 };
 
 __device__ __forceinline__ int scale_exp_of(float mm) {      // input_scale_exp's exponent for a row set whose largest magnitude is mm
@@ -800,12 +754,6 @@ __device__ __forceinline__ int scale_exp_of(float mm) {      // input_scale_exp'
 
 // One convolution pass of the batched kernel: conv_mfma_f16x3's arithmetic over ns samples.  Waves 0-3 / 4-7 take the lower / upper half
 // of the position tiles, wave & 3 picks MT of the cout / 16 output tiles.
-#ifdef DGDM_UB_CLOCKS
-__device__ int g_ub_clk_live;
-#define UBCLK2() do { if (g_ub_clk_live && blockIdx.x == 0 && threadIdx.x == 0) { const int i_ = g_ub_clk_n; if (i_ < 64) { g_ub_clk[i_] = (long long)__builtin_readcyclecounter(); g_ub_clk_n = i_ + 1; } } } while (0)
-#else
-#define UBCLK2() do { } while (0)
-#endif
 template <int NT, int MT, bool SPLIT>
 __device__ void ub_conv(const UbPass &a, const int S, const int ns, const int b0, const lds_i *kxs, lds_f *stage, const int CPo, const int LoutS /* output positions per sample */,
                         const int cout, lds_u4 *slab, const bool from_lds, const lds_f *lin /* from_lds: the input rows in LDS ([S][Lin + 4][lin_ld], the stage itself); else a.in.  (A flag,
@@ -893,10 +841,6 @@ __device__ void ub_conv(const UbPass &a, const int S, const int ns, const int b0
             }
         }
         __syncthreads();
-        UBCLK2();                                            // slab of this pass filled
-#ifdef DGDM_UB_EXP_NOMFMA
-        if (S > 0) { it += GS * ntaps; continue; }           // timing experiment (wrong results): everything but the MFMA loop
-#endif
         for (int gt = 0; gt < GS * ntaps; ++gt, ++it) {
             const int gg = gt >= ntaps ? 1 : 0, t = gt - gg * ntaps;
             f16x8_u ah[MT], al[MT];
@@ -935,7 +879,6 @@ __device__ void ub_conv(const UbPass &a, const int S, const int ns, const int b0
                     for (int nt = 0; nt < NT; ++nt) { tot[m][nt] += acc[m][nt]; acc[m][nt] = (f32x4)(0.f); }
             }
         }
-        UBCLK2();                                            // this pass' MFMAs issued
     }
 #pragma unroll
     for (int m = 0; m < MT; ++m) {
@@ -983,10 +926,6 @@ __global__ __launch_bounds__(UB_THREADS) void ub_layer_kernel(const UbArgs A) {
     if (A.film)
         for (int i = t; i < ns * 2 * cout; i += blockDim.x) { const int sm = i / (2 * cout); filmL[i] = A.film[(size_t)A.film_idx[b0 + sm] * A.film_ld + (i - sm * 2 * cout)]; }
     if (t < 8) amx[t] = 0u;
-#ifdef DGDM_UB_CLOCKS
-    if (blockIdx.x == 0 && t == 0) { g_ub_clk_live = A.clk_on; if (A.clk_on) g_ub_clk_n = 0; }
-#endif
-    UBCLK(A);                                                      // [0] start
     if (A.fuse)
         for (int i = t; i < S * 4 * CPo; i += blockDim.x) { const int r = i / CPo, sm = r >> 2, h = r & 3; stage[(sm * Rso + (h < 2 ? h : Lout + h)) * CPo + (i - r * CPo)] = 0.f; }
     auto gn = [&](const float *gw, const float *gb, bool film, bool want_amax) __attribute__((always_inline)) {
@@ -1014,30 +953,20 @@ __global__ __launch_bounds__(UB_THREADS) void ub_layer_kernel(const UbArgs A) {
                 kxs[t] = scale_exp_of(mm);
             }
             __syncthreads();
-            UBCLK(A);                                              // amax -> kxs
             ub_conv_dispatch(a, S, ns, b0, kxs, stage, CPo, Lout, cout, slab);
         }
         __syncthreads();
-        UBCLK(A);                                                  // pass p done (epilogue in the stage)
         if (p == 0) {
-#ifndef DGDM_UB_EXP_NOGN
             if (A.gn_w) { gn(A.gn_w, A.gn_b, A.film != nullptr, A.fuse != 0); __syncthreads(); }
-#endif
-            UBCLK(A);                                              // GroupNorm + Mish (+ FiLM)
             if (A.fuse) {
                 // t1 is in the stage, its per-sample magnitude (what the unfused form's producer wrote to amax) came out of the GroupNorm pass
                 if (t < S) { kxs[t] = scale_exp_of(t < ns ? __uint_as_float(amx[t]) : 0.f); }
                 __syncthreads();
                 if (t < 8) amx[t] = 0u;
-                UBCLK(A);                                          // t1's magnitude
                 ub_conv_dispatch(A.c1, S, ns, b0, kxs, stage, CPo, Lout, cout, slab, true, stage, CPo);
                 __syncthreads();
-                UBCLK(A);                                          // second convolution done
-#ifndef DGDM_UB_EXP_NOGN
                 gn(A.gn1_w, A.gn1_b, false, false);
                 __syncthreads();
-#endif
-                UBCLK(A);                                          // GroupNorm + Mish of the block's output
             }
         }
     }
@@ -1094,7 +1023,6 @@ __global__ __launch_bounds__(UB_THREADS) void ub_layer_kernel(const UbArgs A) {
     }
     __syncthreads();
     if (t < ns && A.amax_out) A.amax_out[b0 + t] = __uint_as_float(amx[t]);
-    UBCLK(A);                                                      // residual + store
 }
 
 // step encoder + the eight FiLM vectors of every sample (unet_kernel's first two phases): film [B][8][2 cmax].  They depend on the sample's
@@ -1181,31 +1109,12 @@ int unet_launch_batched(const UnetParams &q, const UnetParams *q_dev, float *ws,
         a.istride = 1; a.ioff0 = -2; a.iostep = 1; a.ostride = 1; a.ooff = 0; a.add = 0;
         return a;
     };
-    int launch_no = 0;
     auto launch = [&](UbArgs &A, int Lin) -> int {
         A.B = B; A.S = S; A.groups = q.groups;
-#ifdef DGDM_UB_CLOCKS
-        A.clk_on = (launch_no == DGDM_UB_CLOCKS && B >= 512) ? 1 : 0;
-#endif
-        ++launch_no;
         const size_t lds = ub_lds_bytes(S, Lin, A.Lout, A.cout);
         DGDM_REQUIRE(lds <= 160 * 1024, DGDM_EINVAL, "unet_launch_batched: %zu B of LDS", lds);
         hipLaunchKernelGGL(ub_layer_kernel, dim3((B + S - 1) / S), dim3(UB_THREADS), lds, s, A);
         DGDM_HIP_CHECK(hipGetLastError());
-#ifdef DGDM_UB_CLOCKS
-        if (A.clk_on) {
-            static int printed = 0;
-            long long st[64]; int n = 0;
-            hipStreamSynchronize(s);
-            hipMemcpyFromSymbol(st, HIP_SYMBOL(g_ub_clk), sizeof(st));
-            hipMemcpyFromSymbol(&n, HIP_SYMBOL(g_ub_clk_n), sizeof(n));
-            if (printed++ < 3) {
-                fprintf(stderr, "ub stamps launch %d (Lout %d cout %d passes %d fuse %d): ", launch_no - 1, A.Lout, A.cout, A.n_pass, A.fuse);
-                for (int i = 1; i < n && i < 64; ++i) fprintf(stderr, "%lld ", st[i] - st[i - 1]);
-                fprintf(stderr, "| total %lld\n", n > 0 ? st[n - 1] - st[0] : 0LL);
-            }
-        }
-#endif
         return DGDM_OK;
     };
     int rc;
@@ -1294,8 +1203,3 @@ int unet_launch(const UnetParams &p, const UnetParams *p_dev, bool f16x3, const 
 
 }  // namespace dgdm
 
-#ifdef DGDM_UNET_CLOCKS
-extern "C" int dgdm_debug_unet_clocks(long long *out_host, int n) {
-    return hipMemcpyFromSymbol(out_host, HIP_SYMBOL(dgdm::unet_clk), sizeof(long long) * (size_t)n) == hipSuccess ? 0 : -3;
-}
-#endif
