@@ -124,6 +124,13 @@ PROTOTYPES = {
     "dgdm_trainer3d_running_stats_count": (C.c_int64, [_P]),
     "dgdm_trainer3d_running_stats": (C.c_int, [_P, _P, C.c_int64, C.c_int, _P]),
     "dgdm_trainer3d_debug_read": (C.c_int, [_P, C.c_int, _P, C.c_int64, _P]),
+    "dgdm_mesh_read_obj": (C.c_int, [C.c_char_p, C.POINTER(_P)]),
+    "dgdm_mesh_num_vertices": (C.c_int64, [_P]),
+    "dgdm_mesh_num_triangles": (C.c_int64, [_P]),
+    "dgdm_mesh_copy": (C.c_int, [_P, _P, _P]),
+    "dgdm_mesh_destroy": (None, [_P]),
+    "dgdm_mesh_sample_workspace_bytes": (C.c_int64, [_P, C.c_int]),
+    "dgdm_mesh_sample_points": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_uint64, _P, C.c_int64, _P, _P, C.c_int64, _P]),
 }
 
 _lib = None

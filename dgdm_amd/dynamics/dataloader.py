@@ -1,9 +1,12 @@
 """``DynamicsDataset`` of the dynamics-model training driver (reference: dynamics/dataloader.py:7-78): one ``.npz`` per simulated
 (gripper, object) pair holding the pose grid it was rolled out on.  Host code.  2-D: the object's contour vertices ride in the file.
 3-D (--fingers_3d, :57-67): the file names its object; the reference samples ``object_max_num_vertices`` points from
-``<object_mesh_dir>/<name>/model.obj`` with open3d (dynamics/utils.py, asset tooling outside this package: open3d is not in the image) -
-here the points are read from ``<object_mesh_dir>/<name>/points.npy`` ([n >= object_max_num_vertices, 3] metres, the first
-object_max_num_vertices rows are used) or from an ``object_points`` entry of the data file itself.
+``<object_mesh_dir>/<name>/model.obj`` with open3d (dynamics/utils.py).  Here the points come, in this order, from
+``<object_mesh_dir>/<name>/points.npy`` ([n >= object_max_num_vertices, 3] metres, the first object_max_num_vertices rows are used), from
+an ``object_points`` entry of the data file itself, or from ``<object_mesh_dir>/<name>/model.obj`` sampled on the GPU (dynamics/utils.py,
+csrc/mesh.hip).  The meshes are sampled eagerly, in ``__init__``, in one batched call - every subdirectory with a model.obj and no
+points.npy - and only host arrays are kept, so that forked DataLoader workers never touch the GPU; a second dataset over the same
+directory (the validation set) reuses the clouds of the first.
 
 File format, as the reference's simulator writes it (``np.savez(path, dict)`` -> key ``arr_0``, a pickled dict):
     ctrlpts [n, 2] metres, delta_theta [cells], delta_pos [cells, 2], obj_theta [cells] in [0, 2 pi), obj_pos [cells, >=2] metres,
@@ -36,6 +39,27 @@ def _to_unit(a: np.ndarray, box: Sequence[Sequence[float]]) -> np.ndarray:
     return out
 
 
+_MESH_CLOUDS: Dict[tuple, np.ndarray] = {}     # (path, size, mtime_ns, num_points) -> float64 cloud in metres, for this process
+
+
+def _mesh_clouds(mesh_dir: str, num_points: int) -> Dict[str, np.ndarray]:
+    """{name: (num_points, 3) metres} for every subdirectory of mesh_dir with a model.obj and no points.npy; the meshes not sampled
+    before in this process are sampled in one batched device call."""
+    from . import utils
+    names = sorted(n for n in os.listdir(mesh_dir) if os.path.isfile(os.path.join(mesh_dir, n, utils.MESH_FILE))
+                   and not os.path.isfile(os.path.join(mesh_dir, n, 'points.npy')))
+    memo = {}
+    for n in names:
+        st = os.stat(os.path.join(mesh_dir, n, utils.MESH_FILE))
+        memo[n] = (os.path.abspath(os.path.join(mesh_dir, n, utils.MESH_FILE)), st.st_size, st.st_mtime_ns, int(num_points))
+    todo = [n for n in names if memo[n] not in _MESH_CLOUDS]
+    if todo:
+        clouds = utils.sample_object_clouds(mesh_dir, todo, num_points)
+        for n, c in zip(todo, clouds):
+            _MESH_CLOUDS[memo[n]] = c
+    return {n: _MESH_CLOUDS[memo[n]] for n in names}
+
+
 class DynamicsDataset(Dataset):
     def __init__(self, dataset_dir: str, object_max_num_vertices: int = 10, fingers_3d: bool = False, gripper_box=None,
                  object_box=None, object_mesh_dir: str = "", **unused):
@@ -45,6 +69,7 @@ class DynamicsDataset(Dataset):
         self.object_box = object_box or (OBJECT_BOX_3D if fingers_3d else OBJECT_BOX_2D)
         self.object_max_num_vertices, self.object_mesh_dir, self.object_pts = object_max_num_vertices, object_mesh_dir, {}
         self.data_files = sorted(os.path.join(root, f) for root, _, files in os.walk(dataset_dir) for f in files if f.endswith('.npz'))
+        self.mesh_pts = _mesh_clouds(object_mesh_dir, object_max_num_vertices) if fingers_3d and object_mesh_dir and os.path.isdir(object_mesh_dir) else {}
 
     def __len__(self) -> int:
         return len(self.data_files)
@@ -60,9 +85,11 @@ class DynamicsDataset(Dataset):
                     pts = np.load(f)
                 elif 'object_points' in d:
                     pts = np.asarray(d['object_points'])
+                elif name in self.mesh_pts:
+                    pts = self.mesh_pts[name]
                 else:
-                    raise FileNotFoundError(f"3-D object '{name}': neither {f} nor an 'object_points' entry in {self.data_files[idx]} (the reference samples "
-                                            "the points from model.obj with open3d, which this package does not ship)")
+                    raise FileNotFoundError(f"3-D object '{name}': neither {f}, nor an 'object_points' entry in {self.data_files[idx]}, nor "
+                                            f"{os.path.join(self.object_mesh_dir or '', name, 'model.obj')}")
                 self.object_pts[name] = _to_unit(np.asarray(pts)[:self.object_max_num_vertices, :3], self.object_box)
             verts = torch.from_numpy(self.object_pts[name]).float()
         else:

@@ -7,6 +7,7 @@ PyTorch supplies device memory and the stream; every computation is a HIP kernel
 from __future__ import annotations
 
 import ctypes as C
+import os
 from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
@@ -366,6 +367,56 @@ def finger_decode_3d(samples: torch.Tensor, sample_size: int = 25, scale: float 
     s = _f32(samples).reshape(samples.shape[0], -1)
     out = torch.empty((s.shape[0], 2, sample_size * sample_size, 3), dtype=torch.float32, device=s.device)
     check(lib().dgdm_finger_decode_3d(dptr(s), s.shape[0], s.shape[1], int(sample_size), float(scale), float(offset), dptr(out), stream_ptr()))
+    return out
+
+
+def read_obj(path: str) -> Tuple[np.ndarray, np.ndarray]:
+    """Vertex positions (V, 3) float64 and triangles (T, 3) int32, 0-based, of an OBJ file in file order (the reader of
+    include/dgdm_hip.h: polygons fan-triangulated, everything but `v` / `f` ignored).  Host code; releases the GIL while it parses."""
+    h = C.c_void_p()
+    check(lib().dgdm_mesh_read_obj(os.fsencode(path), C.byref(h)))
+    try:
+        verts = np.empty((lib().dgdm_mesh_num_vertices(h), 3), dtype=np.float64)
+        tris = np.empty((lib().dgdm_mesh_num_triangles(h), 3), dtype=np.int32)
+        check(lib().dgdm_mesh_copy(h, verts.ctypes.data, tris.ctypes.data))
+    finally:
+        lib().dgdm_mesh_destroy(h)
+    return verts, tris
+
+
+def concat_meshes(meshes: Sequence[Tuple[np.ndarray, np.ndarray]]) -> Tuple[np.ndarray, np.ndarray, Tuple[np.ndarray, np.ndarray]]:
+    """[(verts (V_m, 3), tris (T_m, 3) local to the mesh), ...] -> the batch form of sample_mesh_points."""
+    nv = np.array([0] + [len(v) for v, _ in meshes], dtype=np.int64)
+    nt = np.array([0] + [len(t) for _, t in meshes], dtype=np.int64)
+    verts = np.concatenate([np.asarray(v, dtype=np.float64).reshape(-1, 3) for v, _ in meshes])
+    tris = np.concatenate([np.asarray(t, dtype=np.int32).reshape(-1, 3) for _, t in meshes])
+    return verts, tris, (np.cumsum(nv), np.cumsum(nt))
+
+
+def sample_mesh_points(verts, tris, offsets, keys, num_points: int, seed: int = 0) -> torch.Tensor:
+    """Surface point clouds of a batch of meshes, (M, num_points, 3) float64 on the current device: open3d's sample_points_uniformly
+    (dynamics/utils.py:14-18) under the sampling contract of include/dgdm_hip.h (DESIGN.md "Object clouds from meshes").
+    verts (V, 3) float64 and tris (T, 3) int32 (indices local to their mesh) are the meshes concatenated, host or device;
+    offsets = (vertex offsets, triangle offsets), each M + 1 int64 starting at 0 (concat_meshes builds all three);
+    keys: M uint64 mesh keys (callers use zlib.crc32 of the object name).  Synchronises the stream once."""
+    vo = np.ascontiguousarray(offsets[0], dtype=np.int64)
+    to = np.ascontiguousarray(offsets[1], dtype=np.int64)
+    k = np.ascontiguousarray(keys, dtype=np.uint64).reshape(-1)
+    M = len(to) - 1
+    if M < 1 or len(vo) != M + 1 or len(k) != M:
+        raise ValueError(f"sample_mesh_points: {len(vo)} vertex offsets, {len(to)} triangle offsets and {len(k)} keys (need M + 1, M + 1, M)")
+    dev = torch.device("cuda", torch.cuda.current_device())
+    v = torch.as_tensor(verts).to(device=dev, dtype=torch.float64).contiguous()
+    t = torch.as_tensor(tris).to(device=dev, dtype=torch.int32).contiguous()
+    if v.numel() != 3 * int(vo[-1]) or t.numel() != 3 * int(to[-1]):
+        raise ValueError(f"sample_mesh_points: {v.numel() // 3} vertices / {t.numel() // 3} triangles, the offsets say {int(vo[-1])} / {int(to[-1])}")
+    ws_bytes = lib().dgdm_mesh_sample_workspace_bytes(to.ctypes.data, M)
+    if ws_bytes < 0:
+        check(int(ws_bytes))
+    ws = torch.empty(int(ws_bytes), dtype=torch.uint8, device=dev)
+    out = torch.empty((M, int(num_points), 3), dtype=torch.float64, device=dev)
+    check(lib().dgdm_mesh_sample_points(dptr(v), dptr(t), vo.ctypes.data, to.ctypes.data, M, int(seed) & 0xFFFFFFFFFFFFFFFF, k.ctypes.data,
+                                        int(num_points), dptr(out), dptr(ws), int(ws_bytes), stream_ptr()))
     return out
 
 

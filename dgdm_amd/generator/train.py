@@ -11,8 +11,10 @@ fingers, which is what Lightning's ``trainer.validate`` does (:152-156).  ``--mo
 
 Assets the image does not have are substituted, loudly:
 * no checkpoint files  -> deterministic random-init weights (dgdm_amd.synth);
-* no Icons-50 / scanned meshes (and no open3d, cv2) -> synthetic contours / surface-sampled clouds with the same
-  normalisation; an ``--object_dir`` holding ``objects.npy`` ([n, vertices, 2|3], metres) is used when present.
+* no Icons-50 (and no cv2) -> synthetic contours with the same normalisation.
+3-D objects come from ``--object_dir``: ``objects.npy`` ([n, vertices, 2|3], metres) when present; otherwise, as in the reference,
+``<object_dir>/<name>/model.obj`` of the six test objects, sampled on the GPU (dynamics/utils.py, csrc/mesh.hip) - only when one of
+those meshes is missing are synthetic surface-sampled clouds used, and the stderr line names the missing meshes.
 """
 from __future__ import annotations
 
@@ -23,6 +25,7 @@ import numpy as np
 import torch
 
 from .. import synth
+from ..dynamics import utils as object_utils
 from ..dynamics.parser import parse
 from ..dynamics.profile_forward_2d import ProfileForward2DModel
 from ..dynamics.profile_forward_3d import ProfileForward3DModel
@@ -67,11 +70,20 @@ def _load_or_synth(path, spec, seed, what):
 def _objects(args, fingers_3d: bool):
     f = os.path.join(args.object_dir or "", "objects.npy")
     nv = args.object_max_num_vertices
+    lo, hi = (torch.tensor([-0.1, -0.1, 0.0]), torch.tensor([0.1, 0.1, 0.12])) if fingers_3d else (torch.tensor([-0.05] * 2), torch.tensor([0.05] * 2))
     if os.path.isfile(f):
         raw = torch.from_numpy(np.load(f)).float()
-        lo, hi = (torch.tensor([-0.1, -0.1, 0.0]), torch.tensor([0.1, 0.1, 0.12])) if fingers_3d else (torch.tensor([-0.05] * 2), torch.tensor([0.05] * 2))
         return (raw - lo) / (hi - lo) * 2.0 - 1.0, list(range(raw.shape[0]))            # generator/train.py:94-124
-    print("[dgdm_amd] no objects.npy under --object_dir - using synthetic objects", file=sys.stderr)
+    if fingers_3d:
+        # the reference's own inputs: <object_dir>/<name>/model.obj of the six test objects, sampled as sample_pts_from_mesh does (:100-109)
+        missing = [n for n in OBJECT_NAMES_3D if not os.path.isfile(os.path.join(args.object_dir or "", n, object_utils.MESH_FILE))]
+        if not missing:
+            raw = torch.from_numpy(object_utils.sample_object_clouds(args.object_dir, OBJECT_NAMES_3D, nv)).float()
+            return (raw - lo) / (hi - lo) * 2.0 - 1.0, list(OBJECT_NAMES_3D)
+        print(f"[dgdm_amd] no objects.npy and no {object_utils.MESH_FILE} under --object_dir for {', '.join(missing)} - using synthetic objects",
+              file=sys.stderr)
+    else:
+        print("[dgdm_amd] no objects.npy under --object_dir - using synthetic objects", file=sys.stderr)
     if fingers_3d:
         return torch.stack([synth.synth_object_3d(i, nv) for i in range(len(OBJECT_NAMES_3D))]), list(OBJECT_NAMES_3D)
     return torch.stack([synth.synth_object_2d(i, nv) for i in range(len(OBJECT_IDS))]), list(OBJECT_IDS)

@@ -275,6 +275,36 @@ int dgdm_finger_decode_2d(const float *samples_dev, int batch, int num_ctrl, int
 int dgdm_finger_decode_3d(const float *samples_dev, int batch, int num_ctrl, int sample_size, float scale, float offset,
                           float *surface_dev, void *stream);
 
+/* ------------------------------------------------------------------ object point clouds from scanned meshes
+ * sample_pts_from_mesh (dynamics/utils.py:14-18: open3d read_triangle_mesh + sample_points_uniformly), which the reference calls for
+ * the test objects of guided sampling (generator/train.py:100-109) and once per object name in dynamics training
+ * (dynamics/dataloader.py:57-63).  The sampling contract (DESIGN.md "Object clouds from meshes"), all in float64:
+ *   a_t = 0.5 |(v1 - v0) x (v2 - v0)|, A = sum a_t (A <= 0: DGDM_EINVAL naming the mesh), cdf_t = running sum of a_t / A,
+ *   n_t = round_half_away(cdf_t N); triangle t owns the output points n_{t-1} <= p < n_t (grouped by triangle in file order);
+ *   point p: r1, r2 = the uniforms (u >> 11) * 2^-53 of raw outputs 2p, 2p + 1 of numpy.random.Philox(key=[seed, key]) (Philox4x64-10,
+ *   block counter p / 2 + 1), a = 1 - sqrt r1, b = sqrt r1 (1 - r2), c = sqrt r1 r2, x = a v0 + b v1 + c v2.
+ * A point depends on its mesh, its index, seed and key only - not on the other meshes of the batch or the launch geometry.        */
+typedef struct DgdmMesh DgdmMesh;   /* vertex positions and triangles of one OBJ file (host memory) */
+/* OBJ reader: `v x y z [...]` (trailing values ignored) and `f` with i, i/j, i//k, i/j/k tokens, negative = relative, faces of more than 3
+ * corners fan-triangulated as (v0, vi, vi+1); every other statement ignored; CRLF accepted.  A bad index (0 or out of range), a face
+ * with fewer than 3 vertices, an unparsable number or a file without faces: DGDM_EINVAL, dgdm_last_error() = "path:line: reason".
+ * Thread-safe (no global state): several files may be read at once.                                                                  */
+int     dgdm_mesh_read_obj(const char *path, DgdmMesh **out);
+int64_t dgdm_mesh_num_vertices(const DgdmMesh *m);
+int64_t dgdm_mesh_num_triangles(const DgdmMesh *m);
+/* verts_host [num_vertices][3] float64, tris_host [num_triangles][3] int32 0-based, in file order */
+int     dgdm_mesh_copy(const DgdmMesh *m, double *verts_host, int32_t *tris_host);
+void    dgdm_mesh_destroy(DgdmMesh *m);
+/* Bytes of device workspace dgdm_mesh_sample_points needs for this batch; negative: bad offsets. */
+int64_t dgdm_mesh_sample_workspace_bytes(const int64_t *tri_offsets_host, int num_meshes);
+/* A batch of meshes: verts_dev [V][3] float64 and tris_dev [T][3] int32 (indices local to their mesh) concatenated; mesh m is vertices
+ * vert_offsets_host[m] .. [m+1] and triangles tri_offsets_host[m] .. [m+1] (both [num_meshes + 1], starting at 0); keys_host
+ * [num_meshes] -> out_dev [num_meshes][num_points][3] float64.  Synchronises the stream once (after the per-mesh areas are known);
+ * a mesh with no area or a vertex index outside its mesh fails the whole call with DGDM_EINVAL before anything is written to out_dev. */
+int     dgdm_mesh_sample_points(const double *verts_dev, const int32_t *tris_dev, const int64_t *vert_offsets_host,
+                                const int64_t *tri_offsets_host, int num_meshes, uint64_t seed, const uint64_t *keys_host,
+                                int64_t num_points, double *out_dev, void *workspace_dev, int64_t workspace_bytes, void *stream);
+
 /* ------------------------------------------------------------------ measurement hooks
  * When enabled, the launches of every stage of the path are bracketed by hipEvents on the stream they are launched on.
  * dgdm_prof_read_stage synchronises those events and returns, for one stage, the number of bracketed regions, their total
