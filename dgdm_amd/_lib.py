@@ -131,6 +131,11 @@ PROTOTYPES = {
     "dgdm_mesh_destroy": (None, [_P]),
     "dgdm_mesh_sample_workspace_bytes": (C.c_int64, [_P, C.c_int]),
     "dgdm_mesh_sample_points": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_uint64, _P, C.c_int64, _P, _P, C.c_int64, _P]),
+    "dgdm_icon_workspace_bytes": (C.c_int64, [C.c_int]),
+    "dgdm_icon_trace": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_int64, _P, _P]),
+    "dgdm_icon_fetch_contours": (C.c_int, [_P, C.c_int64, C.c_int, _P, _P, _P, C.c_int64, _P]),
+    "dgdm_contour_resample_workspace_bytes": (C.c_int64, [_P, C.c_int]),
+    "dgdm_contour_resample": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _P, _P, C.c_int64, _P]),
 }
 
 _lib = None

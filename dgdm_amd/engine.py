@@ -420,6 +420,79 @@ def sample_mesh_points(verts, tris, offsets, keys, num_points: int, seed: int = 
     return out
 
 
+def _check_value(rc: int) -> None:
+    """check(), with DGDM_EINVAL (a bad image or argument) raised as ValueError, as numpy / cv2 callers expect."""
+    if rc == _lib.EINVAL:
+        raise ValueError(lib().dgdm_last_error().decode("utf-8", "replace"))
+    check(rc)
+
+
+def resample_contours(points, offsets, num_points: int, rescale: bool = False) -> torch.Tensor:
+    """resample_contour (assets/icon_process.py) of a batch of contours, (M, num_points, 2) on the current device: int32, or float64
+    c / 128 * 0.1 - 0.05 when rescale.  points (total, 2) integer pixel pairs, host or device; offsets M + 1 int64 starting at 0,
+    contour m = rows offsets[m] .. offsets[m + 1] (at least one point each).  Contract: include/dgdm_hip.h, DESIGN.md §4.5b."""
+    off = np.ascontiguousarray(offsets, dtype=np.int64).reshape(-1)
+    M, n = len(off) - 1, int(num_points)
+    if M < 1:
+        raise ValueError("resample_contours: need at least one contour (offsets of length M + 1)")
+    if n < 1:
+        raise ValueError(f"resample_contours: num_points {n} (need >= 1)")
+    dev = torch.device("cuda", torch.cuda.current_device())
+    p = torch.as_tensor(points)
+    if p.dtype.is_floating_point or p.dtype.is_complex or p.dtype == torch.bool:
+        raise ValueError(f"resample_contours: integer points expected, got {p.dtype}")
+    p = p.to(device=dev, dtype=torch.int32).contiguous()
+    if p.numel() != 2 * int(off[-1]):
+        raise ValueError(f"resample_contours: {p.numel() // 2} points, the offsets say {int(off[-1])}")
+    ws_bytes = lib().dgdm_contour_resample_workspace_bytes(off.ctypes.data, M)
+    if ws_bytes < 0:
+        _check_value(int(ws_bytes))
+    ws = torch.empty(int(ws_bytes), dtype=torch.uint8, device=dev)
+    out = torch.empty((M, n, 2), dtype=torch.float64 if rescale else torch.int32, device=dev)
+    _check_value(lib().dgdm_contour_resample(dptr(p), off.ctypes.data, M, n, int(bool(rescale)), dptr(out), dptr(ws), int(ws_bytes),
+                                             stream_ptr()))
+    return out
+
+
+def icon_raw_contours(images) -> Tuple[torch.Tensor, np.ndarray]:
+    """The contour extract_contours keeps for each icon, before resampling: (points (total, 2) int32 on the current device, offsets
+    M + 1 int64 on the host), image m's contour = rows offsets[m] .. offsets[m + 1], in cv2's point order.  images (M, H, W, C) uint8,
+    host or device, C = 3 (BGR) or 4 (BGRA, alpha ignored).  An image without foreground raises ValueError naming its index.
+    Synchronises the stream twice (the counts, the points).  Contract: include/dgdm_hip.h, DESIGN.md §4.5b."""
+    im = torch.as_tensor(images)
+    if im.dtype != torch.uint8:
+        raise ValueError(f"icon_contours: uint8 images expected, got {im.dtype}")
+    if im.dim() != 4 or im.shape[3] not in (3, 4) or min(im.shape) < 1:
+        raise ValueError(f"icon_contours: images of shape (M, H, W, 3|4) expected, got {tuple(im.shape)}")
+    M, H, W, Cn = (int(d) for d in im.shape)
+    dev = torch.device("cuda", torch.cuda.current_device())
+    im = im.to(device=dev).contiguous()
+    ws_bytes = lib().dgdm_icon_workspace_bytes(M)
+    if ws_bytes < 0:
+        _check_value(int(ws_bytes))
+    ws = torch.empty(int(ws_bytes), dtype=torch.uint8, device=dev)
+    counts = np.zeros(M, dtype=np.int64)
+    _check_value(lib().dgdm_icon_trace(dptr(im), M, H, W, Cn, dptr(ws), int(ws_bytes), counts.ctypes.data, stream_ptr()))
+    off = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
+    rs_bytes = lib().dgdm_contour_resample_workspace_bytes(off.ctypes.data, M)
+    if rs_bytes < 0:
+        _check_value(int(rs_bytes))
+    rs = torch.empty(int(rs_bytes), dtype=torch.uint8, device=dev)
+    points = torch.empty((int(off[-1]), 2), dtype=torch.int32, device=dev)
+    _check_value(lib().dgdm_icon_fetch_contours(dptr(ws), int(ws_bytes), M, off.ctypes.data, dptr(points), dptr(rs), int(rs_bytes), stream_ptr()))
+    return points, off
+
+
+def icon_contours(images, num_points: int = 100, rescale: bool = False) -> torch.Tensor:
+    """extract_contours (assets/icon_process.py) of a stack of icons in one batch: (M, num_points, 2) on the current device, int32
+    pixel coordinates on the 128 x 128 grid, or float64 c / 128 * 0.1 - 0.05 when rescale.  images as icon_raw_contours takes them.
+    Synchronises the stream three times (the counts, the points, the resample)."""
+    if int(num_points) < 1:
+        raise ValueError(f"icon_contours: num_points {int(num_points)} (need >= 1)")
+    points, off = icon_raw_contours(images)
+    return resample_contours(points, off, num_points, rescale)
+
+
 def prof_enable(on: bool) -> None:
     check(lib().dgdm_prof_enable(int(on)))
 

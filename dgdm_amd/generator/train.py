@@ -10,11 +10,13 @@ fingers, which is what Lightning's ``trainer.validate`` does (:152-156).  ``--mo
 ``last.ckpt``, as the ModelCheckpoint of :137-146 keeps them).
 
 Assets the image does not have are substituted, loudly:
-* no checkpoint files  -> deterministic random-init weights (dgdm_amd.synth);
-* no Icons-50 (and no cv2) -> synthetic contours with the same normalisation.
-3-D objects come from ``--object_dir``: ``objects.npy`` ([n, vertices, 2|3], metres) when present; otherwise, as in the reference,
-``<object_dir>/<name>/model.obj`` of the six test objects, sampled on the GPU (dynamics/utils.py, csrc/mesh.hip) - only when one of
-those meshes is missing are synthetic surface-sampled clouds used, and the stderr line names the missing meshes.
+* no checkpoint files  -> deterministic random-init weights (dgdm_amd.synth).
+Objects come from ``--object_dir``: ``objects.npy`` ([n, vertices, 2|3], metres) when present; otherwise, as in the reference,
+* 2-D: ``--object_dir`` is the Icons-50 ``.npy`` file itself (a pickled dict whose ``'image'`` holds (N, 3, H, W) icons): the
+  contours of the eight test ids are extracted on the GPU without cv2 (assets/icon_process.py, csrc/contour.hip);
+* 3-D: ``<object_dir>/<name>/model.obj`` of the six test objects, sampled on the GPU (dynamics/utils.py, csrc/mesh.hip).
+Only when that input is missing or unreadable are synthetic objects with the same normalisation used, and the stderr line names the
+missing file or meshes.
 """
 from __future__ import annotations
 
@@ -25,6 +27,7 @@ import numpy as np
 import torch
 
 from .. import synth
+from ..assets import icon_process
 from ..dynamics import utils as object_utils
 from ..dynamics.parser import parse
 from ..dynamics.profile_forward_2d import ProfileForward2DModel
@@ -35,6 +38,7 @@ from .diffusion import Diffusion
 from .diffusion_utils import ConditionalUnet1D
 
 OBJECT_IDS = [10000, 2009, 2114, 2082, 1041, 2048, 1045, 1019]     # Icons-50 test ids, generator/train.py:36
+ICON_POINTS = 100                                                   # extract_contours' default num_points (generator/train.py:120)
 OBJECT_NAMES_3D = ["3D_Dollhouse_Swing", "BABY_CAR", "Ecoforms_Plant_Container_B4_Har", "Threshold_Bamboo_Ceramic_Soap_Dish",
                    "Squirt_Strain_Fruit_Basket",
                    "Office_Depot_Canon_CLI_8CMY_Remanufactured_Ink_Cartridges_Color_Cyan_Magenta_Yellow_3_count"]   # assets/object_names_test.txt
@@ -83,10 +87,41 @@ def _objects(args, fingers_3d: bool):
         print(f"[dgdm_amd] no objects.npy and no {object_utils.MESH_FILE} under --object_dir for {', '.join(missing)} - using synthetic objects",
               file=sys.stderr)
     else:
-        print("[dgdm_amd] no objects.npy under --object_dir - using synthetic objects", file=sys.stderr)
+        path = args.object_dir or ""
+        images, why = _icon_images(path)
+        if images is not None:
+            return _icon_objects(images, nv), list(OBJECT_IDS)
+        print(f"[dgdm_amd] no objects.npy under --object_dir and no Icons-50 file at '{path}' ({why}) - using synthetic objects",
+              file=sys.stderr)
     if fingers_3d:
         return torch.stack([synth.synth_object_3d(i, nv) for i in range(len(OBJECT_NAMES_3D))]), list(OBJECT_NAMES_3D)
     return torch.stack([synth.synth_object_2d(i, nv) for i in range(len(OBJECT_IDS))]), list(OBJECT_IDS)
+
+
+def _icon_images(path):
+    """(the 'image' array of the Icons-50 file at path, None) or (None, why not)."""
+    if not os.path.isfile(path):
+        return None, "no such file"
+    try:
+        images = np.load(path, allow_pickle=True).item()["image"]
+    except Exception as e:          # not a .npy, not a pickled dict, no 'image': the file is not Icons-50
+        return None, f"unreadable: {type(e).__name__}: {e}"
+    return images, None
+
+
+def _icon_objects(images, nv: int) -> torch.Tensor:
+    """generator/train.py:111-124: the rescaled 100-point contours of the test icons (all in one device call), float32, normalised to
+    [-1, 1] with the reference's statements."""
+    if nv != ICON_POINTS:
+        raise ValueError(f"--object_max_num_vertices={nv}, but the icon contours have {ICON_POINTS} points (extract_contours' default, "
+                         f"generator/train.py:120): pass --object_max_num_vertices={ICON_POINTS}")
+    icons = np.asarray(images)[OBJECT_IDS].transpose((0, 2, 3, 1))
+    contours = icon_process.extract_contours_batch(icons, ICON_POINTS, rescale=True)
+    object_pts_max_x, object_pts_min_x, object_pts_max_y, object_pts_min_y = 0.05, -0.05, 0.05, -0.05
+    object_vertices = torch.stack([torch.from_numpy(c).float() for c in contours], dim=0)
+    object_vertices[..., 0] = (object_vertices[..., 0] - object_pts_min_x) / (object_pts_max_x - object_pts_min_x) * 2.0 - 1.0
+    object_vertices[..., 1] = (object_vertices[..., 1] - object_pts_min_y) / (object_pts_max_y - object_pts_min_y) * 2.0 - 1.0
+    return object_vertices
 
 
 def fit(model: Diffusion, pts: np.ndarray, args, bounds, dev) -> Diffusion:

@@ -305,6 +305,37 @@ int     dgdm_mesh_sample_points(const double *verts_dev, const int32_t *tris_dev
                                 const int64_t *tri_offsets_host, int num_meshes, uint64_t seed, const uint64_t *keys_host,
                                 int64_t num_points, double *out_dev, void *workspace_dev, int64_t workspace_bytes, void *stream);
 
+/* ------------------------------------------------------------------ object contours from icon images
+ * extract_contours (assets/icon_process.py: cv2.resize to 128 x 128, BGR2GRAY, threshold 240 inverted, findContours RETR_EXTERNAL +
+ * CHAIN_APPROX_SIMPLE, the longest contour by arcLength, resample_contour, int32, rescale), which the reference applies to the
+ * Icons-50 test ids (generator/train.py:111-124).  The contract, exact in integers and float64, is DESIGN.md "Object contours from
+ * icon images".  An image's result depends on that image alone, whatever else is in the batch.  Three calls, on the caller's stream:
+ *   dgdm_icon_trace           binarise + external contours: the winner's point count per image (synchronises once);
+ *   dgdm_icon_fetch_contours  the winners' points into a buffer the caller sized from those counts (synchronises once);
+ *   dgdm_contour_resample     resample_contour of each winner (or of any int32 contours: the reference's public resample_contour). */
+/* Bytes of device workspace dgdm_icon_trace and dgdm_icon_fetch_contours need for num_images images; negative: bad count. */
+int64_t dgdm_icon_workspace_bytes(int num_images);
+/* images_dev [num_images][height][width][channels] uint8, channels 3 (BGR, channel 0 blue as cv2 reads it) or 4 (BGRA, alpha
+ * ignored) -> num_points_host [num_images]: the point count of each image's longest external contour.  An image without a pixel of
+ * grey level <= 240 after the resize has no contour: DGDM_EINVAL naming its index.                                                 */
+int dgdm_icon_trace(const uint8_t *images_dev, int num_images, int height, int width, int channels, void *workspace_dev,
+                    int64_t workspace_bytes, int64_t *num_points_host, void *stream);
+/* After dgdm_icon_trace on the same workspace: image m's contour, as (x, y) int32 pixel pairs in cv2's order, into points_dev rows
+ * offsets_host[m] .. [m+1] ([num_images + 1], starting at 0, the running sum of the counts).  resample_workspace_dev is
+ * dgdm_contour_resample_workspace_bytes(offsets_host, num_images) bytes; it receives the offsets, and may be handed on to
+ * dgdm_contour_resample with the same offsets.                                                                                    */
+int dgdm_icon_fetch_contours(void *workspace_dev, int64_t workspace_bytes, int num_images, const int64_t *offsets_host,
+                             int32_t *points_dev, void *resample_workspace_dev, int64_t resample_workspace_bytes, void *stream);
+/* Bytes of device workspace dgdm_contour_resample needs for these contours; negative: bad offsets. */
+int64_t dgdm_contour_resample_workspace_bytes(const int64_t *offsets_host, int num_contours);
+/* resample_contour of each contour: points_dev [offsets_host[num_contours]][2] int32, contour m = rows offsets_host[m] .. [m+1]
+ * (at least one point each) -> out_dev [num_contours][num_out][2], int32, or float64 c / 128 * 0.1 - 0.05 when rescale != 0.
+ * Arc lengths: sqrt of the integer squared step in float64, summed in order (np.cumsum); u = np.linspace(0, L, num_out); np.interp;
+ * truncation to int32.  Squares are taken in int64 (numpy squares int32 steps in int32: the same for steps below 46341).
+ * Synchronises the stream once.                                                                                                    */
+int dgdm_contour_resample(const int32_t *points_dev, const int64_t *offsets_host, int num_contours, int num_out, int rescale,
+                          void *out_dev, void *workspace_dev, int64_t workspace_bytes, void *stream);
+
 /* ------------------------------------------------------------------ measurement hooks
  * When enabled, the launches of every stage of the path are bracketed by hipEvents on the stream they are launched on.
  * dgdm_prof_read_stage synchronises those events and returns, for one stage, the number of bracketed regions, their total
