@@ -20,7 +20,7 @@
 //     operand of the next two GEMMs; Linear-bias gradients are column sums taken by the weight-gradient loader.
 // Column statistics are summed per workgroup in float32 and across workgroups in float64, in a fixed order: a step is reproducible
 // bit for bit.
-#include "common.h"
+#include "train_core.h"
 #include "mfma_chain.h"
 #include "smallnet.h"
 #include <cmath>
@@ -475,19 +475,6 @@ __global__ void wgrad_reduce_kernel(const float *__restrict__ part, int splits, 
     else gb[m] = a;
 }
 
-// torch.optim.Adam, single-tensor form (lerp for the first moment, bias corrections on the host)
-__global__ void adam_kernel(float *__restrict__ p, const float *__restrict__ g, float *__restrict__ m, float *__restrict__ v, int64_t n, float b1, float b2,
-                            float eps, float wd, float step_size, float bc2_sqrt) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    float gi = g[i];
-    if (wd != 0.f) gi = fmaf(wd, p[i], gi);
-    const float mi = m[i] + (gi - m[i]) * (1.f - b1);
-    const float vi = v[i] * b2 + (1.f - b2) * gi * gi;
-    m[i] = mi; v[i] = vi;
-    p[i] -= step_size * (mi / (sqrtf(vi) / bc2_sqrt + eps));
-}
-
 struct TrDesc { int64_t w, wt; int K; };      // offsets of W [256][K] in the parameter buffer and of Wt [K][256] in the transposed one
 __global__ void transpose_all_kernel(const float *__restrict__ P, float *__restrict__ WT, const TrDesc *__restrict__ d) {
     const TrDesc t = d[blockIdx.y];
@@ -577,8 +564,6 @@ std::vector<float> train_tfreqs(int half) {   // timestep_embedding (profile_for
     return f;
 }
 
-int round_up(int v, int m) { return (v + m - 1) / m * m; }
-
 }  // namespace
 }  // namespace dgdm
 
@@ -586,14 +571,13 @@ using namespace dgdm;
 
 // Linear layers: 0 gripper_encoder.0, 1 gripper_encoder.2, 2 object_encoder.0, 3 object_encoder.2, 4 time_encoder.0, 5 time_encoder.2,
 // 6..13 linears.{0,3,...,21}; then the eight BatchNorm1d layers linears.{1,4,...,22} and the output layer.
-struct DgdmTrainer2d {
+struct DgdmTrainer2d : ParamStore {      // its own padded, column-permuted layout (col_of): `named` stays empty
     struct Lin { std::string name; int K = 0, Kp = 0; size_t w = 0, b = 0, wt = 0; };
     int L = 0, OC = 0, Lp = 0, OCp = 0;
-    float beta1 = 0.9f, beta2 = 0.95f, eps = 1e-8f, wd = 0.f;
-    int64_t adam_steps = 0, bn_batches = 0;
+    int64_t bn_batches = 0;
     Lin lin[14];
-    size_t bn_g[8], bn_b[8], out_w = 0, out_b = 0, n_params = 0, n_wt = 0;
-    DevBuf P, G, M, V, WT, bn_run /* [8][2][256] running mean, var */, coef /* [8][7][256] */, tfreq, trdesc, loss_dev;
+    size_t bn_g[8], bn_b[8], out_w = 0, out_b = 0, n_wt = 0;
+    DevBuf WT, bn_run /* [8][2][256] running mean, var */, coef /* [8][7][256] */, tfreq, trdesc;
     DevBuf red /* [RED_S][3*256 + 4] float64 */, unit /* [256] ones, [256] zeros: coefficients of a ReLU without BatchNorm */;
     DevBuf ws, seg /* grouped encoders: outputs, their gradients, partial sums (grow-only) */;
     int64_t ws_rows = 0;
@@ -603,8 +587,6 @@ struct DgdmTrainer2d {
           *G0 = nullptr, *stats = nullptr, *hpart = nullptr, *wpart = nullptr;
     int64_t wpart_floats = 0;
 
-    float *p(size_t o) const { return P.as<float>() + o; }
-    float *gr(size_t o) const { return G.as<float>() + o; }
     float *cf(int l, int row) const { return coef.as<float>() + ((size_t)l * 7 + row) * 256; }
     int col_of(int l, int c) const;      // internal column c of layer l -> column of the reference's weight, or -1 (padding)
     int reserve(int64_t N);
@@ -613,8 +595,9 @@ struct DgdmTrainer2d {
     int wgrad(int l, const Operand &a, const Operand &dy, int64_t N, hipStream_t s);
     int run(const float *ctrl, const float *noise, const float *sa, const float *sb, const float *t, const float *ori, const float *pos,
             const float *obj, const float *score, int64_t N, int64_t Ntot, float lr, int train, bool update, float *pred, float *loss_host, hipStream_t s);
-    int adam(float lr, hipStream_t s);
-    int copy_state(int which, DgdmTensor *t, int n, bool to_device);
+    int step_adam(float lr, hipStream_t s);
+    int retranspose(hipStream_t s) const;
+    int copy_state(int which, const DgdmTensor *t, int n, bool to_device);
 };
 
 int DgdmTrainer2d::col_of(int l, int c) const {
@@ -712,12 +695,11 @@ int DgdmTrainer2d::wgrad(int l, const Operand &a, const Operand &dy, int64_t N, 
 }
 
 // torch.optim.Adam(lr, betas, weight_decay) over every parameter (trainer.py:46), then the transposed weight copies
-int DgdmTrainer2d::adam(float lr, hipStream_t s) {
-    ++adam_steps;
-    const double bc1 = 1.0 - std::pow((double)beta1, (double)adam_steps), bc2 = 1.0 - std::pow((double)beta2, (double)adam_steps);
-    hipLaunchKernelGGL(adam_kernel, dim3((unsigned)((n_params + 255) / 256)), dim3(256), 0, s, P.as<float>(), G.as<float>(), M.as<float>(), V.as<float>(),
-                       (int64_t)n_params, beta1, beta2, eps, wd, (float)((double)lr / bc1), (float)std::sqrt(bc2));
-    DGDM_HIP_CHECK(hipGetLastError());
+int DgdmTrainer2d::step_adam(float lr, hipStream_t s) {
+    const int rc = adam(lr, n_params, s);
+    return rc ? rc : retranspose(s);
+}
+int DgdmTrainer2d::retranspose(hipStream_t s) const {
     hipLaunchKernelGGL(transpose_all_kernel, dim3((800 * 256 + 255) / 256, 14), dim3(256), 0, s, P.as<float>(), WT.as<float>(), trdesc.as<TrDesc>());
     DGDM_HIP_CHECK(hipGetLastError());
     return DGDM_OK;
@@ -850,35 +832,25 @@ int DgdmTrainer2d::run(const float *ctrl, const float *noise, const float *sa, c
             if ((rc = gemm(true, EPI_BWD, g, s))) return rc;
             if ((rc = wgrad(2 * e, plain(enc_in[e], enc_ld[e]), plain(D[0], 256), erows[e], s))) return rc;
         }
-        if (update && (rc = adam(lr, s))) return rc;
+        if (update && (rc = step_adam(lr, s))) return rc;
         ++bn_batches;
     }
-    if (loss_host) {
-        DGDM_HIP_CHECK(hipMemcpyAsync(loss_host, loss_dev.p, sizeof(float), hipMemcpyDeviceToHost, s));
-        DGDM_HIP_CHECK(hipStreamSynchronize(s));
-    }
-    return DGDM_OK;
+    return read_loss(loss_host, s);
 }
 
 // which: 0 parameters and BatchNorm running statistics, 1 gradients, 2 / 3 Adam's first / second moments
-int DgdmTrainer2d::copy_state(int which, DgdmTensor *t, int n, bool to_device) {
-    DevBuf *src = which == 0 ? &P : which == 1 ? &G : which == 2 ? &M : &V;
+int DgdmTrainer2d::copy_state(int which, const DgdmTensor *t, int n, bool to_device) {
+    DevBuf *src = which == 0 ? &P : which == 1 ? &G : which == 2 ? &M1 : &V;
     std::vector<float> host(n_params), run(8 * 512);
     DGDM_HIP_CHECK(hipDeviceSynchronize());
     DGDM_HIP_CHECK(hipMemcpy(host.data(), src->p, n_params * sizeof(float), hipMemcpyDeviceToHost));
     DGDM_HIP_CHECK(hipMemcpy(run.data(), bn_run.p, run.size() * sizeof(float), hipMemcpyDeviceToHost));
-    std::map<std::string, DgdmTensor *> by;
-    for (int i = 0; i < n; ++i) by[t[i].name] = &t[i];
-    auto slot = [&](const std::string &k, int64_t numel, bool required) -> float * {
-        auto it = by.find(k);
-        if (it == by.end()) { if (required) set_error("state_dict key '%s' missing", k.c_str()); return nullptr; }
-        if (it->second->dtype != 0 || it->second->numel != numel) { set_error("state_dict key '%s': expected %lld float32 values", k.c_str(), (long long)numel); return nullptr; }
-        return const_cast<float *>(static_cast<const float *>(it->second->data));
-    };
+    const StateDict sd(t, n);
+    auto slot = [&](const std::string &k, int64_t numel) { return const_cast<float *>(sd.f32(k, numel)); };
     auto xfer = [&](float *user, float *mine, size_t cnt) { if (to_device) memcpy(mine, user, cnt * sizeof(float)); else memcpy(user, mine, cnt * sizeof(float)); };
     for (int l = 0; l < 14; ++l) {
         const Lin &x = lin[l];
-        float *wu = slot(x.name + ".weight", (int64_t)256 * x.K, true), *bu = slot(x.name + ".bias", 256, true);
+        float *wu = slot(x.name + ".weight", (int64_t)256 * x.K), *bu = slot(x.name + ".bias", 256);
         if (!wu || !bu) return DGDM_EKEY;
         for (int m = 0; m < 256; ++m)
             for (int c = 0; c < x.Kp; ++c) {
@@ -890,24 +862,24 @@ int DgdmTrainer2d::copy_state(int which, DgdmTensor *t, int n, bool to_device) {
     }
     for (int k = 0; k < 8; ++k) {
         const std::string bn = "linears." + std::to_string(3 * k + 1);
-        float *gu = slot(bn + ".weight", 256, true), *bu = slot(bn + ".bias", 256, true);
+        float *gu = slot(bn + ".weight", 256), *bu = slot(bn + ".bias", 256);
         if (!gu || !bu) return DGDM_EKEY;
         xfer(gu, &host[bn_g[k]], 256); xfer(bu, &host[bn_b[k]], 256);
         if (which == 0) {
-            float *mu = slot(bn + ".running_mean", 256, true), *vu = slot(bn + ".running_var", 256, true);
+            float *mu = slot(bn + ".running_mean", 256), *vu = slot(bn + ".running_var", 256);
             if (!mu || !vu) return DGDM_EKEY;
             xfer(mu, &run[(size_t)k * 512], 256); xfer(vu, &run[(size_t)k * 512 + 256], 256);
         }
     }
-    float *wu = slot("output.weight", 3 * 256, true), *bu = slot("output.bias", 3, true);
+    float *wu = slot("output.weight", 3 * 256), *bu = slot("output.bias", 3);
     if (!wu || !bu) return DGDM_EKEY;
     xfer(wu, &host[out_w], 768); xfer(bu, &host[out_b], 3);
     if (to_device) {
         DGDM_HIP_CHECK(hipMemcpy(src->p, host.data(), n_params * sizeof(float), hipMemcpyHostToDevice));
         if (which == 0) {
             DGDM_HIP_CHECK(hipMemcpy(bn_run.p, run.data(), run.size() * sizeof(float), hipMemcpyHostToDevice));
-            hipLaunchKernelGGL(transpose_all_kernel, dim3((800 * 256 + 255) / 256, 14), dim3(256), 0, 0, P.as<float>(), WT.as<float>(), trdesc.as<TrDesc>());
-            DGDM_HIP_CHECK(hipGetLastError());
+            const int rc = retranspose(0);
+            if (rc) return rc;
             DGDM_HIP_CHECK(hipDeviceSynchronize());
         }
     }
@@ -936,15 +908,11 @@ extern "C" int dgdm_trainer2d_create(DgdmTrainer2d **out, const DgdmTensor *stat
     m->out_w = o; o += 768; m->out_b = o; o += 64;
     m->n_params = o; m->n_wt = ot;
     int rc;
-    for (DevBuf *b : {&m->P, &m->G, &m->M, &m->V}) {
-        if ((rc = b->alloc(o * sizeof(float)))) return rc;
-        DGDM_HIP_CHECK(hipMemset(b->p, 0, o * sizeof(float)));
-    }
+    if ((rc = m->alloc_banks())) return rc;
     if ((rc = m->WT.alloc(ot * sizeof(float)))) return rc;
     if ((rc = m->bn_run.alloc(8 * 512 * sizeof(float)))) return rc;
     if ((rc = m->coef.alloc(8 * 7 * 256 * sizeof(float)))) return rc;
     DGDM_HIP_CHECK(hipMemset(m->coef.p, 0, 8 * 7 * 256 * sizeof(float)));
-    if ((rc = m->loss_dev.alloc(64))) return rc;
     if ((rc = m->red.alloc((size_t)RED_S * SEG_GROUPS * 256 * sizeof(double)))) return rc;       // also >= RED_S * (3*256 + 4)
     {
         std::vector<float> u(512, 0.f);
@@ -954,7 +922,7 @@ extern "C" int dgdm_trainer2d_create(DgdmTrainer2d **out, const DgdmTensor *stat
     const std::vector<float> f = train_tfreqs(64);
     if ((rc = m->tfreq.upload(f.data(), f.size() * sizeof(float)))) return rc;
     if ((rc = m->trdesc.upload(td.data(), td.size() * sizeof(TrDesc)))) return rc;
-    if ((rc = m->copy_state(0, const_cast<DgdmTensor *>(state_dict), n_tensors, true))) return rc;
+    if ((rc = m->copy_state(0, state_dict, n_tensors, true))) return rc;
     *out = m.release();
     return DGDM_OK;
 }
@@ -994,23 +962,19 @@ extern "C" int64_t dgdm_trainer2d_gradient_count(const DgdmTrainer2d *m) { retur
 
 extern "C" int dgdm_trainer2d_gradients(DgdmTrainer2d *m, float *flat_dev, int64_t numel, int to_trainer, void *stream) {
     DGDM_REQUIRE(m && flat_dev && numel == (int64_t)m->n_params, DGDM_EINVAL, "dgdm_trainer2d_gradients: expected %lld values", m ? (long long)m->n_params : 0LL);
-    DGDM_HIP_CHECK(hipMemcpyAsync(to_trainer ? m->G.p : (void *)flat_dev, to_trainer ? (const void *)flat_dev : m->G.p, (size_t)numel * sizeof(float),
-                                  hipMemcpyDeviceToDevice, (hipStream_t)stream));
-    return DGDM_OK;
+    return ParamStore::exchange(m->G, flat_dev, numel, to_trainer, stream);
 }
 
 // BatchNorm running statistics [8 layers][mean | var][256] device <-> flat_dev: under data parallelism every rank updates them from ITS
 // chunk, and nn.DataParallel keeps replica 0's (dynamics/trainer.py:41-43) - rank 0's buffers are broadcast after every step
 extern "C" int dgdm_trainer2d_running_stats(DgdmTrainer2d *m, float *flat_dev, int64_t numel, int to_trainer, void *stream) {
     DGDM_REQUIRE(m && flat_dev && numel == 8 * 512, DGDM_EINVAL, "dgdm_trainer2d_running_stats: expected %d values", 8 * 512);
-    DGDM_HIP_CHECK(hipMemcpyAsync(to_trainer ? m->bn_run.p : (void *)flat_dev, to_trainer ? (const void *)flat_dev : m->bn_run.p, (size_t)numel * sizeof(float),
-                                  hipMemcpyDeviceToDevice, (hipStream_t)stream));
-    return DGDM_OK;
+    return ParamStore::exchange(m->bn_run, flat_dev, numel, to_trainer, stream);
 }
 
 extern "C" int dgdm_trainer2d_apply(DgdmTrainer2d *m, float lr, void *stream) {
     DGDM_REQUIRE(m, DGDM_EINVAL, "dgdm_trainer2d_apply: null handle");
-    return m->adam(lr, (hipStream_t)stream);
+    return m->step_adam(lr, (hipStream_t)stream);
 }
 
 extern "C" int dgdm_trainer2d_export(DgdmTrainer2d *m, int which, DgdmTensor *tensors, int n_tensors) {

@@ -299,18 +299,14 @@ std::vector<float> tfreqs128() {      // timestep_embedding (profile_forward_2d.
 
 using namespace dgdm;
 
-struct DgdmTrainer3d {
-    struct Named { std::string name; size_t off; int64_t numel; int kind; };      // kind 0 parameter, 1 running_mean, 2 running_var
+struct DgdmTrainer3d : ParamStore {
     struct Lin { int in = 0, out = 0; size_t w = 0, b = 0; int F = -1, B = -1; };
     struct Bn { int C = 0; size_t g = 0; int slot = 0; };
-    std::vector<Named> named;
-    size_t n_params = 0, n_trainable = 0;
-    DevBuf P, G, M1, V, IMG, descs_dev, ws, wpart, run /* [slots][2][CW] */, coef /* [slots][6][CW] */, freqs, loss_dev;
-    std::vector<ImgDesc> descs;
-    size_t n_img = 0;
-    int max_img_elems = 0, L = 42, Lp = 48, N = 512, n_bn = 0;
-    float beta1 = 0.9f, beta2 = 0.95f, eps = 1e-8f, wd = 0.f;
-    int64_t adam_steps = 0, bn_batches = 0, R_ws = 0, wpart_floats = 0;
+    size_t n_trainable = 0;
+    WeightImages wimg{1024};
+    DevBuf ws, run /* [slots][2][CW] */, coef /* [slots][6][CW] */, freqs;
+    int L = 42, Lp = 48, N = 512, n_bn = 0;
+    int64_t bn_batches = 0, R_ws = 0;
     // the two FPS start vectors of a forward: pinned staging (two slots, alternated per call) -> device, no allocation and no pipeline drain
     // per step (the index entry point dgdm_farthest_point_sample allocates, uploads and synchronises on every call)
     int *start_pin = nullptr; DevBuf start_dev; int64_t start_cap = 0; int start_slot = 0;
@@ -325,17 +321,15 @@ struct DgdmTrainer3d {
           *X0 = nullptr, *dX0 = nullptr, *ty[8] = {}, *ta[8] = {}, *td[2] = {}, *pred = nullptr, *dpred = nullptr, *lpart = nullptr, *cpart = nullptr, *sums = nullptr;
     int *fps1 = nullptr, *idx1 = nullptr, *arg1 = nullptr, *fps2 = nullptr, *idx2 = nullptr, *arg2 = nullptr, *arg3 = nullptr;
 
-    float *p(size_t o) const { return P.as<float>() + o; }
-    float *gr(size_t o) const { return G.as<float>() + o; }
     float *cf(int slot) const { return coef.as<float>() + (size_t)slot * 6 * CW; }
     float *rn(int slot, int which) const { return run.as<float>() + ((size_t)slot * 2 + which) * CW; }
-    size_t add_param(const std::string &name, int64_t numel, int kind = 0) { named.push_back({name, n_params, numel, kind}); const size_t o = n_params; n_params += (size_t)numel; return o; }
-    int add_img(size_t w_off, int Kblk, int N_, int s_kc, int s_n);
     void make_lin(Lin &l, const std::string &name, int in, int out);
     void make_bn(Bn &b, const std::string &name, int C);
     int reserve(int64_t R);
-    int rowgemm(const float *A, int64_t a_rs, int img, float *C, int64_t c_rs, const float *bias, int64_t M, hipStream_t s) const;
-    int colgemm(const float *A, int64_t a_rs, int img, const float *D, int64_t d_rs, int64_t M, hipStream_t s);
+    int rowgemm(const float *A, int64_t a_rs, int img, float *C, int64_t c_rs, const float *bias, int64_t M, hipStream_t s) const {
+        return wimg.rowgemm(A, a_rs, img, C, c_rs, nullptr, 0, bias, M, RowMask{0, 0, 0}, s);
+    }
+    int colgemm(const float *A, int64_t a_rs, int img, const float *D, int64_t d_rs, int64_t M, hipStream_t s) const { return wimg.colgemm(A, a_rs, img, D, d_rs, M, G.as<float>(), s); }
     int bias_grad(const float *D, int64_t rs, int64_t M, int C, size_t b_off, hipStream_t s);
     int lin_fwd(const Lin &l, const float *A, int64_t a_rs, float *C, int64_t c_rs, int64_t M, hipStream_t s) const { return rowgemm(A, a_rs, l.F, C, c_rs, p(l.b), M, s); }
     int lin_bwd(const Lin &l, const float *A, int64_t a_rs, const float *dY, int64_t dy_rs, float *dX, int64_t dx_rs, int64_t M, hipStream_t s);
@@ -345,27 +339,17 @@ struct DgdmTrainer3d {
     int run_step(const float *ctrl1, const float *noise, const float *sa_, const float *sb_, const float *t, const float *ori, const float *pos, const float *xyz_in,
                  const int64_t *start1, const int64_t *start2, const float *score, int64_t R, float lr, int train, float *pred_out, float *loss_host, hipStream_t s,
                  int64_t total_rows = 0 /* 0: R - the loss is the mean over this many rows (a data-parallel chunk: the whole batch's) */, bool apply = true);
-    int adam(float lr, hipStream_t s);
-    int repack(hipStream_t s);
-    int copy_state(int which, DgdmTensor *t, int n, bool to_device);
+    int step_adam(float lr, hipStream_t s);
+    int copy_state(int which, const DgdmTensor *t, int n, bool to_device);
 };
 
-int DgdmTrainer3d::add_img(size_t w_off, int Kblk, int N_, int s_kc, int s_n) {
-    ImgDesc d{};
-    d.src = (int64_t)w_off; d.dst = (int64_t)n_img; d.Kblk = Kblk; d.ntaps = 1; d.taps[0] = 0;
-    d.K = Kblk; d.Kp = round_up(Kblk, KC); d.N = N_; d.Np = round_up(N_, TN); d.s_kc = s_kc; d.s_n = s_n;
-    n_img += (size_t)d.Kp * d.Np;
-    max_img_elems = std::max(max_img_elems, d.Kp * d.Np);
-    descs.push_back(d);
-    return (int)descs.size() - 1;
-}
 // Linear / Conv2d(1x1) weight [out][in]: forward image [in][out], input-gradient image [out][in]
 void DgdmTrainer3d::make_lin(Lin &l, const std::string &name, int in, int out) {
     l.in = in; l.out = out;
     l.w = add_param(name + ".weight", (int64_t)in * out);
     l.b = add_param(name + ".bias", out);
-    l.F = add_img(l.w, in, out, 1, in);
-    l.B = add_img(l.w, out, in, in, 1);
+    l.F = wimg.add((int64_t)l.w, in, {0}, out, 1, in);
+    l.B = wimg.add((int64_t)l.w, out, {0}, in, in, 1);
 }
 void DgdmTrainer3d::make_bn(Bn &b, const std::string &name, int C) {
     b.C = C; b.slot = n_bn++;
@@ -373,34 +357,6 @@ void DgdmTrainer3d::make_bn(Bn &b, const std::string &name, int C) {
     add_param(name + ".bias", C);
 }
 
-int DgdmTrainer3d::rowgemm(const float *A, int64_t a_rs, int img, float *C, int64_t c_rs, const float *bias, int64_t M, hipStream_t s) const {
-    const ImgDesc &d = descs[img];
-    RowGemm g{};
-    g.A = A; g.a_rs = a_rs; g.B = IMG.as<float>() + d.dst; g.Kp = d.Kp; g.Np = d.Np; g.C = C; g.c_rs = c_rs; g.N = d.N; g.bias = bias; g.M = M;
-    g.mk = RowMask{0, 0, 0}; g.scalar_a = (a_rs & 3) != 0 || (reinterpret_cast<uintptr_t>(A) & 15) != 0;
-    hipLaunchKernelGGL(rowgemm_kernel, dim3((unsigned)((M + TM - 1) / TM), (unsigned)(d.Np / TN)), dim3(256), 0, s, g);
-    DGDM_HIP_CHECK(hipGetLastError());
-    return DGDM_OK;
-}
-int DgdmTrainer3d::colgemm(const float *A, int64_t a_rs, int img, const float *D, int64_t d_rs, int64_t M, hipStream_t s) {
-    const ImgDesc &d = descs[img];
-    const int kt = (d.Kp + TM - 1) / TM, nt = d.Np / TN;
-    int64_t splits = std::min<int64_t>(std::max<int64_t>(1, M / 256), std::max(1, 1024 / (kt * nt)));
-    int64_t per = ((M + splits - 1) / splits + KC - 1) / KC * KC;
-    splits = (M + per - 1) / per;
-    ColGemm g{};
-    g.A = A; g.a_rs = a_rs; g.D = D; g.d_rs = d_rs; g.part = wpart.as<float>(); g.ldp = nt * TN; g.split_stride = (int64_t)kt * TM * g.ldp; g.M = M; g.m_per_split = per;
-    g.scalar_a = (a_rs & 3) != 0 || (reinterpret_cast<uintptr_t>(A) & 15) != 0;
-    g.scalar_d = (d_rs & 3) != 0 || (reinterpret_cast<uintptr_t>(D) & 15) != 0;
-    DGDM_REQUIRE(splits * g.split_stride <= wpart_floats, DGDM_EINVAL, "trainer3d: weight-gradient partials do not fit");
-    hipLaunchKernelGGL(colgemm_kernel, dim3(kt, nt, (unsigned)splits), dim3(256), 0, s, g);
-    DGDM_HIP_CHECK(hipGetLastError());
-    const int64_t n = (int64_t)d.K * d.N;
-    hipLaunchKernelGGL(wgrad_scatter_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, wpart.as<float>(), (int)splits, g.split_stride, g.ldp,
-                       descs_dev.as<ImgDesc>(), img, G.as<float>());
-    DGDM_HIP_CHECK(hipGetLastError());
-    return DGDM_OK;
-}
 static int64_t stat_blocks(int64_t M, int64_t &rows_per_block) {
     int64_t blocks = std::min<int64_t>(std::max<int64_t>(1, (M + 255) / 256), 2048);
     rows_per_block = (M + blocks - 1) / blocks;
@@ -464,9 +420,9 @@ int DgdmTrainer3d::relu_bwd(const Bn *b, float *da, const float *y, int64_t M, i
 int DgdmTrainer3d::reserve(int64_t R) {
     if (R <= R_ws) return DGDM_OK;
     const int64_t Mr1 = R * 512, M1r = Mr1 * 32, Mr2 = R * 128, M2r = Mr2 * 64;
-    std::vector<std::pair<void **, int64_t>> want;
-    auto F = [&](float *&q, int64_t n) { want.push_back({(void **)&q, n + 2 * GUARD}); };
-    auto I = [&](int *&q, int64_t n) { want.push_back({(void **)&q, n + 2 * GUARD}); };
+    Arena ar;
+    auto F = [&](float *&q, int64_t n) { ar.add(q, n, GUARD); };
+    auto I = [&](int *&q, int64_t n) { ar.add(q, n, GUARD); };
     F(xyz, R * N * 3); F(nx1, Mr1 * 3); F(nx2, Mr2 * 3);
     I(fps1, Mr1); I(idx1, M1r); I(arg1, Mr1 * 128); I(fps2, Mr2); I(idx2, M2r); I(arg2, Mr2 * 256); I(arg3, R * 256);
     F(feat1, M1r * 4); F(y11, M1r * 64); F(a11, M1r * 64); F(y12, M1r * 128); F(l1p, Mr1 * 128);
@@ -478,34 +434,17 @@ int DgdmTrainer3d::reserve(int64_t R) {
     for (int k = 0; k < 8; ++k) { F(ty[k], R * 512); F(ta[k], R * 512); }
     F(td[0], R * 512); F(td[1], R * 512); F(pred, R * 4); F(dpred, R * 4); F(lpart, R);
     F(cpart, (int64_t)2048 * 2 * CW); F(sums, 2 * CW);
-    int64_t total = 0;
-    for (auto &w : want) total += (w.second + 63) / 64 * 64;
-    int rc = ws.alloc((size_t)total * sizeof(float));
-    if (rc) { set_error("trainer3d: the workspace for %lld clouds per call is %.1f GB (68 MB per cloud): %s", (long long)R, (double)total * 4e-9, dgdm_last_error()); return rc; }
-    DGDM_HIP_CHECK(hipMemset(ws.p, 0, (size_t)total * sizeof(float)));
-    float *q = ws.as<float>();
-    for (auto &w : want) { *w.first = q + GUARD; q += (w.second + 63) / 64 * 64; }
-    wpart_floats = (int64_t)1024 * TM * TN + (int64_t)64 * TM * TN;
-    if ((rc = wpart.alloc((size_t)wpart_floats * sizeof(float)))) return rc;
+    const int rc = ar.commit(ws);
+    if (rc) { set_error("trainer3d: the workspace for %lld clouds per call is %.1f GB (68 MB per cloud): %s", (long long)R, (double)ar.floats() * 4e-9, dgdm_last_error()); return rc; }
     R_ws = R;
     return DGDM_OK;
 }
 
-int DgdmTrainer3d::repack(hipStream_t s) {
-    hipLaunchKernelGGL(repack_kernel, dim3((unsigned)((max_img_elems + 255) / 256), (unsigned)descs.size()), dim3(256), 0, s, P.as<float>(), IMG.as<float>(),
-                       descs_dev.as<ImgDesc>());
-    DGDM_HIP_CHECK(hipGetLastError());
-    return DGDM_OK;
-}
 // torch.optim.Adam over the parameters that received a gradient (time_encoder is never called by ProfileForward3DModel.forward: its
 // .grad stays None and torch skips it - those tensors sit behind n_trainable)
-int DgdmTrainer3d::adam(float lr, hipStream_t s) {
-    ++adam_steps;
-    const double bc1 = 1.0 - std::pow((double)beta1, (double)adam_steps), bc2 = 1.0 - std::pow((double)beta2, (double)adam_steps);
-    hipLaunchKernelGGL(adam_kernel, dim3((unsigned)((n_trainable + 255) / 256)), dim3(256), 0, s, P.as<float>(), G.as<float>(), M1.as<float>(), V.as<float>(),
-                       (int64_t)n_trainable, beta1, beta2, eps, wd, (float)((double)lr / bc1), (float)std::sqrt(bc2));
-    DGDM_HIP_CHECK(hipGetLastError());
-    return repack(s);
+int DgdmTrainer3d::step_adam(float lr, hipStream_t s) {
+    const int rc = adam(lr, n_trainable, s);
+    return rc ? rc : wimg.repack(P.as<float>(), s);
 }
 
 int DgdmTrainer3d::upload_starts(const int64_t *s1, const int64_t *s2, int64_t R, hipStream_t s, const int **d1, const int **d2) {
@@ -643,47 +582,18 @@ int DgdmTrainer3d::run_step(const float *ctrl1, const float *noise, const float 
         if ((rc = lin_bwd(sa[1], a11, 64, dy12, 128, da11, 64, M1r, s))) return rc;
         if ((rc = relu_bwd(&sabn[0], da11, y11, M1r, 64, s))) return rc;
         if ((rc = lin_bwd(sa[0], feat1, 4, da11, 64, nullptr, 0, M1r, s))) return rc;
-        if (apply && (rc = adam(lr, s))) return rc;
+        if (apply && (rc = step_adam(lr, s))) return rc;
         ++bn_batches;
     }
-    if (loss_host) {
-        DGDM_HIP_CHECK(hipMemcpyAsync(loss_host, loss_dev.p, sizeof(float), hipMemcpyDeviceToHost, s));
-        DGDM_HIP_CHECK(hipStreamSynchronize(s));
-    }
-    return DGDM_OK;
+    return read_loss(loss_host, s);
 }
 
 // which: 0 parameters + BatchNorm running statistics, 1 gradients, 2 / 3 Adam's exp_avg / exp_avg_sq
-int DgdmTrainer3d::copy_state(int which, DgdmTensor *t, int n, bool to_device) {
-    DevBuf *src = which == 0 ? &P : which == 1 ? &G : which == 2 ? &M1 : &V;
-    std::vector<float> host(n_params), rs((size_t)n_bn * 2 * CW);
+int DgdmTrainer3d::copy_state(int which, const DgdmTensor *t, int n, bool to_device) {
+    int rc = ParamStore::copy_state(which == 0 ? P : which == 1 ? G : which == 2 ? M1 : V, which == 0 ? &run : nullptr, t, n, to_device);
+    if (rc || !to_device || which != 0) return rc;
+    if ((rc = wimg.repack(P.as<float>(), 0))) return rc;
     DGDM_HIP_CHECK(hipDeviceSynchronize());
-    DGDM_HIP_CHECK(hipMemcpy(host.data(), src->p, n_params * sizeof(float), hipMemcpyDeviceToHost));
-    DGDM_HIP_CHECK(hipMemcpy(rs.data(), run.p, rs.size() * sizeof(float), hipMemcpyDeviceToHost));
-    std::map<std::string, DgdmTensor *> by;
-    for (int i = 0; i < n; ++i) by[t[i].name] = &t[i];
-    for (const Named &nm : named) {
-        if (nm.kind != 0 && which != 0) continue;
-        auto it = by.find(nm.name);
-        if (it == by.end()) { set_error("state_dict key '%s' missing", nm.name.c_str()); return DGDM_EKEY; }
-        if (it->second->dtype != 0 || it->second->numel != nm.numel) {
-            set_error("state_dict key '%s': expected %lld float32 values, got %lld", nm.name.c_str(), (long long)nm.numel, (long long)it->second->numel);
-            return DGDM_EKEY;
-        }
-        float *user = const_cast<float *>(static_cast<const float *>(it->second->data));
-        float *mine = nm.kind == 0 ? &host[nm.off] : &rs[nm.off];
-        if (to_device) memcpy(mine, user, (size_t)nm.numel * sizeof(float));
-        else memcpy(user, mine, (size_t)nm.numel * sizeof(float));
-    }
-    if (to_device) {
-        DGDM_HIP_CHECK(hipMemcpy(src->p, host.data(), n_params * sizeof(float), hipMemcpyHostToDevice));
-        if (which == 0) {
-            DGDM_HIP_CHECK(hipMemcpy(run.p, rs.data(), rs.size() * sizeof(float), hipMemcpyHostToDevice));
-            int rc = repack(0);
-            if (rc) return rc;
-            DGDM_HIP_CHECK(hipDeviceSynchronize());
-        }
-    }
     return DGDM_OK;
 }
 
@@ -698,7 +608,7 @@ extern "C" int dgdm_trainer3d_create(DgdmTrainer3d **out, const DgdmTensor *stat
     auto bn = [&](DgdmTrainer3d::Bn &b, const std::string &name, int C) {
         m->make_bn(b, name, C);
         m->named.push_back({name + ".running_mean", ((size_t)b.slot * 2 + 0) * CW, C, 1});
-        m->named.push_back({name + ".running_var", ((size_t)b.slot * 2 + 1) * CW, C, 2});
+        m->named.push_back({name + ".running_var", ((size_t)b.slot * 2 + 1) * CW, C, 1});
     };
     const int sadim[5][2] = {{3, 64}, {64, 128}, {131, 128}, {128, 256}, {259, 256}};
     const char *saname[5] = {"object_encoder.sa1", "object_encoder.sa1", "object_encoder.sa2", "object_encoder.sa2", "object_encoder.sa3"};
@@ -719,20 +629,15 @@ extern "C" int dgdm_trainer3d_create(DgdmTrainer3d **out, const DgdmTensor *stat
     m->make_lin(m->te0, "time_encoder.0", 128, 256);       // constructed by the reference (profile_forward_3d.py:27-31), never called: no gradient, no update
     m->make_lin(m->te2, "time_encoder.2", 256, 256);
     int rc;
-    for (DevBuf *b : {&m->P, &m->G, &m->M1, &m->V}) {
-        if ((rc = b->alloc(m->n_params * sizeof(float)))) return rc;
-        DGDM_HIP_CHECK(hipMemset(b->p, 0, m->n_params * sizeof(float)));
-    }
-    if ((rc = m->IMG.alloc(m->n_img * sizeof(float)))) return rc;
-    if ((rc = m->descs_dev.upload(m->descs.data(), m->descs.size() * sizeof(ImgDesc)))) return rc;
+    if ((rc = m->alloc_banks())) return rc;
+    if ((rc = m->wimg.alloc())) return rc;
     if ((rc = m->run.alloc((size_t)m->n_bn * 2 * CW * sizeof(float)))) return rc;
     DGDM_HIP_CHECK(hipMemset(m->run.p, 0, (size_t)m->n_bn * 2 * CW * sizeof(float)));
     if ((rc = m->coef.alloc((size_t)m->n_bn * 6 * CW * sizeof(float)))) return rc;
     DGDM_HIP_CHECK(hipMemset(m->coef.p, 0, (size_t)m->n_bn * 6 * CW * sizeof(float)));
-    if ((rc = m->loss_dev.alloc(64))) return rc;
     const std::vector<float> f = tfreqs128();
     if ((rc = m->freqs.upload(f.data(), f.size() * sizeof(float)))) return rc;
-    if ((rc = m->copy_state(0, const_cast<DgdmTensor *>(state_dict), n_tensors, true))) return rc;
+    if ((rc = m->copy_state(0, state_dict, n_tensors, true))) return rc;
     *out = m.release();
     return DGDM_OK;
 }
@@ -767,20 +672,16 @@ extern "C" int dgdm_trainer3d_forward_backward(DgdmTrainer3d *m, const float *ct
 extern "C" int64_t dgdm_trainer3d_gradient_count(const DgdmTrainer3d *m) { return m ? (int64_t)m->n_trainable : -1; }
 extern "C" int dgdm_trainer3d_gradients(DgdmTrainer3d *m, float *flat_dev, int64_t numel, int to_trainer, void *stream) {
     DGDM_REQUIRE(m && flat_dev && numel == (int64_t)m->n_trainable, DGDM_EINVAL, "dgdm_trainer3d_gradients: expected %lld floats", m ? (long long)m->n_trainable : -1LL);
-    DGDM_HIP_CHECK(hipMemcpyAsync(to_trainer ? m->G.p : (void *)flat_dev, to_trainer ? (const void *)flat_dev : m->G.p, (size_t)numel * sizeof(float), hipMemcpyDeviceToDevice,
-                                  (hipStream_t)stream));
-    return DGDM_OK;
+    return ParamStore::exchange(m->G, flat_dev, numel, to_trainer, stream);
 }
 extern "C" int dgdm_trainer3d_apply(DgdmTrainer3d *m, float lr, void *stream) {
     DGDM_REQUIRE(m, DGDM_EINVAL, "dgdm_trainer3d_apply: null handle");
-    return m->adam(lr, (hipStream_t)stream);
+    return m->step_adam(lr, (hipStream_t)stream);
 }
 extern "C" int64_t dgdm_trainer3d_running_stats_count(const DgdmTrainer3d *m) { return m ? (int64_t)m->n_bn * 2 * CW : -1; }
 extern "C" int dgdm_trainer3d_running_stats(DgdmTrainer3d *m, float *flat_dev, int64_t numel, int to_trainer, void *stream) {
     DGDM_REQUIRE(m && flat_dev && numel == (int64_t)m->n_bn * 2 * CW, DGDM_EINVAL, "dgdm_trainer3d_running_stats: expected %lld floats", m ? (long long)m->n_bn * 2 * CW : -1LL);
-    DGDM_HIP_CHECK(hipMemcpyAsync(to_trainer ? m->run.p : (void *)flat_dev, to_trainer ? (const void *)flat_dev : m->run.p, (size_t)numel * sizeof(float), hipMemcpyDeviceToDevice,
-                                  (hipStream_t)stream));
-    return DGDM_OK;
+    return ParamStore::exchange(m->run, flat_dev, numel, to_trainer, stream);
 }
 
 extern "C" int dgdm_trainer3d_export(DgdmTrainer3d *m, int which, DgdmTensor *tensors, int n_tensors) {

@@ -1,9 +1,11 @@
-// Shared pieces of the training paths (unet_train.hip, train3d.hip): the two float32-MFMA GEMM kernels over row WINDOWS, weight images
-// and their inverse (weight-gradient scatter), ordered column sums, Adam.  Every kernel is internal to the translation unit that
+// The GEMM side of the training paths that work on row WINDOWS (unet_train.hip, train3d.hip): the two float32-MFMA GEMM kernels, weight
+// images and their inverse (weight-gradient scatter) with the host struct that owns and launches them, ordered column sums.  What every
+// trainer needs (parameter banks, Adam, workspace arena) is train_core.h.  Every kernel is internal to the translation unit that
 // includes this header (anonymous namespace).  See unet_train.hip for the layout the windows come from.
 #pragma once
-#include "common.h"
+#include "train_core.h"
 #include "mfma_chain.h"
+#include <algorithm>
 
 namespace dgdm {
 namespace {
@@ -259,30 +261,74 @@ __global__ __launch_bounds__(256) void rows_sum_kernel(const float *__restrict__
 inline dim3 rows_sum_grid(int W) { return dim3((unsigned)((W + 63) / 64)); }
 
 
-// torch.optim.Adam (single-tensor form: lerp first moment, bias corrections on the host), as train2d.hip
-__global__ void adam_kernel(float *__restrict__ p, const float *__restrict__ g, float *__restrict__ m, float *__restrict__ v, int64_t n, float b1, float b2,
-                            float eps, float wd, float step_size, float bc2_sqrt) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    float gi = g[i];
-    if (wd != 0.f) gi = fmaf(wd, p[i], gi);
-    const float mi = m[i] + (gi - m[i]) * (1.f - b1);
-    const float vi = v[i] * b2 + (1.f - b2) * gi * gi;
-    m[i] = mi; v[i] = vi;
-    p[i] -= step_size * (mi / (sqrtf(vi) / bc2_sqrt + eps));
-}
-// dst (+)= src
-__global__ void add_kernel(const float *__restrict__ src, float *__restrict__ dst, int64_t n, int accumulate) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) dst[i] = accumulate ? dst[i] + src[i] : src[i];
-}
-__global__ void scale_kernel(float *__restrict__ g, int64_t n, float f) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) g[i] *= f;
-}
+// The weight images of a trainer and the GEMMs on them.  split_tiles caps (tiles x row splits) of a weight gradient: it fixes the order of
+// the ordered sum over the splits, and with it the bits of every weight gradient - each trainer keeps the value it was validated with.
+struct WeightImages {
+    explicit WeightImages(int split_tiles_) : split_tiles(split_tiles_) {}
+    const int split_tiles;
+    std::vector<ImgDesc> descs;
+    DevBuf IMG, descs_dev, wpart;
+    size_t n_img = 0;
+    int max_img_elems = 0;
+    int64_t wpart_floats = 0;
 
-int round_up(int v, int m) { return (v + m - 1) / m * m; }
-
+    int add(int64_t src, int Kblk, std::initializer_list<int> taps, int N, int s_kc, int s_n) {
+        ImgDesc d{};
+        d.src = src; d.dst = (int64_t)n_img;
+        d.Kblk = Kblk; d.ntaps = (int)taps.size();
+        int i = 0;
+        for (int t : taps) d.taps[i++] = t;
+        d.K = Kblk * d.ntaps; d.Kp = round_up(d.K, KC); d.N = N; d.Np = round_up(N, TN); d.s_kc = s_kc; d.s_n = s_n;
+        n_img += (size_t)d.Kp * d.Np;
+        max_img_elems = std::max(max_img_elems, d.Kp * d.Np);
+        descs.push_back(d);
+        return (int)descs.size() - 1;
+    }
+    // after the last add(): the images, the descriptors' device copy, the weight-gradient partials (the largest tiles x splits product)
+    int alloc() {
+        int rc;
+        if ((rc = IMG.alloc(n_img * sizeof(float)))) return rc;
+        if ((rc = descs_dev.upload(descs.data(), descs.size() * sizeof(ImgDesc)))) return rc;
+        wpart_floats = (int64_t)(split_tiles + 64) * TM * TN;
+        return wpart.alloc((size_t)wpart_floats * sizeof(float));
+    }
+    int repack(const float *P, hipStream_t s) const {
+        hipLaunchKernelGGL(repack_kernel, dim3((unsigned)((max_img_elems + 255) / 256), (unsigned)descs.size()), dim3(256), 0, s, P, IMG.as<float>(),
+                           descs_dev.as<ImgDesc>());
+        DGDM_HIP_CHECK(hipGetLastError());
+        return DGDM_OK;
+    }
+    int rowgemm(const float *A, int64_t a_rs, int img, float *C, int64_t c_rs, const float *add, int64_t add_rs, const float *bias, int64_t M, RowMask mk,
+                hipStream_t s) const {
+        const ImgDesc &d = descs[img];
+        RowGemm g{};
+        g.A = A; g.a_rs = a_rs; g.B = IMG.as<float>() + d.dst; g.Kp = d.Kp; g.Np = d.Np; g.C = C; g.c_rs = c_rs; g.N = d.N; g.add = add; g.add_rs = add_rs;
+        g.bias = bias; g.M = M; g.mk = mk; g.scalar_a = (a_rs & 3) != 0 || (reinterpret_cast<uintptr_t>(A) & 15) != 0;
+        hipLaunchKernelGGL(rowgemm_kernel, dim3((unsigned)((M + TM - 1) / TM), (unsigned)(d.Np / TN)), dim3(256), 0, s, g);
+        DGDM_HIP_CHECK(hipGetLastError());
+        return DGDM_OK;
+    }
+    // dW in the layout of image `img` = sum over the rows of window(r) (x) D[r], scattered into the gradient G of the image's tensor
+    int colgemm(const float *A, int64_t a_rs, int img, const float *D, int64_t d_rs, int64_t M, float *G, hipStream_t s) const {
+        const ImgDesc &d = descs[img];
+        const int kt = (d.Kp + TM - 1) / TM, nt = d.Np / TN;
+        int64_t splits = std::min<int64_t>(std::max<int64_t>(1, M / 256), std::max(1, split_tiles / (kt * nt)));
+        int64_t per = ((M + splits - 1) / splits + KC - 1) / KC * KC;
+        splits = (M + per - 1) / per;
+        ColGemm g{};
+        g.A = A; g.a_rs = a_rs; g.D = D; g.d_rs = d_rs; g.part = wpart.as<float>(); g.ldp = nt * TN; g.split_stride = (int64_t)kt * TM * g.ldp; g.M = M; g.m_per_split = per;
+        g.scalar_a = (a_rs & 3) != 0 || (reinterpret_cast<uintptr_t>(A) & 15) != 0;
+        g.scalar_d = (d_rs & 3) != 0 || (reinterpret_cast<uintptr_t>(D) & 15) != 0;
+        DGDM_REQUIRE(splits * g.split_stride <= wpart_floats, DGDM_EINVAL, "weight-gradient partials do not fit");
+        hipLaunchKernelGGL(colgemm_kernel, dim3(kt, nt, (unsigned)splits), dim3(256), 0, s, g);
+        DGDM_HIP_CHECK(hipGetLastError());
+        const int64_t n = (int64_t)d.K * d.N;
+        hipLaunchKernelGGL(wgrad_scatter_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, wpart.as<float>(), (int)splits, g.split_stride, g.ldp,
+                           descs_dev.as<ImgDesc>(), img, G);
+        DGDM_HIP_CHECK(hipGetLastError());
+        return DGDM_OK;
+    }
+};
 
 }  // namespace
 }  // namespace dgdm

@@ -22,8 +22,6 @@
 // lie).  GroupNorm + Mish (+ FiLM, + residual add) is one workgroup per sample forward and backward; per-sample partial sums of the
 // GroupNorm / FiLM / bias gradients and the split weight-gradient tiles are added in a fixed order (float64), so a step is reproducible
 // bit for bit.  No atomics.
-#include "common.h"
-#include "mfma_chain.h"
 #include "train_gemm.h"
 #include <cmath>
 #include <cstring>
@@ -209,17 +207,9 @@ __global__ void ema_kernel(float *__restrict__ e, const float *__restrict__ p, i
 
 using namespace dgdm;
 
-struct DgdmUnetTrainer {
-    // ---- parameters: one flat buffer in the state_dict's own tensor layouts; `named` maps the reference's keys to it
-    struct Named { std::string name; size_t off; int64_t numel; };
-    std::vector<Named> named;
-    size_t n_params = 0;
-    DevBuf P, G, M1, V, E /* EMA copy */, IMG, descs_dev, ws, wpart, freqs, loss_dev;
-    std::vector<ImgDesc> descs;
-    size_t n_img = 0;
-    int max_img_elems = 0;
-    float beta1 = 0.9f, beta2 = 0.999f, eps = 1e-8f, wd = 0.f;
-    int64_t adam_steps = 0;
+struct DgdmUnetTrainer : ParamStore {      // parameters: one flat buffer in the state_dict's own tensor layouts
+    DevBuf E /* EMA copy */, ws, freqs;
+    WeightImages wimg{512};
     int L = 0, d0 = 128, d1 = 256, dsed = 32, ks = 5;
     // ---- graph
     struct T { float *v = nullptr, *g = nullptr; int C = 0, lvl = 0; bool gw = false; };     // lvl 0: one row per sample; 1, 2: padded positions
@@ -236,17 +226,17 @@ struct DgdmUnetTrainer {
     float *f_st = nullptr, *f_sp = nullptr, *lpart = nullptr, *cpart = nullptr;
     int64_t S_ws = 0, M[3] = {0, 0, 0};
     RowMask mk[3];
-    int64_t wpart_floats = 0;
 
-    float *p(size_t o) const { return P.as<float>() + o; }
-    float *gr(size_t o) const { return G.as<float>() + o; }
-    size_t add_param(const std::string &name, int64_t numel) { named.push_back({name, n_params, numel}); const size_t o = n_params; n_params += (size_t)numel; return o; }
-    int add_img(size_t w_off, int Kblk, std::initializer_list<int> taps, int N, int s_kc, int s_n, int base);
+    int add_img(size_t w_off, int Kblk, std::initializer_list<int> taps, int N, int s_kc, int s_n, int base) { return wimg.add((int64_t)w_off + base, Kblk, taps, N, s_kc, s_n); }
     void make_conv(Conv &c, const std::string &name, int kind, int k, int cin, int cout, int nparts = 1);
     int reserve(int S);
     int rowgemm(const float *A, int64_t a_rs, int img, float *C, int64_t c_rs, const float *add, int64_t add_rs, const float *bias, int64_t Mrows, int lvl,
-                hipStream_t s) const;
-    int colgemm(const float *A, int64_t a_rs, int img, const float *D, int64_t d_rs, int64_t Mrows, hipStream_t s);
+                hipStream_t s) const {
+        return wimg.rowgemm(A, a_rs, img, C, c_rs, add, add_rs, bias, Mrows, mk[lvl], s);
+    }
+    int colgemm(const float *A, int64_t a_rs, int img, const float *D, int64_t d_rs, int64_t Mrows, hipStream_t s) const {
+        return wimg.colgemm(A, a_rs, img, D, d_rs, Mrows, G.as<float>(), s);
+    }
     int bias_grad(const float *D, int64_t rs, int64_t Mrows, int N, size_t b_off, hipStream_t s);
     int conv_fwd(const Conv &c, T *const *parts, T &y, hipStream_t s) const;
     int conv_bwd(const Conv &c, T *const *parts, T &y, hipStream_t s);
@@ -256,23 +246,9 @@ struct DgdmUnetTrainer {
     int res_bwd(Res &r, T *const *parts, int S, hipStream_t s);
     int run(const float *x0, const float *noise, const float *sa, const float *sb, const int64_t *t, int S, int64_t S_total, bool backward, float *pred_out,
             float *loss_host, hipStream_t s);
-    int adam(float lr, hipStream_t s);
-    int repack(hipStream_t s);
-    int copy_state(int which, DgdmTensor *t, int n, bool to_device);
+    int step_adam(float lr, hipStream_t s);
+    int copy_state(int which, const DgdmTensor *t, int n, bool to_device);
 };
-
-int DgdmUnetTrainer::add_img(size_t w_off, int Kblk, std::initializer_list<int> taps, int N, int s_kc, int s_n, int base) {
-    ImgDesc d{};
-    d.src = (int64_t)w_off + base; d.dst = (int64_t)n_img;
-    d.Kblk = Kblk; d.ntaps = (int)taps.size();
-    int i = 0;
-    for (int t : taps) d.taps[i++] = t;
-    d.K = Kblk * d.ntaps; d.Kp = round_up(d.K, KC); d.N = N; d.Np = round_up(N, TN); d.s_kc = s_kc; d.s_n = s_n;
-    n_img += (size_t)d.Kp * d.Np;
-    max_img_elems = std::max(max_img_elems, d.Kp * d.Np);
-    descs.push_back(d);
-    return (int)descs.size() - 1;
-}
 
 // Conv1d weight [cout][cin][k] (Linear: k = 1), Downsample1d's Conv1d(k = 3, stride 2, padding 1), Upsample1d's ConvTranspose1d
 // weight [cin][cout][4] (stride 2, padding 1): the forward / input-gradient images of the file header
@@ -306,13 +282,13 @@ int DgdmUnetTrainer::reserve(int S) {
     const int rp1 = L + 8, rp2 = L / 2 + 4;
     M[0] = S; M[1] = (int64_t)S * rp1; M[2] = (int64_t)S * rp2;
     mk[0] = RowMask{0, 0, 0}; mk[1] = RowMask{rp1, 4, L}; mk[2] = RowMask{rp2, 2, L / 2};
-    std::vector<std::pair<float **, int64_t>> want;
+    Arena ar;
     auto tensor = [&](T &t, int C, int lvl, bool grad = true) {
         t.C = C; t.lvl = lvl;
-        want.push_back({&t.v, M[lvl] * C + 2 * GUARD});
-        if (grad) want.push_back({&t.g, M[lvl] * C + 2 * GUARD}); else t.g = nullptr;
+        ar.add(t.v, M[lvl] * C, GUARD);
+        if (grad) ar.add(t.g, M[lvl] * C, GUARD); else t.g = nullptr;
     };
-    auto plain = [&](float *&q, int64_t n) { want.push_back({&q, n}); };
+    auto plain = [&](float *&q, int64_t n) { ar.add(q, n); };
     tensor(t_x0, 1, 1, false); tensor(t_emb, dsed, 0, false); tensor(t_h1, 4 * dsed, 0); tensor(t_a1, 4 * dsed, 0); tensor(t_gf, dsed, 0); tensor(t_mg, dsed, 0);
     for (int i = 0; i < 8; ++i) {
         Res &r = res[i];
@@ -324,54 +300,9 @@ int DgdmUnetTrainer::reserve(int S) {
     tensor(t_ds, d0, 2); tensor(t_us, d0, 1); tensor(t_cf, d0, 1); tensor(t_af, d0, 1); tensor(t_pred, 1, 1);
     plain(f_st, (int64_t)S * 16); plain(f_sp, (int64_t)S * 2 * d0); plain(lpart, S);
     plain(cpart, ((M[1] + CS_ROWS - 1) / CS_ROWS) * 512);
-    int64_t total = 0;
-    for (auto &w : want) total += (w.second + 63) / 64 * 64;
-    int rc = ws.alloc((size_t)total * sizeof(float));
+    const int rc = ar.commit(ws);      // padding rows and guards are zero and stay zero
     if (rc) return rc;
-    DGDM_HIP_CHECK(hipMemset(ws.p, 0, (size_t)total * sizeof(float)));      // padding rows and guards are zero and stay zero
-    float *q = ws.as<float>();
-    for (auto &w : want) { *w.first = q; q += (w.second + 63) / 64 * 64; }
-    // tensors: skip the front guard
-    auto fix = [&](T &t) { t.v += GUARD; if (t.g) t.g += GUARD; };
-    for (T *t : {&t_x0, &t_emb, &t_h1, &t_a1, &t_gf, &t_mg, &t_ds, &t_us, &t_cf, &t_af, &t_pred}) fix(*t);
-    for (int i = 0; i < 8; ++i) { Res &r = res[i]; for (T *t : {&r.t_c1, &r.t_a, &r.t_c2, &r.t_out, &r.t_film}) fix(*t); if (r.has_rc) fix(r.t_rc); }
-    // weight-gradient partials: the largest (tiles x splits) product
-    wpart_floats = (int64_t)512 * TM * TN + (int64_t)64 * TM * TN;
-    if ((rc = wpart.alloc((size_t)wpart_floats * sizeof(float)))) return rc;
     S_ws = S;
-    return DGDM_OK;
-}
-
-int DgdmUnetTrainer::rowgemm(const float *A, int64_t a_rs, int img, float *C, int64_t c_rs, const float *add, int64_t add_rs, const float *bias, int64_t Mrows,
-                             int lvl, hipStream_t s) const {
-    const ImgDesc &d = descs[img];
-    RowGemm g{};
-    g.A = A; g.a_rs = a_rs; g.B = IMG.as<float>() + d.dst; g.Kp = d.Kp; g.Np = d.Np; g.C = C; g.c_rs = c_rs; g.N = d.N; g.add = add; g.add_rs = add_rs;
-    g.bias = bias; g.M = Mrows; g.mk = mk[lvl]; g.scalar_a = (a_rs & 3) != 0 || (reinterpret_cast<uintptr_t>(A) & 15) != 0;
-    hipLaunchKernelGGL(rowgemm_kernel, dim3((unsigned)((Mrows + TM - 1) / TM), (unsigned)(d.Np / TN)), dim3(256), 0, s, g);
-    DGDM_HIP_CHECK(hipGetLastError());
-    return DGDM_OK;
-}
-
-// dW in the layout of image `img` = sum over the rows of window(r) (x) D[r], scattered into the gradient of the image's tensor
-int DgdmUnetTrainer::colgemm(const float *A, int64_t a_rs, int img, const float *D, int64_t d_rs, int64_t Mrows, hipStream_t s) {
-    const ImgDesc &d = descs[img];
-    const int kt = (d.Kp + TM - 1) / TM, nt = d.Np / TN;
-    int64_t splits = std::min<int64_t>(std::max<int64_t>(1, Mrows / 256), std::max(1, 512 / (kt * nt)));
-    int64_t per = ((Mrows + splits - 1) / splits + KC - 1) / KC * KC;
-    splits = (Mrows + per - 1) / per;
-    ColGemm g{};
-    g.A = A; g.a_rs = a_rs; g.D = D; g.d_rs = d_rs; g.part = wpart.as<float>(); g.ldp = nt * TN; g.split_stride = (int64_t)kt * TM * g.ldp;
-    g.M = Mrows; g.m_per_split = per;
-    g.scalar_a = (a_rs & 3) != 0 || (reinterpret_cast<uintptr_t>(A) & 15) != 0;
-    g.scalar_d = (d_rs & 3) != 0 || (reinterpret_cast<uintptr_t>(D) & 15) != 0;
-    DGDM_REQUIRE(splits * g.split_stride <= wpart_floats, DGDM_EINVAL, "unet trainer: weight-gradient partials do not fit");
-    hipLaunchKernelGGL(colgemm_kernel, dim3(kt, nt, (unsigned)splits), dim3(256), 0, s, g);
-    DGDM_HIP_CHECK(hipGetLastError());
-    const int64_t n = (int64_t)d.K * d.N;
-    hipLaunchKernelGGL(wgrad_scatter_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, wpart.as<float>(), (int)splits, g.split_stride, g.ldp,
-                       descs_dev.as<ImgDesc>(), img, G.as<float>());
-    DGDM_HIP_CHECK(hipGetLastError());
     return DGDM_OK;
 }
 
@@ -491,20 +422,9 @@ int DgdmUnetTrainer::res_bwd(Res &r, T *const *parts, int S, hipStream_t s) {
     return DGDM_OK;
 }
 
-int DgdmUnetTrainer::repack(hipStream_t s) {
-    hipLaunchKernelGGL(repack_kernel, dim3((unsigned)((max_img_elems + 255) / 256), (unsigned)descs.size()), dim3(256), 0, s, P.as<float>(), IMG.as<float>(),
-                       descs_dev.as<ImgDesc>());
-    DGDM_HIP_CHECK(hipGetLastError());
-    return DGDM_OK;
-}
-
-int DgdmUnetTrainer::adam(float lr, hipStream_t s) {
-    ++adam_steps;
-    const double bc1 = 1.0 - std::pow((double)beta1, (double)adam_steps), bc2 = 1.0 - std::pow((double)beta2, (double)adam_steps);
-    hipLaunchKernelGGL(adam_kernel, dim3((unsigned)((n_params + 255) / 256)), dim3(256), 0, s, P.as<float>(), G.as<float>(), M1.as<float>(), V.as<float>(),
-                       (int64_t)n_params, beta1, beta2, eps, wd, (float)((double)lr / bc1), (float)std::sqrt(bc2));
-    DGDM_HIP_CHECK(hipGetLastError());
-    return repack(s);
+int DgdmUnetTrainer::step_adam(float lr, hipStream_t s) {
+    const int rc = adam(lr, n_params, s);
+    return rc ? rc : wimg.repack(P.as<float>(), s);
 }
 
 // Diffusion.get_stats (diffusion.py:126-166) on S samples: noisy input, eps-net forward, MSE loss; backward = what loss.backward() leaves
@@ -571,40 +491,15 @@ int DgdmUnetTrainer::run(const float *x0, const float *noise, const float *sa, c
         if ((rc = mish_bwd(t_h1, t_a1))) return rc;
         { auto pa = one(t_emb); if ((rc = conv_bwd(se1, pa.data(), t_h1, s))) return rc; }
     }
-    if (loss_host) {
-        DGDM_HIP_CHECK(hipMemcpyAsync(loss_host, loss_dev.p, sizeof(float), hipMemcpyDeviceToHost, s));
-        DGDM_HIP_CHECK(hipStreamSynchronize(s));
-    }
-    return DGDM_OK;
+    return read_loss(loss_host, s);
 }
 
 // which: 0 parameters, 1 gradients, 2 / 3 Adam's exp_avg / exp_avg_sq, 4 the EMA copy
-int DgdmUnetTrainer::copy_state(int which, DgdmTensor *t, int n, bool to_device) {
-    DevBuf *src = which == 0 ? &P : which == 1 ? &G : which == 2 ? &M1 : which == 3 ? &V : &E;
-    std::vector<float> host(n_params);
+int DgdmUnetTrainer::copy_state(int which, const DgdmTensor *t, int n, bool to_device) {
+    int rc = ParamStore::copy_state(which == 0 ? P : which == 1 ? G : which == 2 ? M1 : which == 3 ? V : E, nullptr, t, n, to_device);
+    if (rc || !to_device || which != 0) return rc;
+    if ((rc = wimg.repack(P.as<float>(), 0))) return rc;
     DGDM_HIP_CHECK(hipDeviceSynchronize());
-    DGDM_HIP_CHECK(hipMemcpy(host.data(), src->p, n_params * sizeof(float), hipMemcpyDeviceToHost));
-    std::map<std::string, DgdmTensor *> by;
-    for (int i = 0; i < n; ++i) by[t[i].name] = &t[i];
-    for (const Named &nm : named) {
-        auto it = by.find(nm.name);
-        if (it == by.end()) { set_error("state_dict key '%s' missing", nm.name.c_str()); return DGDM_EKEY; }
-        if (it->second->dtype != 0 || it->second->numel != nm.numel) {
-            set_error("state_dict key '%s': expected %lld float32 values, got %lld", nm.name.c_str(), (long long)nm.numel, (long long)it->second->numel);
-            return DGDM_EKEY;
-        }
-        float *user = const_cast<float *>(static_cast<const float *>(it->second->data));
-        if (to_device) memcpy(&host[nm.off], user, (size_t)nm.numel * sizeof(float));
-        else memcpy(user, &host[nm.off], (size_t)nm.numel * sizeof(float));
-    }
-    if (to_device) {
-        DGDM_HIP_CHECK(hipMemcpy(src->p, host.data(), n_params * sizeof(float), hipMemcpyHostToDevice));
-        if (which == 0) {
-            int rc = repack(0);
-            if (rc) return rc;
-            DGDM_HIP_CHECK(hipDeviceSynchronize());
-        }
-    }
     return DGDM_OK;
 }
 
@@ -647,13 +542,9 @@ extern "C" int dgdm_unet_trainer_create(DgdmUnetTrainer **out, const DgdmTensor 
     m->fg = m->add_param("final_conv.0.block.1.weight", d0); m->add_param("final_conv.0.block.1.bias", d0);
     m->make_conv(m->oconv, "final_conv.1", UT::S1, 1, d0, 1);
     int rc;
-    for (DevBuf *b : {&m->P, &m->G, &m->M1, &m->V, &m->E}) {
-        if ((rc = b->alloc(m->n_params * sizeof(float)))) return rc;
-        DGDM_HIP_CHECK(hipMemset(b->p, 0, m->n_params * sizeof(float)));
-    }
-    if ((rc = m->IMG.alloc(m->n_img * sizeof(float)))) return rc;
-    if ((rc = m->descs_dev.upload(m->descs.data(), m->descs.size() * sizeof(ImgDesc)))) return rc;
-    if ((rc = m->loss_dev.alloc(64))) return rc;
+    if ((rc = m->alloc_banks())) return rc;
+    if ((rc = m->E.alloc(m->n_params * sizeof(float)))) return rc;
+    if ((rc = m->wimg.alloc())) return rc;
     {   // SinusoidalPosEmb (diffusion_utils.py:32-34): exp(arange(half) * -(log(10000) / (half - 1))) in float32
         const int half = dsed / 2;
         std::vector<float> fr(half);
@@ -661,7 +552,7 @@ extern "C" int dgdm_unet_trainer_create(DgdmUnetTrainer **out, const DgdmTensor 
         for (int i = 0; i < half; ++i) fr[i] = expf((float)i * e);
         if ((rc = m->freqs.upload(fr.data(), fr.size() * sizeof(float)))) return rc;
     }
-    if ((rc = m->copy_state(0, const_cast<DgdmTensor *>(state_dict), n_tensors, true))) return rc;
+    if ((rc = m->copy_state(0, state_dict, n_tensors, true))) return rc;
     DGDM_HIP_CHECK(hipMemcpy(m->E.p, m->P.p, m->n_params * sizeof(float), hipMemcpyDeviceToDevice));     // EMAModel starts as a copy of the model
     *out = m.release();
     return DGDM_OK;
@@ -682,20 +573,16 @@ extern "C" int dgdm_unet_trainer_step(DgdmUnetTrainer *m, const float *x0_dev, c
                                       const int64_t *timesteps_dev, int samples, float lr, float *pred_dev, float *loss_host, void *stream) {
     int rc = dgdm_unet_trainer_forward_backward(m, x0_dev, noise_dev, sqrt_abar_dev, sqrt_1m_abar_dev, timesteps_dev, samples, samples, 1, pred_dev, nullptr, stream);
     if (rc) return rc;
-    if ((rc = m->adam(lr, (hipStream_t)stream))) return rc;
-    if (loss_host) {
-        DGDM_HIP_CHECK(hipMemcpyAsync(loss_host, m->loss_dev.p, sizeof(float), hipMemcpyDeviceToHost, (hipStream_t)stream));
-        DGDM_HIP_CHECK(hipStreamSynchronize((hipStream_t)stream));
-    }
-    return DGDM_OK;
+    if ((rc = m->step_adam(lr, (hipStream_t)stream))) return rc;
+    return m->read_loss(loss_host, stream);
 }
 
 extern "C" int64_t dgdm_unet_trainer_gradient_count(const DgdmUnetTrainer *m) { return m ? (int64_t)m->n_params : -1; }
 
 extern "C" int dgdm_unet_trainer_gradients(DgdmUnetTrainer *m, float *flat_dev, int64_t numel, int to_trainer, float scale, void *stream) {
     DGDM_REQUIRE(m && flat_dev && numel == (int64_t)m->n_params, DGDM_EINVAL, "dgdm_unet_trainer_gradients: expected %lld values", m ? (long long)m->n_params : 0LL);
-    DGDM_HIP_CHECK(hipMemcpyAsync(to_trainer ? m->G.p : (void *)flat_dev, to_trainer ? (const void *)flat_dev : m->G.p, (size_t)numel * sizeof(float),
-                                  hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    const int rc = ParamStore::exchange(m->G, flat_dev, numel, to_trainer, stream);
+    if (rc) return rc;
     if (to_trainer && scale != 1.f) {
         hipLaunchKernelGGL(scale_kernel, dim3((unsigned)((numel + 255) / 256)), dim3(256), 0, (hipStream_t)stream, m->G.as<float>(), numel, scale);
         DGDM_HIP_CHECK(hipGetLastError());
@@ -705,7 +592,7 @@ extern "C" int dgdm_unet_trainer_gradients(DgdmUnetTrainer *m, float *flat_dev, 
 
 extern "C" int dgdm_unet_trainer_apply(DgdmUnetTrainer *m, float lr, void *stream) {
     DGDM_REQUIRE(m, DGDM_EINVAL, "dgdm_unet_trainer_apply: null handle");
-    return m->adam(lr, (hipStream_t)stream);
+    return m->step_adam(lr, (hipStream_t)stream);
 }
 
 extern "C" int dgdm_unet_trainer_ema_step(DgdmUnetTrainer *m, float decay, float one_minus_decay, void *stream) {
@@ -724,7 +611,7 @@ extern "C" int dgdm_unet_trainer_export(DgdmUnetTrainer *m, int which, DgdmTenso
 extern "C" int dgdm_unet_trainer_import(DgdmUnetTrainer *m, int which, const DgdmTensor *tensors, int n_tensors, int64_t adam_steps) {
     DGDM_REQUIRE(m && tensors && which >= 0 && which <= 4, DGDM_EINVAL, "dgdm_unet_trainer_import: bad argument");
     if (adam_steps >= 0) m->adam_steps = adam_steps;
-    return m->copy_state(which, const_cast<DgdmTensor *>(tensors), n_tensors, true);
+    return m->copy_state(which, tensors, n_tensors, true);
 }
 
 extern "C" int64_t dgdm_unet_trainer_steps(const DgdmUnetTrainer *m) { return m ? m->adam_steps : -1; }

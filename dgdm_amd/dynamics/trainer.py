@@ -197,7 +197,7 @@ class Trainer(object):
     def _run(self, ctrl, score, input_ori, input_pos, object_vertices, train: bool, rows_per_sample: Optional[int] = None, drawn=None):
         if self._h is None:
             raise RuntimeError("Trainer.create_model() has not been called")
-        world, rank = _dist.world_rank()
+        world = _dist.world_rank()[0]
         c, nz, sa, sb, t, o, p, ob, sc, rows = self._inputs(ctrl, score, input_ori, input_pos, object_vertices, drawn, ahead=train)
         lr = float(self.optimizer.param_groups[0]["lr"])
         loss = C.c_float()
@@ -207,45 +207,58 @@ class Trainer(object):
             check(lib().dgdm_trainer2d_step(self._h, dptr(c), dptr(nz), dptr(sa), dptr(sb), dptr(t), dptr(o), dptr(p), dptr(ob), dptr(sc), rows, lr,
                                             1 if train else 0, dptr(pred), C.byref(loss), stream_ptr()))
             return float(loss.value), pred
-        # Data parallel, one process per GPU, with nn.DataParallel's semantics (trainer.py:41-43): the batch is cut into `world` chunks
-        # like torch.chunk does for scatter, every replica normalises with ITS chunk's statistics, the loss is the mean over the whole
-        # batch, the replicas' gradients add up (RCCL all-reduce) and every rank takes the same Adam step.  Every rank was handed the
-        # whole batch and drew the whole batch's noise and timesteps from the synchronised CPU generator (dist.init_from_env).
+
+        def cut(lo, hi):
+            self._hint(lo, hi, rows_per_sample)
+            return [v[lo:hi].contiguous() for v in (c, nz, sa, sb, t, o, p, ob, sc)]
+        return self._data_parallel("dgdm_trainer2d", cut, rows, train, 8 * 512, c.device)
+
+    def _data_parallel(self, prefix: str, cut, rows: int, train: bool, n_stats: int, dev):
+        """One step / inference of the `prefix` trainer (dgdm_trainer2d, dgdm_trainer3d) over `world` processes, one per GPU, with
+        nn.DataParallel's semantics (trainer.py:41-43 wraps both models): the rows are cut into `world` chunks as torch.chunk does for
+        scatter, every replica's BatchNorm layers normalise with ITS chunk's statistics, the loss is the mean over all rows, the
+        replicas' gradients add up (RCCL all-reduce) and every rank takes the same Adam step.  Every rank was handed all rows and made
+        all draws - noise, timesteps and, in 3-D, the FPS starts - from the synchronised CPU generator (dist.init_from_env) and keeps
+        its chunk's: the reference's replicas draw their FPS starts from that one generator in thread order, which is not defined;
+        chunk order is the single-process order.  cut(lo, hi) -> the library call's input arguments for the rows [lo, hi): device
+        tensors and host numpy arrays."""
+        world, rank = _dist.world_rank()
+        fn = lambda name: getattr(lib(), prefix + name)                                 # noqa: E731
+        lr = float(self.optimizer.param_groups[0]["lr"])
         cs = -(-rows // world)
-        lo, hi = min(rows, rank * cs), min(rows, (rank + 1) * cs)
+        bounds = [(min(rows, r * cs), min(rows, (r + 1) * cs)) for r in range(world)]
+        lo, hi = bounds[rank]
         n = hi - lo
         # decided from (rows, world), which every rank knows - a rank raising alone would leave the others waiting in the all-reduce
-        if train and any(min(rows, (r + 1) * cs) - min(rows, r * cs) == 1 for r in range(world)):
+        if train and any(b - a == 1 for a, b in bounds):
             raise ValueError("Expected more than 1 value per channel when training (a DataParallel chunk of one row)")
-        cut = lambda v: v[lo:hi].contiguous()                                           # noqa: E731
-        pred = torch.zeros((cs, 3), dtype=torch.float32, device=c.device)
+        args = cut(lo, hi) if n else []                                                 # kept alive until the call has been made
+        ptrs = [v.ctypes.data if isinstance(v, np.ndarray) else dptr(v) for v in args]
+        loss = C.c_float()
+        pred = torch.zeros((cs, 3), dtype=torch.float32, device=dev)
         share = 0.0
         if train:
-            flat = torch.zeros(int(lib().dgdm_trainer2d_gradient_count(self._h)), dtype=torch.float32, device=c.device)
+            flat = torch.zeros(int(fn("_gradient_count")(self._h)), dtype=torch.float32, device=dev)
             if n:
-                self._hint(lo, hi, rows_per_sample)
-                check(lib().dgdm_trainer2d_forward_backward(self._h, *[dptr(cut(v)) for v in (c, nz, sa, sb, t, o, p, ob, sc)], n, rows, dptr(pred),
-                                                            C.byref(loss), stream_ptr()))
-                check(lib().dgdm_trainer2d_gradients(self._h, dptr(flat), flat.numel(), 0, stream_ptr()))
+                check(fn("_forward_backward")(self._h, *ptrs, n, rows, dptr(pred), C.byref(loss), stream_ptr()))
+                check(fn("_gradients")(self._h, dptr(flat), flat.numel(), 0, stream_ptr()))
                 share = float(loss.value)
             flat = _dist.all_reduce_sum(flat)
-            check(lib().dgdm_trainer2d_gradients(self._h, dptr(flat), flat.numel(), 1, stream_ptr()))
-            check(lib().dgdm_trainer2d_apply(self._h, lr, stream_ptr()))
+            check(fn("_gradients")(self._h, dptr(flat), flat.numel(), 1, stream_ptr()))
+            check(fn("_apply")(self._h, lr, stream_ptr()))
             # BatchNorm running statistics: every rank has just updated its own from ITS chunk; nn.DataParallel keeps replica 0's
             # (buffers of the other replicas are thrown away with them), and that is what rank 0 saves - so every rank evaluates with them
-            run = torch.empty(8 * 512, dtype=torch.float32, device=c.device)
-            check(lib().dgdm_trainer2d_running_stats(self._h, dptr(run), run.numel(), 0, stream_ptr()))
+            run = torch.empty(n_stats, dtype=torch.float32, device=dev)
+            check(fn("_running_stats")(self._h, dptr(run), run.numel(), 0, stream_ptr()))
             run = _dist.broadcast_from_rank0(run)
-            check(lib().dgdm_trainer2d_running_stats(self._h, dptr(run), run.numel(), 1, stream_ptr()))
+            check(fn("_running_stats")(self._h, dptr(run), run.numel(), 1, stream_ptr()))
         elif n:
-            self._hint(lo, hi, rows_per_sample)
-            check(lib().dgdm_trainer2d_step(self._h, *[dptr(cut(v)) for v in (c, nz, sa, sb, t, o, p, ob, sc)], n, lr, 0, dptr(pred), C.byref(loss),
-                                            stream_ptr()))
+            check(fn("_step")(self._h, *ptrs, n, lr, 0, dptr(pred), C.byref(loss), stream_ptr()))
             share = float(loss.value) * n / rows
-        tail = torch.zeros((1, 3), dtype=torch.float32, device=c.device)
+        tail = torch.zeros((1, 3), dtype=torch.float32, device=dev)
         tail[0, 0] = share
         got = _dist.all_gather_rows(torch.cat([pred, tail]))                            # [world, cs + 1, 3]
-        full = torch.cat([got[r, :max(0, min(rows, (r + 1) * cs) - min(rows, r * cs))] for r in range(world)])
+        full = torch.cat([got[r, :b - a] for r, (a, b) in enumerate(bounds)])
         return float(got[:, cs, 0].sum()), full
 
     # ------------------------------------------------------------------ 3-D (csrc/train3d.hip)
@@ -254,7 +267,7 @@ class Trainer(object):
         (rows, 3, L): only channel 1 is noised (trainer.py:68) and read (profile_forward_3d.py:77); object_vertices (rows, 3, N)."""
         if self._h is None:
             raise RuntimeError("Trainer.create_model() has not been called")
-        world, rank = _dist.world_rank()
+        world = _dist.world_rank()[0]
         dev = torch.device("cuda", torch.cuda.current_device())
         f = lambda t: t.detach().to(device=dev, dtype=torch.float32).contiguous()       # noqa: E731
         noise, timesteps = drawn
@@ -274,46 +287,11 @@ class Trainer(object):
             check(lib().dgdm_trainer3d_step(self._h, *[dptr(v) for v in args], s1.ctypes.data, s2.ctypes.data, dptr(sc), rows, lr, 1 if train else 0, dptr(pred),
                                             C.byref(loss), stream_ptr()))
             return float(loss.value), pred
-        # Data parallel, one process per GPU, nn.DataParallel's semantics (trainer.py:41-43 wraps the 3-D model too): the rows are cut into
-        # `world` chunks as torch.chunk does for scatter, every replica's BatchNorm layers normalise with ITS chunk's statistics, the loss is
-        # the mean over all rows, the replicas' gradients add up (RCCL all-reduce) and every rank takes the same Adam step; rank 0's
-        # running statistics are the ones that survive (broadcast).  Every rank was handed all rows and made all draws - noise, timesteps
-        # and the FPS starts - from the synchronised CPU generator (dist.init_from_env) and keeps its chunk's: the reference's replicas
-        # draw their FPS starts from that one generator in thread order, which is not defined; chunk order is the single-process order.
-        cs = -(-rows // world)
-        lo, hi = min(rows, rank * cs), min(rows, (rank + 1) * cs)
-        n = hi - lo
-        if train and any(min(rows, (r + 1) * cs) - min(rows, r * cs) == 1 for r in range(world)):
-            raise ValueError("Expected more than 1 value per channel when training (a DataParallel chunk of one row)")
-        args = [f(v[lo:hi]) for v in (ctrl[:, 1, :], noise, ac ** 0.5, (1 - ac) ** 0.5, timesteps.float() / T, input_ori, input_pos)]
-        args.append(f(object_vertices[lo:hi].permute(0, 2, 1)))
-        sc = f(score[lo:hi])
-        a1, a2 = np.ascontiguousarray(s1[lo:hi]), np.ascontiguousarray(s2[lo:hi])
-        pred = torch.zeros((cs, 3), dtype=torch.float32, device=dev)
-        share = 0.0
-        if train:
-            flat = torch.zeros(int(lib().dgdm_trainer3d_gradient_count(self._h)), dtype=torch.float32, device=dev)
-            if n:
-                check(lib().dgdm_trainer3d_forward_backward(self._h, *[dptr(v) for v in args], a1.ctypes.data, a2.ctypes.data, dptr(sc), n, rows, dptr(pred),
-                                                            C.byref(loss), stream_ptr()))
-                check(lib().dgdm_trainer3d_gradients(self._h, dptr(flat), flat.numel(), 0, stream_ptr()))
-                share = float(loss.value)
-            flat = _dist.all_reduce_sum(flat)
-            check(lib().dgdm_trainer3d_gradients(self._h, dptr(flat), flat.numel(), 1, stream_ptr()))
-            check(lib().dgdm_trainer3d_apply(self._h, lr, stream_ptr()))
-            run = torch.empty(int(lib().dgdm_trainer3d_running_stats_count(self._h)), dtype=torch.float32, device=dev)
-            check(lib().dgdm_trainer3d_running_stats(self._h, dptr(run), run.numel(), 0, stream_ptr()))
-            run = _dist.broadcast_from_rank0(run)
-            check(lib().dgdm_trainer3d_running_stats(self._h, dptr(run), run.numel(), 1, stream_ptr()))
-        elif n:
-            check(lib().dgdm_trainer3d_step(self._h, *[dptr(v) for v in args], a1.ctypes.data, a2.ctypes.data, dptr(sc), n, lr, 0, dptr(pred), C.byref(loss),
-                                            stream_ptr()))
-            share = float(loss.value) * n / rows
-        tail = torch.zeros((1, 3), dtype=torch.float32, device=dev)
-        tail[0, 0] = share
-        got = _dist.all_gather_rows(torch.cat([pred, tail]))                            # [world, cs + 1, 3]
-        full = torch.cat([got[r, :max(0, min(rows, (r + 1) * cs) - min(rows, r * cs))] for r in range(world)])
-        return float(got[:, cs, 0].sum()), full
+
+        def cut(lo, hi):
+            args = [f(v[lo:hi]) for v in (ctrl[:, 1, :], noise, ac ** 0.5, (1 - ac) ** 0.5, timesteps.float() / T, input_ori, input_pos)]
+            return args + [f(object_vertices[lo:hi].permute(0, 2, 1)), np.ascontiguousarray(s1[lo:hi]), np.ascontiguousarray(s2[lo:hi]), f(score[lo:hi])]
+        return self._data_parallel("dgdm_trainer3d", cut, rows, train, int(lib().dgdm_trainer3d_running_stats_count(self._h)), dev)
 
     def _draw3d(self, rows: int):
         """trainer.py:68-73 for --fingers_3d: randn for channel 1's noise (the zeros around it draw nothing), then the timesteps."""
