@@ -69,6 +69,7 @@ struct DgdmGuidance {
     // so the A table carries one float32 rounding); ttmp64: scratch of the time encoder
     DevBuf V, genc, atab, chainbias, timepart, ttmp, ttmp64, partial, objdev, objidx, xobj, xobj16, starts, order, xchains, todo, groupoff;
     DevBuf loopx[2], loopeps, loopgrad, loopxrep, loopts;      // workspace of dgdm_guided_chains_run
+    DevBuf scorelogits;                      // dgdm_guidance_score: the logits when the caller does not want them
     DevBuf xidx, xidxchains, xtabptrs;       // embedding-table path: row index per reference row, per-chain lookup info, per-chain table base pointers
     bool xtab_enabled = true;       // test hook: modes 1-3 read materialised rows (per-step gather kernels) instead of the embedding table
     int xtab_policy = 0;            // 0: build the embedding tables once the objects have served more than XTAB_AFTER cond_fn calls; 1: at set_objects (test hook mode 5)
@@ -120,6 +121,11 @@ struct DgdmGuidance {
     // the embeddings of `n_calls` cond_fn calls at once: afterwards call k reads rows [k * R, (k + 1) * R) of every chain
     struct Embedded { bool tab = false, used16 = false; int64_t rows_per_chain = 0; };
     int embed(const int *objidx_host, int n_chains, const int64_t *starts_host, int n_calls, int64_t call_stride, Embedded *e, hipStream_t s);
+    // what cond_fn's gradient and its forward-only scoring share, up to the trunk launch: common_pre, 3-D: the rows' embeddings (`emb` /
+    // `call` as guidance_grad takes them), and the trunk parameters of the cond_fn grid in the float32 form (the caller swaps the weight
+    // streams for its arithmetic and adds its outputs)
+    int trunk_front(int kind, const float *x_dev, int timestep, const int *objidx_host, const int64_t *starts_host, int n_chains, const Embedded *emb,
+                    int call, dgdm::TrunkParams *p, hipStream_t s);
 };
 
 int DgdmGuidance::build_pose_table(const std::vector<float> &ori, const std::vector<float> &pos, DevBuf *dst, DevBuf *dst_tiled, hipStream_t s) {
@@ -666,6 +672,40 @@ int DgdmGuidance::embed(const int *oidx, int n_chains, const int64_t *starts_hos
     return DGDM_OK;
 }
 
+int DgdmGuidance::trunk_front(int kind, const float *x_dev, int timestep, const int *oidx, const int64_t *starts_host, int n_chains, const Embedded *emb,
+                              int call, TrunkParams *pp, hipStream_t s) {
+    DGDM_REQUIRE(n_objects > 0, DGDM_EINVAL, "dgdm_guidance_set_objects has not been called");
+    const float t_scaled = (float)timestep / (float)cfg.num_train_timesteps;      // timesteps.float() / T  (diffusion.py:487,496)
+    int rc;
+    prof_begin(s, DGDM_STAGE_GUIDE_MISC);
+    if ((rc = common_pre(x_dev, t_scaled, oidx, n_chains, s))) return rc;
+    prof_end(s, DGDM_STAGE_GUIDE_MISC, 0.0);
+    TrunkParams &p = *pp;
+    m->fill_trunk(&p);
+    if (kind == 3) {
+        Embedded own;
+        if (!emb) {
+            if ((rc = embed(oidx, n_chains, starts_host, 1, 0, &own, s))) return rc;
+            emb = &own;
+            call = 0;
+        }
+        const size_t row0 = (size_t)call * R;
+        p.xstride = emb->rows_per_chain;
+        if (emb->tab) {
+            p.xidx = xidx.as<int>() + row0;
+            if (bf16) p.xtab16 = xtabptrs.as<const uint32_t *>();
+            else p.xtab = xtabptrs.as<const float *>();
+        } else {
+            p.xobj = xobj.as<float>() + row0 * 256;
+            p.xobj16 = emb->used16 ? xobj16.as<uint32_t>() + row0 * 128 : nullptr;
+        }
+    }
+    p.Atab = atab.as<float>(); p.Ptab = ptab.as<float>(); p.PtabT = ptab_t.as<float>(); p.Pmax = pmax.as<float>();
+    p.B = B; p.C = C; p.tiles_per_b = tiles_per_b; p.ntiles = n_chains * B * tiles_per_b; p.R = R;
+    if (kind != 3) p.xstride = R;
+    return DGDM_OK;
+}
+
 // cond_fn for n_chains chains.  3-D: `emb` = the embeddings made by DgdmGuidance::embed for a run of calls, `call` = which of them this is;
 // emb == nullptr: this call's own (starts_host = its draws).
 static int guidance_grad(DgdmGuidance *g, int kind, const float *x_dev, int timestep, const DgdmObjective *objectives, const float *rowcoef_dev,
@@ -674,7 +714,6 @@ static int guidance_grad(DgdmGuidance *g, int kind, const float *x_dev, int time
     DGDM_REQUIRE(g && x_dev && objectives && grad_dev, DGDM_EINVAL, "guidance_grad: null argument");
     if (g->m->kind != kind) { set_error("model type not supported: %d-D entry point on a %d-D model", kind, g->m->kind); return DGDM_EMODE; }
     DGDM_REQUIRE(n_chains > 0 && n_chains <= g->cfg.max_chains, DGDM_EINVAL, "n_chains %d outside 1..%d", n_chains, g->cfg.max_chains);
-    DGDM_REQUIRE(g->n_objects > 0, DGDM_EINVAL, "dgdm_guidance_set_objects has not been called");
     std::vector<int> oidx(n_chains);
     std::vector<TrunkObjective> tob(n_chains);
     for (int i = 0; i < n_chains; ++i) {
@@ -683,36 +722,12 @@ static int guidance_grad(DgdmGuidance *g, int kind, const float *x_dev, int time
         tob[i].use_rowcoef = objectives[i].use_rowcoef; tob[i].pad = 0;
         DGDM_REQUIRE(!tob[i].use_rowcoef || rowcoef_dev, DGDM_EINVAL, "chain %d uses rowcoef but rowcoef_dev is null", i);
     }
-    const float t_scaled = (float)timestep / (float)g->cfg.num_train_timesteps;      // timesteps.float() / T  (diffusion.py:487,496)
     int rc;
-    prof_begin(s, DGDM_STAGE_GUIDE_MISC);
-    if ((rc = g->common_pre(x_dev, t_scaled, oidx.data(), n_chains, s))) return rc;
-    DGDM_HIP_CHECK(hipMemcpyAsync(g->objdev.p, tob.data(), sizeof(TrunkObjective) * n_chains, hipMemcpyHostToDevice, s));
-    prof_end(s, DGDM_STAGE_GUIDE_MISC, 0.0);
     TrunkParams p;
-    g->m->fill_trunk(&p);
-    if (kind == 3) {
-        DgdmGuidance::Embedded own;
-        if (!emb) {
-            if ((rc = g->embed(oidx.data(), n_chains, starts_host, 1, 0, &own, s))) return rc;
-            emb = &own;
-            call = 0;
-        }
-        const size_t row0 = (size_t)call * g->R;
-        p.xstride = emb->rows_per_chain;
-        if (emb->tab) {
-            p.xidx = g->xidx.as<int>() + row0;
-            if (g->bf16) p.xtab16 = g->xtabptrs.as<const uint32_t *>();
-            else p.xtab = g->xtabptrs.as<const float *>();
-        } else {
-            p.xobj = g->xobj.as<float>() + row0 * 256;
-            p.xobj16 = emb->used16 ? g->xobj16.as<uint32_t>() + row0 * 128 : nullptr;
-        }
-    }
-    p.Atab = g->atab.as<float>(); p.Ptab = g->ptab.as<float>(); p.PtabT = g->ptab_t.as<float>(); p.Pmax = g->pmax.as<float>(); p.obj = g->objdev.as<TrunkObjective>(); p.rowcoef = rowcoef_dev;
+    if ((rc = g->trunk_front(kind, x_dev, timestep, oidx.data(), starts_host, n_chains, emb, call, &p, s))) return rc;
+    DGDM_HIP_CHECK(hipMemcpyAsync(g->objdev.p, tob.data(), sizeof(TrunkObjective) * n_chains, hipMemcpyHostToDevice, s));
+    p.obj = g->objdev.as<TrunkObjective>(); p.rowcoef = rowcoef_dev;
     p.partial = g->partial.as<float>();
-    p.B = g->B; p.C = g->C; p.tiles_per_b = g->tiles_per_b; p.ntiles = n_chains * g->B * g->tiles_per_b; p.R = g->R;
-    if (kind != 3) p.xstride = g->R;
     if (g->bf16) {
         g->m->fill_trunk_bf16(&p);       // only the two weight streams differ
         if ((rc = trunk_bf16_launch(kind, p, s))) return rc;
@@ -738,6 +753,34 @@ extern "C" int dgdm_dyn2d_guidance_grad(DgdmGuidance *g, const float *x_dev, int
 extern "C" int dgdm_dyn3d_guidance_grad(DgdmGuidance *g, const float *x_dev, int timestep, const DgdmObjective *objectives,
                                         const float *rowcoef_dev, const int64_t *starts_host, int n_chains, float *grad_dev, void *stream) {
     return guidance_grad(g, 3, x_dev, timestep, objectives, rowcoef_dev, starts_host, n_chains, grad_dev, (hipStream_t)stream);
+}
+
+// Diffusion.cond_fn's forward half (generator/diffusion.py:473-504 up to the classifier's output) and the classes of :506-532 on it.
+extern "C" int dgdm_guidance_score(DgdmGuidance *g, const float *x_dev, int timestep, const int32_t *object_of_chain, const int64_t *starts_host,
+                                   const float thr[3], int n_chains, float *logits_dev, int32_t *counts_dev, float *sums_dev, void *stream) {
+    DGDM_REQUIRE(g && x_dev && object_of_chain && thr && counts_dev && sums_dev, DGDM_EINVAL, "dgdm_guidance_score: null argument");
+    DGDM_REQUIRE(!g->bf16, DGDM_EINVAL, "dgdm_guidance_score: the bf16 trunk has no forward-only form (contraction dtypes f32 / f32_f16x3 / f32_mfma)");
+    hipStream_t s = (hipStream_t)stream;
+    const int kind = g->m->kind;
+    DGDM_REQUIRE(kind == 2 || starts_host, DGDM_EINVAL, "3-D scoring needs the FPS start indices");
+    DGDM_REQUIRE(n_chains > 0 && n_chains <= g->cfg.max_chains, DGDM_EINVAL, "n_chains %d outside 1..%d", n_chains, g->cfg.max_chains);
+    int rc;
+    if (!logits_dev) {
+        if ((rc = g->scorelogits.alloc((size_t)n_chains * g->R * 3 * sizeof(float)))) return rc;
+        logits_dev = g->scorelogits.as<float>();
+    }
+    const std::vector<int> oidx(object_of_chain, object_of_chain + n_chains);
+    TrunkParams p;
+    if ((rc = g->trunk_front(kind, x_dev, timestep, oidx.data(), starts_host, n_chains, nullptr, 0, &p, s))) return rc;
+    p.logits = logits_dev;
+    if (g->f32_mfma) {
+        if ((rc = trunk_launch(kind, false, true, p, s))) return rc;
+    } else {
+        TrunkF16Scales sc;
+        g->m->fill_trunk_f16(&p, &sc);
+        if ((rc = trunk_f16l_forward_launch(kind, p, sc, s))) return rc;
+    }
+    return score_tally(logits_dev, n_chains, g->B, g->C, thr, counts_dev, sums_dev, s);
 }
 
 // ================================================================================================ the denoise loop as one call

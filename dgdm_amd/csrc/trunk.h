@@ -56,6 +56,13 @@ struct TrunkF16Scales {
 };
 // (the weight stream is shared by the workgroup's four waves through LDS: trunk_f16l.hip)
 int trunk_f16l_launch(int kind, const TrunkParams &p, const TrunkF16Scales &sc, hipStream_t s);
+// The forward half alone: the logits of every valid row to p.logits [nchain][R][3]; p.Wbwd, p.obj, p.rowcoef and p.partial are not read.
+int trunk_f16l_forward_launch(int kind, const TrunkParams &p, const TrunkF16Scales &sc, hipStream_t s);
+
+// Per (chain, finger) tally of forward-only logits [n_chains][B * C][3] (row = cell * B + finger; score.hip): the joint class histogram
+// counts [n_chains][B][27] (bin = (class of d0 * 3 + class of d1) * 3 + class of d2; class 2 if l > thr, 0 if l < -thr, else 1) and
+// sums [n_chains][B][4] = sum d0, sum |d0|, sum d1, sum d2.  Fixed reduction order: the same bits every run.
+int score_tally(const float *logits, int n_chains, int B, int C, const float thr[3], int32_t *counts, float *sums, hipStream_t s);
 
 // bf16-contraction variant (trunk_bf16.hip): table mode, forward + backward only.  p.Wfwd / p.Wbwd point at the bf16 streams
 // (DgdmDynamics::fill_trunk_bf16); everything else in TrunkParams means the same.

@@ -170,7 +170,8 @@ struct LStream {
 // row (E: this lane's row); on return Y = this layer's accumulators and E their scale.  ew: the weight matrix' scale exponent.
 // wn: the operands of the NEXT group to be consumed (read from LDS one group ahead); precondition of every consumer below: wn holds the
 // first group of the pass about to start, postcondition: the first group of the pass that follows in the stream.
-template <bool FWD, bool BIAS>
+// MASKS = false (the forward-only kernel): the ReLU sign bits are neither collected nor stored, smask is not touched.
+template <bool FWD, bool BIAS, bool MASKS = true>
 __device__ __forceinline__ void stream_layer(LStream &ls, v4f32 (&wn)[4], const lds_f4_t *bias /* LDS: the layer's 256 values */, const f32x16 (&Yp)[8], f32x16 (&Y)[8],
                                              uint32_t (*smask)[256], const int slot_in, const int tid, const int h4, int &E, const int ew) {
     float mx = 0.f;
@@ -208,8 +209,10 @@ __device__ __forceinline__ void stream_layer(LStream &ls, v4f32 (&wn)[4], const 
             // stored) - and max(0, -that) is the scaled ReLU.  (Round 5's steps to this form, each bit-identical: DESIGN.md 4.1;
             // what the kernel costs without this item at all, -13 %, and without its LDS operand reads, -1.7 %: measured there too.)
             const hf32x2_t nv = __builtin_elementwise_fma(hf32x2_t{y[2 * d], y[2 * d + 1]}, hf32x2_t{-f, -f}, hf32x2_t{0.f, 0.f});
-            mk = __builtin_amdgcn_alignbit(mk, __float_as_uint(nv.x), 31);
-            mk = __builtin_amdgcn_alignbit(mk, __float_as_uint(nv.y), 31);
+            if (MASKS) {
+                mk = __builtin_amdgcn_alignbit(mk, __float_as_uint(nv.x), 31);
+                mk = __builtin_amdgcn_alignbit(mk, __float_as_uint(nv.y), 31);
+            }
             asm("v_max_f32 %0, 0, -%1" : "=v"(lo) : "v"(nv.x));
             asm("v_max_f32 %0, 0, -%1" : "=v"(hi) : "v"(nv.y));
         } else {
@@ -241,7 +244,7 @@ __device__ __forceinline__ void stream_layer(LStream &ls, v4f32 (&wn)[4], const 
                     const int q = sx * 4 + pp, nb = b + 1;
                     if (q == 0 && (nb & 1) == 0) mk = FWD ? 0u : smask[slot_in + nb / 2][tid];
                     item(Yp[nb], nb, q, true);
-                    if (FWD && q == 7 && (nb & 1) == 1) smask[slot_in + nb / 2][tid] = __builtin_bitreverse32(mk);
+                    if (MASKS && FWD && q == 7 && (nb & 1) == 1) smask[slot_in + nb / 2][tid] = __builtin_bitreverse32(mk);
                 }
                 F16_STEP(Y[2 * pp], Y[2 * pp + 1], w, P[b & 1][0][sx], P[b & 1][1][sx]);
                 __builtin_amdgcn_sched_barrier(0);
@@ -318,7 +321,10 @@ __device__ __forceinline__ void rows_sum2(float &a, float &b) {
 using namespace f16l;
 
 
-template <int KIND>
+// FWD_ONLY: the forward half alone (dgdm_guidance_score) - the same table terms, layers and output layer, the three logits of every
+// valid row to p.logits, and nothing of what only serves the way back: no sign masks (and no LDS for them: smask has no reader or
+// writer left in this instantiation and is not allocated), no backward stream, no objective, no partial sums.
+template <int KIND, bool FWD_ONLY = false>
 __global__ __launch_bounds__(256, 1) void trunk_f16l_kernel(const TrunkParams p, const TrunkF16Scales sc) {
     constexpr int W1B = (KIND == 3) ? 16 : 8;
     constexpr int W1 = W1B * 32;
@@ -473,7 +479,7 @@ __global__ __launch_bounds__(256, 1) void trunk_f16l_kernel(const TrunkParams p,
                     __builtin_amdgcn_sched_barrier(0);
                 }
             }
-            smask[blk / 2][tid] = bits2;
+            if (!FWD_ONLY) smask[blk / 2][tid] = bits2;
         }
         slot = 8;                                             // wn: entries 0 .. 3 of the stack's first chunk already; E: layer 2's row scale
     }
@@ -484,14 +490,16 @@ __global__ __launch_bounds__(256, 1) void trunk_f16l_kernel(const TrunkParams p,
     constexpr int BASE = (KIND == 3) ? 8 : 0;
     f32x16 Z[8];
     for (int l = 0; l < p.n_mid; ++l) {
-        stream_layer<true, true>(ls, wn, sbias + 64 * l, Y, Z, smask, BASE + 4 * l, tid, h4, E, sc.ew_mid[l]);
+        stream_layer<true, true, !FWD_ONLY>(ls, wn, sbias + 64 * l, Y, Z, smask, BASE + 4 * l, tid, h4, E, sc.ew_mid[l]);
 #pragma unroll
         for (int o = 0; o < 8; ++o) Y[o] = Z[o];
     }
     slot = BASE + 4 * p.n_mid;
     relu_mask<8>(Y, m);
+    if (!FWD_ONLY) {
 #pragma unroll
-    for (int i = 0; i < 4; ++i) smask[slot + i][tid] = m[i];
+        for (int i = 0; i < 4; ++i) smask[slot + i][tid] = m[i];
+    }
     slot += 4;
 
     // ---- output layer (256 -> 3) on the VALU on the scaled activations, 2^-E taken out of the three sums
@@ -513,6 +521,16 @@ __global__ __launch_bounds__(256, 1) void trunk_f16l_kernel(const TrunkParams p,
     const float unE = pow2f(-E);
     const float d0 = fmaf(s0, unE, p.bout[0]), d1 = fmaf(s1, unE, p.bout[1]), d2 = fmaf(s2, unE, p.bout[2]);
 
+    if (FWD_ONLY) {
+        // the last stack layer requested chunks behind the end of the stream (the buffer descriptor turns them into zeros): they must have
+        // landed before the workgroup gives its LDS back
+        asm volatile("s_waitcnt vmcnt(0)" : : : "memory");
+        if (live && valid && lane < 32) {                     // a finger's last tile may hold padding rows: not written
+            float *dst = p.logits + ((size_t)chain * p.R + r) * 3;
+            dst[0] = d0; dst[1] = d1; dst[2] = d2;
+        }
+        return;
+    }
     const wrsrc_t rsB = weight_rsrc(p.Wbwd, p.bwd_bytes);
     ls.start(rsB, 0);                                         // in flight while the objective runs on the VALU
     const TrunkObjective ob = p.obj[chain];
@@ -590,6 +608,21 @@ __global__ __launch_bounds__(256, 1) void trunk_f16l_kernel(const TrunkParams p,
 #pragma unroll
         for (int rr = 0; rr < 16; ++rr) fold_one(rr, 15, bits);
     }
+}
+
+int trunk_f16l_forward_launch(int kind, const TrunkParams &p, const TrunkF16Scales &sc, hipStream_t s) {
+    if (p.n_mid != (kind == 3 ? 6 : 7) || !p.logits) return DGDM_EINVAL;
+    const int grid = (p.ntiles + 3) / 4;
+    if (grid == 0) return DGDM_OK;
+    const double rows = (double)(p.ntiles / std::max(1, p.tiles_per_b)) * p.C;
+    const double mid = 2.0 * 256 * 256 * p.n_mid;
+    const double per_row = (kind == 3) ? 2.0 * 256 * 512 * 2 + mid : mid;
+    prof_begin(s, DGDM_STAGE_TRUNK);
+    if (kind == 2) hipLaunchKernelGGL((trunk_f16l_kernel<2, true>), dim3(grid), dim3(256), 0, s, p, sc);
+    else hipLaunchKernelGGL((trunk_f16l_kernel<3, true>), dim3(grid), dim3(256), 0, s, p, sc);
+    DGDM_HIP_CHECK(hipGetLastError());
+    prof_end(s, DGDM_STAGE_TRUNK, rows * per_row);
+    return DGDM_OK;
 }
 
 int trunk_f16l_launch(int kind, const TrunkParams &p, const TrunkF16Scales &sc, hipStream_t s) {

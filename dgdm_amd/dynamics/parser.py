@@ -39,6 +39,7 @@ _FLAGS = [
     ("num_cpus", int, 4, "CPU workers of the (external) simulator"),
     ("fingers_3d", "flag", None, "3-D fingers / PointNet++ dynamics model"),
     ("render_video", "flag", None, "simulator videos (external)"),
+    ("predicted_sim", "flag", None, "fill the objective tables with the dynamics model's predictions (dynamics/predicted.py)"),
     ("seed", int, 0, "seed of the start noise"),
 ]
 

@@ -1,0 +1,177 @@
+"""Scores of finger designs PREDICTED by the dynamics model, in the shapes the validation harness takes from a simulator.
+
+The reference ranks its samples with MuJoCo roll-outs (dynamics/sim_test_mj*.py), which this package does not ship.  The dynamics
+model that guides the chains predicts, for every (finger, object, orientation, position), the normalised motion the simulator
+would measure after one interaction; ``engine.Guidance.score`` evaluates it forward-only on the whole grid.  This module turns
+those numbers into
+
+* ``predicted_objective``: the score dict of one finger from the grid tally (class histogram + sums), and
+* ``PredictedSimulator``: a callable with the ``sim_test_batch`` / ``sim_test_batch_3d`` signature for
+  ``Diffusion(simulator=...)``, so the unguided / guided / multi-object tables are filled without a simulator.
+
+Units.  ``std`` and ``threshold`` are ``DynamicsDataset``'s (dynamics/dataloader.py:11-16, ``SCORE_STD`` / ``SCORE_THRESHOLD``):
+radians for the rotation, metres for the two shifts; the model's outputs are scores divided by ``std``, and the class rule
+compares them with ``threshold / std``.  The dicts built here are in the units of the simulator's ``metrics`` dict
+(sim_test_mj.py:209-218): degrees (x 180 / pi) and centimetres (x 100).
+
+These are the dynamics model's opinion, not simulator measurements; every metric dict carries ``'predicted': True``.
+"""
+from __future__ import annotations
+
+from typing import Any, Dict, List, Optional, Sequence
+
+import numpy as np
+
+from .metrics import _ROT, _SHIFT
+
+DEG = 180.0 / np.pi       # radians -> degrees (sim_test_mj.py:210)
+CM = 100.0                # metres -> centimetres (:211)
+
+
+def classes(logits: np.ndarray, threshold_std: Sequence[float]) -> np.ndarray:
+    """2 above the threshold, 0 below its negative, 1 between, per output (generator/diffusion.py:532, sim_test_mj.py:198-200 + 1)."""
+    thr = np.asarray(threshold_std, dtype=np.float32)
+    l = np.asarray(logits, dtype=np.float32)
+    return np.where(l > thr, 2, np.where(l < -thr, 0, 1)).astype(np.int64)
+
+
+def predicted_objective(counts, sums, n_cells: int, std: Sequence[float], opt_obj: str) -> Dict[str, Any]:
+    """Scores of one finger on one object for ``opt_obj`` from the tally ``Guidance.score`` returns for it: ``counts`` (3, 3, 3),
+    the joint histogram of the classes of (rotation, shift x, shift y) over the finger's ``n_cells`` grid cells, and ``sums`` (4,) =
+    sum d0, sum |d0|, sum d1, sum d2 of the normalised outputs.  Key names and dtypes as ``metric2objective`` (dynamics/metrics.py:
+    67-234) gives them for a metric whose profiles are the grid's classes and whose motions are the un-normalised outputs, with the
+    one-step convention for the ``final_*`` keys (final motion = predicted motion).  ``std``: the dataset's (rad, m, m); the means
+    come out in degrees and centimetres like the simulator's.  'convergence' is scored on final angles per orientation, which a
+    histogram does not hold: use ``build_metric`` + ``metric2objective`` for it."""
+    c = np.asarray(counts).reshape(3, 3, 3).astype(np.int64)
+    s = np.asarray(sums, dtype=np.float64).reshape(4)
+    n = int(n_cells)
+    if int(c.sum()) != n:
+        raise ValueError(f"predicted_objective: the histogram holds {int(c.sum())} cells, n_cells says {n}")
+    std = np.asarray(std, dtype=np.float64).reshape(3)
+    rate = lambda k: np.float32(k) / np.float32(n)                                          # noqa: E731  (np.mean(..., dtype=float32))
+    rot_n = c.sum(axis=(1, 2))                                                              # cells per rotation class
+    shift_n = {'x': c.sum(axis=(0, 2)), 'y': c.sum(axis=(0, 1))}
+    d_theta, d_theta_abs = s[0] / n * std[0] * DEG, s[1] / n * std[0] * DEG
+    d_pos = {'x': s[2] / n * std[1] * CM, 'y': s[3] / n * std[2] * CM}
+
+    def rot_part(rot):
+        return {f'num_{rot}_classes': np.int16(rot_n[_ROT[rot]]), 'delta_theta': d_theta, 'final_delta_theta': d_theta}
+
+    def shift_part(shift):
+        ax, _, cls = _SHIFT[shift]
+        return {f'num_{shift}_classes': np.int16(shift_n[ax][cls]), f'delta_pos_{ax}': d_pos[ax], f'final_pos_{ax}': d_pos[ax]}
+
+    if opt_obj == 'rotate':
+        return {'success_rate': rate(rot_n[0] + rot_n[2]), 'num_zero_classes': np.int16(rot_n[1]), 'delta_theta_abs': d_theta_abs,
+                'final_delta_theta_abs': d_theta_abs}
+    if opt_obj == 'convergence':
+        raise ValueError("predicted_objective: 'convergence' needs the final angle per orientation (build_metric + metric2objective)")
+    head, _, tail = opt_obj.partition('_')
+    if head == 'rotate' and tail in _ROT:
+        return {'success_rate': rate(rot_n[_ROT[tail]]), **rot_part(tail)}
+    if head == 'shift' and tail in _SHIFT:
+        ax, _, cls = _SHIFT[tail]
+        return {'success_rate': rate(shift_n[ax][cls]), **shift_part(tail)}
+    if head in _ROT and tail in _SHIFT:
+        ax, _, cls = _SHIFT[tail]
+        joint = c[_ROT[head]].sum(axis=1 if ax == 'x' else 0)[cls]
+        rot, sh = rot_part(head), shift_part(tail)
+        return {'success_rate': rate(joint), f'num_{head}_{tail}_classes': rot[f'num_{head}_classes'] + sh[f'num_{tail}_classes'], **rot, **sh}
+    raise ValueError('opt obj not supported')
+
+
+def build_metric(logits, threshold_std: Sequence[float], std: Sequence[float], ori_range: Sequence[float] = (-1.0, 1.0)) -> Dict[str, Any]:
+    """The ``metric`` dict ``metric2objective`` consumes (sim_test_mj.py:209-218) for one (object, gripper) from the model's
+    normalised outputs ``logits`` (num_rot, 3) at the centre position over ``num_rot`` orientations of ``ori_range``: profiles from
+    the classes, motions un-normalised with ``std`` (degrees, centimetres).  The model predicts one interaction, not a settled pose:
+    ``final_theta`` = initial angle + predicted rotation, ``final_delta_theta`` = ``delta_theta``, ``final_pos`` = ``delta_pos``."""
+    l = np.asarray(logits, dtype=np.float32).reshape(-1, 3)
+    std = np.asarray(std, dtype=np.float64).reshape(3)
+    cls = classes(l, threshold_std)
+    delta_theta = l[:, 0].astype(np.float64) * std[0] * DEG
+    delta_pos = np.stack([l[:, 1].astype(np.float64) * std[1] * CM, l[:, 2].astype(np.float64) * std[2] * CM, np.zeros(len(l))], axis=1)
+    initial = (np.linspace(ori_range[0], ori_range[1], len(l)) + 1.0) * 180.0              # z_rots of sim_test_mj.py:142, in degrees
+    return {'delta_theta': delta_theta, 'delta_pos': delta_pos, 'profile': cls[:, 0], 'profile_x': cls[:, 1], 'profile_y': cls[:, 2],
+            'final_theta': initial + delta_theta, 'final_delta_theta': delta_theta.copy(), 'final_pos': delta_pos.copy(), 'predicted': True}
+
+
+def center_index(num_pos: int) -> int:
+    """Index of the position 0 in linspace(-1, 1, num_pos); an even num_pos has none."""
+    if num_pos % 2 == 0:
+        raise ValueError(f"PredictedSimulator: num_pos = {num_pos} is even, so the position grid linspace(-1, 1, {num_pos}) has no centre cell "
+                         "(pos = 0); use an odd num_pos")
+    return num_pos // 2
+
+
+def center_rows(logits, batch: int, grid_size: int, num_pos: int):
+    """logits (n, R, 3) on the cond_fn grid (row = cell * B + finger, cell = (g * P + px) * P + py), tensor or array -> (n, B, G, 3):
+    the rows at the centre position px = py = P // 2, where pos = (0, 0)."""
+    c = center_index(num_pos)
+    v = logits.reshape(logits.shape[0], grid_size, num_pos, num_pos, batch, 3)[:, :, c, c]
+    return v.permute(0, 2, 1, 3) if hasattr(v, "permute") else v.transpose(0, 2, 1, 3)
+
+
+class PredictedSimulator:
+    """``sim_test_batch`` / ``sim_test_batch_3d`` (dynamics/sim_test_mj.py:249, sim_test_mj_3d.py:229) answered by the dynamics model
+    of a ``Diffusion``: ``simulator(samples (n, L, 1), object_ids, save_dir, num_cpus=, num_rot=, ori_range=, render=, render_last=)``
+    -> ``(gripper_imgs, metrics, profiles, profiles_x, profiles_y, finals, videos, save_gripper_dirs)``, object-major, gripper-minor.
+
+    Per (object, gripper) the ``metric`` dict is ``build_metric`` of the centre-position cells of ``Guidance.score``'s logits over
+    ``num_rot`` orientations of ``ori_range`` at timestep 0, with ``Diffusion.threshold_std`` / ``Diffusion.std`` (the dataset's units,
+    see the module docstring).  Nothing is rendered: the plot slots are None, the video slots empty lists.
+
+    The handles are the simulator's own (nothing the sampling path keeps is touched), and the 3-D FPS start draws come from a
+    private ``sampler.TorchRng`` seeded from ``Diffusion.seed`` - never from the global CPU generator - so the sampled designs are
+    bit-identical with scoring on and off."""
+
+    def __init__(self, diffusion):
+        self.diffusion = diffusion
+        self._handles: Dict[Any, Any] = {}
+        self._rng = None
+
+    def _guidance(self, batch: int, num_rot: int, ori_range, objects):
+        import torch
+        from .. import engine
+        d = self.diffusion
+        key = (batch, num_rot, float(ori_range[0]), float(ori_range[1]), tuple(objects.shape))
+        g = self._handles.get(key)
+        dyn = d._dyn().handle()
+        if g is None or g.dyn is not dyn:
+            g = engine.Guidance(dyn, batch, num_rot, d.num_pos, ori_range, objects.shape[0], d.noise_scheduler.config.num_train_timesteps,
+                                objects.shape[1], d.sub_batch_size if d.mode == 'point_3d' else 0, max_objects=objects.shape[0],
+                                contraction_dtype=d.contraction_dtype)
+            g._bank = None
+            self._handles[key] = g
+        if g._bank is None or not torch.equal(g._bank, objects):
+            g.set_objects(objects.to(d.device))
+            g._bank = objects.clone()
+        return g
+
+    def __call__(self, samples, object_ids, save_dir: Optional[str] = None, num_cpus: int = 32, num_rot: int = 360,
+                 ori_range: Sequence[float] = (-1.0, 1.0), render: bool = True, render_last: bool = False):
+        import torch
+        from .. import sampler
+        d = self.diffusion
+        center_index(d.num_pos)
+        x = torch.as_tensor(np.asarray(samples), dtype=torch.float32)
+        n = x.shape[0]
+        x = x.reshape(n, -1)
+        bank = torch.as_tensor(d.object_vertices).detach().cpu().float()
+        known = d._object_ids()
+        oidx = [known.index(o) for o in object_ids]
+        g = self._guidance(n, int(num_rot), ori_range, bank)
+        nc = len(oidx)
+        starts = None
+        if d.mode == 'point_3d':
+            if self._rng is None:
+                self._rng = sampler.TorchRng(seed=int(d.seed))
+            starts = self._rng.fps_starts(g.cfg.num_object_points, g.cfg.sub_batch_size, g.rows, n_calls=nc)
+        thr = [float(v) for v in d.threshold_std]
+        _, _, logits = g.score(x.to(d.device)[None].expand(nc, n, x.shape[1]).contiguous(), oidx, thr, timestep=0, starts=starts, want_logits=True)
+        rows = center_rows(logits, n, int(num_rot), d.num_pos).cpu().numpy()                 # (object, gripper, orientation, 3)
+        std = [float(v) for v in d.std]
+        metrics = [build_metric(rows[i, b], thr, std, ori_range) for i in range(nc) for b in range(n)]
+        total = nc * n
+        none: List[Any] = [None] * total
+        return list(none), metrics, list(none), list(none), list(none), list(none), [[] for _ in range(total)], list(none)

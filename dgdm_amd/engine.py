@@ -297,6 +297,27 @@ class Guidance:
             check(lib().dgdm_dyn3d_guidance_grad(self._h, dptr(x), int(timestep), arr, rc_ptr, starts.ctypes.data, nc, dptr(out), stream_ptr()))
         return out
 
+    def score(self, x: torch.Tensor, object_of_chain: Sequence[int], threshold_std: Sequence[float], timestep: int = 0,
+              starts: Optional[np.ndarray] = None, want_logits: bool = False):
+        """Forward-only scoring of x (n_chains, B, L) on the cond_fn grid (generator/diffusion.py:473-504, forward half; classes of
+        :506-532): (counts (n, B, 3, 3, 3) int32 - the joint histogram of the classes of (d0, d1, d2) over the finger's G P^2 cells -,
+        sums (n, B, 4) float32 = sum d0, sum |d0|, sum d1, sum d2[, logits (n, R, 3), row = cell * B + finger]).  threshold_std:
+        threshold / std, the model's normalised units.  3-D: starts as grad() takes them.  'bf16' handles raise DgdmError."""
+        x = _f32(x)
+        nc, B = x.shape[0], self.cfg.batch
+        oc = (C.c_int32 * nc)(*[int(o) for o in object_of_chain])
+        thr = (C.c_float * 3)(*[float(v) for v in threshold_std])
+        counts = torch.empty((nc, B, 3, 3, 3), dtype=torch.int32, device=x.device)
+        sums = torch.empty((nc, B, 4), dtype=torch.float32, device=x.device)
+        logits = torch.empty((nc, self.rows, 3), dtype=torch.float32, device=x.device) if want_logits else None
+        sp = None
+        if self.dyn.kind == 3:
+            assert starts is not None and starts.dtype == np.int64 and starts.size == nc * self.starts_per_call
+            starts = np.ascontiguousarray(starts)
+            sp = starts.ctypes.data
+        check(lib().dgdm_guidance_score(self._h, dptr(x), int(timestep), oc, sp, thr, nc, dptr(logits), dptr(counts), dptr(sums), stream_ptr()))
+        return (counts, sums, logits) if want_logits else (counts, sums)
+
     def sweep(self, x: torch.Tensor, object_of_chain: Sequence[int], starts: Optional[np.ndarray] = None) -> torch.Tensor:
         """Orientation sweep of get_convergence_centers (:506-531): logits (n_chains, B*G, 3), row = g*B + b."""
         x = _f32(x)

@@ -17,6 +17,7 @@ is a callable the user hands to ``Diffusion(simulator=...)`` with the reference'
         -> (gripper_imgs, metrics, profiles, profiles_x, profiles_y, finals, videos, save_gripper_dirs)
 
 Without one the plots are still written and the tables are skipped (noted in ``tables/SKIPPED.txt``).
+``dynamics/predicted.py`` has a stand-in that asks the dynamics model instead (plot slots None, scores marked ``'predicted': True``).
 """
 from __future__ import annotations
 
@@ -121,13 +122,18 @@ def profile_family(opt_obj: str) -> str:
     raise ValueError('opt obj not supported')
 
 
+def _flag(objective: Dict[str, Any], metrics: Sequence[Dict[str, Any]]) -> Dict[str, Any]:
+    """Scores made from metrics that say they are predictions (dynamics/predicted.py) say so too; a simulator's are left as they are."""
+    return dict(objective, predicted=True) if all(m.get('predicted', False) for m in metrics) else objective
+
+
 def unguided_table(model, log: TableLog, sim_out, imgs: Sequence[str], num_objects: int, num_grippers: int, opt_obj: str,
                    ori_range: Sequence[float], fingers_3d: bool) -> Dict[str, Any]:
     """The "val/unguided_sample/<opt_obj>_orirange=..." table (:304-336) from one simulator roll-out of the unguided samples."""
     gripper_imgs, metrics, profiles, profiles_x, profiles_y, finals, videos, _ = sim_out
     imgs_all = list(gripper_imgs) if fingers_3d else [imgs[idx] for _ in range(num_objects) for idx in range(len(imgs))]
     lo, hi = int((ori_range[0] + 1) * 180), int((ori_range[1] + 1) * 180)
-    sliced = [{k: m[k][lo:hi] for k in m.keys()} for m in metrics]                                          # :304
+    sliced = [{k: m[k][lo:hi] if np.ndim(m[k]) else m[k] for k in m.keys()} for m in metrics]                                          # :304
     objs = [metric2objective(m, opt_obj) for m in sliced]
     keys = list(objs[0].keys())
     average = {k: float(np.mean([o[k] for o in objs])) for k in keys}
@@ -138,8 +144,8 @@ def unguided_table(model, log: TableLog, sim_out, imgs: Sequence[str], num_objec
     best_avg = int(model.get_average_best_ids(per_gripper, opt_obj=opt_obj))
     rows = [[-1, -1, None, average, None, None, None, None], [-1, -1, None, average_best, None, None, None, None],
             [-1, best_avg, imgs[best_avg] if best_avg < len(imgs) else None, per_gripper[best_avg], None, None, None, None]]
-    rows += [[i // num_grippers, i % num_grippers, g, o, p, px, py, fi]
-             for i, (g, o, p, px, py, fi) in enumerate(zip(imgs_all, objs, profiles, profiles_x, profiles_y, finals))]
+    rows += [[i // num_grippers, i % num_grippers, g, _flag(o, [m]), p, px, py, fi]
+             for i, (g, o, m, p, px, py, fi) in enumerate(zip(imgs_all, objs, metrics, profiles, profiles_x, profiles_y, finals))]
     log.log_table("val/unguided_sample/%s_orirange=%.3f_%.3f" % (opt_obj, ori_range[0], ori_range[1]),
                   ["object_idx", "gripper_idx", "gripper", "objective", "profile", "profile_x", "profile_y", "final"], rows)
     return {"average": average, "average_best": average_best, "best_average_gripper": best_avg}
@@ -157,7 +163,7 @@ def guided_table(model, log: TableLog, per_object_sim: Sequence[Any], opt_obj: s
         prof = {'profiles': profiles, 'profiles_x': profiles_x, 'profiles_y': profiles_y}[fam]
         best = model.get_best_ids_all_metrics(objs, opt_obj=opt_obj)
         pick = lambda seq: {k: seq[best[k]] for k in best}                                                   # noqa: E731
-        all_obj.append(pick(objs)); all_imgs.append(pick(gripper_imgs)); all_prof.append(pick(prof))
+        all_obj.append(pick([_flag(o, [m]) for o, m in zip(objs, metrics)])); all_imgs.append(pick(gripper_imgs)); all_prof.append(pick(prof))
         all_fin.append(pick(finals)); all_vid.append(pick(videos)); all_dirs.append(pick(dirs))
     if not all_obj:
         return None
@@ -180,7 +186,7 @@ def multi_object_table(model, log: TableLog, per_gripper_sim: Sequence[Any], num
         if len(metrics) != num_objects:
             continue
         objs = [metric2objective(m, opt_obj) for m in metrics]
-        all_obj.append({k: float(np.mean([o[k] for o in objs])) for k in objs[0].keys()})
+        all_obj.append(_flag({k: float(np.mean([o[k] for o in objs])) for k in objs[0].keys()}, metrics))
         all_dirs.append(dirs[0]); all_imgs.append(gripper_imgs[0]); all_vid.append(sum((list(v) for v in videos), []))
     if not all_obj:
         return None

@@ -208,6 +208,19 @@ int dgdm_dyn3d_guidance_grad(DgdmGuidance *g, const float *x_dev, int timestep, 
                              const float *rowcoef_dev, const int64_t *starts_host, int n_chains, float *grad_dev,
                              void *stream);
 
+/* Forward-only scoring on the cond_fn grid: Diffusion.cond_fn's forward half (generator/diffusion.py:473-504: the classifier on every
+ * (finger, orientation, position) row at one timestep) and, per (chain, finger), the tally of the classes :506-532 assigns
+ * (2 if l > thr[k], 0 if l < -thr[k], else 1; thr in the model's normalised units, threshold / std).
+ *   object_of_chain [n_chains] host; starts_host (3-D) as dgdm_dyn3d_guidance_grad takes them, NULL in 2-D
+ *   logits_dev  [n_chains][R][3], row r = cell * B + finger as in cond_fn; NULL: kept in the handle's scratch
+ *   counts_dev  [n_chains][B][27] joint histogram, bin = (class of d0 * 3 + class of d1) * 3 + class of d2; each sums to G * P^2
+ *   sums_dev    [n_chains][B][4]  sum d0, sum |d0|, sum d1, sum d2 over the finger's cells
+ * Contraction dtypes f32 / f32_f16x3 (forward-only form of the f16x3 trunk) and f32_mfma; bf16: DGDM_EINVAL.  Bit-identical run to run;
+ * leaves what dgdm_dyn{2,3}d_guidance_grad computes untouched.                                                                      */
+int dgdm_guidance_score(DgdmGuidance *g, const float *x_dev, int timestep, const int32_t *object_of_chain,
+                        const int64_t *starts_host, const float thr[3], int n_chains, float *logits_dev, int32_t *counts_dev,
+                        float *sums_dev, void *stream);
+
 /* The whole guided denoise loop in one call: Diffusion.guided_sample's loop body (generator/diffusion.py:570-576) for n_chains chains, or
  * guided_sample_multi_object's (:637-647) for n_chains chains that each average n_grad gradients - n_steps x [eps-net; cond_fn; guidance
  * combine; scheduler step] without returning to the host language in between.
