@@ -132,6 +132,14 @@ PROTOTYPES = {
     "dgdm_mesh_destroy": (None, [_P]),
     "dgdm_mesh_sample_workspace_bytes": (C.c_int64, [_P, C.c_int]),
     "dgdm_mesh_sample_points": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_uint64, _P, C.c_int64, _P, _P, C.c_int64, _P]),
+    "dgdm_finger_mesh_counts": (C.c_int, [C.c_int, C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "dgdm_finger_mesh_faces": (C.c_int, [C.c_int, C.c_int, _P]),
+    "dgdm_finger_mesh_vertices_2d": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_float, C.c_float, _P, _P]),
+    "dgdm_finger_mesh_vertices_3d": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_float, _P, _P]),
+    "dgdm_finger_mesh_stats": (C.c_int, [_P, _P, C.c_int64, C.c_int, C.c_int, C.c_double, _P, _P]),
+    "dgdm_finger_pieces_2d": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P, _P, _P]),
+    "dgdm_finger_pieces_3d": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P]),
+    "dgdm_mesh_write_obj": (C.c_int, [C.c_char_p, _P, C.c_int64, _P, C.c_int64]),
     "dgdm_icon_workspace_bytes": (C.c_int64, [C.c_int]),
     "dgdm_icon_trace": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_int64, _P, _P]),
     "dgdm_icon_fetch_contours": (C.c_int, [_P, C.c_int64, C.c_int, _P, _P, _P, C.c_int64, _P]),

@@ -14,6 +14,7 @@
 // step and the geometry.  geomdl is not in this image: the surface follows the published Cox-de Boor recursion and geomdl's
 // documented knot-vector generator, and is checked against scipy.interpolate.BSpline (tests/test_decode.py).
 #include "common.h"
+#include "decode.h"
 #include <cmath>
 #include <map>
 #include <memory>
@@ -114,16 +115,12 @@ std::vector<double> bspline_basis(int degree, int n, const std::vector<double> &
     return N;
 }
 
-struct DecodeTable {
-    DevBuf mat;          // [npts][K] float: weights of the K control values
-    DevBuf fixed;        // [npts][F] float: the coordinates that do not depend on the sample (2-D: x; 3-D: x, z)
-    int npts = 0, K = 0;
-};
-
 std::mutex g_mu;
 std::map<std::pair<int, int>, std::unique_ptr<DecodeTable>> g_tables;     // (kind * 65536 + K, npts) -> table
 
-int get_table(int kind, int K, int n, DecodeTable **out) {
+}  // namespace
+
+int decode_table(int kind, int K, int n, DecodeTable **out) {
     std::lock_guard<std::mutex> lk(g_mu);
     auto key = std::make_pair(kind * 65536 + K, n);
     auto it = g_tables.find(key);
@@ -171,6 +168,8 @@ int get_table(int kind, int K, int n, DecodeTable **out) {
     return DGDM_OK;
 }
 
+namespace {
+
 // out[b][finger][p][:]: 2-D (x_p, y), 3-D (x_p, y, z_p) with y = sum_k mat[p][k] (scale * s[b][finger*K + k] + offset)
 template <int DIM>
 __global__ void decode_kernel(const float *__restrict__ samples, int B, int K, int npts, const float *__restrict__ mat,
@@ -179,10 +178,7 @@ __global__ void decode_kernel(const float *__restrict__ samples, int B, int K, i
     if (e >= (int64_t)B * 2 * npts) return;
     const int p = (int)(e % npts);
     const int64_t bf = e / npts;                       // b * 2 + finger
-    const float *s = samples + bf * K;
-    const float *m = mat + (size_t)p * K;
-    float y = 0.f;
-    for (int k = 0; k < K; ++k) y = fmaf(m[k], fmaf(scale, s[k], offset), y);
+    const float y = decode_y(samples + bf * K, mat + (size_t)p * K, K, scale, offset);
     float *o = out + e * DIM;
     if (DIM == 2) {
         o[0] = fixed[p]; o[1] = y;
@@ -203,7 +199,7 @@ extern "C" int dgdm_finger_decode_2d(const float *samples_dev, int batch, int nu
     if (batch == 0) return DGDM_OK;
     DecodeTable *t = nullptr;
     int rc;
-    if ((rc = get_table(2, num_ctrl / 2, num_points, &t))) return rc;
+    if ((rc = decode_table(2, num_ctrl / 2, num_points, &t))) return rc;
     const int64_t n = (int64_t)batch * 2 * t->npts;
     hipLaunchKernelGGL(decode_kernel<2>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, samples_dev, batch, t->K, t->npts,
                        t->mat.as<float>(), t->fixed.as<float>(), scale, offset, curve_dev);
@@ -220,7 +216,7 @@ extern "C" int dgdm_finger_decode_3d(const float *samples_dev, int batch, int nu
     if (batch == 0) return DGDM_OK;
     DecodeTable *t = nullptr;
     int rc;
-    if ((rc = get_table(3, 21, sample_size, &t))) return rc;
+    if ((rc = decode_table(3, 21, sample_size, &t))) return rc;
     const int64_t n = (int64_t)batch * 2 * t->npts;
     hipLaunchKernelGGL(decode_kernel<3>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, samples_dev, batch, t->K, t->npts,
                        t->mat.as<float>(), t->fixed.as<float>(), scale, offset, surface_dev);

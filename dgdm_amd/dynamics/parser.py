@@ -40,6 +40,7 @@ _FLAGS = [
     ("fingers_3d", "flag", None, "3-D fingers / PointNet++ dynamics model"),
     ("render_video", "flag", None, "simulator videos (external)"),
     ("predicted_sim", "flag", None, "fill the objective tables with the dynamics model's predictions (dynamics/predicted.py)"),
+    ("save_meshes", "flag", None, "also export every emitted gripper as OBJ meshes, collision pieces and gripper_<idx>.xml (assets/finger_mesh.py)"),
     ("seed", int, 0, "seed of the start noise"),
 ]
 

@@ -448,6 +448,98 @@ def _check_value(rc: int) -> None:
     check(rc)
 
 
+# ---------------------------------------------------------------------------------------------------------------- finger meshes
+MESH_2D, MESH_3D, PIECE_2D, PIECE_3D = 2, 3, 12, 13       # the kinds of include/dgdm_hip.h "finger meshes"
+_faces_dev: Dict[Tuple[int, int, str], torch.Tensor] = {}
+
+
+def finger_mesh_faces(kind: int, n: int = 0) -> np.ndarray:
+    """The triangle table (T, 3) int32, 0-based and outward-oriented, of one finger mesh: kind 2 the extruded 2-D finger of n curve
+    points, kind 3 the 3-D finger of n x n surface samples, kinds 12 / 13 one collision piece of either (n unused).  Host code."""
+    nv, nt = C.c_int64(), C.c_int64()
+    _check_value(lib().dgdm_finger_mesh_counts(int(kind), int(n), C.byref(nv), C.byref(nt)))
+    tris = np.empty((nt.value, 3), dtype=np.int32)
+    _check_value(lib().dgdm_finger_mesh_faces(int(kind), int(n), tris.ctypes.data))
+    return tris
+
+
+def _faces_on(kind: int, n: int, device: torch.device) -> torch.Tensor:
+    key = (int(kind), int(n), str(device))
+    if key not in _faces_dev:
+        _faces_dev[key] = torch.from_numpy(finger_mesh_faces(kind, n)).to(device)
+    return _faces_dev[key]
+
+
+def finger_mesh_2d(samples: torch.Tensor, num_points: int = 200, width: float = 0.03, height: float = 0.02, scale: float = 0.03,
+                   offset: float = -0.015) -> torch.Tensor:
+    """(B, L, 1) or (B, L) control values -> (B, 2 fingers, 4 num_points, 3) mesh vertices in metres: the four rings of
+    generate_finger_shape (assets/finger_sampler.py:13-21) over finger_decode_2d's curve; faces are finger_mesh_faces(2, num_points).
+    The defaults are what prepare_finger passes (dynamics/sim_test_mj.py:90-97)."""
+    s = _f32(samples).reshape(samples.shape[0], -1)
+    out = torch.empty((s.shape[0], 2, 4 * int(num_points), 3), dtype=torch.float32, device=s.device)
+    _check_value(lib().dgdm_finger_mesh_vertices_2d(dptr(s), s.shape[0], s.shape[1], int(num_points), float(scale), float(offset), float(width),
+                                                    float(height), dptr(out), stream_ptr()))
+    return out
+
+
+def finger_mesh_3d(samples: torch.Tensor, sample_size: int = 25, width: float = 0.1, scale: float = 0.05, offset: float = -0.05) -> torch.Tensor:
+    """(B, 42, 1) or (B, 42) control values -> (B, 2 fingers, 2 sample_size^2, 3) mesh vertices in metres: finger_decode_3d's sheet and
+    the sheet + width in y (assets/finger_3d.py:41-44); faces are finger_mesh_faces(3, sample_size).  The defaults are what
+    prepare_gripper passes (dynamics/sim_test_mj_3d.py:80-85)."""
+    s = _f32(samples).reshape(samples.shape[0], -1)
+    out = torch.empty((s.shape[0], 2, 2 * int(sample_size) ** 2, 3), dtype=torch.float32, device=s.device)
+    _check_value(lib().dgdm_finger_mesh_vertices_3d(dptr(s), s.shape[0], s.shape[1], int(sample_size), float(scale), float(offset), float(width),
+                                                    dptr(out), stream_ptr()))
+    return out
+
+
+def finger_mesh_stats(verts: torch.Tensor, tris, area_eps: float = 0.0) -> torch.Tensor:
+    """verts (..., V, 3) float32 on the device, tris (T, 3) int32 shared by every mesh -> (..., 4) float64: signed volume, surface area,
+    smallest triangle area, number of triangles with area < area_eps."""
+    v = _f32(verts)
+    t = torch.as_tensor(tris).to(device=v.device, dtype=torch.int32).contiguous()
+    lead = v.shape[:-2]
+    out = torch.empty((*lead, 4), dtype=torch.float64, device=v.device)
+    _check_value(lib().dgdm_finger_mesh_stats(dptr(v), dptr(t), int(np.prod(lead, dtype=np.int64)), v.shape[-2], t.shape[0], float(area_eps),
+                                              dptr(out), stream_ptr()))
+    return out
+
+
+def finger_pieces_2d(verts: torch.Tensor, pieces: int = 16) -> Tuple[torch.Tensor, torch.Tensor]:
+    """finger_mesh_2d's vertices (B, 2, 4 n, 3) -> (collision pieces (B, 2, pieces, 8, 3) float32, chord_err (B, 2) float64 metres).
+    Piece k is the sheared box between knots k and k + 1 of the curve, faces finger_mesh_faces(12); the default is the reference's
+    V-HACD hull cap (dynamics/sim_test_mj.py:69-70)."""
+    v = _f32(verts)
+    B, n = v.shape[0], v.shape[2] // 4
+    out = torch.empty((B, 2, int(pieces), 8, 3), dtype=torch.float32, device=v.device)
+    err = torch.empty((B, 2), dtype=torch.float64, device=v.device)
+    _check_value(lib().dgdm_finger_pieces_2d(dptr(v), B, n, int(pieces), dptr(out), dptr(err), stream_ptr()))
+    return out, err
+
+
+def finger_pieces_3d(verts: torch.Tensor, pu: int = 8, pv: int = 2) -> Tuple[torch.Tensor, torch.Tensor]:
+    """finger_mesh_3d's vertices (B, 2, 2 n^2, 3) -> (collision pieces (B, 2, 2 pu pv, 6, 3) float32, chord_err (B, 2) float64 metres).
+    Each cell of the (pu + 1) x (pv + 1) knot grid gives two triangular prisms, faces finger_mesh_faces(13); the default 2 * 8 * 2 = 32
+    is the reference's V-HACD hull cap (dynamics/sim_test_mj_3d.py:59-60)."""
+    v = _f32(verts)
+    B = v.shape[0]
+    n = int(round((v.shape[2] // 2) ** 0.5))
+    if 2 * n * n != v.shape[2]:
+        raise ValueError(f"finger_pieces_3d: {v.shape[2]} vertices per finger is not 2 n^2")
+    out = torch.empty((B, 2, 2 * int(pu) * int(pv), 6, 3), dtype=torch.float32, device=v.device)
+    err = torch.empty((B, 2), dtype=torch.float64, device=v.device)
+    _check_value(lib().dgdm_finger_pieces_3d(dptr(v), B, n, int(pu), int(pv), dptr(out), dptr(err), stream_ptr()))
+    return out, err
+
+
+def write_obj(path: str, verts, tris) -> None:
+    """Vertices (V, 3), written as float32 with 9 significant digits, and triangles (T, 3), 0-based, as an OBJ file that read_obj returns
+    unchanged.  Host code; releases the GIL while it formats and writes."""
+    v = np.ascontiguousarray(verts, dtype=np.float32).reshape(-1, 3)
+    t = np.ascontiguousarray(tris, dtype=np.int32).reshape(-1, 3)
+    _check_value(lib().dgdm_mesh_write_obj(os.fsencode(path), v.ctypes.data, len(v), t.ctypes.data, len(t)))
+
+
 def resample_contours(points, offsets, num_points: int, rescale: bool = False) -> torch.Tensor:
     """resample_contour (assets/icon_process.py) of a batch of contours, (M, num_points, 2) on the current device: int32, or float64
     c / 128 * 0.1 - 0.05 when rescale.  points (total, 2) integer pixel pairs, host or device; offsets M + 1 int64 starting at 0,

@@ -123,6 +123,10 @@ class Diffusion(nn.Module):
         self.save_dir: Optional[str] = None
         self.last_samples: Dict[str, np.ndarray] = {}
         self.last_geometry: Dict[str, Any] = {}            # decoded finger curves / surfaces of the same batches (engine.finger_decode_*)
+        # not a reference argument: with save_meshes (--save_meshes) every emitted batch is also exported as gripper directories
+        # (assets/finger_mesh.py save_grippers), last_gripper_dirs[tag][i] the directories of names[i] - the reference's save_gripper_dirs
+        self.save_meshes = False
+        self.last_gripper_dirs: Dict[str, List[List[str]]] = {}
         if class_cond:
             self.classifier_model = classifier_model
             self.grid_size, self.num_pos = grid_size, num_pos
@@ -459,6 +463,9 @@ class Diffusion(nn.Module):
                 np.save(os.path.join(d, f"{nm}.npy"), arr[i])
                 if geo is not None:
                     np.save(os.path.join(d, f"{nm}_geometry.npy"), geo[i])
+            if self.save_meshes and geo is not None:
+                from ..assets.finger_mesh import save_grippers
+                self.last_gripper_dirs[tag] = [save_grippers(samples[i].detach(), os.path.join(d, nm), mode=self.mode) for i, nm in enumerate(names)]
 
     # ------------------------------------------------------------------ a3 + harness
     def validation_step(self, tensor_data, batch_idx):

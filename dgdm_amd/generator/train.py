@@ -246,6 +246,7 @@ def train(args):
                       class_cond=args.classifier_guidance, classifier_model=classifier, grid_size=args.grid_size, num_pos=args.num_pos,
                       object_vertices=objects, object_ids=object_ids, num_cpus=args.num_cpus, pts_x_dim=args.ctrlpts_x_dim,
                       pts_z_dim=args.ctrlpts_z_dim, sub_batch_size=args.sub_bs, render_video=args.render_video, seed=args.seed)
+    model.save_meshes = bool(getattr(args, "save_meshes", False))
     if getattr(args, "predicted_sim", False) and args.classifier_guidance and model.simulator is None:
         from ..dynamics.predicted import PredictedSimulator      # opt-in: the tables scored by the dynamics model instead of roll-outs
         model.simulator = PredictedSimulator(model)

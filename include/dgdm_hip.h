@@ -318,6 +318,70 @@ int     dgdm_mesh_sample_points(const double *verts_dev, const int32_t *tris_dev
                                 const int64_t *tri_offsets_host, int num_meshes, uint64_t seed, const uint64_t *keys_host,
                                 int64_t num_points, double *out_dev, void *workspace_dev, int64_t workspace_bytes, void *stream);
 
+/* ------------------------------------------------------------------ finger meshes
+ * The step after the decode: the reference builds a trimesh per finger on the host (assets/finger_sampler.py:7-36 generate_finger_shape,
+ * assets/finger_3d.py:38-57 generate_3d_finger_mesh), exports fingerl.obj / fingerr.obj (save_gripper :52-64, save_3d_gripper :69-80) and runs
+ * V-HACD on each file for the collision pieces (dynamics/sim_test_mj.py:57-103, sim_test_mj_3d.py:47-92).  Here the vertices, the per-mesh
+ * statistics and the collision pieces are computed on the device for a whole batch; the topology is constant per (kind, n).
+ *
+ * Orientation rule, every table: triangles are 0-based and counter-clockwise seen from outside, so (v1 - v0) x (v2 - v0) points out of
+ * the solid and the signed volume sum_t v0 . (v1 x v2) / 6 is positive.  A quad (a, b, c, d) is split as (a, b, c), (a, c, d).
+ *
+ * kind 2 (DGDM_FINGER_MESH_2D), n = num_points >= 2: 4 n vertices in four rings of n - the curve at z = 0, the curve + width in y at
+ *   z = 0, the curve + width at z = height, the curve at z = height - and 2 (4 (n - 1) + 2) triangles from the reference's quads in its
+ *   order (assets/finger_sampler.py:24-31), with i = 0 .. n - 2 inside a family:
+ *     left (i, i+1, i+3n+1, i+3n), right (i+2n, i+2n+1, i+n+1, i+n), front (3n, 2n, n, 0), back (n-1, 2n-1, 3n-1, 4n-1),
+ *     top (i+2n, i+3n, i+3n+1, i+2n+1), bottom (i+n, i+n+1, i+1, i).
+ * kind 3 (DGDM_FINGER_MESH_3D), n = sample_size >= 2, N = n^2: 2 N vertices - the decoded sheet in u-major order (point (a, b) at a n + b),
+ *   then the sheet + width in y - and 4 (n - 1)^2 + 8 (n - 1) triangles:
+ *     sheet, cells (a, b) in a-major order, p00 = a n + b, p01 = p00 + 1, p10 = p00 + n, p11 = p10 + 1: (p00, p10, p11), (p00, p11, p01),
+ *       normal toward -y;
+ *     shifted sheet, same cell order: (N + p00, N + p11, N + p10), (N + p00, N + p01, N + p11);
+ *     walls along the boundary loop c_0, c_1, ... (b = 0 .. n-2 at a = 0; a = 0 .. n-2 at b = n-1; b = n-1 .. 1 at a = n-1; a = n-1 .. 1 at
+ *       b = 0), per edge (c, d = the next loop vertex): (c, d, d + N), (c, d + N, c + N).
+ *   geomdl's own tessellation order is not reproduced (geomdl is not a dependency): this triangulation is the project's.
+ * kind 12 / 13 (DGDM_FINGER_PIECE_2D / _3D), n not used: one collision piece, see dgdm_finger_pieces_2d / _3d.                          */
+enum { DGDM_FINGER_MESH_2D = 2, DGDM_FINGER_MESH_3D = 3, DGDM_FINGER_PIECE_2D = 12, DGDM_FINGER_PIECE_3D = 13 };
+/* Vertex and triangle counts of one mesh of this kind and resolution. */
+int dgdm_finger_mesh_counts(int kind, int n, int64_t *verts, int64_t *tris);
+/* tris_host [tris][3] int32.  Host code, built once per (kind, n) and kept. */
+int dgdm_finger_mesh_faces(int kind, int n, int32_t *tris_host);
+/* samples_dev as dgdm_finger_decode_2d / _3d take it -> verts_dev [batch][2 fingers][V][3] float32 in the vertex order above.  The base
+ * ring / sheet is bit for bit what the decode writes (same tables, same fmaf order); y + width and z = 0 + height are single float32
+ * additions.  Arguments are checked as the decode checks them, plus num_points / sample_size >= 2 and width, height > 0.              */
+int dgdm_finger_mesh_vertices_2d(const float *samples_dev, int batch, int num_ctrl, int num_points, float scale, float offset,
+                                 float width, float height, float *verts_dev, void *stream);
+int dgdm_finger_mesh_vertices_3d(const float *samples_dev, int batch, int num_ctrl, int sample_size, float scale, float offset,
+                                 float width, float *verts_dev, void *stream);
+/* Per-mesh statistics of `meshes` meshes that share one triangle table: verts_dev [meshes][V][3] float32, tris_dev [T][3] int32 ->
+ * stats_dev [meshes][4] float64 = signed volume (divergence theorem, sum_t v0 . (v1 x v2) / 6), surface area, smallest triangle area,
+ * number of triangles whose area is below area_eps.  Everything is accumulated in float64 by one wave per mesh in a fixed order: the
+ * result depends on the mesh alone.  A triangle index outside [0, V) makes all four values of that mesh NaN.
+ * What trimesh's .volume / .area report, and what the exporter uses to refuse a degenerate finger.                                   */
+int dgdm_finger_mesh_stats(const float *verts_dev, const int32_t *tris_dev, int64_t meshes, int V, int T, double area_eps,
+                           double *stats_dev, void *stream);
+/* Collision pieces, in place of the reference's external V-HACD call (TestVHACD -h 16 / -h 32: at most 16 hulls in 2-D, 32 in 3-D):
+ * an exact convex decomposition of the same finger at a coarser resolution.  Knot j of p over n samples is the sample index
+ * floor(j (n - 1) / p + 1/2), j = 0 .. p.
+ * 2-D: verts_dev [batch][2][4 num_points][3] from dgdm_finger_mesh_vertices_2d -> out_dev [batch][2][pieces][8][3]: piece k is the sheared
+ *   box between knots k and k + 1, its vertices rings 0..3 at knot k then rings 0..3 at knot k + 1, its 12 triangles kind 12.
+ * 3-D: verts_dev [batch][2][2 sample_size^2][3] from dgdm_finger_mesh_vertices_3d -> out_dev [batch][2][2 pu pv][6][3]: knot cell (j, l) of
+ *   the (pu + 1) x (pv + 1) knot grid, corners q00, q10 (next u knot), q11, q01, gives pieces 2 (j pv + l) and + 1: the triangles
+ *   (q00, q10, q11) and (q00, q11, q01) swept by width in y, vertices the three sheet corners then the same corners of the shifted sheet,
+ *   8 triangles kind 13.
+ * Both kinds of piece are convex by construction.  pieces (pu, pv) must be 1 .. the number of segments (cells per direction) and a
+ * finger has at most 1000 pieces (the files are numbered %03d): otherwise DGDM_EINVAL.
+ * chord_err_dev [batch][2] float64: the largest |y| distance, in metres, between the full-resolution base ring / sheet vertices and the
+ * coarse piece surface under them (linear between knots in 2-D; the two triangles of the knot cell in 3-D), exactly 0 when every
+ * sample is a knot.  Reported, never thresholded.                                                                                   */
+int dgdm_finger_pieces_2d(const float *verts_dev, int batch, int num_points, int pieces, float *out_dev, double *chord_err_dev, void *stream);
+int dgdm_finger_pieces_3d(const float *verts_dev, int batch, int sample_size, int pu, int pv, float *out_dev, double *chord_err_dev,
+                          void *stream);
+/* OBJ writer (what trimesh's mesh.export(path) does for the reference): verts_host [V][3] float32 as `v` lines with %.9g, which names
+ * every binary32 value uniquely, tris_host [T][3] int32 0-based as 1-based `f` lines.  dgdm_mesh_read_obj on the file returns the same
+ * float32 values and triangles.  Host code, thread-safe.                                                                             */
+int dgdm_mesh_write_obj(const char *path, const float *verts_host, int64_t V, const int32_t *tris_host, int64_t T);
+
 /* ------------------------------------------------------------------ object contours from icon images
  * extract_contours (assets/icon_process.py: cv2.resize to 128 x 128, BGR2GRAY, threshold 240 inverted, findContours RETR_EXTERNAL +
  * CHAIN_APPROX_SIMPLE, the longest contour by arcLength, resample_contour, int32, rescale), which the reference applies to the
