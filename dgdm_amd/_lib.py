@@ -145,6 +145,8 @@ PROTOTYPES = {
     "dgdm_icon_fetch_contours": (C.c_int, [_P, C.c_int64, C.c_int, _P, _P, _P, C.c_int64, _P]),
     "dgdm_contour_resample_workspace_bytes": (C.c_int64, [_P, C.c_int]),
     "dgdm_contour_resample": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _P, _P, C.c_int64, _P]),
+    "dgdm_polygon_triangulate": (C.c_int, [_P, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P]),
+    "dgdm_polygon_convex_pieces": (C.c_int, [_P, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
 }
 
 _lib = None

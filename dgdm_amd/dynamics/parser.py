@@ -41,6 +41,8 @@ _FLAGS = [
     ("render_video", "flag", None, "simulator videos (external)"),
     ("predicted_sim", "flag", None, "fill the objective tables with the dynamics model's predictions (dynamics/predicted.py)"),
     ("save_meshes", "flag", None, "also export every emitted gripper as OBJ meshes, collision pieces and gripper_<idx>.xml (assets/finger_mesh.py)"),
+    ("save_objects", "flag", None, "2-D: also export the run's icon objects as meshes, convex pieces and object_<idx>.xml into every model root "
+                                   "(assets/icon_process.py save_icon_objects)"),
     ("seed", int, 0, "seed of the start noise"),
 ]
 

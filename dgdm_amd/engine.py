@@ -606,6 +606,68 @@ def icon_contours(images, num_points: int = 100, rescale: bool = False) -> torch
     return resample_contours(points, off, num_points, rescale)
 
 
+# ---------------------------------------------------------------------------------------------------------------- integer rings
+POLYGON_MAX_POINTS, POLYGON_MAX_COORD = 256, 32767
+
+
+def _ring_points(points, fn: str) -> torch.Tensor:
+    p = torch.as_tensor(points)
+    if p.dtype.is_floating_point or p.dtype.is_complex or p.dtype == torch.bool:
+        raise ValueError(f"{fn}: integer points expected (extract_contours_batch(..., rescale=False)), got {p.dtype}")
+    if p.dim() != 3 or p.shape[2] != 2 or p.shape[0] < 1:
+        raise ValueError(f"{fn}: points of shape (batch, n, 2) expected, got {tuple(p.shape)}")
+    if p.dtype != torch.int32 and p.numel() and (int(p.min()) < 0 or int(p.max()) > POLYGON_MAX_COORD):
+        raise ValueError(f"{fn}: a coordinate outside [0, {POLYGON_MAX_COORD}]")            # before the cast to int32 can wrap it
+    return p.to(device=torch.device("cuda", torch.cuda.current_device()), dtype=torch.int32).contiguous()
+
+
+def polygon_decompose(points, pieces: bool = True) -> Dict[str, torch.Tensor]:
+    """Steps 1-4 of the ring contract of include/dgdm_hip.h ("integer rings") for a batch of closed rings in one launch.
+    points (batch, n, 2) integer pixel coordinates in [0, 32767], 3 <= n <= 256, host or device.  Device tensors: status (batch,) int32,
+    count (batch,) int32, ring (batch, n) int32, area2 (batch,) int64, triangles (batch, n - 2, 3) int32 and, with pieces, piece_count
+    (batch,), piece_offsets (batch, n - 1), piece_index (batch, 3 (n - 2)) int32; unused entries are -1.  Synchronises the stream once."""
+    p = _ring_points(points, "polygon_decompose")
+    B, n = int(p.shape[0]), int(p.shape[1])
+    new = lambda *shape, dtype=torch.int32: torch.empty(shape, dtype=dtype, device=p.device)      # noqa: E731
+    out = {"status": new(B), "count": new(B), "ring": new(B, n), "area2": new(B, dtype=torch.int64), "triangles": new(B, max(n - 2, 0), 3)}
+    head = [dptr(p), B, n] + [dptr(out[k]) for k in ("status", "count", "ring", "area2", "triangles")]
+    if pieces:
+        out.update(piece_count=new(B), piece_offsets=new(B, max(n - 1, 0)), piece_index=new(B, 3 * max(n - 2, 0)))
+        _check_value(lib().dgdm_polygon_convex_pieces(*head, dptr(out["piece_count"]), dptr(out["piece_offsets"]), dptr(out["piece_index"]),
+                                                      stream_ptr()))
+    else:
+        _check_value(lib().dgdm_polygon_triangulate(*head, stream_ptr()))
+    return out
+
+
+def polygon_triangulate(points) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """(status, count, ring, area2, triangles) of polygon_decompose: the cleaned ring, why it is refused if it is, and its M - 2
+    triangles of original indices in clip order."""
+    o = polygon_decompose(points, pieces=False)
+    return o["status"], o["count"], o["ring"], o["area2"], o["triangles"]
+
+
+def canonical_pieces(piece_count, piece_offsets, piece_index) -> List[List[Tuple[int, ...]]]:
+    """The pieces of polygon_decompose as host tuples in canonical form: each rotated to start at its smallest index, then sorted."""
+    pc, po, pi = (torch.as_tensor(t).cpu().numpy() for t in (piece_count, piece_offsets, piece_index))
+    out = []
+    for b in range(len(pc)):
+        faces = []
+        for q in range(int(pc[b])):
+            f = pi[b, po[b, q]:po[b, q + 1]].tolist()
+            k = f.index(min(f))
+            faces.append(tuple(f[k:] + f[:k]))
+        out.append(sorted(faces))
+    return out
+
+
+def polygon_pieces(points) -> List[List[Tuple[int, ...]]]:
+    """The convex pieces (Hertel-Mehlhorn on polygon_triangulate's triangles) of each ring, canonical: a list per ring (empty for a
+    refused ring) of tuples of original indices, counter-clockwise in the working order."""
+    o = polygon_decompose(points)
+    return canonical_pieces(o["piece_count"], o["piece_offsets"], o["piece_index"])
+
+
 def prof_enable(on: bool) -> None:
     check(lib().dgdm_prof_enable(int(on)))
 

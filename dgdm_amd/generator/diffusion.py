@@ -127,6 +127,9 @@ class Diffusion(nn.Module):
         # (assets/finger_mesh.py save_grippers), last_gripper_dirs[tag][i] the directories of names[i] - the reference's save_gripper_dirs
         self.save_meshes = False
         self.last_gripper_dirs: Dict[str, List[List[str]]] = {}
+        # nor this: object_exporter(model_root, name) (--save_objects, generator/train.py) writes the objects of the run into the model
+        # root of every emitted batch, next to its grippers, so that a scene file over that root finds both halves
+        self.object_exporter = None
         if class_cond:
             self.classifier_model = classifier_model
             self.grid_size, self.num_pos = grid_size, num_pos
@@ -466,6 +469,9 @@ class Diffusion(nn.Module):
             if self.save_meshes and geo is not None:
                 from ..assets.finger_mesh import save_grippers
                 self.last_gripper_dirs[tag] = [save_grippers(samples[i].detach(), os.path.join(d, nm), mode=self.mode) for i, nm in enumerate(names)]
+            if self.object_exporter is not None:
+                for nm in names:
+                    self.object_exporter(os.path.join(d, nm), nm)
 
     # ------------------------------------------------------------------ a3 + harness
     def validation_step(self, tensor_data, batch_idx):

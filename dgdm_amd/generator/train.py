@@ -124,6 +124,24 @@ def _icon_objects(images, nv: int) -> torch.Tensor:
     return object_vertices
 
 
+def _object_exporter(args):
+    """--save_objects: export(model_root, name) for Diffusion.object_exporter, or None (with one line on stderr) when the run's objects are
+    not icons.  A model root named after one object id (the per-object chains) gets that object, any other (allobj, unguided) all eight;
+    an icon whose contour cannot be meshed is named on stderr and left out."""
+    images, why = (None, "3-D objects are scanned meshes, already files") if args.fingers_3d else _icon_images(args.object_dir or "")
+    if images is None:
+        print(f"[dgdm_amd] --save_objects: no Icons-50 file at '{args.object_dir or ''}' ({why}) - nothing to export", file=sys.stderr)
+        return None
+    icons = np.ascontiguousarray(np.asarray(images)[OBJECT_IDS].transpose((0, 2, 3, 1)))
+
+    def export(model_root, name):
+        pick = [i for i, idx in enumerate(OBJECT_IDS) if str(idx) == name] or list(range(len(OBJECT_IDS)))
+        refused = icon_process.save_icon_objects(icons[pick], model_root, [OBJECT_IDS[i] for i in pick], num_points=ICON_POINTS, skip_invalid=True)
+        if refused:
+            print(f"[dgdm_amd] --save_objects: {model_root}: the contours of objects {refused} cannot be meshed - left out", file=sys.stderr)
+    return export
+
+
 def fit(model: Diffusion, pts: np.ndarray, args, bounds, dev) -> Diffusion:
     """``trainer.fit(diffusion_model, train_loader, val_loader)`` (generator/train.py:44-45, 66-67, 147-162) without Lightning: the
     loop its ``LightningTrainer(max_epochs=num_epochs, check_val_every_n_epoch=val_step)`` runs.  Under torchrun every rank takes the
@@ -247,6 +265,8 @@ def train(args):
                       object_vertices=objects, object_ids=object_ids, num_cpus=args.num_cpus, pts_x_dim=args.ctrlpts_x_dim,
                       pts_z_dim=args.ctrlpts_z_dim, sub_batch_size=args.sub_bs, render_video=args.render_video, seed=args.seed)
     model.save_meshes = bool(getattr(args, "save_meshes", False))
+    if getattr(args, "save_objects", False):
+        model.object_exporter = _object_exporter(args)
     if getattr(args, "predicted_sim", False) and args.classifier_guidance and model.simulator is None:
         from ..dynamics.predicted import PredictedSimulator      # opt-in: the tables scored by the dynamics model instead of roll-outs
         model.simulator = PredictedSimulator(model)

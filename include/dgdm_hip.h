@@ -413,6 +413,44 @@ int64_t dgdm_contour_resample_workspace_bytes(const int64_t *offsets_host, int n
 int dgdm_contour_resample(const int32_t *points_dev, const int64_t *offsets_host, int num_contours, int num_out, int rescale,
                           void *out_dev, void *workspace_dev, int64_t workspace_bytes, void *stream);
 
+/* ------------------------------------------------------------------ integer rings: triangulation and convex pieces
+ * The step between an icon's contour and a simulator object: the reference extrudes the contour with `triangle`'s constrained Delaunay
+ * faces as caps (assets/icon_process.py:62-92 generate_icon_mesh / save_icon_mesh) and decomposes the prism with an external V-HACD run
+ * (sim/sim_2d.py:103-111 prepare_icon_object).  Neither is reproduced: this is the project's own contract, exact in integers, computed
+ * by one wave per ring (csrc/polygon.hip).  DESIGN.md §4.5d; tests/polygon_oracle.py is the CPU statement.
+ *
+ * points_dev [batch][n][2] int32, 3 <= n <= 256, every coordinate in [0, 32767] - what dgdm_contour_resample writes without rescale;
+ * anything else is DGDM_EINVAL before a ring is touched (the range is checked on the device: one stream synchronisation).  Every
+ * predicate is a cross or dot product in int64.  A ring's result depends on that ring alone: the same bits alone, in any batch, at any
+ * position.  Per ring:
+ *   1. clean   a point equal to the point kept before it is dropped, then trailing points equal to the first.  count = M points remain,
+ *              ring[k] = the original index of kept point k (-1 from k = M on).  Collinear points are kept.
+ *   2. status  the first that applies: 1  M < 3;  2  the doubled signed area a2 = sum (x_i y_i+1 - x_i+1 y_i) is 0;  3  not simple - two
+ *              non-adjacent closed edges share a point, or two adjacent edges fold back on each other (cross 0, dot < 0);  4  the ear
+ *              rule below found no ear (no simple ring does this; reported instead of looping);  0 otherwise.  area2 carries its sign
+ *              (0 for status 1).  A ring with status != 0 has no triangles and no pieces (-1 / count 0).
+ *   3. triangulate  ear clipping in the working order, the kept points read so that a2 > 0 (backwards when a2 < 0).  A current vertex
+ *              j with neighbours i, l is an ear when cross(p_i, p_j, p_l) > 0 and no other current vertex lies in the closed triangle
+ *              (cross >= 0 on all three sides).  The ear whose tip has the smallest original index is clipped and (i, j, l) emitted, as
+ *              original indices, until three vertices remain; they are emitted with the smallest original index as j.
+ *              triangles [M - 2][3] in clip order (-1 beyond), all counter-clockwise in the working order; their doubled areas are
+ *              positive and add up to |a2| exactly.
+ *   4. convex pieces  Hertel-Mehlhorn on that triangulation: clip t < M - 3 created the diagonal (i, l); the diagonals are visited from
+ *              the last created to the first, and one is removed when at both of its end points the two boundary edges that become
+ *              neighbours turn left or go straight (cross >= 0).  The faces that remain are convex and tile the ring.
+ *              piece_count; piece_offsets [n - 1] (piece q = piece_index[offsets[q] .. offsets[q + 1]), -1 beyond entry piece_count);
+ *              piece_index [3 (n - 2)] original indices, counter-clockwise in the working order (-1 beyond).  Faces come in the order of
+ *              their lowest half-edge (half-edge 3 t + k leaves vertex k of triangle t), each starting there.
+ * dgdm_polygon_triangulate: steps 1-3.  dgdm_polygon_convex_pieces: steps 1-4 in the same launch; its count / ring / area2 / triangles
+ * pointers may each be null.  Outputs: status_dev, count_dev, piece_count_dev [batch] int32; ring_dev [batch][n] int32; area2_dev [batch]
+ * int64; triangles_dev [batch][n - 2][3] int32; piece_offsets_dev [batch][n - 1], piece_index_dev [batch][3 (n - 2)] int32.  All
+ * fixed-stride: no workspace.                                                                                                       */
+int dgdm_polygon_triangulate(const int32_t *points_dev, int batch, int n, int32_t *status_dev, int32_t *count_dev, int32_t *ring_dev,
+                             int64_t *area2_dev, int32_t *triangles_dev, void *stream);
+int dgdm_polygon_convex_pieces(const int32_t *points_dev, int batch, int n, int32_t *status_dev, int32_t *count_dev, int32_t *ring_dev,
+                               int64_t *area2_dev, int32_t *triangles_dev, int32_t *piece_count_dev, int32_t *piece_offsets_dev,
+                               int32_t *piece_index_dev, void *stream);
+
 /* ------------------------------------------------------------------ measurement hooks
  * When enabled, the launches of every stage of the path are bracketed by hipEvents on the stream they are launched on.
  * dgdm_prof_read_stage synchronises those events and returns, for one stage, the number of bracketed regions, their total
