@@ -70,6 +70,10 @@ struct DgdmGuidance {
     DevBuf V, genc, atab, chainbias, timepart, ttmp, ttmp64, partial, objdev, objidx, xobj, xobj16, starts, order, xchains, todo, groupoff;
     DevBuf loopx[2], loopeps, loopgrad, loopxrep, loopts;      // workspace of dgdm_guided_chains_run
     DevBuf scorelogits;                      // dgdm_guidance_score: the logits when the caller does not want them
+    // dgdm_guidance_rollout: the sweep's orientations [G] (built with the handle), and its scratch, grown on demand: the state
+    // [n][B*G][3] doubles, one interaction's logits, the per-row pose operand tiles [ntiles][W1*32] and (3-D) their row maxima [ntiles][32]
+    DevBuf sweep_ori, rollstate, rolllogits, rolltiles, rollpmax;
+    int rolltiles_chains = 0;                // chains the tiles of the last roll-out cover (dgdm_guidance_debug_rollout_table)
     DevBuf xidx, xidxchains, xtabptrs;       // embedding-table path: row index per reference row, per-chain lookup info, per-chain table base pointers
     bool xtab_enabled = true;       // test hook: modes 1-3 read materialised rows (per-step gather kernels) instead of the embedding table
     int xtab_policy = 0;            // 0: build the embedding tables once the objects have served more than XTAB_AFTER cond_fn calls; 1: at set_objects (test hook mode 5)
@@ -182,6 +186,7 @@ extern "C" int dgdm_guidance_create(DgdmGuidance **out, DgdmDynamics *model, con
     }
     std::vector<float> pos0(2 * (size_t)g->G, 0.f);                       // get_convergence_centers: pos = 0 (:511)
     if ((rc = g->build_pose_table(lo, pos0, &g->ptab_sweep, &g->ptab_sweep_t, nullptr))) return rc;
+    if ((rc = g->sweep_ori.upload(lo.data(), lo.size() * sizeof(float)))) return rc;
     const int W1 = model->W1, nc = cfg->max_chains;
     const size_t rows = (size_t)nc * g->B;
     if ((rc = g->V.alloc(rows * 256 * 8)) || (rc = g->genc.alloc(rows * 256 * 8)) || (rc = g->atab.alloc(rows * W1 * 4)) ||
@@ -893,6 +898,87 @@ extern "C" int dgdm_guidance_orientation_sweep(DgdmGuidance *g, const float *x_d
     p.Atab = g->atab.as<float>(); p.Ptab = g->ptab_sweep.as<float>(); p.PtabT = g->ptab_sweep_t.as<float>(); p.logits = logits_dev;
     p.B = g->B; p.C = g->G; p.tiles_per_b = g->sweep_tiles_per_b; p.ntiles = n_chains * g->B * g->sweep_tiles_per_b; p.R = g->Rs; p.xstride = g->Rs;
     return trunk_launch(kind, false, true, p, s);
+}
+
+// ================================================================================================ predicted roll-outs
+// K interactions of the dynamics model with itself from the sweep's poses (include/dgdm_hip.h).  x and t = 0 do not change, so the
+// per-finger table (common_pre) is built once; 3-D: the embeddings of the rows of all K classifier calls are made before the first
+// interaction, as dgdm_guided_chains_run does for its steps (one upload, one gather launch or one index kernel), and call k reads rows
+// [k * Rs, (k + 1) * Rs) of every chain.  Then K x (per-row pose tiles, forward-only f16x3 trunk, state update) on the caller's
+// stream: no copy to the host and no host wait in between.
+extern "C" int dgdm_guidance_rollout(DgdmGuidance *g, const float *x_dev, const int32_t *object_of_chain, const int64_t *starts_host,
+                                     const double scale[3], int n_interactions, int n_chains, double *final_dev, float *first_logits_dev,
+                                     int32_t *left_dev, double *traj_pose_dev, float *traj_logits_dev, void *stream) {
+    DGDM_REQUIRE(g && x_dev && object_of_chain && scale && final_dev && first_logits_dev && left_dev, DGDM_EINVAL, "dgdm_guidance_rollout: null argument");
+    DGDM_REQUIRE(!g->bf16, DGDM_EINVAL, "dgdm_guidance_rollout: the bf16 trunk has no forward-only form (contraction dtypes f32 / f32_f16x3)");
+    DGDM_REQUIRE(!g->f32_mfma, DGDM_EINVAL, "dgdm_guidance_rollout: the float32 MFMA trunk has no per-row pose form (contraction dtypes f32 / f32_f16x3)");
+    DGDM_REQUIRE(n_interactions >= 1, DGDM_EINVAL, "dgdm_guidance_rollout: %d interactions (at least 1)", n_interactions);
+    DGDM_REQUIRE(n_chains > 0 && n_chains <= g->cfg.max_chains, DGDM_EINVAL, "n_chains %d outside 1..%d", n_chains, g->cfg.max_chains);
+    DGDM_REQUIRE(g->n_objects > 0, DGDM_EINVAL, "dgdm_guidance_set_objects has not been called");
+    hipStream_t s = (hipStream_t)stream;
+    const int kind = g->m->kind, K = n_interactions, W1 = g->m->W1;
+    DGDM_REQUIRE(kind == 2 || starts_host, DGDM_EINVAL, "3-D roll-out needs the FPS start indices");
+    const int64_t Rs = g->Rs, rows = (int64_t)n_chains * Rs;
+    const int ntiles = n_chains * g->B * g->sweep_tiles_per_b;
+    int rc;
+    if ((rc = g->rollstate.alloc((size_t)rows * 3 * sizeof(double))) || (rc = g->rolltiles.alloc((size_t)ntiles * 32 * W1 * sizeof(float))) ||
+        (kind == 3 && (rc = g->rollpmax.alloc((size_t)ntiles * 32 * sizeof(float)))) ||
+        (!traj_logits_dev && (rc = g->rolllogits.alloc((size_t)rows * 3 * sizeof(float)))))
+        return rc;
+    if ((rc = g->common_pre(x_dev, 0.f, object_of_chain, n_chains, s))) return rc;       // t = 0, as the sweep
+    TrunkParams p;
+    g->m->fill_trunk(&p);
+    bool tab = false;
+    if (kind == 3) {
+        // float32 embeddings through the sweep's path: table rows when the float32 tables exist, the gather kernels otherwise
+        tab = g->xtab_enabled && !g->force_slow_xobj && g->xobj_mode == 0;
+        for (int i = 0; i < n_chains && tab; ++i) tab = object_of_chain[i] >= 0 && object_of_chain[i] < g->n_objects && g->tables[object_of_chain[i]]->has_x;
+        if ((rc = g->upload_starts(starts_host, n_chains, Rs, s, !tab, K, (int64_t)n_chains * 2 * Rs))) return rc;
+        if ((rc = g->finish_objects())) return rc;
+        if (tab && (rc = g->use_xtab(object_of_chain, n_chains, Rs * K, false, &p, &tab, s))) return rc;
+        if (!tab && (rc = g->run_xobj(object_of_chain, n_chains, Rs * K, false, nullptr, s))) return rc;
+        DGDM_HIP_CHECK(hipEventRecord(g->up_consumed, s));
+        g->consumed_recorded = true;
+    }
+    TrunkF16Scales sc;
+    g->m->fill_trunk_f16(&p, &sc);
+    p.Atab = g->atab.as<float>(); p.Ptab = nullptr; p.PtabT = g->rolltiles.as<float>(); p.Pmax = kind == 3 ? g->rollpmax.as<float>() : nullptr;
+    p.B = g->B; p.C = g->G; p.tiles_per_b = g->sweep_tiles_per_b; p.ntiles = ntiles; p.R = Rs; p.xstride = kind == 3 ? Rs * K : Rs;
+    double *state = g->rollstate.as<double>();
+    if ((rc = rollout_start(g->sweep_ori.as<float>(), n_chains, g->B, g->G, state, left_dev, traj_pose_dev, s))) return rc;
+    g->rolltiles_chains = n_chains;
+    for (int k = 0; k < K; ++k) {
+        if ((rc = rollout_pose_table(state, g->m->blob64.at(g->m->off64.w1p_wt), W1, n_chains, g->B, g->G, g->rolltiles.as<float>(), p.Pmax ? g->rollpmax.as<float>() : nullptr, s)))
+            return rc;
+        p.logits = traj_logits_dev ? traj_logits_dev + (size_t)k * rows * 3 : g->rolllogits.as<float>();
+        if (kind == 3) {
+            if (tab) p.xidx = g->xidx.as<int>() + (size_t)k * Rs;
+            else p.xobj = g->xobj.as<float>() + (size_t)k * Rs * 256;
+        }
+        if ((rc = trunk_f16l_forward_rowpose_launch(kind, p, sc, s))) return rc;
+        if ((rc = rollout_update(p.logits, scale, k, rows, state, left_dev, traj_pose_dev ? traj_pose_dev + (size_t)(k + 1) * rows * 3 : nullptr,
+                                 k == K - 1 ? final_dev : nullptr, k == 0 ? first_logits_dev : nullptr, s)))
+            return rc;
+    }
+    return DGDM_OK;
+}
+
+// Test hook: the pose operand tiles the last dgdm_guidance_rollout call left behind (its LAST interaction's: call it with one
+// interaction to see the start poses') -> rollout_tiles_dev [n_chains * B * tiles_per_finger][W1 * 32], tile = (chain * B + b) *
+// tiles_per_finger + orientation tile, and the sweep's own table in the same layout -> sweep_tiles_dev [tiles_per_finger][W1 * 32].
+extern "C" int dgdm_guidance_debug_rollout_table(DgdmGuidance *g, int n_chains, float *rollout_tiles_dev, float *sweep_tiles_dev,
+                                                 int32_t *tiles_per_finger, int32_t *width, void *stream) {
+    DGDM_REQUIRE(g && n_chains > 0 && n_chains <= g->cfg.max_chains, DGDM_EINVAL, "dgdm_guidance_debug_rollout_table: bad argument");
+    if (tiles_per_finger) *tiles_per_finger = g->sweep_tiles_per_b;
+    if (width) *width = g->m->W1;
+    const size_t per_tile = (size_t)g->m->W1 * 32 * sizeof(float);
+    if (rollout_tiles_dev) {
+        DGDM_REQUIRE(n_chains <= g->rolltiles_chains, DGDM_EINVAL, "dgdm_guidance_debug_rollout_table: the last roll-out had %d chains", g->rolltiles_chains);
+        DGDM_HIP_CHECK(hipMemcpyAsync(rollout_tiles_dev, g->rolltiles.p, (size_t)n_chains * g->B * g->sweep_tiles_per_b * per_tile, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    }
+    if (sweep_tiles_dev)
+        DGDM_HIP_CHECK(hipMemcpyAsync(sweep_tiles_dev, g->ptab_sweep_t.p, (size_t)g->sweep_tiles_per_b * per_tile, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    return DGDM_OK;
 }
 
 // ================================================================================================ PointNet++ on arbitrary rows

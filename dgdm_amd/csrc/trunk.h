@@ -34,8 +34,8 @@ struct TrunkParams {
     // first-layer tables
     const float  *Atab;       // table mode: [nchain*B][W1]; rows mode: [rows][W1]
     const float  *Ptab;       // [C][W1]  (table mode)
-    const float  *PtabT;      // the same, tiled per 32 cells in operand layout (smallnet.h tile_table)
-    const float  *Pmax;       // [C] largest magnitude of a cell's row of Ptab (trunk_f16l.hip: the f16 scale of 3-D layer 2's input); may be null elsewhere
+    const float  *PtabT;      // the same, tiled per 32 cells in operand layout (smallnet.h tile_table); per-row pose mode (trunk_f16l_forward_rowpose_launch): one tile per trunk tile, [ntiles][W1 / 32][4][64] float4
+    const float  *Pmax;       // [C] largest magnitude of a cell's row of Ptab (trunk_f16l.hip: the f16 scale of 3-D layer 2's input); may be null elsewhere; per-row pose mode: [ntiles][32], one value per tile row, padding rows included
     const TrunkObjective *obj;// [nchain]
     const float  *rowcoef;    // [nchain][R] or null
     float        *partial;    // [ntiles][W1]
@@ -58,6 +58,23 @@ struct TrunkF16Scales {
 int trunk_f16l_launch(int kind, const TrunkParams &p, const TrunkF16Scales &sc, hipStream_t s);
 // The forward half alone: the logits of every valid row to p.logits [nchain][R][3]; p.Wbwd, p.obj, p.rowcoef and p.partial are not read.
 int trunk_f16l_forward_launch(int kind, const TrunkParams &p, const TrunkF16Scales &sc, hipStream_t s);
+// The same with a pose per ROW instead of per cell (dgdm_guidance_rollout): p.PtabT = one operand tile per trunk tile,
+// [ntiles][W1 / 32][4][64] float4 in tile_table's layout (tile = (chain * B + finger) * tiles_per_b + cell tile), p.Pmax (3-D) =
+// [ntiles][32], padding rows included; p.Ptab is not read.
+int trunk_f16l_forward_rowpose_launch(int kind, const TrunkParams &p, const TrunkF16Scales &sc, hipStream_t s);
+
+// Roll-out steps around that trunk (rollout.hip).  State [n_chains][B * G][3] doubles = (ori, pos_x, pos_y) in the model's normalised
+// units, row r = g * B + b.
+// rollout_start: state = (ori_grid[g], 0, 0); left = -1; a copy of the state to traj0 when it is not null.
+int rollout_start(const float *ori_grid, int n_chains, int B, int G, double *state, int32_t *left, double *traj0, hipStream_t s);
+// rollout_pose_table: the state rounded to float32 -> layer 1's pose term per row (the 27-wide embedding of pose_embed_kernel times
+// w1p_wt [27][W1] in float64, rounded once), written as the trunk's operand tiles; a finger's padding rows repeat its last valid row.
+// pmax (3-D, else null): [ntiles][32] largest magnitude of each row.
+int rollout_pose_table(const double *state, const double *w1p_wt, int W1, int n_chains, int B, int G, float *tiles, float *pmax, hipStream_t s);
+// rollout_update: state += logits * scale (each product and sum rounded on its own), ori wrapped into [-1, 1]; left[r] = k the first
+// time |pos| leaves 1; copies: the new state to traj_next / final, the logits to first_logits, where those are not null.
+int rollout_update(const float *logits, const double scale[3], int k, int64_t rows, double *state, int32_t *left, double *traj_next,
+                   double *final_state, float *first_logits, hipStream_t s);
 
 // Per (chain, finger) tally of forward-only logits [n_chains][B * C][3] (row = cell * B + finger; score.hip): the joint class histogram
 // counts [n_chains][B][27] (bin = (class of d0 * 3 + class of d1) * 3 + class of d2; class 2 if l > thr, 0 if l < -thr, else 1) and

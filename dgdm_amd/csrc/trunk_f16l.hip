@@ -324,8 +324,11 @@ using namespace f16l;
 // FWD_ONLY: the forward half alone (dgdm_guidance_score) - the same table terms, layers and output layer, the three logits of every
 // valid row to p.logits, and nothing of what only serves the way back: no sign masks (and no LDS for them: smask has no reader or
 // writer left in this instantiation and is not allocated), no backward stream, no objective, no partial sums.
-template <int KIND, bool FWD_ONLY = false>
+// ROWPOSE (only with FWD_ONLY: dgdm_guidance_rollout): every row has a pose of its own - p.PtabT holds one operand tile per trunk tile
+// (chain, finger, 32 cells) and p.Pmax one value per tile row, [ntiles][32], instead of one per cell shared by all chains and fingers.
+template <int KIND, bool FWD_ONLY = false, bool ROWPOSE = false>
 __global__ __launch_bounds__(256, 1) void trunk_f16l_kernel(const TrunkParams p, const TrunkF16Scales sc) {
+    static_assert(FWD_ONLY || !ROWPOSE, "per-row poses: forward-only kernel");
     constexpr int W1B = (KIND == 3) ? 16 : 8;
     constexpr int W1 = W1B * 32;
     constexpr int NSLOT = (KIND == 3) ? 8 + 7 * 4 : 8 * 4;
@@ -352,7 +355,7 @@ __global__ __launch_bounds__(256, 1) void trunk_f16l_kernel(const TrunkParams p,
     const bool valid = c < p.C;
     const int64_t r = (int64_t)(valid ? c : p.C - 1) * p.B + b;
     const float *arow = p.Atab + (size_t)(chain * p.B + b) * W1;
-    const float4 *ptile = reinterpret_cast<const float4 *>(p.PtabT) + (size_t)(rem - b * p.tiles_per_b) * W1B * 4 * 64 + lane;
+    const float4 *ptile = reinterpret_cast<const float4 *>(p.PtabT) + (size_t)(ROWPOSE ? tile : rem - b * p.tiles_per_b) * W1B * 4 * 64 + lane;
 
     f32x16 Y[8];
     uint32_t m[4];
@@ -407,7 +410,7 @@ __global__ __launch_bounds__(256, 1) void trunk_f16l_kernel(const TrunkParams p,
 #pragma unroll
             for (int o = 32; o > 0; o >>= 1) am = fmaxf(am, __shfl_xor(am, o));
         }
-        const float zb = am + p.Pmax[valid ? c : p.C - 1] + sc.l1_norm1 * pow2f(13 - kx);
+        const float zb = am + (ROWPOSE ? p.Pmax[(size_t)tile * 32 + n] : p.Pmax[valid ? c : p.C - 1]) + sc.l1_norm1 * pow2f(13 - kx);
         const int eb = (int)((__float_as_uint(zb) >> 23) & 0xffu);
         const int k2 = (zb > 0.f && eb < 255) ? min(max(12 + 127 - eb, -100), 100) : 0;      // zb 2^k2 in [2^12, 2^13)
         const float f2 = pow2f(k2);
@@ -620,6 +623,21 @@ int trunk_f16l_forward_launch(int kind, const TrunkParams &p, const TrunkF16Scal
     prof_begin(s, DGDM_STAGE_TRUNK);
     if (kind == 2) hipLaunchKernelGGL((trunk_f16l_kernel<2, true>), dim3(grid), dim3(256), 0, s, p, sc);
     else hipLaunchKernelGGL((trunk_f16l_kernel<3, true>), dim3(grid), dim3(256), 0, s, p, sc);
+    DGDM_HIP_CHECK(hipGetLastError());
+    prof_end(s, DGDM_STAGE_TRUNK, rows * per_row);
+    return DGDM_OK;
+}
+
+int trunk_f16l_forward_rowpose_launch(int kind, const TrunkParams &p, const TrunkF16Scales &sc, hipStream_t s) {
+    if (p.n_mid != (kind == 3 ? 6 : 7) || !p.logits || !p.PtabT || (kind == 3 && !p.Pmax)) return DGDM_EINVAL;
+    const int grid = (p.ntiles + 3) / 4;
+    if (grid == 0) return DGDM_OK;
+    const double rows = (double)(p.ntiles / std::max(1, p.tiles_per_b)) * p.C;
+    const double mid = 2.0 * 256 * 256 * p.n_mid;
+    const double per_row = (kind == 3) ? 2.0 * 256 * 512 * 2 + mid : mid;
+    prof_begin(s, DGDM_STAGE_TRUNK);
+    if (kind == 2) hipLaunchKernelGGL((trunk_f16l_kernel<2, true, true>), dim3(grid), dim3(256), 0, s, p, sc);
+    else hipLaunchKernelGGL((trunk_f16l_kernel<3, true, true>), dim3(grid), dim3(256), 0, s, p, sc);
     DGDM_HIP_CHECK(hipGetLastError());
     prof_end(s, DGDM_STAGE_TRUNK, rows * per_row);
     return DGDM_OK;

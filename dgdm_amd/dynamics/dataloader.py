@@ -24,6 +24,7 @@ from torch.utils.data import Dataset
 # score normalisation and class thresholds (dataloader.py:11-16); index 0 = 3-D, 1 = 2-D
 SCORE_STD = (np.array([0.0312, 0.0016, 0.0026]), np.array([0.0565, 0.0026, 0.0047]))
 SCORE_THRESHOLD = (np.array([0.02, 0.001, 0.001]), np.array([0.03, 0.002, 0.003]))
+POS_NORM = 0.03           # metres per unit of the model's position input (dataloader.py:52: obj_pos / 0.03)
 # workspace boxes of dynamics/main.py:61-82 (2-D): metres -> [-1, 1]
 GRIPPER_BOX_2D = ((-0.12, 0.12), (-0.045, 0.015))
 OBJECT_BOX_2D = ((-0.05, 0.05), (-0.05, 0.05))
@@ -98,5 +99,5 @@ class DynamicsDataset(Dataset):
         return {'ctrlpts': torch.from_numpy(_to_unit(d['ctrlpts'], self.gripper_box)).float(),
                 'scores': torch.from_numpy(scores).float(),
                 'input_ori': torch.from_numpy(np.asarray(d['obj_theta']) / np.pi - 1.0).float(),
-                'input_pos': torch.from_numpy(np.asarray(d['obj_pos'])[..., :2] / 0.03).float(),
+                'input_pos': torch.from_numpy(np.asarray(d['obj_pos'])[..., :2] / POS_NORM).float(),
                 'object_vertices': verts}

@@ -40,6 +40,8 @@ _FLAGS = [
     ("fingers_3d", "flag", None, "3-D fingers / PointNet++ dynamics model"),
     ("render_video", "flag", None, "simulator videos (external)"),
     ("predicted_sim", "flag", None, "fill the objective tables with the dynamics model's predictions (dynamics/predicted.py)"),
+    ("predicted_rollout", int, 0, "with --predicted_sim: interactions the dynamics model is iterated for per start orientation, so that the "
+                                  "final_* scores and 'convergence' see a settled pose (40 = the simulator's count; 0 = one interaction)"),
     ("save_meshes", "flag", None, "also export every emitted gripper as OBJ meshes, collision pieces and gripper_<idx>.xml (assets/finger_mesh.py)"),
     ("save_objects", "flag", None, "2-D: also export the run's icon objects as meshes, convex pieces and object_<idx>.xml into every model root "
                                    "(assets/icon_process.py save_icon_objects)"),

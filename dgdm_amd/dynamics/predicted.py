@@ -14,6 +14,11 @@ radians for the rotation, metres for the two shifts; the model's outputs are sco
 compares them with ``threshold / std``.  The dicts built here are in the units of the simulator's ``metrics`` dict
 (sim_test_mj.py:209-218): degrees (x 180 / pi) and centimetres (x 100).
 
+Roll-outs.  The simulator closes the gripper 40 times per start orientation (dynamics/sim_test_mj.py:161-185, sim_test_mj_3d.py:
+154-176) and reports the motion after the first closing and the settled pose after the last.  ``PredictedSimulator(...,
+rollout_interactions=K)`` does the same with the model in the simulator's place (``engine.Guidance.rollout``): the one-step keys from the
+first interaction, the ``final_*`` keys from the pose after the K-th.  With ``K = 0`` one interaction stands for both.
+
 These are the dynamics model's opinion, not simulator measurements; every metric dict carries ``'predicted': True``.
 """
 from __future__ import annotations
@@ -22,6 +27,7 @@ from typing import Any, Dict, List, Optional, Sequence
 
 import numpy as np
 
+from .dataloader import POS_NORM
 from .metrics import _ROT, _SHIFT
 
 DEG = 180.0 / np.pi       # radians -> degrees (sim_test_mj.py:210)
@@ -81,19 +87,47 @@ def predicted_objective(counts, sums, n_cells: int, std: Sequence[float], opt_ob
     raise ValueError('opt obj not supported')
 
 
-def build_metric(logits, threshold_std: Sequence[float], std: Sequence[float], ori_range: Sequence[float] = (-1.0, 1.0)) -> Dict[str, Any]:
+def build_metric(logits, threshold_std: Sequence[float], std: Sequence[float], ori_range: Sequence[float] = (-1.0, 1.0),
+                 final_pose=None, left=None, rollout_interactions: Optional[int] = None) -> Dict[str, Any]:
     """The ``metric`` dict ``metric2objective`` consumes (sim_test_mj.py:209-218) for one (object, gripper) from the model's
     normalised outputs ``logits`` (num_rot, 3) at the centre position over ``num_rot`` orientations of ``ori_range``: profiles from
-    the classes, motions un-normalised with ``std`` (degrees, centimetres).  The model predicts one interaction, not a settled pose:
-    ``final_theta`` = initial angle + predicted rotation, ``final_delta_theta`` = ``delta_theta``, ``final_pos`` = ``delta_pos``."""
+    the classes, motions un-normalised with ``std`` (degrees, centimetres).  Without ``final_pose`` the one interaction stands for
+    the settled pose too: ``final_theta`` = initial angle + predicted rotation, ``final_delta_theta`` = ``delta_theta``,
+    ``final_pos`` = ``delta_pos``.  With ``final_pose`` (num_rot, 3) = (ori, pos_x, pos_y) after a roll-out of K interactions in the
+    model's normalised inputs and ``left`` (num_rot,) (``Guidance.rollout``): ``final_theta`` = (ori + 1) x 180 degrees,
+    ``final_delta_theta`` = the signed difference to the initial angle, folded once into [-180, 180] (``continuous_signed_delta``,
+    dynamics/utils.py:6-12, in degrees), ``final_pos`` = pos x 0.03 m in centimetres; ``'rollout_interactions'`` = K, which the
+    pose does not tell and the caller therefore states (required with ``final_pose``), ``'rollout_left_range'`` counts the orientations whose position left the range the model was trained
+    on (``left >= 0``): past it the model extrapolates."""
     l = np.asarray(logits, dtype=np.float32).reshape(-1, 3)
     std = np.asarray(std, dtype=np.float64).reshape(3)
     cls = classes(l, threshold_std)
     delta_theta = l[:, 0].astype(np.float64) * std[0] * DEG
     delta_pos = np.stack([l[:, 1].astype(np.float64) * std[1] * CM, l[:, 2].astype(np.float64) * std[2] * CM, np.zeros(len(l))], axis=1)
     initial = (np.linspace(ori_range[0], ori_range[1], len(l)) + 1.0) * 180.0              # z_rots of sim_test_mj.py:142, in degrees
-    return {'delta_theta': delta_theta, 'delta_pos': delta_pos, 'profile': cls[:, 0], 'profile_x': cls[:, 1], 'profile_y': cls[:, 2],
-            'final_theta': initial + delta_theta, 'final_delta_theta': delta_theta.copy(), 'final_pos': delta_pos.copy(), 'predicted': True}
+    metric = {'delta_theta': delta_theta, 'delta_pos': delta_pos, 'profile': cls[:, 0], 'profile_x': cls[:, 1], 'profile_y': cls[:, 2],
+              'final_theta': initial + delta_theta, 'final_delta_theta': delta_theta.copy(), 'final_pos': delta_pos.copy(), 'predicted': True}
+    if final_pose is None and left is None:
+        return metric
+    if final_pose is None or left is None:
+        raise ValueError("build_metric: final_pose and left come together (Guidance.rollout returns both)")
+    if rollout_interactions is None or int(rollout_interactions) < 1:
+        raise ValueError("build_metric: a settled pose needs rollout_interactions = K >= 1, the number of interactions that made it")
+    fp = np.asarray(final_pose, dtype=np.float64).reshape(-1, 3)
+    lf = np.asarray(left).reshape(-1)
+    if len(fp) != len(l) or len(lf) != len(l):
+        raise ValueError(f"build_metric: {len(l)} orientations, final_pose holds {len(fp)} and left {len(lf)}")
+    # (`initial` is float64 linspace, the device's start grid float32: a row that never moves shows ~1e-6 degrees, not 0 - far below
+    #  the 3 / 5 / 10 degree thresholds the finals are scored with)
+    final_theta = (fp[:, 0] + 1.0) * 180.0
+    delta = final_theta - initial
+    delta = np.where(delta > 180.0, delta - 360.0, np.where(delta < -180.0, delta + 360.0, delta))
+    metric['final_theta'] = final_theta
+    metric['final_delta_theta'] = delta
+    metric['final_pos'] = np.stack([fp[:, 1] * POS_NORM * CM, fp[:, 2] * POS_NORM * CM, np.zeros(len(l))], axis=1)
+    metric['rollout_interactions'] = int(rollout_interactions)
+    metric['rollout_left_range'] = int(np.count_nonzero(lf >= 0))
+    return metric
 
 
 def center_index(num_pos: int) -> int:
@@ -123,10 +157,17 @@ class PredictedSimulator:
 
     The handles are the simulator's own (nothing the sampling path keeps is touched), and the 3-D FPS start draws come from a
     private ``sampler.TorchRng`` seeded from ``Diffusion.seed`` - never from the global CPU generator - so the sampled designs are
-    bit-identical with scoring on and off."""
+    bit-identical with scoring on, off or rolled out.
 
-    def __init__(self, diffusion):
+    ``rollout_interactions = K > 0``: every key comes from one ``Guidance.rollout`` call of K interactions on the same handle - the
+    one-step keys from its first interaction's logits, the ``final_*`` keys from the pose after the last (``build_metric`` with
+    ``final_pose`` / ``left``), and ``'rollout_interactions': K``.  ``0``: one ``Guidance.score`` call, one interaction for both."""
+
+    def __init__(self, diffusion, rollout_interactions: int = 0):
+        if int(rollout_interactions) < 0:
+            raise ValueError(f"PredictedSimulator: rollout_interactions = {rollout_interactions} is negative")
         self.diffusion = diffusion
+        self.rollout_interactions = int(rollout_interactions)
         self._handles: Dict[Any, Any] = {}
         self._rng = None
 
@@ -153,7 +194,8 @@ class PredictedSimulator:
         import torch
         from .. import sampler
         d = self.diffusion
-        center_index(d.num_pos)
+        if not self.rollout_interactions:
+            center_index(d.num_pos)            # the grid's centre cells; a roll-out starts at pos = 0 whatever the grid
         x = torch.as_tensor(np.asarray(samples), dtype=torch.float32)
         n = x.shape[0]
         x = x.reshape(n, -1)
@@ -163,15 +205,27 @@ class PredictedSimulator:
         g = self._guidance(n, int(num_rot), ori_range, bank)
         nc = len(oidx)
         starts = None
+        K = self.rollout_interactions
         if d.mode == 'point_3d':
             if self._rng is None:
                 self._rng = sampler.TorchRng(seed=int(d.seed))
-            starts = self._rng.fps_starts(g.cfg.num_object_points, g.cfg.sub_batch_size, g.rows, n_calls=nc)
+            starts = self._rng.fps_starts(g.cfg.num_object_points, g.cfg.sub_batch_size, g.sweep_rows if K else g.rows, n_calls=max(K, 1) * nc)
         thr = [float(v) for v in d.threshold_std]
-        _, _, logits = g.score(x.to(d.device)[None].expand(nc, n, x.shape[1]).contiguous(), oidx, thr, timestep=0, starts=starts, want_logits=True)
-        rows = center_rows(logits, n, int(num_rot), d.num_pos).cpu().numpy()                 # (object, gripper, orientation, 3)
         std = [float(v) for v in d.std]
-        metrics = [build_metric(rows[i, b], thr, std, ori_range) for i in range(nc) for b in range(n)]
         total = nc * n
         none: List[Any] = [None] * total
+        if K:
+            xc = x.to(d.device)[None].expand(nc, n, x.shape[1]).contiguous()
+            final, first, left = g.rollout(xc, oidx, std, K, starts=starts)
+            # rows r = g * B + b  ->  (object, gripper, orientation)
+            by = lambda t: t.reshape(nc, int(num_rot), n, *t.shape[2:]).transpose(1, 2).cpu().numpy()          # noqa: E731
+            final, first, left = by(final), by(first), by(left)
+            metrics = []
+            for i in range(nc):
+                for b in range(n):
+                    metrics.append(build_metric(first[i, b], thr, std, ori_range, final_pose=final[i, b], left=left[i, b], rollout_interactions=K))
+            return list(none), metrics, list(none), list(none), list(none), list(none), [[] for _ in range(total)], list(none)
+        _, _, logits = g.score(x.to(d.device)[None].expand(nc, n, x.shape[1]).contiguous(), oidx, thr, timestep=0, starts=starts, want_logits=True)
+        rows = center_rows(logits, n, int(num_rot), d.num_pos).cpu().numpy()                 # (object, gripper, orientation, 3)
+        metrics = [build_metric(rows[i, b], thr, std, ori_range) for i in range(nc) for b in range(n)]
         return list(none), metrics, list(none), list(none), list(none), list(none), [[] for _ in range(total)], list(none)

@@ -332,6 +332,44 @@ class Guidance:
         check(lib().dgdm_guidance_orientation_sweep(self._h, dptr(x), oc, sp, nc, dptr(out), stream_ptr()))
         return out
 
+    def rollout(self, x: torch.Tensor, object_of_chain: Sequence[int], std: Sequence[float], n_interactions: int,
+                starts: Optional[np.ndarray] = None, want_trajectory: bool = False):
+        """The dynamics model iterated on its own output from the sweep's poses (include/dgdm_hip.h, dgdm_guidance_rollout; in place
+        of the simulator's 40 gripper closings per start orientation, dynamics/sim_test_mj.py:161-185): x (n_chains, B, L) ->
+        (final (n, B*G, 3) float64 = (ori, pos_x, pos_y) after the last interaction in the model's normalised inputs, first_logits
+        (n, B*G, 3) float32 of interaction 0, left (n, B*G) int32 = the first interaction after which |pos| > 1 or -1[, traj_pose
+        (K + 1, n, B*G, 3) float64 with slot 0 = the start, traj_logits (K, n, B*G, 3) float32]); row = g*B + b.  std: the dataset's
+        (rad, m, m) the model's outputs are normalised by.  3-D: starts = K consecutive classifier calls' draws, (K, n_chains,
+        2*B*G) int64 in the sweep's layout.  'bf16' and 'f32_mfma' handles raise DgdmError."""
+        from .dynamics.dataloader import POS_NORM
+        x = _f32(x)
+        nc, K, R = x.shape[0], int(n_interactions), self.sweep_rows
+        oc = (C.c_int32 * nc)(*[int(o) for o in object_of_chain])
+        scale = (C.c_double * 3)(float(std[0]) / np.pi, float(std[1]) / POS_NORM, float(std[2]) / POS_NORM)
+        dev = x.device
+        final = torch.empty((nc, R, 3), dtype=torch.float64, device=dev)
+        first = torch.empty((nc, R, 3), dtype=torch.float32, device=dev)
+        left = torch.empty((nc, R), dtype=torch.int32, device=dev)
+        tp = torch.empty((max(K, 0) + 1, nc, R, 3), dtype=torch.float64, device=dev) if want_trajectory else None
+        tl = torch.empty((max(K, 0), nc, R, 3), dtype=torch.float32, device=dev) if want_trajectory else None
+        sp = None
+        if self.dyn.kind == 3:
+            assert starts is not None and starts.dtype == np.int64 and starts.size == max(K, 0) * nc * 2 * R
+            starts = np.ascontiguousarray(starts)
+            sp = starts.ctypes.data
+        check(lib().dgdm_guidance_rollout(self._h, dptr(x), oc, sp, scale, K, nc, dptr(final), dptr(first), dptr(left), dptr(tp), dptr(tl), stream_ptr()))
+        return (final, first, left, tp, tl) if want_trajectory else (final, first, left)
+
+    def debug_rollout_table(self, n_chains: int):
+        """Test hook: (layer 1's pose term of the last rollout()'s last interaction as operand tiles (n_chains, B, tiles_per_finger,
+        W1 * 32), the sweep's own table in the same layout (tiles_per_finger, W1 * 32))."""
+        tpf, w = C.c_int32(), C.c_int32()
+        check(lib().dgdm_guidance_debug_rollout_table(self._h, n_chains, None, None, C.byref(tpf), C.byref(w), stream_ptr()))
+        a = torch.empty((n_chains, self.cfg.batch, tpf.value, w.value * 32), dtype=torch.float32, device="cuda")
+        b = torch.empty((tpf.value, w.value * 32), dtype=torch.float32, device="cuda")
+        check(lib().dgdm_guidance_debug_rollout_table(self._h, n_chains, dptr(a), dptr(b), None, None, stream_ptr()))
+        return a, b
+
 
 def ddim_guided_step(x: torch.Tensor, eps: torch.Tensor, grad: Optional[torch.Tensor], n_grad: int, coef: Tuple[float, float, float, float],
                      scale: float) -> torch.Tensor:

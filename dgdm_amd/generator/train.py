@@ -267,9 +267,14 @@ def train(args):
     model.save_meshes = bool(getattr(args, "save_meshes", False))
     if getattr(args, "save_objects", False):
         model.object_exporter = _object_exporter(args)
+    rollout = int(getattr(args, "predicted_rollout", 0) or 0)
+    if rollout and not getattr(args, "predicted_sim", False):
+        raise ValueError(f"--predicted_rollout={rollout} needs --predicted_sim: it sets how many interactions the predicted simulator iterates")
+    if rollout < 0:
+        raise ValueError(f"--predicted_rollout={rollout}: the number of interactions cannot be negative")
     if getattr(args, "predicted_sim", False) and args.classifier_guidance and model.simulator is None:
         from ..dynamics.predicted import PredictedSimulator      # opt-in: the tables scored by the dynamics model instead of roll-outs
-        model.simulator = PredictedSimulator(model)
+        model.simulator = PredictedSimulator(model, rollout_interactions=rollout)
     if args.mode != 'test':                 # generator/train.py:158-162
         if args.diffusion_checkpoint_path is not None:
             print('loading diffusion checkpoint from', args.diffusion_checkpoint_path)

@@ -243,6 +243,30 @@ int dgdm_guided_chains_run(DgdmUnet1d *unet, DgdmGuidance *g, const float *noise
 int dgdm_guidance_orientation_sweep(DgdmGuidance *g, const float *x_dev, const int32_t *object_of_chain,
                                     const int64_t *starts_host, int n_chains, float *logits_dev, void *stream);
 
+/* Predicted roll-outs: the dynamics model iterated on its own output, from the sweep's poses.  This stands where the reference's
+ * simulator closes the gripper 40 times per start orientation (2-D: dynamics/sim_test_mj.py:161-185, 8000 steps with the gripper reset
+ * every 200; 3-D: sim_test_mj_3d.py:154-176, 32000 steps, reset every 800) and reports the motion after the first closing and the
+ * settled pose after the last; the roll-out itself is ours - the reference's are MuJoCo's.
+ *   State per row (chain, finger b, start orientation g; r = g*B + b as the sweep): (ori, pos_x, pos_y) in float64, in the model's
+ *   normalised inputs (ori = theta/pi - 1, pos = metres / 0.03; dynamics/dataloader.py:51-52).  Start: the sweep's poses,
+ *   ori = linspace(ori_range)[g], pos = 0.  Interaction k = 0 .. K-1: the state rounded once to float32, the model evaluated at t = 0
+ *   -> three float32 logits l; then, in double, each product and sum rounded on its own:
+ *     ori += l0 * scale[0], brought back into [-1, 1] by multiples of 2 (values inside, +-1 included, are left alone);
+ *     pos += l{1,2} * scale[{1,2}], NOT clamped: beyond |pos| = 1 the model extrapolates, and left[r] tells - the first k after which
+ *     |pos_x| > 1 or |pos_y| > 1, -1 if never.
+ *   A non-finite logit makes the row's state non-finite for good.  scale: the caller's std[0]/pi, std[1]/0.03, std[2]/0.03.
+ *   starts_host  3-D: [K][n_chains][2*B*G] int64 - every interaction is a classifier call of its own, each with the sweep's layout and
+ *                sub_batch_size partition, consecutive calls; 2-D: NULL
+ *   final_dev [n][B*G][3] the state after interaction K-1; first_logits_dev [n][B*G][3] interaction 0's logits (= the sweep's poses
+ *   through the f16x3 trunk); left_dev [n][B*G]; traj_pose_dev NULL or [K+1][n][B*G][3] (slot 0 = the start); traj_logits_dev NULL or
+ *   [K][n][B*G][3].
+ * All K interactions are enqueued on `stream`; nothing is copied to the host and the host does not wait between them.  Contraction
+ * dtypes f32 / f32_f16x3 (forward-only f16x3 trunk with a pose per row); bf16 and f32_mfma: DGDM_EINVAL (neither trunk has that
+ * form).  Bit-identical run to run; leaves what grad / score / orientation_sweep compute untouched.                                    */
+int dgdm_guidance_rollout(DgdmGuidance *g, const float *x_dev, const int32_t *object_of_chain, const int64_t *starts_host,
+                          const double scale[3], int n_interactions, int n_chains, double *final_dev, float *first_logits_dev,
+                          int32_t *left_dev, double *traj_pose_dev, float *traj_logits_dev, void *stream);
+
 /* Host helper for 'convergence': rowcoef_host[r] for one chain from its centers [B]
  * (deltas_to_objective :445-452 + slicer; `rows_in_call` is R for 2-D and the sub-batch
  * partition is applied for 3-D exactly as cond_fn :494-499 does).                               */
@@ -480,6 +504,13 @@ int dgdm_guidance_debug_fps_path(DgdmGuidance *g, int mode, int32_t *out_fast_ok
  * (chain * B + b) * tiles_per_finger + t = cells 32 t .. 32 t + 31 of finger b.  A ReLU whose float32 pre-activation has the other sign
  * than in exact arithmetic changes exactly one tile, which is what tests/test_gpu_fullgrid.py looks at.  out_dev may be NULL (sizes only). */
 int dgdm_guidance_debug_partials(DgdmGuidance *g, int n_chains, float *out_dev, int32_t *tiles_per_finger, int32_t *width, void *stream);
+/* Test hook: layer 1's pose term as the last dgdm_guidance_rollout call left it - its LAST interaction's rows (a call with one
+ * interaction shows the start poses') - in the trunk's operand tiles: rollout_tiles_dev [n_chains * B * tiles_per_finger][width * 32],
+ * tile (chain * B + b) * tiles_per_finger + t = orientations 32 t .. 32 t + 31 of finger b; and the orientation sweep's own table in the
+ * same layout, sweep_tiles_dev [tiles_per_finger][width * 32].  At the start poses every tile (chain, b, t) must equal the sweep's tile
+ * t bit for bit, padding rows included.  Either pointer may be NULL (sizes only).                                                      */
+int dgdm_guidance_debug_rollout_table(DgdmGuidance *g, int n_chains, float *rollout_tiles_dev, float *sweep_tiles_dev,
+                                      int32_t *tiles_per_finger, int32_t *width, void *stream);
 int dgdm_prof_read(int64_t *launches, double *total_ms, double *total_flops);
 int dgdm_prof_read_stage(int stage, int64_t *launches, double *total_ms, double *total_work);
 /* Unit-test hook for the register-resident MFMA chain (csrc/mfma_chain.h): one 32-row tile through one 256 -> 256 layer,
