@@ -1,7 +1,5 @@
 // Diffusion.cond_fn / get_convergence_centers (generator/diffusion.py:473-539) for batches of chains,
 // and the PointNet++-backed forward entry points.
-#ifndef DGDM_DEFAULT_F16X3
-#endif
 #include "common.h"
 #include "models.h"
 #include <algorithm>
@@ -44,16 +42,21 @@ struct ObjectTables {       // 3-D, per object
     bool   has16 = false;
 };
 
+// A pose table of the trunk's first layer and the rows it spans: the cond_fn grid (G * P * P cells) or the orientation sweep (G cells)
+struct PoseGrid {
+    DevBuf tab, tiled;      // [cells][W1]; the same tiled for the trunk kernels (smallnet.h tile_table)
+    DevBuf pmax;            // [cells] largest magnitude of a cell's row of tab (trunk_f16l.hip: f16 scale of 3-D layer 2's input); cond_fn grid only
+    int cells = 0, tiles_per_b = 0;
+    int64_t rows = 0;       // rows per chain: B * cells
+};
+
 }  // namespace
 
 struct DgdmGuidance {
     DgdmDynamics *m = nullptr;
     DgdmGuidanceConfig cfg{};
-    int C = 0, G = 0, B = 0, tiles_per_b = 0, sweep_tiles_per_b = 0;
-    int64_t R = 0, Rs = 0;                       // rows per chain: cond_fn grid, orientation sweep
-    DevBuf ptab, ptab_sweep;                     // [C][W1], [G][W1]
-    DevBuf ptab_t, ptab_sweep_t;                 // the same tables tiled for the trunk kernels (smallnet.h tile_table)
-    DevBuf pmax;                                 // [C] largest magnitude of a cell's row of ptab (trunk_f16l.hip: f16 scale of 3-D layer 2's input)
+    int B = 0;
+    PoseGrid grid, sweep;                        // cond_fn grid, orientation sweep
     DevBuf objpart;                              // 2-D: [max_objects][W1] doubles
     DevBuf objtmp;                               // 2-D: scratch of set_objects (the object encoder's hidden layer, [n_objects][512] doubles)
     std::vector<std::unique_ptr<ObjectTables>> tables;   // 3-D
@@ -110,20 +113,33 @@ struct DgdmGuidance {
         if (fdone) (void)hipEventDestroy(fdone);
         if (fstream) (void)hipStreamDestroy(fstream);
     }
-    int build_pose_table(const std::vector<float> &ori, const std::vector<float> &pos, DevBuf *dst, DevBuf *dst_tiled, hipStream_t s);
+    int build_pose_table(const std::vector<float> &ori, const std::vector<float> &pos, PoseGrid *dst, hipStream_t s);
+    // the first-layer tables and the shape of a launch over `g` for n_chains chains
+    void set_grid(dgdm::TrunkParams *p, const PoseGrid &g, int n_chains) const;
+    int check_objects(const int *oidx, int n_chains) const;
+    // test hook (dgdm_guidance_debug_fps_path): the embedding tables may serve the rows (modes 1-3 force the gather kernels)
+    bool tables_wanted() const { return xtab_enabled && !force_slow_xobj && xobj_mode == 0; }
     int common_pre(const float *x_dev, float t_scaled, const int *objidx_host, int n_chains, hipStream_t s);
     // starts of `n_calls` classifier calls per chain: call k of chain c at starts_host + k * call_stride + c * 2 * rows; on the device the
     // chain's rows of all calls form one run of n_calls * rows rows (row k * rows + r)
     int upload_starts(const int64_t *starts_host, int n_chains, int64_t rows, hipStream_t s, bool need_order = true, int n_calls = 1,
                       int64_t call_stride = 0);
     int ensure_rows(int n_chains, int64_t rows_per_chain);      // grows the per-row device buffers and the pinned staging area
-    // true + p filled when every chain's object has its embedding table in the wanted format: then no per-step gather runs at all
-    int use_xtab(const int *objidx_host, int n_chains, int64_t rows, bool want16, dgdm::TrunkParams *p, bool *ok, hipStream_t s);
+    // the rows' indices into the embedding tables (every chain's object has its table in the wanted format): no per-step gather runs at all
+    int use_xtab(const int *objidx_host, int n_chains, int64_t rows, bool want16, hipStream_t s);
     int build_object(int oi, int slot, hipStream_t s);
     int build_xtab(int oi, hipStream_t s);
     int run_xobj(const int *objidx_host, int n_chains, int64_t rows, bool want16, bool *used16, hipStream_t s);
-    // the embeddings of `n_calls` cond_fn calls at once: afterwards call k reads rows [k * R, (k + 1) * R) of every chain
-    struct Embedded { bool tab = false, used16 = false; int64_t rows_per_chain = 0; };
+    // the embeddings of `n_calls` classifier calls at once (3-D): afterwards call k reads rows [k * rows_per_call, (k + 1) * rows_per_call)
+    // of every chain.  tab: index rows into the objects' embedding tables, else materialised rows; used16: bf16 rows
+    struct Embedded {
+        bool tab = false, used16 = false;
+        int64_t rows_per_chain = 0;
+        void point(dgdm::TrunkParams *p, const DgdmGuidance &g, int call, int64_t rows_per_call) const;
+    };
+    int embed_rows(const int *objidx_host, int n_chains, const int64_t *starts_host, int64_t rows_per_call, int n_calls, int64_t call_stride,
+                   bool want16, Embedded *e, hipStream_t s);
+    // cond_fn's: the rows of the cond_fn grid in the handle's arithmetic, counted towards the XTAB_AFTER policy, one `xobj` profiling region
     int embed(const int *objidx_host, int n_chains, const int64_t *starts_host, int n_calls, int64_t call_stride, Embedded *e, hipStream_t s);
     // what cond_fn's gradient and its forward-only scoring share, up to the trunk launch: common_pre, 3-D: the rows' embeddings (`emb` /
     // `call` as guidance_grad takes them), and the trunk parameters of the cond_fn grid in the float32 form (the caller swaps the weight
@@ -132,19 +148,33 @@ struct DgdmGuidance {
                     int call, dgdm::TrunkParams *p, hipStream_t s);
 };
 
-int DgdmGuidance::build_pose_table(const std::vector<float> &ori, const std::vector<float> &pos, DevBuf *dst, DevBuf *dst_tiled, hipStream_t s) {
+int DgdmGuidance::build_pose_table(const std::vector<float> &ori, const std::vector<float> &pos, PoseGrid *dst, hipStream_t s) {
     const int n = (int)ori.size(), W1 = m->W1;
+    dst->cells = n; dst->tiles_per_b = (n + 31) / 32; dst->rows = (int64_t)B * n;
     DevBuf d_ori, d_pos, d_emb;
     int rc;
     if ((rc = d_ori.upload(ori.data(), sizeof(float) * n))) return rc;
     if ((rc = d_pos.upload(pos.data(), sizeof(float) * 2 * n))) return rc;
     if ((rc = d_emb.alloc(sizeof(float) * 27 * n))) return rc;
-    if ((rc = dst->alloc(sizeof(float) * (size_t)W1 * n))) return rc;
+    if ((rc = dst->tab.alloc(sizeof(float) * (size_t)W1 * n))) return rc;
     if ((rc = pose_embed(d_ori.as<float>(), d_pos.as<float>(), d_emb.as<float>(), n, s))) return rc;
-    if ((rc = linear64(d_emb.as<float>(), nullptr, 27, m->blob64.at(m->off64.w1p_wt), nullptr, nullptr, 1, nullptr, dst->as<float>(), W1, n, 27, W1, ACT_NONE, s))) return rc;
-    if ((rc = dst_tiled->alloc(sizeof(float) * (size_t)W1 * ((n + 31) / 32) * 32))) return rc;
-    if ((rc = tile_table(dst->as<float>(), n, W1, dst_tiled->as<float>(), s))) return rc;
+    if ((rc = linear64(d_emb.as<float>(), nullptr, 27, m->blob64.at(m->off64.w1p_wt), nullptr, nullptr, 1, nullptr, dst->tab.as<float>(), W1, n, 27, W1, ACT_NONE, s))) return rc;
+    if ((rc = dst->tiled.alloc(sizeof(float) * (size_t)W1 * dst->tiles_per_b * 32))) return rc;
+    if ((rc = tile_table(dst->tab.as<float>(), n, W1, dst->tiled.as<float>(), s))) return rc;
     DGDM_HIP_CHECK(hipStreamSynchronize(s));     // temporaries die here
+    return DGDM_OK;
+}
+
+void DgdmGuidance::set_grid(TrunkParams *p, const PoseGrid &g, int n_chains) const {
+    p->Atab = atab.as<float>(); p->Ptab = g.tab.as<float>(); p->PtabT = g.tiled.as<float>(); p->Pmax = g.pmax.as<float>();
+    p->B = B; p->C = g.cells; p->tiles_per_b = g.tiles_per_b; p->ntiles = n_chains * B * g.tiles_per_b; p->R = g.rows;
+    p->xstride = g.rows;                         // 3-D: Embedded::point, afterwards
+}
+
+int DgdmGuidance::check_objects(const int *oidx, int n_chains) const {
+    DGDM_REQUIRE(n_objects > 0, DGDM_EINVAL, "dgdm_guidance_set_objects has not been called");
+    for (int i = 0; i < n_chains; ++i)
+        DGDM_REQUIRE(oidx[i] >= 0 && oidx[i] < n_objects, DGDM_EINVAL, "chain %d refers to object %d of %d", i, oidx[i], n_objects);
     return DGDM_OK;
 }
 
@@ -161,50 +191,48 @@ extern "C" int dgdm_guidance_create(DgdmGuidance **out, DgdmDynamics *model, con
     }
     std::unique_ptr<DgdmGuidance> g(new DgdmGuidance());
     g->m = model; g->cfg = *cfg;
-    g->B = cfg->batch; g->G = cfg->grid_size;
-    const int P = cfg->num_pos;
-    g->C = g->G * P * P;
-    g->R = (int64_t)g->B * g->C; g->Rs = (int64_t)g->B * g->G;
-    g->tiles_per_b = (g->C + 31) / 32; g->sweep_tiles_per_b = (g->G + 31) / 32;
+    g->B = cfg->batch;
+    const int G = cfg->grid_size, P = cfg->num_pos, C = G * P * P;
     // pose grid: torch.meshgrid(linspace(ori), linspace(-1,1,P), linspace(-1,1,P)) 'ij' -> cell = (g*P + px)*P + py  (diffusion.py:478)
-    const std::vector<float> lo = linspace_f32(cfg->ori_lo, cfg->ori_hi, g->G), lp = linspace_f32(-1.f, 1.f, P);
-    std::vector<float> ori(g->C), pos(2 * (size_t)g->C);
-    for (int gi = 0; gi < g->G; ++gi)
+    const std::vector<float> lo = linspace_f32(cfg->ori_lo, cfg->ori_hi, G), lp = linspace_f32(-1.f, 1.f, P);
+    std::vector<float> ori(C), pos(2 * (size_t)C);
+    for (int gi = 0; gi < G; ++gi)
         for (int a = 0; a < P; ++a)
             for (int b = 0; b < P; ++b) {
                 const int c = (gi * P + a) * P + b;
                 ori[c] = lo[gi]; pos[2 * c] = lp[a]; pos[2 * c + 1] = lp[b];
             }
     int rc;
-    if ((rc = g->build_pose_table(ori, pos, &g->ptab, &g->ptab_t, nullptr))) return rc;
+    if ((rc = g->build_pose_table(ori, pos, &g->grid, nullptr))) return rc;
     {   // per-cell magnitude bound of the pose table (built once: the pose grid is fixed)
-        std::vector<float> tab((size_t)g->C * model->W1), mx(g->C, 0.f);
-        DGDM_HIP_CHECK(hipMemcpy(tab.data(), g->ptab.p, tab.size() * sizeof(float), hipMemcpyDeviceToHost));
-        for (int c = 0; c < g->C; ++c)
+        std::vector<float> tab((size_t)C * model->W1), mx(C, 0.f);
+        DGDM_HIP_CHECK(hipMemcpy(tab.data(), g->grid.tab.p, tab.size() * sizeof(float), hipMemcpyDeviceToHost));
+        for (int c = 0; c < C; ++c)
             for (int j = 0; j < model->W1; ++j) mx[c] = std::max(mx[c], std::fabs(tab[(size_t)c * model->W1 + j]));
-        if ((rc = g->pmax.upload(mx.data(), mx.size() * sizeof(float)))) return rc;
+        if ((rc = g->grid.pmax.upload(mx.data(), mx.size() * sizeof(float)))) return rc;
     }
-    std::vector<float> pos0(2 * (size_t)g->G, 0.f);                       // get_convergence_centers: pos = 0 (:511)
-    if ((rc = g->build_pose_table(lo, pos0, &g->ptab_sweep, &g->ptab_sweep_t, nullptr))) return rc;
+    std::vector<float> pos0(2 * (size_t)G, 0.f);                          // get_convergence_centers: pos = 0 (:511)
+    if ((rc = g->build_pose_table(lo, pos0, &g->sweep, nullptr))) return rc;
     if ((rc = g->sweep_ori.upload(lo.data(), lo.size() * sizeof(float)))) return rc;
     const int W1 = model->W1, nc = cfg->max_chains;
     const size_t rows = (size_t)nc * g->B;
+    const int64_t R = g->grid.rows;
     if ((rc = g->V.alloc(rows * 256 * 8)) || (rc = g->genc.alloc(rows * 256 * 8)) || (rc = g->atab.alloc(rows * W1 * 4)) ||
         (rc = g->chainbias.alloc((size_t)nc * W1 * 8)) || (rc = g->timepart.alloc((size_t)W1 * 8)) || (rc = g->ttmp.alloc(768 * 4)) ||
         (rc = g->ttmp64.alloc(512 * 8)) ||
-        (rc = g->partial.alloc(rows * g->tiles_per_b * W1 * 4)) || (rc = g->objdev.alloc(sizeof(TrunkObjective) * nc)) ||
+        (rc = g->partial.alloc(rows * g->grid.tiles_per_b * W1 * 4)) || (rc = g->objdev.alloc(sizeof(TrunkObjective) * nc)) ||
         (rc = g->objidx.alloc(sizeof(int) * nc)))
         return rc;
     if (model->kind == 2) {
         if ((rc = g->objpart.alloc((size_t)std::max(1, cfg->max_objects) * W1 * 8))) return rc;
     } else {
-        if ((rc = g->starts.alloc((size_t)nc * g->R * 2 * sizeof(int))) ||
-            (rc = g->order.alloc((size_t)nc * g->R * sizeof(int))) || (rc = g->xchains.alloc(sizeof(XobjChain) * nc)) ||
-            (rc = g->todo.alloc(((size_t)nc * g->R + 1) * sizeof(int))))
+        if ((rc = g->starts.alloc((size_t)nc * R * 2 * sizeof(int))) ||
+            (rc = g->order.alloc((size_t)nc * R * sizeof(int))) || (rc = g->xchains.alloc(sizeof(XobjChain) * nc)) ||
+            (rc = g->todo.alloc(((size_t)nc * R + 1) * sizeof(int))))
             return rc;
-        g->todo_capacity = (int64_t)nc * g->R;
-        g->pinned_bytes = ((size_t)nc * g->R * 3 + (size_t)nc * (cfg->num_object_points + 1)) * sizeof(int);
-        if ((rc = g->groupoff.alloc((size_t)nc * (cfg->num_object_points + 1) * sizeof(int))) || (rc = g->xidx.alloc((size_t)nc * g->R * sizeof(int))) ||
+        g->todo_capacity = (int64_t)nc * R;
+        g->pinned_bytes = ((size_t)nc * R * 3 + (size_t)nc * (cfg->num_object_points + 1)) * sizeof(int);
+        if ((rc = g->groupoff.alloc((size_t)nc * (cfg->num_object_points + 1) * sizeof(int))) || (rc = g->xidx.alloc((size_t)nc * R * sizeof(int))) ||
             (rc = g->xidxchains.alloc(sizeof(XidxChain) * nc)) || (rc = g->xtabptrs.alloc(sizeof(void *) * nc)))
             return rc;
         DGDM_HIP_CHECK(hipHostMalloc(&g->pinned, g->pinned_bytes, hipHostMallocDefault));
@@ -249,18 +277,18 @@ __global__ void partials_true_units_kernel(float *p, const float *unit, size_t n
 // ([n_chains * B * tiles_per_b][W1], tile = (chain * B + b) * tiles_per_b + cell tile; a tile is 32 consecutive pose cells of one finger).
 extern "C" int dgdm_guidance_debug_partials(DgdmGuidance *g, int n_chains, float *out_dev, int32_t *tiles_per_finger, int32_t *width, void *stream) {
     DGDM_REQUIRE(g && n_chains > 0 && n_chains <= g->cfg.max_chains, DGDM_EINVAL, "dgdm_guidance_debug_partials: bad argument");
-    if (tiles_per_finger) *tiles_per_finger = g->tiles_per_b;
+    if (tiles_per_finger) *tiles_per_finger = g->grid.tiles_per_b;
     if (width) *width = g->m->W1;
     if (out_dev) {
-        const size_t n = (size_t)n_chains * g->B * g->tiles_per_b * g->m->W1;
+        const size_t n = (size_t)n_chains * g->B * g->grid.tiles_per_b * g->m->W1;
         DGDM_HIP_CHECK(hipMemcpyAsync(out_dev, g->partial.p, n * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)stream));
         hipLaunchKernelGGL(partials_true_units_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, out_dev, g->m->z1_unit.as<float>(), n, g->m->W1);
         DGDM_HIP_CHECK(hipGetLastError());
     }
     return DGDM_OK;
 }
-extern "C" int64_t dgdm_guidance_rows(const DgdmGuidance *g) { return g ? g->R : 0; }
-extern "C" int64_t dgdm_guidance_starts_per_call(const DgdmGuidance *g) { return (g && g->m->kind == 3) ? 2 * g->R : 0; }
+extern "C" int64_t dgdm_guidance_rows(const DgdmGuidance *g) { return g ? g->grid.rows : 0; }
+extern "C" int64_t dgdm_guidance_starts_per_call(const DgdmGuidance *g) { return (g && g->m->kind == 3) ? 2 * g->grid.rows : 0; }
 
 // ------------------------------------------------------------------------------------------------ objects
 int DgdmGuidance::build_object(int oi, int slot, hipStream_t s) {
@@ -446,8 +474,6 @@ int DgdmGuidance::common_pre(const float *x_dev, float t_scaled, const int *obji
     if ((rc = m->gripper_forward64(x_dev, m->L, V.as<double>(), genc.as<double>(), rows, s))) return rc;
     if ((rc = m->time_part64(t_scaled, ttmp.as<float>(), ttmp64.as<double>(), timepart.as<double>(), s))) return rc;
     if (m->kind == 2) {
-        for (int i = 0; i < n_chains; ++i)
-            DGDM_REQUIRE(objidx_host[i] >= 0 && objidx_host[i] < n_objects, DGDM_EINVAL, "chain %d refers to object %d of %d", i, objidx_host[i], n_objects);
         DGDM_HIP_CHECK(hipMemcpyAsync(objidx.p, objidx_host, sizeof(int) * n_chains, hipMemcpyHostToDevice, s));   // pageable: staged before return
         if ((rc = gather_add64(objpart.as<double>(), objidx.as<int>(), timepart.as<double>(), chainbias.as<double>(), n_chains, W1, s))) return rc;
         return linear64(nullptr, genc.as<double>(), 256, m->blob64.at(m->off64.w1c_wt), nullptr, chainbias.as<double>(), B, nullptr, atab.as<float>(), W1, rows, 256, W1,
@@ -568,34 +594,23 @@ int DgdmGuidance::upload_starts(const int64_t *starts_host, int n_chains, int64_
     return DGDM_OK;
 }
 
-int DgdmGuidance::use_xtab(const int *objidx_host, int n_chains, int64_t rows, bool want16, TrunkParams *p, bool *ok, hipStream_t s) {
-    *ok = false;
-    if (!xtab_enabled || force_slow_xobj || xobj_mode != 0) return DGDM_OK;
+int DgdmGuidance::use_xtab(const int *objidx_host, int n_chains, int64_t rows, bool want16, hipStream_t s) {
     std::vector<XidxChain> xc(n_chains);
     std::vector<const void *> base(n_chains);
     for (int i = 0; i < n_chains; ++i) {
-        DGDM_REQUIRE(objidx_host[i] >= 0 && objidx_host[i] < n_objects, DGDM_EINVAL, "chain %d refers to object %d of %d", i, objidx_host[i], n_objects);
         const ObjectTables &t = *tables[objidx_host[i]];
-        if (!(want16 ? t.has_x16 : t.has_x)) return DGDM_OK;          // built in the other format (or not at all): gather kernels
         xc[i].fps1 = t.fps1; xc[i].N = cfg.num_object_points; xc[i].m0_only = t.ncr == 0;
         // an object without crowded centres has X[s1][q] = M0[q]: its table is M0 itself (xtab_kernel wrote nothing)
         base[i] = want16 ? (t.ncr == 0 ? (const void *)t.M0_16.p : (const void *)t.X16.p) : (t.ncr == 0 ? (const void *)t.M0.p : (const void *)t.X.p);
     }
     DGDM_HIP_CHECK(hipMemcpyAsync(xidxchains.p, xc.data(), sizeof(XidxChain) * n_chains, hipMemcpyHostToDevice, s));      // pageable: staged before return
     DGDM_HIP_CHECK(hipMemcpyAsync(xtabptrs.p, base.data(), sizeof(void *) * n_chains, hipMemcpyHostToDevice, s));
-    int rc;
-    if ((rc = pn_xidx(xidxchains.as<XidxChain>(), starts.as<int>(), rows, n_chains, xidx.as<int>(), s))) return rc;
-    p->xidx = xidx.as<int>();
-    if (want16) p->xtab16 = xtabptrs.as<const uint32_t *>();
-    else p->xtab = xtabptrs.as<const float *>();
-    *ok = true;
-    return DGDM_OK;
+    return pn_xidx(xidxchains.as<XidxChain>(), starts.as<int>(), rows, n_chains, xidx.as<int>(), s);
 }
 
 int DgdmGuidance::run_xobj(const int *objidx_host, int n_chains, int64_t rows, bool want16, bool *used16, hipStream_t s) {
     std::vector<XobjChain> ch(n_chains);
     for (int i = 0; i < n_chains; ++i) {
-        DGDM_REQUIRE(objidx_host[i] >= 0 && objidx_host[i] < n_objects, DGDM_EINVAL, "chain %d refers to object %d of %d", i, objidx_host[i], n_objects);
         const ObjectTables &t = *tables[objidx_host[i]];
         ch[i].xyz = t.xyz; ch[i].fps1 = t.fps1; ch[i].slot_of_start = nullptr; ch[i].Z = t.Z.as<float>();
         ch[i].fps2 = t.fps2; ch[i].flags = t.flags; ch[i].crowded = t.crowded; ch[i].N = cfg.num_object_points;
@@ -608,7 +623,7 @@ int DgdmGuidance::run_xobj(const int *objidx_host, int n_chains, int64_t rows, b
         int rc = want16 ? xobj16.alloc(nrows * 512) : xobj.alloc(nrows * 256 * 4);
         if (rc) return rc;
     }
-    if (used16) *used16 = want16;
+    *used16 = want16;
     XobjParams xp{};
     xp.chains = xchains.as<XobjChain>(); xp.starts = starts.as<int>(); xp.order = order.as<int>(); xp.xobj = xobj.as<float>();
     xp.xobj16 = want16 ? xobj16.as<uint32_t>() : nullptr;
@@ -636,10 +651,40 @@ int DgdmGuidance::run_xobj(const int *objidx_host, int n_chains, int64_t rows, b
     return pn_xobj(xp, all_fast, s);
 }
 
-// The PointNet++ embeddings of the rows of `n_calls` consecutive cond_fn calls (3-D).  They depend on the FPS start draws and the
-// objects only - not on x - so a whole denoise loop's worth can be made before its first step: one upload and ONE gather launch whose
-// (chain, s1) groups hold the rows of all the calls (the variant's slab is staged once for five times the rows), or - when the objects'
-// embedding tables exist - one index kernel.  Call k then reads rows [k * R, (k + 1) * R) of every chain.
+// The PointNet++ embeddings of the rows of `n_calls` consecutive classifier calls (3-D).  They depend on the FPS start draws and the
+// objects only - not on x - so a whole denoise loop's (or roll-out's) worth can be made before its first step: one upload and ONE gather
+// launch whose (chain, s1) groups hold the rows of all the calls (the variant's slab is staged once for five times the rows), or - when
+// every chain's object has its embedding table in the wanted format (float32, or bf16 operand-order rows: want16) - one index kernel.
+// Call k then reads rows [k * rows_per_call, (k + 1) * rows_per_call) of every chain (Embedded::point).
+int DgdmGuidance::embed_rows(const int *oidx, int n_chains, const int64_t *starts_host, int64_t rows_per_call, int n_calls, int64_t call_stride,
+                             bool want16, Embedded *e, hipStream_t s) {
+    bool tab = tables_wanted();
+    for (int i = 0; i < n_chains && tab; ++i) tab = want16 ? tables[oidx[i]]->has_x16 : tables[oidx[i]]->has_x;   // else: built in the other format, or not at all
+    const int64_t rt = rows_per_call * n_calls;
+    int rc;
+    if ((rc = upload_starts(starts_host, n_chains, rows_per_call, s, !tab, n_calls, call_stride))) return rc;     // host work: overlaps a table build still in flight
+    if ((rc = finish_objects())) return rc;
+    e->tab = tab; e->used16 = want16; e->rows_per_chain = rt;
+    if ((rc = tab ? use_xtab(oidx, n_chains, rt, want16, s) : run_xobj(oidx, n_chains, rt, want16, &e->used16, s))) return rc;
+    DGDM_HIP_CHECK(hipEventRecord(up_consumed, s));          // the index buffers may be overwritten once these kernels are through
+    consumed_recorded = true;
+    return DGDM_OK;
+}
+
+// Points the trunk at call `call`'s rows of the run
+void DgdmGuidance::Embedded::point(TrunkParams *p, const DgdmGuidance &g, int call, int64_t rows_per_call) const {
+    const size_t row0 = (size_t)call * rows_per_call;
+    p->xstride = rows_per_chain;
+    if (tab) {
+        p->xidx = g.xidx.as<int>() + row0;
+        if (used16) p->xtab16 = g.xtabptrs.as<const uint32_t *>();
+        else p->xtab = g.xtabptrs.as<const float *>();
+    } else {
+        p->xobj = g.xobj.as<float>() + row0 * 256;
+        p->xobj16 = used16 ? g.xobj16.as<uint32_t>() + row0 * 128 : nullptr;
+    }
+}
+
 int DgdmGuidance::embed(const int *oidx, int n_chains, const int64_t *starts_host, int n_calls, int64_t call_stride, Embedded *e, hipStream_t s) {
     DGDM_REQUIRE(starts_host, DGDM_EINVAL, "3-D guidance needs the FPS start indices");
     int rc;
@@ -649,8 +694,7 @@ int DgdmGuidance::embed(const int *oidx, int n_chains, const int64_t *starts_hos
     // reference's validation sweep runs 12 objectives x 5 steps (+ the multi-object chains) on the same objects - and it would
     // cost 2 % when every pair brings its own object (bench.py).  So it is built when the call count says the objects are being
     // reused: when the calls since set_objects pass XTAB_AFTER.
-    bool tab = xtab_enabled && !force_slow_xobj && xobj_mode == 0;
-    if (tab) {
+    if (tables_wanted()) {
         const bool crosses = grads_since_set <= XTAB_AFTER && grads_since_set + n_calls > XTAB_AFTER;
         grads_since_set += n_calls;
         if (crosses)
@@ -659,34 +703,21 @@ int DgdmGuidance::embed(const int *oidx, int n_chains, const int64_t *starts_hos
                 if (!(t.has16 ? t.has_x16 : t.has_x) && (rc = build_xtab(i, s))) return rc;
             }
     }
-    for (int i = 0; i < n_chains && tab; ++i) {
-        DGDM_REQUIRE(oidx[i] >= 0 && oidx[i] < n_objects, DGDM_EINVAL, "chain %d refers to object %d of %d", i, oidx[i], n_objects);
-        tab = bf16 ? tables[oidx[i]]->has_x16 : tables[oidx[i]]->has_x;
-    }
-    const int64_t rt = R * n_calls;
-    if ((rc = upload_starts(starts_host, n_chains, R, s, !tab, n_calls, call_stride))) return rc;     // host work: overlaps a table build still in flight
-    if ((rc = finish_objects())) return rc;
-    TrunkParams scratch{};
-    if (tab && (rc = use_xtab(oidx, n_chains, rt, bf16, &scratch, &tab, s))) return rc;
-    e->used16 = false;
-    if (!tab && (rc = run_xobj(oidx, n_chains, rt, bf16, &e->used16, s))) return rc;
-    e->tab = tab; e->rows_per_chain = rt;
-    DGDM_HIP_CHECK(hipEventRecord(up_consumed, s));          // the index buffers may be overwritten once these kernels are through
-    consumed_recorded = true;
+    if ((rc = embed_rows(oidx, n_chains, starts_host, grid.rows, n_calls, call_stride, bf16, e, s))) return rc;
     prof_end(s, DGDM_STAGE_XOBJ, 0.0);
     return DGDM_OK;
 }
 
 int DgdmGuidance::trunk_front(int kind, const float *x_dev, int timestep, const int *oidx, const int64_t *starts_host, int n_chains, const Embedded *emb,
                               int call, TrunkParams *pp, hipStream_t s) {
-    DGDM_REQUIRE(n_objects > 0, DGDM_EINVAL, "dgdm_guidance_set_objects has not been called");
     const float t_scaled = (float)timestep / (float)cfg.num_train_timesteps;      // timesteps.float() / T  (diffusion.py:487,496)
     int rc;
+    if ((rc = check_objects(oidx, n_chains))) return rc;
     prof_begin(s, DGDM_STAGE_GUIDE_MISC);
     if ((rc = common_pre(x_dev, t_scaled, oidx, n_chains, s))) return rc;
     prof_end(s, DGDM_STAGE_GUIDE_MISC, 0.0);
-    TrunkParams &p = *pp;
-    m->fill_trunk(&p);
+    m->fill_trunk(pp);
+    set_grid(pp, grid, n_chains);
     if (kind == 3) {
         Embedded own;
         if (!emb) {
@@ -694,20 +725,8 @@ int DgdmGuidance::trunk_front(int kind, const float *x_dev, int timestep, const 
             emb = &own;
             call = 0;
         }
-        const size_t row0 = (size_t)call * R;
-        p.xstride = emb->rows_per_chain;
-        if (emb->tab) {
-            p.xidx = xidx.as<int>() + row0;
-            if (bf16) p.xtab16 = xtabptrs.as<const uint32_t *>();
-            else p.xtab = xtabptrs.as<const float *>();
-        } else {
-            p.xobj = xobj.as<float>() + row0 * 256;
-            p.xobj16 = emb->used16 ? xobj16.as<uint32_t>() + row0 * 128 : nullptr;
-        }
+        emb->point(pp, *this, call, grid.rows);
     }
-    p.Atab = atab.as<float>(); p.Ptab = ptab.as<float>(); p.PtabT = ptab_t.as<float>(); p.Pmax = pmax.as<float>();
-    p.B = B; p.C = C; p.tiles_per_b = tiles_per_b; p.ntiles = n_chains * B * tiles_per_b; p.R = R;
-    if (kind != 3) p.xstride = R;
     return DGDM_OK;
 }
 
@@ -741,10 +760,10 @@ static int guidance_grad(DgdmGuidance *g, int kind, const float *x_dev, int time
     } else {
         TrunkF16Scales sc;
         g->m->fill_trunk_f16(&p, &sc);   // only the two weight streams differ (+ their scale exponents)
-        if ((rc = trunk_f16l_launch(kind, p, sc, s))) return rc;
+        if ((rc = trunk_f16l_launch(kind, TrunkF16Mode::Grad, p, sc, s))) return rc;
     }
     prof_begin(s, DGDM_STAGE_GUIDE_MISC);
-    rc = dyn_post64(g->m->W1, g->partial.as<float>(), g->tiles_per_b, g->m->blob64.at(g->m->off64.w1c_w), g->m->blob64.at(g->m->off64.g2_w),
+    rc = dyn_post64(g->m->W1, g->partial.as<float>(), g->grid.tiles_per_b, g->m->blob64.at(g->m->off64.w1c_w), g->m->blob64.at(g->m->off64.g2_w),
                     g->m->blob64.at(g->m->off64.g0_w), g->V.as<double>(), grad_dev, n_chains * g->B, g->m->L, s);
     prof_end(s, DGDM_STAGE_GUIDE_MISC, 0.0);
     return rc;
@@ -771,7 +790,7 @@ extern "C" int dgdm_guidance_score(DgdmGuidance *g, const float *x_dev, int time
     DGDM_REQUIRE(n_chains > 0 && n_chains <= g->cfg.max_chains, DGDM_EINVAL, "n_chains %d outside 1..%d", n_chains, g->cfg.max_chains);
     int rc;
     if (!logits_dev) {
-        if ((rc = g->scorelogits.alloc((size_t)n_chains * g->R * 3 * sizeof(float)))) return rc;
+        if ((rc = g->scorelogits.alloc((size_t)n_chains * g->grid.rows * 3 * sizeof(float)))) return rc;
         logits_dev = g->scorelogits.as<float>();
     }
     const std::vector<int> oidx(object_of_chain, object_of_chain + n_chains);
@@ -783,9 +802,9 @@ extern "C" int dgdm_guidance_score(DgdmGuidance *g, const float *x_dev, int time
     } else {
         TrunkF16Scales sc;
         g->m->fill_trunk_f16(&p, &sc);
-        if ((rc = trunk_f16l_forward_launch(kind, p, sc, s))) return rc;
+        if ((rc = trunk_f16l_launch(kind, TrunkF16Mode::Forward, p, sc, s))) return rc;
     }
-    return score_tally(logits_dev, n_chains, g->B, g->C, thr, counts_dev, sums_dev, s);
+    return score_tally(logits_dev, n_chains, g->B, g->grid.cells, thr, counts_dev, sums_dev, s);
 }
 
 // ================================================================================================ the denoise loop as one call
@@ -819,7 +838,7 @@ extern "C" int dgdm_guided_chains_run(DgdmUnet1d *unet, DgdmGuidance *g, const f
     hipLaunchKernelGGL(repeat_rows_kernel, dim3((unsigned)((nx + 255) / 256)), dim3(256), 0, s, noise_dev, g->loopx[0].as<float>(), (int64_t)per_chain, n_chains);
     bool same_scale = true;
     for (int c = 1; c < n_chains; ++c) same_scale = same_scale && scales[c] == scales[0];
-    const int64_t spc = kind == 3 ? 2 * g->R : 0;
+    const int64_t spc = kind == 3 ? 2 * g->grid.rows : 0;
     // 3-D: the embeddings of the rows depend on the draws and the objects, not on x, so those of ALL the steps are made before the
     // first one, in one upload and one gather launch: the (chain, s1) groups then hold n_steps times the rows per slab staged (and
     // per slab read from HBM), and more of them are equal rows computed once.  The host's conversion and sort of the draws runs
@@ -829,10 +848,12 @@ extern "C" int dgdm_guided_chains_run(DgdmUnet1d *unet, DgdmGuidance *g, const f
     DgdmGuidance::Embedded emb;
     std::vector<int> oidx(n_chains * n_grad);
     const int64_t call_stride = (int64_t)n_chains * n_grad * spc;
-    int cpe = kind == 3 ? (int)std::min<int64_t>(n_steps, std::max<int64_t>(1, (((int64_t)1 << 22) - 1) / std::max<int64_t>(1, g->R))) : n_steps;
+    int cpe = kind == 3 ? (int)std::min<int64_t>(n_steps, std::max<int64_t>(1, (((int64_t)1 << 22) - 1) / std::max<int64_t>(1, g->grid.rows))) : n_steps;
     if (const char *e = getenv("DGDM_EMBED_CALLS")) cpe = std::max(1, std::min(cpe, atoi(e)));      // test hook: calls per gather launch
-    if (kind == 3)
+    if (kind == 3) {         // the embeddings are made here, ahead of guidance_grad's own check
         for (int i = 0; i < n_chains * n_grad; ++i) oidx[i] = objectives[i].object;
+        if ((rc = g->check_objects(oidx.data(), n_chains * n_grad))) return rc;
+    }
     for (int si = 0; si < n_steps; ++si) {
         float *x = g->loopx[si & 1].as<float>(), *xn = (si + 1 == n_steps) ? x_out_dev : g->loopx[(si + 1) & 1].as<float>();
         const int t = timesteps[si];
@@ -873,30 +894,22 @@ extern "C" int dgdm_guidance_orientation_sweep(DgdmGuidance *g, const float *x_d
                                                int n_chains, float *logits_dev, void *stream) {
     DGDM_REQUIRE(g && x_dev && object_of_chain && logits_dev, DGDM_EINVAL, "dgdm_guidance_orientation_sweep: null argument");
     DGDM_REQUIRE(n_chains > 0 && n_chains <= g->cfg.max_chains, DGDM_EINVAL, "n_chains %d outside 1..%d", n_chains, g->cfg.max_chains);
-    DGDM_REQUIRE(g->n_objects > 0, DGDM_EINVAL, "dgdm_guidance_set_objects has not been called");
     hipStream_t s = (hipStream_t)stream;
     const int kind = g->m->kind;
     int rc;
+    if ((rc = g->check_objects(object_of_chain, n_chains))) return rc;
     if ((rc = g->common_pre(x_dev, 0.f, object_of_chain, n_chains, s))) return rc;       // timesteps = zeros (:515,521)
     TrunkParams p;
     g->m->fill_trunk(&p);
+    g->set_grid(&p, g->sweep, n_chains);
     if (kind == 3) {
         DGDM_REQUIRE(starts_host, DGDM_EINVAL, "3-D sweep needs the FPS start indices");
         // the sweep stays float32: table rows when the float32 tables exist, the gather kernels otherwise (e.g. a bf16-mode handle)
-        bool tab = g->xtab_enabled && !g->force_slow_xobj && g->xobj_mode == 0;
-        for (int i = 0; i < n_chains && tab; ++i) tab = object_of_chain[i] >= 0 && object_of_chain[i] < g->n_objects && g->tables[object_of_chain[i]]->has_x;
-        if ((rc = g->upload_starts(starts_host, n_chains, g->Rs, s, !tab))) return rc;
-        if ((rc = g->finish_objects())) return rc;
-        if (tab && (rc = g->use_xtab(object_of_chain, n_chains, g->Rs, false, &p, &tab, s))) return rc;
-        if (!tab) {
-            if ((rc = g->run_xobj(object_of_chain, n_chains, g->Rs, false, nullptr, s))) return rc;
-            p.xobj = g->xobj.as<float>();
-        }
-        DGDM_HIP_CHECK(hipEventRecord(g->up_consumed, s));
-        g->consumed_recorded = true;
+        DgdmGuidance::Embedded emb;
+        if ((rc = g->embed_rows(object_of_chain, n_chains, starts_host, g->sweep.rows, 1, 0, false, &emb, s))) return rc;
+        emb.point(&p, *g, 0, g->sweep.rows);
     }
-    p.Atab = g->atab.as<float>(); p.Ptab = g->ptab_sweep.as<float>(); p.PtabT = g->ptab_sweep_t.as<float>(); p.logits = logits_dev;
-    p.B = g->B; p.C = g->G; p.tiles_per_b = g->sweep_tiles_per_b; p.ntiles = n_chains * g->B * g->sweep_tiles_per_b; p.R = g->Rs; p.xstride = g->Rs;
+    p.logits = logits_dev;
     return trunk_launch(kind, false, true, p, s);
 }
 
@@ -914,13 +927,13 @@ extern "C" int dgdm_guidance_rollout(DgdmGuidance *g, const float *x_dev, const 
     DGDM_REQUIRE(!g->f32_mfma, DGDM_EINVAL, "dgdm_guidance_rollout: the float32 MFMA trunk has no per-row pose form (contraction dtypes f32 / f32_f16x3)");
     DGDM_REQUIRE(n_interactions >= 1, DGDM_EINVAL, "dgdm_guidance_rollout: %d interactions (at least 1)", n_interactions);
     DGDM_REQUIRE(n_chains > 0 && n_chains <= g->cfg.max_chains, DGDM_EINVAL, "n_chains %d outside 1..%d", n_chains, g->cfg.max_chains);
-    DGDM_REQUIRE(g->n_objects > 0, DGDM_EINVAL, "dgdm_guidance_set_objects has not been called");
-    hipStream_t s = (hipStream_t)stream;
-    const int kind = g->m->kind, K = n_interactions, W1 = g->m->W1;
-    DGDM_REQUIRE(kind == 2 || starts_host, DGDM_EINVAL, "3-D roll-out needs the FPS start indices");
-    const int64_t Rs = g->Rs, rows = (int64_t)n_chains * Rs;
-    const int ntiles = n_chains * g->B * g->sweep_tiles_per_b;
     int rc;
+    if ((rc = g->check_objects(object_of_chain, n_chains))) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    const int kind = g->m->kind, K = n_interactions, W1 = g->m->W1, G = g->sweep.cells;
+    DGDM_REQUIRE(kind == 2 || starts_host, DGDM_EINVAL, "3-D roll-out needs the FPS start indices");
+    const int64_t Rs = g->sweep.rows, rows = (int64_t)n_chains * Rs;
+    const int ntiles = n_chains * g->B * g->sweep.tiles_per_b;
     if ((rc = g->rollstate.alloc((size_t)rows * 3 * sizeof(double))) || (rc = g->rolltiles.alloc((size_t)ntiles * 32 * W1 * sizeof(float))) ||
         (kind == 3 && (rc = g->rollpmax.alloc((size_t)ntiles * 32 * sizeof(float)))) ||
         (!traj_logits_dev && (rc = g->rolllogits.alloc((size_t)rows * 3 * sizeof(float)))))
@@ -928,34 +941,22 @@ extern "C" int dgdm_guidance_rollout(DgdmGuidance *g, const float *x_dev, const 
     if ((rc = g->common_pre(x_dev, 0.f, object_of_chain, n_chains, s))) return rc;       // t = 0, as the sweep
     TrunkParams p;
     g->m->fill_trunk(&p);
-    bool tab = false;
-    if (kind == 3) {
-        // float32 embeddings through the sweep's path: table rows when the float32 tables exist, the gather kernels otherwise
-        tab = g->xtab_enabled && !g->force_slow_xobj && g->xobj_mode == 0;
-        for (int i = 0; i < n_chains && tab; ++i) tab = object_of_chain[i] >= 0 && object_of_chain[i] < g->n_objects && g->tables[object_of_chain[i]]->has_x;
-        if ((rc = g->upload_starts(starts_host, n_chains, Rs, s, !tab, K, (int64_t)n_chains * 2 * Rs))) return rc;
-        if ((rc = g->finish_objects())) return rc;
-        if (tab && (rc = g->use_xtab(object_of_chain, n_chains, Rs * K, false, &p, &tab, s))) return rc;
-        if (!tab && (rc = g->run_xobj(object_of_chain, n_chains, Rs * K, false, nullptr, s))) return rc;
-        DGDM_HIP_CHECK(hipEventRecord(g->up_consumed, s));
-        g->consumed_recorded = true;
-    }
+    // float32 embeddings through the sweep's path: table rows when the float32 tables exist, the gather kernels otherwise
+    DgdmGuidance::Embedded emb;
+    if (kind == 3 && (rc = g->embed_rows(object_of_chain, n_chains, starts_host, Rs, K, (int64_t)n_chains * 2 * Rs, false, &emb, s))) return rc;
     TrunkF16Scales sc;
     g->m->fill_trunk_f16(&p, &sc);
-    p.Atab = g->atab.as<float>(); p.Ptab = nullptr; p.PtabT = g->rolltiles.as<float>(); p.Pmax = kind == 3 ? g->rollpmax.as<float>() : nullptr;
-    p.B = g->B; p.C = g->G; p.tiles_per_b = g->sweep_tiles_per_b; p.ntiles = ntiles; p.R = Rs; p.xstride = kind == 3 ? Rs * K : Rs;
+    g->set_grid(&p, g->sweep, n_chains);
+    p.Ptab = nullptr; p.PtabT = g->rolltiles.as<float>(); p.Pmax = kind == 3 ? g->rollpmax.as<float>() : nullptr;       // a pose per row
     double *state = g->rollstate.as<double>();
-    if ((rc = rollout_start(g->sweep_ori.as<float>(), n_chains, g->B, g->G, state, left_dev, traj_pose_dev, s))) return rc;
+    if ((rc = rollout_start(g->sweep_ori.as<float>(), n_chains, g->B, G, state, left_dev, traj_pose_dev, s))) return rc;
     g->rolltiles_chains = n_chains;
     for (int k = 0; k < K; ++k) {
-        if ((rc = rollout_pose_table(state, g->m->blob64.at(g->m->off64.w1p_wt), W1, n_chains, g->B, g->G, g->rolltiles.as<float>(), p.Pmax ? g->rollpmax.as<float>() : nullptr, s)))
+        if ((rc = rollout_pose_table(state, g->m->blob64.at(g->m->off64.w1p_wt), W1, n_chains, g->B, G, g->rolltiles.as<float>(), p.Pmax ? g->rollpmax.as<float>() : nullptr, s)))
             return rc;
         p.logits = traj_logits_dev ? traj_logits_dev + (size_t)k * rows * 3 : g->rolllogits.as<float>();
-        if (kind == 3) {
-            if (tab) p.xidx = g->xidx.as<int>() + (size_t)k * Rs;
-            else p.xobj = g->xobj.as<float>() + (size_t)k * Rs * 256;
-        }
-        if ((rc = trunk_f16l_forward_rowpose_launch(kind, p, sc, s))) return rc;
+        if (kind == 3) emb.point(&p, *g, k, Rs);
+        if ((rc = trunk_f16l_launch(kind, TrunkF16Mode::ForwardRowPose, p, sc, s))) return rc;
         if ((rc = rollout_update(p.logits, scale, k, rows, state, left_dev, traj_pose_dev ? traj_pose_dev + (size_t)(k + 1) * rows * 3 : nullptr,
                                  k == K - 1 ? final_dev : nullptr, k == 0 ? first_logits_dev : nullptr, s)))
             return rc;
@@ -969,15 +970,15 @@ extern "C" int dgdm_guidance_rollout(DgdmGuidance *g, const float *x_dev, const 
 extern "C" int dgdm_guidance_debug_rollout_table(DgdmGuidance *g, int n_chains, float *rollout_tiles_dev, float *sweep_tiles_dev,
                                                  int32_t *tiles_per_finger, int32_t *width, void *stream) {
     DGDM_REQUIRE(g && n_chains > 0 && n_chains <= g->cfg.max_chains, DGDM_EINVAL, "dgdm_guidance_debug_rollout_table: bad argument");
-    if (tiles_per_finger) *tiles_per_finger = g->sweep_tiles_per_b;
+    if (tiles_per_finger) *tiles_per_finger = g->sweep.tiles_per_b;
     if (width) *width = g->m->W1;
     const size_t per_tile = (size_t)g->m->W1 * 32 * sizeof(float);
     if (rollout_tiles_dev) {
         DGDM_REQUIRE(n_chains <= g->rolltiles_chains, DGDM_EINVAL, "dgdm_guidance_debug_rollout_table: the last roll-out had %d chains", g->rolltiles_chains);
-        DGDM_HIP_CHECK(hipMemcpyAsync(rollout_tiles_dev, g->rolltiles.p, (size_t)n_chains * g->B * g->sweep_tiles_per_b * per_tile, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+        DGDM_HIP_CHECK(hipMemcpyAsync(rollout_tiles_dev, g->rolltiles.p, (size_t)n_chains * g->B * g->sweep.tiles_per_b * per_tile, hipMemcpyDeviceToDevice, (hipStream_t)stream));
     }
     if (sweep_tiles_dev)
-        DGDM_HIP_CHECK(hipMemcpyAsync(sweep_tiles_dev, g->ptab_sweep_t.p, (size_t)g->sweep_tiles_per_b * per_tile, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+        DGDM_HIP_CHECK(hipMemcpyAsync(sweep_tiles_dev, g->sweep.tiled.p, (size_t)g->sweep.tiles_per_b * per_tile, hipMemcpyDeviceToDevice, (hipStream_t)stream));
     return DGDM_OK;
 }
 

@@ -34,7 +34,7 @@ struct TrunkParams {
     // first-layer tables
     const float  *Atab;       // table mode: [nchain*B][W1]; rows mode: [rows][W1]
     const float  *Ptab;       // [C][W1]  (table mode)
-    const float  *PtabT;      // the same, tiled per 32 cells in operand layout (smallnet.h tile_table); per-row pose mode (trunk_f16l_forward_rowpose_launch): one tile per trunk tile, [ntiles][W1 / 32][4][64] float4
+    const float  *PtabT;      // the same, tiled per 32 cells in operand layout (smallnet.h tile_table); per-row pose mode (TrunkF16Mode::ForwardRowPose): one tile per trunk tile, [ntiles][W1 / 32][4][64] float4
     const float  *Pmax;       // [C] largest magnitude of a cell's row of Ptab (trunk_f16l.hip: the f16 scale of 3-D layer 2's input); may be null elsewhere; per-row pose mode: [ntiles][32], one value per tile row, padding rows included
     const TrunkObjective *obj;// [nchain]
     const float  *rowcoef;    // [nchain][R] or null
@@ -43,6 +43,16 @@ struct TrunkParams {
     int           B, C, tiles_per_b, ntiles;
     int64_t       R;          // rows per chain (B*C in table mode, rows in rows mode)
 };
+
+// Algorithmic FLOPs of one trunk launch, whichever arithmetic carries it (DESIGN_HISTORY.md §5; what the `trunk` profiling stage
+// reports): MFMA layers only, real rows only (the last cell tile of a finger is padded to 32: 1125 cells -> 36 tiles = 1152 issued rows)
+inline double trunk_flops(int kind, const TrunkParams &p, bool rows_mode, bool fwd_only) {
+    const double rows = rows_mode ? (double)p.R : (double)(p.ntiles / (p.tiles_per_b > 0 ? p.tiles_per_b : 1)) * p.C;
+    const double mid = 2.0 * 256 * 256 * p.n_mid;
+    double per_row = (kind == 3) ? (2.0 * 256 * 512 * 2 + mid) : mid;
+    if (!fwd_only) per_row += (kind == 3) ? (2.0 * 256 * 512 + mid) : mid;
+    return rows * per_row;
+}
 
 // kind: 2 | 3.  rows_mode: first-layer pre-activations given per row (general forward API).
 int trunk_launch(int kind, bool rows_mode, bool fwd_only, const TrunkParams &p, hipStream_t s);
@@ -55,13 +65,14 @@ struct TrunkF16Scales {
     float l1_norm1;           // 3-D: largest absolute row sum of layer 1's object-embedding columns (bounds a row of layer 1 from its input)
 };
 // (the weight stream is shared by the workgroup's four waves through LDS: trunk_f16l.hip)
-int trunk_f16l_launch(int kind, const TrunkParams &p, const TrunkF16Scales &sc, hipStream_t s);
-// The forward half alone: the logits of every valid row to p.logits [nchain][R][3]; p.Wbwd, p.obj, p.rowcoef and p.partial are not read.
-int trunk_f16l_forward_launch(int kind, const TrunkParams &p, const TrunkF16Scales &sc, hipStream_t s);
-// The same with a pose per ROW instead of per cell (dgdm_guidance_rollout): p.PtabT = one operand tile per trunk tile,
+// Grad: forward + backward.
+// Forward: the forward half alone: the logits of every valid row to p.logits [nchain][R][3]; p.Wbwd, p.obj, p.rowcoef and p.partial are
+// not read.
+// ForwardRowPose: the same with a pose per ROW instead of per cell (dgdm_guidance_rollout): p.PtabT = one operand tile per trunk tile,
 // [ntiles][W1 / 32][4][64] float4 in tile_table's layout (tile = (chain * B + finger) * tiles_per_b + cell tile), p.Pmax (3-D) =
 // [ntiles][32], padding rows included; p.Ptab is not read.
-int trunk_f16l_forward_rowpose_launch(int kind, const TrunkParams &p, const TrunkF16Scales &sc, hipStream_t s);
+enum class TrunkF16Mode { Grad, Forward, ForwardRowPose };
+int trunk_f16l_launch(int kind, TrunkF16Mode mode, const TrunkParams &p, const TrunkF16Scales &sc, hipStream_t s);
 
 // Roll-out steps around that trunk (rollout.hip).  State [n_chains][B * G][3] doubles = (ori, pos_x, pos_y) in the model's normalised
 // units, row r = g * B + b.

@@ -272,12 +272,6 @@ static int launch(const TrunkParams &p, hipStream_t s) {
 }
 
 int trunk_launch(int kind, bool rows_mode, bool fwd_only, const TrunkParams &p, hipStream_t s) {
-    // algorithmic FLOPs of what this launch executes (DESIGN_HISTORY.md §5): MFMA layers only
-    // real rows only (the last cell tile of a finger is padded to 32: 1125 cells -> 36 tiles = 1152 issued rows)
-    const double rows = rows_mode ? (double)p.R : (double)(p.ntiles / std::max(1, p.tiles_per_b)) * p.C;
-    const double mid = 2.0 * 256 * 256 * p.n_mid;
-    double per_row = (kind == 3) ? (2.0 * 256 * 512 * 2 + mid) : mid;
-    if (!fwd_only) per_row += (kind == 3) ? (2.0 * 256 * 512 + mid) : mid;
     prof_begin(s, DGDM_STAGE_TRUNK);
     int rc;
     if (kind == 2) {
@@ -287,7 +281,7 @@ int trunk_launch(int kind, bool rows_mode, bool fwd_only, const TrunkParams &p, 
         if (rows_mode) rc = fwd_only ? launch<3, true, true>(p, s) : DGDM_EINVAL;
         else rc = fwd_only ? launch<3, false, true>(p, s) : launch<3, false, false>(p, s);
     }
-    prof_end(s, DGDM_STAGE_TRUNK, rows * per_row);
+    prof_end(s, DGDM_STAGE_TRUNK, trunk_flops(kind, p, rows_mode, fwd_only));
     return rc;
 }
 

@@ -613,48 +613,21 @@ __global__ __launch_bounds__(256, 1) void trunk_f16l_kernel(const TrunkParams p,
     }
 }
 
-int trunk_f16l_forward_launch(int kind, const TrunkParams &p, const TrunkF16Scales &sc, hipStream_t s) {
-    if (p.n_mid != (kind == 3 ? 6 : 7) || !p.logits) return DGDM_EINVAL;
+int trunk_f16l_launch(int kind, TrunkF16Mode mode, const TrunkParams &p, const TrunkF16Scales &sc, hipStream_t s) {
+    const bool fwd = mode != TrunkF16Mode::Grad, rowpose = mode == TrunkF16Mode::ForwardRowPose;
+    if (p.n_mid != (kind == 3 ? 6 : 7) || (fwd && !p.logits) || (rowpose && (!p.PtabT || (kind == 3 && !p.Pmax)))) return DGDM_EINVAL;
     const int grid = (p.ntiles + 3) / 4;
     if (grid == 0) return DGDM_OK;
-    const double rows = (double)(p.ntiles / std::max(1, p.tiles_per_b)) * p.C;
-    const double mid = 2.0 * 256 * 256 * p.n_mid;
-    const double per_row = (kind == 3) ? 2.0 * 256 * 512 * 2 + mid : mid;
+    void (*kernel)(const TrunkParams, const TrunkF16Scales);
+    switch (mode) {
+    case TrunkF16Mode::Forward: kernel = kind == 2 ? trunk_f16l_kernel<2, true> : trunk_f16l_kernel<3, true>; break;
+    case TrunkF16Mode::ForwardRowPose: kernel = kind == 2 ? trunk_f16l_kernel<2, true, true> : trunk_f16l_kernel<3, true, true>; break;
+    default: kernel = kind == 2 ? trunk_f16l_kernel<2> : trunk_f16l_kernel<3>; break;
+    }
     prof_begin(s, DGDM_STAGE_TRUNK);
-    if (kind == 2) hipLaunchKernelGGL((trunk_f16l_kernel<2, true>), dim3(grid), dim3(256), 0, s, p, sc);
-    else hipLaunchKernelGGL((trunk_f16l_kernel<3, true>), dim3(grid), dim3(256), 0, s, p, sc);
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(256), 0, s, p, sc);
     DGDM_HIP_CHECK(hipGetLastError());
-    prof_end(s, DGDM_STAGE_TRUNK, rows * per_row);
-    return DGDM_OK;
-}
-
-int trunk_f16l_forward_rowpose_launch(int kind, const TrunkParams &p, const TrunkF16Scales &sc, hipStream_t s) {
-    if (p.n_mid != (kind == 3 ? 6 : 7) || !p.logits || !p.PtabT || (kind == 3 && !p.Pmax)) return DGDM_EINVAL;
-    const int grid = (p.ntiles + 3) / 4;
-    if (grid == 0) return DGDM_OK;
-    const double rows = (double)(p.ntiles / std::max(1, p.tiles_per_b)) * p.C;
-    const double mid = 2.0 * 256 * 256 * p.n_mid;
-    const double per_row = (kind == 3) ? 2.0 * 256 * 512 * 2 + mid : mid;
-    prof_begin(s, DGDM_STAGE_TRUNK);
-    if (kind == 2) hipLaunchKernelGGL((trunk_f16l_kernel<2, true, true>), dim3(grid), dim3(256), 0, s, p, sc);
-    else hipLaunchKernelGGL((trunk_f16l_kernel<3, true, true>), dim3(grid), dim3(256), 0, s, p, sc);
-    DGDM_HIP_CHECK(hipGetLastError());
-    prof_end(s, DGDM_STAGE_TRUNK, rows * per_row);
-    return DGDM_OK;
-}
-
-int trunk_f16l_launch(int kind, const TrunkParams &p, const TrunkF16Scales &sc, hipStream_t s) {
-    if (p.n_mid != (kind == 3 ? 6 : 7)) return DGDM_EINVAL;
-    const int grid = (p.ntiles + 3) / 4;
-    if (grid == 0) return DGDM_OK;
-    const double rows = (double)(p.ntiles / std::max(1, p.tiles_per_b)) * p.C;
-    const double mid = 2.0 * 256 * 256 * p.n_mid;
-    const double per_row = (kind == 3) ? (2.0 * 256 * 512 * 2 + mid) + (2.0 * 256 * 512 + mid) : 2.0 * mid;
-    prof_begin(s, DGDM_STAGE_TRUNK);
-    if (kind == 2) hipLaunchKernelGGL((trunk_f16l_kernel<2>), dim3(grid), dim3(256), 0, s, p, sc);
-    else hipLaunchKernelGGL((trunk_f16l_kernel<3>), dim3(grid), dim3(256), 0, s, p, sc);
-    DGDM_HIP_CHECK(hipGetLastError());
-    prof_end(s, DGDM_STAGE_TRUNK, rows * per_row);
+    prof_end(s, DGDM_STAGE_TRUNK, trunk_flops(kind, p, false, fwd));
     return DGDM_OK;
 }
 

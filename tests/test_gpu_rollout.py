@@ -384,6 +384,40 @@ def test_determinism_and_isolation(dev, name):
         assert torch.equal(got, want)
 
 
+def test_sweep_and_rollout_agree_on_every_embedding_path(dev):
+    """3-D: the orientation sweep and the roll-out give the same bits whichever way the rows' embeddings are made - the (chain, s1)-group
+    gather kernel (modes 0 on a fresh handle and 3), the per-row table kernel (2), per-row FPS (1), and the per-object embedding tables
+    (5: the index kernel over Rs * K rows, call k reading xidx + k * Rs).  Shapes of 3d_pad: K = 3 calls (the per-call row offset), 2
+    chains (the chain stride), G = 7 (padding rows); the second object is the duplicate-point cloud of test_xobj_kernels_agree."""
+    kind, B, G, nc, K, L, sd, _, x, Rs, starts = inputs("3d_pad")
+    dup = synth.synth_object_3d(32).clone()
+    dup[9] = dup[400]
+    dup[10] = dup[400]
+    objs = torch.stack([synth.synth_object_3d(50), dup]).to(dev)
+    oc = [c % 2 for c in range(nc)]
+    xd = x.to(dev)
+    gd = make_handle("3d_pad")
+    gd.set_objects(objs)
+
+    def record():
+        return [gd.sweep(xd, oc, starts[0]).cpu()] + [t.cpu() for t in gd.rollout(xd, oc, STD[kind], K, starts=starts, want_trajectory=True)]
+
+    res = {}
+    for mode in (0, 3, 2, 1):
+        gd.debug_fps_path(mode)
+        res[mode] = record()
+    gd.debug_fps_path(5)                         # the next set_objects builds the embedding tables right away
+    gd.set_objects(objs)
+    res[5] = record()
+    other = gd.sweep(xd, oc, starts[1]).cpu()
+    gd.debug_fps_path(0)
+    for mode in (3, 2, 1, 5):
+        for i, (got, want) in enumerate(zip(res[mode], res[0])):
+            assert torch.equal(got, want), (mode, i)
+    assert float(res[0][0].abs().max()) > 0 and float(res[0][5].abs().max()) > 0
+    assert not torch.equal(other, res[5][0])     # the draws are read
+
+
 def test_refusals(dev):
     kind, B, G, nc, K, L, sd, objs, x, Rs, starts = inputs("2d_pad")
     xd = x.to(dev)
