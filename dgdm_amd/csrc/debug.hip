@@ -53,8 +53,7 @@ extern "C" int dgdm_debug_pointnet_indices(DgdmDynamics *m, const float *xyz_dev
     DGDM_REQUIRE(N >= 128 && N <= 1024 && perm_len > 0 && perm_len <= N, DGDM_EINVAL, "dgdm_debug_pointnet_indices: N %d / perm_len %d unsupported", N, perm_len);
     hipStream_t s = (hipStream_t)stream;
     int rc;
-    if ((rc = pn_fps_table(xyz_dev, N, N, 512, fps512_dev, nullptr, s))) return rc;
-    if ((rc = pn_fps_table(xyz_dev, N, N, 128, fps128_dev, fps128_flags_dev, s))) return rc;
+    if ((rc = pn_fps_tables(xyz_dev, N, N, fps512_dev, fps128_dev, fps128_flags_dev, s))) return rc;
     return pn_debug_indices(xyz_dev, N, m->pn(), perm_dev, perm_len, ball1_dev, ball2_dev, ball2_count_dev, crowded_dev, s);
 }
 

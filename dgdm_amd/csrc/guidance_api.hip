@@ -66,8 +66,9 @@ struct DgdmGuidance {
     DevBuf pool_crowded, pool_clist, pool_off, pool_pairs, pool_rank, pool_F1, pool_U;   // [n_objects] x the light build stages' outputs (built by one launch per stage)
     DevBuf pool_xyz, pool_fps1, pool_fps2, pool_flags, pool_ncr;   // [n_objects] x per-object FPS tables (ObjectTables point into these), crowded-centre counts
     DevBuf tmpY[NBUILD], tmpL2[NBUILD], vlist;      // 3-D table-build temporaries of the heavy stages (per build stream)
-    hipStream_t bstream[NBUILD] = {}, fstream = nullptr;    // fstream: sa2's FPS table, beside the builds
-    hipEvent_t bev[NBUILD] = {}, bstart = nullptr, fstart = nullptr, fdone = nullptr, ldone = nullptr;      // ldone: the batched light build stages
+    DevBuf tmpShare[NBUILD];                        // float32 build: the selection stage's outputs (pointnet.h L2Share), carved out of one buffer
+    hipStream_t bstream[NBUILD] = {};
+    hipEvent_t bev[NBUILD] = {}, bstart = nullptr, pooled = nullptr, ldone = nullptr;      // pooled: the objects' coordinates are in the pool; ldone: the batched light build stages
     // V, genc, chainbias, timepart: float64 (smallnet.h linear64: per-finger / per-chain quantities are evaluated in double precision,
     // so the A table carries one float32 rounding); ttmp64: scratch of the time encoder
     DevBuf V, genc, atab, chainbias, timepart, ttmp, ttmp64, partial, objdev, objidx, xobj, xobj16, starts, order, xchains, todo, groupoff;
@@ -109,9 +110,7 @@ struct DgdmGuidance {
         }
         if (bstart) (void)hipEventDestroy(bstart);
         if (ldone) (void)hipEventDestroy(ldone);
-        if (fstart) (void)hipEventDestroy(fstart);
-        if (fdone) (void)hipEventDestroy(fdone);
-        if (fstream) (void)hipStreamDestroy(fstream);
+        if (pooled) (void)hipEventDestroy(pooled);
     }
     int build_pose_table(const std::vector<float> &ori, const std::vector<float> &pos, PoseGrid *dst, hipStream_t s);
     // the first-layer tables and the shape of a launch over `g` for n_chains chains
@@ -129,9 +128,11 @@ struct DgdmGuidance {
     int use_xtab(const int *objidx_host, int n_chains, int64_t rows, bool want16, hipStream_t s);
     int build_object(int oi, int slot, hipStream_t s);
     int build_xtab(int oi, hipStream_t s);
-    int run_xobj(const int *objidx_host, int n_chains, int64_t rows, bool want16, bool *used16, hipStream_t s);
+    // via_tab: the group kernel gathered only the chains that need it (see there) and the trunk reads every chain through xtabptrs / xidx
+    int run_xobj(const int *objidx_host, int n_chains, int64_t rows, bool want16, bool *used16, bool *via_tab, hipStream_t s);
     // the embeddings of `n_calls` classifier calls at once (3-D): afterwards call k reads rows [k * rows_per_call, (k + 1) * rows_per_call)
-    // of every chain.  tab: index rows into the objects' embedding tables, else materialised rows; used16: bf16 rows
+    // of every chain.  tab: index rows into per-chain tables (the objects' embedding tables, or run_xobj's mix of M0 and gathered rows), else
+    // materialised rows; used16: bf16 rows
     struct Embedded {
         bool tab = false, used16 = false;
         int64_t rows_per_chain = 0;
@@ -323,11 +324,28 @@ int DgdmGuidance::build_object(int oi, int slot, hipStream_t s) {
         // (pointnet64.hip); the max stages (T5, T7) are exact as they are
         const PnWeights64 w64 = m->pn64();
         if ((rc = pn_pairs64(xyz, N, reinterpret_cast<const double *>(U), w64, pairs, off, tY.as<float>(), s))) return rc;                 // T4
+        // T5 / T6 of the crowded centres once per DISTINCT first-64 selection: Z[v][c] depends on v only through which points of c's ball
+        // come first in fps1[v], and many variants select the same set.  The test hook's dense build (l2_gather_mode) and clouds the
+        // crowded-centre kernel does not take (N > 512) compute every (variant, centre) row from its own L2 row.
+        const bool shared = !l2_gather_mode && N <= 512;
+        L2Share sh{};
+        if (shared) {
+            const size_t NN = (size_t)N * N;
+            if ((rc = tmpShare[slot].alloc(NN * 64 + NN + NN * sizeof(short) + NN * sizeof(int) + (2 * (size_t)N + 4) * sizeof(int)))) return rc;
+            char *b = static_cast<char *>(tmpShare[slot].p);
+            sh.sel = reinterpret_cast<unsigned char *>(b); b += NN * 64;
+            sh.items = reinterpret_cast<int *>(b); b += NN * sizeof(int);
+            sh.coff = reinterpret_cast<int *>(b); b += N * sizeof(int);
+            sh.ccnt = reinterpret_cast<int *>(b); b += N * sizeof(int);
+            sh.nitems = reinterpret_cast<int *>(b); b += 4 * sizeof(int);
+            sh.rep = reinterpret_cast<short *>(b); b += NN * sizeof(short);
+            sh.cnt = reinterpret_cast<unsigned char *>(b);
+        }
         if ((rc = pn_l2(xyz, N, w, t.fps1, vlist.as<int>(), N, tY.as<float>(), tL2.as<float>(), t.clist, t.clist + N,
-                        off, rank, false, s, l2_gather_mode ? 0 : 1))) return rc;                  // T5
-        if ((rc = pn_z64(xyz, N, N, w64, tL2.as<float>(), t.Z.as<float>(), t.clist, t.clist + N, s))) return rc;                // T6
+                        off, rank, false, s, shared ? 1 : 0, shared ? &sh : nullptr))) return rc;  // T5
+        if ((rc = pn_z64(xyz, N, N, w64, tL2.as<float>(), t.Z.as<float>(), t.clist, t.clist + N, s, sh.items, sh.nitems))) return rc;   // T6
+        if (shared && N > 1 && (rc = pn_zfill(N, N, t.Z.as<float>(), t.clist, t.clist + N, sh.rep, s))) return rc;
     }
-    DGDM_HIP_CHECK(hipStreamWaitEvent(s, fdone, 0));          // fps2 (sa2's FPS table) is built beside the other stages, on its own stream
     if ((rc = pn_m0(t.fps2, t.crowded, N, t.Z.as<float>(), t.M0.as<float>(), t.cl2.as<int>(), t.cnt2.as<int>(), z16,
                     bf16 ? t.M0_16.as<uint32_t>() : nullptr, t.clist, t.clist + N, t.cl2s.as<int>(), t.cl2o.as<unsigned short>(), s))) return rc;          // T7
     if ((rc = pn_pcf(t.fps1, t.cnt2.as<int>(), t.flags, N, t.pcf.as<int>(), s))) return rc;
@@ -393,18 +411,12 @@ extern "C" int dgdm_guidance_set_objects(DgdmGuidance *g, const float *objects_d
             (rc = g->pool_pairs.alloc(no * N * N * sizeof(int))) || (rc = g->pool_rank.alloc(no * N * N * sizeof(short))) ||
             (rc = g->pool_F1.alloc(no * N * 128 * 8)) || (rc = g->pool_U.alloc(no * N * 128 * 8)))
             return rc;
-        if (!g->fstream) {
-            DGDM_HIP_CHECK(hipStreamCreateWithFlags(&g->fstream, hipStreamNonBlocking));
-            DGDM_HIP_CHECK(hipEventCreateWithFlags(&g->fstart, hipEventDisableTiming));
-            DGDM_HIP_CHECK(hipEventCreateWithFlags(&g->fdone, hipEventDisableTiming));
-        }
+        if (!g->pooled) DGDM_HIP_CHECK(hipEventCreateWithFlags(&g->pooled, hipEventDisableTiming));
         DGDM_HIP_CHECK(hipMemcpyAsync(g->pool_xyz.p, objects_dev, no * N * 3 * 4, hipMemcpyDeviceToDevice, s));
-        // sa2's FPS table (fps2) is only read by the last build stage (m0): it runs on its own stream beside sa1's table and the builds
-        DGDM_HIP_CHECK(hipEventRecord(g->fstart, s));
-        DGDM_HIP_CHECK(hipStreamWaitEvent(g->fstream, g->fstart, 0));
-        if ((rc = pn_fps_table(g->pool_xyz.as<float>(), N, N, 128, g->pool_fps2.as<int>(), g->pool_flags.as<int>(), g->fstream, n_objects))) return rc;
-        DGDM_HIP_CHECK(hipEventRecord(g->fdone, g->fstream));
-        if ((rc = pn_fps_table(g->pool_xyz.as<float>(), N, N, 512, g->pool_fps1.as<int>(), nullptr, s, n_objects))) return rc;
+        DGDM_HIP_CHECK(hipEventRecord(g->pooled, s));
+        // sa2's FPS table is the first 128 columns of sa1's (same clouds, same starts): one pass writes both and the tie flags
+        if ((rc = pn_fps_tables(g->pool_xyz.as<float>(), N, N, g->pool_fps1.as<int>(), g->pool_fps2.as<int>(), g->pool_flags.as<int>(), s, n_objects)))
+            return rc;
         for (int i = 0; i < n_objects; ++i) {
             ObjectTables &t = *g->tables[i];
             t.xyz = g->pool_xyz.as<float>() + (size_t)i * N * 3; t.fps1 = g->pool_fps1.as<int>() + (size_t)i * N * 512;
@@ -416,7 +428,7 @@ extern "C" int dgdm_guidance_set_objects(DgdmGuidance *g, const float *objects_d
         // of its time), on the first build stream, beside the FPS tables; the heavy per-object stages (T4 .. T7) follow on the build streams
         {
             hipStream_t ls = g->bstream[0];
-            DGDM_HIP_CHECK(hipStreamWaitEvent(ls, g->fstart, 0));          // the objects' coordinates are in the pool
+            DGDM_HIP_CHECK(hipStreamWaitEvent(ls, g->pooled, 0));          // the objects' coordinates are in the pool
             const PnWeights w = g->m->pn();
             if ((rc = pn_crowd(g->pool_xyz.as<float>(), N, w, g->pool_crowded.as<int>(), g->pool_clist.as<int>(), g->pool_clist.as<int>() + N,
                                g->pool_off.as<int>(), g->pool_pairs.as<int>(), g->pool_rank.as<short>(), ls, g->pool_ncr.as<int>(), n_objects)))
@@ -444,7 +456,6 @@ extern "C" int dgdm_guidance_set_objects(DgdmGuidance *g, const float *objects_d
             DGDM_HIP_CHECK(hipEventRecord(g->bev[i], g->bstream[i]));
             DGDM_HIP_CHECK(hipStreamWaitEvent(s, g->bev[i], 0));
         }
-        DGDM_HIP_CHECK(hipStreamWaitEvent(s, g->fdone, 0));
         // which objects may use the table of FPS(128) sequences (no order-dependent selection anywhere); crowded-centre counts:
         // copied to pinned memory behind an event, read by finish_objects() when first needed
         prof_end(s, DGDM_STAGE_TABLES, 0.0);
@@ -608,7 +619,8 @@ int DgdmGuidance::use_xtab(const int *objidx_host, int n_chains, int64_t rows, b
     return pn_xidx(xidxchains.as<XidxChain>(), starts.as<int>(), rows, n_chains, xidx.as<int>(), s);
 }
 
-int DgdmGuidance::run_xobj(const int *objidx_host, int n_chains, int64_t rows, bool want16, bool *used16, hipStream_t s) {
+int DgdmGuidance::run_xobj(const int *objidx_host, int n_chains, int64_t rows, bool want16, bool *used16, bool *via_tab, hipStream_t s) {
+    *via_tab = false;
     std::vector<XobjChain> ch(n_chains);
     for (int i = 0; i < n_chains; ++i) {
         const ObjectTables &t = *tables[objidx_host[i]];
@@ -641,12 +653,32 @@ int DgdmGuidance::run_xobj(const int *objidx_host, int n_chains, int64_t rows, b
     }
     DGDM_HIP_CHECK(hipMemcpyAsync(xchains.p, ch.data(), sizeof(XobjChain) * n_chains, hipMemcpyHostToDevice, s));     // pageable: staged before return
     if (groups) {
-        xp.group_off = groupoff.as<int>(); xp.nchain = n_chains; xp.group_N = cfg.num_object_points; xp.total_items = n_chains * xp.group_N; xp.use_table = 1;
-        std::vector<int> rank(n_chains);
-        for (int i = 0; i < n_chains; ++i) rank[i] = i;
+        // A chain whose object has no crowded centre and no tie-flagged start has M0[q] as the embedding of every row (use_xtab): it gets no
+        // work items and its block of xobj is never written.  The trunk then reads EVERY chain of the launch through a table and a row
+        // index: such a chain M0 at q = fps1[s1][s2], a gathered chain its own block of xobj at the row's number.  Not when the test hook
+        // asks for materialised rows (modes 1-3), nor for the bf16 trunk on float32 rows (it has no float32 table form).
+        const bool by_index = tables_wanted() && (want16 || !bf16);
+        std::vector<int> rank;
+        std::vector<XidxChain> xc(n_chains);
+        std::vector<const void *> base(n_chains);
+        for (int i = 0; i < n_chains; ++i) {
+            const ObjectTables &t = *tables[objidx_host[i]];
+            const bool m0_only = by_index && t.ncr == 0 && t.fast_ok;
+            if (!m0_only) rank.push_back(i);
+            xc[i].fps1 = m0_only ? t.fps1 : nullptr; xc[i].N = cfg.num_object_points; xc[i].m0_only = 1;
+            base[i] = m0_only ? (want16 ? (const void *)t.M0_16.p : (const void *)t.M0.p)
+                              : (want16 ? (const void *)(xobj16.as<uint32_t>() + (size_t)i * rows * 128) : (const void *)(xobj.as<float>() + (size_t)i * rows * 256));
+        }
+        xp.group_off = groupoff.as<int>(); xp.nchain = n_chains; xp.group_N = cfg.num_object_points; xp.use_table = 1;
+        xp.total_items = (int)rank.size() * xp.group_N;
         std::stable_sort(rank.begin(), rank.end(), [&](int a, int b) { return ch[a].ncr > ch[b].ncr; });
-        for (int i = 0; i < n_chains; ++i) xp.chain_of_rank[i] = (unsigned char)rank[i];
-        return pn_xobj_groups(xp, s);
+        for (size_t i = 0; i < rank.size(); ++i) xp.chain_of_rank[i] = (unsigned char)rank[i];
+        int rc = pn_xobj_groups(xp, s);
+        if (rc || !by_index) return rc;
+        *via_tab = true;
+        DGDM_HIP_CHECK(hipMemcpyAsync(xidxchains.p, xc.data(), sizeof(XidxChain) * n_chains, hipMemcpyHostToDevice, s));      // pageable: staged before return
+        DGDM_HIP_CHECK(hipMemcpyAsync(xtabptrs.p, base.data(), sizeof(void *) * n_chains, hipMemcpyHostToDevice, s));
+        return pn_xidx(xidxchains.as<XidxChain>(), starts.as<int>(), rows, n_chains, xidx.as<int>(), s);
     }
     return pn_xobj(xp, all_fast, s);
 }
@@ -665,7 +697,7 @@ int DgdmGuidance::embed_rows(const int *oidx, int n_chains, const int64_t *start
     if ((rc = upload_starts(starts_host, n_chains, rows_per_call, s, !tab, n_calls, call_stride))) return rc;     // host work: overlaps a table build still in flight
     if ((rc = finish_objects())) return rc;
     e->tab = tab; e->used16 = want16; e->rows_per_chain = rt;
-    if ((rc = tab ? use_xtab(oidx, n_chains, rt, want16, s) : run_xobj(oidx, n_chains, rt, want16, &e->used16, s))) return rc;
+    if ((rc = tab ? use_xtab(oidx, n_chains, rt, want16, s) : run_xobj(oidx, n_chains, rt, want16, &e->used16, &e->tab, s))) return rc;
     DGDM_HIP_CHECK(hipEventRecord(up_consumed, s));          // the index buffers may be overwritten once these kernels are through
     consumed_recorded = true;
     return DGDM_OK;

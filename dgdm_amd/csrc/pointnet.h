@@ -81,7 +81,7 @@ struct XtabObj {
 // builds X (or X16) for one object; start points whose FPS(128) sequence is order-dependent (flags) get their rows from a per-row FPS
 int pn_xtab(const XtabObj &o, bool bf16, hipStream_t s);
 // per reference row the row of X its embedding is: idx[chain][r] = s1 * N + q (or q alone for chains whose object has no crowded centre:
-// their table is M0 itself)
+// their table is M0 itself; or the row's own number r for a chain with fps1 = null: its "table" is a block of materialised rows)
 struct XidxChain { const int *fps1; int N; int m0_only; };
 int pn_xidx(const XidxChain *chains_dev, const int *starts, int64_t R, int nchain, int *idx, hipStream_t s);
 
@@ -91,18 +91,32 @@ int pn_ball_rows(const float *xyz, const float *centres, int B, int N, int S, fl
 int pn_sqdist_rows(const float *src, const float *dst, int B, int S, int N, float *out, hipStream_t s);
 int pn_index_rows(const float *points, const int *idx, int B, int N, int M, int C, float *out, hipStream_t s);
 
+// The float32 table build computes each DISTINCT first-64 selection of a crowded centre once (l2sel_kernel): Z[v][c] depends on the variant v
+// only through which points of c's ball come first in the order fps1[v], as a set.  Per crowded centre (position ci in clist) and variant:
+struct L2Share {
+    unsigned char *sel;           // [N][nv][64] the selection: rows of the centre's block of the pair list (K <= 255; l2c_kernel's bytes)
+    unsigned char *cnt;           // [N][nv] their number
+    short *rep;                   // [N][nv] the smallest variant whose selection is the same set (a ball of K > 255 points: v itself)
+    int   *items;                 // [N * nv] (ci << 16 | v) for every v >= 1 with rep == v; a centre's entries lie together, ascending in v
+    int   *coff, *ccnt;           // [N] a centre's first entry and number of entries
+    int   *nitems;                // device count of the list (zeroed by pn_l2 before the selection stage)
+};
 int pn_fps_table(const float *xyz, int N, int nv, int npoint, int *out, int *flags, hipStream_t s, int nobj = 1);
+// sa1's and sa2's tables from ONE pass of 512 iterations per start: fps1 [nobj][nv][512], fps2 [nobj][nv][128] = its first 128 columns,
+// flags [nobj][nv] = the 128-sequence was order-dependent
+int pn_fps_tables(const float *xyz, int N, int nv, int *fps1, int *fps2, int *flags, hipStream_t s, int nobj = 1);
 int pn_sa1(const float *xyz, int N, const PnWeights &w, float *F1, hipStream_t s, int nobj = 1);      // nobj > 1: pools [nobj][N][..]
 // crowded/clist/ncr: centres whose ball holds > 64 points; off [N+1], pairs [<= N*N], rank [N][N]: the in-radius pair list (T4/T5)
 int pn_crowd(const float *xyz, int N, const PnWeights &w, int *crowded, int *clist, int *ncr, int *off, int *pairs, short *rank, hipStream_t s,
              int *ncr_copy = nullptr, int nobj = 1);
 // Y16 (optional): write bf16 operand-order rows there INSTEAD of the float32 rows (bf16 mode)
 int pn_pairs(const float *xyz, int N, const float *U, const PnWeights &w, const int *pairs, const int *off, float *Y, uint32_t *Y16, hipStream_t s);
-// crowded_mode 1: the variants >= 1 of the crowded centres by l2c_kernel (needs vlist = identity: slot v = start index v, and K <= 255
-// points per ball); 0: l2_kernel throughout
+// crowded_mode 1: the variants >= 1 of the crowded centres by l2c_kernel (needs vlist = identity: slot v = start index v, N <= 1024 and
+// nv <= 512); 0: l2_kernel throughout.  Float32 rows in crowded mode need `share`: the selection stage fills it and only the rows
+// L2[v][c] of its list (rep == v) are written - hand the list to pn_z64 and fill the other Z rows in with pn_zfill.
 int pn_l2(const float *xyz, int N, const PnWeights &w, const int *fps1, const int *vlist, int nv, const float *Y, float *L2,
           const int *clist, const int *ncr, const int *off, const short *rank, bool bf16 /* Y and L2 are bf16 operand-order rows */, hipStream_t s,
-          int crowded_mode = 0);
+          int crowded_mode = 0, const L2Share *share = nullptr);
 // bf16 mode T6: bf16 contraction from L2_16 rows; writes the float32 rows and their bf16 copy
 int pn_z16(const float *xyz, int N, int nv, const PnWeights &w, const uint32_t *L2_16, float *Z, uint32_t *Z16, const int *clist, const int *ncr,
            hipStream_t s);
@@ -110,7 +124,11 @@ int pn_z16(const float *xyz, int N, int nv, const PnWeights &w, const uint32_t *
 // F1_64 [N][128] doubles (sa1 features); U is then linear64(F1_64) -> U64 [N][128] doubles
 int pn_sa1_64(const float *xyz, int N, float r1sq, const PnWeights64 &w, double *F1_64, hipStream_t s, int nobj = 1);
 int pn_pairs64(const float *xyz, int N, const double *U64, const PnWeights64 &w, const int *pairs, const int *off, float *Y, hipStream_t s);
-int pn_z64(const float *xyz, int N, int nv, const PnWeights64 &w, const float *L2, float *Z, const int *clist, const int *ncr, hipStream_t s);
+// items / nitems (L2Share): behind slot 0's N rows only the listed (variant, crowded centre) rows instead of all of them
+int pn_z64(const float *xyz, int N, int nv, const PnWeights64 &w, const float *L2, float *Z, const int *clist, const int *ncr, hipStream_t s,
+           const int *items = nullptr, const int *nitems = nullptr);
+// Z[v][c] = Z[rep][c] for every crowded centre and variant with rep != v (behind pn_z64 on the same stream)
+int pn_zfill(int N, int nv, float *Z, const int *clist, const int *ncr, const short *rep, hipStream_t s);
 int pn_m0(const int *fps2, const int *crowded, int N, const float *Z0, float *M0, int *cl2, int *cnt2, const uint32_t *Z0_16, uint32_t *M0_16,
           const int *clist, const int *ncr, int *cl2s, unsigned short *cl2o, hipStream_t s);
 // lanes per row for an object with `ncr` crowded centres (0 = the group kernel cannot hold its slab: use the per-row kernels):

@@ -66,8 +66,11 @@ __device__ __forceinline__ void wave_argmax(float &v, int &i) {
 // distinct coordinates used up, so the reference falls back to position 0 of its own ordering).
 // A sequence without such an event is the same for every ordering of the cloud, up to which of
 // several bit-identical points represents a coordinate.
-template <int PPL, bool TIES>
-__device__ bool fps_wave(const float *lx, const float *ly, const float *lz, int M, int start, int npoint, int *out, int lane) {
+// DUAL: the choices depend neither on TIES nor on npoint, so the sequence of npoint2 <= npoint points from the same start is this
+// one's prefix: it goes to out2 as well, and the TIES verdict is the shorter sequence's (its tests stop at iteration npoint2 - 2).
+template <int PPL, bool TIES, bool DUAL = false>
+__device__ bool fps_wave(const float *lx, const float *ly, const float *lz, int M, int start, int npoint, int *out, int lane,
+                         int *out2 = nullptr, int npoint2 = 0) {
     float px[PPL], py[PPL], pz[PPL], dist[PPL];
 #pragma unroll
     for (int i = 0; i < PPL; ++i) {
@@ -79,7 +82,10 @@ __device__ bool fps_wave(const float *lx, const float *ly, const float *lz, int 
     int far = start;
     bool ambiguous = false;
     for (int it = 0; it < npoint; ++it) {
-        if (lane == 0) out[it] = far;
+        if (lane == 0) {
+            out[it] = far;
+            if (DUAL && it < npoint2) out2[it] = far;
+        }
         const float cx = lx[far], cy = ly[far], cz = lz[far];
         float bv = -2.f;
         int bi = 0;
@@ -91,7 +97,7 @@ __device__ bool fps_wave(const float *lx, const float *ly, const float *lz, int 
         }
         wave_argmax(bv, bi);
         far = bi;
-        if (TIES && it + 1 < npoint) {
+        if (TIES && it + 1 < (DUAL ? npoint2 : npoint)) {
             const float wx = lx[far], wy = ly[far], wz = lz[far];
             bool t = bv == 0.f;
 #pragma unroll
@@ -105,20 +111,27 @@ __device__ bool fps_wave(const float *lx, const float *ly, const float *lz, int 
 // ------------------------------------------------------------------------------------------------ T1
 // fps[obj][v][0..npoint) for v = 0..nv-1 (start index v) on cloud xyz[obj] [N][3]; flags[obj][v] (optional) = selection was order-dependent.
 // All objects of a set_objects call go in one launch: the 512 dependent iterations are latency bound, so the more waves the better.
+// out2 (with flags): sa2's table fps2[obj][v][0..npoint2) from the same pass - the first npoint2 entries of each sequence - and the
+// flags are those of the npoint2-sequence.
 __global__ __launch_bounds__(256) void fps_table_kernel(const float *__restrict__ xyz, int N, int nv, int npoint, int *__restrict__ out,
-                                                        int *__restrict__ flags) {
+                                                        int *__restrict__ flags, int *__restrict__ out2, int npoint2) {
     extern __shared__ float lds[];
     float *lx = lds, *ly = lds + N, *lz = lds + 2 * N;
     // blockIdx.y = object: clouds, tables and flags of the objects lie back to back
     xyz += (size_t)blockIdx.y * N * 3;
     out += (size_t)blockIdx.y * nv * npoint;
     if (flags) flags += (size_t)blockIdx.y * nv;
+    if (out2) out2 += (size_t)blockIdx.y * nv * npoint2;
     for (int i = threadIdx.x; i < N; i += blockDim.x) { lx[i] = xyz[3 * i]; ly[i] = xyz[3 * i + 1]; lz[i] = xyz[3 * i + 2]; }
     __syncthreads();
     const int v = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
     if (v >= nv) return;
     bool amb;
-    if (flags) {
+    if (out2) {
+        amb = N <= 512 ? fps_wave<8, true, true>(lx, ly, lz, N, v, npoint, out + (size_t)v * npoint, lane, out2 + (size_t)v * npoint2, npoint2)
+                       : fps_wave<16, true, true>(lx, ly, lz, N, v, npoint, out + (size_t)v * npoint, lane, out2 + (size_t)v * npoint2, npoint2);
+        if (lane == 0) flags[v] = amb ? 1 : 0;
+    } else if (flags) {
         amb = N <= 512 ? fps_wave<8, true>(lx, ly, lz, N, v, npoint, out + (size_t)v * npoint, lane)
                        : fps_wave<16, true>(lx, ly, lz, N, v, npoint, out + (size_t)v * npoint, lane);
         if (lane == 0) flags[v] = amb ? 1 : 0;
@@ -456,11 +469,122 @@ __device__ __forceinline__ void l2c_reduce(const uint32_t *ych, const unsigned c
     if (sg == 0) *reinterpret_cast<u4 *>(dst + fl * 4) = best;
 }
 
-// one crowded centre c, the variants of share blockIdx.y
-template <bool BF16>
-__device__ __forceinline__ void l2c_centre(int c, int N, const int *__restrict__ fps1 /*[N][512]*/, int nv, const uint32_t *__restrict__ Y,
+// T5's selection stage of the float32 build: one workgroup per crowded centre, ALL variants.  Each variant's first-64 selection (the
+// code of l2c_centre's selection phase), its membership mask over the centre's ball (256 bits: K <= 255), rep[v] = the smallest variant
+// with an equal mask (whole masks compared; the hash only pre-filters) and the list of (centre, variant) pairs with rep == v, v >= 1.
+// Equal sets give equal bits: l2c_reduce takes an unsigned maximum, which does not depend on order or multiplicity.
+constexpr int L2S_THREADS = 1024;
+__global__ __launch_bounds__(L2S_THREADS) void l2sel_kernel(int N, const int *__restrict__ fps1 /*[N][512]*/, int nv, const int *__restrict__ clist,
+                                                            const int *__restrict__ ncr, const int *__restrict__ off,
+                                                            const short *__restrict__ rank, const L2Share sh) {
+    __shared__ short rks[1024];
+    __shared__ uint32_t mask[512][8];
+    __shared__ uint32_t hash[512];
+    __shared__ int selw[L2S_THREADS / 64][64];
+    __shared__ int wsum[L2S_THREADS / 64], base_s;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, nwave = L2S_THREADS / 64;
+    const int n = *ncr;
+    for (int ci = blockIdx.x; ci < n; ci += gridDim.x) {
+        const int c = clist[ci];
+        const int K = off[c + 1] - off[c];
+        short *repg = sh.rep + (size_t)ci * nv;
+        if (K > 255) {
+            // a ball with more points than a byte can index: no sharing, every variant is its own representative (l2c_centre selects itself)
+            for (int v = tid; v < nv; v += L2S_THREADS) repg[v] = (short)v;
+            if (tid == 0) {
+                base_s = atomicAdd(sh.nitems, nv - 1);
+                sh.coff[ci] = base_s; sh.ccnt[ci] = nv - 1;
+            }
+            __syncthreads();
+            for (int v = 1 + tid; v < nv; v += L2S_THREADS) sh.items[base_s + v - 1] = (ci << 16) | v;
+            __syncthreads();
+            continue;
+        }
+        for (int i = tid; i < N; i += L2S_THREADS) rks[i] = rank[(size_t)c * N + i];
+        __syncthreads();
+        // (the 512 candidates of the next variant are loaded while the current one is scanned, as in l2c_centre)
+        int pv[8], pn[8];
+#pragma unroll
+        for (int i = 0; i < 8; ++i) pn[i] = wave < nv ? fps1[(size_t)wave * 512 + 64 * i + lane] : 0;
+        for (int v = wave; v < nv; v += nwave) {
+#pragma unroll
+            for (int i = 0; i < 8; ++i) pv[i] = pn[i];
+            const int vn = v + nwave;
+            if (vn < nv) {
+#pragma unroll
+                for (int i = 0; i < 8; ++i) pn[i] = fps1[(size_t)vn * 512 + 64 * i + lane];
+            }
+            if (lane < 8) mask[v][lane] = 0u;
+            int cnt = 0;
+#pragma unroll
+            for (int i = 0; i < 8; ++i) {                                 // l2_select on the registers
+                if (cnt >= 64) break;
+                const int r = rks[pv[i]];
+                const bool in = r >= 0;
+                const unsigned long long m = __ballot(in);
+                const int pos = cnt + __popcll(m & ((1ull << lane) - 1ull));
+                if (in && pos < 64) selw[wave][pos] = r;
+                cnt += __popcll(m);
+            }
+            cnt = min(cnt, 64);
+            __builtin_amdgcn_wave_barrier();
+            const int r = selw[wave][lane < cnt ? lane : max(cnt - 1, 0)] & 255;
+            if (lane < cnt) atomicOr(&mask[v][r >> 5], 1u << (r & 31));
+            sh.sel[((size_t)ci * nv + v) * 64 + lane] = (unsigned char)r;
+            if (lane == 0) sh.cnt[(size_t)ci * nv + v] = (unsigned char)cnt;
+            __builtin_amdgcn_wave_barrier();
+        }
+        __syncthreads();
+        uint32_t mine[8];
+        const int v = tid;                                               // nv <= 512 < L2S_THREADS: a thread per variant
+        if (v < nv) {
+            uint32_t h = 0x811c9dc5u;
+#pragma unroll
+            for (int i = 0; i < 8; ++i) { mine[i] = mask[v][i]; h = (h ^ mine[i]) * 0x01000193u; }
+            hash[v] = h;
+        }
+        __syncthreads();
+        bool isrep = false;
+        if (v < nv) {
+            const uint32_t hv = hash[v];
+            int rep = v;
+            for (int u = 0; u < v; ++u) {
+                if (hash[u] == hv && rep == v) {
+                    bool eq = true;
+#pragma unroll
+                    for (int i = 0; i < 8; ++i) eq = eq && mask[u][i] == mine[i];
+                    if (eq) rep = u;
+                }
+            }
+            repg[v] = (short)rep;
+            isrep = rep == v && v >= 1;
+        }
+        const unsigned long long m = __ballot(isrep);
+        if (lane == 0) wsum[wave] = __popcll(m);
+        __syncthreads();
+        if (tid == 0) {
+            int tot = 0;
+            for (int w = 0; w < nwave; ++w) tot += wsum[w];
+            base_s = atomicAdd(sh.nitems, tot);
+            sh.coff[ci] = base_s; sh.ccnt[ci] = tot;
+        }
+        __syncthreads();
+        if (isrep) {
+            int pre = 0;
+            for (int w = 0; w < wave; ++w) pre += wsum[w];
+            sh.items[base_s + pre + __popcll(m & ((1ull << lane) - 1ull))] = (ci << 16) | v;
+        }
+        __syncthreads();                                                  // the LDS arrays are reused by the next centre
+    }
+}
+
+// one crowded centre c (position ci in clist), the variants of share blockIdx.y: a quarter of the variant range, or - REPS, the float32
+// build - a quarter of the centre's representatives (objects differ from 1 % to 97 % distinct selections: variant ranges would be
+// unbalanced), whose selections l2sel_kernel has made
+template <bool BF16, bool REPS>
+__device__ __forceinline__ void l2c_centre(int c, int ci, int N, const int *__restrict__ fps1 /*[N][512]*/, int nv, const uint32_t *__restrict__ Y,
                                            uint32_t *__restrict__ L2 /*[nv][N][W]*/, const int *__restrict__ off, const short *__restrict__ rank,
-                                           int (*selw)[64]) {
+                                           int (*selw)[64], const L2Share &sh) {
     constexpr int W = BF16 ? 128 : 256;                           // dwords per row of Y / L2
     extern __shared__ uint32_t l2c_lds[];
     short *rks = reinterpret_cast<short *>(l2c_lds);              // [1024]
@@ -471,14 +595,26 @@ __device__ __forceinline__ void l2c_centre(int c, int N, const int *__restrict__
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nwave = L2C_THREADS / 64;
     // blockIdx.y: this workgroup's share of the variants (an object has ~40 crowded centres: one workgroup per centre leaves five CUs
     // of six idle, and the reduction is bound by the LDS bandwidth of the CU it runs on; staging the block of Y once per share is cheap)
-    const int vlo = 1 + (int)(((int64_t)(nv - 1) * blockIdx.y) / gridDim.y), vhi = 1 + (int)(((int64_t)(nv - 1) * (blockIdx.y + 1)) / gridDim.y);
+    // the work of this share: entries [vlo, vhi) of the variant range, or of the centre's list of representatives
+    const int *vl = nullptr;
+    int vlo, vhi;
+    if (REPS) {
+        const int nrep = sh.ccnt[ci];
+        vl = sh.items + sh.coff[ci];
+        vlo = (int)(((int64_t)nrep * blockIdx.y) / gridDim.y); vhi = (int)(((int64_t)nrep * (blockIdx.y + 1)) / gridDim.y);
+        if (vhi <= vlo) return;                                   // workgroup-uniform
+    } else {
+        vlo = 1 + (int)(((int64_t)(nv - 1) * blockIdx.y) / gridDim.y); vhi = 1 + (int)(((int64_t)(nv - 1) * (blockIdx.y + 1)) / gridDim.y);
+    }
+    auto variant = [&](int k) { return REPS ? (vl[k] & 0xffff) : k; };
     for (int i = threadIdx.x; i < N; i += L2C_THREADS) rks[i] = rank[(size_t)c * N + i];
     __syncthreads();
     if (K > 255) {
         // a ball with more points than a byte can index (never on the shipped 512-point clouds): gather from global memory as
         // l2_kernel does, W / 64 dwords per lane
         constexpr int D = W / 64;
-        for (int v = vlo + wave; v < vhi; v += nwave) {
+        for (int k = vlo + wave; k < vhi; k += nwave) {
+            const int v = variant(k);
             const int cnt = l2_select(rks, fps1 + (size_t)v * 512, 512, selw[wave], lane);
             uint32_t best[D];
 #pragma unroll
@@ -499,7 +635,14 @@ __device__ __forceinline__ void l2c_centre(int c, int N, const int *__restrict__
     // ---- the first-64 selection of every variant (slot v reads the cloud in the order fps1[v])
     // (the 512 candidates of the next variant are loaded while the current one is scanned: alone in its CU's LDS, the workgroup
     //  has only its own 8 waves to hide the L2 latency of those loads)
-    {
+    if (REPS) {
+        // made by l2sel_kernel: 64 bytes (16 dwords) per representative
+        for (int i = threadIdx.x; i < (vhi - vlo) * 16; i += L2C_THREADS) {
+            const int v = variant(vlo + i / 16), part = i % 16;
+            reinterpret_cast<uint32_t *>(sel)[v * 16 + part] = reinterpret_cast<const uint32_t *>(sh.sel)[((size_t)ci * nv + v) * 16 + part];
+        }
+        for (int k = vlo + threadIdx.x; k < vhi; k += L2C_THREADS) { const int v = variant(k); cnts[v] = sh.cnt[(size_t)ci * nv + v]; }
+    } else {
         int pv[8], pn[8];
         const int v0 = vlo + wave;
 #pragma unroll
@@ -540,7 +683,8 @@ __device__ __forceinline__ void l2c_centre(int c, int N, const int *__restrict__
         for (int i = threadIdx.x; i < pieces; i += L2C_THREADS)
             *reinterpret_cast<uint4 *>(ych + (size_t)i * 4) = *reinterpret_cast<const uint4 *>(Yc + (size_t)(i / lpr) * W + f0 + (i % lpr) * 4);
         __syncthreads();
-        for (int v = vlo + wave; v < vhi; v += nwave) {
+        for (int k = vlo + wave; k < vhi; k += nwave) {
+            const int v = variant(k);
             uint32_t *dst = L2 + ((size_t)v * N + c) * W + f0;
             const unsigned char *sv = sel + (size_t)v * 64;
             const int cnt = cnts[v];
@@ -558,15 +702,15 @@ __device__ __forceinline__ void l2c_centre(int c, int N, const int *__restrict__
 // variants of share blockIdx.y.  The number of crowded centres is device data (0 .. N): the host launches 64 x 4 workgroups - one per
 // CU, ONE round for any count - instead of one workgroup per possible centre (N x shares workgroups of 16 waves and 150 KB of LDS,
 // each of which needs a whole free CU to find out that it has nothing to do: 3072 of them cost more than the 240 that had work).
-template <bool BF16>
+template <bool BF16, bool REPS>
 __global__ __launch_bounds__(L2C_THREADS, 1) void l2c_kernel(int N, const int *__restrict__ fps1 /*[N][512]*/, int nv, const uint32_t *__restrict__ Y,
                                                              uint32_t *__restrict__ L2 /*[nv][N][W]*/, const int *__restrict__ clist,
                                                              const int *__restrict__ ncr, const int *__restrict__ off,
-                                                             const short *__restrict__ rank) {
+                                                             const short *__restrict__ rank, const L2Share sh) {
     __shared__ int selw[L2C_THREADS / 64][64];
     const int n = *ncr;
     for (int ci = blockIdx.x; ci < n; ci += gridDim.x) {
-        l2c_centre<BF16>(clist[ci], N, fps1, nv, Y, L2, off, rank, selw);
+        l2c_centre<BF16, REPS>(clist[ci], ci, N, fps1, nv, Y, L2, off, rank, selw, sh);
         __syncthreads();                                          // the LDS areas are reused by the next centre
     }
 }
@@ -1287,6 +1431,7 @@ __global__ __launch_bounds__(256) void xidx_kernel(const XidxChain *__restrict__
     if (w >= total) return;
     const int chain = (int)(w / R);
     const XidxChain ch = chains[chain];
+    if (!ch.fps1) { idx[w] = (int)(w - (int64_t)chain * R); return; }      // a gathered chain: its table is its own block of rows
     const int s1 = starts[2 * w], s2 = starts[2 * w + 1];
     const int q = ch.fps1[(size_t)s1 * 512 + s2];
     idx[w] = ch.m0_only ? q : s1 * ch.N + q;
@@ -1399,7 +1544,14 @@ int pn_index_rows(const float *points, const int *idx, int B, int N, int M, int 
 
 // ------------------------------------------------------------------------------------------------ host side
 int pn_fps_table(const float *xyz, int N, int nv, int npoint, int *out, int *flags, hipStream_t s, int nobj) {
-    hipLaunchKernelGGL(fps_table_kernel, dim3((nv + 3) / 4, nobj), dim3(256), (size_t)3 * N * sizeof(float), s, xyz, N, nv, npoint, out, flags);
+    hipLaunchKernelGGL(fps_table_kernel, dim3((nv + 3) / 4, nobj), dim3(256), (size_t)3 * N * sizeof(float), s, xyz, N, nv, npoint, out, flags,
+                       (int *)nullptr, 0);
+    DGDM_HIP_CHECK(hipGetLastError());
+    return DGDM_OK;
+}
+
+int pn_fps_tables(const float *xyz, int N, int nv, int *fps1, int *fps2, int *flags, hipStream_t s, int nobj) {
+    hipLaunchKernelGGL(fps_table_kernel, dim3((nv + 3) / 4, nobj), dim3(256), (size_t)3 * N * sizeof(float), s, xyz, N, nv, 512, fps1, flags, fps2, 128);
     DGDM_HIP_CHECK(hipGetLastError());
     return DGDM_OK;
 }
@@ -1427,34 +1579,61 @@ int pn_crowd(const float *xyz, int N, const PnWeights &w, int *crowded, int *cli
 }
 
 int pn_l2c(int N, const int *fps1, int nv, const float *Y, float *L2, const int *clist, const int *ncr, const int *off, const short *rank, bool bf16,
-           hipStream_t s) {
+           hipStream_t s, const L2Share *share) {
     static bool attr_set = false;
     const size_t lds = (size_t)(512 + 512 * 16 + 128) * 4 + L2C_YBYTES;
     if (!attr_set) {
-        DGDM_HIP_CHECK(hipFuncSetAttribute((const void *)l2c_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        DGDM_HIP_CHECK(hipFuncSetAttribute((const void *)l2c_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        DGDM_HIP_CHECK(hipFuncSetAttribute((const void *)l2c_kernel<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        DGDM_HIP_CHECK(hipFuncSetAttribute((const void *)l2c_kernel<true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         attr_set = true;
     }
+    DGDM_REQUIRE(bf16 || share, DGDM_EINVAL, "pn_l2: the float32 crowded mode needs the selection stage's buffers");
     // 64 x 4 = 256 workgroups, one per CU (150 KB of LDS each): ONE round whatever the number of crowded centres is (0 .. N: a few
     // objects of a batch have every centre crowded and carry most of the build's work), and 160 busy CUs at the typical 40
     constexpr int split = 4, gx = 64;
     const dim3 grid(std::min(N, gx), std::min(split, std::max(nv - 1, 1)));
-    if (bf16) hipLaunchKernelGGL(l2c_kernel<true>, grid, dim3(L2C_THREADS), lds, s, N, fps1, nv, reinterpret_cast<const uint32_t *>(Y),
-                                 reinterpret_cast<uint32_t *>(L2), clist, ncr, off, rank);
-    else hipLaunchKernelGGL(l2c_kernel<false>, grid, dim3(L2C_THREADS), lds, s, N, fps1, nv, reinterpret_cast<const uint32_t *>(Y),
-                            reinterpret_cast<uint32_t *>(L2), clist, ncr, off, rank);
+    if (bf16) {
+        hipLaunchKernelGGL((l2c_kernel<true, false>), grid, dim3(L2C_THREADS), lds, s, N, fps1, nv, reinterpret_cast<const uint32_t *>(Y),
+                           reinterpret_cast<uint32_t *>(L2), clist, ncr, off, rank, L2Share{});
+    } else {
+        // the selection stage (one workgroup per crowded centre, all variants), then the representatives only
+        DGDM_HIP_CHECK(hipMemsetAsync(share->nitems, 0, sizeof(int), s));
+        // (a workgroup per possible centre: two of them fit a CU, so ONE round for any count; the surplus ones read the count and leave)
+        hipLaunchKernelGGL(l2sel_kernel, dim3(std::min(N, 512)), dim3(L2S_THREADS), 0, s, N, fps1, nv, clist, ncr, off, rank, *share);
+        hipLaunchKernelGGL((l2c_kernel<false, true>), grid, dim3(L2C_THREADS), lds, s, N, fps1, nv, reinterpret_cast<const uint32_t *>(Y),
+                           reinterpret_cast<uint32_t *>(L2), clist, ncr, off, rank, *share);
+    }
+    DGDM_HIP_CHECK(hipGetLastError());
+    return DGDM_OK;
+}
+
+// Z[v][c] = Z[rep][c] where another variant stands for (v, c): one wave per 1 KiB row.  A representative's row is never written here.
+__global__ __launch_bounds__(256) void zfill_kernel(int N, int nv, float *__restrict__ Z, const int *__restrict__ clist, const int *__restrict__ ncr,
+                                                    const short *__restrict__ rep) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int64_t total = (int64_t)*ncr * nv;
+    for (int64_t w = (int64_t)blockIdx.x * 4 + wave; w < total; w += (int64_t)gridDim.x * 4) {
+        const int v = (int)(w % nv), r = rep[w];
+        if (r == v) continue;
+        const int c = clist[w / nv];
+        reinterpret_cast<float4 *>(Z + ((size_t)v * N + c) * 256)[lane] = reinterpret_cast<const float4 *>(Z + ((size_t)r * N + c) * 256)[lane];
+    }
+}
+
+int pn_zfill(int N, int nv, float *Z, const int *clist, const int *ncr, const short *rep, hipStream_t s) {
+    hipLaunchKernelGGL(zfill_kernel, dim3(2048), dim3(256), 0, s, N, nv, Z, clist, ncr, rep);
     DGDM_HIP_CHECK(hipGetLastError());
     return DGDM_OK;
 }
 
 int pn_l2(const float *xyz, int N, const PnWeights &w, const int *fps1, const int *vlist, int nv, const float *Y, float *L2,
-          const int *clist, const int *ncr, const int *off, const short *rank, bool bf16, hipStream_t s, int crowded_mode) {
+          const int *clist, const int *ncr, const int *off, const short *rank, bool bf16, hipStream_t s, int crowded_mode, const L2Share *share) {
     const dim3 g0(1, (N + 3) / 4), g1((unsigned)(((nv - 1 + 3) / 4) * ((N + 7) / 8) * 8));   // g1: worst case (every centre crowded)
     if (crowded_mode == 1 && N <= 1024 && nv <= 512) {            // slot 0 here, slots >= 1 of the crowded centres by l2c_kernel
         if (bf16) hipLaunchKernelGGL(l2_kernel<true>, g0, dim3(256), 0, s, xyz, N, w.r2sq, fps1, vlist, nv, Y, L2, 0, clist, ncr, off, rank);
         else hipLaunchKernelGGL(l2_kernel<false>, g0, dim3(256), 0, s, xyz, N, w.r2sq, fps1, vlist, nv, Y, L2, 0, clist, ncr, off, rank);
         DGDM_HIP_CHECK(hipGetLastError());
-        return nv > 1 ? pn_l2c(N, fps1, nv, Y, L2, clist, ncr, off, rank, bf16, s) : DGDM_OK;
+        return nv > 1 ? pn_l2c(N, fps1, nv, Y, L2, clist, ncr, off, rank, bf16, s, share) : DGDM_OK;
     }
     if (bf16) {
         hipLaunchKernelGGL(l2_kernel<true>, g0, dim3(256), 0, s, xyz, N, w.r2sq, fps1, vlist, nv, Y, L2, 0, clist, ncr, off, rank);

@@ -182,16 +182,19 @@ __global__ __launch_bounds__(256, 2) void pair64_kernel(const float *__restrict_
 // Z[row][256] = float32( ReLU(W3'[:,3:] L2[row] + W3'[:,0:3] xyz_c + b3') ),  row = slot * N + c, all rows in ONE launch:
 // items 0 .. N-1 are slot 0's rows (every centre), item N + j is (variant 1 + j / ncr, crowded centre clist[j % ncr]).  The item count
 // is device data: a bounded grid whose waves stride over the 16-row tiles (a worst-case grid is 4096 workgroups of which ~330 find work).
+// With `list` (the float32 build's representatives, pointnet.h L2Share) item N + j is instead the (variant, centre) pair list[j] =
+// (position in clist << 16 | variant), j < *nlist: the only rows of L2 behind slot 0's that exist.
 // (Round 5, tried: two tiles per wave against one pass over the weight image - half the L2 traffic per FLOP, one wave per SIMD with
 //  256 accumulator registers: 232 us per object instead of 143, a single wave does not hide the latency of the stream.)
 __global__ __launch_bounds__(256, 2) void z64_kernel(const float *__restrict__ xyz, int N, int nv, const float *__restrict__ L2,
                                                   const double *__restrict__ img, const double *__restrict__ w3x /*[3][256]*/,
                                                   const double *__restrict__ bias, float *__restrict__ Z,
-                                                  const int *__restrict__ clist, const int *__restrict__ ncr) {
+                                                  const int *__restrict__ clist, const int *__restrict__ ncr,
+                                                  const int *__restrict__ list, const int *__restrict__ nlist) {
     const int lane = threadIdx.x & 63, n = lane & 15, kq = lane >> 4;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int ncrv = nv > 1 ? *ncr : 0;
-    const int items = N + (nv - 1) * ncrv;                 // <= nv * N
+    const int items = N + (list ? (nv > 1 ? *nlist : 0) : (nv - 1) * ncrv);                 // <= nv * N
     struct D2 { double lo, hi; };
     const wrsrc_t rs = weight_rsrc(reinterpret_cast<const float4 *>(img), 512 * 1024);
 #pragma nounroll
@@ -199,8 +202,9 @@ __global__ __launch_bounds__(256, 2) void z64_kernel(const float *__restrict__ x
         asm volatile("" ::: "memory");                     // keeps the loop-invariant bias / coordinate-weight loads inside (hoisted they spill)
         const int item = min(tile * 16 + n, items - 1);
         const int j = item - N;
-        const int c = j < 0 ? item : clist[j % ncrv];
-        const int row = j < 0 ? c : (1 + j / ncrv) * N + c;
+        const int pk = (j >= 0 && list) ? list[j] : 0;
+        const int c = j < 0 ? item : clist[list ? pk >> 16 : j % ncrv];
+        const int row = j < 0 ? c : (list ? (pk & 0xffff) : 1 + j / ncrv) * N + c;
         const double x = xyz[3 * c], y = xyz[3 * c + 1], z = xyz[3 * c + 2];
         const float4 *src = reinterpret_cast<const float4 *>(L2 + (size_t)row * 256 + kq * 64);
         f64x4 acc[16];
@@ -268,10 +272,11 @@ int pn_pairs64(const float *xyz, int N, const double *U64, const PnWeights64 &w,
     return DGDM_OK;
 }
 
-int pn_z64(const float *xyz, int N, int nv, const PnWeights64 &w, const float *L2, float *Z, const int *clist, const int *ncr, hipStream_t s) {
+int pn_z64(const float *xyz, int N, int nv, const PnWeights64 &w, const float *L2, float *Z, const int *clist, const int *ncr, hipStream_t s,
+           const int *items, const int *nitems) {
     const int64_t tiles = ((int64_t)nv * N + 15) / 16;     // worst case (every centre crowded)
     hipLaunchKernelGGL(z64_kernel, dim3((unsigned)std::min<int64_t>((tiles + 3) / 4, PN64_GRID)), dim3(256), 0, s, xyz, N, nv, L2, w.sa3_w_img, w.sa3_wx,
-                       w.sa3_b, Z, clist, ncr);
+                       w.sa3_b, Z, clist, ncr, items, nitems);
     DGDM_HIP_CHECK(hipGetLastError());
     return DGDM_OK;
 }

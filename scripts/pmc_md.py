@@ -30,7 +30,7 @@ print("Counters are sums over the launches the pass saw (`n`).  `SQ_WAVE_CYCLES`
 print("## Derived\n")
 print("| kernel | MFMA pipe busy = MFMA_BUSY / (1024 SIMDs x GUI_ACTIVE / 8) | other VALU per MFMA | VALU per LDS instruction | WAIT_ANY / WAVE_CYCLES | WAIT_INST_ANY / WAVE_CYCLES | LDS instruction cycles (4 per instruction) + bank-conflict cycles / (GUI_ACTIVE / 8 x 256 CUs) |")
 print("|---|---|---|---|---|---|---|")
-for k in ("trunk_f16l_kernel<3>", "ub_layer_kernel", "xobj_rows_kernel<false>", "z64_kernel", "l2c_kernel<false>", "fps_table_kernel", "sa1_64_kernel", "m0_kernel"):
+for k in ("trunk_f16l_kernel<3>", "ub_layer_kernel", "xobj_rows_kernel<false>", "z64_kernel", "l2c_kernel<false, true>", "l2sel_kernel", "fps_table_kernel", "sa1_64_kernel", "m0_kernel"):
     a = agg.get(k)
     if not a:
         continue
