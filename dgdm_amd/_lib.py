@@ -34,6 +34,12 @@ class TrainGroups(C.Structure):
     _fields_ = [("t_index_dev", C.c_void_p), ("t_values_dev", C.c_void_p), ("n_t", C.c_int32), ("rows_per_object", C.c_int32)]
 
 
+class DynamicsStore(C.Structure):
+    _fields_ = [("ctrl_dev", C.c_void_p), ("object_dev", C.c_void_p), ("scores_dev", C.c_void_p), ("ori_dev", C.c_void_p), ("pos_dev", C.c_void_p),
+                ("object_of_sample_host", C.c_void_p), ("n_samples", C.c_int64), ("n_objects", C.c_int64), ("cells", C.c_int32),
+                ("n_ctrl", C.c_int32), ("n_object_points", C.c_int32), ("fingers_3d", C.c_int32)]
+
+
 class GuidanceConfig(C.Structure):
     _fields_ = [("batch", C.c_int32), ("grid_size", C.c_int32), ("num_pos", C.c_int32), ("ori_lo", C.c_float),
                 ("ori_hi", C.c_float), ("max_chains", C.c_int32), ("num_train_timesteps", C.c_int32),
@@ -103,6 +109,8 @@ PROTOTYPES = {
     "dgdm_trainer2d_running_stats": (C.c_int, [_P, _P, C.c_int64, C.c_int, _P]),
     "dgdm_trainer2d_export": (C.c_int, [_P, C.c_int, C.POINTER(Tensor), C.c_int]),
     "dgdm_trainer2d_steps": (C.c_int64, [_P]),
+    "dgdm_dynamics_batch_rows": (C.c_int, [C.POINTER(DynamicsStore), _P, C.c_int, _P, _P, _P, _P, _P, _P, _P]),
+    "dgdm_class_agreement": (C.c_int, [_P, _P, C.c_int64, C.POINTER(C.c_float), _P, _P]),
     "dgdm_unet_trainer_create": (C.c_int, [C.POINTER(_P), C.POINTER(Tensor), C.c_int, C.c_int, C.POINTER(C.c_int32), C.c_int, C.c_int, C.c_int, C.c_int,
                                            C.c_float, C.c_float, C.c_float, C.c_float]),
     "dgdm_unet_trainer_destroy": (None, [_P]),

@@ -69,6 +69,7 @@ class DynamicsDataset(Dataset):
         self.gripper_box = gripper_box or (GRIPPER_BOX_3D if fingers_3d else GRIPPER_BOX_2D)
         self.object_box = object_box or (OBJECT_BOX_3D if fingers_3d else OBJECT_BOX_2D)
         self.object_max_num_vertices, self.object_mesh_dir, self.object_pts = object_max_num_vertices, object_mesh_dir, {}
+        self.object_name_of = {}     # 3-D: file index -> the name its cloud is cached under, for every file read so far (device_dataset.py)
         self.data_files = sorted(os.path.join(root, f) for root, _, files in os.walk(dataset_dir) for f in files if f.endswith('.npz'))
         self.mesh_pts = _mesh_clouds(object_mesh_dir, object_max_num_vertices) if fingers_3d and object_mesh_dir and os.path.isdir(object_mesh_dir) else {}
 
@@ -79,7 +80,7 @@ class DynamicsDataset(Dataset):
         d = np.load(self.data_files[idx], allow_pickle=True)['arr_0'].item()
         scores = np.stack([d['delta_theta'] / self.std[0], d['delta_pos'][:, 0] / self.std[1], d['delta_pos'][:, 1] / self.std[2]], axis=1)
         if self.fingers_3d:
-            name = str(d['object_name']) if 'object_name' in d else "object"
+            name = self.object_name_of[idx] = str(d['object_name']) if 'object_name' in d else "object"
             if name not in self.object_pts:                                               # cached per object name (:58-66)
                 f = os.path.join(self.object_mesh_dir or "", name, 'points.npy')
                 if os.path.isfile(f):

@@ -42,6 +42,24 @@ def class_accuracy(score: torch.Tensor, pred: torch.Tensor, threshold_std) -> li
     return (cls(score) == cls(pred.to(score.device))).float().mean(dim=0).tolist()
 
 
+def _row_batches(args, loader, store=None):
+    """Per batch of `loader`: the row tensors and the number of pose cells per sample.  Host loop: `loader` yields collated samples.
+    --device_dataset: it yields sample indices and `store` (device_dataset.DeviceDynamicsStore) writes the rows on the GPU."""
+    for batch in loader:
+        if store is None:
+            yield batch_rows(batch, args.fingers_3d), batch['scores'].size(1)
+        else:
+            yield store.batch_rows(batch), store.cells
+
+
+def _accuracy(score, pred, threshold_std) -> list:
+    """class_accuracy; rows that are on the device (--device_dataset) are counted there and three integers come back."""
+    if score.is_cuda:
+        from .device_dataset import class_accuracy_device
+        return class_accuracy_device(score, pred, threshold_std)
+    return class_accuracy(score, pred.cpu(), threshold_std)
+
+
 class _Log:
     def __init__(self, args):
         self.path = os.path.join(args.save_dir, 'log.jsonl')
@@ -61,12 +79,11 @@ class _Log:
             f.write(json.dumps(scalars) + '\n')
 
 
-def validate(args, val_loader, trainer, threshold_std):
+def validate(args, val_loader, trainer, threshold_std, store=None):
     n, loss_sum, acc_sum = 0, 0.0, [0.0, 0.0, 0.0]
-    for batch in val_loader:
-        ctrl, score, ori, pos, obj = batch_rows(batch, args.fingers_3d)
-        pred, loss = trainer.inference(ctrl, score, ori, pos, obj, rows_per_sample=batch['scores'].size(1))
-        acc = class_accuracy(score, pred.cpu(), threshold_std)
+    for (ctrl, score, ori, pos, obj), cells in _row_batches(args, val_loader, store):
+        pred, loss = trainer.inference(ctrl, score, ori, pos, obj, rows_per_sample=cells)
+        acc = _accuracy(score, pred, threshold_std)
         loss_sum, acc_sum, n = loss_sum + loss, [a + b for a, b in zip(acc_sum, acc)], n + 1
     n = max(n, 1)
     return (loss_sum / n, *[a / n for a in acc_sum])
@@ -85,21 +102,30 @@ def train(args):
     threshold_std = train_set.threshold / train_set.std
     train_loader = DataLoader(train_set, batch_size=args.batch_size, shuffle=True, num_workers=args.num_workers, drop_last=False)
     val_loader = DataLoader(val_set, batch_size=args.batch_size, shuffle=False, num_workers=args.num_workers, drop_last=False)
+    train_store = val_store = None
+    if getattr(args, 'device_dataset', False):
+        # every file is read once, here; the loaders then hand out sample indices (same order, same draws from the CPU generator) and the
+        # stores write the rows on the GPU.  Under a launcher every rank builds the same stores.
+        from .device_dataset import DeviceDynamicsStore
+        val_store = DeviceDynamicsStore(val_set, threads=max(args.num_workers, 1), batch_size=args.batch_size)
+        val_loader = val_store.index_loader(args.batch_size, shuffle=False, drop_last=False)
+        if args.mode != 'validate':
+            train_store = DeviceDynamicsStore(train_set, threads=max(args.num_workers, 1), batch_size=args.batch_size)
+            train_loader = train_store.index_loader(args.batch_size, shuffle=True, drop_last=False)
     trainer = Trainer(args)
     trainer.create_model()
     if args.mode == 'validate':
         if args.checkpoint_path is None:
             raise ValueError('checkpoint path is not specified')
-        return validate(args, val_loader, trainer, threshold_std)
+        return validate(args, val_loader, trainer, threshold_std, val_store)
     log = _Log(args) if rank == 0 else None
     save = trainer.save_checkpoint if rank == 0 else (lambda path: None)
     best, last_best = float('inf'), 0
     for epoch in range(args.num_epochs):
         loss_sum, acc_sum = 0.0, [0.0, 0.0, 0.0]
-        for i, batch in enumerate(train_loader):
-            ctrl, score, ori, pos, obj = batch_rows(batch, args.fingers_3d)
-            loss, pred = trainer.step(ctrl, score, ori, pos, obj, rows_per_sample=batch['scores'].size(1))
-            acc = class_accuracy(score, pred.cpu(), threshold_std)
+        for i, ((ctrl, score, ori, pos, obj), cells) in enumerate(_row_batches(args, train_loader, train_store)):
+            loss, pred = trainer.step(ctrl, score, ori, pos, obj, rows_per_sample=cells)
+            acc = _accuracy(score, pred, threshold_std)
             loss_sum, acc_sum = loss_sum + loss, [a + b for a, b in zip(acc_sum, acc)]
             rank or log.log({'train/lr': trainer.optimizer.param_groups[0]['lr'], 'train/batch loss': loss, 'train/batch accuracy ori': acc[0],
                      'train/batch accuracy x': acc[1], 'train/batch accuracy y': acc[2]})
@@ -111,7 +137,7 @@ def train(args):
         rank or log.log({'train/average loss': loss_sum / nb, 'train/average accuracy ori': acc_sum[0] / nb, 'train/average accuracy x': acc_sum[1] / nb,
                  'train/average accuracy y': acc_sum[2] / nb})
         if epoch % args.val_step == 0:
-            v = validate(args, val_loader, trainer, threshold_std)
+            v = validate(args, val_loader, trainer, threshold_std, val_store)
             rank or log.log({'val/average loss': v[0], 'val/average accuracy ori': v[1], 'val/average accuracy x': v[2], 'val/average accuracy y': v[3]})
             if v[0] < best:
                 best, last_best = v[0], epoch

@@ -46,6 +46,8 @@ _FLAGS = [
     ("save_objects", "flag", None, "2-D: also export the run's icon objects as meshes, convex pieces and object_<idx>.xml into every model root "
                                    "(assets/icon_process.py save_icon_objects)"),
     ("seed", int, 0, "seed of the start noise"),
+    ("device_dataset", "flag", None, "dynamics training: read every data file once, keep the dataset on the GPU and build each batch's rows there "
+                                     "(dynamics/device_dataset.py); same batches, draws and results as the host loop"),
 ]
 
 

@@ -590,6 +590,34 @@ int dgdm_trainer2d_running_stats(DgdmTrainer2d *m, float *flat_dev, int64_t nume
 int dgdm_trainer2d_export(DgdmTrainer2d *m, int which, DgdmTensor *tensors, int n_tensors);
 int64_t dgdm_trainer2d_steps(const DgdmTrainer2d *m);      /* training steps taken = BatchNorm's num_batches_tracked increment */
 
+/* ------------------------------------------------------------------ training from a device-resident dataset (csrc/dataset.hip)
+ * The training set's samples as device arrays, read from their files once (dgdm_amd/dynamics/device_dataset.py), float32 as
+ * DynamicsDataset.__getitem__ returns them:
+ *   ctrl_dev   [n_samples][n_ctrl][2] (3-D: [..][3]); scores_dev [n_samples][cells][3]; ori_dev [n_samples][cells]; pos_dev [n_samples][cells][2]
+ *   object_dev [n_objects][n_object_points][2] (3-D: [..][3]); object_of_sample_host [n_samples] (HOST memory): the object of each sample,
+ *              NULL = sample s has object s (2-D: every file carries its own contour; 3-D: one cloud per object name).                */
+typedef struct DgdmDynamicsStore {
+    const float   *ctrl_dev, *object_dev, *scores_dev, *ori_dev, *pos_dev;
+    const int32_t *object_of_sample_host;
+    int64_t        n_samples, n_objects;
+    int32_t        cells, n_ctrl, n_object_points, fingers_3d;
+} DgdmDynamicsStore;
+/* batch_rows of dynamics/main.py:21-35 on the device: the five row tensors of the batch made of samples sample_ids_host[0 .. nb) (any
+ * order, repeats allowed), R = nb * cells rows, one launch, values copied bit for bit.
+ *   2-D (main.py:33-35), row r = i * cells + c for batch slot i, cell c:
+ *     ctrl_dev [R][n_ctrl] = the y ordinates ctrl[s_i][k][1]; obj_dev [R][2 n_object_points] = object[s_i] flattened
+ *   3-D (main.py:29-32), cell-major as the reference concatenates them, row r = c * nb + i:
+ *     ctrl_dev [R][3][n_ctrl], ctrl[r][d][k] = ctrl[s_i][k][d]; obj_dev [R][3][n_object_points] alike
+ *   both: score_dev [R][3], ori_dev [R], pos_dev [R][2] sample-major, r = i * cells + c.
+ * ids_dev: [2 nb] int64 of device workspace.  Every index (and the object it names) is checked against the store on the host before
+ * anything is enqueued: DGDM_EINVAL.  Row widths need not be multiples of four.                                                        */
+int dgdm_dynamics_batch_rows(const DgdmDynamicsStore *store, const int64_t *sample_ids_host, int nb, int64_t *ids_dev, float *ctrl_dev,
+                             float *obj_dev, float *score_dev, float *ori_dev, float *pos_dev, void *stream);
+/* class_accuracy of dynamics/main.py:37-42 as counts: agree_dev[j] (int64 [3], overwritten) = the rows r of score_dev, pred_dev [rows][3]
+ * with (s > thr[j]) - (s < -thr[j]) == (p > thr[j]) - (p < -thr[j]), s = score[r][j], p = pred[r][j] - torch's comparisons, so a NaN is in
+ * the middle class on both sides.  thr: host.  Exact integers, independent of the launch geometry.                                     */
+int dgdm_class_agreement(const float *score_dev, const float *pred_dev, int64_t rows, const float thr[3], int64_t *agree_dev, void *stream);
+
 /* ------------------------------------------------------------------ (f) rank 4: training the eps-net
  * Diffusion.get_stats / training_step (generator/diffusion.py:126-177) for the ConditionalUnet1D of generator/train.py:80
  * (generator/diffusion_utils.py:123-285; input_dim 1, down_dims [128, 256], kernel 5, 8 groups), torch.optim.Adam
