@@ -157,6 +157,9 @@ PROTOTYPES = {
     "dgdm_contour_resample": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _P, _P, C.c_int64, _P]),
     "dgdm_polygon_triangulate": (C.c_int, [_P, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P]),
     "dgdm_polygon_convex_pieces": (C.c_int, [_P, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "dgdm_render_workspace_bytes": (C.c_int64, [_P, _P, C.c_int, _P, C.c_int, C.c_int]),
+    "dgdm_render_meshes": (C.c_int, [_P, _P, _P, _P, C.c_int, _P, _P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P,
+                                     C.c_int64, _P]),
 }
 
 _lib = None

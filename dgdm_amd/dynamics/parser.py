@@ -42,6 +42,8 @@ _FLAGS = [
     ("predicted_sim", "flag", None, "fill the objective tables with the dynamics model's predictions (dynamics/predicted.py)"),
     ("predicted_rollout", int, 0, "with --predicted_sim: interactions the dynamics model is iterated for per start orientation, so that the "
                                   "final_* scores and 'convergence' see a settled pose (40 = the simulator's count; 0 = one interaction)"),
+    ("predicted_render", "flag", None, "with --predicted_sim, 3-D, objects from mesh files: also write <object>_<gripper>_gripper.png for every pair and, "
+                                       "for settled poses asked with render_last, <object>_<gripper>/<v>.png (sim/render_mesh.py)"),
     ("save_meshes", "flag", None, "also export every emitted gripper as OBJ meshes, collision pieces and gripper_<idx>.xml (assets/finger_mesh.py)"),
     ("save_objects", "flag", None, "2-D: also export the run's icon objects as meshes, convex pieces and object_<idx>.xml into every model root "
                                    "(assets/icon_process.py save_icon_objects)"),

@@ -644,6 +644,76 @@ def icon_contours(images, num_points: int = 100, rescale: bool = False) -> torch
     return resample_contours(points, off, num_points, rescale)
 
 
+# ---------------------------------------------------------------------------------------------------------------- mesh rendering
+RENDER_MAX_SIZE = 2048
+
+
+def render_meshes(verts, tris, offsets, inst_view, inst_mesh, inst_matrix, inst_id, n_views: int, width: int, height: int, inst_rgb=None,
+                  eyes=None, inst_model=None, snapped: bool = False):
+    """One batched z-buffer rendering (include/dgdm_hip.h "mesh rendering") -> (ids (n_views, height, width) int32, -1 =
+    background; depth float32, +inf there; rgb (n_views, height, width, 3) uint8, white there, or None without inst_rgb / eyes; rejected
+    (n_views,) int32: triangles dropped for a vertex behind the eye or off the snapping range), all on the current device.
+    verts (V, 3), tris (T, 3) int32 local to their mesh and offsets = (vertex offsets, triangle offsets) are the meshes concatenated
+    (concat_meshes), host or device.  Per instance: inst_view, inst_mesh, inst_matrix (n_inst, 4, 4) model -> pixel x, pixel y, depth, w
+    (float64 is rounded to float32 once, here), inst_id, inst_rgb (n_inst, 3) in [0, 1].  eyes (n_views, 3): the eye of each view in world
+    coordinates; inst_model (n_inst, 4, 4): the instances' model -> world matrices (identity when None), used only to carry each view's eye
+    into the instance's model frame on the host, in float64.  snapped=True appends the debug table (instance vertices, 4) int32 of
+    X, Y, the bits of zs, kept.  Synchronises the stream once."""
+    vo = np.ascontiguousarray(offsets[0], dtype=np.int64).reshape(-1)
+    to = np.ascontiguousarray(offsets[1], dtype=np.int64).reshape(-1)
+    M = len(vo) - 1
+    view = np.ascontiguousarray(inst_view, dtype=np.int32).reshape(-1)
+    mesh = np.ascontiguousarray(inst_mesh, dtype=np.int32).reshape(-1)
+    ident = np.ascontiguousarray(inst_id, dtype=np.int32).reshape(-1)
+    n = len(view)
+    mat64 = np.asarray(inst_matrix, dtype=np.float64)
+    if M < 1 or len(to) != M + 1 or n < 1 or len(mesh) != n or len(ident) != n or mat64.shape != (n, 4, 4):
+        raise ValueError(f"render_meshes: {len(vo)} / {len(to)} offsets (need M + 1 each), {n} views, {len(mesh)} meshes, {len(ident)} ids and "
+                         f"matrices of shape {mat64.shape} (need (n_inst, 4, 4))")
+    mat = np.ascontiguousarray(mat64, dtype=np.float32)
+    want_rgb = inst_rgb is not None and eyes is not None
+    if (inst_rgb is None) != (eyes is None):
+        raise ValueError("render_meshes: inst_rgb and eyes come together (both for an rgb image, neither without)")
+    n_views, width, height = int(n_views), int(width), int(height)
+    rgbs = eye_m = None
+    if want_rgb:
+        rgbs = np.ascontiguousarray(inst_rgb, dtype=np.float32).reshape(-1, 3)
+        ew = np.asarray(eyes, dtype=np.float64).reshape(-1, 3)
+        if len(rgbs) != n or len(ew) != n_views:
+            raise ValueError(f"render_meshes: {len(rgbs)} colours for {n} instances, {len(ew)} eyes for {n_views} views")
+        if view.min() < 0 or view.max() >= n_views:
+            raise ValueError(f"render_meshes: view indices {int(view.min())} .. {int(view.max())} outside 0 .. {n_views - 1}")
+        e = np.concatenate([ew[view], np.ones((n, 1))], axis=1)
+        if inst_model is not None:
+            mod = np.asarray(inst_model, dtype=np.float64)
+            if mod.shape != (n, 4, 4):
+                raise ValueError(f"render_meshes: inst_model of shape {mod.shape} (need ({n}, 4, 4))")
+            e = np.einsum('nij,nj->ni', np.linalg.inv(mod), e)
+        eye_m = np.ascontiguousarray(e[:, :3] / e[:, 3:4], dtype=np.float32)
+    dev = torch.device("cuda", torch.cuda.current_device())
+    v = torch.as_tensor(verts).to(device=dev, dtype=torch.float32).contiguous()
+    t = torch.as_tensor(tris).to(device=dev, dtype=torch.int32).contiguous()
+    if v.numel() != 3 * int(vo[-1]) or t.numel() != 3 * int(to[-1]):
+        raise ValueError(f"render_meshes: {v.numel() // 3} vertices / {t.numel() // 3} triangles, the offsets say {int(vo[-1])} / {int(to[-1])}")
+    ws_bytes = lib().dgdm_render_workspace_bytes(vo.ctypes.data, to.ctypes.data, M, mesh.ctypes.data, n, n_views)
+    if ws_bytes < 0:
+        _check_value(int(ws_bytes))
+    if not (1 <= width <= RENDER_MAX_SIZE and 1 <= height <= RENDER_MAX_SIZE):
+        raise ValueError(f"render_meshes: image of {width} x {height} (need 1 .. {RENDER_MAX_SIZE} each)")
+    ws = torch.empty(int(ws_bytes), dtype=torch.uint8, device=dev)
+    ids = torch.empty((n_views, height, width), dtype=torch.int32, device=dev)
+    depth = torch.empty((n_views, height, width), dtype=torch.float32, device=dev)
+    rgb = torch.empty((n_views, height, width, 3), dtype=torch.uint8, device=dev) if want_rgb else None
+    rejected = torch.empty((n_views,), dtype=torch.int32, device=dev)
+    n_pv = int(sum(vo[m + 1] - vo[m] for m in mesh))
+    snap = torch.empty((n_pv, 4), dtype=torch.int32, device=dev) if snapped else None
+    _check_value(lib().dgdm_render_meshes(dptr(v), dptr(t), vo.ctypes.data, to.ctypes.data, M, view.ctypes.data, mesh.ctypes.data, mat.ctypes.data,
+                                          ident.ctypes.data, rgbs.ctypes.data if want_rgb else None, eye_m.ctypes.data if want_rgb else None, n,
+                                          n_views, width, height, dptr(ids), dptr(depth), dptr(rgb), dptr(rejected), dptr(snap), dptr(ws),
+                                          int(ws_bytes), stream_ptr()))
+    return (ids, depth, rgb, rejected, snap) if snapped else (ids, depth, rgb, rejected)
+
+
 # ---------------------------------------------------------------------------------------------------------------- integer rings
 POLYGON_MAX_POINTS, POLYGON_MAX_COORD = 256, 32767
 

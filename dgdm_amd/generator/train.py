@@ -98,6 +98,14 @@ def _objects(args, fingers_3d: bool):
     return torch.stack([synth.synth_object_2d(i, nv) for i in range(len(OBJECT_IDS))]), list(OBJECT_IDS)
 
 
+def _object_mesh_dir(args):
+    """The directory whose <name>/model.obj files _objects sampled the run's 3-D objects from, or None (2-D, objects.npy, synthetic)."""
+    d = args.object_dir or ""
+    if not args.fingers_3d or os.path.isfile(os.path.join(d, "objects.npy")):
+        return None
+    return d if all(os.path.isfile(os.path.join(d, n, object_utils.MESH_FILE)) for n in OBJECT_NAMES_3D) else None
+
+
 def _icon_images(path):
     """(the 'image' array of the Icons-50 file at path, None) or (None, why not)."""
     if not os.path.isfile(path):
@@ -272,9 +280,13 @@ def train(args):
         raise ValueError(f"--predicted_rollout={rollout} needs --predicted_sim: it sets how many interactions the predicted simulator iterates")
     if rollout < 0:
         raise ValueError(f"--predicted_rollout={rollout}: the number of interactions cannot be negative")
+    render = bool(getattr(args, "predicted_render", False))
+    if render and not getattr(args, "predicted_sim", False):
+        raise ValueError("--predicted_render needs --predicted_sim: the pictures are drawn by the predicted simulator")
     if getattr(args, "predicted_sim", False) and args.classifier_guidance and model.simulator is None:
         from ..dynamics.predicted import PredictedSimulator      # opt-in: the tables scored by the dynamics model instead of roll-outs
-        model.simulator = PredictedSimulator(model, rollout_interactions=rollout)
+        model.object_mesh_dir = _object_mesh_dir(args) if render else None      # where --predicted_render finds <name>/model.obj
+        model.simulator = PredictedSimulator(model, rollout_interactions=rollout, render_grippers=render)
     if args.mode != 'test':                 # generator/train.py:158-162
         if args.diffusion_checkpoint_path is not None:
             print('loading diffusion checkpoint from', args.diffusion_checkpoint_path)

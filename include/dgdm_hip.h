@@ -475,6 +475,53 @@ int dgdm_polygon_convex_pieces(const int32_t *points_dev, int batch, int n, int3
                                int64_t *area2_dev, int32_t *triangles_dev, int32_t *piece_count_dev, int32_t *piece_offsets_dev,
                                int32_t *piece_index_dev, void *stream);
 
+/* ------------------------------------------------------------------ mesh rendering
+ * Where the reference evaluates a 3-D design with pictures (sim/render_mesh.py render_mesh / render_object_mesh through MuJoCo's OpenGL
+ * renderer, dynamics/sim_test_mj_3d.py:99-106, 218-225) this library has a small batched z-buffer rasteriser (csrc/render.hip): one call
+ * draws many views.  MuJoCo's renderer (lights, materials, shadows, the ground plane, anti-aliasing) is NOT reproduced and is unpinned;
+ * this is the project's own contract, exact in integers and in unfused float32 operations.  DESIGN.md §4.5e; tests/render_oracle.py is
+ * the CPU statement.
+ *
+ * Meshes: verts_dev [V][3] float32 and tris_dev [T][3] int32 (indices local to their mesh, 0-based) are n_meshes meshes concatenated;
+ * mesh m = rows vert_offsets_host[m] .. [m + 1] and tri_offsets_host[m] .. [m + 1] (both int64, starting at 0).
+ * Instances (host tables of n_inst rows): inst_view_host (0 .. n_views - 1), inst_mesh_host, inst_matrix_host [n_inst][16] float32
+ * row-major, inst_id_host int32, inst_rgb_host [n_inst][3] base colour in [0, 1], inst_eye_host [n_inst][3] the eye in the instance's
+ * model frame (the last two may be null without rgb_dev).  The matrix m maps model coordinates straight to pixel coordinates and depth
+ * (viewport x projection x view x model); callers compose it in float64 and round once.
+ *   projection  per (instance, vertex), float32, nothing fused:  c_r = ((m_r0 x + m_r1 y) + m_r2 z) + m_r3,  r = 0 .. 3;
+ *               px = c_0 / c_3, py = c_1 / c_3, zs = c_2 / c_3, one IEEE division each;  X = (int32) rintf(px * 256), Y likewise:
+ *               8 sub-pixel bits, ties to even.
+ *   rejection   a vertex is bad when c_3 <= 0 or not finite, zs is not finite, or |rintf(px * 256)| or |rintf(py * 256)| is not below
+ *               2^20 (a NaN anywhere ends here).  A triangle with a bad vertex is dropped whole and counted in rejected[view].  There is
+ *               no near-plane clipping.
+ *   coverage    int64.  A = (x1 - x0)(y2 - y0) - (y1 - y0)(x2 - x0) on the snapped vertices in file order; A == 0 draws nothing; A < 0
+ *               swaps v1 and v2 (two-sided: OBJ winding is not trusted).  Pixel (i, j) samples at (256 i + 128, 256 j + 128) = (sx, sy).
+ *               For the edges a -> b = v0 -> v1, v1 -> v2, v2 -> v0 with (dx, dy) = b - a:  E = dx (sy - ya) - dy (sx - xa).  The pixel
+ *               is covered iff all three E >= 0, where E == 0 counts only when dy < 0, or dy == 0 and dx > 0.  Triangles that share an
+ *               edge therefore cover each sample on it exactly once.
+ *   depth       float32, nothing fused:  b1 = (float)E_20 / (float)A,  b2 = (float)E_01 / (float)A,
+ *               z = (z0 + b1 (z1 - z0)) + b2 (z2 - z0)  with z_k the zs of (swapped) vertex k.  The smaller z wins; at equal z the
+ *               earlier instance of the view (caller's order), then the lower triangle index.
+ *   shading     rgb only, flat per triangle, float32, nothing fused, in model coordinates with the vertices a, b, c in file order:
+ *               n = (b - a) x (c - a), each component p q - r s;  d = eye - ((a + b) + c) / 3;  dot = (n_x d_x + n_y d_y) + n_z d_z,
+ *               |n|^2 and |d|^2 summed likewise;  q = sqrt(|n|^2 |d|^2);  s = 0.3 + 0.7 min(|dot| / q, 1), or 0.3 when q is 0 or not
+ *               finite;  channel = (uint8) rintf((base s) 255), clamped to 0 .. 255.  (For a rigid model matrix this is the world-space
+ *               |n . v| of the unit normal and the unit direction from the centroid to the eye.)
+ * Outputs: ids_dev [n_views][height][width] int32, the id of the instance seen, -1 where nothing is drawn; depth_dev float32, +inf there;
+ * rgb_dev (may be null) [n_views][height][width][3] uint8, white there; rejected_dev [n_views] int32.  snapped_dev (debug, may be null):
+ * [instance vertices][4] int32 rows X, Y, the bits of zs, 1 = kept, instances in view order (the caller's order within a view).
+ * A view's result depends on that view's instances alone, whatever else is in the batch.  1 <= width, height <= 2048, n_views <= 65535.
+ * DGDM_EINVAL: bad offsets, a mesh or view index out of range, a size out of range, a triangle index outside its mesh (found on the
+ * device; the images are then undefined).  Synchronises the stream once.                                                          */
+/* Bytes of device workspace dgdm_render_meshes needs; negative: bad tables. */
+int64_t dgdm_render_workspace_bytes(const int64_t *vert_offsets_host, const int64_t *tri_offsets_host, int n_meshes,
+                                    const int32_t *inst_mesh_host, int n_inst, int n_views);
+int dgdm_render_meshes(const float *verts_dev, const int32_t *tris_dev, const int64_t *vert_offsets_host, const int64_t *tri_offsets_host,
+                       int n_meshes, const int32_t *inst_view_host, const int32_t *inst_mesh_host, const float *inst_matrix_host,
+                       const int32_t *inst_id_host, const float *inst_rgb_host, const float *inst_eye_host, int n_inst, int n_views,
+                       int width, int height, int32_t *ids_dev, float *depth_dev, uint8_t *rgb_dev, int32_t *rejected_dev,
+                       int32_t *snapped_dev, void *workspace_dev, int64_t workspace_bytes, void *stream);
+
 /* ------------------------------------------------------------------ measurement hooks
  * When enabled, the launches of every stage of the path are bracketed by hipEvents on the stream they are launched on.
  * dgdm_prof_read_stage synchronises those events and returns, for one stage, the number of bracketed regions, their total
