@@ -30,6 +30,13 @@ class Objective(C.Structure):
     _fields_ = [("lin", C.c_float * 3), ("quad", C.c_float * 3), ("use_rowcoef", C.c_int32), ("object", C.c_int32)]
 
 
+class GoalSpec(C.Structure):
+    _fields_ = [("weight", C.c_float * 3), ("ori_window", C.c_float), ("pos_window", C.c_float), ("profile", C.c_int32)]
+
+
+OBJ_ROWFIELD = 2      # Objective.use_rowcoef: the per-row seed of dgdm_guidance_set_row_field
+
+
 class TrainGroups(C.Structure):
     _fields_ = [("t_index_dev", C.c_void_p), ("t_values_dev", C.c_void_p), ("n_t", C.c_int32), ("rows_per_object", C.c_int32)]
 
@@ -82,6 +89,8 @@ PROTOTYPES = {
     "dgdm_guidance_starts_per_call": (C.c_int64, [_P]),
     "dgdm_dyn2d_guidance_grad": (C.c_int, [_P, _P, C.c_int, C.POINTER(Objective), _P, C.c_int, _P, _P]),
     "dgdm_dyn3d_guidance_grad": (C.c_int, [_P, _P, C.c_int, C.POINTER(Objective), _P, _P, C.c_int, _P, _P]),
+    "dgdm_guidance_set_row_field": (C.c_int, [_P, _P, C.c_int, _P]),
+    "dgdm_guidance_goal_field": (C.c_int, [_P, _P, C.POINTER(GoalSpec), C.c_int, _P, _P]),
     "dgdm_guidance_score": (C.c_int, [_P, _P, C.c_int, C.POINTER(C.c_int32), _P, C.POINTER(C.c_float), C.c_int, _P, _P, _P, _P]),
     "dgdm_guided_chains_run": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.POINTER(Objective), _P, _P, C.POINTER(C.c_int32), C.POINTER(C.c_float),
                                          C.POINTER(C.c_float), C.c_int, _P, _P]),

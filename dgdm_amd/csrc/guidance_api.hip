@@ -3,6 +3,7 @@
 #include "common.h"
 #include "models.h"
 #include <algorithm>
+#include <cmath>
 #include <cstring>
 #include <unordered_map>
 #include <atomic>
@@ -77,6 +78,11 @@ struct DgdmGuidance {
     // dgdm_guidance_rollout: the sweep's orientations [G] (built with the handle), and its scratch, grown on demand: the state
     // [n][B*G][3] doubles, one interaction's logits, the per-row pose operand tiles [ntiles][W1*32] and (3-D) their row maxima [ntiles][32]
     DevBuf sweep_ori, rollstate, rolllogits, rolltiles, rollpmax;
+    // dgdm_guidance_set_row_field: the caller's field [rowfield_chains][R][3] (kept, not copied) for chains with use_rowcoef == DGDM_OBJ_ROWFIELD;
+    // dgdm_guidance_goal_field: the position grid [P] beside sweep_ori, and the device copy of the call's specs
+    const float *rowfield = nullptr;
+    int rowfield_chains = 0;
+    DevBuf pos_lin, goalspecs;
     int rolltiles_chains = 0;                // chains the tiles of the last roll-out cover (dgdm_guidance_debug_rollout_table)
     DevBuf xidx, xidxchains, xtabptrs;       // embedding-table path: row index per reference row, per-chain lookup info, per-chain table base pointers
     bool xtab_enabled = true;       // test hook: modes 1-3 read materialised rows (per-step gather kernels) instead of the embedding table
@@ -215,6 +221,7 @@ extern "C" int dgdm_guidance_create(DgdmGuidance **out, DgdmDynamics *model, con
     std::vector<float> pos0(2 * (size_t)G, 0.f);                          // get_convergence_centers: pos = 0 (:511)
     if ((rc = g->build_pose_table(lo, pos0, &g->sweep, nullptr))) return rc;
     if ((rc = g->sweep_ori.upload(lo.data(), lo.size() * sizeof(float)))) return rc;
+    if ((rc = g->pos_lin.upload(lp.data(), lp.size() * sizeof(float)))) return rc;
     const int W1 = model->W1, nc = cfg->max_chains;
     const size_t rows = (size_t)nc * g->B;
     const int64_t R = g->grid.rows;
@@ -762,6 +769,21 @@ int DgdmGuidance::trunk_front(int kind, const float *x_dev, int timestep, const 
     return DGDM_OK;
 }
 
+// What a launch's objectives need of the per-row inputs, checked before anything is enqueued: the trunk reads rowcoef / field rows of
+// chain i without looking again
+static int check_objectives(const DgdmGuidance *g, const DgdmObjective *objectives, const float *rowcoef_dev, int n_chains) {
+    for (int i = 0; i < n_chains; ++i) {
+        const int u = objectives[i].use_rowcoef;
+        DGDM_REQUIRE(u >= 0 && u <= DGDM_OBJ_ROWFIELD, DGDM_EINVAL, "chain %d: use_rowcoef %d (0, 1 or %d)", i, u, DGDM_OBJ_ROWFIELD);
+        DGDM_REQUIRE(u != 1 || rowcoef_dev, DGDM_EINVAL, "chain %d uses rowcoef but rowcoef_dev is null", i);
+        if (u == DGDM_OBJ_ROWFIELD) {
+            DGDM_REQUIRE(g->rowfield, DGDM_EINVAL, "chain %d uses the row field but none is set (dgdm_guidance_set_row_field)", i);
+            DGDM_REQUIRE(i < g->rowfield_chains, DGDM_EINVAL, "chain %d uses the row field, which was set for %d chains", i, g->rowfield_chains);
+        }
+    }
+    return DGDM_OK;
+}
+
 // cond_fn for n_chains chains.  3-D: `emb` = the embeddings made by DgdmGuidance::embed for a run of calls, `call` = which of them this is;
 // emb == nullptr: this call's own (starts_host = its draws).
 static int guidance_grad(DgdmGuidance *g, int kind, const float *x_dev, int timestep, const DgdmObjective *objectives, const float *rowcoef_dev,
@@ -770,19 +792,19 @@ static int guidance_grad(DgdmGuidance *g, int kind, const float *x_dev, int time
     DGDM_REQUIRE(g && x_dev && objectives && grad_dev, DGDM_EINVAL, "guidance_grad: null argument");
     if (g->m->kind != kind) { set_error("model type not supported: %d-D entry point on a %d-D model", kind, g->m->kind); return DGDM_EMODE; }
     DGDM_REQUIRE(n_chains > 0 && n_chains <= g->cfg.max_chains, DGDM_EINVAL, "n_chains %d outside 1..%d", n_chains, g->cfg.max_chains);
+    int rc;
+    if ((rc = check_objectives(g, objectives, rowcoef_dev, n_chains))) return rc;
     std::vector<int> oidx(n_chains);
     std::vector<TrunkObjective> tob(n_chains);
     for (int i = 0; i < n_chains; ++i) {
         oidx[i] = objectives[i].object;
         for (int j = 0; j < 3; ++j) { tob[i].lin[j] = objectives[i].lin[j]; tob[i].quad[j] = objectives[i].quad[j]; }
         tob[i].use_rowcoef = objectives[i].use_rowcoef; tob[i].pad = 0;
-        DGDM_REQUIRE(!tob[i].use_rowcoef || rowcoef_dev, DGDM_EINVAL, "chain %d uses rowcoef but rowcoef_dev is null", i);
     }
-    int rc;
     TrunkParams p;
     if ((rc = g->trunk_front(kind, x_dev, timestep, oidx.data(), starts_host, n_chains, emb, call, &p, s))) return rc;
     DGDM_HIP_CHECK(hipMemcpyAsync(g->objdev.p, tob.data(), sizeof(TrunkObjective) * n_chains, hipMemcpyHostToDevice, s));
-    p.obj = g->objdev.as<TrunkObjective>(); p.rowcoef = rowcoef_dev;
+    p.obj = g->objdev.as<TrunkObjective>(); p.rowcoef = rowcoef_dev; p.rowfield = g->rowfield;
     p.partial = g->partial.as<float>();
     if (g->bf16) {
         g->m->fill_trunk_bf16(&p);       // only the two weight streams differ
@@ -809,6 +831,43 @@ extern "C" int dgdm_dyn2d_guidance_grad(DgdmGuidance *g, const float *x_dev, int
 extern "C" int dgdm_dyn3d_guidance_grad(DgdmGuidance *g, const float *x_dev, int timestep, const DgdmObjective *objectives,
                                         const float *rowcoef_dev, const int64_t *starts_host, int n_chains, float *grad_dev, void *stream) {
     return guidance_grad(g, 3, x_dev, timestep, objectives, rowcoef_dev, starts_host, n_chains, grad_dev, (hipStream_t)stream);
+}
+
+extern "C" int dgdm_guidance_set_row_field(DgdmGuidance *g, const float *field_dev, int n_chains, void *stream) {
+    (void)stream;                                             // nothing is enqueued: the pointer is kept and read by later launches
+    DGDM_REQUIRE(g, DGDM_EINVAL, "dgdm_guidance_set_row_field: null handle");
+    if (!field_dev) { g->rowfield = nullptr; g->rowfield_chains = 0; return DGDM_OK; }
+    DGDM_REQUIRE(n_chains > 0 && n_chains <= g->cfg.max_chains, DGDM_EINVAL, "dgdm_guidance_set_row_field: n_chains %d outside 1..%d", n_chains,
+                 g->cfg.max_chains);
+    g->rowfield = field_dev; g->rowfield_chains = n_chains;
+    return DGDM_OK;
+}
+
+extern "C" int dgdm_guidance_goal_field(DgdmGuidance *g, const float *goals_dev, const DgdmGoalSpec *specs_host, int n_chains, float *field_dev,
+                                        void *stream) {
+    DGDM_REQUIRE(g && goals_dev && specs_host && field_dev, DGDM_EINVAL, "dgdm_guidance_goal_field: null argument");
+    DGDM_REQUIRE(n_chains > 0 && n_chains <= g->cfg.max_chains, DGDM_EINVAL, "dgdm_guidance_goal_field: n_chains %d outside 1..%d", n_chains,
+                 g->cfg.max_chains);
+    hipStream_t s = (hipStream_t)stream;
+    for (int i = 0; i < n_chains; ++i) {
+        const DgdmGoalSpec &q = specs_host[i];
+        DGDM_REQUIRE(q.ori_window > 0.f && q.ori_window <= 1.f, DGDM_EINVAL, "goal %d: ori_window %g outside (0, 1]", i, (double)q.ori_window);
+        DGDM_REQUIRE(q.pos_window > 0.f && std::isfinite(q.pos_window), DGDM_EINVAL, "goal %d: pos_window %g is not a positive number", i, (double)q.pos_window);
+        DGDM_REQUIRE(q.profile == 0 || q.profile == 1, DGDM_EINVAL, "goal %d: profile %d (0 sign, 1 linear)", i, q.profile);
+        for (int j = 0; j < 3; ++j) DGDM_REQUIRE(std::isfinite(q.weight[j]), DGDM_EINVAL, "goal %d: weight %d is not finite", i, j);
+    }
+    // the goals may come from a device-side sweep: they are read back once to refuse a non-finite one (the builder is not a hot path)
+    std::vector<float> goals((size_t)n_chains * g->B * 3);
+    DGDM_HIP_CHECK(hipMemcpyAsync(goals.data(), goals_dev, goals.size() * sizeof(float), hipMemcpyDeviceToHost, s));
+    DGDM_HIP_CHECK(hipStreamSynchronize(s));
+    for (size_t k = 0; k < goals.size(); ++k)
+        DGDM_REQUIRE(std::isfinite(goals[k]), DGDM_EINVAL, "goal %d, finger %d: coordinate %d is not finite", (int)(k / ((size_t)g->B * 3)),
+                     (int)(k / 3 % g->B), (int)(k % 3));
+    int rc;
+    if ((rc = g->goalspecs.alloc(sizeof(DgdmGoalSpec) * g->cfg.max_chains))) return rc;
+    DGDM_HIP_CHECK(hipMemcpyAsync(g->goalspecs.p, specs_host, sizeof(DgdmGoalSpec) * n_chains, hipMemcpyHostToDevice, s));
+    return goal_field_build(g->sweep_ori.as<float>(), g->pos_lin.as<float>(), goals_dev, g->goalspecs.as<DgdmGoalSpec>(), n_chains, g->B,
+                            g->cfg.grid_size, g->cfg.num_pos, field_dev, s);
 }
 
 // Diffusion.cond_fn's forward half (generator/diffusion.py:473-504 up to the classifier's output) and the classes of :506-532 on it.
@@ -863,6 +922,7 @@ extern "C" int dgdm_guided_chains_run(DgdmUnet1d *unet, DgdmGuidance *g, const f
     const size_t per_chain = (size_t)B * L, nx = per_chain * n_chains, ng = nx * n_grad;
     DGDM_REQUIRE(kind == 2 || starts_host, DGDM_EINVAL, "3-D guidance needs the FPS start indices");
     int rc;
+    if ((rc = check_objectives(g, objectives, rowcoef_dev, n_chains * n_grad))) return rc;      // before the first launch of the loop
     if ((rc = g->loopx[0].alloc(nx * 4)) || (rc = g->loopx[1].alloc(nx * 4)) || (rc = g->loopeps.alloc(nx * 4)) || (rc = g->loopgrad.alloc(ng * 4)) ||
         (rc = g->loopxrep.alloc(ng * 4)) || (rc = g->loopts.alloc((size_t)n_chains * B * sizeof(int))))
         return rc;

@@ -6,7 +6,7 @@ namespace dgdm {
 struct TrunkObjective {   // device copy of DgdmObjective (object index not needed on the device)
     float lin[3];
     float quad[3];
-    int   use_rowcoef;
+    int   use_rowcoef;        // 0: lin / quad; 1: d0's seed is rowcoef[r]; 2 (DGDM_OBJ_ROWFIELD): lin / quad + rowfield[r][j]
     int   pad;
 };
 
@@ -38,6 +38,7 @@ struct TrunkParams {
     const float  *Pmax;       // [C] largest magnitude of a cell's row of Ptab (trunk_f16l.hip: the f16 scale of 3-D layer 2's input); may be null elsewhere; per-row pose mode: [ntiles][32], one value per tile row, padding rows included
     const TrunkObjective *obj;// [nchain]
     const float  *rowcoef;    // [nchain][R] or null
+    const float  *rowfield;   // [nchain][R][3] or null: read for chains with use_rowcoef == 2 only (the host checks that it covers them)
     float        *partial;    // [ntiles][W1]
     float        *logits;     // fwd-only: [nchain][R][3]
     int           B, C, tiles_per_b, ntiles;
@@ -91,6 +92,11 @@ int rollout_update(const float *logits, const double scale[3], int k, int64_t ro
 // counts [n_chains][B][27] (bin = (class of d0 * 3 + class of d1) * 3 + class of d2; class 2 if l > thr, 0 if l < -thr, else 1) and
 // sums [n_chains][B][4] = sum d0, sum |d0|, sum d1, sum d2.  Fixed reduction order: the same bits every run.
 int score_tally(const float *logits, int n_chains, int B, int C, const float thr[3], int32_t *counts, float *sums, hipStream_t s);
+
+// Goal field (goal.hip): field [n_chains][R][3], row r = cell * B + b, cell = (g * P + px) * P + py, from the float32 grids ori_grid [G] /
+// pos_grid [P], the goals [n_chains][B][3] and one (validated) spec per chain, all on the device; the definitions are the header's.
+int goal_field_build(const float *ori_grid, const float *pos_grid, const float *goals, const DgdmGoalSpec *specs, int n_chains, int B, int G, int P,
+                     float *field, hipStream_t s);
 
 // bf16-contraction variant (trunk_bf16.hip): table mode, forward + backward only.  p.Wfwd / p.Wbwd point at the bf16 streams
 // (DgdmDynamics::fill_trunk_bf16); everything else in TrunkParams means the same.

@@ -193,7 +193,14 @@ __global__ __launch_bounds__(256, 1) void trunk_kernel(const TrunkParams p) {
         float g0 = ob.lin[0] + 2.f * ob.quad[0] * d0;
         float g1 = ob.lin[1] + 2.f * ob.quad[1] * d1;
         float g2 = ob.lin[2] + 2.f * ob.quad[2] * d2;
-        if (ob.use_rowcoef) g0 = p.rowcoef[(size_t)chain * p.R + r];
+        if (ob.use_rowcoef == 1) g0 = p.rowcoef[(size_t)chain * p.R + r];
+        {   // row field: r is clamped for padding rows, so the rows read lie inside [nchain][R][3].  Loads and selects instead of a branch
+            // (other chains read three floats of bout and drop them): a branch here costs the 2-D kernel 51 SGPR spills
+            const bool rf = ob.use_rowcoef == 2;
+            const float *f = rf ? p.rowfield + ((size_t)chain * p.R + r) * 3 : p.bout;
+            const float f0 = f[0], f1 = f[1], f2 = f[2];
+            g0 = rf ? g0 + f0 : g0; g1 = rf ? g1 + f1 : g1; g2 = rf ? g2 + f2 : g2;
+        }
         if (!valid) { g0 = 0.f; g1 = 0.f; g2 = 0.f; }
 
         slot -= 4;

@@ -552,7 +552,11 @@ __global__ __launch_bounds__(256, 1) void trunk_bf16_kernel(const TrunkParams p)
             float g0 = ob.lin[0] + 2.f * ob.quad[0] * d0;
             float g1 = ob.lin[1] + 2.f * ob.quad[1] * d1;
             float g2 = ob.lin[2] + 2.f * ob.quad[2] * d2;
-            if (ob.use_rowcoef) g0 = p.rowcoef[(size_t)tr.chain * p.R + tr.r];
+            if (ob.use_rowcoef == 1) g0 = p.rowcoef[(size_t)tr.chain * p.R + tr.r];
+            if (ob.use_rowcoef == 2) {                     // tile_rows clamps the tile and r: inside [nchain][R][3]
+                const float *f = p.rowfield + ((size_t)tr.chain * p.R + tr.r) * 3;
+                g0 += f[0]; g1 += f[1]; g2 += f[2];
+            }
             const bool live = tr.valid && lane < 32 && (t == 0 || has1);
             if (!live) { g0 = 0.f; g1 = 0.f; g2 = 0.f; }
             GB.v[t][0][0][0] = pack_bf16(g0, g1);

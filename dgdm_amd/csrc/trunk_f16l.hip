@@ -534,13 +534,23 @@ __global__ __launch_bounds__(256, 1) void trunk_f16l_kernel(const TrunkParams p,
         }
         return;
     }
+    const TrunkObjective ob = p.obj[chain];
+    // row field (use_rowcoef == 2): tile and r are clamped (a wave without a tile, padding rows), so the row lies inside [nchain][R][3].
+    // 2-D: loads and selects, not a branch (other chains read three floats of bout and drop them), requested AHEAD of the backward stream
+    // (a wait for them behind its first chunks would be a wait for those chunks: vmcnt counts in order) - as a branch the seed costs this
+    // instantiation 6 % of its launch.  3-D: the branch, below - there the unconditional loads cost 1 % and the branch nothing
+    const bool rf = ob.use_rowcoef == 2;
+    const float *fp = (KIND == 3 || rf) ? p.rowfield + ((size_t)chain * p.R + r) * 3 : p.bout;
+    float f0 = 0.f, f1 = 0.f, f2 = 0.f;
+    if (KIND == 2) { f0 = fp[0]; f1 = fp[1]; f2 = fp[2]; }
     const wrsrc_t rsB = weight_rsrc(p.Wbwd, p.bwd_bytes);
     ls.start(rsB, 0);                                         // in flight while the objective runs on the VALU
-    const TrunkObjective ob = p.obj[chain];
     float g0 = ob.lin[0] + 2.f * ob.quad[0] * d0;
     float g1 = ob.lin[1] + 2.f * ob.quad[1] * d1;
     float g2 = ob.lin[2] + 2.f * ob.quad[2] * d2;
-    if (ob.use_rowcoef) g0 = p.rowcoef[(size_t)chain * p.R + r];
+    if (ob.use_rowcoef == 1) g0 = p.rowcoef[(size_t)chain * p.R + r];
+    if (KIND == 2) { g0 = rf ? g0 + f0 : g0; g1 = rf ? g1 + f1 : g1; g2 = rf ? g2 + f2 : g2; }
+    else if (rf) { g0 += fp[0]; g1 += fp[1]; g2 += fp[2]; }
     if (!valid) { g0 = 0.f; g1 = 0.f; g2 = 0.f; }
 
 #pragma unroll

@@ -123,7 +123,7 @@ def sync_start_stream_seed(group=None) -> int:
 
 
 def shard_chains(chains: Sequence[Tuple[int, str]], rank: int, world: int):
-    """This rank's block of `chains` [(object index, opt_obj)]: (global index range, the object indices it needs in first-use
+    """This rank's block of `chains` [(object index, opt_obj: objective name or sampler.Goal)]: (global index range, the object indices it needs in first-use
     order, its chains re-indexed into that local object bank)."""
     mine = shard_range(len(chains), rank, world)
     local_objects: List[int] = []
@@ -200,31 +200,34 @@ def guided_multi_object_sharded(unet, spec: GuidanceSpec, sched, mode: str, nois
     from . import engine, sampler
     world, rank = world_rank(group)
     n_obj, (B, L, _) = objects.shape[0], noise.shape
-    if opt_obj == 'convergence':
+    if not sampler.is_goal(opt_obj) and opt_obj == 'convergence':
         raise ValueError("the reference never runs the multi-object loop with 'convergence' (generator/diffusion.py:337)")
     mine = shard_range(n_obj, rank, world)
     is3d = mode == 'point_3d'
     if is3d:
         starts = starts or sampler.StartStream(spec.num_object_points, spec.sub_batch_size)
     guid = (build or spec.build)(objects[mine.start:mine.stop].to(noise.device), len(mine)) if len(mine) else None
-    objectives = [engine.make_objective(opt_obj, k) for k in range(len(mine))]
-    scale = sampler.classifier_scale(mode, opt_obj, multi=True)
-    x = noise.reshape(B, L).contiguous().to(torch.float32)
-    for i, t in enumerate(sched.timesteps):
-        t = int(t)
-        eps = unet.forward(x.reshape(B, L, 1), torch.full((B,), t, dtype=torch.int32, device=x.device)).reshape(B, L)
-        st = None
-        if is3d:
-            per_obj = [starts.call(spec.rows) if j in mine else starts.skip(spec.rows) for j in range(n_obj)]
-            st = np.concatenate([per_obj[j] for j in mine]) if len(mine) else None
-        if guid is not None:
-            g = guid.grad(x.reshape(1, B, L).expand(len(mine), -1, -1).contiguous(), t, objectives, None, st)
-        else:
-            g = torch.zeros((0, B, L), dtype=torch.float32, device=x.device)
-        g = gather_rows(g, n_obj, group)
-        x = engine.ddim_guided_step(x, eps, g, n_obj, sched.coefficients(t), scale)
-        if on_step is not None:
-            on_step(i, x.reshape(B, L, 1))
+    with sampler.keeps_row_field(guid):              # a Goal's field is on the handle for this loop only
+        objectives, field = sampler.chain_objectives(guid, [(k, opt_obj) for k in range(len(mine))]) if guid is not None else ([], None)
+        if field is not None:
+            guid.set_row_field(field)
+        scale = sampler.chain_scale(mode, opt_obj, multi=True)
+        x = noise.reshape(B, L).contiguous().to(torch.float32)
+        for i, t in enumerate(sched.timesteps):
+            t = int(t)
+            eps = unet.forward(x.reshape(B, L, 1), torch.full((B,), t, dtype=torch.int32, device=x.device)).reshape(B, L)
+            st = None
+            if is3d:
+                per_obj = [starts.call(spec.rows) if j in mine else starts.skip(spec.rows) for j in range(n_obj)]
+                st = np.concatenate([per_obj[j] for j in mine]) if len(mine) else None
+            if guid is not None:
+                g = guid.grad(x.reshape(1, B, L).expand(len(mine), -1, -1).contiguous(), t, objectives, None, st)
+            else:
+                g = torch.zeros((0, B, L), dtype=torch.float32, device=x.device)
+            g = gather_rows(g, n_obj, group)
+            x = engine.ddim_guided_step(x, eps, g, n_obj, sched.coefficients(t), scale)
+            if on_step is not None:
+                on_step(i, x.reshape(B, L, 1))
     return x.reshape(B, L, 1)
 
 

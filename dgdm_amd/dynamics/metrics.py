@@ -62,6 +62,9 @@ _ROT = {'clockwise': 0, 'counterclockwise': 2}                       # class ind
 _SHIFT = {'up': ('x', 0, 0), 'down': ('x', 0, 2), 'left': ('y', 1, 0), 'right': ('y', 1, 2)}     # axis name, column, class index
 
 
+GOAL_BASIN_DEG = (3, 5, 10)      # the thresholds 'convergence' scores the final angles with (metric2objective)
+
+
 def convergence_range_from_finals(finals, threshold=0.1):
     """Maximal runs [start, end] of consecutive orientations whose final angles stay within ``threshold`` of each other
     (running min/max since the run began); runs of a single orientation are dropped (metrics.py:40-65)."""
@@ -95,7 +98,12 @@ def _shift_part(metric, shift):
 
 def metric2objective(metric, objective):
     """Scores of one (object, gripper) roll-out for ``objective`` (metrics.py:67-234): a success rate over the orientation grid,
-    class counts, and mean motions.  Key names and dtypes as in the reference."""
+    class counts, and mean motions.  Key names and dtypes as in the reference.  A ``Goal`` (dgdm_amd/goal.py) is scored by
+    ``predicted.goal_objective`` on the roll-out's settled poses."""
+    from ..goal import is_goal
+    if is_goal(objective):
+        from .predicted import goal_objective
+        return goal_objective(metric, objective)
     if objective == 'rotate':
         p = metric['profile']
         return {'success_rate': np.mean((p == 0) | (p == 2), dtype=np.float32), 'num_zero_classes': np.sum(p == 1, dtype=np.int16),
@@ -122,7 +130,11 @@ def metric2objective(metric, objective):
 
 def objective_directions(opt_obj):
     """For every score of ``opt_obj``: +1 if larger is better, -1 if smaller is better - the argmax/argmin choices of
-    Diffusion.get_best_ids_all_metrics (generator/diffusion.py:391-428) - plus the key get_average_best_ids ranks by (:354-389)."""
+    Diffusion.get_best_ids_all_metrics (generator/diffusion.py:391-428) - plus the key get_average_best_ids ranks by (:354-389).
+    A ``Goal``: the scores of ``predicted.goal_objective`` - more start orientations in the basin is better, less error is better."""
+    from ..goal import is_goal
+    if is_goal(opt_obj):
+        return ({**{f'goal_basin_{d}deg': +1 for d in GOAL_BASIN_DEG}, 'goal_error_deg': -1, 'goal_pos_error_cm': -1}, 'goal_basin_5deg')
     if opt_obj in ('rotate', 'rotate_in_place'):
         return {'num_zero_classes': -1, 'delta_theta_abs': +1, 'final_delta_theta_abs': +1}, 'num_zero_classes'
     if opt_obj == 'convergence':

@@ -48,6 +48,13 @@ _FLAGS = [
     ("save_objects", "flag", None, "2-D: also export the run's icon objects as meshes, convex pieces and object_<idx>.xml into every model root "
                                    "(assets/icon_process.py save_icon_objects)"),
     ("seed", int, 0, "seed of the start noise"),
+    ("goal_pose", str, None, "THETA_DEG,X_CM,Y_CM: also guide and score designs toward this object pose (dgdm_amd/goal.py); the validation sweep "
+                             "then adds guided/goal_... and multi/goal_... after the reference's objectives"),
+    ("goal_weight", str, "1,0,0", "with --goal_pose: a,b,c weights of the rotation, x and y terms of the goal's pull"),
+    ("goal_window_deg", float, 90.0, "with --goal_pose: half-width in degrees of the band of orientations pulled toward the goal (0 < w <= 180)"),
+    ("goal_window_cm", float, 3.0, "with --goal_pose: half-width in centimetres of the band of positions pulled toward the goal"),
+    ("goal_profile", str, "sign", "with --goal_pose: 'sign' (unit pull inside the window) or 'linear' (proportional, saturating at the window)"),
+    ("goal_scale", float, None, "with --goal_pose: classifier scale of the goal chains (default: the scale of 'convergence'; untuned for goals)"),
     ("device_dataset", "flag", None, "dynamics training: read every data file once, keep the dataset on the GPU and build each batch's rows there "
                                      "(dynamics/device_dataset.py); same batches, draws and results as the host loop"),
 ]

@@ -19,6 +19,9 @@ Roll-outs.  The simulator closes the gripper 40 times per start orientation (dyn
 rollout_interactions=K)`` does the same with the model in the simulator's place (``engine.Guidance.rollout``): the one-step keys from the
 first interaction, the ``final_*`` keys from the pose after the K-th.  With ``K = 0`` one interaction stands for both.
 
+Goals.  ``goal_objective(metric, goal)`` scores a roll-out's settled poses against a chosen pose (``sampler.Goal``): how many start
+orientations end within 3 / 5 / 10 degrees of it, the mean angle and position error.
+
 These are the dynamics model's opinion, not simulator measurements; every metric dict carries ``'predicted': True``.
 """
 from __future__ import annotations
@@ -28,7 +31,7 @@ from typing import Any, Dict, List, Optional, Sequence
 import numpy as np
 
 from .dataloader import POS_NORM
-from .metrics import _ROT, _SHIFT
+from .metrics import _ROT, _SHIFT, GOAL_BASIN_DEG
 
 DEG = 180.0 / np.pi       # radians -> degrees (sim_test_mj.py:210)
 CM = 100.0                # metres -> centimetres (:211)
@@ -128,6 +131,32 @@ def build_metric(logits, threshold_std: Sequence[float], std: Sequence[float], o
     metric['rollout_interactions'] = int(rollout_interactions)
     metric['rollout_left_range'] = int(np.count_nonzero(lf >= 0))
     return metric
+
+
+def goal_objective(metric: Dict[str, Any], goal) -> Dict[str, Any]:
+    """Scores of one (object, gripper) for a ``Goal`` (dgdm_amd/goal.py) from the settled poses of a predicted roll-out: ``metric``
+    is ``build_metric``'s with ``final_pose`` (it must carry ``'rollout_interactions'``: one interaction settles nothing), read through
+    ``final_theta`` (num_rot,) in degrees and ``final_pos`` (num_rot, 3) in centimetres.
+      goal_basin_{3,5,10}deg  start orientations whose final angle is within that many degrees of the goal angle, the difference wrapped
+                              into [-180, 180] (np.int16, 0 .. num_rot)
+      goal_error_deg          mean absolute wrapped angle error (float64, 0 .. 180)
+      goal_pos_error_cm       mean distance of the final position from the goal position (float64)
+      predicted               True
+    A per-finger Goal is not scored (the metric does not say which finger it belongs to).  Like every score built on roll-outs, these
+    are the dynamics model's opinion of its own iterates, not measurements."""
+    if metric.get('predicted', False) and 'rollout_interactions' not in metric:
+        raise ValueError("goal_objective: the metric holds no settled pose (PredictedSimulator(rollout_interactions=K >= 1) / build_metric(final_pose=...))")
+    if getattr(goal, "fingers", None) is not None:
+        raise ValueError("goal_objective: a per-finger Goal cannot be scored from one metric dict")
+    theta = np.asarray(metric['final_theta'], dtype=np.float64).reshape(-1)
+    pos = np.asarray(metric['final_pos'], dtype=np.float64).reshape(len(theta), -1)
+    err = np.abs((theta - goal.theta_deg + 180.0) % 360.0 - 180.0)
+    goal_cm = np.array([goal.pos[0], goal.pos[1]], dtype=np.float64) * POS_NORM * CM
+    out: Dict[str, Any] = {f'goal_basin_{d}deg': np.sum(err <= d, dtype=np.int16) for d in GOAL_BASIN_DEG}
+    out['goal_error_deg'] = float(np.mean(err))
+    out['goal_pos_error_cm'] = float(np.mean(np.hypot(pos[:, 0] - goal_cm[0], pos[:, 1] - goal_cm[1])))
+    out['predicted'] = True
+    return out
 
 
 def center_index(num_pos: int) -> int:

@@ -199,9 +199,20 @@ def debug_pointnet_indices(dyn: "Dynamics", cloud: torch.Tensor, perm: Optional[
     return {k: v.cpu().numpy() for k, v in out.items()}
 
 
-def make_objective(name: str, object_index: int = 0) -> _lib.Objective:
+def make_objective(name: Optional[str], object_index: int = 0, row_field: bool = False, lin: Sequence[float] = (0.0, 0.0, 0.0),
+                   quad: Sequence[float] = (0.0, 0.0, 0.0)) -> _lib.Objective:
+    """The objective of a reference name - or, with row_field=True (name None), a row-field objective (include/dgdm_hip.h
+    DGDM_OBJ_ROWFIELD): d objective / d delta_j of row r = lin[j] + 2 quad[j] delta_j + field[r][j], the field being the one given to
+    Guidance.set_row_field at the chain's index of the launch."""
     o = _lib.Objective()
     o.object = object_index
+    if row_field:
+        if name is not None:
+            raise ValueError("a row-field objective has no reference name (pass name=None)")
+        for j in range(3):
+            o.lin[j], o.quad[j] = float(lin[j]), float(quad[j])
+        o.use_rowcoef = _lib.OBJ_ROWFIELD
+        return o
     check(lib().dgdm_objective_from_name(name.encode(), C.byref(o)))
     return o
 
@@ -221,6 +232,7 @@ class Guidance:
         self.starts_per_call = int(lib().dgdm_guidance_starts_per_call(h))
         self.sweep_rows = batch * grid_size
         self.n_objects = 0
+        self._row_field: Optional[torch.Tensor] = None      # set_row_field keeps the tensor the library points at
         self.set_contraction_dtype(contraction_dtype)
 
     def set_contraction_dtype(self, dtype: str) -> None:
@@ -279,6 +291,34 @@ class Guidance:
         sub = self.cfg.sub_batch_size if self.dyn.kind == 3 else 0
         check(lib().dgdm_convergence_rowcoef(c.ctypes.data, len(c), self.cfg.grid_size, self.cfg.num_pos, self.rows, sub, out.ctypes.data))
         return out
+
+    def goal_field(self, goals: torch.Tensor, specs: Sequence[_lib.GoalSpec]) -> torch.Tensor:
+        """The row field of goal poses (include/dgdm_hip.h, dgdm_guidance_goal_field): goals (n, B, 3) = (ori, pos_x, pos_y) per chain
+        and finger in the model's normalised inputs, specs one _lib.GoalSpec per chain -> (n, R, 3) float32 on the goals' device.
+        A bad window, profile or a non-finite goal raises ValueError."""
+        dev = torch.device("cuda", torch.cuda.current_device())
+        gl = torch.as_tensor(goals).detach().to(device=dev, dtype=torch.float32).contiguous()
+        n = len(specs)
+        if gl.shape != (n, self.cfg.batch, 3):
+            raise ValueError(f"goal_field: goals of shape {tuple(gl.shape)} for {n} specs (need ({n}, {self.cfg.batch}, 3))")
+        arr = (_lib.GoalSpec * n)(*specs)
+        out = torch.empty((n, self.rows, 3), dtype=torch.float32, device=dev)
+        _check_value(lib().dgdm_guidance_goal_field(self._h, dptr(gl), arr, n, dptr(out), stream_ptr()))
+        return out
+
+    def set_row_field(self, field: Optional[torch.Tensor]) -> None:
+        """field (n, R, 3) float32 on the device: the per-row seed of the chains whose objective is a row-field objective, chain i of a
+        grad() / guided_chains_run launch reading field[i]; None clears it.  The library keeps the POINTER: the tensor is referenced
+        here until it is replaced or cleared (and must not be modified while launches that read it are in flight)."""
+        if field is None:
+            check(lib().dgdm_guidance_set_row_field(self._h, None, 0, stream_ptr()))
+            self._row_field = None
+            return
+        if not (field.is_cuda and field.dtype == torch.float32 and field.is_contiguous() and field.dim() == 3 and
+                tuple(field.shape[1:]) == (self.rows, 3)):
+            raise ValueError(f"set_row_field: a contiguous float32 device tensor (n, {self.rows}, 3) expected, got {tuple(field.shape)} {field.dtype}")
+        check(lib().dgdm_guidance_set_row_field(self._h, dptr(field), field.shape[0], stream_ptr()))
+        self._row_field = field
 
     def grad(self, x: torch.Tensor, timestep: int, objectives: Sequence[_lib.Objective], rowcoef: Optional[torch.Tensor] = None,
              starts: Optional[np.ndarray] = None) -> torch.Tensor:

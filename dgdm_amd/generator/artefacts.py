@@ -112,7 +112,10 @@ class TableLog:
 
 
 def profile_family(opt_obj: str) -> str:
-    """Which of the simulator's profile plots a guided table shows (:584-591)."""
+    """Which of the simulator's profile plots a guided table shows (:584-591); a Goal run shows the rotation profile."""
+    from ..goal import is_goal
+    if is_goal(opt_obj):
+        return 'profiles'
     if opt_obj in ROTATION_FAMILY:
         return 'profiles'
     if opt_obj in ('shift_up', 'shift_down'):

@@ -130,6 +130,8 @@ class Diffusion(nn.Module):
         # nor this: object_exporter(model_root, name) (--save_objects, generator/train.py) writes the objects of the run into the model
         # root of every emitted batch, next to its grippers, so that a scene file over that root finds both halves
         self.object_exporter = None
+        # nor this: a sampler.Goal (--goal_pose) the validation sweep guides and scores toward, after the reference's objectives
+        self.goal = None
         if class_cond:
             self.classifier_model = classifier_model
             self.grid_size, self.num_pos = grid_size, num_pos
@@ -308,9 +310,16 @@ class Diffusion(nn.Module):
             self.ema.optimization_step, self.ema.decay = int(ck["ema"]["optimization_step"]), float(ck["ema"]["decay"])
 
     # ------------------------------------------------------------------ a5
-    def deltas_to_objective(self, deltas, opt_obj, centers=None):
+    def deltas_to_objective(self, deltas, opt_obj, centers=None, ori_range=(-1.0, 1.0)):
         """generator/diffusion.py:430-471 on an arbitrary deltas tensor (the sampling path itself uses the form fused
-        into the trunk kernel; this is for callers that want the objective values)."""
+        into the trunk kernel; this is for callers that want the objective values).  opt_obj may be a ``sampler.Goal``: deltas are
+        then cond_fn's R = B * grid_size * num_pos^2 rows over ``ori_range`` and the value of row r is sum_j field[r][j] * deltas[r][j]."""
+        if sampler.is_goal(opt_obj):
+            cells = self.grid_size * self.num_pos ** 2
+            if deltas.shape[0] % cells:
+                raise ValueError(f"deltas_to_objective: {deltas.shape[0]} rows are not a multiple of the grid's {cells} cells")
+            field = opt_obj.field(deltas.shape[0] // cells, self.grid_size, self.num_pos, ori_range).to(deltas.device)
+            return (deltas * field.to(deltas.dtype)).sum(dim=-1)
         sign = {'rotate_clockwise': (-1, 0, 0), 'rotate_counterclockwise': (1, 0, 0), 'shift_up': (0, -1, 0), 'shift_down': (0, 1, 0),
                 'shift_left': (0, 0, -1), 'shift_right': (0, 0, 1), 'clockwise_up': (-1, -1, 0), 'clockwise_down': (-1, 1, 0),
                 'clockwise_left': (-1, 0, -1), 'clockwise_right': (-1, 0, 1), 'counterclockwise_up': (1, -1, 0),
@@ -339,13 +348,16 @@ class Diffusion(nn.Module):
             raise ValueError('model type not supported')
         B = x.shape[0]
         g = self._guidance_for(B, ori_range, object_vertices.reshape(1, *object_vertices.shape[-2:]), 1)
-        obj = engine.make_objective(opt_obj, 0)
         tt = int(torch.as_tensor(t).reshape(-1)[0])
-        rc = None
-        if opt_obj == 'convergence':
-            rc = torch.from_numpy(g.rowcoef(torch.as_tensor(convergence_centers))).to(self.device).reshape(1, -1)
-        starts = StartStream(g.cfg.num_object_points, g.cfg.sub_batch_size).call(g.rows) if self.mode == 'point_3d' else None
-        grad = g.grad(x.reshape(1, B, -1).to(self.device), tt, [obj], rc, starts)
+        with sampler.keeps_row_field(g):                 # a Goal's field is on the handle for this call only
+            (obj,), field = sampler.chain_objectives(g, [(0, opt_obj)])
+            if field is not None:
+                g.set_row_field(field)
+            rc = None
+            if not sampler.is_goal(opt_obj) and opt_obj == 'convergence':
+                rc = torch.from_numpy(g.rowcoef(torch.as_tensor(convergence_centers))).to(self.device).reshape(1, -1)
+            starts = StartStream(g.cfg.num_object_points, g.cfg.sub_batch_size).call(g.rows) if self.mode == 'point_3d' else None
+            grad = g.grad(x.reshape(1, B, -1).to(self.device), tt, [obj], rc, starts)
         return grad.reshape(x.shape)
 
     # ------------------------------------------------------------------ a6
@@ -359,7 +371,7 @@ class Diffusion(nn.Module):
         """Index of the best gripper for every score of ``opt_obj`` (generator/diffusion.py:391-428)."""
         directions, _ = objective_directions(opt_obj)
         best = {k: (np.argmax if sgn > 0 else np.argmin)([o[k] for o in objectives]) for k, sgn in directions.items()}
-        if opt_obj != 'convergence':
+        if not sampler.is_goal(opt_obj) and opt_obj != 'convergence':
             best['success_rate'] = np.argmax([o['success_rate'] for o in objectives])
         return best
 
@@ -544,7 +556,7 @@ class Diffusion(nn.Module):
         world, rank = ddist.world_rank()
         plots = bool(self.save_dir) and self.render_plots and rank == 0
         jobs = []
-        for opt_obj in OBJECTIVE_SWEEP:
+        for opt_obj in OBJECTIVE_SWEEP + ([self.goal] if getattr(self, "goal", None) is not None else []):
             if opt_obj != 'convergence':
                 if world > 1:
                     mine = ddist.shard_range(n, rank, world)
@@ -572,3 +584,8 @@ class Diffusion(nn.Module):
                 out[f"multi/{opt_obj}"] = self.guided_sample_multi_object(batch_idx, B, noise, self.save_dir, opt_obj=opt_obj, ori_range=rng)
             out[f"guided/{opt_obj}"] = self.guided_sample(batch_idx, B, noise, self.save_dir, opt_obj=opt_obj, ori_range=rng,
                                                           unguided_sample=unguided)
+        goal = getattr(self, "goal", None)
+        if goal is not None:               # --goal_pose: one more objective behind the reference's, keyed by the goal's name ("goal_...")
+            rng = [-1.0, 1.0]
+            out[f"multi/{goal}"] = self.guided_sample_multi_object(batch_idx, B, noise, self.save_dir, opt_obj=goal, ori_range=rng)
+            out[f"guided/{goal}"] = self.guided_sample(batch_idx, B, noise, self.save_dir, opt_obj=goal, ori_range=rng, unguided_sample=unguided)

@@ -287,6 +287,10 @@ def train(args):
         from ..dynamics.predicted import PredictedSimulator      # opt-in: the tables scored by the dynamics model instead of roll-outs
         model.object_mesh_dir = _object_mesh_dir(args) if render else None      # where --predicted_render finds <name>/model.obj
         model.simulator = PredictedSimulator(model, rollout_interactions=rollout, render_grippers=render)
+    from ..goal import goal_from_args
+    model.goal = goal_from_args(args)       # --goal_pose: the sweep adds a goal objective after the reference's (Diffusion._objective_sweep)
+    if model.goal is not None and getattr(args, "predicted_sim", False) and not rollout:
+        raise ValueError("--goal_pose with --predicted_sim needs --predicted_rollout K >= 1: a goal is scored on the pose the roll-out settles to")
     if args.mode != 'test':                 # generator/train.py:158-162
         if args.diffusion_checkpoint_path is not None:
             print('loading diffusion checkpoint from', args.diffusion_checkpoint_path)

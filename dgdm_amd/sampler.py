@@ -9,13 +9,14 @@ the order in which the reference consumes the torch CPU generator for the FPS st
 """
 from __future__ import annotations
 
-from typing import List, Optional, Sequence, Tuple
+from typing import List, Optional, Sequence, Tuple, Union
 
 import numpy as np
 import torch
 
 from . import _lib, engine
 from .engine import Guidance, Unet1d, make_objective
+from .goal import PROFILES, Goal, is_goal
 from .scheduler import DDIMScheduler
 
 SCALE_2D, SCALE_2D_CONV, SCALE_3D, SCALE_3D_CONV = 0.001, 10.0, 0.5, 0.8      # generator/diffusion.py:30-33
@@ -28,6 +29,65 @@ def classifier_scale(mode: str, opt_obj: str, multi: bool = False) -> float:
     if mode == 'point_3d':
         return SCALE_3D_CONV if (opt_obj == 'convergence' and not multi) else SCALE_3D
     return 0.001
+
+
+def chain_scale(mode: str, opt_obj: Union[str, Goal], multi: bool = False) -> float:
+    """The classifier scale of a chain: ``classifier_scale`` for a reference objective; for a Goal its own ``scale``, else the scale of
+    'convergence' - a borrowed default that nobody has tuned for goal objectives (dgdm_amd/goal.py)."""
+    if is_goal(opt_obj):
+        return float(opt_obj.scale) if opt_obj.scale is not None else classifier_scale(mode, 'convergence', multi)
+    return classifier_scale(mode, opt_obj, multi)
+
+
+def chain_objectives(guid: Guidance, chains: Sequence[Tuple[int, Union[str, Goal]]]):
+    """[(object index, objective name or Goal), ...] in launch order -> (the launch's objectives, the row field (n, R, 3) the Goal
+    chains read at their own index or None when there is no Goal).  The library indexes the field by the chain's place in the launch,
+    so it spans all n chains; the rows of the other chains are zero and never read.  Each DISTINCT Goal is built once on the device
+    (guided_multi_object hands the same Goal to every object) and copied to its chains' rows."""
+    objectives = [make_objective(None, oi, row_field=True) if is_goal(o) else make_objective(o, oi) for oi, o in chains]
+    distinct: List[Goal] = []
+    for _, o in chains:
+        if is_goal(o) and not any(o is d for d in distinct):
+            distinct.append(o)
+    if not distinct:
+        return objectives, None
+    B = guid.cfg.batch
+    specs = [_lib.GoalSpec((_lib.C.c_float * 3)(*g.weight), g.ori_window, g.pos_window, PROFILES[g.profile]) for g in distinct]
+    built = guid.goal_field(torch.stack([g.triples(B) for g in distinct]), specs)
+    field = torch.zeros((len(chains), guid.rows, 3), dtype=torch.float32, device=built.device)
+    for c, (_, o) in enumerate(chains):
+        if is_goal(o):
+            field[c] = built[next(k for k, d in enumerate(distinct) if d is o)]
+    return objectives, field
+
+
+class keeps_row_field:
+    """``with keeps_row_field(guid):`` - whatever the body hands the handle through Guidance.set_row_field (the Goal chains' field), on the
+    way out, by return or by exception, the handle holds what it held before: a field does not outlive its launch, and a field the caller
+    set is not lost (the launches are ordered on the stream, and so is the reuse of the field's memory).  guid may be None."""
+
+    def __init__(self, guid: Optional[Guidance]):
+        self.guid = guid
+
+    def __enter__(self):
+        self.before = self.guid._row_field if self.guid is not None else None
+        return self
+
+    def __exit__(self, *exc):
+        if self.guid is not None and self.guid._row_field is not self.before:
+            self.guid.set_row_field(self.before)
+        return False
+
+
+def _restores_row_field(fn):
+    """The loops below run inside keeps_row_field(guid)."""
+    import functools
+
+    @functools.wraps(fn)
+    def run(unet, guid, *args, **kw):
+        with keeps_row_field(guid):
+            return fn(unet, guid, *args, **kw)
+    return run
 
 
 class TorchRng:
@@ -289,11 +349,12 @@ def convergence_centers(guid: Guidance, mode: str, unguided: torch.Tensor, objec
     return out
 
 
-def draw_chain_starts(guid: Guidance, chains: Sequence[Tuple[int, str]], n_steps: int, starts: Optional[StartStream] = None,
+def draw_chain_starts(guid: Guidance, chains: Sequence[Tuple[int, Union[str, Goal]]], n_steps: int, starts: Optional[StartStream] = None,
                       keep: Optional[range] = None, streams: Optional[Sequence[StartStream]] = None, out: Optional[np.ndarray] = None,
                       pool=None):
     """FPS starts of a batch of 3-D chains in the order the reference's sequential loops consume the generator:
     chain after chain (generator/diffusion.py:561); inside a chain the centre sweep (:563) and then every step's cond_fn (:574).
+    A Goal chain draws no sweep, like every objective other than 'convergence'.
 
     keep: only the chains of this index range are returned (sweep list / step array of len(keep) chains); the draws of the
     others are consumed and dropped, so that a rank holding a block of the chains sees exactly the numbers a single process
@@ -308,7 +369,7 @@ def draw_chain_starts(guid: Guidance, chains: Sequence[Tuple[int, str]], n_steps
     assert step.shape == (n_steps, len(keep), guid.starts_per_call) and step.dtype == np.int64 and step.flags.c_contiguous
     def one(c, o, st, mine):
         k = c - keep.start
-        if o == 'convergence':
+        if not is_goal(o) and o == 'convergence':
             sw = st.calls(guid.sweep_rows, 1, keep=mine)
             if mine:
                 sweep[k] = sw[0]
@@ -329,17 +390,21 @@ def draw_chain_starts(guid: Guidance, chains: Sequence[Tuple[int, str]], n_steps
     return sweep, step
 
 
+@_restores_row_field
 def guided_chains(unet: Unet1d, guid: Guidance, sched: DDIMScheduler, mode: str, noise: torch.Tensor,
-                  chains: Sequence[Tuple[int, str]], unguided: Optional[torch.Tensor] = None,
+                  chains: Sequence[Tuple[int, Union[str, Goal]]], unguided: Optional[torch.Tensor] = None,
                   starts: Optional[StartStream] = None, trace: Optional[list] = None, predrawn=None) -> torch.Tensor:
-    """``Diffusion.guided_sample`` loop bodies (:561-576) for the chains [(object index, opt_obj), ...].
+    """``Diffusion.guided_sample`` loop bodies (:561-576) for the chains [(object index, opt_obj), ...]; opt_obj: a reference
+    objective name or a ``Goal`` (dgdm_amd/goal.py), whose chain is guided by the goal's row field.
 
     noise (B, L, 1) is shared by all chains (:570).  Returns (n_chains, B, L, 1)."""
     nc, (B, L, _) = len(chains), noise.shape
     dev = noise.device
     is3d = mode == 'point_3d'
     S = len(sched.timesteps)
-    objectives = [make_objective(o, oi) for oi, o in chains]
+    objectives, field = chain_objectives(guid, chains)
+    if field is not None:
+        guid.set_row_field(field)
     # --- replay of the reference's RNG consumption: chain after chain; inside a chain the centre sweep, then the steps
     sweep_starts: List[Optional[np.ndarray]] = [None] * nc
     step_starts = None
@@ -347,7 +412,7 @@ def guided_chains(unet: Unet1d, guid: Guidance, sched: DDIMScheduler, mode: str,
         sweep_starts, step_starts = predrawn if predrawn is not None else draw_chain_starts(guid, chains, S, starts)
     # --- 'convergence' chains: centres from the unguided sample, then row coefficients
     rowcoef = None
-    conv = [c for c, (_, o) in enumerate(chains) if o == 'convergence']
+    conv = [c for c, (_, o) in enumerate(chains) if not is_goal(o) and o == 'convergence']
     if conv:
         assert unguided is not None, "opt_obj='convergence' needs the unguided sample (generator/diffusion.py:563)"
         st = np.concatenate([sweep_starts[c] for c in conv]) if is3d else None
@@ -356,7 +421,7 @@ def guided_chains(unet: Unet1d, guid: Guidance, sched: DDIMScheduler, mode: str,
         for k, c in enumerate(conv):
             rc[c] = guid.rowcoef(centers[k])
         rowcoef = torch.from_numpy(rc).to(dev)
-    scales = [classifier_scale(mode, o) for _, o in chains]
+    scales = [chain_scale(mode, o) for _, o in chains]
     if trace is None:         # the loop itself runs inside the library (one call); the Python loop below is kept for traced runs
         out = engine.guided_chains_run(unet, guid, noise.reshape(B, L), nc, 1, objectives, rowcoef,
                                        np.ascontiguousarray(step_starts) if is3d else None, [int(t) for t in sched.timesteps],
@@ -384,18 +449,23 @@ def guided_chains(unet: Unet1d, guid: Guidance, sched: DDIMScheduler, mode: str,
     return x.reshape(nc, B, L, 1)
 
 
+@_restores_row_field
 def guided_multi_object(unet: Unet1d, guid: Guidance, sched: DDIMScheduler, mode: str, noise: torch.Tensor,
-                        object_indices: Sequence[int], opt_obj: str, starts: Optional[StartStream] = None, on_step=None) -> torch.Tensor:
-    """``Diffusion.guided_sample_multi_object`` loop (:637-647): one chain, gradient = mean over the objects."""
+                        object_indices: Sequence[int], opt_obj: Union[str, Goal], starts: Optional[StartStream] = None,
+                        on_step=None) -> torch.Tensor:
+    """``Diffusion.guided_sample_multi_object`` loop (:637-647): one chain, gradient = mean over the objects.  opt_obj: a reference
+    objective name or a ``Goal``."""
     n_obj, (B, L, _) = len(object_indices), noise.shape
     dev = noise.device
     is3d = mode == 'point_3d'
-    objectives = [make_objective(opt_obj, oi) for oi in object_indices]
-    if opt_obj == 'convergence':
+    objectives, field = chain_objectives(guid, [(oi, opt_obj) for oi in object_indices])
+    if field is not None:
+        guid.set_row_field(field)
+    if not is_goal(opt_obj) and opt_obj == 'convergence':
         raise ValueError("the reference never runs the multi-object loop with 'convergence' (generator/diffusion.py:337)")
     if is3d:
         starts = starts or StartStream(guid.cfg.num_object_points, guid.cfg.sub_batch_size)
-    scale = classifier_scale(mode, opt_obj, multi=True)
+    scale = chain_scale(mode, opt_obj, multi=True)
     if on_step is None:       # one library call for the whole loop; per step the reference draws object after object (:641-643)
         S = len(sched.timesteps)
         st = starts.calls(guid.rows, S * n_obj).reshape(S, -1) if is3d else None      # per step object after object (:641-643): one run of draws
@@ -436,8 +506,9 @@ def draw_ensemble_starts(guid: Guidance, n_groups: int, n_obj: int, n_steps: int
     return out
 
 
+@_restores_row_field
 def guided_multi_object_groups(unet: Unet1d, guid: Guidance, sched: DDIMScheduler, mode: str, noise: torch.Tensor,
-                               groups: Sequence[Sequence[int]], opt_objs: Sequence[str], streams: Optional[Sequence[StartStream]] = None,
+                               groups: Sequence[Sequence[int]], opt_objs: Sequence[Union[str, Goal]], streams: Optional[Sequence[StartStream]] = None,
                                predrawn: Optional[np.ndarray] = None, python_loop: bool = False) -> torch.Tensor:
     """Several independent ``guided_sample_multi_object`` chains (:637-647) in the same launches: chain k averages the guidance
     gradients of the objects ``groups[k]`` for objective ``opt_objs[k]`` (a guidance ensemble: n_obj dynamics-gradient
@@ -445,15 +516,21 @@ def guided_multi_object_groups(unet: Unet1d, guid: Guidance, sched: DDIMSchedule
     (j, k) -> j * K + k, so the mean over j is one strided reduction for every group at once.  Returns (K, B, L, 1)."""
     K, n_obj, (B, L, _) = len(groups), len(groups[0]), noise.shape
     assert all(len(g) == n_obj for g in groups) and len(opt_objs) == K
-    if any(o == 'convergence' for o in opt_objs):
+    if any(not is_goal(o) and o == 'convergence' for o in opt_objs):
         raise ValueError("the reference never runs the multi-object loop with 'convergence' (generator/diffusion.py:337)")
     dev = noise.device
     is3d = mode == 'point_3d'
     S = len(sched.timesteps)
-    objectives = [make_objective(opt_objs[k], groups[k][j]) for j in range(n_obj) for k in range(K)]
+    # (a Goal group reads the row field at its gradient chains' own indices j * K + k)
+    objectives, field = chain_objectives(guid, [(groups[k][j], opt_objs[k]) for j in range(n_obj) for k in range(K)])
+    if field is not None:
+        guid.set_row_field(field)
     if is3d and predrawn is None:
         predrawn = draw_ensemble_starts(guid, K, n_obj, S, streams)
-    scale = classifier_scale(mode, opt_objs[0], multi=True)
+    scales = {chain_scale(mode, o, multi=True) for o in opt_objs}
+    if len(scales) != 1:      # (dgdm_guided_chains_run refuses per-chain scales with averaged gradients; names share one scale, Goals may not)
+        raise ValueError(f"guided_multi_object_groups: the groups' classifier scales differ ({sorted(scales)}); give the Goals one scale")
+    scale = scales.pop()
     if not python_loop:       # one library call: K chains x n_obj gradients each, gradient chains object-major
         out = engine.guided_chains_run(unet, guid, noise.reshape(B, L), K, n_obj, objectives, None,
                                        np.ascontiguousarray(predrawn) if is3d else None, [int(t) for t in sched.timesteps],

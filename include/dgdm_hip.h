@@ -53,11 +53,16 @@ typedef struct DgdmGuidance DgdmGuidance;  /* state of Diffusion.cond_fn for a b
  *   d objective / d delta_j = lin[j] + 2*quad[j]*delta_j                     (all but 'convergence')
  * 'convergence' sets use_rowcoef: d objective / d delta_0 of reference row r is rowcoef[r],
  * the signed multiplicity of r in the slicer() windows (dynamics/metrics.py:32-38), built by
- * dgdm_convergence_rowcoef().                                                                   */
+ * dgdm_convergence_rowcoef().
+ * use_rowcoef == DGDM_OBJ_ROWFIELD adds a per-row term for all three outputs instead:
+ *   d objective / d delta_j of row r = lin[j] + 2*quad[j]*delta_j + field[r][j]
+ * with the field given to dgdm_guidance_set_row_field() (with lin = quad = 0 the seed is the field
+ * value itself, bit for bit).                                                                   */
+#define DGDM_OBJ_ROWFIELD 2
 typedef struct DgdmObjective {
     float   lin[3];
     float   quad[3];
-    int32_t use_rowcoef;
+    int32_t use_rowcoef;  /* 0: lin / quad only; 1: rowcoef ('convergence'); DGDM_OBJ_ROWFIELD       */
     int32_t object;       /* index into the object bank given to dgdm_guidance_set_objects      */
 } DgdmObjective;
 
@@ -198,7 +203,7 @@ int64_t dgdm_guidance_starts_per_call(const DgdmGuidance *g);
  *   x_dev        [n_chains][B][L]       current samples
  *   timestep     the (shared) integer diffusion timestep t; the model sees t/num_train_timesteps
  *   objectives   [n_chains] host array (objective + object index per chain)
- *   rowcoef_dev  [n_chains][R] or NULL  (only read for chains with use_rowcoef)
+ *   rowcoef_dev  [n_chains][R] or NULL  (only read for chains with use_rowcoef == 1)
  *   starts_host  3-D: [n_chains][starts_per_call] int64 in the order the reference draws them;
  *                2-D: NULL
  *   grad_dev     [n_chains][B][L]       d sum(objective) / d x                                 */
@@ -207,6 +212,30 @@ int dgdm_dyn2d_guidance_grad(DgdmGuidance *g, const float *x_dev, int timestep, 
 int dgdm_dyn3d_guidance_grad(DgdmGuidance *g, const float *x_dev, int timestep, const DgdmObjective *objectives,
                              const float *rowcoef_dev, const int64_t *starts_host, int n_chains, float *grad_dev,
                              void *stream);
+
+/* Row field: a per-row seed for all three outputs, for chains whose use_rowcoef == DGDM_OBJ_ROWFIELD (no counterpart in the reference,
+ * whose objectives are one direction for every row, or 'convergence' on delta_0).
+ * field_dev [n_chains][R][3] float32 (row r = cell*B + b as in cond_fn) or NULL to clear. The pointer is kept, not copied:
+ * it must stay valid for every later grad / chains_run call on the handle. Read only for chains whose use_rowcoef == 2:
+ *   d objective / d delta_j of row r of chain i = lin[j] + 2*quad[j]*delta_j + field[(i*R + r)*3 + j]
+ * In dgdm_guided_chains_run, chain i runs over the n_grad * n_chains gradient chains in objectives[] order.
+ * A chain with use_rowcoef == 2 while no field is set, or whose index is not below the n_chains given here, makes grad / chains_run
+ * return DGDM_EINVAL before anything is launched.  All three contraction dtypes take it.                                              */
+int dgdm_guidance_set_row_field(DgdmGuidance *g, const float *field_dev, int n_chains, void *stream);
+
+/* Goal field: the row field that pulls every pose of the cond_fn grid toward a goal pose, built on the device.
+ * goals_dev [n_chains][B][3] float32 = (ori, pos_x, pos_y) per finger in the model's normalised inputs (ori = theta/pi - 1, pos = m / 0.03);
+ * specs_host [n_chains]; field_dev [n_chains][R][3].
+ * Row r = cell*B + b, cell = (g*P + px)*P + py; ori[] / pos[] are the handle's own float32 grids (linspace(ori_range, G),
+ * linspace(-1, 1, P)); everything below in float64:
+ *   u0 = goal_ori - ori[g], minus 2 if > 1, plus 2 if < -1 (the shorter way round); u1 = goal_x - pos[px]; u2 = goal_y - pos[py]
+ *   half-widths h0 = ori_window (0 < h0 <= 1), h1 = h2 = pos_window (> 0)
+ *   profile 0 (sign):   s_j = sign(u_j) if 0 < |u_j| <= h_j, else 0        profile 1 (linear): s_j = clamp(u_j / h_j, -1, 1)
+ *   field[r][j] = float32(weight[j] * s_j), the product formed in double and rounded once.
+ * The sign is the roll-out's (state += logits * scale): a positive entry rewards motion toward the goal.  A window out of range, a
+ * non-finite goal or weight, an unknown profile: DGDM_EINVAL.  Reads the goals back once (one stream synchronisation).             */
+typedef struct DgdmGoalSpec { float weight[3]; float ori_window; float pos_window; int32_t profile; /* 0 sign, 1 linear */ } DgdmGoalSpec;
+int dgdm_guidance_goal_field(DgdmGuidance *g, const float *goals_dev, const DgdmGoalSpec *specs_host, int n_chains, float *field_dev, void *stream);
 
 /* Forward-only scoring on the cond_fn grid: Diffusion.cond_fn's forward half (generator/diffusion.py:473-504: the classifier on every
  * (finger, orientation, position) row at one timestep) and, per (chain, finger), the tally of the classes :506-532 assigns
