@@ -63,6 +63,9 @@ PROTOTYPES = {
     "dgdm_unet1d_create": (C.c_int, [C.POINTER(_P), C.POINTER(Tensor), C.c_int, C.POINTER(C.c_int32), C.c_int, C.c_int, C.c_int, C.c_int]),
     "dgdm_unet1d_destroy": (None, [_P]),
     "dgdm_unet1d_forward": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, _P]),
+    "dgdm_unet1d_global_cond_dim": (C.c_int, [_P]),
+    "dgdm_unet1d_forward_cond": (C.c_int, [_P, _P, _P, _P, _P, C.c_int, C.c_int, _P]),
+    "dgdm_cfg_mix": (C.c_int, [_P, _P, C.c_float, _P, C.c_int64, _P]),
     "dgdm_ddim_guided_step": (C.c_int, [_P, _P, _P, C.c_int, _P, C.c_int64, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, _P]),
     "dgdm_ddim_add_noise": (C.c_int, [_P, _P, _P, C.c_int64, C.c_float, C.c_float, _P]),
     "dgdm_dynamics_create": (C.c_int, [C.POINTER(_P), C.c_int, C.POINTER(Tensor), C.c_int, C.c_int, C.c_int]),
@@ -94,6 +97,8 @@ PROTOTYPES = {
     "dgdm_guidance_score": (C.c_int, [_P, _P, C.c_int, C.POINTER(C.c_int32), _P, C.POINTER(C.c_float), C.c_int, _P, _P, _P, _P]),
     "dgdm_guided_chains_run": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.POINTER(Objective), _P, _P, C.POINTER(C.c_int32), C.POINTER(C.c_float),
                                          C.POINTER(C.c_float), C.c_int, _P, _P]),
+    "dgdm_guided_chains_run_cond": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.POINTER(Objective), _P, _P, C.POINTER(C.c_int32), C.POINTER(C.c_float),
+                                              C.POINTER(C.c_float), C.c_int, _P, _P, C.c_int64, C.c_float, _P]),
     "dgdm_guidance_orientation_sweep": (C.c_int, [_P, _P, _P, _P, C.c_int, _P, _P]),
     "dgdm_guidance_rollout": (C.c_int, [_P, _P, C.POINTER(C.c_int32), _P, C.POINTER(C.c_double), C.c_int, C.c_int, _P, _P, _P, _P, _P, _P]),
     "dgdm_guidance_debug_rollout_table": (C.c_int, [_P, C.c_int, _P, _P, C.POINTER(C.c_int32), C.POINTER(C.c_int32), _P]),
@@ -125,6 +130,9 @@ PROTOTYPES = {
     "dgdm_unet_trainer_destroy": (None, [_P]),
     "dgdm_unet_trainer_step": (C.c_int, [_P, _P, _P, _P, _P, _P, C.c_int, C.c_float, _P, C.POINTER(C.c_float), _P]),
     "dgdm_unet_trainer_forward_backward": (C.c_int, [_P, _P, _P, _P, _P, _P, C.c_int, C.c_int64, C.c_int, _P, C.POINTER(C.c_float), _P]),
+    "dgdm_unet_trainer_step_cond": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, C.c_int, C.c_float, _P, C.POINTER(C.c_float), _P]),
+    "dgdm_unet_trainer_forward_backward_cond": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, C.c_int, C.c_int64, C.c_int, _P, C.POINTER(C.c_float), _P]),
+    "dgdm_unet_trainer_global_cond_dim": (C.c_int, [_P]),
     "dgdm_unet_trainer_gradient_count": (C.c_int64, [_P]),
     "dgdm_unet_trainer_gradients": (C.c_int, [_P, _P, C.c_int64, C.c_int, C.c_float, _P]),
     "dgdm_unet_trainer_apply": (C.c_int, [_P, C.c_float, _P]),

@@ -74,6 +74,7 @@ struct DgdmGuidance {
     // so the A table carries one float32 rounding); ttmp64: scratch of the time encoder
     DevBuf V, genc, atab, chainbias, timepart, ttmp, ttmp64, partial, objdev, objidx, xobj, xobj16, starts, order, xchains, todo, groupoff;
     DevBuf loopx[2], loopeps, loopgrad, loopxrep, loopts;      // workspace of dgdm_guided_chains_run
+    DevBuf loopcond, loopx2, loopeps2;                         // ... with a condition: [cond rows | zero rows], and the doubled batch of the classifier-free mix
     DevBuf scorelogits;                      // dgdm_guidance_score: the logits when the caller does not want them
     // dgdm_guidance_rollout: the sweep's orientations [G] (built with the handle), and its scratch, grown on demand: the state
     // [n][B*G][3] doubles, one interaction's logits, the per-row pose operand tiles [ntiles][W1*32] and (3-D) their row maxima [ntiles][32]
@@ -908,12 +909,35 @@ __global__ void repeat_rows_kernel(const float *__restrict__ src, float *__restr
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n_src * reps) dst[i] = src[i % n_src];
 }
+// classifier-free guidance: eps_u + w (eps_c - eps_u), every operation rounded on its own (common.h add_rn / mul_rn: never contracted into an fma)
+__global__ void cfg_mix_kernel(const float *ec, const float *eu, float w, float *out, int64_t n) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const float u = eu[i];
+    out[i] = add_rn(u, mul_rn(w, sub_rn(ec[i], u)));
+}
 }  // namespace
+
+extern "C" int dgdm_cfg_mix(const float *eps_c_dev, const float *eps_u_dev, float w, float *out_dev, int64_t numel, void *stream) {
+    DGDM_REQUIRE(eps_c_dev && eps_u_dev && out_dev && numel >= 0, DGDM_EINVAL, "dgdm_cfg_mix: bad argument");
+    if (numel == 0) return DGDM_OK;
+    hipLaunchKernelGGL(cfg_mix_kernel, dim3((unsigned)((numel + 255) / 256)), dim3(256), 0, (hipStream_t)stream, eps_c_dev, eps_u_dev, w, out_dev, numel);
+    DGDM_HIP_CHECK(hipGetLastError());
+    return DGDM_OK;
+}
 
 extern "C" int dgdm_guided_chains_run(DgdmUnet1d *unet, DgdmGuidance *g, const float *noise_dev, int n_chains, int n_grad,
                                       const DgdmObjective *objectives, const float *rowcoef_dev, const int64_t *starts_host,
                                       const int32_t *timesteps, const float *coef, const float *scales, int n_steps, float *x_out_dev,
                                       void *stream) {
+    return dgdm_guided_chains_run_cond(unet, g, noise_dev, n_chains, n_grad, objectives, rowcoef_dev, starts_host, timesteps, coef, scales, n_steps, x_out_dev,
+                                       nullptr, 0, 1.f, stream);
+}
+
+extern "C" int dgdm_guided_chains_run_cond(DgdmUnet1d *unet, DgdmGuidance *g, const float *noise_dev, int n_chains, int n_grad,
+                                           const DgdmObjective *objectives, const float *rowcoef_dev, const int64_t *starts_host,
+                                           const int32_t *timesteps, const float *coef, const float *scales, int n_steps, float *x_out_dev,
+                                           const float *global_cond_dev, int64_t cond_chain_stride, float cfg_weight, void *stream) {
     DGDM_REQUIRE(unet && g && noise_dev && objectives && timesteps && coef && scales && x_out_dev, DGDM_EINVAL, "dgdm_guided_chains_run: null argument");
     DGDM_REQUIRE(n_chains > 0 && n_grad > 0 && n_chains * n_grad <= g->cfg.max_chains && n_steps > 0, DGDM_EINVAL,
                  "dgdm_guided_chains_run: %d chains x %d gradients outside 1..%d", n_chains, n_grad, g->cfg.max_chains);
@@ -921,11 +945,33 @@ extern "C" int dgdm_guided_chains_run(DgdmUnet1d *unet, DgdmGuidance *g, const f
     const int B = g->B, L = g->m->L, kind = g->m->kind;
     const size_t per_chain = (size_t)B * L, nx = per_chain * n_chains, ng = nx * n_grad;
     DGDM_REQUIRE(kind == 2 || starts_host, DGDM_EINVAL, "3-D guidance needs the FPS start indices");
+    const int gc = dgdm_unet1d_global_cond_dim(unet);
+    DGDM_REQUIRE(gc == 0 || global_cond_dev, DGDM_EINVAL, "dgdm_guided_chains_run: the eps-net has global_cond_dim %d and needs a condition", gc);
+    DGDM_REQUIRE(cfg_weight == cfg_weight && std::fabs(cfg_weight) <= 3.0e38f, DGDM_EINVAL, "dgdm_guided_chains_run: cfg_weight is not finite");
+    const bool conditional = gc > 0;
+    DGDM_REQUIRE(!conditional || cond_chain_stride == 0 || cond_chain_stride == (int64_t)B * gc, DGDM_EINVAL,
+                 "dgdm_guided_chains_run: cond_chain_stride %lld is neither 0 (one [B][%d] block for all chains) nor B * gc = %lld", (long long)cond_chain_stride, gc,
+                 (long long)B * gc);
+    const bool per_chain_cond = conditional && cond_chain_stride != 0 && n_chains > 1;
+    // what the eps-net evaluates: 1 the condition rows, 0 the all-zero rows, 2 both in one call of twice the samples, mixed afterwards
+    const int cfg = !conditional ? 1 : cfg_weight == 1.f ? 1 : cfg_weight == 0.f ? 0 : 2;
     int rc;
     if ((rc = check_objectives(g, objectives, rowcoef_dev, n_chains * n_grad))) return rc;      // before the first launch of the loop
     if ((rc = g->loopx[0].alloc(nx * 4)) || (rc = g->loopx[1].alloc(nx * 4)) || (rc = g->loopeps.alloc(nx * 4)) || (rc = g->loopgrad.alloc(ng * 4)) ||
-        (rc = g->loopxrep.alloc(ng * 4)) || (rc = g->loopts.alloc((size_t)n_chains * B * sizeof(int))))
+        (rc = g->loopxrep.alloc(ng * 4)) || (rc = g->loopts.alloc((size_t)2 * n_chains * B * sizeof(int))))
         return rc;
+    // condition rows of all n_chains * B samples, then as many all-zero rows (the unconditional half of the classifier-free mix)
+    const size_t ncond = (size_t)n_chains * B * gc;
+    const float *cond_rows = nullptr, *zero_rows = nullptr;
+    if (conditional) {
+        if ((rc = g->loopcond.alloc(2 * ncond * 4))) return rc;
+        float *cr = g->loopcond.as<float>();
+        if (cond_chain_stride == 0) hipLaunchKernelGGL(repeat_rows_kernel, dim3((unsigned)((ncond + 255) / 256)), dim3(256), 0, s, global_cond_dev, cr, (int64_t)B * gc, n_chains);
+        else DGDM_HIP_CHECK(hipMemcpyAsync(cr, global_cond_dev, ncond * 4, hipMemcpyDeviceToDevice, s));
+        DGDM_HIP_CHECK(hipMemsetAsync(cr + ncond, 0, ncond * 4, s));
+        cond_rows = cr; zero_rows = cr + ncond;
+        if (cfg == 2 && ((rc = g->loopx2.alloc(2 * nx * 4)) || (rc = g->loopeps2.alloc(2 * nx * 4)))) return rc;
+    }
     // every chain starts from the same noise (generator/diffusion.py:570)
     hipLaunchKernelGGL(repeat_rows_kernel, dim3((unsigned)((nx + 255) / 256)), dim3(256), 0, s, noise_dev, g->loopx[0].as<float>(), (int64_t)per_chain, n_chains);
     bool same_scale = true;
@@ -951,10 +997,26 @@ extern "C" int dgdm_guided_chains_run(DgdmUnet1d *unet, DgdmGuidance *g, const f
         const int t = timesteps[si];
         if (kind == 3 && si % cpe == 0 &&
             (rc = g->embed(oidx.data(), n_chains * n_grad, starts_host + (size_t)si * call_stride, std::min(cpe, n_steps - si), call_stride, &emb, s))) return rc;
-        // eps-net: at the first step all chains hold the same B fingers - one evaluation, replicated (same input, same bits)
-        const int nb = (si == 0 && n_chains > 1) ? B : n_chains * B;
-        hipLaunchKernelGGL(fill_i32_kernel, dim3((nb + 255) / 256), dim3(256), 0, s, g->loopts.as<int>(), t, nb);
-        if ((rc = dgdm_unet1d_forward(unet, x, g->loopts.as<int>(), g->loopeps.as<float>(), nb, L, s))) return rc;
+        // eps-net: at the first step all chains hold the same B fingers - one evaluation, replicated (same input, same bits) - unless
+        // every chain has condition rows of its own
+        const int nb = (si == 0 && n_chains > 1 && !per_chain_cond) ? B : n_chains * B;
+        const int ne = cfg == 2 ? 2 * nb : nb;
+        hipLaunchKernelGGL(fill_i32_kernel, dim3((ne + 255) / 256), dim3(256), 0, s, g->loopts.as<int>(), t, ne);
+        if (cfg == 2) {
+            // [x | x] with [condition rows | zero rows] in one call (large runs land in the batched form), then the mix
+            const size_t n = (size_t)nb * L, nc = (size_t)nb * gc;
+            float *x2 = g->loopx2.as<float>(), *e2 = g->loopeps2.as<float>(), *c2 = g->loopcond.as<float>();
+            DGDM_HIP_CHECK(hipMemcpyAsync(x2, x, n * 4, hipMemcpyDeviceToDevice, s));
+            DGDM_HIP_CHECK(hipMemcpyAsync(x2 + n, x, n * 4, hipMemcpyDeviceToDevice, s));
+            // the zero half has to follow the nb condition rows directly: at full size it does (loopcond's layout), at step 0's B rows it is moved up
+            if (nc != ncond) DGDM_HIP_CHECK(hipMemsetAsync(c2 + nc, 0, nc * 4, s));
+            if ((rc = dgdm_unet1d_forward_cond(unet, x2, g->loopts.as<int>(), c2, e2, 2 * nb, L, s))) return rc;
+            if (nc != ncond) {       // restore chain 1's rows for the steps that follow
+                if (cond_chain_stride == 0) hipLaunchKernelGGL(repeat_rows_kernel, dim3((unsigned)((ncond + 255) / 256)), dim3(256), 0, s, global_cond_dev, c2, (int64_t)B * gc, n_chains);
+                else DGDM_HIP_CHECK(hipMemcpyAsync(c2, global_cond_dev, ncond * 4, hipMemcpyDeviceToDevice, s));
+            }
+            if ((rc = dgdm_cfg_mix(e2, e2 + n, cfg_weight, g->loopeps.as<float>(), (int64_t)n, s))) return rc;
+        } else if ((rc = dgdm_unet1d_forward_cond(unet, x, g->loopts.as<int>(), cfg == 0 ? zero_rows : cond_rows, g->loopeps.as<float>(), nb, L, s))) return rc;
         if (nb != n_chains * B) {
             // replicate in place from the back so that the source block [0, per_chain) is read before it could be overwritten: separate buffer instead
             hipLaunchKernelGGL(repeat_rows_kernel, dim3((unsigned)((nx + 255) / 256)), dim3(256), 0, s, g->loopeps.as<float>(), g->loopgrad.as<float>(), (int64_t)per_chain, n_chains);

@@ -109,8 +109,8 @@ struct ResOff { size_t c0w, c0b, g0w, g0b, c1w, c1b, g1w, g1b, cw, cb, rw, rb; b
                 size_t c0w16 = 0, c1w16 = 0, rw16 = 0;         // element offsets of the bf16 images (MFMA convolutions only)
                 size_t c0wh = 0, c1wh = 0, rwh = 0; int c0e = 0, c1e = 0, re = 0; };      // ... of the f16x3 images and their scale exponents
 
-int pack_res(const StateDict &sd, Blob &bl, std::vector<uint16_t> &b16, std::vector<uint16_t> &bh, const std::string &p, int cin, int cout, int cond, int kw,
-             ResOff *o) {
+int pack_res(const StateDict &sd, Blob &bl, std::vector<uint16_t> &b16, std::vector<uint16_t> &bh, const std::string &p, int cin, int cout, int cond,
+             int cond_rows /* >= cond: rows of the transposed cond_encoder weight, zero past cond */, int kw, ResOff *o) {
     auto vec = [&](const std::string &k, int64_t n, size_t *off) -> int {
         const float *d = sd.f32(k, n);
         if (!d) return DGDM_EKEY;
@@ -142,7 +142,11 @@ int pack_res(const StateDict &sd, Blob &bl, std::vector<uint16_t> &b16, std::vec
     if ((rc = vec(p + ".blocks.1.block.1.weight", cout, &o->g1w))) return rc;
     if ((rc = vec(p + ".blocks.1.block.1.bias", cout, &o->g1b))) return rc;
     if (!(w = sd.f32(p + ".cond_encoder.1.weight", (int64_t)2 * cout * cond))) return DGDM_EKEY;
-    o->cw = bl.add(transpose(w, 2 * cout, cond));
+    {
+        std::vector<float> wt = transpose(w, 2 * cout, cond);
+        wt.resize((size_t)cond_rows * 2 * cout, 0.f);
+        o->cw = bl.add(wt);
+    }
     if ((rc = vec(p + ".cond_encoder.1.bias", 2 * cout, &o->cb))) return rc;
     o->has_res = cin != cout;
     if (o->has_res) {
@@ -174,8 +178,22 @@ extern "C" int dgdm_unet1d_create(DgdmUnet1d **out, const DgdmTensor *tensors, i
         {"down_modules.0.0", 1, d0}, {"down_modules.0.1", d0, d0}, {"down_modules.1.0", d0, d1}, {"down_modules.1.1", d1, d1},
         {"mid_modules.0", d1, d1}, {"mid_modules.1", d1, d1}, {"up_modules.0.0", 2 * d1, d0}, {"up_modules.0.1", d0, d0}};
     int rc;
+    // global_cond_dim: what the cond encoders' Linear takes beyond the step embedding (diffusion_utils.py:141-142)
+    int gc = -1;
+    for (int i = 0; i < 8; ++i) {
+        const std::string key = std::string(spec[i].name) + ".cond_encoder.1.weight";
+        auto it = sd.m.find(key);
+        if (it == sd.m.end()) { set_error("state_dict key '%s' missing", key.c_str()); return DGDM_EKEY; }
+        const int64_t numel = it->second->numel, rows = 2 * (int64_t)spec[i].cout;
+        const int64_t g = numel % rows == 0 ? numel / rows - dsed : -1;
+        DGDM_REQUIRE(g >= 0 && g <= 256, DGDM_EINVAL, "%s: %lld values are not [%lld][%d + global_cond_dim] with 0 <= global_cond_dim <= 256", key.c_str(),
+                     (long long)numel, (long long)rows, dsed);
+        DGDM_REQUIRE(gc < 0 || g == gc, DGDM_EINVAL, "%s: global_cond_dim %lld differs from the %d of the blocks before it", key.c_str(), (long long)g, gc);
+        gc = (int)g;
+    }
+    const int gcp = (gc + 7) & ~7;
     for (int i = 0; i < 8; ++i)
-        if ((rc = pack_res(sd, bl, b16, bh, spec[i].name, spec[i].cin, spec[i].cout, dsed, kernel_size, &ro[i]))) return rc;
+        if ((rc = pack_res(sd, bl, b16, bh, spec[i].name, spec[i].cin, spec[i].cout, dsed + gc, dsed + gcp, kernel_size, &ro[i]))) return rc;
     const float *w, *b;
     // diffusion_step_encoder
     std::vector<float> fr(dsed / 2);
@@ -216,6 +234,7 @@ extern "C" int dgdm_unet1d_create(DgdmUnet1d **out, const DgdmTensor *tensors, i
     UnetParams &p = m->p;
     memset(&p, 0, sizeof p);
     p.d0 = d0; p.d1 = d1; p.dsed = dsed; p.groups = n_groups; p.cmax = std::max(d0, d1);
+    p.gc = gc; p.gcp = gcp;
     p.freqs = bl.at(o_fr);
     p.se1_wt = bl.at(o_s1w); p.se1_b = bl.at(o_s1b); p.se3_wt = bl.at(o_s3w); p.se3_b = bl.at(o_s3b);
     for (int i = 0; i < 8; ++i) {
@@ -266,9 +285,19 @@ extern "C" int dgdm_unet1d_create(DgdmUnet1d **out, const DgdmTensor *tensors, i
 
 extern "C" void dgdm_unet1d_destroy(DgdmUnet1d *m) { delete m; }
 
+extern "C" int dgdm_unet1d_global_cond_dim(const DgdmUnet1d *m) { return m ? m->p.gc : -1; }
+
 extern "C" int dgdm_unet1d_forward(DgdmUnet1d *m, const float *sample_dev, const int32_t *timestep_dev, float *eps_dev, int B, int L,
                                    void *stream) {
+    return dgdm_unet1d_forward_cond(m, sample_dev, timestep_dev, nullptr, eps_dev, B, L, stream);
+}
+
+extern "C" int dgdm_unet1d_forward_cond(DgdmUnet1d *m, const float *sample_dev, const int32_t *timestep_dev, const float *global_cond_dev, float *eps_dev,
+                                        int B, int L, void *stream) {
     DGDM_REQUIRE(m && sample_dev && timestep_dev && eps_dev && B >= 0 && L > 0, DGDM_EINVAL, "dgdm_unet1d_forward: bad argument");
+    DGDM_REQUIRE(m->p.gc == 0 || global_cond_dev, DGDM_EINVAL, "dgdm_unet1d_forward: this eps-net has global_cond_dim %d and needs a condition [B][%d]", m->p.gc,
+                 m->p.gc);
+    if (m->p.gc == 0) global_cond_dev = nullptr;      // nothing to condition on
     // useful multiply-adds of one forward (82.0 M per sample at L = 42, 27.4 M at L = 14; the convolutions
     // scale with L, the step encoder / FiLM linears are a 0.3 M constant)
     const double macs = 0.3e6 + (82.0e6 - 0.3e6) * (double)L / 42.0;
@@ -285,11 +314,11 @@ extern "C" int dgdm_unet1d_forward(DgdmUnet1d *m, const float *sample_dev, const
             DGDM_HIP_CHECK(hipMemsetAsync(m->bws.p, 0, n * sizeof(float), (hipStream_t)stream));      // the halo rows stay zero: no launch writes them
             m->bws_B = B; m->bws_L = L;
         }
-        rc = unet_launch_batched(m->pf16, m->pf16_dev.as<UnetParams>(), m->bws.as<float>(), m->bws_B, sample_dev, timestep_dev, eps_dev, B, L, (hipStream_t)stream);
+        rc = unet_launch_batched(m->pf16, m->pf16_dev.as<UnetParams>(), m->bws.as<float>(), m->bws_B, sample_dev, timestep_dev, global_cond_dev, eps_dev, B, L, (hipStream_t)stream);
         prof_end((hipStream_t)stream, DGDM_STAGE_UNET, 2.0 * macs * B);
         return rc;
     }
-    const int rc = unet_launch(m->p, (mode == 1 ? m->p16_dev : mode == 2 ? m->pf16_dev : m->p_dev).as<UnetParams>(), mode == 2, sample_dev, timestep_dev, eps_dev, B, L, (hipStream_t)stream);
+    const int rc = unet_launch(m->p, (mode == 1 ? m->p16_dev : mode == 2 ? m->pf16_dev : m->p_dev).as<UnetParams>(), mode == 2, sample_dev, timestep_dev, global_cond_dev, eps_dev, B, L, (hipStream_t)stream);
     prof_end((hipStream_t)stream, DGDM_STAGE_UNET, 2.0 * macs * B);
     return rc;
 }

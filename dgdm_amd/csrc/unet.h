@@ -9,13 +9,14 @@ struct UnetRes {
     int cin, cout;
     const float *c0_w, *c0_b, *g0_w, *g0_b;      // blocks.0: Conv1d k5 (image; [tap][cout] when cin == 1), GroupNorm
     const float *c1_w, *c1_b, *g1_w, *g1_b;      // blocks.1
-    const float *cond_wt, *cond_b;               // cond_encoder.1: Linear(cond_dim, 2*cout)
+    const float *cond_wt, *cond_b;               // cond_encoder.1: Linear(dsed + gc, 2*cout), [dsed + gcp][2*cout] (rows past dsed + gc are zero)
     const float *res_w, *res_b;                  // residual_conv 1x1 (image; [cout] when cin == 1) or null
     int c0_e, c1_e, res_e;                       // f16x3 images: the convolution's weights are stored times 2^e (unet.hip conv_mfma_f16x3)
 };
 
 struct UnetParams {
     int d0, d1, dsed, groups, cmax;
+    int gc, gcp;                                 // global_cond_dim and the same rounded up to a multiple of 8 (dot_kn's step); 0: unconditional
     int bf16;                                    // what the MFMA convolution images are: 0 float32 (conv_mfma), 1 bf16 (conv_mfma_bf16), 2 two f16 pieces (conv_mfma_f16x3)
     int down_e, up_e_even, up_e_odd, fin_e;      // f16x3: scale exponents of the images below
     const float *freqs;                          // SinusoidalPosEmb frequencies [dsed/2]
@@ -29,12 +30,15 @@ struct UnetParams {
 
 // p: host copy (sizes); p_dev: the same struct in device memory (what the kernel reads)
 // f16x3: p_dev holds the two-piece f16 images (the kernel then needs LDS for the split slabs: unet_f16x3_fits)
-int unet_launch(const UnetParams &p, const UnetParams *p_dev, bool f16x3, const float *sample, const int *timestep, float *eps, int B, int L, hipStream_t s);
+// gcond: [B][p.gc] global condition rows (null when p.gc == 0)
+int unet_launch(const UnetParams &p, const UnetParams *p_dev, bool f16x3, const float *sample, const int *timestep, const float *gcond, float *eps, int B, int L,
+                hipStream_t s);
 bool unet_f16x3_fits(const UnetParams &p, int L);
 // Batched form for large batches (f16x3 only; unet.hip "batched form"): layer-by-layer launches, several samples per workgroup, activations in a
 // zero-initialised global workspace.  unet_batched_samples: samples per workgroup, 0 when the shape is not supported.
 int unet_batched_samples(const UnetParams &p, int L);
 size_t unet_batched_ws_floats(const UnetParams &p, int B, int L);
-int unet_launch_batched(const UnetParams &q, const UnetParams *q_dev, float *ws, int Bcap, const float *sample, const int *timestep, float *eps, int B, int L, hipStream_t s);
+int unet_launch_batched(const UnetParams &q, const UnetParams *q_dev, float *ws, int Bcap, const float *sample, const int *timestep, const float *gcond, float *eps, int B,
+                        int L, hipStream_t s);
 
 }  // namespace dgdm

@@ -612,7 +612,8 @@ __device__ void res_block(const UnetRes &w, const lds_f *in, lds_f *t1, lds_f *o
 // `pp` points at the UnetParams in device memory: passing the struct by value and handing references to its members to the
 // (non-inlined) block functions made the compiler copy all 1.1 KB of it to scratch in every thread.
 __global__ __launch_bounds__(UNET_THREADS) void unet_kernel(const UnetParams *__restrict__ pp, int bufA, int bufS, const float *__restrict__ sample,
-                                                   const int *__restrict__ timestep, float *__restrict__ eps, int L, int slab_groups) {
+                                                   const int *__restrict__ timestep, const float *__restrict__ gcond, float *__restrict__ eps, int L,
+                                                   int slab_groups) {
     extern __shared__ __attribute__((aligned(16))) float lds_raw[];
     lds_f *lds = (lds_f *)lds_raw;
     const UnetParams &p = *pp;
@@ -626,7 +627,7 @@ __global__ __launch_bounds__(UNET_THREADS) void unet_kernel(const UnetParams *__
     s.film = s.D + bufS;
     s.cond = s.film + 8 * 2 * p.cmax;
     s.tmp = s.cond + p.dsed;
-    s.xin = s.tmp + 4 * p.dsed;
+    s.xin = s.tmp + max(4 * p.dsed, p.gcp);       // the global condition takes over tmp once the step encoder is done with it: cond | tmp = cat(step, global)
     s.scr = s.xin + ((L + 4 + 3) & ~3);            // f16x3: 16 floats for the scale reduction, then the activation slab(s)
     s.bf16 = p.bf16;
     s.slab_groups = slab_groups;
@@ -649,6 +650,9 @@ __global__ __launch_bounds__(UNET_THREADS) void unet_kernel(const UnetParams *__
         matvec(p.se3_wt, p.se3_b, s.tmp, s.cond, 4 * p.dsed, p.dsed);
         __syncthreads();
         for (int i = t; i < p.dsed; i += blockDim.x) s.cond[i] = mish(s.cond[i]);   // every cond_encoder starts with Mish (:90-92)
+        // ... and it is applied to cat(step embedding, global_cond) (:254-257): the global part goes behind the step part (tmp was last
+        // read before the barrier above), zeros up to the multiple of 8 that dot_kn steps by (their weight rows are zero too)
+        for (int i = t; i < p.gcp; i += blockDim.x) s.tmp[i] = i < p.gc ? mish(gcond[(size_t)b * p.gc + i]) : 0.f;
     }
     for (int i = t; i < L + 4; i += blockDim.x) s.xin[i] = (i >= 2 && i < 2 + L) ? sample[(size_t)b * L + i - 2] : 0.f;
     __syncthreads();
@@ -660,7 +664,7 @@ __global__ __launch_bounds__(UNET_THREADS) void unet_kernel(const UnetParams *__
         for (int i = t; i < 8 * stride; i += blockDim.x) {
             const int blk = i / stride, n = i - blk * stride, N = 2 * p.res[blk].cout;
             if (n < N) {
-                films[i] = dot_kn(p.res[blk].cond_wt, N, n, s.cond, p.dsed) + p.res[blk].cond_b[n];
+                films[i] = dot_kn(p.res[blk].cond_wt, N, n, s.cond, p.dsed + p.gcp) + p.res[blk].cond_b[n];
             }
         }
     }
@@ -1025,15 +1029,18 @@ __global__ __launch_bounds__(UB_THREADS) void ub_layer_kernel(const UbArgs A) {
     if (t < ns && A.amax_out) A.amax_out[b0 + t] = __uint_as_float(amx[t]);
 }
 
-// step encoder + the eight FiLM vectors of every sample (unet_kernel's first two phases): film [B][8][2 cmax].  They depend on the sample's
-// timestep only, and a denoise step hands every sample the same one: a sample whose timestep equals sample 0's takes sample 0's row
-// (film_idx) instead of recomputing it (1024 workgroups of dependent L2 round trips -> one: 53 -> 6 us).
-__global__ __launch_bounds__(256) void ub_cond_kernel(const UnetParams *__restrict__ pp, const int *__restrict__ timestep, float *__restrict__ film, int *__restrict__ film_idx) {
-    __shared__ float cond_raw[32 * 5 + 8];
+// step encoder + the eight FiLM vectors of every sample (unet_kernel's first two phases): film [B][8][2 cmax].  Without a global condition
+// they depend on the sample's timestep only, and a denoise step hands every sample the same one: a sample whose timestep equals sample 0's
+// takes sample 0's row (film_idx) instead of recomputing it (1024 workgroups of dependent L2 round trips -> one: 53 -> 6 us).  With a
+// condition (gcond [B][gc]) every sample has its own row.
+constexpr int UB_GC_MAX = 256;
+__global__ __launch_bounds__(256) void ub_cond_kernel(const UnetParams *__restrict__ pp, const int *__restrict__ timestep, const float *__restrict__ gcond,
+                                                      float *__restrict__ film, int *__restrict__ film_idx) {
+    __shared__ float cond_raw[32 + UB_GC_MAX + 8];       // cond [dsed <= 32] | tmp [max(4 dsed, gcp)]
     const UnetParams &p = *pp;
     lds_f *cond = (lds_f *)cond_raw, *tmp = cond + p.dsed;
     const int b = blockIdx.x, t = threadIdx.x;
-    const bool same = b > 0 && timestep[b] == timestep[0];
+    const bool same = !gcond && b > 0 && timestep[b] == timestep[0];
     if (t == 0) film_idx[b] = same ? 0 : b;
     if (same) return;
     const int half = p.dsed / 2;
@@ -1051,11 +1058,12 @@ __global__ __launch_bounds__(256) void ub_cond_kernel(const UnetParams *__restri
     matvec(p.se3_wt, p.se3_b, tmp, cond, 4 * p.dsed, p.dsed);
     __syncthreads();
     for (int i = t; i < p.dsed; i += blockDim.x) cond[i] = mish(cond[i]);
+    for (int i = t; i < p.gcp; i += blockDim.x) tmp[i] = i < p.gc ? mish(gcond[(size_t)b * p.gc + i]) : 0.f;      // as unet_kernel: cond | tmp = cat(step, global)
     __syncthreads();
     const int stride = 2 * p.cmax;
     for (int i = t; i < 8 * stride; i += blockDim.x) {
         const int blk = i / stride, n = i - blk * stride, N = 2 * p.res[blk].cout;
-        if (n < N) film[(size_t)b * 8 * stride + i] = dot_kn(p.res[blk].cond_wt, N, n, cond, p.dsed) + p.res[blk].cond_b[n];
+        if (n < N) film[(size_t)b * 8 * stride + i] = dot_kn(p.res[blk].cond_wt, N, n, cond, p.dsed + p.gcp) + p.res[blk].cond_b[n];
     }
 }
 
@@ -1067,7 +1075,7 @@ static size_t ub_lds_bytes(int S, int Lin, int Lout, int cout) {
 // samples per workgroup: the most (<= 4) for which every launch fits the LDS and a half of the waves holds at most 6 position tiles
 int unet_batched_samples(const UnetParams &p, int L) {
     const int L2 = (L - 1) / 2 + 1;
-    if (p.dsed > 32 || p.d0 != 128 || p.d1 != 256) return 0;       // the tilings above are written for the shipped widths (down_dims [128, 256])
+    if (p.dsed > 32 || p.gcp > UB_GC_MAX || p.d0 != 128 || p.d1 != 256) return 0;       // the tilings above are written for the shipped widths (down_dims [128, 256])
     if (2 * L2 != L) return 0;                                      // odd lengths: the per-sample kernel (selection, launch and effective_form agree)
     for (int S = 4; S >= 2; --S) {
         const bool fits = ub_lds_bytes(S, L, L, p.d0) <= 160 * 1024 && ub_lds_bytes(S, L2, L2, p.d1) <= 160 * 1024 && ub_lds_bytes(S, L2, L, p.d0) <= 160 * 1024 &&
@@ -1084,7 +1092,8 @@ size_t unet_batched_ws_floats(const UnetParams &p, int B, int L) {
 
 // q: the host copy of the f16x3 parameter block (images + per-channel factors), q_dev the same in device memory; ws: zero-initialised
 // workspace of unet_batched_ws_floats floats (the halo rows are never written)
-int unet_launch_batched(const UnetParams &q, const UnetParams *q_dev, float *ws, int Bcap, const float *sample, const int *timestep, float *eps, int B, int L, hipStream_t s) {
+int unet_launch_batched(const UnetParams &q, const UnetParams *q_dev, float *ws, int Bcap, const float *sample, const int *timestep, const float *gcond, float *eps, int B,
+                        int L, hipStream_t s) {
     const int L2 = (L - 1) / 2 + 1, S = unet_batched_samples(q, L);
     DGDM_REQUIRE(S > 0 && 2 * L2 == L && B <= Bcap, DGDM_EINVAL, "unet_launch_batched: unsupported shape (L = %d, B = %d of %d)", L, B, Bcap);
     const int d0 = q.d0, d1 = q.d1;
@@ -1100,7 +1109,8 @@ int unet_launch_batched(const UnetParams &q, const UnetParams *q_dev, float *ws,
         attr_set = true;
     }
     int *fidx = reinterpret_cast<int *>(am + (size_t)10 * Bcap);
-    hipLaunchKernelGGL(ub_cond_kernel, dim3(B), dim3(256), 0, s, q_dev, timestep, film, fidx);
+    DGDM_REQUIRE((q.gc > 0) == (gcond != nullptr), DGDM_EINVAL, "unet_launch_batched: global condition %s for global_cond_dim %d", gcond ? "given" : "missing", q.gc);
+    hipLaunchKernelGGL(ub_cond_kernel, dim3(B), dim3(256), 0, s, q_dev, timestep, gcond, film, fidx);
     const int fl = 8 * 2 * q.cmax;
     auto conv5 = [&](const float *in, int in_ld, int Lin, int cin, const float *img, const float *bias, const float *a0, const float *a1) {
         UbPass a{};
@@ -1174,13 +1184,15 @@ static size_t unet_lds_floats(const UnetParams &p, int L) {
     const int L2 = (L - 1) / 2 + 1;
     const int bufS = std::max((L + 4) * (p.d0 + UNET_ROW_PAD), (L2 + 4) * (p.d1 + UNET_ROW_PAD));
     const int bufA = std::max((L + 4) * (p.d0 + UNET_ROW_PAD), (L2 + 4) * (2 * p.d1 + UNET_ROW_PAD));
-    return (size_t)bufA + 3 * (size_t)bufS + 8 * 2 * p.cmax + p.dsed + 4 * p.dsed + (L + 4 + 3) + 16;
+    return (size_t)bufA + 3 * (size_t)bufS + 8 * 2 * p.cmax + p.dsed + std::max(4 * p.dsed, p.gcp) + (L + 4 + 3) + 16;
 }
 static size_t unet_slab_floats(int L) { return 16 + (size_t)UNET_SLAB_GROUPS * (L + 4) * 32; }
 
 bool unet_f16x3_fits(const UnetParams &p, int L) { return (unet_lds_floats(p, L) + unet_slab_floats(L)) * 4 <= 160 * 1024; }
 
-int unet_launch(const UnetParams &p, const UnetParams *p_dev, bool f16x3, const float *sample, const int *timestep, float *eps, int B, int L, hipStream_t s) {
+int unet_launch(const UnetParams &p, const UnetParams *p_dev, bool f16x3, const float *sample, const int *timestep, const float *gcond, float *eps, int B, int L,
+                hipStream_t s) {
+    DGDM_REQUIRE((p.gc > 0) == (gcond != nullptr), DGDM_EINVAL, "unet_launch: global condition %s for global_cond_dim %d", gcond ? "given" : "missing", p.gc);
     if (B <= 0) return DGDM_OK;
     const int L2 = (L - 1) / 2 + 1;
     DGDM_REQUIRE(2 * L2 == L, DGDM_EINVAL, "U-Net needs an even number of control points (got %d): the skip concat of the reference "
@@ -1196,7 +1208,7 @@ int unet_launch(const UnetParams &p, const UnetParams *p_dev, bool f16x3, const 
         DGDM_HIP_CHECK(hipFuncSetAttribute((const void *)unet_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
         attr_set = true;
     }
-    hipLaunchKernelGGL(unet_kernel, dim3(B), dim3(UNET_THREADS), lds_floats * 4, s, p_dev, bufA, bufS, sample, timestep, eps, L, UNET_SLAB_GROUPS);
+    hipLaunchKernelGGL(unet_kernel, dim3(B), dim3(UNET_THREADS), lds_floats * 4, s, p_dev, bufA, bufS, sample, timestep, gcond, eps, L, UNET_SLAB_GROUPS);
     DGDM_HIP_CHECK(hipGetLastError());
     return DGDM_OK;
 }

@@ -175,6 +175,13 @@ __global__ void prep_kernel(const float *__restrict__ x0, const float *__restric
         emb[(int64_t)s * dsed + j] = j < half ? sinf(arg) : cosf(arg);
     }
 }
+// Mish of the global condition rows [S][gc] into [S][gcw] (gcw = gc rounded up to 4: aligned windows), zero columns past gc
+__global__ void cond_prep_kernel(const float *__restrict__ c, int S, int gc, int gcw, float *__restrict__ out) {
+    const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= (int64_t)S * gcw) return;
+    const int s = (int)(e / gcw), j = (int)(e - (int64_t)s * gcw);
+    out[e] = j < gc ? mish_f(c[(int64_t)s * gc + j]) : 0.f;
+}
 // F.mse_loss(noise_pred, noise) (diffusion.py:164): per-sample sums of squares, d loss / d pred = 2 (pred - noise) / (S_total L)
 __global__ void loss_kernel(const float *__restrict__ pred, const float *__restrict__ noise, int S, int L, int rp, int pad, float inv, float *__restrict__ dpred,
                             float *__restrict__ part, float *__restrict__ pred_out) {
@@ -211,6 +218,7 @@ struct DgdmUnetTrainer : ParamStore {      // parameters: one flat buffer in the
     DevBuf E /* EMA copy */, ws, freqs;
     WeightImages wimg{512};
     int L = 0, d0 = 128, d1 = 256, dsed = 32, ks = 5;
+    int gc = 0, gcw = 0;       // global_cond_dim; the width of t_gm's rows (gc rounded up to a multiple of 4)
     // ---- graph
     struct T { float *v = nullptr, *g = nullptr; int C = 0, lvl = 0; bool gw = false; };     // lvl 0: one row per sample; 1, 2: padded positions
     enum { S1 = 0, DOWN = 1, UP = 2 };
@@ -222,13 +230,14 @@ struct DgdmUnetTrainer : ParamStore {      // parameters: one flat buffer in the
     Res res[8];
     Conv se1, se3, down, up, fconv, oconv;
     size_t fg = 0;
-    T t_x0, t_emb, t_h1, t_a1, t_gf, t_mg, t_ds, t_us, t_cf, t_af, t_pred;
+    T t_x0, t_emb, t_h1, t_a1, t_gf, t_mg, t_gm /* Mish(global_cond), data: no gradient */, t_ds, t_us, t_cf, t_af, t_pred;
     float *f_st = nullptr, *f_sp = nullptr, *lpart = nullptr, *cpart = nullptr;
     int64_t S_ws = 0, M[3] = {0, 0, 0};
     RowMask mk[3];
 
     int add_img(size_t w_off, int Kblk, std::initializer_list<int> taps, int N, int s_kc, int s_n, int base) { return wimg.add((int64_t)w_off + base, Kblk, taps, N, s_kc, s_n); }
     void make_conv(Conv &c, const std::string &name, int kind, int k, int cin, int cout, int nparts = 1);
+    void make_cond(Conv &c, const std::string &name, int cout);
     int reserve(int S);
     int rowgemm(const float *A, int64_t a_rs, int img, float *C, int64_t c_rs, const float *add, int64_t add_rs, const float *bias, int64_t Mrows, int lvl,
                 hipStream_t s) const {
@@ -244,8 +253,8 @@ struct DgdmUnetTrainer : ParamStore {      // parameters: one flat buffer in the
     int gn_bwd(T &x, const T &y, size_t gb, const T *film, T *dfilm, const float *stats, float *spart, int S, hipStream_t s);
     int res_fwd(Res &r, T *const *parts, hipStream_t s);
     int res_bwd(Res &r, T *const *parts, int S, hipStream_t s);
-    int run(const float *x0, const float *noise, const float *sa, const float *sb, const int64_t *t, int S, int64_t S_total, bool backward, float *pred_out,
-            float *loss_host, hipStream_t s);
+    int run(const float *x0, const float *noise, const float *sa, const float *sb, const int64_t *t, const float *gcond, int S, int64_t S_total, bool backward,
+            float *pred_out, float *loss_host, hipStream_t s);
     int step_adam(float lr, hipStream_t s);
     int copy_state(int which, const DgdmTensor *t, int n, bool to_device);
 };
@@ -277,6 +286,21 @@ void DgdmUnetTrainer::make_conv(Conv &c, const std::string &name, int kind, int 
     }
 }
 
+// cond_encoder.1: Linear(dsed + gc, 2 cout), weight [2 cout][dsed + gc].  Its input cat(Mish(step embedding), Mish(global_cond)) is two
+// parts of different widths - t_mg [S][dsed] and t_gm [S][gcw] - accumulated into one output, as the concat block's two halves are; the
+// second part's image holds the weight's columns [dsed, dsed + gc) (its K rounded up with zero rows, like every image).  The global part
+// is data: no input-gradient image.
+void DgdmUnetTrainer::make_cond(Conv &c, const std::string &name, int cout) {
+    const int cin = dsed + gc;
+    c.kind = S1; c.k = 1; c.cin = cin; c.cout = cout; c.nparts = gc > 0 ? 2 : 1;
+    c.w = add_param(name + ".weight", (int64_t)cin * cout);
+    c.b = add_param(name + ".bias", cout);
+    c.pc[0] = dsed;
+    c.F[0] = add_img(c.w, dsed, {0}, cout, 1, cin, 0);
+    c.B[0] = add_img(c.w, cout, {0}, dsed, cin, 1, 0);
+    if (gc > 0) { c.pc[1] = gc; c.F[1] = add_img(c.w, gc, {0}, cout, 1, cin, dsed); }
+}
+
 int DgdmUnetTrainer::reserve(int S) {
     if (S <= S_ws) return DGDM_OK;
     const int rp1 = L + 8, rp2 = L / 2 + 4;
@@ -290,6 +314,7 @@ int DgdmUnetTrainer::reserve(int S) {
     };
     auto plain = [&](float *&q, int64_t n) { ar.add(q, n); };
     tensor(t_x0, 1, 1, false); tensor(t_emb, dsed, 0, false); tensor(t_h1, 4 * dsed, 0); tensor(t_a1, 4 * dsed, 0); tensor(t_gf, dsed, 0); tensor(t_mg, dsed, 0);
+    if (gc > 0) tensor(t_gm, gcw, 0, false);
     for (int i = 0; i < 8; ++i) {
         Res &r = res[i];
         tensor(r.t_c1, r.cout, r.lvl); tensor(r.t_a, r.cout, r.lvl); tensor(r.t_c2, r.cout, r.lvl); tensor(r.t_out, r.cout, r.lvl);
@@ -389,7 +414,7 @@ int DgdmUnetTrainer::gn_bwd(T &x, const T &y, size_t gb, const T *film, T *dfilm
 // ConditionalResidualBlock1D.forward (diffusion_utils.py:101-120)
 int DgdmUnetTrainer::res_fwd(Res &r, T *const *parts, hipStream_t s) {
     int rc;
-    T *mg[1] = {&t_mg};
+    T *mg[2] = {&t_mg, &t_gm};
     if ((rc = conv_fwd(r.c1, parts, r.t_c1, s))) return rc;
     if ((rc = conv_fwd(r.cond, mg, r.t_film, s))) return rc;
     if ((rc = gn_fwd(r.t_c1, r.t_a, nullptr, r.g1, &r.t_film, r.st1, s))) return rc;
@@ -407,7 +432,7 @@ int DgdmUnetTrainer::res_bwd(Res &r, T *const *parts, int S, hipStream_t s) {
     r.t_a.gw = false;
     if ((rc = conv_bwd(r.c2, a, r.t_c2, s))) return rc;
     if ((rc = gn_bwd(r.t_c1, r.t_a, r.g1, &r.t_film, &r.t_film, r.st1, r.sp, S, s))) return rc;
-    T *mg[1] = {&t_mg};
+    T *mg[2] = {&t_mg, &t_gm};
     if ((rc = conv_bwd(r.cond, mg, r.t_film, s))) return rc;
     if ((rc = conv_bwd(r.c1, parts, r.t_c1, s))) return rc;
     if (r.has_rc) {
@@ -429,8 +454,9 @@ int DgdmUnetTrainer::step_adam(float lr, hipStream_t s) {
 
 // Diffusion.get_stats (diffusion.py:126-166) on S samples: noisy input, eps-net forward, MSE loss; backward = what loss.backward() leaves
 // in the parameters' .grad (training_step + Lightning's automatic optimization)
-int DgdmUnetTrainer::run(const float *x0, const float *noise, const float *sa, const float *sb, const int64_t *t, int S, int64_t S_total, bool backward,
-                         float *pred_out, float *loss_host, hipStream_t s) {
+int DgdmUnetTrainer::run(const float *x0, const float *noise, const float *sa, const float *sb, const int64_t *t, const float *gcond, int S, int64_t S_total,
+                         bool backward, float *pred_out, float *loss_host, hipStream_t s) {
+    DGDM_REQUIRE(gc == 0 || gcond, DGDM_EINVAL, "this eps-net has global_cond_dim %d: the training calls need a condition [samples][%d]", gc, gc);
     int rc = reserve(S);
     if (rc) return rc;
     if (S != M[0]) {       // a smaller batch than the workspace was sized for: same buffers, fewer rows (padding rows of the unused tail stay zero)
@@ -441,6 +467,11 @@ int DgdmUnetTrainer::run(const float *x0, const float *noise, const float *sa, c
         const int64_t n = (int64_t)S * (L + dsed);
         hipLaunchKernelGGL(prep_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, x0, noise, sa, sb, t, freqs.as<float>(), S, L, mk[1].rp, mk[1].pad, dsed,
                            t_x0.v, t_emb.v);
+        DGDM_HIP_CHECK(hipGetLastError());
+    }
+    if (gc > 0) {
+        const int64_t n = (int64_t)S * gcw;
+        hipLaunchKernelGGL(cond_prep_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, gcond, S, gc, gcw, t_gm.v);
         DGDM_HIP_CHECK(hipGetLastError());
     }
     auto mish = [&](const T &x, T &y) {
@@ -519,6 +550,24 @@ extern "C" int dgdm_unet_trainer_create(DgdmUnetTrainer **out, const DgdmTensor 
     m->beta1 = beta1; m->beta2 = beta2; m->eps = eps; m->wd = weight_decay;
     const int d0 = m->d0, d1 = m->d1;
     using UT = DgdmUnetTrainer;
+    {   // global_cond_dim from the cond encoders' in_features, as dgdm_unet1d_create derives it
+        const StateDict sd(state_dict, n_tensors);
+        const char *blocks[8] = {"down_modules.0.0", "down_modules.0.1", "down_modules.1.0", "down_modules.1.1", "mid_modules.0", "mid_modules.1", "up_modules.0.0",
+                                 "up_modules.0.1"};
+        int gc = -1;
+        for (int i = 0; i < 8; ++i) {
+            const std::string key = std::string(blocks[i]) + ".cond_encoder.1.weight";
+            auto it = sd.m.find(key);
+            if (it == sd.m.end()) { set_error("state_dict key '%s' missing", key.c_str()); return DGDM_EKEY; }
+            const int64_t rows = 2 * (int64_t)(i >= 2 && i < 6 ? m->d1 : m->d0), numel = it->second->numel;
+            const int64_t g = numel % rows == 0 ? numel / rows - dsed : -1;
+            DGDM_REQUIRE(g >= 0 && g <= 256, DGDM_EINVAL, "%s: %lld values are not [%lld][%d + global_cond_dim] with 0 <= global_cond_dim <= 256", key.c_str(),
+                         (long long)numel, (long long)rows, dsed);
+            DGDM_REQUIRE(gc < 0 || g == gc, DGDM_EINVAL, "%s: global_cond_dim %lld differs from the %d of the blocks before it", key.c_str(), (long long)g, gc);
+            gc = (int)g;
+        }
+        m->gc = gc; m->gcw = (gc + 3) & ~3;
+    }
     m->make_conv(m->se1, "diffusion_step_encoder.1", UT::S1, 1, dsed, 4 * dsed);
     m->make_conv(m->se3, "diffusion_step_encoder.3", UT::S1, 1, 4 * dsed, dsed);
     const struct { const char *name; int cin, cout, lvl, nparts; } spec[8] = {
@@ -532,7 +581,7 @@ extern "C" int dgdm_unet_trainer_create(DgdmUnetTrainer **out, const DgdmTensor 
         r.g1 = m->add_param(n + ".blocks.0.block.1.weight", spec[i].cout); m->add_param(n + ".blocks.0.block.1.bias", spec[i].cout);
         m->make_conv(r.c2, n + ".blocks.1.block.0", UT::S1, kernel_size, spec[i].cout, spec[i].cout);
         r.g2 = m->add_param(n + ".blocks.1.block.1.weight", spec[i].cout); m->add_param(n + ".blocks.1.block.1.bias", spec[i].cout);
-        m->make_conv(r.cond, n + ".cond_encoder.1", UT::S1, 1, dsed, 2 * spec[i].cout);
+        m->make_cond(r.cond, n + ".cond_encoder.1", 2 * spec[i].cout);
         r.has_rc = spec[i].cin != spec[i].cout;
         if (r.has_rc) m->make_conv(r.rc, n + ".residual_conv", UT::S1, 1, spec[i].cin, spec[i].cout, spec[i].nparts);
     }
@@ -560,18 +609,35 @@ extern "C" int dgdm_unet_trainer_create(DgdmUnetTrainer **out, const DgdmTensor 
 
 extern "C" void dgdm_unet_trainer_destroy(DgdmUnetTrainer *m) { delete m; }
 
+extern "C" int dgdm_unet_trainer_global_cond_dim(const DgdmUnetTrainer *m) { return m ? m->gc : -1; }
+
 extern "C" int dgdm_unet_trainer_forward_backward(DgdmUnetTrainer *m, const float *x0_dev, const float *noise_dev, const float *sqrt_abar_dev,
                                                   const float *sqrt_1m_abar_dev, const int64_t *timesteps_dev, int samples, int64_t total_samples, int backward,
                                                   float *pred_dev, float *loss_host, void *stream) {
+    return dgdm_unet_trainer_forward_backward_cond(m, x0_dev, noise_dev, sqrt_abar_dev, sqrt_1m_abar_dev, timesteps_dev, nullptr, samples, total_samples, backward,
+                                                   pred_dev, loss_host, stream);
+}
+
+extern "C" int dgdm_unet_trainer_forward_backward_cond(DgdmUnetTrainer *m, const float *x0_dev, const float *noise_dev, const float *sqrt_abar_dev,
+                                                       const float *sqrt_1m_abar_dev, const int64_t *timesteps_dev, const float *global_cond_dev, int samples,
+                                                       int64_t total_samples, int backward, float *pred_dev, float *loss_host, void *stream) {
     DGDM_REQUIRE(m && x0_dev && noise_dev && sqrt_abar_dev && sqrt_1m_abar_dev && timesteps_dev, DGDM_EINVAL, "dgdm_unet_trainer_forward_backward: null argument");
     DGDM_REQUIRE(samples >= 1 && samples <= total_samples && samples <= (1 << 20), DGDM_EINVAL, "dgdm_unet_trainer_forward_backward: %d of %lld samples", samples,
                  (long long)total_samples);
-    return m->run(x0_dev, noise_dev, sqrt_abar_dev, sqrt_1m_abar_dev, timesteps_dev, samples, total_samples, backward != 0, pred_dev, loss_host, (hipStream_t)stream);
+    return m->run(x0_dev, noise_dev, sqrt_abar_dev, sqrt_1m_abar_dev, timesteps_dev, global_cond_dev, samples, total_samples, backward != 0, pred_dev, loss_host,
+                  (hipStream_t)stream);
 }
 
 extern "C" int dgdm_unet_trainer_step(DgdmUnetTrainer *m, const float *x0_dev, const float *noise_dev, const float *sqrt_abar_dev, const float *sqrt_1m_abar_dev,
                                       const int64_t *timesteps_dev, int samples, float lr, float *pred_dev, float *loss_host, void *stream) {
-    int rc = dgdm_unet_trainer_forward_backward(m, x0_dev, noise_dev, sqrt_abar_dev, sqrt_1m_abar_dev, timesteps_dev, samples, samples, 1, pred_dev, nullptr, stream);
+    return dgdm_unet_trainer_step_cond(m, x0_dev, noise_dev, sqrt_abar_dev, sqrt_1m_abar_dev, timesteps_dev, nullptr, samples, lr, pred_dev, loss_host, stream);
+}
+
+extern "C" int dgdm_unet_trainer_step_cond(DgdmUnetTrainer *m, const float *x0_dev, const float *noise_dev, const float *sqrt_abar_dev, const float *sqrt_1m_abar_dev,
+                                           const int64_t *timesteps_dev, const float *global_cond_dev, int samples, float lr, float *pred_dev, float *loss_host,
+                                           void *stream) {
+    int rc = dgdm_unet_trainer_forward_backward_cond(m, x0_dev, noise_dev, sqrt_abar_dev, sqrt_1m_abar_dev, timesteps_dev, global_cond_dev, samples, samples, 1, pred_dev,
+                                                     nullptr, stream);
     if (rc) return rc;
     if ((rc = m->step_adam(lr, (hipStream_t)stream))) return rc;
     return m->read_loss(loss_host, stream);

@@ -161,14 +161,16 @@ class GuidanceSpec:
 
 def guided_chains_sharded(unet, spec: GuidanceSpec, sched, mode: str, noise: torch.Tensor, objects: torch.Tensor,
                           chains: Sequence[Tuple[int, str]], unguided: Optional[torch.Tensor] = None, starts=None,
-                          streams=None, group=None, build: Optional[Callable] = None) -> torch.Tensor:
+                          streams=None, group=None, build: Optional[Callable] = None, global_cond: Optional[torch.Tensor] = None,
+                          cfg_weight: float = 1.0) -> torch.Tensor:
     """``sampler.guided_chains`` for the (object x objective) pairs `chains` over the object bank `objects`, block-partitioned
     over the ranks of `group`; returns all chains' samples [n_chains, B, L, 1] in the original order on every rank.
 
     Each rank builds the tables of the objects ITS chains use (``spec.build`` or `build(local_objects, n_local_chains)`) and
     runs its chains; nothing is communicated inside the denoise loop and the final samples are all-gathered once (SURVEY.md
     §8(e)).  3-D: the FPS start draws are rank-count-invariant - every rank walks the reference's single generator stream over
-    ALL chains (host only: `starts` or the global CPU generator) and keeps its own block, unless per-chain `streams` are given."""
+    ALL chains (host only: `starts` or the global CPU generator) and keeps its own block, unless per-chain `streams` are given.
+    global_cond (B, gc), shared by all chains, and cfg_weight: as in ``sampler.guided_chains``."""
     from . import sampler
     world, rank = world_rank(group)
     mine, local_objects, local_chains = shard_chains(chains, rank, world)
@@ -179,7 +181,8 @@ def guided_chains_sharded(unet, spec: GuidanceSpec, sched, mode: str, noise: tor
         predrawn = sampler.draw_chain_starts(spec, chains, S, starts, keep=mine, streams=streams)
     if len(local_chains):
         guid = (build or spec.build)(objects[local_objects].to(noise.device), len(local_chains))
-        local = sampler.guided_chains(unet, guid, sched, mode, noise, local_chains, unguided=unguided, predrawn=predrawn)
+        cond_kw = {} if global_cond is None else {"global_cond": global_cond, "cfg_weight": cfg_weight}      # an unconditional call is what it was
+        local = sampler.guided_chains(unet, guid, sched, mode, noise, local_chains, unguided=unguided, predrawn=predrawn, **cond_kw)
     else:
         local = torch.zeros((0, B, L, 1), dtype=torch.float32, device=noise.device)
     return gather_pairs(local, len(chains), group)
@@ -191,7 +194,8 @@ def gather_rows(local: torch.Tensor, n_items: int, group=None) -> torch.Tensor:
 
 
 def guided_multi_object_sharded(unet, spec: GuidanceSpec, sched, mode: str, noise: torch.Tensor, objects: torch.Tensor, opt_obj: str,
-                                starts=None, group=None, build: Optional[Callable] = None, on_step=None) -> torch.Tensor:
+                                starts=None, group=None, build: Optional[Callable] = None, on_step=None, global_cond: Optional[torch.Tensor] = None,
+                                cfg_weight: float = 1.0) -> torch.Tensor:
     """``sampler.guided_multi_object`` (generator/diffusion.py:637-647: ONE chain whose step uses the mean of n_obj cond_fn
     gradients) with the objects block-partitioned over the ranks.  Unlike the per-object chains this loop has a real exchange
     step: every denoise step the ranks all-gather their objects' gradients [n_obj, B, L] (a few KB over RCCL) and then all take
@@ -215,7 +219,7 @@ def guided_multi_object_sharded(unet, spec: GuidanceSpec, sched, mode: str, nois
         x = noise.reshape(B, L).contiguous().to(torch.float32)
         for i, t in enumerate(sched.timesteps):
             t = int(t)
-            eps = unet.forward(x.reshape(B, L, 1), torch.full((B,), t, dtype=torch.int32, device=x.device)).reshape(B, L)
+            eps = unet.forward_cfg(x.reshape(B, L, 1), torch.full((B,), t, dtype=torch.int32, device=x.device), global_cond, cfg_weight).reshape(B, L)
             st = None
             if is3d:
                 per_obj = [starts.call(spec.rows) if j in mine else starts.skip(spec.rows) for j in range(n_obj)]

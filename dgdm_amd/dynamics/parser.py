@@ -55,6 +55,12 @@ _FLAGS = [
     ("goal_window_cm", float, 3.0, "with --goal_pose: half-width in centimetres of the band of positions pulled toward the goal"),
     ("goal_profile", str, "sign", "with --goal_pose: 'sign' (unit pull inside the window) or 'linear' (proportional, saturating at the window)"),
     ("goal_scale", float, None, "with --goal_pose: classifier scale of the goal chains (default: the scale of 'convergence'; untuned for goals)"),
+    ("global_cond", str, None, "generator: FILE.npy of float32 condition rows [num_fingers][gc], row i for finger i of the dataset; the eps-net is then "
+                               "built with global_cond_dim = gc and trained (--mode=train) or sampled (--mode=test) on (fingers, condition) pairs"),
+    ("cfg_weight", float, 1.0, "with --global_cond: classifier-free guidance weight w of every sampling loop, eps = eps_u + w (eps_c - eps_u) with eps_u the "
+                               "net on the all-zero condition row (1: the plain conditional eps, 0: the unconditional one)"),
+    ("cond_drop_prob", float, 0.0, "with --global_cond, --mode=train: probability with which a training sample sees the all-zero condition row instead of "
+                                   "its own (what classifier-free guidance needs the net to have learnt)"),
     ("device_dataset", "flag", None, "dynamics training: read every data file once, keep the dataset on the GPU and build each batch's rows there "
                                      "(dynamics/device_dataset.py); same batches, draws and results as the host loop"),
 ]

@@ -21,6 +21,45 @@ def _f32(t: torch.Tensor) -> torch.Tensor:
     return t.detach().to(dtype=torch.float32).contiguous()
 
 
+def check_global_cond(global_cond: Optional[torch.Tensor], gc: int, rows: int, what: str = "global_cond") -> Optional[torch.Tensor]:
+    """The condition rows of `rows` samples for an eps-net of global_cond_dim `gc`: (rows, gc) or None when gc == 0 and none is given.
+    Host-side validation only (no library call, no launch); raises ValueError for a missing condition, a wrong width or row count."""
+    if gc == 0:
+        if global_cond is not None:
+            raise ValueError(f"{what}: this eps-net has global_cond_dim 0 and takes no condition")
+        return None
+    if global_cond is None:
+        raise ValueError(f"{what}: this eps-net has global_cond_dim {gc} and needs a condition of shape ({rows}, {gc})")
+    if global_cond.dim() != 2 or global_cond.shape[1] != gc:
+        raise ValueError(f"{what}: expected width {gc} (shape ({rows}, {gc})), got shape {tuple(global_cond.shape)}")
+    if global_cond.shape[0] != rows:
+        raise ValueError(f"{what}: expected {rows} rows (one per sample), got {global_cond.shape[0]}")
+    return global_cond
+
+
+def chain_cond_layout(global_cond: Optional[torch.Tensor], gc: int, n_chains: int, batch: int):
+    """The chain runner's view of a condition: (B, gc) shared by all chains -> (tensor, 0); (n_chains, B, gc) -> (tensor, B * gc).
+    Host-side validation only; raises ValueError."""
+    if gc == 0 or global_cond is None:
+        check_global_cond(global_cond, gc, batch)
+        return None, 0
+    if global_cond.dim() == 2:
+        return check_global_cond(global_cond, gc, batch), 0
+    if global_cond.dim() != 3 or tuple(global_cond.shape) != (n_chains, batch, gc):
+        raise ValueError(f"global_cond: expected ({batch}, {gc}) or ({n_chains}, {batch}, {gc}), got shape {tuple(global_cond.shape)}")
+    return global_cond, batch * gc
+
+
+def cfg_mix(eps_c: torch.Tensor, eps_u: torch.Tensor, w: float) -> torch.Tensor:
+    """Classifier-free guidance mix eps_u + w (eps_c - eps_u), three separately rounded float32 operations (dgdm_cfg_mix)."""
+    ec, eu = _f32(eps_c), _f32(eps_u)
+    if ec.shape != eu.shape:
+        raise ValueError(f"cfg_mix: shapes differ ({tuple(ec.shape)} and {tuple(eu.shape)})")
+    out = torch.empty_like(ec)
+    check(lib().dgdm_cfg_mix(dptr(ec), dptr(eu), float(w), dptr(out), ec.numel(), stream_ptr()))
+    return out
+
+
 class Unet1d:
     """``ConditionalUnet1D`` weights packed on the device (generator/diffusion_utils.py:123-285)."""
 
@@ -31,6 +70,7 @@ class Unet1d:
         h = C.c_void_p()
         check(lib().dgdm_unet1d_create(C.byref(h), packed.array, packed.n, dd, len(down_dims), step_embed_dim, kernel_size, n_groups))
         self._h = h
+        self.global_cond_dim = int(lib().dgdm_unet1d_global_cond_dim(h))
         self.set_contraction_dtype(contraction_dtype)
 
     def set_contraction_dtype(self, dtype: str) -> None:
@@ -56,15 +96,34 @@ class Unet1d:
             lib().dgdm_unet1d_destroy(self._h)
             self._h = None
 
-    def forward(self, sample: torch.Tensor, timestep: torch.Tensor) -> torch.Tensor:
-        """sample (B, L, 1) float32 cuda, timestep (B,) integer -> eps (B, L, 1)."""
+    def forward(self, sample: torch.Tensor, timestep: torch.Tensor, global_cond: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """sample (B, L, 1) float32 cuda, timestep (B,) integer, global_cond (B, global_cond_dim) or None -> eps (B, L, 1)."""
         assert sample.dim() == 3 and sample.shape[-1] == 1, "input_dim must be 1 (generator/train.py:76)"
+        c = check_global_cond(global_cond, self.global_cond_dim, sample.shape[0])
         x = _f32(sample)
         B, L, _ = x.shape
         t = timestep.to(device=x.device, dtype=torch.int32).expand(B).contiguous()
         out = torch.empty_like(x)
-        check(lib().dgdm_unet1d_forward(self._h, dptr(x), dptr(t), dptr(out), B, L, stream_ptr()))
+        if c is None:
+            check(lib().dgdm_unet1d_forward(self._h, dptr(x), dptr(t), dptr(out), B, L, stream_ptr()))
+        else:
+            c = _f32(c).to(x.device)
+            check(lib().dgdm_unet1d_forward_cond(self._h, dptr(x), dptr(t), dptr(c), dptr(out), B, L, stream_ptr()))
         return out
+
+    def forward_cfg(self, sample: torch.Tensor, timestep: torch.Tensor, global_cond: Optional[torch.Tensor] = None, cfg_weight: float = 1.0) -> torch.Tensor:
+        """eps under classifier-free guidance, as dgdm_guided_chains_run_cond forms it: weight 1 (or no condition) -> the conditional
+        eps, 0 -> the eps of the all-zero condition, otherwise ONE forward of 2B samples [condition rows | zero rows] and the mix."""
+        w = float(cfg_weight)
+        if self.global_cond_dim == 0 or w == 1.0:
+            return self.forward(sample, timestep, global_cond)
+        c = check_global_cond(global_cond, self.global_cond_dim, sample.shape[0])
+        if w == 0.0:
+            return self.forward(sample, timestep, torch.zeros_like(c))
+        B = sample.shape[0]
+        t = timestep.to(device=sample.device).expand(B)
+        both = self.forward(torch.cat((sample, sample)), torch.cat((t, t)), torch.cat((c, torch.zeros_like(c))))
+        return cfg_mix(both[:B], both[B:], w)
 
 
 class UnetTrainer:
@@ -80,6 +139,7 @@ class UnetTrainer:
         check(lib().dgdm_unet_trainer_create(C.byref(h), packed.array, packed.n, num_points, dd, len(down_dims), step_embed_dim, kernel_size, n_groups,
                                              betas[0], betas[1], eps, weight_decay))
         self._h, self.num_points = h, num_points
+        self.global_cond_dim = int(lib().dgdm_unet_trainer_global_cond_dim(h))
 
     def __del__(self):
         if getattr(self, "_h", None) and lib is not None:
@@ -93,23 +153,32 @@ class UnetTrainer:
         assert x0.shape[1] == self.num_points and noise.shape == x0.shape
         return x0, noise, f(sqrt_abar), f(sqrt_1m_abar), timesteps.detach().to(device=dev, dtype=torch.int64).contiguous()
 
-    def step(self, x0, noise, sqrt_abar, sqrt_1m_abar, timesteps, lr: float, want_pred: bool = False, want_loss: bool = True):
-        """One optimisation step; returns (loss or None, noise_pred (B, L, 1) or None)."""
+    def _cond(self, global_cond, rows: int):
+        c = check_global_cond(global_cond, self.global_cond_dim, rows)
+        if c is None:
+            return None
+        return c.detach().to(device=torch.device("cuda", torch.cuda.current_device()), dtype=torch.float32).contiguous()
+
+    def step(self, x0, noise, sqrt_abar, sqrt_1m_abar, timesteps, lr: float, want_pred: bool = False, want_loss: bool = True, global_cond=None):
+        """One optimisation step; returns (loss or None, noise_pred (B, L, 1) or None).  global_cond: (B, global_cond_dim) rows."""
+        c = self._cond(global_cond, x0.shape[0])
         a = self._args(x0, noise, sqrt_abar, sqrt_1m_abar, timesteps)
         B = a[0].shape[0]
         pred = torch.empty_like(a[0]) if want_pred else None
         loss = C.c_float()
-        check(lib().dgdm_unet_trainer_step(self._h, *[dptr(v) for v in a], B, float(lr), dptr(pred), C.byref(loss) if want_loss else None, stream_ptr()))
+        check(lib().dgdm_unet_trainer_step_cond(self._h, *[dptr(v) for v in a], dptr(c), B, float(lr), dptr(pred), C.byref(loss) if want_loss else None,
+                                                stream_ptr()))
         return (float(loss.value) if want_loss else None), (pred.reshape(B, -1, 1) if want_pred else None)
 
     def forward_backward(self, x0, noise, sqrt_abar, sqrt_1m_abar, timesteps, total_samples: Optional[int] = None, backward: bool = True,
-                         want_pred: bool = False):
+                         want_pred: bool = False, global_cond=None):
+        c = self._cond(global_cond, x0.shape[0])
         a = self._args(x0, noise, sqrt_abar, sqrt_1m_abar, timesteps)
         B = a[0].shape[0]
         pred = torch.empty_like(a[0]) if want_pred else None
         loss = C.c_float()
-        check(lib().dgdm_unet_trainer_forward_backward(self._h, *[dptr(v) for v in a], B, int(total_samples or B), 1 if backward else 0, dptr(pred),
-                                                       C.byref(loss), stream_ptr()))
+        check(lib().dgdm_unet_trainer_forward_backward_cond(self._h, *[dptr(v) for v in a], dptr(c), B, int(total_samples or B), 1 if backward else 0,
+                                                            dptr(pred), C.byref(loss), stream_ptr()))
         return float(loss.value), (pred.reshape(B, -1, 1) if want_pred else None)
 
     def gradient_count(self) -> int:
@@ -423,10 +492,15 @@ def ddim_guided_step(x: torch.Tensor, eps: torch.Tensor, grad: Optional[torch.Te
 
 def guided_chains_run(unet: "Unet1d", guid: "Guidance", noise: torch.Tensor, n_chains: int, n_grad: int, objectives: Sequence[_lib.Objective],
                       rowcoef: Optional[torch.Tensor], starts: Optional[np.ndarray], timesteps: Sequence[int],
-                      coefs: Sequence[Tuple[float, float, float, float]], scales: Sequence[float]) -> torch.Tensor:
-    """The whole guided denoise loop in one library call (dgdm_guided_chains_run): noise (B, L) -> (n_chains, B, L)."""
+                      coefs: Sequence[Tuple[float, float, float, float]], scales: Sequence[float], global_cond: Optional[torch.Tensor] = None,
+                      cfg_weight: float = 1.0) -> torch.Tensor:
+    """The whole guided denoise loop in one library call (dgdm_guided_chains_run_cond): noise (B, L) -> (n_chains, B, L).
+    global_cond: (B, gc) shared by all chains or (n_chains, B, gc); cfg_weight: classifier-free guidance weight (1: the plain conditional run)."""
+    cond, cond_stride = chain_cond_layout(global_cond, unet.global_cond_dim, n_chains, noise.shape[0])
     x0 = _f32(noise).reshape(noise.shape[0], -1)
     B, L = x0.shape
+    if cond is not None:
+        cond = _f32(cond).to(x0.device)
     S = len(timesteps)
     assert len(objectives) == n_chains * n_grad and len(scales) == n_chains and len(coefs) == S
     arr = (_lib.Objective * len(objectives))(*objectives)
@@ -439,8 +513,8 @@ def guided_chains_run(unet: "Unet1d", guid: "Guidance", noise: torch.Tensor, n_c
         starts = np.ascontiguousarray(starts)
         sp = starts.ctypes.data
     out = torch.empty((n_chains, B, L), dtype=torch.float32, device=x0.device)
-    check(lib().dgdm_guided_chains_run(unet._h, guid._h, dptr(x0), n_chains, n_grad, arr, dptr(rowcoef) if rowcoef is not None else None, sp,
-                                       ts, cf, sc, S, dptr(out), stream_ptr()))
+    check(lib().dgdm_guided_chains_run_cond(unet._h, guid._h, dptr(x0), n_chains, n_grad, arr, dptr(rowcoef) if rowcoef is not None else None, sp,
+                                            ts, cf, sc, S, dptr(out), dptr(cond), int(cond_stride), float(cfg_weight), stream_ptr()))
     return out         # `starts` has been consumed: every step converts it into the handle's pinned staging buffer before it returns
 
 

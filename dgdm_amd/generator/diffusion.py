@@ -132,6 +132,11 @@ class Diffusion(nn.Module):
         self.object_exporter = None
         # nor this: a sampler.Goal (--goal_pose) the validation sweep guides and scores toward, after the reference's objectives
         self.goal = None
+        # nor these (--cfg_weight, --cond_drop_prob; they matter only when noise_pred_net has global_cond_dim > 0 and the batches are
+        # (fingers, condition rows) pairs): the classifier-free guidance weight of every sampling loop, and the probability with which
+        # a training sample's condition row is replaced by the all-zero (null) row
+        self.cfg_weight = 1.0
+        self.cond_drop_prob = 0.0
         if class_cond:
             self.classifier_model = classifier_model
             self.grid_size, self.num_pos = grid_size, num_pos
@@ -168,10 +173,32 @@ class Diffusion(nn.Module):
             if p.grad is not None:
                 p.grad.zero_()
 
+    @staticmethod
+    def split_batch(batch):
+        """A batch is the fingers tensor (the reference's ``tensor_data``) or a (fingers, condition rows) pair -> (fingers, rows or None)."""
+        if isinstance(batch, (tuple, list)):
+            if len(batch) != 2:
+                raise ValueError(f"a conditional batch is a (fingers, global_cond) pair, got {len(batch)} items")
+            return batch[0], batch[1]
+        return batch, None
+
+    def _cond_rows(self, cond, rows: int):
+        """The batch's condition rows on the device, checked against the eps-net's global_cond_dim (ValueError before any launch)."""
+        gc = int(getattr(self.noise_pred_net, "global_cond_dim", 0))
+        cond = engine.check_global_cond(cond, gc, rows)
+        return None if cond is None else cond.to(device=self.device, dtype=torch.float32)
+
     def load_state_dict(self, state_dict: Mapping[str, Any], strict: bool = True):
         """Accepts a Lightning checkpoint ``state_dict`` (keys ``ema_nets.noise_pred_net.*``, optional nested
         ``ema_model`` and ``_orig_mod.`` prefixes from torch.compile; reference :730-748)."""
         flat = {k.replace("_orig_mod.", ""): v for k, v in state_dict.items() if k != "ema_model"}
+        # a checkpoint of another global_cond_dim cannot be copied into this module: say which widths, not a tensor-size mismatch
+        key = "ema_nets.noise_pred_net.mid_modules.0.cond_encoder.1.weight"
+        if key in flat and hasattr(flat[key], "shape"):
+            have, want = int(flat[key].shape[1]), int(self.noise_pred_net.mid_modules[0].cond_encoder[1].weight.shape[1])
+            if have != want:
+                raise ValueError(f"checkpoint cond_encoder width {have} (global_cond_dim {have - self.noise_pred_net.dsed}) differs from the "
+                                 f"module's {want} (global_cond_dim {want - self.noise_pred_net.dsed})")
         out = super().load_state_dict(flat, strict=False)
         # nn.Module.load_state_dict copies into the children's parameters in place (it never calls the children's own
         # load_state_dict), so their packed device copies and every guidance handle bound to them are stale now
@@ -218,9 +245,12 @@ class Diffusion(nn.Module):
             self._trained = False
         return self._unet_trainer
 
-    def _training_draws(self, tensor_data):
+    def _training_draws(self, tensor_data, cond=None):
         """The draws of get_stats in its order and from its generator (:134-142: torch.randn then torch.randint on self.device - the
-        device generator of torch, which PyTorch-ROCm provides as it is), and DDIMScheduler.add_noise's two coefficients per sample."""
+        device generator of torch, which PyTorch-ROCm provides as it is), and DDIMScheduler.add_noise's two coefficients per sample.
+        With condition rows `cond` (n, gc) a sixth entry: the rows each sample trains on - with probability cond_drop_prob the all-zero
+        row instead of its own.  That draw, ``torch.rand(n) < p``, comes AFTER the reference's two and only when p > 0, so the stream of
+        an unconditional run (and of one without drop-out) is what it was."""
         dev = self.device
         data = tensor_data.to(device=dev, non_blocking=True)
         n = data.shape[0] * self.num_timesteps_per_batch
@@ -228,13 +258,30 @@ class Diffusion(nn.Module):
         noise = torch.randn((n, self.num_points, self.input_dim), device=dev)
         timesteps = torch.randint(0, self.noise_scheduler.config.num_train_timesteps, (n,), device=dev).long()
         ac = self.noise_scheduler.alphas_cumprod.to(dev)[timesteps]
-        return x0, noise, ac ** 0.5, (1 - ac) ** 0.5, timesteps
+        out = (x0, noise, ac ** 0.5, (1 - ac) ** 0.5, timesteps)
+        if cond is None:
+            return out
+        c = cond.to(device=dev, dtype=torch.float32).repeat(self.num_timesteps_per_batch, 1)
+        p = float(self.cond_drop_prob)
+        if p > 0.0:
+            drop = torch.rand(n, device=dev) < p
+            c = torch.where(drop[:, None], torch.zeros_like(c), c)
+        return out + (c,)
+
+    def _draws_for(self, batch):
+        """(the trainer call's positional draws, its global_cond keyword) of a batch, the condition checked before anything is drawn."""
+        tensor_data, cond = self.split_batch(batch)
+        cond = self._cond_rows(cond, tensor_data.shape[0])
+        d = self._training_draws(tensor_data, cond)
+        return d[:5], (d[5] if cond is not None else None)
 
     def get_stats(self, tensor_data) -> Dict[str, Any]:
-        """:126-166 - the loss of one batch (forward only: nothing is updated; ``training_step`` is the call that trains)."""
+        """:126-166 - the loss of one batch (forward only: nothing is updated; ``training_step`` is the call that trains).
+        tensor_data: the fingers, or a (fingers, global_cond) pair for a conditional eps-net."""
         if not hasattr(self, "lr_scheduler"):
             self.configure_optimizers()
-        loss, _ = self._trainer().forward_backward(*self._training_draws(tensor_data), backward=False)
+        args, cond = self._draws_for(tensor_data)
+        loss, _ = self._trainer().forward_backward(*args, backward=False, global_cond=cond)
         return {"loss": torch.tensor(loss), "lr": self.lr_scheduler.get_last_lr()[0]}
 
     def training_step(self, tensor_data, batch_idx):
@@ -246,11 +293,11 @@ class Diffusion(nn.Module):
         tr = self._trainer()
         lr = float(self.optimizer.param_groups[0]["lr"])
         world, _ = ddist.world_rank()
-        args = self._training_draws(tensor_data)
+        args, cond = self._draws_for(tensor_data)
         if world == 1:
-            loss, _ = tr.step(*args, lr)
+            loss, _ = tr.step(*args, lr, global_cond=cond)
         else:
-            loss, _ = tr.forward_backward(*args)
+            loss, _ = tr.forward_backward(*args, global_cond=cond)
             tr.write_gradients(ddist.all_reduce_sum(tr.read_gradients()), 1.0 / world)
             tr.apply(lr)
         self._trained = True
@@ -394,8 +441,10 @@ class Diffusion(nn.Module):
                                   self.noise_scheduler.config.num_train_timesteps, npts,
                                   self.sub_batch_size if self.mode == 'point_3d' else 0, self.contraction_dtype)
 
-    def guided_sample(self, batch_idx, batch_size, noise, save_dir, opt_obj='rotate', ori_range=[-1.0, 1.0], unguided_sample=None):
-        """All objects' chains of generator/diffusion.py:561-576 as one batch.  Returns (n_objects, B, L, 1).
+    def guided_sample(self, batch_idx, batch_size, noise, save_dir, opt_obj='rotate', ori_range=[-1.0, 1.0], unguided_sample=None,
+                      global_cond=None):
+        """All objects' chains of generator/diffusion.py:561-576 as one batch.  Returns (n_objects, B, L, 1).  global_cond (B, gc): the
+        condition rows of a conditional eps-net, shared by all chains (mixed with self.cfg_weight).
 
         Under a process group (torchrun, one rank per GPU) the objects' chains are block-partitioned over the ranks and the
         final samples all-gathered (dgdm_amd/dist.py) - this is what stands in for the reference's nn.DataParallel
@@ -407,10 +456,12 @@ class Diffusion(nn.Module):
         if ddist.world_rank()[0] > 1:
             out = ddist.guided_chains_sharded(self._net(), self._spec(batch_size, ori_range, objs.shape[1]), self.noise_scheduler, self.mode,
                                               noise.to(self.device), objs, chains, unguided=ug,
-                                              build=lambda o, k: self._guidance_for(batch_size, ori_range, o.detach().cpu(), k))
+                                              build=lambda o, k: self._guidance_for(batch_size, ori_range, o.detach().cpu(), k),
+                                              global_cond=global_cond, cfg_weight=self.cfg_weight)
         else:
             g = self._guidance_for(batch_size, ori_range, objs, n)
-            out = sampler.guided_chains(self._net(), g, self.noise_scheduler, self.mode, noise.to(self.device), chains, unguided=ug)
+            out = sampler.guided_chains(self._net(), g, self.noise_scheduler, self.mode, noise.to(self.device), chains, unguided=ug,
+                                        global_cond=global_cond, cfg_weight=self.cfg_weight)
         if ddist.world_rank()[1] == 0:
             tag = f"{opt_obj}_orirange={ori_range[0]:.3f}_{ori_range[1]:.3f}"
             ids = [self.object_ids[i] if self.object_ids is not None else i for i in range(n)]
@@ -423,7 +474,7 @@ class Diffusion(nn.Module):
         return out
 
     # ------------------------------------------------------------------ a2
-    def guided_sample_multi_object(self, batch_idx, batch_size, noise, save_dir, opt_obj='rotate', ori_range=[-1.0, 1.0]):
+    def guided_sample_multi_object(self, batch_idx, batch_size, noise, save_dir, opt_obj='rotate', ori_range=[-1.0, 1.0], global_cond=None):
         objs = torch.as_tensor(self.object_vertices)
         tag = f"{opt_obj}_orirange={ori_range[0]:.3f}_{ori_range[1]:.3f}"
         rank0 = ddist.world_rank()[1] == 0
@@ -436,11 +487,13 @@ class Diffusion(nn.Module):
         if ddist.world_rank()[0] > 1:       # objects over ranks, gradients all-gathered every step (dist.guided_multi_object_sharded)
             out = ddist.guided_multi_object_sharded(self._net(), self._spec(batch_size, ori_range, objs.shape[1]), self.noise_scheduler, self.mode,
                                                     noise.to(self.device), objs, opt_obj,
-                                                    build=lambda o, k: self._guidance_for(batch_size, ori_range, o.detach().cpu(), k), on_step=on_step)
+                                                    build=lambda o, k: self._guidance_for(batch_size, ori_range, o.detach().cpu(), k), on_step=on_step,
+                                                    global_cond=global_cond, cfg_weight=self.cfg_weight)
         else:
             g = self._guidance_for(batch_size, ori_range, objs, objs.shape[0])
             out = sampler.guided_multi_object(self._net(), g, self.noise_scheduler, self.mode, noise.to(self.device),
-                                              list(range(objs.shape[0])), opt_obj, on_step=on_step)
+                                              list(range(objs.shape[0])), opt_obj, on_step=on_step, global_cond=global_cond,
+                                              cfg_weight=self.cfg_weight)
         if rank0:
             self._emit(save_dir, 'vis_guided', tag, out[None], ["allobj"])
             if self.simulator is not None and save_dir:                  # :675-709: every gripper on all objects
@@ -488,9 +541,13 @@ class Diffusion(nn.Module):
     # ------------------------------------------------------------------ a3 + harness
     def validation_step(self, tensor_data, batch_idx):
         """Loops of generator/diffusion.py:179-339 without plotting / simulation: denoise from the partially noised data,
-        unguided chain from noise, then the 12-objective sweep (multi-object chain + per-object chains)."""
+        unguided chain from noise, then the 12-objective sweep (multi-object chain + per-object chains).  tensor_data: the fingers, or a
+        (fingers, global_cond) pair - the batch's condition rows then steer both unguided loops and, shared by all chains, every guided
+        chain, mixed with self.cfg_weight."""
         self.sync_model()          # after training steps: the sampling handle reads the trained parameters
         dev = self.device
+        tensor_data, cond = self.split_batch(tensor_data)
+        cond = self._cond_rows(cond, tensor_data.shape[0])
         data = tensor_data.to(dev)
         B = data.shape[0]
         rs = np.random.RandomState(self.seed)
@@ -502,7 +559,7 @@ class Diffusion(nn.Module):
         rank0 = ddist.world_rank()[1] == 0
         plots = bool(self.save_dir) and self.render_plots and rank0
         for i, t in enumerate(self.noise_scheduler.timesteps):
-            eps = net.forward(sample, torch.full((B,), int(t), device=dev))
+            eps = net.forward_cfg(sample, torch.full((B,), int(t), device=dev), cond, self.cfg_weight)
             noise_pred_loss += float(torch.mean((eps - noise) ** 2))
             sample = self.noise_scheduler.step(eps, t, sample).prev_sample
             if plots and batch_idx == 0:                                 # val_vis/<epoch>_<step>.png, sample 0 (:203-231)
@@ -523,7 +580,8 @@ class Diffusion(nn.Module):
                                            row[:, 0], self.mode, self.pts_x_dim, self.pts_z_dim, stacked=False)
                 if i == last:
                     imgs.append(f)
-        unguided = sampler.unguided_sample(net, self.noise_scheduler, noise, on_step=on_step if plots else None)
+        unguided = sampler.unguided_sample(net, self.noise_scheduler, noise, on_step=on_step if plots else None, global_cond=cond,
+                                           cfg_weight=self.cfg_weight)
         if rank0:
             self._emit(self.save_dir, 'val_vis_noise', 'unguided', unguided[None], ["unguided"])
         out["unguided"] = unguided
@@ -539,7 +597,7 @@ class Diffusion(nn.Module):
                     tables.skipped("no simulator callable was given to Diffusion(simulator=...): the objective tables of "
                                    "generator/diffusion.py:304-336, 592-619, 697-709 need simulator roll-outs (dynamics/sim_test_mj*.py)")
             with self._draw_ahead(B):
-                self._objective_sweep(out, batch_idx, B, noise, unguided, sim_unguided, tables, imgs)
+                self._objective_sweep(out, batch_idx, B, noise, unguided, sim_unguided, tables, imgs, cond)
         return out
 
     def _draw_ahead(self, B: int):
@@ -572,7 +630,7 @@ class Diffusion(nn.Module):
                 jobs.append((rows, S, c in mine))
         return sampler.StartPlan(N, self.sub_batch_size, jobs)
 
-    def _objective_sweep(self, out, batch_idx, B, noise, unguided, sim_unguided, tables, imgs):
+    def _objective_sweep(self, out, batch_idx, B, noise, unguided, sim_unguided, tables, imgs, cond=None):
         """The 12-objective sweep of generator/diffusion.py:307-339: per objective the multi-object chain, then the per-object chains."""
         for opt_obj in OBJECTIVE_SWEEP:
             rng = [-1.0, 1.0]
@@ -581,11 +639,13 @@ class Diffusion(nn.Module):
                     imgs = [None] * B
                 artefacts.unguided_table(self, tables, sim_unguided, imgs, len(self._object_ids()), B, opt_obj, rng, self.mode == 'point_3d')
             if opt_obj != 'convergence':
-                out[f"multi/{opt_obj}"] = self.guided_sample_multi_object(batch_idx, B, noise, self.save_dir, opt_obj=opt_obj, ori_range=rng)
+                out[f"multi/{opt_obj}"] = self.guided_sample_multi_object(batch_idx, B, noise, self.save_dir, opt_obj=opt_obj, ori_range=rng,
+                                                                          global_cond=cond)
             out[f"guided/{opt_obj}"] = self.guided_sample(batch_idx, B, noise, self.save_dir, opt_obj=opt_obj, ori_range=rng,
-                                                          unguided_sample=unguided)
+                                                          unguided_sample=unguided, global_cond=cond)
         goal = getattr(self, "goal", None)
         if goal is not None:               # --goal_pose: one more objective behind the reference's, keyed by the goal's name ("goal_...")
             rng = [-1.0, 1.0]
-            out[f"multi/{goal}"] = self.guided_sample_multi_object(batch_idx, B, noise, self.save_dir, opt_obj=goal, ori_range=rng)
-            out[f"guided/{goal}"] = self.guided_sample(batch_idx, B, noise, self.save_dir, opt_obj=goal, ori_range=rng, unguided_sample=unguided)
+            out[f"multi/{goal}"] = self.guided_sample_multi_object(batch_idx, B, noise, self.save_dir, opt_obj=goal, ori_range=rng, global_cond=cond)
+            out[f"guided/{goal}"] = self.guided_sample(batch_idx, B, noise, self.save_dir, opt_obj=goal, ori_range=rng, unguided_sample=unguided,
+                                                       global_cond=cond)

@@ -62,9 +62,12 @@ class ConditionalUnet1D(HipBacked):
     def __init__(self, input_dim: int, global_cond_dim: int, down_dims: List[int], diffusion_step_embed_dim: int,
                  kernel_size: int = 5, n_groups: int = 8):
         super().__init__()
-        if input_dim != 1 or global_cond_dim != 0:
-            raise NotImplementedError("the HIP U-Net is built for input_dim=1, global_cond_dim=0 (generator/train.py:80)")
+        if input_dim != 1:
+            raise NotImplementedError("the HIP U-Net is built for input_dim=1 (generator/train.py:80)")
+        if not 0 <= int(global_cond_dim) <= 256:
+            raise ValueError(f"global_cond_dim {global_cond_dim} outside 0..256")
         self.input_dim, self.down_dims, self.dsed = input_dim, list(down_dims), diffusion_step_embed_dim
+        self.global_cond_dim = int(global_cond_dim)
         self.kernel_size, self.n_groups = kernel_size, n_groups
         dsed, cond = diffusion_step_embed_dim, diffusion_step_embed_dim + global_cond_dim
         widths = [input_dim] + list(down_dims)
@@ -86,8 +89,7 @@ class ConditionalUnet1D(HipBacked):
         return engine.Unet1d(self.plain_state_dict(), self.down_dims, self.dsed, self.kernel_size, self.n_groups)
 
     def forward(self, sample: torch.Tensor, timestep: torch.Tensor, global_cond: Optional[torch.Tensor] = None):
-        """sample (B, num_points, input_dim), timestep (B,) or 0-dim -> (B, num_points, input_dim)."""
-        if global_cond is not None:
-            raise NotImplementedError("global_cond_dim is 0 on the reference's path (generator/train.py:80)")
+        """sample (B, num_points, input_dim), timestep (B,) or 0-dim, global_cond (B, global_cond_dim) -> (B, num_points, input_dim)."""
+        engine.check_global_cond(global_cond, self.global_cond_dim, sample.shape[0])
         t = torch.as_tensor(timestep, device=sample.device).reshape(-1)
-        return self.handle().forward(sample, t.expand(sample.shape[0]) if t.numel() == 1 else t)
+        return self.handle().forward(sample, t.expand(sample.shape[0]) if t.numel() == 1 else t, global_cond)

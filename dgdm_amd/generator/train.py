@@ -62,6 +62,37 @@ def finger_control_points(num_fingers: int, fingers_3d: bool) -> np.ndarray:
     return np.stack(out, axis=0)
 
 
+def load_global_cond(path, num_fingers: int) -> np.ndarray:
+    """--global_cond FILE.npy: float32 [num_fingers][gc] with 1 <= gc <= 256 and finite values, row i for finger i.  ValueError otherwise."""
+    try:
+        c = np.load(path, allow_pickle=False)
+    except Exception as e:
+        raise ValueError(f"--global_cond: cannot read '{path}' as a .npy array ({type(e).__name__}: {e})")
+    if c.ndim != 2:
+        raise ValueError(f"--global_cond: '{path}' has shape {c.shape}, expected [num_fingers][gc] (rank 2)")
+    if c.shape[0] != num_fingers:
+        raise ValueError(f"--global_cond: '{path}' has {c.shape[0]} rows, expected one per finger of the dataset (--num_fingers={num_fingers})")
+    if not 1 <= c.shape[1] <= 256:
+        raise ValueError(f"--global_cond: '{path}' has gc = {c.shape[1]}, outside 1..256")
+    if c.dtype.kind not in "fiu":
+        raise ValueError(f"--global_cond: '{path}' holds {c.dtype}, expected float32")
+    c = np.ascontiguousarray(c, dtype=np.float32)
+    if not np.isfinite(c).all():
+        raise ValueError(f"--global_cond: '{path}' holds non-finite values (row {int(np.argwhere(~np.isfinite(c))[0][0])})")
+    return c
+
+
+def check_cond_flags(args) -> None:
+    """--cfg_weight / --cond_drop_prob: finite weight, probability in [0, 1); without --global_cond they must be left at their defaults."""
+    w, p = float(args.cfg_weight), float(args.cond_drop_prob)
+    if not np.isfinite(w):
+        raise ValueError(f"--cfg_weight={args.cfg_weight}: not a finite number")
+    if not 0.0 <= p < 1.0:
+        raise ValueError(f"--cond_drop_prob={args.cond_drop_prob}: a probability in [0, 1)")
+    if args.global_cond is None and (w != 1.0 or p != 0.0):
+        raise ValueError("--cfg_weight / --cond_drop_prob need --global_cond: an unconditional eps-net has nothing to mix or drop")
+
+
 def _load_or_synth(path, spec, seed, what):
     if path and os.path.exists(path):
         sd = torch.load(path, map_location="cpu")
@@ -158,7 +189,9 @@ def fit(model: Diffusion, pts: np.ndarray, args, bounds, dev) -> Diffusion:
     from .. import dist as ddist
     n = pts.shape[0]
     train_ids, val_ids = list(range(int(n * 0.9))), list(range(int(n * 0.9), n))
-    train_set, val_set = GripperDataset(pts[train_ids], *bounds), GripperDataset(pts[val_ids], *bounds)
+    cond = getattr(model, "global_cond_rows", None)             # --global_cond: row i belongs to finger i
+    sub = lambda ids: None if cond is None else cond[ids]        # noqa: E731
+    train_set, val_set = GripperDataset(pts[train_ids], *bounds, cond=sub(train_ids)), GripperDataset(pts[val_ids], *bounds, cond=sub(val_ids))
     world, rank = ddist.world_rank()
     if not hasattr(model, "lr_scheduler"):      # a resumed model (load_checkpoint) carries its schedule position
         model.configure_optimizers()
@@ -250,9 +283,12 @@ def train(args):
     dev = torch.device("cuda", torch.cuda.current_device() if torch.cuda.is_available() else int(os.environ.get("LOCAL_RANK", "0")))
     pts = finger_control_points(args.num_fingers, args.fingers_3d)
     max_y, min_y = (0.0, -0.1) if args.fingers_3d else (0.015, -0.045)
-    dataset = GripperDataset(pts, 0.12, -0.12, max_y, min_y)
+    check_cond_flags(args)
+    cond = load_global_cond(args.global_cond, args.num_fingers) if args.global_cond is not None else None
+    gc = 0 if cond is None else cond.shape[1]
+    dataset = GripperDataset(pts, 0.12, -0.12, max_y, min_y, cond=cond)
     L = args.ctrlpts_dim
-    unet = ConditionalUnet1D(input_dim=1, global_cond_dim=0, down_dims=[128, 256], diffusion_step_embed_dim=32)
+    unet = ConditionalUnet1D(input_dim=1, global_cond_dim=gc, down_dims=[128, 256], diffusion_step_embed_dim=32)
     mode = 'point_3d' if args.fingers_3d else 'point'
     scheduler = DDIMScheduler(num_train_timesteps=args.num_train_timesteps, beta_schedule='squaredcos_cap_v2', clip_sample=True,
                               prediction_type='epsilon')
@@ -273,6 +309,7 @@ def train(args):
                       object_vertices=objects, object_ids=object_ids, num_cpus=args.num_cpus, pts_x_dim=args.ctrlpts_x_dim,
                       pts_z_dim=args.ctrlpts_z_dim, sub_batch_size=args.sub_bs, render_video=args.render_video, seed=args.seed)
     model.save_meshes = bool(getattr(args, "save_meshes", False))
+    model.cfg_weight, model.cond_drop_prob, model.global_cond_rows = float(args.cfg_weight), float(args.cond_drop_prob), cond
     if getattr(args, "save_objects", False):
         model.object_exporter = _object_exporter(args)
     rollout = int(getattr(args, "predicted_rollout", 0) or 0)
@@ -298,7 +335,7 @@ def train(args):
             model.load_checkpoint(torch.load(args.diffusion_checkpoint_path, map_location="cpu", weights_only=False))
         model.save_dir = args.save_dir or None
         return fit(model, pts, args, (0.12, -0.12, max_y, min_y), dev), []
-    ck = _load_or_synth(args.diffusion_checkpoint_path, [("ema_nets.noise_pred_net." + k, s) for k, s in synth.unet_spec()], 11,
+    ck = _load_or_synth(args.diffusion_checkpoint_path, [("ema_nets.noise_pred_net." + k, s) for k, s in synth.unet_spec(global_cond_dim=gc)], 11,
                         "diffusion checkpoint")
     res = model.load_state_dict(ck)
     lost = [k for k in res.missing_keys if k.startswith("ema_nets.noise_pred_net.")]
@@ -313,7 +350,11 @@ def train(args):
     n_batches = len(dataset) // args.batch_size                       # DataLoader(drop_last=True), :69
     with torch.no_grad():
         for bi in range(n_batches):
-            batch = torch.from_numpy(np.stack([dataset[i] for i in range(bi * args.batch_size, (bi + 1) * args.batch_size)]))
+            ids = range(bi * args.batch_size, (bi + 1) * args.batch_size)
+            if cond is None:
+                batch = torch.from_numpy(np.stack([dataset[i] for i in ids]))
+            else:
+                batch = (torch.from_numpy(np.stack([dataset[i][0] for i in ids])), torch.from_numpy(cond[list(ids)]))
             res = model.validation_step(batch, bi)
             if int(os.environ.get("RANK", "0")) == 0:
                 print(f"[dgdm_amd] batch {bi}: " + ", ".join(f"{k}={v:.5f}" for k, v in res["stats"].items()))

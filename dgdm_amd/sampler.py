@@ -313,14 +313,28 @@ def pair_stream(num_points: int, sub_batch_size: int, seed: int, pair_index: int
     return StartStream(num_points, sub_batch_size, seed=(int(seed) * 1_000_003 + int(pair_index)) & 0x7FFFFFFFFFFFFFFF)
 
 
-def unguided_sample(unet: Unet1d, sched: DDIMScheduler, x: torch.Tensor, on_step=None) -> torch.Tensor:
+def _chain_cond(unet: Unet1d, global_cond: Optional[torch.Tensor], n_chains: int, batch: int):
+    """(condition rows of all n_chains * B samples or None, whether one (B, gc) block is shared by the chains) for the Python loops."""
+    cond, stride = engine.chain_cond_layout(global_cond, unet.global_cond_dim, n_chains, batch)
+    if cond is None:
+        return None, True
+    if stride == 0:
+        return cond.reshape(1, batch, -1).expand(n_chains, -1, -1).reshape(n_chains * batch, -1), True
+    return cond.reshape(n_chains * batch, -1), n_chains == 1
+
+
+def unguided_sample(unet: Unet1d, sched: DDIMScheduler, x: torch.Tensor, on_step=None, global_cond: Optional[torch.Tensor] = None,
+                    cfg_weight: float = 1.0) -> torch.Tensor:
     """S x [eps-net ; DDIM step]  (generator/diffusion.py:193-201, :249-256).  on_step(i, x_i, eps_i): the harness's per-step hook
-    (plots, noise-prediction loss); it forces a device->host copy per step, as the reference's own plotting does."""
+    (plots, noise-prediction loss); it forces a device->host copy per step, as the reference's own plotting does.
+    global_cond (B, gc), cfg_weight: the condition rows of a conditional eps-net and the classifier-free guidance weight (the mix is
+    the library's: Unet1d.forward_cfg)."""
     B = x.shape[0]
+    engine.check_global_cond(global_cond, unet.global_cond_dim, B)
     x = x.clone()
     for i, t in enumerate(sched.timesteps):
         ts = torch.full((B,), int(t), dtype=torch.int32, device=x.device)
-        eps = unet.forward(x, ts)
+        eps = unet.forward_cfg(x, ts, global_cond, cfg_weight)
         x = engine.ddim_guided_step(x, eps, None, 0, sched.coefficients(int(t)), 0.0)
         if on_step is not None:
             on_step(i, x, eps)
@@ -393,12 +407,15 @@ def draw_chain_starts(guid: Guidance, chains: Sequence[Tuple[int, Union[str, Goa
 @_restores_row_field
 def guided_chains(unet: Unet1d, guid: Guidance, sched: DDIMScheduler, mode: str, noise: torch.Tensor,
                   chains: Sequence[Tuple[int, Union[str, Goal]]], unguided: Optional[torch.Tensor] = None,
-                  starts: Optional[StartStream] = None, trace: Optional[list] = None, predrawn=None) -> torch.Tensor:
+                  starts: Optional[StartStream] = None, trace: Optional[list] = None, predrawn=None,
+                  global_cond: Optional[torch.Tensor] = None, cfg_weight: float = 1.0) -> torch.Tensor:
     """``Diffusion.guided_sample`` loop bodies (:561-576) for the chains [(object index, opt_obj), ...]; opt_obj: a reference
     objective name or a ``Goal`` (dgdm_amd/goal.py), whose chain is guided by the goal's row field.
 
-    noise (B, L, 1) is shared by all chains (:570).  Returns (n_chains, B, L, 1)."""
+    noise (B, L, 1) is shared by all chains (:570).  global_cond: (B, gc) shared by all chains or (n_chains, B, gc); cfg_weight: the
+    classifier-free guidance weight of a conditional eps-net.  Returns (n_chains, B, L, 1)."""
     nc, (B, L, _) = len(chains), noise.shape
+    cond_all, cond_shared = _chain_cond(unet, global_cond, nc, B)
     dev = noise.device
     is3d = mode == 'point_3d'
     S = len(sched.timesteps)
@@ -425,19 +442,21 @@ def guided_chains(unet: Unet1d, guid: Guidance, sched: DDIMScheduler, mode: str,
     if trace is None:         # the loop itself runs inside the library (one call); the Python loop below is kept for traced runs
         out = engine.guided_chains_run(unet, guid, noise.reshape(B, L), nc, 1, objectives, rowcoef,
                                        np.ascontiguousarray(step_starts) if is3d else None, [int(t) for t in sched.timesteps],
-                                       [sched.coefficients(int(t)) for t in sched.timesteps], scales)
+                                       [sched.coefficients(int(t)) for t in sched.timesteps], scales, global_cond, cfg_weight)
         return out.reshape(nc, B, L, 1)
     x = noise.reshape(1, B, L).expand(nc, -1, -1).contiguous().to(torch.float32)
     for si, t in enumerate(sched.timesteps):
         t = int(t)
-        if si == 0 and nc > 1:
+        if si == 0 and nc > 1 and cond_shared:
             # every chain starts from the same noise (generator/diffusion.py:570: `sample = noise.clone()` per object), so the first
             # eps-net call has nc identical copies of the B fingers as its batch: evaluate it once (same input, same kernel, same bits)
+            # - unless every chain has condition rows of its own
             ts = torch.full((B,), t, dtype=torch.int32, device=dev)
-            eps = unet.forward(x[0].reshape(B, L, 1), ts).reshape(1, B, L).expand(nc, -1, -1).contiguous()
+            eps = unet.forward_cfg(x[0].reshape(B, L, 1), ts, None if cond_all is None else cond_all[:B], cfg_weight)
+            eps = eps.reshape(1, B, L).expand(nc, -1, -1).contiguous()
         else:
             ts = torch.full((nc * B,), t, dtype=torch.int32, device=dev)
-            eps = unet.forward(x.reshape(nc * B, L, 1), ts).reshape(nc, B, L)
+            eps = unet.forward_cfg(x.reshape(nc * B, L, 1), ts, cond_all, cfg_weight).reshape(nc, B, L)
         g = guid.grad(x, t, objectives, rowcoef, step_starts[si].reshape(-1) if is3d else None)
         if trace is not None:
             trace.append((eps.clone(), g.clone(), x.clone()))          # eps, gradient and the step's INPUT x
@@ -452,10 +471,11 @@ def guided_chains(unet: Unet1d, guid: Guidance, sched: DDIMScheduler, mode: str,
 @_restores_row_field
 def guided_multi_object(unet: Unet1d, guid: Guidance, sched: DDIMScheduler, mode: str, noise: torch.Tensor,
                         object_indices: Sequence[int], opt_obj: Union[str, Goal], starts: Optional[StartStream] = None,
-                        on_step=None) -> torch.Tensor:
+                        on_step=None, global_cond: Optional[torch.Tensor] = None, cfg_weight: float = 1.0) -> torch.Tensor:
     """``Diffusion.guided_sample_multi_object`` loop (:637-647): one chain, gradient = mean over the objects.  opt_obj: a reference
-    objective name or a ``Goal``."""
+    objective name or a ``Goal``.  global_cond (B, gc), cfg_weight: as in guided_chains."""
     n_obj, (B, L, _) = len(object_indices), noise.shape
+    engine.check_global_cond(global_cond, unet.global_cond_dim, B)
     dev = noise.device
     is3d = mode == 'point_3d'
     objectives, field = chain_objectives(guid, [(oi, opt_obj) for oi in object_indices])
@@ -470,13 +490,13 @@ def guided_multi_object(unet: Unet1d, guid: Guidance, sched: DDIMScheduler, mode
         S = len(sched.timesteps)
         st = starts.calls(guid.rows, S * n_obj).reshape(S, -1) if is3d else None      # per step object after object (:641-643): one run of draws
         out = engine.guided_chains_run(unet, guid, noise.reshape(B, L), 1, n_obj, objectives, None, st, [int(t) for t in sched.timesteps],
-                                       [sched.coefficients(int(t)) for t in sched.timesteps], [scale])
+                                       [sched.coefficients(int(t)) for t in sched.timesteps], [scale], global_cond, cfg_weight)
         return out.reshape(B, L, 1)
     x = noise.reshape(B, L).contiguous().to(torch.float32)
     for i, t in enumerate(sched.timesteps):
         t = int(t)
         ts = torch.full((B,), t, dtype=torch.int32, device=dev)
-        eps = unet.forward(x.reshape(B, L, 1), ts).reshape(B, L)
+        eps = unet.forward_cfg(x.reshape(B, L, 1), ts, global_cond, cfg_weight).reshape(B, L)
         st = starts.calls(guid.rows, n_obj).reshape(-1) if is3d else None      # object after object (:641-643)
         g = guid.grad(x.reshape(1, B, L).expand(n_obj, -1, -1).contiguous(), t, objectives, None, st)
         x = engine.ddim_guided_step(x, eps, g, n_obj, sched.coefficients(t), scale)
@@ -509,13 +529,15 @@ def draw_ensemble_starts(guid: Guidance, n_groups: int, n_obj: int, n_steps: int
 @_restores_row_field
 def guided_multi_object_groups(unet: Unet1d, guid: Guidance, sched: DDIMScheduler, mode: str, noise: torch.Tensor,
                                groups: Sequence[Sequence[int]], opt_objs: Sequence[Union[str, Goal]], streams: Optional[Sequence[StartStream]] = None,
-                               predrawn: Optional[np.ndarray] = None, python_loop: bool = False) -> torch.Tensor:
+                               predrawn: Optional[np.ndarray] = None, python_loop: bool = False, global_cond: Optional[torch.Tensor] = None,
+                               cfg_weight: float = 1.0) -> torch.Tensor:
     """Several independent ``guided_sample_multi_object`` chains (:637-647) in the same launches: chain k averages the guidance
     gradients of the objects ``groups[k]`` for objective ``opt_objs[k]`` (a guidance ensemble: n_obj dynamics-gradient
     evaluations per denoise step).  All groups have the same size.  Launch order of the gradient chains is object-major,
     (j, k) -> j * K + k, so the mean over j is one strided reduction for every group at once.  Returns (K, B, L, 1)."""
     K, n_obj, (B, L, _) = len(groups), len(groups[0]), noise.shape
     assert all(len(g) == n_obj for g in groups) and len(opt_objs) == K
+    cond_all, cond_shared = _chain_cond(unet, global_cond, K, B)       # global_cond: (B, gc) for all groups or (K, B, gc)
     if any(not is_goal(o) and o == 'convergence' for o in opt_objs):
         raise ValueError("the reference never runs the multi-object loop with 'convergence' (generator/diffusion.py:337)")
     dev = noise.device
@@ -534,17 +556,18 @@ def guided_multi_object_groups(unet: Unet1d, guid: Guidance, sched: DDIMSchedule
     if not python_loop:       # one library call: K chains x n_obj gradients each, gradient chains object-major
         out = engine.guided_chains_run(unet, guid, noise.reshape(B, L), K, n_obj, objectives, None,
                                        np.ascontiguousarray(predrawn) if is3d else None, [int(t) for t in sched.timesteps],
-                                       [sched.coefficients(int(t)) for t in sched.timesteps], [scale] * K)
+                                       [sched.coefficients(int(t)) for t in sched.timesteps], [scale] * K, global_cond, cfg_weight)
         return out.reshape(K, B, L, 1)
     x = noise.reshape(1, B, L).expand(K, -1, -1).contiguous().to(torch.float32)
     for si, t in enumerate(sched.timesteps):
         t = int(t)
-        if si == 0 and K > 1:        # all K chains start from the same noise: one eps-net evaluation (see guided_chains)
+        if si == 0 and K > 1 and cond_shared:        # all K chains start from the same noise: one eps-net evaluation (see guided_chains)
             ts = torch.full((B,), t, dtype=torch.int32, device=dev)
-            eps = unet.forward(x[0].reshape(B, L, 1), ts).reshape(1, B, L).expand(K, -1, -1).contiguous()
+            eps = unet.forward_cfg(x[0].reshape(B, L, 1), ts, None if cond_all is None else cond_all[:B], cfg_weight)
+            eps = eps.reshape(1, B, L).expand(K, -1, -1).contiguous()
         else:
             ts = torch.full((K * B,), t, dtype=torch.int32, device=dev)
-            eps = unet.forward(x.reshape(K * B, L, 1), ts).reshape(K, B, L)
+            eps = unet.forward_cfg(x.reshape(K * B, L, 1), ts, cond_all, cfg_weight).reshape(K, B, L)
         g = guid.grad(x.repeat(n_obj, 1, 1), t, objectives, None, predrawn[si].reshape(-1) if is3d else None)     # (n_obj*K, B, L)
         x = engine.ddim_guided_step(x, eps, g, n_obj, sched.coefficients(t), scale)
     return x.reshape(K, B, L, 1)

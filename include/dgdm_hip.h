@@ -75,15 +75,26 @@ int         dgdm_device_init(int ordinal);
 int         dgdm_objective_from_name(const char *opt_obj, DgdmObjective *out);
 
 /* ------------------------------------------------------------------ a7: noise-prediction net
- * ConditionalUnet1D(input_dim=1, global_cond_dim=0, down_dims, diffusion_step_embed_dim,
- * kernel_size=5, n_groups=8)  (generator/diffusion_utils.py:124-236).                          */
+ * ConditionalUnet1D(input_dim=1, global_cond_dim, down_dims, diffusion_step_embed_dim,
+ * kernel_size=5, n_groups=8)  (generator/diffusion_utils.py:124-236).  global_cond_dim (0..256) is read from the state dict: the
+ * in_features of every `*.cond_encoder.1.weight` minus step_embed_dim; the eight blocks must agree (DGDM_EINVAL names the tensor). */
 int dgdm_unet1d_create(DgdmUnet1d **out, const DgdmTensor *state_dict, int n_tensors,
                        const int32_t *down_dims, int n_down, int step_embed_dim, int kernel_size, int n_groups);
 void dgdm_unet1d_destroy(DgdmUnet1d *m);
+int dgdm_unet1d_global_cond_dim(const DgdmUnet1d *m);      /* negative: null handle */
 /* ConditionalUnet1D.forward (diffusion_utils.py:238-285): sample_dev [B][L] (input_dim 1),
  * timestep_dev [B] int32 (one per sample), eps_dev [B][L].                                      */
 int dgdm_unet1d_forward(DgdmUnet1d *m, const float *sample_dev, const int32_t *timestep_dev, float *eps_dev,
                         int B, int L, void *stream);
+/* The same with global_cond (diffusion_utils.py:254-257): global_cond_dev [B][global_cond_dim], one row per sample.  Every block's
+ * FiLM vector is Linear(Mish(cat(step embedding, global_cond row))), float32 in every contraction mode.  With global_cond_dim 0 the
+ * condition is ignored (NULL: the call above, bit for bit); with global_cond_dim > 0 a NULL condition - and so dgdm_unet1d_forward -
+ * is DGDM_EINVAL, before anything is launched.                                                                                    */
+int dgdm_unet1d_forward_cond(DgdmUnet1d *m, const float *sample_dev, const int32_t *timestep_dev, const float *global_cond_dev,
+                             float *eps_dev, int B, int L, void *stream);
+/* Classifier-free guidance mix, elementwise: out = eps_u + w * (eps_c - eps_u), the three float32 operations each rounded on its own
+ * (no fused multiply-add).  out may be either input.                                                                              */
+int dgdm_cfg_mix(const float *eps_c_dev, const float *eps_u_dev, float w, float *out_dev, int64_t numel, void *stream);
 /* Arithmetic of the convolutions with more than one input and output channel.  DGDM_DTYPE_F32 (default, the parity path):
  * float32-grade on the f16 matrix pipe - every float32 product as three f16 MFMA products on operands scaled by exact powers of two
  * (per convolution's weights, per sample and convolution input) and split in two f16 pieces, float32 accumulation (DESIGN_HISTORY.md 4.2;
@@ -94,7 +105,8 @@ int dgdm_unet1d_forward(DgdmUnet1d *m, const float *sample_dev, const int32_t *t
 int dgdm_unet1d_set_contraction_dtype(DgdmUnet1d *m, int dtype);
 /* What a dgdm_unet1d_forward call with B samples of L control points actually runs: the DGDM_DTYPE_* of its convolutions
  * (DGDM_DTYPE_F32_F16X3, DGDM_DTYPE_F32_MFMA - also where the split form's slabs do not fit the LDS - or DGDM_DTYPE_BF16), + 16 when the
- * layer-by-layer batched form is used (large batches; the same bits as the per-sample kernel).  Negative: bad argument.               */
+ * layer-by-layer batched form is used (large batches; the same bits as the per-sample kernel).  Negative: bad argument.  Depends on the
+ * handle's global_cond_dim: up to 128 the condition row shares LDS the step encoder has finished with, beyond that it adds to the footprint. */
 int dgdm_unet1d_effective_form(const DgdmUnet1d *m, int B, int L);
 
 /* ------------------------------------------------------------------ a13/a14: scheduler step
@@ -265,6 +277,18 @@ int dgdm_guidance_score(DgdmGuidance *g, const float *x_dev, int timestep, const
 int dgdm_guided_chains_run(DgdmUnet1d *unet, DgdmGuidance *g, const float *noise_dev, int n_chains, int n_grad,
                            const DgdmObjective *objectives, const float *rowcoef_dev, const int64_t *starts_host,
                            const int32_t *timesteps, const float *coef, const float *scales, int n_steps, float *x_out_dev, void *stream);
+/* The same for a conditional eps-net (dgdm_guided_chains_run is this call with NULL, 0, 1).
+ *   global_cond_dev    cond_chain_stride == 0: [B][gc], shared by all chains; == B * gc: [n_chains][B][gc]; anything else: DGDM_EINVAL
+ *   cfg_weight         classifier-free guidance: eps = eps_u + w (eps_c - eps_u) (dgdm_cfg_mix), eps_u = the net on the all-zero condition
+ *                      row.  w == 1 evaluates eps_c only (the plain conditional run), w == 0 eps_u only; otherwise both halves go through
+ *                      ONE eps-net call of twice the samples.
+ * The classifier-guidance term and the DDIM step follow as above.  With one shared condition block the first eps-net call is still
+ * evaluated once for all chains; with per-chain conditions it covers all n_chains * B samples.  Equivalent, bit for bit, to calling
+ * dgdm_unet1d_forward_cond / dgdm_cfg_mix / dgdm_dyn{2,3}d_guidance_grad / dgdm_ddim_guided_step step by step.                        */
+int dgdm_guided_chains_run_cond(DgdmUnet1d *unet, DgdmGuidance *g, const float *noise_dev, int n_chains, int n_grad,
+                                const DgdmObjective *objectives, const float *rowcoef_dev, const int64_t *starts_host,
+                                const int32_t *timesteps, const float *coef, const float *scales, int n_steps, float *x_out_dev,
+                                const float *global_cond_dev, int64_t cond_chain_stride, float cfg_weight, void *stream);
 
 /* Forward-only sweep of Diffusion.get_convergence_centers (diffusion.py:506-531): G orientations,
  * pos = 0, t = 0, rows r = g*B + b.  logits_dev [n_chains][B*G][3].  starts_host (3-D) holds
@@ -698,7 +722,8 @@ int dgdm_class_agreement(const float *score_dev, const float *pred_dev, int64_t 
  * Diffusion.get_stats / training_step (generator/diffusion.py:126-177) for the ConditionalUnet1D of generator/train.py:80
  * (generator/diffusion_utils.py:123-285; input_dim 1, down_dims [128, 256], kernel 5, 8 groups), torch.optim.Adam
  * (diffusion.py:711-714) and the EMA copy of diffusers' EMAModel (diffusion.py:716-724).  Parameters, gradients, both Adam moments and the
- * EMA copy live on the device in the state_dict's own tensor layouts (keys as ConditionalUnet1D.state_dict() gives them).          */
+ * EMA copy live on the device in the state_dict's own tensor layouts (keys as ConditionalUnet1D.state_dict() gives them).
+ * global_cond_dim is read from the state dict as in dgdm_unet1d_create.                                                           */
 typedef struct DgdmUnetTrainer DgdmUnetTrainer;
 int dgdm_unet_trainer_create(DgdmUnetTrainer **out, const DgdmTensor *state_dict, int n_tensors, int num_points, const int32_t *down_dims,
                              int n_down, int diffusion_step_embed_dim, int kernel_size, int n_groups, float beta1, float beta2, float eps,
@@ -720,6 +745,17 @@ int dgdm_unet_trainer_step(DgdmUnetTrainer *m, const float *x0_dev, const float 
 int dgdm_unet_trainer_forward_backward(DgdmUnetTrainer *m, const float *x0_dev, const float *noise_dev, const float *sqrt_abar_dev,
                                        const float *sqrt_1m_abar_dev, const int64_t *timesteps_dev, int samples, int64_t total_samples,
                                        int backward, float *pred_dev, float *loss_host, void *stream);
+/* The two calls above for a conditional eps-net: global_cond_dev [samples][global_cond_dim] goes, after Mish, into every cond_encoder
+ * next to the step embedding; weight and bias gradients cover all step_embed_dim + global_cond_dim columns, the condition itself is
+ * data (no gradient).  The calls above are these with NULL; a handle with global_cond_dim > 0 needs a condition (DGDM_EINVAL).       */
+int dgdm_unet_trainer_step_cond(DgdmUnetTrainer *m, const float *x0_dev, const float *noise_dev, const float *sqrt_abar_dev,
+                                const float *sqrt_1m_abar_dev, const int64_t *timesteps_dev, const float *global_cond_dev, int samples,
+                                float lr, float *pred_dev, float *loss_host, void *stream);
+int dgdm_unet_trainer_forward_backward_cond(DgdmUnetTrainer *m, const float *x0_dev, const float *noise_dev, const float *sqrt_abar_dev,
+                                            const float *sqrt_1m_abar_dev, const int64_t *timesteps_dev, const float *global_cond_dev,
+                                            int samples, int64_t total_samples, int backward, float *pred_dev, float *loss_host,
+                                            void *stream);
+int dgdm_unet_trainer_global_cond_dim(const DgdmUnetTrainer *m);
 int64_t dgdm_unet_trainer_gradient_count(const DgdmUnetTrainer *m);
 int dgdm_unet_trainer_gradients(DgdmUnetTrainer *m, float *flat_dev, int64_t numel, int to_trainer, float scale, void *stream);
 int dgdm_unet_trainer_apply(DgdmUnetTrainer *m, float lr, void *stream);
