@@ -116,5 +116,6 @@ std::vector<float> transpose(const float *src, int rows, int cols);   // -> [col
 constexpr int PROF_BUCKETS = DGDM_STAGE_COUNT;
 void prof_begin(hipStream_t s, int stage);
 void prof_end(hipStream_t s, int stage, double work);
+bool prof_on();       // the stage events assume one stream: while profiling is enabled the guidance handle keeps its serial step schedule
 
 }  // namespace dgdm

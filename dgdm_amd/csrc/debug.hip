@@ -124,6 +124,24 @@ extern "C" int dgdm_linear_act(const float *x_dev, int ldx, const float *wt_dev,
     return linear(x_dev, ldx, wt_dev, bias_dev, nullptr, 1, y_dev, ldy, rows, K, N, act, false, (hipStream_t)stream);
 }
 
+// Test hooks for the float64 stages around the trunk (smallnet.hip), on caller-supplied operands
+extern "C" int dgdm_debug_linear64(const double *x_dev, int ldx, const double *wt_dev, const double *bias_dev, double *y_dev, int ldy, int rows, int K,
+                                   int N, int act, void *stream) {
+    using namespace dgdm;
+    DGDM_REQUIRE(x_dev && wt_dev && y_dev && rows >= 0 && K > 0 && N > 0 && ldx >= K && ldy >= N, DGDM_EINVAL, "dgdm_debug_linear64: bad argument");
+    DGDM_REQUIRE(act == ACT_NONE || act == ACT_RELU || act == ACT_SILU, DGDM_EINVAL, "dgdm_debug_linear64: activation %d", act);
+    return linear64(nullptr, x_dev, ldx, wt_dev, bias_dev, nullptr, 1, y_dev, nullptr, ldy, rows, K, N, act, (hipStream_t)stream);
+}
+
+extern "C" int dgdm_debug_dyn_post64(int W1, const float *partial_dev, int tiles_per_b, const double *w1c_dev, const double *g2w_dev,
+                                     const double *g0w_dev, const double *V_dev, float *grad_dev, int rows, int L, void *stream) {
+    using namespace dgdm;
+    DGDM_REQUIRE(partial_dev && w1c_dev && g2w_dev && g0w_dev && V_dev && grad_dev && rows >= 0 && tiles_per_b > 0 && L > 0, DGDM_EINVAL,
+                 "dgdm_debug_dyn_post64: bad argument");
+    DGDM_REQUIRE(W1 == 256 || W1 == 512, DGDM_EINVAL, "dgdm_debug_dyn_post64: W1 %d (256 or 512)", W1);
+    return dyn_post64(W1, partial_dev, tiles_per_b, w1c_dev, g2w_dev, g0w_dev, V_dev, grad_dev, rows, L, (hipStream_t)stream);
+}
+
 extern "C" int dgdm_group_max(const float *x_dev, int64_t groups, int nsample, int C, float *out_dev, void *stream) {
     using namespace dgdm;
     DGDM_REQUIRE(x_dev && out_dev && groups >= 0 && nsample > 0 && C > 0, DGDM_EINVAL, "dgdm_group_max: bad argument");

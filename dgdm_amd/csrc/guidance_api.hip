@@ -74,6 +74,7 @@ struct DgdmGuidance {
     // so the A table carries one float32 rounding); ttmp64: scratch of the time encoder
     DevBuf V, genc, atab, chainbias, timepart, ttmp, ttmp64, partial, objdev, objidx, xobj, xobj16, starts, order, xchains, todo, groupoff;
     DevBuf loopx[2], loopeps, loopgrad, loopxrep, loopts;      // workspace of dgdm_guided_chains_run
+    DevBuf loopeps1;                                           // ... step 0's one eps-net evaluation [B][L], replicated into loopeps
     DevBuf loopcond, loopx2, loopeps2;                         // ... with a condition: [cond rows | zero rows], and the doubled batch of the classifier-free mix
     DevBuf scorelogits;                      // dgdm_guidance_score: the logits when the caller does not want them
     // dgdm_guidance_rollout: the sweep's orientations [G] (built with the handle), and its scratch, grown on demand: the state
@@ -103,7 +104,36 @@ struct DgdmGuidance {
     int *ro_host = nullptr; size_t ro_ints = 0; hipEvent_t ro_ev = nullptr; bool ro_pending = false;
     int finish_objects();
     hipStream_t cstream = nullptr; hipEvent_t up_ready = nullptr, up_consumed = nullptr; bool consumed_recorded = false;
+    // Step schedule.  The 3-D table build runs on the build streams alone and ends in ro_ev on bstream[0]; the first
+    // call that reads the tables on a stream makes that stream wait for it (join_tables).  Inside the denoise loop the eps-net runs on
+    // bstream[0] (idle by then) beside common_pre and is joined in front of the trunk.  serial = DGDM_SERIAL_STEP, read at create:
+    // 1 everything on the caller's stream, in the order of the data dependencies (also while dgdm_prof_enable is on: the stage events
+    // assume one stream); for measuring the parts apart, 2 = only the table build stays on the caller's stream, 4 = only the eps-net does
+    int serial = 0;
+    bool tables_off_stream() const { return !(serial & 3) && !prof_on(); }
+    bool eps_beside() const { return !(serial & 5) && !prof_on(); }
+    bool hoist_x_only() const { return !(serial & 1) && !prof_on(); }
+    bool built_off_stream = false, join_pending = false, built_once = false;
+    hipStream_t joined_stream = nullptr;
+    hipEvent_t fork_ev = nullptr, side_ev = nullptr;
+    int join_tables(hipStream_t s) {
+        if (!built_off_stream || (!join_pending && s == joined_stream)) return DGDM_OK;
+        DGDM_HIP_CHECK(hipStreamWaitEvent(s, ro_ev, 0));
+        join_pending = false; joined_stream = s;
+        return DGDM_OK;
+    }
+    int side_stream(hipStream_t *side) {
+        if (!bstream[0]) DGDM_HIP_CHECK(hipStreamCreateWithFlags(&bstream[0], hipStreamNonBlocking));
+        if (!fork_ev) DGDM_HIP_CHECK(hipEventCreateWithFlags(&fork_ev, hipEventDisableTiming));
+        if (!side_ev) DGDM_HIP_CHECK(hipEventCreateWithFlags(&side_ev, hipEventDisableTiming));
+        *side = bstream[0];
+        return DGDM_OK;
+    }
     ~DgdmGuidance() {
+        for (int i = 0; i < NBUILD; ++i)
+            if (bstream[i]) (void)hipStreamSynchronize(bstream[i]);      // a build nobody joined may still be writing the buffers freed below
+        if (fork_ev) (void)hipEventDestroy(fork_ev);
+        if (side_ev) (void)hipEventDestroy(side_ev);
         if (pinned) (void)hipHostFree(pinned);
         if (pinned_ev) (void)hipEventDestroy(pinned_ev);
         if (ro_host) (void)hipHostFree(ro_host);
@@ -152,8 +182,9 @@ struct DgdmGuidance {
     // what cond_fn's gradient and its forward-only scoring share, up to the trunk launch: common_pre, 3-D: the rows' embeddings (`emb` /
     // `call` as guidance_grad takes them), and the trunk parameters of the cond_fn grid in the float32 form (the caller swaps the weight
     // streams for its arithmetic and adds its outputs)
+    // pre_done: the caller has already enqueued common_pre for this x and timestep (the denoise loop does, ahead of the tables' join)
     int trunk_front(int kind, const float *x_dev, int timestep, const int *objidx_host, const int64_t *starts_host, int n_chains, const Embedded *emb,
-                    int call, dgdm::TrunkParams *p, hipStream_t s);
+                    int call, dgdm::TrunkParams *p, hipStream_t s, bool pre_done = false);
 };
 
 int DgdmGuidance::build_pose_table(const std::vector<float> &ori, const std::vector<float> &pos, PoseGrid *dst, hipStream_t s) {
@@ -200,6 +231,7 @@ extern "C" int dgdm_guidance_create(DgdmGuidance **out, DgdmDynamics *model, con
     std::unique_ptr<DgdmGuidance> g(new DgdmGuidance());
     g->m = model; g->cfg = *cfg;
     g->B = cfg->batch;
+    if (const char *e = getenv("DGDM_SERIAL_STEP")) g->serial = atoi(e);      // test hook: the serial step schedule
     const int G = cfg->grid_size, P = cfg->num_pos, C = G * P * P;
     // pose grid: torch.meshgrid(linspace(ori), linspace(-1,1,P), linspace(-1,1,P)) 'ij' -> cell = (g*P + px)*P + py  (diffusion.py:478)
     const std::vector<float> lo = linspace_f32(cfg->ori_lo, cfg->ori_hi, G), lp = linspace_f32(-1.f, 1.f, P);
@@ -404,13 +436,19 @@ extern "C" int dgdm_guidance_set_objects(DgdmGuidance *g, const float *objects_d
         // objects are independent: build them round-robin on a few side streams so the latency-bound stages (FPS: 512
         // dependent iterations on 128 workgroups) of one object overlap the bandwidth/MFMA-bound stages of the others
         const int nb = std::min<int>(DgdmGuidance::NBUILD, n_objects);
+        // off the caller's stream (step schedule): only the copy of the coordinates stays on `s`; the FPS tables go to
+        // the last build stream (a second one even for a single object: they run beside the light stages), and what reads the tables
+        // later waits for the build's end (join_tables)
+        const bool off = g->tables_off_stream();
+        const int ns = off ? std::max(nb, 2) : nb;
+        if (!off && (rc = g->join_tables(s))) return rc;      // an earlier build off this stream that nobody has joined yet
         if (!g->bstart) DGDM_HIP_CHECK(hipEventCreateWithFlags(&g->bstart, hipEventDisableTiming));
         if (!g->ldone) DGDM_HIP_CHECK(hipEventCreateWithFlags(&g->ldone, hipEventDisableTiming));
-        for (int i = 0; i < nb; ++i) {
+        for (int i = 0; i < ns; ++i) {
             if (!g->bstream[i]) DGDM_HIP_CHECK(hipStreamCreateWithFlags(&g->bstream[i], hipStreamNonBlocking));
             if (!g->bev[i]) DGDM_HIP_CHECK(hipEventCreateWithFlags(&g->bev[i], hipEventDisableTiming));
         }
-        // T1 for every object at once, on the caller's stream: fps1[obj][start][512], fps2[obj][start point][128] + tie flags
+        // T1 for every object at once (stream `fs` below): fps1[obj][start][512], fps2[obj][start point][128] + tie flags
         const size_t no = (size_t)n_objects;
         if ((rc = g->pool_xyz.alloc(no * N * 3 * 4)) || (rc = g->pool_fps1.alloc(no * N * 512 * sizeof(int))) ||
             (rc = g->pool_fps2.alloc(no * N * 128 * sizeof(int))) || (rc = g->pool_flags.alloc(no * N * sizeof(int))) ||
@@ -422,9 +460,20 @@ extern "C" int dgdm_guidance_set_objects(DgdmGuidance *g, const float *objects_d
         if (!g->pooled) DGDM_HIP_CHECK(hipEventCreateWithFlags(&g->pooled, hipEventDisableTiming));
         DGDM_HIP_CHECK(hipMemcpyAsync(g->pool_xyz.p, objects_dev, no * N * 3 * 4, hipMemcpyDeviceToDevice, s));
         DGDM_HIP_CHECK(hipEventRecord(g->pooled, s));
+        hipStream_t fs = s;
+        if (off) {
+            // `pooled` lies behind everything the previous chains enqueued on `s` (their side-stream work is joined into `s` before
+            // they return), so the build may overwrite the tables they read; a previous build nobody joined has ended at ro_ev
+            fs = g->bstream[ns - 1];
+            for (int i = 1; i < ns; ++i) {
+                DGDM_HIP_CHECK(hipStreamWaitEvent(g->bstream[i], g->pooled, 0));
+                if (g->built_once) DGDM_HIP_CHECK(hipStreamWaitEvent(g->bstream[i], g->ro_ev, 0));
+            }
+        }
         // sa2's FPS table is the first 128 columns of sa1's (same clouds, same starts): one pass writes both and the tie flags
-        if ((rc = pn_fps_tables(g->pool_xyz.as<float>(), N, N, g->pool_fps1.as<int>(), g->pool_fps2.as<int>(), g->pool_flags.as<int>(), s, n_objects)))
+        if ((rc = pn_fps_tables(g->pool_xyz.as<float>(), N, N, g->pool_fps1.as<int>(), g->pool_fps2.as<int>(), g->pool_flags.as<int>(), fs, n_objects)))
             return rc;
+        DGDM_HIP_CHECK(hipEventRecord(g->bstart, fs));
         for (int i = 0; i < n_objects; ++i) {
             ObjectTables &t = *g->tables[i];
             t.xyz = g->pool_xyz.as<float>() + (size_t)i * N * 3; t.fps1 = g->pool_fps1.as<int>() + (size_t)i * N * 512;
@@ -453,16 +502,17 @@ extern "C" int dgdm_guidance_set_objects(DgdmGuidance *g, const float *objects_d
             }
             DGDM_HIP_CHECK(hipEventRecord(g->ldone, ls));
         }
-        DGDM_HIP_CHECK(hipEventRecord(g->bstart, s));
-        for (int i = 0; i < nb; ++i) {
+        for (int i = 0; i < nb; ++i) {       // the heavy stages need the FPS tables (bstart) and the light stages' outputs
             DGDM_HIP_CHECK(hipStreamWaitEvent(g->bstream[i], g->bstart, 0));
             DGDM_HIP_CHECK(hipStreamWaitEvent(g->bstream[i], g->ldone, 0));
         }
         for (int i = 0; i < n_objects; ++i)
             if ((rc = g->build_object(i, i % nb, g->bstream[i % nb]))) return rc;
-        for (int i = 0; i < nb; ++i) {
+        // the build's end: on the caller's stream, or (off it) on bstream[0], which has the FPS stream behind it through bstart
+        hipStream_t es = off ? g->bstream[0] : s;
+        for (int i = off ? 1 : 0; i < nb; ++i) {
             DGDM_HIP_CHECK(hipEventRecord(g->bev[i], g->bstream[i]));
-            DGDM_HIP_CHECK(hipStreamWaitEvent(s, g->bev[i], 0));
+            DGDM_HIP_CHECK(hipStreamWaitEvent(es, g->bev[i], 0));
         }
         // which objects may use the table of FPS(128) sequences (no order-dependent selection anywhere); crowded-centre counts:
         // copied to pinned memory behind an event, read by finish_objects() when first needed
@@ -475,10 +525,11 @@ extern "C" int dgdm_guidance_set_objects(DgdmGuidance *g, const float *objects_d
             g->ro_ints = need;
         }
         if (!g->ro_ev) DGDM_HIP_CHECK(hipEventCreateWithFlags(&g->ro_ev, hipEventDisableTiming));
-        DGDM_HIP_CHECK(hipMemcpyAsync(g->ro_host, g->pool_flags.p, sizeof(int) * no * N, hipMemcpyDeviceToHost, s));
-        DGDM_HIP_CHECK(hipMemcpyAsync(g->ro_host + no * N, g->pool_ncr.p, sizeof(int) * no, hipMemcpyDeviceToHost, s));
-        DGDM_HIP_CHECK(hipEventRecord(g->ro_ev, s));
+        DGDM_HIP_CHECK(hipMemcpyAsync(g->ro_host, g->pool_flags.p, sizeof(int) * no * N, hipMemcpyDeviceToHost, es));
+        DGDM_HIP_CHECK(hipMemcpyAsync(g->ro_host + no * N, g->pool_ncr.p, sizeof(int) * no, hipMemcpyDeviceToHost, es));
+        DGDM_HIP_CHECK(hipEventRecord(g->ro_ev, es));
         g->ro_pending = true;
+        g->built_once = true; g->built_off_stream = off; g->join_pending = off;
     }
     g->n_objects = n_objects;
     g->grads_since_set = 0;
@@ -702,6 +753,7 @@ int DgdmGuidance::embed_rows(const int *oidx, int n_chains, const int64_t *start
     for (int i = 0; i < n_chains && tab; ++i) tab = want16 ? tables[oidx[i]]->has_x16 : tables[oidx[i]]->has_x;   // else: built in the other format, or not at all
     const int64_t rt = rows_per_call * n_calls;
     int rc;
+    if ((rc = join_tables(s))) return rc;       // every reader of the tables comes through here (or through embed's build_xtab)
     if ((rc = upload_starts(starts_host, n_chains, rows_per_call, s, !tab, n_calls, call_stride))) return rc;     // host work: overlaps a table build still in flight
     if ((rc = finish_objects())) return rc;
     e->tab = tab; e->used16 = want16; e->rows_per_chain = rt;
@@ -728,6 +780,7 @@ void DgdmGuidance::Embedded::point(TrunkParams *p, const DgdmGuidance &g, int ca
 int DgdmGuidance::embed(const int *oidx, int n_chains, const int64_t *starts_host, int n_calls, int64_t call_stride, Embedded *e, hipStream_t s) {
     DGDM_REQUIRE(starts_host, DGDM_EINVAL, "3-D guidance needs the FPS start indices");
     int rc;
+    if ((rc = join_tables(s))) return rc;
     prof_begin(s, DGDM_STAGE_XOBJ);
     // The table X[s1][q] of an object costs about what 7 cond_fn calls spend gathering its rows (it holds all 262 144 (s1, q)
     // pairs; one call touches 36 000 of them): it pays as soon as the objects serve more than one 5-step chain - the
@@ -749,13 +802,15 @@ int DgdmGuidance::embed(const int *oidx, int n_chains, const int64_t *starts_hos
 }
 
 int DgdmGuidance::trunk_front(int kind, const float *x_dev, int timestep, const int *oidx, const int64_t *starts_host, int n_chains, const Embedded *emb,
-                              int call, TrunkParams *pp, hipStream_t s) {
+                              int call, TrunkParams *pp, hipStream_t s, bool pre_done) {
     const float t_scaled = (float)timestep / (float)cfg.num_train_timesteps;      // timesteps.float() / T  (diffusion.py:487,496)
     int rc;
     if ((rc = check_objects(oidx, n_chains))) return rc;
-    prof_begin(s, DGDM_STAGE_GUIDE_MISC);
-    if ((rc = common_pre(x_dev, t_scaled, oidx, n_chains, s))) return rc;
-    prof_end(s, DGDM_STAGE_GUIDE_MISC, 0.0);
+    if (!pre_done) {
+        prof_begin(s, DGDM_STAGE_GUIDE_MISC);
+        if ((rc = common_pre(x_dev, t_scaled, oidx, n_chains, s))) return rc;
+        prof_end(s, DGDM_STAGE_GUIDE_MISC, 0.0);
+    }
     m->fill_trunk(pp);
     set_grid(pp, grid, n_chains);
     if (kind == 3) {
@@ -789,7 +844,7 @@ static int check_objectives(const DgdmGuidance *g, const DgdmObjective *objectiv
 // emb == nullptr: this call's own (starts_host = its draws).
 static int guidance_grad(DgdmGuidance *g, int kind, const float *x_dev, int timestep, const DgdmObjective *objectives, const float *rowcoef_dev,
                          const int64_t *starts_host, int n_chains, float *grad_dev, hipStream_t s, const DgdmGuidance::Embedded *emb = nullptr,
-                         int call = 0) {
+                         int call = 0, bool pre_done = false) {
     DGDM_REQUIRE(g && x_dev && objectives && grad_dev, DGDM_EINVAL, "guidance_grad: null argument");
     if (g->m->kind != kind) { set_error("model type not supported: %d-D entry point on a %d-D model", kind, g->m->kind); return DGDM_EMODE; }
     DGDM_REQUIRE(n_chains > 0 && n_chains <= g->cfg.max_chains, DGDM_EINVAL, "n_chains %d outside 1..%d", n_chains, g->cfg.max_chains);
@@ -803,7 +858,7 @@ static int guidance_grad(DgdmGuidance *g, int kind, const float *x_dev, int time
         tob[i].use_rowcoef = objectives[i].use_rowcoef; tob[i].pad = 0;
     }
     TrunkParams p;
-    if ((rc = g->trunk_front(kind, x_dev, timestep, oidx.data(), starts_host, n_chains, emb, call, &p, s))) return rc;
+    if ((rc = g->trunk_front(kind, x_dev, timestep, oidx.data(), starts_host, n_chains, emb, call, &p, s, pre_done))) return rc;
     DGDM_HIP_CHECK(hipMemcpyAsync(g->objdev.p, tob.data(), sizeof(TrunkObjective) * n_chains, hipMemcpyHostToDevice, s));
     p.obj = g->objdev.as<TrunkObjective>(); p.rowcoef = rowcoef_dev; p.rowfield = g->rowfield;
     p.partial = g->partial.as<float>();
@@ -988,58 +1043,91 @@ extern "C" int dgdm_guided_chains_run_cond(DgdmUnet1d *unet, DgdmGuidance *g, co
     const int64_t call_stride = (int64_t)n_chains * n_grad * spc;
     int cpe = kind == 3 ? (int)std::min<int64_t>(n_steps, std::max<int64_t>(1, (((int64_t)1 << 22) - 1) / std::max<int64_t>(1, g->grid.rows))) : n_steps;
     if (const char *e = getenv("DGDM_EMBED_CALLS")) cpe = std::max(1, std::min(cpe, atoi(e)));      // test hook: calls per gather launch
-    if (kind == 3) {         // the embeddings are made here, ahead of guidance_grad's own check
-        for (int i = 0; i < n_chains * n_grad; ++i) oidx[i] = objectives[i].object;
-        if ((rc = g->check_objects(oidx.data(), n_chains * n_grad))) return rc;
-    }
-    for (int si = 0; si < n_steps; ++si) {
+    // the embeddings and common_pre are made here, ahead of guidance_grad's own check
+    for (int i = 0; i < n_chains * n_grad; ++i) oidx[i] = objectives[i].object;
+    if ((rc = g->check_objects(oidx.data(), n_chains * n_grad))) return rc;
+    DGDM_REQUIRE(same_scale || n_grad == 1, DGDM_EINVAL, "per-chain guidance scales with averaged gradients are not supported");
+    // Step schedule.  eps-net and cond_fn both depend on x_t alone, so the eps-net (with its timestep fill,
+    // classifier-free copies and mix, and step 0's replication) runs on bstream[0] beside common_pre's latency-bound float64 kernels,
+    // between two events: fork_ev on `s` once x_t is final, side_ev on the side stream, which `s` waits for in front of the trunk (beside
+    // the trunk itself the eps-net costs the trunk what it saves: DESIGN.md 4.3b) - every call's side work is joined into `s` before
+    // the call returns.  A 3-D step 0 stays on `s`: the side stream may still be building the tables.  What reads no table - all of
+    // the above and common_pre - is enqueued BEFORE the step's embed(), which joins `s` to the build: step 0 runs it beside the build.
+    const bool hoist = g->hoist_x_only(), beside = g->eps_beside();
+    hipStream_t side = s;
+    if (beside && (rc = g->side_stream(&side))) return rc;
+    if ((rc = g->loopeps1.alloc(per_chain * 4))) return rc;
+    auto step = [&](int si) -> int {
+        int rc;
         float *x = g->loopx[si & 1].as<float>(), *xn = (si + 1 == n_steps) ? x_out_dev : g->loopx[(si + 1) & 1].as<float>();
         const int t = timesteps[si];
-        if (kind == 3 && si % cpe == 0 &&
+        const bool embed_due = kind == 3 && si % cpe == 0;
+        if (embed_due && !hoist &&
             (rc = g->embed(oidx.data(), n_chains * n_grad, starts_host + (size_t)si * call_stride, std::min(cpe, n_steps - si), call_stride, &emb, s))) return rc;
         // eps-net: at the first step all chains hold the same B fingers - one evaluation, replicated (same input, same bits) - unless
         // every chain has condition rows of its own
         const int nb = (si == 0 && n_chains > 1 && !per_chain_cond) ? B : n_chains * B;
         const int ne = cfg == 2 ? 2 * nb : nb;
-        hipLaunchKernelGGL(fill_i32_kernel, dim3((ne + 255) / 256), dim3(256), 0, s, g->loopts.as<int>(), t, ne);
+        const bool fork = beside && !(kind == 3 && si == 0);
+        const hipStream_t es = fork ? side : s;        // the eps-net's stream
+        if (fork) {
+            DGDM_HIP_CHECK(hipEventRecord(g->fork_ev, s));
+            DGDM_HIP_CHECK(hipStreamWaitEvent(es, g->fork_ev, 0));
+        }
+        // one evaluation for all chains lands in a buffer of its own and is replicated from there (loopgrad, the scratch of old, is
+        // cond_fn's output on the other stream)
+        float *eps_dst = nb != n_chains * B ? g->loopeps1.as<float>() : g->loopeps.as<float>();
+        hipLaunchKernelGGL(fill_i32_kernel, dim3((ne + 255) / 256), dim3(256), 0, es, g->loopts.as<int>(), t, ne);
         if (cfg == 2) {
             // [x | x] with [condition rows | zero rows] in one call (large runs land in the batched form), then the mix
             const size_t n = (size_t)nb * L, nc = (size_t)nb * gc;
             float *x2 = g->loopx2.as<float>(), *e2 = g->loopeps2.as<float>(), *c2 = g->loopcond.as<float>();
-            DGDM_HIP_CHECK(hipMemcpyAsync(x2, x, n * 4, hipMemcpyDeviceToDevice, s));
-            DGDM_HIP_CHECK(hipMemcpyAsync(x2 + n, x, n * 4, hipMemcpyDeviceToDevice, s));
+            DGDM_HIP_CHECK(hipMemcpyAsync(x2, x, n * 4, hipMemcpyDeviceToDevice, es));
+            DGDM_HIP_CHECK(hipMemcpyAsync(x2 + n, x, n * 4, hipMemcpyDeviceToDevice, es));
             // the zero half has to follow the nb condition rows directly: at full size it does (loopcond's layout), at step 0's B rows it is moved up
-            if (nc != ncond) DGDM_HIP_CHECK(hipMemsetAsync(c2 + nc, 0, nc * 4, s));
-            if ((rc = dgdm_unet1d_forward_cond(unet, x2, g->loopts.as<int>(), c2, e2, 2 * nb, L, s))) return rc;
+            if (nc != ncond) DGDM_HIP_CHECK(hipMemsetAsync(c2 + nc, 0, nc * 4, es));
+            if ((rc = dgdm_unet1d_forward_cond(unet, x2, g->loopts.as<int>(), c2, e2, 2 * nb, L, es))) return rc;
             if (nc != ncond) {       // restore chain 1's rows for the steps that follow
-                if (cond_chain_stride == 0) hipLaunchKernelGGL(repeat_rows_kernel, dim3((unsigned)((ncond + 255) / 256)), dim3(256), 0, s, global_cond_dev, c2, (int64_t)B * gc, n_chains);
-                else DGDM_HIP_CHECK(hipMemcpyAsync(c2, global_cond_dev, ncond * 4, hipMemcpyDeviceToDevice, s));
+                if (cond_chain_stride == 0) hipLaunchKernelGGL(repeat_rows_kernel, dim3((unsigned)((ncond + 255) / 256)), dim3(256), 0, es, global_cond_dev, c2, (int64_t)B * gc, n_chains);
+                else DGDM_HIP_CHECK(hipMemcpyAsync(c2, global_cond_dev, ncond * 4, hipMemcpyDeviceToDevice, es));
             }
-            if ((rc = dgdm_cfg_mix(e2, e2 + n, cfg_weight, g->loopeps.as<float>(), (int64_t)n, s))) return rc;
-        } else if ((rc = dgdm_unet1d_forward_cond(unet, x, g->loopts.as<int>(), cfg == 0 ? zero_rows : cond_rows, g->loopeps.as<float>(), nb, L, s))) return rc;
-        if (nb != n_chains * B) {
-            // replicate in place from the back so that the source block [0, per_chain) is read before it could be overwritten: separate buffer instead
-            hipLaunchKernelGGL(repeat_rows_kernel, dim3((unsigned)((nx + 255) / 256)), dim3(256), 0, s, g->loopeps.as<float>(), g->loopgrad.as<float>(), (int64_t)per_chain, n_chains);
-            DGDM_HIP_CHECK(hipMemcpyAsync(g->loopeps.p, g->loopgrad.p, nx * 4, hipMemcpyDeviceToDevice, s));
-        }
+            if ((rc = dgdm_cfg_mix(e2, e2 + n, cfg_weight, eps_dst, (int64_t)n, es))) return rc;
+        } else if ((rc = dgdm_unet1d_forward_cond(unet, x, g->loopts.as<int>(), cfg == 0 ? zero_rows : cond_rows, eps_dst, nb, L, es))) return rc;
+        if (nb != n_chains * B)
+            hipLaunchKernelGGL(repeat_rows_kernel, dim3((unsigned)((nx + 255) / 256)), dim3(256), 0, es, eps_dst, g->loopeps.as<float>(), (int64_t)per_chain, n_chains);
+        if (fork) DGDM_HIP_CHECK(hipEventRecord(g->side_ev, es));
         // cond_fn for the n_grad * n_chains gradient chains (object-major: gradient j of chain k is chain j * n_chains + k), x repeated
         const float *xg = x;
         if (n_grad > 1) {
             hipLaunchKernelGGL(repeat_rows_kernel, dim3((unsigned)((ng + 255) / 256)), dim3(256), 0, s, x, g->loopxrep.as<float>(), (int64_t)nx, n_grad);
             xg = g->loopxrep.as<float>();
         }
+        if (hoist) {
+            if ((rc = g->common_pre(xg, (float)t / (float)g->cfg.num_train_timesteps, oidx.data(), n_chains * n_grad, s))) return rc;
+            if (embed_due &&
+                (rc = g->embed(oidx.data(), n_chains * n_grad, starts_host + (size_t)si * call_stride, std::min(cpe, n_steps - si), call_stride, &emb, s))) return rc;
+        }
+        if (fork) DGDM_HIP_CHECK(hipStreamWaitEvent(s, g->side_ev, 0));
         if ((rc = guidance_grad(g, kind, xg, t, objectives, rowcoef_dev, nullptr, n_chains * n_grad, g->loopgrad.as<float>(), s,
-                                kind == 3 ? &emb : nullptr, si % cpe))) return rc;
+                                kind == 3 ? &emb : nullptr, si % cpe, hoist))) return rc;
         const float *cf = coef + 4 * si;
         if (same_scale) {
             if ((rc = dgdm_ddim_guided_step(x, g->loopeps.as<float>(), g->loopgrad.as<float>(), n_grad, xn, (int64_t)nx, cf[0], cf[1], cf[2], cf[3], scales[0], s))) return rc;
         } else {
-            DGDM_REQUIRE(n_grad == 1, DGDM_EINVAL, "per-chain guidance scales with averaged gradients are not supported");
             for (int c = 0; c < n_chains; ++c)
                 if ((rc = dgdm_ddim_guided_step(x + c * per_chain, g->loopeps.as<float>() + c * per_chain, g->loopgrad.as<float>() + c * per_chain, 1,
                                                 xn + c * per_chain, (int64_t)per_chain, cf[0], cf[1], cf[2], cf[3], scales[c], s))) return rc;
         }
-    }
+        return DGDM_OK;
+    };
+    for (int si = 0; si < n_steps; ++si)
+        if ((rc = step(si))) {
+            if (beside) {       // a step that failed half way: what it left on the side stream is joined all the same
+                (void)hipEventRecord(g->side_ev, side);
+                (void)hipStreamWaitEvent(s, g->side_ev, 0);
+            }
+            return rc;
+        }
     DGDM_HIP_CHECK(hipGetLastError());
     return DGDM_OK;
 }

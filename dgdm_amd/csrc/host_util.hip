@@ -148,6 +148,8 @@ struct ProfRec { hipEvent_t a, b; double work; };
 static bool g_prof_on = false;
 static std::vector<ProfRec> g_prof[PROF_BUCKETS];
 
+bool prof_on() { return g_prof_on; }
+
 void prof_begin(hipStream_t s, int bucket) {
     if (!g_prof_on) return;
     ProfRec r{};

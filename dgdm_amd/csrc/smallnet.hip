@@ -209,7 +209,7 @@ __global__ __launch_bounds__(256) void linear64_kernel(const float *__restrict__
                                                        const double *__restrict__ WT, const double *__restrict__ bias,
                                                        const double *__restrict__ rowbias, int rb_div, double *__restrict__ Yd,
                                                        float *__restrict__ Yf, int ldy, int rows, int K, int N) {
-    constexpr int KC = 64;
+    constexpr int KC = 64, KU = KC / 2;
     __shared__ double xs[RB][KC];
     const int r0 = blockIdx.x * RB;
     const int n = blockIdx.y * 256 + threadIdx.x;
@@ -219,6 +219,10 @@ __global__ __launch_bounds__(256) void linear64_kernel(const float *__restrict__
     for (int r = 0; r < RB; ++r) acc[r] = 0.0;
     for (int k0 = 0; k0 < K; k0 += KC) {
         const int kc = min(KC, K - k0);
+        const double *wp = WT + (size_t)k0 * N + nn;
+        double w0[KU], w1[KU];
+#pragma unroll
+        for (int j = 0; j < KU; ++j) w0[j] = wp[(size_t)min(j, kc - 1) * N];
         __syncthreads();
         for (int i = threadIdx.x; i < RB * KC; i += 256) {
             const int r = i / KC, k = i - r * KC;
@@ -227,16 +231,26 @@ __global__ __launch_bounds__(256) void linear64_kernel(const float *__restrict__
             xs[r][k] = v;
         }
         __syncthreads();
-        const double *wp = WT + (size_t)k0 * N + nn;
-        for (int k = 0; k < kc; k += 8) {       // eight weight loads in flight per step (the loop is L2-latency bound otherwise)
-            double w[8];
+        // the loop is L2-latency bound: the chunk's first KU weights are loaded above, beside the staging of X, its other KU before
+        // the first half's fma chain - up to 64 loads in flight per thread; the fma order (k ascending, one accumulator per output) is
+        // that of a one-at-a-time loop
+        if (kc > KU) {
 #pragma unroll
-            for (int j = 0; j < 8; ++j) w[j] = wp[(size_t)min(k + j, kc - 1) * N];
+            for (int j = 0; j < KU; ++j) w1[j] = wp[(size_t)min(KU + j, kc - 1) * N];
+        }
 #pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                if (k + j < kc) {
+        for (int j = 0; j < KU; ++j) {
+            if (j < kc) {
 #pragma unroll
-                    for (int r = 0; r < RB; ++r) acc[r] = fma(xs[r][k + j], w[j], acc[r]);
+                for (int r = 0; r < RB; ++r) acc[r] = fma(xs[r][j], w0[j], acc[r]);
+            }
+        }
+        if (kc > KU) {
+#pragma unroll
+            for (int j = 0; j < KU; ++j) {
+                if (KU + j < kc) {
+#pragma unroll
+                    for (int r = 0; r < RB; ++r) acc[r] = fma(xs[r][KU + j], w1[j], acc[r]);
                 }
             }
         }
@@ -285,52 +299,93 @@ int gather_add64(const double *a, const int *idx, const double *b, double *out, 
     return DGDM_OK;
 }
 
-template <int W1>
+// cond_fn's backward tail in float64 for RB fingers per workgroup.  A finger alone reads all three weight matrices (1.6 MB at W1 = 512)
+// from L2 for 1024 dependent fmas per thread: 1024 fingers made that 1.7 GB of L2 traffic per call, in groups of eight loads.  Here
+// every weight value loaded feeds RB fmas (as in linear64_kernel), U loads are issued per step and the next step's before this
+// step's fma chains.  Each output still has its one accumulator and takes its terms in ascending f, so the result does not depend
+// on RB or U; no dot product is split across threads.
+template <int W1, int RB>
 __global__ __launch_bounds__(256) void dyn_post64_kernel(const float *__restrict__ partial, int tiles_per_b,
                                                          const double *__restrict__ w1c /*[W1][256]*/,
                                                          const double *__restrict__ g2w /*[256][256]*/,
                                                          const double *__restrict__ g0w /*[256][L]*/,
                                                          const double *__restrict__ V /*[rows][256] relu(g0 x + b)*/,
-                                                         float *__restrict__ grad /*[rows][L]*/, int L) {
-    __shared__ double da[W1];
-    __shared__ double v1[256];
-    __shared__ double v2[256];
-    const int row = blockIdx.x, t = threadIdx.x;
-    for (int f = t; f < W1; f += 256) {
-        const float *src = partial + (size_t)row * tiles_per_b * W1 + f;
+                                                         float *__restrict__ grad /*[rows][L]*/, int rows, int L) {
+    __shared__ __attribute__((aligned(16))) double da[W1][RB];
+    __shared__ __attribute__((aligned(16))) double v1[256][RB];
+    __shared__ __attribute__((aligned(16))) double v2[256][RB];
+    const int r0 = blockIdx.x * RB, t = threadIdx.x;
+    // the fold over the cell tiles: twelve partials of a feature loaded before their adds (ct ascending, as a one-at-a-time loop adds
+    // them); rows past the end fold a copy of the last row and are dropped at the store
+    constexpr int CU = 12;
+    for (int i = t; i < RB * W1; i += 256) {
+        const int r = i / W1, f = i - r * W1;
+        const float *src = partial + (size_t)min(r0 + r, rows - 1) * tiles_per_b * W1 + f;
         double acc = 0.0;
-        for (int ct = 0; ct < tiles_per_b; ++ct) acc += (double)src[(size_t)ct * W1];
-        da[f] = acc;
+        for (int c0 = 0; c0 < tiles_per_b; c0 += CU) {
+            float pv[CU];
+#pragma unroll
+            for (int j = 0; j < CU; ++j) pv[j] = src[(size_t)min(c0 + j, tiles_per_b - 1) * W1];
+#pragma unroll
+            for (int j = 0; j < CU; ++j)
+                if (c0 + j < tiles_per_b) acc += (double)pv[j];
+        }
+        da[f][r] = acc;
     }
     __syncthreads();
-    // sum_f w[f][t] x[f] with eight weight loads in flight per step (F a multiple of 8)
-    auto dot = [&](const double *__restrict__ w, int ld, const double *x, int F) {
-        double acc = 0.0;
-        for (int f = 0; f < F; f += 8) {
-            double wv[8];
+    // acc[r] = sum_f w[f][t] x[f][r]  (F a multiple of 2 U)
+    constexpr int U = 16;
+    auto dot = [&](const double *__restrict__ w, int ld, const double (*x)[RB], int F, double (&acc)[RB]) {
+        double wa[U], wb[U];
 #pragma unroll
-            for (int j = 0; j < 8; ++j) wv[j] = w[(size_t)(f + j) * ld + t];
+        for (int r = 0; r < RB; ++r) acc[r] = 0.0;
 #pragma unroll
-            for (int j = 0; j < 8; ++j) acc = fma(wv[j], x[f + j], acc);
+        for (int j = 0; j < U; ++j) wa[j] = w[(size_t)j * ld + t];
+        for (int f = 0; f < F; f += 2 * U) {
+#pragma unroll
+            for (int j = 0; j < U; ++j) wb[j] = w[(size_t)(f + U + j) * ld + t];
+#pragma unroll
+            for (int j = 0; j < U; ++j)
+#pragma unroll
+                for (int r = 0; r < RB; ++r) acc[r] = fma(wa[j], x[f + j][r], acc[r]);
+            if (f + 2 * U < F) {
+#pragma unroll
+                for (int j = 0; j < U; ++j) wa[j] = w[(size_t)(f + 2 * U + j) * ld + t];
+            }
+#pragma unroll
+            for (int j = 0; j < U; ++j)
+#pragma unroll
+                for (int r = 0; r < RB; ++r) acc[r] = fma(wb[j], x[f + U + j][r], acc[r]);
         }
-        return acc;
     };
-    v1[t] = dot(w1c, 256, da, W1);
+    static_assert(W1 % (2 * U) == 0 && 256 % (2 * U) == 0, "dyn_post64_kernel: dot product lengths are multiples of 2 U");
+    double acc[RB];
+    dot(w1c, 256, da, W1, acc);
+#pragma unroll
+    for (int r = 0; r < RB; ++r) v1[t][r] = acc[r];
     __syncthreads();
-    const double a2 = dot(g2w, 256, v1, 256);
-    v2[t] = V[(size_t)row * 256 + t] > 0.0 ? a2 : 0.0;
+    dot(g2w, 256, v1, 256, acc);
+#pragma unroll
+    for (int r = 0; r < RB; ++r) v2[t][r] = V[(size_t)min(r0 + r, rows - 1) * 256 + t] > 0.0 ? acc[r] : 0.0;
     __syncthreads();
-    if (t < L) grad[(size_t)row * L + t] = (float)dot(g0w, L, v2, 256);
+    if (t < L) {
+        dot(g0w, L, v2, 256, acc);
+#pragma unroll
+        for (int r = 0; r < RB; ++r)
+            if (r0 + r < rows) grad[(size_t)(r0 + r) * L + t] = (float)acc[r];
+    }
 }
 
 int dyn_post64(int W1, const float *partial, int tiles_per_b, const double *w1c, const double *g2w, const double *g0w, const double *V64,
                float *grad, int rows, int L, hipStream_t s) {
     if (rows <= 0) return DGDM_OK;
     DGDM_REQUIRE(L <= 256, DGDM_EINVAL, "params_ch %d > 256 not supported", L);
+    constexpr int RB = 4;       // 1024 fingers (32 chains of 32): one workgroup per CU
+    const dim3 grid((rows + RB - 1) / RB);
     if (W1 == 256)
-        hipLaunchKernelGGL(dyn_post64_kernel<256>, dim3(rows), dim3(256), 0, s, partial, tiles_per_b, w1c, g2w, g0w, V64, grad, L);
+        hipLaunchKernelGGL((dyn_post64_kernel<256, RB>), grid, dim3(256), 0, s, partial, tiles_per_b, w1c, g2w, g0w, V64, grad, rows, L);
     else
-        hipLaunchKernelGGL(dyn_post64_kernel<512>, dim3(rows), dim3(256), 0, s, partial, tiles_per_b, w1c, g2w, g0w, V64, grad, L);
+        hipLaunchKernelGGL((dyn_post64_kernel<512, RB>), grid, dim3(256), 0, s, partial, tiles_per_b, w1c, g2w, g0w, V64, grad, rows, L);
     DGDM_HIP_CHECK(hipGetLastError());
     return DGDM_OK;
 }

@@ -320,19 +320,21 @@ class Guidance:
             self._h = None
 
     def set_objects(self, objects: torch.Tensor, wait: bool = False) -> None:
-        """2-D: (n, V, 2); 3-D: (n, N, 3).  The table build (3-D) is enqueued on the current stream and the handle's build streams and
-        the call returns: like every other call of the handle it is ordered by the stream - the coordinates are copied into the
-        handle's pool by a device copy on the current stream before anything else reads them (so `objects` is only needed by that
-        enqueued copy, the contract of any asynchronous call; torch's allocator keeps a freed block for work on the same stream), the
-        build streams start behind everything already enqueued on the current stream (chains still reading the previous tables
-        included), and whatever follows on the current stream waits for the build.  The host is then free to convert and sort the
-        next chains' FPS draws while the tables are being built (`dgdm_guided_chains_run` waits for the build's read-back only when
-        it needs it).  `wait=True` blocks until the tables exist."""
+        """2-D: (n, V, 2); 3-D: (n, N, 3).  The table build (3-D) is enqueued on the handle's build streams and the call returns: like
+        every other call of the handle it is ordered by the stream - the coordinates are copied into the handle's pool by a device
+        copy on the current stream before anything else reads them (so `objects` is only needed by that enqueued copy, the contract
+        of any asynchronous call; torch's allocator keeps a freed block for work on the same stream), the build streams start behind
+        everything already enqueued on the current stream (chains still reading the previous tables included), and every call of the
+        handle that reads the tables makes its stream wait for the build.  Other work that follows on the current stream does NOT
+        wait: the first step's eps-net and per-finger tables run beside the build.  The host is free to convert and sort the next
+        chains' FPS draws while the tables are being built (`dgdm_guided_chains_run` waits for the build's read-back only when it
+        needs it).  `wait=True` blocks until the tables exist (the build streams are not the current stream: it waits for the
+        device)."""
         o = _f32(objects)
         check(lib().dgdm_guidance_set_objects(self._h, dptr(o), o.shape[0], stream_ptr()))
         self._objects_ref = o                            # `o` may be a temporary: it is read by the copy still in flight
         if wait:
-            torch.cuda.current_stream().synchronize()
+            torch.cuda.synchronize()
         self.n_objects = o.shape[0]
 
     def debug_fps_path(self, mode):

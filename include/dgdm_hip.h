@@ -172,6 +172,14 @@ int dgdm_index_points(const float *points_dev, const int32_t *idx_dev, int B, in
 int dgdm_linear_act(const float *x_dev, int ldx, const float *wt_dev, const float *bias_dev, float *y_dev, int ldy, int rows, int K, int N,
                     int act, void *stream);
 int dgdm_group_max(const float *x_dev, int64_t groups, int nsample, int C, float *out_dev, void *stream);
+/* Test hooks: the float64 stages around the trunk on the caller's operands.  dgdm_debug_linear64: y = act(x wt + bias), all doubles,
+ * wt_dev [K][N].  dgdm_debug_dyn_post64: cond_fn's backward tail for `rows` fingers - partial_dev [rows][tiles_per_b][W1] float32 summed
+ * over the tiles, then through w1c_dev [W1][256], g2w_dev [256][256], the ReLU mask of V_dev [rows][256] and g0w_dev [256][L] ->
+ * grad_dev [rows][L] float32; every dot product one ascending chain of float64 fmas.                                                  */
+int dgdm_debug_linear64(const double *x_dev, int ldx, const double *wt_dev, const double *bias_dev, double *y_dev, int ldy, int rows, int K,
+                        int N, int act, void *stream);
+int dgdm_debug_dyn_post64(int W1, const float *partial_dev, int tiles_per_b, const double *w1c_dev, const double *g2w_dev,
+                          const double *g0w_dev, const double *V_dev, float *grad_dev, int rows, int L, void *stream);
 
 /* ------------------------------------------------------------------ a4-a6: guidance gradient
  * One DgdmGuidance serves up to max_chains independent chains (object x objective pairs) that
