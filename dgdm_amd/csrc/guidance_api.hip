@@ -993,7 +993,19 @@ extern "C" int dgdm_guided_chains_run_cond(DgdmUnet1d *unet, DgdmGuidance *g, co
                                            const DgdmObjective *objectives, const float *rowcoef_dev, const int64_t *starts_host,
                                            const int32_t *timesteps, const float *coef, const float *scales, int n_steps, float *x_out_dev,
                                            const float *global_cond_dev, int64_t cond_chain_stride, float cfg_weight, void *stream) {
+    return dgdm_guided_chains_run_bounded(unet, g, noise_dev, n_chains, n_grad, objectives, rowcoef_dev, starts_host, timesteps, coef, scales, n_steps, x_out_dev,
+                                          global_cond_dev, cond_chain_stride, cfg_weight, nullptr, nullptr, stream);
+}
+
+// The single body of the three entries.  lo_dev / hi_dev: per-entry clip of the predicted clean sample ([B][L], one block for all chains)
+// in place of [-1, 1]; both NULL: the plain step.
+extern "C" int dgdm_guided_chains_run_bounded(DgdmUnet1d *unet, DgdmGuidance *g, const float *noise_dev, int n_chains, int n_grad,
+                                              const DgdmObjective *objectives, const float *rowcoef_dev, const int64_t *starts_host,
+                                              const int32_t *timesteps, const float *coef, const float *scales, int n_steps, float *x_out_dev,
+                                              const float *global_cond_dev, int64_t cond_chain_stride, float cfg_weight, const float *lo_dev,
+                                              const float *hi_dev, void *stream) {
     DGDM_REQUIRE(unet && g && noise_dev && objectives && timesteps && coef && scales && x_out_dev, DGDM_EINVAL, "dgdm_guided_chains_run: null argument");
+    DGDM_REQUIRE(!lo_dev == !hi_dev, DGDM_EINVAL, "dgdm_guided_chains_run_bounded: lo and hi come together or not at all");
     DGDM_REQUIRE(n_chains > 0 && n_grad > 0 && n_chains * n_grad <= g->cfg.max_chains && n_steps > 0, DGDM_EINVAL,
                  "dgdm_guided_chains_run: %d chains x %d gradients outside 1..%d", n_chains, n_grad, g->cfg.max_chains);
     hipStream_t s = (hipStream_t)stream;
@@ -1111,12 +1123,18 @@ extern "C" int dgdm_guided_chains_run_cond(DgdmUnet1d *unet, DgdmGuidance *g, co
         if ((rc = guidance_grad(g, kind, xg, t, objectives, rowcoef_dev, nullptr, n_chains * n_grad, g->loopgrad.as<float>(), s,
                                 kind == 3 ? &emb : nullptr, si % cpe, hoist))) return rc;
         const float *cf = coef + 4 * si;
+        // the scheduler step over n entries from offset `off`; with bounds, their [B][L] block repeats for every chain
+        auto ddim = [&](size_t off, int ngr, int64_t n, float scale) -> int {
+            const float *e = g->loopeps.as<float>() + off, *gr = g->loopgrad.as<float>() + off;
+            if (lo_dev)
+                return dgdm_ddim_guided_step_bounded(x + off, e, gr, ngr, xn + off, n, cf[0], cf[1], cf[2], cf[3], scale, lo_dev, hi_dev, (int64_t)per_chain, s);
+            return dgdm_ddim_guided_step(x + off, e, gr, ngr, xn + off, n, cf[0], cf[1], cf[2], cf[3], scale, s);
+        };
         if (same_scale) {
-            if ((rc = dgdm_ddim_guided_step(x, g->loopeps.as<float>(), g->loopgrad.as<float>(), n_grad, xn, (int64_t)nx, cf[0], cf[1], cf[2], cf[3], scales[0], s))) return rc;
+            if ((rc = ddim(0, n_grad, (int64_t)nx, scales[0]))) return rc;
         } else {
             for (int c = 0; c < n_chains; ++c)
-                if ((rc = dgdm_ddim_guided_step(x + c * per_chain, g->loopeps.as<float>() + c * per_chain, g->loopgrad.as<float>() + c * per_chain, 1,
-                                                xn + c * per_chain, (int64_t)per_chain, cf[0], cf[1], cf[2], cf[3], scales[c], s))) return rc;
+                if ((rc = ddim(c * per_chain, 1, (int64_t)per_chain, scales[c]))) return rc;
         }
         return DGDM_OK;
     };

@@ -412,6 +412,30 @@ __global__ void ddim_step_kernel(const float *__restrict__ x, const float *__res
     out[i] = add_rn(mul_rn(sap, x0), mul_rn(sbp, e));
 }
 
+// The same step with the clip of the predicted clean sample per entry: [lo, hi] of entry i % period instead of clip_sample=True's
+// [-1, 1] (see dgdm_hip.h: editing a design).  Everything but the clamp's operands is ddim_step_kernel's sequence, so lo = -1, hi = 1
+// gives its bits; lo == hi pins x0, and with sap = 1, sbp = 0 (the last step) the output is that value exactly.
+__global__ void ddim_step_bounded_kernel(const float *__restrict__ x, const float *__restrict__ eps, const float *__restrict__ grad,
+                                         int n_grad, float *__restrict__ out, int64_t n, float sa, float sb, float sap, float sbp,
+                                         float scale, const float *__restrict__ lo, const float *__restrict__ hi, int64_t period) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const int64_t j = i % period;
+    float e = eps[i];
+    if (grad) {
+        float g = grad[i];
+        if (n_grad > 1) {
+            g = 0.f + g;
+            for (int k = 1; k < n_grad; ++k) g += grad[(size_t)k * n + i];
+            g = g / (float)n_grad;
+        }
+        e = sub_rn(e, mul_rn(mul_rn(sb, g), scale));
+    }
+    float x0 = __fdiv_rn(sub_rn(x[i], mul_rn(sb, e)), sa);
+    x0 = fminf(fmaxf(x0, lo[j]), hi[j]);
+    out[i] = add_rn(mul_rn(sap, x0), mul_rn(sbp, e));
+}
+
 __global__ void add_noise_kernel(const float *__restrict__ x0, const float *__restrict__ noise, float *__restrict__ out, int64_t n,
                                  float sa, float sb) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -429,6 +453,24 @@ extern "C" int dgdm_ddim_guided_step(const float *x_dev, const float *eps_dev, c
     hipLaunchKernelGGL(dgdm::ddim_step_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, x_dev, eps_dev,
                        grad_dev, n_grad, x_next_dev, n, sqrt_abar_t, sqrt_1m_abar_t, sqrt_abar_prev, sqrt_1m_abar_prev, guidance_scale);
     dgdm::prof_end((hipStream_t)stream, DGDM_STAGE_DDIM, (double)n * 4.0 * (3 + n_grad));
+    DGDM_HIP_CHECK(hipGetLastError());
+    return DGDM_OK;
+}
+
+extern "C" int dgdm_ddim_guided_step_bounded(const float *x_dev, const float *eps_dev, const float *grad_dev, int n_grad, float *x_next_dev,
+                                             int64_t n, float sqrt_abar_t, float sqrt_1m_abar_t, float sqrt_abar_prev,
+                                             float sqrt_1m_abar_prev, float guidance_scale, const float *lo_dev, const float *hi_dev,
+                                             int64_t period, void *stream) {
+    DGDM_REQUIRE(x_dev && eps_dev && x_next_dev && n >= 0, DGDM_EINVAL, "dgdm_ddim_guided_step_bounded: null argument");
+    DGDM_REQUIRE(lo_dev && hi_dev, DGDM_EINVAL, "dgdm_ddim_guided_step_bounded: needs both lo and hi");
+    DGDM_REQUIRE(period > 0 && n % period == 0, DGDM_EINVAL, "dgdm_ddim_guided_step_bounded: period %lld does not divide n = %lld", (long long)period,
+                 (long long)n);
+    if (n == 0) return DGDM_OK;
+    dgdm::prof_begin((hipStream_t)stream, DGDM_STAGE_DDIM);
+    hipLaunchKernelGGL(dgdm::ddim_step_bounded_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, x_dev, eps_dev,
+                       grad_dev, n_grad, x_next_dev, n, sqrt_abar_t, sqrt_1m_abar_t, sqrt_abar_prev, sqrt_1m_abar_prev, guidance_scale, lo_dev,
+                       hi_dev, period);
+    dgdm::prof_end((hipStream_t)stream, DGDM_STAGE_DDIM, (double)n * 4.0 * (5 + n_grad));
     DGDM_HIP_CHECK(hipGetLastError());
     return DGDM_OK;
 }

@@ -162,7 +162,7 @@ class GuidanceSpec:
 def guided_chains_sharded(unet, spec: GuidanceSpec, sched, mode: str, noise: torch.Tensor, objects: torch.Tensor,
                           chains: Sequence[Tuple[int, str]], unguided: Optional[torch.Tensor] = None, starts=None,
                           streams=None, group=None, build: Optional[Callable] = None, global_cond: Optional[torch.Tensor] = None,
-                          cfg_weight: float = 1.0) -> torch.Tensor:
+                          cfg_weight: float = 1.0, edit=None) -> torch.Tensor:
     """``sampler.guided_chains`` for the (object x objective) pairs `chains` over the object bank `objects`, block-partitioned
     over the ranks of `group`; returns all chains' samples [n_chains, B, L, 1] in the original order on every rank.
 
@@ -170,18 +170,21 @@ def guided_chains_sharded(unet, spec: GuidanceSpec, sched, mode: str, noise: tor
     runs its chains; nothing is communicated inside the denoise loop and the final samples are all-gathered once (SURVEY.md
     §8(e)).  3-D: the FPS start draws are rank-count-invariant - every rank walks the reference's single generator stream over
     ALL chains (host only: `starts` or the global CPU generator) and keeps its own block, unless per-chain `streams` are given.
-    global_cond (B, gc), shared by all chains, and cfg_weight: as in ``sampler.guided_chains``."""
+    global_cond (B, gc), shared by all chains, and cfg_weight: as in ``sampler.guided_chains``.  edit (dgdm_amd/edit.py) is forwarded:
+    its designs, bounds and start sample are the same on every rank, and the draws are made for its steps."""
     from . import sampler
     world, rank = world_rank(group)
     mine, local_objects, local_chains = shard_chains(chains, rank, world)
     B, L, _ = noise.shape
-    S = len(sched.timesteps)
+    S = len(sched.timesteps) if edit is None else edit.n_steps(sched)
     predrawn = None
     if mode == 'point_3d':
         predrawn = sampler.draw_chain_starts(spec, chains, S, starts, keep=mine, streams=streams)
     if len(local_chains):
         guid = (build or spec.build)(objects[local_objects].to(noise.device), len(local_chains))
         cond_kw = {} if global_cond is None else {"global_cond": global_cond, "cfg_weight": cfg_weight}      # an unconditional call is what it was
+        if edit is not None:
+            cond_kw["edit"] = edit
         local = sampler.guided_chains(unet, guid, sched, mode, noise, local_chains, unguided=unguided, predrawn=predrawn, **cond_kw)
     else:
         local = torch.zeros((0, B, L, 1), dtype=torch.float32, device=noise.device)
@@ -195,12 +198,13 @@ def gather_rows(local: torch.Tensor, n_items: int, group=None) -> torch.Tensor:
 
 def guided_multi_object_sharded(unet, spec: GuidanceSpec, sched, mode: str, noise: torch.Tensor, objects: torch.Tensor, opt_obj: str,
                                 starts=None, group=None, build: Optional[Callable] = None, on_step=None, global_cond: Optional[torch.Tensor] = None,
-                                cfg_weight: float = 1.0) -> torch.Tensor:
+                                cfg_weight: float = 1.0, edit=None) -> torch.Tensor:
     """``sampler.guided_multi_object`` (generator/diffusion.py:637-647: ONE chain whose step uses the mean of n_obj cond_fn
     gradients) with the objects block-partitioned over the ranks.  Unlike the per-object chains this loop has a real exchange
     step: every denoise step the ranks all-gather their objects' gradients [n_obj, B, L] (a few KB over RCCL) and then all take
     the same scheduler step on the full stack, in object order - so every rank holds the single-process result bit for bit.
-    3-D: per step the reference draws the FPS starts object after object (:641-643); every rank walks that stream and keeps its objects'."""
+    3-D: per step the reference draws the FPS starts object after object (:641-643); every rank walks that stream and keeps its objects'.
+    edit (dgdm_amd/edit.py): the start sample, the steps and their bounds are the edit's, the same on every rank."""
     from . import engine, sampler
     world, rank = world_rank(group)
     n_obj, (B, L, _) = objects.shape[0], noise.shape
@@ -216,8 +220,9 @@ def guided_multi_object_sharded(unet, spec: GuidanceSpec, sched, mode: str, nois
         if field is not None:
             guid.set_row_field(field)
         scale = sampler.chain_scale(mode, opt_obj, multi=True)
+        noise, timesteps, bounds = sampler._edit_start(edit, sched, noise)
         x = noise.reshape(B, L).contiguous().to(torch.float32)
-        for i, t in enumerate(sched.timesteps):
+        for i, t in enumerate(timesteps):
             t = int(t)
             eps = unet.forward_cfg(x.reshape(B, L, 1), torch.full((B,), t, dtype=torch.int32, device=x.device), global_cond, cfg_weight).reshape(B, L)
             st = None
@@ -229,7 +234,7 @@ def guided_multi_object_sharded(unet, spec: GuidanceSpec, sched, mode: str, nois
             else:
                 g = torch.zeros((0, B, L), dtype=torch.float32, device=x.device)
             g = gather_rows(g, n_obj, group)
-            x = engine.ddim_guided_step(x, eps, g, n_obj, sched.coefficients(t), scale)
+            x = sampler._ddim_step(x, eps, g, n_obj, sched.coefficients(t), scale, bounds)
             if on_step is not None:
                 on_step(i, x.reshape(B, L, 1))
     return x.reshape(B, L, 1)

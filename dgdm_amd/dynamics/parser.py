@@ -61,6 +61,13 @@ _FLAGS = [
                                "net on the all-zero condition row (1: the plain conditional eps, 0: the unconditional one)"),
     ("cond_drop_prob", float, 0.0, "with --global_cond, --mode=train: probability with which a training sample sees the all-zero condition row instead of "
                                    "its own (what classifier-free guidance needs the net to have learnt)"),
+    ("edit_from", str, None, "generator, --mode=test: FILE.npy of designs (n, L) or (n, L, 1) in sampler units, n >= batch_size (e.g. a vis_guided/<tag>/<obj>.npy "
+                             "of an earlier run); batch b edits rows [b B, (b + 1) B): the guided chains of the sweep start from these designs instead of "
+                             "from noise and are written under vis_edit/ (dgdm_amd/edit.py)"),
+    ("edit_steps", int, None, "with --edit_from: how many of the schedule's last steps an edit runs, 1..num_inference_steps (default: all)"),
+    ("pin", str, None, "with --edit_from: control points held at the design's value, indices and inclusive ranges like 0-6,10 (the first half of the "
+                       "indices is the left finger)"),
+    ("edit_band_mm", float, None, "with --edit_from: no control point moves further than this many millimetres from the design"),
     ("device_dataset", "flag", None, "dynamics training: read every data file once, keep the dataset on the GPU and build each batch's rows there "
                                      "(dynamics/device_dataset.py); same batches, draws and results as the host loop"),
 ]

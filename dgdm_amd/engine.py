@@ -492,12 +492,37 @@ def ddim_guided_step(x: torch.Tensor, eps: torch.Tensor, grad: Optional[torch.Te
     return out
 
 
+def _bounds_block(bounds, numel: int, device) -> Tuple[torch.Tensor, torch.Tensor, int]:
+    """(lo, hi) of an edit as contiguous float32 device tensors and their period; ValueError unless both have the same size and it divides numel."""
+    if not isinstance(bounds, (tuple, list)) or len(bounds) != 2 or bounds[0] is None or bounds[1] is None:
+        raise ValueError("bounds are a (lo, hi) pair of tensors")
+    lo, hi = _f32(bounds[0]).to(device), _f32(bounds[1]).to(device)
+    if lo.numel() != hi.numel() or lo.numel() == 0 or numel % lo.numel():
+        raise ValueError(f"bounds of {lo.numel()} and {hi.numel()} entries do not tile the {numel} entries of the step")
+    return lo, hi, lo.numel()
+
+
+def ddim_guided_step_bounded(x: torch.Tensor, eps: torch.Tensor, grad: Optional[torch.Tensor], n_grad: int, coef: Tuple[float, float, float, float],
+                             scale: float, bounds) -> torch.Tensor:
+    """ddim_guided_step with the predicted clean sample clipped to bounds = (lo, hi) per entry instead of [-1, 1]
+    (dgdm_ddim_guided_step_bounded): lo / hi hold one block that repeats over x (e.g. (B, L) for x (n_chains, B, L))."""
+    x, eps = _f32(x), _f32(eps)
+    lo, hi, period = _bounds_block(bounds, x.numel(), x.device)
+    out = torch.empty_like(x)
+    g = _f32(grad) if grad is not None else None
+    check(lib().dgdm_ddim_guided_step_bounded(dptr(x), dptr(eps), dptr(g), n_grad, dptr(out), x.numel(), *[float(c) for c in coef], float(scale),
+                                              dptr(lo), dptr(hi), period, stream_ptr()))
+    return out
+
+
 def guided_chains_run(unet: "Unet1d", guid: "Guidance", noise: torch.Tensor, n_chains: int, n_grad: int, objectives: Sequence[_lib.Objective],
                       rowcoef: Optional[torch.Tensor], starts: Optional[np.ndarray], timesteps: Sequence[int],
                       coefs: Sequence[Tuple[float, float, float, float]], scales: Sequence[float], global_cond: Optional[torch.Tensor] = None,
-                      cfg_weight: float = 1.0) -> torch.Tensor:
-    """The whole guided denoise loop in one library call (dgdm_guided_chains_run_cond): noise (B, L) -> (n_chains, B, L).
-    global_cond: (B, gc) shared by all chains or (n_chains, B, gc); cfg_weight: classifier-free guidance weight (1: the plain conditional run)."""
+                      cfg_weight: float = 1.0, bounds=None) -> torch.Tensor:
+    """The whole guided denoise loop in one library call (dgdm_guided_chains_run_bounded): noise (B, L) -> (n_chains, B, L).
+    global_cond: (B, gc) shared by all chains or (n_chains, B, gc); cfg_weight: classifier-free guidance weight (1: the plain conditional run).
+    bounds: None, or an edit's (lo, hi), each (B, L), shared by all chains - every step then clips its predicted clean sample to them;
+    `noise` is then the edit's start sample and timesteps / coefs the schedule's last steps (dgdm_amd/edit.py)."""
     cond, cond_stride = chain_cond_layout(global_cond, unet.global_cond_dim, n_chains, noise.shape[0])
     x0 = _f32(noise).reshape(noise.shape[0], -1)
     B, L = x0.shape
@@ -514,9 +539,15 @@ def guided_chains_run(unet: "Unet1d", guid: "Guidance", noise: torch.Tensor, n_c
         assert starts is not None and starts.dtype == np.int64 and starts.size == S * n_chains * n_grad * guid.starts_per_call
         starts = np.ascontiguousarray(starts)
         sp = starts.ctypes.data
+    lo = hi = None
+    if bounds is not None:
+        lo, hi, period = _bounds_block(bounds, B * L, x0.device)
+        if period != B * L:
+            raise ValueError(f"bounds of {period} entries: the chains take one (B, L) = ({B}, {L}) block")
     out = torch.empty((n_chains, B, L), dtype=torch.float32, device=x0.device)
-    check(lib().dgdm_guided_chains_run_cond(unet._h, guid._h, dptr(x0), n_chains, n_grad, arr, dptr(rowcoef) if rowcoef is not None else None, sp,
-                                            ts, cf, sc, S, dptr(out), dptr(cond), int(cond_stride), float(cfg_weight), stream_ptr()))
+    check(lib().dgdm_guided_chains_run_bounded(unet._h, guid._h, dptr(x0), n_chains, n_grad, arr, dptr(rowcoef) if rowcoef is not None else None, sp,
+                                               ts, cf, sc, S, dptr(out), dptr(cond), int(cond_stride), float(cfg_weight), dptr(lo), dptr(hi),
+                                               stream_ptr()))
     return out         # `starts` has been consumed: every step converts it into the handle's pinned staging buffer before it returns
 
 

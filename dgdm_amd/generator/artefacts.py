@@ -6,6 +6,8 @@ samples themselves (generator/diffusion.py:203-231, 258-336, 592-619, 648-709). 
     val_vis/<epoch>_<step>.png                       denoise-from-data loop, sample 0           (:203-231)
     val_vis_noise/<epoch>_<gripper>_<step>.png       unguided chain, every gripper              (:258-292)
     vis_guided/<tag>/allobj_<gripper>_<step>.png     multi-object guided chain, every gripper   (:648-674)
+  (with --edit_from the guided chains edit existing designs, dgdm_amd/edit.py: their files go to vis_edit/<tag>/ instead, the source
+  designs to vis_edit/edit_source/, and their tables are "val/edit_sample/..." with EDIT_COLUMNS - not the reference's)
 * the tables the reference sends to ``self.logger.log_table`` (wandb).  Without wandb they are written as JSON,
   ``tables/<key with '/' -> '__'>.json`` = {"key", "columns", "data"}; images are referenced by file path, placeholder
   images (the reference's 128x128 white ``wandb.Image``) by null.
@@ -154,11 +156,41 @@ def unguided_table(model, log: TableLog, sim_out, imgs: Sequence[str], num_objec
     return {"average": average, "average_best": average_best, "best_average_gripper": best_avg}
 
 
-def guided_table(model, log: TableLog, per_object_sim: Sequence[Any], opt_obj: str, ori_range: Sequence[float]) -> Optional[Dict[str, float]]:
-    """The "val/guided_sample/<opt_obj>_orirange=..." table (:577-619): per object the best gripper for every score."""
+EDIT_COLUMNS = ["edit_moved_mm_max", "edit_moved_mm_rms", "edit_pins"]
+EDIT_SOURCE = "edit_source"       # the tag under which the designs an edit started from are emitted and scored
+
+
+def edit_stats(edit, samples) -> Dict[str, Any]:
+    """What the tables say about the chains of an ``edit.Edit`` besides their scores: how far every gripper of `samples` (..., B, L, 1)
+    moved from its source design, in millimetres of finger geometry (max and rms over the control values), and how many points are pinned."""
+    mx, rms = edit.moved_mm(samples)
+    return {"max": mx, "rms": rms, "pins": len(edit.pins)}
+
+
+def _source_objectives(source_sim, opt_obj: str, num_objects: int) -> List[Optional[Dict[str, Any]]]:
+    """Per object the scores of the source designs, averaged over the grippers, from one simulator call on all objects (object-major)."""
+    if source_sim is None:
+        return [None] * num_objects
+    metrics = source_sim[1]
+    per = len(metrics) // max(num_objects, 1)
+    out: List[Optional[Dict[str, Any]]] = []
+    for i in range(num_objects):
+        block = metrics[i * per:(i + 1) * per]
+        objs = [metric2objective(m, opt_obj) for m in block]
+        out.append(_flag({k: float(np.mean([o[k] for o in objs])) for k in objs[0].keys()}, block) if objs else None)
+    return out
+
+
+def guided_table(model, log: TableLog, per_object_sim: Sequence[Any], opt_obj: str, ori_range: Sequence[float],
+                 edit: Optional[Dict[str, Any]] = None) -> Optional[Dict[str, float]]:
+    """The "val/guided_sample/<opt_obj>_orirange=..." table (:577-619): per object the best gripper for every score.
+    edit (chains that edited designs): ``edit_stats`` of the (objects, B, L, 1) samples, plus 'source': the simulator's output for the
+    source designs on all objects or None.  The table is then "val/edit_sample/...", its rows carry EDIT_COLUMNS (how far the row's
+    gripper moved from its design; pinned points), and per object one more row, gripper "edit_source", holds the scores of the source
+    designs averaged over the grippers: before and after in the same table."""
     fam = profile_family(opt_obj)
-    all_imgs, all_obj, all_prof, all_fin, all_vid, all_dirs = [], [], [], [], [], []
-    for sim_out in per_object_sim:
+    all_imgs, all_obj, all_prof, all_fin, all_vid, all_dirs, all_best, kept = [], [], [], [], [], [], [], []
+    for oi, sim_out in enumerate(per_object_sim):
         gripper_imgs, metrics, profiles, profiles_x, profiles_y, finals, videos, dirs = sim_out
         if len(metrics) == 0:
             continue
@@ -168,33 +200,61 @@ def guided_table(model, log: TableLog, per_object_sim: Sequence[Any], opt_obj: s
         pick = lambda seq: {k: seq[best[k]] for k in best}                                                   # noqa: E731
         all_obj.append(pick([_flag(o, [m]) for o, m in zip(objs, metrics)])); all_imgs.append(pick(gripper_imgs)); all_prof.append(pick(prof))
         all_fin.append(pick(finals)); all_vid.append(pick(videos)); all_dirs.append(pick(dirs))
+        all_best.append(best); kept.append(oi)
     if not all_obj:
         return None
     average_best = {k: float(np.mean([o[k][k] for o in all_obj])) for k in all_obj[0].keys()}
     rows = [[-1, None, average_best, None, None, [None], ""]]
     rows += [[i, all_imgs[i][k], all_obj[i][k], all_prof[i][k], all_fin[i][k], list(all_vid[i][k]), all_dirs[i][k]]
              for i in range(len(all_obj)) for k in all_obj[i].keys()]
-    log.log_table("val/guided_sample/%s_orirange=%.3f_%.3f" % (opt_obj, ori_range[0], ori_range[1]),
-                  ["object_idx", "gripper", "objective", "profile", "final", "last_img", "gripper_dir"], rows)
+    columns = ["object_idx", "gripper", "objective", "profile", "final", "last_img", "gripper_dir"]
+    if edit is None:
+        log.log_table("val/guided_sample/%s_orirange=%.3f_%.3f" % (opt_obj, ori_range[0], ori_range[1]), columns, rows)
+        return average_best
+    pins = int(edit["pins"])
+    rows[0] += [float(np.max(edit["max"])), float(np.sqrt(np.mean(np.square(edit["rms"])))), pins]
+    r = 1
+    for i in range(len(all_obj)):
+        for k in all_obj[i].keys():
+            b = int(all_best[i][k])
+            rows[r] += [float(edit["max"][kept[i]][b]), float(edit["rms"][kept[i]][b]), pins]
+            r += 1
+    source = _source_objectives(edit.get("source"), opt_obj, len(per_object_sim))
+    rows += [[i, EDIT_SOURCE, source[kept[i]], None, None, [None], "", 0.0, 0.0, pins] for i in range(len(all_obj)) if source[kept[i]] is not None]
+    log.log_table("val/edit_sample/%s_orirange=%.3f_%.3f" % (opt_obj, ori_range[0], ori_range[1]), columns + EDIT_COLUMNS, rows)
     return average_best
 
 
 def multi_object_table(model, log: TableLog, per_gripper_sim: Sequence[Any], num_objects: int, opt_obj: str,
-                       ori_range: Sequence[float]) -> Optional[Dict[str, Any]]:
+                       ori_range: Sequence[float], edit: Optional[Dict[str, Any]] = None) -> Optional[Dict[str, Any]]:
     """The "val/guided_sample/allobj_<opt_obj>_orirange=..." table (:675-709): every gripper simulated on all objects,
-    scores averaged over the objects, best gripper per score."""
-    all_obj, all_dirs, all_imgs, all_vid = [], [], [], []
-    for sim_out in per_gripper_sim:
+    scores averaged over the objects, best gripper per score.  edit: as in guided_table, for the (B, L, 1) samples of the one chain:
+    the table is "val/edit_sample/allobj_...", with EDIT_COLUMNS and one "edit_source" row (the source designs' scores averaged over
+    objects and grippers)."""
+    all_obj, all_dirs, all_imgs, all_vid, kept = [], [], [], [], []
+    for gi, sim_out in enumerate(per_gripper_sim):
         gripper_imgs, metrics, _, _, _, _, videos, dirs = sim_out
         if len(metrics) != num_objects:
             continue
         objs = [metric2objective(m, opt_obj) for m in metrics]
         all_obj.append(_flag({k: float(np.mean([o[k] for o in objs])) for k in objs[0].keys()}, metrics))
         all_dirs.append(dirs[0]); all_imgs.append(gripper_imgs[0]); all_vid.append(sum((list(v) for v in videos), []))
+        kept.append(gi)
     if not all_obj:
         return None
     best = model.get_best_ids_all_metrics(all_obj, opt_obj=opt_obj)
     rows = [[all_imgs[best[k]], all_obj[best[k]], all_vid[best[k]], all_dirs[best[k]]] for k in best]
-    log.log_table("val/guided_sample/allobj_%s_orirange=%.3f_%.3f" % (opt_obj, ori_range[0], ori_range[1]),
-                  ["gripper", "objective", "last_img", "gripper_dir"], rows)
+    columns = ["gripper", "objective", "last_img", "gripper_dir"]
+    if edit is None:
+        log.log_table("val/guided_sample/allobj_%s_orirange=%.3f_%.3f" % (opt_obj, ori_range[0], ori_range[1]), columns, rows)
+        return {k: all_obj[best[k]] for k in best}
+    pins = int(edit["pins"])
+    for row, k in zip(rows, best):
+        b = kept[int(best[k])]
+        row += [float(edit["max"][b]), float(edit["rms"][b]), pins]
+    source = [s for s in _source_objectives(edit.get("source"), opt_obj, num_objects) if s is not None]
+    if source:
+        mean = {k: (float(np.mean([s[k] for s in source])) if k != 'predicted' else True) for k in source[0].keys()}
+        rows.append([EDIT_SOURCE, mean, [], "", 0.0, 0.0, pins])
+    log.log_table("val/edit_sample/allobj_%s_orirange=%.3f_%.3f" % (opt_obj, ori_range[0], ori_range[1]), columns + EDIT_COLUMNS, rows)
     return {k: all_obj[best[k]] for k in best}

@@ -137,6 +137,10 @@ class Diffusion(nn.Module):
         # a training sample's condition row is replaced by the all-zero (null) row
         self.cfg_weight = 1.0
         self.cond_drop_prob = 0.0
+        # nor this: an edit.EditPlan (--edit_from, --pin, --edit_band_mm, --edit_steps).  The guided chains of the validation sweep then
+        # edit the plan's designs instead of starting from noise and are emitted under vis_edit/ (the unguided loops are untouched)
+        self.edit_plan = None
+        self._edit_source_sim = None
         if class_cond:
             self.classifier_model = classifier_model
             self.grid_size, self.num_pos = grid_size, num_pos
@@ -441,10 +445,22 @@ class Diffusion(nn.Module):
                                   self.noise_scheduler.config.num_train_timesteps, npts,
                                   self.sub_batch_size if self.mode == 'point_3d' else 0, self.contraction_dtype)
 
+    def _edit(self, batch_idx, batch_size):
+        """The edit.Edit of this batch (rows [b B, (b + 1) B) of --edit_from), or None when the run edits nothing."""
+        plan = getattr(self, "edit_plan", None)
+        return None if plan is None else plan.batch(int(batch_idx), int(batch_size))
+
+    def _edit_table(self, edit, out):
+        """The `edit` argument of artefacts.guided_table / multi_object_table for the samples `out` of the edit's chains."""
+        return dict(artefacts.edit_stats(edit, out), source=self._edit_source_sim)
+
     def guided_sample(self, batch_idx, batch_size, noise, save_dir, opt_obj='rotate', ori_range=[-1.0, 1.0], unguided_sample=None,
                       global_cond=None):
         """All objects' chains of generator/diffusion.py:561-576 as one batch.  Returns (n_objects, B, L, 1).  global_cond (B, gc): the
         condition rows of a conditional eps-net, shared by all chains (mixed with self.cfg_weight).
+
+        With an edit plan (--edit_from) the chains edit this batch's designs (dgdm_amd/edit.py): they are written under vis_edit/<tag>/
+        instead of vis_guided/<tag>/, and their table is val/edit_sample/... with the edit_* columns (artefacts.guided_table).
 
         Under a process group (torchrun, one rank per GPU) the objects' chains are block-partitioned over the ranks and the
         final samples all-gathered (dgdm_amd/dist.py) - this is what stands in for the reference's nn.DataParallel
@@ -453,24 +469,28 @@ class Diffusion(nn.Module):
         n = objs.shape[0]
         chains = [(i, opt_obj) for i in range(n)]
         ug = None if unguided_sample is None else unguided_sample.to(self.device)
+        edit = self._edit(batch_idx, batch_size)
+        edit_kw = {} if edit is None else {"edit": edit}                 # a run without --edit_from makes the calls it made
         if ddist.world_rank()[0] > 1:
             out = ddist.guided_chains_sharded(self._net(), self._spec(batch_size, ori_range, objs.shape[1]), self.noise_scheduler, self.mode,
                                               noise.to(self.device), objs, chains, unguided=ug,
                                               build=lambda o, k: self._guidance_for(batch_size, ori_range, o.detach().cpu(), k),
-                                              global_cond=global_cond, cfg_weight=self.cfg_weight)
+                                              global_cond=global_cond, cfg_weight=self.cfg_weight, **edit_kw)
         else:
             g = self._guidance_for(batch_size, ori_range, objs, n)
             out = sampler.guided_chains(self._net(), g, self.noise_scheduler, self.mode, noise.to(self.device), chains, unguided=ug,
-                                        global_cond=global_cond, cfg_weight=self.cfg_weight)
+                                        global_cond=global_cond, cfg_weight=self.cfg_weight, **edit_kw)
         if ddist.world_rank()[1] == 0:
             tag = f"{opt_obj}_orirange={ori_range[0]:.3f}_{ori_range[1]:.3f}"
+            sub = 'vis_guided' if edit is None else 'vis_edit'
             ids = [self.object_ids[i] if self.object_ids is not None else i for i in range(n)]
-            self._emit(save_dir, 'vis_guided', tag, out, [str(i) for i in ids])
+            self._emit(save_dir, sub, tag, out, [str(i) for i in ids])
             if self.simulator is not None and save_dir:                  # :577-619
                 arr = out.detach().cpu().numpy()
-                sims = [self.simulator(arr[i], [ids[i]], os.path.join(save_dir, 'vis_guided', tag, str(ids[i])), render=self.render_video,
+                sims = [self.simulator(arr[i], [ids[i]], os.path.join(save_dir, sub, tag, str(ids[i])), render=self.render_video,
                                        num_cpus=self.num_cpus, num_rot=int((ori_range[1] - ori_range[0]) * 180), ori_range=ori_range) for i in range(n)]
-                artefacts.guided_table(self, self._tables(save_dir), sims, opt_obj, ori_range)
+                table_kw = {} if edit is None else {"edit": self._edit_table(edit, arr)}
+                artefacts.guided_table(self, self._tables(save_dir), sims, opt_obj, ori_range, **table_kw)
         return out
 
     # ------------------------------------------------------------------ a2
@@ -478,31 +498,35 @@ class Diffusion(nn.Module):
         objs = torch.as_tensor(self.object_vertices)
         tag = f"{opt_obj}_orirange={ori_range[0]:.3f}_{ori_range[1]:.3f}"
         rank0 = ddist.world_rank()[1] == 0
+        edit = self._edit(batch_idx, batch_size)          # --edit_from: the chain edits this batch's designs (see guided_sample)
+        edit_kw = {} if edit is None else {"edit": edit}
+        sub = 'vis_guided' if edit is None else 'vis_edit'
         on_step = None
         if save_dir and self.render_plots and rank0:                     # per-step, per-gripper PNGs (:648-674)
             def on_step(i, x):
                 for gi, row in enumerate(x.detach().cpu().numpy()):
-                    artefacts.plot_fingers(os.path.join(save_dir, 'vis_guided', tag, 'allobj_%d_%d.png' % (batch_idx * batch_size + gi, i)),
+                    artefacts.plot_fingers(os.path.join(save_dir, sub, tag, 'allobj_%d_%d.png' % (batch_idx * batch_size + gi, i)),
                                            row[:, 0], self.mode, self.pts_x_dim, self.pts_z_dim, stacked=False)
         if ddist.world_rank()[0] > 1:       # objects over ranks, gradients all-gathered every step (dist.guided_multi_object_sharded)
             out = ddist.guided_multi_object_sharded(self._net(), self._spec(batch_size, ori_range, objs.shape[1]), self.noise_scheduler, self.mode,
                                                     noise.to(self.device), objs, opt_obj,
                                                     build=lambda o, k: self._guidance_for(batch_size, ori_range, o.detach().cpu(), k), on_step=on_step,
-                                                    global_cond=global_cond, cfg_weight=self.cfg_weight)
+                                                    global_cond=global_cond, cfg_weight=self.cfg_weight, **edit_kw)
         else:
             g = self._guidance_for(batch_size, ori_range, objs, objs.shape[0])
             out = sampler.guided_multi_object(self._net(), g, self.noise_scheduler, self.mode, noise.to(self.device),
                                               list(range(objs.shape[0])), opt_obj, on_step=on_step, global_cond=global_cond,
-                                              cfg_weight=self.cfg_weight)
+                                              cfg_weight=self.cfg_weight, **edit_kw)
         if rank0:
-            self._emit(save_dir, 'vis_guided', tag, out[None], ["allobj"])
+            self._emit(save_dir, sub, tag, out[None], ["allobj"])
             if self.simulator is not None and save_dir:                  # :675-709: every gripper on all objects
                 arr = out.detach().cpu().numpy()
                 ids = list(self.object_ids) if self.object_ids is not None else list(range(objs.shape[0]))
-                sims = [self.simulator(arr[i:i + 1], ids, os.path.join(save_dir, 'vis_guided', tag, 'allobj_%d' % i), render=self.render_video,
+                sims = [self.simulator(arr[i:i + 1], ids, os.path.join(save_dir, sub, tag, 'allobj_%d' % i), render=self.render_video,
                                        num_cpus=self.num_cpus, num_rot=int((ori_range[1] - ori_range[0]) * 180), ori_range=ori_range)
                         for i in range(arr.shape[0])]
-                artefacts.multi_object_table(self, self._tables(save_dir), sims, len(ids), opt_obj, ori_range)
+                table_kw = {} if edit is None else {"edit": self._edit_table(edit, arr)}
+                artefacts.multi_object_table(self, self._tables(save_dir), sims, len(ids), opt_obj, ori_range, **table_kw)
         return out
 
     def _object_ids(self) -> list:
@@ -596,20 +620,32 @@ class Diffusion(nn.Module):
                 else:
                     tables.skipped("no simulator callable was given to Diffusion(simulator=...): the objective tables of "
                                    "generator/diffusion.py:304-336, 592-619, 697-709 need simulator roll-outs (dynamics/sim_test_mj*.py)")
-            with self._draw_ahead(B):
+            edit = self._edit(batch_idx, B)
+            self._edit_source_sim = None
+            if edit is not None and rank0:
+                # the designs the sweep's chains edit, emitted and - with a simulator - scored ONCE, on every object, under the tag
+                # 'edit_source': every edit table shows them beside the edited grippers
+                src = edit.designs_on(dev)
+                self._emit(self.save_dir, 'vis_edit', artefacts.EDIT_SOURCE, src[None], [artefacts.EDIT_SOURCE])
+                if self.simulator is not None and self.save_dir:
+                    self._edit_source_sim = self.simulator(src.cpu().numpy(), self._object_ids(), os.path.join(self.save_dir, 'vis_edit', artefacts.EDIT_SOURCE),
+                                                           render=self.render_video, num_cpus=self.num_cpus)
+            with self._draw_ahead(B, edit):
                 self._objective_sweep(out, batch_idx, B, noise, unguided, sim_unguided, tables, imgs, cond)
         return out
 
-    def _draw_ahead(self, B: int):
+    def _draw_ahead(self, B: int, edit=None):
         """The FPS start draws of the whole objective sweep, made ahead of the launches on a worker thread (sampler.StartPlan): they
         depend on nothing the GPU computes, only on the order in which the loops below consume the generator - per objective the
         multi-object chain (per step object after object, :641-643), then the per-object chains (centre sweep, then the steps, :561-576);
-        under a process group every rank walks the whole stream and skips what belongs to other ranks (dgdm_amd/dist.py)."""
+        under a process group every rank walks the whole stream and skips what belongs to other ranks (dgdm_amd/dist.py).  The chains of
+        an `edit` run its K steps, not the schedule's S."""
         import contextlib
         if self.mode != 'point_3d' or self.object_vertices is None:
             return contextlib.nullcontext()
         objs = torch.as_tensor(self.object_vertices)
-        n, N, S = objs.shape[0], objs.shape[1], len(self.noise_scheduler.timesteps)
+        n, N = objs.shape[0], objs.shape[1]
+        S = len(self.noise_scheduler.timesteps) if edit is None else edit.n_steps(self.noise_scheduler)
         rows, sweep_rows = B * self.grid_size * self.num_pos ** 2, B * self.grid_size
         world, rank = ddist.world_rank()
         plots = bool(self.save_dir) and self.render_plots and rank == 0

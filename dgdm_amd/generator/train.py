@@ -9,6 +9,9 @@ fingers, which is what Lightning's ``trainer.validate`` does (:152-156).  ``--mo
 ``validation_step`` on the held-out 10 % every ``--val_step`` epochs, a Lightning-shaped checkpoint per epoch (the last ten and
 ``last.ckpt``, as the ModelCheckpoint of :137-146 keeps them).
 
+Not the reference's: ``--edit_from FILE.npy`` (with ``--pin``, ``--edit_band_mm``, ``--edit_steps``; dgdm_amd/edit.py) makes the guided
+chains of the test-mode sweep edit the file's designs - batch b its rows [b B, (b + 1) B) - instead of starting from noise.
+
 Assets the image does not have are substituted, loudly:
 * no checkpoint files  -> deterministic random-init weights (dgdm_amd.synth).
 Objects come from ``--object_dir``: ``objects.npy`` ([n, vertices, 2|3], metres) when present; otherwise, as in the reference,
@@ -284,6 +287,10 @@ def train(args):
     pts = finger_control_points(args.num_fingers, args.fingers_3d)
     max_y, min_y = (0.0, -0.1) if args.fingers_3d else (0.015, -0.045)
     check_cond_flags(args)
+    from ..edit import plan_from_args
+    edit_plan = plan_from_args(args)        # --edit_from / --pin / --edit_band_mm / --edit_steps: read and checked before anything is built
+    if edit_plan is not None and (args.mode != 'test' or not args.classifier_guidance):
+        raise ValueError("--edit_from edits designs in the guided chains of --mode=test and needs --classifier_guidance")
     cond = load_global_cond(args.global_cond, args.num_fingers) if args.global_cond is not None else None
     gc = 0 if cond is None else cond.shape[1]
     dataset = GripperDataset(pts, 0.12, -0.12, max_y, min_y, cond=cond)
@@ -309,6 +316,7 @@ def train(args):
                       object_vertices=objects, object_ids=object_ids, num_cpus=args.num_cpus, pts_x_dim=args.ctrlpts_x_dim,
                       pts_z_dim=args.ctrlpts_z_dim, sub_batch_size=args.sub_bs, render_video=args.render_video, seed=args.seed)
     model.save_meshes = bool(getattr(args, "save_meshes", False))
+    model.edit_plan = edit_plan
     model.cfg_weight, model.cond_drop_prob, model.global_cond_rows = float(args.cfg_weight), float(args.cond_drop_prob), cond
     if getattr(args, "save_objects", False):
         model.object_exporter = _object_exporter(args)

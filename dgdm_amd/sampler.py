@@ -15,6 +15,7 @@ import numpy as np
 import torch
 
 from . import _lib, engine
+from .edit import Edit
 from .engine import Guidance, Unet1d, make_objective
 from .goal import PROFILES, Goal, is_goal
 from .scheduler import DDIMScheduler
@@ -323,19 +324,37 @@ def _chain_cond(unet: Unet1d, global_cond: Optional[torch.Tensor], n_chains: int
     return cond.reshape(n_chains * batch, -1), n_chains == 1
 
 
+def _edit_start(edit: Optional[Edit], sched: DDIMScheduler, noise: torch.Tensor):
+    """(start sample, the timesteps the loop runs, the bounds of its steps or None): the noise and the whole schedule, or what the edit
+    makes of them - its designs noised to the first of the schedule's last K timesteps, those K timesteps, its (lo, hi) on the device."""
+    if edit is None:
+        return noise, sched.timesteps, None
+    x, ts = edit.start(sched, noise)
+    return x, ts, edit.bounds_on(noise.device)
+
+
+def _ddim_step(x, eps, grad, n_grad: int, coef, scale: float, bounds):
+    """The scheduler step of the Python loops: the plain one, or the bounded one of an edit."""
+    if bounds is None:
+        return engine.ddim_guided_step(x, eps, grad, n_grad, coef, scale)
+    return engine.ddim_guided_step_bounded(x, eps, grad, n_grad, coef, scale, bounds)
+
+
 def unguided_sample(unet: Unet1d, sched: DDIMScheduler, x: torch.Tensor, on_step=None, global_cond: Optional[torch.Tensor] = None,
-                    cfg_weight: float = 1.0) -> torch.Tensor:
+                    cfg_weight: float = 1.0, edit: Optional[Edit] = None) -> torch.Tensor:
     """S x [eps-net ; DDIM step]  (generator/diffusion.py:193-201, :249-256).  on_step(i, x_i, eps_i): the harness's per-step hook
     (plots, noise-prediction loss); it forces a device->host copy per step, as the reference's own plotting does.
     global_cond (B, gc), cfg_weight: the condition rows of a conditional eps-net and the classifier-free guidance weight (the mix is
-    the library's: Unet1d.forward_cfg)."""
+    the library's: Unet1d.forward_cfg).  edit: x is then the noise the edit's designs are noised with, and the loop runs the edit's K
+    bounded steps (dgdm_amd/edit.py)."""
     B = x.shape[0]
     engine.check_global_cond(global_cond, unet.global_cond_dim, B)
+    x, timesteps, bounds = _edit_start(edit, sched, x)
     x = x.clone()
-    for i, t in enumerate(sched.timesteps):
+    for i, t in enumerate(timesteps):
         ts = torch.full((B,), int(t), dtype=torch.int32, device=x.device)
         eps = unet.forward_cfg(x, ts, global_cond, cfg_weight)
-        x = engine.ddim_guided_step(x, eps, None, 0, sched.coefficients(int(t)), 0.0)
+        x = _ddim_step(x, eps, None, 0, sched.coefficients(int(t)), 0.0, bounds)
         if on_step is not None:
             on_step(i, x, eps)
     return x
@@ -408,17 +427,24 @@ def draw_chain_starts(guid: Guidance, chains: Sequence[Tuple[int, Union[str, Goa
 def guided_chains(unet: Unet1d, guid: Guidance, sched: DDIMScheduler, mode: str, noise: torch.Tensor,
                   chains: Sequence[Tuple[int, Union[str, Goal]]], unguided: Optional[torch.Tensor] = None,
                   starts: Optional[StartStream] = None, trace: Optional[list] = None, predrawn=None,
-                  global_cond: Optional[torch.Tensor] = None, cfg_weight: float = 1.0) -> torch.Tensor:
+                  global_cond: Optional[torch.Tensor] = None, cfg_weight: float = 1.0, edit: Optional[Edit] = None) -> torch.Tensor:
     """``Diffusion.guided_sample`` loop bodies (:561-576) for the chains [(object index, opt_obj), ...]; opt_obj: a reference
     objective name or a ``Goal`` (dgdm_amd/goal.py), whose chain is guided by the goal's row field.
 
     noise (B, L, 1) is shared by all chains (:570).  global_cond: (B, gc) shared by all chains or (n_chains, B, gc); cfg_weight: the
-    classifier-free guidance weight of a conditional eps-net.  Returns (n_chains, B, L, 1)."""
+    classifier-free guidance weight of a conditional eps-net.  Returns (n_chains, B, L, 1).
+
+    edit (dgdm_amd/edit.py): every chain then starts from the edit's designs noised with `noise`, runs the schedule's last K steps (the
+    3-D start draws are made for K steps) and clips every step's predicted clean sample to the edit's bounds.  The centres of a
+    'convergence' chain of an edit come from the SOURCE DESIGNS, not from an unguided sample: `unguided` is not read."""
     nc, (B, L, _) = len(chains), noise.shape
     cond_all, cond_shared = _chain_cond(unet, global_cond, nc, B)
     dev = noise.device
     is3d = mode == 'point_3d'
-    S = len(sched.timesteps)
+    noise, timesteps, bounds = _edit_start(edit, sched, noise)
+    if edit is not None:
+        unguided = edit.designs_on(dev)
+    S = len(timesteps)
     objectives, field = chain_objectives(guid, chains)
     if field is not None:
         guid.set_row_field(field)
@@ -441,11 +467,11 @@ def guided_chains(unet: Unet1d, guid: Guidance, sched: DDIMScheduler, mode: str,
     scales = [chain_scale(mode, o) for _, o in chains]
     if trace is None:         # the loop itself runs inside the library (one call); the Python loop below is kept for traced runs
         out = engine.guided_chains_run(unet, guid, noise.reshape(B, L), nc, 1, objectives, rowcoef,
-                                       np.ascontiguousarray(step_starts) if is3d else None, [int(t) for t in sched.timesteps],
-                                       [sched.coefficients(int(t)) for t in sched.timesteps], scales, global_cond, cfg_weight)
+                                       np.ascontiguousarray(step_starts) if is3d else None, [int(t) for t in timesteps],
+                                       [sched.coefficients(int(t)) for t in timesteps], scales, global_cond, cfg_weight, bounds)
         return out.reshape(nc, B, L, 1)
     x = noise.reshape(1, B, L).expand(nc, -1, -1).contiguous().to(torch.float32)
-    for si, t in enumerate(sched.timesteps):
+    for si, t in enumerate(timesteps):
         t = int(t)
         if si == 0 and nc > 1 and cond_shared:
             # every chain starts from the same noise (generator/diffusion.py:570: `sample = noise.clone()` per object), so the first
@@ -462,18 +488,19 @@ def guided_chains(unet: Unet1d, guid: Guidance, sched: DDIMScheduler, mode: str,
             trace.append((eps.clone(), g.clone(), x.clone()))          # eps, gradient and the step's INPUT x
         coef = sched.coefficients(t)
         if len(set(scales)) == 1:
-            x = engine.ddim_guided_step(x, eps, g, 1, coef, scales[0])
+            x = _ddim_step(x, eps, g, 1, coef, scales[0], bounds)
         else:
-            x = torch.stack([engine.ddim_guided_step(x[c], eps[c], g[c], 1, coef, scales[c]) for c in range(nc)])
+            x = torch.stack([_ddim_step(x[c], eps[c], g[c], 1, coef, scales[c], bounds) for c in range(nc)])
     return x.reshape(nc, B, L, 1)
 
 
 @_restores_row_field
 def guided_multi_object(unet: Unet1d, guid: Guidance, sched: DDIMScheduler, mode: str, noise: torch.Tensor,
                         object_indices: Sequence[int], opt_obj: Union[str, Goal], starts: Optional[StartStream] = None,
-                        on_step=None, global_cond: Optional[torch.Tensor] = None, cfg_weight: float = 1.0) -> torch.Tensor:
+                        on_step=None, global_cond: Optional[torch.Tensor] = None, cfg_weight: float = 1.0,
+                        edit: Optional[Edit] = None) -> torch.Tensor:
     """``Diffusion.guided_sample_multi_object`` loop (:637-647): one chain, gradient = mean over the objects.  opt_obj: a reference
-    objective name or a ``Goal``.  global_cond (B, gc), cfg_weight: as in guided_chains."""
+    objective name or a ``Goal``.  global_cond (B, gc), cfg_weight, edit: as in guided_chains."""
     n_obj, (B, L, _) = len(object_indices), noise.shape
     engine.check_global_cond(global_cond, unet.global_cond_dim, B)
     dev = noise.device
@@ -486,20 +513,21 @@ def guided_multi_object(unet: Unet1d, guid: Guidance, sched: DDIMScheduler, mode
     if is3d:
         starts = starts or StartStream(guid.cfg.num_object_points, guid.cfg.sub_batch_size)
     scale = chain_scale(mode, opt_obj, multi=True)
+    noise, timesteps, bounds = _edit_start(edit, sched, noise)
     if on_step is None:       # one library call for the whole loop; per step the reference draws object after object (:641-643)
-        S = len(sched.timesteps)
+        S = len(timesteps)
         st = starts.calls(guid.rows, S * n_obj).reshape(S, -1) if is3d else None      # per step object after object (:641-643): one run of draws
-        out = engine.guided_chains_run(unet, guid, noise.reshape(B, L), 1, n_obj, objectives, None, st, [int(t) for t in sched.timesteps],
-                                       [sched.coefficients(int(t)) for t in sched.timesteps], [scale], global_cond, cfg_weight)
+        out = engine.guided_chains_run(unet, guid, noise.reshape(B, L), 1, n_obj, objectives, None, st, [int(t) for t in timesteps],
+                                       [sched.coefficients(int(t)) for t in timesteps], [scale], global_cond, cfg_weight, bounds)
         return out.reshape(B, L, 1)
     x = noise.reshape(B, L).contiguous().to(torch.float32)
-    for i, t in enumerate(sched.timesteps):
+    for i, t in enumerate(timesteps):
         t = int(t)
         ts = torch.full((B,), t, dtype=torch.int32, device=dev)
         eps = unet.forward_cfg(x.reshape(B, L, 1), ts, global_cond, cfg_weight).reshape(B, L)
         st = starts.calls(guid.rows, n_obj).reshape(-1) if is3d else None      # object after object (:641-643)
         g = guid.grad(x.reshape(1, B, L).expand(n_obj, -1, -1).contiguous(), t, objectives, None, st)
-        x = engine.ddim_guided_step(x, eps, g, n_obj, sched.coefficients(t), scale)
+        x = _ddim_step(x, eps, g, n_obj, sched.coefficients(t), scale, bounds)
         if on_step is not None:                              # the harness's per-step plots (generator/diffusion.py:648-674)
             on_step(i, x.reshape(B, L, 1))
     return x.reshape(B, L, 1)
@@ -530,11 +558,12 @@ def draw_ensemble_starts(guid: Guidance, n_groups: int, n_obj: int, n_steps: int
 def guided_multi_object_groups(unet: Unet1d, guid: Guidance, sched: DDIMScheduler, mode: str, noise: torch.Tensor,
                                groups: Sequence[Sequence[int]], opt_objs: Sequence[Union[str, Goal]], streams: Optional[Sequence[StartStream]] = None,
                                predrawn: Optional[np.ndarray] = None, python_loop: bool = False, global_cond: Optional[torch.Tensor] = None,
-                               cfg_weight: float = 1.0) -> torch.Tensor:
+                               cfg_weight: float = 1.0, edit: Optional[Edit] = None) -> torch.Tensor:
     """Several independent ``guided_sample_multi_object`` chains (:637-647) in the same launches: chain k averages the guidance
     gradients of the objects ``groups[k]`` for objective ``opt_objs[k]`` (a guidance ensemble: n_obj dynamics-gradient
     evaluations per denoise step).  All groups have the same size.  Launch order of the gradient chains is object-major,
-    (j, k) -> j * K + k, so the mean over j is one strided reduction for every group at once.  Returns (K, B, L, 1)."""
+    (j, k) -> j * K + k, so the mean over j is one strided reduction for every group at once.  Returns (K, B, L, 1).
+    edit: as in guided_chains - every group edits the same designs, and `predrawn` then holds the draws of the edit's steps."""
     K, n_obj, (B, L, _) = len(groups), len(groups[0]), noise.shape
     assert all(len(g) == n_obj for g in groups) and len(opt_objs) == K
     cond_all, cond_shared = _chain_cond(unet, global_cond, K, B)       # global_cond: (B, gc) for all groups or (K, B, gc)
@@ -542,7 +571,8 @@ def guided_multi_object_groups(unet: Unet1d, guid: Guidance, sched: DDIMSchedule
         raise ValueError("the reference never runs the multi-object loop with 'convergence' (generator/diffusion.py:337)")
     dev = noise.device
     is3d = mode == 'point_3d'
-    S = len(sched.timesteps)
+    noise, timesteps, bounds = _edit_start(edit, sched, noise)
+    S = len(timesteps)
     # (a Goal group reads the row field at its gradient chains' own indices j * K + k)
     objectives, field = chain_objectives(guid, [(groups[k][j], opt_objs[k]) for j in range(n_obj) for k in range(K)])
     if field is not None:
@@ -555,11 +585,11 @@ def guided_multi_object_groups(unet: Unet1d, guid: Guidance, sched: DDIMSchedule
     scale = scales.pop()
     if not python_loop:       # one library call: K chains x n_obj gradients each, gradient chains object-major
         out = engine.guided_chains_run(unet, guid, noise.reshape(B, L), K, n_obj, objectives, None,
-                                       np.ascontiguousarray(predrawn) if is3d else None, [int(t) for t in sched.timesteps],
-                                       [sched.coefficients(int(t)) for t in sched.timesteps], [scale] * K, global_cond, cfg_weight)
+                                       np.ascontiguousarray(predrawn) if is3d else None, [int(t) for t in timesteps],
+                                       [sched.coefficients(int(t)) for t in timesteps], [scale] * K, global_cond, cfg_weight, bounds)
         return out.reshape(K, B, L, 1)
     x = noise.reshape(1, B, L).expand(K, -1, -1).contiguous().to(torch.float32)
-    for si, t in enumerate(sched.timesteps):
+    for si, t in enumerate(timesteps):
         t = int(t)
         if si == 0 and K > 1 and cond_shared:        # all K chains start from the same noise: one eps-net evaluation (see guided_chains)
             ts = torch.full((B,), t, dtype=torch.int32, device=dev)
@@ -569,5 +599,5 @@ def guided_multi_object_groups(unet: Unet1d, guid: Guidance, sched: DDIMSchedule
             ts = torch.full((K * B,), t, dtype=torch.int32, device=dev)
             eps = unet.forward_cfg(x.reshape(K * B, L, 1), ts, cond_all, cfg_weight).reshape(K, B, L)
         g = guid.grad(x.repeat(n_obj, 1, 1), t, objectives, None, predrawn[si].reshape(-1) if is3d else None)     # (n_obj*K, B, L)
-        x = engine.ddim_guided_step(x, eps, g, n_obj, sched.coefficients(t), scale)
+        x = _ddim_step(x, eps, g, n_obj, sched.coefficients(t), scale, bounds)
     return x.reshape(K, B, L, 1)

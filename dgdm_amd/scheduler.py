@@ -55,9 +55,12 @@ class DDIMScheduler:
         a_p = self.alphas_cumprod[prev] if prev >= 0 else self.final_alpha_cumprod
         return (float(a_t ** 0.5), float((1 - a_t) ** 0.5), float(a_p ** 0.5), float((1 - a_p) ** 0.5))
 
-    def step(self, model_output: torch.Tensor, timestep, sample: torch.Tensor, eta: float = 0.0, **unused) -> DDIMSchedulerOutput:
+    def step(self, model_output: torch.Tensor, timestep, sample: torch.Tensor, eta: float = 0.0, bounds=None, **unused) -> DDIMSchedulerOutput:
+        """bounds (not a diffusers argument): an edit's (lo, hi) per entry, which replace clip_sample's [-1, 1] (dgdm_amd/edit.py)."""
         if eta != 0.0:
             raise NotImplementedError("the reference always steps with eta = 0")
+        if bounds is not None:
+            return DDIMSchedulerOutput(engine.ddim_guided_step_bounded(sample, model_output, None, 0, self.coefficients(int(timestep)), 0.0, bounds))
         return DDIMSchedulerOutput(engine.ddim_guided_step(sample, model_output, None, 0, self.coefficients(int(timestep)), 0.0))
 
     def add_noise(self, original_samples: torch.Tensor, noise: torch.Tensor, timesteps: torch.Tensor) -> torch.Tensor:

@@ -119,6 +119,19 @@ int dgdm_unet1d_effective_form(const DgdmUnet1d *m, int B, int L);
 int dgdm_ddim_guided_step(const float *x_dev, const float *eps_dev, const float *grad_dev, int n_grad,
                           float *x_next_dev, int64_t n, float sqrt_abar_t, float sqrt_1m_abar_t,
                           float sqrt_abar_prev, float sqrt_1m_abar_prev, float guidance_scale, void *stream);
+/* Editing a design: dgdm_ddim_guided_step with the clip of the predicted clean sample per entry,
+ * x0 = min(max(x0, lo[i % period]), hi[i % period]), instead of clip_sample=True's [-1, 1].  lo = -1, hi = 1 is that step bit for bit;
+ * lo == hi == v pins an entry: its predicted clean value is v at every step, its noisy state sqrt(abar_prev) v + sqrt(1-abar_prev) eps
+ * stays a consistent DDIM state for the eps-net, and after the last step (sqrt(abar_prev) = 1, sqrt(1-abar_prev) = 0) it is exactly v;
+ * lo = max(-1, d-u), hi = min(1, d+u) is a band of half-width u around a design d.  An edit starts from add_noise(design, noise, t)
+ * and runs the schedule's last steps: the move the reference's first validation loop makes with its data (generator/diffusion.py:184-201).
+ * The per-entry clip itself is this project's own: the reference has no counterpart to pin it to.
+ * lo_dev / hi_dev [period] float32, period > 0 divides n (period = B*L: one block shared by all chains); a NULL bound, period <= 0 or
+ * a period that does not divide n: DGDM_EINVAL before anything is launched.  Precondition, not checked on the device:
+ * -1 <= lo <= hi <= 1, finite (any finite bounds are safe: they are only operands of the clamp).                                   */
+int dgdm_ddim_guided_step_bounded(const float *x_dev, const float *eps_dev, const float *grad_dev, int n_grad, float *x_next_dev, int64_t n,
+                                  float sqrt_abar_t, float sqrt_1m_abar_t, float sqrt_abar_prev, float sqrt_1m_abar_prev, float guidance_scale,
+                                  const float *lo_dev, const float *hi_dev, int64_t period, void *stream);
 /* DDIMScheduler.add_noise (diffusion.py:145,185): out = sqrt_abar*x0 + sqrt_1m_abar*noise */
 int dgdm_ddim_add_noise(const float *x0_dev, const float *noise_dev, float *out_dev, int64_t n,
                         float sqrt_abar, float sqrt_1m_abar, void *stream);
@@ -297,6 +310,15 @@ int dgdm_guided_chains_run_cond(DgdmUnet1d *unet, DgdmGuidance *g, const float *
                                 const DgdmObjective *objectives, const float *rowcoef_dev, const int64_t *starts_host,
                                 const int32_t *timesteps, const float *coef, const float *scales, int n_steps, float *x_out_dev,
                                 const float *global_cond_dev, int64_t cond_chain_stride, float cfg_weight, void *stream);
+/* The same with every scheduler step bounded (dgdm_ddim_guided_step_bounded): lo_dev / hi_dev [B][L], one block shared by all chains
+ * (period = B * L).  noise_dev is then the edit's start sample, add_noise(design, noise, timesteps[0]), and timesteps / coef the
+ * schedule's last n_steps entries.  lo_dev == hi_dev == NULL is dgdm_guided_chains_run_cond; exactly one of them NULL: DGDM_EINVAL.
+ * Equivalent, bit for bit, to the step-by-step composition above with dgdm_ddim_guided_step_bounded as its last call.               */
+int dgdm_guided_chains_run_bounded(DgdmUnet1d *unet, DgdmGuidance *g, const float *noise_dev, int n_chains, int n_grad,
+                                   const DgdmObjective *objectives, const float *rowcoef_dev, const int64_t *starts_host,
+                                   const int32_t *timesteps, const float *coef, const float *scales, int n_steps, float *x_out_dev,
+                                   const float *global_cond_dev, int64_t cond_chain_stride, float cfg_weight, const float *lo_dev,
+                                   const float *hi_dev, void *stream);
 
 /* Forward-only sweep of Diffusion.get_convergence_centers (diffusion.py:506-531): G orientations,
  * pos = 0, t = 0, rows r = g*B + b.  logits_dev [n_chains][B*G][3].  starts_host (3-D) holds
