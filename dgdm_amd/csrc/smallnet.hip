@@ -391,12 +391,22 @@ int dyn_post64(int W1, const float *partial, int tiles_per_b, const double *w1c,
 }
 
 // ------------------------------------------------------------------------------------------------
-// a13/a14: guidance combine + DDIM(eta=0, clip) step, elementwise (see dgdm_hip.h)
+// a13/a14: guidance combine + DDIM(eta=0, clip) step, elementwise (see dgdm_hip.h).  BOUNDED: the clip of the predicted clean sample is
+// per entry, [lo, hi] of entry i % period, instead of clip_sample=True's [-1, 1] (editing a design); the plain instantiation neither forms
+// the index nor reads lo / hi.  Everything but the clamp's operands is one sequence, so lo = -1, hi = 1 gives the plain step's bits;
+// lo == hi pins x0, and with sap = 1, sbp = 0 (the last step) the output is that value exactly.
+template <bool BOUNDED>
 __global__ void ddim_step_kernel(const float *__restrict__ x, const float *__restrict__ eps, const float *__restrict__ grad,
                                  int n_grad, float *__restrict__ out, int64_t n, float sa, float sb, float sap, float sbp,
-                                 float scale) {
+                                 float scale, const float *__restrict__ lo, const float *__restrict__ hi, int64_t period) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
+    float cl = -1.f, ch = 1.f;
+    if constexpr (BOUNDED) {
+        const int64_t j = i % period;
+        cl = lo[j];
+        ch = hi[j];
+    }
     float e = eps[i];
     if (grad) {
         float g = grad[i];
@@ -408,31 +418,7 @@ __global__ void ddim_step_kernel(const float *__restrict__ x, const float *__res
         e = sub_rn(e, mul_rn(mul_rn(sb, g), scale));           // eps - (sqrt(1-abar) * grad) * scale, unfused
     }
     float x0 = __fdiv_rn(sub_rn(x[i], mul_rn(sb, e)), sa);        // (x - sqrt(1-abar) eps) / sqrt(abar)
-    x0 = fminf(fmaxf(x0, -1.f), 1.f);
-    out[i] = add_rn(mul_rn(sap, x0), mul_rn(sbp, e));
-}
-
-// The same step with the clip of the predicted clean sample per entry: [lo, hi] of entry i % period instead of clip_sample=True's
-// [-1, 1] (see dgdm_hip.h: editing a design).  Everything but the clamp's operands is ddim_step_kernel's sequence, so lo = -1, hi = 1
-// gives its bits; lo == hi pins x0, and with sap = 1, sbp = 0 (the last step) the output is that value exactly.
-__global__ void ddim_step_bounded_kernel(const float *__restrict__ x, const float *__restrict__ eps, const float *__restrict__ grad,
-                                         int n_grad, float *__restrict__ out, int64_t n, float sa, float sb, float sap, float sbp,
-                                         float scale, const float *__restrict__ lo, const float *__restrict__ hi, int64_t period) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const int64_t j = i % period;
-    float e = eps[i];
-    if (grad) {
-        float g = grad[i];
-        if (n_grad > 1) {
-            g = 0.f + g;
-            for (int k = 1; k < n_grad; ++k) g += grad[(size_t)k * n + i];
-            g = g / (float)n_grad;
-        }
-        e = sub_rn(e, mul_rn(mul_rn(sb, g), scale));
-    }
-    float x0 = __fdiv_rn(sub_rn(x[i], mul_rn(sb, e)), sa);
-    x0 = fminf(fmaxf(x0, lo[j]), hi[j]);
+    x0 = fminf(fmaxf(x0, cl), ch);
     out[i] = add_rn(mul_rn(sap, x0), mul_rn(sbp, e));
 }
 
@@ -444,17 +430,30 @@ __global__ void add_noise_kernel(const float *__restrict__ x0, const float *__re
 
 }  // namespace dgdm
 
+// lo_dev == nullptr: the plain step.  bytes: what prof_end books for the stage.
+static int ddim_step_launch(const float *x_dev, const float *eps_dev, const float *grad_dev, int n_grad, float *x_next_dev, int64_t n, float sa,
+                            float sb, float sap, float sbp, float scale, const float *lo_dev, const float *hi_dev, int64_t period, double bytes,
+                            hipStream_t s) {
+    if (n == 0) return DGDM_OK;
+    const dim3 grid((unsigned)((n + 255) / 256));
+    dgdm::prof_begin(s, DGDM_STAGE_DDIM);
+    if (lo_dev)
+        hipLaunchKernelGGL(dgdm::ddim_step_kernel<true>, grid, dim3(256), 0, s, x_dev, eps_dev, grad_dev, n_grad, x_next_dev, n, sa, sb, sap, sbp,
+                           scale, lo_dev, hi_dev, period);
+    else
+        hipLaunchKernelGGL(dgdm::ddim_step_kernel<false>, grid, dim3(256), 0, s, x_dev, eps_dev, grad_dev, n_grad, x_next_dev, n, sa, sb, sap, sbp,
+                           scale, nullptr, nullptr, (int64_t)0);
+    dgdm::prof_end(s, DGDM_STAGE_DDIM, bytes);
+    DGDM_HIP_CHECK(hipGetLastError());
+    return DGDM_OK;
+}
+
 extern "C" int dgdm_ddim_guided_step(const float *x_dev, const float *eps_dev, const float *grad_dev, int n_grad, float *x_next_dev,
                                      int64_t n, float sqrt_abar_t, float sqrt_1m_abar_t, float sqrt_abar_prev,
                                      float sqrt_1m_abar_prev, float guidance_scale, void *stream) {
     DGDM_REQUIRE(x_dev && eps_dev && x_next_dev && n >= 0, DGDM_EINVAL, "dgdm_ddim_guided_step: null argument");
-    if (n == 0) return DGDM_OK;
-    dgdm::prof_begin((hipStream_t)stream, DGDM_STAGE_DDIM);
-    hipLaunchKernelGGL(dgdm::ddim_step_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, x_dev, eps_dev,
-                       grad_dev, n_grad, x_next_dev, n, sqrt_abar_t, sqrt_1m_abar_t, sqrt_abar_prev, sqrt_1m_abar_prev, guidance_scale);
-    dgdm::prof_end((hipStream_t)stream, DGDM_STAGE_DDIM, (double)n * 4.0 * (3 + n_grad));
-    DGDM_HIP_CHECK(hipGetLastError());
-    return DGDM_OK;
+    return ddim_step_launch(x_dev, eps_dev, grad_dev, n_grad, x_next_dev, n, sqrt_abar_t, sqrt_1m_abar_t, sqrt_abar_prev, sqrt_1m_abar_prev,
+                            guidance_scale, nullptr, nullptr, 0, (double)n * 4.0 * (3 + n_grad), (hipStream_t)stream);
 }
 
 extern "C" int dgdm_ddim_guided_step_bounded(const float *x_dev, const float *eps_dev, const float *grad_dev, int n_grad, float *x_next_dev,
@@ -465,14 +464,8 @@ extern "C" int dgdm_ddim_guided_step_bounded(const float *x_dev, const float *ep
     DGDM_REQUIRE(lo_dev && hi_dev, DGDM_EINVAL, "dgdm_ddim_guided_step_bounded: needs both lo and hi");
     DGDM_REQUIRE(period > 0 && n % period == 0, DGDM_EINVAL, "dgdm_ddim_guided_step_bounded: period %lld does not divide n = %lld", (long long)period,
                  (long long)n);
-    if (n == 0) return DGDM_OK;
-    dgdm::prof_begin((hipStream_t)stream, DGDM_STAGE_DDIM);
-    hipLaunchKernelGGL(dgdm::ddim_step_bounded_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, x_dev, eps_dev,
-                       grad_dev, n_grad, x_next_dev, n, sqrt_abar_t, sqrt_1m_abar_t, sqrt_abar_prev, sqrt_1m_abar_prev, guidance_scale, lo_dev,
-                       hi_dev, period);
-    dgdm::prof_end((hipStream_t)stream, DGDM_STAGE_DDIM, (double)n * 4.0 * (5 + n_grad));
-    DGDM_HIP_CHECK(hipGetLastError());
-    return DGDM_OK;
+    return ddim_step_launch(x_dev, eps_dev, grad_dev, n_grad, x_next_dev, n, sqrt_abar_t, sqrt_1m_abar_t, sqrt_abar_prev, sqrt_1m_abar_prev,
+                            guidance_scale, lo_dev, hi_dev, period, (double)n * 4.0 * (5 + n_grad), (hipStream_t)stream);
 }
 
 extern "C" int dgdm_ddim_add_noise(const float *x0_dev, const float *noise_dev, float *out_dev, int64_t n, float sqrt_abar,

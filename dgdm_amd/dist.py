@@ -182,10 +182,8 @@ def guided_chains_sharded(unet, spec: GuidanceSpec, sched, mode: str, noise: tor
         predrawn = sampler.draw_chain_starts(spec, chains, S, starts, keep=mine, streams=streams)
     if len(local_chains):
         guid = (build or spec.build)(objects[local_objects].to(noise.device), len(local_chains))
-        cond_kw = {} if global_cond is None else {"global_cond": global_cond, "cfg_weight": cfg_weight}      # an unconditional call is what it was
-        if edit is not None:
-            cond_kw["edit"] = edit
-        local = sampler.guided_chains(unet, guid, sched, mode, noise, local_chains, unguided=unguided, predrawn=predrawn, **cond_kw)
+        local = sampler.guided_chains(unet, guid, sched, mode, noise, local_chains, unguided=unguided, predrawn=predrawn, global_cond=global_cond,
+                                      cfg_weight=cfg_weight, edit=edit)
     else:
         local = torch.zeros((0, B, L, 1), dtype=torch.float32, device=noise.device)
     return gather_pairs(local, len(chains), group)
@@ -205,7 +203,7 @@ def guided_multi_object_sharded(unet, spec: GuidanceSpec, sched, mode: str, nois
     the same scheduler step on the full stack, in object order - so every rank holds the single-process result bit for bit.
     3-D: per step the reference draws the FPS starts object after object (:641-643); every rank walks that stream and keeps its objects'.
     edit (dgdm_amd/edit.py): the start sample, the steps and their bounds are the edit's, the same on every rank."""
-    from . import engine, sampler
+    from . import sampler
     world, rank = world_rank(group)
     n_obj, (B, L, _) = objects.shape[0], noise.shape
     if not sampler.is_goal(opt_obj) and opt_obj == 'convergence':
@@ -215,29 +213,27 @@ def guided_multi_object_sharded(unet, spec: GuidanceSpec, sched, mode: str, nois
     if is3d:
         starts = starts or sampler.StartStream(spec.num_object_points, spec.sub_batch_size)
     guid = (build or spec.build)(objects[mine.start:mine.stop].to(noise.device), len(mine)) if len(mine) else None
+
+    def grad_fn(si, t, x):              # this rank's objects' gradients of the one chain x (1, B, L), then everybody's, in object order
+        st = None
+        if is3d:
+            per_obj = [starts.call(spec.rows) if j in mine else starts.skip(spec.rows) for j in range(n_obj)]
+            st = np.concatenate([per_obj[j] for j in mine]) if len(mine) else None
+        if guid is not None:
+            g = guid.grad(x.expand(len(mine), -1, -1).contiguous(), t, objectives, None, st)
+        else:
+            g = torch.zeros((0, B, L), dtype=torch.float32, device=x.device)
+        return gather_rows(g, n_obj, group)
+
     with sampler.keeps_row_field(guid):              # a Goal's field is on the handle for this loop only
         objectives, field = sampler.chain_objectives(guid, [(k, opt_obj) for k in range(len(mine))]) if guid is not None else ([], None)
         if field is not None:
             guid.set_row_field(field)
-        scale = sampler.chain_scale(mode, opt_obj, multi=True)
-        noise, timesteps, bounds = sampler._edit_start(edit, sched, noise)
-        x = noise.reshape(B, L).contiguous().to(torch.float32)
-        for i, t in enumerate(timesteps):
-            t = int(t)
-            eps = unet.forward_cfg(x.reshape(B, L, 1), torch.full((B,), t, dtype=torch.int32, device=x.device), global_cond, cfg_weight).reshape(B, L)
-            st = None
-            if is3d:
-                per_obj = [starts.call(spec.rows) if j in mine else starts.skip(spec.rows) for j in range(n_obj)]
-                st = np.concatenate([per_obj[j] for j in mine]) if len(mine) else None
-            if guid is not None:
-                g = guid.grad(x.reshape(1, B, L).expand(len(mine), -1, -1).contiguous(), t, objectives, None, st)
-            else:
-                g = torch.zeros((0, B, L), dtype=torch.float32, device=x.device)
-            g = gather_rows(g, n_obj, group)
-            x = sampler._ddim_step(x, eps, g, n_obj, sched.coefficients(t), scale, bounds)
-            if on_step is not None:
-                on_step(i, x.reshape(B, L, 1))
-    return x.reshape(B, L, 1)
+        x0, timesteps, bounds = sampler.edit_start(edit, sched, noise)
+        hook = None if on_step is None else lambda i, x, eps: on_step(i, x.reshape(B, L, 1))
+        out = sampler.run_chains(unet, None, sched, x0.reshape(B, L), 1, n_obj, None, None, None, timesteps,
+                                 [sampler.chain_scale(mode, opt_obj, multi=True)], global_cond, cfg_weight, bounds, on_step=hook, grad_fn=grad_fn)
+    return out.reshape(B, L, 1)
 
 
 def all_reduce_sum(t: torch.Tensor, group=None) -> torch.Tensor:

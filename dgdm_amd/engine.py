@@ -482,16 +482,6 @@ class Guidance:
         return a, b
 
 
-def ddim_guided_step(x: torch.Tensor, eps: torch.Tensor, grad: Optional[torch.Tensor], n_grad: int, coef: Tuple[float, float, float, float],
-                     scale: float) -> torch.Tensor:
-    """grad: None or (n_grad, *x.shape) stacked gradients whose mean guides the step."""
-    x, eps = _f32(x), _f32(eps)
-    out = torch.empty_like(x)
-    g = _f32(grad) if grad is not None else None
-    check(lib().dgdm_ddim_guided_step(dptr(x), dptr(eps), dptr(g), n_grad, dptr(out), x.numel(), *[float(c) for c in coef], float(scale), stream_ptr()))
-    return out
-
-
 def _bounds_block(bounds, numel: int, device) -> Tuple[torch.Tensor, torch.Tensor, int]:
     """(lo, hi) of an edit as contiguous float32 device tensors and their period; ValueError unless both have the same size and it divides numel."""
     if not isinstance(bounds, (tuple, list)) or len(bounds) != 2 or bounds[0] is None or bounds[1] is None:
@@ -502,17 +492,26 @@ def _bounds_block(bounds, numel: int, device) -> Tuple[torch.Tensor, torch.Tenso
     return lo, hi, lo.numel()
 
 
-def ddim_guided_step_bounded(x: torch.Tensor, eps: torch.Tensor, grad: Optional[torch.Tensor], n_grad: int, coef: Tuple[float, float, float, float],
-                             scale: float, bounds) -> torch.Tensor:
-    """ddim_guided_step with the predicted clean sample clipped to bounds = (lo, hi) per entry instead of [-1, 1]
-    (dgdm_ddim_guided_step_bounded): lo / hi hold one block that repeats over x (e.g. (B, L) for x (n_chains, B, L))."""
+def ddim_guided_step(x: torch.Tensor, eps: torch.Tensor, grad: Optional[torch.Tensor], n_grad: int, coef: Tuple[float, float, float, float],
+                     scale: float, bounds=None) -> torch.Tensor:
+    """grad: None or (n_grad, *x.shape) stacked gradients whose mean guides the step.  bounds = (lo, hi): the predicted clean sample is
+    clipped to them per entry instead of to [-1, 1] (dgdm_ddim_guided_step_bounded): lo / hi hold one block that repeats over x (e.g.
+    (B, L) for x (n_chains, B, L))."""
     x, eps = _f32(x), _f32(eps)
-    lo, hi, period = _bounds_block(bounds, x.numel(), x.device)
     out = torch.empty_like(x)
     g = _f32(grad) if grad is not None else None
-    check(lib().dgdm_ddim_guided_step_bounded(dptr(x), dptr(eps), dptr(g), n_grad, dptr(out), x.numel(), *[float(c) for c in coef], float(scale),
-                                              dptr(lo), dptr(hi), period, stream_ptr()))
+    args = (dptr(x), dptr(eps), dptr(g), n_grad, dptr(out), x.numel(), *[float(c) for c in coef], float(scale))
+    if bounds is None:
+        check(lib().dgdm_ddim_guided_step(*args, stream_ptr()))
+    else:
+        lo, hi, period = _bounds_block(bounds, x.numel(), x.device)
+        check(lib().dgdm_ddim_guided_step_bounded(*args, dptr(lo), dptr(hi), period, stream_ptr()))
     return out
+
+
+def ddim_guided_step_bounded(x, eps, grad, n_grad: int, coef, scale: float, bounds) -> torch.Tensor:
+    """ddim_guided_step under the name tests and scripts call; here bounds are not optional (None is the ValueError of a malformed pair)."""
+    return ddim_guided_step(x, eps, grad, n_grad, coef, scale, () if bounds is None else bounds)
 
 
 def guided_chains_run(unet: "Unet1d", guid: "Guidance", noise: torch.Tensor, n_chains: int, n_grad: int, objectives: Sequence[_lib.Objective],

@@ -470,16 +470,15 @@ class Diffusion(nn.Module):
         chains = [(i, opt_obj) for i in range(n)]
         ug = None if unguided_sample is None else unguided_sample.to(self.device)
         edit = self._edit(batch_idx, batch_size)
-        edit_kw = {} if edit is None else {"edit": edit}                 # a run without --edit_from makes the calls it made
         if ddist.world_rank()[0] > 1:
             out = ddist.guided_chains_sharded(self._net(), self._spec(batch_size, ori_range, objs.shape[1]), self.noise_scheduler, self.mode,
                                               noise.to(self.device), objs, chains, unguided=ug,
                                               build=lambda o, k: self._guidance_for(batch_size, ori_range, o.detach().cpu(), k),
-                                              global_cond=global_cond, cfg_weight=self.cfg_weight, **edit_kw)
+                                              global_cond=global_cond, cfg_weight=self.cfg_weight, edit=edit)
         else:
             g = self._guidance_for(batch_size, ori_range, objs, n)
             out = sampler.guided_chains(self._net(), g, self.noise_scheduler, self.mode, noise.to(self.device), chains, unguided=ug,
-                                        global_cond=global_cond, cfg_weight=self.cfg_weight, **edit_kw)
+                                        global_cond=global_cond, cfg_weight=self.cfg_weight, edit=edit)
         if ddist.world_rank()[1] == 0:
             tag = f"{opt_obj}_orirange={ori_range[0]:.3f}_{ori_range[1]:.3f}"
             sub = 'vis_guided' if edit is None else 'vis_edit'
@@ -499,7 +498,6 @@ class Diffusion(nn.Module):
         tag = f"{opt_obj}_orirange={ori_range[0]:.3f}_{ori_range[1]:.3f}"
         rank0 = ddist.world_rank()[1] == 0
         edit = self._edit(batch_idx, batch_size)          # --edit_from: the chain edits this batch's designs (see guided_sample)
-        edit_kw = {} if edit is None else {"edit": edit}
         sub = 'vis_guided' if edit is None else 'vis_edit'
         on_step = None
         if save_dir and self.render_plots and rank0:                     # per-step, per-gripper PNGs (:648-674)
@@ -511,12 +509,12 @@ class Diffusion(nn.Module):
             out = ddist.guided_multi_object_sharded(self._net(), self._spec(batch_size, ori_range, objs.shape[1]), self.noise_scheduler, self.mode,
                                                     noise.to(self.device), objs, opt_obj,
                                                     build=lambda o, k: self._guidance_for(batch_size, ori_range, o.detach().cpu(), k), on_step=on_step,
-                                                    global_cond=global_cond, cfg_weight=self.cfg_weight, **edit_kw)
+                                                    global_cond=global_cond, cfg_weight=self.cfg_weight, edit=edit)
         else:
             g = self._guidance_for(batch_size, ori_range, objs, objs.shape[0])
             out = sampler.guided_multi_object(self._net(), g, self.noise_scheduler, self.mode, noise.to(self.device),
                                               list(range(objs.shape[0])), opt_obj, on_step=on_step, global_cond=global_cond,
-                                              cfg_weight=self.cfg_weight, **edit_kw)
+                                              cfg_weight=self.cfg_weight, edit=edit)
         if rank0:
             self._emit(save_dir, sub, tag, out[None], ["allobj"])
             if self.simulator is not None and save_dir:                  # :675-709: every gripper on all objects

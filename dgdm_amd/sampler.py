@@ -314,17 +314,7 @@ def pair_stream(num_points: int, sub_batch_size: int, seed: int, pair_index: int
     return StartStream(num_points, sub_batch_size, seed=(int(seed) * 1_000_003 + int(pair_index)) & 0x7FFFFFFFFFFFFFFF)
 
 
-def _chain_cond(unet: Unet1d, global_cond: Optional[torch.Tensor], n_chains: int, batch: int):
-    """(condition rows of all n_chains * B samples or None, whether one (B, gc) block is shared by the chains) for the Python loops."""
-    cond, stride = engine.chain_cond_layout(global_cond, unet.global_cond_dim, n_chains, batch)
-    if cond is None:
-        return None, True
-    if stride == 0:
-        return cond.reshape(1, batch, -1).expand(n_chains, -1, -1).reshape(n_chains * batch, -1), True
-    return cond.reshape(n_chains * batch, -1), n_chains == 1
-
-
-def _edit_start(edit: Optional[Edit], sched: DDIMScheduler, noise: torch.Tensor):
+def edit_start(edit: Optional[Edit], sched: DDIMScheduler, noise: torch.Tensor):
     """(start sample, the timesteps the loop runs, the bounds of its steps or None): the noise and the whole schedule, or what the edit
     makes of them - its designs noised to the first of the schedule's last K timesteps, those K timesteps, its (lo, hi) on the device."""
     if edit is None:
@@ -333,11 +323,57 @@ def _edit_start(edit: Optional[Edit], sched: DDIMScheduler, noise: torch.Tensor)
     return x, ts, edit.bounds_on(noise.device)
 
 
-def _ddim_step(x, eps, grad, n_grad: int, coef, scale: float, bounds):
-    """The scheduler step of the Python loops: the plain one, or the bounded one of an edit."""
-    if bounds is None:
-        return engine.ddim_guided_step(x, eps, grad, n_grad, coef, scale)
-    return engine.ddim_guided_step_bounded(x, eps, grad, n_grad, coef, scale, bounds)
+def run_chains(unet: Unet1d, guid: Optional[Guidance], sched: DDIMScheduler, x0: torch.Tensor, n_chains: int, n_grad: int, objectives,
+               rowcoef: Optional[torch.Tensor], starts: Optional[np.ndarray], timesteps, scales: Sequence[float],
+               global_cond: Optional[torch.Tensor] = None, cfg_weight: float = 1.0, bounds=None, trace: Optional[list] = None,
+               on_step=None, grad_fn=None, stepwise: bool = False) -> torch.Tensor:
+    """THE denoise loop, S x [eps-net with the classifier-free mix ; guidance gradient ; DDIM step], of every sampler here and in
+    dgdm_amd/dist.py: x0 (B, L) -> (n_chains, B, L).  All n_chains chains start from x0; chain k is guided by the mean of n_grad
+    gradients, gradient j of chain k being gradient chain j * n_chains + k of `objectives` (object-major, as dgdm_guided_chains_run
+    takes them); n_grad == 0: no guidance.  rowcoef, starts ([step][...], 3-D), scales (one per chain), global_cond ((B, gc) shared or
+    (n_chains, B, gc)), cfg_weight, bounds: as engine.guided_chains_run takes them.
+
+    The loop is ONE library call (engine.guided_chains_run) unless something asks to see its steps; then it is walked here, with the
+    same bits (tests/test_gpu_parity.py):
+      trace: a list that receives (eps, grad, x) per step, each (n_chains, B, L), x being the step's INPUT;
+      on_step(si, x, eps): called after each step with its output x;
+      grad_fn(si, t, x) -> (n_grad * n_chains, B, L): the step's gradients instead of guid.grad on n_grad copies of x with step si's starts;
+      stepwise=True: nothing of these, but walk it all the same."""
+    B, L = x0.shape
+    nc = n_chains
+    if not stepwise and trace is None and on_step is None and grad_fn is None:
+        return engine.guided_chains_run(unet, guid, x0, nc, n_grad, objectives, rowcoef, starts, [int(t) for t in timesteps],
+                                        [sched.coefficients(int(t)) for t in timesteps], scales, global_cond, cfg_weight, bounds)
+    # one scheduler launch over all chains, or - chains with scales of their own - one per chain, which has no averaged form
+    steps = [(slice(None), scales[0])] if len(set(scales)) == 1 else list(enumerate(scales))
+    if len(steps) > 1 and n_grad != 1:
+        raise ValueError(f"run_chains: per-chain classifier scales ({sorted(set(scales))}) need n_grad == 1, not {n_grad}")
+    cond, stride = engine.chain_cond_layout(global_cond, unet.global_cond_dim, nc, B)        # stride 0: one (B, gc) block for all chains, or none
+    if cond is not None:
+        cond = (cond.reshape(1, B, -1).expand(nc, -1, -1) if stride == 0 else cond).reshape(nc * B, -1)
+    x = x0.reshape(1, B, L).expand(nc, -1, -1).contiguous().to(torch.float32)
+    for si, t in enumerate(timesteps):
+        t = int(t)
+        # every chain starts from the same sample (generator/diffusion.py:570: `sample = noise.clone()` per object), so the first eps-net
+        # call has nc identical copies of the B fingers as its batch: evaluate it once (same input, same kernel, same bits) - unless
+        # every chain has condition rows of its own
+        n = 1 if si == 0 and stride == 0 else nc
+        ts = torch.full((n * B,), t, dtype=torch.int32, device=x.device)
+        eps = unet.forward_cfg(x[:n].reshape(n * B, L, 1), ts, None if cond is None else cond[:n * B], cfg_weight)
+        eps = eps.reshape(n, B, L).expand(nc, -1, -1).contiguous()
+        g = None
+        if grad_fn is not None:
+            g = grad_fn(si, t, x)
+        elif n_grad:
+            g = guid.grad(x.repeat(n_grad, 1, 1), t, objectives, rowcoef, None if starts is None else starts[si].reshape(-1))
+        if trace is not None:
+            trace.append((eps.clone(), None if g is None else g.clone(), x.clone()))
+        coef = sched.coefficients(t)
+        out = [engine.ddim_guided_step(x[c], eps[c], None if g is None else g[c], n_grad, coef, sc, bounds) for c, sc in steps]
+        x = out[0] if len(out) == 1 else torch.stack(out)
+        if on_step is not None:
+            on_step(si, x, eps)
+    return x
 
 
 def unguided_sample(unet: Unet1d, sched: DDIMScheduler, x: torch.Tensor, on_step=None, global_cond: Optional[torch.Tensor] = None,
@@ -349,15 +385,11 @@ def unguided_sample(unet: Unet1d, sched: DDIMScheduler, x: torch.Tensor, on_step
     bounded steps (dgdm_amd/edit.py)."""
     B = x.shape[0]
     engine.check_global_cond(global_cond, unet.global_cond_dim, B)
-    x, timesteps, bounds = _edit_start(edit, sched, x)
-    x = x.clone()
-    for i, t in enumerate(timesteps):
-        ts = torch.full((B,), int(t), dtype=torch.int32, device=x.device)
-        eps = unet.forward_cfg(x, ts, global_cond, cfg_weight)
-        x = _ddim_step(x, eps, None, 0, sched.coefficients(int(t)), 0.0, bounds)
-        if on_step is not None:
-            on_step(i, x, eps)
-    return x
+    x, timesteps, bounds = edit_start(edit, sched, x)
+    hook = None if on_step is None else lambda i, xi, eps: on_step(i, xi.reshape(x.shape), eps.reshape(x.shape))
+    out = run_chains(unet, None, sched, x.reshape(B, -1), 1, 0, [], None, None, timesteps, [0.0], global_cond, cfg_weight, bounds,
+                     on_step=hook, stepwise=True)
+    return out.reshape(x.shape)
 
 
 def convergence_centers(guid: Guidance, mode: str, unguided: torch.Tensor, objects_of_chain: Sequence[int],
@@ -438,10 +470,10 @@ def guided_chains(unet: Unet1d, guid: Guidance, sched: DDIMScheduler, mode: str,
     3-D start draws are made for K steps) and clips every step's predicted clean sample to the edit's bounds.  The centres of a
     'convergence' chain of an edit come from the SOURCE DESIGNS, not from an unguided sample: `unguided` is not read."""
     nc, (B, L, _) = len(chains), noise.shape
-    cond_all, cond_shared = _chain_cond(unet, global_cond, nc, B)
+    engine.chain_cond_layout(global_cond, unet.global_cond_dim, nc, B)       # a condition of the wrong shape is refused before anything runs
     dev = noise.device
     is3d = mode == 'point_3d'
-    noise, timesteps, bounds = _edit_start(edit, sched, noise)
+    noise, timesteps, bounds = edit_start(edit, sched, noise)
     if edit is not None:
         unguided = edit.designs_on(dev)
     S = len(timesteps)
@@ -464,34 +496,9 @@ def guided_chains(unet: Unet1d, guid: Guidance, sched: DDIMScheduler, mode: str,
         for k, c in enumerate(conv):
             rc[c] = guid.rowcoef(centers[k])
         rowcoef = torch.from_numpy(rc).to(dev)
-    scales = [chain_scale(mode, o) for _, o in chains]
-    if trace is None:         # the loop itself runs inside the library (one call); the Python loop below is kept for traced runs
-        out = engine.guided_chains_run(unet, guid, noise.reshape(B, L), nc, 1, objectives, rowcoef,
-                                       np.ascontiguousarray(step_starts) if is3d else None, [int(t) for t in timesteps],
-                                       [sched.coefficients(int(t)) for t in timesteps], scales, global_cond, cfg_weight, bounds)
-        return out.reshape(nc, B, L, 1)
-    x = noise.reshape(1, B, L).expand(nc, -1, -1).contiguous().to(torch.float32)
-    for si, t in enumerate(timesteps):
-        t = int(t)
-        if si == 0 and nc > 1 and cond_shared:
-            # every chain starts from the same noise (generator/diffusion.py:570: `sample = noise.clone()` per object), so the first
-            # eps-net call has nc identical copies of the B fingers as its batch: evaluate it once (same input, same kernel, same bits)
-            # - unless every chain has condition rows of its own
-            ts = torch.full((B,), t, dtype=torch.int32, device=dev)
-            eps = unet.forward_cfg(x[0].reshape(B, L, 1), ts, None if cond_all is None else cond_all[:B], cfg_weight)
-            eps = eps.reshape(1, B, L).expand(nc, -1, -1).contiguous()
-        else:
-            ts = torch.full((nc * B,), t, dtype=torch.int32, device=dev)
-            eps = unet.forward_cfg(x.reshape(nc * B, L, 1), ts, cond_all, cfg_weight).reshape(nc, B, L)
-        g = guid.grad(x, t, objectives, rowcoef, step_starts[si].reshape(-1) if is3d else None)
-        if trace is not None:
-            trace.append((eps.clone(), g.clone(), x.clone()))          # eps, gradient and the step's INPUT x
-        coef = sched.coefficients(t)
-        if len(set(scales)) == 1:
-            x = _ddim_step(x, eps, g, 1, coef, scales[0], bounds)
-        else:
-            x = torch.stack([_ddim_step(x[c], eps[c], g[c], 1, coef, scales[c], bounds) for c in range(nc)])
-    return x.reshape(nc, B, L, 1)
+    out = run_chains(unet, guid, sched, noise.reshape(B, L), nc, 1, objectives, rowcoef, step_starts, timesteps,
+                     [chain_scale(mode, o) for _, o in chains], global_cond, cfg_weight, bounds, trace=trace)
+    return out.reshape(nc, B, L, 1)
 
 
 @_restores_row_field
@@ -503,7 +510,6 @@ def guided_multi_object(unet: Unet1d, guid: Guidance, sched: DDIMScheduler, mode
     objective name or a ``Goal``.  global_cond (B, gc), cfg_weight, edit: as in guided_chains."""
     n_obj, (B, L, _) = len(object_indices), noise.shape
     engine.check_global_cond(global_cond, unet.global_cond_dim, B)
-    dev = noise.device
     is3d = mode == 'point_3d'
     objectives, field = chain_objectives(guid, [(oi, opt_obj) for oi in object_indices])
     if field is not None:
@@ -512,25 +518,13 @@ def guided_multi_object(unet: Unet1d, guid: Guidance, sched: DDIMScheduler, mode
         raise ValueError("the reference never runs the multi-object loop with 'convergence' (generator/diffusion.py:337)")
     if is3d:
         starts = starts or StartStream(guid.cfg.num_object_points, guid.cfg.sub_batch_size)
-    scale = chain_scale(mode, opt_obj, multi=True)
-    noise, timesteps, bounds = _edit_start(edit, sched, noise)
-    if on_step is None:       # one library call for the whole loop; per step the reference draws object after object (:641-643)
-        S = len(timesteps)
-        st = starts.calls(guid.rows, S * n_obj).reshape(S, -1) if is3d else None      # per step object after object (:641-643): one run of draws
-        out = engine.guided_chains_run(unet, guid, noise.reshape(B, L), 1, n_obj, objectives, None, st, [int(t) for t in timesteps],
-                                       [sched.coefficients(int(t)) for t in timesteps], [scale], global_cond, cfg_weight, bounds)
-        return out.reshape(B, L, 1)
-    x = noise.reshape(B, L).contiguous().to(torch.float32)
-    for i, t in enumerate(timesteps):
-        t = int(t)
-        ts = torch.full((B,), t, dtype=torch.int32, device=dev)
-        eps = unet.forward_cfg(x.reshape(B, L, 1), ts, global_cond, cfg_weight).reshape(B, L)
-        st = starts.calls(guid.rows, n_obj).reshape(-1) if is3d else None      # object after object (:641-643)
-        g = guid.grad(x.reshape(1, B, L).expand(n_obj, -1, -1).contiguous(), t, objectives, None, st)
-        x = _ddim_step(x, eps, g, n_obj, sched.coefficients(t), scale, bounds)
-        if on_step is not None:                              # the harness's per-step plots (generator/diffusion.py:648-674)
-            on_step(i, x.reshape(B, L, 1))
-    return x.reshape(B, L, 1)
+    noise, timesteps, bounds = edit_start(edit, sched, noise)
+    # per step the reference draws object after object (:641-643): one run of draws for the whole loop
+    st = starts.calls(guid.rows, len(timesteps) * n_obj).reshape(len(timesteps), -1) if is3d else None
+    hook = None if on_step is None else lambda i, x, eps: on_step(i, x.reshape(B, L, 1))      # the harness's per-step plots (:648-674)
+    out = run_chains(unet, guid, sched, noise.reshape(B, L), 1, n_obj, objectives, None, st, timesteps, [chain_scale(mode, opt_obj, multi=True)],
+                     global_cond, cfg_weight, bounds, on_step=hook)
+    return out.reshape(B, L, 1)
 
 
 def draw_ensemble_starts(guid: Guidance, n_groups: int, n_obj: int, n_steps: int, streams: Optional[Sequence[StartStream]] = None,
@@ -566,38 +560,21 @@ def guided_multi_object_groups(unet: Unet1d, guid: Guidance, sched: DDIMSchedule
     edit: as in guided_chains - every group edits the same designs, and `predrawn` then holds the draws of the edit's steps."""
     K, n_obj, (B, L, _) = len(groups), len(groups[0]), noise.shape
     assert all(len(g) == n_obj for g in groups) and len(opt_objs) == K
-    cond_all, cond_shared = _chain_cond(unet, global_cond, K, B)       # global_cond: (B, gc) for all groups or (K, B, gc)
+    engine.chain_cond_layout(global_cond, unet.global_cond_dim, K, B)       # global_cond: (B, gc) for all groups or (K, B, gc)
     if any(not is_goal(o) and o == 'convergence' for o in opt_objs):
         raise ValueError("the reference never runs the multi-object loop with 'convergence' (generator/diffusion.py:337)")
-    dev = noise.device
     is3d = mode == 'point_3d'
-    noise, timesteps, bounds = _edit_start(edit, sched, noise)
-    S = len(timesteps)
+    noise, timesteps, bounds = edit_start(edit, sched, noise)
     # (a Goal group reads the row field at its gradient chains' own indices j * K + k)
     objectives, field = chain_objectives(guid, [(groups[k][j], opt_objs[k]) for j in range(n_obj) for k in range(K)])
     if field is not None:
         guid.set_row_field(field)
     if is3d and predrawn is None:
-        predrawn = draw_ensemble_starts(guid, K, n_obj, S, streams)
+        predrawn = draw_ensemble_starts(guid, K, n_obj, len(timesteps), streams)
     scales = {chain_scale(mode, o, multi=True) for o in opt_objs}
     if len(scales) != 1:      # (dgdm_guided_chains_run refuses per-chain scales with averaged gradients; names share one scale, Goals may not)
         raise ValueError(f"guided_multi_object_groups: the groups' classifier scales differ ({sorted(scales)}); give the Goals one scale")
-    scale = scales.pop()
-    if not python_loop:       # one library call: K chains x n_obj gradients each, gradient chains object-major
-        out = engine.guided_chains_run(unet, guid, noise.reshape(B, L), K, n_obj, objectives, None,
-                                       np.ascontiguousarray(predrawn) if is3d else None, [int(t) for t in timesteps],
-                                       [sched.coefficients(int(t)) for t in timesteps], [scale] * K, global_cond, cfg_weight, bounds)
-        return out.reshape(K, B, L, 1)
-    x = noise.reshape(1, B, L).expand(K, -1, -1).contiguous().to(torch.float32)
-    for si, t in enumerate(timesteps):
-        t = int(t)
-        if si == 0 and K > 1 and cond_shared:        # all K chains start from the same noise: one eps-net evaluation (see guided_chains)
-            ts = torch.full((B,), t, dtype=torch.int32, device=dev)
-            eps = unet.forward_cfg(x[0].reshape(B, L, 1), ts, None if cond_all is None else cond_all[:B], cfg_weight)
-            eps = eps.reshape(1, B, L).expand(K, -1, -1).contiguous()
-        else:
-            ts = torch.full((K * B,), t, dtype=torch.int32, device=dev)
-            eps = unet.forward_cfg(x.reshape(K * B, L, 1), ts, cond_all, cfg_weight).reshape(K, B, L)
-        g = guid.grad(x.repeat(n_obj, 1, 1), t, objectives, None, predrawn[si].reshape(-1) if is3d else None)     # (n_obj*K, B, L)
-        x = _ddim_step(x, eps, g, n_obj, sched.coefficients(t), scale, bounds)
-    return x.reshape(K, B, L, 1)
+    # K chains x n_obj gradients each, gradient chains object-major
+    out = run_chains(unet, guid, sched, noise.reshape(B, L), K, n_obj, objectives, None, predrawn if is3d else None, timesteps, [scales.pop()] * K,
+                     global_cond, cfg_weight, bounds, stepwise=python_loop)
+    return out.reshape(K, B, L, 1)

@@ -59,9 +59,7 @@ class DDIMScheduler:
         """bounds (not a diffusers argument): an edit's (lo, hi) per entry, which replace clip_sample's [-1, 1] (dgdm_amd/edit.py)."""
         if eta != 0.0:
             raise NotImplementedError("the reference always steps with eta = 0")
-        if bounds is not None:
-            return DDIMSchedulerOutput(engine.ddim_guided_step_bounded(sample, model_output, None, 0, self.coefficients(int(timestep)), 0.0, bounds))
-        return DDIMSchedulerOutput(engine.ddim_guided_step(sample, model_output, None, 0, self.coefficients(int(timestep)), 0.0))
+        return DDIMSchedulerOutput(engine.ddim_guided_step(sample, model_output, None, 0, self.coefficients(int(timestep)), 0.0, bounds))
 
     def add_noise(self, original_samples: torch.Tensor, noise: torch.Tensor, timesteps: torch.Tensor) -> torch.Tensor:
         ts = torch.unique(timesteps.detach().cpu())

@@ -1,5 +1,5 @@
 """Restatement for the edit tests: the bounded DDIM step (include/dgdm_hip.h dgdm_ddim_guided_step_bounded) in float32 numpy, one rounding
-per operation and in the kernel's order (csrc/smallnet.hip ddim_step_bounded_kernel)."""
+per operation and in the kernel's order (csrc/smallnet.hip ddim_step_kernel<true>)."""
 import numpy as np
 
 

@@ -66,7 +66,7 @@ class _Spec:
 CHAINS = [(0, 'rotate'), (1, 'convergence'), (2, 'shift_up'), (0, 'convergence'), (1, 'clockwise_left'), (2, 'rotate'), (0, 'shift_down')]
 
 
-def _fake_guided_chains(unet, guid, sched, mode, noise, chains, unguided=None, starts=None, trace=None, predrawn=None):
+def _fake_guided_chains(unet, guid, sched, mode, noise, chains, unguided=None, starts=None, trace=None, predrawn=None, **kw):
     """Stand-in for sampler.guided_chains on a box without a GPU: every chain's 'sample' is a checksum of exactly the inputs the
     real loop would consume - its object (through the local bank), its objective and its FPS start draws."""
     sweep, step = predrawn
