@@ -107,6 +107,10 @@ PROTOTYPES = {
                                                  C.POINTER(C.c_float), C.c_int, _P, _P, C.c_int64, C.c_float, _P, _P, _P]),
     "dgdm_guidance_orientation_sweep": (C.c_int, [_P, _P, _P, _P, C.c_int, _P, _P]),
     "dgdm_guidance_rollout": (C.c_int, [_P, _P, C.POINTER(C.c_int32), _P, C.POINTER(C.c_double), C.c_int, C.c_int, _P, _P, _P, _P, _P, _P]),
+    "dgdm_guidance_label": (C.c_int, [_P, _P, C.c_int64, C.POINTER(C.c_int32), C.c_int, C.c_int, C.POINTER(C.c_float), _P, C.c_int, _P, C.c_int64,
+                                      C.c_int64, _P]),
+    "dgdm_guidance_label_settled": (C.c_int, [_P, _P, C.c_int64, C.POINTER(C.c_int32), C.c_int, C.POINTER(C.c_double), C.c_int, _P, C.c_int, _P,
+                                              C.c_int64, C.c_int64, _P]),
     "dgdm_guidance_debug_rollout_table": (C.c_int, [_P, C.c_int, _P, _P, C.POINTER(C.c_int32), C.POINTER(C.c_int32), _P]),
     "dgdm_convergence_rowcoef": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int64, _P]),
     "dgdm_torch_rng_seed": (C.c_int, [_P, C.c_int64, C.c_uint64]),

@@ -85,6 +85,9 @@ struct DgdmGuidance {
     const float *rowfield = nullptr;
     int rowfield_chains = 0;
     DevBuf pos_lin, goalspecs;
+    // dgdm_guidance_label / _label_settled: the batch replicated over the objects' chains [M][B][L], score's counts and sums, the
+    // roll-out's final state, first logits and left, the per-(finger, object) settled values
+    DevBuf labelx, labelcounts, labelsums, labelfinal, labelfirst, labelleft, labelobj;
     int rolltiles_chains = 0;                // chains the tiles of the last roll-out cover (dgdm_guidance_debug_rollout_table)
     DevBuf xidx, xidxchains, xtabptrs;       // embedding-table path: row index per reference row, per-chain lookup info, per-chain table base pointers
     bool xtab_enabled = true;       // test hook: modes 1-3 read materialised rows (per-step gather kernels) instead of the embedding table
@@ -1219,6 +1222,88 @@ extern "C" int dgdm_guidance_rollout(DgdmGuidance *g, const float *x_dev, const 
         if ((rc = trunk_f16l_launch(kind, TrunkF16Mode::ForwardRowPose, p, sc, s))) return rc;
         if ((rc = rollout_update(p.logits, scale, k, rows, state, left_dev, traj_pose_dev ? traj_pose_dev + (size_t)(k + 1) * rows * 3 : nullptr,
                                  k == K - 1 ? final_dev : nullptr, k == 0 ? first_logits_dev : nullptr, s)))
+            return rc;
+    }
+    return DGDM_OK;
+}
+
+// ================================================================================================ condition rows
+// One pass over a set of fingers (include/dgdm_hip.h): per batch a replication copy, dgdm_guidance_score / dgdm_guidance_rollout on the
+// handle's scratch, and label.hip's reduction into the caller's rows - all on the caller's stream, which orders the batches' reuse of
+// the scratch.  Everything is checked here before the first launch; the trunk is the two calls' own.
+namespace {
+int label_check(const char *what, DgdmGuidance *g, const float *fingers_dev, int64_t n_fingers, const int32_t *objects_host, int n_objects,
+                const int64_t *starts_host, int layout, const float *rows_dev, int64_t row_stride, int64_t object_stride, int cols) {
+    DGDM_REQUIRE(g && fingers_dev && objects_host && rows_dev, DGDM_EINVAL, "%s: null argument", what);
+    DGDM_REQUIRE(n_fingers >= 1, DGDM_EINVAL, "%s: %lld fingers (at least 1)", what, (long long)n_fingers);
+    DGDM_REQUIRE(!g->bf16, DGDM_EINVAL, "%s: the bf16 trunk has no forward-only form (contraction dtypes f32 / f32_f16x3 / f32_mfma)", what);
+    DGDM_REQUIRE(n_objects > 0 && n_objects <= g->cfg.max_chains, DGDM_EINVAL, "%s: n_objects %d outside 1..%d", what, n_objects, g->cfg.max_chains);
+    DGDM_REQUIRE(layout == DGDM_LABEL_MEAN || layout == DGDM_LABEL_PER_OBJECT, DGDM_EINVAL, "%s: layout %d (0 mean, 1 per object)", what, layout);
+    if (layout == DGDM_LABEL_PER_OBJECT) {
+        DGDM_REQUIRE(object_stride >= cols, DGDM_EINVAL, "%s: object_stride %lld holds no block of %d columns", what, (long long)object_stride, cols);
+        DGDM_REQUIRE(row_stride >= (int64_t)(n_objects - 1) * object_stride + cols, DGDM_EINVAL, "%s: row_stride %lld holds no %d blocks %lld apart", what,
+                     (long long)row_stride, n_objects, (long long)object_stride);
+    } else {
+        DGDM_REQUIRE(row_stride >= cols, DGDM_EINVAL, "%s: row_stride %lld holds no %d columns", what, (long long)row_stride, cols);
+    }
+    DGDM_REQUIRE(g->m->kind == 2 || starts_host, DGDM_EINVAL, "%s: 3-D labelling needs the FPS start indices", what);
+    return g->check_objects(objects_host, n_objects);
+}
+}  // namespace
+
+extern "C" int dgdm_guidance_label(DgdmGuidance *g, const float *fingers_dev, int64_t n_fingers, const int32_t *objects_host, int n_objects,
+                                   int timestep, const float thr[3], const int64_t *starts_host, int layout, float *rows_dev, int64_t row_stride,
+                                   int64_t object_stride, void *stream) {
+    int rc;
+    if ((rc = label_check("dgdm_guidance_label", g, fingers_dev, n_fingers, objects_host, n_objects, starts_host, layout, rows_dev, row_stride,
+                          object_stride, DGDM_LABEL_TALLY_COLS)))
+        return rc;
+    DGDM_REQUIRE(thr, DGDM_EINVAL, "dgdm_guidance_label: null argument");
+    hipStream_t s = (hipStream_t)stream;
+    const int B = g->B, L = g->m->L, M = n_objects;
+    if ((rc = g->labelx.alloc((size_t)M * B * L * sizeof(float))) || (rc = g->labelcounts.alloc((size_t)M * B * 27 * sizeof(int32_t))) ||
+        (rc = g->labelsums.alloc((size_t)M * B * 4 * sizeof(float))))
+        return rc;
+    const int64_t per_batch = (int64_t)M * dgdm_guidance_starts_per_call(g);
+    for (int64_t first = 0, k = 0; first < n_fingers; first += B, ++k) {
+        const int nvalid = (int)std::min<int64_t>(B, n_fingers - first);
+        if ((rc = label_replicate(fingers_dev, n_fingers, first, M, B, L, g->labelx.as<float>(), s))) return rc;
+        if ((rc = dgdm_guidance_score(g, g->labelx.as<float>(), timestep, objects_host, starts_host ? starts_host + k * per_batch : nullptr, thr, M, nullptr,
+                                      g->labelcounts.as<int32_t>(), g->labelsums.as<float>(), s)))
+            return rc;
+        if ((rc = label_tally(g->labelcounts.as<int32_t>(), g->labelsums.as<float>(), M, B, nvalid, g->grid.cells, layout == DGDM_LABEL_PER_OBJECT,
+                              rows_dev + first * row_stride, row_stride, object_stride, s)))
+            return rc;
+    }
+    return DGDM_OK;
+}
+
+extern "C" int dgdm_guidance_label_settled(DgdmGuidance *g, const float *fingers_dev, int64_t n_fingers, const int32_t *objects_host, int n_objects,
+                                           const double scale[3], int n_interactions, const int64_t *starts_host, int layout, float *rows_dev,
+                                           int64_t row_stride, int64_t object_stride, void *stream) {
+    int rc;
+    if ((rc = label_check("dgdm_guidance_label_settled", g, fingers_dev, n_fingers, objects_host, n_objects, starts_host, layout, rows_dev, row_stride,
+                          object_stride, DGDM_LABEL_SETTLED_COLS)))
+        return rc;
+    DGDM_REQUIRE(scale, DGDM_EINVAL, "dgdm_guidance_label_settled: null argument");
+    DGDM_REQUIRE(!g->f32_mfma, DGDM_EINVAL, "dgdm_guidance_label_settled: the float32 MFMA trunk has no per-row pose form (contraction dtypes f32 / f32_f16x3)");
+    DGDM_REQUIRE(n_interactions >= 1, DGDM_EINVAL, "dgdm_guidance_label_settled: %d interactions (at least 1)", n_interactions);
+    hipStream_t s = (hipStream_t)stream;
+    const int B = g->B, L = g->m->L, M = n_objects, G = g->sweep.cells;
+    const size_t rows = (size_t)M * g->sweep.rows;
+    if ((rc = g->labelx.alloc((size_t)M * B * L * sizeof(float))) || (rc = g->labelfinal.alloc(rows * 3 * sizeof(double))) ||
+        (rc = g->labelfirst.alloc(rows * 3 * sizeof(float))) || (rc = g->labelleft.alloc(rows * sizeof(int32_t))) ||
+        (rc = g->labelobj.alloc((size_t)B * M * 6 * sizeof(double))))
+        return rc;
+    const int64_t per_batch = g->m->kind == 3 ? (int64_t)n_interactions * M * 2 * g->sweep.rows : 0;
+    for (int64_t first = 0, k = 0; first < n_fingers; first += B, ++k) {
+        const int nvalid = (int)std::min<int64_t>(B, n_fingers - first);
+        if ((rc = label_replicate(fingers_dev, n_fingers, first, M, B, L, g->labelx.as<float>(), s))) return rc;
+        if ((rc = dgdm_guidance_rollout(g, g->labelx.as<float>(), objects_host, starts_host ? starts_host + k * per_batch : nullptr, scale, n_interactions, M,
+                                        g->labelfinal.as<double>(), g->labelfirst.as<float>(), g->labelleft.as<int32_t>(), nullptr, nullptr, s)))
+            return rc;
+        if ((rc = label_settled(g->labelfinal.as<double>(), g->labelleft.as<int32_t>(), M, B, G, nvalid, layout == DGDM_LABEL_PER_OBJECT,
+                                g->labelobj.as<double>(), rows_dev + first * row_stride, row_stride, object_stride, s)))
             return rc;
     }
     return DGDM_OK;

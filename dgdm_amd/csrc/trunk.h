@@ -93,6 +93,17 @@ int rollout_update(const float *logits, const double scale[3], int k, int64_t ro
 // sums [n_chains][B][4] = sum d0, sum |d0|, sum d1, sum d2.  Fixed reduction order: the same bits every run.
 int score_tally(const float *logits, int n_chains, int B, int C, const float thr[3], int32_t *counts, float *sums, hipStream_t s);
 
+// Condition rows (label.hip; the columns are the header's, dgdm_guidance_label / dgdm_guidance_label_settled).
+// label_replicate: dst [n_chains][B][L] = fingers first .. first + B - 1 of [N][L] for every chain, past the end copies of finger N - 1.
+int label_replicate(const float *fingers, int64_t N, int64_t first, int n_chains, int B, int L, float *dst, hipStream_t s);
+// label_tally: score_tally's counts / sums of M chains -> the 10 tally columns of the batch's first nvalid fingers; rows points at the
+// first of them.  per_object: M blocks object_stride apart, else one block over all M chains.
+int label_tally(const int32_t *counts, const float *sums, int M, int B, int nvalid, int64_t cells, int per_object, float *rows, int64_t row_stride,
+                int64_t object_stride, hipStream_t s);
+// label_settled: a roll-out's final state [M][B * G][3] and left [M][B * G] -> the 5 settled columns; per_obj: scratch [B][M][6] doubles.
+int label_settled(const double *final_state, const int32_t *left, int M, int B, int G, int nvalid, int per_object, double *per_obj, float *rows,
+                  int64_t row_stride, int64_t object_stride, hipStream_t s);
+
 // Goal field (goal.hip): field [n_chains][R][3], row r = cell * B + b, cell = (g * P + px) * P + py, from the float32 grids ori_grid [G] /
 // pos_grid [P], the goals [n_chains][B][3] and one (validated) spec per chain, all on the device; the definitions are the header's.
 int goal_field_build(const float *ori_grid, const float *pos_grid, const float *goals, const DgdmGoalSpec *specs, int n_chains, int B, int G, int P,

@@ -61,6 +61,14 @@ _FLAGS = [
                                "net on the all-zero condition row (1: the plain conditional eps, 0: the unconditional one)"),
     ("cond_drop_prob", float, 0.0, "with --global_cond, --mode=train: probability with which a training sample sees the all-zero condition row instead of "
                                    "its own (what classifier-free guidance needs the net to have learnt)"),
+    ("label_out", str, None, "generator, --mode=label: FILE.npy the standardised condition rows of all --num_fingers dataset fingers are written to, "
+                             "as --global_cond takes them; FILE_raw.npy (raw units) and FILE.json (the statistics, --cond_stats) go beside it "
+                             "(dgdm_amd/label.py; needs --classifier_guidance: the labels are the dynamics model's predictions)"),
+    ("label_layout", str, "mean", "with --mode=label: 'mean' (one block of columns, averaged over the objects) or 'per_object' (one block per object)"),
+    ("label_rollout", int, 0, "with --mode=label: K > 0 adds the five settled columns of a predicted roll-out of K interactions"),
+    ("cond_stats", str, None, "generator, --mode=test: the FILE.json a labelling run wrote; with --cond_target the eps-net is built with its width"),
+    ("cond_target", str, None, "with --cond_stats: NAME=VALUE,... in raw units (e.g. frac_clockwise=0.9,frac_up=0.7); every batch is sampled under "
+                               "that condition row, columns not named at the dataset mean"),
     ("edit_from", str, None, "generator, --mode=test: FILE.npy of designs (n, L) or (n, L, 1) in sampler units, n >= batch_size (e.g. a vis_guided/<tag>/<obj>.npy "
                              "of an earlier run); batch b edits rows [b B, (b + 1) B): the guided chains of the sweep start from these designs instead of "
                              "from noise and are written under vis_edit/ (dgdm_amd/edit.py)"),

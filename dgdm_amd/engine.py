@@ -471,6 +471,63 @@ class Guidance:
         check(lib().dgdm_guidance_rollout(self._h, dptr(x), oc, sp, scale, K, nc, dptr(final), dptr(first), dptr(left), dptr(tp), dptr(tl), stream_ptr()))
         return (final, first, left, tp, tl) if want_trajectory else (final, first, left)
 
+    LABEL_LAYOUTS = {"mean": 0, "per_object": 1}
+
+    def _label_args(self, fingers, objects, layout, out, cols, column_offset, object_stride):
+        """Shared front of label() / label_settled(): the fingers (N, L), the object array, the layout code, the rows matrix (a new
+        (N, cols or M * cols) one unless `out` is given) and the pointer of its first written float."""
+        x = _f32(fingers)
+        x = x.reshape(x.shape[0], -1)
+        if layout not in self.LABEL_LAYOUTS:
+            raise ValueError(f"label layout {layout!r} not supported ('mean' or 'per_object')")
+        M = len(objects)
+        oc = (C.c_int32 * max(M, 1))(*[int(o) for o in objects])
+        if object_stride is None:
+            object_stride = cols
+        if out is None:
+            out = torch.empty((x.shape[0], cols if layout == "mean" else M * cols), dtype=torch.float32, device=x.device)
+        if not (out.is_cuda and out.dtype == torch.float32 and out.dim() == 2 and out.is_contiguous() and out.shape[0] == x.shape[0]):
+            raise ValueError(f"label rows: a contiguous float32 device matrix of {x.shape[0]} rows expected, got {tuple(out.shape)} {out.dtype}")
+        need = cols if layout == "mean" else (M - 1) * int(object_stride) + cols
+        if column_offset < 0 or column_offset + max(need, cols) > out.shape[1]:
+            raise ValueError(f"label rows: {need} floats from column {column_offset} do not fit rows of {out.shape[1]}")
+        return x, oc, M, self.LABEL_LAYOUTS[layout], out, out.data_ptr() + 4 * int(column_offset), int(out.shape[1]), int(object_stride)
+
+    def label(self, fingers: torch.Tensor, objects: Sequence[int], threshold_std: Sequence[float], timestep: int = 0,
+              starts: Optional[np.ndarray] = None, layout: str = "mean", out: Optional[torch.Tensor] = None, column_offset: int = 0,
+              object_stride: Optional[int] = None) -> torch.Tensor:
+        """The tally columns of every finger (include/dgdm_hip.h, dgdm_guidance_label): fingers (N, L) in sampler units, any N, labelled
+        in batches of the handle's B against `objects` -> rows (N, 10) ('mean') or (N, M * 10) ('per_object').  out / column_offset /
+        object_stride: write into a wider matrix instead (row stride = its width).  3-D: starts (n_batches, M, starts_per_call) int64."""
+        x, oc, M, lay, out, ptr, stride, ostride = self._label_args(fingers, objects, layout, out, 10, column_offset, object_stride)
+        thr = (C.c_float * 3)(*[float(v) for v in threshold_std])
+        sp = None
+        if self.dyn.kind == 3:
+            nb = -(-x.shape[0] // self.cfg.batch)
+            assert starts is not None and starts.dtype == np.int64 and starts.size == nb * M * self.starts_per_call
+            starts = np.ascontiguousarray(starts)
+            sp = starts.ctypes.data
+        check(lib().dgdm_guidance_label(self._h, dptr(x), x.shape[0], oc, M, int(timestep), thr, sp, lay, ptr, stride, ostride, stream_ptr()))
+        return out
+
+    def label_settled(self, fingers: torch.Tensor, objects: Sequence[int], std: Sequence[float], n_interactions: int,
+                      starts: Optional[np.ndarray] = None, layout: str = "mean", out: Optional[torch.Tensor] = None, column_offset: int = 0,
+                      object_stride: Optional[int] = None) -> torch.Tensor:
+        """The settled columns of every finger from roll-outs of n_interactions (dgdm_guidance_label_settled) -> rows (N, 5) or
+        (N, M * 5); placement as label().  std as rollout() takes it.  3-D: starts (n_batches, K, M, 2*B*G) int64."""
+        from .dynamics.dataloader import POS_NORM
+        x, oc, M, lay, out, ptr, stride, ostride = self._label_args(fingers, objects, layout, out, 5, column_offset, object_stride)
+        K = int(n_interactions)
+        scale = (C.c_double * 3)(float(std[0]) / np.pi, float(std[1]) / POS_NORM, float(std[2]) / POS_NORM)
+        sp = None
+        if self.dyn.kind == 3:
+            nb = -(-x.shape[0] // self.cfg.batch)
+            assert starts is not None and starts.dtype == np.int64 and starts.size == nb * max(K, 0) * M * 2 * self.sweep_rows
+            starts = np.ascontiguousarray(starts)
+            sp = starts.ctypes.data
+        check(lib().dgdm_guidance_label_settled(self._h, dptr(x), x.shape[0], oc, M, scale, K, sp, lay, ptr, stride, ostride, stream_ptr()))
+        return out
+
     def debug_rollout_table(self, n_chains: int):
         """Test hook: (layer 1's pose term of the last rollout()'s last interaction as operand tiles (n_chains, B, tiles_per_finger,
         W1 * 32), the sweep's own table in the same layout (tiles_per_finger, W1 * 32))."""

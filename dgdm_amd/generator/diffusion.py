@@ -141,6 +141,9 @@ class Diffusion(nn.Module):
         # edit the plan's designs instead of starting from noise and are emitted under vis_edit/ (the unguided loops are untouched)
         self.edit_plan = None
         self._edit_source_sim = None
+        # nor this: (label.LabelStats, {column: raw value}) of --cond_stats / --cond_target.  The batches then arrive with the target row
+        # as their condition, and validation_step reports what the unguided samples achieve under it (res['cond_target'])
+        self.cond_target = None
         if class_cond:
             self.classifier_model = classifier_model
             self.grid_size, self.num_pos = grid_size, num_pos
@@ -607,6 +610,8 @@ class Diffusion(nn.Module):
         if rank0:
             self._emit(self.save_dir, 'val_vis_noise', 'unguided', unguided[None], ["unguided"])
         out["unguided"] = unguided
+        if getattr(self, "cond_target", None) is not None:
+            out["cond_target"] = self._cond_target_report(unguided, B, rank0)
         if self.class_cond:
             if self.object_vertices is None:
                 raise ValueError('object vertices not provided')
@@ -631,6 +636,34 @@ class Diffusion(nn.Module):
             with self._draw_ahead(B, edit):
                 self._objective_sweep(out, batch_idx, B, noise, unguided, sim_unguided, tables, imgs, cond)
         return out
+
+    def _cond_target_report(self, unguided, B: int, rank0: bool) -> Dict[str, Any]:
+        """--cond_target: what was asked and - with a dynamics model - what the unguided samples achieve, labelled by the recipe stored in
+        the statistics (dgdm_amd/label.py), all in raw units: columns, requested {column: value}, achieved_mean / achieved_std over the
+        batch (None when nothing scores them), baseline_mean = the dataset mean.  The dynamics model's opinion: 'predicted': True."""
+        from .. import label as lb
+        stats, requested = self.cond_target
+        rep: Dict[str, Any] = {"columns": list(stats.columns), "requested": dict(requested), "achieved_mean": None, "achieved_std": None,
+                               "baseline_mean": stats.mean.copy(), "predicted": True}
+        if not self.class_cond or self.object_vertices is None:
+            if rank0:
+                print("[dgdm_amd] --cond_target: no dynamics model in this run (--classifier_guidance): the achieved values were not scored", flush=True)
+            return rep
+        objs = torch.as_tensor(self.object_vertices)
+        r, M = stats.recipe, objs.shape[0]
+        if r.get("G") != self.grid_size or r.get("P") != self.num_pos or M != len(stats.object_ids):
+            raise ValueError(f"cond target: the rows were labelled on a {r.get('G')} x {r.get('P')}^2 grid against {len(stats.object_ids)} objects, "
+                             f"this run has {self.grid_size} x {self.num_pos}^2 and {M}")
+        g = self._guidance_for(B, r.get("ori_range") or [-1.0, 1.0], objs, M)
+        raw = lb.label_fingers(g, unguided.detach(), list(range(M)), r["threshold_std"], std=r.get("score_std"), rollout=int(r.get("K") or 0),
+                               layout=stats.layout, timestep=int(r.get("timestep") or 0), seed=int(r.get("seed") or 0)).cpu().numpy().astype(np.float64)
+        rep["achieved_mean"], rep["achieved_std"] = raw.mean(axis=0), raw.std(axis=0)
+        if rank0:
+            cols = ["column", "requested", "achieved_mean", "achieved_std", "baseline_mean", "objective"]
+            data = [[c, requested.get(c), rep["achieved_mean"][i], rep["achieved_std"][i], stats.mean[i], {"predicted": True}]
+                    for i, c in enumerate(stats.columns)]
+            self._tables(self.save_dir).log_table("val/cond_target/unguided_sample", cols, data)
+        return rep
 
     def _draw_ahead(self, B: int, edit=None):
         """The FPS start draws of the whole objective sweep, made ahead of the launches on a worker thread (sampler.StartPlan): they

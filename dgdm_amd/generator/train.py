@@ -11,6 +11,9 @@ fingers, which is what Lightning's ``trainer.validate`` does (:152-156).  ``--mo
 
 Not the reference's: ``--edit_from FILE.npy`` (with ``--pin``, ``--edit_band_mm``, ``--edit_steps``; dgdm_amd/edit.py) makes the guided
 chains of the test-mode sweep edit the file's designs - batch b its rows [b B, (b + 1) B) - instead of starting from noise.
+``--mode=label --label_out rows.npy`` labels all dataset fingers with the dynamics model's predictions (dgdm_amd/label.py; no eps-net is
+built) and writes the rows ``--global_cond`` takes, the raw rows and their statistics; ``--mode=test --cond_stats rows.json --cond_target
+NAME=VALUE,...`` samples every batch under the target row those statistics make of raw units.
 
 Assets the image does not have are substituted, loudly:
 * no checkpoint files  -> deterministic random-init weights (dgdm_amd.synth).
@@ -92,8 +95,86 @@ def check_cond_flags(args) -> None:
         raise ValueError(f"--cfg_weight={args.cfg_weight}: not a finite number")
     if not 0.0 <= p < 1.0:
         raise ValueError(f"--cond_drop_prob={args.cond_drop_prob}: a probability in [0, 1)")
-    if args.global_cond is None and (w != 1.0 or p != 0.0):
+    if args.global_cond is None and getattr(args, "cond_target", None) is None and (w != 1.0 or p != 0.0):
         raise ValueError("--cfg_weight / --cond_drop_prob need --global_cond: an unconditional eps-net has nothing to mix or drop")
+
+
+def check_label_flags(args):
+    """--mode=label and --cond_stats / --cond_target, checked before anything is built: returns (LabelStats, requested target by column)
+    of a targeted test run, else (None, None).  ValueError for every combination that cannot run."""
+    from .. import dist as ddist
+    from .. import label as lb
+    target, stats_path = getattr(args, "cond_target", None), getattr(args, "cond_stats", None)
+    if args.mode == 'label':
+        if not args.label_out:
+            raise ValueError("--mode=label needs --label_out FILE.npy")
+        if not args.classifier_guidance:
+            raise ValueError("--mode=label needs --classifier_guidance and its flags: the labels are the dynamics model's predictions")
+        if args.label_layout not in lb.LAYOUTS:
+            raise ValueError(f"--label_layout={args.label_layout}: 'mean' or 'per_object'")
+        if int(args.label_rollout) < 0:
+            raise ValueError(f"--label_rollout={args.label_rollout}: the number of interactions cannot be negative")
+        if target is not None or stats_path is not None or args.global_cond is not None:
+            raise ValueError("--mode=label writes condition rows; --global_cond / --cond_stats / --cond_target read them (--mode=train / test)")
+        if max(ddist.world_rank()[0], int(os.environ.get("WORLD_SIZE", "1"))) > 1:      # torchrun, joined or not yet
+            raise ValueError("--mode=label runs in one process: sharded labelling is not supported")
+        return None, None
+    if args.label_out:
+        raise ValueError("--label_out needs --mode=label")
+    if target is None and stats_path is None:
+        return None, None
+    if target is not None and stats_path is None:
+        raise ValueError("--cond_target needs --cond_stats FILE.json: a target in raw units is standardised with the labelling run's statistics")
+    if target is None:
+        raise ValueError("--cond_stats needs --cond_target: the statistics only turn a target into a condition row")
+    if args.mode != 'test':
+        raise ValueError("--cond_target samples under a target row in --mode=test")
+    if args.global_cond is not None:
+        raise ValueError("--cond_target and --global_cond both set the condition rows of --mode=test: give one")
+    stats = lb.LabelStats.load(stats_path)
+    requested = stats.requested(lb.parse_target(target))         # an unknown column raises here
+    if args.classifier_guidance:
+        r = stats.recipe
+        if r.get("G") != args.grid_size or r.get("P") != args.num_pos:
+            raise ValueError(f"--cond_stats: the rows were labelled on a {r.get('G')} x {r.get('P')}^2 grid, this run's is {args.grid_size} x {args.num_pos}^2")
+    return stats, requested
+
+
+def _threshold_std(fingers_3d: bool):
+    """(threshold / std in float32 as Diffusion forms it, std) of the dynamics dataset (dynamics/dataloader.py)."""
+    from ..dynamics.dataloader import SCORE_STD, SCORE_THRESHOLD
+    i = 0 if fingers_3d else 1
+    thr, std = torch.tensor(SCORE_THRESHOLD[i].tolist()), torch.tensor(SCORE_STD[i].tolist())
+    return [float(v) for v in thr / std], [float(v) for v in std]
+
+
+def label_dataset(args, dataset, classifier, objects, object_ids, dev):
+    """--mode=label: every dataset finger labelled at t = 0 with the dataset's threshold / std (as PredictedSimulator scores), the rows
+    standardised and written: <label_out> (what --global_cond takes), <stem>_raw.npy, <stem>.json (LabelStats).  Returns (stats, raw)."""
+    from .. import engine
+    from .. import label as lb
+    M, K, layout = objects.shape[0], int(args.label_rollout), args.label_layout
+    lb.cond_dim(layout, M, K)                                   # more than 256 columns: ValueError before the handle is built
+    thr, std = _threshold_std(args.fingers_3d)
+    fingers = np.stack([dataset[i] for i in range(len(dataset))])
+    g = engine.Guidance(classifier.handle(), args.batch_size, args.grid_size, args.num_pos, (-1.0, 1.0), M, args.num_train_timesteps,
+                        objects.shape[1], args.sub_bs if args.fingers_3d else 0, max_objects=M)
+    g.set_objects(objects.to(dev))
+    raw = lb.label_fingers(g, torch.from_numpy(fingers), list(range(M)), thr, std=std, rollout=K, layout=layout, timestep=0, seed=int(args.seed),
+                           chunk_batches=64).cpu().numpy()
+    recipe = {"G": args.grid_size, "P": args.num_pos, "ori_range": [-1.0, 1.0], "threshold_std": thr, "score_std": std, "K": K, "timestep": 0,
+              "seed": int(args.seed), "contraction_dtype": g.contraction_dtype}
+    stats = lb.LabelStats(lb.column_names(layout, object_ids, K), layout, object_ids, recipe).fit(raw)
+    stem = args.label_out[:-4] if args.label_out.endswith(".npy") else args.label_out
+    if os.path.dirname(stem):
+        os.makedirs(os.path.dirname(stem), exist_ok=True)
+    np.save(stem + ".npy", stats.apply(raw))
+    np.save(stem + "_raw.npy", raw)
+    stats.save(stem + ".json")
+    flat = [c for c, k in zip(stats.columns, stats.constant) if k]
+    print(f"[dgdm_amd] labelled {raw.shape[0]} fingers x {raw.shape[1]} columns ({layout}, {M} objects, K = {K}) -> {stem}.npy, {stem}_raw.npy, {stem}.json"
+          + (f"; constant columns (standardised to 0): {', '.join(flat)}" if flat else ""), flush=True)
+    return stats, raw
 
 
 def _load_or_synth(path, spec, seed, what):
@@ -182,6 +263,20 @@ def _object_exporter(args):
         if refused:
             print(f"[dgdm_amd] --save_objects: {model_root}: the contours of objects {refused} cannot be meshed - left out", file=sys.stderr)
     return export
+
+
+def _classifier(args, L: int, dev):
+    """The frozen dynamics model of --classifier_guidance (generator/train.py:84-92) and the run's objects: (model, objects, object ids)."""
+    if args.fingers_3d:
+        classifier = ProfileForward3DModel(output_ch=3, params_ch=L)
+        spec = synth.dyn3d_spec(L)
+    else:
+        classifier = ProfileForward2DModel(output_ch=3, params_ch=L, object_ch=2 * args.object_max_num_vertices)
+        spec = synth.dyn2d_spec(L, 2 * args.object_max_num_vertices)
+    classifier.load_state_dict(_load_or_synth(args.checkpoint_path, spec, 22 + int(args.fingers_3d), "dynamics checkpoint"))
+    classifier.eval().requires_grad_(False).to(dev)
+    objects, object_ids = _objects(args, args.fingers_3d)
+    return classifier, objects, object_ids
 
 
 def fit(model: Diffusion, pts: np.ndarray, args, bounds, dev) -> Diffusion:
@@ -287,29 +382,29 @@ def train(args):
     pts = finger_control_points(args.num_fingers, args.fingers_3d)
     max_y, min_y = (0.0, -0.1) if args.fingers_3d else (0.015, -0.045)
     check_cond_flags(args)
+    cond_stats, cond_requested = check_label_flags(args)    # --mode=label, --cond_stats / --cond_target: refused here, before anything is built
     from ..edit import plan_from_args
     edit_plan = plan_from_args(args)        # --edit_from / --pin / --edit_band_mm / --edit_steps: read and checked before anything is built
     if edit_plan is not None and (args.mode != 'test' or not args.classifier_guidance):
         raise ValueError("--edit_from edits designs in the guided chains of --mode=test and needs --classifier_guidance")
     cond = load_global_cond(args.global_cond, args.num_fingers) if args.global_cond is not None else None
     gc = 0 if cond is None else cond.shape[1]
+    if cond_stats is not None:
+        gc = cond_stats.dim                 # --cond_target: the eps-net is as wide as the labelling run's rows
     dataset = GripperDataset(pts, 0.12, -0.12, max_y, min_y, cond=cond)
     L = args.ctrlpts_dim
+    if args.mode == 'label':                # no eps-net: the dynamics model and the objects of --classifier_guidance alone
+        classifier, objects, object_ids = _classifier(args, L, dev)
+        return label_dataset(args, dataset, classifier, objects, object_ids, dev)
     unet = ConditionalUnet1D(input_dim=1, global_cond_dim=gc, down_dims=[128, 256], diffusion_step_embed_dim=32)
     mode = 'point_3d' if args.fingers_3d else 'point'
     scheduler = DDIMScheduler(num_train_timesteps=args.num_train_timesteps, beta_schedule='squaredcos_cap_v2', clip_sample=True,
                               prediction_type='epsilon')
     classifier, objects, object_ids = None, None, None
     if args.classifier_guidance:
-        if args.fingers_3d:
-            classifier = ProfileForward3DModel(output_ch=3, params_ch=L)
-            spec = synth.dyn3d_spec(L)
-        else:
-            classifier = ProfileForward2DModel(output_ch=3, params_ch=L, object_ch=2 * args.object_max_num_vertices)
-            spec = synth.dyn2d_spec(L, 2 * args.object_max_num_vertices)
-        classifier.load_state_dict(_load_or_synth(args.checkpoint_path, spec, 22 + int(args.fingers_3d), "dynamics checkpoint"))
-        classifier.eval().requires_grad_(False).to(dev)
-        objects, object_ids = _objects(args, args.fingers_3d)
+        classifier, objects, object_ids = _classifier(args, L, dev)
+        if cond_stats is not None and objects.shape[0] != len(cond_stats.object_ids):
+            raise ValueError(f"--cond_stats: the rows were labelled against {len(cond_stats.object_ids)} objects, this run has {objects.shape[0]}")
     model = Diffusion(noise_pred_net=unet, noise_scheduler=scheduler, num_inference_steps=args.num_inference_steps, mode=mode, input_dim=1,
                       num_points=L, learning_rate=args.learning_rate, lr_warmup_steps=args.lr_warmup_steps, ema_power=args.ema_power,
                       class_cond=args.classifier_guidance, classifier_model=classifier, grid_size=args.grid_size, num_pos=args.num_pos,
@@ -356,10 +451,16 @@ def train(args):
         os.makedirs(model.save_dir, exist_ok=True)
     results = []
     n_batches = len(dataset) // args.batch_size                       # DataLoader(drop_last=True), :69
+    target_row = None
+    if cond_stats is not None:              # --cond_target: one row in the labelling run's standardised units, broadcast to every batch
+        model.cond_target = (cond_stats, cond_requested)
+        target_row = torch.from_numpy(cond_stats.target(cond_requested))[None].expand(args.batch_size, -1).contiguous()
     with torch.no_grad():
         for bi in range(n_batches):
             ids = range(bi * args.batch_size, (bi + 1) * args.batch_size)
-            if cond is None:
+            if target_row is not None:
+                batch = (torch.from_numpy(np.stack([dataset[i] for i in ids])), target_row)
+            elif cond is None:
                 batch = torch.from_numpy(np.stack([dataset[i] for i in ids]))
             else:
                 batch = (torch.from_numpy(np.stack([dataset[i][0] for i in ids])), torch.from_numpy(cond[list(ids)]))

@@ -1,0 +1,227 @@
+"""Condition rows of the eps-net made by the dynamics model: what it predicts every finger of a set does, as ``global_cond`` rows.
+
+``label_fingers`` runs ``engine.Guidance.label`` (and, with ``rollout=K``, ``label_settled``) over all fingers and returns the raw rows;
+``LabelStats`` remembers how a dataset's rows were standardised, so that a request in plain units - "clockwise on 90 % of the grid" -
+becomes a condition row at sampling time (``LabelStats.target``).  The columns are those of include/dgdm_hip.h.
+
+These labels are the dynamics model's opinion, not simulator measurements, and in 3-D they depend on the FPS start seed like every
+``cond_fn`` call.
+"""
+from __future__ import annotations
+
+import json
+from typing import Any, Dict, List, Mapping, Optional, Sequence
+
+import numpy as np
+
+TALLY_COLUMNS = ["frac_clockwise", "frac_counterclockwise", "frac_up", "frac_down", "frac_left", "frac_right",
+                 "mean_rot", "mean_abs_rot", "mean_shift_x", "mean_shift_y"]
+SETTLED_COLUMNS = ["settle_concentration", "settle_cos", "settle_sin", "settle_offset", "left_range"]
+LAYOUTS = ("mean", "per_object")
+MAX_COND_DIM = 256                 # the eps-net's global_cond_dim limit
+# what a labelling run records beside the statistics (score_std: the dataset's (rad, m, m); K: roll-out interactions)
+RECIPE_KEYS = ("G", "P", "ori_range", "threshold_std", "score_std", "K", "timestep", "seed", "contraction_dtype")
+
+_ROT_COLUMN = {"clockwise": "frac_clockwise", "counterclockwise": "frac_counterclockwise"}
+_SHIFT_COLUMN = {"up": "frac_up", "down": "frac_down", "left": "frac_left", "right": "frac_right"}
+# the 14 directional objective names -> the one or two fraction columns they ask for
+ALIASES: Dict[str, List[str]] = {}
+for _r, _rc in _ROT_COLUMN.items():
+    ALIASES[f"rotate_{_r}"] = [_rc]
+    for _s, _sc in _SHIFT_COLUMN.items():
+        ALIASES[f"{_r}_{_s}"] = [_rc, _sc]
+for _s, _sc in _SHIFT_COLUMN.items():
+    ALIASES[f"shift_{_s}"] = [_sc]
+_REFUSED = {"rotate": "'rotate' has no single column: name the two rotation fractions, frac_clockwise and frac_counterclockwise",
+            "convergence": "'convergence' is not a tally column: use settle_concentration (label with --label_rollout K)"}
+
+
+def block_columns(rollout: int) -> List[str]:
+    return TALLY_COLUMNS + (SETTLED_COLUMNS if int(rollout) > 0 else [])
+
+
+def column_names(layout: str, object_ids: Sequence[Any], rollout: int = 0) -> List[str]:
+    """The row's column names: 'mean' the 10 (+5) names, 'per_object' ``<name>@<object id>`` object after object."""
+    if layout not in LAYOUTS:
+        raise ValueError(f"label layout {layout!r} not supported ({' or '.join(LAYOUTS)})")
+    cols = block_columns(rollout)
+    if layout == "mean":
+        return list(cols)
+    return [f"{c}@{o}" for o in object_ids for c in cols]
+
+
+def cond_dim(layout: str, n_objects: int, rollout: int = 0) -> int:
+    """Width of a row; ValueError for an unknown layout or more columns than the eps-net takes."""
+    if layout not in LAYOUTS:
+        raise ValueError(f"label layout {layout!r} not supported ({' or '.join(LAYOUTS)})")
+    gc = len(block_columns(rollout)) * (1 if layout == "mean" else int(n_objects))
+    if gc > MAX_COND_DIM:
+        raise ValueError(f"label rows of {gc} columns ({n_objects} objects, layout {layout!r}): the eps-net takes at most {MAX_COND_DIM}")
+    return gc
+
+
+def label_fingers(guidance, fingers, objects: Sequence[int], threshold_std: Sequence[float], std: Optional[Sequence[float]] = None,
+                  rollout: int = 0, layout: str = "mean", timestep: int = 0, seed: int = 0, chunk_batches: Optional[int] = None):
+    """Raw rows (N, gc) float32 on the device for fingers (N, L[, 1]) in sampler units: gc = 10 (+5 with rollout = K > 0) for 'mean',
+    M times that for 'per_object' (per object the tally block, then the settled block).  objects: indices into the handle's bank.
+    3-D: the FPS start draws come from ``sampler.TorchRng(seed)``, batch after batch (a batch's tally draws, then its roll-out's);
+    chunk_batches bounds how many batches' draws are held at once and does not change the rows.  A non-finite settled state raises
+    ValueError naming the finger."""
+    import torch
+    from . import sampler
+    K, M = int(rollout), len(objects)
+    if K < 0:
+        raise ValueError(f"label_fingers: rollout = {rollout} is negative")
+    if K and std is None:
+        raise ValueError("label_fingers: rollout needs std, the dataset's (rad, m, m)")
+    gc = cond_dim(layout, M, K)
+    x = torch.as_tensor(fingers).detach().to(device=torch.device("cuda", torch.cuda.current_device()), dtype=torch.float32)
+    x = x.reshape(x.shape[0], -1).contiguous()
+    N, B = x.shape[0], guidance.cfg.batch
+    if N < 1:
+        raise ValueError("label_fingers: no fingers")
+    nb = -(-N // B)
+    per = len(block_columns(K))
+    rows = torch.empty((N, gc), dtype=torch.float32, device=x.device)
+    three_d = guidance.dyn.kind == 3
+    rng = sampler.TorchRng(seed=int(seed)) if three_d else None
+    chunk = nb if not chunk_batches or not three_d else max(1, int(chunk_batches))
+    for k0 in range(0, nb, chunk):
+        k1 = min(nb, k0 + chunk)
+        f0, f1 = k0 * B, min(N, k1 * B)
+        st_t = st_s = None
+        if three_d:
+            pts, sub = guidance.cfg.num_object_points, guidance.cfg.sub_batch_size
+            st_t = np.empty((k1 - k0, M, guidance.starts_per_call), dtype=np.int64)
+            st_s = np.empty((k1 - k0, K, M, 2 * guidance.sweep_rows), dtype=np.int64) if K else None
+            for k in range(k1 - k0):
+                rng.fps_starts(pts, sub, guidance.rows, n_calls=M, out=st_t[k])
+                if K:
+                    rng.fps_starts(pts, sub, guidance.sweep_rows, n_calls=K * M, out=st_s[k].reshape(K * M, -1))
+        # the last chunk's padding repeats finger N - 1 of the WHOLE set, which is also the chunk's last finger
+        part = rows[f0:f1]
+        guidance.label(x[f0:f1], objects, threshold_std, timestep=timestep, starts=st_t, layout=layout, out=part, column_offset=0, object_stride=per)
+        if K:
+            guidance.label_settled(x[f0:f1], objects, std, K, starts=st_s, layout=layout, out=part, column_offset=10, object_stride=per)
+    if K:
+        bad = torch.isnan(rows).any(dim=1)
+        if bool(bad.any()):
+            raise ValueError(f"label_fingers: the roll-out of finger {int(torch.nonzero(bad)[0])} reached a non-finite state (its settled columns are NaN)")
+    return rows
+
+
+def parse_target(text: str) -> Dict[str, float]:
+    """``"frac_clockwise=0.9,frac_up=0.7"`` -> {'frac_clockwise': 0.9, 'frac_up': 0.7}; ValueError on anything else."""
+    out: Dict[str, float] = {}
+    for item in str(text).split(","):
+        name, eq, val = item.partition("=")
+        name = name.strip()
+        try:
+            v = float(val)
+        except ValueError:
+            v = float("nan")
+        if not eq or not name or not np.isfinite(v):
+            raise ValueError(f"--cond_target: '{item.strip()}' is not NAME=NUMBER")
+        if name in out:
+            raise ValueError(f"--cond_target: '{name}' is set twice")
+        out[name] = v
+    return out
+
+
+class LabelStats:
+    """How a dataset's raw label rows were standardised, and the recipe that made them.  ``fit(raw)`` -> per-column mean and std in
+    numpy float64 (a column of std 0 is flagged in ``constant`` and standardises to 0); ``apply(raw)`` -> float32 ``(v - mean) / std``;
+    ``target({...})`` -> one row for sampling; ``save`` / ``load``: a JSON file."""
+
+    def __init__(self, columns: Sequence[str], layout: str = "mean", object_ids: Sequence[Any] = (), recipe: Optional[Mapping[str, Any]] = None):
+        if layout not in LAYOUTS:
+            raise ValueError(f"label layout {layout!r} not supported ({' or '.join(LAYOUTS)})")
+        self.columns = [str(c) for c in columns]
+        self.layout = layout
+        self.object_ids = list(object_ids)
+        self.recipe: Dict[str, Any] = dict(recipe or {})
+        n = len(self.columns)
+        self.mean, self.std = np.zeros(n), np.ones(n)
+        self.min, self.max = np.zeros(n), np.zeros(n)
+
+    @property
+    def dim(self) -> int:
+        return len(self.columns)
+
+    @property
+    def constant(self) -> np.ndarray:
+        return self.std == 0.0
+
+    def fit(self, raw) -> "LabelStats":
+        r = np.asarray(raw, dtype=np.float64)
+        if r.ndim != 2 or r.shape[1] != self.dim or r.shape[0] < 1:
+            raise ValueError(f"LabelStats.fit: rows of shape {r.shape} for {self.dim} columns")
+        if not np.isfinite(r).all():
+            raise ValueError(f"LabelStats.fit: non-finite value in row {int(np.argwhere(~np.isfinite(r))[0][0])}")
+        self.mean, self.std = r.mean(axis=0), r.std(axis=0)
+        self.min, self.max = r.min(axis=0), r.max(axis=0)
+        return self
+
+    def _standardise(self, r: np.ndarray) -> np.ndarray:
+        safe = np.where(self.constant, 1.0, self.std)
+        return np.where(self.constant, 0.0, (r - self.mean) / safe)
+
+    def apply(self, raw) -> np.ndarray:
+        r = np.asarray(raw, dtype=np.float64)
+        if r.ndim != 2 or r.shape[1] != self.dim:
+            raise ValueError(f"LabelStats.apply: rows of shape {r.shape} for {self.dim} columns")
+        return self._standardise(r).astype(np.float32)
+
+    def resolve(self, name: str) -> List[int]:
+        """The column indices a target name sets: a column, a bare name (every object's column in 'per_object'), an objective alias."""
+        if name in _REFUSED:
+            raise ValueError(f"cond target: {_REFUSED[name]}")
+        if name in self.columns:
+            return [self.columns.index(name)]
+        bare, at, obj = name.partition("@")
+        names = ALIASES.get(bare, [bare])
+        idx = [i for n in names for i, c in enumerate(self.columns) if c == (f"{n}@{obj}" if at else n) or (not at and c.startswith(n + "@"))]
+        if not idx or any(n not in TALLY_COLUMNS + SETTLED_COLUMNS for n in names):
+            raise ValueError(f"cond target: unknown column '{name}' (columns: {', '.join(self.columns[:15])}{', ...' if self.dim > 15 else ''}; "
+                             f"objective aliases: {', '.join(sorted(ALIASES))})")
+        return idx
+
+    def requested(self, target: Mapping[str, float]) -> Dict[str, float]:
+        """The target by column name, in raw units, aliases and bare names resolved."""
+        out: Dict[str, float] = {}
+        for name, v in target.items():
+            for i in self.resolve(str(name)):
+                out[self.columns[i]] = float(v)
+        return out
+
+    def target(self, target: Mapping[str, float]) -> np.ndarray:
+        """One float32 row (dim,): the named columns standardised from raw units, every other column 0 - the dataset mean."""
+        raw = self.mean.copy()
+        for c, v in self.requested(target).items():
+            raw[self.columns.index(c)] = v
+        return self._standardise(raw[None])[0].astype(np.float32)
+
+    def to_dict(self) -> Dict[str, Any]:
+        return {"columns": self.columns, "mean": self.mean.tolist(), "std": self.std.tolist(), "min": self.min.tolist(), "max": self.max.tolist(),
+                "layout": self.layout, "object_ids": [o.item() if isinstance(o, np.generic) else o for o in self.object_ids],
+                **{k: self.recipe.get(k) for k in RECIPE_KEYS},
+                "predicted": True}
+
+    def save(self, path: str) -> None:
+        with open(path, "w") as f:
+            json.dump(self.to_dict(), f, indent=1)
+
+    @classmethod
+    def load(cls, path: str) -> "LabelStats":
+        try:
+            with open(path) as f:
+                d = json.load(f)
+            s = cls(d["columns"], d["layout"], d["object_ids"],
+                    {k: d.get(k) for k in RECIPE_KEYS})
+            s.mean, s.std = np.asarray(d["mean"], dtype=np.float64), np.asarray(d["std"], dtype=np.float64)
+            s.min, s.max = np.asarray(d["min"], dtype=np.float64), np.asarray(d["max"], dtype=np.float64)
+        except (OSError, KeyError, TypeError, ValueError) as e:
+            raise ValueError(f"--cond_stats: cannot read '{path}' as label statistics ({type(e).__name__}: {e})")
+        if not (len(s.mean) == len(s.std) == len(s.min) == len(s.max) == s.dim) or not 1 <= s.dim <= MAX_COND_DIM:
+            raise ValueError(f"--cond_stats: '{path}' holds {s.dim} columns and statistics of {len(s.mean)}, {len(s.std)}, {len(s.min)}, {len(s.max)} entries")
+        return s

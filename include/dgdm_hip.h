@@ -350,6 +350,50 @@ int dgdm_guidance_rollout(DgdmGuidance *g, const float *x_dev, const int32_t *ob
                           const double scale[3], int n_interactions, int n_chains, double *final_dev, float *first_logits_dev,
                           int32_t *left_dev, double *traj_pose_dev, float *traj_logits_dev, void *stream);
 
+/* Condition rows of the eps-net (global_cond) from the dynamics model: one pass that labels every finger of a set with what the model
+ * predicts it does - the model's opinion, not a simulator's.  Two runners over the two calls above.
+ * Batching (both).  fingers_dev [n_fingers][L] in sampler units, any n_fingers >= 1.  With B the handle's batch, batch k holds fingers
+ *   k*B .. min((k+1)*B, N) - 1; the last batch is padded to B with copies of finger N - 1 (padding rows are computed and thrown away).
+ *   Every batch is evaluated as n_objects chains that all hold the same [B][L] block (a small device copy replicates it), chain m facing
+ *   object objects_host[m].  starts_host, 3-D: label [n_batches][n_objects][starts_per_call], settled [n_batches][K][n_objects][2*B*G] -
+ *   each batch's slice exactly what dgdm_guidance_score / dgdm_guidance_rollout take, uploaded as they upload it; 2-D: NULL.  All batches
+ *   are enqueued on `stream`; in 2-D the host does not wait between batches.  Scratch is the handle's; like score, the calls leave the
+ *   results of dgdm_dyn{2,3}d_guidance_grad untouched.
+ * Placement.  Row i starts at rows_dev + i*row_stride.  layout DGDM_LABEL_MEAN: the 10 (5) columns are written there.
+ *   DGDM_LABEL_PER_OBJECT: object m's block starts m*object_stride floats further on (object_stride = 15 interleaves a tally and a
+ *   settled block per object).  Floats of the row that belong to neither block are not written.
+ * Tally columns (dgdm_guidance_label).  Row i holds, bit for bit, these functions of what dgdm_guidance_score returns for i's padded
+ *   batch with the same thr, timestep, objects and start slice: per object m the histogram c_m[3][3][3] (bin = (class d0 * 3 + class d1)
+ *   * 3 + class d2) and s_m[4]; n = G*P*P; M' = n_objects (MEAN) or 1 (PER_OBJECT).
+ *     0 frac_clockwise (d0 class 0)   1 frac_counterclockwise (d0 class 2)   2 frac_up (d1 class 0)   3 frac_down (d1 class 2)
+ *     4 frac_left (d2 class 0)        5 frac_right (d2 class 2)
+ *       each float32(double(K) / double(M' * n)), K the marginal count summed in int64 over the block's objects;
+ *     6 mean_rot   7 mean_abs_rot   8 mean_shift_x   9 mean_shift_y
+ *       each float32((sum over m ascending of double(s_m[j])) / double(M' * n)), j = 0..3, in the model's normalised units.
+ *   One IEEE division and one rounding per value.
+ * Settled columns (dgdm_guidance_label_settled).  From what dgdm_guidance_rollout returns for the padded batch (final [M][B*G][3]
+ *   float64 and left; finger b's rows are r = g*B + b), per object, everything in double with g ascending, no product fused into a sum:
+ *     theta_g = M_PI * (ori_g + 1.0); c = (sum cos theta_g) / G; s = (sum sin theta_g) / G; rho = sqrt(c*c + s*s);
+ *     p = (sum sqrt(px*px + py*py)) / G; fl = (count of left >= 0) / G
+ *     0 settle_concentration = rho (1 when every start orientation settles at the same angle)   1 settle_cos = c   2 settle_sin = s
+ *     3 settle_offset = p   4 left_range = fl
+ *   MEAN: each per-object value summed over m ascending in double, divided by M', rounded once to float32.  A non-finite state of any
+ *   of the block's rows makes columns 0-3 NaN.
+ * DGDM_EINVAL before anything is launched: a NULL pointer or n_fingers < 1; n_objects outside 1..max_chains; an object index that is
+ * not set; an unknown layout; row_stride / object_stride smaller than the columns they must hold; n_interactions < 1; a bf16 handle
+ * (both calls); an f32_mfma handle for _settled (as rollout refuses it); 3-D without starts_host.                                     */
+#define DGDM_LABEL_TALLY_COLS   10
+#define DGDM_LABEL_SETTLED_COLS 5
+enum { DGDM_LABEL_MEAN = 0, DGDM_LABEL_PER_OBJECT = 1 };
+int dgdm_guidance_label(DgdmGuidance *g, const float *fingers_dev, int64_t n_fingers,
+                        const int32_t *objects_host, int n_objects, int timestep, const float thr[3],
+                        const int64_t *starts_host, int layout,
+                        float *rows_dev, int64_t row_stride, int64_t object_stride, void *stream);
+int dgdm_guidance_label_settled(DgdmGuidance *g, const float *fingers_dev, int64_t n_fingers,
+                        const int32_t *objects_host, int n_objects, const double scale[3], int n_interactions,
+                        const int64_t *starts_host, int layout,
+                        float *rows_dev, int64_t row_stride, int64_t object_stride, void *stream);
+
 /* Host helper for 'convergence': rowcoef_host[r] for one chain from its centers [B]
  * (deltas_to_objective :445-452 + slicer; `rows_in_call` is R for 2-D and the sub-batch
  * partition is applied for 3-D exactly as cond_fn :494-499 does).                               */
