@@ -69,6 +69,9 @@ PROTOTYPES = {
     "dgdm_ddim_guided_step": (C.c_int, [_P, _P, _P, C.c_int, _P, C.c_int64, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, _P]),
     "dgdm_ddim_guided_step_bounded": (C.c_int, [_P, _P, _P, C.c_int, _P, C.c_int64, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, _P, _P,
                                                 C.c_int64, _P]),
+    "dgdm_ddim_guided_step_noisy": (C.c_int, [_P, _P, _P, C.c_int, _P, C.c_int64, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, _P, _P,
+                                              C.c_int64, C.c_float, _P, C.c_uint64, _P, C.c_int64, C.c_int64, _P]),
+    "dgdm_ddim_step_noise": (C.c_int, [C.c_uint64, _P, C.c_int, C.c_int64, C.c_int64, _P, _P]),
     "dgdm_ddim_add_noise": (C.c_int, [_P, _P, _P, C.c_int64, C.c_float, C.c_float, _P]),
     "dgdm_dynamics_create": (C.c_int, [C.POINTER(_P), C.c_int, C.POINTER(Tensor), C.c_int, C.c_int, C.c_int]),
     "dgdm_dynamics_destroy": (None, [_P]),
@@ -105,6 +108,9 @@ PROTOTYPES = {
                                               C.POINTER(C.c_float), C.c_int, _P, _P, C.c_int64, C.c_float, _P]),
     "dgdm_guided_chains_run_bounded": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.POINTER(Objective), _P, _P, C.POINTER(C.c_int32), C.POINTER(C.c_float),
                                                  C.POINTER(C.c_float), C.c_int, _P, _P, C.c_int64, C.c_float, _P, _P, _P]),
+    "dgdm_guided_chains_run_noisy": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.POINTER(Objective), _P, _P, C.POINTER(C.c_int32), C.POINTER(C.c_float),
+                                               C.POINTER(C.c_float), C.c_int, _P, _P, C.c_int64, C.c_float, _P, _P, C.POINTER(C.c_float), C.c_uint64,
+                                               C.POINTER(C.c_uint64), _P]),
     "dgdm_guidance_orientation_sweep": (C.c_int, [_P, _P, _P, _P, C.c_int, _P, _P]),
     "dgdm_guidance_rollout": (C.c_int, [_P, _P, C.POINTER(C.c_int32), _P, C.POINTER(C.c_double), C.c_int, C.c_int, _P, _P, _P, _P, _P, _P]),
     "dgdm_guidance_label": (C.c_int, [_P, _P, C.c_int64, C.POINTER(C.c_int32), C.c_int, C.c_int, C.POINTER(C.c_float), _P, C.c_int, _P, C.c_int64,

@@ -75,6 +75,8 @@ struct DgdmGuidance {
     DevBuf V, genc, atab, chainbias, timepart, ttmp, ttmp64, partial, objdev, objidx, xobj, xobj16, starts, order, xchains, todo, groupoff;
     DevBuf loopx[2], loopeps, loopgrad, loopxrep, loopts;      // workspace of dgdm_guided_chains_run
     DevBuf loopeps1;                                           // ... step 0's one eps-net evaluation [B][L], replicated into loopeps
+    DevBuf loopkeys;                                           // ... the chains' noise keys [n_chains] uint64 (eta > 0)
+    std::vector<uint64_t> loopkeys_host;                       // ... what loopkeys holds
     DevBuf loopcond, loopx2, loopeps2;                         // ... with a condition: [cond rows | zero rows], and the doubled batch of the classifier-free mix
     DevBuf scorelogits;                      // dgdm_guidance_score: the logits when the caller does not want them
     // dgdm_guidance_rollout: the sweep's orientations [G] (built with the handle), and its scratch, grown on demand: the state
@@ -1000,13 +1002,23 @@ extern "C" int dgdm_guided_chains_run_cond(DgdmUnet1d *unet, DgdmGuidance *g, co
                                           global_cond_dev, cond_chain_stride, cfg_weight, nullptr, nullptr, stream);
 }
 
-// The single body of the three entries.  lo_dev / hi_dev: per-entry clip of the predicted clean sample ([B][L], one block for all chains)
-// in place of [-1, 1]; both NULL: the plain step.
 extern "C" int dgdm_guided_chains_run_bounded(DgdmUnet1d *unet, DgdmGuidance *g, const float *noise_dev, int n_chains, int n_grad,
                                               const DgdmObjective *objectives, const float *rowcoef_dev, const int64_t *starts_host,
                                               const int32_t *timesteps, const float *coef, const float *scales, int n_steps, float *x_out_dev,
                                               const float *global_cond_dev, int64_t cond_chain_stride, float cfg_weight, const float *lo_dev,
                                               const float *hi_dev, void *stream) {
+    return dgdm_guided_chains_run_noisy(unet, g, noise_dev, n_chains, n_grad, objectives, rowcoef_dev, starts_host, timesteps, coef, scales, n_steps, x_out_dev,
+                                        global_cond_dev, cond_chain_stride, cfg_weight, lo_dev, hi_dev, nullptr, 0, nullptr, stream);
+}
+
+// The single body of the four entries.  lo_dev / hi_dev: per-entry clip of the predicted clean sample ([B][L], one block for all chains)
+// in place of [-1, 1]; both NULL: the plain step.  eta_coef: (sigma, dir) per step, NULL: sigma = 0 - then, and at every step whose
+// sigma is 0, the step is the eta = 0 launch of old.
+extern "C" int dgdm_guided_chains_run_noisy(DgdmUnet1d *unet, DgdmGuidance *g, const float *noise_dev, int n_chains, int n_grad,
+                                            const DgdmObjective *objectives, const float *rowcoef_dev, const int64_t *starts_host,
+                                            const int32_t *timesteps, const float *coef, const float *scales, int n_steps, float *x_out_dev,
+                                            const float *global_cond_dev, int64_t cond_chain_stride, float cfg_weight, const float *lo_dev,
+                                            const float *hi_dev, const float *eta_coef, uint64_t seed, const uint64_t *chain_keys, void *stream) {
     DGDM_REQUIRE(unet && g && noise_dev && objectives && timesteps && coef && scales && x_out_dev, DGDM_EINVAL, "dgdm_guided_chains_run: null argument");
     DGDM_REQUIRE(!lo_dev == !hi_dev, DGDM_EINVAL, "dgdm_guided_chains_run_bounded: lo and hi come together or not at all");
     DGDM_REQUIRE(n_chains > 0 && n_grad > 0 && n_chains * n_grad <= g->cfg.max_chains && n_steps > 0, DGDM_EINVAL,
@@ -1027,6 +1039,26 @@ extern "C" int dgdm_guided_chains_run_bounded(DgdmUnet1d *unet, DgdmGuidance *g,
     const int cfg = !conditional ? 1 : cfg_weight == 1.f ? 1 : cfg_weight == 0.f ? 0 : 2;
     int rc;
     if ((rc = check_objectives(g, objectives, rowcoef_dev, n_chains * n_grad))) return rc;      // before the first launch of the loop
+    bool noisy = false;
+    for (int si = 0; eta_coef && si < n_steps; ++si) {
+        const float sg = eta_coef[2 * si], dr = eta_coef[2 * si + 1];
+        DGDM_REQUIRE(sg >= 0.f && sg <= 3.0e38f && dr == dr, DGDM_EINVAL, "dgdm_guided_chains_run_noisy: step %d has sigma %g, dir %g", si, (double)sg, (double)dr);
+        noisy = noisy || sg != 0.f;
+    }
+    const uint64_t *keys_dev = nullptr;
+    if (noisy) {         // the chains' keys: uploaded when they differ from what the handle holds (then the stream is waited for once,
+                         // so the host copy is not touched again while a copy may be reading it); a repeated run uploads nothing
+        std::vector<uint64_t> keys(n_chains);
+        for (int c = 0; c < n_chains; ++c) keys[c] = chain_keys ? chain_keys[c] : (uint64_t)c;
+        if (keys != g->loopkeys_host || !g->loopkeys.p) {
+            g->loopkeys_host.clear();
+            if ((rc = g->loopkeys.alloc(sizeof(uint64_t) * n_chains))) return rc;
+            DGDM_HIP_CHECK(hipMemcpyAsync(g->loopkeys.p, keys.data(), sizeof(uint64_t) * n_chains, hipMemcpyHostToDevice, (hipStream_t)stream));
+            DGDM_HIP_CHECK(hipStreamSynchronize((hipStream_t)stream));
+            g->loopkeys_host = keys;
+        }
+        keys_dev = g->loopkeys.as<uint64_t>();
+    }
     if ((rc = g->loopx[0].alloc(nx * 4)) || (rc = g->loopx[1].alloc(nx * 4)) || (rc = g->loopeps.alloc(nx * 4)) || (rc = g->loopgrad.alloc(ng * 4)) ||
         (rc = g->loopxrep.alloc(ng * 4)) || (rc = g->loopts.alloc((size_t)2 * n_chains * B * sizeof(int))))
         return rc;
@@ -1126,9 +1158,13 @@ extern "C" int dgdm_guided_chains_run_bounded(DgdmUnet1d *unet, DgdmGuidance *g,
         if ((rc = guidance_grad(g, kind, xg, t, objectives, rowcoef_dev, nullptr, n_chains * n_grad, g->loopgrad.as<float>(), s,
                                 kind == 3 ? &emb : nullptr, si % cpe, hoist))) return rc;
         const float *cf = coef + 4 * si;
-        // the scheduler step over n entries from offset `off`; with bounds, their [B][L] block repeats for every chain
+        const float sigma = eta_coef ? eta_coef[2 * si] : 0.f;
+        // the scheduler step over n entries, whole chains, from offset `off`; with bounds, their [B][L] block repeats for every chain
         auto ddim = [&](size_t off, int ngr, int64_t n, float scale) -> int {
             const float *e = g->loopeps.as<float>() + off, *gr = g->loopgrad.as<float>() + off;
+            if (sigma != 0.f)
+                return dgdm_ddim_guided_step_noisy(x + off, e, gr, ngr, xn + off, n, cf[0], cf[1], cf[2], eta_coef[2 * si + 1], scale, lo_dev, hi_dev,
+                                                   (int64_t)per_chain, sigma, nullptr, seed, keys_dev + off / per_chain, si, (int64_t)per_chain, s);
             if (lo_dev)
                 return dgdm_ddim_guided_step_bounded(x + off, e, gr, ngr, xn + off, n, cf[0], cf[1], cf[2], cf[3], scale, lo_dev, hi_dev, (int64_t)per_chain, s);
             return dgdm_ddim_guided_step(x + off, e, gr, ngr, xn + off, n, cf[0], cf[1], cf[2], cf[3], scale, s);

@@ -18,6 +18,7 @@
 // 1-3 are the three phases of a reduce-then-scan: no workgroup waits for another, and the result depends on the mesh alone.  A is read
 // back after 3 (the call synchronises once) so that a mesh without area fails before anything is sampled.
 #include "common.h"
+#include "philox.h"
 #include <algorithm>
 #include <cerrno>
 #include <cmath>
@@ -246,29 +247,7 @@ __global__ __launch_bounds__(SCAN_THREADS) void count_kernel(const ChunkDesc *ch
     }
 }
 
-// Philox4x64-10 (Salmon et al., SC'11; the Random123 constants), one block of four 64-bit outputs.
-struct U64x4 { uint64_t v[4]; };
-
-__host__ __device__ inline void mulhilo64(uint64_t a, uint64_t b, uint64_t *hi, uint64_t *lo) {
-#if defined(__HIP_DEVICE_COMPILE__)
-    *hi = __umul64hi(a, b);
-#else
-    *hi = (uint64_t)(((unsigned __int128)a * b) >> 64);
-#endif
-    *lo = a * b;
-}
-
-__host__ __device__ inline U64x4 philox4x64_10(U64x4 c, uint64_t k0, uint64_t k1) {
-    for (int r = 0; r < 10; ++r) {
-        if (r > 0) { k0 += 0x9E3779B97F4A7C15ull; k1 += 0xBB67AE8584CAA73Bull; }
-        uint64_t hi0, lo0, hi1, lo1;
-        mulhilo64(0xD2E7470EE14C6C93ull, c.v[0], &hi0, &lo0);
-        mulhilo64(0xCA5A826395121157ull, c.v[2], &hi1, &lo1);
-        c = U64x4{{hi1 ^ c.v[1] ^ k0, lo1, hi0 ^ c.v[3] ^ k1, lo0}};
-    }
-    return c;
-}
-
+// Philox4x64-10: philox.h, shared with the scheduler step's noise.
 __global__ void sample_kernel(const double *verts, const int32_t *tris, const int64_t *vert_off, const int64_t *tri_off, const uint64_t *keys,
                               uint64_t seed, const int64_t *counts, int64_t n_points, int64_t total, double *out) {
     const int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;

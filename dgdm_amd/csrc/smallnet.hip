@@ -3,6 +3,8 @@
 // All of these touch O(B) or O(cells) rows (KBs..MBs) against the trunk's O(B*cells) rows.
 #include "common.h"
 #include "smallnet.h"
+#include "philox.h"
+#include <algorithm>
 
 // No implicit a*b+c -> fma contraction in this file: the scheduler update, FPS and ball-query distances must round
 // like the reference's separate float32 ops (HIP's __fmul_rn/__fadd_rn are plain * and + and would be contracted).
@@ -395,10 +397,29 @@ int dyn_post64(int W1, const float *partial, int tiles_per_b, const double *w1c,
 // per entry, [lo, hi] of entry i % period, instead of clip_sample=True's [-1, 1] (editing a design); the plain instantiation neither forms
 // the index nor reads lo / hi.  Everything but the clamp's operands is one sequence, so lo = -1, hi = 1 gives the plain step's bits;
 // lo == hi pins x0, and with sap = 1, sbp = 0 (the last step) the output is that value exactly.
-template <bool BOUNDED>
+// NOISY (eta > 0): out = sap x0 + dir eps + sigma z, with sbp holding dir; z is noise[i] or the keyed normal of dgdm_hip.h.  The
+// instantiations without it never form the chain index or touch StepNoise.
+struct StepNoise {
+    float sigma;
+    const float *noise;             // explicit z, or nullptr: the keyed normal
+    uint64_t seed;
+    const uint64_t *chain_keys;     // [n / per_chain]
+    uint64_t step_index;
+    int64_t per_chain;
+};
+
+// The recipe of include/dgdm_hip.h: element e of the chain keyed (seed, key) at step_index -> a standard normal, float64 until the end.
+__device__ inline float keyed_normal(uint64_t seed, uint64_t key, uint64_t step_index, uint64_t e) {
+    const U64x4 r = philox4x64_10(U64x4{{e / 2 + 1, step_index, 0, 0}}, seed, key);
+    const int lane = 2 * (int)(e & 1);
+    const double u1 = (double)((r.v[lane] >> 11) + 1) * 0x1.0p-53, u2 = (double)(r.v[lane + 1] >> 11) * 0x1.0p-53;
+    return (float)(sqrt(-2.0 * log(u1)) * cos(6.283185307179586 * u2));
+}
+
+template <bool BOUNDED, bool NOISY>
 __global__ void ddim_step_kernel(const float *__restrict__ x, const float *__restrict__ eps, const float *__restrict__ grad,
                                  int n_grad, float *__restrict__ out, int64_t n, float sa, float sb, float sap, float sbp,
-                                 float scale, const float *__restrict__ lo, const float *__restrict__ hi, int64_t period) {
+                                 float scale, const float *__restrict__ lo, const float *__restrict__ hi, int64_t period, StepNoise nz) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     float cl = -1.f, ch = 1.f;
@@ -419,7 +440,21 @@ __global__ void ddim_step_kernel(const float *__restrict__ x, const float *__res
     }
     float x0 = __fdiv_rn(sub_rn(x[i], mul_rn(sb, e)), sa);        // (x - sqrt(1-abar) eps) / sqrt(abar)
     x0 = fminf(fmaxf(x0, cl), ch);
-    out[i] = add_rn(mul_rn(sap, x0), mul_rn(sbp, e));
+    if constexpr (NOISY) {
+        const int64_t c = i / nz.per_chain;
+        const float z = nz.noise ? nz.noise[i] : keyed_normal(nz.seed, nz.chain_keys[c], nz.step_index, (uint64_t)(i - c * nz.per_chain));
+        out[i] = add_rn(add_rn(mul_rn(sap, x0), mul_rn(sbp, e)), mul_rn(nz.sigma, z));
+    } else {
+        out[i] = add_rn(mul_rn(sap, x0), mul_rn(sbp, e));
+    }
+}
+
+__global__ void step_noise_kernel(uint64_t seed, const uint64_t *__restrict__ chain_keys, uint64_t step_index, int64_t per_chain, int64_t n,
+                                  float *__restrict__ z) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const int64_t c = i / per_chain;
+    z[i] = keyed_normal(seed, chain_keys[c], step_index, (uint64_t)(i - c * per_chain));
 }
 
 __global__ void add_noise_kernel(const float *__restrict__ x0, const float *__restrict__ noise, float *__restrict__ out, int64_t n,
@@ -430,19 +465,27 @@ __global__ void add_noise_kernel(const float *__restrict__ x0, const float *__re
 
 }  // namespace dgdm
 
-// lo_dev == nullptr: the plain step.  bytes: what prof_end books for the stage.
+// lo_dev == nullptr: the plain step; nz == nullptr or sigma == 0: the eta = 0 instantiations.  bytes: what prof_end books for the stage.
 static int ddim_step_launch(const float *x_dev, const float *eps_dev, const float *grad_dev, int n_grad, float *x_next_dev, int64_t n, float sa,
                             float sb, float sap, float sbp, float scale, const float *lo_dev, const float *hi_dev, int64_t period, double bytes,
-                            hipStream_t s) {
+                            hipStream_t s, const dgdm::StepNoise *nz = nullptr) {
     if (n == 0) return DGDM_OK;
     const dim3 grid((unsigned)((n + 255) / 256));
+    const dgdm::StepNoise none{};
     dgdm::prof_begin(s, DGDM_STAGE_DDIM);
-    if (lo_dev)
-        hipLaunchKernelGGL(dgdm::ddim_step_kernel<true>, grid, dim3(256), 0, s, x_dev, eps_dev, grad_dev, n_grad, x_next_dev, n, sa, sb, sap, sbp,
-                           scale, lo_dev, hi_dev, period);
+    if (nz && nz->sigma != 0.f) {
+        if (lo_dev)
+            hipLaunchKernelGGL((dgdm::ddim_step_kernel<true, true>), grid, dim3(256), 0, s, x_dev, eps_dev, grad_dev, n_grad, x_next_dev, n, sa, sb, sap,
+                               sbp, scale, lo_dev, hi_dev, period, *nz);
+        else
+            hipLaunchKernelGGL((dgdm::ddim_step_kernel<false, true>), grid, dim3(256), 0, s, x_dev, eps_dev, grad_dev, n_grad, x_next_dev, n, sa, sb, sap,
+                               sbp, scale, nullptr, nullptr, (int64_t)0, *nz);
+    } else if (lo_dev)
+        hipLaunchKernelGGL((dgdm::ddim_step_kernel<true, false>), grid, dim3(256), 0, s, x_dev, eps_dev, grad_dev, n_grad, x_next_dev, n, sa, sb, sap, sbp,
+                           scale, lo_dev, hi_dev, period, none);
     else
-        hipLaunchKernelGGL(dgdm::ddim_step_kernel<false>, grid, dim3(256), 0, s, x_dev, eps_dev, grad_dev, n_grad, x_next_dev, n, sa, sb, sap, sbp,
-                           scale, nullptr, nullptr, (int64_t)0);
+        hipLaunchKernelGGL((dgdm::ddim_step_kernel<false, false>), grid, dim3(256), 0, s, x_dev, eps_dev, grad_dev, n_grad, x_next_dev, n, sa, sb, sap, sbp,
+                           scale, nullptr, nullptr, (int64_t)0, none);
     dgdm::prof_end(s, DGDM_STAGE_DDIM, bytes);
     DGDM_HIP_CHECK(hipGetLastError());
     return DGDM_OK;
@@ -466,6 +509,38 @@ extern "C" int dgdm_ddim_guided_step_bounded(const float *x_dev, const float *ep
                  (long long)n);
     return ddim_step_launch(x_dev, eps_dev, grad_dev, n_grad, x_next_dev, n, sqrt_abar_t, sqrt_1m_abar_t, sqrt_abar_prev, sqrt_1m_abar_prev,
                             guidance_scale, lo_dev, hi_dev, period, (double)n * 4.0 * (5 + n_grad), (hipStream_t)stream);
+}
+
+extern "C" int dgdm_ddim_guided_step_noisy(const float *x_dev, const float *eps_dev, const float *grad_dev, int n_grad, float *x_next_dev, int64_t n,
+                                           float sqrt_abar_t, float sqrt_1m_abar_t, float sqrt_abar_prev, float dir, float guidance_scale,
+                                           const float *lo_dev, const float *hi_dev, int64_t period, float sigma, const float *noise_dev,
+                                           uint64_t seed, const uint64_t *chain_keys_dev, int64_t step_index, int64_t per_chain, void *stream) {
+    const char *fn = "dgdm_ddim_guided_step_noisy";
+    DGDM_REQUIRE(x_dev && eps_dev && x_next_dev && n >= 0, DGDM_EINVAL, "%s: null argument", fn);
+    DGDM_REQUIRE(!lo_dev == !hi_dev, DGDM_EINVAL, "%s: lo and hi come together or not at all", fn);
+    DGDM_REQUIRE(!lo_dev || (period > 0 && n % period == 0), DGDM_EINVAL, "%s: period %lld does not divide n = %lld", fn, (long long)period, (long long)n);
+    DGDM_REQUIRE(sigma >= 0.f && sigma <= 3.0e38f, DGDM_EINVAL, "%s: sigma %g is not a finite non-negative number", fn, (double)sigma);
+    if (sigma != 0.f && !noise_dev) {
+        DGDM_REQUIRE(chain_keys_dev, DGDM_EINVAL, "%s: sigma > 0 needs noise_dev or chain_keys_dev", fn);
+        DGDM_REQUIRE(step_index >= 0, DGDM_EINVAL, "%s: step_index %lld is negative", fn, (long long)step_index);
+        DGDM_REQUIRE(per_chain > 0 && n % per_chain == 0, DGDM_EINVAL, "%s: per_chain %lld does not divide n = %lld", fn, (long long)per_chain, (long long)n);
+    }
+    // with explicit noise the chain index is formed but never used: any positive per_chain will do
+    const dgdm::StepNoise nz{sigma, noise_dev, seed, chain_keys_dev, (uint64_t)step_index, noise_dev ? std::max<int64_t>(1, n) : per_chain};
+    return ddim_step_launch(x_dev, eps_dev, grad_dev, n_grad, x_next_dev, n, sqrt_abar_t, sqrt_1m_abar_t, sqrt_abar_prev, dir, guidance_scale, lo_dev,
+                            hi_dev, period, (double)n * 4.0 * ((lo_dev ? 5 : 3) + n_grad + (noise_dev && sigma != 0.f ? 1 : 0)), (hipStream_t)stream, &nz);
+}
+
+extern "C" int dgdm_ddim_step_noise(uint64_t seed, const uint64_t *chain_keys_dev, int n_chains, int64_t step_index, int64_t per_chain, float *z_dev,
+                                    void *stream) {
+    DGDM_REQUIRE(chain_keys_dev && z_dev, DGDM_EINVAL, "dgdm_ddim_step_noise: null argument");
+    DGDM_REQUIRE(n_chains >= 0 && per_chain >= 0 && step_index >= 0, DGDM_EINVAL, "dgdm_ddim_step_noise: negative argument");
+    const int64_t n = (int64_t)n_chains * per_chain;
+    if (n == 0) return DGDM_OK;
+    hipLaunchKernelGGL(dgdm::step_noise_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, seed, chain_keys_dev,
+                       (uint64_t)step_index, per_chain, n, z_dev);
+    DGDM_HIP_CHECK(hipGetLastError());
+    return DGDM_OK;
 }
 
 extern "C" int dgdm_ddim_add_noise(const float *x0_dev, const float *noise_dev, float *out_dev, int64_t n, float sqrt_abar,

@@ -136,6 +136,11 @@ def shard_chains(chains: Sequence[Tuple[int, str]], rank: int, world: int):
     return mine, local_objects, local_chains
 
 
+def chain_noise_keys(mine: range) -> List[int]:
+    """The step-noise keys of a rank's block of chains: their global indices."""
+    return list(mine)
+
+
 class GuidanceSpec:
     """What defines a guidance handle apart from its objects.  Quacks like ``engine.Guidance`` for the start-stream arithmetic
     (rows per cond_fn call, rows per centre sweep), so a rank can walk the draw stream without building a handle."""
@@ -162,7 +167,8 @@ class GuidanceSpec:
 def guided_chains_sharded(unet, spec: GuidanceSpec, sched, mode: str, noise: torch.Tensor, objects: torch.Tensor,
                           chains: Sequence[Tuple[int, str]], unguided: Optional[torch.Tensor] = None, starts=None,
                           streams=None, group=None, build: Optional[Callable] = None, global_cond: Optional[torch.Tensor] = None,
-                          cfg_weight: float = 1.0, edit=None) -> torch.Tensor:
+                          cfg_weight: float = 1.0, edit=None, eta: float = 0.0, noise_seed: int = 0,
+                          shared_step_noise: bool = False) -> torch.Tensor:
     """``sampler.guided_chains`` for the (object x objective) pairs `chains` over the object bank `objects`, block-partitioned
     over the ranks of `group`; returns all chains' samples [n_chains, B, L, 1] in the original order on every rank.
 
@@ -171,7 +177,9 @@ def guided_chains_sharded(unet, spec: GuidanceSpec, sched, mode: str, noise: tor
     §8(e)).  3-D: the FPS start draws are rank-count-invariant - every rank walks the reference's single generator stream over
     ALL chains (host only: `starts` or the global CPU generator) and keeps its own block, unless per-chain `streams` are given.
     global_cond (B, gc), shared by all chains, and cfg_weight: as in ``sampler.guided_chains``.  edit (dgdm_amd/edit.py) is forwarded:
-    its designs, bounds and start sample are the same on every rank, and the draws are made for its steps."""
+    its designs, bounds and start sample are the same on every rank, and the draws are made for its steps.
+    eta, noise_seed, shared_step_noise (sampler.guided_chains): a chain's step noise is keyed by its GLOBAL index in `chains`, so the
+    gathered result does not depend on the number of ranks."""
     from . import sampler
     world, rank = world_rank(group)
     mine, local_objects, local_chains = shard_chains(chains, rank, world)
@@ -183,7 +191,8 @@ def guided_chains_sharded(unet, spec: GuidanceSpec, sched, mode: str, noise: tor
     if len(local_chains):
         guid = (build or spec.build)(objects[local_objects].to(noise.device), len(local_chains))
         local = sampler.guided_chains(unet, guid, sched, mode, noise, local_chains, unguided=unguided, predrawn=predrawn, global_cond=global_cond,
-                                      cfg_weight=cfg_weight, edit=edit)
+                                      cfg_weight=cfg_weight, edit=edit, eta=eta, noise_seed=noise_seed, shared_step_noise=shared_step_noise,
+                                      chain_keys=chain_noise_keys(mine))
     else:
         local = torch.zeros((0, B, L, 1), dtype=torch.float32, device=noise.device)
     return gather_pairs(local, len(chains), group)
@@ -196,13 +205,15 @@ def gather_rows(local: torch.Tensor, n_items: int, group=None) -> torch.Tensor:
 
 def guided_multi_object_sharded(unet, spec: GuidanceSpec, sched, mode: str, noise: torch.Tensor, objects: torch.Tensor, opt_obj: str,
                                 starts=None, group=None, build: Optional[Callable] = None, on_step=None, global_cond: Optional[torch.Tensor] = None,
-                                cfg_weight: float = 1.0, edit=None) -> torch.Tensor:
+                                cfg_weight: float = 1.0, edit=None, eta: float = 0.0, noise_seed: int = 0,
+                                shared_step_noise: bool = False) -> torch.Tensor:
     """``sampler.guided_multi_object`` (generator/diffusion.py:637-647: ONE chain whose step uses the mean of n_obj cond_fn
     gradients) with the objects block-partitioned over the ranks.  Unlike the per-object chains this loop has a real exchange
     step: every denoise step the ranks all-gather their objects' gradients [n_obj, B, L] (a few KB over RCCL) and then all take
     the same scheduler step on the full stack, in object order - so every rank holds the single-process result bit for bit.
     3-D: per step the reference draws the FPS starts object after object (:641-643); every rank walks that stream and keeps its objects'.
-    edit (dgdm_amd/edit.py): the start sample, the steps and their bounds are the edit's, the same on every rank."""
+    edit (dgdm_amd/edit.py): the start sample, the steps and their bounds are the edit's, the same on every rank.
+    eta, noise_seed: every rank steps the one chain with key 0, as sampler.guided_multi_object does: the same noise on all of them."""
     from . import sampler
     world, rank = world_rank(group)
     n_obj, (B, L, _) = objects.shape[0], noise.shape
@@ -232,7 +243,8 @@ def guided_multi_object_sharded(unet, spec: GuidanceSpec, sched, mode: str, nois
         x0, timesteps, bounds = sampler.edit_start(edit, sched, noise)
         hook = None if on_step is None else lambda i, x, eps: on_step(i, x.reshape(B, L, 1))
         out = sampler.run_chains(unet, None, sched, x0.reshape(B, L), 1, n_obj, None, None, None, timesteps,
-                                 [sampler.chain_scale(mode, opt_obj, multi=True)], global_cond, cfg_weight, bounds, on_step=hook, grad_fn=grad_fn)
+                                 [sampler.chain_scale(mode, opt_obj, multi=True)], global_cond, cfg_weight, bounds, on_step=hook, grad_fn=grad_fn,
+                                 eta=eta, noise_seed=noise_seed, chain_keys=[0])
     return out.reshape(B, L, 1)
 
 

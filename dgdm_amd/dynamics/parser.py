@@ -76,6 +76,12 @@ _FLAGS = [
     ("pin", str, None, "with --edit_from: control points held at the design's value, indices and inclusive ranges like 0-6,10 (the first half of the "
                        "indices is the left finger)"),
     ("edit_band_mm", float, None, "with --edit_from: no control point moves further than this many millimetres from the design"),
+    ("eta", float, 0.0, "generator, --mode=test: eta of the DDIM step in every sampling loop (0: the deterministic step, 1: the DDPM variance); the "
+                        "noise is made on the device, keyed by (--noise_seed, chain, step) (dgdm_amd/scheduler.py; the classifier scales are untuned "
+                        "for eta > 0)"),
+    ("noise_seed", int, None, "with --eta: seed of the steps' noise (default: --seed)"),
+    ("shared_step_noise", "flag", None, "with --eta: every chain of a launch draws the same step noise (common random numbers, for comparing "
+                                        "objectives on equal noise)"),
     ("device_dataset", "flag", None, "dynamics training: read every data file once, keep the dataset on the GPU and build each batch's rows there "
                                      "(dynamics/device_dataset.py); same batches, draws and results as the host loop"),
 ]

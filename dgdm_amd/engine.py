@@ -549,15 +549,61 @@ def _bounds_block(bounds, numel: int, device) -> Tuple[torch.Tensor, torch.Tenso
     return lo, hi, lo.numel()
 
 
+def _u64(v: int) -> int:
+    return int(v) & 0xFFFFFFFFFFFFFFFF
+
+
+def chain_keys_tensor(keys: Sequence[int], device) -> torch.Tensor:
+    """Noise keys (uint64 values; negative ints wrap) as the int64 device tensor whose bits the library reads as uint64."""
+    return torch.from_numpy(np.array([_u64(k) for k in keys], dtype=np.uint64).view(np.int64)).to(device)
+
+
+def step_noise(seed: int, keys: Sequence[int], step_index: int, per_chain: int) -> torch.Tensor:
+    """The keyed normals the stochastic step draws (dgdm_ddim_step_noise; the recipe is in include/dgdm_hip.h): (len(keys), per_chain)
+    float32, row c = element 0 .. per_chain - 1 of the chain keyed (seed, keys[c]) at step `step_index`."""
+    kd = chain_keys_tensor(keys, "cuda")
+    out = torch.empty((len(keys), int(per_chain)), dtype=torch.float32, device="cuda")
+    check(lib().dgdm_ddim_step_noise(_u64(seed), dptr(kd), len(keys), int(step_index), int(per_chain), dptr(out), stream_ptr()))
+    return out
+
+
 def ddim_guided_step(x: torch.Tensor, eps: torch.Tensor, grad: Optional[torch.Tensor], n_grad: int, coef: Tuple[float, float, float, float],
-                     scale: float, bounds=None) -> torch.Tensor:
+                     scale: float, bounds=None, eta_coef: Optional[Tuple[float, float]] = None, seed: int = 0,
+                     chain_keys: Optional[Sequence[int]] = None, step_index: int = 0, variance_noise: Optional[torch.Tensor] = None) -> torch.Tensor:
     """grad: None or (n_grad, *x.shape) stacked gradients whose mean guides the step.  bounds = (lo, hi): the predicted clean sample is
     clipped to them per entry instead of to [-1, 1] (dgdm_ddim_guided_step_bounded): lo / hi hold one block that repeats over x (e.g.
-    (B, L) for x (n_chains, B, L))."""
+    (B, L) for x (n_chains, B, L)).
+
+    eta_coef = (sigma, dir) (DDIMScheduler.eta_coefficients): the stochastic step (dgdm_ddim_guided_step_noisy), dir in the place of
+    coef[3].  Its noise is `variance_noise` (like x), or the keyed device normal: x holds len(chain_keys) whole chains, chain c keyed
+    (seed, chain_keys[c]) at `step_index`.  sigma > 0 with neither: ValueError.  eta_coef None is the eta = 0 step of old."""
     x, eps = _f32(x), _f32(eps)
     out = torch.empty_like(x)
     g = _f32(grad) if grad is not None else None
-    args = (dptr(x), dptr(eps), dptr(g), n_grad, dptr(out), x.numel(), *[float(c) for c in coef], float(scale))
+    args = (dptr(x), dptr(eps), dptr(g), n_grad, dptr(out), x.numel(), *[float(c) for c in coef[:3]])
+    if eta_coef is not None:
+        sigma, dirc = float(eta_coef[0]), float(eta_coef[1])
+        lo = hi = None
+        period = 0
+        if bounds is not None:
+            lo, hi, period = _bounds_block(bounds, x.numel(), x.device)
+        z = kd = None
+        per_chain = 0
+        if sigma != 0.0:
+            if variance_noise is not None:
+                z = _f32(variance_noise).to(x.device)
+                if z.numel() != x.numel():
+                    raise ValueError(f"variance_noise of {z.numel()} entries for a step of {x.numel()}")
+            elif chain_keys is not None:
+                if len(chain_keys) == 0 or x.numel() % len(chain_keys):
+                    raise ValueError(f"{len(chain_keys)} chain keys do not divide the {x.numel()} entries of the step into whole chains")
+                kd, per_chain = chain_keys_tensor(chain_keys, x.device), x.numel() // len(chain_keys)
+            else:
+                raise ValueError("a step with sigma > 0 needs variance_noise or chain_keys")
+        check(lib().dgdm_ddim_guided_step_noisy(*args, dirc, float(scale), dptr(lo), dptr(hi), period, sigma, dptr(z), _u64(seed), dptr(kd),
+                                                int(step_index), per_chain, stream_ptr()))
+        return out
+    args = args + (float(coef[3]), float(scale))
     if bounds is None:
         check(lib().dgdm_ddim_guided_step(*args, stream_ptr()))
     else:
@@ -574,8 +620,11 @@ def ddim_guided_step_bounded(x, eps, grad, n_grad: int, coef, scale: float, boun
 def guided_chains_run(unet: "Unet1d", guid: "Guidance", noise: torch.Tensor, n_chains: int, n_grad: int, objectives: Sequence[_lib.Objective],
                       rowcoef: Optional[torch.Tensor], starts: Optional[np.ndarray], timesteps: Sequence[int],
                       coefs: Sequence[Tuple[float, float, float, float]], scales: Sequence[float], global_cond: Optional[torch.Tensor] = None,
-                      cfg_weight: float = 1.0, bounds=None) -> torch.Tensor:
-    """The whole guided denoise loop in one library call (dgdm_guided_chains_run_bounded): noise (B, L) -> (n_chains, B, L).
+                      cfg_weight: float = 1.0, bounds=None, eta_coef: Optional[Sequence[Tuple[float, float]]] = None, seed: int = 0,
+                      chain_keys: Optional[Sequence[int]] = None) -> torch.Tensor:
+    """The whole guided denoise loop in one library call (dgdm_guided_chains_run_noisy): noise (B, L) -> (n_chains, B, L).
+    eta_coef: None (eta = 0), or one (sigma, dir) per step - chain k's step si then draws the keyed normal of (seed, chain_keys[k]) at
+    step_index si; chain_keys None: 0 .. n_chains - 1.
     global_cond: (B, gc) shared by all chains or (n_chains, B, gc); cfg_weight: classifier-free guidance weight (1: the plain conditional run).
     bounds: None, or an edit's (lo, hi), each (B, L), shared by all chains - every step then clips its predicted clean sample to them;
     `noise` is then the edit's start sample and timesteps / coefs the schedule's last steps (dgdm_amd/edit.py)."""
@@ -601,9 +650,15 @@ def guided_chains_run(unet: "Unet1d", guid: "Guidance", noise: torch.Tensor, n_c
         if period != B * L:
             raise ValueError(f"bounds of {period} entries: the chains take one (B, L) = ({B}, {L}) block")
     out = torch.empty((n_chains, B, L), dtype=torch.float32, device=x0.device)
-    check(lib().dgdm_guided_chains_run_bounded(unet._h, guid._h, dptr(x0), n_chains, n_grad, arr, dptr(rowcoef) if rowcoef is not None else None, sp,
-                                               ts, cf, sc, S, dptr(out), dptr(cond), int(cond_stride), float(cfg_weight), dptr(lo), dptr(hi),
-                                               stream_ptr()))
+    ec = ck = None
+    if eta_coef is not None:
+        assert len(eta_coef) == S and (chain_keys is None or len(chain_keys) == n_chains)
+        ec = (C.c_float * (2 * S))(*[float(v) for c in eta_coef for v in c])
+        if chain_keys is not None:
+            ck = (C.c_uint64 * n_chains)(*[_u64(k) for k in chain_keys])
+    check(lib().dgdm_guided_chains_run_noisy(unet._h, guid._h, dptr(x0), n_chains, n_grad, arr, dptr(rowcoef) if rowcoef is not None else None, sp,
+                                             ts, cf, sc, S, dptr(out), dptr(cond), int(cond_stride), float(cfg_weight), dptr(lo), dptr(hi),
+                                             ec, _u64(seed), ck, stream_ptr()))
     return out         # `starts` has been consumed: every step converts it into the handle's pinned staging buffer before it returns
 
 

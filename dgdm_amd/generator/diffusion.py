@@ -97,8 +97,13 @@ class Diffusion(nn.Module):
                  classifier_model=None, grid_size: int = 360, num_pos: int = 5, object_vertices: Optional[torch.Tensor] = None,
                  object_ids: Optional[List[int]] = None, num_cpus: int = 32, sub_batch_size: int = 1024, pts_x_dim: int = 7,
                  pts_z_dim: int = 3, render_video: bool = False, seed: int = 0, contraction_dtype: str = "f32", simulator=None,
-                 render_plots: bool = True, table_logger=None):
+                 render_plots: bool = True, table_logger=None, eta: float = 0.0, noise_seed: Optional[int] = None):
         super().__init__()
+        # not reference arguments (--eta, --noise_seed, --shared_step_noise): stochastic DDIM steps in every sampling loop, their noise
+        # keyed on the device by (noise_seed, chain, step); noise_seed None: `seed`.  eta = 0 is the reference's step
+        if not (float(eta) >= 0.0 and float(eta) < float("inf")):
+            raise ValueError(f"eta {eta!r}: not a finite non-negative number")
+        self.eta, self.noise_seed, self.shared_step_noise = float(eta), int(seed if noise_seed is None else noise_seed), False
         if contraction_dtype not in ("f32", "bf16", "f32_mfma", "f32_f16x3"):
             raise ValueError(f"contraction dtype {contraction_dtype!r} not supported")
         # not a reference argument: 'bf16' runs the trunk / eps-net / sa3 contractions with bf16 operands (DESIGN_HISTORY.md 4.6)
@@ -457,6 +462,12 @@ class Diffusion(nn.Module):
         """The `edit` argument of artefacts.guided_table / multi_object_table for the samples `out` of the edit's chains."""
         return dict(artefacts.edit_stats(edit, out), source=self._edit_source_sim)
 
+    def _noise_kw(self) -> Dict[str, Any]:
+        """eta / noise_seed / shared_step_noise as the samplers take them; nothing at eta = 0, whose calls are those of old."""
+        if self.eta == 0.0:
+            return {}
+        return dict(eta=self.eta, noise_seed=self.noise_seed, shared_step_noise=bool(self.shared_step_noise))
+
     def guided_sample(self, batch_idx, batch_size, noise, save_dir, opt_obj='rotate', ori_range=[-1.0, 1.0], unguided_sample=None,
                       global_cond=None):
         """All objects' chains of generator/diffusion.py:561-576 as one batch.  Returns (n_objects, B, L, 1).  global_cond (B, gc): the
@@ -477,11 +488,11 @@ class Diffusion(nn.Module):
             out = ddist.guided_chains_sharded(self._net(), self._spec(batch_size, ori_range, objs.shape[1]), self.noise_scheduler, self.mode,
                                               noise.to(self.device), objs, chains, unguided=ug,
                                               build=lambda o, k: self._guidance_for(batch_size, ori_range, o.detach().cpu(), k),
-                                              global_cond=global_cond, cfg_weight=self.cfg_weight, edit=edit)
+                                              global_cond=global_cond, cfg_weight=self.cfg_weight, edit=edit, **self._noise_kw())
         else:
             g = self._guidance_for(batch_size, ori_range, objs, n)
             out = sampler.guided_chains(self._net(), g, self.noise_scheduler, self.mode, noise.to(self.device), chains, unguided=ug,
-                                        global_cond=global_cond, cfg_weight=self.cfg_weight, edit=edit)
+                                        global_cond=global_cond, cfg_weight=self.cfg_weight, edit=edit, **self._noise_kw())
         if ddist.world_rank()[1] == 0:
             tag = f"{opt_obj}_orirange={ori_range[0]:.3f}_{ori_range[1]:.3f}"
             sub = 'vis_guided' if edit is None else 'vis_edit'
@@ -512,12 +523,12 @@ class Diffusion(nn.Module):
             out = ddist.guided_multi_object_sharded(self._net(), self._spec(batch_size, ori_range, objs.shape[1]), self.noise_scheduler, self.mode,
                                                     noise.to(self.device), objs, opt_obj,
                                                     build=lambda o, k: self._guidance_for(batch_size, ori_range, o.detach().cpu(), k), on_step=on_step,
-                                                    global_cond=global_cond, cfg_weight=self.cfg_weight, edit=edit)
+                                                    global_cond=global_cond, cfg_weight=self.cfg_weight, edit=edit, **self._noise_kw())
         else:
             g = self._guidance_for(batch_size, ori_range, objs, objs.shape[0])
             out = sampler.guided_multi_object(self._net(), g, self.noise_scheduler, self.mode, noise.to(self.device),
                                               list(range(objs.shape[0])), opt_obj, on_step=on_step, global_cond=global_cond,
-                                              cfg_weight=self.cfg_weight, edit=edit)
+                                              cfg_weight=self.cfg_weight, edit=edit, **self._noise_kw())
         if rank0:
             self._emit(save_dir, sub, tag, out[None], ["allobj"])
             if self.simulator is not None and save_dir:                  # :675-709: every gripper on all objects
@@ -586,14 +597,16 @@ class Diffusion(nn.Module):
         for i, t in enumerate(self.noise_scheduler.timesteps):
             eps = net.forward_cfg(sample, torch.full((B,), int(t), device=dev), cond, self.cfg_weight)
             noise_pred_loss += float(torch.mean((eps - noise) ** 2))
-            sample = self.noise_scheduler.step(eps, t, sample).prev_sample
+            # eta > 0: this loop's one chain has key 0, like the unguided loop below
+            step_kw = {} if self.eta == 0.0 else dict(eta=self.eta, noise_key=(self.noise_seed, 0, i))
+            sample = self.noise_scheduler.step(eps, t, sample, **step_kw).prev_sample
             if plots and batch_idx == 0:                                 # val_vis/<epoch>_<step>.png, sample 0 (:203-231)
                 artefacts.plot_fingers(os.path.join(self.save_dir, 'val_vis', '%d_%d.png' % (self.current_epoch, i)),
                                        sample[0, :, 0].detach().cpu().numpy(), self.mode, self.pts_x_dim, self.pts_z_dim, stacked=True)
         stats = {"val/noise pred loss": noise_pred_loss / self.num_inference_steps,
                  "val/denoise loss": float(torch.mean((sample - data) ** 2)),
                  "val/accuracy": float(torch.mean((torch.abs(sample - data) < 0.01).float()))}
-        out: Dict[str, Any] = {"stats": stats}
+        out: Dict[str, Any] = {"stats": stats, "eta": self.eta, "noise_seed": self.noise_seed}
         if batch_idx != 0:
             return out
         imgs: List[str] = []                                             # last-step PNG of every gripper (:273, :292)
@@ -606,7 +619,7 @@ class Diffusion(nn.Module):
                 if i == last:
                     imgs.append(f)
         unguided = sampler.unguided_sample(net, self.noise_scheduler, noise, on_step=on_step if plots else None, global_cond=cond,
-                                           cfg_weight=self.cfg_weight)
+                                           cfg_weight=self.cfg_weight, **self._noise_kw())
         if rank0:
             self._emit(self.save_dir, 'val_vis_noise', 'unguided', unguided[None], ["unguided"])
         out["unguided"] = unguided

@@ -409,7 +409,9 @@ def train(args):
                       num_points=L, learning_rate=args.learning_rate, lr_warmup_steps=args.lr_warmup_steps, ema_power=args.ema_power,
                       class_cond=args.classifier_guidance, classifier_model=classifier, grid_size=args.grid_size, num_pos=args.num_pos,
                       object_vertices=objects, object_ids=object_ids, num_cpus=args.num_cpus, pts_x_dim=args.ctrlpts_x_dim,
-                      pts_z_dim=args.ctrlpts_z_dim, sub_batch_size=args.sub_bs, render_video=args.render_video, seed=args.seed)
+                      pts_z_dim=args.ctrlpts_z_dim, sub_batch_size=args.sub_bs, render_video=args.render_video, seed=args.seed,
+                      eta=float(getattr(args, "eta", 0.0) or 0.0), noise_seed=getattr(args, "noise_seed", None))
+    model.shared_step_noise = bool(getattr(args, "shared_step_noise", False))
     model.save_meshes = bool(getattr(args, "save_meshes", False))
     model.edit_plan = edit_plan
     model.cfg_weight, model.cond_drop_prob, model.global_cond_rows = float(args.cfg_weight), float(args.cond_drop_prob), cond

@@ -323,10 +323,20 @@ def edit_start(edit: Optional[Edit], sched: DDIMScheduler, noise: torch.Tensor):
     return x, ts, edit.bounds_on(noise.device)
 
 
+def step_noise_keys(n_chains: int, shared_step_noise: bool = False, chain_keys: Optional[Sequence[int]] = None) -> List[int]:
+    """The noise keys of a launch's chains: `chain_keys` when given (a slice of a larger run: the chains' global indices), else their
+    indices; shared_step_noise: key 0 for every chain (common random numbers)."""
+    keys = list(range(n_chains)) if chain_keys is None else [int(k) for k in chain_keys]
+    if len(keys) != n_chains:
+        raise ValueError(f"{len(keys)} chain keys for {n_chains} chains")
+    return [0] * n_chains if shared_step_noise else keys
+
+
 def run_chains(unet: Unet1d, guid: Optional[Guidance], sched: DDIMScheduler, x0: torch.Tensor, n_chains: int, n_grad: int, objectives,
                rowcoef: Optional[torch.Tensor], starts: Optional[np.ndarray], timesteps, scales: Sequence[float],
                global_cond: Optional[torch.Tensor] = None, cfg_weight: float = 1.0, bounds=None, trace: Optional[list] = None,
-               on_step=None, grad_fn=None, stepwise: bool = False) -> torch.Tensor:
+               on_step=None, grad_fn=None, stepwise: bool = False, eta: float = 0.0, noise_seed: int = 0,
+               chain_keys: Optional[Sequence[int]] = None) -> torch.Tensor:
     """THE denoise loop, S x [eps-net with the classifier-free mix ; guidance gradient ; DDIM step], of every sampler here and in
     dgdm_amd/dist.py: x0 (B, L) -> (n_chains, B, L).  All n_chains chains start from x0; chain k is guided by the mean of n_grad
     gradients, gradient j of chain k being gradient chain j * n_chains + k of `objectives` (object-major, as dgdm_guided_chains_run
@@ -338,12 +348,25 @@ def run_chains(unet: Unet1d, guid: Optional[Guidance], sched: DDIMScheduler, x0:
       trace: a list that receives (eps, grad, x) per step, each (n_chains, B, L), x being the step's INPUT;
       on_step(si, x, eps): called after each step with its output x;
       grad_fn(si, t, x) -> (n_grad * n_chains, B, L): the step's gradients instead of guid.grad on n_grad copies of x with step si's starts;
-      stepwise=True: nothing of these, but walk it all the same."""
+      stepwise=True: nothing of these, but walk it all the same.
+
+    eta > 0: stochastic DDIM steps (DDIMScheduler.eta_coefficients).  Step si of chain k adds sigma times the keyed device
+    normal of (noise_seed, chain_keys[k], si) - a pure function of those and the element, so the library call, the walk, a run split over
+    ranks and a run split into several calls give the same bits as long as a chain keeps its key.  chain_keys None: range(n_chains).
+    eta == 0 is the loop of old, launch for launch."""
     B, L = x0.shape
     nc = n_chains
+    eta = float(eta)
+    if eta < 0.0:
+        raise ValueError(f"run_chains: eta {eta} is negative")
+    keys = list(range(nc)) if chain_keys is None else [int(k) for k in chain_keys]
+    if len(keys) != nc:
+        raise ValueError(f"run_chains: {len(keys)} chain keys for {nc} chains")
+    eta_coef = [sched.eta_coefficients(int(t), eta) for t in timesteps] if eta != 0.0 else None
     if not stepwise and trace is None and on_step is None and grad_fn is None:
         return engine.guided_chains_run(unet, guid, x0, nc, n_grad, objectives, rowcoef, starts, [int(t) for t in timesteps],
-                                        [sched.coefficients(int(t)) for t in timesteps], scales, global_cond, cfg_weight, bounds)
+                                        [sched.coefficients(int(t)) for t in timesteps], scales, global_cond, cfg_weight, bounds,
+                                        eta_coef, noise_seed, keys if eta_coef is not None else None)
     # one scheduler launch over all chains, or - chains with scales of their own - one per chain, which has no averaged form
     steps = [(slice(None), scales[0])] if len(set(scales)) == 1 else list(enumerate(scales))
     if len(steps) > 1 and n_grad != 1:
@@ -369,7 +392,10 @@ def run_chains(unet: Unet1d, guid: Optional[Guidance], sched: DDIMScheduler, x0:
         if trace is not None:
             trace.append((eps.clone(), None if g is None else g.clone(), x.clone()))
         coef = sched.coefficients(t)
-        out = [engine.ddim_guided_step(x[c], eps[c], None if g is None else g[c], n_grad, coef, sc, bounds) for c, sc in steps]
+        # eta > 0: the launch over all chains takes all keys, a chain's own launch its own key
+        noisy = lambda c: {} if eta_coef is None else dict(eta_coef=eta_coef[si], seed=noise_seed, step_index=si,      # noqa: E731
+                                                           chain_keys=keys if isinstance(c, slice) else [keys[c]])
+        out = [engine.ddim_guided_step(x[c], eps[c], None if g is None else g[c], n_grad, coef, sc, bounds, **noisy(c)) for c, sc in steps]
         x = out[0] if len(out) == 1 else torch.stack(out)
         if on_step is not None:
             on_step(si, x, eps)
@@ -377,18 +403,20 @@ def run_chains(unet: Unet1d, guid: Optional[Guidance], sched: DDIMScheduler, x0:
 
 
 def unguided_sample(unet: Unet1d, sched: DDIMScheduler, x: torch.Tensor, on_step=None, global_cond: Optional[torch.Tensor] = None,
-                    cfg_weight: float = 1.0, edit: Optional[Edit] = None) -> torch.Tensor:
+                    cfg_weight: float = 1.0, edit: Optional[Edit] = None, eta: float = 0.0, noise_seed: int = 0,
+                    shared_step_noise: bool = False) -> torch.Tensor:
     """S x [eps-net ; DDIM step]  (generator/diffusion.py:193-201, :249-256).  on_step(i, x_i, eps_i): the harness's per-step hook
     (plots, noise-prediction loss); it forces a device->host copy per step, as the reference's own plotting does.
     global_cond (B, gc), cfg_weight: the condition rows of a conditional eps-net and the classifier-free guidance weight (the mix is
     the library's: Unet1d.forward_cfg).  edit: x is then the noise the edit's designs are noised with, and the loop runs the edit's K
-    bounded steps (dgdm_amd/edit.py)."""
+    bounded steps (dgdm_amd/edit.py).  eta, noise_seed: stochastic steps as in run_chains; the one chain has key 0 (so
+    shared_step_noise changes nothing here)."""
     B = x.shape[0]
     engine.check_global_cond(global_cond, unet.global_cond_dim, B)
     x, timesteps, bounds = edit_start(edit, sched, x)
     hook = None if on_step is None else lambda i, xi, eps: on_step(i, xi.reshape(x.shape), eps.reshape(x.shape))
     out = run_chains(unet, None, sched, x.reshape(B, -1), 1, 0, [], None, None, timesteps, [0.0], global_cond, cfg_weight, bounds,
-                     on_step=hook, stepwise=True)
+                     on_step=hook, stepwise=True, eta=eta, noise_seed=noise_seed, chain_keys=[0])
     return out.reshape(x.shape)
 
 
@@ -459,7 +487,8 @@ def draw_chain_starts(guid: Guidance, chains: Sequence[Tuple[int, Union[str, Goa
 def guided_chains(unet: Unet1d, guid: Guidance, sched: DDIMScheduler, mode: str, noise: torch.Tensor,
                   chains: Sequence[Tuple[int, Union[str, Goal]]], unguided: Optional[torch.Tensor] = None,
                   starts: Optional[StartStream] = None, trace: Optional[list] = None, predrawn=None,
-                  global_cond: Optional[torch.Tensor] = None, cfg_weight: float = 1.0, edit: Optional[Edit] = None) -> torch.Tensor:
+                  global_cond: Optional[torch.Tensor] = None, cfg_weight: float = 1.0, edit: Optional[Edit] = None, eta: float = 0.0,
+                  noise_seed: int = 0, shared_step_noise: bool = False, chain_keys: Optional[Sequence[int]] = None) -> torch.Tensor:
     """``Diffusion.guided_sample`` loop bodies (:561-576) for the chains [(object index, opt_obj), ...]; opt_obj: a reference
     objective name or a ``Goal`` (dgdm_amd/goal.py), whose chain is guided by the goal's row field.
 
@@ -468,7 +497,13 @@ def guided_chains(unet: Unet1d, guid: Guidance, sched: DDIMScheduler, mode: str,
 
     edit (dgdm_amd/edit.py): every chain then starts from the edit's designs noised with `noise`, runs the schedule's last K steps (the
     3-D start draws are made for K steps) and clips every step's predicted clean sample to the edit's bounds.  The centres of a
-    'convergence' chain of an edit come from the SOURCE DESIGNS, not from an unguided sample: `unguided` is not read."""
+    'convergence' chain of an edit come from the SOURCE DESIGNS, not from an unguided sample: `unguided` is not read.
+
+    eta > 0 (run_chains): chain k's steps draw the noise keyed (noise_seed, chain_keys[k]); chain_keys None: the chain's index in
+    `chains` (dist.guided_chains_sharded passes the GLOBAL indices of its slice).  A pair may appear several times in `chains`: at
+    eta = 0 its replicas are identical, at eta > 0 they diverge through their keys - that is how one asks for several candidate designs
+    per task; with an edit, for several edits of one design (the bounded clip is inside the same step).  shared_step_noise=True gives
+    every chain key 0: common random numbers, for comparing objectives on equal noise (replicas are then identical again)."""
     nc, (B, L, _) = len(chains), noise.shape
     engine.chain_cond_layout(global_cond, unet.global_cond_dim, nc, B)       # a condition of the wrong shape is refused before anything runs
     dev = noise.device
@@ -497,7 +532,8 @@ def guided_chains(unet: Unet1d, guid: Guidance, sched: DDIMScheduler, mode: str,
             rc[c] = guid.rowcoef(centers[k])
         rowcoef = torch.from_numpy(rc).to(dev)
     out = run_chains(unet, guid, sched, noise.reshape(B, L), nc, 1, objectives, rowcoef, step_starts, timesteps,
-                     [chain_scale(mode, o) for _, o in chains], global_cond, cfg_weight, bounds, trace=trace)
+                     [chain_scale(mode, o) for _, o in chains], global_cond, cfg_weight, bounds, trace=trace, eta=eta, noise_seed=noise_seed,
+                     chain_keys=step_noise_keys(nc, shared_step_noise, chain_keys))
     return out.reshape(nc, B, L, 1)
 
 
@@ -505,9 +541,10 @@ def guided_chains(unet: Unet1d, guid: Guidance, sched: DDIMScheduler, mode: str,
 def guided_multi_object(unet: Unet1d, guid: Guidance, sched: DDIMScheduler, mode: str, noise: torch.Tensor,
                         object_indices: Sequence[int], opt_obj: Union[str, Goal], starts: Optional[StartStream] = None,
                         on_step=None, global_cond: Optional[torch.Tensor] = None, cfg_weight: float = 1.0,
-                        edit: Optional[Edit] = None) -> torch.Tensor:
+                        edit: Optional[Edit] = None, eta: float = 0.0, noise_seed: int = 0, shared_step_noise: bool = False) -> torch.Tensor:
     """``Diffusion.guided_sample_multi_object`` loop (:637-647): one chain, gradient = mean over the objects.  opt_obj: a reference
-    objective name or a ``Goal``.  global_cond (B, gc), cfg_weight, edit: as in guided_chains."""
+    objective name or a ``Goal``.  global_cond (B, gc), cfg_weight, edit: as in guided_chains.  eta, noise_seed: stochastic steps as
+    in run_chains; the one chain has key 0 (dist.guided_multi_object_sharded steps it with the same key on every rank)."""
     n_obj, (B, L, _) = len(object_indices), noise.shape
     engine.check_global_cond(global_cond, unet.global_cond_dim, B)
     is3d = mode == 'point_3d'
@@ -523,7 +560,7 @@ def guided_multi_object(unet: Unet1d, guid: Guidance, sched: DDIMScheduler, mode
     st = starts.calls(guid.rows, len(timesteps) * n_obj).reshape(len(timesteps), -1) if is3d else None
     hook = None if on_step is None else lambda i, x, eps: on_step(i, x.reshape(B, L, 1))      # the harness's per-step plots (:648-674)
     out = run_chains(unet, guid, sched, noise.reshape(B, L), 1, n_obj, objectives, None, st, timesteps, [chain_scale(mode, opt_obj, multi=True)],
-                     global_cond, cfg_weight, bounds, on_step=hook)
+                     global_cond, cfg_weight, bounds, on_step=hook, eta=eta, noise_seed=noise_seed, chain_keys=[0])
     return out.reshape(B, L, 1)
 
 
@@ -552,12 +589,14 @@ def draw_ensemble_starts(guid: Guidance, n_groups: int, n_obj: int, n_steps: int
 def guided_multi_object_groups(unet: Unet1d, guid: Guidance, sched: DDIMScheduler, mode: str, noise: torch.Tensor,
                                groups: Sequence[Sequence[int]], opt_objs: Sequence[Union[str, Goal]], streams: Optional[Sequence[StartStream]] = None,
                                predrawn: Optional[np.ndarray] = None, python_loop: bool = False, global_cond: Optional[torch.Tensor] = None,
-                               cfg_weight: float = 1.0, edit: Optional[Edit] = None) -> torch.Tensor:
+                               cfg_weight: float = 1.0, edit: Optional[Edit] = None, eta: float = 0.0, noise_seed: int = 0,
+                               shared_step_noise: bool = False, chain_keys: Optional[Sequence[int]] = None) -> torch.Tensor:
     """Several independent ``guided_sample_multi_object`` chains (:637-647) in the same launches: chain k averages the guidance
     gradients of the objects ``groups[k]`` for objective ``opt_objs[k]`` (a guidance ensemble: n_obj dynamics-gradient
     evaluations per denoise step).  All groups have the same size.  Launch order of the gradient chains is object-major,
     (j, k) -> j * K + k, so the mean over j is one strided reduction for every group at once.  Returns (K, B, L, 1).
-    edit: as in guided_chains - every group edits the same designs, and `predrawn` then holds the draws of the edit's steps."""
+    edit: as in guided_chains - every group edits the same designs, and `predrawn` then holds the draws of the edit's steps.
+    eta, noise_seed, shared_step_noise, chain_keys: as in guided_chains, group k being chain k."""
     K, n_obj, (B, L, _) = len(groups), len(groups[0]), noise.shape
     assert all(len(g) == n_obj for g in groups) and len(opt_objs) == K
     engine.chain_cond_layout(global_cond, unet.global_cond_dim, K, B)       # global_cond: (B, gc) for all groups or (K, B, gc)
@@ -576,5 +615,6 @@ def guided_multi_object_groups(unet: Unet1d, guid: Guidance, sched: DDIMSchedule
         raise ValueError(f"guided_multi_object_groups: the groups' classifier scales differ ({sorted(scales)}); give the Goals one scale")
     # K chains x n_obj gradients each, gradient chains object-major
     out = run_chains(unet, guid, sched, noise.reshape(B, L), K, n_obj, objectives, None, predrawn if is3d else None, timesteps, [scales.pop()] * K,
-                     global_cond, cfg_weight, bounds, stepwise=python_loop)
+                     global_cond, cfg_weight, bounds, stepwise=python_loop, eta=eta, noise_seed=noise_seed,
+                     chain_keys=step_noise_keys(K, shared_step_noise, chain_keys))
     return out.reshape(K, B, L, 1)

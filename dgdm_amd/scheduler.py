@@ -47,19 +47,58 @@ class DDIMScheduler:
         ratio = self.config.num_train_timesteps // self.num_inference_steps
         self.timesteps = torch.from_numpy((np.arange(0, self.num_inference_steps) * ratio).round()[::-1].copy().astype(np.int64))
 
-    def coefficients(self, t: int) -> Tuple[float, float, float, float]:
-        """float32 sqrt(abar_t), sqrt(1-abar_t), sqrt(abar_prev), sqrt(1-abar_prev) as the reference's tensor ops give them."""
+    def coefficients(self, t: int, eta: Optional[float] = None):
+        """float32 sqrt(abar_t), sqrt(1-abar_t), sqrt(abar_prev), sqrt(1-abar_prev) as the reference's tensor ops give them.
+
+        eta given: those four followed by (sigma, dir) of ``eta_coefficients`` - six values."""
         t = int(t)
         prev = t - self.config.num_train_timesteps // self.num_inference_steps
         a_t = self.alphas_cumprod[t]
         a_p = self.alphas_cumprod[prev] if prev >= 0 else self.final_alpha_cumprod
-        return (float(a_t ** 0.5), float((1 - a_t) ** 0.5), float(a_p ** 0.5), float((1 - a_p) ** 0.5))
+        four = (float(a_t ** 0.5), float((1 - a_t) ** 0.5), float(a_p ** 0.5), float((1 - a_p) ** 0.5))
+        return four if eta is None else four + self.eta_coefficients(t, eta)
 
-    def step(self, model_output: torch.Tensor, timestep, sample: torch.Tensor, eta: float = 0.0, bounds=None, **unused) -> DDIMSchedulerOutput:
-        """bounds (not a diffusers argument): an edit's (lo, hi) per entry, which replace clip_sample's [-1, 1] (dgdm_amd/edit.py)."""
-        if eta != 0.0:
-            raise NotImplementedError("the reference always steps with eta = 0")
-        return DDIMSchedulerOutput(engine.ddim_guided_step(sample, model_output, None, 0, self.coefficients(int(timestep)), 0.0, bounds))
+    def eta_coefficients(self, t: int, eta: float) -> Tuple[float, float]:
+        """(sigma, dir) of the stochastic step, diffusers 0.11.1 ``DDIMScheduler.step(eta=...)`` restated in the float32 tensor
+        operations it uses (``_get_variance``, ``std_dev_t = eta * variance ** 0.5``, ``(1 - alpha_prod_t_prev - std_dev_t**2) ** 0.5``):
+
+            variance = (1 - abar_prev) / (1 - abar_t) * (1 - abar_t / abar_prev)
+            sigma    = eta * variance ** 0.5
+            dir      = (1 - abar_prev - sigma**2) ** 0.5
+            x_prev   = sqrt(abar_prev) * clip(x0_pred) + dir * eps + sigma * z
+
+        with ``clip_sample=True``, ``use_clipped_model_output=False`` (eps is NOT re-derived from the clipped x0) and epsilon prediction.
+        The last step has abar_prev = final_alpha_cumprod = 1, hence sigma = 0: no noise enters a finished design.  eta = 0 gives
+        dir == sqrt(1-abar_prev) of ``coefficients`` bit for bit.  diffusers is not on hand to compare with: parity unpinned, like the
+        eta = 0 step."""
+        t = int(t)
+        prev = t - self.config.num_train_timesteps // self.num_inference_steps
+        a_t = self.alphas_cumprod[t]
+        a_p = self.alphas_cumprod[prev] if prev >= 0 else self.final_alpha_cumprod
+        variance = (1 - a_p) / (1 - a_t) * (1 - a_t / a_p)
+        sigma = float(eta) * variance ** 0.5
+        return (float(sigma), float((1 - a_p - sigma ** 2) ** 0.5))
+
+    def step(self, model_output: torch.Tensor, timestep, sample: torch.Tensor, eta: float = 0.0, bounds=None, variance_noise=None,
+             noise_key=None, **unused) -> DDIMSchedulerOutput:
+        """bounds (not a diffusers argument): an edit's (lo, hi) per entry, which replace clip_sample's [-1, 1] (dgdm_amd/edit.py).
+
+        eta > 0 needs a noise source: ``variance_noise``, a tensor like `sample` (diffusers' own argument), or ``noise_key = (seed, key,
+        step_index)`` (not a diffusers argument), the keyed device normal of include/dgdm_hip.h for ONE chain: `sample` as a whole is the
+        chain, element for element.  Neither: ValueError - this scheduler does not draw from a torch generator."""
+        coef = self.coefficients(int(timestep))
+        if eta == 0.0:
+            return DDIMSchedulerOutput(engine.ddim_guided_step(sample, model_output, None, 0, coef, 0.0, bounds))
+        if variance_noise is None and noise_key is None:
+            raise ValueError("eta > 0 needs variance_noise or noise_key=(seed, key, step_index)")
+        if variance_noise is not None and noise_key is not None:
+            raise ValueError("variance_noise and noise_key are two sources of the same noise: give one")
+        kw = dict(variance_noise=variance_noise)
+        if noise_key is not None:
+            seed, key, step_index = noise_key
+            kw = dict(seed=int(seed), chain_keys=[int(key)], step_index=int(step_index))
+        return DDIMSchedulerOutput(engine.ddim_guided_step(sample, model_output, None, 0, coef, 0.0, bounds,
+                                                           eta_coef=self.eta_coefficients(int(timestep), eta), **kw))
 
     def add_noise(self, original_samples: torch.Tensor, noise: torch.Tensor, timesteps: torch.Tensor) -> torch.Tensor:
         ts = torch.unique(timesteps.detach().cpu())

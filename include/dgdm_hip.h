@@ -132,6 +132,29 @@ int dgdm_ddim_guided_step(const float *x_dev, const float *eps_dev, const float 
 int dgdm_ddim_guided_step_bounded(const float *x_dev, const float *eps_dev, const float *grad_dev, int n_grad, float *x_next_dev, int64_t n,
                                   float sqrt_abar_t, float sqrt_1m_abar_t, float sqrt_abar_prev, float sqrt_1m_abar_prev, float guidance_scale,
                                   const float *lo_dev, const float *hi_dev, int64_t period, void *stream);
+/* The stochastic step, eta > 0 (extends dgdm_ddim_guided_step / _bounded; diffusers 0.11.1 DDIMScheduler.step(eta, variance_noise),
+ * restated from the published algorithm - parity unpinned, as the eta = 0 step):
+ *   x_prev = sqrt_abar_prev * clip(x0) + dir * eps + sigma * z,  rounded as add(add(mul, mul), mul), nothing fused;
+ *   sigma = eta * sqrt((1 - abar_prev) / (1 - abar_t) * (1 - abar_t / abar_prev)),  dir = sqrt(1 - abar_prev - sigma^2)   (host, float32).
+ * lo_dev == hi_dev == NULL: the [-1, 1] clip; both given: the per-entry clip of _bounded (period as there).
+ * z is noise_dev[i] when noise_dev is given (diffusers' variance_noise), otherwise the keyed device normal below.
+ * sigma == 0 launches the eta = 0 kernel with sqrt_1m_abar_prev = dir: bit for bit dgdm_ddim_guided_step / _bounded.
+ *
+ * The keyed normal (THE recipe: tests/step_noise_oracle.py states the same text in numpy).  Entry i of the step belongs to chain
+ * c = i / per_chain and is element e = i % per_chain of it (per_chain > 0 divides n; chain_keys_dev [n / per_chain] uint64, device):
+ *   r0, r1 = raw outputs 2e, 2e + 1 of numpy.random.Philox(key=[seed, chain_keys[c]], counter=[0, step_index, 0, 0]).random_raw():
+ *            Philox4x64-10, block counter (e / 2 + 1, step_index, 0, 0) (numpy counts up before a block), lanes 2 (e & 1), 2 (e & 1) + 1;
+ *   u1 = ((r0 >> 11) + 1) * 2^-53  in (0, 1],   u2 = (r1 >> 11) * 2^-53  in [0, 1);
+ *   z  = (float)( sqrt(-2 ln u1) * cos(6.283185307179586 * u2) )    every operation float64, one rounding to float32 at the end.
+ * z depends on (seed, chain key, step_index, e) only - not on the chain's place in the launch, the launch geometry, the rank or how a
+ * run is split into calls.  |z| <= sqrt(2 * 53 ln 2) < 8.6: always finite.                                                            */
+int dgdm_ddim_guided_step_noisy(const float *x_dev, const float *eps_dev, const float *grad_dev, int n_grad, float *x_next_dev, int64_t n,
+                                float sqrt_abar_t, float sqrt_1m_abar_t, float sqrt_abar_prev, float dir, float guidance_scale,
+                                const float *lo_dev, const float *hi_dev, int64_t period, float sigma, const float *noise_dev,
+                                uint64_t seed, const uint64_t *chain_keys_dev, int64_t step_index, int64_t per_chain, void *stream);
+/* Debug / test entry: the z values of the recipe above -> z_dev [n_chains][per_chain] float32. */
+int dgdm_ddim_step_noise(uint64_t seed, const uint64_t *chain_keys_dev, int n_chains, int64_t step_index, int64_t per_chain, float *z_dev,
+                         void *stream);
 /* DDIMScheduler.add_noise (diffusion.py:145,185): out = sqrt_abar*x0 + sqrt_1m_abar*noise */
 int dgdm_ddim_add_noise(const float *x0_dev, const float *noise_dev, float *out_dev, int64_t n,
                         float sqrt_abar, float sqrt_1m_abar, void *stream);
@@ -319,6 +342,18 @@ int dgdm_guided_chains_run_bounded(DgdmUnet1d *unet, DgdmGuidance *g, const floa
                                    const int32_t *timesteps, const float *coef, const float *scales, int n_steps, float *x_out_dev,
                                    const float *global_cond_dev, int64_t cond_chain_stride, float cfg_weight, const float *lo_dev,
                                    const float *hi_dev, void *stream);
+/* The same with stochastic steps (dgdm_ddim_guided_step_noisy); the single body of the four entries.
+ *   eta_coef    [n_steps][2] host = sigma, dir per step, or NULL: every step has sigma = 0, dir = coef[.][3] (dgdm_guided_chains_run_bounded)
+ *   seed        the noise seed of the run
+ *   chain_keys  [n_chains] host: chain k's step si draws the stream of key (seed, chain_keys[k]) at step_index si - the chain's global
+ *               identity, so a run split over calls or ranks draws what the single call draws; NULL: 0 .. n_chains - 1
+ * A step with sigma == 0 (the last one: abar_prev = 1) is the eta = 0 step.  Equivalent, bit for bit, to the step-by-step composition
+ * with dgdm_ddim_guided_step_noisy as its last call.                                                                                 */
+int dgdm_guided_chains_run_noisy(DgdmUnet1d *unet, DgdmGuidance *g, const float *noise_dev, int n_chains, int n_grad,
+                                 const DgdmObjective *objectives, const float *rowcoef_dev, const int64_t *starts_host,
+                                 const int32_t *timesteps, const float *coef, const float *scales, int n_steps, float *x_out_dev,
+                                 const float *global_cond_dev, int64_t cond_chain_stride, float cfg_weight, const float *lo_dev,
+                                 const float *hi_dev, const float *eta_coef, uint64_t seed, const uint64_t *chain_keys, void *stream);
 
 /* Forward-only sweep of Diffusion.get_convergence_centers (diffusion.py:506-531): G orientations,
  * pos = 0, t = 0, rows r = g*B + b.  logits_dev [n_chains][B*G][3].  starts_host (3-D) holds
