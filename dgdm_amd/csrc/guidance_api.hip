@@ -66,6 +66,7 @@ struct DgdmGuidance {
     static constexpr int NBUILD = 3;             // most objects whose tables are built concurrently (own stream + 0.5 GB of temporaries each)
     DevBuf pool_crowded, pool_clist, pool_off, pool_pairs, pool_rank, pool_F1, pool_U;   // [n_objects] x the light build stages' outputs (built by one launch per stage)
     DevBuf pool_xyz, pool_fps1, pool_fps2, pool_flags, pool_ncr;   // [n_objects] x per-object FPS tables (ObjectTables point into these), crowded-centre counts
+    DevBuf pool_fps1t;                              // float32 build: [n_objects] x fps1 by position [64][N] x 16 B (l2sel_kernel reads it with the variants on its lanes)
     DevBuf tmpY[NBUILD], tmpL2[NBUILD], vlist;      // 3-D table-build temporaries of the heavy stages (per build stream)
     DevBuf tmpShare[NBUILD];                        // float32 build: the selection stage's outputs (pointnet.h L2Share), carved out of one buffer
     hipStream_t bstream[NBUILD] = {};
@@ -385,6 +386,7 @@ int DgdmGuidance::build_object(int oi, int slot, hipStream_t s) {
             sh.nitems = reinterpret_cast<int *>(b); b += 4 * sizeof(int);
             sh.rep = reinterpret_cast<short *>(b); b += NN * sizeof(short);
             sh.cnt = reinterpret_cast<unsigned char *>(b);
+            sh.fps1t = pool_fps1t.as<uint4>() + (size_t)oi * N * 64;
         }
         if ((rc = pn_l2(xyz, N, w, t.fps1, vlist.as<int>(), N, tY.as<float>(), tL2.as<float>(), t.clist, t.clist + N,
                         off, rank, false, s, shared ? 1 : 0, shared ? &sh : nullptr))) return rc;  // T5
@@ -460,7 +462,8 @@ extern "C" int dgdm_guidance_set_objects(DgdmGuidance *g, const float *objects_d
             (rc = g->pool_ncr.alloc(no * sizeof(int))) || (rc = g->pool_crowded.alloc(no * N * sizeof(int))) ||
             (rc = g->pool_clist.alloc(no * (N + 1) * sizeof(int))) || (rc = g->pool_off.alloc(no * (N + 1) * sizeof(int))) ||
             (rc = g->pool_pairs.alloc(no * N * N * sizeof(int))) || (rc = g->pool_rank.alloc(no * N * N * sizeof(short))) ||
-            (rc = g->pool_F1.alloc(no * N * 128 * 8)) || (rc = g->pool_U.alloc(no * N * 128 * 8)))
+            (rc = g->pool_F1.alloc(no * N * 128 * 8)) || (rc = g->pool_U.alloc(no * N * 128 * 8)) ||
+            (rc = g->pool_fps1t.alloc(no * N * 64 * sizeof(uint4))))
             return rc;
         if (!g->pooled) DGDM_HIP_CHECK(hipEventCreateWithFlags(&g->pooled, hipEventDisableTiming));
         DGDM_HIP_CHECK(hipMemcpyAsync(g->pool_xyz.p, objects_dev, no * N * 3 * 4, hipMemcpyDeviceToDevice, s));
@@ -478,6 +481,9 @@ extern "C" int dgdm_guidance_set_objects(DgdmGuidance *g, const float *objects_d
         // sa2's FPS table is the first 128 columns of sa1's (same clouds, same starts): one pass writes both and the tie flags
         if ((rc = pn_fps_tables(g->pool_xyz.as<float>(), N, N, g->pool_fps1.as<int>(), g->pool_fps2.as<int>(), g->pool_flags.as<int>(), fs, n_objects)))
             return rc;
+        // the float32 build's selection stage reads the table by position (variants on its lanes): a transposed copy behind it
+        if (!g->bf16 && !g->l2_gather_mode && N <= 512 &&
+            (rc = pn_fps_transpose(g->pool_fps1.as<int>(), N, g->pool_fps1t.as<uint4>(), fs, n_objects))) return rc;
         DGDM_HIP_CHECK(hipEventRecord(g->bstart, fs));
         for (int i = 0; i < n_objects; ++i) {
             ObjectTables &t = *g->tables[i];

@@ -94,6 +94,7 @@ int pn_index_rows(const float *points, const int *idx, int B, int N, int M, int 
 // The float32 table build computes each DISTINCT first-64 selection of a crowded centre once (l2sel_kernel): Z[v][c] depends on the variant v
 // only through which points of c's ball come first in the order fps1[v], as a set.  Per crowded centre (position ci in clist) and variant:
 struct L2Share {
+    const uint4 *fps1t;           // in: [64][N] the FPS table by position, 8 positions of a start per entry (pn_fps_transpose)
     unsigned char *sel;           // [N][nv][64] the selection: rows of the centre's block of the pair list (K <= 255; l2c_kernel's bytes)
     unsigned char *cnt;           // [N][nv] their number
     short *rep;                   // [N][nv] the smallest variant whose selection is the same set (a ball of K > 255 points: v itself)
@@ -105,6 +106,8 @@ int pn_fps_table(const float *xyz, int N, int nv, int npoint, int *out, int *fla
 // sa1's and sa2's tables from ONE pass of 512 iterations per start: fps1 [nobj][nv][512], fps2 [nobj][nv][128] = its first 128 columns,
 // flags [nobj][nv] = the 128-sequence was order-dependent
 int pn_fps_tables(const float *xyz, int N, int nv, int *fps1, int *fps2, int *flags, hipStream_t s, int nobj = 1);
+// fps1t [nobj][64][nv] from fps1 [nobj][nv][512]: entry [b][v] = fps1[v][8 b .. 8 b + 7] as eight 16-bit numbers, twice the point id each
+int pn_fps_transpose(const int *fps1, int nv, uint4 *fps1t, hipStream_t s, int nobj = 1);
 int pn_sa1(const float *xyz, int N, const PnWeights &w, float *F1, hipStream_t s, int nobj = 1);      // nobj > 1: pools [nobj][N][..]
 // crowded/clist/ncr: centres whose ball holds > 64 points; off [N+1], pairs [<= N*N], rank [N][N]: the in-radius pair list (T4/T5)
 int pn_crowd(const float *xyz, int N, const PnWeights &w, int *crowded, int *clist, int *ncr, int *off, int *pairs, short *rank, hipStream_t s,

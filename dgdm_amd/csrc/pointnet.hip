@@ -141,6 +141,25 @@ __global__ __launch_bounds__(256) void fps_table_kernel(const float *__restrict_
     }
 }
 
+// The FPS table by position for the float32 build's selection stage, which runs with the variants on its lanes (l2sel_kernel):
+// fps1t[obj][b][start] = the 8 entries fps1[obj][start][8 b .. 8 b + 7] as 16-bit numbers, each TWICE the point id (the byte offset of
+// the point in a row of the rank table), so that a lane fetches 8 positions of its variant with one 16-byte load and a wave's loads are
+// contiguous.  32 x 32 tiles through LDS, both sides coalesced.
+__global__ __launch_bounds__(256) void fps_transpose_kernel(const int *__restrict__ fps1 /*[nv][512]*/, int nv, uint4 *__restrict__ fps1t /*[64][nv]*/) {
+    __shared__ int tile[32][33];
+    fps1 += (size_t)blockIdx.z * nv * 512; fps1t += (size_t)blockIdx.z * nv * 64;
+    const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
+    const int p0 = blockIdx.x * 32, v0 = blockIdx.y * 32;
+    for (int j = ty; j < 32; j += 8)
+        if (v0 + j < nv) tile[j][tx] = fps1[(size_t)(v0 + j) * 512 + p0 + tx];
+    __syncthreads();
+    if (ty < 4 && v0 + tx < nv) {
+        const int *t = &tile[tx][8 * ty];
+        fps1t[(size_t)(p0 / 8 + ty) * nv + v0 + tx] = make_uint4((uint32_t)(2 * t[0]) | (uint32_t)(2 * t[1]) << 16, (uint32_t)(2 * t[2]) | (uint32_t)(2 * t[3]) << 16,
+                                                                  (uint32_t)(2 * t[4]) | (uint32_t)(2 * t[5]) << 16, (uint32_t)(2 * t[6]) | (uint32_t)(2 * t[7]) << 16);
+    }
+}
+
 // ------------------------------------------------------------------------------------------------ T2
 // sa1 feature of every point p as a centre: first 32 in-radius (r=0.2) points in index order, padded with
 // the first; Conv(3->64)+BN+ReLU, Conv(64->128)+BN+ReLU, max  (pointnet2.py:17, pointnet2_utils.py:95-146,203-208)
@@ -469,96 +488,118 @@ __device__ __forceinline__ void l2c_reduce(const uint32_t *ych, const unsigned c
     if (sg == 0) *reinterpret_cast<u4 *>(dst + fl * 4) = best;
 }
 
-// T5's selection stage of the float32 build: one workgroup per crowded centre, ALL variants.  Each variant's first-64 selection (the
-// code of l2c_centre's selection phase), its membership mask over the centre's ball (256 bits: K <= 255), rep[v] = the smallest variant
-// with an equal mask (whole masks compared; the hash only pre-filters) and the list of (centre, variant) pairs with rep == v, v >= 1.
+// T5's selection stage of the float32 build: one workgroup per crowded centre, ALL variants.  Each variant's first-64 selection, its
+// membership mask over the centre's ball (256 bits: K <= 255), rep[v] = the smallest variant with an equal mask and the list of
+// (centre, variant) pairs with rep == v, v >= 1.
 // Equal sets give equal bits: l2c_reduce takes an unsigned maximum, which does not depend on order or multiplicity.
-constexpr int L2S_THREADS = 1024;
-__global__ __launch_bounds__(L2S_THREADS) void l2sel_kernel(int N, const int *__restrict__ fps1 /*[N][512]*/, int nv, const int *__restrict__ clist,
+// The selection runs with the VARIANTS ON THE LANES: the scan over the positions of the FPS order is the same for every variant of a
+// centre, only the order differs, so thread v walks column v of the table by position (fps_transpose_kernel: 8 positions per 16-byte
+// load, a wave's loads contiguous) and appends the in-ball points to its own row of LDS until it holds 64 - some 20 instructions per
+// position for 64 variants, where a wave per (centre, variant) spent ~200 per 64 positions on ballots, prefix counts and 64
+// same-address LDS atomics.  A wave stops once all its lanes are full.
+// The representatives come from rounds of a hash table in LDS instead of every variant comparing itself with all smaller ones (512
+// dependent LDS reads for the last wave): the unresolved variants put their number into the slot of their mask's hash with an atomic
+// minimum; a variant whose slot holds a variant with an EQUAL MASK (whole masks compared) has found its representative - the smallest
+// of its class, since the whole class shares the slot and is still in play - the others go to the next round, where the slots are
+// dealt differently.  Every round settles at least the class of each slot's winner; 1024 slots settle 512 variants in 3-4 rounds.
+constexpr int L2S_THREADS = 512;                // = the most variants (pn_l2: nv <= 512)
+constexpr int L2S_SELROW = 68, L2S_MASKROW = 9; // LDS rows of a variant: 64 selection bytes / 8 mask words, padded by one bank
+constexpr int L2S_SLOTS = 1024;
+__global__ __launch_bounds__(L2S_THREADS) void l2sel_kernel(int N, int nv, const int *__restrict__ clist,
                                                             const int *__restrict__ ncr, const int *__restrict__ off,
                                                             const short *__restrict__ rank, const L2Share sh) {
     __shared__ short rks[1024];
-    __shared__ uint32_t mask[512][8];
-    __shared__ uint32_t hash[512];
-    __shared__ int selw[L2S_THREADS / 64][64];
-    __shared__ int wsum[L2S_THREADS / 64], base_s;
+    __shared__ __attribute__((aligned(4))) unsigned char sel[512 * L2S_SELROW];
+    __shared__ uint32_t mask[512 * L2S_MASKROW];
+    __shared__ uint32_t hash[512], slot[L2S_SLOTS];
+    __shared__ int wsum[L2S_THREADS / 64], base_s, pending;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, nwave = L2S_THREADS / 64;
     const int n = *ncr;
+    const int v = tid;                                                   // a thread per variant
+    const bool act = v < nv;
     for (int ci = blockIdx.x; ci < n; ci += gridDim.x) {
         const int c = clist[ci];
         const int K = off[c + 1] - off[c];
         short *repg = sh.rep + (size_t)ci * nv;
         if (K > 255) {
             // a ball with more points than a byte can index: no sharing, every variant is its own representative (l2c_centre selects itself)
-            for (int v = tid; v < nv; v += L2S_THREADS) repg[v] = (short)v;
+            if (act) repg[v] = (short)v;
             if (tid == 0) {
                 base_s = atomicAdd(sh.nitems, nv - 1);
                 sh.coff[ci] = base_s; sh.ccnt[ci] = nv - 1;
             }
             __syncthreads();
-            for (int v = 1 + tid; v < nv; v += L2S_THREADS) sh.items[base_s + v - 1] = (ci << 16) | v;
+            if (act && v >= 1) sh.items[base_s + v - 1] = (ci << 16) | v;
             __syncthreads();
             continue;
         }
         for (int i = tid; i < N; i += L2S_THREADS) rks[i] = rank[(size_t)c * N + i];
+        unsigned char *selv = sel + v * L2S_SELROW;
+        uint32_t *mv = mask + v * L2S_MASKROW;
+#pragma unroll
+        for (int i = 0; i < 8; ++i) mv[i] = 0u;
         __syncthreads();
-        // (the 512 candidates of the next variant are loaded while the current one is scanned, as in l2c_centre)
-        int pv[8], pn[8];
+        // ---- selection: positions in batches of 8, the next batch's loads in flight while this one is scanned
+        int cnt = act ? 0 : 64, last = 0;                                // an idle lane counts as full
+        const uint4 *col = sh.fps1t + (act ? v : 0);
+        uint4 pn = col[0];
+        for (int b = 0; b < 64; ++b) {
+            const uint4 pv = pn;
+            if (b + 1 < 64) pn = col[(size_t)(b + 1) * N];
+            const uint32_t w[4] = {pv.x, pv.y, pv.z, pv.w};
+            int rk[8];
 #pragma unroll
-        for (int i = 0; i < 8; ++i) pn[i] = wave < nv ? fps1[(size_t)wave * 512 + 64 * i + lane] : 0;
-        for (int v = wave; v < nv; v += nwave) {
+            for (int k = 0; k < 8; ++k)                                  // the batch's 8 rank reads together: one LDS latency, not 8
+                rk[k] = *reinterpret_cast<const short *>(reinterpret_cast<const char *>(rks) + ((w[k >> 1] >> (16 * (k & 1))) & 0xffffu));
 #pragma unroll
-            for (int i = 0; i < 8; ++i) pv[i] = pn[i];
-            const int vn = v + nwave;
-            if (vn < nv) {
-#pragma unroll
-                for (int i = 0; i < 8; ++i) pn[i] = fps1[(size_t)vn * 512 + 64 * i + lane];
-            }
-            if (lane < 8) mask[v][lane] = 0u;
-            int cnt = 0;
-#pragma unroll
-            for (int i = 0; i < 8; ++i) {                                 // l2_select on the registers
-                if (cnt >= 64) break;
-                const int r = rks[pv[i]];
-                const bool in = r >= 0;
-                const unsigned long long m = __ballot(in);
-                const int pos = cnt + __popcll(m & ((1ull << lane) - 1ull));
-                if (in && pos < 64) selw[wave][pos] = r;
-                cnt += __popcll(m);
-            }
-            cnt = min(cnt, 64);
-            __builtin_amdgcn_wave_barrier();
-            const int r = selw[wave][lane < cnt ? lane : max(cnt - 1, 0)] & 255;
-            if (lane < cnt) atomicOr(&mask[v][r >> 5], 1u << (r & 31));
-            sh.sel[((size_t)ci * nv + v) * 64 + lane] = (unsigned char)r;
-            if (lane == 0) sh.cnt[(size_t)ci * nv + v] = (unsigned char)cnt;
-            __builtin_amdgcn_wave_barrier();
-        }
-        __syncthreads();
-        uint32_t mine[8];
-        const int v = tid;                                               // nv <= 512 < L2S_THREADS: a thread per variant
-        if (v < nv) {
-            uint32_t h = 0x811c9dc5u;
-#pragma unroll
-            for (int i = 0; i < 8; ++i) { mine[i] = mask[v][i]; h = (h ^ mine[i]) * 0x01000193u; }
-            hash[v] = h;
-        }
-        __syncthreads();
-        bool isrep = false;
-        if (v < nv) {
-            const uint32_t hv = hash[v];
-            int rep = v;
-            for (int u = 0; u < v; ++u) {
-                if (hash[u] == hv && rep == v) {
-                    bool eq = true;
-#pragma unroll
-                    for (int i = 0; i < 8; ++i) eq = eq && mask[u][i] == mine[i];
-                    if (eq) rep = u;
+            for (int k = 0; k < 8; ++k) {
+                const int r = rk[k];
+                if (r >= 0 && cnt < 64) {
+                    selv[cnt++] = (unsigned char)r;
+                    atomicOr(&mv[r >> 5], 1u << (r & 31));               // the lane's own word (ds_or_b32, nothing waits for it)
+                    last = r;
                 }
             }
-            repg[v] = (short)rep;
-            isrep = rep == v && v >= 1;
+            if (__all(cnt >= 64)) break;
         }
+        for (int j = cnt; j < 64; ++j) selv[j] = (unsigned char)last;    // lanes past cnt repeat the last member
+        if (act) sh.cnt[(size_t)ci * nv + v] = (unsigned char)cnt;
+        __syncthreads();
+        {   // sel[ci][v][64] out, 16 dwords per variant: consecutive threads write consecutive dwords
+            uint32_t *dst = reinterpret_cast<uint32_t *>(sh.sel) + (size_t)ci * nv * 16;
+            for (int d = tid; d < nv * 16; d += L2S_THREADS)
+                dst[d] = *reinterpret_cast<const uint32_t *>(sel + (d >> 4) * L2S_SELROW + (d & 15) * 4);
+        }
+        uint32_t mine[8], h = 0x811c9dc5u;
+        if (act) {
+#pragma unroll
+            for (int i = 0; i < 8; ++i) { mine[i] = mv[i]; h = (h ^ mine[i]) * 0x01000193u; }
+            hash[v] = h;
+        }
+        int rep = act ? -1 : v;                                          // -1: not settled yet
+        for (uint32_t round = 0;; ++round) {
+            for (int i = tid; i < L2S_SLOTS; i += L2S_THREADS) slot[i] = 0xffffffffu;
+            __syncthreads();
+            if (tid == 0) pending = 0;                                   // (everybody has read the last round's verdict)
+            const uint32_t s = (h * (0x9e3779b1u + 2u * round)) >> 22;   // the top 10 bits of a product with an odd constant: a new deal per round
+            if (rep < 0) atomicMin(&slot[s], (uint32_t)v);
+            __syncthreads();
+            if (rep < 0) {
+                const int u = (int)slot[s];                              // <= v
+                if (u == v) rep = v;
+                else if (hash[u] == h) {
+                    bool eq = true;
+#pragma unroll
+                    for (int i = 0; i < 8; ++i) eq = eq && mask[u * L2S_MASKROW + i] == mine[i];
+                    if (eq) rep = u;
+                }
+                if (rep < 0) pending = 1;
+            }
+            __syncthreads();
+            if (!pending) break;
+        }
+        if (act) repg[v] = (short)rep;
+        const bool isrep = act && rep == v && v >= 1;
         const unsigned long long m = __ballot(isrep);
         if (lane == 0) wsum[wave] = __popcll(m);
         __syncthreads();
@@ -1556,6 +1597,12 @@ int pn_fps_tables(const float *xyz, int N, int nv, int *fps1, int *fps2, int *fl
     return DGDM_OK;
 }
 
+int pn_fps_transpose(const int *fps1, int nv, uint4 *fps1t, hipStream_t s, int nobj) {
+    hipLaunchKernelGGL(fps_transpose_kernel, dim3(16, (nv + 31) / 32, nobj), dim3(256), 0, s, fps1, nv, fps1t);
+    DGDM_HIP_CHECK(hipGetLastError());
+    return DGDM_OK;
+}
+
 int pn_sa1(const float *xyz, int N, const PnWeights &w, float *F1, hipStream_t s, int nobj) {
     hipLaunchKernelGGL(sa1_kernel, dim3(std::min(N, 1024), nobj), dim3(128), 0, s, xyz, N, w.r1sq, w.sa1_w0t, w.sa1_b0, w.sa1_w1, w.sa1_b1, F1);
     DGDM_HIP_CHECK(hipGetLastError());
@@ -1587,7 +1634,7 @@ int pn_l2c(int N, const int *fps1, int nv, const float *Y, float *L2, const int 
         DGDM_HIP_CHECK(hipFuncSetAttribute((const void *)l2c_kernel<true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         attr_set = true;
     }
-    DGDM_REQUIRE(bf16 || share, DGDM_EINVAL, "pn_l2: the float32 crowded mode needs the selection stage's buffers");
+    DGDM_REQUIRE(bf16 || (share && share->fps1t), DGDM_EINVAL, "pn_l2: the float32 crowded mode needs the selection stage's buffers");
     // 64 x 4 = 256 workgroups, one per CU (150 KB of LDS each): ONE round whatever the number of crowded centres is (0 .. N: a few
     // objects of a batch have every centre crowded and carry most of the build's work), and 160 busy CUs at the typical 40
     constexpr int split = 4, gx = 64;
@@ -1599,7 +1646,7 @@ int pn_l2c(int N, const int *fps1, int nv, const float *Y, float *L2, const int 
         // the selection stage (one workgroup per crowded centre, all variants), then the representatives only
         DGDM_HIP_CHECK(hipMemsetAsync(share->nitems, 0, sizeof(int), s));
         // (a workgroup per possible centre: two of them fit a CU, so ONE round for any count; the surplus ones read the count and leave)
-        hipLaunchKernelGGL(l2sel_kernel, dim3(std::min(N, 512)), dim3(L2S_THREADS), 0, s, N, fps1, nv, clist, ncr, off, rank, *share);
+        hipLaunchKernelGGL(l2sel_kernel, dim3(std::min(N, 512)), dim3(L2S_THREADS), 0, s, N, nv, clist, ncr, off, rank, *share);
         hipLaunchKernelGGL((l2c_kernel<false, true>), grid, dim3(L2C_THREADS), lds, s, N, fps1, nv, reinterpret_cast<const uint32_t *>(Y),
                            reinterpret_cast<uint32_t *>(L2), clist, ncr, off, rank, *share);
     }
