@@ -102,6 +102,10 @@ PROTOTYPES = {
     "dgdm_guidance_set_row_field": (C.c_int, [_P, _P, C.c_int, _P]),
     "dgdm_guidance_goal_field": (C.c_int, [_P, _P, C.POINTER(GoalSpec), C.c_int, _P, _P]),
     "dgdm_guidance_score": (C.c_int, [_P, _P, C.c_int, C.POINTER(C.c_int32), _P, C.POINTER(C.c_float), C.c_int, _P, _P, _P, _P]),
+    "dgdm_guidance_objective_values": (C.c_int, [_P, _P, C.POINTER(Objective), _P, C.c_int, _P, _P]),
+    "dgdm_chain_resample": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_uint64, _P, C.c_int64, _P, _P, _P, _P, _P,
+                                      _P, _P]),
+    "dgdm_resample_uniform": (C.c_int, [C.c_uint64, _P, C.c_int, C.c_int64, _P, _P]),
     "dgdm_guided_chains_run": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.POINTER(Objective), _P, _P, C.POINTER(C.c_int32), C.POINTER(C.c_float),
                                          C.POINTER(C.c_float), C.c_int, _P, _P]),
     "dgdm_guided_chains_run_cond": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.POINTER(Objective), _P, _P, C.POINTER(C.c_int32), C.POINTER(C.c_float),

@@ -80,6 +80,7 @@ struct DgdmGuidance {
     std::vector<uint64_t> loopkeys_host;                       // ... what loopkeys holds
     DevBuf loopcond, loopx2, loopeps2;                         // ... with a condition: [cond rows | zero rows], and the doubled batch of the classifier-free mix
     DevBuf scorelogits;                      // dgdm_guidance_score: the logits when the caller does not want them
+    DevBuf valobj;                           // dgdm_guidance_objective_values: the device copy of the call's objectives
     // dgdm_guidance_rollout: the sweep's orientations [G] (built with the handle), and its scratch, grown on demand: the state
     // [n][B*G][3] doubles, one interaction's logits, the per-row pose operand tiles [ntiles][W1*32] and (3-D) their row maxima [ntiles][32]
     DevBuf sweep_ori, rollstate, rolllogits, rolltiles, rollpmax;
@@ -963,6 +964,23 @@ extern "C" int dgdm_guidance_score(DgdmGuidance *g, const float *x_dev, int time
         if ((rc = trunk_f16l_launch(kind, TrunkF16Mode::Forward, p, sc, s))) return rc;
     }
     return score_tally(logits_dev, n_chains, g->B, g->grid.cells, thr, counts_dev, sums_dev, s);
+}
+
+extern "C" int dgdm_guidance_objective_values(DgdmGuidance *g, const float *logits_dev, const DgdmObjective *objectives, const float *rowcoef_dev,
+                                              int n_chains, double *values_dev, void *stream) {
+    DGDM_REQUIRE(g && logits_dev && objectives && values_dev, DGDM_EINVAL, "dgdm_guidance_objective_values: null argument");
+    DGDM_REQUIRE(n_chains > 0 && n_chains <= g->cfg.max_chains, DGDM_EINVAL, "n_chains %d outside 1..%d", n_chains, g->cfg.max_chains);
+    int rc;
+    if ((rc = check_objectives(g, objectives, rowcoef_dev, n_chains))) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    std::vector<TrunkObjective> tob(n_chains);
+    for (int i = 0; i < n_chains; ++i) {
+        for (int j = 0; j < 3; ++j) { tob[i].lin[j] = objectives[i].lin[j]; tob[i].quad[j] = objectives[i].quad[j]; }
+        tob[i].use_rowcoef = objectives[i].use_rowcoef; tob[i].pad = 0;
+    }
+    if ((rc = g->valobj.alloc(sizeof(TrunkObjective) * g->cfg.max_chains))) return rc;
+    DGDM_HIP_CHECK(hipMemcpyAsync(g->valobj.p, tob.data(), sizeof(TrunkObjective) * n_chains, hipMemcpyHostToDevice, s));
+    return objective_values_launch(logits_dev, g->valobj.as<TrunkObjective>(), rowcoef_dev, g->rowfield, n_chains, g->B, g->grid.cells, values_dev, s);
 }
 
 // ================================================================================================ the denoise loop as one call

@@ -93,6 +93,12 @@ int rollout_update(const float *logits, const double scale[3], int k, int64_t ro
 // sums [n_chains][B][4] = sum d0, sum |d0|, sum d1, sum d2.  Fixed reduction order: the same bits every run.
 int score_tally(const float *logits, int n_chains, int B, int C, const float thr[3], int32_t *counts, float *sums, hipStream_t s);
 
+// The objective's VALUE per (chain, finger) from forward-only logits (resample.hip; the formula is the header's, dgdm_guidance_objective_values):
+// logits [n_chains][B * C][3], obj [n_chains] on the device, rowcoef [n_chains][B * C] / rowfield [n_chains][B * C][3] read only for the
+// chains that use them (the caller checks that they cover those) -> values [n_chains][B] float64.
+int objective_values_launch(const float *logits, const TrunkObjective *obj, const float *rowcoef, const float *rowfield, int n_chains, int B, int C,
+                            double *values, hipStream_t s);
+
 // Condition rows (label.hip; the columns are the header's, dgdm_guidance_label / dgdm_guidance_label_settled).
 // label_replicate: dst [n_chains][B][L] = fingers first .. first + B - 1 of [N][L] for every chain, past the end copies of finger N - 1.
 int label_replicate(const float *fingers, int64_t N, int64_t first, int n_chains, int B, int L, float *dst, hipStream_t s);

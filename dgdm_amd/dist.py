@@ -168,7 +168,7 @@ def guided_chains_sharded(unet, spec: GuidanceSpec, sched, mode: str, noise: tor
                           chains: Sequence[Tuple[int, str]], unguided: Optional[torch.Tensor] = None, starts=None,
                           streams=None, group=None, build: Optional[Callable] = None, global_cond: Optional[torch.Tensor] = None,
                           cfg_weight: float = 1.0, edit=None, eta: float = 0.0, noise_seed: int = 0,
-                          shared_step_noise: bool = False) -> torch.Tensor:
+                          shared_step_noise: bool = False, resample=None, resample_log: Optional[list] = None) -> torch.Tensor:
     """``sampler.guided_chains`` for the (object x objective) pairs `chains` over the object bank `objects`, block-partitioned
     over the ranks of `group`; returns all chains' samples [n_chains, B, L, 1] in the original order on every rank.
 
@@ -179,20 +179,25 @@ def guided_chains_sharded(unet, spec: GuidanceSpec, sched, mode: str, noise: tor
     global_cond (B, gc), shared by all chains, and cfg_weight: as in ``sampler.guided_chains``.  edit (dgdm_amd/edit.py) is forwarded:
     its designs, bounds and start sample are the same on every rank, and the draws are made for its steps.
     eta, noise_seed, shared_step_noise (sampler.guided_chains): a chain's step noise is keyed by its GLOBAL index in `chains`, so the
-    gathered result does not depend on the number of ranks."""
+    gathered result does not depend on the number of ranks.
+    resample (sampler.run_chains): chains are whole per rank - a chain resamples among its own B fingers - and the uniform is keyed like
+    the step noise, so the gathered result equals the one-process run bit for bit; 3-D: every rank walks the evaluations' draws of ALL
+    chains behind all guidance draws and keeps its block's.  resample_log receives this rank's chains' entries."""
     from . import sampler
     world, rank = world_rank(group)
     mine, local_objects, local_chains = shard_chains(chains, rank, world)
     B, L, _ = noise.shape
+    sampler.check_resample(resample, eta, spec, 1, edit=edit, global_cond=global_cond)
     S = len(sched.timesteps) if edit is None else edit.n_steps(sched)
     predrawn = None
     if mode == 'point_3d':
-        predrawn = sampler.draw_chain_starts(spec, chains, S, starts, keep=mine, streams=streams)
+        n_pot = 0 if resample is None else len(resample.evaluations(S))
+        predrawn = sampler.draw_chain_starts(spec, chains, S, starts, keep=mine, streams=streams, n_potential=n_pot)
     if len(local_chains):
         guid = (build or spec.build)(objects[local_objects].to(noise.device), len(local_chains))
         local = sampler.guided_chains(unet, guid, sched, mode, noise, local_chains, unguided=unguided, predrawn=predrawn, global_cond=global_cond,
                                       cfg_weight=cfg_weight, edit=edit, eta=eta, noise_seed=noise_seed, shared_step_noise=shared_step_noise,
-                                      chain_keys=chain_noise_keys(mine))
+                                      chain_keys=chain_noise_keys(mine), resample=resample, resample_log=resample_log)
     else:
         local = torch.zeros((0, B, L, 1), dtype=torch.float32, device=noise.device)
     return gather_pairs(local, len(chains), group)
@@ -206,15 +211,18 @@ def gather_rows(local: torch.Tensor, n_items: int, group=None) -> torch.Tensor:
 def guided_multi_object_sharded(unet, spec: GuidanceSpec, sched, mode: str, noise: torch.Tensor, objects: torch.Tensor, opt_obj: str,
                                 starts=None, group=None, build: Optional[Callable] = None, on_step=None, global_cond: Optional[torch.Tensor] = None,
                                 cfg_weight: float = 1.0, edit=None, eta: float = 0.0, noise_seed: int = 0,
-                                shared_step_noise: bool = False) -> torch.Tensor:
+                                shared_step_noise: bool = False, resample=None) -> torch.Tensor:
     """``sampler.guided_multi_object`` (generator/diffusion.py:637-647: ONE chain whose step uses the mean of n_obj cond_fn
     gradients) with the objects block-partitioned over the ranks.  Unlike the per-object chains this loop has a real exchange
     step: every denoise step the ranks all-gather their objects' gradients [n_obj, B, L] (a few KB over RCCL) and then all take
     the same scheduler step on the full stack, in object order - so every rank holds the single-process result bit for bit.
     3-D: per step the reference draws the FPS starts object after object (:641-643); every rank walks that stream and keeps its objects'.
     edit (dgdm_amd/edit.py): the start sample, the steps and their bounds are the edit's, the same on every rank.
-    eta, noise_seed: every rank steps the one chain with key 0, as sampler.guided_multi_object does: the same noise on all of them."""
+    eta, noise_seed: every rank steps the one chain with key 0, as sampler.guided_multi_object does: the same noise on all of them.
+    resample: ValueError - the objects' values would need a gather of their own beside the gradients', which is not built."""
     from . import sampler
+    if resample is not None:
+        raise ValueError("guided_multi_object_sharded: resampling is not supported (the objects' values live on different ranks)")
     world, rank = world_rank(group)
     n_obj, (B, L, _) = objects.shape[0], noise.shape
     if not sampler.is_goal(opt_obj) and opt_obj == 'convergence':

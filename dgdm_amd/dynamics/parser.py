@@ -82,6 +82,12 @@ _FLAGS = [
     ("noise_seed", int, None, "with --eta: seed of the steps' noise (default: --seed)"),
     ("shared_step_noise", "flag", None, "with --eta: every chain of a launch draws the same step noise (common random numbers, for comparing "
                                         "objectives on equal noise)"),
+    ("resample_every", int, None, "with --eta > 0 and --classifier_guidance: after every K-th DDIM step (never the last) the fingers of a chain are "
+                                  "weighed by the dynamics model's objective at (x_t, t) and, where the weights have degenerated, promising fingers are "
+                                  "copied over poor ones (dgdm_amd/resample.py; the mechanism is this project's own, no reference counterpart)"),
+    ("resample_beta", float, None, "with --resample_every: inverse temperature of the weights, per grid cell of a finger (untuned; 0 never resamples)"),
+    ("resample_ess", float, None, "with --resample_every: resample when the effective sample size falls below this fraction of the fingers "
+                                  "(default 0.5; above 1: at every evaluation)"),
     ("device_dataset", "flag", None, "dynamics training: read every data file once, keep the dataset on the GPU and build each batch's rows there "
                                      "(dynamics/device_dataset.py); same batches, draws and results as the host loop"),
 ]

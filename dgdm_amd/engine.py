@@ -429,6 +429,23 @@ class Guidance:
         check(lib().dgdm_guidance_score(self._h, dptr(x), int(timestep), oc, sp, thr, nc, dptr(logits), dptr(counts), dptr(sums), stream_ptr()))
         return (counts, sums, logits) if want_logits else (counts, sums)
 
+    def objective_values(self, logits: torch.Tensor, objectives: Sequence[_lib.Objective], rowcoef: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """The objectives' VALUES per finger (include/dgdm_hip.h, dgdm_guidance_objective_values): logits (n_chains, R, 3) float32 as
+        score(want_logits=True) returns them, objectives / rowcoef as grad() takes them (the row field is the handle's) ->
+        (n_chains, B) float64, the objective of chain i summed over finger b's grid cells.  A row-field chain without a field raises
+        DgdmError before anything is launched."""
+        nc = len(objectives)
+        if not (logits.is_cuda and logits.dtype == torch.float32 and tuple(logits.shape) == (nc, self.rows, 3)):
+            raise ValueError(f"objective_values: float32 device logits ({nc}, {self.rows}, 3) expected, got {tuple(logits.shape)} {logits.dtype}")
+        lg = logits.contiguous()
+        arr = (_lib.Objective * nc)(*objectives)
+        rc = _f32(rowcoef) if rowcoef is not None else None
+        if rc is not None and rc.numel() != nc * self.rows:
+            raise ValueError(f"objective_values: rowcoef of {rc.numel()} entries for {nc} chains of {self.rows} rows")
+        out = torch.empty((nc, self.cfg.batch), dtype=torch.float64, device=lg.device)
+        check(lib().dgdm_guidance_objective_values(self._h, dptr(lg), arr, dptr(rc), nc, dptr(out), stream_ptr()))
+        return out
+
     def sweep(self, x: torch.Tensor, object_of_chain: Sequence[int], starts: Optional[np.ndarray] = None) -> torch.Tensor:
         """Orientation sweep of get_convergence_centers (:506-531): logits (n_chains, B*G, 3), row = g*B + b."""
         x = _f32(x)
@@ -565,6 +582,42 @@ def step_noise(seed: int, keys: Sequence[int], step_index: int, per_chain: int) 
     out = torch.empty((len(keys), int(per_chain)), dtype=torch.float32, device="cuda")
     check(lib().dgdm_ddim_step_noise(_u64(seed), dptr(kd), len(keys), int(step_index), int(per_chain), dptr(out), stream_ptr()))
     return out
+
+
+def resample_uniform(seed: int, keys: Sequence[int], step_index: int) -> torch.Tensor:
+    """The uniform the resampling step of (seed, keys[c], step_index) draws (dgdm_resample_uniform): (len(keys),) float64 in [0, 1)."""
+    kd = chain_keys_tensor(keys, "cuda")
+    out = torch.empty((len(keys),), dtype=torch.float64, device="cuda")
+    check(lib().dgdm_resample_uniform(_u64(seed), dptr(kd), len(keys), int(step_index), dptr(out), stream_ptr()))
+    return out
+
+
+def chain_resample(x: torch.Tensor, values: torch.Tensor, n_grad: int, beta_per_cell: float, ess_frac: float, seed: int, chain_keys: Sequence[int],
+                   step_index: int, logw: torch.Tensor, vprev: torch.Tensor):
+    """One weight / effective-sample-size / systematic-resampling step (include/dgdm_hip.h, dgdm_chain_resample): x (n_chains, B, L)
+    float32, values (n_grad * n_chains, B) float64 object-major, logw / vprev (n_chains, B) float64 device tensors UPDATED IN PLACE (a
+    run's state, zero at its start) -> (x_out (n_chains, B, L), ancestors (n_chains, B) int32, ess (n_chains,) float64,
+    did (n_chains,) int32).  Shapes and dtypes are checked here (ValueError); the library refuses B, L, n_grad < 1."""
+    if x.dim() != 3 or not x.is_cuda:
+        raise ValueError(f"chain_resample: x (n_chains, B, L) on the device expected, got {tuple(x.shape)}")
+    x = _f32(x)
+    nc, B, L = x.shape
+    if len(chain_keys) != nc:
+        raise ValueError(f"chain_resample: {len(chain_keys)} chain keys for {nc} chains")
+    if not (values.is_cuda and values.dtype == torch.float64 and tuple(values.shape) == (int(n_grad) * nc, B)):
+        raise ValueError(f"chain_resample: float64 device values ({int(n_grad) * nc}, {B}) expected, got {tuple(values.shape)} {values.dtype}")
+    for name, t in (("logw", logw), ("vprev", vprev)):
+        if not (t.is_cuda and t.dtype == torch.float64 and tuple(t.shape) == (nc, B) and t.is_contiguous()):
+            raise ValueError(f"chain_resample: {name} is a contiguous float64 device tensor ({nc}, {B}), got {tuple(t.shape)} {t.dtype}")
+    values = values.contiguous()
+    kd = chain_keys_tensor(chain_keys, x.device)
+    out = torch.empty_like(x)
+    anc = torch.empty((nc, B), dtype=torch.int32, device=x.device)
+    ess = torch.empty((nc,), dtype=torch.float64, device=x.device)
+    did = torch.empty((nc,), dtype=torch.int32, device=x.device)
+    check(lib().dgdm_chain_resample(dptr(x), dptr(values), nc, B, L, int(n_grad), float(beta_per_cell), float(ess_frac), _u64(seed), dptr(kd),
+                                    int(step_index), dptr(logw), dptr(vprev), dptr(out), dptr(anc), dptr(ess), dptr(did), stream_ptr()))
+    return out, anc, ess, did
 
 
 def ddim_guided_step(x: torch.Tensor, eps: torch.Tensor, grad: Optional[torch.Tensor], n_grad: int, coef: Tuple[float, float, float, float],

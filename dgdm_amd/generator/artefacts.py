@@ -181,13 +181,23 @@ def _source_objectives(source_sim, opt_obj: str, num_objects: int) -> List[Optio
     return out
 
 
+RESAMPLE_COLUMNS = ["resample_count", "resample_ess_min", "resample_distinct_min"]
+
+
+def _resample_cells(chains: Sequence[Dict[str, Any]]) -> List[Any]:
+    """RESAMPLE_COLUMNS of a row that stands for `chains` (dgdm_amd.resample.summarise): resamples summed, the minima over them."""
+    return [int(sum(c["resamples"] for c in chains)), float(min(c["ess_min"] for c in chains)), int(min(c["distinct_min"] for c in chains))]
+
+
 def guided_table(model, log: TableLog, per_object_sim: Sequence[Any], opt_obj: str, ori_range: Sequence[float],
-                 edit: Optional[Dict[str, Any]] = None) -> Optional[Dict[str, float]]:
+                 edit: Optional[Dict[str, Any]] = None, resample: Optional[Sequence[Dict[str, Any]]] = None) -> Optional[Dict[str, float]]:
     """The "val/guided_sample/<opt_obj>_orirange=..." table (:577-619): per object the best gripper for every score.
     edit (chains that edited designs): ``edit_stats`` of the (objects, B, L, 1) samples, plus 'source': the simulator's output for the
     source designs on all objects or None.  The table is then "val/edit_sample/...", its rows carry EDIT_COLUMNS (how far the row's
     gripper moved from its design; pinned points), and per object one more row, gripper "edit_source", holds the scores of the source
-    designs averaged over the grippers: before and after in the same table."""
+    designs averaged over the grippers: before and after in the same table.
+    resample (--resample_*, never with an edit): one dgdm_amd.resample.summarise entry per object's chain; the rows then carry
+    RESAMPLE_COLUMNS - the object's chain, and in the average row all chains."""
     fam = profile_family(opt_obj)
     all_imgs, all_obj, all_prof, all_fin, all_vid, all_dirs, all_best, kept = [], [], [], [], [], [], [], []
     for oi, sim_out in enumerate(per_object_sim):
@@ -208,6 +218,14 @@ def guided_table(model, log: TableLog, per_object_sim: Sequence[Any], opt_obj: s
     rows += [[i, all_imgs[i][k], all_obj[i][k], all_prof[i][k], all_fin[i][k], list(all_vid[i][k]), all_dirs[i][k]]
              for i in range(len(all_obj)) for k in all_obj[i].keys()]
     columns = ["object_idx", "gripper", "objective", "profile", "final", "last_img", "gripper_dir"]
+    if resample is not None and edit is None:
+        columns = columns + RESAMPLE_COLUMNS
+        rows[0] += _resample_cells(resample)
+        r = 1
+        for i in range(len(all_obj)):
+            for _ in all_obj[i].keys():
+                rows[r] += _resample_cells([resample[kept[i]]])
+                r += 1
     if edit is None:
         log.log_table("val/guided_sample/%s_orirange=%.3f_%.3f" % (opt_obj, ori_range[0], ori_range[1]), columns, rows)
         return average_best
@@ -226,11 +244,12 @@ def guided_table(model, log: TableLog, per_object_sim: Sequence[Any], opt_obj: s
 
 
 def multi_object_table(model, log: TableLog, per_gripper_sim: Sequence[Any], num_objects: int, opt_obj: str,
-                       ori_range: Sequence[float], edit: Optional[Dict[str, Any]] = None) -> Optional[Dict[str, Any]]:
+                       ori_range: Sequence[float], edit: Optional[Dict[str, Any]] = None,
+                       resample: Optional[Sequence[Dict[str, Any]]] = None) -> Optional[Dict[str, Any]]:
     """The "val/guided_sample/allobj_<opt_obj>_orirange=..." table (:675-709): every gripper simulated on all objects,
     scores averaged over the objects, best gripper per score.  edit: as in guided_table, for the (B, L, 1) samples of the one chain:
     the table is "val/edit_sample/allobj_...", with EDIT_COLUMNS and one "edit_source" row (the source designs' scores averaged over
-    objects and grippers)."""
+    objects and grippers).  resample: the one chain's dgdm_amd.resample.summarise entry in a list; every row then carries RESAMPLE_COLUMNS."""
     all_obj, all_dirs, all_imgs, all_vid, kept = [], [], [], [], []
     for gi, sim_out in enumerate(per_gripper_sim):
         gripper_imgs, metrics, _, _, _, _, videos, dirs = sim_out
@@ -245,6 +264,10 @@ def multi_object_table(model, log: TableLog, per_gripper_sim: Sequence[Any], num
     best = model.get_best_ids_all_metrics(all_obj, opt_obj=opt_obj)
     rows = [[all_imgs[best[k]], all_obj[best[k]], all_vid[best[k]], all_dirs[best[k]]] for k in best]
     columns = ["gripper", "objective", "last_img", "gripper_dir"]
+    if resample is not None and edit is None:
+        columns = columns + RESAMPLE_COLUMNS
+        for row in rows:
+            row += _resample_cells(resample)
     if edit is None:
         log.log_table("val/guided_sample/allobj_%s_orirange=%.3f_%.3f" % (opt_obj, ori_range[0], ori_range[1]), columns, rows)
         return {k: all_obj[best[k]] for k in best}

@@ -104,6 +104,8 @@ class Diffusion(nn.Module):
         if not (float(eta) >= 0.0 and float(eta) < float("inf")):
             raise ValueError(f"eta {eta!r}: not a finite non-negative number")
         self.eta, self.noise_seed, self.shared_step_noise = float(eta), int(seed if noise_seed is None else noise_seed), False
+        # --resample_*: a dgdm_amd.resample.Resample for the guided chains, and per tag what its evaluations did
+        self.resample, self.last_resample = None, {}
         if contraction_dtype not in ("f32", "bf16", "f32_mfma", "f32_f16x3"):
             raise ValueError(f"contraction dtype {contraction_dtype!r} not supported")
         # not a reference argument: 'bf16' runs the trunk / eps-net / sa3 contractions with bf16 operands (DESIGN_HISTORY.md 4.6)
@@ -468,6 +470,20 @@ class Diffusion(nn.Module):
             return {}
         return dict(eta=self.eta, noise_seed=self.noise_seed, shared_step_noise=bool(self.shared_step_noise))
 
+    def _resample_kw(self, log: list) -> Dict[str, Any]:
+        """resample / resample_log as the samplers take them; nothing without --resample_*, whose calls are those of old."""
+        if getattr(self, "resample", None) is None:
+            return {}
+        return dict(resample=self.resample, resample_log=log)
+
+    def _resample_done(self, key: str, log: list, n_chains: int, batch: int):
+        """Files the evaluations of the chains run under `key` (validation_step's res['resample'][key]); None without --resample_*."""
+        if getattr(self, "resample", None) is None:
+            return None
+        from ..resample import summarise
+        self.last_resample[key] = summarise(log, n_chains, batch)
+        return self.last_resample[key]
+
     def guided_sample(self, batch_idx, batch_size, noise, save_dir, opt_obj='rotate', ori_range=[-1.0, 1.0], unguided_sample=None,
                       global_cond=None):
         """All objects' chains of generator/diffusion.py:561-576 as one batch.  Returns (n_objects, B, L, 1).  global_cond (B, gc): the
@@ -484,15 +500,18 @@ class Diffusion(nn.Module):
         chains = [(i, opt_obj) for i in range(n)]
         ug = None if unguided_sample is None else unguided_sample.to(self.device)
         edit = self._edit(batch_idx, batch_size)
+        rlog: list = []
         if ddist.world_rank()[0] > 1:
             out = ddist.guided_chains_sharded(self._net(), self._spec(batch_size, ori_range, objs.shape[1]), self.noise_scheduler, self.mode,
                                               noise.to(self.device), objs, chains, unguided=ug,
                                               build=lambda o, k: self._guidance_for(batch_size, ori_range, o.detach().cpu(), k),
-                                              global_cond=global_cond, cfg_weight=self.cfg_weight, edit=edit, **self._noise_kw())
+                                              global_cond=global_cond, cfg_weight=self.cfg_weight, edit=edit, **self._noise_kw(),
+                                              **self._resample_kw(rlog))
         else:
             g = self._guidance_for(batch_size, ori_range, objs, n)
             out = sampler.guided_chains(self._net(), g, self.noise_scheduler, self.mode, noise.to(self.device), chains, unguided=ug,
-                                        global_cond=global_cond, cfg_weight=self.cfg_weight, edit=edit, **self._noise_kw())
+                                        global_cond=global_cond, cfg_weight=self.cfg_weight, edit=edit, **self._noise_kw(), **self._resample_kw(rlog))
+        rsum = self._resample_done(f"guided/{opt_obj}", rlog, rlog[0][1].shape[0] if rlog else n, batch_size)      # (a rank of a process group logs its own chains)
         if ddist.world_rank()[1] == 0:
             tag = f"{opt_obj}_orirange={ori_range[0]:.3f}_{ori_range[1]:.3f}"
             sub = 'vis_guided' if edit is None else 'vis_edit'
@@ -503,6 +522,8 @@ class Diffusion(nn.Module):
                 sims = [self.simulator(arr[i], [ids[i]], os.path.join(save_dir, sub, tag, str(ids[i])), render=self.render_video,
                                        num_cpus=self.num_cpus, num_rot=int((ori_range[1] - ori_range[0]) * 180), ori_range=ori_range) for i in range(n)]
                 table_kw = {} if edit is None else {"edit": self._edit_table(edit, arr)}
+                if rsum is not None and len(rsum) == n:      # (a rank of a process group holds its own chains' entries only: no columns)
+                    table_kw["resample"] = rsum
                 artefacts.guided_table(self, self._tables(save_dir), sims, opt_obj, ori_range, **table_kw)
         return out
 
@@ -514,12 +535,15 @@ class Diffusion(nn.Module):
         edit = self._edit(batch_idx, batch_size)          # --edit_from: the chain edits this batch's designs (see guided_sample)
         sub = 'vis_guided' if edit is None else 'vis_edit'
         on_step = None
+        rlog: list = []
         if save_dir and self.render_plots and rank0:                     # per-step, per-gripper PNGs (:648-674)
             def on_step(i, x):
                 for gi, row in enumerate(x.detach().cpu().numpy()):
                     artefacts.plot_fingers(os.path.join(save_dir, sub, tag, 'allobj_%d_%d.png' % (batch_idx * batch_size + gi, i)),
                                            row[:, 0], self.mode, self.pts_x_dim, self.pts_z_dim, stacked=False)
         if ddist.world_rank()[0] > 1:       # objects over ranks, gradients all-gathered every step (dist.guided_multi_object_sharded)
+            if getattr(self, "resample", None) is not None:
+                raise ValueError("--resample_*: the multi-object chain has no sharded form (dist.guided_multi_object_sharded); run one process")
             out = ddist.guided_multi_object_sharded(self._net(), self._spec(batch_size, ori_range, objs.shape[1]), self.noise_scheduler, self.mode,
                                                     noise.to(self.device), objs, opt_obj,
                                                     build=lambda o, k: self._guidance_for(batch_size, ori_range, o.detach().cpu(), k), on_step=on_step,
@@ -528,7 +552,8 @@ class Diffusion(nn.Module):
             g = self._guidance_for(batch_size, ori_range, objs, objs.shape[0])
             out = sampler.guided_multi_object(self._net(), g, self.noise_scheduler, self.mode, noise.to(self.device),
                                               list(range(objs.shape[0])), opt_obj, on_step=on_step, global_cond=global_cond,
-                                              cfg_weight=self.cfg_weight, edit=edit, **self._noise_kw())
+                                              cfg_weight=self.cfg_weight, edit=edit, **self._noise_kw(), **self._resample_kw(rlog))
+        rsum = self._resample_done(f"multi/{opt_obj}", rlog, 1, batch_size)
         if rank0:
             self._emit(save_dir, sub, tag, out[None], ["allobj"])
             if self.simulator is not None and save_dir:                  # :675-709: every gripper on all objects
@@ -538,6 +563,8 @@ class Diffusion(nn.Module):
                                        num_cpus=self.num_cpus, num_rot=int((ori_range[1] - ori_range[0]) * 180), ori_range=ori_range)
                         for i in range(arr.shape[0])]
                 table_kw = {} if edit is None else {"edit": self._edit_table(edit, arr)}
+                if rsum is not None:
+                    table_kw["resample"] = rsum
                 artefacts.multi_object_table(self, self._tables(save_dir), sims, len(ids), opt_obj, ori_range, **table_kw)
         return out
 
@@ -646,8 +673,12 @@ class Diffusion(nn.Module):
                 if self.simulator is not None and self.save_dir:
                     self._edit_source_sim = self.simulator(src.cpu().numpy(), self._object_ids(), os.path.join(self.save_dir, 'vis_edit', artefacts.EDIT_SOURCE),
                                                            render=self.render_video, num_cpus=self.num_cpus)
+            self.last_resample = {}
             with self._draw_ahead(B, edit):
                 self._objective_sweep(out, batch_idx, B, noise, unguided, sim_unguided, tables, imgs, cond)
+            if getattr(self, "resample", None) is not None:
+                # per sampler key ("guided/<objective>", "multi/<objective>") one entry per chain: evaluations, resamples, ess_min, distinct_min
+                out["resample"] = dict(self.last_resample)
         return out
 
     def _cond_target_report(self, unguided, B: int, rank0: bool) -> Dict[str, Any]:
@@ -694,6 +725,8 @@ class Diffusion(nn.Module):
         world, rank = ddist.world_rank()
         plots = bool(self.save_dir) and self.render_plots and rank == 0
         jobs = []
+        # --resample_* (one process only): every run's evaluations draw behind all of its guidance draws (sampler.run_chains)
+        n_pot = 0 if getattr(self, "resample", None) is None else len(self.resample.evaluations(S))
         for opt_obj in OBJECTIVE_SWEEP + ([self.goal] if getattr(self, "goal", None) is not None else []):
             if opt_obj != 'convergence':
                 if world > 1:
@@ -703,11 +736,15 @@ class Diffusion(nn.Module):
                     jobs += [(rows, n, True)] * S
                 else:
                     jobs.append((rows, S * n, True))
+                if n_pot:
+                    jobs.append((rows, n_pot * n, True))
             mine = ddist.shard_range(n, rank, world)
             for c in range(n):
                 if opt_obj == 'convergence':
                     jobs.append((sweep_rows, 1, c in mine))
                 jobs.append((rows, S, c in mine))
+            if n_pot:
+                jobs += [(rows, n_pot, c in mine) for c in range(n)]
         return sampler.StartPlan(N, self.sub_batch_size, jobs)
 
     def _objective_sweep(self, out, batch_idx, B, noise, unguided, sim_unguided, tables, imgs, cond=None):

@@ -387,6 +387,8 @@ def train(args):
     edit_plan = plan_from_args(args)        # --edit_from / --pin / --edit_band_mm / --edit_steps: read and checked before anything is built
     if edit_plan is not None and (args.mode != 'test' or not args.classifier_guidance):
         raise ValueError("--edit_from edits designs in the guided chains of --mode=test and needs --classifier_guidance")
+    from ..resample import resample_from_args
+    resample = resample_from_args(args)     # --resample_every / --resample_beta / --resample_ess: refused here unless --classifier_guidance and --eta > 0
     cond = load_global_cond(args.global_cond, args.num_fingers) if args.global_cond is not None else None
     gc = 0 if cond is None else cond.shape[1]
     if cond_stats is not None:
@@ -414,6 +416,7 @@ def train(args):
     model.shared_step_noise = bool(getattr(args, "shared_step_noise", False))
     model.save_meshes = bool(getattr(args, "save_meshes", False))
     model.edit_plan = edit_plan
+    model.resample = resample
     model.cfg_weight, model.cond_drop_prob, model.global_cond_rows = float(args.cfg_weight), float(args.cond_drop_prob), cond
     if getattr(args, "save_objects", False):
         model.object_exporter = _object_exporter(args)

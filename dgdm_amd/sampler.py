@@ -18,6 +18,7 @@ from . import _lib, engine
 from .edit import Edit
 from .engine import Guidance, Unet1d, make_objective
 from .goal import PROFILES, Goal, is_goal
+from .resample import Resample
 from .scheduler import DDIMScheduler
 
 SCALE_2D, SCALE_2D_CONV, SCALE_3D, SCALE_3D_CONV = 0.001, 10.0, 0.5, 0.8      # generator/diffusion.py:30-33
@@ -332,11 +333,35 @@ def step_noise_keys(n_chains: int, shared_step_noise: bool = False, chain_keys: 
     return [0] * n_chains if shared_step_noise else keys
 
 
+def check_resample(resample: Optional[Resample], eta: float, guid: Optional[Guidance], n_grad: int, scales: Optional[Sequence[float]] = None,
+                   bounds=None, edit=None, global_cond=None, grad_fn=None) -> None:
+    """What a run with `resample` refuses, by ValueError and before any launch: eta == 0 (copies would never part), bounds / an edit
+    (a finger's bounds belong to its slot, not to the design that is copied into it), global_cond (likewise its condition row),
+    n_grad == 0 or no guidance handle (nothing to weigh by), a bf16 handle (score has no bf16 form), per-chain scales with n_grad != 1."""
+    if resample is None:
+        return
+    if not isinstance(resample, Resample):
+        raise ValueError(f"resample: a dgdm_amd.resample.Resample expected, got {type(resample).__name__}")
+    if not float(eta) > 0.0:
+        raise ValueError("resample: eta == 0 - copies of a finger would never part again; give eta > 0")
+    if bounds is not None or edit is not None:
+        raise ValueError("resample: bounds / an edit belong to a finger's slot; resampled edits are not supported")
+    if global_cond is not None:
+        raise ValueError("resample: global_cond rows belong to a finger's slot; resampled conditional rows are not supported")
+    if n_grad == 0 or guid is None or grad_fn is not None:
+        raise ValueError("resample: needs the guidance handle and its objectives (n_grad >= 1, no grad_fn): there is nothing else to weigh fingers by")
+    if getattr(guid, "contraction_dtype", "f32") == "bf16":
+        raise ValueError("resample: the bf16 trunk has no forward-only form (Guidance.score refuses it)")
+    if scales is not None and len(set(scales)) > 1 and n_grad != 1:
+        raise ValueError(f"resample: per-chain classifier scales ({sorted(set(scales))}) need n_grad == 1, not {n_grad}")
+
+
 def run_chains(unet: Unet1d, guid: Optional[Guidance], sched: DDIMScheduler, x0: torch.Tensor, n_chains: int, n_grad: int, objectives,
                rowcoef: Optional[torch.Tensor], starts: Optional[np.ndarray], timesteps, scales: Sequence[float],
                global_cond: Optional[torch.Tensor] = None, cfg_weight: float = 1.0, bounds=None, trace: Optional[list] = None,
                on_step=None, grad_fn=None, stepwise: bool = False, eta: float = 0.0, noise_seed: int = 0,
-               chain_keys: Optional[Sequence[int]] = None) -> torch.Tensor:
+               chain_keys: Optional[Sequence[int]] = None, resample: Optional[Resample] = None, resample_log: Optional[list] = None,
+               resample_starts: Optional[np.ndarray] = None) -> torch.Tensor:
     """THE denoise loop, S x [eps-net with the classifier-free mix ; guidance gradient ; DDIM step], of every sampler here and in
     dgdm_amd/dist.py: x0 (B, L) -> (n_chains, B, L).  All n_chains chains start from x0; chain k is guided by the mean of n_grad
     gradients, gradient j of chain k being gradient chain j * n_chains + k of `objectives` (object-major, as dgdm_guided_chains_run
@@ -353,12 +378,30 @@ def run_chains(unet: Unet1d, guid: Optional[Guidance], sched: DDIMScheduler, x0:
     eta > 0: stochastic DDIM steps (DDIMScheduler.eta_coefficients).  Step si of chain k adds sigma times the keyed device
     normal of (noise_seed, chain_keys[k], si) - a pure function of those and the element, so the library call, the walk, a run split over
     ranks and a run split into several calls give the same bits as long as a chain keeps its key.  chain_keys None: range(n_chains).
-    eta == 0 is the loop of old, launch for launch."""
+    eta == 0 is the loop of old, launch for launch.
+
+    resample (dgdm_amd/resample.py): a Resample forces the walk.  After the DDIM step of walk step si with
+    (si + 1) % every == 0 and si < S - 1 - never after the last step, whose duplicates no noise could part - the step's output is scored
+    forward-only at timesteps[si + 1] on n_grad copies, as grad is called; the objectives' values per finger weigh the B fingers of every
+    chain, and engine.chain_resample (step_index si, the run's noise_seed and chain keys) copies fingers over fingers where the weights
+    have degenerated.  Its output is the x the walk continues with (on_step sees it).  The log weights and last potentials live for the
+    run and start at zero.  resample_log: a list that receives (si, ess (n_chains,), did (n_chains,), ancestors (n_chains, B)) per
+    evaluation, device tensors.  resample_starts (3-D): the evaluations' FPS draws, [evaluation][n_grad * n_chains][starts_per_call], taken
+    from the start stream AFTER all of the run's guidance draws (draw_chain_starts / draw_ensemble_starts, n_potential) - the guidance
+    draws are those of the run without resampling.  check_resample lists what is refused, before any launch."""
     B, L = x0.shape
     nc = n_chains
     eta = float(eta)
     if eta < 0.0:
         raise ValueError(f"run_chains: eta {eta} is negative")
+    if resample is not None:
+        check_resample(resample, eta, guid, n_grad, scales, bounds=bounds, global_cond=global_cond, grad_fn=grad_fn)
+        n_eval = len(resample.evaluations(len(timesteps)))
+        if guid.dyn.kind == 3 and n_eval:
+            if resample_starts is None or resample_starts.dtype != np.int64 or resample_starts.size != n_eval * n_grad * nc * guid.starts_per_call:
+                raise ValueError(f"run_chains: 3-D resampling needs resample_starts, {n_eval} x {n_grad * nc} x {guid.starts_per_call} int64 draws")
+            resample_starts = np.ascontiguousarray(resample_starts).reshape(n_eval, -1)
+        stepwise = True
     keys = list(range(nc)) if chain_keys is None else [int(k) for k in chain_keys]
     if len(keys) != nc:
         raise ValueError(f"run_chains: {len(keys)} chain keys for {nc} chains")
@@ -375,6 +418,10 @@ def run_chains(unet: Unet1d, guid: Optional[Guidance], sched: DDIMScheduler, x0:
     if cond is not None:
         cond = (cond.reshape(1, B, -1).expand(nc, -1, -1) if stride == 0 else cond).reshape(nc * B, -1)
     x = x0.reshape(1, B, L).expand(nc, -1, -1).contiguous().to(torch.float32)
+    if resample is not None:
+        logw, vprev = (torch.zeros((nc, B), dtype=torch.float64, device=x.device) for _ in range(2))
+        beta_per_cell = resample.beta / float(guid.rows // B)          # a finger has G P^2 cells
+        n_seen = 0
     for si, t in enumerate(timesteps):
         t = int(t)
         # every chain starts from the same sample (generator/diffusion.py:570: `sample = noise.clone()` per object), so the first eps-net
@@ -397,6 +444,16 @@ def run_chains(unet: Unet1d, guid: Optional[Guidance], sched: DDIMScheduler, x0:
                                                            chain_keys=keys if isinstance(c, slice) else [keys[c]])
         out = [engine.ddim_guided_step(x[c], eps[c], None if g is None else g[c], n_grad, coef, sc, bounds, **noisy(c)) for c, sc in steps]
         x = out[0] if len(out) == 1 else torch.stack(out)
+        if resample is not None and resample.evaluates(si, len(timesteps)):
+            # the forward-only trunk on the step's output; only the logits are used (the tally's thresholds are placeholders)
+            st = None if guid.dyn.kind != 3 else resample_starts[n_seen]
+            logits = guid.score(x.repeat(n_grad, 1, 1), [int(o.object) for o in objectives], (1.0, 1.0, 1.0), int(timesteps[si + 1]), st,
+                                want_logits=True)[2]
+            values = guid.objective_values(logits, objectives, rowcoef)
+            x, anc, ess, did = engine.chain_resample(x, values, n_grad, beta_per_cell, resample.ess_frac, noise_seed, keys, si, logw, vprev)
+            n_seen += 1
+            if resample_log is not None:
+                resample_log.append((si, ess, did, anc))
         if on_step is not None:
             on_step(si, x, eps)
     return x
@@ -444,7 +501,7 @@ def convergence_centers(guid: Guidance, mode: str, unguided: torch.Tensor, objec
 
 def draw_chain_starts(guid: Guidance, chains: Sequence[Tuple[int, Union[str, Goal]]], n_steps: int, starts: Optional[StartStream] = None,
                       keep: Optional[range] = None, streams: Optional[Sequence[StartStream]] = None, out: Optional[np.ndarray] = None,
-                      pool=None):
+                      pool=None, n_potential: int = 0):
     """FPS starts of a batch of 3-D chains in the order the reference's sequential loops consume the generator:
     chain after chain (generator/diffusion.py:561); inside a chain the centre sweep (:563) and then every step's cond_fn (:574).
     A Goal chain draws no sweep, like every objective other than 'convergence'.
@@ -452,7 +509,11 @@ def draw_chain_starts(guid: Guidance, chains: Sequence[Tuple[int, Union[str, Goa
     keep: only the chains of this index range are returned (sweep list / step array of len(keep) chains); the draws of the
     others are consumed and dropped, so that a rank holding a block of the chains sees exactly the numbers a single process
     would have handed those chains (dgdm_amd/dist.py).  streams: one StartStream per chain instead of the shared one (then
-    nothing has to be skipped: chains outside `keep` are not touched)."""
+    nothing has to be skipped: chains outside `keep` are not touched).
+
+    n_potential > 0 (a run with a Resample: its number of evaluations): a third result, (n_potential, len(keep), starts_per_call) - the
+    evaluations' draws, taken AFTER all chains' guidance draws, chain after chain (with `streams`, from each chain's own stream behind its
+    guidance draws); the first two results are those of n_potential == 0."""
     nc = len(chains)
     keep = range(nc) if keep is None else keep
     if streams is None:
@@ -480,6 +541,13 @@ def draw_chain_starts(guid: Guidance, chains: Sequence[Tuple[int, Union[str, Goa
     else:
         for c, (_, o) in enumerate(chains):
             one(c, o, starts, c in keep)
+    if n_potential > 0:
+        pot = np.empty((n_potential, len(keep), guid.starts_per_call), dtype=np.int64)
+        for c in range(nc):
+            mine = c in keep
+            if streams is None or mine:
+                (starts if streams is None else streams[c]).calls(guid.rows, n_potential, keep=mine, out=pot[:, c - keep.start] if mine else None)
+        return sweep, step, pot
     return sweep, step
 
 
@@ -488,7 +556,8 @@ def guided_chains(unet: Unet1d, guid: Guidance, sched: DDIMScheduler, mode: str,
                   chains: Sequence[Tuple[int, Union[str, Goal]]], unguided: Optional[torch.Tensor] = None,
                   starts: Optional[StartStream] = None, trace: Optional[list] = None, predrawn=None,
                   global_cond: Optional[torch.Tensor] = None, cfg_weight: float = 1.0, edit: Optional[Edit] = None, eta: float = 0.0,
-                  noise_seed: int = 0, shared_step_noise: bool = False, chain_keys: Optional[Sequence[int]] = None) -> torch.Tensor:
+                  noise_seed: int = 0, shared_step_noise: bool = False, chain_keys: Optional[Sequence[int]] = None,
+                  resample: Optional[Resample] = None, resample_log: Optional[list] = None) -> torch.Tensor:
     """``Diffusion.guided_sample`` loop bodies (:561-576) for the chains [(object index, opt_obj), ...]; opt_obj: a reference
     objective name or a ``Goal`` (dgdm_amd/goal.py), whose chain is guided by the goal's row field.
 
@@ -503,8 +572,12 @@ def guided_chains(unet: Unet1d, guid: Guidance, sched: DDIMScheduler, mode: str,
     `chains` (dist.guided_chains_sharded passes the GLOBAL indices of its slice).  A pair may appear several times in `chains`: at
     eta = 0 its replicas are identical, at eta > 0 they diverge through their keys - that is how one asks for several candidate designs
     per task; with an edit, for several edits of one design (the bounded clip is inside the same step).  shared_step_noise=True gives
-    every chain key 0: common random numbers, for comparing objectives on equal noise (replicas are then identical again)."""
+    every chain key 0: common random numbers, for comparing objectives on equal noise (replicas are then identical again).
+
+    resample, resample_log: run_chains' (every chain resamples among its own B fingers).  3-D: the evaluations' draws follow all
+    guidance draws on the start stream; `predrawn` then is draw_chain_starts' triple (n_potential = len(resample.evaluations(S)))."""
     nc, (B, L, _) = len(chains), noise.shape
+    check_resample(resample, eta, guid, 1, edit=edit, global_cond=global_cond)
     engine.chain_cond_layout(global_cond, unet.global_cond_dim, nc, B)       # a condition of the wrong shape is refused before anything runs
     dev = noise.device
     is3d = mode == 'point_3d'
@@ -517,9 +590,15 @@ def guided_chains(unet: Unet1d, guid: Guidance, sched: DDIMScheduler, mode: str,
         guid.set_row_field(field)
     # --- replay of the reference's RNG consumption: chain after chain; inside a chain the centre sweep, then the steps
     sweep_starts: List[Optional[np.ndarray]] = [None] * nc
-    step_starts = None
+    step_starts = pot_starts = None
     if is3d:
-        sweep_starts, step_starts = predrawn if predrawn is not None else draw_chain_starts(guid, chains, S, starts)
+        n_pot = 0 if resample is None else len(resample.evaluations(S))
+        if predrawn is None:
+            predrawn = draw_chain_starts(guid, chains, S, starts, n_potential=n_pot)
+        if n_pot and len(predrawn) != 3:
+            raise ValueError("guided_chains: resampling 3-D chains needs the evaluations' draws as well (draw_chain_starts n_potential)")
+        sweep_starts, step_starts = predrawn[0], predrawn[1]
+        pot_starts = predrawn[2] if n_pot else None
     # --- 'convergence' chains: centres from the unguided sample, then row coefficients
     rowcoef = None
     conv = [c for c, (_, o) in enumerate(chains) if not is_goal(o) and o == 'convergence']
@@ -533,7 +612,8 @@ def guided_chains(unet: Unet1d, guid: Guidance, sched: DDIMScheduler, mode: str,
         rowcoef = torch.from_numpy(rc).to(dev)
     out = run_chains(unet, guid, sched, noise.reshape(B, L), nc, 1, objectives, rowcoef, step_starts, timesteps,
                      [chain_scale(mode, o) for _, o in chains], global_cond, cfg_weight, bounds, trace=trace, eta=eta, noise_seed=noise_seed,
-                     chain_keys=step_noise_keys(nc, shared_step_noise, chain_keys))
+                     chain_keys=step_noise_keys(nc, shared_step_noise, chain_keys), resample=resample, resample_log=resample_log,
+                     resample_starts=pot_starts)
     return out.reshape(nc, B, L, 1)
 
 
@@ -541,11 +621,15 @@ def guided_chains(unet: Unet1d, guid: Guidance, sched: DDIMScheduler, mode: str,
 def guided_multi_object(unet: Unet1d, guid: Guidance, sched: DDIMScheduler, mode: str, noise: torch.Tensor,
                         object_indices: Sequence[int], opt_obj: Union[str, Goal], starts: Optional[StartStream] = None,
                         on_step=None, global_cond: Optional[torch.Tensor] = None, cfg_weight: float = 1.0,
-                        edit: Optional[Edit] = None, eta: float = 0.0, noise_seed: int = 0, shared_step_noise: bool = False) -> torch.Tensor:
+                        edit: Optional[Edit] = None, eta: float = 0.0, noise_seed: int = 0, shared_step_noise: bool = False,
+                        resample: Optional[Resample] = None, resample_log: Optional[list] = None) -> torch.Tensor:
     """``Diffusion.guided_sample_multi_object`` loop (:637-647): one chain, gradient = mean over the objects.  opt_obj: a reference
     objective name or a ``Goal``.  global_cond (B, gc), cfg_weight, edit: as in guided_chains.  eta, noise_seed: stochastic steps as
-    in run_chains; the one chain has key 0 (dist.guided_multi_object_sharded steps it with the same key on every rank)."""
+    in run_chains; the one chain has key 0 (dist.guided_multi_object_sharded steps it with the same key on every rank).
+    resample, resample_log: run_chains' - the fingers are weighed by the mean of the objects' values; 3-D: the evaluations' draws
+    (object after object) follow the loop's guidance draws on the start stream."""
     n_obj, (B, L, _) = len(object_indices), noise.shape
+    check_resample(resample, eta, guid, n_obj, edit=edit, global_cond=global_cond)
     engine.check_global_cond(global_cond, unet.global_cond_dim, B)
     is3d = mode == 'point_3d'
     objectives, field = chain_objectives(guid, [(oi, opt_obj) for oi in object_indices])
@@ -558,31 +642,40 @@ def guided_multi_object(unet: Unet1d, guid: Guidance, sched: DDIMScheduler, mode
     noise, timesteps, bounds = edit_start(edit, sched, noise)
     # per step the reference draws object after object (:641-643): one run of draws for the whole loop
     st = starts.calls(guid.rows, len(timesteps) * n_obj).reshape(len(timesteps), -1) if is3d else None
+    n_pot = 0 if resample is None else len(resample.evaluations(len(timesteps)))
+    pot = starts.calls(guid.rows, n_pot * n_obj).reshape(n_pot, -1) if is3d and n_pot else None
     hook = None if on_step is None else lambda i, x, eps: on_step(i, x.reshape(B, L, 1))      # the harness's per-step plots (:648-674)
     out = run_chains(unet, guid, sched, noise.reshape(B, L), 1, n_obj, objectives, None, st, timesteps, [chain_scale(mode, opt_obj, multi=True)],
-                     global_cond, cfg_weight, bounds, on_step=hook, eta=eta, noise_seed=noise_seed, chain_keys=[0])
+                     global_cond, cfg_weight, bounds, on_step=hook, eta=eta, noise_seed=noise_seed, chain_keys=[0], resample=resample,
+                     resample_log=resample_log, resample_starts=pot)
     return out.reshape(B, L, 1)
 
 
 def draw_ensemble_starts(guid: Guidance, n_groups: int, n_obj: int, n_steps: int, streams: Optional[Sequence[StartStream]] = None,
-                         out: Optional[np.ndarray] = None, pool=None):
+                         out: Optional[np.ndarray] = None, pool=None, n_potential: int = 0):
     """FPS starts of ``n_groups`` independent multi-object chains: every group has its own generator stream and consumes it as
     ``guided_sample_multi_object`` does - step after step, inside a step object after object (generator/diffusion.py:641-643).
-    Returned as (n_steps, n_obj, n_groups, starts_per_call): the launch order of ``guided_multi_object_groups``."""
+    Returned as (n_steps, n_obj, n_groups, starts_per_call): the launch order of ``guided_multi_object_groups``.
+    n_potential > 0 (a run with a Resample): every group's stream then goes on with n_potential evaluations' draws, object after object,
+    AFTER all its guidance draws, and the result is the pair (steps, (n_potential, n_obj, n_groups, starts_per_call))."""
     streams = streams or [StartStream(guid.cfg.num_object_points, guid.cfg.sub_batch_size) for _ in range(n_groups)]
     out = out if out is not None else np.empty((n_steps, n_obj, n_groups, guid.starts_per_call), dtype=np.int64)
     assert out.shape == (n_steps, n_obj, n_groups, guid.starts_per_call) and out.dtype == np.int64 and out.flags.c_contiguous
 
+    pot = np.empty((n_potential, n_obj, n_groups, guid.starts_per_call), dtype=np.int64) if n_potential > 0 else None
+
     def one(k):
         for si in range(n_steps):               # a group's stream is consumed step after step, object after object
             streams[k].calls(guid.rows, n_obj, out=out[si, :, k])
+        for e in range(n_potential):
+            streams[k].calls(guid.rows, n_obj, out=pot[e, :, k])
 
     if pool is not None and n_groups > 1:
         list(pool.map(one, range(n_groups)))
     else:
         for k in range(n_groups):
             one(k)
-    return out
+    return out if pot is None else (out, pot)
 
 
 @_restores_row_field
@@ -590,14 +683,17 @@ def guided_multi_object_groups(unet: Unet1d, guid: Guidance, sched: DDIMSchedule
                                groups: Sequence[Sequence[int]], opt_objs: Sequence[Union[str, Goal]], streams: Optional[Sequence[StartStream]] = None,
                                predrawn: Optional[np.ndarray] = None, python_loop: bool = False, global_cond: Optional[torch.Tensor] = None,
                                cfg_weight: float = 1.0, edit: Optional[Edit] = None, eta: float = 0.0, noise_seed: int = 0,
-                               shared_step_noise: bool = False, chain_keys: Optional[Sequence[int]] = None) -> torch.Tensor:
+                               shared_step_noise: bool = False, chain_keys: Optional[Sequence[int]] = None,
+                               resample: Optional[Resample] = None, resample_log: Optional[list] = None) -> torch.Tensor:
     """Several independent ``guided_sample_multi_object`` chains (:637-647) in the same launches: chain k averages the guidance
     gradients of the objects ``groups[k]`` for objective ``opt_objs[k]`` (a guidance ensemble: n_obj dynamics-gradient
     evaluations per denoise step).  All groups have the same size.  Launch order of the gradient chains is object-major,
     (j, k) -> j * K + k, so the mean over j is one strided reduction for every group at once.  Returns (K, B, L, 1).
     edit: as in guided_chains - every group edits the same designs, and `predrawn` then holds the draws of the edit's steps.
-    eta, noise_seed, shared_step_noise, chain_keys: as in guided_chains, group k being chain k."""
+    eta, noise_seed, shared_step_noise, chain_keys: as in guided_chains, group k being chain k.
+    resample, resample_log: run_chains' (the walk, whatever python_loop says); 3-D: `predrawn` then is draw_ensemble_starts' pair."""
     K, n_obj, (B, L, _) = len(groups), len(groups[0]), noise.shape
+    check_resample(resample, eta, guid, n_obj, edit=edit, global_cond=global_cond)
     assert all(len(g) == n_obj for g in groups) and len(opt_objs) == K
     engine.chain_cond_layout(global_cond, unet.global_cond_dim, K, B)       # global_cond: (B, gc) for all groups or (K, B, gc)
     if any(not is_goal(o) and o == 'convergence' for o in opt_objs):
@@ -608,13 +704,19 @@ def guided_multi_object_groups(unet: Unet1d, guid: Guidance, sched: DDIMSchedule
     objectives, field = chain_objectives(guid, [(groups[k][j], opt_objs[k]) for j in range(n_obj) for k in range(K)])
     if field is not None:
         guid.set_row_field(field)
+    n_pot = 0 if resample is None else len(resample.evaluations(len(timesteps)))
     if is3d and predrawn is None:
-        predrawn = draw_ensemble_starts(guid, K, n_obj, len(timesteps), streams)
+        predrawn = draw_ensemble_starts(guid, K, n_obj, len(timesteps), streams, n_potential=n_pot)
+    pot = None
+    if is3d and n_pot:
+        if not isinstance(predrawn, tuple) or len(predrawn) != 2:
+            raise ValueError("guided_multi_object_groups: resampling 3-D groups needs the evaluations' draws as well (draw_ensemble_starts n_potential)")
+        predrawn, pot = predrawn
     scales = {chain_scale(mode, o, multi=True) for o in opt_objs}
     if len(scales) != 1:      # (dgdm_guided_chains_run refuses per-chain scales with averaged gradients; names share one scale, Goals may not)
         raise ValueError(f"guided_multi_object_groups: the groups' classifier scales differ ({sorted(scales)}); give the Goals one scale")
     # K chains x n_obj gradients each, gradient chains object-major
     out = run_chains(unet, guid, sched, noise.reshape(B, L), K, n_obj, objectives, None, predrawn if is3d else None, timesteps, [scales.pop()] * K,
                      global_cond, cfg_weight, bounds, stepwise=python_loop, eta=eta, noise_seed=noise_seed,
-                     chain_keys=step_noise_keys(K, shared_step_noise, chain_keys))
+                     chain_keys=step_noise_keys(K, shared_step_noise, chain_keys), resample=resample, resample_log=resample_log, resample_starts=pot)
     return out.reshape(K, B, L, 1)

@@ -306,6 +306,51 @@ int dgdm_guidance_score(DgdmGuidance *g, const float *x_dev, int timestep, const
                         const int64_t *starts_host, const float thr[3], int n_chains, float *logits_dev, int32_t *counts_dev,
                         float *sums_dev, void *stream);
 
+/* ------------------------------------------------------------------ resampling fingers by predicted objective
+ * The B fingers of a chain as particles of a stochastic run (eta > 0): weighted by the objective whose gradient guides the chain, the
+ * promising ones copied over the poor ones, the keyed step noise parting the copies again.  No counterpart in the reference.
+ *
+ * The objective's VALUE per (chain, finger) (THE recipe: tests/resample_oracle.py states the same text in numpy).
+ *   logits_dev  [n_chains][R][3] float32: what dgdm_guidance_score writes, row r = cell * B + b
+ *   objectives  [n_chains] host; rowcoef_dev [n_chains][R] or NULL; the row field is the handle's (dgdm_guidance_set_row_field)
+ *   values_dev  [n_chains][B] float64
+ * For chain i and finger b, over the rows r with r % B == b, every delta widened to double, every product and sum in double:
+ *   V = sum_rows [ sum_j (lin[j] * delta_j + quad[j] * delta_j^2) + (use_rowcoef == 1 ? rowcoef[i][r] * delta_0 : 0)
+ *                  + (use_rowcoef == 2 ? sum_j field[i][r][j] * delta_j : 0) ]
+ * Its derivative in delta is the gradient form of DgdmObjective above; for the reference's names it is
+ * deltas_to_objective(...).sum() (generator/diffusion.py:430-471) over the rows that depend on finger b.
+ * Validation as dgdm_dyn{2,3}d_guidance_grad: a chain that uses rowcoef without one, or the row field while none is set or one that
+ * does not reach its index, is DGDM_EINVAL before anything is launched.  One wave per (chain, finger), a fixed reduction order:
+ * bit-identical run to run.                                                                                                        */
+int dgdm_guidance_objective_values(DgdmGuidance *g, const float *logits_dev, const DgdmObjective *objectives, const float *rowcoef_dev,
+                                   int n_chains, double *values_dev, void *stream);
+
+/* One weight / effective-sample-size / systematic-resampling step for n_chains chains of B fingers of L entries.
+ *   x_dev [n_chains][B][L]; values_dev [n_grad * n_chains][B] float64, object-major as the gradients are; beta_per_cell: the caller's
+ *   beta with 1 / (G P^2) folded in; ess_frac; seed, chain_keys_dev [n_chains] uint64 (device), step_index: the keys of the step noise
+ *   in / out: logw_dev, vprev_dev [n_chains][B] float64 - the log weights and the last potentials of a run, zero at its start
+ *   out: x_out_dev [n_chains][B][L] (must not overlap x_dev), ancestors_dev [n_chains][B] int32, ess_dev [n_chains] float64,
+ *        did_dev [n_chains] int32
+ * Per chain k, everything in float64 and in ascending finger order:
+ *   1. v_b = beta_per_cell * mean_j values[j * n_chains + k][b]      (the sum in j order, then one division, as the gradients' mean)
+ *   2. v_b not finite: logw_b = -inf.  Otherwise logw_b += v_b - vprev_b, then vprev_b = v_b.
+ *   3. m = max_b logw_b.  m == -inf (every value non-finite): ancestors = identity, ess = 0, did = 0, logw = 0; done.
+ *   4. w_b = exp(logw_b - m); s = sum w; w /= s; ess = 1 / sum w^2.
+ *   5. ess < ess_frac * B: resample.  u = the uniform below; cum_b = the running sum of w; p_j = (u + j) / B;
+ *      a_j = min(#{b : cum_b <= p_j}, B - 1); x_out[k][j] = x[k][a_j] (bit copies); vprev[j] = vprev_old[a_j]; logw = 0; did = 1.
+ *   6. otherwise x_out = x, ancestors = identity, did = 0; logw is kept.
+ * The uniform: raw output 0 of numpy.random.Philox(key=[seed, chain_keys[k]], counter=[0, step_index, 1, 0]), u = (r >> 11) * 2^-53
+ * in [0, 1) - Philox4x64-10 block (1, step_index, 1, 0), lane 0.  The third counter word 1 keeps it clear of the step noise's blocks
+ * (e / 2 + 1, step_index, 0, 0): u depends on (seed, key, step_index) only.
+ * n_chains, B, L, n_grad >= 1, step_index >= 0, no NULL pointer, x_out_dev apart from x_dev: anything else is DGDM_EINVAL before a
+ * launch.  One lane walks a chain's fingers (the order above is literal); the gather is a second, coalesced kernel over all entries.
+ * Whatever the values hold, every ancestor lies in 0 .. B - 1.                                                                       */
+int dgdm_chain_resample(const float *x_dev, const double *values_dev, int n_chains, int B, int L, int n_grad, double beta_per_cell,
+                        double ess_frac, uint64_t seed, const uint64_t *chain_keys_dev, int64_t step_index, double *logw_dev, double *vprev_dev,
+                        float *x_out_dev, int32_t *ancestors_dev, double *ess_dev, int32_t *did_dev, void *stream);
+/* Debug / test entry: the uniform of the recipe above -> u_dev [n_chains] float64. */
+int dgdm_resample_uniform(uint64_t seed, const uint64_t *chain_keys_dev, int n_chains, int64_t step_index, double *u_dev, void *stream);
+
 /* The whole guided denoise loop in one call: Diffusion.guided_sample's loop body (generator/diffusion.py:570-576) for n_chains chains, or
  * guided_sample_multi_object's (:637-647) for n_chains chains that each average n_grad gradients - n_steps x [eps-net; cond_fn; guidance
  * combine; scheduler step] without returning to the host language in between.
