@@ -53,6 +53,11 @@ class GuidanceConfig(C.Structure):
                 ("sub_batch_size", C.c_int32), ("num_object_points", C.c_int32), ("max_objects", C.c_int32)]
 
 
+class SqueezeConfig(C.Structure):
+    _fields_ = [("theta_cells", C.c_int32), ("x_cells", C.c_int32), ("window", C.c_int32), ("closing_steps", C.c_int32),
+                ("x_half", C.c_double), ("travel_max", C.c_double), ("finger_half_len", C.c_double)]
+
+
 _P = C.c_void_p
 # name -> (restype, argtypes); mirrors include/dgdm_hip.h line by line (tests/test_host_logic.py::test_abi_exports_every_declared_symbol checks the symbol list)
 PROTOTYPES = {
@@ -197,6 +202,9 @@ PROTOTYPES = {
     "dgdm_render_workspace_bytes": (C.c_int64, [_P, _P, C.c_int, _P, C.c_int, C.c_int]),
     "dgdm_render_meshes": (C.c_int, [_P, _P, _P, _P, C.c_int, _P, _P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P,
                                      C.c_int64, _P]),
+    "dgdm_squeeze_workspace_bytes": (C.c_int64, [C.POINTER(SqueezeConfig), C.c_int]),
+    "dgdm_squeeze_map": (C.c_int, [C.POINTER(SqueezeConfig), _P, C.c_int, C.c_int, _P, C.c_int, C.c_int, _P, C.c_int, _P, _P, C.c_int, _P, _P, _P, _P,
+                                   _P, _P, _P, _P, C.c_int64, _P]),
 }
 
 _lib = None

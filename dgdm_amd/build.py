@@ -14,12 +14,14 @@ from concurrent.futures import ThreadPoolExecutor
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(CSRC, "libdgdm_hip.so")
-SOURCES = ["host_util.hip", "smallnet.hip", "unet.hip", "trunk.hip", "trunk_bf16.hip", "trunk_f16l.hip", "score.hip", "resample.hip", "rollout.hip", "label.hip", "goal.hip", "pointnet.hip", "pointnet64.hip", "models_api.hip", "guidance_api.hip", "decode.hip", "debug.hip", "train2d.hip", "dataset.hip", "unet_train.hip", "train3d.hip", "torch_rng.hip", "mesh.hip", "contour.hip", "finger_mesh.hip", "polygon.hip", "render.hip"]
+SOURCES = ["host_util.hip", "smallnet.hip", "unet.hip", "trunk.hip", "trunk_bf16.hip", "trunk_f16l.hip", "score.hip", "resample.hip", "rollout.hip", "label.hip", "goal.hip", "pointnet.hip", "pointnet64.hip", "models_api.hip", "guidance_api.hip", "decode.hip", "debug.hip", "train2d.hip", "dataset.hip", "unet_train.hip", "train3d.hip", "torch_rng.hip", "mesh.hip", "contour.hip", "finger_mesh.hip", "polygon.hip", "render.hip", "squeeze.hip"]
 # unet.hip: its block functions as real calls cost 200 VGPRs and a register save/restore through scratch at every call (152 MB of
 # scratch writes per 1024-sample launch in the round-2 PMC pass); fully inlined the kernel needs 126 VGPRs
 # contour.hip: the contour contract is exact in float32 / float64 operations that must not be fused
 # render.hip: likewise the rasteriser's float32 projection, depth and shade
-PER_FILE_FLAGS = {"unet.hip": ["-mllvm", "-amdgpu-function-calls=false"], "contour.hip": ["-ffp-contract=off"], "render.hip": ["-ffp-contract=off"]}
+# squeeze.hip: likewise the squeeze simulator's float64 gaps and poses
+PER_FILE_FLAGS = {"unet.hip": ["-mllvm", "-amdgpu-function-calls=false"], "contour.hip": ["-ffp-contract=off"], "render.hip": ["-ffp-contract=off"],
+                  "squeeze.hip": ["-ffp-contract=off"]}
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function"] + os.environ.get("DGDM_EXTRA_FLAGS", "").split()
 
 

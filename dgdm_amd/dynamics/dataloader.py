@@ -40,6 +40,27 @@ def _to_unit(a: np.ndarray, box: Sequence[Sequence[float]]) -> np.ndarray:
     return out
 
 
+def _three(v, what: str, positive: bool = False) -> np.ndarray:
+    a = np.asarray(v, dtype=np.float64).reshape(-1)
+    if a.shape != (3,) or not np.all(np.isfinite(a)) or (positive and not np.all(a > 0.0)):
+        raise ValueError(f"DynamicsDataset: {what} = {v!r} (need three finite{' positive' if positive else ''} numbers: rotation in radians, "
+                         "x and y shift in metres)")
+    return a
+
+
+def load_score_stats(path: str) -> Dict[str, np.ndarray]:
+    """The DynamicsDataset keywords a stats.json of sim/sim_2d.py carries: score_std (required) and score_threshold (when present)."""
+    import json
+    with open(path) as f:
+        d = json.load(f)
+    if 'score_std' not in d:
+        raise ValueError(f"--score_stats: '{path}' holds no 'score_std'")
+    out = {'score_std': _three(d['score_std'], f"score_std of {path}", positive=True)}
+    if d.get('score_threshold') is not None:
+        out['score_threshold'] = _three(d['score_threshold'], f"score_threshold of {path}")
+    return out
+
+
 _MESH_CLOUDS: Dict[tuple, np.ndarray] = {}     # (path, size, mtime_ns, num_points) -> float64 cloud in metres, for this process
 
 
@@ -63,9 +84,12 @@ def _mesh_clouds(mesh_dir: str, num_points: int) -> Dict[str, np.ndarray]:
 
 class DynamicsDataset(Dataset):
     def __init__(self, dataset_dir: str, object_max_num_vertices: int = 10, fingers_3d: bool = False, gripper_box=None,
-                 object_box=None, object_mesh_dir: str = "", **unused):
+                 object_box=None, object_mesh_dir: str = "", score_std=None, score_threshold=None, **unused):
         self.fingers_3d = fingers_3d
-        self.std, self.threshold = SCORE_STD[0 if fingers_3d else 1], SCORE_THRESHOLD[0 if fingers_3d else 1]
+        # score_std / score_threshold: the scales of data that does not come from the reference's simulator (sim/sim_2d.py's stats.json);
+        # None = the reference's constants
+        self.std = SCORE_STD[0 if fingers_3d else 1] if score_std is None else _three(score_std, "score_std", positive=True)
+        self.threshold = SCORE_THRESHOLD[0 if fingers_3d else 1] if score_threshold is None else _three(score_threshold, "score_threshold")
         self.gripper_box = gripper_box or (GRIPPER_BOX_3D if fingers_3d else GRIPPER_BOX_2D)
         self.object_box = object_box or (OBJECT_BOX_3D if fingers_3d else OBJECT_BOX_2D)
         self.object_max_num_vertices, self.object_mesh_dir, self.object_pts = object_max_num_vertices, object_mesh_dir, {}

@@ -98,6 +98,9 @@ def train(args):
     os.makedirs(args.save_dir, exist_ok=True)
     # the reference reads args.object_mesh_dir (main.py:83,101), which its parser never defines (dynamics/parser.py:22 has --object_dir): that flag it is
     kw = dict(object_max_num_vertices=args.object_max_num_vertices, fingers_3d=args.fingers_3d, object_mesh_dir=getattr(args, 'object_mesh_dir', None) or args.object_dir)
+    if getattr(args, 'score_stats', None):          # data made by sim/sim_2d.py: its own scales instead of the MuJoCo constants
+        from .dataloader import load_score_stats
+        kw.update(load_score_stats(args.score_stats))
     train_set, val_set = DynamicsDataset(args.data_dir, **kw), DynamicsDataset(args.test_data_dir, **kw)
     threshold_std = train_set.threshold / train_set.std
     train_loader = DataLoader(train_set, batch_size=args.batch_size, shuffle=True, num_workers=args.num_workers, drop_last=False)

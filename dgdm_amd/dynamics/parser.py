@@ -44,6 +44,12 @@ _FLAGS = [
                                   "final_* scores and 'convergence' see a settled pose (40 = the simulator's count; 0 = one interaction)"),
     ("predicted_render", "flag", None, "with --predicted_sim, 3-D, objects from mesh files: also write <object>_<gripper>_gripper.png for every pair and, "
                                        "for settled poses asked with render_last, <object>_<gripper>/<v>.png (sim/render_mesh.py)"),
+    ("squeeze_sim", "flag", None, "2-D, --mode=test: fill the objective tables with the squeeze simulator (sim/squeeze.py: a frictionless, "
+                                  "quasi-static parallel-jaw squeeze; its own model, not MuJoCo's); the scores are marked 'simulated': 'squeeze'"),
+    ("squeeze_closing_steps", int, None, "with --squeeze_sim: grid steps the object climbs in one closing (default 6; untuned)"),
+    ("squeeze_window", int, None, "with --squeeze_sim: half-width in cells of the neighbourhood a step searches (default 2; untuned)"),
+    ("score_stats", str, None, "dynamics training: the stats.json sim/sim_2d.py wrote beside its data; scores are divided by its score_std "
+                               "instead of the reference's constants"),
     ("save_meshes", "flag", None, "also export every emitted gripper as OBJ meshes, collision pieces and gripper_<idx>.xml (assets/finger_mesh.py)"),
     ("save_objects", "flag", None, "2-D: also export the run's icon objects as meshes, convex pieces and object_<idx>.xml into every model root "
                                    "(assets/icon_process.py save_icon_objects)"),

@@ -1087,6 +1087,65 @@ def polygon_pieces(points) -> List[List[Tuple[int, ...]]]:
     return canonical_pieces(o["piece_count"], o["piece_offsets"], o["piece_index"])
 
 
+# ---------------------------------------------------------------------------------------------------------------- squeeze simulator
+SQUEEZE_DEFAULTS = dict(theta_cells=720, x_cells=241, x_half=0.06, window=2, closing_steps=6, travel_max=0.1, finger_half_len=0.12)
+SQUEEZE_WORKSPACE_BYTES = 1 << 30       # default chunking of squeeze_tables: as many pairs as fit 1 GiB (7.6 MB per pair at the defaults)
+
+
+def squeeze_rotation_table(theta_cells: int) -> np.ndarray:
+    """rot (theta_cells, 2) float64 = (cos, sin) of 2 pi a / theta_cells: the table dgdm_squeeze_map takes (host, numpy)."""
+    ang = 2.0 * np.pi * np.arange(int(theta_cells), dtype=np.float64) / float(theta_cells)
+    return np.ascontiguousarray(np.stack([np.cos(ang), np.sin(ang)], axis=1))
+
+
+def squeeze_config(**kw) -> _lib.SqueezeConfig:
+    c = dict(SQUEEZE_DEFAULTS)
+    unknown = set(kw) - set(c)
+    if unknown:
+        raise ValueError(f"squeeze_config: unknown keys {sorted(unknown)}")
+    c.update(kw)
+    return _lib.SqueezeConfig(int(c["theta_cells"]), int(c["x_cells"]), int(c["window"]), int(c["closing_steps"]), float(c["x_half"]),
+                              float(c["travel_max"]), float(c["finger_half_len"]))
+
+
+def squeeze_tables(surfaces, objects, pairs, starts=None, rot=None, tables: bool = False, workspace_bytes: Optional[int] = None,
+                   **config) -> Dict[str, torch.Tensor]:
+    """dgdm_squeeze_map (include/dgdm_hip.h "squeeze simulator") on the current device.  surfaces (F, 2, m) float64: the
+    lower and upper jaw surface at travel 0; objects (O, nv, 2) float64 polygons; pairs (P, 2) (finger, object), host; starts (N, 3)
+    float64 (theta0, x0, y0) shared by all pairs, or None; rot: squeeze_rotation_table(theta_cells) when None; config: the keys of
+    SQUEEZE_DEFAULTS.  -> cells (P, N, 3) int32 (start, closed, settled cell = a * x_cells + b), y (P, N, 2) float64, flags (P, N) int32
+    and, with tables, S / touch_l / touch_r (P, theta_cells, x_cells) float64 and succ (P, theta_cells * x_cells) int32.  The pairs run in
+    chunks of as many as workspace_bytes holds.  Synchronises the stream once."""
+    cfg = squeeze_config(**config)
+    one = lib().dgdm_squeeze_workspace_bytes(C.byref(cfg), 1)
+    if one < 0:
+        _check_value(int(one))
+    dev = torch.device("cuda", torch.cuda.current_device())
+    f64 = lambda t: torch.as_tensor(t).detach().to(device=dev, dtype=torch.float64).contiguous()      # noqa: E731
+    sf, ob = f64(surfaces), f64(objects)
+    if sf.dim() != 3 or sf.shape[1] != 2 or ob.dim() != 3 or ob.shape[2] != 2:
+        raise ValueError(f"squeeze_tables: surfaces (F, 2, m) and objects (O, nv, 2) expected, got {tuple(sf.shape)} and {tuple(ob.shape)}")
+    pr = np.ascontiguousarray(pairs, dtype=np.int32).reshape(-1, 2)
+    P, T, X = len(pr), cfg.theta_cells, cfg.x_cells
+    rt = f64(squeeze_rotation_table(T) if rot is None else rot)
+    if rt.shape != (max(T, 0), 2):
+        raise ValueError(f"squeeze_tables: rot of shape {tuple(rt.shape)} (need ({T}, 2))")
+    st = f64(starts).reshape(-1, 3) if starts is not None else None
+    N = 0 if st is None else int(st.shape[0])
+    ws_bytes = int(workspace_bytes) if workspace_bytes is not None else min(max(SQUEEZE_WORKSPACE_BYTES, int(one)), int(one) * max(P, 1))
+    ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=dev)
+    new = lambda *shape, dtype: torch.empty(shape, dtype=dtype, device=dev)                            # noqa: E731
+    out = {"cells": new(P, N, 3, dtype=torch.int32), "y": new(P, N, 2, dtype=torch.float64), "flags": new(P, N, dtype=torch.int32)}
+    if tables:
+        out.update({k: new(P, max(T, 0), max(X, 0), dtype=torch.float64) for k in ("S", "touch_l", "touch_r")})
+        out["succ"] = new(P, max(T, 0) * max(X, 0), dtype=torch.int32)
+    _check_value(lib().dgdm_squeeze_map(C.byref(cfg), dptr(sf), int(sf.shape[0]), int(sf.shape[2]), dptr(ob), int(ob.shape[0]), int(ob.shape[1]),
+                                        pr.ctypes.data, P, dptr(rt), dptr(st), N, dptr(out["cells"]), dptr(out["y"]), dptr(out["flags"]),
+                                        dptr(out.get("S")), dptr(out.get("touch_l")), dptr(out.get("touch_r")), dptr(out.get("succ")), dptr(ws),
+                                        ws_bytes, stream_ptr()))
+    return out
+
+
 def prof_enable(on: bool) -> None:
     check(lib().dgdm_prof_enable(int(on)))
 

@@ -128,7 +128,11 @@ def profile_family(opt_obj: str) -> str:
 
 
 def _flag(objective: Dict[str, Any], metrics: Sequence[Dict[str, Any]]) -> Dict[str, Any]:
-    """Scores made from metrics that say they are predictions (dynamics/predicted.py) say so too; a simulator's are left as they are."""
+    """Scores made from metrics that say they are predictions (dynamics/predicted.py) or a model-made simulation (sim/squeeze.py:
+    'simulated': its name) say so too; a simulator's are left as they are."""
+    kinds = {m.get('simulated') for m in metrics}
+    if len(kinds) == 1 and None not in kinds:             # a model-made simulation (sim/squeeze.py) names itself
+        return dict(objective, simulated=kinds.pop())
     return dict(objective, predicted=True) if all(m.get('predicted', False) for m in metrics) else objective
 
 
@@ -277,7 +281,7 @@ def multi_object_table(model, log: TableLog, per_gripper_sim: Sequence[Any], num
         row += [float(edit["max"][b]), float(edit["rms"][b]), pins]
     source = [s for s in _source_objectives(edit.get("source"), opt_obj, num_objects) if s is not None]
     if source:
-        mean = {k: (float(np.mean([s[k] for s in source])) if k != 'predicted' else True) for k in source[0].keys()}
+        mean = {k: (float(np.mean([s[k] for s in source])) if k not in ('predicted', 'simulated') else source[0][k]) for k in source[0].keys()}
         rows.append([EDIT_SOURCE, mean, [], "", 0.0, 0.0, pins])
     log.log_table("val/edit_sample/allobj_%s_orirange=%.3f_%.3f" % (opt_obj, ori_range[0], ori_range[1]), columns + EDIT_COLUMNS, rows)
     return {k: all_obj[best[k]] for k in best}

@@ -377,11 +377,38 @@ def fit(model: Diffusion, pts: np.ndarray, args, bounds, dev) -> Diffusion:
     return model
 
 
+def squeeze_from_args(args):
+    """--squeeze_sim [--squeeze_closing_steps K --squeeze_window R] -> SqueezeSimulator's keywords, or None without the flag.  Host-side
+    checks only."""
+    k, r = getattr(args, "squeeze_closing_steps", None), getattr(args, "squeeze_window", None)
+    if not getattr(args, "squeeze_sim", False):
+        if k is not None or r is not None:
+            raise ValueError("--squeeze_closing_steps / --squeeze_window need --squeeze_sim")
+        return None
+    if getattr(args, "fingers_3d", False):
+        raise ValueError("--squeeze_sim is 2-D only: the squeeze model has no 3-D fingers (--fingers_3d)")
+    if getattr(args, "predicted_sim", False):
+        raise ValueError("--squeeze_sim and --predicted_sim both fill the objective tables: choose one")
+    if getattr(args, "mode", "test") != 'test':
+        raise ValueError("--squeeze_sim scores the samples of --mode=test")
+    if getattr(args, "goal_pose", None):
+        raise ValueError("--squeeze_sim with --goal_pose: goal scores (dynamics/predicted.py goal_objective) are marked as the dynamics model's "
+                         "predictions, which squeeze results are not - not supported")
+    if not getattr(args, "classifier_guidance", False):
+        raise ValueError("--squeeze_sim needs --classifier_guidance: the run's objects come with it")
+    if k is not None and k < 0:
+        raise ValueError(f"--squeeze_closing_steps={k}: the number of steps cannot be negative")
+    if r is not None and r < 1:
+        raise ValueError(f"--squeeze_window={r}: the window is at least 1 cell")
+    return {key: v for key, v in (("closing_steps", k), ("window", r)) if v is not None}
+
+
 def train(args):
     dev = torch.device("cuda", torch.cuda.current_device() if torch.cuda.is_available() else int(os.environ.get("LOCAL_RANK", "0")))
     pts = finger_control_points(args.num_fingers, args.fingers_3d)
     max_y, min_y = (0.0, -0.1) if args.fingers_3d else (0.015, -0.045)
     check_cond_flags(args)
+    squeeze_from_args(args)                 # --squeeze_sim: refused here, before anything is built
     cond_stats, cond_requested = check_label_flags(args)    # --mode=label, --cond_stats / --cond_target: refused here, before anything is built
     from ..edit import plan_from_args
     edit_plan = plan_from_args(args)        # --edit_from / --pin / --edit_band_mm / --edit_steps: read and checked before anything is built
@@ -432,6 +459,10 @@ def train(args):
         from ..dynamics.predicted import PredictedSimulator      # opt-in: the tables scored by the dynamics model instead of roll-outs
         model.object_mesh_dir = _object_mesh_dir(args) if render else None      # where --predicted_render finds <name>/model.obj
         model.simulator = PredictedSimulator(model, rollout_interactions=rollout, render_grippers=render)
+    squeeze = squeeze_from_args(args)       # --squeeze_sim: refused with --fingers_3d, --predicted_sim, outside --mode=test
+    if squeeze is not None and model.simulator is None:
+        from ..sim.squeeze import SqueezeSimulator               # opt-in: the tables scored by the squeeze model (its own idealisation)
+        model.simulator = SqueezeSimulator(model, **squeeze)
     from ..goal import goal_from_args
     model.goal = goal_from_args(args)       # --goal_pose: the sweep adds a goal objective after the reference's (Diffusion._objective_sweep)
     if model.goal is not None and getattr(args, "predicted_sim", False) and not rollout:

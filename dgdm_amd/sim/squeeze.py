@@ -1,0 +1,143 @@
+"""Squeeze simulator: a model-free 2-D closing simulator on the GPU (csrc/squeeze.hip, include/dgdm_hip.h "squeeze simulator",
+DESIGN.md §4.1d) - a frictionless, quasi-static parallel-jaw squeeze of the object contour by the two decoded finger profiles.
+
+It is this package's own idealisation and is NOT pinned to the reference's MuJoCo scene (assets/finger_sampler.py:154-177: friction 1.0,
+soft position actuators; this model has neither).  What pins it are closed-form results of frictionless squeezing (the diameter function
+of a rectangle between flat jaws, a disc in a V) and the float64 restatement tests/squeeze_oracle.py, which the device reproduces bit for
+bit.  A jaw that touches alone is assumed to carry the object along y without turning it.  ``window`` and ``closing_steps`` are untuned.
+
+* ``squeeze_map``        designs x contours -> closed and settled poses per start pose, on device tensors;
+* ``SqueezeSimulator``   a callable with the ``sim_test_batch`` signature for ``Diffusion(simulator=...)``: the tables that
+                         ``--predicted_sim`` fills with the dynamics model's opinion, filled by this model instead and marked
+                         ``'simulated': 'squeeze'`` (never ``'predicted'``).
+"""
+from __future__ import annotations
+
+from typing import Any, Dict, List, Optional, Sequence
+
+import numpy as np
+
+from ..dynamics.dataloader import SCORE_THRESHOLD
+
+# where the two jaw surfaces stand at jaw travel 0 (assets/finger_sampler.py:7-21,126-137): the lower jaw's body at y = -0.15, its profile
+# extruded 0.03 toward the object; the upper jaw's body at y = +0.15
+LOWER_OFFSET, UPPER_OFFSET = -0.12, 0.15
+OBJECT_HALF_BOX_2D = 0.05           # metres per unit of Diffusion.object_vertices (generator/train.py:111-124)
+DEG, CM = 180.0 / np.pi, 100.0
+SIMULATED = 'squeeze'
+
+
+def finger_surfaces(samples, num_points: int = 200, scale: Optional[float] = None, offset: Optional[float] = None):
+    """(B, L[, 1]) control values -> surfaces (B, 2, num_points) float64 on the device: L_j = yl_j - 0.12 and U_j = yr_j + 0.15 over
+    dgdm_finger_decode_2d's curves.  scale / offset default to DGDM_DECODE_2D_* (sampler units); 1, 0 takes metres."""
+    import torch
+    from .. import engine
+    kw = {}
+    if scale is not None:
+        kw["scale"] = float(scale)
+    if offset is not None:
+        kw["offset"] = float(offset)
+    dev = torch.device("cuda", torch.cuda.current_device())
+    s = torch.as_tensor(samples).to(dev)
+    y = engine.finger_decode_2d(s, int(num_points), **kw)[..., 1].double()
+    return torch.stack([y[:, 0] + LOWER_OFFSET, y[:, 1] + UPPER_OFFSET], dim=1).contiguous()
+
+
+def all_pairs(n_fingers: int, n_objects: int) -> np.ndarray:
+    """(finger, object) of every combination, object-major, gripper-minor (the simulator's order)."""
+    return np.array([(f, o) for o in range(n_objects) for f in range(n_fingers)], dtype=np.int32).reshape(-1, 2)
+
+
+def fold(delta, period: float):
+    """continuous_signed_delta (dynamics/utils.py:6-12) of arrays: folded once into [-period / 2, period / 2]."""
+    d = np.asarray(delta, dtype=np.float64)
+    return np.where(d > period / 2, d - period, np.where(d < -period / 2, d + period, d))
+
+
+def squeeze_map(samples, contours, starts, pairs=None, num_points: int = 200, scale: Optional[float] = None, offset: Optional[float] = None,
+                tables: bool = False, workspace_bytes: Optional[int] = None, **config) -> Dict[str, Any]:
+    """samples (B, L[, 1]) designs, contours (O, nv, 2) polygons in metres, starts (N, 3) = (theta0 rad, x0 m, y0 m) shared by all pairs,
+    pairs (P, 2) (finger, object) or None = all, object-major.  config: engine.SQUEEZE_DEFAULTS' keys.  Device tensors:
+      closed, settled (P, N, 3) float64 = (theta rad, x m, y m) after one closing and settled;  start (P, N, 2) = the snapped start cell's
+      (theta, x);  cells (P, N, 3) int32;  flags (P, N) int32 (1 loose at the start, 2 ended loose, 4 cut by the x range);  with tables:
+      S, touch_l, touch_r (P, theta_cells, x_cells), succ."""
+    import torch
+    from .. import engine
+    sf = finger_surfaces(samples, num_points, scale, offset)
+    ob = torch.as_tensor(contours)
+    pr = all_pairs(sf.shape[0], ob.shape[0]) if pairs is None else np.ascontiguousarray(pairs, dtype=np.int32).reshape(-1, 2)
+    out = engine.squeeze_tables(sf, ob, pr, starts, tables=tables, workspace_bytes=workspace_bytes, **config)
+    cfg = engine.squeeze_config(**config)
+    T, X = cfg.theta_cells, cfg.x_cells
+    cells = out["cells"].long()
+    theta = (cells // X).double() * (2.0 * np.pi) / float(T)
+    x = -cfg.x_half + (cells % X).double() * (2.0 * cfg.x_half / (X - 1))
+    out["start"] = torch.stack([theta[..., 0], x[..., 0]], dim=-1)
+    out["closed"] = torch.stack([theta[..., 1], x[..., 1], out["y"][..., 0]], dim=-1)
+    out["settled"] = torch.stack([theta[..., 2], x[..., 2], out["y"][..., 1]], dim=-1)
+    out["pairs"] = pr
+    return out
+
+
+def squeeze_metric(start, closed, settled, flags, y0=0.0, threshold: Sequence[float] = SCORE_THRESHOLD[1]) -> Dict[str, Any]:
+    """The metric dict of one (object, gripper) with build_metric's keys (dynamics/predicted.py, sim_test_mj.py:209-218) from
+    squeeze_map's rows over the start orientations: start (n, 2), closed / settled (n, 3), flags (n,), host arrays.  One-step keys from
+    one closing, classes with ``threshold`` in radians and metres as sim_test_mj.py:198-200 (+ 1); ``final_*`` from the settled pose;
+    degrees and centimetres."""
+    st, cl, se = (np.asarray(a, dtype=np.float64) for a in (start, closed, settled))
+    fl = np.asarray(flags).reshape(-1)
+    thr = np.asarray(threshold, dtype=np.float64).reshape(3)
+    d = np.stack([fold(cl[:, 0] - st[:, 0], 2.0 * np.pi), cl[:, 1] - st[:, 1], cl[:, 2] - y0], axis=1)
+    cls = np.where(d > thr, 2, np.where(d < -thr, 0, 1)).astype(np.int64)
+    zeros = np.zeros(len(d))
+    return {'delta_theta': d[:, 0] * DEG, 'delta_pos': np.stack([d[:, 1] * CM, d[:, 2] * CM, zeros], axis=1),
+            'profile': cls[:, 0], 'profile_x': cls[:, 1], 'profile_y': cls[:, 2],
+            'final_theta': se[:, 0] * DEG, 'final_delta_theta': fold(se[:, 0] - st[:, 0], 2.0 * np.pi) * DEG,
+            'final_pos': np.stack([se[:, 1] * CM, se[:, 2] * CM, zeros], axis=1),
+            'simulated': SIMULATED, 'squeeze_loose': int(np.count_nonzero(fl & 1)), 'squeeze_cut': int(np.count_nonzero(fl & 4))}
+
+
+class SqueezeSimulator:
+    """``sim_test_batch`` (dynamics/sim_test_mj.py:249) answered by the squeeze model: ``simulator(samples (n, L, 1), object_ids,
+    save_dir, num_cpus=, num_rot=, ori_range=, render=, render_last=)`` -> ``(gripper_imgs, metrics, profiles, profiles_x, profiles_y,
+    finals, videos, save_gripper_dirs)``, object-major, gripper-minor, like ``PredictedSimulator``.
+
+    Per (object, gripper) the metric is ``squeeze_metric`` over ``num_rot`` start orientations (linspace(ori_range) + 1) * pi at
+    x0 = y0 = 0.  It carries ``'simulated': 'squeeze'``, ``'squeeze_loose'`` and ``'squeeze_cut'`` and never ``'predicted'``: these are
+    this model's results, not MuJoCo measurements and not the dynamics model's opinion.  Nothing is rendered: the plot slots are None.
+    2-D only.  The call draws no random number and touches none of the sampling path's handles, so the sampled designs are the same
+    with the simulator on or off."""
+
+    def __init__(self, diffusion, closing_steps: Optional[int] = None, window: Optional[int] = None, **config):
+        if getattr(diffusion, "mode", "point") == 'point_3d':
+            raise ValueError("SqueezeSimulator: the squeeze model is 2-D only")
+        self.diffusion = diffusion
+        self.config = dict(config)
+        if closing_steps is not None:
+            self.config["closing_steps"] = int(closing_steps)
+        if window is not None:
+            self.config["window"] = int(window)
+        from .. import engine
+        c = engine.squeeze_config(**self.config)
+        if c.closing_steps < 0 or c.window < 1:
+            raise ValueError(f"SqueezeSimulator: closing_steps = {c.closing_steps} (need >= 0), window = {c.window} (need >= 1)")
+
+    def __call__(self, samples, object_ids, save_dir: Optional[str] = None, num_cpus: int = 32, num_rot: int = 360,
+                 ori_range: Sequence[float] = (-1.0, 1.0), render: bool = True, render_last: bool = False):
+        import torch
+        d = self.diffusion
+        if d.object_vertices is None:
+            raise ValueError("SqueezeSimulator: the Diffusion holds no objects (object_vertices)")
+        x = torch.as_tensor(np.asarray(samples), dtype=torch.float32)
+        n = x.shape[0]
+        known = d._object_ids()
+        oidx = [known.index(o) for o in object_ids]
+        bank = torch.as_tensor(d.object_vertices).detach().cpu().double()[oidx] * OBJECT_HALF_BOX_2D
+        theta0 = (np.linspace(ori_range[0], ori_range[1], int(num_rot)) + 1.0) * np.pi
+        starts = np.stack([theta0, np.zeros_like(theta0), np.zeros_like(theta0)], axis=1)
+        out = squeeze_map(x.reshape(n, -1), bank, starts, **self.config)
+        start, closed, settled, flags = (out[k].cpu().numpy() for k in ("start", "closed", "settled", "flags"))
+        thr = SCORE_THRESHOLD[1]
+        metrics = [squeeze_metric(start[p], closed[p], settled[p], flags[p], 0.0, thr) for p in range(len(oidx) * n)]
+        none: List[Any] = [None] * (len(oidx) * n)
+        return list(none), metrics, list(none), list(none), list(none), list(none), [[] for _ in none], list(none)

@@ -729,6 +729,68 @@ int dgdm_render_meshes(const float *verts_dev, const int32_t *tris_dev, const in
                        int width, int height, int32_t *ids_dev, float *depth_dev, uint8_t *rgb_dev, int32_t *rejected_dev,
                        int32_t *snapped_dev, void *workspace_dev, int64_t workspace_bytes, void *stream);
 
+/* ------------------------------------------------------------------ squeeze simulator (csrc/squeeze.hip)
+ * A model-free 2-D closing simulator: a frictionless, quasi-static parallel-jaw squeeze of an object contour by two finger surfaces.  It
+ * is this project's own idealisation, not the reference's MuJoCo scene (friction 1.0, soft position actuators: assets/finger_sampler.py:
+ * 154-177), and is pinned by closed-form results of frictionless squeezing and by tests/squeeze_oracle.py, which the device reproduces
+ * bit for bit.  All arithmetic is float64; every product, sum and quotient below is rounded on its own, in the order written; no
+ * transcendental function is evaluated on the device.
+ *
+ * Inputs.  surfaces_dev [n_fingers][2][m]: the lower (L) and upper (U) jaw surface of each finger pair in the world frame at jaw
+ *   travel 0, sampled at u_j = -hl + j h, h = 2 hl / (m - 1), hl = finger_half_len.  objects_dev [n_objects][nv][2]: closed polygons in
+ *   metres about their own origin, either winding.  rot_dev [theta_cells][2] = (cos, sin) of theta_a = 2 pi a / theta_cells, made by the
+ *   caller.  pairs_host [n_pairs][2] int32 = (finger, object), HOST memory.  starts_dev [n_starts][3] = (theta0, x0, y0), shared by all
+ *   pairs.
+ * Cell (a, b): the pose theta_a, x_b = -x_half + b dx, dx = 2 x_half / (x_cells - 1), the object at y = 0;
+ *   P_i = (c vx_i - s vy_i + x_b, s vx_i + c vy_i).  Two candidate sets, for both jaws:
+ *   A  the vertices with -hl <= P_ix <= hl:  t = (P_ix + hl) / h, j = min(floor t, m - 2), f = t - j, Lp = L_j + f (L_{j+1} - L_j), Up
+ *      likewise; gaps P_iy - Lp and Up - P_iy;
+ *   B  for every edge (P_i, P_{i+1}), cyclic, with xa != xb, the finger samples j0 = max(ceil((min(xa, xb) + hl) / h), 0) <= j <=
+ *      j1 = min(floor((max(xa, xb) + hl) / h), m - 1):  ye = ya + (u_j - xa) ((yb - ya) / (xb - xa)); gaps ye - L_j and U_j - ye.
+ *   touch_l = the least lower gap, touch_r = the least upper gap (+inf for an empty set): both functions are piecewise linear, so the
+ *   two sets hold the exact minimum, and a minimum does not depend on the order it is taken in.  S = (touch_l + touch_r) / 2 is the
+ *   common jaw travel at which both jaws touch.
+ * Motion.  Two jaws under a constant closing force are a potential -2 F S; overdamped and frictionless, the object climbs S.  A jaw that
+ *   touches alone carries the object along y without turning it (an assumption of this model, not a result).
+ *   Successor of a cell: itself (a fixed point) if S >= travel_max - the jaws are fully closed and the object is loose; +inf included.
+ *   Otherwise the candidates (da, db), |da|, |db| <= window, not both 0, a + da modulo theta_cells, b + db outside 0 .. x_cells - 1
+ *   dropped, are visited in ascending (|db|, |da|, da, db); the best starts at the cell's own S and is replaced on strictly greater only
+ *   (so a pure rotation wins a tie).  S rises strictly along a path: no cycles.
+ *   One closing = the closing_steps-th successor (or the fixed point if reached first); settled = the fixed point.  Both by pointer
+ *   doubling over ceil(log2(cells)) rounds on the device, no host wait in between.
+ *   A start snaps to the nearest cell:  a = floor(theta0 / (2 pi / theta_cells) + 0.5) modulo theta_cells,
+ *   b = floor((x0 + x_half) / dx + 0.5) clamped to 0 .. x_cells - 1 (halves round up; a non-finite start lands on cell 0).
+ *   y at a reached cell: (touch_r - touch_l) / 2 if S < travel_max, else y0 clamped to [travel_max - touch_l, touch_r - travel_max].
+ *   Flags per start: 1 = loose at the start cell; 2 = the path ended on a cell with S >= travel_max; 4 = settled on b = 0 or
+ *   b = x_cells - 1, where the table's x range cut the path.
+ * Known limit: a ridge of S oblique to the grid can stall the climb early; `window` widens the directions it can take - a mitigation,
+ *   not a cure.  window and closing_steps are untuned.
+ * Outputs, device memory: cells_dev [n_pairs][n_starts][3] int32 = the start, closed and settled cell (a x_cells + b);
+ *   y_dev [n_pairs][n_starts][2] = y at the closed and the settled cell; flags_dev [n_pairs][n_starts] int32 (n_starts = 0: all
+ *   may be null).  Optional (null = not wanted): table_s_dev, touch_l_dev, touch_r_dev [n_pairs][theta_cells][x_cells] float64 and
+ *   succ_dev [n_pairs][theta_cells x_cells] int32.
+ * Pairs are processed in chunks of as many as workspace_bytes holds (dgdm_squeeze_workspace_bytes(cfg, chunk_pairs); at least one).
+ * Every argument is validated before any launch: DGDM_EINVAL for theta_cells < 1, x_cells < 2, more than 2^30 cells, window outside
+ * 1 .. 64, closing_steps < 0, non-finite or non-positive x_half / finger_half_len, a non-finite travel_max, m outside 2 .. 1024, nv
+ * outside 3 .. 1024, a pair index out of range, a null required pointer, a workspace too small for one pair.  Synchronises the stream
+ * once, at the end (the pair list is the caller's).                                                                                   */
+typedef struct DgdmSqueezeConfig {
+    int32_t theta_cells;        /* 720 */
+    int32_t x_cells;            /* 241 */
+    int32_t window;             /* R: 2 */
+    int32_t closing_steps;      /* k: 6 */
+    double  x_half;             /* 0.06 */
+    double  travel_max;         /* 0.1 */
+    double  finger_half_len;    /* hl: 0.12 */
+} DgdmSqueezeConfig;
+/* Bytes of device workspace for chunks of chunk_pairs pairs; negative: bad config. */
+int64_t dgdm_squeeze_workspace_bytes(const DgdmSqueezeConfig *cfg, int chunk_pairs);
+int dgdm_squeeze_map(const DgdmSqueezeConfig *cfg, const double *surfaces_dev, int n_fingers, int num_points, const double *objects_dev,
+                     int n_objects, int num_vertices, const int32_t *pairs_host, int n_pairs, const double *rot_dev,
+                     const double *starts_dev, int n_starts, int32_t *cells_dev, double *y_dev, int32_t *flags_dev, double *table_s_dev,
+                     double *touch_l_dev, double *touch_r_dev, int32_t *succ_dev, void *workspace_dev, int64_t workspace_bytes,
+                     void *stream);
+
 /* ------------------------------------------------------------------ measurement hooks
  * When enabled, the launches of every stage of the path are bracketed by hipEvents on the stream they are launched on.
  * dgdm_prof_read_stage synchronises those events and returns, for one stage, the number of bracketed regions, their total

@@ -1,5 +1,6 @@
-"""Import-path shim: ``sim.render_mesh`` of the reference maps onto ``dgdm_amd.sim.render_mesh`` (gripper pictures and object
-silhouettes on the library's rasteriser, see dgdm_amd/sim/__init__.py)."""
+"""Import-path shim: ``sim.render_mesh`` / ``sim.sim_2d`` of the reference map onto ``dgdm_amd.sim.*`` (``sim_2d`` makes its data with the
+squeeze simulator of ``dgdm_amd.sim.squeeze`` instead of MuJoCo)."""
 import sys as _sys
-from dgdm_amd.sim import render_mesh  # noqa: F401
-_sys.modules[__name__ + ".render_mesh"] = render_mesh
+from dgdm_amd.sim import render_mesh, sim_2d, squeeze  # noqa: F401
+for _n in ("render_mesh", "sim_2d", "squeeze"):
+    _sys.modules.setdefault(__name__ + "." + _n, getattr(_sys.modules[__name__], _n))
