@@ -109,8 +109,10 @@ struct ResOff { size_t c0w, c0b, g0w, g0b, c1w, c1b, g1w, g1b, cw, cb, rw, rb; b
                 size_t c0w16 = 0, c1w16 = 0, rw16 = 0;         // element offsets of the bf16 images (MFMA convolutions only)
                 size_t c0wh = 0, c1wh = 0, rwh = 0; int c0e = 0, c1e = 0, re = 0; };      // ... of the f16x3 images and their scale exponents
 
-int pack_res(const StateDict &sd, Blob &bl, std::vector<uint16_t> &b16, std::vector<uint16_t> &bh, const std::string &p, int cin, int cout, int cond,
-             int cond_rows /* >= cond: rows of the transposed cond_encoder weight, zero past cond */, int kw, ResOff *o) {
+int pack_res(const StateDict &sd, Blob &bl, std::vector<uint16_t> &b16, std::vector<uint16_t> &bh, const std::string &p, int cin, int cout, int dsed, int gc,
+             int dsp, int gcp /* dsed and gc rounded up to dot_kn's step of 8: the transposed cond_encoder weight is [dsp + gcp][2 cout], the step part's
+             rows [dsed, dsp) and the condition part's rows past gc zero */, int kw, ResOff *o) {
+    const int cond = dsed + gc;
     auto vec = [&](const std::string &k, int64_t n, size_t *off) -> int {
         const float *d = sd.f32(k, n);
         if (!d) return DGDM_EKEY;
@@ -143,8 +145,11 @@ int pack_res(const StateDict &sd, Blob &bl, std::vector<uint16_t> &b16, std::vec
     if ((rc = vec(p + ".blocks.1.block.1.bias", cout, &o->g1b))) return rc;
     if (!(w = sd.f32(p + ".cond_encoder.1.weight", (int64_t)2 * cout * cond))) return DGDM_EKEY;
     {
-        std::vector<float> wt = transpose(w, 2 * cout, cond);
-        wt.resize((size_t)cond_rows * 2 * cout, 0.f);
+        const std::vector<float> t = transpose(w, 2 * cout, cond);
+        const size_t N = (size_t)2 * cout;
+        std::vector<float> wt((size_t)(dsp + gcp) * N, 0.f);
+        std::copy(t.begin(), t.begin() + (size_t)dsed * N, wt.begin());
+        std::copy(t.begin() + (size_t)dsed * N, t.end(), wt.begin() + (size_t)dsp * N);
         o->cw = bl.add(wt);
     }
     if ((rc = vec(p + ".cond_encoder.1.bias", 2 * cout, &o->cb))) return rc;
@@ -166,7 +171,11 @@ extern "C" int dgdm_unet1d_create(DgdmUnet1d **out, const DgdmTensor *tensors, i
     DGDM_REQUIRE(n_down == 2, DGDM_EINVAL, "only two-level U-Nets (len(down_dims) == 2, as generator/train.py:80 builds) are supported, got %d", n_down);
     DGDM_REQUIRE(kernel_size == 5, DGDM_EINVAL, "kernel_size %d unsupported (reference uses 5)", kernel_size);
     const int d0 = down_dims[0], d1 = down_dims[1];
-    DGDM_REQUIRE(d0 % n_groups == 0 && d1 % n_groups == 0 && dsed % 2 == 0 && dsed >= 4, DGDM_EINVAL, "bad U-Net dims");
+    DGDM_REQUIRE(n_groups >= 1 && d0 >= 128 && d1 >= 128, DGDM_EINVAL, "bad U-Net dims (widths %d, %d, n_groups %d)", d0, d1, n_groups);
+    // dsed: SinusoidalPosEmb needs half - 1 > 0.  Above 64 the step encoder's and the FiLM linears' serial float32 chains (4 dsed and dsed + gc
+    // terms, dot_kn) no longer hold the 1e-6 against float64 the tests ask for (measured 2.3e-6 at dsed = 256)
+    DGDM_REQUIRE(d0 % n_groups == 0 && d1 % n_groups == 0 && dsed % 2 == 0 && dsed >= 4 && dsed <= 64, DGDM_EINVAL,
+                 "bad U-Net dims (n_groups %d must divide the widths %d, %d; diffusion_step_embed_dim %d must be even, 4 ... 64)", n_groups, d0, d1, dsed);
     DGDM_REQUIRE(d0 % 128 == 0 && d1 % 128 == 0, DGDM_EINVAL, "U-Net widths must be multiples of 128 for the MFMA tiling and its chunked accumulation (got %d, %d)", d0, d1);
     StateDict sd(tensors, n_tensors);
     std::unique_ptr<DgdmUnet1d> m(new DgdmUnet1d());
@@ -191,9 +200,11 @@ extern "C" int dgdm_unet1d_create(DgdmUnet1d **out, const DgdmTensor *tensors, i
         DGDM_REQUIRE(gc < 0 || g == gc, DGDM_EINVAL, "%s: global_cond_dim %lld differs from the %d of the blocks before it", key.c_str(), (long long)g, gc);
         gc = (int)g;
     }
-    const int gcp = (gc + 7) & ~7;
+    // dot_kn walks its K in steps of 8: the step part and the condition part of cat(step embedding, global_cond) are each padded to a
+    // multiple of 8 with zero weight rows (and zeros in the LDS vector they meet, unet.hip); dsed = 32 pads nothing
+    const int gcp = (gc + 7) & ~7, dsp = (dsed + 7) & ~7;
     for (int i = 0; i < 8; ++i)
-        if ((rc = pack_res(sd, bl, b16, bh, spec[i].name, spec[i].cin, spec[i].cout, dsed + gc, dsed + gcp, kernel_size, &ro[i]))) return rc;
+        if ((rc = pack_res(sd, bl, b16, bh, spec[i].name, spec[i].cin, spec[i].cout, dsed, gc, dsp, gcp, kernel_size, &ro[i]))) return rc;
     const float *w, *b;
     // diffusion_step_encoder
     std::vector<float> fr(dsed / 2);
@@ -204,7 +215,9 @@ extern "C" int dgdm_unet1d_create(DgdmUnet1d **out, const DgdmTensor *tensors, i
     }
     const size_t o_fr = bl.add(fr);
     if (!(w = sd.f32("diffusion_step_encoder.1.weight", (int64_t)4 * dsed * dsed)) || !(b = sd.f32("diffusion_step_encoder.1.bias", 4 * dsed))) return DGDM_EKEY;
-    const size_t o_s1w = bl.add(transpose(w, 4 * dsed, dsed)), o_s1b = bl.add(b, 4 * dsed);
+    std::vector<float> s1wt = transpose(w, 4 * dsed, dsed);
+    s1wt.resize((size_t)dsp * 4 * dsed, 0.f);                          // [dsp][4 dsed], rows past dsed zero
+    const size_t o_s1w = bl.add(s1wt), o_s1b = bl.add(b, 4 * dsed);
     if (!(w = sd.f32("diffusion_step_encoder.3.weight", (int64_t)4 * dsed * dsed)) || !(b = sd.f32("diffusion_step_encoder.3.bias", dsed))) return DGDM_EKEY;
     const size_t o_s3w = bl.add(transpose(w, dsed, 4 * dsed)), o_s3b = bl.add(b, dsed);
     if (!(w = sd.f32("down_modules.0.2.conv.weight", (int64_t)d0 * d0 * 3)) || !(b = sd.f32("down_modules.0.2.conv.bias", d0))) return DGDM_EKEY;
@@ -234,7 +247,7 @@ extern "C" int dgdm_unet1d_create(DgdmUnet1d **out, const DgdmTensor *tensors, i
     UnetParams &p = m->p;
     memset(&p, 0, sizeof p);
     p.d0 = d0; p.d1 = d1; p.dsed = dsed; p.groups = n_groups; p.cmax = std::max(d0, d1);
-    p.gc = gc; p.gcp = gcp;
+    p.gc = gc; p.gcp = gcp; p.dsp = dsp;
     p.freqs = bl.at(o_fr);
     p.se1_wt = bl.at(o_s1w); p.se1_b = bl.at(o_s1b); p.se3_wt = bl.at(o_s3w); p.se3_b = bl.at(o_s3b);
     for (int i = 0; i < 8; ++i) {

@@ -626,7 +626,7 @@ __global__ __launch_bounds__(UNET_THREADS) void unet_kernel(const UnetParams *__
     s.D = s.C + bufS;
     s.film = s.D + bufS;
     s.cond = s.film + 8 * 2 * p.cmax;
-    s.tmp = s.cond + p.dsed;
+    s.tmp = s.cond + p.dsp;                        // cond holds dsp floats: dsed values, then zeros up to dot_kn's step of 8
     s.xin = s.tmp + max(4 * p.dsed, p.gcp);       // the global condition takes over tmp once the step encoder is done with it: cond | tmp = cat(step, global)
     s.scr = s.xin + ((L + 4 + 3) & ~3);            // f16x3: 16 floats for the scale reduction, then the activation slab(s)
     s.bf16 = p.bf16;
@@ -642,8 +642,11 @@ __global__ __launch_bounds__(UNET_THREADS) void unet_kernel(const UnetParams *__
             s.cond[t] = sinf(a);
             s.cond[half + t] = cosf(a);
         }
+        // the rows of se1_wt and of every cond_wt past dsed are zero up to dsp (models_api.hip), and so is the vector they meet: nothing
+        // below writes cond[dsed, dsp), so both dot_kn passes over it add 0 * 0
+        if (t >= p.dsed && t < p.dsp) s.cond[t] = 0.f;
         __syncthreads();
-        matvec(p.se1_wt, p.se1_b, s.cond, s.tmp, p.dsed, 4 * p.dsed);
+        matvec(p.se1_wt, p.se1_b, s.cond, s.tmp, p.dsp, 4 * p.dsed);
         __syncthreads();
         for (int i = t; i < 4 * p.dsed; i += blockDim.x) s.tmp[i] = mish(s.tmp[i]);
         __syncthreads();
@@ -664,7 +667,7 @@ __global__ __launch_bounds__(UNET_THREADS) void unet_kernel(const UnetParams *__
         for (int i = t; i < 8 * stride; i += blockDim.x) {
             const int blk = i / stride, n = i - blk * stride, N = 2 * p.res[blk].cout;
             if (n < N) {
-                films[i] = dot_kn(p.res[blk].cond_wt, N, n, s.cond, p.dsed + p.gcp) + p.res[blk].cond_b[n];
+                films[i] = dot_kn(p.res[blk].cond_wt, N, n, s.cond, p.dsp + p.gcp) + p.res[blk].cond_b[n];
             }
         }
     }
@@ -1036,9 +1039,9 @@ __global__ __launch_bounds__(UB_THREADS) void ub_layer_kernel(const UbArgs A) {
 constexpr int UB_GC_MAX = 256;
 __global__ __launch_bounds__(256) void ub_cond_kernel(const UnetParams *__restrict__ pp, const int *__restrict__ timestep, const float *__restrict__ gcond,
                                                       float *__restrict__ film, int *__restrict__ film_idx) {
-    __shared__ float cond_raw[32 + UB_GC_MAX + 8];       // cond [dsed <= 32] | tmp [max(4 dsed, gcp)]
+    __shared__ float cond_raw[32 + UB_GC_MAX + 8];       // cond [dsp <= 32] | tmp [max(4 dsed, gcp)]
     const UnetParams &p = *pp;
-    lds_f *cond = (lds_f *)cond_raw, *tmp = cond + p.dsed;
+    lds_f *cond = (lds_f *)cond_raw, *tmp = cond + p.dsp;
     const int b = blockIdx.x, t = threadIdx.x;
     const bool same = !gcond && b > 0 && timestep[b] == timestep[0];
     if (t == 0) film_idx[b] = same ? 0 : b;
@@ -1050,8 +1053,9 @@ __global__ __launch_bounds__(256) void ub_cond_kernel(const UnetParams *__restri
         cond[t] = sinf(a);
         cond[half + t] = cosf(a);
     }
+    if (t >= p.dsed && t < p.dsp) cond[t] = 0.f;         // as unet_kernel: zeros against the zero weight rows [dsed, dsp)
     __syncthreads();
-    matvec(p.se1_wt, p.se1_b, cond, tmp, p.dsed, 4 * p.dsed);
+    matvec(p.se1_wt, p.se1_b, cond, tmp, p.dsp, 4 * p.dsed);
     __syncthreads();
     for (int i = t; i < 4 * p.dsed; i += blockDim.x) tmp[i] = mish(tmp[i]);
     __syncthreads();
@@ -1063,7 +1067,7 @@ __global__ __launch_bounds__(256) void ub_cond_kernel(const UnetParams *__restri
     const int stride = 2 * p.cmax;
     for (int i = t; i < 8 * stride; i += blockDim.x) {
         const int blk = i / stride, n = i - blk * stride, N = 2 * p.res[blk].cout;
-        if (n < N) film[(size_t)b * 8 * stride + i] = dot_kn(p.res[blk].cond_wt, N, n, cond, p.dsed + p.gcp) + p.res[blk].cond_b[n];
+        if (n < N) film[(size_t)b * 8 * stride + i] = dot_kn(p.res[blk].cond_wt, N, n, cond, p.dsp + p.gcp) + p.res[blk].cond_b[n];
     }
 }
 
@@ -1184,7 +1188,7 @@ static size_t unet_lds_floats(const UnetParams &p, int L) {
     const int L2 = (L - 1) / 2 + 1;
     const int bufS = std::max((L + 4) * (p.d0 + UNET_ROW_PAD), (L2 + 4) * (p.d1 + UNET_ROW_PAD));
     const int bufA = std::max((L + 4) * (p.d0 + UNET_ROW_PAD), (L2 + 4) * (2 * p.d1 + UNET_ROW_PAD));
-    return (size_t)bufA + 3 * (size_t)bufS + 8 * 2 * p.cmax + p.dsed + std::max(4 * p.dsed, p.gcp) + (L + 4 + 3) + 16;
+    return (size_t)bufA + 3 * (size_t)bufS + 8 * 2 * p.cmax + p.dsp + std::max(4 * p.dsed, p.gcp) + (L + 4 + 3) + 16;
 }
 static size_t unet_slab_floats(int L) { return 16 + (size_t)UNET_SLAB_GROUPS * (L + 4) * 32; }
 

@@ -544,7 +544,9 @@ extern "C" int dgdm_unet_trainer_create(DgdmUnetTrainer **out, const DgdmTensor 
                  down_dims[0], down_dims[1]);
     DGDM_REQUIRE(num_points >= 2 && num_points % 2 == 0 && num_points <= 512, DGDM_EINVAL, "dgdm_unet_trainer_create: num_points %d (must be even: the up path "
                  "returns 2 * (L / 2) positions)", num_points);
-    DGDM_REQUIRE(dsed >= 4 && dsed % 4 == 0, DGDM_EINVAL, "dgdm_unet_trainer_create: diffusion_step_embed_dim %d", dsed);
+    // dsed % 4: the GEMMs' row windows of the [S][dsed] tensors are read as aligned float4 (train_gemm.h); a window runs up to the image's K
+    // rounded to 16 - into the following rows or the buffer's guard, all finite - and meets the image's zero rows there
+    DGDM_REQUIRE(dsed >= 4 && dsed % 4 == 0 && dsed <= 64, DGDM_EINVAL, "dgdm_unet_trainer_create: diffusion_step_embed_dim %d (a multiple of 4, 4 ... 64: what dgdm_unet1d_create takes)", dsed);
     std::unique_ptr<DgdmUnetTrainer> m(new DgdmUnetTrainer());
     m->L = num_points; m->d0 = down_dims[0]; m->d1 = down_dims[1]; m->dsed = dsed; m->ks = kernel_size;
     m->beta1 = beta1; m->beta2 = beta2; m->eps = eps; m->wd = weight_decay;

@@ -77,7 +77,22 @@ int         dgdm_objective_from_name(const char *opt_obj, DgdmObjective *out);
 /* ------------------------------------------------------------------ a7: noise-prediction net
  * ConditionalUnet1D(input_dim=1, global_cond_dim, down_dims, diffusion_step_embed_dim,
  * kernel_size=5, n_groups=8)  (generator/diffusion_utils.py:124-236).  global_cond_dim (0..256) is read from the state dict: the
- * in_features of every `*.cond_encoder.1.weight` minus step_embed_dim; the eight blocks must agree (DGDM_EINVAL names the tensor). */
+ * in_features of every `*.cond_encoder.1.weight` minus step_embed_dim; the eight blocks must agree (DGDM_EINVAL names the tensor).
+ *
+ * Accepted domain (everything else is DGDM_EINVAL from the host code, before any launch; tests/test_gpu_unet_shapes.py runs it):
+ *   n_down          2 (down_dims = {d0, d1}); kernel_size 5; input_dim 1
+ *   d0, d1          multiples of 128 (16-channel MFMA tiles, accumulation chunks of 128 input channels); d0 == d1 is allowed
+ *   n_groups        >= 1 and a divisor of both widths
+ *   step_embed_dim  even, 4 ... 64 (widths that are no multiple of 8 are padded with zero weight rows; above 64 the float32 chains of
+ *                   the step encoder no longer hold 1e-6 against float64)
+ *   L (forward)     even, 2 ... 64, and one sample's activations must fit the 160 KiB LDS.  With CPx = x + 8, L2 = L / 2:
+ *                     floats = max((L+4) CP(d0), (L2+4) CP(2 d1)) + 3 max((L+4) CP(d0), (L2+4) CP(d1)) + 16 max(d0, d1)
+ *                              + pad8(step_embed_dim) + max(4 step_embed_dim, pad8(global_cond_dim)) + L + 23,   4 floats <= 163840.
+ *                   Largest L: 46 for (128, 256), 64 for (128, 128), 28 for (256, 256), 26 for (128, 384), 16 for (256, 512).
+ *                   The default arithmetic (three f16 products) needs 64 + 256 (L + 4) bytes more for its split slabs; where only that
+ *                   does not fit - (128, 256): L = 44, 46; (128, 128): 60 ... 64; (256, 256): 28; (128, 384): 26 - the float32 MFMA chain runs instead
+ *                   and dgdm_unet1d_effective_form says so.
+ *   batched form    (large batches) only for (128, 256) and step_embed_dim <= 32; other nets run the per-sample kernel at every B.  */
 int dgdm_unet1d_create(DgdmUnet1d **out, const DgdmTensor *state_dict, int n_tensors,
                        const int32_t *down_dims, int n_down, int step_embed_dim, int kernel_size, int n_groups);
 void dgdm_unet1d_destroy(DgdmUnet1d *m);
@@ -939,7 +954,11 @@ int dgdm_class_agreement(const float *score_dev, const float *pred_dev, int64_t 
  * (generator/diffusion_utils.py:123-285; input_dim 1, down_dims [128, 256], kernel 5, 8 groups), torch.optim.Adam
  * (diffusion.py:711-714) and the EMA copy of diffusers' EMAModel (diffusion.py:716-724).  Parameters, gradients, both Adam moments and the
  * EMA copy live on the device in the state_dict's own tensor layouts (keys as ConditionalUnet1D.state_dict() gives them).
- * global_cond_dim is read from the state dict as in dgdm_unet1d_create.                                                           */
+ * global_cond_dim is read from the state dict as in dgdm_unet1d_create.
+ * Accepted domain (else DGDM_EINVAL; tests/test_gpu_unet_train.py): n_down 2 with down_dims {128, 256}, kernel_size 5, n_groups 8 (the
+ * GroupNorm kernels are written for these); num_points even, 2 ... 512 (rows per sample num_points + 8 and num_points / 2 + 4, general
+ * in num_points); diffusion_step_embed_dim a multiple of 4, 4 ... 64 (the GEMMs read aligned float4 windows of the [B][dsed] tensors;
+ * K is rounded up to 16 inside the weight images, zero rows against whatever finite values the window runs into).                  */
 typedef struct DgdmUnetTrainer DgdmUnetTrainer;
 int dgdm_unet_trainer_create(DgdmUnetTrainer **out, const DgdmTensor *state_dict, int n_tensors, int num_points, const int32_t *down_dims,
                              int n_down, int diffusion_step_embed_dim, int kernel_size, int n_groups, float beta1, float beta2, float eps,

@@ -99,21 +99,22 @@ def _conv_gn_mish(sd: SD, p: str, x: torch.Tensor, groups: int = 8) -> torch.Ten
     return F.mish(x)
 
 
-def _film_res_block(sd: SD, p: str, x: torch.Tensor, cond: torch.Tensor) -> torch.Tensor:
+def _film_res_block(sd: SD, p: str, x: torch.Tensor, cond: torch.Tensor, n_groups: int = 8) -> torch.Tensor:
     # generator/diffusion_utils.py:101-120
-    out = _conv_gn_mish(sd, p + ".blocks.0", x)
+    out = _conv_gn_mish(sd, p + ".blocks.0", x, n_groups)
     e = F.linear(F.mish(cond), sd[p + ".cond_encoder.1.weight"], sd[p + ".cond_encoder.1.bias"])
     c = out.shape[1]
     out = e[:, :c, None] * out + e[:, c:, None]
-    out = _conv_gn_mish(sd, p + ".blocks.1", out)
+    out = _conv_gn_mish(sd, p + ".blocks.1", out, n_groups)
     if p + ".residual_conv.weight" in sd:
         xc, wc = _rc(x, sd[p + ".residual_conv.weight"])
         x = F.conv1d(xc, wc, sd[p + ".residual_conv.bias"])
     return out + x
 
 
-def unet1d_forward(sd: SD, sample: torch.Tensor, timestep: torch.Tensor) -> torch.Tensor:
-    """``ConditionalUnet1D.forward`` (generator/diffusion_utils.py:238-285); sample (B,L,C), timestep (B,)."""
+def unet1d_forward(sd: SD, sample: torch.Tensor, timestep: torch.Tensor, n_groups: int = 8) -> torch.Tensor:
+    """``ConditionalUnet1D.forward`` (generator/diffusion_utils.py:238-285); sample (B,L,C), timestep (B,).  n_groups: the GroupNorm
+    group count of every Conv1dBlock (the constructor's argument; it leaves no trace in the state_dict)."""
     x = sample.transpose(1, 2)
     dsed = sd["diffusion_step_encoder.1.weight"].shape[1]
     half = dsed // 2
@@ -126,22 +127,22 @@ def unet1d_forward(sd: SD, sample: torch.Tensor, timestep: torch.Tensor) -> torc
     n_up = 1 + max(int(k.split(".")[1]) for k in sd if k.startswith("up_modules."))
     skips: List[torch.Tensor] = []
     for lvl in range(n_down):                                                 # :265-269
-        x = _film_res_block(sd, f"down_modules.{lvl}.0", x, g)
-        x = _film_res_block(sd, f"down_modules.{lvl}.1", x, g)
+        x = _film_res_block(sd, f"down_modules.{lvl}.0", x, g, n_groups)
+        x = _film_res_block(sd, f"down_modules.{lvl}.1", x, g, n_groups)
         skips.append(x)
         if f"down_modules.{lvl}.2.conv.weight" in sd:
             xc, wc = _rc(x, sd[f"down_modules.{lvl}.2.conv.weight"])
             x = F.conv1d(xc, wc, sd[f"down_modules.{lvl}.2.conv.bias"], stride=2, padding=1)
     for i in range(2):                                                        # :271-272
-        x = _film_res_block(sd, f"mid_modules.{i}", x, g)
+        x = _film_res_block(sd, f"mid_modules.{i}", x, g, n_groups)
     for lvl in range(n_up):                                                   # :274-278
         x = torch.cat((x, skips.pop()), dim=1)
-        x = _film_res_block(sd, f"up_modules.{lvl}.0", x, g)
-        x = _film_res_block(sd, f"up_modules.{lvl}.1", x, g)
+        x = _film_res_block(sd, f"up_modules.{lvl}.0", x, g, n_groups)
+        x = _film_res_block(sd, f"up_modules.{lvl}.1", x, g, n_groups)
         if f"up_modules.{lvl}.2.conv.weight" in sd:
             xc, wc = _rc(x, sd[f"up_modules.{lvl}.2.conv.weight"])
             x = F.conv_transpose1d(xc, wc, sd[f"up_modules.{lvl}.2.conv.bias"], stride=2, padding=1)
-    x = _conv_gn_mish(sd, "final_conv.0", x)                                  # :280
+    x = _conv_gn_mish(sd, "final_conv.0", x, n_groups)                        # :280
     x = F.conv1d(x, sd["final_conv.1.weight"], sd["final_conv.1.bias"])
     return x.transpose(1, 2)
 

@@ -19,7 +19,7 @@ def global_cond_dim(sd: SD) -> int:
     return int(sd["mid_modules.0.cond_encoder.1.weight"].shape[1] - sd["diffusion_step_encoder.1.weight"].shape[1])
 
 
-def unet1d_forward_cond(sd: SD, sample: torch.Tensor, timestep: torch.Tensor, cond: Optional[torch.Tensor]) -> torch.Tensor:
+def unet1d_forward_cond(sd: SD, sample: torch.Tensor, timestep: torch.Tensor, cond: Optional[torch.Tensor], n_groups: int = 8) -> torch.Tensor:
     """sample (B, L, 1), timestep (B,), cond (B, gc) or None (gc == 0) -> (B, L, 1), in sd's dtype."""
     dt = sd["diffusion_step_encoder.1.weight"].dtype
     x = sample.to(dt).transpose(1, 2)
@@ -32,18 +32,18 @@ def unet1d_forward_cond(sd: SD, sample: torch.Tensor, timestep: torch.Tensor, co
     g = F.linear(F.mish(g), sd["diffusion_step_encoder.3.weight"], sd["diffusion_step_encoder.3.bias"])
     if cond is not None:
         g = torch.cat((g, cond.to(dt)), dim=-1)                                  # :254-257
-    x = orc._film_res_block(sd, "down_modules.0.0", x, g)
-    x = orc._film_res_block(sd, "down_modules.0.1", x, g)
+    x = orc._film_res_block(sd, "down_modules.0.0", x, g, n_groups)
+    x = orc._film_res_block(sd, "down_modules.0.1", x, g, n_groups)
     x = F.conv1d(x, sd["down_modules.0.2.conv.weight"], sd["down_modules.0.2.conv.bias"], stride=2, padding=1)
-    x = orc._film_res_block(sd, "down_modules.1.0", x, g)
-    skip = x = orc._film_res_block(sd, "down_modules.1.1", x, g)
-    x = orc._film_res_block(sd, "mid_modules.0", x, g)
-    x = orc._film_res_block(sd, "mid_modules.1", x, g)
+    x = orc._film_res_block(sd, "down_modules.1.0", x, g, n_groups)
+    skip = x = orc._film_res_block(sd, "down_modules.1.1", x, g, n_groups)
+    x = orc._film_res_block(sd, "mid_modules.0", x, g, n_groups)
+    x = orc._film_res_block(sd, "mid_modules.1", x, g, n_groups)
     x = torch.cat((x, skip), dim=1)
-    x = orc._film_res_block(sd, "up_modules.0.0", x, g)
-    x = orc._film_res_block(sd, "up_modules.0.1", x, g)
+    x = orc._film_res_block(sd, "up_modules.0.0", x, g, n_groups)
+    x = orc._film_res_block(sd, "up_modules.0.1", x, g, n_groups)
     x = F.conv_transpose1d(x, sd["up_modules.0.2.conv.weight"], sd["up_modules.0.2.conv.bias"], stride=2, padding=1)
-    x = orc._conv_gn_mish(sd, "final_conv.0", x)
+    x = orc._conv_gn_mish(sd, "final_conv.0", x, n_groups)
     x = F.conv1d(x, sd["final_conv.1.weight"], sd["final_conv.1.bias"])
     return x.transpose(1, 2)
 

@@ -502,7 +502,8 @@ def test_unet_batched_equals_per_sample(dev):
     """The eps-net's two execution forms of the default (f16x3) arithmetic - one workgroup per sample with the whole network in LDS, and, for
     large batches, layer-by-layer launches with four samples per workgroup and the activations in global memory (csrc/unet.hip, "batched
     form") - are the same arithmetic operation for operation: identical bits, for every batch size (ragged last workgroup included), both
-    finger lengths, mixed timesteps, and when a smaller batch follows a larger one in the same workspace."""
+    finger lengths, mixed timesteps, and when a smaller batch follows a larger one in the same workspace.  Also at the lengths where a sample's
+    boundary falls elsewhere inside the batched form's 16-row position tiles (L = 2, 4, 16, 32, 34), and with a step embedding of 12."""
     sd = util.unet_sd(11)
     env = os.environ.get("DGDM_UNET_BATCHED_MIN")
     try:
@@ -510,14 +511,23 @@ def test_unet_batched_equals_per_sample(dev):
         per_sample = engine.Unet1d(sd)
         os.environ["DGDM_UNET_BATCHED_MIN"] = "1"
         batched = engine.Unet1d(sd)
+        # a step embedding narrower than dot_kn's step of 8 (dsed = 12: padded rows in se1_wt / cond_wt, ub_cond_kernel's copy of the walk)
+        sd12 = synth.synth_state_dict(synth.unet_spec(dsed=12), 12)
+        os.environ["DGDM_UNET_BATCHED_MIN"] = "0"
+        per_sample12 = engine.Unet1d(sd12, step_embed_dim=12)
+        os.environ["DGDM_UNET_BATCHED_MIN"] = "1"
+        batched12 = engine.Unet1d(sd12, step_embed_dim=12)
     finally:
         if env is None:
             os.environ.pop("DGDM_UNET_BATCHED_MIN", None)
         else:
             os.environ["DGDM_UNET_BATCHED_MIN"] = env
     g = torch.Generator().manual_seed(5)
-    for L in (42, 14):
-        for B in (1024, 37, 5, 4, 3, 1, 130):
+    # L = 2, 4, 16, 32, 34: where a sample's boundary falls inside the 16-row position tiles moves with L (one-position second level, exactly
+    # full tiles, a tile and two rows)
+    for L in (2, 4, 16, 32, 34, 42, 14):
+        assert batched.effective_form(37, L) == ("f32_f16x3", True) and per_sample.effective_form(37, L) == ("f32_f16x3", False)
+        for B in ((1024, 37, 5, 4, 3, 1, 130) if L in (42, 14) else (37, 5, 4, 3, 1)):
             x = torch.randn((B, L, 1), generator=g).to(dev)
             x[B // 2] *= 1e-3                                   # samples of very different magnitude in one workgroup (the scale is per sample)
             t = torch.randint(0, 15, (B,), generator=g).to(dev)
@@ -526,6 +536,16 @@ def test_unet_batched_equals_per_sample(dev):
             assert torch.equal(a, b), (L, B, float((a - b).abs().max()))
     ref = orc.unet1d_forward(sd, x.cpu(), t.cpu())
     assert util.rel_l2(b.cpu(), ref) < REL
+    for L in (34, 14):
+        assert batched12.effective_form(37, L) == ("f32_f16x3", True) and per_sample12.effective_form(37, L) == ("f32_f16x3", False)
+        for B in (37, 5, 4, 3, 1):
+            x = torch.randn((B, L, 1), generator=g).to(dev)
+            x[B // 2] *= 1e-3
+            t = torch.randint(0, 1000, (B,), generator=g).to(dev)
+            a, b = per_sample12.forward(x, t), batched12.forward(x, t)
+            assert bool(torch.isfinite(b).all())
+            assert torch.equal(a, b), ("dsed 12", L, B, float((a - b).abs().max()))
+    assert util.rel_l2(b.cpu(), orc.unet1d_forward(sd12, x.cpu(), t.cpu())) < REL
     # what runs is reported, not assumed (advisor, round 4): the split form falls back to the float32 chain where its slabs do not fit
     assert batched.effective_form(1024, 42) == ("f32_f16x3", True) and per_sample.effective_form(1024, 42) == ("f32_f16x3", False)
     assert batched.effective_form(4, 46) == ("f32_mfma", False)

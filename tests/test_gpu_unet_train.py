@@ -71,15 +71,12 @@ def test_unet_trainer_golden(tag):
     print(f"{tag}: parameters after 3 steps within {worst:.2e} of the reference's ({flips} sign-of-rounding entries)")
 
 
-@pytest.mark.parametrize("B,L", [(3, 14), (130, 14), (129, 42)])
-def test_unet_trainer_vs_oracle(B, L):
-    """Ragged batch sizes (one sample tile and a half, odd counts): loss, noise prediction and EVERY gradient tensor against the oracle's
-    autograd on the same draws; then one Adam + EMA step."""
+def _trainer_vs_oracle(B, L, dsed=32):
     from dgdm_amd import engine, synth
     from oracle import dgdm_oracle as orc
-    sd = synth.synth_state_dict(synth.unet_spec(), 5)
+    sd = synth.synth_state_dict(synth.unet_spec(dsed=dsed), 5)
     o = orc.UnetTrainer(sd, 15, L, 1e-4, ema_power=0.85)
-    tr = engine.UnetTrainer(sd, L)
+    tr = engine.UnetTrainer(sd, L, step_embed_dim=dsed)
     rs = np.random.RandomState(B * 100 + L)
     x0 = torch.from_numpy(rs.uniform(-1, 1, (B, L, 1)).astype(np.float32))
     torch.manual_seed(B + L)
@@ -95,7 +92,7 @@ def test_unet_trainer_vs_oracle(B, L):
         worst = max(_rel(gh[k], o.grads[k]) for k in gh)
         assert worst < 2e-4, sorted(((_rel(gh[k], o.grads[k]), k) for k in gh), reverse=True)[:5]
         tr.ema_step(o.ema.decay)       # the oracle stepped its EMA with this decay inside step()
-        print(f"B={B} L={L} step {step}: loss {lh:.6f} (oracle {lo:.6f}), worst gradient tensor rel L2 {worst:.2e}")
+        print(f"B={B} L={L} dsed={dsed} step {step}: loss {lh:.6f} (oracle {lo:.6f}), worst gradient tensor rel L2 {worst:.2e}")
     ph, eh = tr.export(0), tr.export(4)
     for k in ph:
         assert float((ph[k] - o.sd[k]).abs().max()) < 2.5e-4, k        # <= 2 lr (+ rounding) wherever a sign is decided by rounding
@@ -103,6 +100,36 @@ def test_unet_trainer_vs_oracle(B, L):
     frac = sum(int(((ph[k] - o.sd[k]).abs() > 4e-6).sum()) for k in ph) / sum(v.numel() for v in ph.values())
     assert frac < 1e-4, frac
     assert tr.steps() == 2
+
+
+@pytest.mark.parametrize("B,L", [(3, 14), (130, 14), (129, 42)])
+def test_unet_trainer_vs_oracle(B, L):
+    """Ragged batch sizes (one sample tile and a half, odd counts): loss, noise prediction and EVERY gradient tensor against the oracle's
+    autograd on the same draws; then one Adam + EMA step."""
+    _trainer_vs_oracle(B, L)
+
+
+@pytest.mark.parametrize("B,L,dsed", [(3, 2, 32), (5, 16, 32), (3, 64, 32), (2, 130, 32), (3, 14, 4), (3, 14, 12)])
+def test_unet_trainer_vs_oracle_shapes(B, L, dsed):
+    """The same assertions and tolerances over the trainer's accepted domain (include/dgdm_hip.h): the row layout - four / two padding rows
+    around every sample, level-1 rows 2r + j paired with level-2 row r - at the one-position second level (L = 2), at exactly full 16-row
+    tiles (16), at the sampling path's longest finger (64) and beyond it (130: rows per sample 138 / 69, more than one 128-row GEMM tile per
+    sample); step embeddings narrower than the GEMM's K chunk of 16 (dsed = 4, 12: the row windows of t_emb / t_mg run into the next rows
+    and meet the images' zero rows)."""
+    _trainer_vs_oracle(B, L, dsed)
+
+
+def test_unet_trainer_rejections():
+    """Outside the accepted domain: EINVAL from dgdm_unet_trainer_create, nothing built."""
+    from dgdm_amd import _lib, engine, synth
+    sd = synth.synth_state_dict(synth.unet_spec(), 5)
+    for kw in (dict(num_points=3), dict(num_points=514), dict(num_points=0), dict(num_points=14, step_embed_dim=6), dict(num_points=14, step_embed_dim=68),
+               dict(num_points=14, down_dims=(128, 128)), dict(num_points=14, n_groups=4)):
+        w = sd
+        if "step_embed_dim" in kw or "down_dims" in kw:
+            w = synth.synth_state_dict(synth.unet_spec(down_dims=kw.get("down_dims", (128, 256)), dsed=kw.get("step_embed_dim", 32)), 5)
+        with pytest.raises(_lib.DgdmError, match="error -1"):
+            engine.UnetTrainer(w, **kw)
 
 
 def test_unet_trainer_deterministic_and_resume():
