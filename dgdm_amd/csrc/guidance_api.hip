@@ -41,6 +41,11 @@ struct ObjectTables {       // 3-D, per object
     int    ncr = 0;         // number of crowded centres (read back by set_objects)
     DevBuf Z16, M0_16;      // bf16 operand-order copies, built when the handle is in bf16 mode at set_objects time
     bool   has16 = false;
+    // [N][512] float, [N] int: layer 1's object part of the f16x3 trunk for the rows M0[q] - the scaled accumulators and the row's scale
+    // exponent (trunk.h TrunkParams::l1z / l1k).  Written by set_objects' float32 build for an object without crowded centres (the
+    // kernel looks at the device-side count); has_l1: the last build launched it, so the table is current whenever ncr == 0
+    DevBuf L1Z, L1K;
+    bool   has_l1 = false;
 };
 
 // A pose table of the trunk's first layer and the rows it spans: the cond_fn grid (G * P * P cells) or the orientation sweep (G cells)
@@ -94,6 +99,13 @@ struct DgdmGuidance {
     DevBuf labelx, labelcounts, labelsums, labelfinal, labelfirst, labelleft, labelobj;
     int rolltiles_chains = 0;                // chains the tiles of the last roll-out cover (dgdm_guidance_debug_rollout_table)
     DevBuf xidx, xidxchains, xtabptrs;       // embedding-table path: row index per reference row, per-chain lookup info, per-chain table base pointers
+    // layer-1 tables of the f16x3 gradient trunk (ObjectTables::L1Z / L1K).  l1ptrs: beside xtabptrs, [2][max_chains] pointers - a chain's
+    // L1Z and L1K where its table is its object's float32 M0 and the object has them, else null - and behind them the chain list
+    // [max_chains] ints, those chains first (trunk.h TrunkParams::chainlist); l1objs: set_objects' per-object pointer arrays.
+    // l1tab = DGDM_L1TAB, read at create: 0 builds no table, every chain takes the trunk's general front (same-binary reference, A/B)
+    DevBuf l1ptrs, l1objs;
+    bool l1tab = true;
+    int fill_l1ptrs(const std::vector<const ObjectTables *> &of_chain, int *n_tabled, hipStream_t s);
     bool xtab_enabled = true;       // test hook: modes 1-3 read materialised rows (per-step gather kernels) instead of the embedding table
     int xtab_policy = 0;            // 0: build the embedding tables once the objects have served more than XTAB_AFTER cond_fn calls; 1: at set_objects (test hook mode 5)
     int grads_since_set = 0;
@@ -169,16 +181,18 @@ struct DgdmGuidance {
                       int64_t call_stride = 0);
     int ensure_rows(int n_chains, int64_t rows_per_chain);      // grows the per-row device buffers and the pinned staging area
     // the rows' indices into the embedding tables (every chain's object has its table in the wanted format): no per-step gather runs at all
-    int use_xtab(const int *objidx_host, int n_chains, int64_t rows, bool want16, hipStream_t s);
+    int use_xtab(const int *objidx_host, int n_chains, int64_t rows, bool want16, int *l1, hipStream_t s);
     int build_object(int oi, int slot, hipStream_t s);
     int build_xtab(int oi, hipStream_t s);
     // via_tab: the group kernel gathered only the chains that need it (see there) and the trunk reads every chain through xtabptrs / xidx
-    int run_xobj(const int *objidx_host, int n_chains, int64_t rows, bool want16, bool *used16, bool *via_tab, hipStream_t s);
+    // l1: the number of chains whose layer-1 tables went into l1ptrs
+    int run_xobj(const int *objidx_host, int n_chains, int64_t rows, bool want16, bool *used16, bool *via_tab, int *l1, hipStream_t s);
     // the embeddings of `n_calls` classifier calls at once (3-D): afterwards call k reads rows [k * rows_per_call, (k + 1) * rows_per_call)
     // of every chain.  tab: index rows into per-chain tables (the objects' embedding tables, or run_xobj's mix of M0 and gathered rows), else
     // materialised rows; used16: bf16 rows
     struct Embedded {
         bool tab = false, used16 = false;
+        int l1 = 0;           // tab, float32: the chains whose layer-1 tables l1ptrs holds (the tabled front of the f16x3 gradient trunk)
         int64_t rows_per_chain = 0;
         void point(dgdm::TrunkParams *p, const DgdmGuidance &g, int call, int64_t rows_per_call) const;
     };
@@ -239,6 +253,7 @@ extern "C" int dgdm_guidance_create(DgdmGuidance **out, DgdmDynamics *model, con
     g->m = model; g->cfg = *cfg;
     g->B = cfg->batch;
     if (const char *e = getenv("DGDM_SERIAL_STEP")) g->serial = atoi(e);      // test hook: the serial step schedule
+    if (const char *e = getenv("DGDM_L1TAB")) g->l1tab = atoi(e) != 0;        // test hook: 0 = no layer-1 tables, the trunk's general front everywhere
     const int G = cfg->grid_size, P = cfg->num_pos, C = G * P * P;
     // pose grid: torch.meshgrid(linspace(ori), linspace(-1,1,P), linspace(-1,1,P)) 'ij' -> cell = (g*P + px)*P + py  (diffusion.py:478)
     const std::vector<float> lo = linspace_f32(cfg->ori_lo, cfg->ori_hi, G), lp = linspace_f32(-1.f, 1.f, P);
@@ -281,7 +296,8 @@ extern "C" int dgdm_guidance_create(DgdmGuidance **out, DgdmDynamics *model, con
         g->todo_capacity = (int64_t)nc * R;
         g->pinned_bytes = ((size_t)nc * R * 3 + (size_t)nc * (cfg->num_object_points + 1)) * sizeof(int);
         if ((rc = g->groupoff.alloc((size_t)nc * (cfg->num_object_points + 1) * sizeof(int))) || (rc = g->xidx.alloc((size_t)nc * R * sizeof(int))) ||
-            (rc = g->xidxchains.alloc(sizeof(XidxChain) * nc)) || (rc = g->xtabptrs.alloc(sizeof(void *) * nc)))
+            (rc = g->xidxchains.alloc(sizeof(XidxChain) * nc)) || (rc = g->xtabptrs.alloc(sizeof(void *) * nc)) ||
+            (rc = g->l1ptrs.alloc(sizeof(void *) * 3 * nc)))
             return rc;
         DGDM_HIP_CHECK(hipHostMalloc(&g->pinned, g->pinned_bytes, hipHostMallocDefault));
         DGDM_HIP_CHECK(hipEventCreateWithFlags(&g->pinned_ev, hipEventDisableTiming));
@@ -466,6 +482,22 @@ extern "C" int dgdm_guidance_set_objects(DgdmGuidance *g, const float *objects_d
             (rc = g->pool_F1.alloc(no * N * 128 * 8)) || (rc = g->pool_U.alloc(no * N * 128 * 8)) ||
             (rc = g->pool_fps1t.alloc(no * N * 64 * sizeof(uint4))))
             return rc;
+        // the layer-1 tables of the f16x3 gradient trunk (built at the end, below): the float32 build's, for clouds the M0-only path serves.
+        // Their pointer arrays [M0 | L1Z | L1K][max_objects] go up in front of `pooled`, which every build stream waits for (the buffers
+        // never move - N and max_objects are the handle's - so a build still in flight reads the same values)
+        const bool l1 = g->l1tab && !g->bf16 && N >= 128;
+        const size_t l1mo = (size_t)std::max(1, g->cfg.max_objects);
+        if (l1) {
+            std::vector<const void *> ptrs(3 * l1mo, nullptr);
+            for (int i = 0; i < (int)g->tables.size(); ++i) {
+                ObjectTables &t = *g->tables[i];
+                if ((rc = t.M0.alloc((size_t)N * 256 * 4)) || (rc = t.L1Z.alloc((size_t)N * 512 * 4)) || (rc = t.L1K.alloc((size_t)N * sizeof(int)))) return rc;
+                ptrs[i] = t.M0.p; ptrs[l1mo + i] = t.L1Z.p; ptrs[2 * l1mo + i] = t.L1K.p;
+            }
+            if ((rc = g->l1objs.alloc(sizeof(void *) * ptrs.size()))) return rc;
+            DGDM_HIP_CHECK(hipMemcpyAsync(g->l1objs.p, ptrs.data(), sizeof(void *) * ptrs.size(), hipMemcpyHostToDevice, s));      // pageable: staged before return
+        }
+        for (int i = 0; i < n_objects; ++i) g->tables[i]->has_l1 = l1;
         if (!g->pooled) DGDM_HIP_CHECK(hipEventCreateWithFlags(&g->pooled, hipEventDisableTiming));
         DGDM_HIP_CHECK(hipMemcpyAsync(g->pool_xyz.p, objects_dev, no * N * 3 * 4, hipMemcpyDeviceToDevice, s));
         DGDM_HIP_CHECK(hipEventRecord(g->pooled, s));
@@ -525,6 +557,13 @@ extern "C" int dgdm_guidance_set_objects(DgdmGuidance *g, const float *objects_d
         for (int i = off ? 1 : 0; i < nb; ++i) {
             DGDM_HIP_CHECK(hipEventRecord(g->bev[i], g->bstream[i]));
             DGDM_HIP_CHECK(hipStreamWaitEvent(es, g->bev[i], 0));
+        }
+        // every object's M0 and crowded count exist: the layer-1 tables of the uncrowded ones, all objects in one launch (in front of ro_ev:
+        // join_tables covers it)
+        if (l1) {
+            void *const *po = g->l1objs.as<void *>();
+            if ((rc = trunk_f16l_l1_tables(reinterpret_cast<const float *const *>(po), g->pool_ncr.as<int>(), reinterpret_cast<float *const *>(po + l1mo),
+                                           reinterpret_cast<int *const *>(po + 2 * l1mo), N, n_objects, g->m->fwdh(), es))) return rc;
         }
         // which objects may use the table of FPS(128) sequences (no order-dependent selection anywhere); crowded-centre counts:
         // copied to pinned memory behind an event, read by finish_objects() when first needed
@@ -676,22 +715,47 @@ int DgdmGuidance::upload_starts(const int64_t *starts_host, int n_chains, int64_
     return DGDM_OK;
 }
 
-int DgdmGuidance::use_xtab(const int *objidx_host, int n_chains, int64_t rows, bool want16, hipStream_t s) {
+// The layer-1 tables of the chains in of_chain (null: the chain does not read its object's float32 M0) and the chain list -> l1ptrs;
+// *n_tabled: how many chains have a table (0: nothing was uploaded)
+int DgdmGuidance::fill_l1ptrs(const std::vector<const ObjectTables *> &of_chain, int *n_tabled, hipStream_t s) {
+    const int nc = cfg.max_chains;
+    std::vector<const void *> ptrs(3 * (size_t)nc, nullptr);                       // [L1Z | L1K][nc] pointers, then the chain list [nc] ints
+    int *list = reinterpret_cast<int *>(ptrs.data() + 2 * (size_t)nc);
+    std::vector<int> rest;
+    int nt = 0;
+    for (size_t i = 0; i < of_chain.size(); ++i) {
+        const ObjectTables *t = of_chain[i];
+        if (!t || !l1tab || !t->has_l1 || t->ncr != 0) { rest.push_back((int)i); continue; }
+        ptrs[i] = t->L1Z.p; ptrs[nc + i] = t->L1K.p;
+        list[nt++] = (int)i;
+    }
+    std::copy(rest.begin(), rest.end(), list + nt);
+    *n_tabled = nt;
+    if (nt) DGDM_HIP_CHECK(hipMemcpyAsync(l1ptrs.p, ptrs.data(), sizeof(void *) * ptrs.size(), hipMemcpyHostToDevice, s));      // pageable: staged before return
+    return DGDM_OK;
+}
+
+int DgdmGuidance::use_xtab(const int *objidx_host, int n_chains, int64_t rows, bool want16, int *l1, hipStream_t s) {
     std::vector<XidxChain> xc(n_chains);
     std::vector<const void *> base(n_chains);
+    std::vector<const ObjectTables *> m0_of(n_chains, nullptr);      // chains that read their object's float32 M0
     for (int i = 0; i < n_chains; ++i) {
         const ObjectTables &t = *tables[objidx_host[i]];
         xc[i].fps1 = t.fps1; xc[i].N = cfg.num_object_points; xc[i].m0_only = t.ncr == 0;
         // an object without crowded centres has X[s1][q] = M0[q]: its table is M0 itself (xtab_kernel wrote nothing)
         base[i] = want16 ? (t.ncr == 0 ? (const void *)t.M0_16.p : (const void *)t.X16.p) : (t.ncr == 0 ? (const void *)t.M0.p : (const void *)t.X.p);
+        if (!want16 && t.ncr == 0) m0_of[i] = &t;
     }
+    int rc;
+    if ((rc = fill_l1ptrs(m0_of, l1, s))) return rc;
     DGDM_HIP_CHECK(hipMemcpyAsync(xidxchains.p, xc.data(), sizeof(XidxChain) * n_chains, hipMemcpyHostToDevice, s));      // pageable: staged before return
     DGDM_HIP_CHECK(hipMemcpyAsync(xtabptrs.p, base.data(), sizeof(void *) * n_chains, hipMemcpyHostToDevice, s));
     return pn_xidx(xidxchains.as<XidxChain>(), starts.as<int>(), rows, n_chains, xidx.as<int>(), s);
 }
 
-int DgdmGuidance::run_xobj(const int *objidx_host, int n_chains, int64_t rows, bool want16, bool *used16, bool *via_tab, hipStream_t s) {
+int DgdmGuidance::run_xobj(const int *objidx_host, int n_chains, int64_t rows, bool want16, bool *used16, bool *via_tab, int *l1, hipStream_t s) {
     *via_tab = false;
+    *l1 = 0;
     std::vector<XobjChain> ch(n_chains);
     for (int i = 0; i < n_chains; ++i) {
         const ObjectTables &t = *tables[objidx_host[i]];
@@ -732,10 +796,12 @@ int DgdmGuidance::run_xobj(const int *objidx_host, int n_chains, int64_t rows, b
         std::vector<int> rank;
         std::vector<XidxChain> xc(n_chains);
         std::vector<const void *> base(n_chains);
+        std::vector<const ObjectTables *> m0_of(n_chains, nullptr);      // chains that read their object's float32 M0
         for (int i = 0; i < n_chains; ++i) {
             const ObjectTables &t = *tables[objidx_host[i]];
             const bool m0_only = by_index && t.ncr == 0 && t.fast_ok;
             if (!m0_only) rank.push_back(i);
+            if (m0_only && !want16) m0_of[i] = &t;
             xc[i].fps1 = m0_only ? t.fps1 : nullptr; xc[i].N = cfg.num_object_points; xc[i].m0_only = 1;
             base[i] = m0_only ? (want16 ? (const void *)t.M0_16.p : (const void *)t.M0.p)
                               : (want16 ? (const void *)(xobj16.as<uint32_t>() + (size_t)i * rows * 128) : (const void *)(xobj.as<float>() + (size_t)i * rows * 256));
@@ -749,6 +815,7 @@ int DgdmGuidance::run_xobj(const int *objidx_host, int n_chains, int64_t rows, b
         *via_tab = true;
         DGDM_HIP_CHECK(hipMemcpyAsync(xidxchains.p, xc.data(), sizeof(XidxChain) * n_chains, hipMemcpyHostToDevice, s));      // pageable: staged before return
         DGDM_HIP_CHECK(hipMemcpyAsync(xtabptrs.p, base.data(), sizeof(void *) * n_chains, hipMemcpyHostToDevice, s));
+        if ((rc = fill_l1ptrs(m0_of, l1, s))) return rc;
         return pn_xidx(xidxchains.as<XidxChain>(), starts.as<int>(), rows, n_chains, xidx.as<int>(), s);
     }
     return pn_xobj(xp, all_fast, s);
@@ -769,7 +836,7 @@ int DgdmGuidance::embed_rows(const int *oidx, int n_chains, const int64_t *start
     if ((rc = upload_starts(starts_host, n_chains, rows_per_call, s, !tab, n_calls, call_stride))) return rc;     // host work: overlaps a table build still in flight
     if ((rc = finish_objects())) return rc;
     e->tab = tab; e->used16 = want16; e->rows_per_chain = rt;
-    if ((rc = tab ? use_xtab(oidx, n_chains, rt, want16, s) : run_xobj(oidx, n_chains, rt, want16, &e->used16, &e->tab, s))) return rc;
+    if ((rc = tab ? use_xtab(oidx, n_chains, rt, want16, &e->l1, s) : run_xobj(oidx, n_chains, rt, want16, &e->used16, &e->tab, &e->l1, s))) return rc;
     DGDM_HIP_CHECK(hipEventRecord(up_consumed, s));          // the index buffers may be overwritten once these kernels are through
     consumed_recorded = true;
     return DGDM_OK;
@@ -783,6 +850,12 @@ void DgdmGuidance::Embedded::point(TrunkParams *p, const DgdmGuidance &g, int ca
         p->xidx = g.xidx.as<int>() + row0;
         if (used16) p->xtab16 = g.xtabptrs.as<const uint32_t *>();
         else p->xtab = g.xtabptrs.as<const float *>();
+        if (l1 && !used16) {                     // read by the f16x3 gradient trunk alone
+            p->l1z = g.l1ptrs.as<const float *>();
+            p->l1k = g.l1ptrs.as<const int *>() + g.cfg.max_chains;
+            p->chainlist = reinterpret_cast<const int *>(g.l1ptrs.as<const void *>() + 2 * (size_t)g.cfg.max_chains);
+            p->n_tabled = l1;
+        }
     } else {
         p->xobj = g.xobj.as<float>() + row0 * 256;
         p->xobj16 = used16 ? g.xobj16.as<uint32_t>() + row0 * 128 : nullptr;

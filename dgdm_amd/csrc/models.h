@@ -55,8 +55,9 @@ struct DgdmDynamics {
     dgdm::DevBuf ws2;
     dgdm::DevBuf w16;       // bf16 weight streams of the trunk (trunk_bf16.hip): forward then backward
     size_t fwd16_bytes = 0, bwd16_bytes = 0, sa3_16_offset = 0;     // sa3 bf16 image (z16_kernel) follows the two trunk streams
-    dgdm::DevBuf wf16;      // two-way f16 split streams of the trunk (trunk_f16l.hip): forward then backward
-    size_t fwdh_bytes = 0, bwdh_bytes = 0;
+    dgdm::DevBuf wf16;      // two-way f16 split streams of the trunk (trunk_f16l.hip): forward, backward, 3-D: forward without layer 1
+    size_t fwdh_bytes = 0, bwdh_bytes = 0, fwdh_nl1_bytes = 0;
+    const float4 *fwdh() const { return reinterpret_cast<const float4 *>(wf16.p); }      // the full forward f16 stream
     dgdm::TrunkF16Scales f16_scales{};
     dgdm::DevBuf z1_unit;   // [W1] floats 2^e: the library carries unit j of the first trunk layer as (true value) x 2^e_j (models_api.hip TrunkEquil)
 

@@ -675,7 +675,22 @@ extern "C" int dgdm_dynamics_create(DgdmDynamics **out, int kind, const DgdmTens
                 for (int ks = 0; ks < 16; ++ks) st.emit(bs, kb, ks / 2, ks % 2);
         }
         m->fwdh_bytes = fs.size() * 2; m->bwdh_bytes = bs.size() * 2;
+        // 3-D: the forward stream once more without the layer-1 entries (the tabled front of trunk_f16l.hip takes layer 1 from a table):
+        // the same chunks in the same order - per layer-1 block the two chunks of layer 2, then the stack
+        std::vector<uint16_t> fn;
+        if (kind == 3) {
+            const size_t CHK = 16 * 512;                      // f16 values per chunk of 16 entries
+            for (int kb = 0; kb < 16; ++kb) fn.insert(fn.end(), fs.begin() + (size_t)(4 * kb + 2) * CHK, fs.begin() + (size_t)(4 * kb + 4) * CHK);
+            fn.insert(fn.end(), fs.begin() + 64 * CHK, fs.end());
+            DGDM_REQUIRE(fn.size() % CHK == 0 && fn.size() + 32 * CHK == fs.size(), DGDM_EINVAL, "f16 split: the stream without layer 1 has the wrong length");
+            for (size_t c = 0; c < fn.size() / CHK; ++c) {
+                const size_t full = c < 32 ? 4 * (c / 2) + 2 + (c & 1) : c + 32;
+                DGDM_REQUIRE(!memcmp(&fn[c * CHK], &fs[full * CHK], CHK * 2), DGDM_EINVAL, "f16 split: chunk %zu of the stream without layer 1 differs from the full stream's", c);
+            }
+        }
+        m->fwdh_nl1_bytes = fn.size() * 2;
         fs.insert(fs.end(), bs.begin(), bs.end());
+        fs.insert(fs.end(), fn.begin(), fn.end());
         if ((rc = m->wf16.upload(fs.data(), fs.size() * 2))) return rc;
     }
     std::vector<float> bwd;
@@ -751,6 +766,8 @@ void DgdmDynamics::fill_trunk_bf16(TrunkParams *p) const {     // after fill_tru
 void DgdmDynamics::fill_trunk_f16(TrunkParams *p, TrunkF16Scales *sc) const {     // after fill_trunk: swaps the two weight streams only
     p->Wfwd = reinterpret_cast<const float4 *>(static_cast<const char *>(wf16.p)); p->fwd_bytes = (unsigned)fwdh_bytes;
     p->Wbwd = reinterpret_cast<const float4 *>(static_cast<const char *>(wf16.p) + fwdh_bytes); p->bwd_bytes = (unsigned)bwdh_bytes;
+    p->Wfwd_nl1 = fwdh_nl1_bytes ? reinterpret_cast<const float4 *>(static_cast<const char *>(wf16.p) + fwdh_bytes + bwdh_bytes) : nullptr;
+    p->fwd_nl1_bytes = (unsigned)fwdh_nl1_bytes;
     *sc = f16_scales;
 }
 

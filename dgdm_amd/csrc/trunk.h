@@ -31,6 +31,19 @@ struct TrunkParams {
     const uint32_t *const *xtab16;
     const int    *xidx;
     int64_t       xstride;    // rows per chain in xobj / xobj16 / xidx (>= R: a launch may read one denoise step's rows out of buffers that hold all steps')
+    // layer 1's object part from a table (trunk_f16l.hip, the gradient kernel only; table mode): l1z[c] / l1k[c] = the tables of chain c's
+    // object - [N][512] scaled layer-1 accumulators and [N] row scale exponents of the rows M0[q], indexed by xidx like xtab[c] - or null
+    // for a chain without one.  l1z null: no chain has one.  Wfwd_nl1: the forward f16 stream without its layer-1 entries.
+    // chainlist (device): the launch's chains, the n_tabled ones with a table first - trunk_f16l_launch runs the tabled instantiation
+    // over those and the general one over the rest.  chains: what a kernel reads - the list its tiles run along (tile t belongs to
+    // chains[t / (B * tiles_per_b)]), null: all chains in order; set by the launcher
+    const float *const *l1z;
+    const int   *const *l1k;
+    const float4 *Wfwd_nl1;
+    unsigned      fwd_nl1_bytes;
+    const int    *chainlist;
+    int           n_tabled;
+    const int    *chains;
     // first-layer tables
     const float  *Atab;       // table mode: [nchain*B][W1]; rows mode: [rows][W1]
     const float  *Ptab;       // [C][W1]  (table mode)
@@ -74,6 +87,11 @@ struct TrunkF16Scales {
 // [ntiles][32], padding rows included; p.Ptab is not read.
 enum class TrunkF16Mode { Grad, Forward, ForwardRowPose };
 int trunk_f16l_launch(int kind, TrunkF16Mode mode, const TrunkParams &p, const TrunkF16Scales &sc, hipStream_t s);
+// The layer-1 tables (TrunkParams::l1z / l1k) of n_objects 3-D objects in one launch: object i's rows are m0[i] [N][256]; an object whose
+// ncr[i] (device: its crowded-centre count) is not zero is skipped.  Wfwd: the full forward f16 stream.  The same code on the same
+// operands as the trunk's front: entry [q] holds the bits a tile row with the embedding M0[q] gets there.
+int trunk_f16l_l1_tables(const float *const *m0, const int *ncr, float *const *l1z, int *const *l1k, int N, int n_objects, const float4 *Wfwd,
+                         hipStream_t s);
 
 // Roll-out steps around that trunk (rollout.hip).  State [n_chains][B * G][3] doubles = (ori, pos_x, pos_y) in the model's normalised
 // units, row r = g * B + b.

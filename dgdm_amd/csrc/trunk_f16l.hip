@@ -30,7 +30,8 @@
 // accumulator pair into its two pieces - is done just in time, one register pair per group of six MFMAs, in the shadow of the matrix
 // pipe.  The 512-wide first layers of the 3-D model and the last layer back are produced block by block (block_out).
 // Stream entries per (K-step, output-block pair): [A.h A.l B.h B.l], per block-out K-step: [h l] (host: Split2 / f16_layer_stream,
-// models_api.hip).
+// models_api.hip).  3-D gradient launches: chains whose rows are rows of their object's M0 take layer 1's object part from a table built
+// with this file's own block_out (l1_table_kernel) and run the TABLED instantiation on a stream without layer 1.
 //
 // The weight stream is SHARED by the workgroup's four waves through LDS.  Pulled through the CU's L1 once per wave (the ring form of
 // round 4's first version, 683 bytes per MFMA) it arrived at ~50 of the 85 B/clk/CU the MFMAs ask for: a 256 -> 256 layer took 22 k
@@ -156,6 +157,16 @@ struct LStream {
     __device__ __forceinline__ v4f32 read(const int e) const { return buf[(slot * CH + e) * 64 + lane]; }
 };
 
+// The layer-1 entries of the 3-D forward stream read straight from global memory, with LStream's read / advance: what the table
+// builder (l1_table_kernel) hands to block_out.  Per layer-1 block the full image holds two chunks of layer 1 and two of layer 2:
+// advance() steps over the latter.
+struct GStream {
+    const v4f32 *img;
+    int lane, cur;
+    __device__ __forceinline__ void advance() { ++cur; if ((cur & 1) == 0) cur += 2; }
+    __device__ __forceinline__ v4f32 read(const int e) const { return img[((size_t)cur * CH + e) * 64 + lane]; }
+};
+
 // the three terms of one K-step for two accumulators (w: [A.h A.l B.h B.l]); small terms first
 #define F16_STEP(accA, accB, w, xh, xl)      \
     do {                                     \
@@ -257,8 +268,8 @@ __device__ __forceinline__ void stream_layer(LStream &ls, v4f32 (&wn)[4], const 
 // (32 entries = two chunks).  Three MFMAs per K-step are 96 cycles - less than an LDS round trip under load - so the operands are read TWO
 // K-steps ahead: on entry wn[0..1] / wn[2..3] hold K-steps 0 / 1 of this pass (= its entries 0 .. 3, the same precondition as a stack
 // layer's), on return entries 0 .. 3 of the pass that follows.
-template <class Side>
-__device__ __forceinline__ f32x16 block_out(LStream &ls, v4f32 (&wn)[4], const Act2 &X, f32x16 za, f32x16 zb, Side &&side) {
+template <class Stream, class Side>
+__device__ __forceinline__ f32x16 block_out(Stream &ls, v4f32 (&wn)[4], const Act2 &X, f32x16 za, f32x16 zb, Side &&side) {
 #pragma unroll
     for (int ks = 0; ks < 16; ++ks) {
         const int s = (ks & 1) * 2;
@@ -326,9 +337,14 @@ using namespace f16l;
 // writer left in this instantiation and is not allocated), no backward stream, no objective, no partial sums.
 // ROWPOSE (only with FWD_ONLY: dgdm_guidance_rollout): every row has a pose of its own - p.PtabT holds one operand tile per trunk tile
 // (chain, finger, 32 cells) and p.Pmax one value per tile row, [ntiles][32], instead of one per cell shared by all chains and fingers.
-template <int KIND, bool FWD_ONLY = false, bool ROWPOSE = false>
+// TABLED (3-D gradient kernel only): layer 1's object part comes from the objects' tables (TrunkParams::l1z / l1k) and the stream is the
+// one without layer 1.  An instantiation of its own, launched over the chains that have a table (p.chains), beside the general one over
+// the others: as a second front inside one kernel it cost the general front its registers (136 VGPRs spilled).
+template <int KIND, bool FWD_ONLY = false, bool ROWPOSE = false, bool TABLED = false>
 __global__ __launch_bounds__(256, 1) void trunk_f16l_kernel(const TrunkParams p, const TrunkF16Scales sc) {
     static_assert(FWD_ONLY || !ROWPOSE, "per-row poses: forward-only kernel");
+    static_assert(!TABLED || (KIND == 3 && !FWD_ONLY), "layer-1 tables: the 3-D gradient kernel");
+    constexpr bool tabled = TABLED;
     constexpr int W1B = (KIND == 3) ? 16 : 8;
     constexpr int W1 = W1B * 32;
     constexpr int NSLOT = (KIND == 3) ? 8 + 7 * 4 : 8 * 4;
@@ -348,8 +364,13 @@ __global__ __launch_bounds__(256, 1) void trunk_f16l_kernel(const TrunkParams p,
     const int voff = lane * 16;
 
     const int per_chain = p.B * p.tiles_per_b;
-    const int chain = tile / per_chain;
-    const int rem = tile - chain * per_chain;
+    // (3-D gradient kernel: a launch may run over a list of chains - its tiles are numbered along the list, its chains keep their numbers)
+    const int cpos = tile / per_chain;
+    const int rem = tile - cpos * per_chain;
+    int chain = cpos, otile = tile;                           // otile: the tile's number among all chains' (where its partial sums go)
+    if constexpr (KIND == 3 && !FWD_ONLY) {
+        if (p.chains) { chain = p.chains[cpos]; otile = chain * per_chain + rem; }
+    }
     const int b = rem / p.tiles_per_b;
     const int c = (rem - b * p.tiles_per_b) * 32 + n;
     const bool valid = c < p.C;
@@ -361,7 +382,7 @@ __global__ __launch_bounds__(256, 1) void trunk_f16l_kernel(const TrunkParams p,
     uint32_t m[4];
     int slot = 0;
     int E = 0;                                                // Y = true values x 2^E for this lane's row
-    const wrsrc_t rsF = weight_rsrc(p.Wfwd, p.fwd_bytes);
+    const wrsrc_t rsF = tabled ? weight_rsrc(p.Wfwd_nl1, p.fwd_nl1_bytes) : weight_rsrc(p.Wfwd, p.fwd_bytes);
     LStream ls;
     ls.buf = (lds_f4_t *)wbuf; ls.voff = voff; ls.wave = wave; ls.lane = lane;
     v4f32 wn[4];
@@ -377,7 +398,7 @@ __global__ __launch_bounds__(256, 1) void trunk_f16l_kernel(const TrunkParams p,
                 Y[o][4 * q + 0] = v.x + w.x; Y[o][4 * q + 1] = v.y + w.y; Y[o][4 * q + 2] = v.z + w.z; Y[o][4 * q + 3] = v.w + w.w;
             }
         }
-    } else {
+    } else if (!tabled) {                                     // (a tabled tile never reads its embedding row)
         const float *xrow = p.xtab ? p.xtab[chain] + (size_t)p.xidx[(size_t)chain * p.xstride + r] * 256 : p.xobj + ((size_t)chain * p.xstride + r) * 256;
 #pragma unroll
         for (int o = 0; o < 8; ++o) {
@@ -399,7 +420,19 @@ __global__ __launch_bounds__(256, 1) void trunk_f16l_kernel(const TrunkParams p,
 #pragma unroll
         for (int j = 0; j < 4; ++j) wn[j] = ls.read(j);
         Act2 X;
-        const int kx = split_rows(Y, X);
+        int kx;
+        // tabled: the row's 512 scaled layer-1 accumulators (what the 16 block_out passes return).  A global-memory pointer by type: loaded
+        // from the pointer array it is a generic one, whose loads (flat_load) also count as LDS traffic - every wait for a weight operand
+        // out of LDS would wait for them
+        typedef const __attribute__((address_space(1))) float *gfloat_p;
+        gfloat_p zrow = nullptr;
+        if (tabled) {
+            const int tq = p.xidx[(size_t)chain * p.xstride + r];
+            zrow = (gfloat_p)p.l1z[chain] + (size_t)tq * 512;
+            kx = p.l1k[chain][tq];
+        } else {
+            kx = split_rows(Y, X);
+        }
         const float un1 = pow2f(-(kx + sc.ew_l1));            // layer-1 accumulators -> true values
         // The f16 scale of layer 2's input rows, from a bound on layer 1's output that is known now (the file header says why a bound
         // does): |z_j| <= max |A[finger]| + max |P[cell]| + ||W1o_j||_1 max |x|, and max |x| < 2^(13 - kx) by the choice of kx.
@@ -443,48 +476,126 @@ __global__ __launch_bounds__(256, 1) void trunk_f16l_kernel(const TrunkParams p,
                 tt[4 * q + 0] = tv[q].x + tw[q].x; tt[4 * q + 1] = tv[q].y + tw[q].y; tt[4 * q + 2] = tv[q].z + tw[q].z; tt[4 * q + 3] = tv[q].w + tw[q].w;
             }
         };
-        table_terms_request(0);
-        for (int blk = 0; blk < 16; blk += 2) {
-            uint32_t bits2 = 0;
+        // one register pair of a block of layer 1 -> sign bits, ReLU, layer 2's row scale, the two f16 pieces (both fronts: the same operations)
+        auto l1_pair = [&](const f32x16 &z, const int d, const int sh, uint32_t &bits, uint32_t &a, uint32_t &bb) __attribute__((always_inline)) {
+            float lo = z[2 * d], hi = z[2 * d + 1];
+            bits |= (lo > 0.f ? 1u : 0u) << sh;
+            bits |= (hi > 0.f ? 1u : 0u) << (sh + 1);
+            asm("v_max_f32 %0, 0, %1" : "=v"(lo) : "v"(lo));
+            asm("v_max_f32 %0, 0, %1" : "=v"(hi) : "v"(hi));
+            split2(lo * f2, hi * f2, a, bb);
+        };
+        if (!tabled) {
+            table_terms_request(0);
+            for (int blk = 0; blk < 16; blk += 2) {
+                uint32_t bits2 = 0;
 #pragma unroll
-            for (int e = 0; e < 2; ++e) {
-                const int kb = blk + e;
-                f32x16 z = block_out(ls, wn, X, zero, zero, [](int) __attribute__((always_inline)) {});      // leaves wn = entries 0 .. 3 of layer 2's pass
-                table_terms();
-                table_terms_request((kb + 1) & 15);
+                for (int e = 0; e < 2; ++e) {
+                    const int kb = blk + e;
+                    f32x16 z = block_out(ls, wn, X, zero, zero, [](int) __attribute__((always_inline)) {});      // leaves wn = entries 0 .. 3 of layer 2's pass
+                    table_terms();
+                    table_terms_request((kb + 1) & 15);
 #pragma unroll
-                for (int rr = 0; rr < 16; ++rr) z[rr] = fmaf(z[rr], un1, tt[rr]);       // the scaled sum back to true units (exact) + the table terms: one rounding
-                hu32x4_t ah[2], al[2];
+                    for (int rr = 0; rr < 16; ++rr) z[rr] = fmaf(z[rr], un1, tt[rr]);       // the scaled sum back to true units (exact) + the table terms: one rounding
+                    hu32x4_t ah[2], al[2];
 #pragma unroll
-                for (int d = 0; d < 8; ++d) {
-                    float lo = z[2 * d], hi = z[2 * d + 1];
-                    const int sh = 2 * d + 16 * e;
-                    bits2 |= (lo > 0.f ? 1u : 0u) << sh;
-                    bits2 |= (hi > 0.f ? 1u : 0u) << (sh + 1);
-                    asm("v_max_f32 %0, 0, %1" : "=v"(lo) : "v"(lo));
-                    asm("v_max_f32 %0, 0, %1" : "=v"(hi) : "v"(hi));
-                    uint32_t a, bb;
-                    split2(lo * f2, hi * f2, a, bb);
-                    ah[d / 4][d % 4] = a; al[d / 4][d % 4] = bb;
+                    for (int d = 0; d < 8; ++d) {
+                        uint32_t a, bb;
+                        l1_pair(z, d, 2 * d + 16 * e, bits2, a, bb);
+                        ah[d / 4][d % 4] = a; al[d / 4][d % 4] = bb;
+                    }
+                    // layer 2: 32 entries = two chunks, eight groups of [A.h A.l B.h B.l]; the group's operands are read one group ahead (wn holds
+                    // the first group on entry, the next pass' entries 0 .. 3 - layer 1's next block, or the stack's first group - on return)
+#pragma unroll
+                    for (int gq = 0; gq < 8; ++gq) {
+                        const int pp = gq / 2, sx = gq % 2;
+                        v4f32 w[4];
+#pragma unroll
+                        for (int j = 0; j < 4; ++j) w[j] = wn[j];
+                        if ((gq & (CG - 1)) == CG - 1) ls.advance();
+#pragma unroll
+                        for (int j = 0; j < 4; ++j) wn[j] = ls.read(((gq + 1) & (CG - 1)) * 4 + j);
+                        F16_STEP(Y[2 * pp], Y[2 * pp + 1], w, ah[sx], al[sx]);
+                        __builtin_amdgcn_sched_barrier(0);
+                    }
                 }
-                // layer 2: 32 entries = two chunks, eight groups of [A.h A.l B.h B.l]; the group's operands are read one group ahead (wn holds
-                // the first group on entry, the next pass' entries 0 .. 3 - layer 1's next block, or the stack's first group - on return)
-#pragma unroll
-                for (int gq = 0; gq < 8; ++gq) {
-                    const int pp = gq / 2, sx = gq % 2;
-                    v4f32 w[4];
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) w[j] = wn[j];
-                    if ((gq & (CG - 1)) == CG - 1) ls.advance();
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) wn[j] = ls.read(((gq + 1) & (CG - 1)) * 4 + j);
-                    F16_STEP(Y[2 * pp], Y[2 * pp + 1], w, ah[sx], al[sx]);
-                    __builtin_amdgcn_sched_barrier(0);
-                }
+                if (!FWD_ONLY) smask[blk / 2][tid] = bits2;
             }
-            if (!FWD_ONLY) smask[blk / 2][tid] = bits2;
+        } else if constexpr (!FWD_ONLY) {
+            // Tabled front: the stream holds layer 2 alone (eight groups per block, as above), and a block of layer 1 is 16 table values per
+            // lane + the table terms.  Software-pipelined, as a stack layer's items are: while block kb's groups run, group d takes register
+            // pair d of block kb + 1 through l1_pair (split2, not split2_mix: its pieces are read two groups later at the earliest).
+            // The loads run FOUR blocks ahead, in two register sets: in front of the advance() of group 3, block kb + 2's loads (requested
+            // two blocks ago) are added up into zc, then block kb + 4's are requested into the set just freed.  The wait the compiler puts
+            // in front of the adding is vmcnt(12) - the twelve loads of block kb + 3's request are younger - and vmcnt counts every load
+            // in order, the stream's included: the twelve youngest loads at that point are the stream's two chunks in flight and a third
+            // of that request, so the wait leaves the stream alone.  (One block ahead in one set it was vmcnt(0): the stream drained
+            // sixteen times per tile, and the front gained 5 % instead of what it gains now.)  Past block 15 the requests wrap around and
+            // the pairs are dropped.
+            struct Raw { float4 zv[4], tv[4], tw[4]; } R[2];
+            auto request = [&](Raw &w, const int kb) __attribute__((always_inline)) {
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                    const v4f32 v = *(const __attribute__((address_space(1))) v4f32 *)(zrow + 32 * kb + 8 * q + h4);
+                    w.zv[q] = make_float4(v.x, v.y, v.z, v.w);
+                    w.tv[q] = *reinterpret_cast<const float4 *>(arow + 32 * kb + 8 * q + h4);
+                    w.tw[q] = ptile[(kb * 4 + q) * 64];
+                }
+            };
+            auto take = [&](const Raw &w, f32x16 &z) __attribute__((always_inline)) {      // fmaf(z, un1, A + P): the general front's operations
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                    z[4 * q + 0] = fmaf(w.zv[q].x, un1, w.tv[q].x + w.tw[q].x); z[4 * q + 1] = fmaf(w.zv[q].y, un1, w.tv[q].y + w.tw[q].y);
+                    z[4 * q + 2] = fmaf(w.zv[q].z, un1, w.tv[q].z + w.tw[q].z); z[4 * q + 3] = fmaf(w.zv[q].w, un1, w.tv[q].w + w.tw[q].w);
+                }
+            };
+            f32x16 zc[2];                                     // [block parity]
+            hu32x4_t P[2][2][2];                              // [block parity][piece][K-step]
+            uint32_t bits_lo = 0;                             // the even block's half of a word of smask
+            request(R[0], 0);
+            request(R[1], 1);
+            take(R[0], zc[0]);
+            request(R[0], 2);
+#pragma unroll
+            for (int d = 0; d < 8; ++d) {
+                uint32_t a, bb;
+                l1_pair(zc[0], d, 2 * d, bits_lo, a, bb);
+                P[0][0][d / 4][d % 4] = a; P[0][1][d / 4][d % 4] = bb;
+            }
+            take(R[1], zc[1]);
+            request(R[1], 3);
+            // (unrolled: as a loop its back edge copied both register sets, in flight, into the next round's registers - behind a vmcnt(0))
+#pragma unroll
+            for (int blk = 0; blk < 16; blk += 2) {
+                uint32_t bits_hi = 0, bits_next = 0;
+#pragma unroll
+                for (int e = 0; e < 2; ++e) {
+                    const int kb = blk + e;
+#pragma unroll
+                    for (int gq = 0; gq < 8; ++gq) {
+                        const int pp = gq / 2, sx = gq % 2;
+                        v4f32 w[4];
+#pragma unroll
+                        for (int j = 0; j < 4; ++j) w[j] = wn[j];
+                        if (gq == 3) {
+                            take(R[e], zc[e]);                // block kb + 2 (block kb's own values were used up under block kb - 1)
+                            request(R[e], (kb + 4) & 15);
+                        }
+                        if ((gq & (CG - 1)) == CG - 1) ls.advance();
+#pragma unroll
+                        for (int j = 0; j < 4; ++j) wn[j] = ls.read(((gq + 1) & (CG - 1)) * 4 + j);
+                        uint32_t a, bb;                       // pair gq of block kb + 1
+                        l1_pair(zc[e ^ 1], gq, 2 * gq + 16 * (e ^ 1), e == 0 ? bits_hi : bits_next, a, bb);
+                        P[e ^ 1][0][gq / 4][gq % 4] = a; P[e ^ 1][1][gq / 4][gq % 4] = bb;
+                        F16_STEP(Y[2 * pp], Y[2 * pp + 1], w, P[e][0][sx], P[e][1][sx]);
+                        __builtin_amdgcn_sched_barrier(0);
+                    }
+                    if (e == 0) smask[blk / 2][tid] = bits_lo | bits_hi;
+                }
+                bits_lo = bits_next;
+            }
         }
-        slot = 8;                                             // wn: entries 0 .. 3 of the stack's first chunk already; E: layer 2's row scale
+        slot = 8;                                            // wn: entries 0 .. 3 of the stack's first chunk already; E: layer 2's row scale
     }
     if (KIND == 2) {
 #pragma unroll
@@ -578,7 +689,7 @@ __global__ __launch_bounds__(256, 1) void trunk_f16l_kernel(const TrunkParams p,
     for (int i = 0; i < 4; ++i) m[i] = smask[BASE + i][tid];
     apply_mask<8>(Y, m);
 
-    float *dst = p.partial + (size_t)tile * W1;
+    float *dst = p.partial + (size_t)otile * W1;
     if (KIND == 2) {
         const float un = pow2f(-E);                           // per row: back to true units before the 32 rows are folded
 #pragma unroll
@@ -623,11 +734,65 @@ __global__ __launch_bounds__(256, 1) void trunk_f16l_kernel(const TrunkParams p,
     }
 }
 
+// The layer-1 tables of the tabled front (TrunkParams::l1z / l1k): one wave = 32 rows q of one object's M0, through the trunk's own
+// split_rows and block_out on the layer-1 entries of the forward stream - the same pieces in the same K order on the same two
+// accumulators, and rows are independent columns of the MFMA with a scale of their own, so entry [q] is bit for bit what a tile row with
+// that embedding gets in the general front.  Operands straight from global memory (GStream): 16 waves per object, once per set_objects.
+__global__ __launch_bounds__(64) void l1_table_kernel(const float *const *m0, const int *ncr, float *const *l1z, int *const *l1k, const int N, const v4f32 *img) {
+    const int obj = blockIdx.y;
+    if (ncr[obj] != 0) return;                                // a crowded object's chains are gathered: they never read the table
+    const int lane = threadIdx.x, n = lane & 31, h4 = (lane >> 5) * 4;
+    const int row = blockIdx.x * 32 + n;
+    const bool valid = row < N;
+    const float *xrow = m0[obj] + (size_t)min(row, N - 1) * 256;
+    f32x16 Y[8];
+#pragma unroll
+    for (int o = 0; o < 8; ++o) {
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const float4 v = feat4(xrow, o, q, h4);
+            Y[o][4 * q + 0] = v.x; Y[o][4 * q + 1] = v.y; Y[o][4 * q + 2] = v.z; Y[o][4 * q + 3] = v.w;
+        }
+    }
+    Act2 X;
+    const int kx = split_rows(Y, X);
+    if (valid && lane < 32) l1k[obj][row] = kx;
+    GStream gs{img, lane, 0};
+    v4f32 wn[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) wn[j] = gs.read(j);
+    f32x16 zero;
+#pragma unroll
+    for (int rr = 0; rr < 16; ++rr) zero[rr] = 0.f;
+    float *dst = l1z[obj] + (size_t)min(row, N - 1) * 512;
+    for (int kb = 0; kb < 16; ++kb) {
+        const f32x16 z = block_out(gs, wn, X, zero, zero, [](int) __attribute__((always_inline)) {});
+        if (valid) {
+#pragma unroll
+            for (int q = 0; q < 4; ++q) *reinterpret_cast<float4 *>(dst + 32 * kb + 8 * q + h4) = make_float4(z[4 * q + 0], z[4 * q + 1], z[4 * q + 2], z[4 * q + 3]);
+        }
+    }
+}
+
+int trunk_f16l_l1_tables(const float *const *m0, const int *ncr, float *const *l1z, int *const *l1k, int N, int n_objects, const float4 *Wfwd,
+                         hipStream_t s) {
+    if (N <= 0 || n_objects <= 0) return DGDM_OK;
+    hipLaunchKernelGGL(l1_table_kernel, dim3((N + 31) / 32, n_objects), dim3(64), 0, s, m0, ncr, l1z, l1k, N, reinterpret_cast<const v4f32 *>(Wfwd));
+    DGDM_HIP_CHECK(hipGetLastError());
+    return DGDM_OK;
+}
+
 int trunk_f16l_launch(int kind, TrunkF16Mode mode, const TrunkParams &p, const TrunkF16Scales &sc, hipStream_t s) {
     const bool fwd = mode != TrunkF16Mode::Grad, rowpose = mode == TrunkF16Mode::ForwardRowPose;
     if (p.n_mid != (kind == 3 ? 6 : 7) || (fwd && !p.logits) || (rowpose && (!p.PtabT || (kind == 3 && !p.Pmax)))) return DGDM_EINVAL;
     const int grid = (p.ntiles + 3) / 4;
     if (grid == 0) return DGDM_OK;
+    // layer-1 tables (3-D gradient launch only; the forward-only kernels keep the general front): the chains that have one run the tabled
+    // instantiation, the others the general one, each over its part of the chain list
+    const bool split = !fwd && kind == 3 && p.l1z;
+    const int per_chain = p.B * p.tiles_per_b, n_chains = per_chain > 0 ? p.ntiles / per_chain : 0;
+    if (split && (!p.l1k || !p.xtab || !p.xidx || !p.Wfwd_nl1 || !p.chainlist || p.n_tabled < 1 || p.n_tabled > n_chains || n_chains * per_chain != p.ntiles))
+        return DGDM_EINVAL;                                   // (the tabled front indexes its tables as xtab is indexed)
     void (*kernel)(const TrunkParams, const TrunkF16Scales);
     switch (mode) {
     case TrunkF16Mode::Forward: kernel = kind == 2 ? trunk_f16l_kernel<2, true> : trunk_f16l_kernel<3, true>; break;
@@ -635,7 +800,19 @@ int trunk_f16l_launch(int kind, TrunkF16Mode mode, const TrunkParams &p, const T
     default: kernel = kind == 2 ? trunk_f16l_kernel<2> : trunk_f16l_kernel<3>; break;
     }
     prof_begin(s, DGDM_STAGE_TRUNK);
-    hipLaunchKernelGGL(kernel, dim3(grid), dim3(256), 0, s, p, sc);
+    if (split) {
+        TrunkParams q = p;
+        if (p.n_tabled < n_chains) {
+            q.chains = p.chainlist + p.n_tabled; q.ntiles = (n_chains - p.n_tabled) * per_chain;
+            hipLaunchKernelGGL(kernel, dim3((q.ntiles + 3) / 4), dim3(256), 0, s, q, sc);
+        }
+        q.chains = p.chainlist; q.ntiles = p.n_tabled * per_chain;
+        hipLaunchKernelGGL((trunk_f16l_kernel<3, false, false, true>), dim3((q.ntiles + 3) / 4), dim3(256), 0, s, q, sc);
+    } else {
+        TrunkParams q = p;
+        q.chains = nullptr;
+        hipLaunchKernelGGL(kernel, dim3(grid), dim3(256), 0, s, q, sc);
+    }
     DGDM_HIP_CHECK(hipGetLastError());
     prof_end(s, DGDM_STAGE_TRUNK, trunk_flops(kind, p, false, fwd));
     return DGDM_OK;
