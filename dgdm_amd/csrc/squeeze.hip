@@ -10,6 +10,9 @@
 //   3. apply_kernel / square_kernel, ceil(log2(cells)) rounds of pointer doubling, int32 only: round r holds succ^(2^r); the k-th
 //                       successor collects the rounds of k's set bits, the last square is the fixed point;
 //   4. lookup_kernel    one thread per (pair, start): snap, read the two maps, y and flags.
+// dgdm_squeeze_map_3d (3-D fingers: the same contract on the horizontal planes of the finger grid, include/dgdm_hip.h "squeeze
+// simulator, 3-D fingers") runs the same chunk loop (run_chunks) with table3d_kernel in table_kernel's place; dgdm_squeeze_slice cuts
+// the object meshes into the per-level segment lists it reads.  Their kernels are described where they stand, below.
 // This file is compiled with -ffp-contract=off (build.py): no operation of the contract is fused.
 #include "common.h"
 #include <cmath>
@@ -213,6 +216,282 @@ int check_config(const DgdmSqueezeConfig *c, const char *fn) {
     return DGDM_OK;
 }
 
+Grid grid_of(const DgdmSqueezeConfig *cfg) {
+    Grid g = {};
+    g.T = cfg->theta_cells;
+    g.X = cfg->x_cells;
+    g.R = cfg->window;
+    g.x_half = cfg->x_half;
+    g.dx = 2.0 * cfg->x_half / (double)(cfg->x_cells - 1);
+    g.travel_max = cfg->travel_max;
+    return g;
+}
+
+struct Outputs {
+    int32_t *cells;
+    double *y;
+    int32_t *flags;
+    double *S, *tl, *tr;
+    int32_t *succ;
+};
+
+// The chunk loop of both entries: as many pairs per chunk as the workspace's `bytes` hold (the caller has checked that one fits);
+// `table(n, pairs, tl, tr, S, stream)` launches the entry's table kernel for the chunk's n pairs, whose (finger, object) are at `pairs`.
+template <class Table>
+int run_chunks(const DgdmSqueezeConfig *cfg, const Grid &g, const int32_t *pairs_host, int n_pairs, const double *starts_dev, int n_starts,
+               const Outputs &out, void *workspace_dev, int64_t bytes, hipStream_t s, Table table) {
+    const int64_t cells = (int64_t)g.T * g.X;
+    int64_t chunk = std::min<int64_t>(std::min<int64_t>(n_pairs, MAX_CHUNK), bytes / (int64_t)layout(cells, 1).bytes + 1);
+    while (chunk > 1 && (int64_t)layout(cells, chunk).bytes > bytes) --chunk;
+    int rounds = 0;
+    while (((int64_t)1 << rounds) < cells) ++rounds;                     // ceil(log2(cells)): no path is longer than cells - 1 steps
+    const bool k_settles = rounds < 31 && (int64_t)cfg->closing_steps >= ((int64_t)1 << rounds);
+
+    const Layout L = layout(cells, chunk);
+    uint8_t *ws = static_cast<uint8_t *>(workspace_dev);
+    int32_t *pairs = reinterpret_cast<int32_t *>(ws + L.pairs);
+    double *tl = reinterpret_cast<double *>(ws + L.tl), *tr = reinterpret_cast<double *>(ws + L.tr), *S = reinterpret_cast<double *>(ws + L.S);
+    int32_t *succ = reinterpret_cast<int32_t *>(ws + L.succ), *kth = reinterpret_cast<int32_t *>(ws + L.kth);
+    int32_t *buf[2] = {reinterpret_cast<int32_t *>(ws + L.ping), reinterpret_cast<int32_t *>(ws + L.pong)};
+    const unsigned cb = (unsigned)((cells + 255) / 256);
+    for (int64_t p0 = 0; p0 < n_pairs; p0 += chunk) {
+        const unsigned n = (unsigned)std::min<int64_t>(chunk, n_pairs - p0);
+        DGDM_HIP_CHECK(hipMemcpyAsync(pairs, pairs_host + 2 * p0, sizeof(int32_t) * 2 * n, hipMemcpyHostToDevice, s));
+        table(n, pairs, tl, tr, S, s);
+        DGDM_HIP_CHECK(hipGetLastError());
+        hipLaunchKernelGGL(successor_kernel, dim3(cb, n), dim3(256), 0, s, g, S, succ);
+        DGDM_HIP_CHECK(hipGetLastError());
+        hipLaunchKernelGGL(iota_kernel, dim3(cb, n), dim3(256), 0, s, (int)cells, kth);
+        DGDM_HIP_CHECK(hipGetLastError());
+        const int32_t *power = succ;
+        for (int r = 0; r < rounds; ++r) {
+            if (!k_settles && ((cfg->closing_steps >> r) & 1)) {
+                hipLaunchKernelGGL(apply_kernel, dim3(cb, n), dim3(256), 0, s, (int)cells, power, kth);
+                DGDM_HIP_CHECK(hipGetLastError());
+            }
+            hipLaunchKernelGGL(square_kernel, dim3(cb, n), dim3(256), 0, s, (int)cells, power, buf[r & 1]);
+            DGDM_HIP_CHECK(hipGetLastError());
+            power = buf[r & 1];
+        }
+        const int32_t *fix = power;                                      // succ^(2^rounds): every path has ended
+        const int32_t *closed = k_settles ? fix : kth;
+        if (n_starts > 0) {
+            hipLaunchKernelGGL(lookup_kernel, dim3((unsigned)((n_starts + 255) / 256), n), dim3(256), 0, s, g, starts_dev, n_starts, tl, tr, S, closed,
+                               fix, (int)p0, out.cells, out.y, out.flags);
+            DGDM_HIP_CHECK(hipGetLastError());
+        }
+        const size_t off = (size_t)p0 * cells, cnt = (size_t)n * cells;
+        if (out.S) DGDM_HIP_CHECK(hipMemcpyAsync(out.S + off, S, sizeof(double) * cnt, hipMemcpyDeviceToDevice, s));
+        if (out.tl) DGDM_HIP_CHECK(hipMemcpyAsync(out.tl + off, tl, sizeof(double) * cnt, hipMemcpyDeviceToDevice, s));
+        if (out.tr) DGDM_HIP_CHECK(hipMemcpyAsync(out.tr + off, tr, sizeof(double) * cnt, hipMemcpyDeviceToDevice, s));
+        if (out.succ) DGDM_HIP_CHECK(hipMemcpyAsync(out.succ + off, succ, sizeof(int32_t) * cnt, hipMemcpyDeviceToDevice, s));
+    }
+    DGDM_HIP_CHECK(hipStreamSynchronize(s));        // the pair list's host buffer belongs to the caller
+    return DGDM_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------- 3-D: a sliced squeeze
+// include/dgdm_hip.h "squeeze simulator, 3-D fingers"; tests/squeeze3d_oracle.py is the CPU oracle.
+//   slice_kernel<false / true>  one workgroup per (level, object): the count pass and, after the host's scan of the n_objects x mv
+//                       counts, the emit pass - a block scan of the crossing flags per 256 triangles keeps the triangle order;
+//   table3d_kernel      one workgroup per (pair, theta), lanes on the x cells (table_kernel's layout): the pair's 2 mv mu surface doubles,
+//                       gx and the object's level offsets staged in LDS once, the rotated segments in tiles of SEG_TILE; each lane
+//                       carries its two minima in registers across tiles - no atomics, no cross-lane reduction.
+// SEG_TILE = 1024 segments x 4 doubles = 32 KB: with the 16 KB of surfaces at the limits a workgroup stays under 50 KB, three per CU in
+// the 160 KB of LDS; a larger tile saves two barriers per 1024 segments, which the ~100 float64 operations per segment and lane dwarf.
+constexpr int SEG_TILE = 1024;
+constexpr int MAX_MU = 128, MAX_MV = 512, MAX_SURFACE_3D = 1024, MAX_LEVELS = 1024;
+
+struct Grid3 {
+    int T, X, mu, mv;
+    double x_half, dx;
+};
+
+template <bool EMIT>
+__global__ __launch_bounds__(256) void slice_kernel(const double *verts, const int32_t *tris, const int64_t *vert_off, const int64_t *tri_off,
+                                                    const double *gz, int mv, int32_t *counts, const int32_t *seg_off, double *segments) {
+    __shared__ int sc[256];
+    const int j = blockIdx.x, o = blockIdx.y, tid = threadIdx.x;
+    const double z = gz[j];
+    const double *V = verts + 3 * vert_off[o];
+    const int32_t *F = tris + 3 * tri_off[o];
+    const int nt = (int)(tri_off[o + 1] - tri_off[o]);
+    int base = 0;                                                          // EMIT: segments of earlier rounds; else this thread's count
+    for (int t0 = 0; t0 < nt; t0 += 256) {
+        const int t = t0 + tid;
+        int v[3] = {0, 0, 0};
+        bool up[3] = {false, false, false};
+        bool cross = false;
+        if (t < nt) {
+            for (int e = 0; e < 3; ++e) {
+                v[e] = F[3 * t + e];
+                up[e] = V[3 * v[e] + 2] >= z;
+            }
+            const int nup = (int)up[0] + (int)up[1] + (int)up[2];
+            cross = nup != 0 && nup != 3;
+        }
+        if (!EMIT) {
+            base += cross ? 1 : 0;
+            continue;
+        }
+        sc[tid] = cross ? 1 : 0;                                           // inclusive scan of the flags: the triangle order is kept
+        __syncthreads();
+        for (int off = 1; off < 256; off <<= 1) {
+            const int add = tid >= off ? sc[tid - off] : 0;
+            __syncthreads();
+            sc[tid] += add;
+            __syncthreads();
+        }
+        const int incl = sc[tid], total = sc[255];
+        __syncthreads();
+        if (cross) {
+            double pt[4];
+            int n = 0;
+            for (int e = 0; e < 3; ++e) {
+                const int e1 = e == 2 ? 0 : e + 1;
+                if (up[e] == up[e1]) continue;
+                const double *D = V + 3 * (up[e] ? v[e1] : v[e]), *W = V + 3 * (up[e] ? v[e] : v[e1]);
+                const double r = (z - D[2]) / (W[2] - D[2]);
+                pt[n++] = D[0] + r * (W[0] - D[0]);
+                pt[n++] = D[1] + r * (W[1] - D[1]);
+            }
+            double *dst = segments + 4 * ((int64_t)seg_off[o * (mv + 1) + j] + base + incl - 1);
+            for (int q = 0; q < 4; ++q) dst[q] = pt[q];
+        }
+        base += total;
+    }
+    if (!EMIT) {
+        sc[tid] = base;
+        __syncthreads();
+        for (int off = 128; off > 0; off >>= 1) {
+            if (tid < off) sc[tid] += sc[tid + off];
+            __syncthreads();
+        }
+        if (tid == 0) counts[o * mv + j] = sc[0];
+    }
+}
+
+// the greatest i with gx[i] <= x, -1 when there is none (or x is a NaN): comparisons only
+__device__ __forceinline__ int last_le(const double *gx, int mu, double x) {
+    int lo = -1, hi = mu;
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (gx[mid] <= x) lo = mid; else hi = mid;
+    }
+    return lo;
+}
+
+// touch_l / touch_r / S [pairs][T][X] of this chunk.  Grid: (T, pairs) workgroups.
+__global__ __launch_bounds__(TABLE_THREADS) void table3d_kernel(Grid3 g, const double *surfaces, const double *gx, const double *segments,
+                                                                const int32_t *seg_offsets, const int32_t *pairs, const double *rot,
+                                                                double *touch_l, double *touch_r, double *S) {
+    extern __shared__ double lds[];
+    const int ms = g.mv * g.mu, mu = g.mu, tid = threadIdx.x;
+    double *sL = lds, *sU = lds + ms, *sG = lds + 2 * ms, *sSeg = sG + mu;
+    int32_t *sOff = reinterpret_cast<int32_t *>(sSeg + 4 * SEG_TILE);
+    const int a = blockIdx.x, p = blockIdx.y;
+    const double *sf = surfaces + (int64_t)pairs[2 * p] * 2 * ms;
+    const int32_t *off = seg_offsets + (int64_t)pairs[2 * p + 1] * (g.mv + 1);
+    const double c = rot[2 * a], s = rot[2 * a + 1];
+    for (int i = tid; i < 2 * ms; i += TABLE_THREADS) sL[i] = sf[i];       // L then U, as the pair holds them
+    for (int i = tid; i < mu; i += TABLE_THREADS) sG[i] = gx[i];
+    for (int i = tid; i <= g.mv; i += TABLE_THREADS) sOff[i] = off[i];
+    __syncthreads();
+    const int s0 = sOff[0], s1 = sOff[g.mv];
+    const double glast = sG[mu - 1], inf = INFINITY;
+    for (int b0 = 0; b0 < g.X; b0 += TABLE_THREADS) {
+        const int b = b0 + tid;
+        const double xg = -g.x_half + (double)b * g.dx;
+        double gl = inf, gu = inf;
+        int j = 0;                                                         // the level of the segment at hand: they come level-sorted
+        for (int t0 = s0; t0 < s1; t0 += SEG_TILE) {
+            const int n = min(SEG_TILE, s1 - t0);
+            __syncthreads();                                               // the tile before has been read by every lane
+            for (int k = tid; k < n; k += TABLE_THREADS) {
+                const double *sg = segments + 4 * (int64_t)(t0 + k);
+                const double ax = sg[0], ay = sg[1], bx = sg[2], by = sg[3];
+                sSeg[4 * k] = c * ax - s * ay;
+                sSeg[4 * k + 1] = s * ax + c * ay;
+                sSeg[4 * k + 2] = c * bx - s * by;
+                sSeg[4 * k + 3] = s * bx + c * by;
+            }
+            __syncthreads();
+            if (b >= g.X) continue;
+            for (int k = 0; k < n; ++k) {
+                while (t0 + k >= sOff[j + 1]) ++j;                         // t0 + k < s1 = sOff[mv]: j stays below mv
+                const double *Lj = sL + j * mu, *Uj = sU + j * mu;
+                const double px = sSeg[4 * k] + xg, py = sSeg[4 * k + 1], qx = sSeg[4 * k + 2] + xg, qy = sSeg[4 * k + 3];
+                // one search per endpoint serves set A and, gx being ascending, both ends of set B's range of abscissae
+                const int ip = last_le(sG, mu, px), iq = last_le(sG, mu, qx);
+                if (ip >= 0 && px <= glast) {                              // set A: P against the interpolated profiles
+                    const int i = min(ip, mu - 2);
+                    const double g0 = sG[i], f = (px - g0) / (sG[i + 1] - g0);
+                    const double l0 = Lj[i], u0 = Uj[i];
+                    const double lp = l0 + f * (Lj[i + 1] - l0);
+                    const double up = u0 + f * (Uj[i + 1] - u0);
+                    gl = fmin(gl, py - lp);
+                    gu = fmin(gu, up - py);
+                }
+                if (iq >= 0 && qx <= glast) {                              // set A: Q
+                    const int i = min(iq, mu - 2);
+                    const double g0 = sG[i], f = (qx - g0) / (sG[i + 1] - g0);
+                    const double l0 = Lj[i], u0 = Uj[i];
+                    const double lp = l0 + f * (Lj[i + 1] - l0);
+                    const double up = u0 + f * (Uj[i + 1] - u0);
+                    gl = fmin(gl, qy - lp);
+                    gu = fmin(gu, up - qy);
+                }
+                if (px < qx || qx < px) {                                  // set B: the abscissae under the segment (false for a NaN)
+                    const bool fwd = px < qx;
+                    const int ilo = fwd ? ip : iq, ihi = fwd ? iq : ip;
+                    const double xlo = fwd ? px : qx;
+                    const int i0 = (ilo >= 0 && sG[ilo] == xlo) ? ilo : ilo + 1;
+                    if (i0 <= ihi) {
+                        const double slope = (qy - py) / (qx - px);
+                        for (int i = i0; i <= ihi; ++i) {
+                            const double ye = py + (sG[i] - px) * slope;
+                            gl = fmin(gl, ye - Lj[i]);
+                            gu = fmin(gu, Uj[i] - ye);
+                        }
+                    }
+                }
+            }
+        }
+        if (b < g.X) {
+            const int64_t o = ((int64_t)p * g.T + a) * g.X + b;
+            touch_l[o] = gl;
+            touch_r[o] = gu;
+            S[o] = (gl + gu) / 2.0;
+        }
+    }
+}
+
+// the 3-D entry's workspace: the chunk's layout, then gx [mu] and the level offsets [n_objects][mv + 1]
+struct Extra3 { size_t gx, off, bytes; };
+Extra3 extra3(int mu, int mv, int n_objects) {
+    Extra3 e;
+    e.gx = 0;
+    e.off = align256(sizeof(double) * (size_t)mu);
+    e.bytes = e.off + align256(sizeof(int32_t) * (size_t)n_objects * (size_t)(mv + 1));
+    return e;
+}
+
+int check_sizes_3d(int mu, int mv, int n_objects, const char *fn) {
+    DGDM_REQUIRE(mu >= 2 && mu <= MAX_MU, DGDM_EINVAL, "%s: %d abscissae (need 2 .. %d)", fn, mu, MAX_MU);
+    DGDM_REQUIRE(mv >= 1 && mv <= MAX_MV, DGDM_EINVAL, "%s: %d levels (need 1 .. %d)", fn, mv, MAX_MV);
+    DGDM_REQUIRE(mu * mv <= MAX_SURFACE_3D, DGDM_EINVAL, "%s: %d x %d surface samples (need at most %d)", fn, mv, mu, MAX_SURFACE_3D);
+    DGDM_REQUIRE(n_objects >= 1 && n_objects <= (1 << 20), DGDM_EINVAL, "%s: %d objects (need 1 .. 2^20)", fn, n_objects);
+    return DGDM_OK;
+}
+
+int check_ascending(const double *v, int n, const char *what, const char *fn) {
+    for (int i = 0; i < n; ++i) {
+        DGDM_REQUIRE(std::isfinite(v[i]), DGDM_EINVAL, "%s: %s[%d] = %g is not finite", fn, what, i, v[i]);
+        DGDM_REQUIRE(i == 0 || v[i] > v[i - 1], DGDM_EINVAL, "%s: %s is not strictly ascending at %d (%g after %g)", fn, what, i, v[i], v[i - 1]);
+    }
+    return DGDM_OK;
+}
+
 }  // namespace
 }  // namespace dgdm
 
@@ -249,65 +528,143 @@ extern "C" int dgdm_squeeze_map(const DgdmSqueezeConfig *cfg, const double *surf
     DGDM_REQUIRE(workspace_bytes >= (int64_t)layout(cells, 1).bytes, DGDM_EINVAL,
                  "%s: workspace of %lld bytes holds no pair, one needs %lld (dgdm_squeeze_workspace_bytes)", fn, (long long)workspace_bytes,
                  (long long)layout(cells, 1).bytes);
-    int64_t chunk = std::min<int64_t>(std::min<int64_t>(n_pairs, MAX_CHUNK), workspace_bytes / (int64_t)layout(cells, 1).bytes + 1);
-    while (chunk > 1 && (int64_t)layout(cells, chunk).bytes > workspace_bytes) --chunk;
-
-    Grid g;
-    g.T = cfg->theta_cells;
-    g.X = cfg->x_cells;
-    g.R = cfg->window;
+    Grid g = grid_of(cfg);
     g.m = num_points;
     g.nv = num_vertices;
-    g.x_half = cfg->x_half;
-    g.dx = 2.0 * cfg->x_half / (double)(cfg->x_cells - 1);
     g.hl = cfg->finger_half_len;
     g.h = 2.0 * cfg->finger_half_len / (double)(num_points - 1);
-    g.travel_max = cfg->travel_max;
-    int rounds = 0;
-    while (((int64_t)1 << rounds) < cells) ++rounds;                     // ceil(log2(cells)): no path is longer than cells - 1 steps
-    const bool k_settles = rounds < 31 && (int64_t)cfg->closing_steps >= ((int64_t)1 << rounds);
-
-    const Layout L = layout(cells, chunk);
-    uint8_t *ws = static_cast<uint8_t *>(workspace_dev);
-    int32_t *pairs = reinterpret_cast<int32_t *>(ws + L.pairs);
-    double *tl = reinterpret_cast<double *>(ws + L.tl), *tr = reinterpret_cast<double *>(ws + L.tr), *S = reinterpret_cast<double *>(ws + L.S);
-    int32_t *succ = reinterpret_cast<int32_t *>(ws + L.succ), *kth = reinterpret_cast<int32_t *>(ws + L.kth);
-    int32_t *buf[2] = {reinterpret_cast<int32_t *>(ws + L.ping), reinterpret_cast<int32_t *>(ws + L.pong)};
-    hipStream_t s = (hipStream_t)stream;
     const size_t lds = sizeof(double) * (size_t)(2 * g.m + 2 * g.nv);
-    const unsigned cb = (unsigned)((cells + 255) / 256);
-    for (int64_t p0 = 0; p0 < n_pairs; p0 += chunk) {
-        const unsigned n = (unsigned)std::min<int64_t>(chunk, n_pairs - p0);
-        DGDM_HIP_CHECK(hipMemcpyAsync(pairs, pairs_host + 2 * p0, sizeof(int32_t) * 2 * n, hipMemcpyHostToDevice, s));
-        hipLaunchKernelGGL(table_kernel, dim3((unsigned)g.T, n), dim3(TABLE_THREADS), lds, s, g, surfaces_dev, objects_dev, pairs, rot_dev, tl, tr, S);
-        DGDM_HIP_CHECK(hipGetLastError());
-        hipLaunchKernelGGL(successor_kernel, dim3(cb, n), dim3(256), 0, s, g, S, succ);
-        DGDM_HIP_CHECK(hipGetLastError());
-        hipLaunchKernelGGL(iota_kernel, dim3(cb, n), dim3(256), 0, s, (int)cells, kth);
-        DGDM_HIP_CHECK(hipGetLastError());
-        const int32_t *power = succ;
-        for (int r = 0; r < rounds; ++r) {
-            if (!k_settles && ((cfg->closing_steps >> r) & 1)) {
-                hipLaunchKernelGGL(apply_kernel, dim3(cb, n), dim3(256), 0, s, (int)cells, power, kth);
-                DGDM_HIP_CHECK(hipGetLastError());
-            }
-            hipLaunchKernelGGL(square_kernel, dim3(cb, n), dim3(256), 0, s, (int)cells, power, buf[r & 1]);
-            DGDM_HIP_CHECK(hipGetLastError());
-            power = buf[r & 1];
-        }
-        const int32_t *fix = power;                                      // succ^(2^rounds): every path has ended
-        const int32_t *closed = k_settles ? fix : kth;
-        if (n_starts > 0) {
-            hipLaunchKernelGGL(lookup_kernel, dim3((unsigned)((n_starts + 255) / 256), n), dim3(256), 0, s, g, starts_dev, n_starts, tl, tr, S, closed,
-                               fix, (int)p0, cells_dev, y_dev, flags_dev);
-            DGDM_HIP_CHECK(hipGetLastError());
-        }
-        const size_t off = (size_t)p0 * cells, cnt = (size_t)n * cells;
-        if (table_s_dev) DGDM_HIP_CHECK(hipMemcpyAsync(table_s_dev + off, S, sizeof(double) * cnt, hipMemcpyDeviceToDevice, s));
-        if (touch_l_dev) DGDM_HIP_CHECK(hipMemcpyAsync(touch_l_dev + off, tl, sizeof(double) * cnt, hipMemcpyDeviceToDevice, s));
-        if (touch_r_dev) DGDM_HIP_CHECK(hipMemcpyAsync(touch_r_dev + off, tr, sizeof(double) * cnt, hipMemcpyDeviceToDevice, s));
-        if (succ_dev) DGDM_HIP_CHECK(hipMemcpyAsync(succ_dev + off, succ, sizeof(int32_t) * cnt, hipMemcpyDeviceToDevice, s));
+    Outputs out = {cells_dev, y_dev, flags_dev, table_s_dev, touch_l_dev, touch_r_dev, succ_dev};
+    return run_chunks(cfg, g, pairs_host, n_pairs, starts_dev, n_starts, out, workspace_dev, workspace_bytes, (hipStream_t)stream,
+                      [&](unsigned n, const int32_t *pairs, double *tl, double *tr, double *S, hipStream_t s) {
+                          hipLaunchKernelGGL(table_kernel, dim3((unsigned)g.T, n), dim3(TABLE_THREADS), lds, s, g, surfaces_dev, objects_dev, pairs,
+                                             rot_dev, tl, tr, S);
+                      });
+}
+
+extern "C" int dgdm_squeeze_slice(const double *verts_host, const int64_t *vert_offsets_host, const int32_t *tris_host,
+                                  const int64_t *tri_offsets_host, int n_objects, const double *gz_host, int mv, double *segments_dev,
+                                  int64_t capacity, int32_t *seg_offsets_host, int64_t *n_segments_host, void *stream) {
+    const char *fn = "dgdm_squeeze_slice";
+    DGDM_REQUIRE(verts_host && vert_offsets_host && tris_host && tri_offsets_host && gz_host && seg_offsets_host && n_segments_host, DGDM_EINVAL,
+                 "%s: null argument", fn);
+    DGDM_REQUIRE(n_objects >= 1 && n_objects <= 65535, DGDM_EINVAL, "%s: %d objects (need 1 .. 65535)", fn, n_objects);
+    DGDM_REQUIRE(mv >= 1 && mv <= MAX_LEVELS, DGDM_EINVAL, "%s: %d levels (need 1 .. %d)", fn, mv, MAX_LEVELS);
+    DGDM_REQUIRE(capacity >= 0 && (segments_dev || capacity == 0), DGDM_EINVAL, "%s: capacity %lld with%s segments_dev", fn, (long long)capacity,
+                 segments_dev ? "" : " no");
+    int rc = check_ascending(gz_host, mv, "gz", fn);
+    if (rc) return rc;
+    DGDM_REQUIRE(vert_offsets_host[0] == 0 && tri_offsets_host[0] == 0, DGDM_EINVAL, "%s: offsets start at %lld and %lld (need 0)", fn,
+                 (long long)vert_offsets_host[0], (long long)tri_offsets_host[0]);
+    for (int o = 0; o < n_objects; ++o) {
+        const int64_t nv = vert_offsets_host[o + 1] - vert_offsets_host[o], nt = tri_offsets_host[o + 1] - tri_offsets_host[o];
+        DGDM_REQUIRE(nv >= 1 && nt >= 0, DGDM_EINVAL, "%s: mesh %d has %lld vertices and %lld triangles", fn, o, (long long)nv, (long long)nt);
+        DGDM_REQUIRE(vert_offsets_host[o + 1] <= INT32_MAX && tri_offsets_host[o + 1] <= INT32_MAX, DGDM_EINVAL,
+                     "%s: more than 2^31 - 1 vertices or triangles", fn);
+        const double *V = verts_host + 3 * vert_offsets_host[o];
+        for (int64_t i = 0; i < 3 * nv; ++i)
+            DGDM_REQUIRE(std::isfinite(V[i]), DGDM_EINVAL, "%s: mesh %d, vertex %lld is not finite", fn, o, (long long)(i / 3));
+        const int32_t *F = tris_host + 3 * tri_offsets_host[o];
+        for (int64_t i = 0; i < 3 * nt; ++i)
+            DGDM_REQUIRE(F[i] >= 0 && F[i] < nv, DGDM_EINVAL, "%s: mesh %d, triangle %lld names vertex %d of %lld", fn, o, (long long)(i / 3), F[i],
+                         (long long)nv);
     }
-    DGDM_HIP_CHECK(hipStreamSynchronize(s));        // the pair list's host buffer belongs to the caller
+    const int64_t nv_all = vert_offsets_host[n_objects], nt_all = tri_offsets_host[n_objects];
+    hipStream_t s = (hipStream_t)stream;
+    DevBuf verts, tris, voff, toff, gz, counts, offs;
+    const size_t no1 = (size_t)n_objects + 1, nl = (size_t)n_objects * mv, nl1 = (size_t)n_objects * (mv + 1);
+    if ((rc = verts.alloc(sizeof(double) * 3 * (size_t)nv_all)) || (rc = tris.alloc(sizeof(int32_t) * 3 * (size_t)std::max<int64_t>(nt_all, 1))) ||
+        (rc = voff.alloc(sizeof(int64_t) * no1)) || (rc = toff.alloc(sizeof(int64_t) * no1)) || (rc = gz.alloc(sizeof(double) * mv)) ||
+        (rc = counts.alloc(sizeof(int32_t) * nl)) || (rc = offs.alloc(sizeof(int32_t) * nl1)))
+        return rc;
+    DGDM_HIP_CHECK(hipMemcpyAsync(verts.p, verts_host, sizeof(double) * 3 * (size_t)nv_all, hipMemcpyHostToDevice, s));
+    if (nt_all > 0) DGDM_HIP_CHECK(hipMemcpyAsync(tris.p, tris_host, sizeof(int32_t) * 3 * (size_t)nt_all, hipMemcpyHostToDevice, s));
+    DGDM_HIP_CHECK(hipMemcpyAsync(voff.p, vert_offsets_host, sizeof(int64_t) * no1, hipMemcpyHostToDevice, s));
+    DGDM_HIP_CHECK(hipMemcpyAsync(toff.p, tri_offsets_host, sizeof(int64_t) * no1, hipMemcpyHostToDevice, s));
+    DGDM_HIP_CHECK(hipMemcpyAsync(gz.p, gz_host, sizeof(double) * mv, hipMemcpyHostToDevice, s));
+    hipLaunchKernelGGL(slice_kernel<false>, dim3((unsigned)mv, (unsigned)n_objects), dim3(256), 0, s, verts.as<double>(), tris.as<int32_t>(),
+                       voff.as<int64_t>(), toff.as<int64_t>(), gz.as<double>(), mv, counts.as<int32_t>(), (const int32_t *)nullptr, (double *)nullptr);
+    DGDM_HIP_CHECK(hipGetLastError());
+    std::vector<int32_t> cnt(nl);
+    DGDM_HIP_CHECK(hipMemcpyAsync(cnt.data(), counts.p, sizeof(int32_t) * nl, hipMemcpyDeviceToHost, s));
+    DGDM_HIP_CHECK(hipStreamSynchronize(s));
+    int64_t total = 0;                                                     // the scan: n_objects x mv counts, on the host
+    for (int o = 0; o < n_objects; ++o) {
+        for (int j = 0; j < mv; ++j) {
+            DGDM_REQUIRE(total <= INT32_MAX, DGDM_EINVAL, "%s: more than 2^31 - 1 segments", fn);
+            seg_offsets_host[(size_t)o * (mv + 1) + j] = (int32_t)total;
+            total += cnt[(size_t)o * mv + j];
+        }
+        DGDM_REQUIRE(total <= INT32_MAX, DGDM_EINVAL, "%s: more than 2^31 - 1 segments", fn);
+        seg_offsets_host[(size_t)o * (mv + 1) + mv] = (int32_t)total;
+    }
+    *n_segments_host = total;
+    if (!segments_dev && capacity == 0) return DGDM_OK;                    // count only
+    DGDM_REQUIRE(capacity >= total, DGDM_EINVAL, "%s: capacity of %lld segments, %lld needed", fn, (long long)capacity, (long long)total);
+    if (total == 0) return DGDM_OK;
+    DGDM_HIP_CHECK(hipMemcpyAsync(offs.p, seg_offsets_host, sizeof(int32_t) * nl1, hipMemcpyHostToDevice, s));
+    hipLaunchKernelGGL(slice_kernel<true>, dim3((unsigned)mv, (unsigned)n_objects), dim3(256), 0, s, verts.as<double>(), tris.as<int32_t>(),
+                       voff.as<int64_t>(), toff.as<int64_t>(), gz.as<double>(), mv, (int32_t *)nullptr, offs.as<int32_t>(), segments_dev);
+    DGDM_HIP_CHECK(hipGetLastError());
+    DGDM_HIP_CHECK(hipStreamSynchronize(s));
     return DGDM_OK;
+}
+
+extern "C" int64_t dgdm_squeeze_map_3d_workspace_bytes(const DgdmSqueezeConfig *cfg, int chunk_pairs, int mu, int mv, int n_objects) {
+    const char *fn = "dgdm_squeeze_map_3d_workspace_bytes";
+    if (check_config(cfg, fn) || check_sizes_3d(mu, mv, n_objects, fn)) return DGDM_EINVAL;
+    DGDM_REQUIRE(chunk_pairs >= 1 && chunk_pairs <= MAX_CHUNK, DGDM_EINVAL, "%s: %d pairs per chunk (need 1 .. %d)", fn, chunk_pairs, MAX_CHUNK);
+    return (int64_t)(layout((int64_t)cfg->theta_cells * cfg->x_cells, chunk_pairs).bytes + extra3(mu, mv, n_objects).bytes);
+}
+
+extern "C" int dgdm_squeeze_map_3d(const DgdmSqueezeConfig *cfg, const double *surfaces_dev, int n_fingers, const double *gx_host, int mu, int mv,
+                                   const double *segments_dev, int64_t n_segments, const int32_t *seg_offsets_host, int n_objects,
+                                   const int32_t *pairs_host, int n_pairs, const double *rot_dev, const double *starts_dev, int n_starts,
+                                   int32_t *cells_dev, double *y_dev, int32_t *flags_dev, double *table_s_dev, double *touch_l_dev,
+                                   double *touch_r_dev, int32_t *succ_dev, void *workspace_dev, int64_t workspace_bytes, void *stream) {
+    const char *fn = "dgdm_squeeze_map_3d";
+    int rc = check_config(cfg, fn);
+    if (rc) return rc;
+    DGDM_REQUIRE(surfaces_dev && gx_host && seg_offsets_host && pairs_host && rot_dev && workspace_dev, DGDM_EINVAL, "%s: null argument", fn);
+    DGDM_REQUIRE(n_fingers >= 1 && n_pairs >= 1, DGDM_EINVAL, "%s: %d fingers, %d pairs (need >= 1 each)", fn, n_fingers, n_pairs);
+    if ((rc = check_sizes_3d(mu, mv, n_objects, fn)) || (rc = check_ascending(gx_host, mu, "gx", fn))) return rc;
+    DGDM_REQUIRE(n_segments >= 0 && n_segments <= INT32_MAX && (segments_dev || n_segments == 0), DGDM_EINVAL, "%s: %lld segments with%s segments_dev",
+                 fn, (long long)n_segments, segments_dev ? "" : " no");
+    const size_t nl1 = (size_t)n_objects * (size_t)(mv + 1);
+    DGDM_REQUIRE(seg_offsets_host[0] == 0, DGDM_EINVAL, "%s: seg_offsets start at %d (need 0)", fn, seg_offsets_host[0]);
+    for (size_t i = 1; i < nl1; ++i)
+        DGDM_REQUIRE(seg_offsets_host[i] >= seg_offsets_host[i - 1], DGDM_EINVAL, "%s: seg_offsets descend at %lld (%d after %d)", fn, (long long)i,
+                     seg_offsets_host[i], seg_offsets_host[i - 1]);
+    DGDM_REQUIRE(seg_offsets_host[nl1 - 1] <= n_segments, DGDM_EINVAL, "%s: seg_offsets end at %d, past the %lld segments", fn,
+                 seg_offsets_host[nl1 - 1], (long long)n_segments);
+    DGDM_REQUIRE(n_starts >= 0, DGDM_EINVAL, "%s: %d starts", fn, n_starts);
+    DGDM_REQUIRE(n_starts == 0 || (starts_dev && cells_dev && y_dev && flags_dev), DGDM_EINVAL, "%s: %d starts need starts_dev and the three outputs",
+                 fn, n_starts);
+    for (int p = 0; p < n_pairs; ++p)
+        DGDM_REQUIRE(pairs_host[2 * p] >= 0 && pairs_host[2 * p] < n_fingers && pairs_host[2 * p + 1] >= 0 && pairs_host[2 * p + 1] < n_objects,
+                     DGDM_EINVAL, "%s: pair %d = (finger %d, object %d) outside %d fingers x %d objects", fn, p, pairs_host[2 * p],
+                     pairs_host[2 * p + 1], n_fingers, n_objects);
+    const int64_t cells = (int64_t)cfg->theta_cells * cfg->x_cells;
+    const Extra3 e = extra3(mu, mv, n_objects);
+    const int64_t one = (int64_t)(layout(cells, 1).bytes + e.bytes);
+    DGDM_REQUIRE(workspace_bytes >= one, DGDM_EINVAL, "%s: workspace of %lld bytes holds no pair, one needs %lld (dgdm_squeeze_map_3d_workspace_bytes)",
+                 fn, (long long)workspace_bytes, (long long)one);
+    const int64_t chunk_bytes = workspace_bytes - (int64_t)e.bytes;       // the extra block sits behind the largest chunk layout that fits
+    int64_t chunk = std::min<int64_t>(std::min<int64_t>(n_pairs, MAX_CHUNK), chunk_bytes / (int64_t)layout(cells, 1).bytes + 1);
+    while (chunk > 1 && (int64_t)layout(cells, chunk).bytes > chunk_bytes) --chunk;
+    uint8_t *ex = static_cast<uint8_t *>(workspace_dev) + layout(cells, chunk).bytes;
+    double *gx = reinterpret_cast<double *>(ex + e.gx);
+    int32_t *offs = reinterpret_cast<int32_t *>(ex + e.off);
+    hipStream_t s = (hipStream_t)stream;
+    DGDM_HIP_CHECK(hipMemcpyAsync(gx, gx_host, sizeof(double) * mu, hipMemcpyHostToDevice, s));
+    DGDM_HIP_CHECK(hipMemcpyAsync(offs, seg_offsets_host, sizeof(int32_t) * nl1, hipMemcpyHostToDevice, s));
+    const Grid g = grid_of(cfg);
+    Grid3 g3 = {g.T, g.X, mu, mv, g.x_half, g.dx};
+    const size_t lds = sizeof(double) * (size_t)(2 * mu * mv + mu + 4 * SEG_TILE) + sizeof(int32_t) * (size_t)(mv + 1);
+    Outputs out = {cells_dev, y_dev, flags_dev, table_s_dev, touch_l_dev, touch_r_dev, succ_dev};
+    return run_chunks(cfg, g, pairs_host, n_pairs, starts_dev, n_starts, out, workspace_dev, chunk_bytes, s,
+                      [&](unsigned n, const int32_t *pairs, double *tl, double *tr, double *S, hipStream_t st) {
+                          hipLaunchKernelGGL(table3d_kernel, dim3((unsigned)g3.T, n), dim3(TABLE_THREADS), lds, st, g3, surfaces_dev, gx, segments_dev,
+                                             offs, pairs, rot_dev, tl, tr, S);
+                      });
 }

@@ -46,9 +46,12 @@ _FLAGS = [
                                        "for settled poses asked with render_last, <object>_<gripper>/<v>.png (sim/render_mesh.py)"),
     ("squeeze_sim", "flag", None, "2-D, --mode=test: fill the objective tables with the squeeze simulator (sim/squeeze.py: a frictionless, "
                                   "quasi-static parallel-jaw squeeze; its own model, not MuJoCo's); the scores are marked 'simulated': 'squeeze'"),
-    ("squeeze_closing_steps", int, None, "with --squeeze_sim: grid steps the object climbs in one closing (default 6; untuned)"),
-    ("squeeze_window", int, None, "with --squeeze_sim: half-width in cells of the neighbourhood a step searches (default 2; untuned)"),
-    ("score_stats", str, None, "dynamics training: the stats.json sim/sim_2d.py wrote beside its data; scores are divided by its score_std "
+    ("squeeze_sim_3d", "flag", None, "--fingers_3d, --mode=test, objects from mesh files: fill the objective tables with the sliced squeeze simulator "
+                                     "(sim/squeeze.py SqueezeSimulator3D: the 2-D model on the finger grid's horizontal planes); marked "
+                                     "'simulated': 'squeeze'"),
+    ("squeeze_closing_steps", int, None, "with --squeeze_sim / --squeeze_sim_3d: grid steps the object climbs in one closing (default 6; untuned)"),
+    ("squeeze_window", int, None, "with --squeeze_sim / --squeeze_sim_3d: half-width in cells of the neighbourhood a step searches (default 2; untuned)"),
+    ("score_stats", str, None, "dynamics training: the stats.json sim/sim_2d.py or sim/sim_3d.py wrote beside its data; scores are divided by its score_std "
                                "instead of the reference's constants"),
     ("save_meshes", "flag", None, "also export every emitted gripper as OBJ meshes, collision pieces and gripper_<idx>.xml (assets/finger_mesh.py)"),
     ("save_objects", "flag", None, "2-D: also export the run's icon objects as meshes, convex pieces and object_<idx>.xml into every model root "

@@ -1146,6 +1146,78 @@ def squeeze_tables(surfaces, objects, pairs, starts=None, rot=None, tables: bool
     return out
 
 
+def squeeze_slice(meshes, gz) -> Dict[str, object]:
+    """dgdm_squeeze_slice (include/dgdm_hip.h "squeeze simulator, 3-D fingers"): the cross-sections of triangle meshes on the planes
+    z = gz[j].  meshes: a sequence of (vertices (nv, 3) float64 in metres, triangles (nt, 3) int32), host arrays; gz (mv,) strictly
+    ascending.  -> segments (n, 4) float64 on the current device = (A_x, A_y, B_x, B_y), listed by (object, level, triangle), and
+    offsets (O, mv + 1) int32, host: level j of object o is segments offsets[o, j] .. offsets[o, j + 1] - 1.  Two calls: the count,
+    then the emit into a tensor of that size.  Synchronises the stream."""
+    meshes = list(meshes)
+    if not meshes:
+        raise ValueError("squeeze_slice: no meshes")
+    vs = [np.ascontiguousarray(v, dtype=np.float64).reshape(-1, 3) for v, _ in meshes]
+    fs = [np.ascontiguousarray(f, dtype=np.int32).reshape(-1, 3) for _, f in meshes]
+    verts, tris = np.concatenate(vs), np.concatenate(fs)
+    voff = np.concatenate([[0], np.cumsum([len(v) for v in vs])]).astype(np.int64)
+    toff = np.concatenate([[0], np.cumsum([len(f) for f in fs])]).astype(np.int64)
+    z = np.ascontiguousarray(gz, dtype=np.float64).reshape(-1)
+    O, mv = len(meshes), len(z)
+    offsets = np.zeros((O, mv + 1), dtype=np.int32)
+    n = C.c_int64(0)
+    args = (verts.ctypes.data, voff.ctypes.data, tris.ctypes.data, toff.ctypes.data, O, z.ctypes.data, mv)
+    _check_value(lib().dgdm_squeeze_slice(*args, None, 0, offsets.ctypes.data, C.byref(n), stream_ptr()))
+    dev = torch.device("cuda", torch.cuda.current_device())
+    segments = torch.empty((int(n.value), 4), dtype=torch.float64, device=dev)
+    if n.value:
+        _check_value(lib().dgdm_squeeze_slice(*args, dptr(segments), int(n.value), offsets.ctypes.data, C.byref(n), stream_ptr()))
+    return {"segments": segments, "offsets": offsets}
+
+
+def squeeze_tables_3d(surfaces, gx, segments, offsets, pairs, starts=None, rot=None, tables: bool = False, workspace_bytes: Optional[int] = None,
+                      **config) -> Dict[str, torch.Tensor]:
+    """dgdm_squeeze_map_3d on the current device.  surfaces (F, 2, mv, mu) float64: the lower and upper jaw face at travel 0 on the levels
+    and the abscissae gx (mu,), strictly ascending; segments (n, 4) / offsets (O, mv + 1): squeeze_slice's, for the same levels; the
+    rest and the outputs as squeeze_tables.  config: the keys of SQUEEZE_DEFAULTS (finger_half_len is unused here)."""
+    cfg = squeeze_config(**config)
+    dev = torch.device("cuda", torch.cuda.current_device())
+    f64 = lambda t: torch.as_tensor(t).detach().to(device=dev, dtype=torch.float64).contiguous()      # noqa: E731
+    sf, sg = f64(surfaces), f64(segments).reshape(-1, 4)
+    g = np.ascontiguousarray(gx, dtype=np.float64).reshape(-1)
+    of = np.ascontiguousarray(offsets, dtype=np.int32)
+    if sf.dim() != 4 or sf.shape[1] != 2 or sf.shape[3] != len(g) or of.ndim != 2 or of.shape[1] != sf.shape[2] + 1:
+        raise ValueError(f"squeeze_tables_3d: surfaces (F, 2, mv, mu), gx (mu,) and offsets (O, mv + 1) expected, got {tuple(sf.shape)}, "
+                         f"{g.shape} and {of.shape}")
+    mu, mv, O = int(sf.shape[3]), int(sf.shape[2]), int(of.shape[0])
+    one = lib().dgdm_squeeze_map_3d_workspace_bytes(C.byref(cfg), 1, mu, mv, O)
+    if one < 0:
+        _check_value(int(one))
+    pr = np.ascontiguousarray(pairs, dtype=np.int32).reshape(-1, 2)
+    P, T, X = len(pr), cfg.theta_cells, cfg.x_cells
+    rt = f64(squeeze_rotation_table(T) if rot is None else rot)
+    if rt.shape != (T, 2):
+        raise ValueError(f"squeeze_tables_3d: rot of shape {tuple(rt.shape)} (need ({T}, 2))")
+    st = f64(starts).reshape(-1, 3) if starts is not None else None
+    N = 0 if st is None else int(st.shape[0])
+    if workspace_bytes is not None:
+        ws_bytes = int(workspace_bytes)
+    else:
+        ws_bytes = int(one)
+        if P > 1:
+            fit = int(lib().dgdm_squeeze_map_3d_workspace_bytes(C.byref(cfg), min(P, 65535), mu, mv, O))
+            ws_bytes = fit if 0 < fit <= SQUEEZE_WORKSPACE_BYTES else max(SQUEEZE_WORKSPACE_BYTES, int(one))
+    ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=dev)
+    new = lambda *shape, dtype: torch.empty(shape, dtype=dtype, device=dev)                            # noqa: E731
+    out = {"cells": new(P, N, 3, dtype=torch.int32), "y": new(P, N, 2, dtype=torch.float64), "flags": new(P, N, dtype=torch.int32)}
+    if tables:
+        out.update({k: new(P, T, X, dtype=torch.float64) for k in ("S", "touch_l", "touch_r")})
+        out["succ"] = new(P, T * X, dtype=torch.int32)
+    _check_value(lib().dgdm_squeeze_map_3d(C.byref(cfg), dptr(sf), int(sf.shape[0]), g.ctypes.data, mu, mv, dptr(sg) if len(sg) else None, int(len(sg)),
+                                           of.ctypes.data, O, pr.ctypes.data, P, dptr(rt), dptr(st), N, dptr(out["cells"]), dptr(out["y"]),
+                                           dptr(out["flags"]), dptr(out.get("S")), dptr(out.get("touch_l")), dptr(out.get("touch_r")),
+                                           dptr(out.get("succ")), dptr(ws), ws_bytes, stream_ptr()))
+    return out
+
+
 def prof_enable(on: bool) -> None:
     check(lib().dgdm_prof_enable(int(on)))
 

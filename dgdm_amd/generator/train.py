@@ -382,11 +382,14 @@ def squeeze_from_args(args):
     checks only."""
     k, r = getattr(args, "squeeze_closing_steps", None), getattr(args, "squeeze_window", None)
     if not getattr(args, "squeeze_sim", False):
-        if k is not None or r is not None:
-            raise ValueError("--squeeze_closing_steps / --squeeze_window need --squeeze_sim")
+        if (k is not None or r is not None) and not getattr(args, "squeeze_sim_3d", False):
+            raise ValueError("--squeeze_closing_steps / --squeeze_window need --squeeze_sim (or, with --fingers_3d, --squeeze_sim_3d)")
         return None
+    if getattr(args, "squeeze_sim_3d", False):
+        raise ValueError("--squeeze_sim and --squeeze_sim_3d: choose one (--squeeze_sim is 2-D only, --squeeze_sim_3d is for --fingers_3d)")
     if getattr(args, "fingers_3d", False):
-        raise ValueError("--squeeze_sim is 2-D only: the squeeze model has no 3-D fingers (--fingers_3d)")
+        raise ValueError("--squeeze_sim is 2-D only: the squeeze model has no 3-D fingers (--fingers_3d); --squeeze_sim_3d is the sliced form "
+                         "for them")
     if getattr(args, "predicted_sim", False):
         raise ValueError("--squeeze_sim and --predicted_sim both fill the objective tables: choose one")
     if getattr(args, "mode", "test") != 'test':
@@ -403,12 +406,39 @@ def squeeze_from_args(args):
     return {key: v for key, v in (("closing_steps", k), ("window", r)) if v is not None}
 
 
+def squeeze_3d_from_args(args):
+    """--squeeze_sim_3d [--squeeze_closing_steps K --squeeze_window R] -> SqueezeSimulator3D's keywords, or None without the flag.
+    Host-side checks only; that the run's objects are mesh files is checked where they are known (train)."""
+    if not getattr(args, "squeeze_sim_3d", False):
+        return None
+    k, r = getattr(args, "squeeze_closing_steps", None), getattr(args, "squeeze_window", None)
+    if not getattr(args, "fingers_3d", False):
+        raise ValueError("--squeeze_sim_3d needs --fingers_3d: it is the squeeze model for 3-D fingers (--squeeze_sim is the 2-D one)")
+    if getattr(args, "predicted_sim", False):
+        raise ValueError("--squeeze_sim_3d and --predicted_sim both fill the objective tables: choose one")
+    if getattr(args, "mode", "test") != 'test':
+        raise ValueError("--squeeze_sim_3d scores the samples of --mode=test")
+    if getattr(args, "goal_pose", None):
+        raise ValueError("--squeeze_sim_3d with --goal_pose: goal scores (dynamics/predicted.py goal_objective) are marked as the dynamics "
+                         "model's predictions, which squeeze results are not - not supported")
+    if not getattr(args, "classifier_guidance", False):
+        raise ValueError("--squeeze_sim_3d needs --classifier_guidance: the run's objects come with it")
+    if k is not None and k < 0:
+        raise ValueError(f"--squeeze_closing_steps={k}: the number of steps cannot be negative")
+    if r is not None and r < 1:
+        raise ValueError(f"--squeeze_window={r}: the window is at least 1 cell")
+    return {key: v for key, v in (("closing_steps", k), ("window", r)) if v is not None}
+
+
 def train(args):
     dev = torch.device("cuda", torch.cuda.current_device() if torch.cuda.is_available() else int(os.environ.get("LOCAL_RANK", "0")))
     pts = finger_control_points(args.num_fingers, args.fingers_3d)
     max_y, min_y = (0.0, -0.1) if args.fingers_3d else (0.015, -0.045)
     check_cond_flags(args)
     squeeze_from_args(args)                 # --squeeze_sim: refused here, before anything is built
+    if squeeze_3d_from_args(args) is not None and _object_mesh_dir(args) is None:      # --squeeze_sim_3d: likewise
+        raise ValueError("--squeeze_sim_3d needs the run's objects as mesh files (<object_dir>/<name>/model.obj): objects.npy and synthetic "
+                         "clouds have no cross-sections")
     cond_stats, cond_requested = check_label_flags(args)    # --mode=label, --cond_stats / --cond_target: refused here, before anything is built
     from ..edit import plan_from_args
     edit_plan = plan_from_args(args)        # --edit_from / --pin / --edit_band_mm / --edit_steps: read and checked before anything is built
@@ -463,6 +493,10 @@ def train(args):
     if squeeze is not None and model.simulator is None:
         from ..sim.squeeze import SqueezeSimulator               # opt-in: the tables scored by the squeeze model (its own idealisation)
         model.simulator = SqueezeSimulator(model, **squeeze)
+    squeeze3 = squeeze_3d_from_args(args)   # --squeeze_sim_3d: the sliced form for --fingers_3d, on the run's mesh files
+    if squeeze3 is not None and model.simulator is None:
+        from ..sim.squeeze import SqueezeSimulator3D
+        model.simulator = SqueezeSimulator3D(model, object_mesh_dir=_object_mesh_dir(args), **squeeze3)
     from ..goal import goal_from_args
     model.goal = goal_from_args(args)       # --goal_pose: the sweep adds a goal objective after the reference's (Diffusion._objective_sweep)
     if model.goal is not None and getattr(args, "predicted_sim", False) and not rollout:

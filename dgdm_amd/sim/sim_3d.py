@@ -1,0 +1,119 @@
+"""Data generation for the 3-D dynamics model (reference: sim/sim_3d.py) with the sliced squeeze in MuJoCo's place.
+
+``generate`` writes one ``<object>_<gripper>.npz`` per pair in the reference's format (sim/sim_3d.py:162-172: ``np.savez_compressed(path,
+dict)`` with the keys and order below) on its 360 x 5 x 5 pose grid, so that ``python dynamics/main.py --fingers_3d`` trains on data made
+here:
+
+    ctrlpts [42, 3], allpts [1250, 3], object_name str, obj_pos [9000, 3], obj_theta [9000] float32,
+    delta_theta [9000] float32 (folded as continuous_signed_delta), delta_pos [9000, 3]
+
+Poses run rotation-major, then x, then y.  The motion is ONE closing of the sliced squeeze (sim/squeeze.py, DESIGN.md §4.1d "3-D form"): a
+frictionless, quasi-static idealisation that compares object and jaws on the finger grid's 25 horizontal planes only - not MuJoCo's
+scene.  The object neither tilts nor lifts (delta_pos z = 0; the reference drops poses whose object fell over, this model has none).
+``stats.json`` beside the files holds the configuration and the standard deviations of the three deltas for ``dynamics/main.py
+--score_stats``.  The dataset reads the object's cloud from ``<object_mesh_dir>/<object_name>/model.obj``.
+"""
+from __future__ import annotations
+
+import os
+import sys
+from typing import List, Sequence
+
+import numpy as np
+
+from .sim_2d import pose_grid, write_dataset
+from .squeeze import FINGER_WIDTH_3D, fold
+
+NUM_CTRL, SAMPLE_SIZE = 21, 25                          # sim/sim_3d.py:73-83
+
+
+def gripper_design(gripper_idx: int):
+    """(yl, yr) of gripper `gripper_idx`, in metres (prepare_gripper, sim/sim_3d.py:73-75)."""
+    rs = np.random.RandomState(int(gripper_idx))
+    yl = rs.uniform(-0.1, 0, size=(NUM_CTRL))
+    yr = rs.uniform(-0.1, 0, size=(NUM_CTRL))
+    return yl, yr
+
+
+def generate(out_dir: str, gripper_ids: Sequence[int], meshes, object_ids: Sequence[int], object_names: Sequence[str], **config) -> List[str]:
+    """Writes ``<out_dir>/<object>_<gripper>.npz`` for every (gripper, object) and ``<out_dir>/stats.json``; returns the data files.
+    meshes: (vertices (nv, 3) in metres, triangles (nt, 3)) per object, object_ids / object_names their numbers and names.  config: the
+    squeeze model's (engine.SQUEEZE_DEFAULTS).  One device call for all pairs."""
+    from .. import engine
+    from ..assets import finger_3d
+    from . import squeeze
+    meshes = list(meshes)
+    if not (len(meshes) == len(object_ids) == len(object_names)):
+        raise ValueError(f"generate: {len(meshes)} meshes for {len(object_ids)} object ids and {len(object_names)} names")
+    designs = [gripper_design(g) for g in gripper_ids]
+    shapes = [finger_3d.generate_3d_gripper(yl, yr, sample_size=SAMPLE_SIZE) for yl, yr in designs]
+    samples = np.stack([np.concatenate([yl, yr]) for yl, yr in designs]).astype(np.float32)
+    starts = pose_grid()
+    out = squeeze.squeeze_map_3d(samples, meshes, starts, sample_size=SAMPLE_SIZE, width=FINGER_WIDTH_3D, scale=1.0, offset=0.0, **config)
+    start, closed = out["start"].cpu().numpy(), out["closed"].cpu().numpy()
+    records = [(int(object_ids[o]), int(gripper_ids[f]), pair_record(*shapes[f], object_names[o], starts, start[p], closed[p]))
+               for p, (f, o) in enumerate(out["pairs"])]
+    return write_dataset(out_dir, records, engine.squeeze_config(**config), int(np.count_nonzero(out["flags"].cpu().numpy() & 1)))
+
+
+def pair_record(ctrlpts, allpts, object_name, starts, start, closed) -> dict:
+    """The dict of one data file, keys in the reference's order (sim/sim_3d.py:162-170).  starts (n, 3): the start poses; start (n, 2): the
+    (theta, x) of the cells they snapped to; closed (n, 3): the pose after one closing.  Host code."""
+    starts, start, closed = (np.asarray(a, dtype=np.float64) for a in (starts, start, closed))
+    zeros = np.zeros(len(starts))
+    return {
+        "ctrlpts": ctrlpts,
+        "allpts": allpts,
+        "object_name": str(object_name),
+        "obj_pos": np.stack([starts[:, 1], starts[:, 2], zeros], axis=1),
+        "obj_theta": starts[:, 0].astype(np.float32),
+        "delta_theta": fold(closed[:, 0] - start[:, 0], 2.0 * np.pi).astype(np.float32),
+        "delta_pos": np.stack([closed[:, 1] - start[:, 1], closed[:, 2] - starts[:, 2], zeros], axis=1),
+    }
+
+
+def object_names_in(object_dir: str, names_file: str = "") -> List[str]:
+    """The objects of a directory of ``<name>/model.obj``: the names listed in `names_file`, one per line, or every sub-directory that
+    holds a mesh - numbered ones (the reference's MODEL_ROOT/objects/<idx>) in numeric order, then the rest by name."""
+    from ..dynamics.utils import MESH_FILE
+    if names_file:
+        with open(names_file) as fh:
+            return [line.strip() for line in fh if line.strip()]
+    names = [n for n in os.listdir(object_dir) if os.path.isfile(os.path.join(object_dir, n, MESH_FILE))]
+    return sorted(names, key=lambda n: (0, int(n), "") if n.isdigit() else (1, 0, n))
+
+
+def main(argv=None):
+    """python sim/sim_3d.py MODEL_ROOT GRIPPER_IDX OBJECT_IDX NUM_GRIPPERS NUM_OBJECTS SAVE_DIR NUM_CPUS: the reference's positional arguments
+    (sim/sim_3d.py:174-181; NUM_CPUS is accepted and unused - no Ray).  The objects are ``<object_dir>/<name>/model.obj``; --object_dir
+    defaults to MODEL_ROOT/objects, where the reference's prepare_object copies them; OBJECT_IDX counts through --object_names (a file
+    of names, one per line) or the directory's listing."""
+    import argparse
+    p = argparse.ArgumentParser(description=main.__doc__)
+    for name, kind in (("model_root", str), ("gripper_idx", int), ("object_idx", int), ("num_gripper_parallel", int), ("num_object_parallel", int),
+                       ("save_dir", str), ("num_cpus", int)):
+        p.add_argument(name, type=kind)
+    p.add_argument("--object_dir", default=None, help="directory of <name>/model.obj (default: MODEL_ROOT/objects)")
+    p.add_argument("--object_names", default="", help="file of object names, one per line (default: the directory's listing)")
+    p.add_argument("--squeeze_closing_steps", type=int, default=None)
+    p.add_argument("--squeeze_window", type=int, default=None)
+    a = p.parse_args(argv)
+    from .. import _lib, engine
+    from ..dynamics.utils import MESH_FILE
+    _lib.device_init(0)
+    object_dir = a.object_dir or os.path.join(a.model_root, "objects")
+    if not os.path.isdir(object_dir):
+        raise ValueError(f"sim_3d: no object directory at {object_dir} (--object_dir)")
+    names = object_names_in(object_dir, a.object_names)
+    object_ids = list(range(a.object_idx, a.object_idx + a.num_object_parallel))
+    if not names or object_ids[-1] >= len(names):
+        raise ValueError(f"sim_3d: objects {object_ids[0]} .. {object_ids[-1]} asked for, {len(names)} found under {object_dir}")
+    meshes = [engine.read_obj(os.path.join(object_dir, names[i], MESH_FILE)) for i in object_ids]
+    config = {k: v for k, v in (("closing_steps", a.squeeze_closing_steps), ("window", a.squeeze_window)) if v is not None}
+    files = generate(a.save_dir, list(range(a.gripper_idx, a.gripper_idx + a.num_gripper_parallel)), meshes, object_ids, [names[i] for i in object_ids],
+                     **config)
+    print(f"[dgdm_amd] wrote {len(files)} files and stats.json to {a.save_dir}")
+
+
+if __name__ == "__main__":
+    main(sys.argv[1:])

@@ -10,6 +10,14 @@ bit.  A jaw that touches alone is assumed to carry the object along y without tu
 * ``SqueezeSimulator``   a callable with the ``sim_test_batch`` signature for ``Diffusion(simulator=...)``: the tables that
                          ``--predicted_sim`` fills with the dynamics model's opinion, filled by this model instead and marked
                          ``'simulated': 'squeeze'`` (never ``'predicted'``).
+
+For 3-D fingers the same model runs sliced (DESIGN.md §4.1d "3-D form"; tests/squeeze3d_oracle.py): object meshes are cut on the finger
+grid's horizontal planes and the 2-D contract applies on each plane; what lies between two planes is not seen, and the object neither
+tilts nor lifts.
+
+* ``finger_surfaces_3d`` designs -> the abscissae, the levels and the two jaw faces on them;
+* ``squeeze_map_3d``     designs x meshes -> ``squeeze_map``'s outputs;
+* ``SqueezeSimulator3D`` the callable with the ``sim_test_batch_3d`` signature (``--squeeze_sim_3d``).
 """
 from __future__ import annotations
 
@@ -140,4 +148,113 @@ class SqueezeSimulator:
         thr = SCORE_THRESHOLD[1]
         metrics = [squeeze_metric(start[p], closed[p], settled[p], flags[p], 0.0, thr) for p in range(len(oidx) * n)]
         none: List[Any] = [None] * (len(oidx) * n)
+        return list(none), metrics, list(none), list(none), list(none), list(none), [[] for _ in none], list(none)
+
+
+# ---------------------------------------------------------------------------------------------------------------- 3-D: a sliced squeeze
+# where the two jaw faces stand at jaw travel 0 in the 3-D scene: the left jaw's body at y = -0.23 (assets/finger_3d.py:126), its mesh the
+# decoded surface y = yl(x, z) and a copy shifted by `width` in y (:38-57, called with width = 0.1 by sim/sim_3d.py:78-84) - the copy is
+# the face that looks at the object, L = yl - 0.23 + width; the right jaw's body at y = +0.23 (:135), its decoded surface itself looking
+# at the object, U = yr + 0.23
+LOWER_OFFSET_3D, UPPER_OFFSET_3D, FINGER_WIDTH_3D = -0.23, 0.23, 0.1
+
+
+def finger_surfaces_3d(samples, sample_size: int = 25, width: float = FINGER_WIDTH_3D, scale: Optional[float] = None, offset: Optional[float] = None):
+    """(B, 42[, 1]) control values -> (gx (mu,), gz (mv,), surfaces (B, 2, mv, mu) float64 on the device), mu = mv = sample_size:
+    L_j[i] = yl(gx_i, gz_j) - 0.23 + width and U_j[i] = yr(gx_i, gz_j) + 0.23 over dgdm_finger_decode_3d's u-major grid, whose x depends
+    on the u index only (cubic, clamped knots: NOT uniform) and whose z on the v index only.  gx / gz: host float64, read off the first
+    finger.  scale / offset default to the sampler's units; 1, 0 takes metres."""
+    import torch
+    from .. import engine
+    kw = {}
+    if scale is not None:
+        kw["scale"] = float(scale)
+    if offset is not None:
+        kw["offset"] = float(offset)
+    dev = torch.device("cuda", torch.cuda.current_device())
+    s = torch.as_tensor(samples).to(dev)
+    n = int(sample_size)
+    pts = engine.finger_decode_3d(s, n, **kw).double().reshape(s.shape[0], 2, n, n, 3)      # [B][finger][u][v][xyz]
+    y = pts[..., 1].transpose(2, 3)                                                           # [B][finger][v][u]
+    surfaces = torch.stack([y[:, 0] + LOWER_OFFSET_3D + float(width), y[:, 1] + UPPER_OFFSET_3D], dim=1).contiguous()
+    return pts[0, 0, :, 0, 0].cpu().numpy().copy(), pts[0, 0, 0, :, 2].cpu().numpy().copy(), surfaces
+
+
+def squeeze_map_3d(samples, meshes, starts, pairs=None, sample_size: int = 25, width: float = FINGER_WIDTH_3D, scale: Optional[float] = None,
+                   offset: Optional[float] = None, tables: bool = False, workspace_bytes: Optional[int] = None, **config) -> Dict[str, Any]:
+    """squeeze_map for 3-D fingers: samples (B, 42[, 1]) designs, meshes a sequence of (vertices (nv, 3) in metres, triangles (nt, 3)) in
+    the scene's frame (standing on z = 0), starts (N, 3) = (theta0 rad, x0 m, y0 m) shared by all pairs.  The meshes are sliced on the
+    finger grid's levels (engine.squeeze_slice) and squeezed level by level (engine.squeeze_tables_3d); what lies between two levels is
+    not seen.  Output keys as squeeze_map, plus segments / offsets."""
+    import torch
+    from .. import engine
+    gx, gz, sf = finger_surfaces_3d(samples, sample_size, width, scale, offset)
+    sl = engine.squeeze_slice(meshes, gz)
+    pr = all_pairs(sf.shape[0], len(sl["offsets"])) if pairs is None else np.ascontiguousarray(pairs, dtype=np.int32).reshape(-1, 2)
+    out = engine.squeeze_tables_3d(sf, gx, sl["segments"], sl["offsets"], pr, starts, tables=tables, workspace_bytes=workspace_bytes, **config)
+    cfg = engine.squeeze_config(**config)
+    T, X = cfg.theta_cells, cfg.x_cells
+    cells = out["cells"].long()
+    theta = (cells // X).double() * (2.0 * np.pi) / float(T)
+    x = -cfg.x_half + (cells % X).double() * (2.0 * cfg.x_half / (X - 1))
+    out["start"] = torch.stack([theta[..., 0], x[..., 0]], dim=-1)
+    out["closed"] = torch.stack([theta[..., 1], x[..., 1], out["y"][..., 0]], dim=-1)
+    out["settled"] = torch.stack([theta[..., 2], x[..., 2], out["y"][..., 1]], dim=-1)
+    out["pairs"] = pr
+    out.update(segments=sl["segments"], offsets=sl["offsets"])
+    return out
+
+
+class SqueezeSimulator3D:
+    """``sim_test_batch_3d`` (dynamics/sim_test_mj_3d.py:229) answered by the sliced squeeze: ``simulator(samples (n, 42, 1), object_names,
+    save_dir, num_cpus=, num_rot=, ori_range=, render=, render_last=)`` -> the same eight lists as ``SqueezeSimulator``, object-major,
+    gripper-minor.  An object name is read from ``<object_mesh_dir>/<name>/model.obj`` (engine.read_obj) as it stands, in metres; a run
+    whose objects have no meshes (objects.npy, synthetic clouds) is refused with a ValueError - a point cloud has no cross-section.
+    Metrics: ``squeeze_metric`` with the 3-D thresholds SCORE_THRESHOLD[0], marked ``'simulated': 'squeeze'`` and never ``'predicted'``."""
+
+    def __init__(self, diffusion, object_mesh_dir: Optional[str] = None, closing_steps: Optional[int] = None, window: Optional[int] = None,
+                 sample_size: int = 25, width: float = FINGER_WIDTH_3D, **config):
+        if getattr(diffusion, "mode", "point_3d") != 'point_3d':
+            raise ValueError("SqueezeSimulator3D: the sliced squeeze is for 3-D fingers (mode 'point_3d'); SqueezeSimulator is the 2-D one")
+        self.diffusion = diffusion
+        self.object_mesh_dir = object_mesh_dir if object_mesh_dir is not None else getattr(diffusion, "object_mesh_dir", None)
+        if not self.object_mesh_dir:
+            raise ValueError("SqueezeSimulator3D: the run's objects have no meshes (objects.npy or synthetic clouds): the sliced squeeze needs "
+                             "<object_dir>/<name>/model.obj")
+        self.sample_size, self.width = int(sample_size), float(width)
+        self.config = dict(config)
+        if closing_steps is not None:
+            self.config["closing_steps"] = int(closing_steps)
+        if window is not None:
+            self.config["window"] = int(window)
+        from .. import engine
+        c = engine.squeeze_config(**self.config)
+        if c.closing_steps < 0 or c.window < 1:
+            raise ValueError(f"SqueezeSimulator3D: closing_steps = {c.closing_steps} (need >= 0), window = {c.window} (need >= 1)")
+        self._meshes: Dict[str, Any] = {}
+
+    def mesh(self, name):
+        import os
+        from .. import engine
+        from ..dynamics.utils import MESH_FILE
+        if name not in self._meshes:
+            path = os.path.join(self.object_mesh_dir, str(name), MESH_FILE)
+            if not os.path.isfile(path):
+                raise ValueError(f"SqueezeSimulator3D: object '{name}' has no mesh at {path}")
+            self._meshes[name] = engine.read_obj(path)
+        return self._meshes[name]
+
+    def __call__(self, samples, object_names, save_dir: Optional[str] = None, num_cpus: int = 32, num_rot: int = 360,
+                 ori_range: Sequence[float] = (-1.0, 1.0), render: bool = True, render_last: bool = False):
+        import torch
+        x = torch.as_tensor(np.asarray(samples), dtype=torch.float32)
+        n = x.shape[0]
+        meshes = [self.mesh(o) for o in object_names]
+        theta0 = (np.linspace(ori_range[0], ori_range[1], int(num_rot)) + 1.0) * np.pi
+        starts = np.stack([theta0, np.zeros_like(theta0), np.zeros_like(theta0)], axis=1)
+        out = squeeze_map_3d(x.reshape(n, -1), meshes, starts, sample_size=self.sample_size, width=self.width, **self.config)
+        start, closed, settled, flags = (out[k].cpu().numpy() for k in ("start", "closed", "settled", "flags"))
+        thr = SCORE_THRESHOLD[0]
+        metrics = [squeeze_metric(start[p], closed[p], settled[p], flags[p], 0.0, thr) for p in range(len(meshes) * n)]
+        none: List[Any] = [None] * (len(meshes) * n)
         return list(none), metrics, list(none), list(none), list(none), list(none), [[] for _ in none], list(none)

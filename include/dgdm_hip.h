@@ -806,6 +806,67 @@ int dgdm_squeeze_map(const DgdmSqueezeConfig *cfg, const double *surfaces_dev, i
                      double *touch_l_dev, double *touch_r_dev, int32_t *succ_dev, void *workspace_dev, int64_t workspace_bytes,
                      void *stream);
 
+/* ------------------------------------------------------------------ squeeze simulator, 3-D fingers: a sliced squeeze (csrc/squeeze.hip,
+ * DESIGN.md §4.1d "3-D form")
+ * The same model for the 3-D scene (assets/finger_3d.py:110-177, sim/sim_3d.py:127-158): the object stands on a plane, is turned about z
+ * and placed in x; two jaws close along y; a jaw's face is a surface over (x, z).  Like the 2-D form it is this project's own
+ * idealisation, pinned to nothing in MuJoCo and claiming nothing about it; tests/squeeze3d_oracle.py restates it in numpy float64 and the
+ * device reproduces that bit for bit.  All arithmetic is float64; every product, sum and quotient below is rounded on its own, in the
+ * order written; no transcendental function is evaluated on the device.
+ *
+ * Model.  Object and jaws are compared on the mv horizontal planes z = gz[j] only.  On each plane the 2-D contract applies unchanged:
+ *   the object is the cross-section of its mesh there, an unordered soup of segments; the jaws are that level's two profiles,
+ *   piecewise linear on the abscissae gx[0 .. mu - 1] (strictly ascending, NOT uniform).  A cell's touch_l / touch_r is the least gap
+ *   over all levels.  Known limit: what lies between two levels (5 mm for a 25 x 25 finger grid over 0.12 m) is not seen - a ledge,
+ *   rim or tip that falls between two planes does not touch, and the jaws' faces between their own sample rows do not either.  This
+ *   is the model's stated resolution, not an error bound.  The object does not tilt, lift or slide in z.
+ *
+ * dgdm_squeeze_slice.  n_objects meshes, HOST memory: verts_host [sum nv][3] float64 in metres, tris_host [sum nt][3] int32 indexing
+ *   their own mesh's vertices from 0, vert_offsets_host / tri_offsets_host [n_objects + 1] int64 (first 0, ascending); gz_host [mv]
+ *   strictly ascending.  They are uploaded; the slicing runs on the device in three passes (count, scan, emit).
+ *   1. vertex i is UP at level j iff V_iz >= gz_j;  2. triangle t crosses level j iff its vertices are neither all up nor all down;
+ *   3. a crossing triangle has exactly two edges whose ends differ.  For such an edge, D = its down end and W = its up end, whichever
+ *      way the triangle lists them (so the two triangles that share an edge make identical bits):
+ *        r = (gz_j - D_z) / (W_z - D_z),  point = (D_x + r (W_x - D_x), D_y + r (W_y - D_y));
+ *   4. the segment is (first point, second point) in the triangle's edge order (v0 v1, v1 v2, v2 v0);
+ *   5. segments_dev [n][4] = (A_x, A_y, B_x, B_y), listed by (object, level, triangle index ascending);  seg_offsets_host
+ *      [n_objects][mv + 1] int32, HOST: level j of object o is segments seg_offsets[o][j] .. seg_offsets[o][j + 1] - 1 of the one
+ *      list, seg_offsets[o][mv] = seg_offsets[o + 1][0];
+ *   6. a vertex exactly on a level gives zero-length or touching segments.  They stay: set A handles them, set B skips P_x == Q_x.
+ *   *n_segments_host receives the number of segments.  segments_dev == null with capacity 0 counts only (DGDM_OK).  A capacity smaller
+ *   than the count returns DGDM_EINVAL after the count pass, with the count needed in *n_segments_host and nothing emitted.
+ *   Validated before any launch (DGDM_EINVAL): null pointers, n_objects outside 1 .. 65535, mv outside 1 .. 1024, gz not strictly ascending or
+ *   non-finite, offsets not starting at 0 or descending, a mesh with no vertex, a non-finite vertex, a triangle index outside its
+ *   mesh, more than 2^31 - 1 vertices or triangles in all.  Synchronises the stream.
+ *
+ * dgdm_squeeze_map_3d.  surfaces_dev [n_fingers][2][mv][mu]: the lower (L) and upper (U) jaw face in the world frame at jaw travel 0,
+ *   L_j[i] at (gx_i, gz_j).  gx_host [mu], HOST.  segments_dev / seg_offsets_host as dgdm_squeeze_slice made them for the same gz
+ *   (finite coordinates).  pairs_host [n_pairs][2] = (finger, object), HOST.  rot_dev, starts_dev and cfg as dgdm_squeeze_map;
+ *   cfg->finger_half_len is checked as there and is otherwise UNUSED here (gx says where the samples are).
+ *   Cell (a, b), level j, segment (A, B) of that level:  P = (c A_x - s A_y + x_b, s A_x + c A_y), Q likewise from B.
+ *   A  for each of P and Q with gx_0 <= P_x <= gx_{mu-1}:  i = the greatest index with gx_i <= P_x, capped at mu - 2;
+ *      f = (P_x - gx_i) / (gx_{i+1} - gx_i);  Lp = L_j[i] + f (L_j[i+1] - L_j[i]), Up likewise;  gaps P_y - Lp and Up - P_y.  Only
+ *      comparisons choose i, so any search gives the same bits;
+ *   B  if P_x != Q_x:  slope = (Q_y - P_y) / (Q_x - P_x);  for every i with min(P_x, Q_x) <= gx_i <= max(P_x, Q_x):
+ *      ye = P_y + (gx_i - P_x) slope;  gaps ye - L_j[i] and U_j[i] - ye.
+ *   touch_l / touch_r = the least lower / upper gap over levels and segments, +inf when there is none;  S = (touch_l + touch_r) / 2.
+ *   Everything after S - successors, one closing, settled, snap, y, flags, the outputs and the chunking - is dgdm_squeeze_map's
+ *   contract verbatim.
+ *   Validated before any launch (DGDM_EINVAL): cfg as dgdm_squeeze_map, null required pointers, mu outside 2 .. 128, mv outside
+ *   1 .. 512, mu mv > 1024 (the pair's 2 mv mu surface doubles stay in 16 KB of LDS), gx not strictly ascending or non-finite,
+ *   seg_offsets not starting at 0, descending or passing n_segments, a pair index out of range, n_fingers / n_pairs < 1, n_objects outside 1 .. 2^20,
+ *   a workspace too small for one pair (dgdm_squeeze_map_3d_workspace_bytes).  Synchronises the stream once, at the end.                */
+int dgdm_squeeze_slice(const double *verts_host, const int64_t *vert_offsets_host, const int32_t *tris_host, const int64_t *tri_offsets_host,
+                       int n_objects, const double *gz_host, int mv, double *segments_dev, int64_t capacity, int32_t *seg_offsets_host,
+                       int64_t *n_segments_host, void *stream);
+/* Bytes of device workspace for chunks of chunk_pairs pairs; negative: bad config or sizes. */
+int64_t dgdm_squeeze_map_3d_workspace_bytes(const DgdmSqueezeConfig *cfg, int chunk_pairs, int mu, int mv, int n_objects);
+int dgdm_squeeze_map_3d(const DgdmSqueezeConfig *cfg, const double *surfaces_dev, int n_fingers, const double *gx_host, int mu, int mv,
+                        const double *segments_dev, int64_t n_segments, const int32_t *seg_offsets_host, int n_objects,
+                        const int32_t *pairs_host, int n_pairs, const double *rot_dev, const double *starts_dev, int n_starts,
+                        int32_t *cells_dev, double *y_dev, int32_t *flags_dev, double *table_s_dev, double *touch_l_dev,
+                        double *touch_r_dev, int32_t *succ_dev, void *workspace_dev, int64_t workspace_bytes, void *stream);
+
 /* ------------------------------------------------------------------ measurement hooks
  * When enabled, the launches of every stage of the path are bracketed by hipEvents on the stream they are launched on.
  * dgdm_prof_read_stage synchronises those events and returns, for one stage, the number of bracketed regions, their total
