@@ -78,6 +78,7 @@ PROTOTYPES = {
                                               C.c_int64, C.c_float, _P, C.c_uint64, _P, C.c_int64, C.c_int64, _P]),
     "dgdm_ddim_step_noise": (C.c_int, [C.c_uint64, _P, C.c_int, C.c_int64, C.c_int64, _P, _P]),
     "dgdm_ddim_add_noise": (C.c_int, [_P, _P, _P, C.c_int64, C.c_float, C.c_float, _P]),
+    "dgdm_ddim_pred_x0": (C.c_int, [_P, _P, _P, C.c_int64, C.c_float, C.c_float, _P]),
     "dgdm_dynamics_create": (C.c_int, [C.POINTER(_P), C.c_int, C.POINTER(Tensor), C.c_int, C.c_int, C.c_int]),
     "dgdm_dynamics_destroy": (None, [_P]),
     "dgdm_dyn2d_forward": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, C.c_int, _P]),
@@ -205,6 +206,8 @@ PROTOTYPES = {
     "dgdm_squeeze_workspace_bytes": (C.c_int64, [C.POINTER(SqueezeConfig), C.c_int]),
     "dgdm_squeeze_map": (C.c_int, [C.POINTER(SqueezeConfig), _P, C.c_int, C.c_int, _P, C.c_int, C.c_int, _P, C.c_int, _P, _P, C.c_int, _P, _P, _P, _P,
                                    _P, _P, _P, _P, C.c_int64, _P]),
+    "dgdm_squeeze_objective_values": (C.c_int, [C.POINTER(SqueezeConfig), _P, _P, _P, C.c_int, C.c_int, C.c_int, C.POINTER(Objective), _P,
+                                                C.POINTER(C.c_double), _P, _P]),
     "dgdm_squeeze_slice": (C.c_int, [_P, _P, _P, _P, C.c_int, _P, C.c_int, _P, C.c_int64, _P, C.POINTER(C.c_int64), _P]),
     "dgdm_squeeze_map_3d_workspace_bytes": (C.c_int64, [C.POINTER(SqueezeConfig), C.c_int, C.c_int, C.c_int, C.c_int]),
     "dgdm_squeeze_map_3d": (C.c_int, [C.POINTER(SqueezeConfig), _P, C.c_int, _P, C.c_int, C.c_int, _P, C.c_int64, _P, C.c_int, _P, C.c_int, _P, _P,

@@ -463,6 +463,12 @@ __global__ void add_noise_kernel(const float *__restrict__ x0, const float *__re
     if (i < n) out[i] = add_rn(mul_rn(sa, x0[i]), mul_rn(sb, noise[i]));
 }
 
+// The predicted clean sample ddim_step_kernel forms, on its own: the unguided eps, the [-1, 1] clip, the same helpers in the same order.
+__global__ void pred_x0_kernel(const float *__restrict__ x, const float *__restrict__ eps, float *__restrict__ out, int64_t n, float sa, float sb) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) out[i] = fminf(fmaxf(__fdiv_rn(sub_rn(x[i], mul_rn(sb, eps[i])), sa), -1.f), 1.f);
+}
+
 }  // namespace dgdm
 
 // lo_dev == nullptr: the plain step; nz == nullptr or sigma == 0: the eta = 0 instantiations.  bytes: what prof_end books for the stage.
@@ -549,6 +555,16 @@ extern "C" int dgdm_ddim_add_noise(const float *x0_dev, const float *noise_dev, 
     if (n == 0) return DGDM_OK;
     hipLaunchKernelGGL(dgdm::add_noise_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, x0_dev, noise_dev,
                        out_dev, n, sqrt_abar, sqrt_1m_abar);
+    DGDM_HIP_CHECK(hipGetLastError());
+    return DGDM_OK;
+}
+
+extern "C" int dgdm_ddim_pred_x0(const float *x_dev, const float *eps_dev, float *out_dev, int64_t n, float sqrt_abar_t, float sqrt_1m_abar_t,
+                                 void *stream) {
+    DGDM_REQUIRE(x_dev && eps_dev && out_dev && n >= 0, DGDM_EINVAL, "dgdm_ddim_pred_x0: null argument");
+    if (n == 0) return DGDM_OK;
+    hipLaunchKernelGGL(dgdm::pred_x0_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, x_dev, eps_dev, out_dev, n,
+                       sqrt_abar_t, sqrt_1m_abar_t);
     DGDM_HIP_CHECK(hipGetLastError());
     return DGDM_OK;
 }

@@ -180,6 +180,45 @@ __global__ void lookup_kernel(Grid g, const double *starts, int n_starts, const 
     flags_out[r] = (S[o + c0] >= g.travel_max ? 1 : 0) | (S[o + cf] >= g.travel_max ? 2 : 0) | ((bf == 0 || bf == g.X - 1) ? 4 : 0);
 }
 
+// The objective's value of every pair from its map (include/dgdm_hip.h, dgdm_squeeze_objective_values): one wave per pair, every lane its
+// own starts in ascending order, an xor butterfly across the wave, lane 0 stores - the fixed shape of resample.hip's
+// objective_values_kernel, the same bits run to run.  The cells are only taken apart, never used as an index.
+struct ValueGrid {
+    int T, X, n_starts, B;
+    double dth, dx, std0, std1, std2;
+};
+
+__global__ __launch_bounds__(64) void squeeze_values_kernel(ValueGrid g, const int32_t *__restrict__ cells, const double *__restrict__ y,
+                                                            const double *__restrict__ starts, const DgdmObjective *__restrict__ obj,
+                                                            const float *__restrict__ rowcoef, double *__restrict__ values) {
+    const int lane = threadIdx.x;
+    const int64_t p = blockIdx.x;
+    const int64_t group = p / g.B;
+    const int b = (int)(p - group * g.B);
+    const DgdmObjective o = obj[group];
+    double lin[3], quad[3];
+#pragma unroll
+    for (int j = 0; j < 3; ++j) { lin[j] = (double)o.lin[j]; quad[j] = (double)o.quad[j]; }
+    double v = 0.0;
+    for (int n = lane; n < g.n_starts; n += 64) {
+        const int64_t r = p * g.n_starts + n;
+        const int c0 = cells[3 * r], c1 = cells[3 * r + 1];
+        const int a0 = c0 / g.X, b0 = c0 % g.X, a1 = c1 / g.X, b1 = c1 % g.X;
+        int64_t da = (int64_t)a1 - a0;
+        if (2 * da > g.T) da -= g.T;                                      // squeeze.fold's strict rule: +-T / 2 stays
+        if (2 * da < -(int64_t)g.T) da += g.T;
+        const double d0 = ((double)da * g.dth) / g.std0;
+        const double d1 = ((double)(b1 - b0) * g.dx) / g.std1;
+        const double d2 = (y[2 * r] - starts[3 * n + 2]) / g.std2;
+        double t = ((lin[0] * d0 + quad[0] * (d0 * d0)) + (lin[1] * d1 + quad[1] * (d1 * d1))) + (lin[2] * d2 + quad[2] * (d2 * d2));
+        if (o.use_rowcoef == 1) t += (double)rowcoef[(group * g.n_starts + n) * g.B + b] * d0;
+        v += t;
+    }
+#pragma unroll
+    for (int s = 32; s > 0; s >>= 1) v += __shfl_xor(v, s);
+    if (lane == 0) values[p] = v;
+}
+
 inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 
 // workspace of a chunk of n pairs: [pairs | touch_l | touch_r | S | succ | ping | pong | kth]
@@ -540,6 +579,38 @@ extern "C" int dgdm_squeeze_map(const DgdmSqueezeConfig *cfg, const double *surf
                           hipLaunchKernelGGL(table_kernel, dim3((unsigned)g.T, n), dim3(TABLE_THREADS), lds, s, g, surfaces_dev, objects_dev, pairs,
                                              rot_dev, tl, tr, S);
                       });
+}
+
+extern "C" int dgdm_squeeze_objective_values(const DgdmSqueezeConfig *cfg, const int32_t *cells_dev, const double *y_dev, const double *starts_dev,
+                                             int n_pairs, int n_starts, int B, const DgdmObjective *objectives_host, const float *rowcoef_dev,
+                                             const double score_std[3], double *values_dev, void *stream) {
+    const char *fn = "dgdm_squeeze_objective_values";
+    int rc = check_config(cfg, fn);
+    if (rc) return rc;
+    DGDM_REQUIRE(cells_dev && y_dev && starts_dev && objectives_host && score_std && values_dev, DGDM_EINVAL, "%s: null argument", fn);
+    DGDM_REQUIRE(B >= 1 && n_starts >= 1 && n_pairs >= 0 && n_pairs % B == 0, DGDM_EINVAL,
+                 "%s: %d pairs of %d starts in groups of %d (need B >= 1, n_starts >= 1, whole groups)", fn, n_pairs, n_starts, B);
+    for (int j = 0; j < 3; ++j)
+        DGDM_REQUIRE(std::isfinite(score_std[j]) && score_std[j] > 0.0, DGDM_EINVAL, "%s: score_std[%d] = %g (need finite, > 0)", fn, j, score_std[j]);
+    const int groups = n_pairs / B;
+    for (int i = 0; i < groups; ++i) {
+        const int u = objectives_host[i].use_rowcoef;
+        DGDM_REQUIRE(u != DGDM_OBJ_ROWFIELD, DGDM_EINVAL, "%s: objective %d reads a row field; goal fields have no squeeze form", fn, i);
+        DGDM_REQUIRE(u == 0 || u == 1, DGDM_EINVAL, "%s: objective %d has use_rowcoef %d", fn, i, u);
+        DGDM_REQUIRE(u == 0 || rowcoef_dev, DGDM_EINVAL, "%s: objective %d uses rowcoef, rowcoef_dev is null", fn, i);
+    }
+    if (n_pairs == 0) return DGDM_OK;
+    hipStream_t s = (hipStream_t)stream;
+    DevBuf obj;
+    if ((rc = obj.alloc(sizeof(DgdmObjective) * (size_t)groups))) return rc;
+    DGDM_HIP_CHECK(hipMemcpyAsync(obj.p, objectives_host, sizeof(DgdmObjective) * (size_t)groups, hipMemcpyHostToDevice, s));
+    const Grid g = grid_of(cfg);
+    const ValueGrid vg = {g.T, g.X, n_starts, B, TWO_PI / (double)g.T, g.dx, score_std[0], score_std[1], score_std[2]};
+    hipLaunchKernelGGL(squeeze_values_kernel, dim3((unsigned)n_pairs), dim3(64), 0, s, vg, cells_dev, y_dev, starts_dev, obj.as<DgdmObjective>(),
+                       rowcoef_dev, values_dev);
+    DGDM_HIP_CHECK(hipGetLastError());
+    DGDM_HIP_CHECK(hipStreamSynchronize(s));        // the objectives' host array and their device copy belong to this call
+    return DGDM_OK;
 }
 
 extern "C" int dgdm_squeeze_slice(const double *verts_host, const int64_t *vert_offsets_host, const int32_t *tris_host,

@@ -97,6 +97,11 @@ _FLAGS = [
     ("resample_beta", float, None, "with --resample_every: inverse temperature of the weights, per grid cell of a finger (untuned; 0 never resamples)"),
     ("resample_ess", float, None, "with --resample_every: resample when the effective sample size falls below this fraction of the fingers "
                                   "(default 0.5; above 1: at every evaluation)"),
+    ("resample_potential", str, "model", "with --resample_every: whose objective weighs the fingers - 'model' (the dynamics model's at (x_t, t)) or "
+                                         "'squeeze' (the squeeze simulator's on the predicted clean design: 2-D only, frictionless, this project's "
+                                         "own mechanism, not MuJoCo's; honours --squeeze_closing_steps / --squeeze_window)"),
+    ("resample_squeeze_cells", str, None, "with --resample_potential squeeze: the squeeze table's theta,x cells as T,X (default: the squeeze defaults, "
+                                          "720,241)"),
     ("device_dataset", "flag", None, "dynamics training: read every data file once, keep the dataset on the GPU and build each batch's rows there "
                                      "(dynamics/device_dataset.py); same batches, draws and results as the host loop"),
 ]

@@ -722,6 +722,23 @@ def ddim_add_noise(x0: torch.Tensor, noise: torch.Tensor, sqrt_abar: float, sqrt
     return out
 
 
+def ddim_pred_x0(x: torch.Tensor, eps: torch.Tensor, coef: Sequence[float]) -> torch.Tensor:
+    """The predicted clean sample of a DDIM step on its own (dgdm_ddim_pred_x0): clip((x - coef[1] eps) / coef[0], -1, 1) in the step's
+    float32 operations, coef = DDIMScheduler.coefficients(t)[:2] = (sqrt(abar_t), sqrt(1 - abar_t)).  x, eps: float32 device tensors of one
+    shape (ValueError otherwise)."""
+    for name, t in (("x", x), ("eps", eps)):
+        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32):
+            raise ValueError(f"ddim_pred_x0: {name} is a float32 device tensor, got {getattr(t, 'dtype', type(t).__name__)}")
+    if x.shape != eps.shape:
+        raise ValueError(f"ddim_pred_x0: x {tuple(x.shape)} and eps {tuple(eps.shape)} differ in shape")
+    if len(coef) < 2:
+        raise ValueError("ddim_pred_x0: coef holds sqrt(abar_t) and sqrt(1 - abar_t)")
+    x, eps = x.contiguous(), eps.contiguous()
+    out = torch.empty_like(x)
+    check(lib().dgdm_ddim_pred_x0(dptr(x), dptr(eps), dptr(out), x.numel(), float(coef[0]), float(coef[1]), stream_ptr()))
+    return out
+
+
 def finger_decode_2d(samples: torch.Tensor, num_points: int = 200, scale: float = 0.03, offset: float = -0.015) -> torch.Tensor:
     """(B, L, 1) or (B, L) control values -> (B, 2 fingers, num_points, 2) spline points in metres; the defaults map sampler
     units [-1, 1] as dynamics/sim_test_mj.py:257-262 does before assets/finger_sampler.py:39-51."""
@@ -1143,6 +1160,44 @@ def squeeze_tables(surfaces, objects, pairs, starts=None, rot=None, tables: bool
                                         pr.ctypes.data, P, dptr(rt), dptr(st), N, dptr(out["cells"]), dptr(out["y"]), dptr(out["flags"]),
                                         dptr(out.get("S")), dptr(out.get("touch_l")), dptr(out.get("touch_r")), dptr(out.get("succ")), dptr(ws),
                                         ws_bytes, stream_ptr()))
+    return out
+
+
+def squeeze_objective_values(cells: torch.Tensor, y: torch.Tensor, starts: torch.Tensor, batch: int, objectives: Sequence[_lib.Objective],
+                             rowcoef: Optional[torch.Tensor] = None, score_std: Optional[Sequence[float]] = None, **config) -> torch.Tensor:
+    """The objectives' VALUES per pair from a squeeze map (include/dgdm_hip.h, dgdm_squeeze_objective_values): cells
+    (P, N, 3) int32 and y (P, N, 2) float64 as squeeze_tables returns them, starts (N, 3) float64 on the device, pair p being finger
+    p % batch of group p // batch; objectives: one per group; rowcoef (P // batch, N * batch) float32 or None, row n * batch + b as the
+    guidance handle lays it out; score_std: (theta rad, x m, y m), the 2-D SCORE_STD by default; config: the map's (theta_cells, x_cells
+    and x_half are read) -> (P // batch, batch) float64.  Shapes and dtypes are checked here, the rest by the library (ValueError)."""
+    cfg = squeeze_config(**config)
+    B = int(batch)
+    if score_std is None:
+        from .dynamics.dataloader import SCORE_STD
+        score_std = SCORE_STD[1]
+    if not (isinstance(cells, torch.Tensor) and cells.is_cuda and cells.dtype == torch.int32 and cells.dim() == 3 and cells.shape[2] == 3):
+        raise ValueError(f"squeeze_objective_values: int32 device cells (P, N, 3) expected, got {tuple(getattr(cells, 'shape', ()))}")
+    P, N = int(cells.shape[0]), int(cells.shape[1])
+    if not (isinstance(y, torch.Tensor) and y.is_cuda and y.dtype == torch.float64 and tuple(y.shape) == (P, N, 2)):
+        raise ValueError(f"squeeze_objective_values: float64 device y ({P}, {N}, 2) expected, got {tuple(getattr(y, 'shape', ()))}")
+    if not (isinstance(starts, torch.Tensor) and starts.is_cuda and starts.dtype == torch.float64 and tuple(starts.shape) == (N, 3)):
+        raise ValueError(f"squeeze_objective_values: float64 device starts ({N}, 3) expected, got {tuple(getattr(starts, 'shape', ()))}")
+    if B < 1 or P % B or len(objectives) != P // B:
+        raise ValueError(f"squeeze_objective_values: {P} pairs in groups of {B} with {len(objectives)} objectives")
+    rc = None
+    if rowcoef is not None:
+        if not (rowcoef.is_cuda and rowcoef.dtype == torch.float32 and rowcoef.numel() == (P // B) * N * B):
+            raise ValueError(f"squeeze_objective_values: float32 device rowcoef of {P // B} x {N * B} entries expected, got "
+                             f"{tuple(rowcoef.shape)} {rowcoef.dtype}")
+        rc = rowcoef.contiguous()
+    if len(score_std) != 3:
+        raise ValueError("squeeze_objective_values: score_std holds three entries (theta, x, y)")
+    cells, y, starts = cells.contiguous(), y.contiguous(), starts.contiguous()
+    arr = (_lib.Objective * max(P // B, 1))(*objectives)
+    std = (C.c_double * 3)(*[float(v) for v in score_std])
+    out = torch.empty((P // B, B), dtype=torch.float64, device=cells.device)
+    _check_value(lib().dgdm_squeeze_objective_values(C.byref(cfg), dptr(cells), dptr(y), dptr(starts), P, N, B, arr, dptr(rc), std, dptr(out),
+                                                     stream_ptr()))
     return out
 
 

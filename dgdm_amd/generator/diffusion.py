@@ -679,6 +679,8 @@ class Diffusion(nn.Module):
             if getattr(self, "resample", None) is not None:
                 # per sampler key ("guided/<objective>", "multi/<objective>") one entry per chain: evaluations, resamples, ess_min, distinct_min
                 out["resample"] = dict(self.last_resample)
+                if getattr(self.resample, "potential", 'model') != 'model':     # whose opinion weighed the fingers, when not the dynamics model's
+                    out["resample"]["potential"] = self.resample.potential
         return out
 
     def _cond_target_report(self, unguided, B: int, rank0: bool) -> Dict[str, Any]:

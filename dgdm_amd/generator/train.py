@@ -382,8 +382,10 @@ def squeeze_from_args(args):
     checks only."""
     k, r = getattr(args, "squeeze_closing_steps", None), getattr(args, "squeeze_window", None)
     if not getattr(args, "squeeze_sim", False):
-        if (k is not None or r is not None) and not getattr(args, "squeeze_sim_3d", False):
-            raise ValueError("--squeeze_closing_steps / --squeeze_window need --squeeze_sim (or, with --fingers_3d, --squeeze_sim_3d)")
+        if (k is not None or r is not None) and not getattr(args, "squeeze_sim_3d", False) and \
+                (getattr(args, "resample_potential", None) or 'model') != 'squeeze':
+            raise ValueError("--squeeze_closing_steps / --squeeze_window need --squeeze_sim (or, with --fingers_3d, --squeeze_sim_3d), or "
+                             "--resample_potential squeeze")
         return None
     if getattr(args, "squeeze_sim_3d", False):
         raise ValueError("--squeeze_sim and --squeeze_sim_3d: choose one (--squeeze_sim is 2-D only, --squeeze_sim_3d is for --fingers_3d)")
@@ -473,6 +475,13 @@ def train(args):
     model.shared_step_noise = bool(getattr(args, "shared_step_noise", False))
     model.save_meshes = bool(getattr(args, "save_meshes", False))
     model.edit_plan = edit_plan
+    from ..resample import squeeze_potential_from_args
+    potential = squeeze_potential_from_args(args)       # --resample_potential squeeze: the fingers weighed by the squeeze model
+    if resample is not None and potential is not None:
+        from ..resample import with_squeeze
+        from ..sim.squeeze import OBJECT_HALF_BOX_2D
+        bank = torch.as_tensor(objects).detach().cpu().double() * OBJECT_HALF_BOX_2D      # the bank SqueezeSimulator builds, in the handle's order
+        resample = with_squeeze(resample, bank.numpy(), **potential)
     model.resample = resample
     model.cfg_weight, model.cond_drop_prob, model.global_cond_rows = float(args.cfg_weight), float(args.cond_drop_prob), cond
     if getattr(args, "save_objects", False):

@@ -5,19 +5,111 @@ gradient already guides the chain - the dynamics model's objective at (x_t, t), 
 weights have degenerated the promising fingers are copied over the poor ones (systematic resampling); the keyed step noise parts the
 copies again.  The mechanism is this project's own: the reference has no counterpart, `beta` is untuned, and nothing here shows that it
 improves an objective on real checkpoints.  The device recipe is in include/dgdm_hip.h (dgdm_chain_resample); the loop that applies it
-is sampler.run_chains."""
+is sampler.run_chains.
+
+A second potential, potential='squeeze' (SqueezePotential): the squeeze simulator's objective on every finger's predicted
+clean design, over the same pose grid and in the same units - an opinion that does not come from the model whose gradient guides the
+chain.  Everything after the values is the same.  Equally this project's own: 2-D only, frictionless, no claim that it improves an
+objective under MuJoCo or on real checkpoints."""
 from __future__ import annotations
 
 import math
 from typing import Any, Dict, List, Optional, Sequence
 
 
+POTENTIALS = ('model', 'squeeze')
+
+
+def start_grid(grid_size: int, num_pos: int, ori_range: Sequence[float]):
+    """The cells of cond_fn's pose grid (generator/diffusion.py:478) as squeeze starts, (G P^2, 3) float64 = (theta0 rad, x0 m, y0 m) in
+    the grid's order n = (io * P + ix) * P + iy: theta0 = (linspace(ori_lo, ori_hi, G)[io] + 1) * pi, x0 = POS_NORM * linspace(-1, 1, P)[ix],
+    y0 likewise - the model's inputs in the simulator's units."""
+    import numpy as np
+    from .dynamics.dataloader import POS_NORM
+    G, P = int(grid_size), int(num_pos)
+    theta = (np.linspace(float(ori_range[0]), float(ori_range[1]), G) + 1.0) * np.pi
+    pos = POS_NORM * np.linspace(-1.0, 1.0, P)
+    io, ix, iy = np.meshgrid(np.arange(G), np.arange(P), np.arange(P), indexing="ij")
+    return np.ascontiguousarray(np.stack([theta[io], pos[ix], pos[iy]], axis=-1).reshape(G * P * P, 3))
+
+
+class SqueezePotential:
+    """The squeeze simulator's opinion of a predicted clean design: the objective's value per finger from one
+    closing of the chain's object by the finger, over the starts of cond_fn's pose grid, in the units of the dynamics model's outputs -
+    a potential for Resample that does not come from the model whose gradient guides the chain.  This project's own mechanism: the
+    reference has no counterpart; 2-D only, frictionless, and nothing here shows that it improves an objective under MuJoCo or on real
+    checkpoints.
+
+    contours (O, nv, 2) float64, metres: the object bank in the guidance handle's object order.  score_std: (theta rad, x m, y m), the
+    2-D SCORE_STD by default.  squeeze_config: engine.SQUEEZE_DEFAULTS' keys.  The rotation table, the bank and the start grid stay on
+    the device between evaluations."""
+
+    def __init__(self, contours, score_std=None, num_points: int = 200, **squeeze_config):
+        import numpy as np
+        from .dynamics.dataloader import SCORE_STD
+        c = np.ascontiguousarray(np.asarray(contours, dtype=np.float64))
+        if c.ndim != 3 or c.shape[2] != 2 or c.shape[0] < 1 or c.shape[1] < 3:
+            raise ValueError(f"SqueezePotential: contours (O, nv, 2) with O >= 1, nv >= 3 expected, got {c.shape}")
+        std = np.asarray(SCORE_STD[1] if score_std is None else score_std, dtype=np.float64).reshape(-1)
+        if std.shape != (3,) or not (np.isfinite(std).all() and (std > 0).all()):
+            raise ValueError(f"SqueezePotential: score_std {std.tolist()} is not three finite positive numbers")
+        unknown = set(squeeze_config) - {"theta_cells", "x_cells", "x_half", "window", "closing_steps", "travel_max", "finger_half_len"}
+        if unknown:
+            raise ValueError(f"SqueezePotential: unknown squeeze_config keys {sorted(unknown)}")
+        self.contours, self.score_std, self.num_points, self.config = c, tuple(float(v) for v in std), int(num_points), dict(squeeze_config)
+        self._bank = self._rot = None
+        self._starts: Dict[Any, Any] = {}
+
+    @property
+    def n_objects(self) -> int:
+        return int(self.contours.shape[0])
+
+    def __repr__(self) -> str:
+        return f"SqueezePotential({self.n_objects} contours of {self.contours.shape[1]} vertices, {self.config})"
+
+    def starts(self, grid_size: int, num_pos: int, ori_range: Sequence[float]):
+        """start_grid on the device, made once per grid."""
+        import torch
+        key = (int(grid_size), int(num_pos), float(ori_range[0]), float(ori_range[1]))
+        if key not in self._starts:
+            self._starts[key] = torch.from_numpy(start_grid(*key[:2], key[2:])).to(torch.device("cuda", torch.cuda.current_device()))
+        return self._starts[key]
+
+    def values(self, x0, objectives: Sequence, rowcoef, n_grad: int, grid_size: int, num_pos: int, ori_range: Sequence[float]):
+        """x0 (nc, B, L) float32 on the device: predicted clean designs in sampler units; objectives [n_grad * nc], object-major as
+        run_chains holds them, rowcoef (n_grad * nc, G P^2 B) or None -> (n_grad * nc, B) float64 as engine.chain_resample takes them.
+        Pair (j * nc + k) * B + b = (finger k * B + b, objectives[j * nc + k].object).  One squeeze map, one values launch."""
+        import numpy as np
+        import torch
+        from . import engine
+        from .sim.squeeze import finger_surfaces
+        nc, B, L = x0.shape
+        n_grad = int(n_grad)
+        if len(objectives) != n_grad * nc:
+            raise ValueError(f"SqueezePotential.values: {len(objectives)} objectives for {n_grad} x {nc} chains")
+        obj = np.array([int(o.object) for o in objectives], dtype=np.int32)
+        if obj.min() < 0 or obj.max() >= self.n_objects:
+            raise ValueError(f"SqueezePotential.values: an objective names object {int(obj.max())} of a bank of {self.n_objects}")
+        dev = x0.device
+        if self._bank is None:
+            self._bank = torch.from_numpy(self.contours).to(dev)
+            self._rot = torch.from_numpy(engine.squeeze_rotation_table(engine.squeeze_config(**self.config).theta_cells)).to(dev)
+        st = self.starts(grid_size, num_pos, ori_range)
+        sf = finger_surfaces(x0.reshape(nc * B, L), self.num_points)
+        finger = (np.arange(nc, dtype=np.int32)[None, :, None] * B + np.arange(B, dtype=np.int32)[None, None, :]).repeat(n_grad, axis=0)
+        pairs = np.stack([finger.reshape(-1), np.repeat(obj, B)], axis=1)
+        out = engine.squeeze_tables(sf, self._bank, pairs, st, rot=self._rot, **self.config)
+        return engine.squeeze_objective_values(out["cells"], out["y"], st, B, list(objectives), rowcoef, self.score_std, **self.config)
+
+
 class Resample:
     """every: evaluate after every `every`-th DDIM step (never after the last one).  beta: the inverse temperature of the weights,
     exp(beta * mean objective per grid cell), relative to the previous evaluation; 0 weighs all fingers alike and never resamples.
-    ess_frac: resample when the effective sample size falls below ess_frac * B; above 1: whenever evaluated."""
+    ess_frac: resample when the effective sample size falls below ess_frac * B; above 1: whenever evaluated.
+    potential: whose objective weighs the fingers - 'model': the dynamics model's at (x_t, t), the quantity whose gradient guides the
+    chain; 'squeeze': the squeeze simulator's on the predicted clean design (`squeeze`: a SqueezePotential), a second opinion."""
 
-    def __init__(self, every: int, beta: float, ess_frac: float = 0.5):
+    def __init__(self, every: int, beta: float, ess_frac: float = 0.5, potential: str = 'model', squeeze: Optional[SqueezePotential] = None):
         if isinstance(every, bool) or int(every) != every or int(every) < 1:
             raise ValueError(f"Resample: every {every!r} is not a positive integer")
         beta, ess_frac = float(beta), float(ess_frac)
@@ -25,10 +117,17 @@ class Resample:
             raise ValueError(f"Resample: beta {beta!r} is not a finite non-negative number")
         if not ess_frac > 0.0:
             raise ValueError(f"Resample: ess_frac {ess_frac!r} is not positive")
-        self.every, self.beta, self.ess_frac = int(every), beta, ess_frac
+        if potential not in POTENTIALS:
+            raise ValueError(f"Resample: potential {potential!r} is not one of {POTENTIALS}")
+        if potential == 'squeeze' and not isinstance(squeeze, SqueezePotential):
+            raise ValueError("Resample: potential 'squeeze' needs a SqueezePotential (squeeze=...)")
+        if potential == 'model' and squeeze is not None:
+            raise ValueError("Resample: a SqueezePotential goes with potential='squeeze'")
+        self.every, self.beta, self.ess_frac, self.potential, self.squeeze = int(every), beta, ess_frac, potential, squeeze
 
     def __repr__(self) -> str:
-        return f"Resample(every={self.every}, beta={self.beta}, ess_frac={self.ess_frac})"
+        tail = "" if self.potential == 'model' else f", potential={self.potential!r}"
+        return f"Resample(every={self.every}, beta={self.beta}, ess_frac={self.ess_frac}{tail})"
 
     def evaluates(self, si: int, n_steps: int) -> bool:
         """Whether walk step `si` of `n_steps` is followed by an evaluation: every `every`-th step, never the last."""
@@ -67,10 +166,56 @@ def summarise(log: Sequence, n_chains: int, batch: int) -> List[Dict[str, Any]]:
     return out
 
 
+def squeeze_potential_from_args(args) -> Optional[Dict[str, int]]:
+    """--resample_potential squeeze [--resample_squeeze_cells T,X --squeeze_closing_steps K --squeeze_window R] -> SqueezePotential's
+    squeeze_config, or None for the model's potential.  ValueError: an unknown potential, 'squeeze' with --fingers_3d (a sliced-squeeze
+    evaluation costs seconds, DESIGN.md 4.1d), with --goal_pose (goal fields have no squeeze form) or without --resample_every;
+    --resample_squeeze_cells without it or not two positive integers."""
+    potential = getattr(args, "resample_potential", None) or 'model'
+    cells = getattr(args, "resample_squeeze_cells", None)
+    if potential not in POTENTIALS:
+        raise ValueError(f"--resample_potential {potential!r}: choose one of {', '.join(POTENTIALS)}")
+    if potential == 'model':
+        if cells is not None:
+            raise ValueError("--resample_squeeze_cells needs --resample_potential squeeze")
+        return None
+    if getattr(args, "resample_every", None) is None:
+        raise ValueError("--resample_potential squeeze needs --resample_every (and --resample_beta): it is a potential for resampling")
+    if getattr(args, "fingers_3d", False):
+        raise ValueError("--resample_potential squeeze is 2-D only: a sliced-squeeze evaluation of --fingers_3d costs seconds, not supported")
+    if getattr(args, "goal_pose", None) is not None:
+        raise ValueError("--resample_potential squeeze with --goal_pose: goal fields have no squeeze form, not supported")
+    config: Dict[str, int] = {}
+    if cells is not None:
+        try:
+            t, x = (int(v) for v in str(cells).split(","))
+        except ValueError:
+            raise ValueError(f"--resample_squeeze_cells {cells!r}: two integers T,X expected") from None
+        if t < 1 or x < 2:
+            raise ValueError(f"--resample_squeeze_cells {cells!r}: need T >= 1 and X >= 2")
+        config.update(theta_cells=t, x_cells=x)
+    k, r = getattr(args, "squeeze_closing_steps", None), getattr(args, "squeeze_window", None)
+    if k is not None:
+        if k < 0:
+            raise ValueError(f"--squeeze_closing_steps={k}: the number of steps cannot be negative")
+        config["closing_steps"] = int(k)
+    if r is not None:
+        if r < 1:
+            raise ValueError(f"--squeeze_window={r}: the window is at least 1 cell")
+        config["window"] = int(r)
+    return config
+
+
+def with_squeeze(resample: Resample, contours, **squeeze_config) -> Resample:
+    """`resample` with the squeeze simulator's potential over the contour bank (O, nv, 2) in metres."""
+    return Resample(resample.every, resample.beta, resample.ess_frac, 'squeeze', SqueezePotential(contours, **squeeze_config))
+
+
 def resample_from_args(args) -> Optional[Resample]:
     """--resample_every / --resample_beta / --resample_ess of the generator's entry point, checked before anything is built."""
     r = from_flags(getattr(args, "resample_every", None), getattr(args, "resample_beta", None), getattr(args, "resample_ess", None),
                    bool(getattr(args, "classifier_guidance", False)), float(getattr(args, "eta", 0.0) or 0.0))
+    squeeze_potential_from_args(args)       # --resample_potential / --resample_squeeze_cells: refused here too
     if r is None:
         return None
     if getattr(args, "mode", "test") != "test":

@@ -334,10 +334,13 @@ def step_noise_keys(n_chains: int, shared_step_noise: bool = False, chain_keys: 
 
 
 def check_resample(resample: Optional[Resample], eta: float, guid: Optional[Guidance], n_grad: int, scales: Optional[Sequence[float]] = None,
-                   bounds=None, edit=None, global_cond=None, grad_fn=None) -> None:
+                   bounds=None, edit=None, global_cond=None, grad_fn=None, objectives=None) -> None:
     """What a run with `resample` refuses, by ValueError and before any launch: eta == 0 (copies would never part), bounds / an edit
     (a finger's bounds belong to its slot, not to the design that is copied into it), global_cond (likewise its condition row),
-    n_grad == 0 or no guidance handle (nothing to weigh by), a bf16 handle (score has no bf16 form), per-chain scales with n_grad != 1."""
+    n_grad == 0 or no guidance handle (nothing to weigh by), per-chain scales with n_grad != 1; with the model's potential a bf16 handle
+    (score has no bf16 form); with the squeeze simulator's (which needs no forward-only trunk, so bf16 handles pass) a 3-D handle (a
+    sliced-squeeze evaluation costs seconds), a goal objective among `objectives` (names, Goals or the launch's
+    objectives; goal fields have no squeeze form) and a contour bank whose object count differs from the handle's."""
     if resample is None:
         return
     if not isinstance(resample, Resample):
@@ -350,7 +353,15 @@ def check_resample(resample: Optional[Resample], eta: float, guid: Optional[Guid
         raise ValueError("resample: global_cond rows belong to a finger's slot; resampled conditional rows are not supported")
     if n_grad == 0 or guid is None or grad_fn is not None:
         raise ValueError("resample: needs the guidance handle and its objectives (n_grad >= 1, no grad_fn): there is nothing else to weigh fingers by")
-    if getattr(guid, "contraction_dtype", "f32") == "bf16":
+    if resample.potential == 'squeeze':
+        if guid.dyn.kind == 3:
+            raise ValueError("resample: the squeeze potential is 2-D only (a sliced-squeeze evaluation of 3-D fingers costs seconds)")
+        if any(is_goal(o) or getattr(o, "use_rowcoef", 0) == _lib.OBJ_ROWFIELD for o in (objectives or ())):
+            raise ValueError("resample: goal objectives have no squeeze form (the squeeze potential reads no row field)")
+        if resample.squeeze.n_objects != guid.n_objects:
+            raise ValueError(f"resample: the squeeze potential's bank holds {resample.squeeze.n_objects} contours, the guidance handle "
+                             f"{guid.n_objects} objects")
+    elif getattr(guid, "contraction_dtype", "f32") == "bf16":
         raise ValueError("resample: the bf16 trunk has no forward-only form (Guidance.score refuses it)")
     if scales is not None and len(set(scales)) > 1 and n_grad != 1:
         raise ValueError(f"resample: per-chain classifier scales ({sorted(set(scales))}) need n_grad == 1, not {n_grad}")
@@ -388,14 +399,17 @@ def run_chains(unet: Unet1d, guid: Optional[Guidance], sched: DDIMScheduler, x0:
     run and start at zero.  resample_log: a list that receives (si, ess (n_chains,), did (n_chains,), ancestors (n_chains, B)) per
     evaluation, device tensors.  resample_starts (3-D): the evaluations' FPS draws, [evaluation][n_grad * n_chains][starts_per_call], taken
     from the start stream AFTER all of the run's guidance draws (draw_chain_starts / draw_ensemble_starts, n_potential) - the guidance
-    draws are those of the run without resampling.  check_resample lists what is refused, before any launch."""
+    draws are those of the run without resampling.  check_resample lists what is refused, before any launch.
+    resample.potential == 'squeeze' (2-D): the values come from the squeeze simulator instead - one eps-net call on the step's output at
+    timesteps[si + 1], x0 = engine.ddim_pred_x0 of it, resample.squeeze.values over the same G P^2 cells in the same units; no
+    guid.score call, no FPS draws; everything after the values is the same engine.chain_resample call."""
     B, L = x0.shape
     nc = n_chains
     eta = float(eta)
     if eta < 0.0:
         raise ValueError(f"run_chains: eta {eta} is negative")
     if resample is not None:
-        check_resample(resample, eta, guid, n_grad, scales, bounds=bounds, global_cond=global_cond, grad_fn=grad_fn)
+        check_resample(resample, eta, guid, n_grad, scales, bounds=bounds, global_cond=global_cond, grad_fn=grad_fn, objectives=objectives)
         n_eval = len(resample.evaluations(len(timesteps)))
         if guid.dyn.kind == 3 and n_eval:
             if resample_starts is None or resample_starts.dtype != np.int64 or resample_starts.size != n_eval * n_grad * nc * guid.starts_per_call:
@@ -444,7 +458,19 @@ def run_chains(unet: Unet1d, guid: Optional[Guidance], sched: DDIMScheduler, x0:
                                                            chain_keys=keys if isinstance(c, slice) else [keys[c]])
         out = [engine.ddim_guided_step(x[c], eps[c], None if g is None else g[c], n_grad, coef, sc, bounds, **noisy(c)) for c, sc in steps]
         x = out[0] if len(out) == 1 else torch.stack(out)
-        if resample is not None and resample.evaluates(si, len(timesteps)):
+        if resample is not None and resample.evaluates(si, len(timesteps)) and resample.potential == 'squeeze':
+            # the squeeze model's opinion of the predicted clean design: one eps-net call on the step's output at the next timestep (as the
+            # loop calls it; cond is None here), the step's own x0 expression, one squeeze map over cond_fn's grid cells, one values launch
+            tn = int(timesteps[si + 1])
+            eps_n = unet.forward_cfg(x.reshape(nc * B, L, 1), torch.full((nc * B,), tn, dtype=torch.int32, device=x.device), None, cfg_weight)
+            clean = engine.ddim_pred_x0(x, eps_n.reshape(nc, B, L).contiguous(), sched.coefficients(tn)[:2])
+            values = resample.squeeze.values(clean, objectives, rowcoef, n_grad, guid.cfg.grid_size, guid.cfg.num_pos,
+                                             (guid.cfg.ori_lo, guid.cfg.ori_hi))
+            x, anc, ess, did = engine.chain_resample(x, values, n_grad, beta_per_cell, resample.ess_frac, noise_seed, keys, si, logw, vprev)
+            n_seen += 1
+            if resample_log is not None:
+                resample_log.append((si, ess, did, anc))
+        elif resample is not None and resample.evaluates(si, len(timesteps)):
             # the forward-only trunk on the step's output; only the logits are used (the tally's thresholds are placeholders)
             st = None if guid.dyn.kind != 3 else resample_starts[n_seen]
             logits = guid.score(x.repeat(n_grad, 1, 1), [int(o.object) for o in objectives], (1.0, 1.0, 1.0), int(timesteps[si + 1]), st,
@@ -577,7 +603,7 @@ def guided_chains(unet: Unet1d, guid: Guidance, sched: DDIMScheduler, mode: str,
     resample, resample_log: run_chains' (every chain resamples among its own B fingers).  3-D: the evaluations' draws follow all
     guidance draws on the start stream; `predrawn` then is draw_chain_starts' triple (n_potential = len(resample.evaluations(S)))."""
     nc, (B, L, _) = len(chains), noise.shape
-    check_resample(resample, eta, guid, 1, edit=edit, global_cond=global_cond)
+    check_resample(resample, eta, guid, 1, edit=edit, global_cond=global_cond, objectives=[o for _, o in chains])
     engine.chain_cond_layout(global_cond, unet.global_cond_dim, nc, B)       # a condition of the wrong shape is refused before anything runs
     dev = noise.device
     is3d = mode == 'point_3d'
@@ -629,7 +655,7 @@ def guided_multi_object(unet: Unet1d, guid: Guidance, sched: DDIMScheduler, mode
     resample, resample_log: run_chains' - the fingers are weighed by the mean of the objects' values; 3-D: the evaluations' draws
     (object after object) follow the loop's guidance draws on the start stream."""
     n_obj, (B, L, _) = len(object_indices), noise.shape
-    check_resample(resample, eta, guid, n_obj, edit=edit, global_cond=global_cond)
+    check_resample(resample, eta, guid, n_obj, edit=edit, global_cond=global_cond, objectives=[opt_obj])
     engine.check_global_cond(global_cond, unet.global_cond_dim, B)
     is3d = mode == 'point_3d'
     objectives, field = chain_objectives(guid, [(oi, opt_obj) for oi in object_indices])
@@ -693,7 +719,7 @@ def guided_multi_object_groups(unet: Unet1d, guid: Guidance, sched: DDIMSchedule
     eta, noise_seed, shared_step_noise, chain_keys: as in guided_chains, group k being chain k.
     resample, resample_log: run_chains' (the walk, whatever python_loop says); 3-D: `predrawn` then is draw_ensemble_starts' pair."""
     K, n_obj, (B, L, _) = len(groups), len(groups[0]), noise.shape
-    check_resample(resample, eta, guid, n_obj, edit=edit, global_cond=global_cond)
+    check_resample(resample, eta, guid, n_obj, edit=edit, global_cond=global_cond, objectives=opt_objs)
     assert all(len(g) == n_obj for g in groups) and len(opt_objs) == K
     engine.chain_cond_layout(global_cond, unet.global_cond_dim, K, B)       # global_cond: (B, gc) for all groups or (K, B, gc)
     if any(not is_goal(o) and o == 'convergence' for o in opt_objs):

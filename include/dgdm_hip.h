@@ -173,6 +173,12 @@ int dgdm_ddim_step_noise(uint64_t seed, const uint64_t *chain_keys_dev, int n_ch
 /* DDIMScheduler.add_noise (diffusion.py:145,185): out = sqrt_abar*x0 + sqrt_1m_abar*noise */
 int dgdm_ddim_add_noise(const float *x0_dev, const float *noise_dev, float *out_dev, int64_t n,
                         float sqrt_abar, float sqrt_1m_abar, void *stream);
+/* The predicted clean sample the DDIM steps above form, on its own, from the unguided eps and with clip_sample's [-1, 1]:
+ *   out = fmin(fmax(fdiv_rn(sub_rn(x, mul_rn(sqrt_1m_abar_t, eps)), sqrt_abar_t), -1), 1)    float32, elementwise, nothing fused
+ * - the bits dgdm_ddim_guided_step's x0 has when grad_dev is NULL.  A NaN passes through as fmaxf / fminf give it.  n >= 0; a NULL
+ * pointer is DGDM_EINVAL.                                                                                                          */
+int dgdm_ddim_pred_x0(const float *x_dev, const float *eps_dev, float *out_dev, int64_t n, float sqrt_abar_t, float sqrt_1m_abar_t,
+                      void *stream);
 
 /* ------------------------------------------------------------------ a8-a12: dynamics models
  * kind 2: ProfileForward2DModel(W=256, params_ch, object_ch) (dynamics/profile_forward_2d.py:78-135)
@@ -805,6 +811,33 @@ int dgdm_squeeze_map(const DgdmSqueezeConfig *cfg, const double *surfaces_dev, i
                      const double *starts_dev, int n_starts, int32_t *cells_dev, double *y_dev, int32_t *flags_dev, double *table_s_dev,
                      double *touch_l_dev, double *touch_r_dev, int32_t *succ_dev, void *workspace_dev, int64_t workspace_bytes,
                      void *stream);
+
+/* The objective's VALUE per (pair) from a squeeze map: what dgdm_guidance_objective_values makes of the dynamics model's logits, made
+ * of the squeeze model's one-closing deltas instead - a second opinion for resampling.  This project's own mechanism:
+ * no counterpart in the reference, 2-D only, frictionless.  THE recipe (tests/resample_squeeze_oracle.py states the same text in numpy).
+ *   cells_dev  [n_pairs][n_starts][3] int32, y_dev [n_pairs][n_starts][2] float64: as dgdm_squeeze_map writes them
+ *   starts_dev [n_starts][3] float64: the starts of that map (y0 is read)
+ *   pair p belongs to group p / B and is finger p % B of it;  objectives_host [n_pairs / B], HOST
+ *   rowcoef_dev [n_pairs / B][n_starts * B] float32 or NULL, read at [group][n * B + p % B] - the guidance row cell * B + b
+ *   score_std[3]: the theta, x, y entries of the dataset's SCORE_STD (radians, metres, metres);  values_dev [n_pairs] float64
+ * For pair p and start n, everything float64, every product, sum and quotient rounded on its own, in the order written:
+ *   a = cell / x_cells, b = cell % x_cells of the start cell and of the closed cell;  da = a_closed - a_start as an integer,
+ *   2 da > T: da -= T;  2 da < -T: da += T   (T = theta_cells; +-T / 2 is kept: the strict rule of continuous_signed_delta)
+ *   d0 = ((double)da * (6.283185307179586 / T)) / std0
+ *   d1 = ((double)(b_closed - b_start) * (2 x_half / (x_cells - 1))) / std1
+ *   d2 = (y[p][n][0] - starts[n][2]) / std2
+ *   t  = ((l0 d0 + q0 (d0 d0)) + (l1 d1 + q1 (d1 d1))) + (l2 d2 + q2 (d2 d2)),   lin / quad widened to double;
+ *        use_rowcoef == 1: t = t + (double)rowcoef * d0
+ * - the delta order (theta, x, y) and the units (each over its SCORE_STD entry) of the dynamics model's outputs and of the dataset
+ * files sim_2d.py writes.  V[p] = sum_n t: one wave of 64 lanes per pair, lane l adds n = l, l + 64, ... in ascending order from 0.0,
+ * then v += shfl_xor(v, s) for s = 32, 16, .., 1, lane 0 stores: bit-identical run to run.
+ * DGDM_EINVAL before any launch: use_rowcoef == DGDM_OBJ_ROWFIELD (goal fields have no squeeze form) or any value other than 0 / 1,
+ * use_rowcoef == 1 with a NULL rowcoef_dev, n_pairs % B != 0, n_pairs < 0, B < 1, n_starts < 1, a non-finite or non-positive
+ * score_std, a bad cfg by dgdm_squeeze_map's rules, a NULL required pointer.  Synchronises the stream once, at the end (the
+ * objectives are the caller's).                                                                                                      */
+int dgdm_squeeze_objective_values(const DgdmSqueezeConfig *cfg, const int32_t *cells_dev, const double *y_dev, const double *starts_dev,
+                                  int n_pairs, int n_starts, int B, const DgdmObjective *objectives_host, const float *rowcoef_dev,
+                                  const double score_std[3], double *values_dev, void *stream);
 
 /* ------------------------------------------------------------------ squeeze simulator, 3-D fingers: a sliced squeeze (csrc/squeeze.hip,
  * DESIGN.md §4.1d "3-D form")
