@@ -118,20 +118,28 @@ struct DgdmGuidance {
     int64_t todo_capacity = 0;
     // uploads of the start indices go through their own stream (the copy engine works beside the kernels of the launch stream):
     // up_ready orders the consumers behind the copy, up_consumed the next copy behind the last reader of the device buffers
-    // set_objects' read-back (tie flags, crowded-centre counts) lands in pinned memory behind ro_ev and is only waited for when its
-    // values are first needed - the host converts and uploads the first step's start indices while the tables are still being built
-    int *ro_host = nullptr; size_t ro_ints = 0; hipEvent_t ro_ev = nullptr; bool ro_pending = false;
+    // set_objects' read-back (tie flags, crowded-centre counts) lands in pinned memory behind rb_ev and is only waited for when its
+    // values are first needed - the host converts and uploads the first step's start indices while the tables are still being built.
+    // A build off the caller's stream copies them as soon as both exist (behind the FPS tables and crowd_ev, the first light stage):
+    // the host then plans the gather while the heavy stages still run.  ro_ev is the END of the build (behind the last heavy stage
+    // and the layer-1 tables): join_tables, the next set_objects and the destructor order themselves by it, never by rb_ev.
+    int *ro_host = nullptr; size_t ro_ints = 0; hipEvent_t ro_ev = nullptr, rb_ev = nullptr, crowd_ev = nullptr; bool ro_pending = false;
+    std::vector<hipEvent_t> odone;      // odone[i]: object i's tables are complete (the end of build_object on its build stream); created once, re-recorded by every build
     int finish_objects();
     hipStream_t cstream = nullptr; hipEvent_t up_ready = nullptr, up_consumed = nullptr; bool consumed_recorded = false;
     // Step schedule.  The 3-D table build runs on the build streams alone and ends in ro_ev on bstream[0]; the first
     // call that reads the tables on a stream makes that stream wait for it (join_tables).  Inside the denoise loop the eps-net runs on
     // bstream[0] (idle by then) beside common_pre and is joined in front of the trunk.  serial = DGDM_SERIAL_STEP, read at create:
     // 1 everything on the caller's stream, in the order of the data dependencies (also while dgdm_prof_enable is on: the stage events
-    // assume one stream); for measuring the parts apart, 2 = only the table build stays on the caller's stream, 4 = only the eps-net does
+    // assume one stream); for measuring the parts apart, 2 = only the table build stays on the caller's stream, 4 = only the eps-net does,
+    // 8 = only the gather stays behind the END of the build (one launch behind join_tables) instead of starting object by object
     int serial = 0;
     bool tables_off_stream() const { return !(serial & 3) && !prof_on(); }
     bool eps_beside() const { return !(serial & 5) && !prof_on(); }
     bool hoist_x_only() const { return !(serial & 1) && !prof_on(); }
+    // the gather of an object's rows starts behind odone[object]: only where a build off the stream has still to be joined (afterwards,
+    // and on tables built earlier, one launch over all chains as ever)
+    bool gather_early(hipStream_t s) const { return !(serial & 9) && !prof_on() && built_off_stream && (join_pending || s != joined_stream); }
     bool built_off_stream = false, join_pending = false, built_once = false;
     hipStream_t joined_stream = nullptr;
     hipEvent_t fork_ev = nullptr, side_ev = nullptr;
@@ -157,6 +165,9 @@ struct DgdmGuidance {
         if (pinned_ev) (void)hipEventDestroy(pinned_ev);
         if (ro_host) (void)hipHostFree(ro_host);
         if (ro_ev) (void)hipEventDestroy(ro_ev);
+        if (rb_ev) (void)hipEventDestroy(rb_ev);
+        if (crowd_ev) (void)hipEventDestroy(crowd_ev);
+        for (hipEvent_t e : odone) (void)hipEventDestroy(e);
         if (cstream) (void)hipStreamDestroy(cstream);
         if (up_ready) (void)hipEventDestroy(up_ready);
         if (up_consumed) (void)hipEventDestroy(up_consumed);
@@ -178,7 +189,7 @@ struct DgdmGuidance {
     // starts of `n_calls` classifier calls per chain: call k of chain c at starts_host + k * call_stride + c * 2 * rows; on the device the
     // chain's rows of all calls form one run of n_calls * rows rows (row k * rows + r)
     int upload_starts(const int64_t *starts_host, int n_chains, int64_t rows, hipStream_t s, bool need_order = true, int n_calls = 1,
-                      int64_t call_stride = 0);
+                      int64_t call_stride = 0, bool on_launch_stream = false);
     int ensure_rows(int n_chains, int64_t rows_per_chain);      // grows the per-row device buffers and the pinned staging area
     // the rows' indices into the embedding tables (every chain's object has its table in the wanted format): no per-step gather runs at all
     int use_xtab(const int *objidx_host, int n_chains, int64_t rows, bool want16, int *l1, hipStream_t s);
@@ -518,6 +529,22 @@ extern "C" int dgdm_guidance_set_objects(DgdmGuidance *g, const float *objects_d
         if (!g->bf16 && !g->l2_gather_mode && N <= 512 &&
             (rc = pn_fps_transpose(g->pool_fps1.as<int>(), N, g->pool_fps1t.as<uint4>(), fs, n_objects))) return rc;
         DGDM_HIP_CHECK(hipEventRecord(g->bstart, fs));
+        // per-object completion events and the pinned target of the read-back (a copy of an earlier build into the old block has ended
+        // at rb_ev before the block goes)
+        while ((int)g->odone.size() < n_objects) {
+            hipEvent_t e = nullptr;
+            DGDM_HIP_CHECK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+            g->odone.push_back(e);
+        }
+        if (!g->rb_ev) DGDM_HIP_CHECK(hipEventCreateWithFlags(&g->rb_ev, hipEventDisableTiming));
+        if (!g->crowd_ev) DGDM_HIP_CHECK(hipEventCreateWithFlags(&g->crowd_ev, hipEventDisableTiming));
+        const size_t ro_need = no * N + no;
+        if (ro_need > g->ro_ints) {
+            if (g->ro_host) { DGDM_HIP_CHECK(hipEventSynchronize(g->rb_ev)); DGDM_HIP_CHECK(hipHostFree(g->ro_host)); }
+            g->ro_host = nullptr; g->ro_ints = 0;
+            DGDM_HIP_CHECK(hipHostMalloc(reinterpret_cast<void **>(&g->ro_host), ro_need * sizeof(int), hipHostMallocDefault));
+            g->ro_ints = ro_need;
+        }
         for (int i = 0; i < n_objects; ++i) {
             ObjectTables &t = *g->tables[i];
             t.xyz = g->pool_xyz.as<float>() + (size_t)i * N * 3; t.fps1 = g->pool_fps1.as<int>() + (size_t)i * N * 512;
@@ -534,6 +561,7 @@ extern "C" int dgdm_guidance_set_objects(DgdmGuidance *g, const float *objects_d
             if ((rc = pn_crowd(g->pool_xyz.as<float>(), N, w, g->pool_crowded.as<int>(), g->pool_clist.as<int>(), g->pool_clist.as<int>() + N,
                                g->pool_off.as<int>(), g->pool_pairs.as<int>(), g->pool_rank.as<short>(), ls, g->pool_ncr.as<int>(), n_objects)))
                 return rc;
+            DGDM_HIP_CHECK(hipEventRecord(g->crowd_ev, ls));               // the crowded-centre counts exist
             if (g->bf16) {
                 if ((rc = pn_sa1(g->pool_xyz.as<float>(), N, w, g->pool_F1.as<float>(), ls, n_objects))) return rc;                                   // T2
                 if ((rc = linear(g->pool_F1.as<float>(), 128, w.sa2_wf_t, w.sa2_b0, nullptr, 1, g->pool_U.as<float>(), 128, n_objects * N, 128, 128,
@@ -546,12 +574,30 @@ extern "C" int dgdm_guidance_set_objects(DgdmGuidance *g, const float *objects_d
             }
             DGDM_HIP_CHECK(hipEventRecord(g->ldone, ls));
         }
+        // which objects may use the table of FPS(128) sequences (no order-dependent selection anywhere); crowded-centre counts: copied
+        // to pinned memory behind rb_ev, read by finish_objects() when first needed.  Off the caller's stream they go as soon as both
+        // exist: on the FPS stream right behind the tables (pool_flags) and behind the first light stage (pool_ncr), in front of that
+        // stream's heavy stages - the host can plan the chains' gathers while those run
+        auto read_back = [&](hipStream_t rs) -> int {
+            DGDM_HIP_CHECK(hipMemcpyAsync(g->ro_host, g->pool_flags.p, sizeof(int) * no * N, hipMemcpyDeviceToHost, rs));
+            DGDM_HIP_CHECK(hipMemcpyAsync(g->ro_host + no * N, g->pool_ncr.p, sizeof(int) * no, hipMemcpyDeviceToHost, rs));
+            DGDM_HIP_CHECK(hipEventRecord(g->rb_ev, rs));
+            return DGDM_OK;
+        };
+        if (off) {
+            DGDM_HIP_CHECK(hipStreamWaitEvent(fs, g->crowd_ev, 0));
+            if ((rc = read_back(fs))) return rc;
+        }
         for (int i = 0; i < nb; ++i) {       // the heavy stages need the FPS tables (bstart) and the light stages' outputs
             DGDM_HIP_CHECK(hipStreamWaitEvent(g->bstream[i], g->bstart, 0));
             DGDM_HIP_CHECK(hipStreamWaitEvent(g->bstream[i], g->ldone, 0));
         }
-        for (int i = 0; i < n_objects; ++i)
+        for (int i = 0; i < n_objects; ++i) {
             if ((rc = g->build_object(i, i % nb, g->bstream[i % nb]))) return rc;
+            // the object's tables are complete: the gather of its chains' rows may start (run_xobj).  The stream waited for bstart and
+            // ldone, so the pool's parts of the object (fps1, clist, ..) are covered too
+            DGDM_HIP_CHECK(hipEventRecord(g->odone[i], g->bstream[i % nb]));
+        }
         // the build's end: on the caller's stream, or (off it) on bstream[0], which has the FPS stream behind it through bstart
         hipStream_t es = off ? g->bstream[0] : s;
         for (int i = off ? 1 : 0; i < nb; ++i) {
@@ -565,19 +611,12 @@ extern "C" int dgdm_guidance_set_objects(DgdmGuidance *g, const float *objects_d
             if ((rc = trunk_f16l_l1_tables(reinterpret_cast<const float *const *>(po), g->pool_ncr.as<int>(), reinterpret_cast<float *const *>(po + l1mo),
                                            reinterpret_cast<int *const *>(po + 2 * l1mo), N, n_objects, g->m->fwdh(), es))) return rc;
         }
-        // which objects may use the table of FPS(128) sequences (no order-dependent selection anywhere); crowded-centre counts:
-        // copied to pinned memory behind an event, read by finish_objects() when first needed
         prof_end(s, DGDM_STAGE_TABLES, 0.0);
-        const size_t need = no * N + no;
-        if (need > g->ro_ints) {
-            if (g->ro_host) DGDM_HIP_CHECK(hipHostFree(g->ro_host));
-            g->ro_host = nullptr;
-            DGDM_HIP_CHECK(hipHostMalloc(reinterpret_cast<void **>(&g->ro_host), need * sizeof(int), hipHostMallocDefault));
-            g->ro_ints = need;
-        }
+        if (!off && (rc = read_back(es))) return rc;
+        // ro_ev: the END of the build (join_tables, the next build, the destructor), whatever the place of the read-back.  It has the
+        // early read-back behind it as well (long complete by then): the next build's, possibly on another stream, cannot overtake it
+        if (off) DGDM_HIP_CHECK(hipStreamWaitEvent(es, g->rb_ev, 0));
         if (!g->ro_ev) DGDM_HIP_CHECK(hipEventCreateWithFlags(&g->ro_ev, hipEventDisableTiming));
-        DGDM_HIP_CHECK(hipMemcpyAsync(g->ro_host, g->pool_flags.p, sizeof(int) * no * N, hipMemcpyDeviceToHost, es));
-        DGDM_HIP_CHECK(hipMemcpyAsync(g->ro_host + no * N, g->pool_ncr.p, sizeof(int) * no, hipMemcpyDeviceToHost, es));
         DGDM_HIP_CHECK(hipEventRecord(g->ro_ev, es));
         g->ro_pending = true;
         g->built_once = true; g->built_off_stream = off; g->join_pending = off;
@@ -607,7 +646,7 @@ int DgdmGuidance::common_pre(const float *x_dev, float t_scaled, const int *obji
 // Reference draw order per chain: for each sub-batch i, sa1's torch.randint(rows_i) then sa2's  ->  device [chain][row][2]
 int DgdmGuidance::finish_objects() {
     if (!ro_pending) return DGDM_OK;
-    DGDM_HIP_CHECK(hipEventSynchronize(ro_ev));
+    DGDM_HIP_CHECK(hipEventSynchronize(rb_ev));      // the read-back alone: the build may still be running
     const int N = cfg.num_object_points;
     for (int i = 0; i < n_objects; ++i) {
         bool ok = N >= 128;
@@ -639,7 +678,7 @@ int DgdmGuidance::ensure_rows(int n_chains, int64_t rows_per_chain) {
 }
 
 int DgdmGuidance::upload_starts(const int64_t *starts_host, int n_chains, int64_t rows, hipStream_t s, bool need_order, int n_calls,
-                                int64_t call_stride) {
+                                int64_t call_stride, bool on_launch_stream) {
     const int N = cfg.num_object_points;
     const int64_t sb = cfg.sub_batch_size;
     const int64_t rt = rows * n_calls;                         // rows per chain on the device
@@ -702,16 +741,23 @@ int DgdmGuidance::upload_starts(const int64_t *starts_host, int n_chains, int64_
         DGDM_HIP_CHECK(hipEventCreateWithFlags(&up_consumed, hipEventDisableTiming));
     }
     // the copy may start as soon as the previous readers of the device buffers (the last gather / index kernel on the launch stream)
-    // are done - not behind everything queued on the launch stream since
-    if (consumed_recorded) DGDM_HIP_CHECK(hipStreamWaitEvent(cstream, up_consumed, 0));
-    DGDM_HIP_CHECK(hipMemcpyAsync(starts.p, pinned, (size_t)n_chains * rt * 2 * sizeof(int), hipMemcpyHostToDevice, cstream));
-    if (need_order) {
-        DGDM_HIP_CHECK(hipMemcpyAsync(order.p, ord, (size_t)n_chains * rt * sizeof(int), hipMemcpyHostToDevice, cstream));
-        DGDM_HIP_CHECK(hipMemcpyAsync(groupoff.p, goff, (size_t)n_chains * (N + 1) * sizeof(int), hipMemcpyHostToDevice, cstream));
+    // are done - not behind everything queued on the launch stream since.
+    // on_launch_stream (the gathers start beside a table build still in flight, run_xobj): the copies go on `s` itself.  The process
+    // has more streams than hardware queues, and up_ready's marker on the upload stream was seen to come out only behind the LAST
+    // kernel of the build stream whose queue it shares - the gathers then started at the build's end whatever they waited for
+    // (DESIGN.md 4.3b).  `s` has nothing else to run until the build ends, so the copy costs the gathers' start, not the step.
+    hipStream_t us = on_launch_stream ? s : cstream;
+    if (consumed_recorded) DGDM_HIP_CHECK(hipStreamWaitEvent(us, up_consumed, 0));
+    if (need_order) {         // what the gathers read first
+        DGDM_HIP_CHECK(hipMemcpyAsync(order.p, ord, (size_t)n_chains * rt * sizeof(int), hipMemcpyHostToDevice, us));
+        DGDM_HIP_CHECK(hipMemcpyAsync(groupoff.p, goff, (size_t)n_chains * (N + 1) * sizeof(int), hipMemcpyHostToDevice, us));
     }
-    DGDM_HIP_CHECK(hipEventRecord(pinned_ev, cstream));
-    DGDM_HIP_CHECK(hipEventRecord(up_ready, cstream));
-    DGDM_HIP_CHECK(hipStreamWaitEvent(s, up_ready, 0));
+    DGDM_HIP_CHECK(hipMemcpyAsync(starts.p, pinned, (size_t)n_chains * rt * 2 * sizeof(int), hipMemcpyHostToDevice, us));
+    DGDM_HIP_CHECK(hipEventRecord(pinned_ev, us));
+    if (!on_launch_stream) {
+        DGDM_HIP_CHECK(hipEventRecord(up_ready, cstream));
+        DGDM_HIP_CHECK(hipStreamWaitEvent(s, up_ready, 0));
+    }
     return DGDM_OK;
 }
 
@@ -786,6 +832,12 @@ int DgdmGuidance::run_xobj(const int *objidx_host, int n_chains, int64_t rows, b
         groups = lpr > 0 && want16 == t.has16;     // the slot offsets are scaled for the build's mode
         ch[i].clist = t.clist; ch[i].cl2s = t.cl2s.as<int>(); ch[i].cl2o = t.cl2o.as<unsigned short>(); ch[i].pcf = t.pcf.as<int>(); ch[i].ncr = t.ncr; ch[i].lpr = lpr;
     }
+    // only the group kernel's launches start ahead of the build's end (below); everything else reads the tables behind the join
+    const bool early = groups && gather_early(s);
+    if (!early) {
+        int rc = join_tables(s);
+        if (rc) return rc;
+    }
     DGDM_HIP_CHECK(hipMemcpyAsync(xchains.p, ch.data(), sizeof(XobjChain) * n_chains, hipMemcpyHostToDevice, s));     // pageable: staged before return
     if (groups) {
         // A chain whose object has no crowded centre and no tie-flagged start has M0[q] as the embedding of every row (use_xtab): it gets no
@@ -807,23 +859,61 @@ int DgdmGuidance::run_xobj(const int *objidx_host, int n_chains, int64_t rows, b
                               : (want16 ? (const void *)(xobj16.as<uint32_t>() + (size_t)i * rows * 128) : (const void *)(xobj.as<float>() + (size_t)i * rows * 256));
         }
         xp.group_off = groupoff.as<int>(); xp.nchain = n_chains; xp.group_N = cfg.num_object_points; xp.use_table = 1;
-        xp.total_items = (int)rank.size() * xp.group_N;
-        std::stable_sort(rank.begin(), rank.end(), [&](int a, int b) { return ch[a].ncr > ch[b].ncr; });
-        for (size_t i = 0; i < rank.size(); ++i) xp.chain_of_rank[i] = (unsigned char)rank[i];
-        int rc = pn_xobj_groups(xp, s);
-        if (rc || !by_index) return rc;
-        *via_tab = true;
-        DGDM_HIP_CHECK(hipMemcpyAsync(xidxchains.p, xc.data(), sizeof(XidxChain) * n_chains, hipMemcpyHostToDevice, s));      // pageable: staged before return
-        DGDM_HIP_CHECK(hipMemcpyAsync(xtabptrs.p, base.data(), sizeof(void *) * n_chains, hipMemcpyHostToDevice, s));
-        if ((rc = fill_l1ptrs(m0_of, l1, s))) return rc;
-        return pn_xidx(xidxchains.as<XidxChain>(), starts.as<int>(), rows, n_chains, xidx.as<int>(), s);
+        auto index = [&]() -> int {          // what the trunk reads the chains through; the index kernel reads fps1 and the draws only
+            int rc;
+            *via_tab = true;
+            DGDM_HIP_CHECK(hipMemcpyAsync(xidxchains.p, xc.data(), sizeof(XidxChain) * n_chains, hipMemcpyHostToDevice, s));      // pageable: staged before return
+            DGDM_HIP_CHECK(hipMemcpyAsync(xtabptrs.p, base.data(), sizeof(void *) * n_chains, hipMemcpyHostToDevice, s));
+            if ((rc = fill_l1ptrs(m0_of, l1, s))) return rc;
+            return pn_xidx(xidxchains.as<XidxChain>(), starts.as<int>(), rows, n_chains, xidx.as<int>(), s);
+        };
+        int rc;
+        if (!early) {                        // one launch over all chains behind the joined build
+            xp.total_items = (int)rank.size() * xp.group_N;
+            std::stable_sort(rank.begin(), rank.end(), [&](int a, int b) { return ch[a].ncr > ch[b].ncr; });
+            for (size_t i = 0; i < rank.size(); ++i) xp.chain_of_rank[i] = (unsigned char)rank[i];
+            if ((rc = pn_xobj_groups(xp, s)) || !by_index) return rc;
+            return index();
+        }
+        // Step schedule: the build is still running on its streams and `s` has not joined it.  A chain's rows are gathered
+        // from its own object's tables alone, so they start behind that object's odone and run beside the float64 stages of the objects
+        // still being built: one launch per object with gathered chains, in the order in which the builds end (object index order, round-
+        // robin over the build streams).  All of them are on `s`, so what is recorded on `s` afterwards lies behind every gather:
+        // up_consumed (embed_rows), the next set_objects' `pooled` (it may overwrite tables and pool), the previous run's trunk that
+        // read xobj lies in front.  The launches append to ONE list of tie-flagged rows, emptied once; those rows (they read the
+        // tables of any chain), and the trunk's reads of M0 / L1Z, come behind join_tables(s) - which is reached on every way out,
+        // an error half way included, so that nothing enqueued here is left un-joined.
+        auto gathers = [&]() -> int {
+            int rc;
+            if (by_index) {                  // the index kernel needs the FPS tables, nothing of the heavy stages
+                DGDM_HIP_CHECK(hipStreamWaitEvent(s, bstart, 0));
+                if ((rc = index())) return rc;
+            }
+            if (rank.empty()) return DGDM_OK;
+            if ((rc = pn_xobj_groups_begin(xp, s))) return rc;
+            for (int o = 0; o < n_objects; ++o) {
+                int n = 0;                   // (the chains of one object have the same ncr: no heaviest-first order within a launch)
+                for (int c : rank)
+                    if (objidx_host[c] == o) xp.chain_of_rank[n++] = (unsigned char)c;
+                if (!n) continue;
+                xp.total_items = n * xp.group_N;
+                DGDM_HIP_CHECK(hipStreamWaitEvent(s, odone[o], 0));
+                if ((rc = pn_xobj_groups_rows(xp, s))) return rc;
+            }
+            return DGDM_OK;
+        };
+        rc = gathers();
+        const int jrc = join_tables(s);
+        if (rc || jrc) return rc ? rc : jrc;
+        return rank.empty() ? DGDM_OK : pn_xobj_groups_ties(xp, s);
     }
     return pn_xobj(xp, all_fast, s);
 }
 
 // The PointNet++ embeddings of the rows of `n_calls` consecutive classifier calls (3-D).  They depend on the FPS start draws and the
 // objects only - not on x - so a whole denoise loop's (or roll-out's) worth can be made before its first step: one upload and ONE gather
-// launch whose (chain, s1) groups hold the rows of all the calls (the variant's slab is staged once for five times the rows), or - when
+// launch whose (chain, s1) groups hold the rows of all the calls (the variant's slab is staged once for five times the rows; beside a
+// table build still in flight the launch is cut by object, each part behind its object's tables: run_xobj), or - when
 // every chain's object has its embedding table in the wanted format (float32, or bf16 operand-order rows: want16) - one index kernel.
 // Call k then reads rows [k * rows_per_call, (k + 1) * rows_per_call) of every chain (Embedded::point).
 int DgdmGuidance::embed_rows(const int *oidx, int n_chains, const int64_t *starts_host, int64_t rows_per_call, int n_calls, int64_t call_stride,
@@ -832,8 +922,11 @@ int DgdmGuidance::embed_rows(const int *oidx, int n_chains, const int64_t *start
     for (int i = 0; i < n_chains && tab; ++i) tab = want16 ? tables[oidx[i]]->has_x16 : tables[oidx[i]]->has_x;   // else: built in the other format, or not at all
     const int64_t rt = rows_per_call * n_calls;
     int rc;
-    if ((rc = join_tables(s))) return rc;       // every reader of the tables comes through here (or through embed's build_xtab)
-    if ((rc = upload_starts(starts_host, n_chains, rows_per_call, s, !tab, n_calls, call_stride))) return rc;     // host work: overlaps a table build still in flight
+    // Every reader of the tables joins the build (join_tables) in front of its first read: the embedding-table path here, run_xobj
+    // where its kernels need the whole build (its per-object gathers start earlier, see there), embed() in front of a build_xtab.  Every
+    // way through this function ends joined, so the trunk's reads of M0 / L1Z through xtabptrs / l1ptrs are covered.
+    if (tab && (rc = join_tables(s))) return rc;
+    if ((rc = upload_starts(starts_host, n_chains, rows_per_call, s, !tab, n_calls, call_stride, !tab && gather_early(s)))) return rc;     // host work: overlaps a table build still in flight
     if ((rc = finish_objects())) return rc;
     e->tab = tab; e->used16 = want16; e->rows_per_chain = rt;
     if ((rc = tab ? use_xtab(oidx, n_chains, rt, want16, &e->l1, s) : run_xobj(oidx, n_chains, rt, want16, &e->used16, &e->tab, &e->l1, s))) return rc;
@@ -865,7 +958,7 @@ void DgdmGuidance::Embedded::point(TrunkParams *p, const DgdmGuidance &g, int ca
 int DgdmGuidance::embed(const int *oidx, int n_chains, const int64_t *starts_host, int n_calls, int64_t call_stride, Embedded *e, hipStream_t s) {
     DGDM_REQUIRE(starts_host, DGDM_EINVAL, "3-D guidance needs the FPS start indices");
     int rc;
-    if ((rc = join_tables(s))) return rc;
+    if (prof_on() && (rc = join_tables(s))) return rc;      // the stage's events bracket the gather, not a wait for the build
     prof_begin(s, DGDM_STAGE_XOBJ);
     // The table X[s1][q] of an object costs about what 7 cond_fn calls spend gathering its rows (it holds all 262 144 (s1, q)
     // pairs; one call touches 36 000 of them): it pays as soon as the objects serve more than one 5-step chain - the
@@ -875,6 +968,7 @@ int DgdmGuidance::embed(const int *oidx, int n_chains, const int64_t *starts_hos
     if (tables_wanted()) {
         const bool crosses = grads_since_set <= XTAB_AFTER && grads_since_set + n_calls > XTAB_AFTER;
         grads_since_set += n_calls;
+        if (crosses && (rc = join_tables(s))) return rc;      // build_xtab reads the finished tables
         if (crosses)
             for (int i = 0; i < n_objects; ++i) {
                 ObjectTables &t = *tables[i];

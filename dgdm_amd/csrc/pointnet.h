@@ -143,6 +143,12 @@ __host__ __device__ inline int xobj_rows_lpr(int ncr, bool bf16) {
 }
 // one workgroup per (chain, s1): per feature chunk the variant's crowded Z rows staged once in LDS, all rows of the group reduced from there
 int pn_xobj_groups(const XobjParams &p, hipStream_t s);
+// its parts, for several launches that share one list of tie-flagged rows: _begin empties the list, every _rows launch covers the
+// chains of its p.chain_of_rank[0 .. p.total_items / p.group_N) and appends to it, _ties (once, last) computes the listed rows.
+// _rows reads only the tables of the objects of ITS chains; _ties reads those of any chain.
+int pn_xobj_groups_begin(const XobjParams &p, hipStream_t s);
+int pn_xobj_groups_rows(const XobjParams &p, hipStream_t s);
+int pn_xobj_groups_ties(const XobjParams &p, hipStream_t s);
 // the row-metadata table of xobj_rows_kernel: pcf [N][512]
 int pn_pcf(const int *fps1, const int *cnt2, const int *flags, int N, int *pcf, hipStream_t s);
 // index test hook (dgdm_debug_pointnet_indices): sa1's 32-neighbour lists [N][32], sa2's first-64 lists [N][64] + counts for the

@@ -1264,8 +1264,10 @@ int pn_pcf(const int *fps1, const int *cnt2, const int *flags, int N, int *pcf, 
     return DGDM_OK;
 }
 
-int pn_xobj_groups(const XobjParams &p, hipStream_t s) {
-    if (p.total_items <= 0) return DGDM_OK;
+// The three parts of a group gather: an empty list of tie-flagged rows, one or more launches of xobj_rows_kernel that append to it
+// (each over the chains in its own chain_of_rank / total_items), the listed rows.  pn_xobj_groups is the three in a row for one launch
+// over all chains; the step schedule (guidance_api.hip run_xobj) launches the rows per object.
+int pn_xobj_groups_begin(const XobjParams &p, hipStream_t s) {
     static bool attr_set = false;
     if (!attr_set) {
         DGDM_HIP_CHECK(hipFuncSetAttribute((const void *)xobj_rows_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, XR_LDS_BYTES));
@@ -1273,10 +1275,26 @@ int pn_xobj_groups(const XobjParams &p, hipStream_t s) {
         attr_set = true;
     }
     DGDM_HIP_CHECK(hipMemsetAsync(p.todo_count, 0, sizeof(int), s));
+    return DGDM_OK;
+}
+
+int pn_xobj_groups_rows(const XobjParams &p, hipStream_t s) {
+    if (p.total_items <= 0) return DGDM_OK;
     if (p.xobj16) hipLaunchKernelGGL(xobj_rows_kernel<true>, dim3((unsigned)p.total_items), dim3(64 * XR_WAVES), XR_LDS_BYTES, s, p);
     else hipLaunchKernelGGL(xobj_rows_kernel<false>, dim3((unsigned)p.total_items), dim3(64 * XR_WAVES), XR_LDS_BYTES, s, p);
     DGDM_HIP_CHECK(hipGetLastError());
-    // the rows it recorded (tie-flagged start points) run their own FPS
+    return DGDM_OK;
+}
+
+int pn_xobj_groups(const XobjParams &p, hipStream_t s) {
+    if (p.total_items <= 0) return DGDM_OK;
+    int rc;
+    if ((rc = pn_xobj_groups_begin(p, s)) || (rc = pn_xobj_groups_rows(p, s))) return rc;
+    return pn_xobj_groups_ties(p, s);
+}
+
+int pn_xobj_groups_ties(const XobjParams &p, hipStream_t s) {
+    // the rows the launches recorded (tie-flagged start points) run their own FPS
     XobjParams q = p;
     q.skip_fast = 1;
     const int64_t cap = std::min<int64_t>(std::min<int64_t>(p.total_rows, p.todo_capacity), 8192);
