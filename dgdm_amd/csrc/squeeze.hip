@@ -10,6 +10,10 @@
 //   3. apply_kernel / square_kernel, ceil(log2(cells)) rounds of pointer doubling, int32 only: round r holds succ^(2^r); the k-th
 //                       successor collects the rounds of k's set bits, the last square is the fixed point;
 //   4. lookup_kernel    one thread per (pair, start): snap, read the two maps, y and flags.
+// dgdm_squeeze_map_friction (include/dgdm_hip.h "squeeze simulator with Coulomb friction"; tests/squeeze_friction_oracle.py is its CPU
+// oracle) runs the same launches with table_kernel<true>, which also fills the chunk's jam table: a jammed cell is its own successor
+// (successor_kernel) and raises the flags 8 / 16 (lookup_kernel).  table_kernel<false> is dgdm_squeeze_map's kernel, instruction for
+// instruction what it was before the template.
 // dgdm_squeeze_map_3d (3-D fingers: the same contract on the horizontal planes of the finger grid, include/dgdm_hip.h "squeeze
 // simulator, 3-D fingers") runs the same chunk loop (run_chunks) with table3d_kernel in table_kernel's place; dgdm_squeeze_slice cuts
 // the object meshes into the per-level segment lists it reads.  Their kernels are described where they stand, below.
@@ -29,9 +33,43 @@ struct Grid {
     double x_half, dx, hl, h, travel_max;
 };
 
-// touch_l / touch_r / S [pairs][T][X] of this chunk.  Grid: (T, pairs) workgroups.
+// The contact `code` of one jaw (UPPER: the upper one), rebuilt after the walk by the walk's own operations in the walk's own order, so
+// that every bit is the candidate's: its point c on the object and its unnormalised normal n from the jaw into the object (the header's
+// table).  sF: that jaw's surface; code in 0 .. nv + nv m - 1.
+template <bool UPPER>
+__device__ __forceinline__ void contact_of(const Grid &g, const double *sF, const double *sRx, const double *sRy, double xg, int code, double &cx,
+                                           double &cy, double &nx, double &ny) {
+    if (code < g.nv) {                                                     // set A: vertex `code` on the segment j, j + 1
+        const double px = sRx[code] + xg;
+        const double t = (px + g.hl) / g.h;
+        const int j = (int)fmin(floor(t), (double)(g.m - 2));
+        const double d = sF[j + 1] - sF[j];
+        cx = px;
+        cy = sRy[code];
+        nx = UPPER ? d : -d;
+        ny = UPPER ? -g.h : g.h;
+    } else {                                                               // set B: finger sample j under the edge (i, i + 1)
+        const int r = code - g.nv, i = r / g.m, j = r - i * g.m, i1 = i + 1 == g.nv ? 0 : i + 1;
+        const double px = sRx[i] + xg, py = sRy[i], qx = sRx[i1] + xg, qy = sRy[i1];
+        const double ex = qx - px, ey = qy - py;
+        const double slope = ey / ex;
+        const double uj = -g.hl + (double)j * g.h;
+        cx = uj;
+        cy = py + (uj - px) * slope;
+        const bool flip = (ex > 0.0) == UPPER;                             // lower: (-ey, ex) if ex > 0, else (ey, -ex); upper: its negative
+        nx = flip ? ey : -ey;
+        ny = flip ? -ex : ex;
+    }
+}
+
+// touch_l / touch_r / S [pairs][T][X] of this chunk.  Grid: (T, pairs) workgroups.  FRICTION (dgdm_squeeze_map_friction): each lane also
+// keeps, per jaw, the code of the first candidate to attain the least gap - two ints beside the two minima, one compare and one select per
+// candidate - and after the walk rebuilds the two contacts from their codes (contact_of) and evaluates the jam test once; jam
+// [pairs][T][X], contact [pairs][T][X][2] or null.  The false instantiation reads none of the last three arguments.
+template <bool FRICTION>
 __global__ __launch_bounds__(TABLE_THREADS) void table_kernel(Grid g, const double *surfaces, const double *objects, const int32_t *pairs,
-                                                              const double *rot, double *touch_l, double *touch_r, double *S) {
+                                                              const double *rot, double *touch_l, double *touch_r, double *S, double mu,
+                                                              int32_t *jam, int32_t *contact) {
     extern __shared__ double lds[];
     double *sL = lds, *sU = lds + g.m, *sRx = lds + 2 * g.m, *sRy = sRx + g.nv;
     const int a = blockIdx.x, p = blockIdx.y;
@@ -53,6 +91,7 @@ __global__ __launch_bounds__(TABLE_THREADS) void table_kernel(Grid g, const doub
     for (int b = threadIdx.x; b < g.X; b += TABLE_THREADS) {
         const double xg = -g.x_half + (double)b * g.dx;
         double gl = inf, gu = inf;
+        [[maybe_unused]] int kl = -1, ku = -1;                             // FRICTION: the two contacts' codes
         // t = (x + hl) / h of a vertex serves set A and, x -> t being monotone, both ends of the two edges' sample ranges:
         // (min(xa, xb) + hl) / h is the smaller of the two t, bit for bit - one quotient per vertex instead of three
         double px = sRx[0] + xg, py = sRy[0];
@@ -68,6 +107,10 @@ __global__ __launch_bounds__(TABLE_THREADS) void table_kernel(Grid g, const doub
                 const double l0 = sL[j], u0 = sU[j];
                 const double lp = l0 + f * (sL[j + 1] - l0);
                 const double up = u0 + f * (sU[j + 1] - u0);
+                if constexpr (FRICTION) {                                  // the first candidate to attain the least gap: strictly less only
+                    kl = py - lp < gl ? i : kl;
+                    ku = up - py < gu ? i : ku;
+                }
                 gl = fmin(gl, py - lp);
                 gu = fmin(gu, up - py);
             }
@@ -77,9 +120,14 @@ __global__ __launch_bounds__(TABLE_THREADS) void table_kernel(Grid g, const doub
                 if (j0 <= j1) {                                            // both in 0 .. m - 1 then (false for a NaN)
                     const double slope = (qy - py) / (qx - px);
                     const int je = (int)j1;
+                    [[maybe_unused]] const int kb = g.nv + i * g.m;        // FRICTION: the code of (edge i, sample 0)
                     for (int j = (int)j0; j <= je; ++j) {
                         const double uj = -hl + (double)j * h;
                         const double ye = py + (uj - px) * slope;
+                        if constexpr (FRICTION) {
+                            kl = ye - sL[j] < gl ? kb + j : kl;
+                            ku = sU[j] - ye < gu ? kb + j : ku;
+                        }
                         gl = fmin(gl, ye - sL[j]);
                         gu = fmin(gu, sU[j] - ye);
                     }
@@ -93,11 +141,30 @@ __global__ __launch_bounds__(TABLE_THREADS) void table_kernel(Grid g, const doub
         touch_l[o] = gl;
         touch_r[o] = gu;
         S[o] = (gl + gu) / 2.0;
+        if constexpr (FRICTION) {
+            const double Sc = (gl + gu) / 2.0;
+            int jm = 0;
+            if (kl >= 0 && ku >= 0) {
+                double clx, cly, nlx, nly, crx, cry, nrx, nry;
+                contact_of<false>(g, sL, sRx, sRy, xg, kl, clx, cly, nlx, nly);
+                contact_of<true>(g, sU, sRx, sRy, xg, ku, crx, cry, nrx, nry);
+                const double ddx = crx - clx, ddy = cry - cly;
+                const double dot_l = nlx * ddx + nly * ddy, crs_l = nlx * ddy - nly * ddx;
+                const double dot_u = -(nrx * ddx + nry * ddy), crs_u = nrx * ddy - nry * ddx;
+                jm = (mu > 0.0 && Sc < g.travel_max && dot_l > 0.0 && dot_u > 0.0 && fabs(crs_l) <= mu * dot_l && fabs(crs_u) <= mu * dot_u) ? 1 : 0;
+            }
+            jam[o] = jm;
+            if (contact) {
+                contact[2 * o] = kl;
+                contact[2 * o + 1] = ku;
+            }
+        }
     }
 }
 
 // succ [pairs][cells]: the neighbour with the greatest S, visited in ascending (|db|, |da|, da, db), replaced on strictly greater only.
-__global__ void successor_kernel(Grid g, const double *S, int32_t *succ) {
+// jam [pairs][cells] or null (frictionless): a jammed cell is its own successor.
+__global__ void successor_kernel(Grid g, const double *S, const int32_t *jam, int32_t *succ) {
     const int cells = g.T * g.X;
     const int cell = blockIdx.x * blockDim.x + threadIdx.x;
     if (cell >= cells) return;
@@ -105,7 +172,8 @@ __global__ void successor_kernel(Grid g, const double *S, int32_t *succ) {
     const int a = cell / g.X, b = cell - a * g.X;
     double best = Sp[cell];
     int arg = cell;
-    if (!(best >= g.travel_max)) {
+    const bool jammed = jam && jam[(int64_t)blockIdx.y * cells + cell] != 0;
+    if (!(best >= g.travel_max) && !jammed) {
         for (int adb = 0; adb <= g.R; ++adb)
             for (int ada = 0; ada <= g.R; ++ada)
                 for (int sa = 0; sa < (ada ? 2 : 1); ++sa)
@@ -154,8 +222,10 @@ __device__ double pose_y(double y0, double tl, double tr, double S, double tm) {
 }
 
 // Per (pair, start): cells (start, closed, settled), y (closed, settled), flags.  `pair0`: the chunk's first pair in the outputs.
+// jam [pairs][cells] or null (frictionless): flags 8 (the start cell is jammed) and 16 (the settled cell is).
 __global__ void lookup_kernel(Grid g, const double *starts, int n_starts, const double *touch_l, const double *touch_r, const double *S,
-                              const int32_t *kth, const int32_t *fix, int pair0, int32_t *cells_out, double *y_out, int32_t *flags_out) {
+                              const int32_t *jam, const int32_t *kth, const int32_t *fix, int pair0, int32_t *cells_out, double *y_out,
+                              int32_t *flags_out) {
     const int n = blockIdx.x * blockDim.x + threadIdx.x;
     if (n >= n_starts) return;
     const int cells = g.T * g.X;
@@ -177,7 +247,9 @@ __global__ void lookup_kernel(Grid g, const double *starts, int n_starts, const 
     cells_out[3 * r + 2] = cf;
     y_out[2 * r] = pose_y(y0, touch_l[o + ck], touch_r[o + ck], S[o + ck], g.travel_max);
     y_out[2 * r + 1] = pose_y(y0, touch_l[o + cf], touch_r[o + cf], S[o + cf], g.travel_max);
-    flags_out[r] = (S[o + c0] >= g.travel_max ? 1 : 0) | (S[o + cf] >= g.travel_max ? 2 : 0) | ((bf == 0 || bf == g.X - 1) ? 4 : 0);
+    int fl = (S[o + c0] >= g.travel_max ? 1 : 0) | (S[o + cf] >= g.travel_max ? 2 : 0) | ((bf == 0 || bf == g.X - 1) ? 4 : 0);
+    if (jam) fl |= (jam[o + c0] ? 8 : 0) | (jam[o + cf] ? 16 : 0);
+    flags_out[r] = fl;
 }
 
 // The objective's value of every pair from its map (include/dgdm_hip.h, dgdm_squeeze_objective_values): one wave per pair, every lane its
@@ -221,9 +293,9 @@ __global__ __launch_bounds__(64) void squeeze_values_kernel(ValueGrid g, const i
 
 inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 
-// workspace of a chunk of n pairs: [pairs | touch_l | touch_r | S | succ | ping | pong | kth]
-struct Layout { size_t pairs, tl, tr, S, succ, ping, pong, kth, bytes; };
-Layout layout(int64_t cells, int64_t n) {
+// workspace of a chunk of n pairs: [pairs | touch_l | touch_r | S | succ | ping | pong | kth] and, with friction, [jam] behind them
+struct Layout { size_t pairs, tl, tr, S, succ, ping, pong, kth, jam, bytes; };
+Layout layout(int64_t cells, int64_t n, bool friction = false) {
     Layout L;
     const size_t d = align256(sizeof(double) * (size_t)(cells * n)), i = align256(sizeof(int32_t) * (size_t)(cells * n));
     L.pairs = 0;
@@ -234,7 +306,8 @@ Layout layout(int64_t cells, int64_t n) {
     L.ping = L.succ + i;
     L.pong = L.ping + i;
     L.kth = L.pong + i;
-    L.bytes = L.kth + i;
+    L.jam = L.kth + i;
+    L.bytes = L.jam + (friction ? i : 0);
     return L;
 }
 
@@ -272,22 +345,25 @@ struct Outputs {
     int32_t *flags;
     double *S, *tl, *tr;
     int32_t *succ;
+    int32_t *jam;       // friction only
 };
 
-// The chunk loop of both entries: as many pairs per chunk as the workspace's `bytes` hold (the caller has checked that one fits);
-// `table(n, pairs, tl, tr, S, stream)` launches the entry's table kernel for the chunk's n pairs, whose (finger, object) are at `pairs`.
+// The chunk loop of all entries: as many pairs per chunk as the workspace's `bytes` hold (the caller has checked that one fits);
+// `table(n, p0, pairs, tl, tr, S, jam, stream)` launches the entry's table kernel for the chunk's n pairs from pair p0 on, whose (finger,
+// object) are at `pairs`.  `friction`: the chunk holds a jam table, which the table kernel fills and the successors and the flags read.
 template <class Table>
 int run_chunks(const DgdmSqueezeConfig *cfg, const Grid &g, const int32_t *pairs_host, int n_pairs, const double *starts_dev, int n_starts,
-               const Outputs &out, void *workspace_dev, int64_t bytes, hipStream_t s, Table table) {
+               const Outputs &out, void *workspace_dev, int64_t bytes, hipStream_t s, bool friction, Table table) {
     const int64_t cells = (int64_t)g.T * g.X;
-    int64_t chunk = std::min<int64_t>(std::min<int64_t>(n_pairs, MAX_CHUNK), bytes / (int64_t)layout(cells, 1).bytes + 1);
-    while (chunk > 1 && (int64_t)layout(cells, chunk).bytes > bytes) --chunk;
+    int64_t chunk = std::min<int64_t>(std::min<int64_t>(n_pairs, MAX_CHUNK), bytes / (int64_t)layout(cells, 1, friction).bytes + 1);
+    while (chunk > 1 && (int64_t)layout(cells, chunk, friction).bytes > bytes) --chunk;
     int rounds = 0;
     while (((int64_t)1 << rounds) < cells) ++rounds;                     // ceil(log2(cells)): no path is longer than cells - 1 steps
     const bool k_settles = rounds < 31 && (int64_t)cfg->closing_steps >= ((int64_t)1 << rounds);
 
-    const Layout L = layout(cells, chunk);
+    const Layout L = layout(cells, chunk, friction);
     uint8_t *ws = static_cast<uint8_t *>(workspace_dev);
+    int32_t *jam = friction ? reinterpret_cast<int32_t *>(ws + L.jam) : nullptr;
     int32_t *pairs = reinterpret_cast<int32_t *>(ws + L.pairs);
     double *tl = reinterpret_cast<double *>(ws + L.tl), *tr = reinterpret_cast<double *>(ws + L.tr), *S = reinterpret_cast<double *>(ws + L.S);
     int32_t *succ = reinterpret_cast<int32_t *>(ws + L.succ), *kth = reinterpret_cast<int32_t *>(ws + L.kth);
@@ -296,9 +372,9 @@ int run_chunks(const DgdmSqueezeConfig *cfg, const Grid &g, const int32_t *pairs
     for (int64_t p0 = 0; p0 < n_pairs; p0 += chunk) {
         const unsigned n = (unsigned)std::min<int64_t>(chunk, n_pairs - p0);
         DGDM_HIP_CHECK(hipMemcpyAsync(pairs, pairs_host + 2 * p0, sizeof(int32_t) * 2 * n, hipMemcpyHostToDevice, s));
-        table(n, pairs, tl, tr, S, s);
+        table(n, p0, pairs, tl, tr, S, jam, s);
         DGDM_HIP_CHECK(hipGetLastError());
-        hipLaunchKernelGGL(successor_kernel, dim3(cb, n), dim3(256), 0, s, g, S, succ);
+        hipLaunchKernelGGL(successor_kernel, dim3(cb, n), dim3(256), 0, s, g, S, (const int32_t *)jam, succ);
         DGDM_HIP_CHECK(hipGetLastError());
         hipLaunchKernelGGL(iota_kernel, dim3(cb, n), dim3(256), 0, s, (int)cells, kth);
         DGDM_HIP_CHECK(hipGetLastError());
@@ -315,8 +391,8 @@ int run_chunks(const DgdmSqueezeConfig *cfg, const Grid &g, const int32_t *pairs
         const int32_t *fix = power;                                      // succ^(2^rounds): every path has ended
         const int32_t *closed = k_settles ? fix : kth;
         if (n_starts > 0) {
-            hipLaunchKernelGGL(lookup_kernel, dim3((unsigned)((n_starts + 255) / 256), n), dim3(256), 0, s, g, starts_dev, n_starts, tl, tr, S, closed,
-                               fix, (int)p0, out.cells, out.y, out.flags);
+            hipLaunchKernelGGL(lookup_kernel, dim3((unsigned)((n_starts + 255) / 256), n), dim3(256), 0, s, g, starts_dev, n_starts, tl, tr, S,
+                               (const int32_t *)jam, closed, fix, (int)p0, out.cells, out.y, out.flags);
             DGDM_HIP_CHECK(hipGetLastError());
         }
         const size_t off = (size_t)p0 * cells, cnt = (size_t)n * cells;
@@ -324,6 +400,7 @@ int run_chunks(const DgdmSqueezeConfig *cfg, const Grid &g, const int32_t *pairs
         if (out.tl) DGDM_HIP_CHECK(hipMemcpyAsync(out.tl + off, tl, sizeof(double) * cnt, hipMemcpyDeviceToDevice, s));
         if (out.tr) DGDM_HIP_CHECK(hipMemcpyAsync(out.tr + off, tr, sizeof(double) * cnt, hipMemcpyDeviceToDevice, s));
         if (out.succ) DGDM_HIP_CHECK(hipMemcpyAsync(out.succ + off, succ, sizeof(int32_t) * cnt, hipMemcpyDeviceToDevice, s));
+        if (jam && out.jam) DGDM_HIP_CHECK(hipMemcpyAsync(out.jam + off, jam, sizeof(int32_t) * cnt, hipMemcpyDeviceToDevice, s));
     }
     DGDM_HIP_CHECK(hipStreamSynchronize(s));        // the pair list's host buffer belongs to the caller
     return DGDM_OK;
@@ -543,14 +620,15 @@ extern "C" int64_t dgdm_squeeze_workspace_bytes(const DgdmSqueezeConfig *cfg, in
     return (int64_t)layout((int64_t)cfg->theta_cells * cfg->x_cells, chunk_pairs).bytes;
 }
 
-extern "C" int dgdm_squeeze_map(const DgdmSqueezeConfig *cfg, const double *surfaces_dev, int n_fingers, int num_points,
-                                const double *objects_dev, int n_objects, int num_vertices, const int32_t *pairs_host, int n_pairs,
-                                const double *rot_dev, const double *starts_dev, int n_starts, int32_t *cells_dev, double *y_dev,
-                                int32_t *flags_dev, double *table_s_dev, double *touch_l_dev, double *touch_r_dev, int32_t *succ_dev,
-                                void *workspace_dev, int64_t workspace_bytes, void *stream) {
-    const char *fn = "dgdm_squeeze_map";
+// The body of dgdm_squeeze_map (friction = false: mu, jam_dev and contact_dev unused) and dgdm_squeeze_map_friction.
+static int squeeze_map_common(const char *fn, bool friction, double mu, const DgdmSqueezeConfig *cfg, const double *surfaces_dev, int n_fingers,
+                              int num_points, const double *objects_dev, int n_objects, int num_vertices, const int32_t *pairs_host, int n_pairs,
+                              const double *rot_dev, const double *starts_dev, int n_starts, int32_t *cells_dev, double *y_dev, int32_t *flags_dev,
+                              double *table_s_dev, double *touch_l_dev, double *touch_r_dev, int32_t *succ_dev, int32_t *jam_dev,
+                              int32_t *contact_dev, void *workspace_dev, int64_t workspace_bytes, void *stream) {
     int rc = check_config(cfg, fn);
     if (rc) return rc;
+    DGDM_REQUIRE(!friction || (std::isfinite(mu) && mu >= 0.0), DGDM_EINVAL, "%s: friction coefficient %g (need finite, >= 0)", fn, mu);
     DGDM_REQUIRE(surfaces_dev && objects_dev && pairs_host && rot_dev && workspace_dev, DGDM_EINVAL, "%s: null argument", fn);
     DGDM_REQUIRE(n_fingers >= 1 && n_objects >= 1 && n_pairs >= 1, DGDM_EINVAL, "%s: %d fingers, %d objects, %d pairs (need >= 1 each)", fn,
                  n_fingers, n_objects, n_pairs);
@@ -564,21 +642,53 @@ extern "C" int dgdm_squeeze_map(const DgdmSqueezeConfig *cfg, const double *surf
                      DGDM_EINVAL, "%s: pair %d = (finger %d, object %d) outside %d fingers x %d objects", fn, p, pairs_host[2 * p],
                      pairs_host[2 * p + 1], n_fingers, n_objects);
     const int64_t cells = (int64_t)cfg->theta_cells * cfg->x_cells;
-    DGDM_REQUIRE(workspace_bytes >= (int64_t)layout(cells, 1).bytes, DGDM_EINVAL,
-                 "%s: workspace of %lld bytes holds no pair, one needs %lld (dgdm_squeeze_workspace_bytes)", fn, (long long)workspace_bytes,
-                 (long long)layout(cells, 1).bytes);
+    DGDM_REQUIRE(workspace_bytes >= (int64_t)layout(cells, 1, friction).bytes, DGDM_EINVAL,
+                 "%s: workspace of %lld bytes holds no pair, one needs %lld (%s)", fn, (long long)workspace_bytes,
+                 (long long)layout(cells, 1, friction).bytes, friction ? "dgdm_squeeze_friction_workspace_bytes" : "dgdm_squeeze_workspace_bytes");
     Grid g = grid_of(cfg);
     g.m = num_points;
     g.nv = num_vertices;
     g.hl = cfg->finger_half_len;
     g.h = 2.0 * cfg->finger_half_len / (double)(num_points - 1);
     const size_t lds = sizeof(double) * (size_t)(2 * g.m + 2 * g.nv);
-    Outputs out = {cells_dev, y_dev, flags_dev, table_s_dev, touch_l_dev, touch_r_dev, succ_dev};
-    return run_chunks(cfg, g, pairs_host, n_pairs, starts_dev, n_starts, out, workspace_dev, workspace_bytes, (hipStream_t)stream,
-                      [&](unsigned n, const int32_t *pairs, double *tl, double *tr, double *S, hipStream_t s) {
-                          hipLaunchKernelGGL(table_kernel, dim3((unsigned)g.T, n), dim3(TABLE_THREADS), lds, s, g, surfaces_dev, objects_dev, pairs,
-                                             rot_dev, tl, tr, S);
+    Outputs out = {cells_dev, y_dev, flags_dev, table_s_dev, touch_l_dev, touch_r_dev, succ_dev, jam_dev};
+    return run_chunks(cfg, g, pairs_host, n_pairs, starts_dev, n_starts, out, workspace_dev, workspace_bytes, (hipStream_t)stream, friction,
+                      [&](unsigned n, int64_t p0, const int32_t *pairs, double *tl, double *tr, double *S, int32_t *jam, hipStream_t s) {
+                          if (friction)
+                              hipLaunchKernelGGL(table_kernel<true>, dim3((unsigned)g.T, n), dim3(TABLE_THREADS), lds, s, g, surfaces_dev, objects_dev,
+                                                 pairs, rot_dev, tl, tr, S, mu, jam, contact_dev ? contact_dev + 2 * p0 * cells : nullptr);
+                          else
+                              hipLaunchKernelGGL(table_kernel<false>, dim3((unsigned)g.T, n), dim3(TABLE_THREADS), lds, s, g, surfaces_dev, objects_dev,
+                                                 pairs, rot_dev, tl, tr, S, 0.0, (int32_t *)nullptr, (int32_t *)nullptr);
                       });
+}
+
+extern "C" int dgdm_squeeze_map(const DgdmSqueezeConfig *cfg, const double *surfaces_dev, int n_fingers, int num_points,
+                                const double *objects_dev, int n_objects, int num_vertices, const int32_t *pairs_host, int n_pairs,
+                                const double *rot_dev, const double *starts_dev, int n_starts, int32_t *cells_dev, double *y_dev,
+                                int32_t *flags_dev, double *table_s_dev, double *touch_l_dev, double *touch_r_dev, int32_t *succ_dev,
+                                void *workspace_dev, int64_t workspace_bytes, void *stream) {
+    return squeeze_map_common("dgdm_squeeze_map", false, 0.0, cfg, surfaces_dev, n_fingers, num_points, objects_dev, n_objects, num_vertices,
+                              pairs_host, n_pairs, rot_dev, starts_dev, n_starts, cells_dev, y_dev, flags_dev, table_s_dev, touch_l_dev, touch_r_dev,
+                              succ_dev, nullptr, nullptr, workspace_dev, workspace_bytes, stream);
+}
+
+extern "C" int64_t dgdm_squeeze_friction_workspace_bytes(const DgdmSqueezeConfig *cfg, int chunk_pairs) {
+    const char *fn = "dgdm_squeeze_friction_workspace_bytes";
+    if (check_config(cfg, fn)) return DGDM_EINVAL;
+    DGDM_REQUIRE(chunk_pairs >= 1 && chunk_pairs <= MAX_CHUNK, DGDM_EINVAL, "%s: %d pairs per chunk (need 1 .. %d)", fn, chunk_pairs, MAX_CHUNK);
+    return (int64_t)layout((int64_t)cfg->theta_cells * cfg->x_cells, chunk_pairs, true).bytes;
+}
+
+extern "C" int dgdm_squeeze_map_friction(const DgdmSqueezeConfig *cfg, const double *surfaces_dev, int n_fingers, int num_points,
+                                         const double *objects_dev, int n_objects, int num_vertices, const int32_t *pairs_host, int n_pairs,
+                                         const double *rot_dev, const double *starts_dev, int n_starts, int32_t *cells_dev, double *y_dev,
+                                         int32_t *flags_dev, double *table_s_dev, double *touch_l_dev, double *touch_r_dev, int32_t *succ_dev,
+                                         void *workspace_dev, int64_t workspace_bytes, void *stream, double mu, int32_t *jam_dev,
+                                         int32_t *contact_dev) {
+    return squeeze_map_common("dgdm_squeeze_map_friction", true, mu, cfg, surfaces_dev, n_fingers, num_points, objects_dev, n_objects,
+                              num_vertices, pairs_host, n_pairs, rot_dev, starts_dev, n_starts, cells_dev, y_dev, flags_dev, table_s_dev,
+                              touch_l_dev, touch_r_dev, succ_dev, jam_dev, contact_dev, workspace_dev, workspace_bytes, stream);
 }
 
 extern "C" int dgdm_squeeze_objective_values(const DgdmSqueezeConfig *cfg, const int32_t *cells_dev, const double *y_dev, const double *starts_dev,
@@ -732,9 +842,9 @@ extern "C" int dgdm_squeeze_map_3d(const DgdmSqueezeConfig *cfg, const double *s
     const Grid g = grid_of(cfg);
     Grid3 g3 = {g.T, g.X, mu, mv, g.x_half, g.dx};
     const size_t lds = sizeof(double) * (size_t)(2 * mu * mv + mu + 4 * SEG_TILE) + sizeof(int32_t) * (size_t)(mv + 1);
-    Outputs out = {cells_dev, y_dev, flags_dev, table_s_dev, touch_l_dev, touch_r_dev, succ_dev};
-    return run_chunks(cfg, g, pairs_host, n_pairs, starts_dev, n_starts, out, workspace_dev, chunk_bytes, s,
-                      [&](unsigned n, const int32_t *pairs, double *tl, double *tr, double *S, hipStream_t st) {
+    Outputs out = {cells_dev, y_dev, flags_dev, table_s_dev, touch_l_dev, touch_r_dev, succ_dev, nullptr};
+    return run_chunks(cfg, g, pairs_host, n_pairs, starts_dev, n_starts, out, workspace_dev, chunk_bytes, s, false,
+                      [&](unsigned n, int64_t, const int32_t *pairs, double *tl, double *tr, double *S, int32_t *, hipStream_t st) {
                           hipLaunchKernelGGL(table3d_kernel, dim3((unsigned)g3.T, n), dim3(TABLE_THREADS), lds, st, g3, surfaces_dev, gx, segments_dev,
                                              offs, pairs, rot_dev, tl, tr, S);
                       });

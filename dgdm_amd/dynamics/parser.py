@@ -44,13 +44,16 @@ _FLAGS = [
                                   "final_* scores and 'convergence' see a settled pose (40 = the simulator's count; 0 = one interaction)"),
     ("predicted_render", "flag", None, "with --predicted_sim, 3-D, objects from mesh files: also write <object>_<gripper>_gripper.png for every pair and, "
                                        "for settled poses asked with render_last, <object>_<gripper>/<v>.png (sim/render_mesh.py)"),
-    ("squeeze_sim", "flag", None, "2-D, --mode=test: fill the objective tables with the squeeze simulator (sim/squeeze.py: a frictionless, "
+    ("squeeze_sim", "flag", None, "2-D, --mode=test: fill the objective tables with the squeeze simulator (sim/squeeze.py: a frictionless - with --squeeze_friction a jamming-by-friction -, "
                                   "quasi-static parallel-jaw squeeze; its own model, not MuJoCo's); the scores are marked 'simulated': 'squeeze'"),
     ("squeeze_sim_3d", "flag", None, "--fingers_3d, --mode=test, objects from mesh files: fill the objective tables with the sliced squeeze simulator "
                                      "(sim/squeeze.py SqueezeSimulator3D: the 2-D model on the finger grid's horizontal planes); marked "
                                      "'simulated': 'squeeze'"),
     ("squeeze_closing_steps", int, None, "with --squeeze_sim / --squeeze_sim_3d: grid steps the object climbs in one closing (default 6; untuned)"),
     ("squeeze_window", int, None, "with --squeeze_sim / --squeeze_sim_3d: half-width in cells of the neighbourhood a step searches (default 2; untuned)"),
+    ("squeeze_friction", float, None, "with --squeeze_sim or --resample_potential squeeze (2-D only, refused with --squeeze_sim_3d): the Coulomb "
+                                      "friction coefficient of the squeeze - poses whose two contacts hold the object are jammed and stay where "
+                                      "they are (default: none, the frictionless model; untuned)"),
     ("score_stats", str, None, "dynamics training: the stats.json sim/sim_2d.py or sim/sim_3d.py wrote beside its data; scores are divided by its score_std "
                                "instead of the reference's constants"),
     ("save_meshes", "flag", None, "also export every emitted gripper as OBJ meshes, collision pieces and gripper_<idx>.xml (assets/finger_mesh.py)"),
@@ -98,7 +101,7 @@ _FLAGS = [
     ("resample_ess", float, None, "with --resample_every: resample when the effective sample size falls below this fraction of the fingers "
                                   "(default 0.5; above 1: at every evaluation)"),
     ("resample_potential", str, "model", "with --resample_every: whose objective weighs the fingers - 'model' (the dynamics model's at (x_t, t)) or "
-                                         "'squeeze' (the squeeze simulator's on the predicted clean design: 2-D only, frictionless, this project's "
+                                         "'squeeze' (the squeeze simulator's on the predicted clean design: 2-D only, frictionless unless --squeeze_friction is given, this project's "
                                          "own mechanism, not MuJoCo's; honours --squeeze_closing_steps / --squeeze_window)"),
     ("resample_squeeze_cells", str, None, "with --resample_potential squeeze: the squeeze table's theta,x cells as T,X (default: the squeeze defaults, "
                                           "720,241)"),

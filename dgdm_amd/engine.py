@@ -1126,15 +1126,23 @@ def squeeze_config(**kw) -> _lib.SqueezeConfig:
 
 
 def squeeze_tables(surfaces, objects, pairs, starts=None, rot=None, tables: bool = False, workspace_bytes: Optional[int] = None,
-                   **config) -> Dict[str, torch.Tensor]:
+                   friction: float = 0.0, jam: bool = False, contact: bool = False, **config) -> Dict[str, torch.Tensor]:
     """dgdm_squeeze_map (include/dgdm_hip.h "squeeze simulator") on the current device.  surfaces (F, 2, m) float64: the
     lower and upper jaw surface at travel 0; objects (O, nv, 2) float64 polygons; pairs (P, 2) (finger, object), host; starts (N, 3)
     float64 (theta0, x0, y0) shared by all pairs, or None; rot: squeeze_rotation_table(theta_cells) when None; config: the keys of
     SQUEEZE_DEFAULTS.  -> cells (P, N, 3) int32 (start, closed, settled cell = a * x_cells + b), y (P, N, 2) float64, flags (P, N) int32
     and, with tables, S / touch_l / touch_r (P, theta_cells, x_cells) float64 and succ (P, theta_cells * x_cells) int32.  The pairs run in
-    chunks of as many as workspace_bytes holds.  Synchronises the stream once."""
+    chunks of as many as workspace_bytes holds.  Synchronises the stream once.
+    friction: the Coulomb coefficient mu of dgdm_squeeze_map_friction ("squeeze simulator with Coulomb friction"); that entry runs when
+    friction > 0 or when its tables are asked for - jam (P, theta_cells, x_cells) int32 and contact (P, theta_cells, x_cells, 2) int32
+    (the lower and upper contact's code), both also returned with tables=True - and flags then carries 8 / 16 (start / settled cell
+    jammed).  Otherwise dgdm_squeeze_map runs, as it always did."""
     cfg = squeeze_config(**config)
-    one = lib().dgdm_squeeze_workspace_bytes(C.byref(cfg), 1)
+    mu = float(friction)
+    if not (np.isfinite(mu) and mu >= 0.0):
+        raise ValueError(f"squeeze_tables: friction {friction!r} is not a finite non-negative number")
+    with_friction = mu > 0.0 or bool(jam) or bool(contact)
+    one = (lib().dgdm_squeeze_friction_workspace_bytes if with_friction else lib().dgdm_squeeze_workspace_bytes)(C.byref(cfg), 1)
     if one < 0:
         _check_value(int(one))
     dev = torch.device("cuda", torch.cuda.current_device())
@@ -1156,10 +1164,17 @@ def squeeze_tables(surfaces, objects, pairs, starts=None, rot=None, tables: bool
     if tables:
         out.update({k: new(P, max(T, 0), max(X, 0), dtype=torch.float64) for k in ("S", "touch_l", "touch_r")})
         out["succ"] = new(P, max(T, 0) * max(X, 0), dtype=torch.int32)
-    _check_value(lib().dgdm_squeeze_map(C.byref(cfg), dptr(sf), int(sf.shape[0]), int(sf.shape[2]), dptr(ob), int(ob.shape[0]), int(ob.shape[1]),
-                                        pr.ctypes.data, P, dptr(rt), dptr(st), N, dptr(out["cells"]), dptr(out["y"]), dptr(out["flags"]),
-                                        dptr(out.get("S")), dptr(out.get("touch_l")), dptr(out.get("touch_r")), dptr(out.get("succ")), dptr(ws),
-                                        ws_bytes, stream_ptr()))
+    if with_friction and (tables or jam):
+        out["jam"] = new(P, max(T, 0), max(X, 0), dtype=torch.int32)
+    if with_friction and (tables or contact):
+        out["contact"] = new(P, max(T, 0), max(X, 0), 2, dtype=torch.int32)
+    args = (C.byref(cfg), dptr(sf), int(sf.shape[0]), int(sf.shape[2]), dptr(ob), int(ob.shape[0]), int(ob.shape[1]), pr.ctypes.data, P, dptr(rt),
+            dptr(st), N, dptr(out["cells"]), dptr(out["y"]), dptr(out["flags"]), dptr(out.get("S")), dptr(out.get("touch_l")),
+            dptr(out.get("touch_r")), dptr(out.get("succ")), dptr(ws), ws_bytes, stream_ptr())
+    if with_friction:
+        _check_value(lib().dgdm_squeeze_map_friction(*args, mu, dptr(out.get("jam")), dptr(out.get("contact"))))
+    else:
+        _check_value(lib().dgdm_squeeze_map(*args))
     return out
 
 

@@ -377,10 +377,26 @@ def fit(model: Diffusion, pts: np.ndarray, args, bounds, dev) -> Diffusion:
     return model
 
 
+def squeeze_friction_from_args(args):
+    """--squeeze_friction MU -> mu, or None without the flag.  ValueError: a negative or non-finite mu, --squeeze_sim_3d (friction is 2-D
+    only), no squeeze user (--squeeze_sim or --resample_potential squeeze).  Host-side checks only."""
+    mu = getattr(args, "squeeze_friction", None)
+    if mu is None:
+        return None
+    from ..sim.squeeze import FRICTION_2D_ONLY, check_friction
+    mu = check_friction(mu, "--squeeze_friction")
+    if getattr(args, "squeeze_sim_3d", False):
+        raise ValueError(f"--squeeze_friction with --squeeze_sim_3d: {FRICTION_2D_ONLY}")
+    if not getattr(args, "squeeze_sim", False) and (getattr(args, "resample_potential", None) or 'model') != 'squeeze':
+        raise ValueError("--squeeze_friction needs --squeeze_sim or --resample_potential squeeze")
+    return mu
+
+
 def squeeze_from_args(args):
-    """--squeeze_sim [--squeeze_closing_steps K --squeeze_window R] -> SqueezeSimulator's keywords, or None without the flag.  Host-side
-    checks only."""
+    """--squeeze_sim [--squeeze_closing_steps K --squeeze_window R --squeeze_friction MU] -> SqueezeSimulator's keywords, or None without
+    the flag.  Host-side checks only."""
     k, r = getattr(args, "squeeze_closing_steps", None), getattr(args, "squeeze_window", None)
+    mu = squeeze_friction_from_args(args)
     if not getattr(args, "squeeze_sim", False):
         if (k is not None or r is not None) and not getattr(args, "squeeze_sim_3d", False) and \
                 (getattr(args, "resample_potential", None) or 'model') != 'squeeze':
@@ -405,7 +421,7 @@ def squeeze_from_args(args):
         raise ValueError(f"--squeeze_closing_steps={k}: the number of steps cannot be negative")
     if r is not None and r < 1:
         raise ValueError(f"--squeeze_window={r}: the window is at least 1 cell")
-    return {key: v for key, v in (("closing_steps", k), ("window", r)) if v is not None}
+    return {key: v for key, v in (("closing_steps", k), ("window", r), ("friction", mu)) if v is not None}
 
 
 def squeeze_3d_from_args(args):
@@ -413,6 +429,7 @@ def squeeze_3d_from_args(args):
     Host-side checks only; that the run's objects are mesh files is checked where they are known (train)."""
     if not getattr(args, "squeeze_sim_3d", False):
         return None
+    squeeze_friction_from_args(args)        # --squeeze_friction: refused, friction is 2-D only
     k, r = getattr(args, "squeeze_closing_steps", None), getattr(args, "squeeze_window", None)
     if not getattr(args, "fingers_3d", False):
         raise ValueError("--squeeze_sim_3d needs --fingers_3d: it is the squeeze model for 3-D fingers (--squeeze_sim is the 2-D one)")

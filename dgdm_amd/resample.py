@@ -41,12 +41,15 @@ class SqueezePotential:
     checkpoints.
 
     contours (O, nv, 2) float64, metres: the object bank in the guidance handle's object order.  score_std: (theta rad, x m, y m), the
-    2-D SCORE_STD by default.  squeeze_config: engine.SQUEEZE_DEFAULTS' keys.  The rotation table, the bank and the start grid stay on
+    2-D SCORE_STD by default.  friction: the squeeze's Coulomb coefficient (0: frictionless; the values kernel reads the map's cells
+    and y either way).  squeeze_config: engine.SQUEEZE_DEFAULTS' keys.  The rotation table, the bank and the start grid stay on
     the device between evaluations."""
 
-    def __init__(self, contours, score_std=None, num_points: int = 200, **squeeze_config):
+    def __init__(self, contours, score_std=None, num_points: int = 200, friction: float = 0.0, **squeeze_config):
         import numpy as np
         from .dynamics.dataloader import SCORE_STD
+        from .sim.squeeze import check_friction
+        self.friction = check_friction(friction, "SqueezePotential")
         c = np.ascontiguousarray(np.asarray(contours, dtype=np.float64))
         if c.ndim != 3 or c.shape[2] != 2 or c.shape[0] < 1 or c.shape[1] < 3:
             raise ValueError(f"SqueezePotential: contours (O, nv, 2) with O >= 1, nv >= 3 expected, got {c.shape}")
@@ -65,7 +68,8 @@ class SqueezePotential:
         return int(self.contours.shape[0])
 
     def __repr__(self) -> str:
-        return f"SqueezePotential({self.n_objects} contours of {self.contours.shape[1]} vertices, {self.config})"
+        tail = f", friction={self.friction}" if self.friction > 0.0 else ""
+        return f"SqueezePotential({self.n_objects} contours of {self.contours.shape[1]} vertices, {self.config}{tail})"
 
     def starts(self, grid_size: int, num_pos: int, ori_range: Sequence[float]):
         """start_grid on the device, made once per grid."""
@@ -98,7 +102,7 @@ class SqueezePotential:
         sf = finger_surfaces(x0.reshape(nc * B, L), self.num_points)
         finger = (np.arange(nc, dtype=np.int32)[None, :, None] * B + np.arange(B, dtype=np.int32)[None, None, :]).repeat(n_grad, axis=0)
         pairs = np.stack([finger.reshape(-1), np.repeat(obj, B)], axis=1)
-        out = engine.squeeze_tables(sf, self._bank, pairs, st, rot=self._rot, **self.config)
+        out = engine.squeeze_tables(sf, self._bank, pairs, st, rot=self._rot, friction=self.friction, **self.config)
         return engine.squeeze_objective_values(out["cells"], out["y"], st, B, list(objectives), rowcoef, self.score_std, **self.config)
 
 
@@ -166,9 +170,9 @@ def summarise(log: Sequence, n_chains: int, batch: int) -> List[Dict[str, Any]]:
     return out
 
 
-def squeeze_potential_from_args(args) -> Optional[Dict[str, int]]:
-    """--resample_potential squeeze [--resample_squeeze_cells T,X --squeeze_closing_steps K --squeeze_window R] -> SqueezePotential's
-    squeeze_config, or None for the model's potential.  ValueError: an unknown potential, 'squeeze' with --fingers_3d (a sliced-squeeze
+def squeeze_potential_from_args(args) -> Optional[Dict[str, Any]]:
+    """--resample_potential squeeze [--resample_squeeze_cells T,X --squeeze_closing_steps K --squeeze_window R --squeeze_friction MU] ->
+    SqueezePotential's squeeze_config (and friction), or None for the model's potential.  ValueError: an unknown potential, 'squeeze' with --fingers_3d (a sliced-squeeze
     evaluation costs seconds, DESIGN.md 4.1d), with --goal_pose (goal fields have no squeeze form) or without --resample_every;
     --resample_squeeze_cells without it or not two positive integers."""
     potential = getattr(args, "resample_potential", None) or 'model'
@@ -185,7 +189,11 @@ def squeeze_potential_from_args(args) -> Optional[Dict[str, int]]:
         raise ValueError("--resample_potential squeeze is 2-D only: a sliced-squeeze evaluation of --fingers_3d costs seconds, not supported")
     if getattr(args, "goal_pose", None) is not None:
         raise ValueError("--resample_potential squeeze with --goal_pose: goal fields have no squeeze form, not supported")
-    config: Dict[str, int] = {}
+    config: Dict[str, Any] = {}
+    mu = getattr(args, "squeeze_friction", None)
+    if mu is not None:
+        from .sim.squeeze import check_friction
+        config["friction"] = check_friction(mu, "--squeeze_friction")
     if cells is not None:
         try:
             t, x = (int(v) for v in str(cells).split(","))

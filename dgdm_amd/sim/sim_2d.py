@@ -9,7 +9,8 @@ dict)`` with the keys and order below) on its 360 x 5 x 5 pose grid, so that ``p
 Poses run theta-major, then x, then y.  The motion is ONE closing of the squeeze model (sim/squeeze.py): a frictionless,
 quasi-static idealisation, not MuJoCo's scene - its deltas are multiples of the table's cell sizes in theta and x and differ in scale
 from the reference's data.  ``stats.json`` beside the files holds the configuration and the standard deviations of the three deltas;
-``dynamics/main.py --score_stats stats.json`` normalises with them (with the MuJoCo constants of dynamics/dataloader.py the squeeze
+``generate(..., friction=mu)`` / ``--friction MU`` squeezes with Coulomb friction (sim/squeeze.py: jammed poses stay where they are;
+this model's own rule, 2-D only); stats.json records ``"friction"``.  ``dynamics/main.py --score_stats stats.json`` normalises with them (with the MuJoCo constants of dynamics/dataloader.py the squeeze
 deltas are merely scaled oddly).  The class thresholds and the generator's ``Diffusion.std`` are not retuned here.
 """
 from __future__ import annotations
@@ -44,13 +45,15 @@ def gripper_design(gripper_idx: int):
     return x, yl, yr
 
 
-def generate(out_dir: str, gripper_ids: Sequence[int], contours, object_ids: Sequence[int], **config) -> List[str]:
+def generate(out_dir: str, gripper_ids: Sequence[int], contours, object_ids: Sequence[int], friction: float = 0.0, **config) -> List[str]:
     """Writes ``<out_dir>/<object>_<gripper>.npz`` for every (gripper, object) and ``<out_dir>/stats.json``; returns the data files.
     contours (O, nv, 2): the objects' contours in metres (extract_contours' output), object_ids their names.  config: the squeeze
-    model's (engine.SQUEEZE_DEFAULTS).  One device call for all pairs."""
+    model's (engine.SQUEEZE_DEFAULTS); friction: its Coulomb coefficient (0: frictionless), recorded in stats.json.  One device call for
+    all pairs."""
     from .. import engine
     from ..assets import finger_sampler
     from . import squeeze
+    friction = squeeze.check_friction(friction, "generate")
     contours = np.asarray(contours, dtype=np.float64)
     if contours.ndim != 3 or contours.shape[2] != 2 or len(contours) != len(object_ids):
         raise ValueError(f"generate: contours of shape {contours.shape} for {len(object_ids)} objects (need (O, nv, 2))")
@@ -58,11 +61,11 @@ def generate(out_dir: str, gripper_ids: Sequence[int], contours, object_ids: Seq
     shapes = [finger_sampler.generate_gripper(x, yl, yr, NUM_POINTS) for x, yl, yr in designs]
     samples = np.stack([np.concatenate([yl, yr]) for _, yl, yr in designs]).astype(np.float32)
     starts = pose_grid()
-    out = squeeze.squeeze_map(samples, contours, starts, scale=1.0, offset=0.0, num_points=NUM_POINTS, **config)
+    out = squeeze.squeeze_map(samples, contours, starts, scale=1.0, offset=0.0, num_points=NUM_POINTS, friction=friction, **config)
     start, closed = out["start"].cpu().numpy(), out["closed"].cpu().numpy()
     records = [(int(object_ids[o]), int(gripper_ids[f]), pair_record(*shapes[f], contours[o], starts, start[p], closed[p]))
                for p, (f, o) in enumerate(out["pairs"])]
-    return write_dataset(out_dir, records, engine.squeeze_config(**config), int(np.count_nonzero(out["flags"].cpu().numpy() & 1)))
+    return write_dataset(out_dir, records, engine.squeeze_config(**config), int(np.count_nonzero(out["flags"].cpu().numpy() & 1)), friction)
 
 
 def pair_record(ctrlpts, allpts, contour, starts, start, closed) -> dict:
@@ -81,9 +84,10 @@ def pair_record(ctrlpts, allpts, contour, starts, start, closed) -> dict:
     }
 
 
-def write_dataset(out_dir: str, records, cfg, loose_starts: int = 0) -> List[str]:
+def write_dataset(out_dir: str, records, cfg, loose_starts: int = 0, friction=None) -> List[str]:
     """records: (object_id, gripper_id, pair_record) per pair -> the data files and stats.json (the configuration and the standard
-    deviations of delta_theta, delta_pos x and delta_pos y over all files: DynamicsDataset's score_std).  Host code."""
+    deviations of delta_theta, delta_pos x and delta_pos y over all files: DynamicsDataset's score_std; "friction": the squeeze's Coulomb
+    coefficient, when one is given).  Host code."""
     os.makedirs(out_dir, exist_ok=True)
     files, deltas = [], []
     for object_id, gripper_id, save_data in records:
@@ -94,6 +98,8 @@ def write_dataset(out_dir: str, records, cfg, loose_starts: int = 0) -> List[str
     stats = {"simulated": SIMULATED, "config": {k: getattr(cfg, k) for k, _ in cfg._fields_}, "num_files": len(files),
              "gripper_ids": sorted({g for _, g, _ in records}), "object_ids": sorted({o for o, _, _ in records}),
              "loose_starts": int(loose_starts), "score_std": np.concatenate(deltas).std(axis=0).tolist()}
+    if friction is not None:
+        stats["friction"] = float(friction)
     with open(os.path.join(out_dir, "stats.json"), "w") as fh:
         json.dump(stats, fh, indent=1)
     return files
@@ -111,7 +117,10 @@ def main(argv=None):
     p.add_argument("--object_dir", required=True, help="the Icons-50 .npy file")
     p.add_argument("--squeeze_closing_steps", type=int, default=None)
     p.add_argument("--squeeze_window", type=int, default=None)
+    p.add_argument("--friction", type=float, default=0.0, help="Coulomb friction coefficient of the squeeze (default 0: frictionless)")
     a = p.parse_args(argv)
+    from .squeeze import check_friction
+    check_friction(a.friction, "--friction")
     from .. import _lib
     from ..assets import icon_process
     _lib.device_init(0)
@@ -119,7 +128,8 @@ def main(argv=None):
     images = np.load(a.object_dir, allow_pickle=True).item()['image'][object_ids].transpose((0, 2, 3, 1))
     contours = icon_process.extract_contours_batch(images)
     config = {k: v for k, v in (("closing_steps", a.squeeze_closing_steps), ("window", a.squeeze_window)) if v is not None}
-    files = generate(a.save_dir, list(range(a.gripper_idx, a.gripper_idx + a.num_gripper_parallel)), contours, object_ids, **config)
+    files = generate(a.save_dir, list(range(a.gripper_idx, a.gripper_idx + a.num_gripper_parallel)), contours, object_ids, friction=a.friction,
+                     **config)
     print(f"[dgdm_amd] wrote {len(files)} files and stats.json to {a.save_dir}")
 
 

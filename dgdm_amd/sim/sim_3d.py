@@ -35,13 +35,17 @@ def gripper_design(gripper_idx: int):
     return yl, yr
 
 
-def generate(out_dir: str, gripper_ids: Sequence[int], meshes, object_ids: Sequence[int], object_names: Sequence[str], **config) -> List[str]:
+def generate(out_dir: str, gripper_ids: Sequence[int], meshes, object_ids: Sequence[int], object_names: Sequence[str], friction=None,
+             **config) -> List[str]:
     """Writes ``<out_dir>/<object>_<gripper>.npz`` for every (gripper, object) and ``<out_dir>/stats.json``; returns the data files.
     meshes: (vertices (nv, 3) in metres, triangles (nt, 3)) per object, object_ids / object_names their numbers and names.  config: the
-    squeeze model's (engine.SQUEEZE_DEFAULTS).  One device call for all pairs."""
+    squeeze model's (engine.SQUEEZE_DEFAULTS).  One device call for all pairs.  Frictionless only: a ``friction`` argument is refused
+    (squeeze.FRICTION_2D_ONLY)."""
     from .. import engine
     from ..assets import finger_3d
     from . import squeeze
+    if friction is not None:
+        raise ValueError(f"sim_3d.generate: {squeeze.FRICTION_2D_ONLY}")
     meshes = list(meshes)
     if not (len(meshes) == len(object_ids) == len(object_names)):
         raise ValueError(f"generate: {len(meshes)} meshes for {len(object_ids)} object ids and {len(object_names)} names")
@@ -97,7 +101,11 @@ def main(argv=None):
     p.add_argument("--object_names", default="", help="file of object names, one per line (default: the directory's listing)")
     p.add_argument("--squeeze_closing_steps", type=int, default=None)
     p.add_argument("--squeeze_window", type=int, default=None)
+    p.add_argument("--friction", type=float, default=None, help="refused: friction is 2-D only (sim_2d.py --friction)")
     a = p.parse_args(argv)
+    if a.friction is not None:
+        from .squeeze import FRICTION_2D_ONLY
+        raise ValueError(f"sim_3d --friction: {FRICTION_2D_ONLY}")
     from .. import _lib, engine
     from ..dynamics.utils import MESH_FILE
     _lib.device_init(0)

@@ -6,6 +6,11 @@ soft position actuators; this model has neither).  What pins it are closed-form 
 of a rectangle between flat jaws, a disc in a V) and the float64 restatement tests/squeeze_oracle.py, which the device reproduces bit for
 bit.  A jaw that touches alone is assumed to carry the object along y without turning it.  ``window`` and ``closing_steps`` are untuned.
 
+Coulomb friction is an opt-in (``friction=mu``; include/dgdm_hip.h "squeeze simulator with Coulomb friction", DESIGN.md §4.1d "friction";
+tests/squeeze_friction_oracle.py): a cell whose two contacts hold the object against any squeezing force (the two-contact antipodal
+condition) is jammed and stays where it is; everything else moves as without friction - friction decides whether, not where, which is an
+assumption of the model.  ``friction=0`` is the frictionless model, bit for bit.  2-D only.
+
 * ``squeeze_map``        designs x contours -> closed and settled poses per start pose, on device tensors;
 * ``SqueezeSimulator``   a callable with the ``sim_test_batch`` signature for ``Diffusion(simulator=...)``: the tables that
                          ``--predicted_sim`` fills with the dynamics model's opinion, filled by this model instead and marked
@@ -63,18 +68,20 @@ def fold(delta, period: float):
 
 
 def squeeze_map(samples, contours, starts, pairs=None, num_points: int = 200, scale: Optional[float] = None, offset: Optional[float] = None,
-                tables: bool = False, workspace_bytes: Optional[int] = None, **config) -> Dict[str, Any]:
+                tables: bool = False, workspace_bytes: Optional[int] = None, friction: float = 0.0, **config) -> Dict[str, Any]:
     """samples (B, L[, 1]) designs, contours (O, nv, 2) polygons in metres, starts (N, 3) = (theta0 rad, x0 m, y0 m) shared by all pairs,
     pairs (P, 2) (finger, object) or None = all, object-major.  config: engine.SQUEEZE_DEFAULTS' keys.  Device tensors:
       closed, settled (P, N, 3) float64 = (theta rad, x m, y m) after one closing and settled;  start (P, N, 2) = the snapped start cell's
       (theta, x);  cells (P, N, 3) int32;  flags (P, N) int32 (1 loose at the start, 2 ended loose, 4 cut by the x range);  with tables:
-      S, touch_l, touch_r (P, theta_cells, x_cells), succ."""
+      S, touch_l, touch_r (P, theta_cells, x_cells), succ.  friction: the Coulomb coefficient mu (0: frictionless); with mu > 0 flags also
+      carries 8 (the start cell is jammed) and 16 (the settled cell is), and tables adds jam and contact (engine.squeeze_tables)."""
     import torch
     from .. import engine
     sf = finger_surfaces(samples, num_points, scale, offset)
     ob = torch.as_tensor(contours)
     pr = all_pairs(sf.shape[0], ob.shape[0]) if pairs is None else np.ascontiguousarray(pairs, dtype=np.int32).reshape(-1, 2)
-    out = engine.squeeze_tables(sf, ob, pr, starts, tables=tables, workspace_bytes=workspace_bytes, **config)
+    out = engine.squeeze_tables(sf, ob, pr, starts, tables=tables, workspace_bytes=workspace_bytes, friction=check_friction(friction, "squeeze_map"),
+                                **config)
     cfg = engine.squeeze_config(**config)
     T, X = cfg.theta_cells, cfg.x_cells
     cells = out["cells"].long()
@@ -87,22 +94,34 @@ def squeeze_map(samples, contours, starts, pairs=None, num_points: int = 200, sc
     return out
 
 
-def squeeze_metric(start, closed, settled, flags, y0=0.0, threshold: Sequence[float] = SCORE_THRESHOLD[1]) -> Dict[str, Any]:
+def check_friction(friction, who: str) -> float:
+    """The Coulomb coefficient as a float; ValueError for a negative or non-finite one.  Host code."""
+    mu = float(friction)
+    if not (np.isfinite(mu) and mu >= 0.0):
+        raise ValueError(f"{who}: friction {friction!r} is not a finite non-negative number")
+    return mu
+
+
+def squeeze_metric(start, closed, settled, flags, y0=0.0, threshold: Sequence[float] = SCORE_THRESHOLD[1], friction: float = 0.0) -> Dict[str, Any]:
     """The metric dict of one (object, gripper) with build_metric's keys (dynamics/predicted.py, sim_test_mj.py:209-218) from
     squeeze_map's rows over the start orientations: start (n, 2), closed / settled (n, 3), flags (n,), host arrays.  One-step keys from
     one closing, classes with ``threshold`` in radians and metres as sim_test_mj.py:198-200 (+ 1); ``final_*`` from the settled pose;
-    degrees and centimetres."""
+    degrees and centimetres.  With friction > 0 (and only then) the dict also holds ``'squeeze_friction'``: mu and ``'squeeze_jammed'``: the
+    number of starts that settled on a jammed cell (flag 16)."""
     st, cl, se = (np.asarray(a, dtype=np.float64) for a in (start, closed, settled))
     fl = np.asarray(flags).reshape(-1)
     thr = np.asarray(threshold, dtype=np.float64).reshape(3)
     d = np.stack([fold(cl[:, 0] - st[:, 0], 2.0 * np.pi), cl[:, 1] - st[:, 1], cl[:, 2] - y0], axis=1)
     cls = np.where(d > thr, 2, np.where(d < -thr, 0, 1)).astype(np.int64)
     zeros = np.zeros(len(d))
-    return {'delta_theta': d[:, 0] * DEG, 'delta_pos': np.stack([d[:, 1] * CM, d[:, 2] * CM, zeros], axis=1),
-            'profile': cls[:, 0], 'profile_x': cls[:, 1], 'profile_y': cls[:, 2],
-            'final_theta': se[:, 0] * DEG, 'final_delta_theta': fold(se[:, 0] - st[:, 0], 2.0 * np.pi) * DEG,
-            'final_pos': np.stack([se[:, 1] * CM, se[:, 2] * CM, zeros], axis=1),
-            'simulated': SIMULATED, 'squeeze_loose': int(np.count_nonzero(fl & 1)), 'squeeze_cut': int(np.count_nonzero(fl & 4))}
+    out = {'delta_theta': d[:, 0] * DEG, 'delta_pos': np.stack([d[:, 1] * CM, d[:, 2] * CM, zeros], axis=1),
+           'profile': cls[:, 0], 'profile_x': cls[:, 1], 'profile_y': cls[:, 2],
+           'final_theta': se[:, 0] * DEG, 'final_delta_theta': fold(se[:, 0] - st[:, 0], 2.0 * np.pi) * DEG,
+           'final_pos': np.stack([se[:, 1] * CM, se[:, 2] * CM, zeros], axis=1),
+           'simulated': SIMULATED, 'squeeze_loose': int(np.count_nonzero(fl & 1)), 'squeeze_cut': int(np.count_nonzero(fl & 4))}
+    if float(friction) > 0.0:
+        out.update({'squeeze_friction': float(friction), 'squeeze_jammed': int(np.count_nonzero(fl & 16))})
+    return out
 
 
 class SqueezeSimulator:
@@ -114,11 +133,13 @@ class SqueezeSimulator:
     x0 = y0 = 0.  It carries ``'simulated': 'squeeze'``, ``'squeeze_loose'`` and ``'squeeze_cut'`` and never ``'predicted'``: these are
     this model's results, not MuJoCo measurements and not the dynamics model's opinion.  Nothing is rendered: the plot slots are None.
     2-D only.  The call draws no random number and touches none of the sampling path's handles, so the sampled designs are the same
-    with the simulator on or off."""
+    with the simulator on or off.  ``friction``: the Coulomb coefficient mu (0: frictionless); with mu > 0 the metrics also carry
+    ``'squeeze_friction'`` and ``'squeeze_jammed'``."""
 
-    def __init__(self, diffusion, closing_steps: Optional[int] = None, window: Optional[int] = None, **config):
+    def __init__(self, diffusion, closing_steps: Optional[int] = None, window: Optional[int] = None, friction: float = 0.0, **config):
         if getattr(diffusion, "mode", "point") == 'point_3d':
             raise ValueError("SqueezeSimulator: the squeeze model is 2-D only")
+        self.friction = check_friction(friction, "SqueezeSimulator")
         self.diffusion = diffusion
         self.config = dict(config)
         if closing_steps is not None:
@@ -143,10 +164,10 @@ class SqueezeSimulator:
         bank = torch.as_tensor(d.object_vertices).detach().cpu().double()[oidx] * OBJECT_HALF_BOX_2D
         theta0 = (np.linspace(ori_range[0], ori_range[1], int(num_rot)) + 1.0) * np.pi
         starts = np.stack([theta0, np.zeros_like(theta0), np.zeros_like(theta0)], axis=1)
-        out = squeeze_map(x.reshape(n, -1), bank, starts, **self.config)
+        out = squeeze_map(x.reshape(n, -1), bank, starts, friction=self.friction, **self.config)
         start, closed, settled, flags = (out[k].cpu().numpy() for k in ("start", "closed", "settled", "flags"))
         thr = SCORE_THRESHOLD[1]
-        metrics = [squeeze_metric(start[p], closed[p], settled[p], flags[p], 0.0, thr) for p in range(len(oidx) * n)]
+        metrics = [squeeze_metric(start[p], closed[p], settled[p], flags[p], 0.0, thr, self.friction) for p in range(len(oidx) * n)]
         none: List[Any] = [None] * (len(oidx) * n)
         return list(none), metrics, list(none), list(none), list(none), list(none), [[] for _ in none], list(none)
 
@@ -157,6 +178,8 @@ class SqueezeSimulator:
 # the face that looks at the object, L = yl - 0.23 + width; the right jaw's body at y = +0.23 (:135), its decoded surface itself looking
 # at the object, U = yr + 0.23
 LOWER_OFFSET_3D, UPPER_OFFSET_3D, FINGER_WIDTH_3D = -0.23, 0.23, 0.1
+FRICTION_2D_ONLY = ("friction is 2-D only: the contact normals of 3-D fingers have a z component that the sliced, per-plane model does not "
+                    "see")
 
 
 def finger_surfaces_3d(samples, sample_size: int = 25, width: float = FINGER_WIDTH_3D, scale: Optional[float] = None, offset: Optional[float] = None):
@@ -181,13 +204,16 @@ def finger_surfaces_3d(samples, sample_size: int = 25, width: float = FINGER_WID
 
 
 def squeeze_map_3d(samples, meshes, starts, pairs=None, sample_size: int = 25, width: float = FINGER_WIDTH_3D, scale: Optional[float] = None,
-                   offset: Optional[float] = None, tables: bool = False, workspace_bytes: Optional[int] = None, **config) -> Dict[str, Any]:
+                   offset: Optional[float] = None, tables: bool = False, workspace_bytes: Optional[int] = None, friction=None,
+                   **config) -> Dict[str, Any]:
     """squeeze_map for 3-D fingers: samples (B, 42[, 1]) designs, meshes a sequence of (vertices (nv, 3) in metres, triangles (nt, 3)) in
     the scene's frame (standing on z = 0), starts (N, 3) = (theta0 rad, x0 m, y0 m) shared by all pairs.  The meshes are sliced on the
     finger grid's levels (engine.squeeze_slice) and squeezed level by level (engine.squeeze_tables_3d); what lies between two levels is
-    not seen.  Output keys as squeeze_map, plus segments / offsets."""
+    not seen.  Output keys as squeeze_map, plus segments / offsets.  Frictionless only: a ``friction`` argument is refused (FRICTION_2D_ONLY)."""
     import torch
     from .. import engine
+    if friction is not None:
+        raise ValueError(f"squeeze_map_3d: {FRICTION_2D_ONLY}")
     gx, gz, sf = finger_surfaces_3d(samples, sample_size, width, scale, offset)
     sl = engine.squeeze_slice(meshes, gz)
     pr = all_pairs(sf.shape[0], len(sl["offsets"])) if pairs is None else np.ascontiguousarray(pairs, dtype=np.int32).reshape(-1, 2)
@@ -210,10 +236,13 @@ class SqueezeSimulator3D:
     save_dir, num_cpus=, num_rot=, ori_range=, render=, render_last=)`` -> the same eight lists as ``SqueezeSimulator``, object-major,
     gripper-minor.  An object name is read from ``<object_mesh_dir>/<name>/model.obj`` (engine.read_obj) as it stands, in metres; a run
     whose objects have no meshes (objects.npy, synthetic clouds) is refused with a ValueError - a point cloud has no cross-section.
-    Metrics: ``squeeze_metric`` with the 3-D thresholds SCORE_THRESHOLD[0], marked ``'simulated': 'squeeze'`` and never ``'predicted'``."""
+    Metrics: ``squeeze_metric`` with the 3-D thresholds SCORE_THRESHOLD[0], marked ``'simulated': 'squeeze'`` and never ``'predicted'``.
+    Frictionless only: a ``friction`` argument is refused (FRICTION_2D_ONLY)."""
 
     def __init__(self, diffusion, object_mesh_dir: Optional[str] = None, closing_steps: Optional[int] = None, window: Optional[int] = None,
-                 sample_size: int = 25, width: float = FINGER_WIDTH_3D, **config):
+                 sample_size: int = 25, width: float = FINGER_WIDTH_3D, friction=None, **config):
+        if friction is not None:
+            raise ValueError(f"SqueezeSimulator3D: {FRICTION_2D_ONLY}")
         if getattr(diffusion, "mode", "point_3d") != 'point_3d':
             raise ValueError("SqueezeSimulator3D: the sliced squeeze is for 3-D fingers (mode 'point_3d'); SqueezeSimulator is the 2-D one")
         self.diffusion = diffusion

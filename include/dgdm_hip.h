@@ -812,6 +812,53 @@ int dgdm_squeeze_map(const DgdmSqueezeConfig *cfg, const double *surfaces_dev, i
                      double *touch_l_dev, double *touch_r_dev, int32_t *succ_dev, void *workspace_dev, int64_t workspace_bytes,
                      void *stream);
 
+/* ------------------------------------------------------------------ squeeze simulator with Coulomb friction (csrc/squeeze.hip,
+ * DESIGN.md §4.1d "friction")
+ * dgdm_squeeze_map with a friction coefficient mu between the jaws and the object, as an antipodal jamming rule.  It is this project's
+ * own model, stated exactly here, pinned to nothing in MuJoCo and claiming nothing about it; tests/squeeze_friction_oracle.py restates
+ * it in numpy float64 and the device reproduces that bit for bit.  2-D only.
+ * The model.  Friction decides WHETHER the object moves, not WHERE.  A cell in which both jaws touch and whose two contacts can hold the
+ *   object against any squeezing force - the line through the two contact points lies inside both friction cones (the two-contact
+ *   antipodal condition) - is JAMMED, and a jammed cell is a fixed point.  Every other cell moves by the frictionless rule above, the
+ *   climb of S: that a part which slides, slides where it would without friction is an ASSUMPTION of this model, not a result.  No
+ *   friction with the support plane, no jaw compliance.
+ * Contacts.  The candidates of a cell are visited for i = 0 .. nv - 1 in this order: the set-A candidate of vertex i, if
+ *   -hl <= P_ix <= hl; then the set-B candidates of the edge (P_i, P_{i+1}), j ascending from j0 to j1.  The lower and the upper contact
+ *   are tracked independently: each starts as "none" with the running least gap +inf and is replaced by a candidate whose gap is
+ *   strictly less than the running least gap of its side before that candidate - so each is the first candidate to attain the least
+ *   gap, and a NaN gap replaces nothing.  touch_l, touch_r and S are dgdm_squeeze_map's, bit for bit.
+ *   A contact is a point c on the object (in the cell's pose, the object at y = 0) and an unnormalised normal n from the jaw into the
+ *   object.  With (px, py) = P_i, (qx, qy) = P_{i+1}, e = (qx - px, qy - py), ye as above (its slope is e_y / e_x) and j of set A as
+ *   above:
+ *     lower, set A:  c = (P_ix, P_iy)   n = (-(L_{j+1} - L_j), h)
+ *     lower, set B:  c = (u_j, ye)      n = (-e_y, e_x) if e_x > 0, else (e_y, -e_x)
+ *     upper, set A:  c = (P_ix, P_iy)   n = (U_{j+1} - U_j, -h)
+ *     upper, set B:  c = (u_j, ye)      n = (e_y, -e_x) if e_x > 0, else (-e_y, e_x)
+ *   The code of a contact: i for set A, nv + i m + j for set B, -1 for none.
+ * Jam test, float64, every product, sum and difference rounded on its own in the order written, no transcendental function and no
+ *   normalisation (l: the lower contact, r: the upper):
+ *     dx = c_rx - c_lx;   dy = c_ry - c_ly
+ *     dot_l = n_lx dx + n_ly dy;       crs_l = n_lx dy - n_ly dx
+ *     dot_u = -(n_rx dx + n_ry dy);    crs_u = n_rx dy - n_ry dx
+ *     jam = both contacts exist && mu > 0 && S < travel_max && dot_l > 0 && dot_u > 0
+ *           && fabs(crs_l) <= mu dot_l && fabs(crs_u) <= mu dot_u                      (any NaN: not jammed)
+ *   mu = 0 jams nothing: the maps are dgdm_squeeze_map's bit for bit, jam is all 0, the contacts are still reported.
+ * Motion.  A jammed cell is its own successor, exactly as a cell with S >= travel_max is.  Everything else - the successor order, the
+ *   pointer doubling, the snap, y, closing_steps as "the k-th successor or the fixed point if reached first" - is dgdm_squeeze_map's.
+ *   Flags: 1, 2 and 4 as there; 8 = the start cell is jammed; 16 = the settled cell is jammed.
+ * Arguments: dgdm_squeeze_map's, then mu, then two optional outputs (null = not wanted), device memory: jam_dev
+ *   [n_pairs][theta_cells][x_cells] int32 (0 / 1) and contact_dev [n_pairs][theta_cells][x_cells][2] int32 = the code of the lower and of
+ *   the upper contact.  The jam table of a chunk lives in the workspace: dgdm_squeeze_friction_workspace_bytes(cfg, chunk_pairs) (negative:
+ *   bad config) is this entry's size function; at least one pair must fit.
+ * DGDM_EINVAL before any launch: a non-finite or negative mu, and everything dgdm_squeeze_map refuses.  Synchronises the stream once,
+ * at the end.                                                                                                                          */
+int64_t dgdm_squeeze_friction_workspace_bytes(const DgdmSqueezeConfig *cfg, int chunk_pairs);
+int dgdm_squeeze_map_friction(const DgdmSqueezeConfig *cfg, const double *surfaces_dev, int n_fingers, int num_points,
+                              const double *objects_dev, int n_objects, int num_vertices, const int32_t *pairs_host, int n_pairs,
+                              const double *rot_dev, const double *starts_dev, int n_starts, int32_t *cells_dev, double *y_dev,
+                              int32_t *flags_dev, double *table_s_dev, double *touch_l_dev, double *touch_r_dev, int32_t *succ_dev,
+                              void *workspace_dev, int64_t workspace_bytes, void *stream, double mu, int32_t *jam_dev, int32_t *contact_dev);
+
 /* The objective's VALUE per (pair) from a squeeze map: what dgdm_guidance_objective_values makes of the dynamics model's logits, made
  * of the squeeze model's one-closing deltas instead - a second opinion for resampling.  This project's own mechanism:
  * no counterpart in the reference, 2-D only, frictionless.  THE recipe (tests/resample_squeeze_oracle.py states the same text in numpy).

@@ -6,6 +6,9 @@ orientation and set against the vector float64 peak (78.6 TFLOP/s, AMD's figure 
 built without FMA contraction, so half of it is the most plain operations can reach).
   --oracle            also time the numpy oracle (tests/squeeze_oracle.py) on one pair on this host: the only baseline there is
   --windows 1,2,3,5   also print the mean settled S over all cells for these windows, design 0 on object 0 scaled by 1.5 (DESIGN.md 4.1d's table)
+  --friction MU       also time the call with Coulomb friction (dgdm_squeeze_map_friction) and report ms_friction, the share of jammed cells
+                      and of starts that settle jammed; the operation count above is the frictionless kernel's
+  --friction-only     with --friction: time only the friction call (for a kernel trace of its own)
   --tables-only       no starts (for a kernel trace: `rocprofv3 --kernel-trace --stats -- python scripts/bench_squeeze.py --reps 1`)
 One JSON line."""
 import argparse, json, os, sys, time
@@ -65,6 +68,8 @@ if __name__ == "__main__":
     ap.add_argument("--oracle-only", action="store_true", help="no GPU: time the numpy oracle on one pair")
     ap.add_argument("--windows", type=str, default="")
     ap.add_argument("--tables-only", action="store_true")
+    ap.add_argument("--friction", type=float, default=None)
+    ap.add_argument("--friction-only", action="store_true")
     a = ap.parse_args()
     cfg = dict(engine.SQUEEZE_DEFAULTS)
     samples, contours = inputs()
@@ -78,6 +83,17 @@ if __name__ == "__main__":
         st = None if a.tables_only else torch.as_tensor(starts).cuda()
         rot = torch.as_tensor(engine.squeeze_rotation_table(cfg["theta_cells"])).cuda()
         run = lambda **kw: engine.squeeze_tables(sf, ob, pairs, st, rot=rot, **dict(cfg, **kw))      # noqa: E731
+        if a.friction is not None:
+            fric = lambda: run(friction=a.friction, jam=True)      # noqa: E731
+            t = fric()
+            fms = [event_ms(fric) for _ in range(a.reps)]
+            out.update({"friction": a.friction, "ms_friction": float(np.median(fms)), "ms_friction_all": [round(v, 3) for v in fms],
+                        "jammed_cell_share": float(t["jam"].double().mean())})
+            if not a.tables_only:
+                out["settled_jammed_share"] = float(((t["flags"] & 16) != 0).double().mean())
+            if a.friction_only:
+                print(json.dumps(out), flush=True)
+                sys.exit(0)
         run()
         ms = [event_ms(run) for _ in range(a.reps)]
         med = float(np.median(ms))
