@@ -17,6 +17,11 @@
 // dgdm_squeeze_map_3d (3-D fingers: the same contract on the horizontal planes of the finger grid, include/dgdm_hip.h "squeeze
 // simulator, 3-D fingers") runs the same chunk loop (run_chunks) with table3d_kernel in table_kernel's place; dgdm_squeeze_slice cuts
 // the object meshes into the per-level segment lists it reads.  Their kernels are described where they stand, below.
+// Host side: a map entry checks the sizes of its own inputs, then check_map_args checks what all three take alike (config, shared
+// pointers, counts, starts and outputs, pair range, a workspace of at least one pair), then the entry checks what its own arrays hold.
+// run_chunks alone decides how many pairs a workspace holds and where a chunk's tables lie; the 3-D entry's extra block (gx, level
+// offsets) is the workspace's first bytes, so its place does not depend on the chunk size.  workspace_bytes_of is the one sum behind the
+// three *_workspace_bytes entries.
 // This file is compiled with -ffp-contract=off (build.py): no operation of the contract is fused.
 #include "common.h"
 #include <cmath>
@@ -339,6 +344,13 @@ Grid grid_of(const DgdmSqueezeConfig *cfg) {
     return g;
 }
 
+// The three *_workspace_bytes entries: a chunk of chunk_pairs pairs and the `extra` bytes the entry keeps in front of it.
+int64_t workspace_bytes_of(const char *fn, const DgdmSqueezeConfig *cfg, int chunk_pairs, bool friction, size_t extra) {
+    if (check_config(cfg, fn)) return DGDM_EINVAL;
+    DGDM_REQUIRE(chunk_pairs >= 1 && chunk_pairs <= MAX_CHUNK, DGDM_EINVAL, "%s: %d pairs per chunk (need 1 .. %d)", fn, chunk_pairs, MAX_CHUNK);
+    return (int64_t)(extra + layout((int64_t)cfg->theta_cells * cfg->x_cells, chunk_pairs, friction).bytes);
+}
+
 struct Outputs {
     int32_t *cells;
     double *y;
@@ -347,6 +359,34 @@ struct Outputs {
     int32_t *succ;
     int32_t *jam;       // friction only
 };
+
+// What every map entry checks alike, after the checks on its own inputs: the config, the pointers all entries take, the counts, the
+// starts and their outputs, the pair range, and that the workspace holds the entry's `extra` bytes and one pair's chunk.  `own`: the
+// entry's own pointers are all set.  `count_objects`: the 2-D entries name n_objects in the counts' message; the 3-D entry has checked
+// it with its sizes.  `bytes_fn`: the entry that sizes this workspace, for the message.
+int check_map_args(const char *fn, const DgdmSqueezeConfig *cfg, bool own, bool count_objects, int n_fingers, int n_objects,
+                   const int32_t *pairs_host, int n_pairs, const double *starts_dev, int n_starts, const Outputs &out, const void *workspace_dev,
+                   int64_t workspace_bytes, bool friction, size_t extra, const char *bytes_fn) {
+    int rc = check_config(cfg, fn);
+    if (rc) return rc;
+    DGDM_REQUIRE(own && pairs_host && workspace_dev, DGDM_EINVAL, "%s: null argument", fn);
+    if (count_objects)
+        DGDM_REQUIRE(n_fingers >= 1 && n_objects >= 1 && n_pairs >= 1, DGDM_EINVAL, "%s: %d fingers, %d objects, %d pairs (need >= 1 each)", fn,
+                     n_fingers, n_objects, n_pairs);
+    else
+        DGDM_REQUIRE(n_fingers >= 1 && n_pairs >= 1, DGDM_EINVAL, "%s: %d fingers, %d pairs (need >= 1 each)", fn, n_fingers, n_pairs);
+    DGDM_REQUIRE(n_starts >= 0, DGDM_EINVAL, "%s: %d starts", fn, n_starts);
+    DGDM_REQUIRE(n_starts == 0 || (starts_dev && out.cells && out.y && out.flags), DGDM_EINVAL, "%s: %d starts need starts_dev and the three outputs",
+                 fn, n_starts);
+    for (int p = 0; p < n_pairs; ++p)
+        DGDM_REQUIRE(pairs_host[2 * p] >= 0 && pairs_host[2 * p] < n_fingers && pairs_host[2 * p + 1] >= 0 && pairs_host[2 * p + 1] < n_objects,
+                     DGDM_EINVAL, "%s: pair %d = (finger %d, object %d) outside %d fingers x %d objects", fn, p, pairs_host[2 * p],
+                     pairs_host[2 * p + 1], n_fingers, n_objects);
+    const int64_t one = (int64_t)(extra + layout((int64_t)cfg->theta_cells * cfg->x_cells, 1, friction).bytes);
+    DGDM_REQUIRE(workspace_bytes >= one, DGDM_EINVAL, "%s: workspace of %lld bytes holds no pair, one needs %lld (%s)", fn,
+                 (long long)workspace_bytes, (long long)one, bytes_fn);
+    return DGDM_OK;
+}
 
 // The chunk loop of all entries: as many pairs per chunk as the workspace's `bytes` hold (the caller has checked that one fits);
 // `table(n, p0, pairs, tl, tr, S, jam, stream)` launches the entry's table kernel for the chunk's n pairs from pair p0 on, whose (finger,
@@ -582,7 +622,8 @@ __global__ __launch_bounds__(TABLE_THREADS) void table3d_kernel(Grid3 g, const d
     }
 }
 
-// the 3-D entry's workspace: the chunk's layout, then gx [mu] and the level offsets [n_objects][mv + 1]
+// the 3-D entry's workspace: gx [mu] and the level offsets [n_objects][mv + 1] in front, wherever the chunks are cut, then the chunk's
+// layout (run_chunks gets what lies behind the block)
 struct Extra3 { size_t gx, off, bytes; };
 Extra3 extra3(int mu, int mv, int n_objects) {
     Extra3 e;
@@ -614,10 +655,7 @@ int check_ascending(const double *v, int n, const char *what, const char *fn) {
 using namespace dgdm;
 
 extern "C" int64_t dgdm_squeeze_workspace_bytes(const DgdmSqueezeConfig *cfg, int chunk_pairs) {
-    if (check_config(cfg, "dgdm_squeeze_workspace_bytes")) return DGDM_EINVAL;
-    DGDM_REQUIRE(chunk_pairs >= 1 && chunk_pairs <= MAX_CHUNK, DGDM_EINVAL, "dgdm_squeeze_workspace_bytes: %d pairs per chunk (need 1 .. %d)",
-                 chunk_pairs, MAX_CHUNK);
-    return (int64_t)layout((int64_t)cfg->theta_cells * cfg->x_cells, chunk_pairs).bytes;
+    return workspace_bytes_of("dgdm_squeeze_workspace_bytes", cfg, chunk_pairs, false, 0);
 }
 
 // The body of dgdm_squeeze_map (friction = false: mu, jam_dev and contact_dev unused) and dgdm_squeeze_map_friction.
@@ -626,32 +664,21 @@ static int squeeze_map_common(const char *fn, bool friction, double mu, const Dg
                               const double *rot_dev, const double *starts_dev, int n_starts, int32_t *cells_dev, double *y_dev, int32_t *flags_dev,
                               double *table_s_dev, double *touch_l_dev, double *touch_r_dev, int32_t *succ_dev, int32_t *jam_dev,
                               int32_t *contact_dev, void *workspace_dev, int64_t workspace_bytes, void *stream) {
-    int rc = check_config(cfg, fn);
-    if (rc) return rc;
     DGDM_REQUIRE(!friction || (std::isfinite(mu) && mu >= 0.0), DGDM_EINVAL, "%s: friction coefficient %g (need finite, >= 0)", fn, mu);
-    DGDM_REQUIRE(surfaces_dev && objects_dev && pairs_host && rot_dev && workspace_dev, DGDM_EINVAL, "%s: null argument", fn);
-    DGDM_REQUIRE(n_fingers >= 1 && n_objects >= 1 && n_pairs >= 1, DGDM_EINVAL, "%s: %d fingers, %d objects, %d pairs (need >= 1 each)", fn,
-                 n_fingers, n_objects, n_pairs);
     DGDM_REQUIRE(num_points >= 2 && num_points <= MAX_SURFACE, DGDM_EINVAL, "%s: %d surface samples (need 2 .. %d)", fn, num_points, MAX_SURFACE);
     DGDM_REQUIRE(num_vertices >= 3 && num_vertices <= MAX_VERTS, DGDM_EINVAL, "%s: %d vertices (need 3 .. %d)", fn, num_vertices, MAX_VERTS);
-    DGDM_REQUIRE(n_starts >= 0, DGDM_EINVAL, "%s: %d starts", fn, n_starts);
-    DGDM_REQUIRE(n_starts == 0 || (starts_dev && cells_dev && y_dev && flags_dev), DGDM_EINVAL, "%s: %d starts need starts_dev and the three outputs",
-                 fn, n_starts);
-    for (int p = 0; p < n_pairs; ++p)
-        DGDM_REQUIRE(pairs_host[2 * p] >= 0 && pairs_host[2 * p] < n_fingers && pairs_host[2 * p + 1] >= 0 && pairs_host[2 * p + 1] < n_objects,
-                     DGDM_EINVAL, "%s: pair %d = (finger %d, object %d) outside %d fingers x %d objects", fn, p, pairs_host[2 * p],
-                     pairs_host[2 * p + 1], n_fingers, n_objects);
+    Outputs out = {cells_dev, y_dev, flags_dev, table_s_dev, touch_l_dev, touch_r_dev, succ_dev, jam_dev};
+    int rc = check_map_args(fn, cfg, surfaces_dev && objects_dev && rot_dev, true, n_fingers, n_objects, pairs_host, n_pairs, starts_dev, n_starts, out,
+                            workspace_dev, workspace_bytes, friction, 0,
+                            friction ? "dgdm_squeeze_friction_workspace_bytes" : "dgdm_squeeze_workspace_bytes");
+    if (rc) return rc;
     const int64_t cells = (int64_t)cfg->theta_cells * cfg->x_cells;
-    DGDM_REQUIRE(workspace_bytes >= (int64_t)layout(cells, 1, friction).bytes, DGDM_EINVAL,
-                 "%s: workspace of %lld bytes holds no pair, one needs %lld (%s)", fn, (long long)workspace_bytes,
-                 (long long)layout(cells, 1, friction).bytes, friction ? "dgdm_squeeze_friction_workspace_bytes" : "dgdm_squeeze_workspace_bytes");
     Grid g = grid_of(cfg);
     g.m = num_points;
     g.nv = num_vertices;
     g.hl = cfg->finger_half_len;
     g.h = 2.0 * cfg->finger_half_len / (double)(num_points - 1);
     const size_t lds = sizeof(double) * (size_t)(2 * g.m + 2 * g.nv);
-    Outputs out = {cells_dev, y_dev, flags_dev, table_s_dev, touch_l_dev, touch_r_dev, succ_dev, jam_dev};
     return run_chunks(cfg, g, pairs_host, n_pairs, starts_dev, n_starts, out, workspace_dev, workspace_bytes, (hipStream_t)stream, friction,
                       [&](unsigned n, int64_t p0, const int32_t *pairs, double *tl, double *tr, double *S, int32_t *jam, hipStream_t s) {
                           if (friction)
@@ -674,10 +701,7 @@ extern "C" int dgdm_squeeze_map(const DgdmSqueezeConfig *cfg, const double *surf
 }
 
 extern "C" int64_t dgdm_squeeze_friction_workspace_bytes(const DgdmSqueezeConfig *cfg, int chunk_pairs) {
-    const char *fn = "dgdm_squeeze_friction_workspace_bytes";
-    if (check_config(cfg, fn)) return DGDM_EINVAL;
-    DGDM_REQUIRE(chunk_pairs >= 1 && chunk_pairs <= MAX_CHUNK, DGDM_EINVAL, "%s: %d pairs per chunk (need 1 .. %d)", fn, chunk_pairs, MAX_CHUNK);
-    return (int64_t)layout((int64_t)cfg->theta_cells * cfg->x_cells, chunk_pairs, true).bytes;
+    return workspace_bytes_of("dgdm_squeeze_friction_workspace_bytes", cfg, chunk_pairs, true, 0);
 }
 
 extern "C" int dgdm_squeeze_map_friction(const DgdmSqueezeConfig *cfg, const double *surfaces_dev, int n_fingers, int num_points,
@@ -793,9 +817,8 @@ extern "C" int dgdm_squeeze_slice(const double *verts_host, const int64_t *vert_
 
 extern "C" int64_t dgdm_squeeze_map_3d_workspace_bytes(const DgdmSqueezeConfig *cfg, int chunk_pairs, int mu, int mv, int n_objects) {
     const char *fn = "dgdm_squeeze_map_3d_workspace_bytes";
-    if (check_config(cfg, fn) || check_sizes_3d(mu, mv, n_objects, fn)) return DGDM_EINVAL;
-    DGDM_REQUIRE(chunk_pairs >= 1 && chunk_pairs <= MAX_CHUNK, DGDM_EINVAL, "%s: %d pairs per chunk (need 1 .. %d)", fn, chunk_pairs, MAX_CHUNK);
-    return (int64_t)(layout((int64_t)cfg->theta_cells * cfg->x_cells, chunk_pairs).bytes + extra3(mu, mv, n_objects).bytes);
+    if (check_sizes_3d(mu, mv, n_objects, fn)) return DGDM_EINVAL;
+    return workspace_bytes_of(fn, cfg, chunk_pairs, false, extra3(mu, mv, n_objects).bytes);
 }
 
 extern "C" int dgdm_squeeze_map_3d(const DgdmSqueezeConfig *cfg, const double *surfaces_dev, int n_fingers, const double *gx_host, int mu, int mv,
@@ -804,11 +827,14 @@ extern "C" int dgdm_squeeze_map_3d(const DgdmSqueezeConfig *cfg, const double *s
                                    int32_t *cells_dev, double *y_dev, int32_t *flags_dev, double *table_s_dev, double *touch_l_dev,
                                    double *touch_r_dev, int32_t *succ_dev, void *workspace_dev, int64_t workspace_bytes, void *stream) {
     const char *fn = "dgdm_squeeze_map_3d";
-    int rc = check_config(cfg, fn);
+    int rc = check_sizes_3d(mu, mv, n_objects, fn);
     if (rc) return rc;
-    DGDM_REQUIRE(surfaces_dev && gx_host && seg_offsets_host && pairs_host && rot_dev && workspace_dev, DGDM_EINVAL, "%s: null argument", fn);
-    DGDM_REQUIRE(n_fingers >= 1 && n_pairs >= 1, DGDM_EINVAL, "%s: %d fingers, %d pairs (need >= 1 each)", fn, n_fingers, n_pairs);
-    if ((rc = check_sizes_3d(mu, mv, n_objects, fn)) || (rc = check_ascending(gx_host, mu, "gx", fn))) return rc;
+    const Extra3 e = extra3(mu, mv, n_objects);
+    Outputs out = {cells_dev, y_dev, flags_dev, table_s_dev, touch_l_dev, touch_r_dev, succ_dev, nullptr};
+    if ((rc = check_map_args(fn, cfg, surfaces_dev && gx_host && seg_offsets_host && rot_dev, false, n_fingers, n_objects, pairs_host, n_pairs,
+                             starts_dev, n_starts, out, workspace_dev, workspace_bytes, false, e.bytes, "dgdm_squeeze_map_3d_workspace_bytes")) ||
+        (rc = check_ascending(gx_host, mu, "gx", fn)))
+        return rc;
     DGDM_REQUIRE(n_segments >= 0 && n_segments <= INT32_MAX && (segments_dev || n_segments == 0), DGDM_EINVAL, "%s: %lld segments with%s segments_dev",
                  fn, (long long)n_segments, segments_dev ? "" : " no");
     const size_t nl1 = (size_t)n_objects * (size_t)(mv + 1);
@@ -818,32 +844,16 @@ extern "C" int dgdm_squeeze_map_3d(const DgdmSqueezeConfig *cfg, const double *s
                      seg_offsets_host[i], seg_offsets_host[i - 1]);
     DGDM_REQUIRE(seg_offsets_host[nl1 - 1] <= n_segments, DGDM_EINVAL, "%s: seg_offsets end at %d, past the %lld segments", fn,
                  seg_offsets_host[nl1 - 1], (long long)n_segments);
-    DGDM_REQUIRE(n_starts >= 0, DGDM_EINVAL, "%s: %d starts", fn, n_starts);
-    DGDM_REQUIRE(n_starts == 0 || (starts_dev && cells_dev && y_dev && flags_dev), DGDM_EINVAL, "%s: %d starts need starts_dev and the three outputs",
-                 fn, n_starts);
-    for (int p = 0; p < n_pairs; ++p)
-        DGDM_REQUIRE(pairs_host[2 * p] >= 0 && pairs_host[2 * p] < n_fingers && pairs_host[2 * p + 1] >= 0 && pairs_host[2 * p + 1] < n_objects,
-                     DGDM_EINVAL, "%s: pair %d = (finger %d, object %d) outside %d fingers x %d objects", fn, p, pairs_host[2 * p],
-                     pairs_host[2 * p + 1], n_fingers, n_objects);
-    const int64_t cells = (int64_t)cfg->theta_cells * cfg->x_cells;
-    const Extra3 e = extra3(mu, mv, n_objects);
-    const int64_t one = (int64_t)(layout(cells, 1).bytes + e.bytes);
-    DGDM_REQUIRE(workspace_bytes >= one, DGDM_EINVAL, "%s: workspace of %lld bytes holds no pair, one needs %lld (dgdm_squeeze_map_3d_workspace_bytes)",
-                 fn, (long long)workspace_bytes, (long long)one);
-    const int64_t chunk_bytes = workspace_bytes - (int64_t)e.bytes;       // the extra block sits behind the largest chunk layout that fits
-    int64_t chunk = std::min<int64_t>(std::min<int64_t>(n_pairs, MAX_CHUNK), chunk_bytes / (int64_t)layout(cells, 1).bytes + 1);
-    while (chunk > 1 && (int64_t)layout(cells, chunk).bytes > chunk_bytes) --chunk;
-    uint8_t *ex = static_cast<uint8_t *>(workspace_dev) + layout(cells, chunk).bytes;
-    double *gx = reinterpret_cast<double *>(ex + e.gx);
-    int32_t *offs = reinterpret_cast<int32_t *>(ex + e.off);
+    uint8_t *ws = static_cast<uint8_t *>(workspace_dev);                  // the extra block in front, the chunks' tables behind it
+    double *gx = reinterpret_cast<double *>(ws + e.gx);
+    int32_t *offs = reinterpret_cast<int32_t *>(ws + e.off);
     hipStream_t s = (hipStream_t)stream;
     DGDM_HIP_CHECK(hipMemcpyAsync(gx, gx_host, sizeof(double) * mu, hipMemcpyHostToDevice, s));
     DGDM_HIP_CHECK(hipMemcpyAsync(offs, seg_offsets_host, sizeof(int32_t) * nl1, hipMemcpyHostToDevice, s));
     const Grid g = grid_of(cfg);
     Grid3 g3 = {g.T, g.X, mu, mv, g.x_half, g.dx};
     const size_t lds = sizeof(double) * (size_t)(2 * mu * mv + mu + 4 * SEG_TILE) + sizeof(int32_t) * (size_t)(mv + 1);
-    Outputs out = {cells_dev, y_dev, flags_dev, table_s_dev, touch_l_dev, touch_r_dev, succ_dev, nullptr};
-    return run_chunks(cfg, g, pairs_host, n_pairs, starts_dev, n_starts, out, workspace_dev, chunk_bytes, s, false,
+    return run_chunks(cfg, g, pairs_host, n_pairs, starts_dev, n_starts, out, ws + e.bytes, workspace_bytes - (int64_t)e.bytes, s, false,
                       [&](unsigned n, int64_t, const int32_t *pairs, double *tl, double *tr, double *S, int32_t *, hipStream_t st) {
                           hipLaunchKernelGGL(table3d_kernel, dim3((unsigned)g3.T, n), dim3(TABLE_THREADS), lds, st, g3, surfaces_dev, gx, segments_dev,
                                              offs, pairs, rot_dev, tl, tr, S);

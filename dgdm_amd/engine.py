@@ -1125,6 +1125,44 @@ def squeeze_config(**kw) -> _lib.SqueezeConfig:
                               float(c["travel_max"]), float(c["finger_half_len"]))
 
 
+def _squeeze_mover():
+    """t -> a contiguous float64 tensor on the current device (no copy of one that is there already)."""
+    dev = torch.device("cuda", torch.cuda.current_device())
+    return lambda t: torch.as_tensor(t).detach().to(device=dev, dtype=torch.float64).contiguous()
+
+
+def _squeeze_front(who: str, cfg, f64, sizer, pairs, starts, rot, tables: bool, workspace_bytes: Optional[int]):
+    """What squeeze_tables and squeeze_tables_3d (`who`) do alike.  f64: _squeeze_mover(); sizer(n): the entry's *_workspace_bytes for
+    chunks of n pairs.  -> (out, tail, keep): the output dict; the entries' common trailing arguments, from pairs_host to stream; the
+    arrays behind them.  Without workspace_bytes the workspace holds as many pairs as fit SQUEEZE_WORKSPACE_BYTES, at least one, never
+    more than the call has."""
+    pr = np.ascontiguousarray(pairs, dtype=np.int32).reshape(-1, 2)
+    P, T, X = len(pr), cfg.theta_cells, cfg.x_cells
+    fit = int(sizer(min(max(P, 1), 65535)))         # all pairs in one chunk; negative: a config or sizes the library refuses
+    if fit < 0:
+        _check_value(fit)
+    rt = f64(squeeze_rotation_table(T) if rot is None else rot)
+    if rt.shape != (T, 2):
+        raise ValueError(f"{who}: rot of shape {tuple(rt.shape)} (need ({T}, 2))")
+    st = f64(starts).reshape(-1, 3) if starts is not None else None
+    N = 0 if st is None else int(st.shape[0])
+    if workspace_bytes is not None:
+        ws_bytes = int(workspace_bytes)
+    elif fit <= SQUEEZE_WORKSPACE_BYTES:
+        ws_bytes = fit
+    else:                                           # the library cuts the budget into chunks of as many pairs as fit it
+        ws_bytes = max(SQUEEZE_WORKSPACE_BYTES, int(sizer(1)))
+    ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=rt.device)
+    new = lambda *shape, dtype: torch.empty(shape, dtype=dtype, device=rt.device)                      # noqa: E731
+    out = {"cells": new(P, N, 3, dtype=torch.int32), "y": new(P, N, 2, dtype=torch.float64), "flags": new(P, N, dtype=torch.int32)}
+    if tables:
+        out.update({k: new(P, T, X, dtype=torch.float64) for k in ("S", "touch_l", "touch_r")})
+        out["succ"] = new(P, T * X, dtype=torch.int32)
+    tail = (pr.ctypes.data, P, dptr(rt), dptr(st), N, dptr(out["cells"]), dptr(out["y"]), dptr(out["flags"]), dptr(out.get("S")),
+            dptr(out.get("touch_l")), dptr(out.get("touch_r")), dptr(out.get("succ")), dptr(ws), ws_bytes, stream_ptr())
+    return out, tail, (pr, rt, st, ws)
+
+
 def squeeze_tables(surfaces, objects, pairs, starts=None, rot=None, tables: bool = False, workspace_bytes: Optional[int] = None,
                    friction: float = 0.0, jam: bool = False, contact: bool = False, **config) -> Dict[str, torch.Tensor]:
     """dgdm_squeeze_map (include/dgdm_hip.h "squeeze simulator") on the current device.  surfaces (F, 2, m) float64: the
@@ -1137,40 +1175,22 @@ def squeeze_tables(surfaces, objects, pairs, starts=None, rot=None, tables: bool
     friction > 0 or when its tables are asked for - jam (P, theta_cells, x_cells) int32 and contact (P, theta_cells, x_cells, 2) int32
     (the lower and upper contact's code), both also returned with tables=True - and flags then carries 8 / 16 (start / settled cell
     jammed).  Otherwise dgdm_squeeze_map runs, as it always did."""
+    from .sim.squeeze import check_friction
     cfg = squeeze_config(**config)
-    mu = float(friction)
-    if not (np.isfinite(mu) and mu >= 0.0):
-        raise ValueError(f"squeeze_tables: friction {friction!r} is not a finite non-negative number")
+    mu = check_friction(friction, "squeeze_tables")
     with_friction = mu > 0.0 or bool(jam) or bool(contact)
-    one = (lib().dgdm_squeeze_friction_workspace_bytes if with_friction else lib().dgdm_squeeze_workspace_bytes)(C.byref(cfg), 1)
-    if one < 0:
-        _check_value(int(one))
-    dev = torch.device("cuda", torch.cuda.current_device())
-    f64 = lambda t: torch.as_tensor(t).detach().to(device=dev, dtype=torch.float64).contiguous()      # noqa: E731
+    f64 = _squeeze_mover()
     sf, ob = f64(surfaces), f64(objects)
     if sf.dim() != 3 or sf.shape[1] != 2 or ob.dim() != 3 or ob.shape[2] != 2:
         raise ValueError(f"squeeze_tables: surfaces (F, 2, m) and objects (O, nv, 2) expected, got {tuple(sf.shape)} and {tuple(ob.shape)}")
-    pr = np.ascontiguousarray(pairs, dtype=np.int32).reshape(-1, 2)
-    P, T, X = len(pr), cfg.theta_cells, cfg.x_cells
-    rt = f64(squeeze_rotation_table(T) if rot is None else rot)
-    if rt.shape != (max(T, 0), 2):
-        raise ValueError(f"squeeze_tables: rot of shape {tuple(rt.shape)} (need ({T}, 2))")
-    st = f64(starts).reshape(-1, 3) if starts is not None else None
-    N = 0 if st is None else int(st.shape[0])
-    ws_bytes = int(workspace_bytes) if workspace_bytes is not None else min(max(SQUEEZE_WORKSPACE_BYTES, int(one)), int(one) * max(P, 1))
-    ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=dev)
-    new = lambda *shape, dtype: torch.empty(shape, dtype=dtype, device=dev)                            # noqa: E731
-    out = {"cells": new(P, N, 3, dtype=torch.int32), "y": new(P, N, 2, dtype=torch.float64), "flags": new(P, N, dtype=torch.int32)}
-    if tables:
-        out.update({k: new(P, max(T, 0), max(X, 0), dtype=torch.float64) for k in ("S", "touch_l", "touch_r")})
-        out["succ"] = new(P, max(T, 0) * max(X, 0), dtype=torch.int32)
+    sizer = lib().dgdm_squeeze_friction_workspace_bytes if with_friction else lib().dgdm_squeeze_workspace_bytes
+    out, tail, keep = _squeeze_front("squeeze_tables", cfg, f64, lambda n: sizer(C.byref(cfg), n), pairs, starts, rot, tables, workspace_bytes)
+    shape = (len(keep[0]), cfg.theta_cells, cfg.x_cells)
     if with_friction and (tables or jam):
-        out["jam"] = new(P, max(T, 0), max(X, 0), dtype=torch.int32)
+        out["jam"] = torch.empty(shape, dtype=torch.int32, device=sf.device)
     if with_friction and (tables or contact):
-        out["contact"] = new(P, max(T, 0), max(X, 0), 2, dtype=torch.int32)
-    args = (C.byref(cfg), dptr(sf), int(sf.shape[0]), int(sf.shape[2]), dptr(ob), int(ob.shape[0]), int(ob.shape[1]), pr.ctypes.data, P, dptr(rt),
-            dptr(st), N, dptr(out["cells"]), dptr(out["y"]), dptr(out["flags"]), dptr(out.get("S")), dptr(out.get("touch_l")),
-            dptr(out.get("touch_r")), dptr(out.get("succ")), dptr(ws), ws_bytes, stream_ptr())
+        out["contact"] = torch.empty(shape + (2,), dtype=torch.int32, device=sf.device)
+    args = (C.byref(cfg), dptr(sf), int(sf.shape[0]), int(sf.shape[2]), dptr(ob), int(ob.shape[0]), int(ob.shape[1])) + tail
     if with_friction:
         _check_value(lib().dgdm_squeeze_map_friction(*args, mu, dptr(out.get("jam")), dptr(out.get("contact"))))
     else:
@@ -1249,8 +1269,7 @@ def squeeze_tables_3d(surfaces, gx, segments, offsets, pairs, starts=None, rot=N
     and the abscissae gx (mu,), strictly ascending; segments (n, 4) / offsets (O, mv + 1): squeeze_slice's, for the same levels; the
     rest and the outputs as squeeze_tables.  config: the keys of SQUEEZE_DEFAULTS (finger_half_len is unused here)."""
     cfg = squeeze_config(**config)
-    dev = torch.device("cuda", torch.cuda.current_device())
-    f64 = lambda t: torch.as_tensor(t).detach().to(device=dev, dtype=torch.float64).contiguous()      # noqa: E731
+    f64 = _squeeze_mover()
     sf, sg = f64(surfaces), f64(segments).reshape(-1, 4)
     g = np.ascontiguousarray(gx, dtype=np.float64).reshape(-1)
     of = np.ascontiguousarray(offsets, dtype=np.int32)
@@ -1258,33 +1277,10 @@ def squeeze_tables_3d(surfaces, gx, segments, offsets, pairs, starts=None, rot=N
         raise ValueError(f"squeeze_tables_3d: surfaces (F, 2, mv, mu), gx (mu,) and offsets (O, mv + 1) expected, got {tuple(sf.shape)}, "
                          f"{g.shape} and {of.shape}")
     mu, mv, O = int(sf.shape[3]), int(sf.shape[2]), int(of.shape[0])
-    one = lib().dgdm_squeeze_map_3d_workspace_bytes(C.byref(cfg), 1, mu, mv, O)
-    if one < 0:
-        _check_value(int(one))
-    pr = np.ascontiguousarray(pairs, dtype=np.int32).reshape(-1, 2)
-    P, T, X = len(pr), cfg.theta_cells, cfg.x_cells
-    rt = f64(squeeze_rotation_table(T) if rot is None else rot)
-    if rt.shape != (T, 2):
-        raise ValueError(f"squeeze_tables_3d: rot of shape {tuple(rt.shape)} (need ({T}, 2))")
-    st = f64(starts).reshape(-1, 3) if starts is not None else None
-    N = 0 if st is None else int(st.shape[0])
-    if workspace_bytes is not None:
-        ws_bytes = int(workspace_bytes)
-    else:
-        ws_bytes = int(one)
-        if P > 1:
-            fit = int(lib().dgdm_squeeze_map_3d_workspace_bytes(C.byref(cfg), min(P, 65535), mu, mv, O))
-            ws_bytes = fit if 0 < fit <= SQUEEZE_WORKSPACE_BYTES else max(SQUEEZE_WORKSPACE_BYTES, int(one))
-    ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=dev)
-    new = lambda *shape, dtype: torch.empty(shape, dtype=dtype, device=dev)                            # noqa: E731
-    out = {"cells": new(P, N, 3, dtype=torch.int32), "y": new(P, N, 2, dtype=torch.float64), "flags": new(P, N, dtype=torch.int32)}
-    if tables:
-        out.update({k: new(P, T, X, dtype=torch.float64) for k in ("S", "touch_l", "touch_r")})
-        out["succ"] = new(P, T * X, dtype=torch.int32)
+    out, tail, keep = _squeeze_front("squeeze_tables_3d", cfg, f64, lambda n: lib().dgdm_squeeze_map_3d_workspace_bytes(C.byref(cfg), n, mu, mv, O),
+                                     pairs, starts, rot, tables, workspace_bytes)
     _check_value(lib().dgdm_squeeze_map_3d(C.byref(cfg), dptr(sf), int(sf.shape[0]), g.ctypes.data, mu, mv, dptr(sg) if len(sg) else None, int(len(sg)),
-                                           of.ctypes.data, O, pr.ctypes.data, P, dptr(rt), dptr(st), N, dptr(out["cells"]), dptr(out["y"]),
-                                           dptr(out["flags"]), dptr(out.get("S")), dptr(out.get("touch_l")), dptr(out.get("touch_r")),
-                                           dptr(out.get("succ")), dptr(ws), ws_bytes, stream_ptr()))
+                                           of.ctypes.data, O, *tail))
     return out
 
 

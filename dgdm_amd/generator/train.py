@@ -392,6 +392,21 @@ def squeeze_friction_from_args(args):
     return mu
 
 
+def squeeze_sim_config(args, flag: str):
+    """What --squeeze_sim and --squeeze_sim_3d (`flag`) refuse alike, then the config keys of --squeeze_closing_steps / --squeeze_window."""
+    if getattr(args, "predicted_sim", False):
+        raise ValueError(f"{flag} and --predicted_sim both fill the objective tables: choose one")
+    if getattr(args, "mode", "test") != 'test':
+        raise ValueError(f"{flag} scores the samples of --mode=test")
+    if getattr(args, "goal_pose", None):
+        raise ValueError(f"{flag} with --goal_pose: goal scores (dynamics/predicted.py goal_objective) are marked as the dynamics model's "
+                         "predictions, which squeeze results are not - not supported")
+    if not getattr(args, "classifier_guidance", False):
+        raise ValueError(f"{flag} needs --classifier_guidance: the run's objects come with it")
+    from ..sim.squeeze import steps_from_args
+    return steps_from_args(args)
+
+
 def squeeze_from_args(args):
     """--squeeze_sim [--squeeze_closing_steps K --squeeze_window R --squeeze_friction MU] -> SqueezeSimulator's keywords, or None without
     the flag.  Host-side checks only."""
@@ -408,20 +423,8 @@ def squeeze_from_args(args):
     if getattr(args, "fingers_3d", False):
         raise ValueError("--squeeze_sim is 2-D only: the squeeze model has no 3-D fingers (--fingers_3d); --squeeze_sim_3d is the sliced form "
                          "for them")
-    if getattr(args, "predicted_sim", False):
-        raise ValueError("--squeeze_sim and --predicted_sim both fill the objective tables: choose one")
-    if getattr(args, "mode", "test") != 'test':
-        raise ValueError("--squeeze_sim scores the samples of --mode=test")
-    if getattr(args, "goal_pose", None):
-        raise ValueError("--squeeze_sim with --goal_pose: goal scores (dynamics/predicted.py goal_objective) are marked as the dynamics model's "
-                         "predictions, which squeeze results are not - not supported")
-    if not getattr(args, "classifier_guidance", False):
-        raise ValueError("--squeeze_sim needs --classifier_guidance: the run's objects come with it")
-    if k is not None and k < 0:
-        raise ValueError(f"--squeeze_closing_steps={k}: the number of steps cannot be negative")
-    if r is not None and r < 1:
-        raise ValueError(f"--squeeze_window={r}: the window is at least 1 cell")
-    return {key: v for key, v in (("closing_steps", k), ("window", r), ("friction", mu)) if v is not None}
+    config = squeeze_sim_config(args, "--squeeze_sim")
+    return config if mu is None else dict(config, friction=mu)
 
 
 def squeeze_3d_from_args(args):
@@ -430,23 +433,9 @@ def squeeze_3d_from_args(args):
     if not getattr(args, "squeeze_sim_3d", False):
         return None
     squeeze_friction_from_args(args)        # --squeeze_friction: refused, friction is 2-D only
-    k, r = getattr(args, "squeeze_closing_steps", None), getattr(args, "squeeze_window", None)
     if not getattr(args, "fingers_3d", False):
         raise ValueError("--squeeze_sim_3d needs --fingers_3d: it is the squeeze model for 3-D fingers (--squeeze_sim is the 2-D one)")
-    if getattr(args, "predicted_sim", False):
-        raise ValueError("--squeeze_sim_3d and --predicted_sim both fill the objective tables: choose one")
-    if getattr(args, "mode", "test") != 'test':
-        raise ValueError("--squeeze_sim_3d scores the samples of --mode=test")
-    if getattr(args, "goal_pose", None):
-        raise ValueError("--squeeze_sim_3d with --goal_pose: goal scores (dynamics/predicted.py goal_objective) are marked as the dynamics "
-                         "model's predictions, which squeeze results are not - not supported")
-    if not getattr(args, "classifier_guidance", False):
-        raise ValueError("--squeeze_sim_3d needs --classifier_guidance: the run's objects come with it")
-    if k is not None and k < 0:
-        raise ValueError(f"--squeeze_closing_steps={k}: the number of steps cannot be negative")
-    if r is not None and r < 1:
-        raise ValueError(f"--squeeze_window={r}: the window is at least 1 cell")
-    return {key: v for key, v in (("closing_steps", k), ("window", r)) if v is not None}
+    return squeeze_sim_config(args, "--squeeze_sim_3d")
 
 
 def train(args):

@@ -202,15 +202,8 @@ def squeeze_potential_from_args(args) -> Optional[Dict[str, Any]]:
         if t < 1 or x < 2:
             raise ValueError(f"--resample_squeeze_cells {cells!r}: need T >= 1 and X >= 2")
         config.update(theta_cells=t, x_cells=x)
-    k, r = getattr(args, "squeeze_closing_steps", None), getattr(args, "squeeze_window", None)
-    if k is not None:
-        if k < 0:
-            raise ValueError(f"--squeeze_closing_steps={k}: the number of steps cannot be negative")
-        config["closing_steps"] = int(k)
-    if r is not None:
-        if r < 1:
-            raise ValueError(f"--squeeze_window={r}: the window is at least 1 cell")
-        config["window"] = int(r)
+    from .sim.squeeze import steps_from_args
+    config.update(steps_from_args(args))
     return config
 
 

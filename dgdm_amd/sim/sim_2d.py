@@ -62,26 +62,38 @@ def generate(out_dir: str, gripper_ids: Sequence[int], contours, object_ids: Seq
     samples = np.stack([np.concatenate([yl, yr]) for _, yl, yr in designs]).astype(np.float32)
     starts = pose_grid()
     out = squeeze.squeeze_map(samples, contours, starts, scale=1.0, offset=0.0, num_points=NUM_POINTS, friction=friction, **config)
-    start, closed = out["start"].cpu().numpy(), out["closed"].cpu().numpy()
-    records = [(int(object_ids[o]), int(gripper_ids[f]), pair_record(*shapes[f], contours[o], starts, start[p], closed[p]))
-               for p, (f, o) in enumerate(out["pairs"])]
-    return write_dataset(out_dir, records, engine.squeeze_config(**config), int(np.count_nonzero(out["flags"].cpu().numpy() & 1)), friction)
+    return write_map(out_dir, out, gripper_ids, object_ids, lambda f, o, start, closed: pair_record(*shapes[f], contours[o], starts, start, closed),
+                     engine.squeeze_config(**config), friction)
 
 
-def pair_record(ctrlpts, allpts, contour, starts, start, closed) -> dict:
-    """The dict of one data file, keys in the reference's order (sim/sim_2d.py:172-180).  starts (n, 3): the start poses; start (n, 2): the
-    (theta, x) of the cells they snapped to; closed (n, 3): the pose after one closing.  Host code."""
+def record(ctrlpts, allpts, object_key: str, object_value, starts, start, closed) -> dict:
+    """The dict of one data file, keys in the reference's order (sim/sim_2d.py:172-180, sim/sim_3d.py:162-170), the object under
+    `object_key`.  starts (n, 3): the start poses; start (n, 2): the (theta, x) of the cells they snapped to; closed (n, 3): the pose after
+    one closing.  Host code."""
     starts, start, closed = (np.asarray(a, dtype=np.float64) for a in (starts, start, closed))
     zeros = np.zeros(len(starts))
     return {
         "ctrlpts": ctrlpts,
         "allpts": allpts,
-        "object_vertices": np.asarray(contour, dtype=np.float64),
+        object_key: object_value,
         "obj_pos": np.stack([starts[:, 1], starts[:, 2], zeros], axis=1),
         "obj_theta": starts[:, 0].astype(np.float32),
         "delta_theta": fold(closed[:, 0] - start[:, 0], 2.0 * np.pi).astype(np.float32),
         "delta_pos": np.stack([closed[:, 1] - start[:, 1], closed[:, 2] - starts[:, 2], zeros], axis=1),
     }
+
+
+def pair_record(ctrlpts, allpts, contour, starts, start, closed) -> dict:
+    """`record` of a 2-D pair: the object is its contour, ``object_vertices``."""
+    return record(ctrlpts, allpts, "object_vertices", np.asarray(contour, dtype=np.float64), starts, start, closed)
+
+
+def write_map(out_dir: str, out, gripper_ids: Sequence[int], object_ids: Sequence[int], record_of, cfg, friction=None) -> List[str]:
+    """write_dataset of a squeeze map's pairs: record_of(finger, object, start, closed) is the pair's data file; the loose starts are
+    counted from the flags."""
+    start, closed = out["start"].cpu().numpy(), out["closed"].cpu().numpy()
+    records = [(int(object_ids[o]), int(gripper_ids[f]), record_of(f, o, start[p], closed[p])) for p, (f, o) in enumerate(out["pairs"])]
+    return write_dataset(out_dir, records, cfg, int(np.count_nonzero(out["flags"].cpu().numpy() & 1)), friction)
 
 
 def write_dataset(out_dir: str, records, cfg, loose_starts: int = 0, friction=None) -> List[str]:
@@ -105,18 +117,29 @@ def write_dataset(out_dir: str, records, cfg, loose_starts: int = 0, friction=No
     return files
 
 
+def cli_parser(description: str):
+    """The parser sim_2d.py and sim_3d.py start from: the reference's seven positional arguments and the squeeze model's two flags."""
+    import argparse
+    p = argparse.ArgumentParser(description=description)
+    for name, kind in (("model_root", str), ("gripper_idx", int), ("object_idx", int), ("num_gripper_parallel", int), ("num_object_parallel", int),
+                       ("save_dir", str), ("num_cpus", int)):
+        p.add_argument(name, type=kind)
+    p.add_argument("--squeeze_closing_steps", type=int, default=None)
+    p.add_argument("--squeeze_window", type=int, default=None)
+    return p
+
+
+def cli_config(a) -> dict:
+    """generate's config keys from cli_parser's two squeeze flags: those that were given."""
+    return {k: v for k, v in (("closing_steps", a.squeeze_closing_steps), ("window", a.squeeze_window)) if v is not None}
+
+
 def main(argv=None):
     """python sim/sim_2d.py MODEL_ROOT GRIPPER_IDX OBJECT_IDX NUM_GRIPPERS NUM_OBJECTS SAVE_DIR NUM_CPUS --object_dir Icons-50.npy: the
     reference's positional arguments (sim/sim_2d.py:184-191; MODEL_ROOT and NUM_CPUS are accepted and unused - no scene files, no Ray),
     plus the icon file, which the reference keeps in a constant."""
-    import argparse
-    p = argparse.ArgumentParser(description=main.__doc__)
-    for name, kind in (("model_root", str), ("gripper_idx", int), ("object_idx", int), ("num_gripper_parallel", int), ("num_object_parallel", int),
-                       ("save_dir", str), ("num_cpus", int)):
-        p.add_argument(name, type=kind)
+    p = cli_parser(main.__doc__)
     p.add_argument("--object_dir", required=True, help="the Icons-50 .npy file")
-    p.add_argument("--squeeze_closing_steps", type=int, default=None)
-    p.add_argument("--squeeze_window", type=int, default=None)
     p.add_argument("--friction", type=float, default=0.0, help="Coulomb friction coefficient of the squeeze (default 0: frictionless)")
     a = p.parse_args(argv)
     from .squeeze import check_friction
@@ -127,9 +150,8 @@ def main(argv=None):
     object_ids = list(range(a.object_idx, a.object_idx + a.num_object_parallel))
     images = np.load(a.object_dir, allow_pickle=True).item()['image'][object_ids].transpose((0, 2, 3, 1))
     contours = icon_process.extract_contours_batch(images)
-    config = {k: v for k, v in (("closing_steps", a.squeeze_closing_steps), ("window", a.squeeze_window)) if v is not None}
     files = generate(a.save_dir, list(range(a.gripper_idx, a.gripper_idx + a.num_gripper_parallel)), contours, object_ids, friction=a.friction,
-                     **config)
+                     **cli_config(a))
     print(f"[dgdm_amd] wrote {len(files)} files and stats.json to {a.save_dir}")
 
 

@@ -21,8 +21,8 @@ from typing import List, Sequence
 
 import numpy as np
 
-from .sim_2d import pose_grid, write_dataset
-from .squeeze import FINGER_WIDTH_3D, fold
+from .sim_2d import cli_config, cli_parser, pose_grid, record, write_map
+from .squeeze import FINGER_WIDTH_3D
 
 NUM_CTRL, SAMPLE_SIZE = 21, 25                          # sim/sim_3d.py:73-83
 
@@ -54,26 +54,13 @@ def generate(out_dir: str, gripper_ids: Sequence[int], meshes, object_ids: Seque
     samples = np.stack([np.concatenate([yl, yr]) for yl, yr in designs]).astype(np.float32)
     starts = pose_grid()
     out = squeeze.squeeze_map_3d(samples, meshes, starts, sample_size=SAMPLE_SIZE, width=FINGER_WIDTH_3D, scale=1.0, offset=0.0, **config)
-    start, closed = out["start"].cpu().numpy(), out["closed"].cpu().numpy()
-    records = [(int(object_ids[o]), int(gripper_ids[f]), pair_record(*shapes[f], object_names[o], starts, start[p], closed[p]))
-               for p, (f, o) in enumerate(out["pairs"])]
-    return write_dataset(out_dir, records, engine.squeeze_config(**config), int(np.count_nonzero(out["flags"].cpu().numpy() & 1)))
+    return write_map(out_dir, out, gripper_ids, object_ids, lambda f, o, start, closed: pair_record(*shapes[f], object_names[o], starts, start, closed),
+                     engine.squeeze_config(**config))
 
 
 def pair_record(ctrlpts, allpts, object_name, starts, start, closed) -> dict:
-    """The dict of one data file, keys in the reference's order (sim/sim_3d.py:162-170).  starts (n, 3): the start poses; start (n, 2): the
-    (theta, x) of the cells they snapped to; closed (n, 3): the pose after one closing.  Host code."""
-    starts, start, closed = (np.asarray(a, dtype=np.float64) for a in (starts, start, closed))
-    zeros = np.zeros(len(starts))
-    return {
-        "ctrlpts": ctrlpts,
-        "allpts": allpts,
-        "object_name": str(object_name),
-        "obj_pos": np.stack([starts[:, 1], starts[:, 2], zeros], axis=1),
-        "obj_theta": starts[:, 0].astype(np.float32),
-        "delta_theta": fold(closed[:, 0] - start[:, 0], 2.0 * np.pi).astype(np.float32),
-        "delta_pos": np.stack([closed[:, 1] - start[:, 1], closed[:, 2] - starts[:, 2], zeros], axis=1),
-    }
+    """sim_2d.record of a 3-D pair: the object is its name, ``object_name`` (sim/sim_3d.py:162-170)."""
+    return record(ctrlpts, allpts, "object_name", str(object_name), starts, start, closed)
 
 
 def object_names_in(object_dir: str, names_file: str = "") -> List[str]:
@@ -92,15 +79,9 @@ def main(argv=None):
     (sim/sim_3d.py:174-181; NUM_CPUS is accepted and unused - no Ray).  The objects are ``<object_dir>/<name>/model.obj``; --object_dir
     defaults to MODEL_ROOT/objects, where the reference's prepare_object copies them; OBJECT_IDX counts through --object_names (a file
     of names, one per line) or the directory's listing."""
-    import argparse
-    p = argparse.ArgumentParser(description=main.__doc__)
-    for name, kind in (("model_root", str), ("gripper_idx", int), ("object_idx", int), ("num_gripper_parallel", int), ("num_object_parallel", int),
-                       ("save_dir", str), ("num_cpus", int)):
-        p.add_argument(name, type=kind)
+    p = cli_parser(main.__doc__)
     p.add_argument("--object_dir", default=None, help="directory of <name>/model.obj (default: MODEL_ROOT/objects)")
     p.add_argument("--object_names", default="", help="file of object names, one per line (default: the directory's listing)")
-    p.add_argument("--squeeze_closing_steps", type=int, default=None)
-    p.add_argument("--squeeze_window", type=int, default=None)
     p.add_argument("--friction", type=float, default=None, help="refused: friction is 2-D only (sim_2d.py --friction)")
     a = p.parse_args(argv)
     if a.friction is not None:
@@ -117,9 +98,8 @@ def main(argv=None):
     if not names or object_ids[-1] >= len(names):
         raise ValueError(f"sim_3d: objects {object_ids[0]} .. {object_ids[-1]} asked for, {len(names)} found under {object_dir}")
     meshes = [engine.read_obj(os.path.join(object_dir, names[i], MESH_FILE)) for i in object_ids]
-    config = {k: v for k, v in (("closing_steps", a.squeeze_closing_steps), ("window", a.squeeze_window)) if v is not None}
     files = generate(a.save_dir, list(range(a.gripper_idx, a.gripper_idx + a.num_gripper_parallel)), meshes, object_ids, [names[i] for i in object_ids],
-                     **config)
+                     **cli_config(a))
     print(f"[dgdm_amd] wrote {len(files)} files and stats.json to {a.save_dir}")
 
 

@@ -40,19 +40,19 @@ DEG, CM = 180.0 / np.pi, 100.0
 SIMULATED = 'squeeze'
 
 
+def _decode_units(scale: Optional[float], offset: Optional[float]) -> Dict[str, float]:
+    """The decoders' scale / offset keywords: those that were given (the decoders' defaults are the sampler's units)."""
+    return {k: float(v) for k, v in (("scale", scale), ("offset", offset)) if v is not None}
+
+
 def finger_surfaces(samples, num_points: int = 200, scale: Optional[float] = None, offset: Optional[float] = None):
     """(B, L[, 1]) control values -> surfaces (B, 2, num_points) float64 on the device: L_j = yl_j - 0.12 and U_j = yr_j + 0.15 over
     dgdm_finger_decode_2d's curves.  scale / offset default to DGDM_DECODE_2D_* (sampler units); 1, 0 takes metres."""
     import torch
     from .. import engine
-    kw = {}
-    if scale is not None:
-        kw["scale"] = float(scale)
-    if offset is not None:
-        kw["offset"] = float(offset)
     dev = torch.device("cuda", torch.cuda.current_device())
     s = torch.as_tensor(samples).to(dev)
-    y = engine.finger_decode_2d(s, int(num_points), **kw)[..., 1].double()
+    y = engine.finger_decode_2d(s, int(num_points), **_decode_units(scale, offset))[..., 1].double()
     return torch.stack([y[:, 0] + LOWER_OFFSET, y[:, 1] + UPPER_OFFSET], dim=1).contiguous()
 
 
@@ -65,6 +65,22 @@ def fold(delta, period: float):
     """continuous_signed_delta (dynamics/utils.py:6-12) of arrays: folded once into [-period / 2, period / 2]."""
     d = np.asarray(delta, dtype=np.float64)
     return np.where(d > period / 2, d - period, np.where(d < -period / 2, d + period, d))
+
+
+def add_poses(out: Dict[str, Any], pairs, **config) -> None:
+    """engine.squeeze_tables' cells and y -> out's start (P, N, 2), closed and settled (P, N, 3): the cells' (theta rad, x m) and y; and
+    out's pairs."""
+    import torch
+    from .. import engine
+    cfg = engine.squeeze_config(**config)
+    T, X = cfg.theta_cells, cfg.x_cells
+    cells = out["cells"].long()
+    theta = (cells // X).double() * (2.0 * np.pi) / float(T)
+    x = -cfg.x_half + (cells % X).double() * (2.0 * cfg.x_half / (X - 1))
+    out["start"] = torch.stack([theta[..., 0], x[..., 0]], dim=-1)
+    out["closed"] = torch.stack([theta[..., 1], x[..., 1], out["y"][..., 0]], dim=-1)
+    out["settled"] = torch.stack([theta[..., 2], x[..., 2], out["y"][..., 1]], dim=-1)
+    out["pairs"] = pairs
 
 
 def squeeze_map(samples, contours, starts, pairs=None, num_points: int = 200, scale: Optional[float] = None, offset: Optional[float] = None,
@@ -82,15 +98,7 @@ def squeeze_map(samples, contours, starts, pairs=None, num_points: int = 200, sc
     pr = all_pairs(sf.shape[0], ob.shape[0]) if pairs is None else np.ascontiguousarray(pairs, dtype=np.int32).reshape(-1, 2)
     out = engine.squeeze_tables(sf, ob, pr, starts, tables=tables, workspace_bytes=workspace_bytes, friction=check_friction(friction, "squeeze_map"),
                                 **config)
-    cfg = engine.squeeze_config(**config)
-    T, X = cfg.theta_cells, cfg.x_cells
-    cells = out["cells"].long()
-    theta = (cells // X).double() * (2.0 * np.pi) / float(T)
-    x = -cfg.x_half + (cells % X).double() * (2.0 * cfg.x_half / (X - 1))
-    out["start"] = torch.stack([theta[..., 0], x[..., 0]], dim=-1)
-    out["closed"] = torch.stack([theta[..., 1], x[..., 1], out["y"][..., 0]], dim=-1)
-    out["settled"] = torch.stack([theta[..., 2], x[..., 2], out["y"][..., 1]], dim=-1)
-    out["pairs"] = pr
+    add_poses(out, pr, **config)
     return out
 
 
@@ -100,6 +108,17 @@ def check_friction(friction, who: str) -> float:
     if not (np.isfinite(mu) and mu >= 0.0):
         raise ValueError(f"{who}: friction {friction!r} is not a finite non-negative number")
     return mu
+
+
+def steps_from_args(args) -> Dict[str, int]:
+    """--squeeze_closing_steps K / --squeeze_window R -> the config keys of those that were given; ValueError for K < 0 or R < 1.
+    Host code."""
+    k, r = getattr(args, "squeeze_closing_steps", None), getattr(args, "squeeze_window", None)
+    if k is not None and k < 0:
+        raise ValueError(f"--squeeze_closing_steps={k}: the number of steps cannot be negative")
+    if r is not None and r < 1:
+        raise ValueError(f"--squeeze_window={r}: the window is at least 1 cell")
+    return {key: int(v) for key, v in (("closing_steps", k), ("window", r)) if v is not None}
 
 
 def squeeze_metric(start, closed, settled, flags, y0=0.0, threshold: Sequence[float] = SCORE_THRESHOLD[1], friction: float = 0.0) -> Dict[str, Any]:
@@ -124,7 +143,37 @@ def squeeze_metric(start, closed, settled, flags, y0=0.0, threshold: Sequence[fl
     return out
 
 
-class SqueezeSimulator:
+def start_orientations(num_rot: int, ori_range: Sequence[float]) -> np.ndarray:
+    """starts (num_rot, 3): the simulators' start poses, (linspace(ori_range) + 1) * pi at x0 = y0 = 0."""
+    theta0 = (np.linspace(ori_range[0], ori_range[1], int(num_rot)) + 1.0) * np.pi
+    return np.stack([theta0, np.zeros_like(theta0), np.zeros_like(theta0)], axis=1)
+
+
+def simulator_lists(out: Dict[str, Any], threshold: Sequence[float], friction: float = 0.0):
+    """A map's outputs -> the simulators' eight lists, one entry per pair: ``squeeze_metric`` in the metrics' slot, None (no videos: [])
+    in the others - nothing is rendered."""
+    start, closed, settled, flags = (out[k].cpu().numpy() for k in ("start", "closed", "settled", "flags"))
+    metrics = [squeeze_metric(start[p], closed[p], settled[p], flags[p], 0.0, threshold, friction) for p in range(len(flags))]
+    none: List[Any] = [None] * len(flags)
+    return list(none), metrics, list(none), list(none), list(none), list(none), [[] for _ in none], list(none)
+
+
+class _Simulator:
+    """What the two simulators share: the model's config with ``closing_steps`` / ``window`` laid over it, checked on the host."""
+
+    def configure(self, closing_steps: Optional[int], window: Optional[int], config: Dict[str, Any]) -> None:
+        self.config = dict(config)
+        if closing_steps is not None:
+            self.config["closing_steps"] = int(closing_steps)
+        if window is not None:
+            self.config["window"] = int(window)
+        from .. import engine
+        c = engine.squeeze_config(**self.config)
+        if c.closing_steps < 0 or c.window < 1:
+            raise ValueError(f"{type(self).__name__}: closing_steps = {c.closing_steps} (need >= 0), window = {c.window} (need >= 1)")
+
+
+class SqueezeSimulator(_Simulator):
     """``sim_test_batch`` (dynamics/sim_test_mj.py:249) answered by the squeeze model: ``simulator(samples (n, L, 1), object_ids,
     save_dir, num_cpus=, num_rot=, ori_range=, render=, render_last=)`` -> ``(gripper_imgs, metrics, profiles, profiles_x, profiles_y,
     finals, videos, save_gripper_dirs)``, object-major, gripper-minor, like ``PredictedSimulator``.
@@ -141,15 +190,7 @@ class SqueezeSimulator:
             raise ValueError("SqueezeSimulator: the squeeze model is 2-D only")
         self.friction = check_friction(friction, "SqueezeSimulator")
         self.diffusion = diffusion
-        self.config = dict(config)
-        if closing_steps is not None:
-            self.config["closing_steps"] = int(closing_steps)
-        if window is not None:
-            self.config["window"] = int(window)
-        from .. import engine
-        c = engine.squeeze_config(**self.config)
-        if c.closing_steps < 0 or c.window < 1:
-            raise ValueError(f"SqueezeSimulator: closing_steps = {c.closing_steps} (need >= 0), window = {c.window} (need >= 1)")
+        self.configure(closing_steps, window, config)
 
     def __call__(self, samples, object_ids, save_dir: Optional[str] = None, num_cpus: int = 32, num_rot: int = 360,
                  ori_range: Sequence[float] = (-1.0, 1.0), render: bool = True, render_last: bool = False):
@@ -162,14 +203,8 @@ class SqueezeSimulator:
         known = d._object_ids()
         oidx = [known.index(o) for o in object_ids]
         bank = torch.as_tensor(d.object_vertices).detach().cpu().double()[oidx] * OBJECT_HALF_BOX_2D
-        theta0 = (np.linspace(ori_range[0], ori_range[1], int(num_rot)) + 1.0) * np.pi
-        starts = np.stack([theta0, np.zeros_like(theta0), np.zeros_like(theta0)], axis=1)
-        out = squeeze_map(x.reshape(n, -1), bank, starts, friction=self.friction, **self.config)
-        start, closed, settled, flags = (out[k].cpu().numpy() for k in ("start", "closed", "settled", "flags"))
-        thr = SCORE_THRESHOLD[1]
-        metrics = [squeeze_metric(start[p], closed[p], settled[p], flags[p], 0.0, thr, self.friction) for p in range(len(oidx) * n)]
-        none: List[Any] = [None] * (len(oidx) * n)
-        return list(none), metrics, list(none), list(none), list(none), list(none), [[] for _ in none], list(none)
+        out = squeeze_map(x.reshape(n, -1), bank, start_orientations(num_rot, ori_range), friction=self.friction, **self.config)
+        return simulator_lists(out, SCORE_THRESHOLD[1], self.friction)
 
 
 # ---------------------------------------------------------------------------------------------------------------- 3-D: a sliced squeeze
@@ -189,15 +224,10 @@ def finger_surfaces_3d(samples, sample_size: int = 25, width: float = FINGER_WID
     finger.  scale / offset default to the sampler's units; 1, 0 takes metres."""
     import torch
     from .. import engine
-    kw = {}
-    if scale is not None:
-        kw["scale"] = float(scale)
-    if offset is not None:
-        kw["offset"] = float(offset)
     dev = torch.device("cuda", torch.cuda.current_device())
     s = torch.as_tensor(samples).to(dev)
     n = int(sample_size)
-    pts = engine.finger_decode_3d(s, n, **kw).double().reshape(s.shape[0], 2, n, n, 3)      # [B][finger][u][v][xyz]
+    pts = engine.finger_decode_3d(s, n, **_decode_units(scale, offset)).double().reshape(s.shape[0], 2, n, n, 3)      # [B][finger][u][v][xyz]
     y = pts[..., 1].transpose(2, 3)                                                           # [B][finger][v][u]
     surfaces = torch.stack([y[:, 0] + LOWER_OFFSET_3D + float(width), y[:, 1] + UPPER_OFFSET_3D], dim=1).contiguous()
     return pts[0, 0, :, 0, 0].cpu().numpy().copy(), pts[0, 0, 0, :, 2].cpu().numpy().copy(), surfaces
@@ -210,7 +240,6 @@ def squeeze_map_3d(samples, meshes, starts, pairs=None, sample_size: int = 25, w
     the scene's frame (standing on z = 0), starts (N, 3) = (theta0 rad, x0 m, y0 m) shared by all pairs.  The meshes are sliced on the
     finger grid's levels (engine.squeeze_slice) and squeezed level by level (engine.squeeze_tables_3d); what lies between two levels is
     not seen.  Output keys as squeeze_map, plus segments / offsets.  Frictionless only: a ``friction`` argument is refused (FRICTION_2D_ONLY)."""
-    import torch
     from .. import engine
     if friction is not None:
         raise ValueError(f"squeeze_map_3d: {FRICTION_2D_ONLY}")
@@ -218,20 +247,12 @@ def squeeze_map_3d(samples, meshes, starts, pairs=None, sample_size: int = 25, w
     sl = engine.squeeze_slice(meshes, gz)
     pr = all_pairs(sf.shape[0], len(sl["offsets"])) if pairs is None else np.ascontiguousarray(pairs, dtype=np.int32).reshape(-1, 2)
     out = engine.squeeze_tables_3d(sf, gx, sl["segments"], sl["offsets"], pr, starts, tables=tables, workspace_bytes=workspace_bytes, **config)
-    cfg = engine.squeeze_config(**config)
-    T, X = cfg.theta_cells, cfg.x_cells
-    cells = out["cells"].long()
-    theta = (cells // X).double() * (2.0 * np.pi) / float(T)
-    x = -cfg.x_half + (cells % X).double() * (2.0 * cfg.x_half / (X - 1))
-    out["start"] = torch.stack([theta[..., 0], x[..., 0]], dim=-1)
-    out["closed"] = torch.stack([theta[..., 1], x[..., 1], out["y"][..., 0]], dim=-1)
-    out["settled"] = torch.stack([theta[..., 2], x[..., 2], out["y"][..., 1]], dim=-1)
-    out["pairs"] = pr
+    add_poses(out, pr, **config)
     out.update(segments=sl["segments"], offsets=sl["offsets"])
     return out
 
 
-class SqueezeSimulator3D:
+class SqueezeSimulator3D(_Simulator):
     """``sim_test_batch_3d`` (dynamics/sim_test_mj_3d.py:229) answered by the sliced squeeze: ``simulator(samples (n, 42, 1), object_names,
     save_dir, num_cpus=, num_rot=, ori_range=, render=, render_last=)`` -> the same eight lists as ``SqueezeSimulator``, object-major,
     gripper-minor.  An object name is read from ``<object_mesh_dir>/<name>/model.obj`` (engine.read_obj) as it stands, in metres; a run
@@ -251,15 +272,7 @@ class SqueezeSimulator3D:
             raise ValueError("SqueezeSimulator3D: the run's objects have no meshes (objects.npy or synthetic clouds): the sliced squeeze needs "
                              "<object_dir>/<name>/model.obj")
         self.sample_size, self.width = int(sample_size), float(width)
-        self.config = dict(config)
-        if closing_steps is not None:
-            self.config["closing_steps"] = int(closing_steps)
-        if window is not None:
-            self.config["window"] = int(window)
-        from .. import engine
-        c = engine.squeeze_config(**self.config)
-        if c.closing_steps < 0 or c.window < 1:
-            raise ValueError(f"SqueezeSimulator3D: closing_steps = {c.closing_steps} (need >= 0), window = {c.window} (need >= 1)")
+        self.configure(closing_steps, window, config)
         self._meshes: Dict[str, Any] = {}
 
     def mesh(self, name):
@@ -279,11 +292,6 @@ class SqueezeSimulator3D:
         x = torch.as_tensor(np.asarray(samples), dtype=torch.float32)
         n = x.shape[0]
         meshes = [self.mesh(o) for o in object_names]
-        theta0 = (np.linspace(ori_range[0], ori_range[1], int(num_rot)) + 1.0) * np.pi
-        starts = np.stack([theta0, np.zeros_like(theta0), np.zeros_like(theta0)], axis=1)
-        out = squeeze_map_3d(x.reshape(n, -1), meshes, starts, sample_size=self.sample_size, width=self.width, **self.config)
-        start, closed, settled, flags = (out[k].cpu().numpy() for k in ("start", "closed", "settled", "flags"))
-        thr = SCORE_THRESHOLD[0]
-        metrics = [squeeze_metric(start[p], closed[p], settled[p], flags[p], 0.0, thr) for p in range(len(meshes) * n)]
-        none: List[Any] = [None] * (len(meshes) * n)
-        return list(none), metrics, list(none), list(none), list(none), list(none), [[] for _ in none], list(none)
+        out = squeeze_map_3d(x.reshape(n, -1), meshes, start_orientations(num_rot, ori_range), sample_size=self.sample_size, width=self.width,
+                             **self.config)
+        return simulator_lists(out, SCORE_THRESHOLD[0])

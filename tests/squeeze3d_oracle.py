@@ -8,7 +8,7 @@ from typing import Dict, Sequence, Tuple
 
 import numpy as np
 
-from tests.squeeze_oracle import INF, kth_successor, pose_y, rotation_table, settled, snap, successors  # noqa: F401
+from tests.squeeze_oracle import INF, kth_successor, map_outputs, pose_y, rotation_table, settled, snap, successors  # noqa: F401
 
 
 def slice_mesh(verts, tris, gz) -> Tuple[np.ndarray, np.ndarray]:
@@ -105,18 +105,8 @@ def touch_tables_3d(lower, upper, gx, segments, offsets, rot, x_cells: int, x_ha
 def squeeze_pair_3d(lower, upper, gx, segments, offsets, rot, starts, x_cells: int, x_half: float, window: int, closing_steps: int,
                     travel_max: float) -> Dict[str, np.ndarray]:
     """Everything dgdm_squeeze_map_3d returns for one pair."""
-    T = len(rot)
     tl, tr, S = touch_tables_3d(lower, upper, gx, segments, offsets, rot, x_cells, x_half)
-    succ = successors(S, window, travel_max)
-    kth, fix = kth_successor(succ, closing_steps), settled(succ)
-    st = np.asarray(starts, dtype=np.float64).reshape(-1, 3)
-    c0 = snap(st, T, x_cells, x_half)
-    ck, cf = kth[c0].astype(np.int64), fix[c0].astype(np.int64)
-    Sf = S.reshape(-1)
-    flags = (Sf[c0] >= travel_max) * 1 + (Sf[cf] >= travel_max) * 2 + ((cf % x_cells == 0) | (cf % x_cells == x_cells - 1)) * 4
-    y = np.stack([pose_y(ck, st[:, 2], tl, tr, S, travel_max), pose_y(cf, st[:, 2], tl, tr, S, travel_max)], axis=1)
-    return {"touch_l": tl, "touch_r": tr, "S": S, "succ": succ, "cells": np.stack([c0, ck, cf], axis=1).astype(np.int32), "y": y,
-            "flags": flags.astype(np.int32)}
+    return map_outputs(tl, tr, S, successors(S, window, travel_max), starts, len(rot), x_cells, x_half, closing_steps, travel_max)
 
 
 def squeeze_map_3d(surfaces, gx, segments, offsets, pairs: Sequence, rot, starts, **cfg) -> Dict[str, np.ndarray]:

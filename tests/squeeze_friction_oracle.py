@@ -118,21 +118,13 @@ def squeeze_pair(lower, upper, verts, rot, starts, x_cells: int, x_half: float, 
     """Everything dgdm_squeeze_map_friction returns for one pair: the three tables, succ, jam, contact, and per start cells (start, closed,
     settled), y (closed, settled) and flags (1 / 2 / 4 as without friction, 8 the start cell is jammed, 16 the settled cell is).
     tables: contact_tables of the same inputs, when the caller already holds them (they do not depend on mu)."""
-    T = len(rot)
     tab = tables if tables is not None else contact_tables(lower, upper, verts, rot, x_cells, x_half, half_len)
-    tl, tr, S = tab["touch_l"], tab["touch_r"], tab["S"]
+    S = tab["S"]
     jam = jam_table(tab, mu, travel_max)
-    succ = successors(S, jam, window, travel_max)
-    kth, fix = so.kth_successor(succ, closing_steps), so.settled(succ)
-    st = np.asarray(starts, dtype=np.float64).reshape(-1, 3)
-    c0 = so.snap(st, T, x_cells, x_half)
-    ck, cf = kth[c0].astype(np.int64), fix[c0].astype(np.int64)
-    Sf, jf = S.reshape(-1), jam.reshape(-1)
-    flags = (Sf[c0] >= travel_max) * 1 + (Sf[cf] >= travel_max) * 2 + ((cf % x_cells == 0) | (cf % x_cells == x_cells - 1)) * 4 + \
-        (jf[c0] != 0) * 8 + (jf[cf] != 0) * 16
-    y = np.stack([so.pose_y(ck, st[:, 2], tl, tr, S, travel_max), so.pose_y(cf, st[:, 2], tl, tr, S, travel_max)], axis=1)
-    return {"touch_l": tl, "touch_r": tr, "S": S, "succ": succ, "jam": jam, "contact": tab["contact"],
-            "cells": np.stack([c0, ck, cf], axis=1).astype(np.int32), "y": y, "flags": flags.astype(np.int32)}
+    out = so.map_outputs(tab["touch_l"], tab["touch_r"], S, successors(S, jam, window, travel_max), starts, len(rot), x_cells, x_half,
+                         closing_steps, travel_max, jam=jam)
+    out["contact"] = tab["contact"]
+    return out
 
 
 def squeeze_map(surfaces, objects, pairs: Sequence, rot, starts, **cfg) -> Dict[str, np.ndarray]:

@@ -145,9 +145,15 @@ def squeeze_pair(lower, upper, verts, rot, starts, x_cells: int, x_half: float, 
                  half_len: float = 0.12) -> Dict[str, np.ndarray]:
     """Everything dgdm_squeeze_map returns for one pair: the three tables, succ, and per start cells (start, closed, settled), y
     (closed, settled) and flags."""
-    T = len(rot)
     tl, tr, S = touch_tables(lower, upper, verts, rot, x_cells, x_half, half_len)
-    succ = successors(S, window, travel_max)
+    return map_outputs(tl, tr, S, successors(S, window, travel_max), starts, len(rot), x_cells, x_half, closing_steps, travel_max)
+
+
+def map_outputs(tl, tr, S, succ, starts, T: int, x_cells: int, x_half: float, closing_steps: int, travel_max: float,
+                jam=None) -> Dict[str, np.ndarray]:
+    """From one pair's tables and successors to a map entry's outputs, the same for all three entries: the tables, succ, and per start
+    cells (start, closed, settled), y (closed, settled) and flags 1 / 2 / 4.  jam [theta][x_cells] (friction; succ then holds its
+    override): also returned, and flags carries 8 (the start cell is jammed) and 16 (the settled cell is)."""
     kth, fix = kth_successor(succ, closing_steps), settled(succ)
     st = np.asarray(starts, dtype=np.float64).reshape(-1, 3)
     c0 = snap(st, T, x_cells, x_half)
@@ -155,8 +161,13 @@ def squeeze_pair(lower, upper, verts, rot, starts, x_cells: int, x_half: float, 
     Sf = S.reshape(-1)
     flags = (Sf[c0] >= travel_max) * 1 + (Sf[cf] >= travel_max) * 2 + ((cf % x_cells == 0) | (cf % x_cells == x_cells - 1)) * 4
     y = np.stack([pose_y(ck, st[:, 2], tl, tr, S, travel_max), pose_y(cf, st[:, 2], tl, tr, S, travel_max)], axis=1)
-    return {"touch_l": tl, "touch_r": tr, "S": S, "succ": succ, "cells": np.stack([c0, ck, cf], axis=1).astype(np.int32), "y": y,
-            "flags": flags.astype(np.int32)}
+    out = {"touch_l": tl, "touch_r": tr, "S": S, "succ": succ, "cells": np.stack([c0, ck, cf], axis=1).astype(np.int32), "y": y}
+    if jam is not None:
+        jf = np.asarray(jam).reshape(-1)
+        flags = flags + (jf[c0] != 0) * 8 + (jf[cf] != 0) * 16
+        out["jam"] = jam
+    out["flags"] = flags.astype(np.int32)
+    return out
 
 
 def squeeze_map(surfaces, objects, pairs: Sequence, rot, starts, **cfg) -> Dict[str, np.ndarray]:

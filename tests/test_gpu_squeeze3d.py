@@ -120,12 +120,16 @@ def reference(name):
                               closing_steps=cfg["closing_steps"], travel_max=cfg["travel_max"])
 
 
-def run(name, chunk_pairs=4):
+def workspace(name, chunk_pairs):
+    return int(_lib.lib().dgdm_squeeze_map_3d_workspace_bytes(C.byref(engine.squeeze_config(**case_inputs(name)[2])), chunk_pairs, len(GX), len(GZ), 4))
+
+
+def run(name, chunk_pairs=4, slack=0):
+    """slack: bytes on top of the size the library gives for chunk_pairs - a workspace that is no size it returned."""
     sf, st, cfg, pairs = case_inputs(name)
     sl = engine.squeeze_slice(meshes(), GZ)
-    ws = _lib.lib().dgdm_squeeze_map_3d_workspace_bytes(C.byref(engine.squeeze_config(**cfg)), chunk_pairs, len(GX), len(GZ), 4)
-    out = engine.squeeze_tables_3d(sf, GX, sl["segments"], sl["offsets"], pairs, st, rot=so.rotation_table(THETA), tables=True, workspace_bytes=int(ws),
-                                   **cfg)
+    out = engine.squeeze_tables_3d(sf, GX, sl["segments"], sl["offsets"], pairs, st, rot=so.rotation_table(THETA), tables=True,
+                                   workspace_bytes=workspace(name, chunk_pairs) + slack, **cfg)
     return {k: v.cpu().numpy() for k, v in out.items()}
 
 
@@ -175,6 +179,13 @@ def test_repeated_calls_and_chunkings_are_bit_identical(dev):
     a, b, c = run("all_k3"), run("all_k3"), run("all_k3", chunk_pairs=1)
     for k in a:
         assert np.array_equal(a[k].view(np.uint8), b[k].view(np.uint8)) and np.array_equal(a[k].view(np.uint8), c[k].view(np.uint8)), k
+    # 8 pairs in chunks of 3, 3, 2: a shorter last chunk beside the entry's extra block (gx, level offsets); then 1000 bytes more, which
+    # is still 3 pairs and no size the library returns
+    assert workspace("all_k3", 4) - workspace("all_k3", 3) > 1000
+    for got in (run("all_k3", chunk_pairs=3), run("all_k3", chunk_pairs=3, slack=1000)):
+        assert set(got) == set(a)
+        for k in a:
+            assert np.array_equal(a[k].view(np.uint8), got[k].view(np.uint8)), k
 
 
 def test_an_object_without_segments_is_loose_everywhere(dev):

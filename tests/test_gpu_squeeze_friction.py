@@ -89,10 +89,12 @@ def reference(m, nv, window, k, mu, T=24, X=7):
     return {key: np.stack([o[key] for o in outs]) for key in outs[0]}
 
 
-def run(m, nv, window, k, mu, T=24, X=7, chunk_pairs=6, entry="friction"):
+def run(m, nv, window, k, mu, T=24, X=7, chunk_pairs=6, entry="friction", slack=0):
+    """slack: bytes on top of the size the library gives for chunk_pairs, which must still hold no further pair."""
     cfg = dict(theta_cells=T, x_cells=X, x_half=XH, window=window, closing_steps=k, travel_max=TM, finger_half_len=HL)
     size = _lib.lib().dgdm_squeeze_friction_workspace_bytes if entry == "friction" else _lib.lib().dgdm_squeeze_workspace_bytes
-    ws = int(size(C.byref(engine.squeeze_config(**cfg)), chunk_pairs))
+    ws = int(size(C.byref(engine.squeeze_config(**cfg)), chunk_pairs)) + slack
+    assert slack == 0 or ws < int(size(C.byref(engine.squeeze_config(**cfg)), chunk_pairs + 1))
     kw = dict(friction=mu, jam=True, contact=True) if entry == "friction" else {}
     out = engine.squeeze_tables(fingers(m), polygons(nv), PAIRS, starts(T, XH), rot=so.rotation_table(T), tables=True, workspace_bytes=ws, **cfg, **kw)
     return {key: v.cpu().numpy() for key, v in out.items()}
@@ -130,6 +132,13 @@ def test_a_workspace_of_one_pair_runs_the_chunk_loop(dev):
     compare(one, ref)
     for key in one:
         assert np.array_equal(one[key].view(np.uint8), six[key].view(np.uint8)), key
+    # 6 pairs in chunks of 4 and 2: a shorter last chunk behind the jam table; then 1000 bytes more, still 4 pairs and no size the
+    # library returns
+    assert {"jam", "contact"} <= set(six)
+    for got in (run(9, 12, 2, 3, 0.5, chunk_pairs=4), run(9, 12, 2, 3, 0.5, chunk_pairs=4, slack=1000)):
+        assert set(got) == set(six)
+        for key in six:
+            assert np.array_equal(six[key].view(np.uint8), got[key].view(np.uint8)), key
 
 
 def test_more_x_cells_than_lanes(dev):
