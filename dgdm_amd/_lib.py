@@ -129,6 +129,7 @@ PROTOTYPES = {
                                               C.c_int64, C.c_int64, _P]),
     "dgdm_guidance_debug_rollout_table": (C.c_int, [_P, C.c_int, _P, _P, C.POINTER(C.c_int32), C.POINTER(C.c_int32), _P]),
     "dgdm_convergence_rowcoef": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int64, _P]),
+    "dgdm_debug_row_plan": (C.c_int, [_P, C.c_int, C.c_int64, C.c_int, C.c_int64, C.c_int64, C.c_int, C.c_int, _P, _P, _P]),
     "dgdm_torch_rng_seed": (C.c_int, [_P, C.c_int64, C.c_uint64]),
     "dgdm_torch_rng_randint": (C.c_int, [_P, C.c_int64, C.c_uint32, C.c_int64, _P]),
     "dgdm_torch_rng_fps_starts": (C.c_int, [_P, C.c_int64, C.c_int, C.c_int64, C.c_int64, C.c_int64, _P, C.c_int64]),

@@ -73,6 +73,76 @@ struct DevBuf {
     template <class T> T *as() const { return reinterpret_cast<T *>(p); }
 };
 
+// A timing-disabled event, created on first use and destroyed with its owner.  Never recorded = never created: waiting for such an
+// event, on a stream or on the host, is the no-op it is in HIP.
+struct Event {
+    hipEvent_t e = nullptr;
+    Event() = default;
+    Event(const Event &) = delete;
+    Event &operator=(const Event &) = delete;
+    ~Event() { if (e) (void)hipEventDestroy(e); }
+    int get(hipEvent_t *out) {
+        if (!e) DGDM_HIP_CHECK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+        *out = e;
+        return DGDM_OK;
+    }
+    int record(hipStream_t s) {
+        hipEvent_t ev;
+        int rc = get(&ev);
+        if (rc) return rc;
+        DGDM_HIP_CHECK(hipEventRecord(ev, s));
+        return DGDM_OK;
+    }
+    int wait(hipStream_t s) const {                 // `s` waits for what the event was last recorded behind
+        if (e) DGDM_HIP_CHECK(hipStreamWaitEvent(s, e, 0));
+        return DGDM_OK;
+    }
+    int synchronize() const {                       // the host waits
+        if (e) DGDM_HIP_CHECK(hipEventSynchronize(e));
+        return DGDM_OK;
+    }
+};
+
+// A non-blocking stream, created on first use and destroyed with its owner.
+struct Stream {
+    hipStream_t s = nullptr;
+    Stream() = default;
+    Stream(const Stream &) = delete;
+    Stream &operator=(const Stream &) = delete;
+    ~Stream() { if (s) (void)hipStreamDestroy(s); }
+    int get(hipStream_t *out) {
+        if (!s) DGDM_HIP_CHECK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
+        *out = s;
+        return DGDM_OK;
+    }
+    void synchronize() const { if (s) (void)hipStreamSynchronize(s); }
+};
+
+// A grow-only pinned host block and the event that guards it: whoever enqueues a copy out of (or into) the block records `ev` behind
+// it, and growing the block waits for `ev` before the old block is freed.
+struct PinnedBuf {
+    void  *p = nullptr;
+    size_t bytes = 0;
+    Event  ev;
+    PinnedBuf() = default;
+    PinnedBuf(const PinnedBuf &) = delete;
+    PinnedBuf &operator=(const PinnedBuf &) = delete;
+    ~PinnedBuf() { if (p) (void)hipHostFree(p); }
+    int reserve(size_t n) {
+        if (n <= bytes) return DGDM_OK;
+        if (p) {
+            int rc = ev.synchronize();
+            if (rc) return rc;
+            DGDM_HIP_CHECK(hipHostFree(p));
+            p = nullptr; bytes = 0;
+        }
+        DGDM_HIP_CHECK(hipHostMalloc(&p, n, hipHostMallocDefault));
+        bytes = n;
+        return DGDM_OK;
+    }
+    template <class T> T *as() const { return reinterpret_cast<T *>(p); }
+};
+
 // state_dict lookup
 struct StateDict {
     std::map<std::string, const DgdmTensor *> m;

@@ -501,6 +501,17 @@ int dgdm_guidance_label_settled(DgdmGuidance *g, const float *fingers_dev, int64
 int dgdm_convergence_rowcoef(const int64_t *centers_host, int n_centers, int grid_size, int num_pos,
                              int64_t total_rows, int64_t sub_batch_size /* 0 = no sub-batching */, float *rowcoef_host);
 
+/* Host-only test entry (no HIP call): the row plan of a 3-D gather launch, as the guidance handle makes it from the FPS start draws.
+ *   in:  call k of chain c at starts_host + k * call_stride + c * 2 * rows, in the draw order of dgdm_dyn3d_guidance_grad's starts_host:
+ *        per sub-batch of up to sub_batch_size rows, its sa1 draws (each in [0, num_object_points)), then its sa2 draws (in [0, 512))
+ *   pairs_out [n_chains][n_calls * rows][2]: (s1, s2) per row; a chain's rows of all calls form one run, row k * rows + r
+ *   need_order != 0: order_out [n_chains][n_calls * rows] - the chain's rows sorted by (s1, s2), rows with equal draws in row order,
+ *        each as row | s2 << 22 - and group_off_out [n_chains][num_object_points + 1] - where the rows of each s1 start in that list
+ *        ([num_object_points] = their number); need_order == 0: neither is touched (both may be NULL).
+ * DGDM_EINVAL for a draw out of range, and with need_order for n_calls * rows >= 2^22 (the row id's bits below s2).                 */
+int dgdm_debug_row_plan(const int64_t *starts_host, int n_chains, int64_t rows, int n_calls, int64_t call_stride, int64_t sub_batch_size,
+                        int num_object_points, int need_order, int32_t *pairs_out, int32_t *order_out, int32_t *group_off_out);
+
 /* ------------------------------------------------------------------ the path's random input: FPS start draws
  * farthest_point_sample draws its start index with torch.randint(0, N, (rows,)) on torch's CPU default generator
  * (dynamics/models/pointnet2_utils.py:83), twice per classifier call and sub-batch.  These host functions replay that generator

@@ -70,6 +70,108 @@ def test_convergence_rowcoef_matches_autograd(lib, rows, sub):
     assert cells > 0
 
 
+def _row_plan(lib, starts, n_chains, rows, n_calls, stride, sub, N, need_order=1, fill=-7):
+    """dgdm_debug_row_plan -> (rc, pairs, order, group offsets); the outputs start out filled with `fill`."""
+    rt = rows * n_calls
+    pairs = np.full((n_chains, rt, 2), fill, np.int32)
+    order = np.full((n_chains, rt), fill, np.int32)
+    goff = np.full((n_chains, N + 1), fill, np.int32)
+    starts = np.ascontiguousarray(starts, np.int64)
+    rc = lib.dgdm_debug_row_plan(starts.ctypes.data, n_chains, rows, n_calls, stride, sub, N, need_order, pairs.ctypes.data, order.ctypes.data,
+                                 goff.ctypes.data)
+    return rc, pairs, order, goff
+
+
+def _row_plan_restated(starts, n_chains, rows, n_calls, stride, sub, N):
+    """include/dgdm_hip.h's description of dgdm_debug_row_plan in numpy."""
+    rt = rows * n_calls
+    pairs = np.empty((n_chains, rt, 2), np.int32)
+    for c in range(n_chains):
+        for k in range(n_calls):
+            call = starts[k * stride + c * 2 * rows:][:2 * rows]
+            for r0 in range(0, rows, sub):
+                n = min(sub, rows - r0)
+                pairs[c, k * rows + r0:k * rows + r0 + n, 0] = call[2 * r0:2 * r0 + n]              # the sub-batch's sa1 draws, then its sa2 draws
+                pairs[c, k * rows + r0:k * rows + r0 + n, 1] = call[2 * r0 + n:2 * r0 + 2 * n]
+    order = np.empty((n_chains, rt), np.int32)
+    goff = np.empty((n_chains, N + 1), np.int32)
+    for c in range(n_chains):
+        s1, s2 = pairs[c, :, 0], pairs[c, :, 1]
+        idx = np.lexsort((s2, s1))                           # stable: by s1, then s2, equal draws in row order
+        order[c] = idx | (s2[idx] << 22)
+        goff[c] = np.concatenate([[0], np.cumsum(np.bincount(s1, minlength=N))])
+    return pairs, order, goff
+
+
+def _draws(rs, n_chains, rows, n_calls, stride, sub, N, s1_values=None):
+    """Random draws in the starts_host layout; what lies between the calls' blocks is -1 (a read of it would be refused)."""
+    starts = np.full((n_calls - 1) * stride + n_chains * 2 * rows, -1, np.int64)
+    for k in range(n_calls):
+        for c in range(n_chains):
+            call = starts[k * stride + c * 2 * rows:][:2 * rows]
+            for r0 in range(0, rows, sub):
+                n = min(sub, rows - r0)
+                call[2 * r0:2 * r0 + n] = rs.choice(s1_values, n) if s1_values is not None else rs.randint(0, N, n)
+                call[2 * r0 + n:2 * r0 + 2 * n] = rs.randint(0, 512, n)
+    return starts
+
+
+def test_row_plan_matches_its_description(lib):
+    """dgdm_debug_row_plan (= plan_chain_rows, the host half of the 3-D gather's upload) against the header's description restated in
+    numpy, at the smallest sizes at which each branch runs."""
+    rs = np.random.RandomState(11)
+    # a short last sub-batch (7 = 3 + 3 + 1), two chains; s1 = 3 is never drawn (an empty group); repeated (s1, s2) pairs, where the
+    # stable order shows; s2 = 511
+    N, rows, sub = 5, 7, 3
+    starts = _draws(rs, 2, rows, 1, 0, sub, N, s1_values=[0, 1, 2, 4])
+    starts[[0, 1, 2]] = [4, 4, 2]; starts[[3, 4, 5]] = [511, 511, 0]          # chain 0, first sub-batch: rows 0 and 1 share (4, 511)
+    starts[6:9] = [4, 2, 2]; starts[9:12] = [511, 0, 0]                       # second sub-batch: row 3 repeats it, rows 2, 4 and 5 share (2, 0)
+    rc, pairs, order, goff = _row_plan(lib, starts, 2, rows, 1, 0, sub, N)
+    assert rc == _lib.OK
+    want = _row_plan_restated(starts, 2, rows, 1, 0, sub, N)
+    assert np.array_equal(pairs, want[0]) and np.array_equal(order, want[1]) and np.array_equal(goff, want[2])
+    assert pairs[0, :6].tolist() == [[4, 511], [4, 511], [2, 0], [4, 511], [2, 0], [2, 0]]
+    assert (goff[:, 4] == goff[:, 3]).all()                                   # the empty group of s1 = 3
+    chain0 = order[0][goff[0, 2]:goff[0, 3]]                                  # s1 = 2: rows 2, 4, 5 in row order
+    assert (chain0 & ((1 << 22) - 1)).tolist()[:3] == [2, 4, 5] and (order[0] >> 22).max() == 511
+    # two calls, their blocks further apart than the chains need
+    stride = 2 * 2 * rows + 5
+    starts = _draws(rs, 2, rows, 2, stride, sub, N)
+    rc, pairs, order, goff = _row_plan(lib, starts, 2, rows, 2, stride, sub, N)
+    assert rc == _lib.OK
+    want = _row_plan_restated(starts, 2, rows, 2, stride, sub, N)
+    assert np.array_equal(pairs, want[0]) and np.array_equal(order, want[1]) and np.array_equal(goff, want[2])
+    # need_order = 0: the pairs alone; order and offsets are left as they were
+    rc, pairs, order, goff = _row_plan(lib, starts, 2, rows, 2, stride, sub, N, need_order=0)
+    assert rc == _lib.OK and np.array_equal(pairs, want[0]) and (order == -7).all() and (goff == -7).all()
+    # the threaded branch: 4 chains x 40 000 rows = 2 x 65 536 rows and a bit -> 2 threads
+    N, rows, sub = 512, 40000, 512
+    starts = _draws(rs, 4, rows, 1, 0, sub, N)
+    rc, pairs, order, goff = _row_plan(lib, starts, 4, rows, 1, 0, sub, N)
+    assert rc == _lib.OK
+    want = _row_plan_restated(starts, 4, rows, 1, 0, sub, N)
+    assert np.array_equal(pairs, want[0]) and np.array_equal(order, want[1]) and np.array_equal(goff, want[2])
+
+
+def test_row_plan_refusals(lib):
+    N, rows, sub = 5, 7, 3
+    good = _draws(np.random.RandomState(3), 1, rows, 1, 0, sub, N)
+    for at, value in ((1, -1), (1, N), (4, 512)):            # an sa1 draw below and above its range, an sa2 draw above its
+        starts = good.copy()
+        starts[at] = value
+        rc = _row_plan(lib, starts, 1, rows, 1, 0, sub, N)[0]
+        assert rc == _lib.EINVAL
+        assert lib.dgdm_last_error().decode() == "FPS start out of range (sa1 must be in [0, 5), sa2 in [0, 512))"
+    assert _row_plan(lib, good, 1, rows, 1, 0, sub, N)[0] == _lib.OK
+    # 2^22 rows per chain do not fit beside s2 in a sorted row; without the order they do not need to
+    rows = 1 << 21
+    starts = np.zeros(2 * 2 * rows, np.int64)
+    rt = 2 * rows
+    pairs, order, goff = np.zeros((rt, 2), np.int32), np.zeros(rt, np.int32), np.zeros(N + 1, np.int32)
+    rc = lib.dgdm_debug_row_plan(starts.ctypes.data, 1, rows, 2, 2 * rows, 512, N, 1, pairs.ctypes.data, order.ctypes.data, goff.ctypes.data)
+    assert rc == _lib.EINVAL and lib.dgdm_last_error().decode() == "4194304 rows per chain in one gather launch (limit 4194303)"
+
+
 def test_start_stream_matches_reference_draws():
     """StartStream replays torch.randint exactly as the oracle's (= the reference's) classifier calls consume it."""
     g = util.load("g5_dyn3d.npz")
