@@ -420,13 +420,19 @@ __global__ __launch_bounds__(256, 1) void trunk_bf16_kernel(const TrunkParams p)
     const int tid = threadIdx.x;
     const int lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    int tile0 = (blockIdx.x * 4 + wave) * 2;
+    // A wave's two tiles are a pair of ONE chain, counted from the chain's first tile: tiles of the same finger are added in float32
+    // before the fold (same_b below), so which tiles pair up decides bits, and it must not depend on where the chain stands in the
+    // launch (with an odd number of tiles per chain, pairs counted over the whole launch would straddle the chains' seams).
+    const int per_chain = p.B * p.tiles_per_b, wpc = (per_chain + 1) / 2, nwaves = (p.ntiles / per_chain) * wpc;
+    int w = blockIdx.x * 4 + wave;
     // 2-D: a wave without a tile leaves (no barrier anywhere).  3-D: the front's weight stream is staged by all four waves together,
-    // so a wave without a tile goes through the front on the last tile's rows (nothing it computes is stored) and leaves after it.
-    const bool active = tile0 < p.ntiles;
+    // so a wave without a tile goes through the front on the last wave's rows (nothing it computes is stored) and leaves after it.
+    const bool active = w < nwaves;
     if (KIND != 3 && !active) return;
-    if (!active) tile0 = (p.ntiles - 1) & ~1;
-    const bool has1 = tile0 + 1 < p.ntiles;               // an odd tile count leaves the last wave one real tile
+    if (!active) w = nwaves - 1;
+    const int wchain = w / wpc, wtile = 2 * (w - wchain * wpc);
+    const int tile0 = wchain * per_chain + wtile;
+    const bool has1 = wtile + 1 < per_chain;              // an odd tile count leaves the chain's last wave one real tile
     const int n = lane & 31;
     const int h4 = (lane >> 5) * 4;
     const int voff = lane * 16;
@@ -646,7 +652,9 @@ __global__ __launch_bounds__(256, 1) void trunk_bf16_kernel(const TrunkParams p)
 
 int trunk_bf16_launch(int kind, const TrunkParams &p, hipStream_t s) {
     if (p.n_mid != (kind == 3 ? 6 : 7)) return DGDM_EINVAL;
-    const int waves = (p.ntiles + 1) / 2, grid = (waves + 3) / 4;
+    const int per_chain = p.B * p.tiles_per_b;
+    if (per_chain <= 0 || p.ntiles % per_chain) return DGDM_EINVAL;
+    const int waves = (p.ntiles / per_chain) * ((per_chain + 1) / 2), grid = (waves + 3) / 4;      // a chain's tiles pair up among themselves
     if (grid == 0) return DGDM_OK;
     prof_begin(s, DGDM_STAGE_TRUNK);
     if (kind == 2) hipLaunchKernelGGL((trunk_bf16_kernel<2>), dim3(grid), dim3(256), 0, s, p);

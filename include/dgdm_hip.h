@@ -184,7 +184,12 @@ int dgdm_ddim_pred_x0(const float *x_dev, const float *eps_dev, float *out_dev, 
  * kind 2: ProfileForward2DModel(W=256, params_ch, object_ch) (dynamics/profile_forward_2d.py:78-135)
  * kind 3: ProfileForward3DModel(W=256, params_ch)            (dynamics/profile_forward_3d.py:13-65)
  * BatchNorm layers are folded with their running statistics (the reference runs the classifier
- * in eval mode with frozen parameters: generator/train.py:91-92).                 */
+ * in eval mode with frozen parameters: generator/train.py:91-92).
+ *
+ * Accepted domain (tests/test_gpu_grad_shapes.py runs its edges through the guidance gradient): kind 2 or 3 (else DGDM_EMODE);
+ * params_ch 1..256 (else DGDM_EINVAL); object_ch: kind 2 any size, it has to be the
+ * input width of the state dict's object_encoder.0 (a tensor of another size is DGDM_EKEY, like a missing one); kind 3 ignores it.
+ * The hidden width is the reference's W = 256.                                                                                       */
 int dgdm_dynamics_create(DgdmDynamics **out, int kind, const DgdmTensor *state_dict, int n_tensors,
                          int params_ch, int object_ch);
 void dgdm_dynamics_destroy(DgdmDynamics *m);
@@ -255,6 +260,17 @@ typedef struct DgdmGuidanceConfig {
     int32_t max_objects;
 } DgdmGuidanceConfig;
 
+/* Accepted domain (everything else is DGDM_EINVAL from the host code, and no handle; tests/test_gpu_grad_shapes.py holds the gradient and
+ * the logits to the oracle in float64 at its edges - one row, one cell, a cell count that is no multiple of a 32-row tile, params_ch 1 and
+ * 256, 256 chains, the first and the last timestep):
+ *   batch, grid_size, num_pos      any positive value (a one-cell grid takes ori_lo and position -1, as torch.linspace with one step does)
+ *   ori_lo, ori_hi                 any pair, equal or descending included: linspace(ori_lo, ori_hi, grid_size)
+ *   max_chains                     1..256 (DGDM_MAX_CHAINS); a call takes n_chains in 1..max_chains
+ *   num_train_timesteps            any positive value; a call's timestep enters as float32(timestep) / float32(num_train_timesteps)
+ *   sub_batch_size                 3-D: any positive value, larger than the row count included; 2-D: not read
+ *   num_object_points              2-D: object_ch / 2 of the model; 3-D: 1..1024 - N = 512 is the only cloud size the test suite holds to
+ *                                  the oracle
+ *   max_objects                    values below 1 count as 1; an objective's object index is held to the objects set, at every call   */
 int  dgdm_guidance_create(DgdmGuidance **out, DgdmDynamics *model, const DgdmGuidanceConfig *cfg);
 void dgdm_guidance_destroy(DgdmGuidance *g);
 /* Arithmetic of the trunk contractions inside dgdm_dyn{2,3}d_guidance_grad.  DGDM_DTYPE_F32 (default, the parity path) =

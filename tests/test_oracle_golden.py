@@ -317,3 +317,37 @@ def test_trainer3d_matches_reference(tag):
         t3.check_sub_loosely(g, rec)        # (two optimizer steps per call with BatchNorm over 4 rows in between: see there)
     else:
         t3.check(g, tag, rec, 2e-5, 5e-5, 4e-6, verbose=True, tol_run=2e-3, tol_later=1e-2, tol_inf=2e-2)
+
+
+def test_grad_shapes_2d_margins():
+    """tests/test_gpu_grad_shapes.py holds the gradient to float64 without any allowance for ReLU ties: every 2-D chain's hard-coded inputs
+    keep every ReLU input of the float64 oracle at least 5e-7 (relative) away from zero."""
+    from tests import grad_shapes_cases as gc
+    for case in gc.CASES_2D:
+        sd64, objs, xs = gc.f64(gc.state_dict(case)), gc.objects(case), gc.x_all(case)
+        for c in range(case["distinct"]):
+            _, m = gc.oracle_logits(case, sd64, xs[c], objs[case["chain_obj"][c]], torch.float64, want_margin=True)
+            assert float(m.min()) >= gc.MARGIN, (case["name"], c, m)
+
+
+def test_grad_shapes_3d_fixture():
+    """tests/golden/g16_grad_shapes.npz (make_golden_grad_shapes.py) is what the oracle gives for the inputs tests/grad_shapes_cases.py
+    states: margins and inputs of every case; the two smallest cases regenerated - float64 gradients and logits to 1e-12 relative, the
+    margin (a relative figure itself) to 1e-12, the float32 yardsticks to 1e-4 (they move with the summation order)."""
+    from tests import grad_shapes_cases as gc
+    g = util.load(gc.GOLDEN_3D)
+    for case in gc.CASES_3D:
+        n = case["name"]
+        assert float(g[f"{n}/margin"].min()) >= gc.MARGIN, (n, g[f"{n}/margin"])
+        assert np.array_equal(g[f"{n}/x"], gc.x_all(case).numpy())
+        assert np.array_equal(g[f"{n}/starts"], np.stack([gc.starts(case, c) for c in range(case["distinct"])]))
+        assert ((f"{n}/g16" in g.files) == case["bf16"]) and g[f"{n}/g64"].shape == (case["distinct"], case["B"], case["L"])
+        assert g[f"{n}/l64"].shape == (case["distinct"], case["R"], 3)
+    for n in gc.SMALLEST_3D:
+        case = gc.by_name(gc.CASES_3D, n)
+        ref = gc.reference(case)
+        for k in ("g64", "l64"):
+            assert util.rel_l2(ref[k], g[f"{n}/{k}"]) < 1e-12, (n, k)
+        assert np.abs(ref["margin"].numpy() - g[f"{n}/margin"]).max() < 1e-12, n
+        for k in ("g32", "l32") + (("g16",) if case["bf16"] else ()):
+            assert util.rel_l2(ref[k], g[f"{n}/{k}"]) < 1e-4, (n, k)
