@@ -210,6 +210,10 @@ PROTOTYPES = {
     "dgdm_squeeze_friction_workspace_bytes": (C.c_int64, [C.POINTER(SqueezeConfig), C.c_int]),
     "dgdm_squeeze_map_friction": (C.c_int, [C.POINTER(SqueezeConfig), _P, C.c_int, C.c_int, _P, C.c_int, C.c_int, _P, C.c_int, _P, _P, C.c_int, _P,
                                             _P, _P, _P, _P, _P, _P, _P, C.c_int64, _P, C.c_double, _P, _P]),
+    "dgdm_squeeze_label_workspace_bytes": (C.c_int64, [C.POINTER(SqueezeConfig), C.c_int, C.c_int, C.c_int]),
+    "dgdm_squeeze_label": (C.c_int, [C.POINTER(SqueezeConfig), _P, C.c_int, C.c_int, _P, C.c_int, C.c_int, _P, C.c_int, _P, _P, C.c_int, C.c_int,
+                                     C.c_double, C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_double, C.c_int, _P, C.c_int64, C.c_int, C.c_int,
+                                     _P, _P, C.c_int64, _P]),
     "dgdm_squeeze_objective_values": (C.c_int, [C.POINTER(SqueezeConfig), _P, _P, _P, C.c_int, C.c_int, C.c_int, C.POINTER(Objective), _P,
                                                 C.POINTER(C.c_double), _P, _P]),
     "dgdm_squeeze_slice": (C.c_int, [_P, _P, _P, _P, C.c_int, _P, C.c_int, _P, C.c_int64, _P, C.POINTER(C.c_int64), _P]),

@@ -22,9 +22,13 @@
 // run_chunks alone decides how many pairs a workspace holds and where a chunk's tables lie; the 3-D entry's extra block (gx, level
 // offsets) is the workspace's first bytes, so its place does not depend on the chunk size.  workspace_bytes_of is the one sum behind the
 // three *_workspace_bytes entries.
+// dgdm_squeeze_label (include/dgdm_hip.h "squeeze-simulator labels") is a fourth map entry behind the same front end: it hands run_chunks a
+// consumer, which reduces each chunk's tables to condition rows where lookup_kernel would write per-start outputs, and fixes the chunk at
+// whole fingers, since a row is made of all of a finger's pairs.
 // This file is compiled with -ffp-contract=off (build.py): no operation of the contract is fused.
 #include "common.h"
 #include <cmath>
+#include <type_traits>
 
 namespace dgdm {
 namespace {
@@ -226,6 +230,18 @@ __device__ double pose_y(double y0, double tl, double tr, double S, double tm) {
     return y;
 }
 
+// The cell a start (theta0, x0) snaps to: the nearest, halves up, theta modulo 2 pi, x clamped; a non-finite start lands on cell 0.
+__device__ __forceinline__ int snap_cell(const Grid &g, double th, double x0) {
+    const double dth = TWO_PI / (double)g.T;
+    const double q = floor(th / dth + 0.5);
+    const double v = q - (double)g.T * floor(q / (double)g.T);
+    const int a = (v >= 0.0 && v < (double)g.T) ? (int)v : 0;
+    double w = floor((x0 + g.x_half) / g.dx + 0.5);
+    if (!(w >= 0.0)) w = 0.0;
+    if (!(w <= (double)(g.X - 1))) w = (double)(g.X - 1);
+    return a * g.X + (int)w;
+}
+
 // Per (pair, start): cells (start, closed, settled), y (closed, settled), flags.  `pair0`: the chunk's first pair in the outputs.
 // jam [pairs][cells] or null (frictionless): flags 8 (the start cell is jammed) and 16 (the settled cell is).
 __global__ void lookup_kernel(Grid g, const double *starts, int n_starts, const double *touch_l, const double *touch_r, const double *S,
@@ -236,14 +252,7 @@ __global__ void lookup_kernel(Grid g, const double *starts, int n_starts, const 
     const int cells = g.T * g.X;
     const int64_t o = (int64_t)blockIdx.y * cells;
     const double th = starts[3 * n], x0 = starts[3 * n + 1], y0 = starts[3 * n + 2];
-    const double dth = TWO_PI / (double)g.T;
-    const double q = floor(th / dth + 0.5);
-    const double v = q - (double)g.T * floor(q / (double)g.T);
-    const int a = (v >= 0.0 && v < (double)g.T) ? (int)v : 0;
-    double w = floor((x0 + g.x_half) / g.dx + 0.5);
-    if (!(w >= 0.0)) w = 0.0;
-    if (!(w <= (double)(g.X - 1))) w = (double)(g.X - 1);
-    const int c0 = a * g.X + (int)w;
+    const int c0 = snap_cell(g, th, x0);
     const int ck = kth[o + c0], cf = fix[o + c0];
     const int bf = cf % g.X;
     const int64_t r = (int64_t)(pair0 + blockIdx.y) * n_starts + n;
@@ -294,6 +303,147 @@ __global__ __launch_bounds__(64) void squeeze_values_kernel(ValueGrid g, const i
 #pragma unroll
     for (int s = 32; s > 0; s >>= 1) v += __shfl_xor(v, s);
     if (lane == 0) values[p] = v;
+}
+
+// ---------------------------------------------------------------------------------------------------------------- labels: condition rows
+// dgdm_squeeze_label (include/dgdm_hip.h "squeeze-simulator labels"; tests/squeeze_label_oracle.py is the CPU oracle): the chunk loop's
+// consumer in lookup_kernel's place.  Per chunk, straight from the chunk's tables, no per-start row is stored:
+//   label_pair_kernel   one wave per pair: every lane its own starts in ascending order (snap, the two maps, y - lookup_kernel's steps),
+//                       class counts, flag counts and the sums in registers, an xor butterfly across the wave, lane 0 stores the pair's
+//                       partials - squeeze_values_kernel's shape, the same bits run to run;
+//   label_rows_kernel   one thread per finger: its pairs' partials, objects ascending, to the row's blocks.
+struct LabelGrid {
+    int n_tally, n_settle, M, layout, column_offset, object_stride;
+    int64_t row_stride;
+    double dth, thr[3], std[3], pos_norm;
+};
+
+struct PairPart {
+    double sum[4];          // d0, |d0|, d1, d2 over the tally starts
+    double settle[3];       // cos, sin, r over the settle starts
+    int32_t cls[6];         // e0 class 0 / 2, e1 class 0 / 2, e2 class 0 / 2
+    int32_t flag[3];        // tally starts with flag 1, 2, 4
+    int32_t left, bad, pad; // settle starts out of range; any non-finite y_settled
+};
+
+__device__ __forceinline__ double wave_sum(double v) {
+#pragma unroll
+    for (int s = 32; s > 0; s >>= 1) v += __shfl_xor(v, s);
+    return v;
+}
+
+__device__ __forceinline__ int wave_sum(int v) {
+#pragma unroll
+    for (int s = 32; s > 0; s >>= 1) v += __shfl_xor(v, s);
+    return v;
+}
+
+// Grid: one workgroup of one wave per pair of the chunk.  closed / fix [pairs][cells]: the one-closing and the settled map.
+__global__ __launch_bounds__(64) void label_pair_kernel(Grid g, LabelGrid lg, const double *__restrict__ starts, const double *__restrict__ rot,
+                                                        const double *__restrict__ touch_l, const double *__restrict__ touch_r,
+                                                        const double *__restrict__ S, const int32_t *__restrict__ closed,
+                                                        const int32_t *__restrict__ fix, PairPart *__restrict__ part) {
+    const int lane = threadIdx.x;
+    const int64_t o = (int64_t)blockIdx.x * g.T * g.X;
+    double sum[4] = {0.0, 0.0, 0.0, 0.0};
+    int cls[6] = {0, 0, 0, 0, 0, 0}, flag[3] = {0, 0, 0};
+    for (int n = lane; n < lg.n_tally; n += 64) {
+        const double th = starts[3 * (int64_t)n], x0 = starts[3 * (int64_t)n + 1], y0 = starts[3 * (int64_t)n + 2];
+        const int c0 = snap_cell(g, th, x0);
+        const int ck = closed[o + c0], cf = fix[o + c0];
+        const int a0 = c0 / g.X, b0 = c0 % g.X, a1 = ck / g.X, b1 = ck % g.X, bf = cf % g.X;
+        int64_t da = (int64_t)a1 - a0;
+        if (2 * da > g.T) da -= g.T;                                      // squeeze.fold's strict rule: +-T / 2 stays
+        if (2 * da < -(int64_t)g.T) da += g.T;
+        double e[3];
+        e[0] = (double)da * lg.dth;
+        e[1] = (double)(b1 - b0) * g.dx;
+        e[2] = pose_y(y0, touch_l[o + ck], touch_r[o + ck], S[o + ck], g.travel_max) - y0;
+#pragma unroll
+        for (int j = 0; j < 3; ++j) {                                      // class 2 first: squeeze_metric's where(d > thr, 2, where(d < -thr, 0, 1))
+            const bool hi = e[j] > lg.thr[j];
+            cls[2 * j] += (!hi && e[j] < -lg.thr[j]) ? 1 : 0;
+            cls[2 * j + 1] += hi ? 1 : 0;
+        }
+        const double d0 = e[0] / lg.std[0];
+        sum[0] += d0;
+        sum[1] += fabs(d0);
+        sum[2] += e[1] / lg.std[1];
+        sum[3] += e[2] / lg.std[2];
+        flag[0] += S[o + c0] >= g.travel_max ? 1 : 0;
+        flag[1] += S[o + cf] >= g.travel_max ? 1 : 0;
+        flag[2] += (bf == 0 || bf == g.X - 1) ? 1 : 0;
+    }
+    double settle[3] = {0.0, 0.0, 0.0};
+    int left = 0, bad = 0;
+    for (int q = lane; q < lg.n_settle; q += 64) {
+        const int64_t n = (int64_t)lg.n_tally + q;
+        const double th = starts[3 * n], x0 = starts[3 * n + 1], y0 = starts[3 * n + 2];
+        const int cf = fix[o + snap_cell(g, th, x0)];
+        const int as = cf / g.X, bs = cf % g.X;
+        const double ys = pose_y(y0, touch_l[o + cf], touch_r[o + cf], S[o + cf], g.travel_max);
+        const double xs = -g.x_half + (double)bs * g.dx;
+        const double px = xs / lg.pos_norm, py = ys / lg.pos_norm;
+        settle[0] += rot[2 * as];
+        settle[1] += rot[2 * as + 1];
+        settle[2] += sqrt(px * px + py * py);
+        left += (bs == 0 || bs == g.X - 1 || fabs(px) > 1.0 || fabs(py) > 1.0) ? 1 : 0;
+        bad |= isfinite(ys) ? 0 : 1;
+    }
+    PairPart r;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) r.sum[j] = wave_sum(sum[j]);
+#pragma unroll
+    for (int j = 0; j < 3; ++j) r.settle[j] = wave_sum(settle[j]);
+#pragma unroll
+    for (int j = 0; j < 6; ++j) r.cls[j] = wave_sum(cls[j]);
+#pragma unroll
+    for (int j = 0; j < 3; ++j) r.flag[j] = wave_sum(flag[j]);
+    r.left = wave_sum(left);
+    r.bad = wave_sum(bad);
+    r.pad = 0;
+    if (lane == 0) part[blockIdx.x] = r;
+}
+
+// One thread per finger of the chunk (`finger0`: the chunk's first finger): its M pairs' partials to the row's blocks, and the flag counts.
+__global__ void label_rows_kernel(LabelGrid lg, const PairPart *__restrict__ part, int n_fingers, int64_t finger0, float *__restrict__ rows,
+                                  int32_t *__restrict__ counts) {
+    const int f = blockIdx.x * blockDim.x + threadIdx.x;
+    if (f >= n_fingers) return;
+    const PairPart *pp = part + (int64_t)f * lg.M;
+    float *row = rows + (finger0 + f) * lg.row_stride + lg.column_offset;
+    const int blocks = lg.layout == DGDM_LABEL_PER_OBJECT ? lg.M : 1, per = lg.layout == DGDM_LABEL_PER_OBJECT ? 1 : lg.M;
+    const double G = (double)lg.n_settle, Mp = (double)per, nn = (double)((int64_t)per * lg.n_tally);
+    for (int blk = 0; blk < blocks; ++blk) {
+        float *dst = row + (int64_t)blk * lg.object_stride;                // MEAN: one block, blk = 0
+        int64_t K[6] = {0, 0, 0, 0, 0, 0};
+        double s[4] = {0.0, 0.0, 0.0, 0.0}, v[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
+        for (int k = blk * per; k < (blk + 1) * per; ++k) {
+            const PairPart &p = pp[k];
+            for (int j = 0; j < 6; ++j) K[j] += p.cls[j];
+            for (int j = 0; j < 4; ++j) s[j] += p.sum[j];
+            if (lg.n_settle > 0) {
+                double c = p.settle[0] / G, sn = p.settle[1] / G;
+                double rho = sqrt(c * c + sn * sn), off = p.settle[2] / G;
+                if (p.bad) rho = c = sn = off = NAN;
+                v[0] += rho;
+                v[1] += c;
+                v[2] += sn;
+                v[3] += off;
+                v[4] += (double)p.left / G;
+            }
+        }
+        for (int j = 0; j < 6; ++j) dst[j] = (float)((double)K[j] / nn);
+        for (int j = 0; j < 4; ++j) dst[6 + j] = (float)(s[j] / nn);
+        if (lg.n_settle > 0)
+            for (int j = 0; j < 5; ++j) dst[DGDM_LABEL_TALLY_COLS + j] = (float)(v[j] / Mp);
+    }
+    if (counts) {
+        int32_t c[3] = {0, 0, 0};
+        for (int k = 0; k < lg.M; ++k)
+            for (int j = 0; j < 3; ++j) c[j] += pp[k].flag[j];
+        for (int j = 0; j < 3; ++j) counts[3 * (finger0 + f) + j] = c[j];
+    }
 }
 
 inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
@@ -391,12 +541,18 @@ int check_map_args(const char *fn, const DgdmSqueezeConfig *cfg, bool own, bool 
 // The chunk loop of all entries: as many pairs per chunk as the workspace's `bytes` hold (the caller has checked that one fits);
 // `table(n, p0, pairs, tl, tr, S, jam, stream)` launches the entry's table kernel for the chunk's n pairs from pair p0 on, whose (finger,
 // object) are at `pairs`.  `friction`: the chunk holds a jam table, which the table kernel fills and the successors and the flags read.
-template <class Table>
+// `consume(n, p0, tl, tr, S, closed, fix, stream)`, optional: an entry's own reduction of the chunk, launched where lookup_kernel stands
+// (which still runs when there are starts); an entry that passes one also passes `fixed`, the pairs per chunk it has sized its own
+// buffers and the workspace for.  The map entries pass neither: their launches are what they were.
+struct NoConsumer {};
+template <class Table, class Consume = NoConsumer>
 int run_chunks(const DgdmSqueezeConfig *cfg, const Grid &g, const int32_t *pairs_host, int n_pairs, const double *starts_dev, int n_starts,
-               const Outputs &out, void *workspace_dev, int64_t bytes, hipStream_t s, bool friction, Table table) {
+               const Outputs &out, void *workspace_dev, int64_t bytes, hipStream_t s, bool friction, Table table, Consume consume = Consume(),
+               int64_t fixed = 0) {
     const int64_t cells = (int64_t)g.T * g.X;
     int64_t chunk = std::min<int64_t>(std::min<int64_t>(n_pairs, MAX_CHUNK), bytes / (int64_t)layout(cells, 1, friction).bytes + 1);
     while (chunk > 1 && (int64_t)layout(cells, chunk, friction).bytes > bytes) --chunk;
+    if (fixed > 0) chunk = std::min<int64_t>(n_pairs, fixed);
     int rounds = 0;
     while (((int64_t)1 << rounds) < cells) ++rounds;                     // ceil(log2(cells)): no path is longer than cells - 1 steps
     const bool k_settles = rounds < 31 && (int64_t)cfg->closing_steps >= ((int64_t)1 << rounds);
@@ -433,6 +589,10 @@ int run_chunks(const DgdmSqueezeConfig *cfg, const Grid &g, const int32_t *pairs
         if (n_starts > 0) {
             hipLaunchKernelGGL(lookup_kernel, dim3((unsigned)((n_starts + 255) / 256), n), dim3(256), 0, s, g, starts_dev, n_starts, tl, tr, S,
                                (const int32_t *)jam, closed, fix, (int)p0, out.cells, out.y, out.flags);
+            DGDM_HIP_CHECK(hipGetLastError());
+        }
+        if constexpr (!std::is_same<Consume, NoConsumer>::value) {
+            consume(n, p0, tl, tr, S, closed, fix, s);
             DGDM_HIP_CHECK(hipGetLastError());
         }
         const size_t off = (size_t)p0 * cells, cnt = (size_t)n * cells;
@@ -658,6 +818,35 @@ extern "C" int64_t dgdm_squeeze_workspace_bytes(const DgdmSqueezeConfig *cfg, in
     return workspace_bytes_of("dgdm_squeeze_workspace_bytes", cfg, chunk_pairs, false, 0);
 }
 
+// table_kernel<friction> for the n pairs of a chunk (g.m, g.nv, g.hl and g.h set).  Without friction mu, jam and contact are unused.
+static void launch_table(bool friction, const Grid &g, const double *surfaces_dev, const double *objects_dev, const int32_t *pairs,
+                         const double *rot_dev, double *tl, double *tr, double *S, double mu, int32_t *jam, int32_t *contact, unsigned n,
+                         hipStream_t s) {
+    const size_t lds = sizeof(double) * (size_t)(2 * g.m + 2 * g.nv);
+    if (friction)
+        hipLaunchKernelGGL(table_kernel<true>, dim3((unsigned)g.T, n), dim3(TABLE_THREADS), lds, s, g, surfaces_dev, objects_dev, pairs, rot_dev, tl, tr,
+                           S, mu, jam, contact);
+    else
+        hipLaunchKernelGGL(table_kernel<false>, dim3((unsigned)g.T, n), dim3(TABLE_THREADS), lds, s, g, surfaces_dev, objects_dev, pairs, rot_dev, tl, tr,
+                           S, 0.0, (int32_t *)nullptr, (int32_t *)nullptr);
+}
+
+// What the 2-D entries refuse of their own sizes, and the grid made of them once the config has been checked.
+static int check_sizes_2d(const char *fn, int num_points, int num_vertices) {
+    DGDM_REQUIRE(num_points >= 2 && num_points <= MAX_SURFACE, DGDM_EINVAL, "%s: %d surface samples (need 2 .. %d)", fn, num_points, MAX_SURFACE);
+    DGDM_REQUIRE(num_vertices >= 3 && num_vertices <= MAX_VERTS, DGDM_EINVAL, "%s: %d vertices (need 3 .. %d)", fn, num_vertices, MAX_VERTS);
+    return DGDM_OK;
+}
+
+static Grid grid_2d(const DgdmSqueezeConfig *cfg, int num_points, int num_vertices) {
+    Grid g = grid_of(cfg);
+    g.m = num_points;
+    g.nv = num_vertices;
+    g.hl = cfg->finger_half_len;
+    g.h = 2.0 * cfg->finger_half_len / (double)(num_points - 1);
+    return g;
+}
+
 // The body of dgdm_squeeze_map (friction = false: mu, jam_dev and contact_dev unused) and dgdm_squeeze_map_friction.
 static int squeeze_map_common(const char *fn, bool friction, double mu, const DgdmSqueezeConfig *cfg, const double *surfaces_dev, int n_fingers,
                               int num_points, const double *objects_dev, int n_objects, int num_vertices, const int32_t *pairs_host, int n_pairs,
@@ -665,28 +854,19 @@ static int squeeze_map_common(const char *fn, bool friction, double mu, const Dg
                               double *table_s_dev, double *touch_l_dev, double *touch_r_dev, int32_t *succ_dev, int32_t *jam_dev,
                               int32_t *contact_dev, void *workspace_dev, int64_t workspace_bytes, void *stream) {
     DGDM_REQUIRE(!friction || (std::isfinite(mu) && mu >= 0.0), DGDM_EINVAL, "%s: friction coefficient %g (need finite, >= 0)", fn, mu);
-    DGDM_REQUIRE(num_points >= 2 && num_points <= MAX_SURFACE, DGDM_EINVAL, "%s: %d surface samples (need 2 .. %d)", fn, num_points, MAX_SURFACE);
-    DGDM_REQUIRE(num_vertices >= 3 && num_vertices <= MAX_VERTS, DGDM_EINVAL, "%s: %d vertices (need 3 .. %d)", fn, num_vertices, MAX_VERTS);
-    Outputs out = {cells_dev, y_dev, flags_dev, table_s_dev, touch_l_dev, touch_r_dev, succ_dev, jam_dev};
-    int rc = check_map_args(fn, cfg, surfaces_dev && objects_dev && rot_dev, true, n_fingers, n_objects, pairs_host, n_pairs, starts_dev, n_starts, out,
-                            workspace_dev, workspace_bytes, friction, 0,
-                            friction ? "dgdm_squeeze_friction_workspace_bytes" : "dgdm_squeeze_workspace_bytes");
+    int rc = check_sizes_2d(fn, num_points, num_vertices);
     if (rc) return rc;
+    Outputs out = {cells_dev, y_dev, flags_dev, table_s_dev, touch_l_dev, touch_r_dev, succ_dev, jam_dev};
+    if ((rc = check_map_args(fn, cfg, surfaces_dev && objects_dev && rot_dev, true, n_fingers, n_objects, pairs_host, n_pairs, starts_dev, n_starts, out,
+                             workspace_dev, workspace_bytes, friction, 0,
+                             friction ? "dgdm_squeeze_friction_workspace_bytes" : "dgdm_squeeze_workspace_bytes")))
+        return rc;
     const int64_t cells = (int64_t)cfg->theta_cells * cfg->x_cells;
-    Grid g = grid_of(cfg);
-    g.m = num_points;
-    g.nv = num_vertices;
-    g.hl = cfg->finger_half_len;
-    g.h = 2.0 * cfg->finger_half_len / (double)(num_points - 1);
-    const size_t lds = sizeof(double) * (size_t)(2 * g.m + 2 * g.nv);
+    const Grid g = grid_2d(cfg, num_points, num_vertices);
     return run_chunks(cfg, g, pairs_host, n_pairs, starts_dev, n_starts, out, workspace_dev, workspace_bytes, (hipStream_t)stream, friction,
                       [&](unsigned n, int64_t p0, const int32_t *pairs, double *tl, double *tr, double *S, int32_t *jam, hipStream_t s) {
-                          if (friction)
-                              hipLaunchKernelGGL(table_kernel<true>, dim3((unsigned)g.T, n), dim3(TABLE_THREADS), lds, s, g, surfaces_dev, objects_dev,
-                                                 pairs, rot_dev, tl, tr, S, mu, jam, contact_dev ? contact_dev + 2 * p0 * cells : nullptr);
-                          else
-                              hipLaunchKernelGGL(table_kernel<false>, dim3((unsigned)g.T, n), dim3(TABLE_THREADS), lds, s, g, surfaces_dev, objects_dev,
-                                                 pairs, rot_dev, tl, tr, S, 0.0, (int32_t *)nullptr, (int32_t *)nullptr);
+                          launch_table(friction, g, surfaces_dev, objects_dev, pairs, rot_dev, tl, tr, S, mu, jam,
+                                       contact_dev ? contact_dev + 2 * p0 * cells : nullptr, n, s);
                       });
 }
 
@@ -713,6 +893,108 @@ extern "C" int dgdm_squeeze_map_friction(const DgdmSqueezeConfig *cfg, const dou
     return squeeze_map_common("dgdm_squeeze_map_friction", true, mu, cfg, surfaces_dev, n_fingers, num_points, objects_dev, n_objects,
                               num_vertices, pairs_host, n_pairs, rot_dev, starts_dev, n_starts, cells_dev, y_dev, flags_dev, table_s_dev,
                               touch_l_dev, touch_r_dev, succ_dev, jam_dev, contact_dev, workspace_dev, workspace_bytes, stream);
+}
+
+// The label entry's partial sums lie in front of the chunk's tables, one PairPart per pair of the chunk.
+static size_t label_extra(int64_t chunk_pairs) { return align256(sizeof(PairPart) * (size_t)chunk_pairs); }
+
+static int check_label_objects(const char *fn, int n_objects) {
+    DGDM_REQUIRE(n_objects >= 1 && n_objects <= MAX_CHUNK, DGDM_EINVAL, "%s: %d objects per finger (need 1 .. %d)", fn, n_objects, MAX_CHUNK);
+    return DGDM_OK;
+}
+
+extern "C" int64_t dgdm_squeeze_label_workspace_bytes(const DgdmSqueezeConfig *cfg, int chunk_fingers, int n_objects, int friction) {
+    const char *fn = "dgdm_squeeze_label_workspace_bytes";
+    if (check_label_objects(fn, n_objects)) return DGDM_EINVAL;
+    DGDM_REQUIRE(chunk_fingers >= 1 && (int64_t)chunk_fingers * n_objects <= MAX_CHUNK, DGDM_EINVAL,
+                 "%s: %d fingers of %d objects per chunk (need >= 1 finger, at most %d pairs)", fn, chunk_fingers, n_objects, MAX_CHUNK);
+    const int chunk_pairs = chunk_fingers * n_objects;
+    return workspace_bytes_of(fn, cfg, chunk_pairs, friction != 0, label_extra(chunk_pairs));
+}
+
+extern "C" int dgdm_squeeze_label(const DgdmSqueezeConfig *cfg, const double *surfaces_dev, int n_fingers, int num_points, const double *bank_dev,
+                                  int n_bank, int num_vertices, const int32_t *objects_host, int n_objects, const double *rot_dev,
+                                  const double *starts_dev, int n_tally, int n_settle, double mu, const double threshold[3],
+                                  const double score_std[3], double pos_norm, int row_layout, float *rows_dev, int64_t row_stride, int column_offset,
+                                  int object_stride, int32_t *counts_dev, void *workspace_dev, int64_t workspace_bytes, void *stream) {
+    const char *fn = "dgdm_squeeze_label";
+    const char *bytes_fn = "dgdm_squeeze_label_workspace_bytes";
+    DGDM_REQUIRE(std::isfinite(mu) && mu >= 0.0, DGDM_EINVAL, "%s: friction coefficient %g (need finite, >= 0)", fn, mu);
+    int rc = check_sizes_2d(fn, num_points, num_vertices);
+    if (rc || (rc = check_label_objects(fn, n_objects))) return rc;
+    DGDM_REQUIRE(objects_host && threshold && score_std && rows_dev && starts_dev, DGDM_EINVAL, "%s: null argument", fn);
+    DGDM_REQUIRE(n_fingers >= 1 && n_bank >= 1, DGDM_EINVAL, "%s: %d fingers, a bank of %d objects (need >= 1 each)", fn, n_fingers, n_bank);
+    DGDM_REQUIRE((int64_t)n_fingers * n_objects <= INT32_MAX, DGDM_EINVAL, "%s: %d fingers x %d objects exceed 2^31 - 1 pairs", fn, n_fingers, n_objects);
+    for (int k = 0; k < n_objects; ++k)
+        DGDM_REQUIRE(objects_host[k] >= 0 && objects_host[k] < n_bank, DGDM_EINVAL, "%s: object %d = %d outside the bank of %d", fn, k, objects_host[k],
+                     n_bank);
+    DGDM_REQUIRE(n_tally >= 1 && n_settle >= 0 && (int64_t)n_tally + n_settle <= INT32_MAX, DGDM_EINVAL,
+                 "%s: %d tally and %d settle starts (need n_tally >= 1, n_settle >= 0)", fn, n_tally, n_settle);
+    DGDM_REQUIRE((int64_t)n_objects * n_tally <= INT32_MAX, DGDM_EINVAL, "%s: %d objects x %d tally starts exceed 2^31 - 1", fn, n_objects, n_tally);
+    for (int j = 0; j < 3; ++j) {
+        DGDM_REQUIRE(std::isfinite(score_std[j]) && score_std[j] > 0.0, DGDM_EINVAL, "%s: score_std[%d] = %g (need finite, > 0)", fn, j, score_std[j]);
+        DGDM_REQUIRE(std::isfinite(threshold[j]) && threshold[j] >= 0.0, DGDM_EINVAL, "%s: threshold[%d] = %g (need finite, >= 0)", fn, j, threshold[j]);
+    }
+    DGDM_REQUIRE(std::isfinite(pos_norm) && pos_norm > 0.0, DGDM_EINVAL, "%s: pos_norm %g (need finite, > 0)", fn, pos_norm);
+    DGDM_REQUIRE(row_layout == DGDM_LABEL_MEAN || row_layout == DGDM_LABEL_PER_OBJECT, DGDM_EINVAL, "%s: unknown layout %d", fn, row_layout);
+    const int cols = DGDM_LABEL_TALLY_COLS + (n_settle > 0 ? DGDM_LABEL_SETTLED_COLS : 0);
+    const bool per_object = row_layout == DGDM_LABEL_PER_OBJECT;
+    DGDM_REQUIRE(column_offset >= 0, DGDM_EINVAL, "%s: column_offset %d is negative", fn, column_offset);
+    DGDM_REQUIRE(!per_object || object_stride >= cols, DGDM_EINVAL, "%s: object_stride %d holds no block of %d columns", fn, object_stride, cols);
+    const int64_t width = (int64_t)column_offset + (per_object ? (int64_t)(n_objects - 1) * object_stride : 0) + cols;
+    DGDM_REQUIRE(row_stride >= width, DGDM_EINVAL, "%s: row_stride %lld holds no row of %lld floats", fn, (long long)row_stride, (long long)width);
+
+    const bool friction = mu > 0.0;
+    const int n_pairs = n_fingers * n_objects;
+    std::vector<int32_t> pairs((size_t)2 * n_pairs);                      // finger-major: pair f * M + k = (f, objects_host[k])
+    for (int f = 0; f < n_fingers; ++f)
+        for (int k = 0; k < n_objects; ++k) {
+            pairs[2 * ((size_t)f * n_objects + k)] = f;
+            pairs[2 * ((size_t)f * n_objects + k) + 1] = objects_host[k];
+        }
+    const Outputs out = {};
+    if ((rc = check_map_args(fn, cfg, surfaces_dev && bank_dev && rot_dev, true, n_fingers, n_bank, pairs.data(), n_pairs, nullptr, 0, out, workspace_dev,
+                             workspace_bytes, friction, label_extra(1), bytes_fn)))
+        return rc;
+    // whole fingers only: the most fingers whose partials and tables the workspace holds
+    const int64_t cells = (int64_t)cfg->theta_cells * cfg->x_cells;
+    auto need = [&](int64_t fingers) { return (int64_t)(label_extra(fingers * n_objects) + layout(cells, fingers * n_objects, friction).bytes); };
+    DGDM_REQUIRE(workspace_bytes >= need(1), DGDM_EINVAL, "%s: workspace of %lld bytes holds no finger of %d objects, one needs %lld (%s)", fn,
+                 (long long)workspace_bytes, n_objects, (long long)need(1), bytes_fn);
+    int64_t fingers = 1, over = std::min<int64_t>(n_fingers, MAX_CHUNK / n_objects) + 1;      // need() does not fall: bisect [fingers, over)
+    while (over - fingers > 1) {
+        const int64_t mid = fingers + (over - fingers) / 2;
+        if (need(mid) <= workspace_bytes) fingers = mid; else over = mid;
+    }
+    const int64_t cap = fingers * n_objects;
+    const size_t extra = label_extra(cap);
+
+    const Grid g = grid_2d(cfg, num_points, num_vertices);
+    LabelGrid lg = {};
+    lg.n_tally = n_tally;
+    lg.n_settle = n_settle;
+    lg.M = n_objects;
+    lg.layout = row_layout;
+    lg.column_offset = column_offset;
+    lg.object_stride = per_object ? object_stride : 0;
+    lg.row_stride = row_stride;
+    lg.dth = TWO_PI / (double)g.T;
+    for (int j = 0; j < 3; ++j) { lg.thr[j] = threshold[j]; lg.std[j] = score_std[j]; }
+    lg.pos_norm = pos_norm;
+    uint8_t *ws = static_cast<uint8_t *>(workspace_dev);                  // the partials in front, the chunk's tables behind them
+    PairPart *part = reinterpret_cast<PairPart *>(ws);
+    return run_chunks(
+        cfg, g, pairs.data(), n_pairs, nullptr, 0, out, ws + extra, workspace_bytes - (int64_t)extra, (hipStream_t)stream, friction,
+        [&](unsigned n, int64_t, const int32_t *prs, double *tl, double *tr, double *S, int32_t *jam, hipStream_t s) {
+            launch_table(friction, g, surfaces_dev, bank_dev, prs, rot_dev, tl, tr, S, mu, jam, nullptr, n, s);
+        },
+        [&](unsigned n, int64_t p0, const double *tl, const double *tr, const double *S, const int32_t *closed, const int32_t *fix, hipStream_t s) {
+            const int nf = (int)(n / (unsigned)n_objects);                // cap and n_pairs are whole fingers: so is every chunk
+            hipLaunchKernelGGL(label_pair_kernel, dim3(n), dim3(64), 0, s, g, lg, starts_dev, rot_dev, tl, tr, S, closed, fix, part);
+            hipLaunchKernelGGL(label_rows_kernel, dim3((unsigned)((nf + 63) / 64)), dim3(64), 0, s, lg, (const PairPart *)part, nf,
+                               p0 / n_objects, rows_dev, counts_dev);
+        },
+        cap);
 }
 
 extern "C" int dgdm_squeeze_objective_values(const DgdmSqueezeConfig *cfg, const int32_t *cells_dev, const double *y_dev, const double *starts_dev,

@@ -1198,6 +1198,74 @@ def squeeze_tables(surfaces, objects, pairs, starts=None, rot=None, tables: bool
     return out
 
 
+LABEL_LAYOUTS = {"mean": 0, "per_object": 1}        # DGDM_LABEL_MEAN / DGDM_LABEL_PER_OBJECT
+
+
+def squeeze_label(surfaces, bank, objects: Sequence[int], starts, n_tally: int, threshold: Sequence[float], score_std: Sequence[float],
+                  pos_norm: Optional[float] = None, layout: str = "mean", friction: float = 0.0, rot=None, out: Optional[torch.Tensor] = None,
+                  column_offset: int = 0, object_stride: Optional[int] = None, counts: bool = True, workspace_bytes: Optional[int] = None,
+                  **config) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
+    """dgdm_squeeze_label (include/dgdm_hip.h "squeeze-simulator labels", DESIGN.md §4.1b "source: squeeze") on the current device: the
+    eps-net's condition rows of every finger from the squeeze simulator, reduced on the device chunk by chunk - no per-start output is
+    stored.  surfaces (F, 2, m) float64; bank (O, nv, 2) float64 polygons in metres; objects: M indices into the bank (pair f * M + k is
+    finger f on objects[k]); starts (n_tally + n_settle, 3) float64, the first n_tally tallied after one closing, the rest followed until
+    they settle (none: the 10 tally columns only); threshold (rad, m, m) and score_std (rad, m, m); pos_norm: metres per unit of position,
+    the dataset's POS_NORM by default; friction: the Coulomb coefficient (0: frictionless); config: the keys of SQUEEZE_DEFAULTS.
+    -> (rows, counts): rows (F, gc) float32, gc = 10 (+5) for 'mean' and M times that for 'per_object' - or `out` (F, >= width) float32,
+    written at column_offset with object blocks object_stride apart, every other float left alone; counts (F, 3) int32 = the finger's
+    tally (pair, start)s that were loose at the start, ended loose, and were cut by the x range (None with counts=False).
+    The workspace follows squeeze_tables' rule, counted in fingers: as many fingers as fit SQUEEZE_WORKSPACE_BYTES, at least one, never
+    more than the call has; workspace_bytes overrides it and does not change a bit of the rows.  Synchronises the stream once."""
+    from .sim.squeeze import check_friction
+    cfg = squeeze_config(**config)
+    mu = check_friction(friction, "squeeze_label")
+    if layout not in LABEL_LAYOUTS:
+        raise ValueError(f"squeeze_label: layout {layout!r} not supported ({' or '.join(LABEL_LAYOUTS)})")
+    f64 = _squeeze_mover()
+    sf, ob, st = f64(surfaces), f64(bank), f64(starts).reshape(-1, 3)
+    if sf.dim() != 3 or sf.shape[1] != 2 or ob.dim() != 3 or ob.shape[2] != 2:
+        raise ValueError(f"squeeze_label: surfaces (F, 2, m) and bank (O, nv, 2) expected, got {tuple(sf.shape)} and {tuple(ob.shape)}")
+    oi = np.ascontiguousarray(objects, dtype=np.int32).reshape(-1)
+    F, M, nt = int(sf.shape[0]), len(oi), int(n_tally)
+    ns = int(st.shape[0]) - nt
+    if pos_norm is None:
+        from .dynamics.dataloader import POS_NORM
+        pos_norm = POS_NORM
+    if len(threshold) != 3 or len(score_std) != 3:
+        raise ValueError("squeeze_label: threshold and score_std hold three entries (theta, x, y)")
+    cols = 10 + (5 if ns > 0 else 0)
+    per_object = layout == "per_object"
+    stride = cols if object_stride is None else int(object_stride)
+    width = int(column_offset) + ((M - 1) * stride if per_object else 0) + cols
+    if out is None:
+        out = torch.empty((F, width), dtype=torch.float32, device=sf.device)
+    if not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype == torch.float32 and out.dim() == 2 and out.shape[0] == F and out.shape[1] >= width
+            and out.stride(1) == 1):
+        raise ValueError(f"squeeze_label: out must be a float32 device tensor ({F}, >= {width}) with unit column stride")
+    T = cfg.theta_cells
+    rt = f64(squeeze_rotation_table(T) if rot is None else rot)
+    if rt.shape != (T, 2):
+        raise ValueError(f"squeeze_label: rot of shape {tuple(rt.shape)} (need ({T}, 2))")
+    sizer = lambda n: int(lib().dgdm_squeeze_label_workspace_bytes(C.byref(cfg), n, M, int(mu > 0.0)))      # noqa: E731
+    fit = sizer(min(max(F, 1), max(65535 // max(M, 1), 1)))       # all fingers in one chunk; negative: what the library refuses
+    if fit < 0:
+        _check_value(fit)
+    if workspace_bytes is not None:
+        ws_bytes = int(workspace_bytes)
+    elif fit <= SQUEEZE_WORKSPACE_BYTES:
+        ws_bytes = fit
+    else:                                           # the library cuts the budget into chunks of as many fingers as fit it
+        ws_bytes = max(SQUEEZE_WORKSPACE_BYTES, sizer(1))
+    ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=sf.device)
+    cnt = torch.empty((F, 3), dtype=torch.int32, device=sf.device) if counts else None
+    thr = (C.c_double * 3)(*[float(v) for v in threshold])
+    std = (C.c_double * 3)(*[float(v) for v in score_std])
+    _check_value(lib().dgdm_squeeze_label(C.byref(cfg), dptr(sf), F, int(sf.shape[2]), dptr(ob), int(ob.shape[0]), int(ob.shape[1]), oi.ctypes.data, M,
+                                          dptr(rt), dptr(st), nt, ns, mu, thr, std, float(pos_norm), LABEL_LAYOUTS[layout], out.data_ptr(),
+                                          int(out.stride(0)), int(column_offset), stride, dptr(cnt), dptr(ws), ws_bytes, stream_ptr()))
+    return out, cnt
+
+
 def squeeze_objective_values(cells: torch.Tensor, y: torch.Tensor, starts: torch.Tensor, batch: int, objectives: Sequence[_lib.Objective],
                              rowcoef: Optional[torch.Tensor] = None, score_std: Optional[Sequence[float]] = None, **config) -> torch.Tensor:
     """The objectives' VALUES per pair from a squeeze map (include/dgdm_hip.h, dgdm_squeeze_objective_values): cells

@@ -686,9 +686,12 @@ class Diffusion(nn.Module):
     def _cond_target_report(self, unguided, B: int, rank0: bool) -> Dict[str, Any]:
         """--cond_target: what was asked and - with a dynamics model - what the unguided samples achieve, labelled by the recipe stored in
         the statistics (dgdm_amd/label.py), all in raw units: columns, requested {column: value}, achieved_mean / achieved_std over the
-        batch (None when nothing scores them), baseline_mean = the dataset mean.  The dynamics model's opinion: 'predicted': True."""
+        batch (None when nothing scores them), baseline_mean = the dataset mean.  The dynamics model's opinion: 'predicted': True -
+        unless the statistics' rows were made by the squeeze simulator, which then also scores the samples (_cond_target_report_squeeze)."""
         from .. import label as lb
         stats, requested = self.cond_target
+        if stats.source == 'squeeze':
+            return self._cond_target_report_squeeze(stats, requested, unguided, rank0)
         rep: Dict[str, Any] = {"columns": list(stats.columns), "requested": dict(requested), "achieved_mean": None, "achieved_std": None,
                                "baseline_mean": stats.mean.copy(), "predicted": True}
         if not self.class_cond or self.object_vertices is None:
@@ -707,6 +710,38 @@ class Diffusion(nn.Module):
         if rank0:
             cols = ["column", "requested", "achieved_mean", "achieved_std", "baseline_mean", "objective"]
             data = [[c, requested.get(c), rep["achieved_mean"][i], rep["achieved_std"][i], stats.mean[i], {"predicted": True}]
+                    for i, c in enumerate(stats.columns)]
+            self._tables(self.save_dir).log_table("val/cond_target/unguided_sample", cols, data)
+        return rep
+
+    def _cond_target_report_squeeze(self, stats, requested, unguided, rank0: bool) -> Dict[str, Any]:
+        """The report for statistics whose rows the squeeze simulator made (label.label_fingers_squeeze): the unguided samples labelled
+        by the same simulator under the stored recipe - grid, thresholds, config, friction - against the run's objects.  No dynamics
+        model takes part: 'simulated': 'squeeze' and no 'predicted' key.  The squeeze model's opinion, not MuJoCo's."""
+        from .. import label as lb
+        from ..sim.squeeze import OBJECT_HALF_BOX_2D, SIMULATED
+        rep: Dict[str, Any] = {"columns": list(stats.columns), "requested": dict(requested), "achieved_mean": None, "achieved_std": None,
+                               "baseline_mean": stats.mean.copy(), "simulated": SIMULATED}
+        objects = getattr(self, "object_vertices", None)
+        if objects is None:
+            if rank0:
+                print("[dgdm_amd] --cond_target: no objects in this run: the achieved values were not scored", flush=True)
+            return rep
+        if self.mode == 'point_3d':
+            raise ValueError("cond target: rows labelled by the squeeze simulator belong to 2-D fingers")
+        objs = torch.as_tensor(objects)
+        r, M = stats.recipe, objs.shape[0]
+        if M != len(stats.object_ids):
+            raise ValueError(f"cond target: the rows were labelled against {len(stats.object_ids)} objects, this run has {M}")
+        bank = objs.detach().cpu().double() * OBJECT_HALF_BOX_2D          # the bank SqueezeSimulator builds
+        raw, _ = lb.label_fingers_squeeze(unguided.detach(), bank, list(range(M)), r["G"], r["P"], r.get("ori_range") or [-1.0, 1.0], r["threshold"],
+                                          r["score_std"], settled=bool(r.get("settled")), layout=stats.layout, friction=float(r.get("friction") or 0.0),
+                                          **(r.get("squeeze_config") or {}))
+        raw = raw.cpu().numpy().astype(np.float64)
+        rep["achieved_mean"], rep["achieved_std"] = raw.mean(axis=0), raw.std(axis=0)
+        if rank0:
+            cols = ["column", "requested", "achieved_mean", "achieved_std", "baseline_mean", "objective"]
+            data = [[c, requested.get(c), rep["achieved_mean"][i], rep["achieved_std"][i], stats.mean[i], {"simulated": SIMULATED}]
                     for i, c in enumerate(stats.columns)]
             self._tables(self.save_dir).log_table("val/cond_target/unguided_sample", cols, data)
         return rep

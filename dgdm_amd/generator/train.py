@@ -13,7 +13,9 @@ Not the reference's: ``--edit_from FILE.npy`` (with ``--pin``, ``--edit_band_mm`
 chains of the test-mode sweep edit the file's designs - batch b its rows [b B, (b + 1) B) - instead of starting from noise.
 ``--mode=label --label_out rows.npy`` labels all dataset fingers with the dynamics model's predictions (dgdm_amd/label.py; no eps-net is
 built) and writes the rows ``--global_cond`` takes, the raw rows and their statistics; ``--mode=test --cond_stats rows.json --cond_target
-NAME=VALUE,...`` samples every batch under the target row those statistics make of raw units.
+NAME=VALUE,...`` samples every batch under the target row those statistics make of raw units.  ``--label_source squeeze`` makes the same
+files from the squeeze simulator instead (sim/squeeze.py; 2-D, no dynamics model, no checkpoint), and the target's report is then that
+simulator's too.
 
 Assets the image does not have are substituted, loudly:
 * no checkpoint files  -> deterministic random-init weights (dgdm_amd.synth).
@@ -105,11 +107,27 @@ def check_label_flags(args):
     from .. import dist as ddist
     from .. import label as lb
     target, stats_path = getattr(args, "cond_target", None), getattr(args, "cond_stats", None)
+    source = getattr(args, "label_source", None) or 'model'
+    if (getattr(args, "label_settled", False) or getattr(args, "label_squeeze_cells", None) is not None) and \
+            not (args.mode == 'label' and source == 'squeeze'):
+        raise ValueError("--label_settled / --label_squeeze_cells need --mode=label --label_source squeeze")
+    if source != 'model' and args.mode != 'label':
+        raise ValueError("--label_source needs --mode=label")
     if args.mode == 'label':
         if not args.label_out:
             raise ValueError("--mode=label needs --label_out FILE.npy")
-        if not args.classifier_guidance:
-            raise ValueError("--mode=label needs --classifier_guidance and its flags: the labels are the dynamics model's predictions")
+        if source not in lb.SOURCES:
+            raise ValueError(f"--label_source={source}: 'model' or 'squeeze'")
+        if source == 'squeeze':
+            if args.fingers_3d:
+                raise ValueError("--label_source squeeze is 2-D only: a sliced squeeze evaluation per finger of a --fingers_3d dataset is out of "
+                                 "scope, not supported")
+            if int(args.label_rollout) != 0:
+                raise ValueError("--label_rollout is the dynamics model's roll-out: with --label_source squeeze the settled columns are --label_settled")
+            label_squeeze_config(args)          # --label_squeeze_cells / --squeeze_*: refused here
+        elif not args.classifier_guidance:
+            raise ValueError("--mode=label needs --classifier_guidance and its flags: the labels are the dynamics model's predictions "
+                             "(--label_source squeeze needs neither)")
         if args.label_layout not in lb.LAYOUTS:
             raise ValueError(f"--label_layout={args.label_layout}: 'mean' or 'per_object'")
         if int(args.label_rollout) < 0:
@@ -133,11 +151,70 @@ def check_label_flags(args):
         raise ValueError("--cond_target and --global_cond both set the condition rows of --mode=test: give one")
     stats = lb.LabelStats.load(stats_path)
     requested = stats.requested(lb.parse_target(target))         # an unknown column raises here
-    if args.classifier_guidance:
+    if stats.source == 'squeeze':               # the report labels the samples on the recipe's own grid, whatever this run's is
+        if args.fingers_3d:
+            raise ValueError("--cond_stats: the rows were labelled by the squeeze simulator, which is 2-D only (--fingers_3d)")
+    elif args.classifier_guidance:
         r = stats.recipe
         if r.get("G") != args.grid_size or r.get("P") != args.num_pos:
             raise ValueError(f"--cond_stats: the rows were labelled on a {r.get('G')} x {r.get('P')}^2 grid, this run's is {args.grid_size} x {args.num_pos}^2")
     return stats, requested
+
+
+def label_squeeze_config(args):
+    """--label_source squeeze [--label_squeeze_cells T,X --squeeze_closing_steps K --squeeze_window R --squeeze_friction MU] ->
+    (squeeze_config, friction).  ValueError for cells that are not two integers T >= 1, X >= 2, K < 0, R < 1, a bad MU.  Host code."""
+    from ..sim.squeeze import check_friction, steps_from_args
+    config = {}
+    cells = getattr(args, "label_squeeze_cells", None)
+    if cells is not None:
+        try:
+            t, x = (int(v) for v in str(cells).split(","))
+        except ValueError:
+            raise ValueError(f"--label_squeeze_cells {cells!r}: two integers T,X expected") from None
+        if t < 1 or x < 2:
+            raise ValueError(f"--label_squeeze_cells {cells!r}: need T >= 1 and X >= 2")
+        config.update(theta_cells=t, x_cells=x)
+    config.update(steps_from_args(args))
+    mu = getattr(args, "squeeze_friction", None)
+    return config, 0.0 if mu is None else check_friction(mu, "--squeeze_friction")
+
+
+def label_dataset_squeeze(args, dataset, objects, object_ids):
+    """--mode=label --label_source squeeze: every dataset finger labelled by the squeeze simulator (label.label_fingers_squeeze) on the
+    run's pose grid with the 2-D dataset's raw threshold and std; the same three files as label_dataset.  No dynamics model, no
+    checkpoint.  The squeeze model's opinion: frictionless unless --squeeze_friction; its steps, window, friction and the thresholds
+    are untuned for squeeze deltas; nothing is claimed about MuJoCo.  Returns (stats, raw)."""
+    from .. import engine
+    from .. import label as lb
+    from ..dynamics.dataloader import SCORE_STD, SCORE_THRESHOLD
+    from ..sim.squeeze import OBJECT_HALF_BOX_2D, SIMULATED
+    config, mu = label_squeeze_config(args)
+    M, layout, settled = objects.shape[0], args.label_layout, bool(args.label_settled)
+    lb.cond_dim(layout, M, int(settled))
+    thr, std = [float(v) for v in SCORE_THRESHOLD[1]], [float(v) for v in SCORE_STD[1]]
+    fingers = np.stack([dataset[i] for i in range(len(dataset))])
+    bank = torch.as_tensor(objects).detach().cpu().double() * OBJECT_HALF_BOX_2D       # the bank SqueezeSimulator builds
+    rows, counts = lb.label_fingers_squeeze(torch.from_numpy(fingers), bank, list(range(M)), args.grid_size, args.num_pos, (-1.0, 1.0), thr, std,
+                                            settled=settled, layout=layout, friction=mu, **config)
+    raw, counts = rows.cpu().numpy(), counts.cpu().numpy().astype(np.int64)
+    full = {k: getattr(engine.squeeze_config(**config), k) for k in engine.SQUEEZE_DEFAULTS}
+    recipe = {"G": args.grid_size, "P": args.num_pos, "ori_range": [-1.0, 1.0], "score_std": std, "source": SIMULATED, "squeeze_config": full,
+              "friction": mu, "settled": settled, "threshold": thr}
+    stats = lb.LabelStats(lb.column_names(layout, object_ids, int(settled)), layout, object_ids, recipe).fit(raw)
+    stem = args.label_out[:-4] if args.label_out.endswith(".npy") else args.label_out
+    if os.path.dirname(stem):
+        os.makedirs(os.path.dirname(stem), exist_ok=True)
+    np.save(stem + ".npy", stats.apply(raw))
+    np.save(stem + "_raw.npy", raw)
+    stats.save(stem + ".json")
+    flat = [c for c, k in zip(stats.columns, stats.constant) if k]
+    n_starts = raw.shape[0] * M * args.grid_size * args.num_pos ** 2
+    print(f"[dgdm_amd] labelled {raw.shape[0]} fingers x {raw.shape[1]} columns by the squeeze simulator ({layout}, {M} objects, friction {mu:g}"
+          f"{', settled' if settled else ''}) -> {stem}.npy, {stem}_raw.npy, {stem}.json; of {n_starts} tally starts {int(counts[:, 0].sum())} were loose "
+          f"at the start, {int(counts[:, 1].sum())} ended loose, {int(counts[:, 2].sum())} were cut by the table's x range"
+          + (f"; constant columns (standardised to 0): {', '.join(flat)}" if flat else ""), flush=True)
+    return stats, raw
 
 
 def _threshold_std(fingers_3d: bool):
@@ -377,6 +454,11 @@ def fit(model: Diffusion, pts: np.ndarray, args, bounds, dev) -> Diffusion:
     return model
 
 
+def _labels_by_squeeze(args) -> bool:
+    """--mode=label --label_source squeeze: a user of the --squeeze_* flags."""
+    return getattr(args, "mode", "test") == 'label' and (getattr(args, "label_source", None) or 'model') == 'squeeze'
+
+
 def squeeze_friction_from_args(args):
     """--squeeze_friction MU -> mu, or None without the flag.  ValueError: a negative or non-finite mu, --squeeze_sim_3d (friction is 2-D
     only), no squeeze user (--squeeze_sim or --resample_potential squeeze).  Host-side checks only."""
@@ -387,8 +469,8 @@ def squeeze_friction_from_args(args):
     mu = check_friction(mu, "--squeeze_friction")
     if getattr(args, "squeeze_sim_3d", False):
         raise ValueError(f"--squeeze_friction with --squeeze_sim_3d: {FRICTION_2D_ONLY}")
-    if not getattr(args, "squeeze_sim", False) and (getattr(args, "resample_potential", None) or 'model') != 'squeeze':
-        raise ValueError("--squeeze_friction needs --squeeze_sim or --resample_potential squeeze")
+    if not getattr(args, "squeeze_sim", False) and (getattr(args, "resample_potential", None) or 'model') != 'squeeze' and not _labels_by_squeeze(args):
+        raise ValueError("--squeeze_friction needs --squeeze_sim or --resample_potential squeeze (or --mode=label --label_source squeeze)")
     return mu
 
 
@@ -414,7 +496,7 @@ def squeeze_from_args(args):
     mu = squeeze_friction_from_args(args)
     if not getattr(args, "squeeze_sim", False):
         if (k is not None or r is not None) and not getattr(args, "squeeze_sim_3d", False) and \
-                (getattr(args, "resample_potential", None) or 'model') != 'squeeze':
+                (getattr(args, "resample_potential", None) or 'model') != 'squeeze' and not _labels_by_squeeze(args):
             raise ValueError("--squeeze_closing_steps / --squeeze_window need --squeeze_sim (or, with --fingers_3d, --squeeze_sim_3d), or "
                              "--resample_potential squeeze")
         return None
@@ -460,6 +542,9 @@ def train(args):
         gc = cond_stats.dim                 # --cond_target: the eps-net is as wide as the labelling run's rows
     dataset = GripperDataset(pts, 0.12, -0.12, max_y, min_y, cond=cond)
     L = args.ctrlpts_dim
+    if args.mode == 'label' and (getattr(args, "label_source", None) or 'model') == 'squeeze':      # no eps-net, no dynamics model: objects alone
+        objects, object_ids = _objects(args, False)
+        return label_dataset_squeeze(args, dataset, objects, object_ids)
     if args.mode == 'label':                # no eps-net: the dynamics model and the objects of --classifier_guidance alone
         classifier, objects, object_ids = _classifier(args, L, dev)
         return label_dataset(args, dataset, classifier, objects, object_ids, dev)
@@ -470,14 +555,18 @@ def train(args):
     classifier, objects, object_ids = None, None, None
     if args.classifier_guidance:
         classifier, objects, object_ids = _classifier(args, L, dev)
-        if cond_stats is not None and objects.shape[0] != len(cond_stats.object_ids):
-            raise ValueError(f"--cond_stats: the rows were labelled against {len(cond_stats.object_ids)} objects, this run has {objects.shape[0]}")
+    elif cond_stats is not None and cond_stats.source == 'squeeze':
+        objects, object_ids = _objects(args, False)     # the squeeze report's objects: the object flags without a dynamics model, for this only
+    if cond_stats is not None and objects is not None and objects.shape[0] != len(cond_stats.object_ids):
+        raise ValueError(f"--cond_stats: the rows were labelled against {len(cond_stats.object_ids)} objects, this run has {objects.shape[0]}")
     model = Diffusion(noise_pred_net=unet, noise_scheduler=scheduler, num_inference_steps=args.num_inference_steps, mode=mode, input_dim=1,
                       num_points=L, learning_rate=args.learning_rate, lr_warmup_steps=args.lr_warmup_steps, ema_power=args.ema_power,
                       class_cond=args.classifier_guidance, classifier_model=classifier, grid_size=args.grid_size, num_pos=args.num_pos,
                       object_vertices=objects, object_ids=object_ids, num_cpus=args.num_cpus, pts_x_dim=args.ctrlpts_x_dim,
                       pts_z_dim=args.ctrlpts_z_dim, sub_batch_size=args.sub_bs, render_video=args.render_video, seed=args.seed,
                       eta=float(getattr(args, "eta", 0.0) or 0.0), noise_seed=getattr(args, "noise_seed", None))
+    if not args.classifier_guidance and objects is not None:
+        model.object_vertices, model.object_ids = objects, object_ids      # Diffusion keeps them only with class_cond: the squeeze report reads them
     model.shared_step_noise = bool(getattr(args, "shared_step_noise", False))
     model.save_meshes = bool(getattr(args, "save_meshes", False))
     model.edit_plan = edit_plan

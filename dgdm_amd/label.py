@@ -1,11 +1,12 @@
 """Condition rows of the eps-net made by the dynamics model: what it predicts every finger of a set does, as ``global_cond`` rows.
 
 ``label_fingers`` runs ``engine.Guidance.label`` (and, with ``rollout=K``, ``label_settled``) over all fingers and returns the raw rows;
+``label_fingers_squeeze`` makes the same columns from the squeeze simulator's closings instead, with no dynamics model (source 'squeeze');
 ``LabelStats`` remembers how a dataset's rows were standardised, so that a request in plain units - "clockwise on 90 % of the grid" -
 becomes a condition row at sampling time (``LabelStats.target``).  The columns are those of include/dgdm_hip.h.
 
-These labels are the dynamics model's opinion, not simulator measurements, and in 3-D they depend on the FPS start seed like every
-``cond_fn`` call.
+Model labels are the dynamics model's opinion, not simulator measurements, and in 3-D they depend on the FPS start seed like every
+``cond_fn`` call.  Squeeze labels are the squeeze model's (sim/squeeze.py): this project's own idealisation, not MuJoCo's.
 """
 from __future__ import annotations
 
@@ -21,6 +22,10 @@ LAYOUTS = ("mean", "per_object")
 MAX_COND_DIM = 256                 # the eps-net's global_cond_dim limit
 # what a labelling run records beside the statistics (score_std: the dataset's (rad, m, m); K: roll-out interactions)
 RECIPE_KEYS = ("G", "P", "ori_range", "threshold_std", "score_std", "K", "timestep", "seed", "contraction_dtype")
+# who made the rows: the dynamics model (the key is absent from its files) or the squeeze simulator, whose files also record its recipe
+# (threshold: the raw (rad, m, m) of squeeze_metric's classes; settled: the 5 settled columns were made)
+SOURCES = ("model", "squeeze")
+SQUEEZE_RECIPE_KEYS = ("source", "squeeze_config", "friction", "settled", "threshold")
 
 _ROT_COLUMN = {"clockwise": "frac_clockwise", "counterclockwise": "frac_counterclockwise"}
 _SHIFT_COLUMN = {"up": "frac_up", "down": "frac_down", "left": "frac_left", "right": "frac_right"}
@@ -110,6 +115,61 @@ def label_fingers(guidance, fingers, objects: Sequence[int], threshold_std: Sequ
     return rows
 
 
+def label_fingers_squeeze(fingers, contours, objects: Sequence[int], grid_size: int, num_pos: int, ori_range: Sequence[float],
+                          threshold: Sequence[float], score_std: Sequence[float], settled: bool = False, layout: str = "mean", friction: float = 0.0,
+                          num_points: int = 200, **squeeze_config):
+    """The same rows made by the squeeze simulator instead of the dynamics model (engine.squeeze_label; include/dgdm_hip.h
+    "squeeze-simulator labels", DESIGN.md 4.1b "source: squeeze"): no model, no checkpoint, no random draw.  fingers (N, L[, 1]) in sampler
+    units; contours (O, nv, 2) float64 polygons in metres; objects: indices into contours.  The tally starts are the pose grid's cells
+    (resample.start_grid(G, P, ori_range)), one closing each; with settled=True the G start orientations (sim.squeeze.start_orientations)
+    follow, each run until it settles, and the rows carry the 5 settled columns.  threshold: raw (rad, m, m), squeeze_metric's classes;
+    score_std: the dataset's (rad, m, m).  -> (rows (N, gc) float32 on the device, counts (N, 3) int32 on the device: per finger the
+    tally (object, start)s that were loose at the start, ended loose, and were cut by the table's x range).  The fingers are decoded and
+    run in chunks of as many as one workspace holds, so only one chunk's surfaces exist at a time; the chunking does not change the rows.
+    The simulator's opinion: frictionless unless friction > 0, its steps, window, friction and these thresholds untuned for squeeze
+    deltas; nothing is claimed about MuJoCo.  NaN settled columns raise ValueError naming the finger."""
+    import ctypes as C
+    import torch
+    from . import engine
+    from .resample import start_grid
+    from .sim import squeeze as sq
+    M = len(objects)
+    gc = cond_dim(layout, M, 1 if settled else 0)
+    dev = torch.device("cuda", torch.cuda.current_device())
+    x = torch.as_tensor(fingers).detach().to(device=dev, dtype=torch.float32)
+    x = x.reshape(x.shape[0], -1).contiguous()
+    N = x.shape[0]
+    if N < 1:
+        raise ValueError("label_fingers_squeeze: no fingers")
+    if M < 1:
+        raise ValueError("label_fingers_squeeze: no objects")
+    mu = sq.check_friction(friction, "label_fingers_squeeze")
+    tally = start_grid(grid_size, num_pos, ori_range)
+    starts = np.concatenate([tally, sq.start_orientations(grid_size, ori_range)]) if settled else tally
+    cfg = engine.squeeze_config(**squeeze_config)
+    f64 = lambda a: torch.as_tensor(np.ascontiguousarray(a, dtype=np.float64)).to(dev)      # noqa: E731
+    bank, st, rot = f64(torch.as_tensor(contours).detach().cpu().numpy()), f64(starts), f64(engine.squeeze_rotation_table(cfg.theta_cells))
+    sizer = lambda n: int(engine.lib().dgdm_squeeze_label_workspace_bytes(C.byref(cfg), n, M, int(mu > 0.0)))      # noqa: E731
+    one = sizer(1)
+    if one < 0:
+        engine._check_value(one)
+    chunk = max(1, min(N, engine.SQUEEZE_WORKSPACE_BYTES // one, 65535 // M))
+    rows = torch.empty((N, gc), dtype=torch.float32, device=dev)
+    counts = torch.empty((N, 3), dtype=torch.int32, device=dev)
+    per = len(block_columns(1 if settled else 0))
+    for f0 in range(0, N, chunk):
+        f1 = min(N, f0 + chunk)
+        sf = sq.finger_surfaces(x[f0:f1], int(num_points))
+        _, cnt = engine.squeeze_label(sf, bank, objects, st, len(tally), threshold, score_std, layout=layout, friction=mu, rot=rot, out=rows[f0:f1],
+                                      object_stride=per, workspace_bytes=sizer(f1 - f0), **squeeze_config)
+        counts[f0:f1] = cnt
+    if settled:
+        bad = torch.isnan(rows).any(dim=1)
+        if bool(bad.any()):
+            raise ValueError(f"label_fingers_squeeze: finger {int(torch.nonzero(bad)[0])} settled on a non-finite pose (its settled columns are NaN)")
+    return rows, counts
+
+
 def parse_target(text: str) -> Dict[str, float]:
     """``"frac_clockwise=0.9,frac_up=0.7"`` -> {'frac_clockwise': 0.9, 'frac_up': 0.7}; ValueError on anything else."""
     out: Dict[str, float] = {}
@@ -147,6 +207,11 @@ class LabelStats:
     @property
     def dim(self) -> int:
         return len(self.columns)
+
+    @property
+    def source(self) -> str:
+        """'model' (also when the recipe does not say) or 'squeeze'."""
+        return self.recipe.get("source") or "model"
 
     @property
     def constant(self) -> np.ndarray:
@@ -205,7 +270,8 @@ class LabelStats:
         return {"columns": self.columns, "mean": self.mean.tolist(), "std": self.std.tolist(), "min": self.min.tolist(), "max": self.max.tolist(),
                 "layout": self.layout, "object_ids": [o.item() if isinstance(o, np.generic) else o for o in self.object_ids],
                 **{k: self.recipe.get(k) for k in RECIPE_KEYS},
-                "predicted": True}
+                **({"predicted": True} if self.source == "model" else
+                   {**{k: self.recipe.get(k) for k in SQUEEZE_RECIPE_KEYS}, "simulated": self.source})}
 
     def save(self, path: str) -> None:
         with open(path, "w") as f:
@@ -216,8 +282,11 @@ class LabelStats:
         try:
             with open(path) as f:
                 d = json.load(f)
+            source = d.get("source") or "model"
+            if source not in SOURCES:
+                raise ValueError(f"label source {source!r} (need one of {', '.join(SOURCES)})")
             s = cls(d["columns"], d["layout"], d["object_ids"],
-                    {k: d.get(k) for k in RECIPE_KEYS})
+                    {k: d.get(k) for k in RECIPE_KEYS + (SQUEEZE_RECIPE_KEYS if source != "model" else ())})
             s.mean, s.std = np.asarray(d["mean"], dtype=np.float64), np.asarray(d["std"], dtype=np.float64)
             s.min, s.max = np.asarray(d["min"], dtype=np.float64), np.asarray(d["max"], dtype=np.float64)
         except (OSError, KeyError, TypeError, ValueError) as e:

@@ -886,6 +886,64 @@ int dgdm_squeeze_map_friction(const DgdmSqueezeConfig *cfg, const double *surfac
                               int32_t *flags_dev, double *table_s_dev, double *touch_l_dev, double *touch_r_dev, int32_t *succ_dev,
                               void *workspace_dev, int64_t workspace_bytes, void *stream, double mu, int32_t *jam_dev, int32_t *contact_dev);
 
+/* ------------------------------------------------------------------ squeeze-simulator labels (csrc/squeeze.hip, DESIGN.md §4.1b
+ * "source: squeeze")
+ * Condition rows of the eps-net (global_cond) from the squeeze simulator: dgdm_guidance_label's and dgdm_guidance_label_settled's columns
+ * made of the squeeze model's closings, with no dynamics model anywhere.  This project's own mechanism, 2-D only; frictionless unless
+ * mu > 0; k, R, mu and the thresholds are untuned for squeeze deltas; nothing is claimed about MuJoCo.  tests/squeeze_label_oracle.py
+ * restates the text below in numpy float64 and the device reproduces it (bit for bit, but for the two columns that pass through sqrt).
+ * The per-start outputs of the map are never written: each chunk's tables are reduced to rows on the device.
+ * Inputs.  cfg, surfaces_dev [n_fingers][2][m], objects_dev (the bank) [n_bank][nv][2], rot_dev: dgdm_squeeze_map's.  objects_host
+ *   [n_objects] int32 indices into the bank, HOST.  The pairs are implied, finger-major: pair f * n_objects + k is (finger f, object
+ *   objects_host[k]).  starts_dev [n_tally + n_settle][3] = (theta0, x0, y0): the first n_tally starts are tallied after one closing,
+ *   the last n_settle are followed until they settle; n_settle = 0 writes the tally columns only.  mu = 0: dgdm_squeeze_map's tables;
+ *   mu > 0: dgdm_squeeze_map_friction's (a jammed cell is its own successor) - the rows of mu = 0 are the frictionless rows bit for bit.
+ * Everything below is float64, every product, sum and quotient rounded on its own, in the order written; no transcendental function is
+ * evaluated on the device.  T = theta_cells, X = x_cells, dx = 2 x_half / (X - 1), tm = travel_max.
+ * Tally start n < n_tally of a pair.  c0 = the snapped start cell, ck = the closed cell (the closing_steps-th successor), cf = the
+ *   settled cell, y_closed = y at ck: all dgdm_squeeze_map's.  a = cell / X, b = cell % X;  da = a_k - a_0 as an integer,
+ *   2 da > T: da -= T;  2 da < -T: da += T   (dgdm_squeeze_objective_values' fold);
+ *     e0 = (double)da * (6.283185307179586 / T)        radians
+ *     e1 = (double)(b_k - b_0) * dx                    metres
+ *     e2 = y_closed - y0                               metres
+ *   class of e_j: 2 if e_j > threshold[j], else 0 if e_j < -threshold[j], else 1 (a NaN: 1) - sim.squeeze.squeeze_metric's rule on raw
+ *   radians and metres;  d0 = e0 / score_std[0], d1 = e1 / score_std[1], d2 = e2 / score_std[2].
+ *   Per pair, one wave of 64 lanes: lane l takes n = l, l + 64, ... in ascending order, counting the six classes below in int32 and
+ *   adding the four terms d0, fabs(d0), d1, d2 to four sums that start at 0.0; then v += shfl_xor(v, s) for s = 32, 16, .., 1 (the shape
+ *   of dgdm_squeeze_objective_values).  This gives the pair's counts c[6] and sums s[4].
+ * Settle start g < n_settle (start n_tally + g) of a pair, (a_s, b_s) = cf's:  (cos_g, sin_g) = rot_dev[a_s];
+ *     x_s = -x_half + (double)b_s * dx;   px = x_s / pos_norm;   py = y_settled / pos_norm;   r_g = sqrt(px px + py py)
+ *     out_g = b_s == 0 or b_s == X - 1 (flag 4) or fabs(px) > 1 or fabs(py) > 1
+ *   Per pair the same wave shape over g gives sum cos, sum sin, sum r (from 0.0) and the count of out_g; with G = (double)n_settle:
+ *     c = (sum cos) / G;  s = (sum sin) / G;  rho = sqrt(c c + s s);  offset = (sum r) / G;  left = (double)count / G
+ *   A non-finite y_settled at any g makes rho, c, s and offset of that pair NaN.
+ * Rows.  Row f starts at rows_dev + f row_stride + column_offset.  layout DGDM_LABEL_MEAN: one block there, over all n_objects pairs of
+ *   the finger, M' = n_objects.  DGDM_LABEL_PER_OBJECT: object k's block starts k object_stride floats further on and holds pair k
+ *   alone, M' = 1.  A block, its pairs k ascending, n' = (int64)M' n_tally:
+ *     0 frac_clockwise (e0 class 0)   1 frac_counterclockwise (e0 class 2)   2 frac_up (e1 class 0)   3 frac_down (e1 class 2)
+ *     4 frac_left (e2 class 0)        5 frac_right (e2 class 2)
+ *       each float32((double)K / (double)n'), K the class count summed in int64 over the block's pairs;
+ *     6 mean_rot   7 mean_abs_rot   8 mean_shift_x   9 mean_shift_y
+ *       each float32((0.0 + s_k0[j] + s_k1[j] + ...) / (double)n'), j = 0 .. 3: the dynamics model's normalised units;
+ *     10 settle_concentration   11 settle_cos   12 settle_sin   13 settle_offset   14 left_range     (n_settle > 0 only)
+ *       each float32((0.0 + v_k0 + v_k1 + ...) / (double)M') of the pairs' rho, c, s, offset, left.
+ *   Floats of the row that belong to no block are not written.
+ * counts_dev [n_fingers][3] int32 or NULL: per finger the number of tally (pair, start)s with flag 1 (loose at the start cell), flag 2
+ *   (ended loose) and flag 4 (settled on the edge of the x range).
+ * Chunks hold whole fingers only: the workspace holds the tables of as many fingers' pairs as fit it and their partial sums
+ *   (dgdm_squeeze_label_workspace_bytes(cfg, chunk_fingers, n_objects, friction != 0); negative: bad arguments); the chunking does not
+ *   change a bit of the rows.
+ * DGDM_EINVAL before any launch: everything dgdm_squeeze_map(_friction) refuses; n_objects < 1 or more than 65535; an object index
+ *   outside the bank; n_tally < 1; n_settle < 0; n_objects n_tally or n_fingers n_objects beyond 2^31 - 1; a non-finite or non-positive
+ *   score_std or pos_norm; a non-finite or negative threshold; an unknown layout; column_offset < 0; object_stride (PER_OBJECT) or
+ *   row_stride smaller than the columns they must hold; a workspace too small for one finger.  Synchronises the stream once, at the end. */
+int64_t dgdm_squeeze_label_workspace_bytes(const DgdmSqueezeConfig *cfg, int chunk_fingers, int n_objects, int friction);
+int dgdm_squeeze_label(const DgdmSqueezeConfig *cfg, const double *surfaces_dev, int n_fingers, int num_points, const double *bank_dev,
+                       int n_bank, int num_vertices, const int32_t *objects_host, int n_objects, const double *rot_dev,
+                       const double *starts_dev, int n_tally, int n_settle, double mu, const double threshold[3],
+                       const double score_std[3], double pos_norm, int layout, float *rows_dev, int64_t row_stride, int column_offset,
+                       int object_stride, int32_t *counts_dev, void *workspace_dev, int64_t workspace_bytes, void *stream);
+
 /* The objective's VALUE per (pair) from a squeeze map: what dgdm_guidance_objective_values makes of the dynamics model's logits, made
  * of the squeeze model's one-closing deltas instead - a second opinion for resampling.  This project's own mechanism:
  * no counterpart in the reference, 2-D only, frictionless.  THE recipe (tests/resample_squeeze_oracle.py states the same text in numpy).
