@@ -25,6 +25,9 @@
 // dgdm_squeeze_label (include/dgdm_hip.h "squeeze-simulator labels") is a fourth map entry behind the same front end: it hands run_chunks a
 // consumer, which reduces each chunk's tables to condition rows where lookup_kernel would write per-start outputs, and fixes the chunk at
 // whole fingers, since a row is made of all of a finger's pairs.
+// dgdm_squeeze_label_3d (include/dgdm_hip.h "squeeze-simulator labels, 3-D fingers") is the fifth: the label entry's consumer behind the 3-D
+// entry's inputs, both entries' checks (label_front, check_slices), and table3d_fingers_kernel for the chunk's tables, which shares the
+// finger-independent work of table3d_kernel among a block of fingers and gives that kernel's tables bit for bit.
 // This file is compiled with -ffp-contract=off (build.py): no operation of the contract is fused.
 #include "common.h"
 #include <cmath>
@@ -782,6 +785,139 @@ __global__ __launch_bounds__(TABLE_THREADS) void table3d_kernel(Grid3 g, const d
     }
 }
 
+// table3d_kernel's tables for a chunk of whole fingers x M objects (dgdm_squeeze_label_3d; pair f * M + k of the chunk is its finger f on
+// object k, as that entry lists them), with what does not read the finger done once per block of FB fingers.  Grid: (T, M, blocks of FB
+// fingers) workgroups, lanes on the x cells.  Per (segment, lane) the two searches, set A's i and f, set B's range and slope and each
+// abscissa's ye are evaluated once; the loops over the block's fingers hold only the contract's operations on that finger's profiles, and
+// each finger's two minima stay in registers.  Every finger sees its candidates in table3d_kernel's order (P, Q, then the abscissae
+// ascending, segment by segment), so its three tables are table3d_kernel's bit for bit.  A tail block runs the same loops under the
+// uniform bound nfb < FB and reads no finger past the chunk.
+// LDS: the current level's profiles of the block only, restaged when the level changes - the segments come level-sorted and the level
+// loop is uniform across the workgroup, so the barriers in it are legal.  sP[i][f] = (L_j[i], U_j[i]) of finger f as one 16-byte pair,
+// entries LABEL3_ENTRY = 2 FB + 2 doubles apart: a lane's reads of the entries i and i + 1 of all FB fingers are 2 FB ds_read_b128 of one
+// contiguous run, and the 16 bytes of padding put the entries i .. i + 15, which one ds_read_b128 service group of 16 (non-contiguous)
+// lanes may span, on 16 distinct quarters of the 64 banks (entry stride 144 B at FB = 8: i * 36 mod 64 is a different multiple of 4 for
+// 16 consecutive i; lanes on one entry read one address, a broadcast).  Bytes, FB = 8: mu * 144 (profiles) + 8 mu (gx) + 16384 (a tile
+// of FSEG_TILE = 512 rotated segments) + 4 (mv + 1) (level offsets) = 3600 + 200 + 16384 + 104 = 20288 at 25 x 25; at the limits
+// mu = 128 (mv = 8): 18432 + 1024 + 16384 + 36 = 35876, and mu = 2 (mv = 512): 288 + 16 + 16384 + 2052 = 18740.  Whole surfaces of the
+// block would be 16 KB per finger at the limits, 128 KB for FB = 8: one workgroup per CU.
+constexpr int LABEL3_FB = 8, FSEG_TILE = 512;
+constexpr int LABEL3_ENTRY = 2 * LABEL3_FB + 2;
+
+template <int FB, bool TAIL>
+__device__ __forceinline__ void table3d_fingers_body(const Grid3 &g, int M, int nfb, const double *surfaces, const double *gx,
+                                                     const double *segments, const int32_t *seg_offsets, const int32_t *pairs, const double *rot,
+                                                     double *touch_l, double *touch_r, double *S, double *lds) {
+    constexpr int ENTRY = 2 * FB + 2;
+    const int ms = g.mv * g.mu, mu = g.mu, tid = threadIdx.x;
+    double *sP = lds, *sG = lds + mu * ENTRY, *sSeg = sG + mu;
+    int32_t *sOff = reinterpret_cast<int32_t *>(sSeg + 4 * FSEG_TILE);
+    const int a = blockIdx.x, k = blockIdx.y;
+    const int64_t pr0 = (int64_t)blockIdx.z * FB * M + k;                  // the block's first pair of the chunk; finger f's is M f further on
+    const double *sf = surfaces + (int64_t)pairs[2 * pr0] * 2 * ms;        // the chunk's fingers are consecutive: finger f's is 2 ms f further on
+    const int32_t *off = seg_offsets + (int64_t)pairs[2 * pr0 + 1] * (g.mv + 1);
+    const double c = rot[2 * a], s = rot[2 * a + 1];
+    for (int i = tid; i < mu; i += TABLE_THREADS) sG[i] = gx[i];
+    for (int i = tid; i <= g.mv; i += TABLE_THREADS) sOff[i] = off[i];
+    __syncthreads();
+    const double glast = sG[mu - 1], inf = INFINITY;
+    for (int b0 = 0; b0 < g.X; b0 += TABLE_THREADS) {
+        const int b = b0 + tid;
+        const double xg = -g.x_half + (double)b * g.dx;
+        double gl[FB], gu[FB];
+#pragma unroll
+        for (int f = 0; f < FB; ++f) gl[f] = gu[f] = inf;
+        for (int j = 0; j < g.mv; ++j) {
+            const int s0 = sOff[j], s1 = sOff[j + 1];
+            if (s0 == s1) continue;                                        // uniform: an empty level stages nothing
+            __syncthreads();                                               // the level and the tile before have been read by every lane
+            for (int e = tid; e < nfb * 2 * mu; e += TABLE_THREADS) {      // L_j then U_j of finger f, as the finger holds them
+                const int f = e / (2 * mu), r = e - f * 2 * mu, u = r >= mu ? 1 : 0, i = r - u * mu;
+                sP[i * ENTRY + 2 * f + u] = sf[(int64_t)f * 2 * ms + (int64_t)u * ms + j * mu + i];
+            }
+            for (int t0 = s0; t0 < s1; t0 += FSEG_TILE) {
+                const int n = min(FSEG_TILE, s1 - t0);
+                if (t0 > s0) __syncthreads();
+                for (int q = tid; q < n; q += TABLE_THREADS) {
+                    const double *sg = segments + 4 * (int64_t)(t0 + q);
+                    const double ax = sg[0], ay = sg[1], bx = sg[2], by = sg[3];
+                    sSeg[4 * q] = c * ax - s * ay;
+                    sSeg[4 * q + 1] = s * ax + c * ay;
+                    sSeg[4 * q + 2] = c * bx - s * by;
+                    sSeg[4 * q + 3] = s * bx + c * by;
+                }
+                __syncthreads();
+                if (b >= g.X) continue;
+                for (int q = 0; q < n; ++q) {
+                    const double px = sSeg[4 * q] + xg, py = sSeg[4 * q + 1], qx = sSeg[4 * q + 2] + xg, qy = sSeg[4 * q + 3];
+                    const int ip = last_le(sG, mu, px), iq = last_le(sG, mu, qx);
+#pragma unroll
+                    for (int end = 0; end < 2; ++end) {                    // set A: P, then Q
+                        const int ie = end ? iq : ip;
+                        const double ex = end ? qx : px, ey = end ? qy : py;
+                        if (ie >= 0 && ex <= glast) {
+                            const int i = min(ie, mu - 2);
+                            const double g0 = sG[i], fr = (ex - g0) / (sG[i + 1] - g0);
+                            const double2 *e0 = reinterpret_cast<const double2 *>(sP + i * ENTRY), *e1 = e0 + ENTRY / 2;
+#pragma unroll
+                            for (int f = 0; f < FB; ++f) {
+                                if (TAIL && f >= nfb) break;
+                                const double2 v0 = e0[f], v1 = e1[f];
+                                const double lp = v0.x + fr * (v1.x - v0.x);
+                                const double up = v0.y + fr * (v1.y - v0.y);
+                                gl[f] = fmin(gl[f], ey - lp);
+                                gu[f] = fmin(gu[f], up - ey);
+                            }
+                        }
+                    }
+                    if (px < qx || qx < px) {                              // set B
+                        const bool fwd = px < qx;
+                        const int ilo = fwd ? ip : iq, ihi = fwd ? iq : ip;
+                        const double xlo = fwd ? px : qx;
+                        const int i0 = (ilo >= 0 && sG[ilo] == xlo) ? ilo : ilo + 1;
+                        if (i0 <= ihi) {
+                            const double slope = (qy - py) / (qx - px);
+                            for (int i = i0; i <= ihi; ++i) {
+                                const double ye = py + (sG[i] - px) * slope;
+                                const double2 *e0 = reinterpret_cast<const double2 *>(sP + i * ENTRY);
+#pragma unroll
+                                for (int f = 0; f < FB; ++f) {
+                                    if (TAIL && f >= nfb) break;
+                                    const double2 v = e0[f];
+                                    gl[f] = fmin(gl[f], ye - v.x);
+                                    gu[f] = fmin(gu[f], v.y - ye);
+                                }
+                            }
+                        }
+                    }
+                }
+            }
+        }
+        if (b < g.X) {
+#pragma unroll
+            for (int f = 0; f < FB; ++f) {
+                if (f >= nfb) break;
+                const int64_t o = ((pr0 + (int64_t)f * M) * g.T + a) * g.X + b;
+                touch_l[o] = gl[f];
+                touch_r[o] = gu[f];
+                S[o] = (gl[f] + gu[f]) / 2.0;
+            }
+        }
+    }
+}
+
+// `nf`: the chunk's fingers.  The branch on a full block is uniform across the grid's z.
+__global__ __launch_bounds__(TABLE_THREADS) void table3d_fingers_kernel(Grid3 g, int M, int nf, const double *surfaces, const double *gx,
+                                                                        const double *segments, const int32_t *seg_offsets, const int32_t *pairs,
+                                                                        const double *rot, double *touch_l, double *touch_r, double *S) {
+    extern __shared__ __align__(16) double lds16[];
+    const int nfb = min(LABEL3_FB, nf - (int)blockIdx.z * LABEL3_FB);
+    if (nfb == LABEL3_FB)
+        table3d_fingers_body<LABEL3_FB, false>(g, M, nfb, surfaces, gx, segments, seg_offsets, pairs, rot, touch_l, touch_r, S, lds16);
+    else
+        table3d_fingers_body<LABEL3_FB, true>(g, M, nfb, surfaces, gx, segments, seg_offsets, pairs, rot, touch_l, touch_r, S, lds16);
+}
+
 // the 3-D entry's workspace: gx [mu] and the level offsets [n_objects][mv + 1] in front, wherever the chunks are cut, then the chunk's
 // layout (run_chunks gets what lies behind the block)
 struct Extra3 { size_t gx, off, bytes; };
@@ -912,16 +1048,11 @@ extern "C" int64_t dgdm_squeeze_label_workspace_bytes(const DgdmSqueezeConfig *c
     return workspace_bytes_of(fn, cfg, chunk_pairs, friction != 0, label_extra(chunk_pairs));
 }
 
-extern "C" int dgdm_squeeze_label(const DgdmSqueezeConfig *cfg, const double *surfaces_dev, int n_fingers, int num_points, const double *bank_dev,
-                                  int n_bank, int num_vertices, const int32_t *objects_host, int n_objects, const double *rot_dev,
-                                  const double *starts_dev, int n_tally, int n_settle, double mu, const double threshold[3],
-                                  const double score_std[3], double pos_norm, int row_layout, float *rows_dev, int64_t row_stride, int column_offset,
-                                  int object_stride, int32_t *counts_dev, void *workspace_dev, int64_t workspace_bytes, void *stream) {
-    const char *fn = "dgdm_squeeze_label";
-    const char *bytes_fn = "dgdm_squeeze_label_workspace_bytes";
-    DGDM_REQUIRE(std::isfinite(mu) && mu >= 0.0, DGDM_EINVAL, "%s: friction coefficient %g (need finite, >= 0)", fn, mu);
-    int rc = check_sizes_2d(fn, num_points, num_vertices);
-    if (rc || (rc = check_label_objects(fn, n_objects))) return rc;
+// What both label entries check alike of the arguments they share, after the sizes of their own inputs and before check_map_args: on
+// DGDM_OK `lg` holds all but dth (the config is checked later) and `pairs` the finger-major list, pair f * M + k = (f, objects_host[k]).
+static int label_front(const char *fn, int n_fingers, int n_bank, const int32_t *objects_host, int n_objects, const double *starts_dev, int n_tally,
+                       int n_settle, const double threshold[3], const double score_std[3], double pos_norm, int row_layout, const float *rows_dev,
+                       int64_t row_stride, int column_offset, int object_stride, LabelGrid &lg, std::vector<int32_t> &pairs) {
     DGDM_REQUIRE(objects_host && threshold && score_std && rows_dev && starts_dev, DGDM_EINVAL, "%s: null argument", fn);
     DGDM_REQUIRE(n_fingers >= 1 && n_bank >= 1, DGDM_EINVAL, "%s: %d fingers, a bank of %d objects (need >= 1 each)", fn, n_fingers, n_bank);
     DGDM_REQUIRE((int64_t)n_fingers * n_objects <= INT32_MAX, DGDM_EINVAL, "%s: %d fingers x %d objects exceed 2^31 - 1 pairs", fn, n_fingers, n_objects);
@@ -943,34 +1074,7 @@ extern "C" int dgdm_squeeze_label(const DgdmSqueezeConfig *cfg, const double *su
     DGDM_REQUIRE(!per_object || object_stride >= cols, DGDM_EINVAL, "%s: object_stride %d holds no block of %d columns", fn, object_stride, cols);
     const int64_t width = (int64_t)column_offset + (per_object ? (int64_t)(n_objects - 1) * object_stride : 0) + cols;
     DGDM_REQUIRE(row_stride >= width, DGDM_EINVAL, "%s: row_stride %lld holds no row of %lld floats", fn, (long long)row_stride, (long long)width);
-
-    const bool friction = mu > 0.0;
-    const int n_pairs = n_fingers * n_objects;
-    std::vector<int32_t> pairs((size_t)2 * n_pairs);                      // finger-major: pair f * M + k = (f, objects_host[k])
-    for (int f = 0; f < n_fingers; ++f)
-        for (int k = 0; k < n_objects; ++k) {
-            pairs[2 * ((size_t)f * n_objects + k)] = f;
-            pairs[2 * ((size_t)f * n_objects + k) + 1] = objects_host[k];
-        }
-    const Outputs out = {};
-    if ((rc = check_map_args(fn, cfg, surfaces_dev && bank_dev && rot_dev, true, n_fingers, n_bank, pairs.data(), n_pairs, nullptr, 0, out, workspace_dev,
-                             workspace_bytes, friction, label_extra(1), bytes_fn)))
-        return rc;
-    // whole fingers only: the most fingers whose partials and tables the workspace holds
-    const int64_t cells = (int64_t)cfg->theta_cells * cfg->x_cells;
-    auto need = [&](int64_t fingers) { return (int64_t)(label_extra(fingers * n_objects) + layout(cells, fingers * n_objects, friction).bytes); };
-    DGDM_REQUIRE(workspace_bytes >= need(1), DGDM_EINVAL, "%s: workspace of %lld bytes holds no finger of %d objects, one needs %lld (%s)", fn,
-                 (long long)workspace_bytes, n_objects, (long long)need(1), bytes_fn);
-    int64_t fingers = 1, over = std::min<int64_t>(n_fingers, MAX_CHUNK / n_objects) + 1;      // need() does not fall: bisect [fingers, over)
-    while (over - fingers > 1) {
-        const int64_t mid = fingers + (over - fingers) / 2;
-        if (need(mid) <= workspace_bytes) fingers = mid; else over = mid;
-    }
-    const int64_t cap = fingers * n_objects;
-    const size_t extra = label_extra(cap);
-
-    const Grid g = grid_2d(cfg, num_points, num_vertices);
-    LabelGrid lg = {};
+    lg = {};
     lg.n_tally = n_tally;
     lg.n_settle = n_settle;
     lg.M = n_objects;
@@ -978,9 +1082,71 @@ extern "C" int dgdm_squeeze_label(const DgdmSqueezeConfig *cfg, const double *su
     lg.column_offset = column_offset;
     lg.object_stride = per_object ? object_stride : 0;
     lg.row_stride = row_stride;
-    lg.dth = TWO_PI / (double)g.T;
     for (int j = 0; j < 3; ++j) { lg.thr[j] = threshold[j]; lg.std[j] = score_std[j]; }
     lg.pos_norm = pos_norm;
+    pairs.resize((size_t)2 * n_fingers * n_objects);
+    for (int f = 0; f < n_fingers; ++f)
+        for (int k = 0; k < n_objects; ++k) {
+            pairs[2 * ((size_t)f * n_objects + k)] = f;
+            pairs[2 * ((size_t)f * n_objects + k) + 1] = objects_host[k];
+        }
+    return DGDM_OK;
+}
+
+// Whole fingers only: the most fingers whose partials and tables a workspace holds behind the `front` bytes the entry keeps ahead of them.
+static int label_chunk_fingers(const char *fn, const char *bytes_fn, const DgdmSqueezeConfig *cfg, int n_fingers, int n_objects, bool friction,
+                               int64_t workspace_bytes, size_t front, int64_t &fingers) {
+    const int64_t cells = (int64_t)cfg->theta_cells * cfg->x_cells;
+    auto need = [&](int64_t f) { return (int64_t)(front + label_extra(f * n_objects) + layout(cells, f * n_objects, friction).bytes); };
+    DGDM_REQUIRE(workspace_bytes >= need(1), DGDM_EINVAL, "%s: workspace of %lld bytes holds no finger of %d objects, one needs %lld (%s)", fn,
+                 (long long)workspace_bytes, n_objects, (long long)need(1), bytes_fn);
+    fingers = 1;
+    int64_t over = std::min<int64_t>(n_fingers, MAX_CHUNK / n_objects) + 1;                   // need() does not fall: bisect [fingers, over)
+    while (over - fingers > 1) {
+        const int64_t mid = fingers + (over - fingers) / 2;
+        if (need(mid) <= workspace_bytes) fingers = mid; else over = mid;
+    }
+    return DGDM_OK;
+}
+
+// The label entries' consumer: a chunk's n pairs (whole fingers, the first one pair p0's) from its tables to rows and counts.
+static void launch_label(const Grid &g, const LabelGrid &lg, unsigned n, int64_t p0, const double *starts_dev, const double *rot_dev, const double *tl,
+                         const double *tr, const double *S, const int32_t *closed, const int32_t *fix, PairPart *part, float *rows_dev,
+                         int32_t *counts_dev, hipStream_t s) {
+    const int nf = (int)(n / (unsigned)lg.M);
+    hipLaunchKernelGGL(label_pair_kernel, dim3(n), dim3(64), 0, s, g, lg, starts_dev, rot_dev, tl, tr, S, closed, fix, part);
+    hipLaunchKernelGGL(label_rows_kernel, dim3((unsigned)((nf + 63) / 64)), dim3(64), 0, s, lg, (const PairPart *)part, nf, p0 / lg.M, rows_dev,
+                       counts_dev);
+}
+
+extern "C" int dgdm_squeeze_label(const DgdmSqueezeConfig *cfg, const double *surfaces_dev, int n_fingers, int num_points, const double *bank_dev,
+                                  int n_bank, int num_vertices, const int32_t *objects_host, int n_objects, const double *rot_dev,
+                                  const double *starts_dev, int n_tally, int n_settle, double mu, const double threshold[3],
+                                  const double score_std[3], double pos_norm, int row_layout, float *rows_dev, int64_t row_stride, int column_offset,
+                                  int object_stride, int32_t *counts_dev, void *workspace_dev, int64_t workspace_bytes, void *stream) {
+    const char *fn = "dgdm_squeeze_label";
+    const char *bytes_fn = "dgdm_squeeze_label_workspace_bytes";
+    DGDM_REQUIRE(std::isfinite(mu) && mu >= 0.0, DGDM_EINVAL, "%s: friction coefficient %g (need finite, >= 0)", fn, mu);
+    int rc = check_sizes_2d(fn, num_points, num_vertices);
+    if (rc || (rc = check_label_objects(fn, n_objects))) return rc;
+    LabelGrid lg;
+    std::vector<int32_t> pairs;
+    if ((rc = label_front(fn, n_fingers, n_bank, objects_host, n_objects, starts_dev, n_tally, n_settle, threshold, score_std, pos_norm, row_layout,
+                          rows_dev, row_stride, column_offset, object_stride, lg, pairs)))
+        return rc;
+    const bool friction = mu > 0.0;
+    const int n_pairs = n_fingers * n_objects;
+    const Outputs out = {};
+    if ((rc = check_map_args(fn, cfg, surfaces_dev && bank_dev && rot_dev, true, n_fingers, n_bank, pairs.data(), n_pairs, nullptr, 0, out, workspace_dev,
+                             workspace_bytes, friction, label_extra(1), bytes_fn)))
+        return rc;
+    int64_t fingers;
+    if ((rc = label_chunk_fingers(fn, bytes_fn, cfg, n_fingers, n_objects, friction, workspace_bytes, 0, fingers))) return rc;
+    const int64_t cap = fingers * n_objects;
+    const size_t extra = label_extra(cap);
+
+    const Grid g = grid_2d(cfg, num_points, num_vertices);
+    lg.dth = TWO_PI / (double)g.T;
     uint8_t *ws = static_cast<uint8_t *>(workspace_dev);                  // the partials in front, the chunk's tables behind them
     PairPart *part = reinterpret_cast<PairPart *>(ws);
     return run_chunks(
@@ -989,10 +1155,7 @@ extern "C" int dgdm_squeeze_label(const DgdmSqueezeConfig *cfg, const double *su
             launch_table(friction, g, surfaces_dev, bank_dev, prs, rot_dev, tl, tr, S, mu, jam, nullptr, n, s);
         },
         [&](unsigned n, int64_t p0, const double *tl, const double *tr, const double *S, const int32_t *closed, const int32_t *fix, hipStream_t s) {
-            const int nf = (int)(n / (unsigned)n_objects);                // cap and n_pairs are whole fingers: so is every chunk
-            hipLaunchKernelGGL(label_pair_kernel, dim3(n), dim3(64), 0, s, g, lg, starts_dev, rot_dev, tl, tr, S, closed, fix, part);
-            hipLaunchKernelGGL(label_rows_kernel, dim3((unsigned)((nf + 63) / 64)), dim3(64), 0, s, lg, (const PairPart *)part, nf,
-                               p0 / n_objects, rows_dev, counts_dev);
+            launch_label(g, lg, n, p0, starts_dev, rot_dev, tl, tr, S, closed, fix, part, rows_dev, counts_dev, s);
         },
         cap);
 }
@@ -1097,6 +1260,30 @@ extern "C" int dgdm_squeeze_slice(const double *verts_host, const int64_t *vert_
     return DGDM_OK;
 }
 
+// What the two 3-D entries check of the slices they are handed, and how they put gx and the level offsets into the workspace's first
+// bytes (extra3).
+static int check_slices(const char *fn, const double *segments_dev, int64_t n_segments, const int32_t *seg_offsets_host, int n_objects, int mv) {
+    DGDM_REQUIRE(n_segments >= 0 && n_segments <= INT32_MAX && (segments_dev || n_segments == 0), DGDM_EINVAL, "%s: %lld segments with%s segments_dev",
+                 fn, (long long)n_segments, segments_dev ? "" : " no");
+    const size_t nl1 = (size_t)n_objects * (size_t)(mv + 1);
+    DGDM_REQUIRE(seg_offsets_host[0] == 0, DGDM_EINVAL, "%s: seg_offsets start at %d (need 0)", fn, seg_offsets_host[0]);
+    for (size_t i = 1; i < nl1; ++i)
+        DGDM_REQUIRE(seg_offsets_host[i] >= seg_offsets_host[i - 1], DGDM_EINVAL, "%s: seg_offsets descend at %lld (%d after %d)", fn, (long long)i,
+                     seg_offsets_host[i], seg_offsets_host[i - 1]);
+    DGDM_REQUIRE(seg_offsets_host[nl1 - 1] <= n_segments, DGDM_EINVAL, "%s: seg_offsets end at %d, past the %lld segments", fn,
+                 seg_offsets_host[nl1 - 1], (long long)n_segments);
+    return DGDM_OK;
+}
+
+static int upload_extra3(const Extra3 &e, uint8_t *ws, const double *gx_host, int mu, const int32_t *seg_offsets_host, int n_objects, int mv,
+                         hipStream_t s, double *&gx, int32_t *&offs) {
+    gx = reinterpret_cast<double *>(ws + e.gx);
+    offs = reinterpret_cast<int32_t *>(ws + e.off);
+    DGDM_HIP_CHECK(hipMemcpyAsync(gx, gx_host, sizeof(double) * mu, hipMemcpyHostToDevice, s));
+    DGDM_HIP_CHECK(hipMemcpyAsync(offs, seg_offsets_host, sizeof(int32_t) * (size_t)n_objects * (size_t)(mv + 1), hipMemcpyHostToDevice, s));
+    return DGDM_OK;
+}
+
 extern "C" int64_t dgdm_squeeze_map_3d_workspace_bytes(const DgdmSqueezeConfig *cfg, int chunk_pairs, int mu, int mv, int n_objects) {
     const char *fn = "dgdm_squeeze_map_3d_workspace_bytes";
     if (check_sizes_3d(mu, mv, n_objects, fn)) return DGDM_EINVAL;
@@ -1117,21 +1304,12 @@ extern "C" int dgdm_squeeze_map_3d(const DgdmSqueezeConfig *cfg, const double *s
                              starts_dev, n_starts, out, workspace_dev, workspace_bytes, false, e.bytes, "dgdm_squeeze_map_3d_workspace_bytes")) ||
         (rc = check_ascending(gx_host, mu, "gx", fn)))
         return rc;
-    DGDM_REQUIRE(n_segments >= 0 && n_segments <= INT32_MAX && (segments_dev || n_segments == 0), DGDM_EINVAL, "%s: %lld segments with%s segments_dev",
-                 fn, (long long)n_segments, segments_dev ? "" : " no");
-    const size_t nl1 = (size_t)n_objects * (size_t)(mv + 1);
-    DGDM_REQUIRE(seg_offsets_host[0] == 0, DGDM_EINVAL, "%s: seg_offsets start at %d (need 0)", fn, seg_offsets_host[0]);
-    for (size_t i = 1; i < nl1; ++i)
-        DGDM_REQUIRE(seg_offsets_host[i] >= seg_offsets_host[i - 1], DGDM_EINVAL, "%s: seg_offsets descend at %lld (%d after %d)", fn, (long long)i,
-                     seg_offsets_host[i], seg_offsets_host[i - 1]);
-    DGDM_REQUIRE(seg_offsets_host[nl1 - 1] <= n_segments, DGDM_EINVAL, "%s: seg_offsets end at %d, past the %lld segments", fn,
-                 seg_offsets_host[nl1 - 1], (long long)n_segments);
+    if ((rc = check_slices(fn, segments_dev, n_segments, seg_offsets_host, n_objects, mv))) return rc;
     uint8_t *ws = static_cast<uint8_t *>(workspace_dev);                  // the extra block in front, the chunks' tables behind it
-    double *gx = reinterpret_cast<double *>(ws + e.gx);
-    int32_t *offs = reinterpret_cast<int32_t *>(ws + e.off);
     hipStream_t s = (hipStream_t)stream;
-    DGDM_HIP_CHECK(hipMemcpyAsync(gx, gx_host, sizeof(double) * mu, hipMemcpyHostToDevice, s));
-    DGDM_HIP_CHECK(hipMemcpyAsync(offs, seg_offsets_host, sizeof(int32_t) * nl1, hipMemcpyHostToDevice, s));
+    double *gx;
+    int32_t *offs;
+    if ((rc = upload_extra3(e, ws, gx_host, mu, seg_offsets_host, n_objects, mv, s, gx, offs))) return rc;
     const Grid g = grid_of(cfg);
     Grid3 g3 = {g.T, g.X, mu, mv, g.x_half, g.dx};
     const size_t lds = sizeof(double) * (size_t)(2 * mu * mv + mu + 4 * SEG_TILE) + sizeof(int32_t) * (size_t)(mv + 1);
@@ -1140,4 +1318,67 @@ extern "C" int dgdm_squeeze_map_3d(const DgdmSqueezeConfig *cfg, const double *s
                           hipLaunchKernelGGL(table3d_kernel, dim3((unsigned)g3.T, n), dim3(TABLE_THREADS), lds, st, g3, surfaces_dev, gx, segments_dev,
                                              offs, pairs, rot_dev, tl, tr, S);
                       });
+}
+
+extern "C" int64_t dgdm_squeeze_label_3d_workspace_bytes(const DgdmSqueezeConfig *cfg, int chunk_fingers, int n_objects, int mu, int mv, int n_bank) {
+    const char *fn = "dgdm_squeeze_label_3d_workspace_bytes";
+    if (check_sizes_3d(mu, mv, n_bank, fn) || check_label_objects(fn, n_objects)) return DGDM_EINVAL;
+    DGDM_REQUIRE(chunk_fingers >= 1 && (int64_t)chunk_fingers * n_objects <= MAX_CHUNK, DGDM_EINVAL,
+                 "%s: %d fingers of %d objects per chunk (need >= 1 finger, at most %d pairs)", fn, chunk_fingers, n_objects, MAX_CHUNK);
+    const int chunk_pairs = chunk_fingers * n_objects;
+    return workspace_bytes_of(fn, cfg, chunk_pairs, false, extra3(mu, mv, n_bank).bytes + label_extra(chunk_pairs));
+}
+
+extern "C" int dgdm_squeeze_label_3d(const DgdmSqueezeConfig *cfg, const double *surfaces_dev, int n_fingers, const double *gx_host, int mu, int mv,
+                                     const double *segments_dev, int64_t n_segments, const int32_t *seg_offsets_host, int n_bank,
+                                     const int32_t *objects_host, int n_objects, const double *rot_dev, const double *starts_dev, int n_tally,
+                                     int n_settle, const double threshold[3], const double score_std[3], double pos_norm, int row_layout,
+                                     float *rows_dev, int64_t row_stride, int column_offset, int object_stride, int32_t *counts_dev,
+                                     double *table_s_dev, double *touch_l_dev, double *touch_r_dev, void *workspace_dev, int64_t workspace_bytes,
+                                     void *stream) {
+    const char *fn = "dgdm_squeeze_label_3d";
+    const char *bytes_fn = "dgdm_squeeze_label_3d_workspace_bytes";
+    int rc = check_sizes_3d(mu, mv, n_bank, fn);
+    if (rc || (rc = check_label_objects(fn, n_objects))) return rc;
+    LabelGrid lg;
+    std::vector<int32_t> pairs;
+    if ((rc = label_front(fn, n_fingers, n_bank, objects_host, n_objects, starts_dev, n_tally, n_settle, threshold, score_std, pos_norm, row_layout,
+                          rows_dev, row_stride, column_offset, object_stride, lg, pairs)))
+        return rc;
+    const int n_pairs = n_fingers * n_objects;
+    const Extra3 e = extra3(mu, mv, n_bank);
+    Outputs out = {};
+    out.S = table_s_dev;
+    out.tl = touch_l_dev;
+    out.tr = touch_r_dev;
+    if ((rc = check_map_args(fn, cfg, surfaces_dev && gx_host && seg_offsets_host && rot_dev, false, n_fingers, n_bank, pairs.data(), n_pairs, nullptr, 0,
+                             out, workspace_dev, workspace_bytes, false, e.bytes + label_extra(1), bytes_fn)) ||
+        (rc = check_ascending(gx_host, mu, "gx", fn)) || (rc = check_slices(fn, segments_dev, n_segments, seg_offsets_host, n_bank, mv)))
+        return rc;
+    int64_t fingers;
+    if ((rc = label_chunk_fingers(fn, bytes_fn, cfg, n_fingers, n_objects, false, workspace_bytes, e.bytes, fingers))) return rc;
+    const int64_t cap = fingers * n_objects;
+    const size_t front = e.bytes + label_extra(cap);                      // gx and the offsets, then the partials, then the chunk's tables
+
+    uint8_t *ws = static_cast<uint8_t *>(workspace_dev);
+    hipStream_t s = (hipStream_t)stream;
+    double *gx;
+    int32_t *offs;
+    if ((rc = upload_extra3(e, ws, gx_host, mu, seg_offsets_host, n_bank, mv, s, gx, offs))) return rc;
+    PairPart *part = reinterpret_cast<PairPart *>(ws + e.bytes);
+    const Grid g = grid_of(cfg);
+    lg.dth = TWO_PI / (double)g.T;
+    Grid3 g3 = {g.T, g.X, mu, mv, g.x_half, g.dx};
+    const size_t lds = sizeof(double) * (size_t)(mu * LABEL3_ENTRY + mu + 4 * FSEG_TILE) + sizeof(int32_t) * (size_t)(mv + 1);
+    return run_chunks(
+        cfg, g, pairs.data(), n_pairs, nullptr, 0, out, ws + front, workspace_bytes - (int64_t)front, s, false,
+        [&](unsigned n, int64_t, const int32_t *prs, double *tl, double *tr, double *S, int32_t *, hipStream_t st) {
+            const int nf = (int)(n / (unsigned)n_objects);                // cap and n_pairs are whole fingers: so is every chunk
+            hipLaunchKernelGGL(table3d_fingers_kernel, dim3((unsigned)g3.T, (unsigned)n_objects, (unsigned)((nf + LABEL3_FB - 1) / LABEL3_FB)),
+                               dim3(TABLE_THREADS), lds, st, g3, n_objects, nf, surfaces_dev, gx, segments_dev, offs, prs, rot_dev, tl, tr, S);
+        },
+        [&](unsigned n, int64_t p0, const double *tl, const double *tr, const double *S, const int32_t *closed, const int32_t *fix, hipStream_t st) {
+            launch_label(g, lg, n, p0, starts_dev, rot_dev, tl, tr, S, closed, fix, part, rows_dev, counts_dev, st);
+        },
+        cap);
 }

@@ -80,9 +80,10 @@ _FLAGS = [
     ("label_rollout", int, 0, "with --mode=label: K > 0 adds the five settled columns of a predicted roll-out of K interactions"),
     ("label_source", str, "model", "with --mode=label: 'model' (the dynamics model's predictions; needs --classifier_guidance) or 'squeeze' (the squeeze "
                                    "simulator's closings, sim/squeeze.py: 2-D only, needs no dynamics model and no checkpoint; frictionless unless "
-                                   "--squeeze_friction; honours --squeeze_closing_steps / --squeeze_window; its own model, not MuJoCo's)"),
-    ("label_settled", "flag", None, "with --label_source squeeze: add the five settled columns, from the start orientations run until they settle"),
-    ("label_squeeze_cells", str, None, "with --label_source squeeze: the squeeze table's theta,x cells as T,X (default: the squeeze defaults)"),
+                                   "--squeeze_friction; honours --squeeze_closing_steps / --squeeze_window; its own model, not MuJoCo's) or 'squeeze_3d' "
+                                   "(the sliced squeeze of --fingers_3d on <object_dir>/<name>/model.obj; frictionless only)"),
+    ("label_settled", "flag", None, "with --label_source squeeze / squeeze_3d: add the five settled columns, from the start orientations run until they settle"),
+    ("label_squeeze_cells", str, None, "with --label_source squeeze / squeeze_3d: the squeeze table's theta,x cells as T,X (default: the squeeze defaults)"),
     ("cond_stats", str, None, "generator, --mode=test: the FILE.json a labelling run wrote; with --cond_target the eps-net is built with its width"),
     ("cond_target", str, None, "with --cond_stats: NAME=VALUE,... in raw units (e.g. frac_clockwise=0.9,frac_up=0.7); every batch is sampled under "
                                "that condition row, columns not named at the dataset mean"),

@@ -1201,6 +1201,53 @@ def squeeze_tables(surfaces, objects, pairs, starts=None, rot=None, tables: bool
 LABEL_LAYOUTS = {"mean": 0, "per_object": 1}        # DGDM_LABEL_MEAN / DGDM_LABEL_PER_OBJECT
 
 
+def _squeeze_label_front(who: str, cfg, f64, sf, objects, starts, n_tally, threshold, score_std, pos_norm, layout, rot, out, column_offset,
+                         object_stride, counts, workspace_bytes, sizer):
+    """What squeeze_label and squeeze_label_3d (`who`) do alike once their own inputs are on the device (sf: the surfaces, fingers
+    leading).  sizer(n, M): the entry's *_workspace_bytes for chunks of n fingers of M objects.  -> (out, counts, (objects int32, M, rot,
+    starts, n_tally, n_settle), the entries' common arguments from threshold to counts_dev, (workspace, its bytes, what `tail` points to)).  Without
+    workspace_bytes the workspace holds as many fingers as fit SQUEEZE_WORKSPACE_BYTES, at least one, never more than the call has."""
+    if layout not in LABEL_LAYOUTS:
+        raise ValueError(f"{who}: layout {layout!r} not supported ({' or '.join(LABEL_LAYOUTS)})")
+    st = f64(starts).reshape(-1, 3)
+    oi = np.ascontiguousarray(objects, dtype=np.int32).reshape(-1)
+    F, M, nt = int(sf.shape[0]), len(oi), int(n_tally)
+    ns = int(st.shape[0]) - nt
+    if pos_norm is None:
+        from .dynamics.dataloader import POS_NORM
+        pos_norm = POS_NORM
+    if len(threshold) != 3 or len(score_std) != 3:
+        raise ValueError(f"{who}: threshold and score_std hold three entries (theta, x, y)")
+    cols = 10 + (5 if ns > 0 else 0)
+    per_object = layout == "per_object"
+    stride = cols if object_stride is None else int(object_stride)
+    width = int(column_offset) + ((M - 1) * stride if per_object else 0) + cols
+    if out is None:
+        out = torch.empty((F, width), dtype=torch.float32, device=sf.device)
+    if not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype == torch.float32 and out.dim() == 2 and out.shape[0] == F and out.shape[1] >= width
+            and out.stride(1) == 1):
+        raise ValueError(f"{who}: out must be a float32 device tensor ({F}, >= {width}) with unit column stride")
+    T = cfg.theta_cells
+    rt = f64(squeeze_rotation_table(T) if rot is None else rot)
+    if rt.shape != (T, 2):
+        raise ValueError(f"{who}: rot of shape {tuple(rt.shape)} (need ({T}, 2))")
+    fit = int(sizer(min(max(F, 1), max(65535 // max(M, 1), 1)), M))      # all fingers in one chunk; negative: what the library refuses
+    if fit < 0:
+        _check_value(fit)
+    if workspace_bytes is not None:
+        ws_bytes = int(workspace_bytes)
+    elif fit <= SQUEEZE_WORKSPACE_BYTES:
+        ws_bytes = fit
+    else:                                           # the library cuts the budget into chunks of as many fingers as fit it
+        ws_bytes = max(SQUEEZE_WORKSPACE_BYTES, int(sizer(1, M)))
+    ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=sf.device)
+    cnt = torch.empty((F, 3), dtype=torch.int32, device=sf.device) if counts else None
+    thr = (C.c_double * 3)(*[float(v) for v in threshold])
+    std = (C.c_double * 3)(*[float(v) for v in score_std])
+    tail = (thr, std, float(pos_norm), LABEL_LAYOUTS[layout], out.data_ptr(), int(out.stride(0)), int(column_offset), stride, dptr(cnt))
+    return out, cnt, (oi, M, rt, st, nt, ns), tail, (ws, ws_bytes, thr, std)
+
+
 def squeeze_label(surfaces, bank, objects: Sequence[int], starts, n_tally: int, threshold: Sequence[float], score_std: Sequence[float],
                   pos_norm: Optional[float] = None, layout: str = "mean", friction: float = 0.0, rot=None, out: Optional[torch.Tensor] = None,
                   column_offset: int = 0, object_stride: Optional[int] = None, counts: bool = True, workspace_bytes: Optional[int] = None,
@@ -1219,50 +1266,16 @@ def squeeze_label(surfaces, bank, objects: Sequence[int], starts, n_tally: int, 
     from .sim.squeeze import check_friction
     cfg = squeeze_config(**config)
     mu = check_friction(friction, "squeeze_label")
-    if layout not in LABEL_LAYOUTS:
-        raise ValueError(f"squeeze_label: layout {layout!r} not supported ({' or '.join(LABEL_LAYOUTS)})")
     f64 = _squeeze_mover()
-    sf, ob, st = f64(surfaces), f64(bank), f64(starts).reshape(-1, 3)
+    sf, ob = f64(surfaces), f64(bank)
     if sf.dim() != 3 or sf.shape[1] != 2 or ob.dim() != 3 or ob.shape[2] != 2:
         raise ValueError(f"squeeze_label: surfaces (F, 2, m) and bank (O, nv, 2) expected, got {tuple(sf.shape)} and {tuple(ob.shape)}")
-    oi = np.ascontiguousarray(objects, dtype=np.int32).reshape(-1)
-    F, M, nt = int(sf.shape[0]), len(oi), int(n_tally)
-    ns = int(st.shape[0]) - nt
-    if pos_norm is None:
-        from .dynamics.dataloader import POS_NORM
-        pos_norm = POS_NORM
-    if len(threshold) != 3 or len(score_std) != 3:
-        raise ValueError("squeeze_label: threshold and score_std hold three entries (theta, x, y)")
-    cols = 10 + (5 if ns > 0 else 0)
-    per_object = layout == "per_object"
-    stride = cols if object_stride is None else int(object_stride)
-    width = int(column_offset) + ((M - 1) * stride if per_object else 0) + cols
-    if out is None:
-        out = torch.empty((F, width), dtype=torch.float32, device=sf.device)
-    if not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype == torch.float32 and out.dim() == 2 and out.shape[0] == F and out.shape[1] >= width
-            and out.stride(1) == 1):
-        raise ValueError(f"squeeze_label: out must be a float32 device tensor ({F}, >= {width}) with unit column stride")
-    T = cfg.theta_cells
-    rt = f64(squeeze_rotation_table(T) if rot is None else rot)
-    if rt.shape != (T, 2):
-        raise ValueError(f"squeeze_label: rot of shape {tuple(rt.shape)} (need ({T}, 2))")
-    sizer = lambda n: int(lib().dgdm_squeeze_label_workspace_bytes(C.byref(cfg), n, M, int(mu > 0.0)))      # noqa: E731
-    fit = sizer(min(max(F, 1), max(65535 // max(M, 1), 1)))       # all fingers in one chunk; negative: what the library refuses
-    if fit < 0:
-        _check_value(fit)
-    if workspace_bytes is not None:
-        ws_bytes = int(workspace_bytes)
-    elif fit <= SQUEEZE_WORKSPACE_BYTES:
-        ws_bytes = fit
-    else:                                           # the library cuts the budget into chunks of as many fingers as fit it
-        ws_bytes = max(SQUEEZE_WORKSPACE_BYTES, sizer(1))
-    ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=sf.device)
-    cnt = torch.empty((F, 3), dtype=torch.int32, device=sf.device) if counts else None
-    thr = (C.c_double * 3)(*[float(v) for v in threshold])
-    std = (C.c_double * 3)(*[float(v) for v in score_std])
-    _check_value(lib().dgdm_squeeze_label(C.byref(cfg), dptr(sf), F, int(sf.shape[2]), dptr(ob), int(ob.shape[0]), int(ob.shape[1]), oi.ctypes.data, M,
-                                          dptr(rt), dptr(st), nt, ns, mu, thr, std, float(pos_norm), LABEL_LAYOUTS[layout], out.data_ptr(),
-                                          int(out.stride(0)), int(column_offset), stride, dptr(cnt), dptr(ws), ws_bytes, stream_ptr()))
+    out, cnt, head, tail, keep = _squeeze_label_front("squeeze_label", cfg, f64, sf, objects, starts, n_tally, threshold, score_std, pos_norm, layout, rot,
+                                                      out, column_offset, object_stride, counts, workspace_bytes,
+                                                      lambda n, M: lib().dgdm_squeeze_label_workspace_bytes(C.byref(cfg), n, M, int(mu > 0.0)))
+    oi, M, rt, st, nt, ns = head
+    _check_value(lib().dgdm_squeeze_label(C.byref(cfg), dptr(sf), int(sf.shape[0]), int(sf.shape[2]), dptr(ob), int(ob.shape[0]), int(ob.shape[1]),
+                                          oi.ctypes.data, M, dptr(rt), dptr(st), nt, ns, mu, *tail, dptr(keep[0]), keep[1], stream_ptr()))
     return out, cnt
 
 
@@ -1350,6 +1363,37 @@ def squeeze_tables_3d(surfaces, gx, segments, offsets, pairs, starts=None, rot=N
     _check_value(lib().dgdm_squeeze_map_3d(C.byref(cfg), dptr(sf), int(sf.shape[0]), g.ctypes.data, mu, mv, dptr(sg) if len(sg) else None, int(len(sg)),
                                            of.ctypes.data, O, *tail))
     return out
+
+
+def squeeze_label_3d(surfaces, gx, segments, offsets, objects: Sequence[int], starts, n_tally: int, threshold: Sequence[float],
+                     score_std: Sequence[float], pos_norm: Optional[float] = None, layout: str = "mean", rot=None, out: Optional[torch.Tensor] = None,
+                     column_offset: int = 0, object_stride: Optional[int] = None, counts: bool = True, tables: bool = False,
+                     workspace_bytes: Optional[int] = None, **config):
+    """dgdm_squeeze_label_3d (include/dgdm_hip.h "squeeze-simulator labels, 3-D fingers", DESIGN.md §4.1b "source: squeeze_3d") on the
+    current device: squeeze_label's rows for 3-D fingers from the sliced squeeze.  surfaces (F, 2, mv, mu) float64, gx (mu,), segments
+    (n, 4) / offsets (O, mv + 1): squeeze_tables_3d's (the bank is the O sliced meshes); objects: M indices into the bank; everything
+    else, the workspace rule and (rows, counts) as squeeze_label - there is no friction.  tables=True -> (rows, counts, tables): S /
+    touch_l / touch_r (F * M, theta_cells, x_cells) float64 of every pair, finger-major, for comparison with squeeze_tables_3d's.
+    Synchronises the stream once."""
+    cfg = squeeze_config(**config)
+    f64 = _squeeze_mover()
+    sf, sg = f64(surfaces), f64(segments).reshape(-1, 4)
+    g = np.ascontiguousarray(gx, dtype=np.float64).reshape(-1)
+    of = np.ascontiguousarray(offsets, dtype=np.int32)
+    if sf.dim() != 4 or sf.shape[1] != 2 or sf.shape[3] != len(g) or of.ndim != 2 or of.shape[1] != sf.shape[2] + 1:
+        raise ValueError(f"squeeze_label_3d: surfaces (F, 2, mv, mu), gx (mu,) and offsets (O, mv + 1) expected, got {tuple(sf.shape)}, "
+                         f"{g.shape} and {of.shape}")
+    mu, mv, O = int(sf.shape[3]), int(sf.shape[2]), int(of.shape[0])
+    out, cnt, head, tail, keep = _squeeze_label_front("squeeze_label_3d", cfg, f64, sf, objects, starts, n_tally, threshold, score_std, pos_norm, layout,
+                                                      rot, out, column_offset, object_stride, counts, workspace_bytes,
+                                                      lambda n, M: lib().dgdm_squeeze_label_3d_workspace_bytes(C.byref(cfg), n, M, mu, mv, O))
+    oi, M, rt, st, nt, ns = head
+    shape = (int(sf.shape[0]) * M, cfg.theta_cells, cfg.x_cells)
+    tab = {k: torch.empty(shape, dtype=torch.float64, device=sf.device) for k in ("S", "touch_l", "touch_r")} if tables else {}
+    _check_value(lib().dgdm_squeeze_label_3d(C.byref(cfg), dptr(sf), int(sf.shape[0]), g.ctypes.data, mu, mv, dptr(sg) if len(sg) else None, int(len(sg)),
+                                             of.ctypes.data, O, oi.ctypes.data, M, dptr(rt), dptr(st), nt, ns, *tail, dptr(tab.get("S")),
+                                             dptr(tab.get("touch_l")), dptr(tab.get("touch_r")), dptr(keep[0]), keep[1], stream_ptr()))
+    return (out, cnt, tab) if tables else (out, cnt)
 
 
 def prof_enable(on: bool) -> None:

@@ -690,7 +690,7 @@ class Diffusion(nn.Module):
         unless the statistics' rows were made by the squeeze simulator, which then also scores the samples (_cond_target_report_squeeze)."""
         from .. import label as lb
         stats, requested = self.cond_target
-        if stats.source == 'squeeze':
+        if stats.source in ('squeeze', 'squeeze_3d'):
             return self._cond_target_report_squeeze(stats, requested, unguided, rank0)
         rep: Dict[str, Any] = {"columns": list(stats.columns), "requested": dict(requested), "achieved_mean": None, "achieved_std": None,
                                "baseline_mean": stats.mean.copy(), "predicted": True}
@@ -715,7 +715,8 @@ class Diffusion(nn.Module):
         return rep
 
     def _cond_target_report_squeeze(self, stats, requested, unguided, rank0: bool) -> Dict[str, Any]:
-        """The report for statistics whose rows the squeeze simulator made (label.label_fingers_squeeze): the unguided samples labelled
+        """The report for statistics whose rows the squeeze simulator made (label.label_fingers_squeeze, or label_fingers_squeeze_3d for
+        source 'squeeze_3d', on <object_mesh_dir>/<name>/model.obj): the unguided samples labelled
         by the same simulator under the stored recipe - grid, thresholds, config, friction - against the run's objects.  No dynamics
         model takes part: 'simulated': 'squeeze' and no 'predicted' key.  The squeeze model's opinion, not MuJoCo's."""
         from .. import label as lb
@@ -727,16 +728,30 @@ class Diffusion(nn.Module):
             if rank0:
                 print("[dgdm_amd] --cond_target: no objects in this run: the achieved values were not scored", flush=True)
             return rep
-        if self.mode == 'point_3d':
-            raise ValueError("cond target: rows labelled by the squeeze simulator belong to 2-D fingers")
+        three_d = stats.source == 'squeeze_3d'
+        if (self.mode == 'point_3d') != three_d:
+            raise ValueError("cond target: rows labelled by the squeeze simulator belong to 2-D fingers" if not three_d else
+                             "cond target: rows labelled by the sliced squeeze belong to 3-D fingers")
         objs = torch.as_tensor(objects)
         r, M = stats.recipe, objs.shape[0]
         if M != len(stats.object_ids):
             raise ValueError(f"cond target: the rows were labelled against {len(stats.object_ids)} objects, this run has {M}")
-        bank = objs.detach().cpu().double() * OBJECT_HALF_BOX_2D          # the bank SqueezeSimulator builds
-        raw, _ = lb.label_fingers_squeeze(unguided.detach(), bank, list(range(M)), r["G"], r["P"], r.get("ori_range") or [-1.0, 1.0], r["threshold"],
-                                          r["score_std"], settled=bool(r.get("settled")), layout=stats.layout, friction=float(r.get("friction") or 0.0),
-                                          **(r.get("squeeze_config") or {}))
+        common = dict(settled=bool(r.get("settled")), layout=stats.layout, **(r.get("squeeze_config") or {}))
+        grid = (r["G"], r["P"], r.get("ori_range") or [-1.0, 1.0], r["threshold"], r["score_std"])
+        if three_d:                                                        # label.label_fingers_squeeze_3d on the run's mesh files
+            import os
+            from .. import engine
+            from ..dynamics.utils import MESH_FILE
+            from ..sim.squeeze import NO_MESHES_3D
+            mesh_dir = getattr(self, "object_mesh_dir", None)
+            if not mesh_dir:
+                raise ValueError(f"cond target: {NO_MESHES_3D}")
+            meshes = [engine.read_obj(os.path.join(mesh_dir, str(n), MESH_FILE)) for n in self._object_ids()]
+            raw, _ = lb.label_fingers_squeeze_3d(unguided.detach(), meshes, list(range(M)), *grid, sample_size=int(r.get("sample_size") or 25),
+                                                 width=r.get("width"), **common)
+        else:
+            bank = objs.detach().cpu().double() * OBJECT_HALF_BOX_2D      # the bank SqueezeSimulator builds
+            raw, _ = lb.label_fingers_squeeze(unguided.detach(), bank, list(range(M)), *grid, friction=float(r.get("friction") or 0.0), **common)
         raw = raw.cpu().numpy().astype(np.float64)
         rep["achieved_mean"], rep["achieved_std"] = raw.mean(axis=0), raw.std(axis=0)
         if rank0:

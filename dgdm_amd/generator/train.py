@@ -109,7 +109,7 @@ def check_label_flags(args):
     target, stats_path = getattr(args, "cond_target", None), getattr(args, "cond_stats", None)
     source = getattr(args, "label_source", None) or 'model'
     if (getattr(args, "label_settled", False) or getattr(args, "label_squeeze_cells", None) is not None) and \
-            not (args.mode == 'label' and source == 'squeeze'):
+            not (args.mode == 'label' and source in ('squeeze', 'squeeze_3d')):
         raise ValueError("--label_settled / --label_squeeze_cells need --mode=label --label_source squeeze")
     if source != 'model' and args.mode != 'label':
         raise ValueError("--label_source needs --mode=label")
@@ -117,7 +117,7 @@ def check_label_flags(args):
         if not args.label_out:
             raise ValueError("--mode=label needs --label_out FILE.npy")
         if source not in lb.SOURCES:
-            raise ValueError(f"--label_source={source}: 'model' or 'squeeze'")
+            raise ValueError(f"--label_source={source}: 'model', 'squeeze' or 'squeeze_3d'")
         if source == 'squeeze':
             if args.fingers_3d:
                 raise ValueError("--label_source squeeze is 2-D only: a sliced squeeze evaluation per finger of a --fingers_3d dataset is out of "
@@ -125,6 +125,14 @@ def check_label_flags(args):
             if int(args.label_rollout) != 0:
                 raise ValueError("--label_rollout is the dynamics model's roll-out: with --label_source squeeze the settled columns are --label_settled")
             label_squeeze_config(args)          # --label_squeeze_cells / --squeeze_*: refused here
+        elif source == 'squeeze_3d':
+            if not args.fingers_3d:
+                raise ValueError("--label_source squeeze_3d needs --fingers_3d: it is the sliced squeeze of 3-D fingers (--label_source squeeze is "
+                                 "the 2-D one)")
+            if int(args.label_rollout) != 0:
+                raise ValueError("--label_rollout is the dynamics model's roll-out: with --label_source squeeze_3d the settled columns are "
+                                 "--label_settled")
+            label_squeeze_config(args)          # --label_squeeze_cells / --squeeze_*: refused here (--squeeze_friction: squeeze_friction_from_args)
         elif not args.classifier_guidance:
             raise ValueError("--mode=label needs --classifier_guidance and its flags: the labels are the dynamics model's predictions "
                              "(--label_source squeeze needs neither)")
@@ -154,6 +162,9 @@ def check_label_flags(args):
     if stats.source == 'squeeze':               # the report labels the samples on the recipe's own grid, whatever this run's is
         if args.fingers_3d:
             raise ValueError("--cond_stats: the rows were labelled by the squeeze simulator, which is 2-D only (--fingers_3d)")
+    elif stats.source == 'squeeze_3d':          # likewise, by the sliced squeeze on the run's mesh files
+        if not args.fingers_3d:
+            raise ValueError("--cond_stats: the rows were labelled by the sliced squeeze of 3-D fingers: the run needs --fingers_3d")
     elif args.classifier_guidance:
         r = stats.recipe
         if r.get("G") != args.grid_size or r.get("P") != args.num_pos:
@@ -180,6 +191,27 @@ def label_squeeze_config(args):
     return config, 0.0 if mu is None else check_friction(mu, "--squeeze_friction")
 
 
+def _save_squeeze_labels(args, raw, counts, recipe, object_ids, by: str):
+    """What the two squeeze sources do with their raw rows alike: the statistics, label_dataset's three files, and the line that says how
+    many tally starts were loose or cut.  `by`: who made the rows, for that line.  Returns (stats, raw)."""
+    from .. import label as lb
+    layout, settled, M = args.label_layout, bool(recipe["settled"]), len(object_ids)
+    stats = lb.LabelStats(lb.column_names(layout, object_ids, int(settled)), layout, object_ids, recipe).fit(raw)
+    stem = args.label_out[:-4] if args.label_out.endswith(".npy") else args.label_out
+    if os.path.dirname(stem):
+        os.makedirs(os.path.dirname(stem), exist_ok=True)
+    np.save(stem + ".npy", stats.apply(raw))
+    np.save(stem + "_raw.npy", raw)
+    stats.save(stem + ".json")
+    flat = [c for c, k in zip(stats.columns, stats.constant) if k]
+    n_starts = raw.shape[0] * M * args.grid_size * args.num_pos ** 2
+    print(f"[dgdm_amd] labelled {raw.shape[0]} fingers x {raw.shape[1]} columns by {by}"
+          f"{', settled' if settled else ''}) -> {stem}.npy, {stem}_raw.npy, {stem}.json; of {n_starts} tally starts {int(counts[:, 0].sum())} were loose "
+          f"at the start, {int(counts[:, 1].sum())} ended loose, {int(counts[:, 2].sum())} were cut by the table's x range"
+          + (f"; constant columns (standardised to 0): {', '.join(flat)}" if flat else ""), flush=True)
+    return stats, raw
+
+
 def label_dataset_squeeze(args, dataset, objects, object_ids):
     """--mode=label --label_source squeeze: every dataset finger labelled by the squeeze simulator (label.label_fingers_squeeze) on the
     run's pose grid with the 2-D dataset's raw threshold and std; the same three files as label_dataset.  No dynamics model, no
@@ -201,20 +233,33 @@ def label_dataset_squeeze(args, dataset, objects, object_ids):
     full = {k: getattr(engine.squeeze_config(**config), k) for k in engine.SQUEEZE_DEFAULTS}
     recipe = {"G": args.grid_size, "P": args.num_pos, "ori_range": [-1.0, 1.0], "score_std": std, "source": SIMULATED, "squeeze_config": full,
               "friction": mu, "settled": settled, "threshold": thr}
-    stats = lb.LabelStats(lb.column_names(layout, object_ids, int(settled)), layout, object_ids, recipe).fit(raw)
-    stem = args.label_out[:-4] if args.label_out.endswith(".npy") else args.label_out
-    if os.path.dirname(stem):
-        os.makedirs(os.path.dirname(stem), exist_ok=True)
-    np.save(stem + ".npy", stats.apply(raw))
-    np.save(stem + "_raw.npy", raw)
-    stats.save(stem + ".json")
-    flat = [c for c, k in zip(stats.columns, stats.constant) if k]
-    n_starts = raw.shape[0] * M * args.grid_size * args.num_pos ** 2
-    print(f"[dgdm_amd] labelled {raw.shape[0]} fingers x {raw.shape[1]} columns by the squeeze simulator ({layout}, {M} objects, friction {mu:g}"
-          f"{', settled' if settled else ''}) -> {stem}.npy, {stem}_raw.npy, {stem}.json; of {n_starts} tally starts {int(counts[:, 0].sum())} were loose "
-          f"at the start, {int(counts[:, 1].sum())} ended loose, {int(counts[:, 2].sum())} were cut by the table's x range"
-          + (f"; constant columns (standardised to 0): {', '.join(flat)}" if flat else ""), flush=True)
-    return stats, raw
+    return _save_squeeze_labels(args, raw, counts, recipe, object_ids, f"the squeeze simulator ({layout}, {M} objects, friction {mu:g}")
+
+
+def label_dataset_squeeze_3d(args, dataset, object_ids, mesh_dir):
+    """--mode=label --label_source squeeze_3d: every finger of a --fingers_3d dataset labelled by the sliced squeeze
+    (label.label_fingers_squeeze_3d) on the run's pose grid against <mesh_dir>/<name>/model.obj, with the 3-D dataset's raw threshold and
+    std (SCORE_THRESHOLD[0] / SCORE_STD[0]); label_dataset's three files.  No dynamics model, no eps-net, no checkpoint.  The sliced
+    squeeze's opinion: this project's model, not MuJoCo's; blind between two levels of the finger grid; frictionless; steps, window and
+    thresholds untuned for squeeze deltas.  Returns (stats, raw)."""
+    from .. import engine
+    from .. import label as lb
+    from ..dynamics.dataloader import SCORE_STD, SCORE_THRESHOLD
+    from ..sim.squeeze import FINGER_WIDTH_3D, SIMULATED_3D
+    config, _ = label_squeeze_config(args)
+    M, layout, settled = len(object_ids), args.label_layout, bool(args.label_settled)
+    lb.cond_dim(layout, M, int(settled))
+    thr, std = [float(v) for v in SCORE_THRESHOLD[0]], [float(v) for v in SCORE_STD[0]]
+    fingers = np.stack([dataset[i] for i in range(len(dataset))])
+    meshes = [engine.read_obj(os.path.join(mesh_dir, str(n), object_utils.MESH_FILE)) for n in object_ids]
+    sample_size, width = 25, FINGER_WIDTH_3D
+    rows, counts = lb.label_fingers_squeeze_3d(torch.from_numpy(fingers), meshes, list(range(M)), args.grid_size, args.num_pos, (-1.0, 1.0), thr, std,
+                                               settled=settled, layout=layout, sample_size=sample_size, width=width, **config)
+    raw, counts = rows.cpu().numpy(), counts.cpu().numpy().astype(np.int64)
+    full = {k: getattr(engine.squeeze_config(**config), k) for k in engine.SQUEEZE_DEFAULTS}
+    recipe = {"G": args.grid_size, "P": args.num_pos, "ori_range": [-1.0, 1.0], "score_std": std, "source": SIMULATED_3D, "squeeze_config": full,
+              "sample_size": sample_size, "width": width, "settled": settled, "threshold": thr}
+    return _save_squeeze_labels(args, raw, counts, recipe, object_ids, f"the sliced squeeze of 3-D fingers ({layout}, {M} meshes")
 
 
 def _threshold_std(fingers_3d: bool):
@@ -455,8 +500,8 @@ def fit(model: Diffusion, pts: np.ndarray, args, bounds, dev) -> Diffusion:
 
 
 def _labels_by_squeeze(args) -> bool:
-    """--mode=label --label_source squeeze: a user of the --squeeze_* flags."""
-    return getattr(args, "mode", "test") == 'label' and (getattr(args, "label_source", None) or 'model') == 'squeeze'
+    """--mode=label --label_source squeeze / squeeze_3d: a user of the --squeeze_* flags (squeeze_3d: but for --squeeze_friction)."""
+    return getattr(args, "mode", "test") == 'label' and (getattr(args, "label_source", None) or 'model') in ('squeeze', 'squeeze_3d')
 
 
 def squeeze_friction_from_args(args):
@@ -469,6 +514,8 @@ def squeeze_friction_from_args(args):
     mu = check_friction(mu, "--squeeze_friction")
     if getattr(args, "squeeze_sim_3d", False):
         raise ValueError(f"--squeeze_friction with --squeeze_sim_3d: {FRICTION_2D_ONLY}")
+    if getattr(args, "mode", "test") == 'label' and getattr(args, "label_source", None) == 'squeeze_3d':
+        raise ValueError(f"--squeeze_friction with --label_source squeeze_3d: {FRICTION_2D_ONLY}")
     if not getattr(args, "squeeze_sim", False) and (getattr(args, "resample_potential", None) or 'model') != 'squeeze' and not _labels_by_squeeze(args):
         raise ValueError("--squeeze_friction needs --squeeze_sim or --resample_potential squeeze (or --mode=label --label_source squeeze)")
     return mu
@@ -530,6 +577,10 @@ def train(args):
         raise ValueError("--squeeze_sim_3d needs the run's objects as mesh files (<object_dir>/<name>/model.obj): objects.npy and synthetic "
                          "clouds have no cross-sections")
     cond_stats, cond_requested = check_label_flags(args)    # --mode=label, --cond_stats / --cond_target: refused here, before anything is built
+    label_3d = args.mode == 'label' and getattr(args, "label_source", None) == 'squeeze_3d'
+    if (label_3d or (cond_stats is not None and cond_stats.source == 'squeeze_3d')) and _object_mesh_dir(args) is None:
+        from ..sim.squeeze import NO_MESHES_3D
+        raise ValueError(f"{'--label_source squeeze_3d' if label_3d else '--cond_stats'}: {NO_MESHES_3D}")
     from ..edit import plan_from_args
     edit_plan = plan_from_args(args)        # --edit_from / --pin / --edit_band_mm / --edit_steps: read and checked before anything is built
     if edit_plan is not None and (args.mode != 'test' or not args.classifier_guidance):
@@ -545,6 +596,8 @@ def train(args):
     if args.mode == 'label' and (getattr(args, "label_source", None) or 'model') == 'squeeze':      # no eps-net, no dynamics model: objects alone
         objects, object_ids = _objects(args, False)
         return label_dataset_squeeze(args, dataset, objects, object_ids)
+    if label_3d:                            # likewise: the mesh files alone
+        return label_dataset_squeeze_3d(args, dataset, list(OBJECT_NAMES_3D), _object_mesh_dir(args))
     if args.mode == 'label':                # no eps-net: the dynamics model and the objects of --classifier_guidance alone
         classifier, objects, object_ids = _classifier(args, L, dev)
         return label_dataset(args, dataset, classifier, objects, object_ids, dev)
@@ -557,6 +610,8 @@ def train(args):
         classifier, objects, object_ids = _classifier(args, L, dev)
     elif cond_stats is not None and cond_stats.source == 'squeeze':
         objects, object_ids = _objects(args, False)     # the squeeze report's objects: the object flags without a dynamics model, for this only
+    elif cond_stats is not None and cond_stats.source == 'squeeze_3d':
+        objects, object_ids = _objects(args, True)      # the names the report reads <object_dir>/<name>/model.obj by
     if cond_stats is not None and objects is not None and objects.shape[0] != len(cond_stats.object_ids):
         raise ValueError(f"--cond_stats: the rows were labelled against {len(cond_stats.object_ids)} objects, this run has {objects.shape[0]}")
     model = Diffusion(noise_pred_net=unet, noise_scheduler=scheduler, num_inference_steps=args.num_inference_steps, mode=mode, input_dim=1,
@@ -601,6 +656,8 @@ def train(args):
     if squeeze3 is not None and model.simulator is None:
         from ..sim.squeeze import SqueezeSimulator3D
         model.simulator = SqueezeSimulator3D(model, object_mesh_dir=_object_mesh_dir(args), **squeeze3)
+    if cond_stats is not None and cond_stats.source == 'squeeze_3d':
+        model.object_mesh_dir = _object_mesh_dir(args)  # where the --cond_target report finds <name>/model.obj
     from ..goal import goal_from_args
     model.goal = goal_from_args(args)       # --goal_pose: the sweep adds a goal objective after the reference's (Diffusion._objective_sweep)
     if model.goal is not None and getattr(args, "predicted_sim", False) and not rollout:

@@ -1,7 +1,8 @@
 """Condition rows of the eps-net made by the dynamics model: what it predicts every finger of a set does, as ``global_cond`` rows.
 
 ``label_fingers`` runs ``engine.Guidance.label`` (and, with ``rollout=K``, ``label_settled``) over all fingers and returns the raw rows;
-``label_fingers_squeeze`` makes the same columns from the squeeze simulator's closings instead, with no dynamics model (source 'squeeze');
+``label_fingers_squeeze`` makes the same columns from the squeeze simulator's closings instead, with no dynamics model (source 'squeeze'),
+``label_fingers_squeeze_3d`` from the sliced squeeze of 3-D fingers on object meshes (source 'squeeze_3d');
 ``LabelStats`` remembers how a dataset's rows were standardised, so that a request in plain units - "clockwise on 90 % of the grid" -
 becomes a condition row at sampling time (``LabelStats.target``).  The columns are those of include/dgdm_hip.h.
 
@@ -24,8 +25,11 @@ MAX_COND_DIM = 256                 # the eps-net's global_cond_dim limit
 RECIPE_KEYS = ("G", "P", "ori_range", "threshold_std", "score_std", "K", "timestep", "seed", "contraction_dtype")
 # who made the rows: the dynamics model (the key is absent from its files) or the squeeze simulator, whose files also record its recipe
 # (threshold: the raw (rad, m, m) of squeeze_metric's classes; settled: the 5 settled columns were made)
-SOURCES = ("model", "squeeze")
+# 'squeeze_3d': the sliced squeeze of 3-D fingers, which has no friction and records the finger grid it sliced on instead
+SOURCES = ("model", "squeeze", "squeeze_3d")
 SQUEEZE_RECIPE_KEYS = ("source", "squeeze_config", "friction", "settled", "threshold")
+SQUEEZE_3D_RECIPE_KEYS = ("source", "squeeze_config", "sample_size", "width", "settled", "threshold")
+SOURCE_RECIPE_KEYS = {"model": (), "squeeze": SQUEEZE_RECIPE_KEYS, "squeeze_3d": SQUEEZE_3D_RECIPE_KEYS}
 
 _ROT_COLUMN = {"clockwise": "frac_clockwise", "counterclockwise": "frac_counterclockwise"}
 _SHIFT_COLUMN = {"up": "frac_up", "down": "frac_down", "left": "frac_left", "right": "frac_right"}
@@ -170,6 +174,63 @@ def label_fingers_squeeze(fingers, contours, objects: Sequence[int], grid_size: 
     return rows, counts
 
 
+def label_fingers_squeeze_3d(fingers, meshes, objects: Sequence[int], grid_size: int, num_pos: int, ori_range: Sequence[float],
+                             threshold: Sequence[float], score_std: Sequence[float], settled: bool = False, layout: str = "mean",
+                             sample_size: int = 25, width: Optional[float] = None, **squeeze_config):
+    """label_fingers_squeeze for 3-D fingers (engine.squeeze_label_3d; include/dgdm_hip.h "squeeze-simulator labels, 3-D fingers",
+    DESIGN.md 4.1b "source: squeeze_3d"): fingers (N, 42[, 1]) in sampler units; meshes a sequence of (vertices (nv, 3) in metres,
+    triangles (nt, 3)) standing on z = 0; objects: indices into meshes.  The starts, threshold, score_std, settled, layout and the
+    returned (rows, counts) are label_fingers_squeeze's.  The meshes are sliced once, on the levels gz of the first chunk's decode (the
+    finger grid's z depends on the v index only, so every chunk has the same); the fingers are decoded chunk by chunk
+    (sim.squeeze.finger_surfaces_3d with sample_size and width).  The sliced squeeze's opinion: blind between two levels, frictionless,
+    its steps, window and these thresholds untuned; nothing is claimed about MuJoCo.  NaN settled columns raise ValueError naming the
+    finger."""
+    import ctypes as C
+    import torch
+    from . import engine
+    from .resample import start_grid
+    from .sim import squeeze as sq
+    M, n = len(objects), int(sample_size)
+    gc = cond_dim(layout, M, 1 if settled else 0)
+    dev = torch.device("cuda", torch.cuda.current_device())
+    x = torch.as_tensor(fingers).detach().to(device=dev, dtype=torch.float32)
+    x = x.reshape(x.shape[0], -1).contiguous()
+    N = x.shape[0]
+    if N < 1:
+        raise ValueError("label_fingers_squeeze_3d: no fingers")
+    if M < 1:
+        raise ValueError("label_fingers_squeeze_3d: no objects")
+    meshes = list(meshes)
+    w = sq.FINGER_WIDTH_3D if width is None else float(width)
+    tally = start_grid(grid_size, num_pos, ori_range)
+    starts = np.concatenate([tally, sq.start_orientations(grid_size, ori_range)]) if settled else tally
+    cfg = engine.squeeze_config(**squeeze_config)
+    f64 = lambda a: torch.as_tensor(np.ascontiguousarray(a, dtype=np.float64)).to(dev)      # noqa: E731
+    st, rot = f64(starts), f64(engine.squeeze_rotation_table(cfg.theta_cells))
+    sizer = lambda k: int(engine.lib().dgdm_squeeze_label_3d_workspace_bytes(C.byref(cfg), k, M, n, n, max(len(meshes), 1)))      # noqa: E731
+    one = sizer(1)
+    if one < 0:
+        engine._check_value(one)
+    chunk = max(1, min(N, engine.SQUEEZE_WORKSPACE_BYTES // one, 65535 // M))
+    rows = torch.empty((N, gc), dtype=torch.float32, device=dev)
+    counts = torch.empty((N, 3), dtype=torch.int32, device=dev)
+    per = len(block_columns(1 if settled else 0))
+    sl = None
+    for f0 in range(0, N, chunk):
+        f1 = min(N, f0 + chunk)
+        gx, gz, sf = sq.finger_surfaces_3d(x[f0:f1], n, w)
+        if sl is None:
+            sl = engine.squeeze_slice(meshes, gz)
+        _, cnt = engine.squeeze_label_3d(sf, gx, sl["segments"], sl["offsets"], objects, st, len(tally), threshold, score_std, layout=layout, rot=rot,
+                                         out=rows[f0:f1], object_stride=per, workspace_bytes=sizer(f1 - f0), **squeeze_config)
+        counts[f0:f1] = cnt
+    if settled:
+        bad = torch.isnan(rows).any(dim=1)
+        if bool(bad.any()):
+            raise ValueError(f"label_fingers_squeeze_3d: finger {int(torch.nonzero(bad)[0])} settled on a non-finite pose (its settled columns are NaN)")
+    return rows, counts
+
+
 def parse_target(text: str) -> Dict[str, float]:
     """``"frac_clockwise=0.9,frac_up=0.7"`` -> {'frac_clockwise': 0.9, 'frac_up': 0.7}; ValueError on anything else."""
     out: Dict[str, float] = {}
@@ -210,7 +271,7 @@ class LabelStats:
 
     @property
     def source(self) -> str:
-        """'model' (also when the recipe does not say) or 'squeeze'."""
+        """'model' (also when the recipe does not say), 'squeeze' or 'squeeze_3d'."""
         return self.recipe.get("source") or "model"
 
     @property
@@ -271,7 +332,7 @@ class LabelStats:
                 "layout": self.layout, "object_ids": [o.item() if isinstance(o, np.generic) else o for o in self.object_ids],
                 **{k: self.recipe.get(k) for k in RECIPE_KEYS},
                 **({"predicted": True} if self.source == "model" else
-                   {**{k: self.recipe.get(k) for k in SQUEEZE_RECIPE_KEYS}, "simulated": self.source})}
+                   {**{k: self.recipe.get(k) for k in SOURCE_RECIPE_KEYS.get(self.source, SQUEEZE_RECIPE_KEYS)}, "simulated": "squeeze"})}
 
     def save(self, path: str) -> None:
         with open(path, "w") as f:
@@ -286,7 +347,7 @@ class LabelStats:
             if source not in SOURCES:
                 raise ValueError(f"label source {source!r} (need one of {', '.join(SOURCES)})")
             s = cls(d["columns"], d["layout"], d["object_ids"],
-                    {k: d.get(k) for k in RECIPE_KEYS + (SQUEEZE_RECIPE_KEYS if source != "model" else ())})
+                    {k: d.get(k) for k in RECIPE_KEYS + SOURCE_RECIPE_KEYS[source]})
             s.mean, s.std = np.asarray(d["mean"], dtype=np.float64), np.asarray(d["std"], dtype=np.float64)
             s.min, s.max = np.asarray(d["min"], dtype=np.float64), np.asarray(d["max"], dtype=np.float64)
         except (OSError, KeyError, TypeError, ValueError) as e:

@@ -38,6 +38,7 @@ LOWER_OFFSET, UPPER_OFFSET = -0.12, 0.15
 OBJECT_HALF_BOX_2D = 0.05           # metres per unit of Diffusion.object_vertices (generator/train.py:111-124)
 DEG, CM = 180.0 / np.pi, 100.0
 SIMULATED = 'squeeze'
+SIMULATED_3D = 'squeeze_3d'      # label.SOURCES' name for the sliced form's rows; their 'simulated' mark is SIMULATED all the same
 
 
 def _decode_units(scale: Optional[float], offset: Optional[float]) -> Dict[str, float]:
@@ -213,6 +214,7 @@ class SqueezeSimulator(_Simulator):
 # the face that looks at the object, L = yl - 0.23 + width; the right jaw's body at y = +0.23 (:135), its decoded surface itself looking
 # at the object, U = yr + 0.23
 LOWER_OFFSET_3D, UPPER_OFFSET_3D, FINGER_WIDTH_3D = -0.23, 0.23, 0.1
+NO_MESHES_3D = "the run's objects have no meshes (objects.npy or synthetic clouds): the sliced squeeze needs <object_dir>/<name>/model.obj"
 FRICTION_2D_ONLY = ("friction is 2-D only: the contact normals of 3-D fingers have a z component that the sliced, per-plane model does not "
                     "see")
 
@@ -269,8 +271,7 @@ class SqueezeSimulator3D(_Simulator):
         self.diffusion = diffusion
         self.object_mesh_dir = object_mesh_dir if object_mesh_dir is not None else getattr(diffusion, "object_mesh_dir", None)
         if not self.object_mesh_dir:
-            raise ValueError("SqueezeSimulator3D: the run's objects have no meshes (objects.npy or synthetic clouds): the sliced squeeze needs "
-                             "<object_dir>/<name>/model.obj")
+            raise ValueError(f"SqueezeSimulator3D: {NO_MESHES_3D}")
         self.sample_size, self.width = int(sample_size), float(width)
         self.configure(closing_steps, window, config)
         self._meshes: Dict[str, Any] = {}

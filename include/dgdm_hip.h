@@ -1032,6 +1032,33 @@ int dgdm_squeeze_map_3d(const DgdmSqueezeConfig *cfg, const double *surfaces_dev
                         int32_t *cells_dev, double *y_dev, int32_t *flags_dev, double *table_s_dev, double *touch_l_dev,
                         double *touch_r_dev, int32_t *succ_dev, void *workspace_dev, int64_t workspace_bytes, void *stream);
 
+/* ------------------------------------------------------------------ squeeze-simulator labels, 3-D fingers (csrc/squeeze.hip, DESIGN.md
+ * §4.1b "source: squeeze_3d")
+ * dgdm_squeeze_label with dgdm_squeeze_map_3d's inputs: condition rows of 3-D fingers from the sliced squeeze.  The contract is those two
+ * entries' and nothing else: the tables touch_l / touch_r / S of pair f * n_objects + k = (finger f, object objects_host[k]) are
+ * dgdm_squeeze_map_3d's for that pair, bit for bit; everything from the tables to rows_dev and counts_dev - successors, closing, settling,
+ * the tally and settle starts, the columns, the layouts, row_stride / column_offset / object_stride, the whole-finger chunks - is
+ * dgdm_squeeze_label's text verbatim with these tables where the 2-D ones stood.  The composition of tests/squeeze3d_oracle.py and
+ * tests/squeeze_label_oracle.py is the CPU oracle.  The same caveats hold: this project's own idealisation, blind between two levels,
+ * frictionless (friction has no sliced form: there is no mu argument), k, R and the thresholds untuned, nothing claimed about MuJoCo.
+ * What is new:
+ *   seg_offsets_host [n_bank][mv + 1] describes the bank of sliced meshes; objects_host [n_objects] indexes that bank (repeats allowed).
+ *   table_s_dev / touch_l_dev / touch_r_dev [n_fingers n_objects][T][X] float64 or NULL (not wanted): the tables of every pair, in pair
+ *   order - they exist so that the tables can be compared with dgdm_squeeze_map_3d's, which rows of counts and means cannot be.
+ *   The tables are made for a block of fingers at a time (what does not read the finger is evaluated once per block); every finger
+ *   still sees its candidates in dgdm_squeeze_map_3d's order, so neither the blocks nor the chunks change a bit.
+ *   Workspace: dgdm_squeeze_label_3d_workspace_bytes(cfg, chunk_fingers, n_objects, mu, mv, n_bank) (negative: bad arguments) holds gx
+ *   and the level offsets, then chunk_fingers n_objects partial sums, then that chunk's tables.
+ * DGDM_EINVAL before any launch: everything dgdm_squeeze_map_3d refuses (n_bank in n_objects' place there), and everything
+ *   dgdm_squeeze_label refuses that concerns neither friction nor the 2-D sizes.  Synchronises the stream once, at the end.             */
+int64_t dgdm_squeeze_label_3d_workspace_bytes(const DgdmSqueezeConfig *cfg, int chunk_fingers, int n_objects, int mu, int mv, int n_bank);
+int dgdm_squeeze_label_3d(const DgdmSqueezeConfig *cfg, const double *surfaces_dev, int n_fingers, const double *gx_host, int mu, int mv,
+                          const double *segments_dev, int64_t n_segments, const int32_t *seg_offsets_host, int n_bank,
+                          const int32_t *objects_host, int n_objects, const double *rot_dev, const double *starts_dev, int n_tally,
+                          int n_settle, const double threshold[3], const double score_std[3], double pos_norm, int layout, float *rows_dev,
+                          int64_t row_stride, int column_offset, int object_stride, int32_t *counts_dev, double *table_s_dev,
+                          double *touch_l_dev, double *touch_r_dev, void *workspace_dev, int64_t workspace_bytes, void *stream);
+
 /* ------------------------------------------------------------------ measurement hooks
  * When enabled, the launches of every stage of the path are bracketed by hipEvents on the stream they are launched on.
  * dgdm_prof_read_stage synchronises those events and returns, for one stage, the number of bracketed regions, their total
