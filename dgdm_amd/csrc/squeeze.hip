@@ -28,6 +28,9 @@
 // dgdm_squeeze_label_3d (include/dgdm_hip.h "squeeze-simulator labels, 3-D fingers") is the fifth: the label entry's consumer behind the 3-D
 // entry's inputs, both entries' checks (label_front, check_slices), and table3d_fingers_kernel for the chunk's tables, which shares the
 // finger-independent work of table3d_kernel among a block of fingers and gives that kernel's tables bit for bit.
+// dgdm_squeeze_values_3d (include/dgdm_hip.h "squeeze objective of 3-D fingers") is the sixth: groups of consecutive fingers on one object
+// each, table3d_fingers_kernel over the groups for the chunk's tables, and values3d_pair_kernel as the consumer, which sums the objective
+// per pair from the tables where lookup_kernel and squeeze_values_kernel would go through cells and y; chunks are whole groups.
 // This file is compiled with -ffp-contract=off (build.py): no operation of the contract is fused.
 #include "common.h"
 #include <cmath>
@@ -301,6 +304,46 @@ __global__ __launch_bounds__(64) void squeeze_values_kernel(ValueGrid g, const i
         const double d2 = (y[2 * r] - starts[3 * n + 2]) / g.std2;
         double t = ((lin[0] * d0 + quad[0] * (d0 * d0)) + (lin[1] * d1 + quad[1] * (d1 * d1))) + (lin[2] * d2 + quad[2] * (d2 * d2));
         if (o.use_rowcoef == 1) t += (double)rowcoef[(group * g.n_starts + n) * g.B + b] * d0;
+        v += t;
+    }
+#pragma unroll
+    for (int s = 32; s > 0; s >>= 1) v += __shfl_xor(v, s);
+    if (lane == 0) values[p] = v;
+}
+
+// dgdm_squeeze_values_3d's consumer (include/dgdm_hip.h "squeeze objective of 3-D fingers"): squeeze_values_kernel's sum straight from a
+// chunk's tables, in lookup_kernel's place - no per-start row is stored.  Grid: one workgroup of one wave per pair of the chunk, `pair0`
+// the chunk's first pair of the call (a whole group's), `obj` the chunk's groups.  Per start lookup_kernel's steps (the snap, the closed
+// cell, pose_y at it), then squeeze_values_kernel's expressions in its order.  The cells are taken apart only after closed[] has been
+// read at the snapped index; they index nothing else.
+__global__ __launch_bounds__(64) void values3d_pair_kernel(Grid g, ValueGrid vg, const double *__restrict__ starts, const double *__restrict__ touch_l,
+                                                           const double *__restrict__ touch_r, const double *__restrict__ S,
+                                                           const int32_t *__restrict__ closed, const DgdmObjective *__restrict__ obj,
+                                                           const float *__restrict__ rowcoef, int64_t pair0, double *__restrict__ values) {
+    const int lane = threadIdx.x;
+    const int64_t tab = (int64_t)blockIdx.x * g.T * g.X;
+    const int64_t p = pair0 + blockIdx.x;
+    const int64_t group = p / vg.B;
+    const int b = (int)(p - group * vg.B);
+    const DgdmObjective o = obj[group - pair0 / vg.B];
+    double lin[3], quad[3];
+#pragma unroll
+    for (int j = 0; j < 3; ++j) { lin[j] = (double)o.lin[j]; quad[j] = (double)o.quad[j]; }
+    double v = 0.0;
+    for (int n = lane; n < vg.n_starts; n += 64) {
+        const double th = starts[3 * (int64_t)n], x0 = starts[3 * (int64_t)n + 1], y0 = starts[3 * (int64_t)n + 2];
+        const int c0 = snap_cell(g, th, x0);
+        const int c1 = closed[tab + c0];
+        const double yc = pose_y(y0, touch_l[tab + c1], touch_r[tab + c1], S[tab + c1], g.travel_max);
+        const int a0 = c0 / vg.X, b0 = c0 % vg.X, a1 = c1 / vg.X, b1 = c1 % vg.X;
+        int64_t da = (int64_t)a1 - a0;
+        if (2 * da > vg.T) da -= vg.T;                                    // squeeze.fold's strict rule: +-T / 2 stays
+        if (2 * da < -(int64_t)vg.T) da += vg.T;
+        const double d0 = ((double)da * vg.dth) / vg.std0;
+        const double d1 = ((double)(b1 - b0) * vg.dx) / vg.std1;
+        const double d2 = (yc - y0) / vg.std2;
+        double t = ((lin[0] * d0 + quad[0] * (d0 * d0)) + (lin[1] * d1 + quad[1] * (d1 * d1))) + (lin[2] * d2 + quad[2] * (d2 * d2));
+        if (o.use_rowcoef == 1) t += (double)rowcoef[(group * vg.n_starts + n) * vg.B + b] * d0;
         v += t;
     }
 #pragma unroll
@@ -791,7 +834,8 @@ __global__ __launch_bounds__(TABLE_THREADS) void table3d_kernel(Grid3 g, const d
 // abscissa's ye are evaluated once; the loops over the block's fingers hold only the contract's operations on that finger's profiles, and
 // each finger's two minima stay in registers.  Every finger sees its candidates in table3d_kernel's order (P, Q, then the abscissae
 // ascending, segment by segment), so its three tables are table3d_kernel's bit for bit.  A tail block runs the same loops under the
-// uniform bound nfb < FB and reads no finger past the chunk.
+// uniform bound nfb < FB and reads no finger past the chunk.  dgdm_squeeze_values_3d launches the same body over groups of `batch`
+// consecutive fingers on one object each, pair k * batch + b of the chunk (the strides ks, fs at the kernel, below).
 // LDS: the current level's profiles of the block only, restaged when the level changes - the segments come level-sorted and the level
 // loop is uniform across the workgroup, so the barriers in it are legal.  sP[i][f] = (L_j[i], U_j[i]) of finger f as one 16-byte pair,
 // entries LABEL3_ENTRY = 2 FB + 2 doubles apart: a lane's reads of the entries i and i + 1 of all FB fingers are 2 FB ds_read_b128 of one
@@ -805,7 +849,7 @@ constexpr int LABEL3_FB = 8, FSEG_TILE = 512;
 constexpr int LABEL3_ENTRY = 2 * LABEL3_FB + 2;
 
 template <int FB, bool TAIL>
-__device__ __forceinline__ void table3d_fingers_body(const Grid3 &g, int M, int nfb, const double *surfaces, const double *gx,
+__device__ __forceinline__ void table3d_fingers_body(const Grid3 &g, int ks, int fs, int nfb, const double *surfaces, const double *gx,
                                                      const double *segments, const int32_t *seg_offsets, const int32_t *pairs, const double *rot,
                                                      double *touch_l, double *touch_r, double *S, double *lds) {
     constexpr int ENTRY = 2 * FB + 2;
@@ -813,7 +857,7 @@ __device__ __forceinline__ void table3d_fingers_body(const Grid3 &g, int M, int 
     double *sP = lds, *sG = lds + mu * ENTRY, *sSeg = sG + mu;
     int32_t *sOff = reinterpret_cast<int32_t *>(sSeg + 4 * FSEG_TILE);
     const int a = blockIdx.x, k = blockIdx.y;
-    const int64_t pr0 = (int64_t)blockIdx.z * FB * M + k;                  // the block's first pair of the chunk; finger f's is M f further on
+    const int64_t pr0 = (int64_t)blockIdx.z * FB * fs + (int64_t)k * ks;   // the block's first pair of the chunk; finger f's is fs f further on
     const double *sf = surfaces + (int64_t)pairs[2 * pr0] * 2 * ms;        // the chunk's fingers are consecutive: finger f's is 2 ms f further on
     const int32_t *off = seg_offsets + (int64_t)pairs[2 * pr0 + 1] * (g.mv + 1);
     const double c = rot[2 * a], s = rot[2 * a + 1];
@@ -897,7 +941,7 @@ __device__ __forceinline__ void table3d_fingers_body(const Grid3 &g, int M, int 
 #pragma unroll
             for (int f = 0; f < FB; ++f) {
                 if (f >= nfb) break;
-                const int64_t o = ((pr0 + (int64_t)f * M) * g.T + a) * g.X + b;
+                const int64_t o = ((pr0 + (int64_t)f * fs) * g.T + a) * g.X + b;
                 touch_l[o] = gl[f];
                 touch_r[o] = gu[f];
                 S[o] = (gl[f] + gu[f]) / 2.0;
@@ -906,16 +950,19 @@ __device__ __forceinline__ void table3d_fingers_body(const Grid3 &g, int M, int 
     }
 }
 
-// `nf`: the chunk's fingers.  The branch on a full block is uniform across the grid's z.
-__global__ __launch_bounds__(TABLE_THREADS) void table3d_fingers_kernel(Grid3 g, int M, int nf, const double *surfaces, const double *gx,
+// `nf`: the fingers that meet one object (the grid's y) - the label's: the chunk's; the groups form's: a group's.  (ks, fs): the pair
+// strides of the grid's y and of a finger - the label's finger-major chunk is (1, M), dgdm_squeeze_values_3d's group-major one (batch, 1);
+// either way a block's fingers are consecutive in `surfaces` and the loops are the same.  The branch on a full block is uniform across
+// the grid's z.
+__global__ __launch_bounds__(TABLE_THREADS) void table3d_fingers_kernel(Grid3 g, int ks, int fs, int nf, const double *surfaces, const double *gx,
                                                                         const double *segments, const int32_t *seg_offsets, const int32_t *pairs,
                                                                         const double *rot, double *touch_l, double *touch_r, double *S) {
     extern __shared__ __align__(16) double lds16[];
     const int nfb = min(LABEL3_FB, nf - (int)blockIdx.z * LABEL3_FB);
     if (nfb == LABEL3_FB)
-        table3d_fingers_body<LABEL3_FB, false>(g, M, nfb, surfaces, gx, segments, seg_offsets, pairs, rot, touch_l, touch_r, S, lds16);
+        table3d_fingers_body<LABEL3_FB, false>(g, ks, fs, nfb, surfaces, gx, segments, seg_offsets, pairs, rot, touch_l, touch_r, S, lds16);
     else
-        table3d_fingers_body<LABEL3_FB, true>(g, M, nfb, surfaces, gx, segments, seg_offsets, pairs, rot, touch_l, touch_r, S, lds16);
+        table3d_fingers_body<LABEL3_FB, true>(g, ks, fs, nfb, surfaces, gx, segments, seg_offsets, pairs, rot, touch_l, touch_r, S, lds16);
 }
 
 // the 3-D entry's workspace: gx [mu] and the level offsets [n_objects][mv + 1] in front, wherever the chunks are cut, then the chunk's
@@ -1375,10 +1422,106 @@ extern "C" int dgdm_squeeze_label_3d(const DgdmSqueezeConfig *cfg, const double 
         [&](unsigned n, int64_t, const int32_t *prs, double *tl, double *tr, double *S, int32_t *, hipStream_t st) {
             const int nf = (int)(n / (unsigned)n_objects);                // cap and n_pairs are whole fingers: so is every chunk
             hipLaunchKernelGGL(table3d_fingers_kernel, dim3((unsigned)g3.T, (unsigned)n_objects, (unsigned)((nf + LABEL3_FB - 1) / LABEL3_FB)),
-                               dim3(TABLE_THREADS), lds, st, g3, n_objects, nf, surfaces_dev, gx, segments_dev, offs, prs, rot_dev, tl, tr, S);
+                               dim3(TABLE_THREADS), lds, st, g3, 1, n_objects, nf, surfaces_dev, gx, segments_dev, offs, prs, rot_dev, tl, tr, S);
         },
         [&](unsigned n, int64_t p0, const double *tl, const double *tr, const double *S, const int32_t *closed, const int32_t *fix, hipStream_t st) {
             launch_label(g, lg, n, p0, starts_dev, rot_dev, tl, tr, S, closed, fix, part, rows_dev, counts_dev, st);
         },
         cap);
+}
+
+// dgdm_squeeze_values_3d's workspace: gx and the level offsets (extra3), then the chunk's objectives, then the chunk's tables.
+static size_t values_extra(int64_t chunk_groups) { return align256(sizeof(DgdmObjective) * (size_t)chunk_groups); }
+
+extern "C" int64_t dgdm_squeeze_values_3d_workspace_bytes(const DgdmSqueezeConfig *cfg, int chunk_groups, int batch, int mu, int mv, int n_bank) {
+    const char *fn = "dgdm_squeeze_values_3d_workspace_bytes";
+    if (check_sizes_3d(mu, mv, n_bank, fn)) return DGDM_EINVAL;
+    DGDM_REQUIRE(batch >= 1 && chunk_groups >= 1 && (int64_t)chunk_groups * batch <= MAX_CHUNK, DGDM_EINVAL,
+                 "%s: %d groups of %d fingers per chunk (need >= 1 each, at most %d pairs)", fn, chunk_groups, batch, MAX_CHUNK);
+    return workspace_bytes_of(fn, cfg, chunk_groups * batch, false, extra3(mu, mv, n_bank).bytes + values_extra(chunk_groups));
+}
+
+extern "C" int dgdm_squeeze_values_3d(const DgdmSqueezeConfig *cfg, const double *surfaces_dev, int n_fingers, const double *gx_host, int mu, int mv,
+                                      const double *segments_dev, int64_t n_segments, const int32_t *seg_offsets_host, int n_bank,
+                                      const double *rot_dev, const double *starts_dev, int n_starts, int n_groups, int batch,
+                                      const int32_t *group_first_host, const DgdmObjective *objectives_host, const float *rowcoef_dev,
+                                      const double score_std[3], double *values_dev, double *table_s_dev, double *touch_l_dev,
+                                      double *touch_r_dev, void *workspace_dev, int64_t workspace_bytes, void *stream) {
+    const char *fn = "dgdm_squeeze_values_3d";
+    const char *bytes_fn = "dgdm_squeeze_values_3d_workspace_bytes";
+    int rc = check_sizes_3d(mu, mv, n_bank, fn);
+    if (rc) return rc;
+    DGDM_REQUIRE(group_first_host && objectives_host && score_std && values_dev && starts_dev, DGDM_EINVAL, "%s: null argument", fn);
+    DGDM_REQUIRE(n_fingers >= 1 && n_groups >= 1 && batch >= 1 && n_starts >= 1, DGDM_EINVAL,
+                 "%s: %d fingers, %d groups of %d fingers, %d starts (need >= 1 each)", fn, n_fingers, n_groups, batch, n_starts);
+    DGDM_REQUIRE(batch <= MAX_CHUNK, DGDM_EINVAL, "%s: a group of %d fingers exceeds a chunk's %d pairs", fn, batch, MAX_CHUNK);
+    DGDM_REQUIRE((int64_t)n_groups * batch <= INT32_MAX, DGDM_EINVAL, "%s: %d groups x %d fingers exceed 2^31 - 1 pairs", fn, n_groups, batch);
+    for (int j = 0; j < 3; ++j)
+        DGDM_REQUIRE(std::isfinite(score_std[j]) && score_std[j] > 0.0, DGDM_EINVAL, "%s: score_std[%d] = %g (need finite, > 0)", fn, j, score_std[j]);
+    for (int i = 0; i < n_groups; ++i) {
+        const int u = objectives_host[i].use_rowcoef, first = group_first_host[i], ob = objectives_host[i].object;
+        DGDM_REQUIRE(u != DGDM_OBJ_ROWFIELD, DGDM_EINVAL, "%s: objective %d reads a row field; goal fields have no squeeze form", fn, i);
+        DGDM_REQUIRE(u == 0 || u == 1, DGDM_EINVAL, "%s: objective %d has use_rowcoef %d", fn, i, u);
+        DGDM_REQUIRE(u == 0 || rowcoef_dev, DGDM_EINVAL, "%s: objective %d uses rowcoef, rowcoef_dev is null", fn, i);
+        DGDM_REQUIRE(first >= 0 && (int64_t)first + batch <= n_fingers, DGDM_EINVAL, "%s: group %d = fingers %d .. %lld of %d", fn, i, first,
+                     (long long)first + batch - 1, n_fingers);
+        DGDM_REQUIRE(ob >= 0 && ob < n_bank, DGDM_EINVAL, "%s: group %d names object %d outside the bank of %d", fn, i, ob, n_bank);
+    }
+    const int n_pairs = n_groups * batch;
+    std::vector<int32_t> pairs((size_t)2 * n_pairs);                       // group-major: pair g * batch + b = (group_first[g] + b, its object)
+    for (int i = 0; i < n_groups; ++i)
+        for (int b = 0; b < batch; ++b) {
+            pairs[2 * ((size_t)i * batch + b)] = group_first_host[i] + b;
+            pairs[2 * ((size_t)i * batch + b) + 1] = objectives_host[i].object;
+        }
+    const Extra3 e = extra3(mu, mv, n_bank);
+    Outputs out = {};
+    out.S = table_s_dev;
+    out.tl = touch_l_dev;
+    out.tr = touch_r_dev;
+    if ((rc = check_map_args(fn, cfg, surfaces_dev && gx_host && seg_offsets_host && rot_dev, false, n_fingers, n_bank, pairs.data(), n_pairs, nullptr, 0,
+                             out, workspace_dev, workspace_bytes, false, e.bytes + values_extra(1), bytes_fn)) ||
+        (rc = check_ascending(gx_host, mu, "gx", fn)) || (rc = check_slices(fn, segments_dev, n_segments, seg_offsets_host, n_bank, mv)))
+        return rc;
+    const int64_t cells = (int64_t)cfg->theta_cells * cfg->x_cells;
+    auto need = [&](int64_t gr) { return (int64_t)(e.bytes + values_extra(gr) + layout(cells, gr * batch).bytes); };
+    DGDM_REQUIRE(workspace_bytes >= need(1), DGDM_EINVAL, "%s: workspace of %lld bytes holds no group of %d fingers, one needs %lld (%s)", fn,
+                 (long long)workspace_bytes, batch, (long long)need(1), bytes_fn);
+    int64_t groups = 1, over = std::min<int64_t>(n_groups, MAX_CHUNK / batch) + 1;            // need() does not fall: bisect [groups, over)
+    while (over - groups > 1) {
+        const int64_t mid = groups + (over - groups) / 2;
+        if (need(mid) <= workspace_bytes) groups = mid; else over = mid;
+    }
+    const int64_t cap = groups * batch;                                   // whole groups: a block of fingers never straddles two chunks
+    const size_t front = e.bytes + values_extra(groups);
+
+    uint8_t *ws = static_cast<uint8_t *>(workspace_dev);
+    hipStream_t s = (hipStream_t)stream;
+    double *gx;
+    int32_t *offs;
+    if ((rc = upload_extra3(e, ws, gx_host, mu, seg_offsets_host, n_bank, mv, s, gx, offs))) return rc;
+    DgdmObjective *obj = reinterpret_cast<DgdmObjective *>(ws + e.bytes);
+    const Grid g = grid_of(cfg);
+    const ValueGrid vg = {g.T, g.X, n_starts, batch, TWO_PI / (double)g.T, g.dx, score_std[0], score_std[1], score_std[2]};
+    Grid3 g3 = {g.T, g.X, mu, mv, g.x_half, g.dx};
+    const size_t lds = sizeof(double) * (size_t)(mu * LABEL3_ENTRY + mu + 4 * FSEG_TILE) + sizeof(int32_t) * (size_t)(mv + 1);
+    int copy_rc = DGDM_OK;
+    rc = run_chunks(
+        cfg, g, pairs.data(), n_pairs, nullptr, 0, out, ws + front, workspace_bytes - (int64_t)front, s, false,
+        [&](unsigned n, int64_t, const int32_t *prs, double *tl, double *tr, double *S, int32_t *, hipStream_t st) {
+            const unsigned ng = n / (unsigned)batch;                       // cap and n_pairs are whole groups: so is every chunk
+            hipLaunchKernelGGL(table3d_fingers_kernel, dim3((unsigned)g3.T, ng, (unsigned)((batch + LABEL3_FB - 1) / LABEL3_FB)), dim3(TABLE_THREADS),
+                               lds, st, g3, batch, 1, batch, surfaces_dev, gx, segments_dev, offs, prs, rot_dev, tl, tr, S);
+        },
+        [&](unsigned n, int64_t p0, const double *tl, const double *tr, const double *S, const int32_t *closed, const int32_t *, hipStream_t st) {
+            if (hipMemcpyAsync(obj, objectives_host + p0 / batch, sizeof(DgdmObjective) * (size_t)(n / (unsigned)batch), hipMemcpyHostToDevice, st) !=
+                hipSuccess) {
+                copy_rc = DGDM_EHIP;
+                return;
+            }
+            hipLaunchKernelGGL(values3d_pair_kernel, dim3(n), dim3(64), 0, st, g, vg, starts_dev, tl, tr, S, closed, (const DgdmObjective *)obj,
+                               rowcoef_dev, p0, values_dev);
+        },
+        cap);
+    return rc ? rc : copy_rc;
 }

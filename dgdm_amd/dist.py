@@ -182,22 +182,24 @@ def guided_chains_sharded(unet, spec: GuidanceSpec, sched, mode: str, noise: tor
     gathered result does not depend on the number of ranks.
     resample (sampler.run_chains): chains are whole per rank - a chain resamples among its own B fingers - and the uniform is keyed like
     the step noise, so the gathered result equals the one-process run bit for bit; 3-D: every rank walks the evaluations' draws of ALL
-    chains behind all guidance draws and keeps its block's.  resample_log receives this rank's chains' entries."""
+    chains behind all guidance draws and keeps its block's; a squeeze potential's bank is cut to the rank's objects, in the rank's object order
+    (Resample.for_objects), and draws nothing.  resample_log receives this rank's chains' entries."""
     from . import sampler
     world, rank = world_rank(group)
     mine, local_objects, local_chains = shard_chains(chains, rank, world)
     B, L, _ = noise.shape
-    sampler.check_resample(resample, eta, spec, 1, edit=edit, global_cond=global_cond)
+    sampler.check_resample(resample, eta, spec, 1, edit=edit, global_cond=global_cond, n_objects=int(objects.shape[0]))
     S = len(sched.timesteps) if edit is None else edit.n_steps(sched)
     predrawn = None
     if mode == 'point_3d':
-        n_pot = 0 if resample is None else len(resample.evaluations(S))
+        n_pot = 0 if resample is None else resample.fps_evaluations(S)
         predrawn = sampler.draw_chain_starts(spec, chains, S, starts, keep=mine, streams=streams, n_potential=n_pot)
     if len(local_chains):
         guid = (build or spec.build)(objects[local_objects].to(noise.device), len(local_chains))
         local = sampler.guided_chains(unet, guid, sched, mode, noise, local_chains, unguided=unguided, predrawn=predrawn, global_cond=global_cond,
                                       cfg_weight=cfg_weight, edit=edit, eta=eta, noise_seed=noise_seed, shared_step_noise=shared_step_noise,
-                                      chain_keys=chain_noise_keys(mine), resample=resample, resample_log=resample_log)
+                                      chain_keys=chain_noise_keys(mine), resample=None if resample is None else resample.for_objects(local_objects),
+                                      resample_log=resample_log)
     else:
         local = torch.zeros((0, B, L, 1), dtype=torch.float32, device=noise.device)
     return gather_pairs(local, len(chains), group)

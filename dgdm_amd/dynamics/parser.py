@@ -108,8 +108,10 @@ _FLAGS = [
                                   "(default 0.5; above 1: at every evaluation)"),
     ("resample_potential", str, "model", "with --resample_every: whose objective weighs the fingers - 'model' (the dynamics model's at (x_t, t)) or "
                                          "'squeeze' (the squeeze simulator's on the predicted clean design: 2-D only, frictionless unless --squeeze_friction is given, this project's "
-                                         "own mechanism, not MuJoCo's; honours --squeeze_closing_steps / --squeeze_window)"),
-    ("resample_squeeze_cells", str, None, "with --resample_potential squeeze: the squeeze table's theta,x cells as T,X (default: the squeeze defaults, "
+                                         "own mechanism, not MuJoCo's; honours --squeeze_closing_steps / --squeeze_window) or 'squeeze_3d' (with --fingers_3d and objects from "
+                                         "mesh files: the sliced squeeze of 3-D fingers, blind between two planes of the finger grid, frictionless; the same companions "
+                                         "but --squeeze_friction)"),
+    ("resample_squeeze_cells", str, None, "with --resample_potential squeeze / squeeze_3d: the squeeze table's theta,x cells as T,X (default: the squeeze defaults, "
                                           "720,241)"),
     ("device_dataset", "flag", None, "dynamics training: read every data file once, keep the dataset on the GPU and build each batch's rows there "
                                      "(dynamics/device_dataset.py); same batches, draws and results as the host loop"),

@@ -1396,6 +1396,71 @@ def squeeze_label_3d(surfaces, gx, segments, offsets, objects: Sequence[int], st
     return (out, cnt, tab) if tables else (out, cnt)
 
 
+def squeeze_values_3d(surfaces, gx, segments, offsets, group_first: Sequence[int], batch: int, objectives: Sequence[_lib.Objective], starts,
+                      rowcoef: Optional[torch.Tensor] = None, score_std: Optional[Sequence[float]] = None, rot=None, tables: bool = False,
+                      workspace_bytes: Optional[int] = None, **config):
+    """dgdm_squeeze_values_3d (include/dgdm_hip.h "squeeze objective of 3-D fingers") on the current device: the
+    objectives' VALUES of groups of 3-D fingers from the sliced squeeze - squeeze_tables_3d followed by squeeze_objective_values, bit for
+    bit, with no per-start output stored and the tables made for blocks of fingers that meet the same object.  surfaces (F, 2, mv, mu)
+    float64, gx (mu,), segments (n, 4) / offsets (O, mv + 1): squeeze_tables_3d's; group g is the `batch` consecutive fingers from
+    group_first[g] on, against the bank's object objectives[g].object (two groups may name the same fingers); starts (N, 3) float64;
+    rowcoef (groups, N * batch) float32 or None, as the guidance handle lays it out; score_std (theta rad, x m, y m), the 3-D SCORE_STD
+    by default; config: the keys of SQUEEZE_DEFAULTS -> (groups, batch) float64; tables=True -> (values, tables): S / touch_l / touch_r
+    (groups * batch, theta_cells, x_cells) float64 in pair order, for comparison with squeeze_tables_3d's.  The workspace follows
+    squeeze_label_3d's rule, counted in groups: as many groups as fit SQUEEZE_WORKSPACE_BYTES, at least one, never more than the call
+    has; workspace_bytes overrides it and does not change a bit of the values.  Synchronises the stream once."""
+    cfg = squeeze_config(**config)
+    f64 = _squeeze_mover()
+    sf, sg = f64(surfaces), f64(segments).reshape(-1, 4)
+    g = np.ascontiguousarray(gx, dtype=np.float64).reshape(-1)
+    of = np.ascontiguousarray(offsets, dtype=np.int32)
+    if sf.dim() != 4 or sf.shape[1] != 2 or sf.shape[3] != len(g) or of.ndim != 2 or of.shape[1] != sf.shape[2] + 1:
+        raise ValueError(f"squeeze_values_3d: surfaces (F, 2, mv, mu), gx (mu,) and offsets (O, mv + 1) expected, got {tuple(sf.shape)}, "
+                         f"{g.shape} and {of.shape}")
+    mu, mv, O = int(sf.shape[3]), int(sf.shape[2]), int(of.shape[0])
+    gf = np.ascontiguousarray(group_first, dtype=np.int32).reshape(-1)
+    n_groups, B = len(gf), int(batch)
+    if len(objectives) != n_groups:
+        raise ValueError(f"squeeze_values_3d: {n_groups} groups with {len(objectives)} objectives")
+    if score_std is None:
+        from .dynamics.dataloader import SCORE_STD
+        score_std = SCORE_STD[0]
+    if len(score_std) != 3:
+        raise ValueError("squeeze_values_3d: score_std holds three entries (theta, x, y)")
+    st = f64(starts).reshape(-1, 3)
+    N, T = int(st.shape[0]), cfg.theta_cells
+    rt = f64(squeeze_rotation_table(T) if rot is None else rot)
+    if rt.shape != (T, 2):
+        raise ValueError(f"squeeze_values_3d: rot of shape {tuple(rt.shape)} (need ({T}, 2))")
+    rc = None
+    if rowcoef is not None:
+        if not (isinstance(rowcoef, torch.Tensor) and rowcoef.is_cuda and rowcoef.dtype == torch.float32 and rowcoef.numel() == n_groups * N * max(B, 0)):
+            raise ValueError(f"squeeze_values_3d: float32 device rowcoef of {n_groups} x {N * B} entries expected, got "
+                             f"{tuple(getattr(rowcoef, 'shape', ()))} {getattr(rowcoef, 'dtype', None)}")
+        rc = rowcoef.contiguous()
+    sizer = lambda n: int(lib().dgdm_squeeze_values_3d_workspace_bytes(C.byref(cfg), n, B, mu, mv, O))      # noqa: E731
+    fit = sizer(min(max(n_groups, 1), max(65535 // max(B, 1), 1)))       # all groups in one chunk; negative: what the library refuses
+    if fit < 0:
+        _check_value(fit)
+    if workspace_bytes is not None:
+        ws_bytes = int(workspace_bytes)
+    elif fit <= SQUEEZE_WORKSPACE_BYTES:
+        ws_bytes = fit
+    else:                                           # the library cuts the budget into chunks of as many groups as fit it
+        ws_bytes = max(SQUEEZE_WORKSPACE_BYTES, sizer(1))
+    ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=sf.device)
+    values = torch.empty((n_groups, max(B, 0)), dtype=torch.float64, device=sf.device)
+    shape = (n_groups * max(B, 0), T, cfg.x_cells)
+    tab = {k: torch.empty(shape, dtype=torch.float64, device=sf.device) for k in ("S", "touch_l", "touch_r")} if tables else {}
+    arr = (_lib.Objective * max(n_groups, 1))(*objectives)
+    std = (C.c_double * 3)(*[float(v) for v in score_std])
+    _check_value(lib().dgdm_squeeze_values_3d(C.byref(cfg), dptr(sf), int(sf.shape[0]), g.ctypes.data, mu, mv, dptr(sg) if len(sg) else None,
+                                              int(len(sg)), of.ctypes.data, O, dptr(rt), dptr(st), N, n_groups, B, gf.ctypes.data, arr, dptr(rc), std,
+                                              dptr(values), dptr(tab.get("S")), dptr(tab.get("touch_l")), dptr(tab.get("touch_r")), dptr(ws), ws_bytes,
+                                              stream_ptr()))
+    return (values, tab) if tables else values
+
+
 def prof_enable(on: bool) -> None:
     check(lib().dgdm_prof_enable(int(on)))
 

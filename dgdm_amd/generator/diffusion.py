@@ -778,7 +778,7 @@ class Diffusion(nn.Module):
         plots = bool(self.save_dir) and self.render_plots and rank == 0
         jobs = []
         # --resample_* (one process only): every run's evaluations draw behind all of its guidance draws (sampler.run_chains)
-        n_pot = 0 if getattr(self, "resample", None) is None else len(self.resample.evaluations(S))
+        n_pot = 0 if getattr(self, "resample", None) is None else self.resample.fps_evaluations(S)      # 0 for a squeeze potential
         for opt_obj in OBJECTIVE_SWEEP + ([self.goal] if getattr(self, "goal", None) is not None else []):
             if opt_obj != 'convergence':
                 if world > 1:

@@ -516,6 +516,8 @@ def squeeze_friction_from_args(args):
         raise ValueError(f"--squeeze_friction with --squeeze_sim_3d: {FRICTION_2D_ONLY}")
     if getattr(args, "mode", "test") == 'label' and getattr(args, "label_source", None) == 'squeeze_3d':
         raise ValueError(f"--squeeze_friction with --label_source squeeze_3d: {FRICTION_2D_ONLY}")
+    if (getattr(args, "resample_potential", None) or 'model') == 'squeeze_3d':
+        raise ValueError(f"--squeeze_friction with --resample_potential squeeze_3d: {FRICTION_2D_ONLY}")
     if not getattr(args, "squeeze_sim", False) and (getattr(args, "resample_potential", None) or 'model') != 'squeeze' and not _labels_by_squeeze(args):
         raise ValueError("--squeeze_friction needs --squeeze_sim or --resample_potential squeeze (or --mode=label --label_source squeeze)")
     return mu
@@ -543,9 +545,9 @@ def squeeze_from_args(args):
     mu = squeeze_friction_from_args(args)
     if not getattr(args, "squeeze_sim", False):
         if (k is not None or r is not None) and not getattr(args, "squeeze_sim_3d", False) and \
-                (getattr(args, "resample_potential", None) or 'model') != 'squeeze' and not _labels_by_squeeze(args):
+                (getattr(args, "resample_potential", None) or 'model') not in ('squeeze', 'squeeze_3d') and not _labels_by_squeeze(args):
             raise ValueError("--squeeze_closing_steps / --squeeze_window need --squeeze_sim (or, with --fingers_3d, --squeeze_sim_3d), or "
-                             "--resample_potential squeeze")
+                             "--resample_potential squeeze / squeeze_3d")
         return None
     if getattr(args, "squeeze_sim_3d", False):
         raise ValueError("--squeeze_sim and --squeeze_sim_3d: choose one (--squeeze_sim is 2-D only, --squeeze_sim_3d is for --fingers_3d)")
@@ -587,6 +589,9 @@ def train(args):
         raise ValueError("--edit_from edits designs in the guided chains of --mode=test and needs --classifier_guidance")
     from ..resample import resample_from_args
     resample = resample_from_args(args)     # --resample_every / --resample_beta / --resample_ess: refused here unless --classifier_guidance and --eta > 0
+    if (getattr(args, "resample_potential", None) or 'model') == 'squeeze_3d' and _object_mesh_dir(args) is None:
+        from ..sim.squeeze import NO_MESHES_3D
+        raise ValueError(f"--resample_potential squeeze_3d: {NO_MESHES_3D}")
     cond = load_global_cond(args.global_cond, args.num_fingers) if args.global_cond is not None else None
     gc = 0 if cond is None else cond.shape[1]
     if cond_stats is not None:
@@ -627,7 +632,12 @@ def train(args):
     model.edit_plan = edit_plan
     from ..resample import squeeze_potential_from_args
     potential = squeeze_potential_from_args(args)       # --resample_potential squeeze: the fingers weighed by the squeeze model
-    if resample is not None and potential is not None:
+    if resample is not None and potential is not None and args.resample_potential == 'squeeze_3d':
+        from ..resample import with_squeeze_3d
+        from ..sim.squeeze import SqueezeSimulator3D
+        reader = SqueezeSimulator3D(model, object_mesh_dir=_object_mesh_dir(args))     # the mesh files --squeeze_sim_3d reads, in the handle's order
+        resample = with_squeeze_3d(resample, [reader.mesh(n) for n in OBJECT_NAMES_3D], **potential)
+    elif resample is not None and potential is not None:
         from ..resample import with_squeeze
         from ..sim.squeeze import OBJECT_HALF_BOX_2D
         bank = torch.as_tensor(objects).detach().cpu().double() * OBJECT_HALF_BOX_2D      # the bank SqueezeSimulator builds, in the handle's order

@@ -10,14 +10,15 @@ is sampler.run_chains.
 A second potential, potential='squeeze' (SqueezePotential): the squeeze simulator's objective on every finger's predicted
 clean design, over the same pose grid and in the same units - an opinion that does not come from the model whose gradient guides the
 chain.  Everything after the values is the same.  Equally this project's own: 2-D only, frictionless, no claim that it improves an
-objective under MuJoCo or on real checkpoints."""
+objective under MuJoCo or on real checkpoints.  potential='squeeze_3d' (SqueezePotential3D) is its form for 3-D fingers: the sliced
+squeeze of the chain's mesh object (DESIGN.md 4.1d "3-D form"), blind between two planes of the finger grid, frictionless, untuned."""
 from __future__ import annotations
 
 import math
 from typing import Any, Dict, List, Optional, Sequence
 
 
-POTENTIALS = ('model', 'squeeze')
+POTENTIALS = ('model', 'squeeze', 'squeeze_3d')
 
 
 def start_grid(grid_size: int, num_pos: int, ori_range: Sequence[float]):
@@ -71,6 +72,10 @@ class SqueezePotential:
         tail = f", friction={self.friction}" if self.friction > 0.0 else ""
         return f"SqueezePotential({self.n_objects} contours of {self.contours.shape[1]} vertices, {self.config}{tail})"
 
+    def subset(self, objects: Sequence[int]) -> "SqueezePotential":
+        """The same potential over the contours `objects` of the bank, in that order."""
+        return SqueezePotential(self.contours[list(objects)], self.score_std, self.num_points, self.friction, **self.config)
+
     def starts(self, grid_size: int, num_pos: int, ori_range: Sequence[float]):
         """start_grid on the device, made once per grid."""
         import torch
@@ -106,14 +111,98 @@ class SqueezePotential:
         return engine.squeeze_objective_values(out["cells"], out["y"], st, B, list(objectives), rowcoef, self.score_std, **self.config)
 
 
+class SqueezePotential3D:
+    """SqueezePotential for 3-D fingers (DESIGN.md 4.3e "potential: squeeze_3d", 4.1d "3-D form"): the sliced squeeze's objective per
+    finger of a chain on that chain's object, from one engine.squeeze_values_3d call per evaluation - the tables of a chain's B fingers
+    share the per-segment work, and no per-start output is stored.  Equally this project's own mechanism: the sliced model is blind
+    between two planes of the finger grid and frictionless; beta, the table size and the closing steps are untuned; nothing here shows
+    that it improves an objective under MuJoCo or on real checkpoints.
+
+    meshes: a sequence of (vertices (nv, 3) in metres standing on z = 0, triangles (nt, 3)) in the guidance handle's object order.
+    score_std: (theta rad, x m, y m), the 3-D SCORE_STD by default.  sample_size, width: sim.squeeze.finger_surfaces_3d's.
+    squeeze_config: engine.SQUEEZE_DEFAULTS' keys; ``friction`` is refused (FRICTION_2D_ONLY).  The meshes are sliced once, at the first
+    evaluation, on the levels gz of that decode (the finger grid's z depends on the v index only); the segments, the rotation table and
+    the start grid stay on the device between evaluations."""
+
+    def __init__(self, meshes, score_std=None, sample_size: int = 25, width: Optional[float] = None, **squeeze_config):
+        import numpy as np
+        from .dynamics.dataloader import SCORE_STD
+        from .sim.squeeze import FINGER_WIDTH_3D, FRICTION_2D_ONLY
+        if "friction" in squeeze_config:
+            raise ValueError(f"SqueezePotential3D: {FRICTION_2D_ONLY}")
+        try:
+            ms = [(np.ascontiguousarray(np.asarray(v, dtype=np.float64)), np.ascontiguousarray(np.asarray(f, dtype=np.int32))) for v, f in meshes]
+        except (TypeError, ValueError):
+            raise ValueError("SqueezePotential3D: meshes must be a sequence of (vertices (nv, 3), triangles (nt, 3))") from None
+        if not ms:
+            raise ValueError("SqueezePotential3D: no meshes")
+        for i, (v, f) in enumerate(ms):
+            if v.ndim != 2 or v.shape[1] != 3 or v.shape[0] < 1 or f.ndim != 2 or f.shape[1] != 3 or not np.isfinite(v).all():
+                raise ValueError(f"SqueezePotential3D: mesh {i}: finite vertices (nv, 3) and triangles (nt, 3) expected, got {v.shape} and {f.shape}")
+            if f.size and (f.min() < 0 or f.max() >= v.shape[0]):
+                raise ValueError(f"SqueezePotential3D: mesh {i}: a triangle names a vertex outside its {v.shape[0]}")
+        std = np.asarray(SCORE_STD[0] if score_std is None else score_std, dtype=np.float64).reshape(-1)
+        if std.shape != (3,) or not (np.isfinite(std).all() and (std > 0).all()):
+            raise ValueError(f"SqueezePotential3D: score_std {std.tolist()} is not three finite positive numbers")
+        unknown = set(squeeze_config) - {"theta_cells", "x_cells", "x_half", "window", "closing_steps", "travel_max", "finger_half_len"}
+        if unknown:
+            raise ValueError(f"SqueezePotential3D: unknown squeeze_config keys {sorted(unknown)}")
+        if isinstance(sample_size, bool) or int(sample_size) != sample_size or int(sample_size) < 2:
+            raise ValueError(f"SqueezePotential3D: sample_size {sample_size!r} is not an integer >= 2")
+        self.meshes, self.score_std, self.sample_size, self.config = ms, tuple(float(v) for v in std), int(sample_size), dict(squeeze_config)
+        self.width = FINGER_WIDTH_3D if width is None else float(width)
+        self._slices = self._rot = self._gz = None
+        self._starts: Dict[Any, Any] = {}
+
+    @property
+    def n_objects(self) -> int:
+        return len(self.meshes)
+
+    def __repr__(self) -> str:
+        return f"SqueezePotential3D({self.n_objects} meshes, sample_size={self.sample_size}, {self.config})"
+
+    def subset(self, objects: Sequence[int]) -> "SqueezePotential3D":
+        """The same potential over the meshes `objects` of the bank, in that order."""
+        return SqueezePotential3D([self.meshes[int(i)] for i in objects], self.score_std, self.sample_size, self.width, **self.config)
+
+    starts = SqueezePotential.starts
+
+    def values(self, x0, objectives: Sequence, rowcoef, n_grad: int, grid_size: int, num_pos: int, ori_range: Sequence[float]):
+        """SqueezePotential.values for 3-D fingers: x0 (nc, B, 42) float32 on the device -> (n_grad * nc, B) float64.  Group j * nc + k
+        is chain k's B fingers, k * B .. k * B + B - 1 of the decode, on objectives[j * nc + k].object.  One decode of the nc * B
+        designs, one engine.squeeze_values_3d call; no FPS draws, no guid.score call."""
+        import numpy as np
+        import torch
+        from . import engine
+        from .sim.squeeze import finger_surfaces_3d
+        nc, B, L = x0.shape
+        n_grad = int(n_grad)
+        if len(objectives) != n_grad * nc:
+            raise ValueError(f"SqueezePotential3D.values: {len(objectives)} objectives for {n_grad} x {nc} chains")
+        obj = np.array([int(o.object) for o in objectives], dtype=np.int32)
+        if obj.min() < 0 or obj.max() >= self.n_objects:
+            raise ValueError(f"SqueezePotential3D.values: an objective names object {int(obj.max())} of a bank of {self.n_objects}")
+        gx, gz, sf = finger_surfaces_3d(x0.reshape(nc * B, L), self.sample_size, self.width)
+        if self._slices is None:
+            self._slices = engine.squeeze_slice(self.meshes, gz)
+            self._gz = gz
+            self._rot = torch.from_numpy(engine.squeeze_rotation_table(engine.squeeze_config(**self.config).theta_cells)).to(x0.device)
+        assert np.array_equal(gz, self._gz), "SqueezePotential3D: the finger grid's levels changed between evaluations"
+        st = self.starts(grid_size, num_pos, ori_range)
+        group_first = np.tile(np.arange(nc, dtype=np.int32) * B, n_grad)
+        return engine.squeeze_values_3d(sf, gx, self._slices["segments"], self._slices["offsets"], group_first, B, list(objectives), st, rowcoef,
+                                        self.score_std, rot=self._rot, **self.config)
+
+
 class Resample:
     """every: evaluate after every `every`-th DDIM step (never after the last one).  beta: the inverse temperature of the weights,
     exp(beta * mean objective per grid cell), relative to the previous evaluation; 0 weighs all fingers alike and never resamples.
     ess_frac: resample when the effective sample size falls below ess_frac * B; above 1: whenever evaluated.
     potential: whose objective weighs the fingers - 'model': the dynamics model's at (x_t, t), the quantity whose gradient guides the
-    chain; 'squeeze': the squeeze simulator's on the predicted clean design (`squeeze`: a SqueezePotential), a second opinion."""
+    chain; 'squeeze': the squeeze simulator's on the predicted clean design (`squeeze`: a SqueezePotential), a second opinion;
+    'squeeze_3d': the same for 3-D fingers, by the sliced squeeze (`squeeze`: a SqueezePotential3D)."""
 
-    def __init__(self, every: int, beta: float, ess_frac: float = 0.5, potential: str = 'model', squeeze: Optional[SqueezePotential] = None):
+    def __init__(self, every: int, beta: float, ess_frac: float = 0.5, potential: str = 'model', squeeze=None):
         if isinstance(every, bool) or int(every) != every or int(every) < 1:
             raise ValueError(f"Resample: every {every!r} is not a positive integer")
         beta, ess_frac = float(beta), float(ess_frac)
@@ -125,8 +214,10 @@ class Resample:
             raise ValueError(f"Resample: potential {potential!r} is not one of {POTENTIALS}")
         if potential == 'squeeze' and not isinstance(squeeze, SqueezePotential):
             raise ValueError("Resample: potential 'squeeze' needs a SqueezePotential (squeeze=...)")
+        if potential == 'squeeze_3d' and not isinstance(squeeze, SqueezePotential3D):
+            raise ValueError("Resample: potential 'squeeze_3d' needs a SqueezePotential3D (squeeze=...)")
         if potential == 'model' and squeeze is not None:
-            raise ValueError("Resample: a SqueezePotential goes with potential='squeeze'")
+            raise ValueError("Resample: a SqueezePotential goes with potential='squeeze', a SqueezePotential3D with potential='squeeze_3d'")
         self.every, self.beta, self.ess_frac, self.potential, self.squeeze = int(every), beta, ess_frac, potential, squeeze
 
     def __repr__(self) -> str:
@@ -139,6 +230,17 @@ class Resample:
 
     def evaluations(self, n_steps: int) -> List[int]:
         return [si for si in range(n_steps) if self.evaluates(si, n_steps)]
+
+    def fps_evaluations(self, n_steps: int) -> int:
+        """How many of the evaluations draw FPS starts on a 3-D handle: all of the model's potential, none of a squeeze potential."""
+        return len(self.evaluations(n_steps)) if self.potential == 'model' else 0
+
+    def for_objects(self, objects: Sequence[int]) -> "Resample":
+        """This Resample for a handle that holds only `objects` of the bank, in that order (a rank's local bank, dist.shard_chains): a
+        squeeze potential's bank is cut alike; the model's potential reads the handle and is returned as it is."""
+        if self.squeeze is None:
+            return self
+        return Resample(self.every, self.beta, self.ess_frac, self.potential, self.squeeze.subset(objects))
 
 
 def from_flags(every: Optional[int], beta: Optional[float], ess_frac: Optional[float], classifier_guidance: bool, eta: float) -> Optional[Resample]:
@@ -172,26 +274,35 @@ def summarise(log: Sequence, n_chains: int, batch: int) -> List[Dict[str, Any]]:
 
 def squeeze_potential_from_args(args) -> Optional[Dict[str, Any]]:
     """--resample_potential squeeze [--resample_squeeze_cells T,X --squeeze_closing_steps K --squeeze_window R --squeeze_friction MU] ->
-    SqueezePotential's squeeze_config (and friction), or None for the model's potential.  ValueError: an unknown potential, 'squeeze' with --fingers_3d (a sliced-squeeze
-    evaluation costs seconds, DESIGN.md 4.1d), with --goal_pose (goal fields have no squeeze form) or without --resample_every;
-    --resample_squeeze_cells without it or not two positive integers."""
+    SqueezePotential's squeeze_config (and friction), or None for the model's potential.  --resample_potential squeeze_3d (with the
+    same companions but --squeeze_friction) -> SqueezePotential3D's squeeze_config.  ValueError: an unknown potential; 'squeeze' with
+    --fingers_3d (it is 2-D only: 3-D fingers have squeeze_3d); 'squeeze_3d' without --fingers_3d or with --squeeze_friction
+    (FRICTION_2D_ONLY); either with --goal_pose (goal fields have no squeeze form) or without --resample_every; --resample_squeeze_cells
+    without either or not two positive integers."""
     potential = getattr(args, "resample_potential", None) or 'model'
     cells = getattr(args, "resample_squeeze_cells", None)
     if potential not in POTENTIALS:
         raise ValueError(f"--resample_potential {potential!r}: choose one of {', '.join(POTENTIALS)}")
     if potential == 'model':
         if cells is not None:
-            raise ValueError("--resample_squeeze_cells needs --resample_potential squeeze")
+            raise ValueError("--resample_squeeze_cells needs --resample_potential squeeze (or squeeze_3d)")
         return None
+    flag = f"--resample_potential {potential}"
     if getattr(args, "resample_every", None) is None:
-        raise ValueError("--resample_potential squeeze needs --resample_every (and --resample_beta): it is a potential for resampling")
-    if getattr(args, "fingers_3d", False):
-        raise ValueError("--resample_potential squeeze is 2-D only: a sliced-squeeze evaluation of --fingers_3d costs seconds, not supported")
+        raise ValueError(f"{flag} needs --resample_every (and --resample_beta): it is a potential for resampling")
+    if potential == 'squeeze' and getattr(args, "fingers_3d", False):
+        raise ValueError("--resample_potential squeeze is 2-D only: for --fingers_3d give --resample_potential squeeze_3d (the sliced squeeze)")
+    if potential == 'squeeze_3d' and not getattr(args, "fingers_3d", False):
+        raise ValueError("--resample_potential squeeze_3d needs --fingers_3d: it is the sliced squeeze of 3-D fingers (--resample_potential squeeze "
+                         "is the 2-D one)")
     if getattr(args, "goal_pose", None) is not None:
-        raise ValueError("--resample_potential squeeze with --goal_pose: goal fields have no squeeze form, not supported")
+        raise ValueError(f"{flag} with --goal_pose: goal fields have no squeeze form, not supported")
     config: Dict[str, Any] = {}
     mu = getattr(args, "squeeze_friction", None)
     if mu is not None:
+        if potential == 'squeeze_3d':
+            from .sim.squeeze import FRICTION_2D_ONLY
+            raise ValueError(f"--squeeze_friction with --resample_potential squeeze_3d: {FRICTION_2D_ONLY}")
         from .sim.squeeze import check_friction
         config["friction"] = check_friction(mu, "--squeeze_friction")
     if cells is not None:
@@ -210,6 +321,11 @@ def squeeze_potential_from_args(args) -> Optional[Dict[str, Any]]:
 def with_squeeze(resample: Resample, contours, **squeeze_config) -> Resample:
     """`resample` with the squeeze simulator's potential over the contour bank (O, nv, 2) in metres."""
     return Resample(resample.every, resample.beta, resample.ess_frac, 'squeeze', SqueezePotential(contours, **squeeze_config))
+
+
+def with_squeeze_3d(resample: Resample, meshes, **squeeze_config) -> Resample:
+    """`resample` with the sliced squeeze's potential over the meshes (vertices in metres standing on z = 0, triangles)."""
+    return Resample(resample.every, resample.beta, resample.ess_frac, 'squeeze_3d', SqueezePotential3D(meshes, **squeeze_config))
 
 
 def resample_from_args(args) -> Optional[Resample]:

@@ -334,13 +334,14 @@ def step_noise_keys(n_chains: int, shared_step_noise: bool = False, chain_keys: 
 
 
 def check_resample(resample: Optional[Resample], eta: float, guid: Optional[Guidance], n_grad: int, scales: Optional[Sequence[float]] = None,
-                   bounds=None, edit=None, global_cond=None, grad_fn=None, objectives=None) -> None:
+                   bounds=None, edit=None, global_cond=None, grad_fn=None, objectives=None, n_objects: Optional[int] = None) -> None:
     """What a run with `resample` refuses, by ValueError and before any launch: eta == 0 (copies would never part), bounds / an edit
     (a finger's bounds belong to its slot, not to the design that is copied into it), global_cond (likewise its condition row),
     n_grad == 0 or no guidance handle (nothing to weigh by), per-chain scales with n_grad != 1; with the model's potential a bf16 handle
-    (score has no bf16 form); with the squeeze simulator's (which needs no forward-only trunk, so bf16 handles pass) a 3-D handle (a
-    sliced-squeeze evaluation costs seconds), a goal objective among `objectives` (names, Goals or the launch's
-    objectives; goal fields have no squeeze form) and a contour bank whose object count differs from the handle's."""
+    (score has no bf16 form); with a squeeze potential (which needs no forward-only trunk, so bf16 handles pass) a goal objective among
+    `objectives` (names, Goals or the launch's objectives; goal fields have no squeeze form) and a bank of contours / meshes whose
+    object count differs from the handle's (`n_objects`: the count to compare with, for a caller whose `guid` is a GuidanceSpec and
+    holds no objects); 'squeeze' on a 3-D handle (it is 2-D only: 'squeeze_3d' is the sliced form) and 'squeeze_3d' on a 2-D one."""
     if resample is None:
         return
     if not isinstance(resample, Resample):
@@ -353,14 +354,18 @@ def check_resample(resample: Optional[Resample], eta: float, guid: Optional[Guid
         raise ValueError("resample: global_cond rows belong to a finger's slot; resampled conditional rows are not supported")
     if n_grad == 0 or guid is None or grad_fn is not None:
         raise ValueError("resample: needs the guidance handle and its objectives (n_grad >= 1, no grad_fn): there is nothing else to weigh fingers by")
-    if resample.potential == 'squeeze':
-        if guid.dyn.kind == 3:
-            raise ValueError("resample: the squeeze potential is 2-D only (a sliced-squeeze evaluation of 3-D fingers costs seconds)")
+    if resample.potential in ('squeeze', 'squeeze_3d'):
+        if resample.potential == 'squeeze' and guid.dyn.kind == 3:
+            raise ValueError("resample: the squeeze potential is 2-D only; 3-D fingers have potential='squeeze_3d' (the sliced squeeze)")
+        if resample.potential == 'squeeze_3d' and guid.dyn.kind != 3:
+            raise ValueError("resample: the squeeze_3d potential is the sliced squeeze of 3-D fingers; 2-D fingers have potential='squeeze'")
         if any(is_goal(o) or getattr(o, "use_rowcoef", 0) == _lib.OBJ_ROWFIELD for o in (objectives or ())):
             raise ValueError("resample: goal objectives have no squeeze form (the squeeze potential reads no row field)")
-        if resample.squeeze.n_objects != guid.n_objects:
-            raise ValueError(f"resample: the squeeze potential's bank holds {resample.squeeze.n_objects} contours, the guidance handle "
-                             f"{guid.n_objects} objects")
+        have = guid.n_objects if n_objects is None else int(n_objects)
+        if resample.squeeze.n_objects != have:
+            what = "contours" if resample.potential == 'squeeze' else "meshes"
+            raise ValueError(f"resample: the squeeze potential's bank holds {resample.squeeze.n_objects} {what}, the guidance handle "
+                             f"{have} objects")
     elif getattr(guid, "contraction_dtype", "f32") == "bf16":
         raise ValueError("resample: the bf16 trunk has no forward-only form (Guidance.score refuses it)")
     if scales is not None and len(set(scales)) > 1 and n_grad != 1:
@@ -400,9 +405,10 @@ def run_chains(unet: Unet1d, guid: Optional[Guidance], sched: DDIMScheduler, x0:
     evaluation, device tensors.  resample_starts (3-D): the evaluations' FPS draws, [evaluation][n_grad * n_chains][starts_per_call], taken
     from the start stream AFTER all of the run's guidance draws (draw_chain_starts / draw_ensemble_starts, n_potential) - the guidance
     draws are those of the run without resampling.  check_resample lists what is refused, before any launch.
-    resample.potential == 'squeeze' (2-D): the values come from the squeeze simulator instead - one eps-net call on the step's output at
-    timesteps[si + 1], x0 = engine.ddim_pred_x0 of it, resample.squeeze.values over the same G P^2 cells in the same units; no
-    guid.score call, no FPS draws; everything after the values is the same engine.chain_resample call."""
+    resample.potential == 'squeeze' (2-D) or 'squeeze_3d' (3-D): the values come from the squeeze simulator instead - one eps-net call on
+    the step's output at timesteps[si + 1], x0 = engine.ddim_pred_x0 of it, resample.squeeze.values over the same G P^2 cells in the same
+    units; no guid.score call, no FPS draws (resample_starts is not read: Resample.fps_evaluations is 0); everything after the values is
+    the same engine.chain_resample call."""
     B, L = x0.shape
     nc = n_chains
     eta = float(eta)
@@ -410,7 +416,7 @@ def run_chains(unet: Unet1d, guid: Optional[Guidance], sched: DDIMScheduler, x0:
         raise ValueError(f"run_chains: eta {eta} is negative")
     if resample is not None:
         check_resample(resample, eta, guid, n_grad, scales, bounds=bounds, global_cond=global_cond, grad_fn=grad_fn, objectives=objectives)
-        n_eval = len(resample.evaluations(len(timesteps)))
+        n_eval = resample.fps_evaluations(len(timesteps))
         if guid.dyn.kind == 3 and n_eval:
             if resample_starts is None or resample_starts.dtype != np.int64 or resample_starts.size != n_eval * n_grad * nc * guid.starts_per_call:
                 raise ValueError(f"run_chains: 3-D resampling needs resample_starts, {n_eval} x {n_grad * nc} x {guid.starts_per_call} int64 draws")
@@ -458,7 +464,7 @@ def run_chains(unet: Unet1d, guid: Optional[Guidance], sched: DDIMScheduler, x0:
                                                            chain_keys=keys if isinstance(c, slice) else [keys[c]])
         out = [engine.ddim_guided_step(x[c], eps[c], None if g is None else g[c], n_grad, coef, sc, bounds, **noisy(c)) for c, sc in steps]
         x = out[0] if len(out) == 1 else torch.stack(out)
-        if resample is not None and resample.evaluates(si, len(timesteps)) and resample.potential == 'squeeze':
+        if resample is not None and resample.evaluates(si, len(timesteps)) and resample.potential in ('squeeze', 'squeeze_3d'):
             # the squeeze model's opinion of the predicted clean design: one eps-net call on the step's output at the next timestep (as the
             # loop calls it; cond is None here), the step's own x0 expression, one squeeze map over cond_fn's grid cells, one values launch
             tn = int(timesteps[si + 1])
@@ -601,7 +607,7 @@ def guided_chains(unet: Unet1d, guid: Guidance, sched: DDIMScheduler, mode: str,
     every chain key 0: common random numbers, for comparing objectives on equal noise (replicas are then identical again).
 
     resample, resample_log: run_chains' (every chain resamples among its own B fingers).  3-D: the evaluations' draws follow all
-    guidance draws on the start stream; `predrawn` then is draw_chain_starts' triple (n_potential = len(resample.evaluations(S)))."""
+    guidance draws on the start stream; `predrawn` then is draw_chain_starts' triple (n_potential = resample.fps_evaluations(S))."""
     nc, (B, L, _) = len(chains), noise.shape
     check_resample(resample, eta, guid, 1, edit=edit, global_cond=global_cond, objectives=[o for _, o in chains])
     engine.chain_cond_layout(global_cond, unet.global_cond_dim, nc, B)       # a condition of the wrong shape is refused before anything runs
@@ -618,7 +624,7 @@ def guided_chains(unet: Unet1d, guid: Guidance, sched: DDIMScheduler, mode: str,
     sweep_starts: List[Optional[np.ndarray]] = [None] * nc
     step_starts = pot_starts = None
     if is3d:
-        n_pot = 0 if resample is None else len(resample.evaluations(S))
+        n_pot = 0 if resample is None else resample.fps_evaluations(S)
         if predrawn is None:
             predrawn = draw_chain_starts(guid, chains, S, starts, n_potential=n_pot)
         if n_pot and len(predrawn) != 3:
@@ -668,7 +674,7 @@ def guided_multi_object(unet: Unet1d, guid: Guidance, sched: DDIMScheduler, mode
     noise, timesteps, bounds = edit_start(edit, sched, noise)
     # per step the reference draws object after object (:641-643): one run of draws for the whole loop
     st = starts.calls(guid.rows, len(timesteps) * n_obj).reshape(len(timesteps), -1) if is3d else None
-    n_pot = 0 if resample is None else len(resample.evaluations(len(timesteps)))
+    n_pot = 0 if resample is None else resample.fps_evaluations(len(timesteps))
     pot = starts.calls(guid.rows, n_pot * n_obj).reshape(n_pot, -1) if is3d and n_pot else None
     hook = None if on_step is None else lambda i, x, eps: on_step(i, x.reshape(B, L, 1))      # the harness's per-step plots (:648-674)
     out = run_chains(unet, guid, sched, noise.reshape(B, L), 1, n_obj, objectives, None, st, timesteps, [chain_scale(mode, opt_obj, multi=True)],
@@ -730,7 +736,7 @@ def guided_multi_object_groups(unet: Unet1d, guid: Guidance, sched: DDIMSchedule
     objectives, field = chain_objectives(guid, [(groups[k][j], opt_objs[k]) for j in range(n_obj) for k in range(K)])
     if field is not None:
         guid.set_row_field(field)
-    n_pot = 0 if resample is None else len(resample.evaluations(len(timesteps)))
+    n_pot = 0 if resample is None else resample.fps_evaluations(len(timesteps))
     if is3d and predrawn is None:
         predrawn = draw_ensemble_starts(guid, K, n_obj, len(timesteps), streams, n_potential=n_pot)
     pot = None

@@ -946,7 +946,7 @@ int dgdm_squeeze_label(const DgdmSqueezeConfig *cfg, const double *surfaces_dev,
 
 /* The objective's VALUE per (pair) from a squeeze map: what dgdm_guidance_objective_values makes of the dynamics model's logits, made
  * of the squeeze model's one-closing deltas instead - a second opinion for resampling.  This project's own mechanism:
- * no counterpart in the reference, 2-D only, frictionless.  THE recipe (tests/resample_squeeze_oracle.py states the same text in numpy).
+ * no counterpart in the reference, frictionless; the 3-D fingers' form is dgdm_squeeze_values_3d, below.  THE recipe (tests/resample_squeeze_oracle.py states the same text in numpy).
  *   cells_dev  [n_pairs][n_starts][3] int32, y_dev [n_pairs][n_starts][2] float64: as dgdm_squeeze_map writes them
  *   starts_dev [n_starts][3] float64: the starts of that map (y0 is read)
  *   pair p belongs to group p / B and is finger p % B of it;  objectives_host [n_pairs / B], HOST
@@ -1058,6 +1058,38 @@ int dgdm_squeeze_label_3d(const DgdmSqueezeConfig *cfg, const double *surfaces_d
                           int n_settle, const double threshold[3], const double score_std[3], double pos_norm, int layout, float *rows_dev,
                           int64_t row_stride, int column_offset, int object_stride, int32_t *counts_dev, double *table_s_dev,
                           double *touch_l_dev, double *touch_r_dev, void *workspace_dev, int64_t workspace_bytes, void *stream);
+
+/* ------------------------------------------------------------------ squeeze objective of 3-D fingers (csrc/squeeze.hip, DESIGN.md §4.3e
+ * "potential: squeeze_3d")
+ * The objective's VALUE per (finger of a chain, the chain's object) from the sliced squeeze: the potential of a resampling step for 3-D
+ * fingers.  The contract is two existing entries' and nothing else: values_dev[g * batch + b] is, bit for bit, what
+ *   dgdm_squeeze_map_3d on the pairs (group_first_host[g] + b, objectives_host[g].object), listed group-major, with the same starts, then
+ *   dgdm_squeeze_objective_values on its cells / y with B = batch and the same objectives, rowcoef and score_std
+ * give; the composition of tests/squeeze3d_oracle.py and tests/resample_squeeze_oracle.py is the CPU oracle.  No per-start output is
+ * stored: a chunk's tables are reduced where dgdm_squeeze_map_3d would write cells and y.  The same caveats hold: this project's own
+ * idealisation, blind between two levels of the finger grid, frictionless, k, R and the table size untuned, nothing claimed about
+ * MuJoCo or about real checkpoints.
+ *   cfg, surfaces_dev [n_fingers][2][mv][mu], gx_host, segments_dev / seg_offsets_host [n_bank][mv + 1], rot_dev, starts_dev
+ *   [n_starts][3]: dgdm_squeeze_map_3d's.  Group g is the `batch` consecutive fingers group_first_host[g] .. + batch - 1 against the
+ *   object objectives_host[g].object of the bank; two groups may name the same fingers (one chain weighed on several objects).
+ *   objectives_host [n_groups], rowcoef_dev [n_groups][n_starts * batch] float32 or NULL, score_std[3]: dgdm_squeeze_objective_values'.
+ *   values_dev [n_groups * batch] float64.  table_s_dev / touch_l_dev / touch_r_dev [n_groups * batch][T][X] float64 or NULL (not
+ *   wanted): the tables of every pair in pair order, dgdm_squeeze_map_3d's bit for bit - they exist so that tests can compare them.
+ *   The tables are made for blocks of 8 fingers of a group at a time, as dgdm_squeeze_label_3d makes them (what does not read the
+ *   finger is evaluated once per block; every finger still sees its candidates in dgdm_squeeze_map_3d's order).  Chunks are whole
+ *   groups; neither the blocks nor the chunks change a bit.  Workspace: dgdm_squeeze_values_3d_workspace_bytes(cfg, chunk_groups,
+ *   batch, mu, mv, n_bank) (negative: bad arguments) holds gx and the level offsets, chunk_groups objectives, then that chunk's tables.
+ * DGDM_EINVAL before any launch: everything dgdm_squeeze_map_3d refuses (n_bank in n_objects' place); everything
+ *   dgdm_squeeze_objective_values refuses (a row-field objective, use_rowcoef == 1 without rowcoef_dev, a bad score_std, n_starts < 1);
+ *   batch < 1, n_groups < 1, a group or a chunk of more than 65535 pairs; a group that reaches past n_fingers; an object outside the
+ *   bank; a workspace too small for one group.  Synchronises the stream once, at the end (the host arrays are the caller's).           */
+int64_t dgdm_squeeze_values_3d_workspace_bytes(const DgdmSqueezeConfig *cfg, int chunk_groups, int batch, int mu, int mv, int n_bank);
+int dgdm_squeeze_values_3d(const DgdmSqueezeConfig *cfg, const double *surfaces_dev, int n_fingers, const double *gx_host, int mu, int mv,
+                           const double *segments_dev, int64_t n_segments, const int32_t *seg_offsets_host, int n_bank, const double *rot_dev,
+                           const double *starts_dev, int n_starts, int n_groups, int batch, const int32_t *group_first_host,
+                           const DgdmObjective *objectives_host, const float *rowcoef_dev, const double score_std[3], double *values_dev,
+                           double *table_s_dev, double *touch_l_dev, double *touch_r_dev, void *workspace_dev, int64_t workspace_bytes,
+                           void *stream);
 
 /* ------------------------------------------------------------------ measurement hooks
  * When enabled, the launches of every stage of the path are bracketed by hipEvents on the stream they are launched on.
