@@ -220,6 +220,10 @@ PROTOTYPES = {
     "dgdm_squeeze_map_3d_workspace_bytes": (C.c_int64, [C.POINTER(SqueezeConfig), C.c_int, C.c_int, C.c_int, C.c_int]),
     "dgdm_squeeze_map_3d": (C.c_int, [C.POINTER(SqueezeConfig), _P, C.c_int, _P, C.c_int, C.c_int, _P, C.c_int64, _P, C.c_int, _P, C.c_int, _P, _P,
                                       C.c_int, _P, _P, _P, _P, _P, _P, _P, _P, C.c_int64, _P]),
+    "dgdm_squeeze_slice_normals": (C.c_int, [_P, _P, _P, _P, C.c_int, _P, C.c_int, _P, C.c_int64, _P, C.POINTER(C.c_int64), _P, _P]),
+    "dgdm_squeeze_map_3d_friction_workspace_bytes": (C.c_int64, [C.POINTER(SqueezeConfig), C.c_int, C.c_int, C.c_int, C.c_int]),
+    "dgdm_squeeze_map_3d_friction": (C.c_int, [C.POINTER(SqueezeConfig), _P, C.c_int, _P, C.c_int, C.c_int, _P, C.c_int64, _P, C.c_int, _P, C.c_int,
+                                               _P, _P, C.c_int, _P, _P, _P, _P, _P, _P, _P, _P, C.c_int64, _P, _P, _P, C.c_double, _P, _P]),
     "dgdm_squeeze_label_3d_workspace_bytes": (C.c_int64, [C.POINTER(SqueezeConfig), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
     "dgdm_squeeze_label_3d": (C.c_int, [C.POINTER(SqueezeConfig), _P, C.c_int, _P, C.c_int, C.c_int, _P, C.c_int64, _P, C.c_int, _P, C.c_int, _P, _P,
                                         C.c_int, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_double, C.c_int, _P, C.c_int64, C.c_int,

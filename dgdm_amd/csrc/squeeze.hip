@@ -17,6 +17,10 @@
 // dgdm_squeeze_map_3d (3-D fingers: the same contract on the horizontal planes of the finger grid, include/dgdm_hip.h "squeeze
 // simulator, 3-D fingers") runs the same chunk loop (run_chunks) with table3d_kernel in table_kernel's place; dgdm_squeeze_slice cuts
 // the object meshes into the per-level segment lists it reads.  Their kernels are described where they stand, below.
+// dgdm_squeeze_map_3d_friction (include/dgdm_hip.h "squeeze simulator, 3-D fingers, with Coulomb friction"; tests/squeeze3d_friction_oracle.py
+// is its CPU oracle) is dgdm_squeeze_map_3d with table3d_kernel<true>, which also fills the chunk's jam table by a 3-D antipodal test on
+// the two contacts' points and normals; dgdm_squeeze_slice_normals is the slicer that also emits the crossing triangles' normals it reads.
+// table3d_kernel<false> is dgdm_squeeze_map_3d's kernel, instruction for instruction what it was before the template.
 // Host side: a map entry checks the sizes of its own inputs, then check_map_args checks what all three take alike (config, shared
 // pointers, counts, starts and outputs, pair range, a workspace of at least one pair), then the entry checks what its own arrays hold.
 // run_chunks alone decides how many pairs a workspace holds and where a chunk's tables lie; the 3-D entry's extra block (gx, level
@@ -671,7 +675,8 @@ struct Grid3 {
 
 template <bool EMIT>
 __global__ __launch_bounds__(256) void slice_kernel(const double *verts, const int32_t *tris, const int64_t *vert_off, const int64_t *tri_off,
-                                                    const double *gz, int mv, int32_t *counts, const int32_t *seg_off, double *segments) {
+                                                    const double *gz, int mv, int32_t *counts, const int32_t *seg_off, double *segments,
+                                                    double *normals) {
     __shared__ int sc[256];
     const int j = blockIdx.x, o = blockIdx.y, tid = threadIdx.x;
     const double z = gz[j];
@@ -719,6 +724,15 @@ __global__ __launch_bounds__(256) void slice_kernel(const double *verts, const i
             }
             double *dst = segments + 4 * ((int64_t)seg_off[o * (mv + 1) + j] + base + incl - 1);
             for (int q = 0; q < 4; ++q) dst[q] = pt[q];
+            if (normals) {                                                 // dgdm_squeeze_slice_normals: N = (V1 - V0) x (V2 - V0), as the header writes it
+                const double *V0 = V + 3 * v[0], *V1 = V + 3 * v[1], *V2 = V + 3 * v[2];
+                const double ex = V1[0] - V0[0], ey = V1[1] - V0[1], ez = V1[2] - V0[2];
+                const double fx = V2[0] - V0[0], fy = V2[1] - V0[1], fz = V2[2] - V0[2];
+                double *nd = normals + 3 * ((int64_t)seg_off[o * (mv + 1) + j] + base + incl - 1);
+                nd[0] = ey * fz - ez * fy;
+                nd[1] = ez * fx - ex * fz;
+                nd[2] = ex * fy - ey * fx;
+            }
         }
         base += total;
     }
@@ -743,10 +757,66 @@ __device__ __forceinline__ int last_le(const double *gx, int mu, double x) {
     return lo;
 }
 
-// touch_l / touch_r / S [pairs][T][X] of this chunk.  Grid: (T, pairs) workgroups.
+// The contact `code` of one jaw (UPPER: the upper one) of a 3-D cell, rebuilt after the walk by the walk's own operations in the walk's own
+// order (include/dgdm_hip.h "squeeze simulator, 3-D fingers, with Coulomb friction"): the winner's segment and, for set B, its triangle's
+// normal are read from global memory and rotated again, so every bit is the candidate's.  sF: that jaw's surface [mv][mu] in LDS; sG, sOff:
+// the abscissae and the object's level offsets in LDS; s0 = sOff[0]; code in 0 .. (segments of the object) (mu + 2) - 1.
+template <bool UPPER>
+__device__ __forceinline__ void contact3d_of(const Grid3 &g, const double *sF, const double *sG, const int32_t *sOff, const double *gz,
+                                             const double *segments, const double *normals, int s0, double c, double s, double xg, int code,
+                                             double &cx, double &cy, double &cz, double &nx, double &ny, double &nz) {
+    const int mu = g.mu, w = mu + 2, si = code / w, k = code - si * w, t = s0 + si;
+    int j = 0;
+    while (t >= sOff[j + 1]) ++j;                                          // t < sOff[mv]: j stays below mv
+    const double *sg = segments + 4 * (int64_t)t;
+    const double ax = sg[0], ay = sg[1], bx = sg[2], by = sg[3];
+    const double px = (c * ax - s * ay) + xg, py = s * ax + c * ay, qx = (c * bx - s * by) + xg, qy = s * bx + c * by;
+    cz = gz[j];
+    if (k < 2) {                                                           // set A: P or Q on the jaw's patch i, i + 1 of level j
+        const double ex = k ? qx : px;
+        const int i = max(min(last_le(sG, mu, ex), mu - 2), 0);
+        const double g0 = sG[i], hx = sG[i + 1] - g0, f = (ex - g0) / hx;
+        const double *Fj = sF + j * mu;
+        const double dF = Fj[i + 1] - Fj[i];
+        double hz = 1.0, sz = 0.0;                                         // mv = 1: no z slope
+        if (g.mv > 1) {
+            const int jm = max(j - 1, 0), jp = min(j + 1, g.mv - 1);
+            const double *Fm = sF + jm * mu, *Fp = sF + jp * mu;
+            const double m0 = Fm[i], p0 = Fp[i];
+            const double fm = m0 + f * (Fm[i + 1] - m0), fp = p0 + f * (Fp[i + 1] - p0);
+            hz = gz[jp] - gz[jm];
+            sz = (fp - fm) * hx;
+        }
+        cx = ex;
+        cy = k ? qy : py;
+        nx = UPPER ? dF * hz : -dF * hz;
+        ny = UPPER ? -(hx * hz) : hx * hz;
+        nz = g.mv > 1 ? (UPPER ? sz : -sz) : 0.0;
+    } else {                                                               // set B: abscissa k - 2 under the segment, the triangle's normal
+        const int i = k - 2;
+        const double slope = (qy - py) / (qx - px);
+        const double *N = normals + 3 * (int64_t)t;
+        const double rx = c * N[0] - s * N[1], ry = s * N[0] + c * N[1], rz = N[2];
+        const bool flip = UPPER ? ry > 0.0 : ry < 0.0;                     // lower: n_y > 0, upper: n_y < 0, whatever the mesh's winding
+        cx = sG[i];
+        cy = py + (sG[i] - px) * slope;
+        nx = flip ? -rx : rx;
+        ny = flip ? -ry : ry;
+        nz = flip ? -rz : rz;
+    }
+}
+
+// touch_l / touch_r / S [pairs][T][X] of this chunk.  Grid: (T, pairs) workgroups.  FRICTION (dgdm_squeeze_map_3d_friction): each lane also
+// keeps, per jaw, the code of the first candidate to attain the least gap - two ints beside the two minima, one compare and one select per
+// candidate - and after the walk rebuilds the two contacts from their codes (contact3d_of) and evaluates the 3-D jam test once per cell;
+// jam [pairs][T][X], contact [pairs][T][X][2] or null.  The false instantiation reads none of the last six arguments and is
+// dgdm_squeeze_map_3d's kernel, instruction for instruction what it was before the template.
+template <bool FRICTION>
 __global__ __launch_bounds__(TABLE_THREADS) void table3d_kernel(Grid3 g, const double *surfaces, const double *gx, const double *segments,
                                                                 const int32_t *seg_offsets, const int32_t *pairs, const double *rot,
-                                                                double *touch_l, double *touch_r, double *S) {
+                                                                double *touch_l, double *touch_r, double *S, const double *gz,
+                                                                const double *normals, double fmu, double travel_max, int32_t *jam,
+                                                                int32_t *contact) {
     extern __shared__ double lds[];
     const int ms = g.mv * g.mu, mu = g.mu, tid = threadIdx.x;
     double *sL = lds, *sU = lds + ms, *sG = lds + 2 * ms, *sSeg = sG + mu;
@@ -765,6 +835,7 @@ __global__ __launch_bounds__(TABLE_THREADS) void table3d_kernel(Grid3 g, const d
         const int b = b0 + tid;
         const double xg = -g.x_half + (double)b * g.dx;
         double gl = inf, gu = inf;
+        [[maybe_unused]] int kl = -1, ku = -1;                             // FRICTION: the two contacts' codes
         int j = 0;                                                         // the level of the segment at hand: they come level-sorted
         for (int t0 = s0; t0 < s1; t0 += SEG_TILE) {
             const int n = min(SEG_TILE, s1 - t0);
@@ -785,12 +856,17 @@ __global__ __launch_bounds__(TABLE_THREADS) void table3d_kernel(Grid3 g, const d
                 const double px = sSeg[4 * k] + xg, py = sSeg[4 * k + 1], qx = sSeg[4 * k + 2] + xg, qy = sSeg[4 * k + 3];
                 // one search per endpoint serves set A and, gx being ascending, both ends of set B's range of abscissae
                 const int ip = last_le(sG, mu, px), iq = last_le(sG, mu, qx);
+                [[maybe_unused]] const int kc = (t0 + k - s0) * (mu + 2);  // FRICTION: the code of (this segment, P)
                 if (ip >= 0 && px <= glast) {                              // set A: P against the interpolated profiles
                     const int i = min(ip, mu - 2);
                     const double g0 = sG[i], f = (px - g0) / (sG[i + 1] - g0);
                     const double l0 = Lj[i], u0 = Uj[i];
                     const double lp = l0 + f * (Lj[i + 1] - l0);
                     const double up = u0 + f * (Uj[i + 1] - u0);
+                    if constexpr (FRICTION) {                              // the first candidate to attain the least gap: strictly less only
+                        kl = py - lp < gl ? kc : kl;
+                        ku = up - py < gu ? kc : ku;
+                    }
                     gl = fmin(gl, py - lp);
                     gu = fmin(gu, up - py);
                 }
@@ -800,6 +876,10 @@ __global__ __launch_bounds__(TABLE_THREADS) void table3d_kernel(Grid3 g, const d
                     const double l0 = Lj[i], u0 = Uj[i];
                     const double lp = l0 + f * (Lj[i + 1] - l0);
                     const double up = u0 + f * (Uj[i + 1] - u0);
+                    if constexpr (FRICTION) {
+                        kl = qy - lp < gl ? kc + 1 : kl;
+                        ku = up - qy < gu ? kc + 1 : ku;
+                    }
                     gl = fmin(gl, qy - lp);
                     gu = fmin(gu, up - qy);
                 }
@@ -812,6 +892,10 @@ __global__ __launch_bounds__(TABLE_THREADS) void table3d_kernel(Grid3 g, const d
                         const double slope = (qy - py) / (qx - px);
                         for (int i = i0; i <= ihi; ++i) {
                             const double ye = py + (sG[i] - px) * slope;
+                            if constexpr (FRICTION) {
+                                kl = ye - Lj[i] < gl ? kc + 2 + i : kl;
+                                ku = Uj[i] - ye < gu ? kc + 2 + i : ku;
+                            }
                             gl = fmin(gl, ye - Lj[i]);
                             gu = fmin(gu, Uj[i] - ye);
                         }
@@ -824,6 +908,29 @@ __global__ __launch_bounds__(TABLE_THREADS) void table3d_kernel(Grid3 g, const d
             touch_l[o] = gl;
             touch_r[o] = gu;
             S[o] = (gl + gu) / 2.0;
+            if constexpr (FRICTION) {
+                const double Sc = (gl + gu) / 2.0;
+                int jm = 0;
+                if (kl >= 0 && ku >= 0) {
+                    double clx, cly, clz, nlx, nly, nlz, cux, cuy, cuz, nux, nuy, nuz;
+                    contact3d_of<false>(g, sL, sG, sOff, gz, segments, normals, s0, c, s, xg, kl, clx, cly, clz, nlx, nly, nlz);
+                    contact3d_of<true>(g, sU, sG, sOff, gz, segments, normals, s0, c, s, xg, ku, cux, cuy, cuz, nux, nuy, nuz);
+                    const double ddx = cux - clx, ddy = cuy - cly, ddz = cuz - clz;
+                    const double a_l = nlx * ddx + nly * ddy + nlz * ddz;
+                    const double wlx = nly * ddz - nlz * ddy, wly = nlz * ddx - nlx * ddz, wlz = nlx * ddy - nly * ddx;
+                    const double q_l = wlx * wlx + wly * wly + wlz * wlz;
+                    const double a_u = -(nux * ddx + nuy * ddy + nuz * ddz);
+                    const double wux = nuy * ddz - nuz * ddy, wuy = nuz * ddx - nux * ddz, wuz = nux * ddy - nuy * ddx;
+                    const double q_u = wux * wux + wuy * wuy + wuz * wuz;
+                    const double ml = fmu * a_l, mr = fmu * a_u;
+                    jm = (fmu > 0.0 && Sc < travel_max && a_l > 0.0 && a_u > 0.0 && q_l <= ml * ml && q_u <= mr * mr) ? 1 : 0;
+                }
+                jam[o] = jm;
+                if (contact) {
+                    contact[2 * o] = kl;
+                    contact[2 * o + 1] = ku;
+                }
+            }
         }
     }
 }
@@ -967,12 +1074,13 @@ __global__ __launch_bounds__(TABLE_THREADS) void table3d_fingers_kernel(Grid3 g,
 
 // the 3-D entry's workspace: gx [mu] and the level offsets [n_objects][mv + 1] in front, wherever the chunks are cut, then the chunk's
 // layout (run_chunks gets what lies behind the block)
-struct Extra3 { size_t gx, off, bytes; };
-Extra3 extra3(int mu, int mv, int n_objects) {
+struct Extra3 { size_t gx, off, gz, bytes; };
+Extra3 extra3(int mu, int mv, int n_objects, bool with_gz = false) {      // with_gz (the friction entry): the levels gz [mv] behind the two
     Extra3 e;
     e.gx = 0;
     e.off = align256(sizeof(double) * (size_t)mu);
-    e.bytes = e.off + align256(sizeof(int32_t) * (size_t)n_objects * (size_t)(mv + 1));
+    e.gz = e.off + align256(sizeof(int32_t) * (size_t)n_objects * (size_t)(mv + 1));
+    e.bytes = e.gz + (with_gz ? align256(sizeof(double) * (size_t)mv) : 0);
     return e;
 }
 
@@ -1239,16 +1347,17 @@ extern "C" int dgdm_squeeze_objective_values(const DgdmSqueezeConfig *cfg, const
     return DGDM_OK;
 }
 
-extern "C" int dgdm_squeeze_slice(const double *verts_host, const int64_t *vert_offsets_host, const int32_t *tris_host,
-                                  const int64_t *tri_offsets_host, int n_objects, const double *gz_host, int mv, double *segments_dev,
-                                  int64_t capacity, int32_t *seg_offsets_host, int64_t *n_segments_host, void *stream) {
-    const char *fn = "dgdm_squeeze_slice";
+// The body of dgdm_squeeze_slice (with_normals = false: normals_dev unused) and dgdm_squeeze_slice_normals.
+static int slice_common(const char *fn, bool with_normals, const double *verts_host, const int64_t *vert_offsets_host, const int32_t *tris_host,
+                        const int64_t *tri_offsets_host, int n_objects, const double *gz_host, int mv, double *segments_dev, int64_t capacity,
+                        int32_t *seg_offsets_host, int64_t *n_segments_host, void *stream, double *normals_dev) {
     DGDM_REQUIRE(verts_host && vert_offsets_host && tris_host && tri_offsets_host && gz_host && seg_offsets_host && n_segments_host, DGDM_EINVAL,
                  "%s: null argument", fn);
     DGDM_REQUIRE(n_objects >= 1 && n_objects <= 65535, DGDM_EINVAL, "%s: %d objects (need 1 .. 65535)", fn, n_objects);
     DGDM_REQUIRE(mv >= 1 && mv <= MAX_LEVELS, DGDM_EINVAL, "%s: %d levels (need 1 .. %d)", fn, mv, MAX_LEVELS);
     DGDM_REQUIRE(capacity >= 0 && (segments_dev || capacity == 0), DGDM_EINVAL, "%s: capacity %lld with%s segments_dev", fn, (long long)capacity,
                  segments_dev ? "" : " no");
+    DGDM_REQUIRE(!with_normals || normals_dev || !segments_dev, DGDM_EINVAL, "%s: segments_dev with no normals_dev", fn);
     int rc = check_ascending(gz_host, mv, "gz", fn);
     if (rc) return rc;
     DGDM_REQUIRE(vert_offsets_host[0] == 0 && tri_offsets_host[0] == 0, DGDM_EINVAL, "%s: offsets start at %lld and %lld (need 0)", fn,
@@ -1280,7 +1389,8 @@ extern "C" int dgdm_squeeze_slice(const double *verts_host, const int64_t *vert_
     DGDM_HIP_CHECK(hipMemcpyAsync(toff.p, tri_offsets_host, sizeof(int64_t) * no1, hipMemcpyHostToDevice, s));
     DGDM_HIP_CHECK(hipMemcpyAsync(gz.p, gz_host, sizeof(double) * mv, hipMemcpyHostToDevice, s));
     hipLaunchKernelGGL(slice_kernel<false>, dim3((unsigned)mv, (unsigned)n_objects), dim3(256), 0, s, verts.as<double>(), tris.as<int32_t>(),
-                       voff.as<int64_t>(), toff.as<int64_t>(), gz.as<double>(), mv, counts.as<int32_t>(), (const int32_t *)nullptr, (double *)nullptr);
+                       voff.as<int64_t>(), toff.as<int64_t>(), gz.as<double>(), mv, counts.as<int32_t>(), (const int32_t *)nullptr, (double *)nullptr,
+                       (double *)nullptr);
     DGDM_HIP_CHECK(hipGetLastError());
     std::vector<int32_t> cnt(nl);
     DGDM_HIP_CHECK(hipMemcpyAsync(cnt.data(), counts.p, sizeof(int32_t) * nl, hipMemcpyDeviceToHost, s));
@@ -1301,10 +1411,26 @@ extern "C" int dgdm_squeeze_slice(const double *verts_host, const int64_t *vert_
     if (total == 0) return DGDM_OK;
     DGDM_HIP_CHECK(hipMemcpyAsync(offs.p, seg_offsets_host, sizeof(int32_t) * nl1, hipMemcpyHostToDevice, s));
     hipLaunchKernelGGL(slice_kernel<true>, dim3((unsigned)mv, (unsigned)n_objects), dim3(256), 0, s, verts.as<double>(), tris.as<int32_t>(),
-                       voff.as<int64_t>(), toff.as<int64_t>(), gz.as<double>(), mv, (int32_t *)nullptr, offs.as<int32_t>(), segments_dev);
+                       voff.as<int64_t>(), toff.as<int64_t>(), gz.as<double>(), mv, (int32_t *)nullptr, offs.as<int32_t>(), segments_dev,
+                       with_normals ? normals_dev : (double *)nullptr);
     DGDM_HIP_CHECK(hipGetLastError());
     DGDM_HIP_CHECK(hipStreamSynchronize(s));
     return DGDM_OK;
+}
+
+extern "C" int dgdm_squeeze_slice(const double *verts_host, const int64_t *vert_offsets_host, const int32_t *tris_host,
+                                  const int64_t *tri_offsets_host, int n_objects, const double *gz_host, int mv, double *segments_dev,
+                                  int64_t capacity, int32_t *seg_offsets_host, int64_t *n_segments_host, void *stream) {
+    return slice_common("dgdm_squeeze_slice", false, verts_host, vert_offsets_host, tris_host, tri_offsets_host, n_objects, gz_host, mv, segments_dev,
+                        capacity, seg_offsets_host, n_segments_host, stream, nullptr);
+}
+
+extern "C" int dgdm_squeeze_slice_normals(const double *verts_host, const int64_t *vert_offsets_host, const int32_t *tris_host,
+                                          const int64_t *tri_offsets_host, int n_objects, const double *gz_host, int mv, double *segments_dev,
+                                          int64_t capacity, int32_t *seg_offsets_host, int64_t *n_segments_host, void *stream,
+                                          double *normals_dev) {
+    return slice_common("dgdm_squeeze_slice_normals", true, verts_host, vert_offsets_host, tris_host, tri_offsets_host, n_objects, gz_host, mv,
+                        segments_dev, capacity, seg_offsets_host, n_segments_host, stream, normals_dev);
 }
 
 // What the two 3-D entries check of the slices they are handed, and how they put gx and the level offsets into the workspace's first
@@ -1337,34 +1463,88 @@ extern "C" int64_t dgdm_squeeze_map_3d_workspace_bytes(const DgdmSqueezeConfig *
     return workspace_bytes_of(fn, cfg, chunk_pairs, false, extra3(mu, mv, n_objects).bytes);
 }
 
+// The body of dgdm_squeeze_map_3d (friction = false: gz_host, normals_dev, fmu, jam_dev and contact_dev unused) and
+// dgdm_squeeze_map_3d_friction.
+static int squeeze_map_3d_common(const char *fn, const char *bytes_fn, bool friction, const DgdmSqueezeConfig *cfg, const double *surfaces_dev,
+                                 int n_fingers, const double *gx_host, int mu, int mv, const double *segments_dev, int64_t n_segments,
+                                 const int32_t *seg_offsets_host, int n_objects, const int32_t *pairs_host, int n_pairs, const double *rot_dev,
+                                 const double *starts_dev, int n_starts, int32_t *cells_dev, double *y_dev, int32_t *flags_dev, double *table_s_dev,
+                                 double *touch_l_dev, double *touch_r_dev, int32_t *succ_dev, void *workspace_dev, int64_t workspace_bytes,
+                                 void *stream, const double *gz_host, const double *normals_dev, double fmu, int32_t *jam_dev,
+                                 int32_t *contact_dev) {
+    int rc = check_sizes_3d(mu, mv, n_objects, fn);
+    if (rc) return rc;
+    DGDM_REQUIRE(!friction || (std::isfinite(fmu) && fmu >= 0.0), DGDM_EINVAL, "%s: friction coefficient %g (need finite, >= 0)", fn, fmu);
+    const Extra3 e = extra3(mu, mv, n_objects, friction);
+    Outputs out = {cells_dev, y_dev, flags_dev, table_s_dev, touch_l_dev, touch_r_dev, succ_dev, friction ? jam_dev : nullptr};
+    if ((rc = check_map_args(fn, cfg, surfaces_dev && gx_host && seg_offsets_host && rot_dev && (!friction || gz_host), false, n_fingers, n_objects,
+                             pairs_host, n_pairs, starts_dev, n_starts, out, workspace_dev, workspace_bytes, friction, e.bytes, bytes_fn)) ||
+        (rc = check_ascending(gx_host, mu, "gx", fn)))
+        return rc;
+    if ((rc = check_slices(fn, segments_dev, n_segments, seg_offsets_host, n_objects, mv))) return rc;
+    if (friction) {
+        if ((rc = check_ascending(gz_host, mv, "gz", fn))) return rc;
+        DGDM_REQUIRE(normals_dev || n_segments == 0, DGDM_EINVAL, "%s: %lld segments with no normals_dev", fn, (long long)n_segments);
+        for (int o = 0; o < n_objects; ++o) {                              // a contact's code s (mu + 2) + k stays an int32
+            const int64_t ns = (int64_t)seg_offsets_host[(size_t)o * (mv + 1) + mv] - seg_offsets_host[(size_t)o * (mv + 1)];
+            DGDM_REQUIRE(ns * (mu + 2) <= INT32_MAX, DGDM_EINVAL, "%s: object %d has %lld segments, contact codes of %d abscissae pass 2^31 - 1", fn, o,
+                         (long long)ns, mu);
+        }
+    }
+    uint8_t *ws = static_cast<uint8_t *>(workspace_dev);                  // the extra block in front, the chunks' tables behind it
+    hipStream_t s = (hipStream_t)stream;
+    double *gx, *gz = nullptr;
+    int32_t *offs;
+    if ((rc = upload_extra3(e, ws, gx_host, mu, seg_offsets_host, n_objects, mv, s, gx, offs))) return rc;
+    if (friction) {
+        gz = reinterpret_cast<double *>(ws + e.gz);
+        DGDM_HIP_CHECK(hipMemcpyAsync(gz, gz_host, sizeof(double) * mv, hipMemcpyHostToDevice, s));
+    }
+    const Grid g = grid_of(cfg);
+    Grid3 g3 = {g.T, g.X, mu, mv, g.x_half, g.dx};
+    const int64_t cells = (int64_t)g.T * g.X;
+    const size_t lds = sizeof(double) * (size_t)(2 * mu * mv + mu + 4 * SEG_TILE) + sizeof(int32_t) * (size_t)(mv + 1);
+    return run_chunks(cfg, g, pairs_host, n_pairs, starts_dev, n_starts, out, ws + e.bytes, workspace_bytes - (int64_t)e.bytes, s, friction,
+                      [&](unsigned n, int64_t p0, const int32_t *pairs, double *tl, double *tr, double *S, int32_t *jam, hipStream_t st) {
+                          if (friction)
+                              hipLaunchKernelGGL(table3d_kernel<true>, dim3((unsigned)g3.T, n), dim3(TABLE_THREADS), lds, st, g3, surfaces_dev, gx,
+                                                 segments_dev, offs, pairs, rot_dev, tl, tr, S, (const double *)gz, normals_dev, fmu, g.travel_max, jam,
+                                                 contact_dev ? contact_dev + 2 * p0 * cells : nullptr);
+                          else
+                              hipLaunchKernelGGL(table3d_kernel<false>, dim3((unsigned)g3.T, n), dim3(TABLE_THREADS), lds, st, g3, surfaces_dev, gx,
+                                                 segments_dev, offs, pairs, rot_dev, tl, tr, S, (const double *)nullptr, (const double *)nullptr, 0.0,
+                                                 0.0, (int32_t *)nullptr, (int32_t *)nullptr);
+                      });
+}
+
 extern "C" int dgdm_squeeze_map_3d(const DgdmSqueezeConfig *cfg, const double *surfaces_dev, int n_fingers, const double *gx_host, int mu, int mv,
                                    const double *segments_dev, int64_t n_segments, const int32_t *seg_offsets_host, int n_objects,
                                    const int32_t *pairs_host, int n_pairs, const double *rot_dev, const double *starts_dev, int n_starts,
                                    int32_t *cells_dev, double *y_dev, int32_t *flags_dev, double *table_s_dev, double *touch_l_dev,
                                    double *touch_r_dev, int32_t *succ_dev, void *workspace_dev, int64_t workspace_bytes, void *stream) {
-    const char *fn = "dgdm_squeeze_map_3d";
-    int rc = check_sizes_3d(mu, mv, n_objects, fn);
-    if (rc) return rc;
-    const Extra3 e = extra3(mu, mv, n_objects);
-    Outputs out = {cells_dev, y_dev, flags_dev, table_s_dev, touch_l_dev, touch_r_dev, succ_dev, nullptr};
-    if ((rc = check_map_args(fn, cfg, surfaces_dev && gx_host && seg_offsets_host && rot_dev, false, n_fingers, n_objects, pairs_host, n_pairs,
-                             starts_dev, n_starts, out, workspace_dev, workspace_bytes, false, e.bytes, "dgdm_squeeze_map_3d_workspace_bytes")) ||
-        (rc = check_ascending(gx_host, mu, "gx", fn)))
-        return rc;
-    if ((rc = check_slices(fn, segments_dev, n_segments, seg_offsets_host, n_objects, mv))) return rc;
-    uint8_t *ws = static_cast<uint8_t *>(workspace_dev);                  // the extra block in front, the chunks' tables behind it
-    hipStream_t s = (hipStream_t)stream;
-    double *gx;
-    int32_t *offs;
-    if ((rc = upload_extra3(e, ws, gx_host, mu, seg_offsets_host, n_objects, mv, s, gx, offs))) return rc;
-    const Grid g = grid_of(cfg);
-    Grid3 g3 = {g.T, g.X, mu, mv, g.x_half, g.dx};
-    const size_t lds = sizeof(double) * (size_t)(2 * mu * mv + mu + 4 * SEG_TILE) + sizeof(int32_t) * (size_t)(mv + 1);
-    return run_chunks(cfg, g, pairs_host, n_pairs, starts_dev, n_starts, out, ws + e.bytes, workspace_bytes - (int64_t)e.bytes, s, false,
-                      [&](unsigned n, int64_t, const int32_t *pairs, double *tl, double *tr, double *S, int32_t *, hipStream_t st) {
-                          hipLaunchKernelGGL(table3d_kernel, dim3((unsigned)g3.T, n), dim3(TABLE_THREADS), lds, st, g3, surfaces_dev, gx, segments_dev,
-                                             offs, pairs, rot_dev, tl, tr, S);
-                      });
+    return squeeze_map_3d_common("dgdm_squeeze_map_3d", "dgdm_squeeze_map_3d_workspace_bytes", false, cfg, surfaces_dev, n_fingers, gx_host, mu, mv,
+                                 segments_dev, n_segments, seg_offsets_host, n_objects, pairs_host, n_pairs, rot_dev, starts_dev, n_starts, cells_dev,
+                                 y_dev, flags_dev, table_s_dev, touch_l_dev, touch_r_dev, succ_dev, workspace_dev, workspace_bytes, stream, nullptr,
+                                 nullptr, 0.0, nullptr, nullptr);
+}
+
+extern "C" int64_t dgdm_squeeze_map_3d_friction_workspace_bytes(const DgdmSqueezeConfig *cfg, int chunk_pairs, int mu, int mv, int n_objects) {
+    const char *fn = "dgdm_squeeze_map_3d_friction_workspace_bytes";
+    if (check_sizes_3d(mu, mv, n_objects, fn)) return DGDM_EINVAL;
+    return workspace_bytes_of(fn, cfg, chunk_pairs, true, extra3(mu, mv, n_objects, true).bytes);
+}
+
+extern "C" int dgdm_squeeze_map_3d_friction(const DgdmSqueezeConfig *cfg, const double *surfaces_dev, int n_fingers, const double *gx_host, int mu,
+                                            int mv, const double *segments_dev, int64_t n_segments, const int32_t *seg_offsets_host, int n_objects,
+                                            const int32_t *pairs_host, int n_pairs, const double *rot_dev, const double *starts_dev, int n_starts,
+                                            int32_t *cells_dev, double *y_dev, int32_t *flags_dev, double *table_s_dev, double *touch_l_dev,
+                                            double *touch_r_dev, int32_t *succ_dev, void *workspace_dev, int64_t workspace_bytes, void *stream,
+                                            const double *gz_host, const double *normals_dev, double friction, int32_t *jam_dev,
+                                            int32_t *contact_dev) {
+    return squeeze_map_3d_common("dgdm_squeeze_map_3d_friction", "dgdm_squeeze_map_3d_friction_workspace_bytes", true, cfg, surfaces_dev, n_fingers,
+                                 gx_host, mu, mv, segments_dev, n_segments, seg_offsets_host, n_objects, pairs_host, n_pairs, rot_dev, starts_dev,
+                                 n_starts, cells_dev, y_dev, flags_dev, table_s_dev, touch_l_dev, touch_r_dev, succ_dev, workspace_dev, workspace_bytes,
+                                 stream, gz_host, normals_dev, friction, jam_dev, contact_dev);
 }
 
 extern "C" int64_t dgdm_squeeze_label_3d_workspace_bytes(const DgdmSqueezeConfig *cfg, int chunk_fingers, int n_objects, int mu, int mv, int n_bank) {

@@ -54,6 +54,10 @@ _FLAGS = [
     ("squeeze_friction", float, None, "with --squeeze_sim or --resample_potential squeeze (2-D only, refused with --squeeze_sim_3d): the Coulomb "
                                       "friction coefficient of the squeeze - poses whose two contacts hold the object are jammed and stay where "
                                       "they are (default: none, the frictionless model; untuned)"),
+    ("squeeze_friction_3d", float, None, "with --squeeze_sim_3d: the Coulomb friction coefficient of the sliced squeeze, a 3-D antipodal jamming rule on "
+                                         "the jaws' surface normals and the mesh triangles' normals (not --squeeze_friction's per-plane rule) - poses "
+                                         "whose two contacts hold the object are jammed and stay where they are (default: none, the frictionless "
+                                         "model; this project's own model, untuned, nothing claimed about MuJoCo)"),
     ("score_stats", str, None, "dynamics training: the stats.json sim/sim_2d.py or sim/sim_3d.py wrote beside its data; scores are divided by its score_std "
                                "instead of the reference's constants"),
     ("save_meshes", "flag", None, "also export every emitted gripper as OBJ meshes, collision pieces and gripper_<idx>.xml (assets/finger_mesh.py)"),

@@ -1317,12 +1317,15 @@ def squeeze_objective_values(cells: torch.Tensor, y: torch.Tensor, starts: torch
     return out
 
 
-def squeeze_slice(meshes, gz) -> Dict[str, object]:
+def squeeze_slice(meshes, gz, normals: bool = False) -> Dict[str, object]:
     """dgdm_squeeze_slice (include/dgdm_hip.h "squeeze simulator, 3-D fingers"): the cross-sections of triangle meshes on the planes
     z = gz[j].  meshes: a sequence of (vertices (nv, 3) float64 in metres, triangles (nt, 3) int32), host arrays; gz (mv,) strictly
     ascending.  -> segments (n, 4) float64 on the current device = (A_x, A_y, B_x, B_y), listed by (object, level, triangle), and
     offsets (O, mv + 1) int32, host: level j of object o is segments offsets[o, j] .. offsets[o, j + 1] - 1.  Two calls: the count,
-    then the emit into a tensor of that size.  Synchronises the stream."""
+    then the emit into a tensor of that size.  Synchronises the stream.
+    normals=True: dgdm_squeeze_slice_normals emits instead, and the result also holds 'normals' (n, 3) float64 on the device, every
+    segment's crossing triangle's (V1 - V0) x (V2 - V0) - what squeeze_tables_3d's friction_3d reads; segments and offsets are the same
+    bits."""
     meshes = list(meshes)
     if not meshes:
         raise ValueError("squeeze_slice: no meshes")
@@ -1339,16 +1342,33 @@ def squeeze_slice(meshes, gz) -> Dict[str, object]:
     _check_value(lib().dgdm_squeeze_slice(*args, None, 0, offsets.ctypes.data, C.byref(n), stream_ptr()))
     dev = torch.device("cuda", torch.cuda.current_device())
     segments = torch.empty((int(n.value), 4), dtype=torch.float64, device=dev)
+    if not normals:
+        if n.value:
+            _check_value(lib().dgdm_squeeze_slice(*args, dptr(segments), int(n.value), offsets.ctypes.data, C.byref(n), stream_ptr()))
+        return {"segments": segments, "offsets": offsets}
+    nrm = torch.empty((int(n.value), 3), dtype=torch.float64, device=dev)
     if n.value:
-        _check_value(lib().dgdm_squeeze_slice(*args, dptr(segments), int(n.value), offsets.ctypes.data, C.byref(n), stream_ptr()))
-    return {"segments": segments, "offsets": offsets}
+        _check_value(lib().dgdm_squeeze_slice_normals(*args, dptr(segments), int(n.value), offsets.ctypes.data, C.byref(n), stream_ptr(), dptr(nrm)))
+    return {"segments": segments, "offsets": offsets, "normals": nrm}
 
 
 def squeeze_tables_3d(surfaces, gx, segments, offsets, pairs, starts=None, rot=None, tables: bool = False, workspace_bytes: Optional[int] = None,
-                      **config) -> Dict[str, torch.Tensor]:
+                      friction_3d: float = 0.0, gz=None, normals=None, jam: bool = False, contact: bool = False, **config) -> Dict[str, torch.Tensor]:
     """dgdm_squeeze_map_3d on the current device.  surfaces (F, 2, mv, mu) float64: the lower and upper jaw face at travel 0 on the levels
     and the abscissae gx (mu,), strictly ascending; segments (n, 4) / offsets (O, mv + 1): squeeze_slice's, for the same levels; the
-    rest and the outputs as squeeze_tables.  config: the keys of SQUEEZE_DEFAULTS (finger_half_len is unused here)."""
+    rest and the outputs as squeeze_tables.  config: the keys of SQUEEZE_DEFAULTS (finger_half_len is unused here).
+    friction_3d: the Coulomb coefficient of dgdm_squeeze_map_3d_friction ("squeeze simulator, 3-D fingers, with Coulomb friction": a 3-D
+    antipodal jamming rule, not the 2-D `friction`); that entry runs when friction_3d > 0 or when its tables are asked for - jam
+    (P, theta_cells, x_cells) int32 and contact (P, theta_cells, x_cells, 2) int32 (the lower and upper contact's code), both also
+    returned with tables=True - and it needs gz (mv,), the levels the meshes were sliced on, and normals (n, 3), squeeze_slice(...,
+    normals=True)'s; flags then carries 8 / 16 (start / settled cell jammed).  Otherwise dgdm_squeeze_map_3d runs, as it always did."""
+    from .sim.squeeze import check_friction
+    fmu = check_friction(friction_3d, "squeeze_tables_3d: friction_3d")
+    with_friction = fmu > 0.0 or bool(jam) or bool(contact)
+    if with_friction and (gz is None or normals is None):
+        missing = " and ".join(n for n, v in (("gz", gz), ("normals", normals)) if v is None)
+        raise ValueError(f"squeeze_tables_3d: friction_3d (or jam / contact) needs {missing}: the levels the meshes were sliced on and "
+                         "squeeze_slice(..., normals=True)'s normals")
     cfg = squeeze_config(**config)
     f64 = _squeeze_mover()
     sf, sg = f64(surfaces), f64(segments).reshape(-1, 4)
@@ -1358,10 +1378,24 @@ def squeeze_tables_3d(surfaces, gx, segments, offsets, pairs, starts=None, rot=N
         raise ValueError(f"squeeze_tables_3d: surfaces (F, 2, mv, mu), gx (mu,) and offsets (O, mv + 1) expected, got {tuple(sf.shape)}, "
                          f"{g.shape} and {of.shape}")
     mu, mv, O = int(sf.shape[3]), int(sf.shape[2]), int(of.shape[0])
-    out, tail, keep = _squeeze_front("squeeze_tables_3d", cfg, f64, lambda n: lib().dgdm_squeeze_map_3d_workspace_bytes(C.byref(cfg), n, mu, mv, O),
-                                     pairs, starts, rot, tables, workspace_bytes)
-    _check_value(lib().dgdm_squeeze_map_3d(C.byref(cfg), dptr(sf), int(sf.shape[0]), g.ctypes.data, mu, mv, dptr(sg) if len(sg) else None, int(len(sg)),
-                                           of.ctypes.data, O, *tail))
+    sizer = lib().dgdm_squeeze_map_3d_friction_workspace_bytes if with_friction else lib().dgdm_squeeze_map_3d_workspace_bytes
+    out, tail, keep = _squeeze_front("squeeze_tables_3d", cfg, f64, lambda n: sizer(C.byref(cfg), n, mu, mv, O), pairs, starts, rot, tables,
+                                     workspace_bytes)
+    args = (C.byref(cfg), dptr(sf), int(sf.shape[0]), g.ctypes.data, mu, mv, dptr(sg) if len(sg) else None, int(len(sg)), of.ctypes.data, O) + tail
+    if not with_friction:
+        _check_value(lib().dgdm_squeeze_map_3d(*args))
+        return out
+    z = np.ascontiguousarray(gz, dtype=np.float64).reshape(-1)
+    nr = f64(normals).reshape(-1, 3)
+    if len(z) != mv or len(nr) != len(sg):
+        raise ValueError(f"squeeze_tables_3d: gz ({mv},) and normals ({len(sg)}, 3) expected, got {z.shape} and {tuple(nr.shape)}")
+    shape = (len(keep[0]), cfg.theta_cells, cfg.x_cells)
+    if tables or jam:
+        out["jam"] = torch.empty(shape, dtype=torch.int32, device=sf.device)
+    if tables or contact:
+        out["contact"] = torch.empty(shape + (2,), dtype=torch.int32, device=sf.device)
+    _check_value(lib().dgdm_squeeze_map_3d_friction(*args, z.ctypes.data, dptr(nr) if len(nr) else None, fmu, dptr(out.get("jam")),
+                                                    dptr(out.get("contact"))))
     return out
 
 

@@ -558,15 +558,31 @@ def squeeze_from_args(args):
     return config if mu is None else dict(config, friction=mu)
 
 
+def squeeze_friction_3d_from_args(args):
+    """--squeeze_friction_3d MU -> mu, or None without the flag.  ValueError: a negative or non-finite mu, no --squeeze_sim_3d (the labels
+    and the resampling potential of 3-D fingers have no friction).  Host-side checks only."""
+    mu = getattr(args, "squeeze_friction_3d", None)
+    if mu is None:
+        return None
+    from ..sim.squeeze import check_friction
+    mu = check_friction(mu, "--squeeze_friction_3d")
+    if not getattr(args, "squeeze_sim_3d", False):
+        raise ValueError("--squeeze_friction_3d needs --squeeze_sim_3d: it is the friction of the sliced squeeze's scores (--squeeze_friction is "
+                         "the 2-D one; --label_source squeeze_3d and --resample_potential squeeze_3d are frictionless)")
+    return mu
+
+
 def squeeze_3d_from_args(args):
-    """--squeeze_sim_3d [--squeeze_closing_steps K --squeeze_window R] -> SqueezeSimulator3D's keywords, or None without the flag.
-    Host-side checks only; that the run's objects are mesh files is checked where they are known (train)."""
+    """--squeeze_sim_3d [--squeeze_closing_steps K --squeeze_window R --squeeze_friction_3d MU] -> SqueezeSimulator3D's keywords, or None
+    without the flag.  Host-side checks only; that the run's objects are mesh files is checked where they are known (train)."""
+    mu = squeeze_friction_3d_from_args(args)
     if not getattr(args, "squeeze_sim_3d", False):
         return None
-    squeeze_friction_from_args(args)        # --squeeze_friction: refused, friction is 2-D only
+    squeeze_friction_from_args(args)        # --squeeze_friction: refused, that rule is 2-D only
     if not getattr(args, "fingers_3d", False):
         raise ValueError("--squeeze_sim_3d needs --fingers_3d: it is the squeeze model for 3-D fingers (--squeeze_sim is the 2-D one)")
-    return squeeze_sim_config(args, "--squeeze_sim_3d")
+    config = squeeze_sim_config(args, "--squeeze_sim_3d")
+    return config if mu is None else dict(config, friction_3d=mu)
 
 
 def train(args):

@@ -88,18 +88,18 @@ def pair_record(ctrlpts, allpts, contour, starts, start, closed) -> dict:
     return record(ctrlpts, allpts, "object_vertices", np.asarray(contour, dtype=np.float64), starts, start, closed)
 
 
-def write_map(out_dir: str, out, gripper_ids: Sequence[int], object_ids: Sequence[int], record_of, cfg, friction=None) -> List[str]:
+def write_map(out_dir: str, out, gripper_ids: Sequence[int], object_ids: Sequence[int], record_of, cfg, friction=None, friction_3d=None) -> List[str]:
     """write_dataset of a squeeze map's pairs: record_of(finger, object, start, closed) is the pair's data file; the loose starts are
     counted from the flags."""
     start, closed = out["start"].cpu().numpy(), out["closed"].cpu().numpy()
     records = [(int(object_ids[o]), int(gripper_ids[f]), record_of(f, o, start[p], closed[p])) for p, (f, o) in enumerate(out["pairs"])]
-    return write_dataset(out_dir, records, cfg, int(np.count_nonzero(out["flags"].cpu().numpy() & 1)), friction)
+    return write_dataset(out_dir, records, cfg, int(np.count_nonzero(out["flags"].cpu().numpy() & 1)), friction, friction_3d)
 
 
-def write_dataset(out_dir: str, records, cfg, loose_starts: int = 0, friction=None) -> List[str]:
+def write_dataset(out_dir: str, records, cfg, loose_starts: int = 0, friction=None, friction_3d=None) -> List[str]:
     """records: (object_id, gripper_id, pair_record) per pair -> the data files and stats.json (the configuration and the standard
     deviations of delta_theta, delta_pos x and delta_pos y over all files: DynamicsDataset's score_std; "friction": the squeeze's Coulomb
-    coefficient, when one is given).  Host code."""
+    coefficient, when one is given; "friction_3d": the 3-D fingers' rule's, likewise).  Host code."""
     os.makedirs(out_dir, exist_ok=True)
     files, deltas = [], []
     for object_id, gripper_id, save_data in records:
@@ -112,6 +112,8 @@ def write_dataset(out_dir: str, records, cfg, loose_starts: int = 0, friction=No
              "loose_starts": int(loose_starts), "score_std": np.concatenate(deltas).std(axis=0).tolist()}
     if friction is not None:
         stats["friction"] = float(friction)
+    if friction_3d is not None:
+        stats["friction_3d"] = float(friction_3d)
     with open(os.path.join(out_dir, "stats.json"), "w") as fh:
         json.dump(stats, fh, indent=1)
     return files

@@ -36,16 +36,19 @@ def gripper_design(gripper_idx: int):
 
 
 def generate(out_dir: str, gripper_ids: Sequence[int], meshes, object_ids: Sequence[int], object_names: Sequence[str], friction=None,
-             **config) -> List[str]:
+             friction_3d=None, **config) -> List[str]:
     """Writes ``<out_dir>/<object>_<gripper>.npz`` for every (gripper, object) and ``<out_dir>/stats.json``; returns the data files.
     meshes: (vertices (nv, 3) in metres, triangles (nt, 3)) per object, object_ids / object_names their numbers and names.  config: the
-    squeeze model's (engine.SQUEEZE_DEFAULTS).  One device call for all pairs.  Frictionless only: a ``friction`` argument is refused
-    (squeeze.FRICTION_2D_ONLY)."""
+    squeeze model's (engine.SQUEEZE_DEFAULTS).  One device call for all pairs.  The 2-D ``friction`` argument is refused
+    (squeeze.FRICTION_2D_ONLY).  friction_3d: the Coulomb coefficient of the 3-D antipodal jamming rule (squeeze.squeeze_map_3d; this
+    project's own model, untuned, nothing claimed about MuJoCo); None: frictionless, today's files; when given, stats.json records it as
+    ``"friction_3d"``."""
     from .. import engine
     from ..assets import finger_3d
     from . import squeeze
     if friction is not None:
         raise ValueError(f"sim_3d.generate: {squeeze.FRICTION_2D_ONLY}")
+    fmu = None if friction_3d is None else squeeze.check_friction(friction_3d, "sim_3d.generate: friction_3d")
     meshes = list(meshes)
     if not (len(meshes) == len(object_ids) == len(object_names)):
         raise ValueError(f"generate: {len(meshes)} meshes for {len(object_ids)} object ids and {len(object_names)} names")
@@ -53,9 +56,10 @@ def generate(out_dir: str, gripper_ids: Sequence[int], meshes, object_ids: Seque
     shapes = [finger_3d.generate_3d_gripper(yl, yr, sample_size=SAMPLE_SIZE) for yl, yr in designs]
     samples = np.stack([np.concatenate([yl, yr]) for yl, yr in designs]).astype(np.float32)
     starts = pose_grid()
-    out = squeeze.squeeze_map_3d(samples, meshes, starts, sample_size=SAMPLE_SIZE, width=FINGER_WIDTH_3D, scale=1.0, offset=0.0, **config)
+    extra = {} if fmu is None else {"friction_3d": fmu}
+    out = squeeze.squeeze_map_3d(samples, meshes, starts, sample_size=SAMPLE_SIZE, width=FINGER_WIDTH_3D, scale=1.0, offset=0.0, **extra, **config)
     return write_map(out_dir, out, gripper_ids, object_ids, lambda f, o, start, closed: pair_record(*shapes[f], object_names[o], starts, start, closed),
-                     engine.squeeze_config(**config))
+                     engine.squeeze_config(**config), friction_3d=fmu)
 
 
 def pair_record(ctrlpts, allpts, object_name, starts, start, closed) -> dict:
@@ -83,10 +87,17 @@ def main(argv=None):
     p.add_argument("--object_dir", default=None, help="directory of <name>/model.obj (default: MODEL_ROOT/objects)")
     p.add_argument("--object_names", default="", help="file of object names, one per line (default: the directory's listing)")
     p.add_argument("--friction", type=float, default=None, help="refused: friction is 2-D only (sim_2d.py --friction)")
+    p.add_argument("--friction_3d", type=float, default=None,
+                   help="the Coulomb coefficient of the 3-D antipodal jamming rule (DESIGN.md 4.1d '3-D friction'): poses whose two contacts hold the "
+                        "object are jammed and stay where they are; this project's own model, untuned, nothing claimed about MuJoCo (default: "
+                        "none, the frictionless model)")
     a = p.parse_args(argv)
     if a.friction is not None:
         from .squeeze import FRICTION_2D_ONLY
         raise ValueError(f"sim_3d --friction: {FRICTION_2D_ONLY}")
+    if a.friction_3d is not None:
+        from .squeeze import check_friction
+        check_friction(a.friction_3d, "--friction_3d")
     from .. import _lib, engine
     from ..dynamics.utils import MESH_FILE
     _lib.device_init(0)
@@ -99,7 +110,7 @@ def main(argv=None):
         raise ValueError(f"sim_3d: objects {object_ids[0]} .. {object_ids[-1]} asked for, {len(names)} found under {object_dir}")
     meshes = [engine.read_obj(os.path.join(object_dir, names[i], MESH_FILE)) for i in object_ids]
     files = generate(a.save_dir, list(range(a.gripper_idx, a.gripper_idx + a.num_gripper_parallel)), meshes, object_ids, [names[i] for i in object_ids],
-                     **cli_config(a))
+                     friction_3d=a.friction_3d, **cli_config(a))
     print(f"[dgdm_amd] wrote {len(files)} files and stats.json to {a.save_dir}")
 
 

@@ -122,12 +122,14 @@ def steps_from_args(args) -> Dict[str, int]:
     return {key: int(v) for key, v in (("closing_steps", k), ("window", r)) if v is not None}
 
 
-def squeeze_metric(start, closed, settled, flags, y0=0.0, threshold: Sequence[float] = SCORE_THRESHOLD[1], friction: float = 0.0) -> Dict[str, Any]:
+def squeeze_metric(start, closed, settled, flags, y0=0.0, threshold: Sequence[float] = SCORE_THRESHOLD[1], friction: float = 0.0,
+                   friction_3d: float = 0.0) -> Dict[str, Any]:
     """The metric dict of one (object, gripper) with build_metric's keys (dynamics/predicted.py, sim_test_mj.py:209-218) from
     squeeze_map's rows over the start orientations: start (n, 2), closed / settled (n, 3), flags (n,), host arrays.  One-step keys from
     one closing, classes with ``threshold`` in radians and metres as sim_test_mj.py:198-200 (+ 1); ``final_*`` from the settled pose;
     degrees and centimetres.  With friction > 0 (and only then) the dict also holds ``'squeeze_friction'``: mu and ``'squeeze_jammed'``: the
-    number of starts that settled on a jammed cell (flag 16)."""
+    number of starts that settled on a jammed cell (flag 16).  With friction_3d > 0 (3-D fingers' rule, and only then) it holds
+    ``'squeeze_friction_3d'`` and ``'squeeze_jammed'`` likewise."""
     st, cl, se = (np.asarray(a, dtype=np.float64) for a in (start, closed, settled))
     fl = np.asarray(flags).reshape(-1)
     thr = np.asarray(threshold, dtype=np.float64).reshape(3)
@@ -141,6 +143,8 @@ def squeeze_metric(start, closed, settled, flags, y0=0.0, threshold: Sequence[fl
            'simulated': SIMULATED, 'squeeze_loose': int(np.count_nonzero(fl & 1)), 'squeeze_cut': int(np.count_nonzero(fl & 4))}
     if float(friction) > 0.0:
         out.update({'squeeze_friction': float(friction), 'squeeze_jammed': int(np.count_nonzero(fl & 16))})
+    if float(friction_3d) > 0.0:
+        out.update({'squeeze_friction_3d': float(friction_3d), 'squeeze_jammed': int(np.count_nonzero(fl & 16))})
     return out
 
 
@@ -150,11 +154,11 @@ def start_orientations(num_rot: int, ori_range: Sequence[float]) -> np.ndarray:
     return np.stack([theta0, np.zeros_like(theta0), np.zeros_like(theta0)], axis=1)
 
 
-def simulator_lists(out: Dict[str, Any], threshold: Sequence[float], friction: float = 0.0):
+def simulator_lists(out: Dict[str, Any], threshold: Sequence[float], friction: float = 0.0, friction_3d: float = 0.0):
     """A map's outputs -> the simulators' eight lists, one entry per pair: ``squeeze_metric`` in the metrics' slot, None (no videos: [])
     in the others - nothing is rendered."""
     start, closed, settled, flags = (out[k].cpu().numpy() for k in ("start", "closed", "settled", "flags"))
-    metrics = [squeeze_metric(start[p], closed[p], settled[p], flags[p], 0.0, threshold, friction) for p in range(len(flags))]
+    metrics = [squeeze_metric(start[p], closed[p], settled[p], flags[p], 0.0, threshold, friction, friction_3d) for p in range(len(flags))]
     none: List[Any] = [None] * len(flags)
     return list(none), metrics, list(none), list(none), list(none), list(none), [[] for _ in none], list(none)
 
@@ -237,20 +241,27 @@ def finger_surfaces_3d(samples, sample_size: int = 25, width: float = FINGER_WID
 
 def squeeze_map_3d(samples, meshes, starts, pairs=None, sample_size: int = 25, width: float = FINGER_WIDTH_3D, scale: Optional[float] = None,
                    offset: Optional[float] = None, tables: bool = False, workspace_bytes: Optional[int] = None, friction=None,
-                   **config) -> Dict[str, Any]:
+                   friction_3d: float = 0.0, **config) -> Dict[str, Any]:
     """squeeze_map for 3-D fingers: samples (B, 42[, 1]) designs, meshes a sequence of (vertices (nv, 3) in metres, triangles (nt, 3)) in
     the scene's frame (standing on z = 0), starts (N, 3) = (theta0 rad, x0 m, y0 m) shared by all pairs.  The meshes are sliced on the
     finger grid's levels (engine.squeeze_slice) and squeezed level by level (engine.squeeze_tables_3d); what lies between two levels is
-    not seen.  Output keys as squeeze_map, plus segments / offsets.  Frictionless only: a ``friction`` argument is refused (FRICTION_2D_ONLY)."""
+    not seen.  Output keys as squeeze_map, plus segments / offsets.  The 2-D ``friction`` argument is refused (FRICTION_2D_ONLY).
+    friction_3d: the Coulomb coefficient of the 3-D antipodal jamming rule (include/dgdm_hip.h "squeeze simulator, 3-D fingers, with
+    Coulomb friction"; 0: frictionless, today's outputs bit for bit); with friction_3d > 0 flags also carries 8 / 16 (start / settled
+    cell jammed), tables adds jam and contact, and the outputs hold the slicer's normals."""
     from .. import engine
     if friction is not None:
         raise ValueError(f"squeeze_map_3d: {FRICTION_2D_ONLY}")
+    fmu = check_friction(friction_3d, "squeeze_map_3d: friction_3d")
     gx, gz, sf = finger_surfaces_3d(samples, sample_size, width, scale, offset)
-    sl = engine.squeeze_slice(meshes, gz)
+    sl = engine.squeeze_slice(meshes, gz, normals=fmu > 0.0)
     pr = all_pairs(sf.shape[0], len(sl["offsets"])) if pairs is None else np.ascontiguousarray(pairs, dtype=np.int32).reshape(-1, 2)
-    out = engine.squeeze_tables_3d(sf, gx, sl["segments"], sl["offsets"], pr, starts, tables=tables, workspace_bytes=workspace_bytes, **config)
+    extra = dict(friction_3d=fmu, gz=gz, normals=sl["normals"]) if fmu > 0.0 else {}
+    out = engine.squeeze_tables_3d(sf, gx, sl["segments"], sl["offsets"], pr, starts, tables=tables, workspace_bytes=workspace_bytes, **extra, **config)
     add_poses(out, pr, **config)
     out.update(segments=sl["segments"], offsets=sl["offsets"])
+    if fmu > 0.0:
+        out["normals"] = sl["normals"]
     return out
 
 
@@ -260,12 +271,15 @@ class SqueezeSimulator3D(_Simulator):
     gripper-minor.  An object name is read from ``<object_mesh_dir>/<name>/model.obj`` (engine.read_obj) as it stands, in metres; a run
     whose objects have no meshes (objects.npy, synthetic clouds) is refused with a ValueError - a point cloud has no cross-section.
     Metrics: ``squeeze_metric`` with the 3-D thresholds SCORE_THRESHOLD[0], marked ``'simulated': 'squeeze'`` and never ``'predicted'``.
-    Frictionless only: a ``friction`` argument is refused (FRICTION_2D_ONLY)."""
+    The 2-D ``friction`` argument is refused (FRICTION_2D_ONLY).  ``friction_3d``: the Coulomb coefficient of the 3-D antipodal jamming
+    rule (squeeze_map_3d; 0: frictionless); with friction_3d > 0, and only then, the metrics also carry ``'squeeze_friction_3d'`` and
+    ``'squeeze_jammed'``.  This project's own model, untuned; nothing is claimed about MuJoCo."""
 
     def __init__(self, diffusion, object_mesh_dir: Optional[str] = None, closing_steps: Optional[int] = None, window: Optional[int] = None,
-                 sample_size: int = 25, width: float = FINGER_WIDTH_3D, friction=None, **config):
+                 sample_size: int = 25, width: float = FINGER_WIDTH_3D, friction=None, friction_3d: float = 0.0, **config):
         if friction is not None:
             raise ValueError(f"SqueezeSimulator3D: {FRICTION_2D_ONLY}")
+        self.friction_3d = check_friction(friction_3d, "SqueezeSimulator3D: friction_3d")
         if getattr(diffusion, "mode", "point_3d") != 'point_3d':
             raise ValueError("SqueezeSimulator3D: the sliced squeeze is for 3-D fingers (mode 'point_3d'); SqueezeSimulator is the 2-D one")
         self.diffusion = diffusion
@@ -294,5 +308,5 @@ class SqueezeSimulator3D(_Simulator):
         n = x.shape[0]
         meshes = [self.mesh(o) for o in object_names]
         out = squeeze_map_3d(x.reshape(n, -1), meshes, start_orientations(num_rot, ori_range), sample_size=self.sample_size, width=self.width,
-                             **self.config)
-        return simulator_lists(out, SCORE_THRESHOLD[0])
+                             friction_3d=self.friction_3d, **self.config)
+        return simulator_lists(out, SCORE_THRESHOLD[0], friction_3d=self.friction_3d)

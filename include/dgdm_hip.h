@@ -1032,6 +1032,73 @@ int dgdm_squeeze_map_3d(const DgdmSqueezeConfig *cfg, const double *surfaces_dev
                         int32_t *cells_dev, double *y_dev, int32_t *flags_dev, double *table_s_dev, double *touch_l_dev,
                         double *touch_r_dev, int32_t *succ_dev, void *workspace_dev, int64_t workspace_bytes, void *stream);
 
+/* ------------------------------------------------------------------ squeeze simulator, 3-D fingers, with Coulomb friction
+ * (csrc/squeeze.hip, DESIGN.md §4.1d "3-D friction")
+ * dgdm_squeeze_map_3d with a friction coefficient between the jaws and the object, as a 3-D antipodal jamming rule on 3-D contact points
+ * and 3-D normals: the jaw's surface normal including its z slope, and the mesh triangle's own normal.  It is a different rule from
+ * dgdm_squeeze_map_friction's per-plane one, not a port of it, and like the rest of the squeeze family it is this project's own model,
+ * stated exactly here, pinned to nothing in MuJoCo and claiming nothing about it; the coefficient is untuned.
+ * tests/squeeze3d_friction_oracle.py restates it in numpy float64 and the device reproduces that bit for bit.
+ * The model.  Friction decides WHETHER a cell moves, not WHERE.  touch_l, touch_r and S are dgdm_squeeze_map_3d's, bit for bit.  A cell
+ *   whose two contacts can hold the object against any squeezing force - the line through the two contact points lies inside both
+ *   friction cones - is JAMMED, and a jammed cell is its own successor.  ASSUMPTIONS of this model, not results: two point contacts; a
+ *   free cell moves by the frictionless rule; the object still neither tilts, lifts nor slides in z, so a z component of the contact
+ *   force can only jam or not jam; the jaw's z slope is a difference over neighbouring sample rows, so it is blind between planes, as the
+ *   sliced squeeze is.  No friction with the support plane, no sliding rule under friction.
+ * Contacts.  Per cell and jaw the contact is the first candidate to attain the least gap in this visiting order, replaced on strictly
+ *   less only (a NaN gap replaces nothing): the object's segments in list order (level by level, as dgdm_squeeze_slice lists them), and
+ *   per segment P (set A), Q (set A), then the set-B abscissae i ascending.  The code of a contact is the int32
+ *       s (mu + 2) + k,    s = the segment's index within its object (its place in the list minus seg_offsets[o][0]),
+ *                          k = 0 for P, 1 for Q, 2 + i for abscissa i;   -1 = none.
+ *   The level j of segment s comes from the object's offsets.  The point c and the unnormalised normal n (from the jaw into the object)
+ *   of a contact are rebuilt from its code by the operations of dgdm_squeeze_map_3d's cell text, in its order, so P, Q, i, f, slope and
+ *   ye below are the candidate's own bits:
+ *   point   set A: (P_x, P_y, gz[j]) (Q likewise);   set B: (gx[i], ye, gz[j]).
+ *   normal  set A, the jaw's surface at (P_x, level j), i and f of set A:
+ *             hx = gx[i+1] - gx[i];  j- = max(j - 1, 0), j+ = min(j + 1, mv - 1);  hz = gz[j+] - gz[j-];
+ *             Lp- = L_{j-}[i] + f (L_{j-}[i+1] - L_{j-}[i]), Lp+ likewise on row j+, Up-, Up+ likewise;
+ *             lower: n = (-(L_j[i+1] - L_j[i]) hz,  hx hz,  -(Lp+ - Lp-) hx)
+ *             upper: n = ( (U_j[i+1] - U_j[i]) hz, -(hx hz),  (Up+ - Up-) hx)
+ *             mv = 1: hz = 1 and n_z = 0.  With the z terms zero this is the 2-D rule's (-d, h) and (d, -h).
+ *           set B, the object's face: N = the crossing triangle's normal in the object frame (dgdm_squeeze_slice_normals, below);
+ *             r = (c N_x - s N_y,  s N_x + c N_y,  N_z) with the cell's (c, s);  n = -r (all three components) if the y component has the
+ *             wrong sign - the lower jaw flips iff r_y < 0, the upper iff r_y > 0 - else n = r.  Mesh winding is therefore irrelevant; a
+ *             degenerate triangle gives n = 0 and jams nothing.
+ * Jam test, float64, every product, sum and difference rounded on its own in the order written (sums left to right), no normalisation,
+ *   no sqrt, no transcendental function (l: the lower contact, u: the upper):
+ *     d = c_u - c_l (three differences)
+ *     per jaw:  a = n_x d_x + n_y d_y + n_z d_z;   w = (n_y d_z - n_z d_y,  n_z d_x - n_x d_z,  n_x d_y - n_y d_x);
+ *               q = w_x w_x + w_y w_y + w_z w_z;      a_l = a of the lower jaw,  a_u = -(a of the upper jaw)
+ *     jam = both contacts exist && friction > 0 && S < travel_max && a_l > 0 && a_u > 0
+ *           && q_l <= (friction a_l)(friction a_l) && q_u <= (friction a_u)(friction a_u)          (any NaN: not jammed)
+ *   friction = 0 jams nothing: every output is dgdm_squeeze_map_3d's bit for bit, jam is all 0, the contacts are still reported.
+ * Motion.  A jammed cell is its own successor; everything after the jam table is dgdm_squeeze_map_friction's contract: flags 1, 2, 4 as
+ *   dgdm_squeeze_map, 8 = the start cell is jammed, 16 = the settled cell is jammed.
+ *
+ * dgdm_squeeze_slice_normals.  dgdm_squeeze_slice, which also emits normals_dev [capacity][3], in the same segment order: for the
+ *   crossing triangle (V0, V1, V2) of a segment, e = V1 - V0, g = V2 - V0 (three differences each),
+ *     N = (e_y g_z - e_z g_y,  e_z g_x - e_x g_z,  e_x g_y - e_y g_x).
+ *   The segments and offsets are dgdm_squeeze_slice's bit for bit.  normals_dev may be null only where segments_dev may (count only).
+ *
+ * dgdm_squeeze_map_3d_friction.  dgdm_squeeze_map_3d's arguments, then gz_host [mv] (HOST, the levels the meshes were sliced on),
+ *   normals_dev [n_segments][3], friction, and two optional outputs (null = not wanted), device memory: jam_dev [n_pairs][T][X] int32
+ *   (0 / 1) and contact_dev [n_pairs][T][X][2] int32 = the code of the lower and of the upper contact.  The jam table of a chunk lives in
+ *   the workspace: dgdm_squeeze_map_3d_friction_workspace_bytes(cfg, chunk_pairs, mu, mv, n_objects) (negative: bad config or sizes) is
+ *   this entry's size function; at least one pair must fit.
+ *   DGDM_EINVAL before any launch: everything dgdm_squeeze_map_3d refuses; a null gz_host; gz not strictly ascending or non-finite; null
+ *   normals_dev with n_segments > 0; a negative or non-finite friction; an object with so many segments that a code would pass
+ *   2^31 - 1 (segments (mu + 2) > 2^31 - 1).  Synchronises the stream once, at the end.                                                 */
+int dgdm_squeeze_slice_normals(const double *verts_host, const int64_t *vert_offsets_host, const int32_t *tris_host,
+                               const int64_t *tri_offsets_host, int n_objects, const double *gz_host, int mv, double *segments_dev,
+                               int64_t capacity, int32_t *seg_offsets_host, int64_t *n_segments_host, void *stream, double *normals_dev);
+int64_t dgdm_squeeze_map_3d_friction_workspace_bytes(const DgdmSqueezeConfig *cfg, int chunk_pairs, int mu, int mv, int n_objects);
+int dgdm_squeeze_map_3d_friction(const DgdmSqueezeConfig *cfg, const double *surfaces_dev, int n_fingers, const double *gx_host, int mu,
+                                 int mv, const double *segments_dev, int64_t n_segments, const int32_t *seg_offsets_host, int n_objects,
+                                 const int32_t *pairs_host, int n_pairs, const double *rot_dev, const double *starts_dev, int n_starts,
+                                 int32_t *cells_dev, double *y_dev, int32_t *flags_dev, double *table_s_dev, double *touch_l_dev,
+                                 double *touch_r_dev, int32_t *succ_dev, void *workspace_dev, int64_t workspace_bytes, void *stream,
+                                 const double *gz_host, const double *normals_dev, double friction, int32_t *jam_dev, int32_t *contact_dev);
+
 /* ------------------------------------------------------------------ squeeze-simulator labels, 3-D fingers (csrc/squeeze.hip, DESIGN.md
  * §4.1b "source: squeeze_3d")
  * dgdm_squeeze_label with dgdm_squeeze_map_3d's inputs: condition rows of 3-D fingers from the sliced squeeze.  The contract is those two

@@ -6,6 +6,9 @@ searches count 0) on every --count-stride-th orientation and set against the vec
 MI355X, which counts an FMA as 2 - this file is built without FMA contraction, so half of it is the most plain operations can reach).
   --oracle / --oracle-only   time the numpy oracle (tests/squeeze3d_oracle.py) on one pair on this host: the only baseline there is
   --tables-only              no starts (for a kernel trace: `rocprofv3 --kernel-trace --stats -- python scripts/bench_squeeze3d.py --reps 1`)
+  --friction_3d MU           also time the call with Coulomb friction (dgdm_squeeze_map_3d_friction) and report ms_friction, the share of
+                             jammed cells and of starts that settle jammed; --friction-only skips the frictionless call (for a kernel trace
+                             of the friction call alone)
 One JSON line."""
 import argparse, json, os, sys, time
 import numpy as np, torch
@@ -73,6 +76,8 @@ if __name__ == "__main__":
     ap.add_argument("--oracle", action="store_true")
     ap.add_argument("--oracle-only", action="store_true", help="no GPU: time the numpy oracle on one pair")
     ap.add_argument("--tables-only", action="store_true")
+    ap.add_argument("--friction_3d", type=float, default=None)
+    ap.add_argument("--friction-only", action="store_true")
     a = ap.parse_args()
     cfg = {k: v for k, v in engine.SQUEEZE_DEFAULTS.items() if k != "finger_half_len"}
     meshes = [vase(i) for i in range(a.objects)]
@@ -90,6 +95,21 @@ if __name__ == "__main__":
         st = None if a.tables_only else torch.as_tensor(starts).cuda()
         rot = torch.as_tensor(engine.squeeze_rotation_table(cfg["theta_cells"])).cuda()
         run = lambda: engine.squeeze_tables_3d(sf, gx, sl["segments"], sl["offsets"], pairs, st, rot=rot, **cfg)      # noqa: E731
+        if a.friction_3d is not None:
+            sn = engine.squeeze_slice(meshes, gz, normals=True)
+            fric = lambda **kw: engine.squeeze_tables_3d(sf, gx, sn["segments"], sn["offsets"], pairs, st, rot=rot, friction_3d=a.friction_3d, gz=gz,      # noqa: E731
+                                                         normals=sn["normals"], **kw, **cfg)
+            fric()
+            fms = [event_ms(fric) for _ in range(a.reps)]
+            if not a.friction_only:
+                res = fric(jam=True)
+                out.update({"jammed_cells": float(res["jam"].float().mean())})
+                if st is not None:
+                    out.update({"starts_settled_jammed": float((res["flags"] & 16).ne(0).float().mean())})
+            out.update({"friction_3d": a.friction_3d, "ms_friction": float(np.median(fms)), "ms_friction_all": [round(v, 3) for v in fms]})
+        if a.friction_only:
+            print(json.dumps(out), flush=True)
+            sys.exit(0)
         run()
         ms = [event_ms(run) for _ in range(a.reps)]
         med = float(np.median(ms))
